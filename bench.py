@@ -6,7 +6,10 @@ dimensions (nq 11, nu 8, nw 2, nc 4, nb 8), mode :configuration, H = 40, H_ref =
 fp64, B Monte-Carlo rollouts per GPU (synthetic horizons, seeded - SURVEY.md section 8d).
 `value` = rollouts * steps / wall time, inputs resident in HBM before the timed region.
 
-    python bench.py --gpus N --steps K --warmup W [--rollouts B] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--rollouts B] [--scaling weak|strong] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR writes what the last timed step
+returned (float64 .npy); --full adds every other measurement (per-class kernel times, PMC traffic, B = 1 latency legs,
+real-gait and centroidal legs, CPU baseline, the N > 1 self-check and other scaling).
 For N > 1 the driver launches one rank per GPU with torch.distributed.run.  Rank 0 builds the shared problem and
 BROADCASTS the packed linearization tables / gait / objective over RCCL, every rank solves its contiguous shard of
 the global rollout indices (no collective inside a solve), and ONE all-gather per reporting interval returns
@@ -118,6 +121,32 @@ def csrc_hash():
             hsh.update(f.encode())
             hsh.update(open(os.path.join(base, f), "rb").read())
     return hsh.hexdigest()[:16]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, s, gathered, n_global, dev, rank):
+    """--dump-outputs DIR: what the last timed step returned, as DIR/<name>.npy in float64 - the per-rollout results of the all-gather
+    (u1, newton_iters, r_norm, sweeps) and the planned trajectory core.traj (traj_q, traj_u, traj_gamma, traj_b, traj_nu), every
+    rollout in global order.  Above DUMP_LIMIT_BYTES in all, the same fixed seeded sample of rollouts is taken from every array;
+    rollout_index.npy names the rows written.  Every rank takes part (N > 1: one all-gather per trajectory array), rank 0 writes."""
+    import torch
+    from contactimplicitmpc.jl_amd.sharding import allgather_rollouts
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in gathered.items()}
+    for k, v in s.trajectory().items():
+        arrays["traj_" + k] = allgather_rollouts(torch.from_numpy(v).to(dev), n_global).cpu().numpy()
+    rows = np.arange(n_global)
+    per_row = sum(a.nbytes for a in arrays.values()) / n_global + 8
+    if per_row * n_global > DUMP_LIMIT_BYTES:
+        keep = max(1, int(DUMP_LIMIT_BYTES // per_row))
+        rows = np.sort(np.random.default_rng(0).choice(n_global, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    arrays["rollout_index"] = rows.astype(np.float64)
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        for k, a in arrays.items():
+            np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
 
 
 def measure_sweep_traffic(B, H, timeout_s=150):
@@ -705,6 +734,13 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="N-rank control flow only (broadcast, shard, all-gather of stand-in rows; no solve, no GPU needed with "
                          "CIMPC_BENCH_BACKEND=gloo): covers the launcher in the CPU test suite, measures nothing")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-class kernel times, the in-run PMC traffic passes, the N > 1 gather self-check "
+                         "and other scaling, the B = 1 legs, the perturb 0.1 and real-gait batches, the centroidal legs, the CPU baseline "
+                         "(the --no-* options switch single legs off again); without it only the timed steps are run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (u1, newton_iters, r_norm, sweeps of every rollout "
+                         "and the planned trajectory) as DIR/<name>.npy, float64, at most 64 MB in all")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -830,9 +866,12 @@ def main():
         job_sweeps, job_ip_solves, job_ip_iters, job_newton = sweeps, ip_solves, ip_iters, newton_iters
     prof = s.profile_read()
     s.profile_enable(False)
-    # per-class kernel times (informative: `kernel_time_ms_per_step`): a second, untimed pass with events around every launch
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, s, gathered, n_global, dev, rank)
+    # per-class kernel times (informative: `kernel_time_ms_per_step`, --full): a second, untimed pass with events around every launch
     prof_all, n_all = prof, args.steps
-    if not os.environ.get("CIMPC_BENCH_NOPROF"):
+    per_class = args.full and not os.environ.get("CIMPC_BENCH_NOPROF")
+    if per_class:
         s.profile_enable(1); s.profile_reset()
         n_all = max(1, min(args.steps, 3))
         for _ in range(n_all):
@@ -844,7 +883,7 @@ def main():
             dist.barrier()
 
     multi = None
-    if dist is not None:
+    if dist is not None and args.full:
         # (1) self-check of the collective path: the rows of this rank's shard in the all-gathered result must be the rank's own
         #     local result, bit for bit (the gather only moves data); the verdict of all ranks is combined with a MIN all-reduce
         u1_loc, it_loc, rn_loc = s.newton_info()
@@ -896,8 +935,8 @@ def main():
     flops_per_solve = K * alg["flop_iter"] + alg["flop_tail"]
     tflops = solves_per_launch * flops_per_solve / (avg_launch_ms * 1e-3) / 1e12 if ip_ms > 0 else 0.0
     # roofline.traffic: measured in this run (N = 1), else the committed measurement IF it belongs to these kernels
-    traffic, traffic_src = None, "skipped (--no-traffic)"
-    if not args.no_traffic and world == 1:
+    traffic, traffic_src = None, "skipped (--no-traffic)" if args.full else "not measured (only with --full)"
+    if args.full and not args.no_traffic and world == 1:
         traffic, traffic_src = measure_sweep_traffic(B, H)
     if traffic is None:
         tpath = os.path.join(ROOT, "profiles", "ip_sweep_traffic.json")
@@ -977,9 +1016,14 @@ def main():
                         "the duo kernel (two one-wave chains per system in one workgroup, rounds whose sweep has <= 20 k problems queued) and the packed kernel "
                         "(one wavefront per system, two per workgroup) - latency chains of H / 2 resp. H block steps; per-kernel averages: profiles/r06/kernel_stats.csv"),
     ]
+    if not args.full:       # the classes other than the sweep, and the schedule's launch counts, come from the second pass of --full
+        out["kernel_time_ms_per_step"] = {"ip_sweep": out["kernel_time_ms_per_step"]["ip_sweep"],
+                                          "note": "ip_sweep: HIP events of the timed region; the other classes: --full"}
+        out["schedule"] = {k: out["schedule"][k] for k in ("ip_problems_in_rounds", "ip_problems_in_async_tail")}
+        del out["roofline"]["kernels"][1:]
     if multi is not None:
         out["multi_gpu"] = multi
-    if not args.no_latency and world == 1:
+    if args.full and not args.no_latency and world == 1:
         # BASELINE configs[2]: the same quadruped problem for ONE robot, cold start
         s1, a0, a1 = make(1, rollouts[:1])
         for _ in range(3):
@@ -1021,7 +1065,7 @@ def main():
                                                        "(beside mpc_loop_b1.quadruped_h40_real_gait2 = the device-resident glue cimpc_set_gait + cimpc_mpc_advance)")
         except Exception as e:
             out["dropin_b4_host_path"] = {"error": repr(e)}
-    if world == 1 and abs(args.perturb - 0.1) > 1e-12 and not args.no_real_problem:
+    if args.full and world == 1 and abs(args.perturb - 0.1) > 1e-12 and not args.no_real_problem:
         # SURVEY.md 8(d) cfg 4 draws the initial conditions as q_ref + U(-0.1, 0.1); the headline batch uses 0.05 (rounds 1-4, kept for
         # continuity).  The contract's own spread stands beside it (outside the timed region, same kernels, same counting):
         try:
@@ -1044,14 +1088,14 @@ def main():
             s2.close()
         except Exception as e:
             out["headline"]["synthetic_perturb_0.1 (SURVEY 8d cfg 4)"] = {"error": repr(e)}
-    if not args.no_real_problem and world == 1:      # informative second workload (N = 1 only), outside the timed region
+    if args.full and not args.no_real_problem and world == 1:      # informative second workload (N = 1 only), outside the timed region
         try:
             out["real_problem"] = real_problem_leg(B, H, local_rank)
             # the better-conditioned workload stands beside the synthetic one in the headline block
             out["headline"]["real_gait2"] = {k: out["real_problem"][k] for k in ("value", "unit", "ms_per_step", "converged_rollouts", "rollouts")}
         except Exception as e:
             out["real_problem"] = {"error": repr(e)}
-    if not args.no_centroidal and world == 1:        # BASELINE configs[4]: per-GPU share of 512 rollouts, mixed-precision KKT next to fp64
+    if args.full and not args.no_centroidal and world == 1:        # BASELINE configs[4]: per-GPU share of 512 rollouts, mixed-precision KKT next to fp64
         try:
             out["centroidal_payload_h60"] = cp = centroidal_payload_leg(64, 60, local_rank)
             c64, v64 = cp["fp64_kkt"], cp["velocity_objective"]
@@ -1077,7 +1121,7 @@ def main():
             out["centroidal_payload_h60_b1"] = centroidal_b1_leg(60, local_rank)
         except Exception as e:
             out["centroidal_payload_h60_b1"] = {"error": repr(e)}
-    if not args.no_cpu_baseline and world == 1:      # the CPU baseline is a rank-0, N = 1 measurement
+    if args.full and not args.no_cpu_baseline and world == 1:      # the CPU baseline is a rank-0, N = 1 measurement
         try:
             from contactimplicitmpc.jl_amd.trajectory import Objective
             cb = cpu_baseline(d, prob, Objective(q=obj_q, u=obj_u), rollouts, H, H_ref)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of two builds of the library on ONE box, alternating runs: scripts/ab.sh <libA> <libB> [rounds] [extra bench args]
 A=$1; B=$2; N=${3:-3}; shift 3
-ARGS="--steps 10 --warmup 2 --no-cpu-baseline --no-real-problem --no-latency --no-traffic --no-centroidal $@"
+ARGS="--full --steps 10 --warmup 2 --no-cpu-baseline --no-real-problem --no-latency --no-traffic --no-centroidal $@"
 for i in $(seq $N); do
   for L in $A $B; do
     CIMPC_LIB=$PWD/$L python bench.py $ARGS 2>/dev/null | python -c "

@@ -3,7 +3,7 @@
 A=$1; B=$2; N=${3:-2}
 for i in $(seq $N); do
   for L in $A $B; do
-    CIMPC_LIB=$PWD/$L python bench.py --steps 3 --warmup 1 --rollouts 64 --no-cpu-baseline --no-real-problem --no-traffic --no-centroidal 2>/dev/null | python -c "
+    CIMPC_LIB=$PWD/$L python bench.py --full --steps 3 --warmup 1 --rollouts 64 --no-cpu-baseline --no-real-problem --no-traffic --no-centroidal 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 m=d['mpc_loop_b1']

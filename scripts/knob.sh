@@ -1,6 +1,6 @@
 #!/bin/bash
 # knob sweep on ONE box: scripts/knob.sh "<ENV=V ...>" ... (each argument = one environment setting, "" = defaults)
-ARGS="--steps 10 --warmup 2 --no-cpu-baseline --no-real-problem --no-latency --no-traffic --no-centroidal ${BENCH_ARGS}"
+ARGS="--full --steps 10 --warmup 2 --no-cpu-baseline --no-real-problem --no-latency --no-traffic --no-centroidal ${BENCH_ARGS}"
 for E in "$@"; do
   env $E python bench.py $ARGS 2>/dev/null | python -c "
 import json,sys

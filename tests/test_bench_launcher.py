@@ -64,10 +64,12 @@ def test_refuses_a_world_that_is_not_gpus():
 
 
 @pytest.mark.gpu
-def test_bare_gpus_2_bench_line_on_one_gpu_box():
+def test_bare_gpus_2_bench_line_on_one_gpu_box(tmp_path):
     """The real thing minus the second GPU: `python bench.py --gpus 2` with no launcher and no WORLD_SIZE, two ranks on the one
-    device, a real sharded solve per rank, the all-gather self-check and both scalings on the line."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1", "--warmup", "1", "--rollouts", "32"],
+    device, a real sharded solve per rank, the all-gather self-check and both scalings on the line (both --full only), and the
+    dumped outputs of both shards in global order."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1", "--warmup", "1", "--rollouts", "32", "--full",
+                        "--dump-outputs", str(tmp_path)],
                        env=_env(CIMPC_BENCH_BACKEND="gloo"), capture_output=True, text=True, timeout=900, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-3000:]
     o = _json_line(r.stdout)
@@ -76,3 +78,8 @@ def test_bare_gpus_2_bench_line_on_one_gpu_box():
     assert o["scaling"] == "weak" and o["multi_gpu"]["other_scaling"]["scaling"] == "strong"
     assert o["multi_gpu"]["other_scaling"]["rollouts_total"] == 32 and o["multi_gpu"]["other_scaling"]["value"] > 0
     assert o["value"] > 0 and o["roofline"]["bound"] == "fp64_valu"
+    import numpy as np
+    u1, traj_u = np.load(str(tmp_path / "u1.npy")), np.load(str(tmp_path / "traj_u.npy"))
+    assert u1.shape == (64, 8) and traj_u.shape == (64, 40, 8)
+    np.testing.assert_array_equal(u1, traj_u[:, 0])                  # rank 1's trajectories land in rank 1's rows
+    np.testing.assert_array_equal(np.load(str(tmp_path / "rollout_index.npy")), np.arange(64))

@@ -2,6 +2,7 @@
 module names a function `include/cimpc.h` declares, with the same number of arguments and C-compatible argument / return
 types (Ptr{Cdouble} <-> double*, Cint <-> int, Ref{Dims} <-> const cimpc_dims*, ...), and that the Julia mirrors of the
 option structs list the header's fields in the header's order."""
+import json
 import os
 import re
 
@@ -197,23 +198,16 @@ NEWTON_SOLVE_ARGS = [("core", "Newton"), ("s", "Simulation{T}"), ("q0", "Vector{
 
 
 def test_reference_declarations_are_what_the_binding_was_written_against():
-    """Only where the reference tree is present (this container; not the GPU box): newton.jl still declares Newton with these
-    fifteen type parameters, `solver::LS` as a field, and newton_solve! with these seven positional arguments + warm_start."""
-    ref = "/root/reference/src/controller/newton.jl"
-    if not os.path.exists(ref):
-        import pytest
-        pytest.skip("reference tree not present")
-    src = open(ref).read()
-    m = re.search(r"mutable struct Newton\{([^}]*)\}", src)
-    assert [x.strip() for x in m.group(1).split(",")] == NEWTON_PARAMS
-    assert re.search(r"^\s*solver::LS\s*$", src, flags=re.M)
-    assert re.search(r"solver = eval\(opts\.solver\)\(jac\.R\)", src)
-    sig = src[src.index("function newton_solve!("):]
-    sig = sig[:sig.index("where T")]
-    names = re.findall(r"^\s*(\w+)::", sig, flags=re.M)
-    assert names == [a for a, _ in NEWTON_SOLVE_ARGS] + ["warm_start"]
-    pol = open("/root/reference/src/controller/policy.jl").read()
-    assert re.search(r"newton_solve!\(p\.newton, p\.s, p\.q0, q1,\s*p\.window, p\.im_traj, p\.traj, warm_start = t > 1\)", pol)
+    """newton.jl declares Newton with these fifteen type parameters, `solver::LS` as a field, and newton_solve! with these seven
+    positional arguments + warm_start; policy.jl calls it with the warm-start keyword.  Read from the committed fixture
+    tests/golden/reference_declarations.json, extracted from the reference's newton.jl / policy.jl by
+    tests/golden/make_reference_declarations.py."""
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_declarations.json")))
+    assert rec["newton_type_parameters"] == NEWTON_PARAMS
+    assert rec["solver_field_is_LS"] is True
+    assert rec["solver_built_by_eval_opts_solver"] is True
+    assert rec["newton_solve_argument_names"] == [a for a, _ in NEWTON_SOLVE_ARGS] + ["warm_start"]
+    assert rec["policy_calls_newton_solve_with_warm_start"] is True
 
 
 def test_b4_is_a_drop_in_under_the_unchanged_policy():
