@@ -49,6 +49,14 @@ class Profile(C.Structure):
                 ("async_ms", C.c_double), ("async_launches", C.c_longlong), ("async_problems", C.c_longlong)]
 
 
+MAX_TERRAIN_PIECES = 8      # CIMPC_TERRAIN_MAX_PIECES
+
+
+class Terrain(C.Structure):
+    _fields_ = [("kind", C.c_int), ("n_pieces", C.c_int), ("p", C.c_double * 4), ("brk", C.c_double * MAX_TERRAIN_PIECES),
+                ("off", C.c_double * MAX_TERRAIN_PIECES), ("coef", (C.c_double * 4) * MAX_TERRAIN_PIECES)]
+
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _h = C.c_void_p
@@ -83,6 +91,8 @@ SIGNATURES = {
     "cimpc_set_gait": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "cimpc_plant_step": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.POINTER(IpOpts),
                                    _dp, _dp, _dp, _ip, _ip]),
+    "cimpc_plant_step_terrain": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, _dp, C.c_double, C.c_double,
+                                           C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip]),
     "cimpc_get_reference": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "cimpc_get_stats": (C.c_int, [_h, C.POINTER(Stats)]),
     "cimpc_get_newton_log": (C.c_int, [_h, _dp, C.c_int]),

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 
 #include <cmath>
 
@@ -45,14 +46,34 @@ __device__ __forceinline__ double wave_sum(double v) {
 
 }  // namespace
 
+// TERRAIN = false: flat ground (cimpc_plant_step).  TERRAIN = true: robot rb stands on terrain[n_terrain == 1 ? 0 : rb]; a flat
+// robot still evaluates plant_residual, so its step is the TERRAIN = false one (a uniform branch per robot).
+template <bool TERRAIN>
 __global__ __launch_bounds__(64) void plant_step_kernel(PlantModel M, PlantOpts o, int B, const double* q0, const double* q1,
                                                         const double* u, const double* w, double mu, double h, double* q2,
-                                                        double* gamma, double* bb, int* status, int* iters) {
+                                                        double* gamma, double* bb, int* status, int* iters,
+                                                        const cimpc_terrain* terrain, int n_terrain) {
     __shared__ double A[NZM * LDA];
     __shared__ double zs[NZM], rs[NZM], ds[NZM], xs[NZM], ths[2 * PLANT_MAX_Q + PLANT_MAX_U + PLANT_NW + 2];
     __shared__ int piv[NZM];
+    __shared__ cimpc_terrain ter;
     const int rb = blockIdx.x, lane = threadIdx.x;
     if (rb >= B) return;
+    bool rough = false;
+    if constexpr (TERRAIN) {
+        static_assert(sizeof(cimpc_terrain) % sizeof(double) == 0 && sizeof(cimpc_terrain) / sizeof(double) <= 64, "one word per lane");
+        const double* src = reinterpret_cast<const double*>(terrain + (n_terrain == 1 ? 0 : rb));
+        if (lane < (int)(sizeof(cimpc_terrain) / sizeof(double))) reinterpret_cast<double*>(&ter)[lane] = src[lane];
+        wsync();
+        rough = ter.kind != CIMPC_TERRAIN_FLAT || M.kind == PLANT_KIND_PARTICLE_2D;
+    }
+    auto residual = [&](const auto* zz, double kappa, auto* rr) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(zz)>>;
+        if constexpr (TERRAIN) {
+            if (rough) { plant_residual_terrain<T>(M, ter, zz, ths, kappa, rr); return; }
+        }
+        plant_residual<T>(M, zz, ths, kappa, rr);
+    };
     const int nq = M.nq, nu = M.nu, nz = M.nz(), ny = 2 * M.nc + M.nb(), nxy = nq + ny;
     // θ = [q0; q1; u1; w1; μ; h], z = (q1, 1, ..., 1)
     for (int i = lane; i < M.nth(); i += 64) {
@@ -71,7 +92,7 @@ __global__ __launch_bounds__(64) void plant_step_kernel(PlantModel M, PlantOpts 
     auto eval_r = [&](double kappa, double* out) {
         double zl[NZM], rl[NZM];
         for (int i = 0; i < nz; ++i) zl[i] = zs[i];
-        plant_residual<double>(M, zl, ths, kappa, rl);
+        residual(zl, kappa, rl);
         if (lane == 0) for (int i = 0; i < nz; ++i) out[i] = rl[i];
         wsync();
     };
@@ -91,7 +112,7 @@ __global__ __launch_bounds__(64) void plant_step_kernel(PlantModel M, PlantOpts 
         for (int col = lane; col < nz; col += 64) {
             Dual zl[NZM], rl[NZM];
             for (int i = 0; i < nz; ++i) zl[i] = {zs[i], i == col ? 1.0 : 0.0};
-            plant_residual<Dual>(M, zl, ths, 0.0, rl);
+            residual(zl, 0.0, rl);
             for (int i = 0; i < nz; ++i) A[i * LDA + col] = rl[i].d;
         }
         wsync();
@@ -202,7 +223,8 @@ struct PlantWs {
     hipStream_t st = nullptr;
     double *d_in = nullptr, *d_out = nullptr;
     int* d_st = nullptr;
-    size_t cap_in = 0, cap_out = 0, cap_st = 0;
+    cimpc_terrain* d_ter = nullptr;
+    size_t cap_in = 0, cap_out = 0, cap_st = 0, cap_ter = 0;
 };
 constexpr int PLANT_MAX_DEVICES = 16;
 PlantWs g_plant_ws[PLANT_MAX_DEVICES];
@@ -219,14 +241,29 @@ bool plant_grow(T** p, size_t* cap, size_t need) {
 }
 }  // namespace
 
-extern "C" int cimpc_plant_step(int model, int B, const double* q0, const double* q1, const double* u, const double* w,
-                                double mu, double h, const cimpc_ip_opts* opts, double* q2, double* gamma, double* b,
-                                int* status, int* iters) {
+namespace {
+// Both entry points: validate, pick the model, stage inputs on the device's private stream, launch, read back.  terrain = nullptr
+// (or every terrain flat on a model cimpc_plant_step has) runs plant_step_kernel<false>, the flat step.
+int plant_step_impl(int model, int B, int n_terrain, const cimpc_terrain* terrain, const double* q0, const double* q1,
+                    const double* u, const double* w, double mu, double h, const cimpc_ip_opts* opts, double* q2, double* gamma,
+                    double* b, int* status, int* iters) {
     using namespace cimpc;
     if (B <= 0 || !q0 || !q1 || !u || !opts || !q2 || !gamma || !b || !status || !iters || h <= 0.0) return CIMPC_ERR_INVALID;
-    if (model < CIMPC_PLANT_QUADRUPED || model > CIMPC_PLANT_PARTICLE) return CIMPC_ERR_INVALID;
+    if (model < CIMPC_PLANT_QUADRUPED || model > (terrain ? CIMPC_PLANT_PARTICLE_2D : CIMPC_PLANT_PARTICLE)) return CIMPC_ERR_INVALID;
     if (opts->max_iter <= 0 || opts->max_ls < 0 || !(opts->r_tol > 0.0) || !(opts->kappa_tol > 0.0) || !(opts->ls_scale > 0.0 && opts->ls_scale < 1.0))
         return CIMPC_ERR_INVALID;
+    const PlantModel M = model == CIMPC_PLANT_QUADRUPED ? plant_quadruped() : model == CIMPC_PLANT_FLAMINGO ? plant_flamingo()
+                         : model == CIMPC_PLANT_HOPPER_2D ? plant_hopper_2d() : model == CIMPC_PLANT_PARTICLE ? plant_particle()
+                         : model == CIMPC_PLANT_PARTICLE_2D ? plant_particle_2d()
+                         : plant_centroidal(model == CIMPC_PLANT_CENTROIDAL);
+    bool rough = model == CIMPC_PLANT_PARTICLE_2D;
+    if (terrain) {
+        if (n_terrain != 1 && n_terrain != B) return CIMPC_ERR_INVALID;
+        for (int i = 0; i < n_terrain; ++i) {
+            if (!terrain_valid_for(M, terrain[i])) return CIMPC_ERR_INVALID;
+            rough = rough || terrain[i].kind != CIMPC_TERRAIN_FLAT;
+        }
+    }
     // runs on the calling thread's CURRENT device (the caller selects it, e.g. hipSetDevice(rank) / torch.cuda.set_device)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PLANT_MAX_DEVICES) return CIMPC_ERR_NO_DEVICE;
@@ -234,9 +271,6 @@ extern "C" int cimpc_plant_step(int model, int B, const double* q0, const double
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, dev) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return CIMPC_ERR_NO_DEVICE;
     }
-    const PlantModel M = model == CIMPC_PLANT_QUADRUPED ? plant_quadruped() : model == CIMPC_PLANT_FLAMINGO ? plant_flamingo()
-                         : model == CIMPC_PLANT_HOPPER_2D ? plant_hopper_2d() : model == CIMPC_PLANT_PARTICLE ? plant_particle()
-                         : plant_centroidal(model == CIMPC_PLANT_CENTROIDAL);
     const size_t pnc = (size_t)M.nc, pnb = (size_t)M.nb();
     PlantOpts o{opts->r_tol, opts->kappa_tol, std::isinf(opts->undercut) ? 0.0 : opts->kappa_tol / opts->undercut, opts->eps_min,
                 opts->ls_scale, opts->stall_alpha, opts->max_iter, opts->max_ls};
@@ -250,6 +284,7 @@ extern "C" int cimpc_plant_step(int model, int B, const double* q0, const double
     }
     if (!plant_grow(&W.d_in, &W.cap_in, n_in) || !plant_grow(&W.d_out, &W.cap_out, n_out) || !plant_grow(&W.d_st, &W.cap_st, 2 * (size_t)B))
         return CIMPC_ERR_HIP;
+    if (rough && !plant_grow(&W.d_ter, &W.cap_ter, (size_t)n_terrain)) return CIMPC_ERR_HIP;
     double* dq0 = W.d_in; double* dq1 = dq0 + B * nq; double* du = dq1 + B * nq; double* dw = du + B * nu;
     double* dq2 = W.d_out; double* dg = dq2 + B * nq; double* db = dg + (size_t)B * pnc;
     int* d_st = W.d_st;
@@ -258,9 +293,14 @@ extern "C" int cimpc_plant_step(int model, int B, const double* q0, const double
               hipMemcpyAsync(dq1, q1, B * nq * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
               hipMemcpyAsync(du, u, B * nu * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
     if (ok && w) ok = hipMemcpyAsync(dw, w, (size_t)B * M.nw * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok && rough) ok = hipMemcpyAsync(W.d_ter, terrain, (size_t)n_terrain * sizeof(cimpc_terrain), hipMemcpyHostToDevice, st) == hipSuccess;
     if (ok) {
-        hipLaunchKernelGGL(plant_step_kernel, dim3(B), dim3(64), 0, st, M, o, B, dq0, dq1, du, w ? dw : nullptr, mu, h, dq2, dg, db,
-                           d_st, d_st + B);
+        if (rough)
+            hipLaunchKernelGGL(plant_step_kernel<true>, dim3(B), dim3(64), 0, st, M, o, B, dq0, dq1, du, w ? dw : nullptr, mu, h, dq2, dg, db,
+                               d_st, d_st + B, W.d_ter, n_terrain);
+        else
+            hipLaunchKernelGGL(plant_step_kernel<false>, dim3(B), dim3(64), 0, st, M, o, B, dq0, dq1, du, w ? dw : nullptr, mu, h, dq2, dg, db,
+                               d_st, d_st + B, (const cimpc_terrain*)nullptr, 0);
         ok = hipGetLastError() == hipSuccess;
     }
     if (ok) ok = hipMemcpyAsync(q2, dq2, B * nq * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
@@ -270,4 +310,18 @@ extern "C" int cimpc_plant_step(int model, int B, const double* q0, const double
                  hipMemcpyAsync(iters, d_st + B, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
     return ok ? CIMPC_OK : CIMPC_ERR_HIP;
+}
+}  // namespace
+
+extern "C" int cimpc_plant_step(int model, int B, const double* q0, const double* q1, const double* u, const double* w,
+                                double mu, double h, const cimpc_ip_opts* opts, double* q2, double* gamma, double* b,
+                                int* status, int* iters) {
+    return plant_step_impl(model, B, 0, nullptr, q0, q1, u, w, mu, h, opts, q2, gamma, b, status, iters);
+}
+
+extern "C" int cimpc_plant_step_terrain(int model, int B, int n_terrain, const cimpc_terrain* terrain, const double* q0,
+                                        const double* q1, const double* u, const double* w, double mu, double h,
+                                        const cimpc_ip_opts* opts, double* q2, double* gamma, double* b, int* status, int* iters) {
+    if (!terrain) return CIMPC_ERR_INVALID;
+    return plant_step_impl(model, B, n_terrain, terrain, q0, q1, u, w, mu, h, opts, q2, gamma, b, status, iters);
 }

@@ -1,7 +1,8 @@
 // Plant-side residual of the reference's planar-chain models (quadruped, flamingo) for the batched simulator step
 // (SURVEY.md section 8f-4).  Host- and device-compilable.
 //
-//   residual            src/simulation/simulation.jl:133-158     (LinearizedCone, flat ground: surface rotation = identity)
+//   residual            src/simulation/simulation.jl:133-158     (LinearizedCone; plant_residual: flat ground, surface rotation =
+//                                                                 identity; plant_residual_terrain: any cimpc_terrain)
 //   dynamics            src/dynamics/model.jl:11-36              (variational midpoint integrator)
 //   quadruped           src/dynamics/quadruped/model.jl:75-590   flamingo  src/dynamics/flamingo/model.jl:62-503
 //
@@ -13,6 +14,8 @@
 // numbers (one tangent direction per lane in the kernel): exact derivatives.
 #pragma once
 #include <cmath>
+
+#include "../../../include/cimpc.h"
 
 #if defined(__HIPCC__)
 #define PLANT_HD __host__ __device__ __forceinline__
@@ -40,13 +43,23 @@ PLANT_HD double psin(double a) { return sin(a); }
 PLANT_HD double pcos(double a) { return cos(a); }
 PLANT_HD double pval(double a) { return a; }
 PLANT_HD double pval(Dual a) { return a.v; }
+PLANT_HD Dual operator/(Dual a, Dual b) { return {a.v / b.v, (a.d * b.v - a.v * b.d) / (b.v * b.v)}; }
+PLANT_HD Dual operator/(double a, Dual b) { return {a / b.v, -a * b.d / (b.v * b.v)}; }
+PLANT_HD Dual operator+(double a, Dual b) { return {a + b.v, b.d}; }
+PLANT_HD Dual operator-(double a, Dual b) { return {a - b.v, -b.d}; }
+PLANT_HD Dual psqrt(Dual a) { const double r = sqrt(a.v); return {r, a.d / (2.0 * r)}; }
+PLANT_HD Dual pexp(Dual a) { const double e = exp(a.v); return {e, a.d * e}; }
+PLANT_HD Dual plog1p(Dual a) { return {log1p(a.v), a.d / (1.0 + a.v)}; }
+PLANT_HD double psqrt(double a) { return sqrt(a); }
+PLANT_HD double pexp(double a) { return exp(a); }
+PLANT_HD double plog1p(double a) { return log1p(a); }
 template <class T> PLANT_HD T pconst(double a);
 template <> PLANT_HD double pconst<double>(double a) { return a; }
 template <> PLANT_HD Dual pconst<Dual>(double a) { return {a, 0.0}; }
 
 constexpr int PLANT_MAX_Q = 18, PLANT_MAX_U = 12, PLANT_MAX_BODIES = 9, PLANT_MAX_SEG = 3;
 constexpr int PLANT_NC = 4, PLANT_NB = 16, PLANT_NW = 3;     // maxima: four contacts, two (flat_2D_lc) or four (flat_3D_lc) friction directions each
-constexpr int PLANT_KIND_CHAIN = 0, PLANT_KIND_HOPPER_2D = 1, PLANT_KIND_CENTROIDAL = 2, PLANT_KIND_PARTICLE = 3;
+constexpr int PLANT_KIND_CHAIN = 0, PLANT_KIND_HOPPER_2D = 1, PLANT_KIND_CENTROIDAL = 2, PLANT_KIND_PARTICLE = 3, PLANT_KIND_PARTICLE_2D = 4;
 
 struct PlantChain { int n; double r[PLANT_MAX_SEG]; int k[PLANT_MAX_SEG]; };
 struct PlantModel {
@@ -262,6 +275,236 @@ PLANT_HD void plant_residual(const PlantModel& M, const T* z, const double* th, 
     for (int i = 0; i < nq; ++i) r[i] = dyn[i];
 }
 
+// ---- terrain (src/simulator/environment.jl, src/simulation/environments/*.jl) ----------------
+// surf(x[, y]) and its gradient on T = double | Dual, so the dual-number Jacobian carries d(surface)/dq and d(rotation)/dq.
+// Branches (piece of a PIECEWISE table, sign in the softplus) are taken on the value, like the reference's IfElse.
+template <class T>
+PLANT_HD void terrain_eval(const cimpc_terrain& E, T x, T y, T& s, T& gx, T& gy) {
+    const double* p = E.p;
+    gy = pconst<T>(0.0);
+    switch (E.kind) {
+    case CIMPC_TERRAIN_PIECEWISE: {
+        int i = 0;
+        for (int k = 1; k < E.n_pieces; ++k) if (pval(x) >= E.brk[k]) i = k;
+        const double* a = E.coef[i];
+        const T t = x - E.off[i];
+        s = ((a[3] * t + a[2]) * t + a[1]) * t + a[0];
+        gx = (3.0 * a[3] * t + 2.0 * a[2]) * t + a[1];
+        return;
+    }
+    case CIMPC_TERRAIN_SOFTPLUS: {          // (m / t) log(1 + e^u), u = t (x - x0); gradient m e^u / (1 + e^u)
+        const T u = p[1] * (x - p[2]);
+        if (pval(u) > 0.0) {
+            const T e = pexp(-u);
+            s = (p[0] / p[1]) * (u + plog1p(e));
+            gx = p[0] / (1.0 + e);
+        } else {
+            const T e = pexp(u);
+            s = (p[0] / p[1]) * plog1p(e);
+            gx = (p[0] * e) / (1.0 + e);
+        }
+        return;
+    }
+    case CIMPC_TERRAIN_SINE: {
+        const T c = pcos(p[2] * x), sn = psin(p[2] * x);
+        s = (p[0] * c + p[1] * sn) + p[3];
+        gx = p[2] * (p[1] * c - p[0] * sn);
+        return;
+    }
+    case CIMPC_TERRAIN_SINE_SUM_3D:
+        s = p[0] * psin(p[1] * x) + p[2] * psin(p[3] * y);
+        gx = (p[0] * p[1]) * pcos(p[1] * x);
+        gy = (p[2] * p[3]) * pcos(p[3] * y);
+        return;
+    case CIMPC_TERRAIN_SINE_PRODUCT_3D: {
+        const T sx = psin(p[1] * x), sy = psin(p[1] * y);
+        s = p[0] * (sx * sy);
+        gx = (p[0] * p[1]) * (pcos(p[1] * x) * sy);
+        gy = (p[0] * p[1]) * (sx * pcos(p[1] * y));
+        return;
+    }
+    case CIMPC_TERRAIN_BOWL_3D:
+        s = p[0] * (x * x + y * y);
+        gx = (2.0 * p[0]) * x;
+        gy = (2.0 * p[0]) * y;
+        return;
+    default:
+        s = pconst<T>(0.0); gx = pconst<T>(0.0);
+        return;
+    }
+}
+PLANT_HD bool terrain_is_3d(int kind) {
+    return kind == CIMPC_TERRAIN_SINE_SUM_3D || kind == CIMPC_TERRAIN_SINE_PRODUCT_3D || kind == CIMPC_TERRAIN_BOWL_3D;
+}
+
+// 2-D contact frame: rotation(env, x) of environment.jl:79-92 in closed form (no atan): the angle between the world normal and
+// n = (-g, 1) / sqrt(1 + g^2) is -atan(g), so R = [c -s; s c] with c = 1 / sqrt(1 + g^2), s = -g c.  The foot's world force is
+// R^T [lt; γ], its tangential velocity the first entry of R v.
+template <class T>
+PLANT_HD void terrain_frame_2d(const cimpc_terrain& E, T px, T& surf, T& c, T& s) {
+    T gx, gy;
+    terrain_eval(E, px, pconst<T>(0.0), surf, gx, gy);
+    c = 1.0 / psqrt(1.0 + gx * gx);
+    s = -(gx * c);
+}
+
+// particle_2D (src/dynamics/particle_2D/model.jl): q = (x, z), M = m I, C = (0, m g), B = A = J = I, one contact (the particle)
+// with two friction directions.  mass[0] = m.  Also its flat case: the model has no cimpc_plant_step path.
+template <class T>
+PLANT_HD void plant_residual_particle_2d(const PlantModel& M, const cimpc_terrain& E, const T* z, const double* th, double kappa, T* r) {
+    const double* q0 = th; const double* q1 = th + 2; const double* u1 = th + 4; const double* w1 = th + 6;
+    const double mu = th[8], h = th[9], m = M.mass[0];
+    const T* q2 = z; const T* gam = z + 2; const T* b = z + 3; const T* psi = z + 5; const T* s1 = z + 6; const T* eta = z + 7; const T* s2 = z + 9;
+    T surf, c, s;
+    terrain_frame_2d(E, q2[0], surf, c, s);
+    const T lt = b[0] - b[1];
+    const T lam[2] = {c * lt + s * gam[0], c * gam[0] - s * lt};
+    T vm2[2];
+    for (int i = 0; i < 2; ++i) vm2[i] = (q2[i] - q1[i]) / h;
+    for (int i = 0; i < 2; ++i) {
+        const double grav = i == 1 ? -m * M.g : 0.0;
+        r[i] = pconst<T>(0.5 * h * grav + m * ((q1[i] - q0[i]) / h) + 0.5 * h * grav + u1[i] + w1[i]) - m * vm2[i] + lam[i];
+    }
+    const T vt = c * vm2[0] - s * vm2[1];
+    r[2] = s1[0] - (q2[1] - surf);
+    r[3] = eta[0] - vt - psi[0]; r[4] = eta[1] + vt - psi[0];
+    r[5] = s2[0] - (mu * gam[0] - (b[0] + b[1]));
+    r[6] = gam[0] * s1[0] - kappa;
+    for (int k = 0; k < 2; ++k) r[7 + k] = b[k] * eta[k] - kappa;
+    r[9] = psi[0] * s2[0] - kappa;
+}
+
+// particle on a 3-D surface (particle/model.jl:58-109): R = rot(n_s, e_z) = I + [v]x + [v]x^2 / (1 + c), v = n_s x e_z = (n_y, -n_x, 0),
+// c = n_z (environment.jl:58-77), written out; force R^T [m b; γ], tangential velocity (R v)[1:2].
+template <class T>
+PLANT_HD void plant_residual_particle_terrain(const PlantModel& M, const cimpc_terrain& E, const T* z, const double* th, double kappa, T* r) {
+    const double* q0 = th; const double* q1 = th + 3; const double* u1 = th + 6; const double* w1 = th + 9;
+    const double mu = th[12], h = th[13], m = M.mass[0];
+    const T* q2 = z; const T* gam = z + 3; const T* b = z + 4; const T* psi = z + 8; const T* s1 = z + 9; const T* eta = z + 10; const T* s2 = z + 14;
+    T surf, gx, gy;
+    terrain_eval(E, q2[0], q2[1], surf, gx, gy);
+    const T inv = 1.0 / psqrt(1.0 + gx * gx + gy * gy);
+    const T nx = -(gx * inv), ny = -(gy * inv), nz = inv;
+    const T vx = ny, vy = -nx, k = 1.0 / (1.0 + nz);
+    T R[3][3];
+    R[0][0] = 1.0 - k * (vy * vy); R[0][1] = k * (vx * vy);       R[0][2] = vy;
+    R[1][0] = k * (vx * vy);       R[1][1] = 1.0 - k * (vx * vx); R[1][2] = -vx;
+    R[2][0] = -vy;                 R[2][1] = vx;                  R[2][2] = 1.0 - k * (vx * vx + vy * vy);
+    const T fl[3] = {b[0] - b[2], b[1] - b[3], gam[0]};
+    T vm2[3];
+    for (int i = 0; i < 3; ++i) vm2[i] = (q2[i] - q1[i]) / h;
+    for (int i = 0; i < 3; ++i) {
+        const double grav = i == 2 ? -m * M.g : 0.0;
+        const T lam = R[0][i] * fl[0] + R[1][i] * fl[1] + R[2][i] * fl[2];
+        r[i] = pconst<T>(0.5 * h * grav + m * ((q1[i] - q0[i]) / h) + 0.5 * h * grav + u1[i] + w1[i]) - m * vm2[i] + lam;
+    }
+    const T v0 = R[0][0] * vm2[0] + R[0][1] * vm2[1] + R[0][2] * vm2[2];
+    const T v1 = R[1][0] * vm2[0] + R[1][1] * vm2[1] + R[1][2] * vm2[2];
+    r[3] = s1[0] - (q2[2] - surf);
+    r[4] = eta[0] - v0 - psi[0]; r[5] = eta[1] - v1 - psi[0];
+    r[6] = eta[2] + v0 - psi[0]; r[7] = eta[3] + v1 - psi[0];
+    r[8] = s2[0] - (mu * gam[0] - (b[0] + b[1] + b[2] + b[3]));
+    r[9] = gam[0] * s1[0] - kappa;
+    for (int q = 0; q < 4; ++q) r[10 + q] = b[q] * eta[q] - kappa;
+    r[14] = psi[0] * s2[0] - kappa;
+}
+
+// r(z, θ, κ) on terrain E: plant_residual with, per contact i at foot p_i, ϕ_i = p_z - surf(p_x), the world force R_i^T [m b_i; γ_i]
+// through both Jacobian rows of the foot and the tangential velocity (R_i J_i (q2 - q1) / h)[1] (simulation.jl:133-158,
+// contact_methods.jl, quadruped/model.jl:472-492, hopper_2D/model.jl:54-85).  Each contact's rotation is taken at its own foot.
+// Planar chains, hopper_2D, particle_2D and (3-D kinds) particle; centroidal_quadruped is refused by the caller.
+template <class T>
+PLANT_HD void plant_residual_terrain(const PlantModel& M, const cimpc_terrain& E, const T* z, const double* th, double kappa, T* r) {
+    if (M.kind == PLANT_KIND_PARTICLE) { plant_residual_particle_terrain<T>(M, E, z, th, kappa, r); return; }
+    if (M.kind == PLANT_KIND_PARTICLE_2D) { plant_residual_particle_2d<T>(M, E, z, th, kappa, r); return; }
+    const int nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb();
+    const double* q0 = th; const double* q1 = th + nq; const double* u1 = th + 2 * nq; const double* w1 = u1 + nu;
+    const double mu = w1[M.nw], h = w1[M.nw + 1];
+    const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc; const T* psi = b + nb; const T* s1 = psi + nc;
+    const T* eta = s1 + nc; const T* s2 = eta + nb;
+    T qm1[PLANT_MAX_Q], vm1[PLANT_MAX_Q], qm2[PLANT_MAX_Q], vm2[PLANT_MAX_Q];
+    for (int i = 0; i < nq; ++i) {
+        qm1[i] = pconst<T>(0.5 * (q0[i] + q1[i])); vm1[i] = pconst<T>((q1[i] - q0[i]) / h);
+        qm2[i] = (q2[i] + q1[i]) * 0.5; vm2[i] = (q2[i] - q1[i]) / h;
+    }
+    T a1[PLANT_MAX_Q], b1[PLANT_MAX_Q], a2[PLANT_MAX_Q], b2[PLANT_MAX_Q];
+    plant_lagrangian_derivatives(M, qm1, vm1, a1, b1);
+    plant_lagrangian_derivatives(M, qm2, vm2, a2, b2);
+    T dyn[PLANT_MAX_Q];
+    for (int i = 0; i < nq; ++i)
+        dyn[i] = (0.5 * h) * a1[i] + b1[i] + (0.5 * h) * a2[i] - b2[i] - (h * M.joint_friction[i]) * vm2[i];
+    if (M.kind == PLANT_KIND_HOPPER_2D) {
+        const T st = psin(qm2[2]), ct = pcos(qm2[2]);
+        dyn[2] = dyn[2] + u1[0];
+        dyn[0] = dyn[0] - u1[1] * st; dyn[1] = dyn[1] + u1[1] * ct; dyn[3] = dyn[3] + u1[1];
+    } else {
+        for (int i = 0; i < nu; ++i) { dyn[M.tq_a[i]] = dyn[M.tq_a[i]] - u1[i]; dyn[M.tq_b[i]] = dyn[M.tq_b[i]] + u1[i]; }
+    }
+    for (int i = 0; i < M.nw; ++i) dyn[i] = dyn[i] + w1[i];
+    T s[PLANT_MAX_Q], c[PLANT_MAX_Q];
+    for (int i = 0; i < nq; ++i) { s[i] = psin(q2[i]); c[i] = pcos(q2[i]); }
+    for (int f = 0; f < nc; ++f) {
+        const PlantChain& ch = M.foot[f];
+        T px = q2[0], pz = q2[1];
+        T vx = (q2[0] - q1[0]) / h, vz = (q2[1] - q1[1]) / h;        // foot velocity J (q2 - q1) / h
+        if (M.kind == PLANT_KIND_HOPPER_2D) {
+            const T rl = q2[3];
+            px = px + rl * s[2];
+            pz = pz - rl * c[2];
+            vx = vx + rl * (c[2] * ((q2[2] - q1[2]) / h)) + s[2] * ((q2[3] - q1[3]) / h);
+            vz = vz + rl * (s[2] * ((q2[2] - q1[2]) / h)) - c[2] * ((q2[3] - q1[3]) / h);
+        }
+        for (int e = 0; e < (M.kind == PLANT_KIND_HOPPER_2D ? 0 : ch.n); ++e) {
+            const int k = ch.k[e]; const double rr = ch.r[e];
+            px = px + rr * s[k];
+            pz = pz - rr * c[k];
+            vx = vx + rr * (c[k] * ((q2[k] - q1[k]) / h));
+            vz = vz + rr * (s[k] * ((q2[k] - q1[k]) / h));
+        }
+        T surf, cr, sr;
+        terrain_frame_2d(E, px, surf, cr, sr);
+        const T lt = b[2 * f] - b[2 * f + 1];
+        const T lx = cr * lt + sr * gam[f], lz = cr * gam[f] - sr * lt;      // R^T [lt; γ]
+        const T vt = cr * vx - sr * vz;                                       // (R v)[1]
+        dyn[0] = dyn[0] + lx; dyn[1] = dyn[1] + lz;
+        if (M.kind == PLANT_KIND_HOPPER_2D) {
+            const T rl = q2[3];
+            dyn[2] = dyn[2] + rl * (c[2] * lx + s[2] * lz);
+            dyn[3] = dyn[3] + (s[2] * lx - c[2] * lz);
+        }
+        for (int e = 0; e < (M.kind == PLANT_KIND_HOPPER_2D ? 0 : ch.n); ++e) {
+            const int k = ch.k[e]; const double rr = ch.r[e];
+            dyn[k] = dyn[k] + rr * (c[k] * lx + s[k] * lz);
+        }
+        r[nq + f] = s1[f] - (pz - surf);
+        r[nq + nc + 2 * f] = eta[2 * f] - vt - psi[f];
+        r[nq + nc + 2 * f + 1] = eta[2 * f + 1] + vt - psi[f];
+        r[nq + nc + nb + f] = s2[f] - (mu * gam[f] - (b[2 * f] + b[2 * f + 1]));
+        r[nq + 2 * nc + nb + f] = gam[f] * s1[f] - kappa;
+        r[nq + 3 * nc + nb + 2 * f] = b[2 * f] * eta[2 * f] - kappa;
+        r[nq + 3 * nc + nb + 2 * f + 1] = b[2 * f + 1] * eta[2 * f + 1] - kappa;
+        r[nq + 3 * nc + 2 * nb + f] = psi[f] * s2[f] - kappa;
+    }
+    for (int i = 0; i < nq; ++i) r[i] = dyn[i];
+}
+
+// Which terrains a model takes (cimpc_plant_step_terrain): FLAT everywhere; planar kinds on the planar models; 3-D kinds on the
+// particle; centroidal_quadruped flat only (its reference model never calls surf or rotation).
+inline bool terrain_valid_for(const PlantModel& M, const cimpc_terrain& E) {
+    const double* f[] = {E.p, E.brk + 1, E.off, &E.coef[0][0]};
+    const int n[] = {4, CIMPC_TERRAIN_MAX_PIECES - 1, CIMPC_TERRAIN_MAX_PIECES, 4 * CIMPC_TERRAIN_MAX_PIECES};
+    for (int a = 0; a < 4; ++a) for (int i = 0; i < n[a]; ++i) if (!std::isfinite(f[a][i])) return false;
+    if (E.kind < CIMPC_TERRAIN_FLAT || E.kind > CIMPC_TERRAIN_BOWL_3D) return false;
+    if (E.kind == CIMPC_TERRAIN_PIECEWISE) {
+        if (E.n_pieces < 1 || E.n_pieces > CIMPC_TERRAIN_MAX_PIECES) return false;
+        for (int i = 2; i < E.n_pieces; ++i) if (!(E.brk[i] > E.brk[i - 1])) return false;
+    }
+    if (E.kind == CIMPC_TERRAIN_SOFTPLUS && E.p[1] == 0.0) return false;
+    if (E.kind == CIMPC_TERRAIN_FLAT) return true;
+    if (M.kind == PLANT_KIND_CENTROIDAL) return false;
+    return terrain_is_3d(E.kind) == (M.kind == PLANT_KIND_PARTICLE);
+}
+
 // ---- the two models the reference tests in closed loop ---------------------------------------------------------------
 inline PlantChain plant_chain(int n, double r0, int k0, double r1 = 0, int k1 = 0, double r2 = 0, int k2 = 0) {
     PlantChain c{}; c.n = n; c.r[0] = r0; c.k[0] = k0; c.r[1] = r1; c.k[1] = k1; c.r[2] = r2; c.k[2] = k2; return c;
@@ -319,6 +562,14 @@ inline PlantModel plant_particle() {           // particle/model.jl:113-121
     M.nq = 3; M.nu = 3; M.g = 9.81; M.mu_world = 1.0; M.n_bodies = 0;
     M.mass[0] = 1.0;
     for (int i = 0; i < 3; ++i) M.joint_friction[i] = 0.0;
+    return M;
+}
+inline PlantModel plant_particle_2d() {        // particle_2D/model.jl (particle_2D = Particle2D(2, 2, 2, 1, 1.0, 9.81, 1.0, 0.0, ...))
+    PlantModel M{};
+    M.kind = PLANT_KIND_PARTICLE_2D; M.nc = 1; M.fd = 2; M.nw = 2;
+    M.nq = 2; M.nu = 2; M.g = 9.81; M.mu_world = 1.0; M.n_bodies = 0;
+    M.mass[0] = 1.0;
+    for (int i = 0; i < 2; ++i) M.joint_friction[i] = 0.0;
     return M;
 }
 inline PlantModel plant_flamingo() {           // flamingo/model.jl:458-495

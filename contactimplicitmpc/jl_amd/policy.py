@@ -38,11 +38,14 @@ def update_altitude(model, alt, gamma_hist, q_hist, threshold=1.0):
 class CIMPCPolicy:
     def __init__(self, problem, obj_q, obj_u, H_mpc=None, N_sample=1, kappa_mpc=None, B=1, mode=0,
                  n_opts: NewtonOptions | None = None, ip_opts: InteriorPointOptions | None = None, device=0,
-                 phase=None, obj_gamma=None, obj_b=None, obj_v=None, v_target=None):
+                 phase=None, obj_gamma=None, obj_b=None, obj_v=None, v_target=None, altitude_update=False,
+                 altitude_impact_threshold=1.0):
         """problem: a `lcp_models.ReferenceProblem` (reference trajectory + per-knot linearization at κ_mpc);
         obj_q, obj_u: (H_mpc, nq, nq), (H_mpc, nu, nu) TrackingObjective weights; obj_gamma / obj_b: contact-force
         weights of `:configurationforce` mode (mode = 1, the default of ci_mpc_policy); obj_v (+ v_target): the
-        velocity weights of a TrackingVelocityObjective."""
+        velocity weights of a TrackingVelocityObjective.  altitude_update / altitude_impact_threshold: CIMPCOptions
+        (policy.jl:5-14): before every solve after the first, `update_altitude!` over the simulator steps since the last solve
+        (handed over through `observe`, which `plant.simulate` calls), then `set_altitude!` (policy.jl:110-117)."""
         m = problem.model
         self.problem = problem
         self.H = H_mpc or problem.H
@@ -61,6 +64,8 @@ class CIMPCPolicy:
         self.stride = get_stride(m, problem.q)
         self.phase0 = None if phase is None else np.asarray(phase, dtype=np.int32).reshape(B)
         self.newton_iters = []
+        self.altitude_update = bool(altitude_update)
+        self.altitude_impact_threshold = float(altitude_impact_threshold)
         self.reset()
 
     def reset(self):
@@ -72,11 +77,25 @@ class CIMPCPolicy:
         self.cnt = self.N_sample
         self.solves = 0
         self.u = np.zeros((self.B, P.model.nu))
+        self.altitude = np.zeros((self.B, P.model.nc))          # p.altitude .= 0.0 (policy.jl:102)
+        self.gamma_hist, self.q_hist = [], []
+
+    def observe(self, q2, gamma):
+        """The outcome of one simulator step, (B, nq) and (B, nc): the part of `traj` the altitude update reads."""
+        if self.altitude_update:
+            self.q_hist = (self.q_hist + [np.array(q2, dtype=np.float64).reshape(self.B, -1)])[-self.N_sample:]
+            self.gamma_hist = (self.gamma_hist + [np.array(gamma, dtype=np.float64).reshape(self.B, -1)])[-self.N_sample:]
 
     def __call__(self, q1):
         """One simulator step: q1 = current configurations (B, nq) (`traj.q[t+1]`).  Returns the controls (B, nu)."""
         q1 = np.asarray(q1, dtype=np.float64).reshape(self.B, -1)
         if self.cnt == self.N_sample:
+            if self.altitude_update:
+                if self.solves > 0 and self.gamma_hist:               # steps max(0, t-1-N_sample)+1 .. t-1 (mpc_utils.jl:112)
+                    g, qh = np.stack(self.gamma_hist, axis=1), np.stack(self.q_hist, axis=1)
+                    for r in range(self.B):
+                        update_altitude(self.problem.model, self.altitude[r], g[r], qh[r], self.altitude_impact_threshold)
+                self.set_altitude(self.altitude)
             u1, it, rn = self.solver.newton_solve(self.q0, q1, warm_start=self.solves > 0)
             self.newton_iters.append(it.copy())
             self.solver.mpc_advance(self.stride)            # rot_n_stride! + update_window!

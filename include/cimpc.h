@@ -340,6 +340,43 @@ int cimpc_plant_step(int model, int B, const double* q0, const double* q1, const
                      double mu, double h, const cimpc_ip_opts* opts, double* q2, double* gamma, double* b,
                      int* status, int* iters);
 
+/* ---- plant step on non-flat terrain (src/simulator/environment.jl, src/simulation/environments) ------------------
+ * A terrain is a surface z = surf(x) (planar models) or z = surf(x, y) (the 3-D particle) with its gradient; the contact
+ * frame of every contact is rotated onto the surface normal under it.  Kinds:
+ *   FLAT                0                                              flat_2D_lc, flat_3D_lc
+ *   PIECEWISE           piece i (x >= brk[i], brk[0] = -inf): sum_k coef[i][k] (x - off[i])^k    slope1, piecewise1/2, stairs3
+ *   SOFTPLUS            (p0 / p1) log(1 + exp(p1 (x - p2)))            slope_smooth_2D_lc (evaluated overflow-safe)
+ *   SINE                p0 cos(p2 x) + p1 sin(p2 x) + p3               sine1/2/3_2D_lc
+ *   SINE_SUM_3D         p0 sin(p1 x) + p2 sin(p3 y)                    sine1/2_3D_lc
+ *   SINE_PRODUCT_3D     p0 sin(p1 x) sin(p1 y)                         sine3_3D_lc
+ *   BOWL_3D             p0 (x^2 + y^2)                                 quadratic_bowl_3D_lc
+ * The gradient of PIECEWISE is the derivative of the piece (the reference's hand-written surf_grad; zero for stairs3).
+ * Every field must be finite; PIECEWISE needs 1 <= n_pieces <= CIMPC_TERRAIN_MAX_PIECES and increasing brk[1..n-1]. */
+#define CIMPC_PLANT_PARTICLE_2D 6           /* src/dynamics/particle_2D/model.jl (nq 2, nu 2, nc 1, nw 2); cimpc_plant_step_terrain only */
+#define CIMPC_TERRAIN_FLAT 0
+#define CIMPC_TERRAIN_PIECEWISE 1
+#define CIMPC_TERRAIN_SOFTPLUS 2
+#define CIMPC_TERRAIN_SINE 3
+#define CIMPC_TERRAIN_SINE_SUM_3D 4
+#define CIMPC_TERRAIN_SINE_PRODUCT_3D 5
+#define CIMPC_TERRAIN_BOWL_3D 6
+#define CIMPC_TERRAIN_MAX_PIECES 8
+typedef struct cimpc_terrain {
+    int kind;
+    int n_pieces;
+    double p[4];
+    double brk[CIMPC_TERRAIN_MAX_PIECES];
+    double off[CIMPC_TERRAIN_MAX_PIECES];
+    double coef[CIMPC_TERRAIN_MAX_PIECES][4];
+} cimpc_terrain;
+/* cimpc_plant_step on terrain: n_terrain = 1 (every robot on `terrain[0]`) or B (robot i on terrain[i]).  Planar kinds (PIECEWISE,
+ * SOFTPLUS, SINE) apply to quadruped, flamingo, hopper_2D and particle_2D; 3-D kinds to particle; centroidal_quadruped takes FLAT
+ * only (its reference model ignores the environment).  A flat robot runs exactly the code of cimpc_plant_step (bit-identical
+ * results).  Any other count, an unknown kind, a kind the model does not take or a non-finite field: CIMPC_ERR_INVALID. */
+int cimpc_plant_step_terrain(int model, int B, int n_terrain, const cimpc_terrain* terrain, const double* q0, const double* q1,
+                             const double* u, const double* w, double mu, double h, const cimpc_ip_opts* opts, double* q2,
+                             double* gamma, double* b, int* status, int* iters);
+
 #ifdef __cplusplus
 }
 #endif

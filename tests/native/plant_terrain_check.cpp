@@ -1,0 +1,53 @@
+// Host harness for the terrain residual of contactimplicitmpc/jl_amd/csrc/plant_model.h: reads
+// "model kappa kind n_pieces p[4] brk[8] off[8] coef[8][4] z... th..." from stdin and prints nz nth, then the residual and
+// the dual-number Jacobian dr/dz (row-major) of plant_residual_terrain, then (models cimpc_plant_step has) the same two of
+// the flat plant_residual.
+#include <cstdio>
+#include <type_traits>
+#include <vector>
+#include "../../contactimplicitmpc/jl_amd/csrc/plant_model.h"
+using cimpc::Dual;
+template <class F>
+static void dump(int nz, const std::vector<double>& z, F eval) {
+    std::vector<double> r(nz);
+    eval(z.data(), r.data());
+    for (double v : r) printf("%.17g ", v);
+    printf("\n");
+    std::vector<Dual> zd(nz), rd(nz);
+    std::vector<double> J((size_t)nz * nz);
+    for (int j = 0; j < nz; ++j) {
+        for (int i = 0; i < nz; ++i) zd[i] = {z[i], i == j ? 1.0 : 0.0};
+        eval(zd.data(), rd.data());
+        for (int i = 0; i < nz; ++i) J[(size_t)i * nz + j] = rd[i].d;
+    }
+    for (double v : J) printf("%.17g ", v);
+    printf("\n");
+}
+int main() {
+    int model; double kappa;
+    if (scanf("%d %lf", &model, &kappa) != 2) return 1;
+    cimpc_terrain E{};
+    if (scanf("%d %d", &E.kind, &E.n_pieces) != 2) return 1;
+    for (double& v : E.p) if (scanf("%lf", &v) != 1) return 1;
+    for (double& v : E.brk) if (scanf("%lf", &v) != 1) return 1;
+    for (double& v : E.off) if (scanf("%lf", &v) != 1) return 1;
+    for (auto& row : E.coef) for (double& v : row) if (scanf("%lf", &v) != 1) return 1;
+    const cimpc::PlantModel M = model == 0 ? cimpc::plant_quadruped() : model == 1 ? cimpc::plant_flamingo() : model == 2 ? cimpc::plant_hopper_2d()
+                                : model == 5 ? cimpc::plant_particle() : model == 6 ? cimpc::plant_particle_2d() : cimpc::plant_centroidal(model == 3);
+    if (!cimpc::terrain_valid_for(M, E)) { printf("invalid\n"); return 0; }
+    const int nz = M.nz(), nth = M.nth();
+    std::vector<double> z(nz), th(nth);
+    for (auto& v : z) if (scanf("%lf", &v) != 1) return 1;
+    for (auto& v : th) if (scanf("%lf", &v) != 1) return 1;
+    printf("%d %d\n", nz, nth);
+    dump(nz, z, [&](const auto* zz, auto* rr) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(zz)>>;
+        cimpc::plant_residual_terrain<T>(M, E, zz, th.data(), kappa, rr);
+    });
+    if (model != 6)
+        dump(nz, z, [&](const auto* zz, auto* rr) {
+            using T = std::remove_const_t<std::remove_pointer_t<decltype(zz)>>;
+            cimpc::plant_residual<T>(M, zz, th.data(), kappa, rr);
+        });
+    return 0;
+}
