@@ -60,21 +60,9 @@ struct Knobs {
                                  // Measured 128 -> 64 (round 3): B = 96 8.88 -> 8.11 ms, B = 128 9.72 -> 9.48 ms, B = 64 unchanged (6.9 ms); 64 -> 32 (round 6,
                                  // after the rounds' sweep and KKT stage got faster): B = 64 5.0-5.7 -> 4.35-4.4 ms, B = 48 4.54 -> 4.07 ms with the hand-over at 32
     bool generic_static = false; // CIMPC_GENERIC_STATIC: runtime-dimension sweep with the static queue partition of rounds 2-3 instead of the dynamic pull
-    int kkt_pipe = -1;           // CIMPC_KKT_PIPE: three-wave pipelined KKT kernel 0 never, 1 always, -1 where the solve is on the critical path
-    int kkt_twisted = -1;        // CIMPC_KKT_TWISTED: twisted (two-ended) condensed solve, two workgroups per rollout: 0 never, 1 wherever the
-                                 // pipelined kernel would run, -1 = 1
+    KktPolicy kkt{};             // CIMPC_KKT_PIPE, _TWISTED, _DUO, _DUO_HINT, CIMPC_LAZY_DZ, CIMPC_ASYNC_KKT_TW and the KKT kernels' bounds (kkt_plan.h)
     int kkt_tw_nb = 0;           // CIMPC_KKT_TW_NB: rows eliminated from the bottom (0: the default split)
-    int kkt_duo = 1;             // CIMPC_KKT_DUO: 0 = packed one-wave kernel next to the sweep (rounds 2-5), 1 = the duo kernel where it applies
-    int kkt_duo_hint = 20000;    // CIMPC_KKT_DUO_HINT: ... in rounds whose sweep has at most this many problems queued (a shorter launch than the packed recursion)
-    int kkt_duo_max = 256;       // ... for at most this many systems per launch (one workgroup per CU at a time)
-    bool lazy_dz = true;         // CIMPC_LAZY_DZ: 0 = the decision kernel copies the accepted sensitivities itself (rounds 3-5)
     int kkt_tw_spins = 0;        // bound of a chain's wait for its partner, in polls (0: 2^21); the tests force the time-out path through cimpc_debug_set_tw_spins
-    int kkt_tw_max = 120;        // twisted kernel for at most this many rollouts per launch (two workgroups each must be resident together)
-    int async_kkt_tw = 1;        // CIMPC_ASYNC_KKT_TW: the persistent kernel's KKT stage as TWO cooperating jobs (the chains of the twisted solve): 0 never,
-                                 // 1 where it was measured a gain - single launches of at most 32 rollouts (quadruped H = 40, B = 4 / 16 / 32: 2.08 -> 1.85,
-                                 // 2.43 -> 2.27, 3.55 -> 3.41 ms; B = 64: 4.4 -> 4.9 ms - twice the jobs when every rollout reaches its KKT stage at once;
-                                 // hybrid tail of B = 512: no difference in six alternating pairs, the tail's chain is its interior-point evaluations) and hybrid
-                                 // tails of at most 32 rollouts (B = 48 / 64 / 96 / 128: -1.5 / -3 / -1 / 0 % in alternating pairs) -, 2 always
     // ---- constants ----
     int async_mem = 0;           // exchange buffers: ordinary device memory (uncached / fine-grained variants lost)
     int spec_all = -1;           // speculative slots of later line-search rounds: by batch size
@@ -92,11 +80,8 @@ struct Knobs {
     int async_sleep = 2;         // idle back-off of the asynchronous kernel (units of ~2 us), polls before looking around, wake-up fan
     int async_spins = 48;
     int async_fan = 1;
-    bool kkt_packed = true;      // two rollouts per KKT workgroup next to the sweep
-    bool kkt_scalar = false;     // scalar KKT kernel only where the MFMA one does not apply (tiles beyond 24, long horizons)
     int async_tail_grid = -1;    // workgroups of the hybrid tail's persistent kernel: 3 per rollout handed over (B = 512: 512 / 320 / 256 / 192 / 96
                                  // workgroups -> 10.85 / 10.42 / 10.35 / 10.38 / 10.6 ms)
-    int kkt_pipe_max = 128;      // pipelined KKT kernel for at most this many rollouts per round (it takes three times the waves)
 
     static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
     void read_environment() {
@@ -111,13 +96,13 @@ struct Knobs {
         async_full_max = env_int("CIMPC_ASYNC_FULL_MAX", async_full_max);
         drain_pct = env_int("CIMPC_DRAIN_PCT", drain_pct);
         drain_min = std::max(1, env_int("CIMPC_DRAIN_MIN", drain_min));
-        kkt_pipe = env_int("CIMPC_KKT_PIPE", kkt_pipe);
-        kkt_twisted = env_int("CIMPC_KKT_TWISTED", kkt_twisted);
+        kkt.kkt_pipe = env_int("CIMPC_KKT_PIPE", kkt.kkt_pipe);
+        kkt.kkt_twisted = env_int("CIMPC_KKT_TWISTED", kkt.kkt_twisted);
         kkt_tw_nb = env_int("CIMPC_KKT_TW_NB", kkt_tw_nb);
-        lazy_dz = env_int("CIMPC_LAZY_DZ", 1) != 0;
-        kkt_duo = env_int("CIMPC_KKT_DUO", kkt_duo);
-        kkt_duo_hint = env_int("CIMPC_KKT_DUO_HINT", kkt_duo_hint);
-        async_kkt_tw = env_int("CIMPC_ASYNC_KKT_TW", async_kkt_tw);
+        kkt.lazy_dz = env_int("CIMPC_LAZY_DZ", 1) != 0;
+        kkt.kkt_duo = env_int("CIMPC_KKT_DUO", kkt.kkt_duo);
+        kkt.kkt_duo_hint = env_int("CIMPC_KKT_DUO_HINT", kkt.kkt_duo_hint);
+        kkt.async_kkt_tw = env_int("CIMPC_ASYNC_KKT_TW", kkt.async_kkt_tw);
         generic_static = env_int("CIMPC_GENERIC_STATIC", generic_static ? 1 : 0) != 0;
         sweep_wgs = env_int("CIMPC_SWEEP_WGS", sweep_wgs);
         waves32 = env_int("CIMPC_WAVES32", waves32);
@@ -146,7 +131,7 @@ struct cimpc_ctx {
     int* g_phase = nullptr;
     bool gait_set = false;
     int dz_producer = 0;            // who wrote the per-step sensitivity memory last: 0 nobody, 1 newton_solve (dz_good), 2 implicit_dynamics (slot 0)
-    int* d_good_src = nullptr;      // [B][H] NewtonDev::good_src (in use where the KKT stage is the condensed MFMA solve: select_kkt_backend)
+    int* d_good_src = nullptr;      // [B][H] NewtonDev::good_src (in use where kkt_lazy_commit holds: set_kkt_backend)
     double* d_dz_knot = nullptr;    // [B][H_ref][nths*nd] per-knot archive, allocated at the first window change that needs it
     int wpk = 1;                 // persistent workgroups of a sweep launch
     double* d_alt = nullptr;
@@ -171,27 +156,25 @@ struct cimpc_ctx {
     std::vector<char> knot_set;
     int n_knots_set = 0;
     bool objective_set = false, window_set = false, reference_set = false, alt_set = false;
-    bool velocity_objective = false;
-    bool use_dense = false;        // KKT through kkt_dense.hip: the reference-default dense LU (any mode / objective) ...
-    bool use_banded = false;       // ... or its banded LDL^T (:configuration mode, velocity objective / on request)
-    int kkt_tw_overlap_max = 0;    // overlapped rounds: twisted KKT kernel when at most this many rollouts need a solve (0: never)
+    // KKT stage (kkt_plan.h): the knobs that take part, what the kernels can do for the problem, the solver family
+    KktPolicy kp{};
+    KktCaps kc{};
+    KktBackend kb = KktBackend::Condensed;
     long long adapt32 = 0;         // 32-lane models: problems per sweep launch from which the throughput build is taken (0: the handle's one build)
     long long n_kkt_twisted = 0;   // KKT launches that took the twisted kernel (cimpc_get_kkt_twisted)
     int* h_twfail = nullptr;       // host-mapped: hand-overs of the twisted kernels that timed out (NewtonDev::kkt_tw_fail), never reset
     int twfail_seen = 0;           // ... its value when the host last looked
     long long n_kkt_tw_fallbacks = 0;   // KKT stages repeated on the one-ended kernels after such a time-out (cimpc_get_kkt_twisted_fallbacks)
     bool band_reduce_ok = false;   // every R_t could be inverted: the banded LDL^T may eliminate the controls first (NewtonDev::band_reduce)
-    bool use_mixed = false;        // condensed solve in mixed precision (CIMPC_KKT_CONDENSED_MIXED)
     double* d_mix_ws = nullptr;
     int* d_mix_nfb = nullptr;
     size_t dense_ws_doubles = 0;
     // :configurationforce with negligible gamma / b weights: eliminated onto the :configuration solvers (newton_kernels.hip)
-    bool cf_reduce = false, cf_tiny = true;
+    bool cf_tiny = true;
     double* d_cf_ws = nullptr;
     double* d_dense_ws = nullptr;  // [B][N*N + 2N], allocated on first use
     double *d_V = nullptr, *d_qt = nullptr, *d_vt = nullptr;
     int waves = 4;
-    bool kkt_overlap = true;
     int* d_ring = nullptr;       // [MAX_DEPTH][8] device counters per in-flight round (behind the queue counters: Q.count .. +ctl_ints)
     size_t ctl_ints = 0;
     int* h_ring = nullptr;       // pinned, host-mapped: {n_sweep, n_kkt, stamp}
@@ -371,7 +354,7 @@ int run_sweep(cimpc_ctx* h, int par, int* pending_counter, double* zout, hipStre
     // build (8 waves, two per SIMD) from there on.  Parked iterates are the model's, not the build's: a solve may change builds.
     // (only where the host's count is complete: with the KKT stage in the same round as the evaluation of its candidates - small
     //  batches - the requests of that round are not known at launch; a first version sized a B = 1 sweep for ONE workgroup: 1.1 -> 20 ms)
-    if (h->ki.G == 32 && h->adapt32 > 0 && hint > 0 && h->kkt_overlap && h->kn.sweep_wgs <= 0 && !(h->kn.waves32 == 4 || h->kn.waves32 == 8)) {      // (an explicit CIMPC_SWEEP_WGS keeps its grid)
+    if (h->ki.G == 32 && h->adapt32 > 0 && hint > 0 && h->kp.kkt_overlap && h->kn.sweep_wgs <= 0 && !(h->kn.waves32 == 4 || h->kn.waves32 == 8)) {      // (an explicit CIMPC_SWEEP_WGS keeps its grid)
         waves = hint >= h->adapt32 ? 8 : 4;
         const size_t groups_per_wg = 2 * (size_t)waves;
         size_t w = ((size_t)hint + 2 * groups_per_wg - 1) / (2 * groups_per_wg);
@@ -396,60 +379,62 @@ int run_sweep(cimpc_ctx* h, int par, int* pending_counter, double* zout, hipStre
     return CIMPC_OK;
 }
 
-int ensure_dense_ws(cimpc_ctx* h) {
-    if (h->cf_reduce && !h->d_cf_ws && dev_alloc(h, &h->d_cf_ws, cf_reduce_doubles(h->S)) != CIMPC_OK) return CIMPC_ERR_HIP;
-    if (h->cf_reduce && h->S.V == nullptr) return CIMPC_OK;            // reduced problem goes to the condensed MFMA solve
-    const size_t need = h->cf_reduce ? kkt_dense_workspace_doubles(cf_shadow(h->S), true) : kkt_dense_workspace_doubles(h->S, h->use_banded);
+// KktCaps of the handle's problem, the backend they allow for the requested kkt_backend, and what follows from it
+static void set_kkt_backend(cimpc_ctx* h) {
+    NewtonDev& S = h->S;
+    KktCaps& c = h->kc;
+    c.cfg = h->dm.mode == CIMPC_MODE_CONFIGURATION;
+    c.velocity = S.V != nullptr;
+    c.cf_tiny = h->cf_tiny;
+    c.wide_tiles = (h->dm.nq > 16 || h->dm.nu > 16) && h->dm.nq <= 24 && h->dm.nu <= 24;
+    c.condensed = kkt_condensed_available(S);
+    c.mfma = kkt_mfma_available(S);
+    c.packed = kkt_packed_available(S);
+    c.twisted = kkt_twisted_available(S);
+    c.duo = kkt_duo_available(S);
+    c.mixed = kkt_mixed_available(S);
+    // Form of the banded LDL^T.  The reduced form (controls eliminated first) needs LDS for its pre-pass as well as the
+    // window: where that does not fit (long horizons of wide models) the full interleaved form is tried, and the dense LU
+    // serves what neither fits.  avail() = the availability test of whoever would run the banded kernel on S.
+    auto pick_band_form = [&](auto avail) {
+        for (int r = h->band_reduce_ok ? 1 : 0; r >= 0; --r) { S.band_reduce = r; if (avail()) return true; }
+        S.band_reduce = h->band_reduce_ok ? 1 : 0;
+        return false;
+    };
+    S.band_reduce = h->band_reduce_ok ? 1 : 0;
+    c.banded = c.cfg && pick_band_form([&] { return kkt_banded_available(S); });
+    c.cf_reduce = !c.cfg && (c.velocity ? pick_band_form([&] { return kkt_cf_reduce_available(S); }) : kkt_cf_reduce_available(S));
+    c.banded_twisted = kkt_banded_twisted_available(c.cfg ? S : cf_shadow(S));
+    h->kb = select_kkt_backend(c, h->nt.kkt_backend);
+    S.good_src = kkt_lazy_commit(h->kp, c, h->kb) ? h->d_good_src : nullptr;
+}
+
+// workspaces of the handle's KKT backend, allocated on first use
+int ensure_kkt_ws(cimpc_ctx* h) {
+    if (h->kb == KktBackend::Condensed) return CIMPC_OK;
+    if (h->kb == KktBackend::CondensedMixed) {
+        if (h->d_mix_ws) return CIMPC_OK;
+        if (dev_alloc(h, &h->d_mix_ws, kkt_mixed_workspace_doubles(h->S)) != CIMPC_OK) return CIMPC_ERR_HIP;
+        return dev_alloc(h, &h->d_mix_nfb, 1);
+    }
+    const bool cf = h->kb == KktBackend::CfCondensed || h->kb == KktBackend::CfBanded;
+    if (cf && !h->d_cf_ws && dev_alloc(h, &h->d_cf_ws, cf_reduce_doubles(h->S)) != CIMPC_OK) return CIMPC_ERR_HIP;
+    if (h->kb == KktBackend::CfCondensed) return CIMPC_OK;            // reduced problem goes to the condensed MFMA solve
+    const size_t need = cf ? kkt_dense_workspace_doubles(cf_shadow(h->S), true) : kkt_dense_workspace_doubles(h->S, h->kb == KktBackend::Banded);
     if (h->d_dense_ws && h->dense_ws_doubles >= need) return CIMPC_OK;
     h->d_dense_ws = nullptr;                      // (an earlier, smaller workspace stays in h->allocs until destroy)
     h->dense_ws_doubles = need;
     return dev_alloc(h, &h->d_dense_ws, need);
 }
 
-// which kkt_dense.hip path serves the current mode / objective / requested backend
-static void select_kkt_backend(cimpc_ctx* h) {
-    const bool cfg = h->dm.mode == CIMPC_MODE_CONFIGURATION;
-    const int want = h->nt.kkt_backend;
-    const bool velocity = h->S.V != nullptr;
-    // (dimension sets without a compiled condensed solve - the runtime-dimension path - take the banded LDL^T / dense LU)
-    h->use_dense = !cfg || want == CIMPC_KKT_DENSE_LU || want == CIMPC_KKT_BANDED_LDL || velocity || !kkt_condensed_available(h->S);
-    // Form of the banded LDL^T.  The reduced form (controls eliminated first) needs LDS for its pre-pass as well as the
-    // window: where that does not fit (long horizons of wide models) the full interleaved form is tried, and the dense LU
-    // serves what neither fits.  avail() = the availability test of whoever would run the banded kernel on h->S.
-    auto pick_band_form = [&](auto avail) {
-        h->S.band_reduce = h->band_reduce_ok ? 1 : 0;
-        if (avail()) return true;
-        if (h->S.band_reduce == 0) return false;
-        h->S.band_reduce = 0;
-        if (avail()) return true;
-        h->S.band_reduce = 1;
-        return false;
-    };
-    h->S.band_reduce = h->band_reduce_ok ? 1 : 0;
-    h->use_banded = h->use_dense && cfg && want != CIMPC_KKT_DENSE_LU && pick_band_form([&] { return kkt_banded_available(h->S); });
-    h->cf_reduce = !cfg && want != CIMPC_KKT_DENSE_LU && h->cf_tiny &&
-                   (velocity ? pick_band_form([&] { return kkt_cf_reduce_available(h->S); }) : kkt_cf_reduce_available(h->S));
-    h->use_mixed = want == CIMPC_KKT_CONDENSED_MIXED && !h->use_dense && kkt_mixed_available(h->S);
-    // lazy commit of the accepted sensitivities (NewtonDev::good_src): where every KKT stage is the condensed fp64 MFMA solve
-    // (CIMPC_LAZY_DZ=0 keeps the copy at the accept, for the A/B lines)
-    h->S.good_src = (!h->use_dense && !h->use_mixed && !h->cf_reduce && h->kn.lazy_dz && kkt_lazy_commit_available(h->S)) ? h->d_good_src : nullptr;
+// the form of a KKT stage at `site`, counted: the only place n_kkt_twisted moves
+static KktForm plan_kkt_stage(cimpc_ctx* h, const KktSite& site) {
+    const KktForm f = choose_kkt_form(h->kp, h->kc, h->kb, site);
+    if (two_ended(f)) h->n_kkt_twisted++;
+    return f;
 }
-
-int ensure_mixed_ws(cimpc_ctx* h) {
-    if (!h->use_mixed || h->d_mix_ws) return CIMPC_OK;
-    if (dev_alloc(h, &h->d_mix_ws, kkt_mixed_workspace_doubles(h->S)) != CIMPC_OK) return CIMPC_ERR_HIP;
-    return dev_alloc(h, &h->d_mix_nfb, 1);
-}
-
-// KKT stage of the Newton loop for everything that is not the plain condensed solve
-static int launch_kkt_general(cimpc_ctx* h, const NewtonDev& Sk, hipStream_t st) {
-    if (h->use_mixed) return launch_kkt_mixed_newton(Sk, h->d_mix_ws, h->d_mix_nfb, st);
-    if (h->cf_reduce) {
-        if (h->velocity_objective && kkt_banded_twisted_available(cf_shadow(Sk))) h->n_kkt_twisted++;
-        return launch_kkt_cf_reduced_newton(Sk, h->d_cf_ws, h->d_dense_ws, st);
-    }
-    if (h->use_banded && kkt_banded_twisted_available(Sk)) h->n_kkt_twisted++;      // (launch_kkt_dense's own test)
-    return launch_kkt_dense_newton(Sk, h->d_dense_ws, st, h->use_banded);
+static int run_kkt_stage(cimpc_ctx* h, const NewtonDev& Sk, const KktArgs& K, const KktSite& site, const int* list, int n, const int* n_dev, hipStream_t st) {
+    return launch_kkt_stage(Sk, K, h->kb, plan_kkt_stage(h, site), list, n, n_dev, KktWorkspace{h->d_dense_ws, h->d_cf_ws, h->d_mix_ws, h->d_mix_nfb}, st);
 }
 
 // statistics of the running / last solve: the per-rollout records of the decision stage, summed (NewtonDev::stats)
@@ -697,19 +682,17 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
     if (hipMemset(h->d_good_src, 0xFF, B * H * sizeof(int)) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {      // -1: every block is in dz_good
         g_create_error = "hipMemset failed"; cimpc_destroy(h); return CIMPC_ERR_HIP;
     }
-    S.kkt_scalar = h->kn.kkt_scalar ? 1 : 0;      // (select_kkt_backend reads it)
     S.band_form = h->kn.banded_form;
     S.r_tol = h->nt.r_tol; S.beta_init = h->nt.beta_init; S.kappa = h->nt.kappa; S.max_iter = h->nt.max_iter;
     // all-seven-step-lengths speculation: shortens the chain of rollouts that exhaust their line search; pays
     // when the solve is latency-bound (small batches), costs throughput otherwise (B = 2048: -8 %)
-    // condensed MFMA/scalar solve: :configuration + TrackingObjective; everything else (and kkt_backend = dense LU)
-    // goes through the reference-default dense LU
-    select_kkt_backend(h);
+    h->kp = h->kn.kkt;
+    h->kp.kkt_overlap = h->kn.kkt_overlap >= 0 ? h->kn.kkt_overlap != 0 : B >= 64;
+    set_kkt_backend(h);
     S.spec_all = h->kn.spec_all >= 0 ? h->kn.spec_all : (d.B <= 128 ? 3 : 8);
     // first line search of a solve (no history yet): 1, 1/2, 1/4 evaluated together up to mid-size batches (B = 512: 9.65 -> 9.50 ms,
     // B = 128: 8.14 -> 8.03 ms for 0.3 more evaluated sweeps per step; B = 2048: 25.4 -> 25.6 ms, throughput-bound: one candidate there)
     S.spec_first = h->kn.spec_first >= 0 ? h->kn.spec_first : (d.B <= 1024 ? 3 : 1);
-    S.kkt_scalar = h->kn.kkt_scalar ? 1 : 0;
     S.kkt_tw_nb = h->kn.kkt_tw_nb;
     S.kkt_tw_epoch = 0;
     S.kkt_tw_spins = h->kn.kkt_tw_spins > 0 ? h->kn.kkt_tw_spins : (1 << 21);
@@ -722,14 +705,6 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
         h->h_twfail[0] = 0;
         S.kkt_tw_fail = dv;
     }
-    S.kkt_tw_raw = (h->kn.kkt_twisted != 0 && d.B <= h->kn.kkt_tw_max) ? 1 : 0;
-    if (h->kn.kkt_duo == 2 && h->kn.kkt_twisted != 0) S.kkt_tw_raw = 2;      // CIMPC_KKT_DUO=2: the duo kernel at the B1 seam (tests)
-    // Overlapped rounds (B >= 64, hybrid schedule): the twisted kernel where EVERY round's KKT set fits the pair bound, i.e. batches
-    // of up to 120 rollouts - B = 96: 5.56 -> 4.8-5.1 ms per batch step; with a bound below the batch size the rounds mix kernels
-    // and lose (B = 128: 6.04 -> 6.8 ms at 48 / 96; B = 256 and 512 within the noise: profiles/r05/ab_tw_overlap.log).
-    // (CIMPC_KKT_TWISTED >= 2: the bound itself, for the A/B lines)
-    h->kkt_tw_overlap_max = h->kn.kkt_twisted >= 2 ? h->kn.kkt_twisted : (h->kn.kkt_twisted != 0 && d.B <= h->kn.kkt_tw_max ? h->kn.kkt_tw_max : 0);
-    S.kkt_tw_band = S.kkt_tw_raw;      // (the banded LDL^T is launched over all rollouts of the handle: the same bound applies)
     // large batches: a rollout whose previous search needed a back-off starts the next one with 1, 1/2, 1/4 together (one
     // round less per Newton iteration for 0.9 more evaluated sweeps per step: B = 512 11.4 -> 10.9 ms); small batches already
     // evaluate all seven step lengths from depth 3 on
@@ -754,8 +729,6 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
     // (measured B = 8: 5.2 -> 4.4 ms, B = 64: 8.5 -> 7.5 ms)
     if (h->async_on && (h->async_mode == 1 || (h->async_mode == 2 && B >= 4 && B <= h->kn.async_full_max))) h->waves = 4;
     if (h->kn.waves == 1 || h->kn.waves == 2 || (h->kn.waves >= 4 && h->kn.waves <= 8)) h->waves = h->kn.waves;   // (5..8: builds with CIMPC_SWEEP_THREADS > 256)
-    h->kkt_overlap = B >= 64;
-    if (h->kn.kkt_overlap >= 0) h->kkt_overlap = h->kn.kkt_overlap != 0;
     if (hipHostMalloc((void**)&h->h_ring, 32 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
         hipHostGetDevicePointer((void**)&h->h_ring_dev, h->h_ring, 0) != hipSuccess) {
         g_create_error = "ring allocation failed"; cimpc_destroy(h); return CIMPC_ERR_HIP;
@@ -985,11 +958,9 @@ int cimpc_set_objective(cimpc_handle h, const double* Q, const double* R, const 
         HIP_TRY(h, hipMemcpy(h->d_V, V, H * d.nq * d.nq * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(h->d_qt, qt.data(), qt.size() * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(h, hipMemcpy(h->d_vt, vt.data(), vt.size() * sizeof(double), hipMemcpyHostToDevice));
-        h->S.V = h->d_V; h->S.q_target = h->d_qt; h->S.v_target = h->d_vt;
-        h->velocity_objective = true;      // P is block tridiagonal: the condensed solve does not apply (banded LDL^T / dense LU)
+        h->S.V = h->d_V; h->S.q_target = h->d_qt; h->S.v_target = h->d_vt;      // P is block tridiagonal: banded LDL^T / dense LU
     } else {
         h->S.V = nullptr; h->S.q_target = nullptr; h->S.v_target = nullptr;
-        h->velocity_objective = false;
     }
     // the inverses first: whether every R_t could be inverted decides the form of the banded LDL^T (kkt_dense.hip:
     // kkt_banded_kernel eliminates the controls when it can), and that form decides whether the backend fits
@@ -1000,9 +971,9 @@ int cimpc_set_objective(cimpc_handle h, const double* Q, const double* R, const 
         if (d.nu > 0 && !invert(R + i * d.nu * d.nu, Ri.data() + i * d.nu * d.nu, d.nu)) r_inverted = false;
     }
     h->band_reduce_ok = r_inverted && d.nu > 0 && (h->kn.banded_form & 4) == 0;
-    select_kkt_backend(h);
+    set_kkt_backend(h);
     // (the inverses feed the condensed solve - also behind the cf-mode reduction - and the control elimination of the banded LDL^T)
-    const bool need_inv = !h->use_dense || (h->cf_reduce && V == nullptr);
+    const bool need_inv = h->kb == KktBackend::Condensed || h->kb == KktBackend::CondensedMixed || h->kb == KktBackend::CfCondensed;
     // (a refused objective leaves NO objective: the backend selection above is already committed while the device blocks still hold
     //  the previous call's - ADVICE r05 - so the handle goes back to "set_objective has not been called" instead of solving a mix)
     if (need_inv && !q_inverted) { h->objective_set = false; return fail(h, CIMPC_ERR_INVALID, "objective block Q[i] is singular"); }
@@ -1207,26 +1178,15 @@ int cimpc_kkt_solve(cimpc_handle h, const double* r, double beta, double* delta)
     const size_t n = (size_t)h->dm.B * h->N;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipMemcpyAsync(h->d_rhs, r, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (h->use_mixed) { rc = ensure_mixed_ws(h); if (rc != CIMPC_OK) return rc; }
-    else if (h->use_dense) { rc = ensure_dense_ws(h); if (rc != CIMPC_OK) return rc; }
+    if ((rc = ensure_kkt_ws(h)) != CIMPC_OK) return rc;
     // attempt 0 may take a twisted kernel (two chains per rollout with bounded hand-over waits); if one of them timed out - the
     // mapped counter moved - the numbers are poisoned and the solve is repeated ONCE on the one-ended kernels (round 6)
     for (int attempt = 0; attempt < 2; ++attempt) {
         h->S.kkt_tw_epoch += 1;
-        NewtonDev Sk = h->S;
-        if (attempt == 1) { Sk.kkt_tw_raw = 0; Sk.kkt_tw_band = 0; }
         const int fails0 = *(volatile int*)h->h_twfail;
         prof_begin(h, PC_KKT);
-        if (h->use_mixed) {
-            rc = launch_kkt_mixed_raw(Sk, h->d_rhs, beta, Sk.delta, h->d_mix_ws, h->d_mix_nfb, h->stream);
-        } else if (h->use_dense) {
-            if (h->cf_reduce ? (h->velocity_objective && kkt_banded_twisted_available(cf_shadow(Sk))) : (h->use_banded && kkt_banded_twisted_available(Sk))) h->n_kkt_twisted++;
-            rc = h->cf_reduce ? launch_kkt_cf_reduced_raw(Sk, h->d_rhs, beta, Sk.delta, h->d_cf_ws, h->d_dense_ws, h->stream)
-                              : launch_kkt_dense_raw(Sk, h->d_rhs, beta, Sk.delta, h->d_dense_ws, h->stream, h->use_banded);
-        } else {
-            if (Sk.kkt_tw_raw != 0 && kkt_twisted_available(Sk)) h->n_kkt_twisted++;      // (launch_kkt_raw's own test)
-            rc = launch_kkt_raw(Sk, h->d_rhs, beta, Sk.delta, h->stream);
-        }
+        rc = run_kkt_stage(h, h->S, kkt_raw_args(h->d_rhs, beta, h->S.delta), KktSite{.kind = KktSite::Seam, .attempt = attempt, .B = h->dm.B},
+                           nullptr, h->S.nb_launch, nullptr, h->stream);
         prof_end(h);
         if (rc != CIMPC_OK) return fail(h, rc, "kkt launch failed");
         HIP_TRY(h, hipMemcpyAsync(delta, h->S.delta, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1332,11 +1292,10 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
         A.dbg = h->a_dbg;
         if (h->a_dbg) HIP_TRY(h, hipMemsetAsync(h->a_dbg, 0, 16 * sizeof(long long), st));
         A.B = h->dm.B;
-        // KKT stage of the persistent kernel as two cooperating jobs (the chains of the twisted solve, newton_async_impl.h): 16-wide tiles,
-        // four-wave workgroups, a horizon the twisted form accepts, and no hand-over of this solve has timed out so far
-        A.kkt_tw = ((h->kn.async_kkt_tw == 2 || (h->kn.async_kkt_tw == 1 && (from_reset ? h->dm.B <= 32 : h->async_tail <= 32))) && h->kn.kkt_twisted != 0 && h->dm.nq <= 16 && h->dm.nu <= 16 && std::min(h->waves, 4) == 4 && kkt_twisted_available(Sk) &&
-                    *(volatile int*)h->h_twfail == tw_fail0) ? 1 : 0;
-        if (A.kkt_tw) h->n_kkt_twisted++;
+        // KKT stage of the persistent kernel: one job, or two cooperating jobs (the chains of the twisted solve, newton_async_impl.h)
+        const KktSite site{.kind = from_reset ? KktSite::Persistent : KktSite::HybridTail, .tw_off = *(volatile int*)h->h_twfail != tw_fail0,
+                           .B = h->dm.B, .async_tail = h->async_tail, .waves = std::min(h->waves, 4)};
+        A.kkt_tw = plan_kkt_stage(h, site) == KktForm::AsyncTwoJob ? 1 : 0;
         S.kkt_tw_epoch += h->nt.max_iter + 2;      // the launch's KKT stages take the stamps Sk.kkt_tw_epoch + 1 + (Newton iterations done)
         prof_begin(h, PC_OTHER, st);
         int rc2 = from_reset ? launch_reset(Sk, q0_dev, q1_dev, warm_start, st) : launch_async_handoff(Sk, LQ, st);
@@ -1390,10 +1349,10 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
         if (from_reset) h->prof_kkt_systems += h->last_stats.newton_iters;
         return CIMPC_OK;
     };
-    if (h->use_dense) { rc = ensure_dense_ws(h); if (rc != CIMPC_OK) return rc; }
-    if (h->use_mixed) { rc = ensure_mixed_ws(h); if (rc != CIMPC_OK) return rc; }
-    const bool full_async = h->async_on && !h->use_dense && !h->use_mixed && (h->async_mode == 1 || (h->async_mode == 2 && h->dm.B >= 4 && h->dm.B <= h->kn.async_full_max));
-    const bool hybrid = h->async_on && !h->use_dense && !h->use_mixed && h->async_mode == 2 && !full_async && h->dm.B > h->kn.async_full_max;
+    if ((rc = ensure_kkt_ws(h)) != CIMPC_OK) return rc;
+    const bool condensed = h->kb == KktBackend::Condensed;
+    const bool full_async = h->async_on && condensed && (h->async_mode == 1 || (h->async_mode == 2 && h->dm.B >= 4 && h->dm.B <= h->kn.async_full_max));
+    const bool hybrid = h->async_on && condensed && h->async_mode == 2 && !full_async && h->dm.B > h->kn.async_full_max;
     if (full_async) return run_async(true, 0);
     // safety net only: every Newton iteration needs at most 3 (speculative) rounds, each evaluation at
     // most ceil(max_iter / iter_cap) launches of the resumable interior-point sweep
@@ -1419,7 +1378,7 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
     // four rounds of a cold start lose more to the empty launches than they gain (0.685 -> 0.706 ms).
     // (not with a wall-clock budget: the round queued ahead would still run - and step the trajectory - after the host has stopped
     //  waiting, newton.jl:187-277 ends silently at the check)
-    const bool ahead = h->dm.B < 4 && !h->use_mixed && warm_start != 0 && !(h->nt.max_time > 0.0 && h->nt.max_time < 1.0e6);
+    const bool ahead = h->dm.B < 4 && h->kb != KktBackend::CondensedMixed && warm_start != 0 && !(h->nt.max_time > 0.0 && h->nt.max_time < 1.0e6);
     auto launch_round = [&](long long r, bool blind) -> int {
         // [KKT for rollouts that start an iteration] || sweep -> residual of every evaluated slot -> line-search decision
         const int slot = (int)(r & 1), par = (int)(r & 1);      // round r consumes Q[par] and leaves the next round's requests in Q[par ^ 1]
@@ -1430,7 +1389,6 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
         if (tw_fails != h->twfail_seen) { h->n_kkt_tw_fallbacks += tw_fails - h->twfail_seen; h->twfail_seen = tw_fails; }
         const bool tw_off = tw_fails != tw_fail0;
         NewtonDev Sk = S;
-        if (tw_off) Sk.kkt_tw_band = 0;
         Sk.b0 = 0; Sk.nb_launch = h->dm.B; Sk.counters = d_cnt;
         Sk.counters_next = h->d_ring + 8 * CPAD * (slot ^ 1);
         Sk.host_flag = h->h_ring_dev + 8 * slot;
@@ -1440,61 +1398,23 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
         const bool kkt = (r > 0) && (blind || last_kkt > 0);
         const int n_kkt = blind ? h->dm.B : last_kkt;
         const int* n_kkt_dev = blind ? h->d_ring + 8 * CPAD * (slot ^ 1) + 1 * CPAD : nullptr;      // the previous round's count of KKT requests
-        // (round 4, measured and removed: the three-wave kernel in rounds whose sweep is light - <= 16 k / 26 k / 60 k problems: KKT kernel
-        //  time 3.6 -> 3.4 / 3.0 / 2.7 ms per step, but the sweep and the tail give it back, 7.93 -> 7.88 / 7.88 / 7.96 ms:
-        //  profiles/r04/knob_kkt_pipe_small.log)
-        // Wide tiles (nq or nu in 17 .. 24: the centroidal sizes) hold one rollout per CU in either kernel (105 KB / 128 KB of LDS), so the
-        // three-wave kernel costs no extra CUs there - always taken (round 4, BASELINE configs[4] at 64 rollouts: KKT 6.1 -> 3.2 ms per
-        // step, 16.3 -> 13.3 ms; at 128 rollouts 24.2 -> 21.2 ms: profiles/r04/cent_kkt_pipe.log)
-        const bool wide_tiles = (h->dm.nq > 16 || h->dm.nu > 16) && h->dm.nq <= 24 && h->dm.nu <= 24;
-        // (CIMPC_KKT_PIPE selects between the one-wave and the three-wave kernel only - ADVICE r05: a 2 from the environment went
-        //  to the twisted kernel past its availability test and its pair bound; the twisted form is chosen below, where both are checked)
-        int pipe = h->kn.kkt_pipe >= 0 ? std::min(h->kn.kkt_pipe, 1) : ((!h->kkt_overlap && n_kkt <= h->kn.kkt_pipe_max) || wide_tiles) ? 1 : 0;
-        // Round 5: where the pipelined kernel runs - the solve is on the critical path - the TWISTED solve takes its place: two
-        // workgroups per rollout factor the block penta-diagonal matrix from both ends (two chains of about H / 2 steps), as long as
-        // every pair is resident at once
-        if (pipe == 1 && !tw_off && h->kn.kkt_twisted != 0 && n_kkt <= h->kn.kkt_tw_max && kkt_twisted_available(Sk)) pipe = 2;
-        // ... and in the OVERLAPPED rounds of larger batches when few rollouts start a Newton iteration (late rounds): the packed
-        // one-wave recursion (266 us) then outlasts the thinning sweep next to it, the twisted pair (two workgroups per rollout) does not
-        if (pipe == 0 && !tw_off && h->kkt_overlap && !blind && h->kn.kkt_twisted != 0 && h->kkt_tw_overlap_max > 0 && n_kkt > 0 && n_kkt <= h->kkt_tw_overlap_max &&
-            kkt_twisted_available(Sk)) pipe = 2;
-        // Round 6: the rounds' KKT stage NEXT TO the sweep (overlapped rounds, one-wave packed kernel so far) takes the DUO kernel - the
-        // two-ended solve as two one-wave chains in one workgroup, the LDS footprint of the packed kernel's workgroup - while every
-        // system gets a workgroup at once (one per CU): the packed recursion is a chain of H steps, 0.27 - 0.33 ms whatever the
-        // number of systems, and outlasted the sweep in 11 of the 16 rounds of the headline step
-        // ... in the rounds whose sweep is SHORTER than the packed recursion would be (the host knows the problems queued for it: evaluation
-        // slots requested + solves parked; a launch takes about 80 us + 1 us per 112 problems): next to a long sweep the packed kernel is
-        // off the critical path anyway and takes half as many CUs from it (B = 1024: 11.7 -> 12.5 ms with the duo kernel everywhere;
-        // B = 256: 6.46 -> 5.89 ms, B = 512 unchanged)
-        // (the NEWLY REQUESTED evaluation slots only - not the parked solves, not the slots re-listed while they wait for one: which
-        //  solves a launch parks depends on timing, and a kernel choice that followed it would make the iterates differ from run to
-        //  run - the two kernels agree to 1e-12, not to the bit; scripts/dbg/repro_check.py)
-        const long long sweep_problems = blind ? -1 : (long long)last_new_slots * h->dm.H;
-        if (pipe == 0 && !tw_off && h->kkt_overlap && h->kn.kkt_duo != 0 && h->kn.kkt_twisted != 0 && n_kkt > 0 && n_kkt <= h->kn.kkt_duo_max && sweep_problems >= 0 &&
-            sweep_problems <= h->kn.kkt_duo_hint && kkt_duo_available(Sk)) pipe = 3;
-        if (kkt && (pipe == 2 || pipe == 3) && !h->use_dense && !h->use_mixed && (h->kkt_overlap ? h->kn.kkt_packed : true)) h->n_kkt_twisted++;
-        if (kkt && !h->kkt_overlap) {   // small batches: latency matters, keep the KKT result in this round
-            Sk.kkt_same_round = 1;
-            prof_begin(h, PC_KKT, sb.st);
-            // (same compact list / packed or pipelined kernel as the overlapped path)
-            int rr = (h->use_dense || h->use_mixed) ? launch_kkt_general(h, Sk, sb.st) : launch_kkt_packed(Sk, n_kkt, par ^ 1, sb.st, n_kkt_dev, pipe);
-            prof_end(h, sb.st);
-            if (rr != CIMPC_OK) return fail(h, rr, "kkt launch failed");
-        }
-        if (kkt && h->kkt_overlap) {
-            // KKT of the rollouts that start a Newton iteration, next to the sweep on its own stream.  No fork
-            // event: the host has seen the previous round's stamp, so everything before is complete (every decision
-            // block releases its results before it takes its ticket).  (Launched BEFORE the sweep: the other order was
-            // measured 10 % slower in round 1 and 20 % slower in round 3 (8.37 -> 10.05 ms, profiles/r03/knob_order.log) - behind the
-            // persistent sweep the KKT workgroups wait for sweep workgroups to leave: 3.6 -> 6.2 ms of KKT time per step.)
-            prof_begin(h, PC_KKT, sb.st_kkt);
-            // the list was built by the decision kernel of the previous round (its queue parity)
-            int rk = (h->use_dense || h->use_mixed) ? launch_kkt_general(h, Sk, sb.st_kkt)
-                                  : h->kn.kkt_packed ? launch_kkt_packed(Sk, last_kkt, par ^ 1, sb.st_kkt, nullptr, pipe)
-                                                     : launch_kkt(Sk, sb.st_kkt);
-            prof_end(h, sb.st_kkt);
+        if (kkt) {
+            // KKT of the rollouts that start a Newton iteration (list of the previous round's decision kernel, its queue parity).  Small
+            // batches: latency matters, ahead of the sweep on its stream, the result kept in this round.  Overlapped: next to the sweep
+            // on its own stream, no fork event (every decision block of the previous round released its results before its ticket).
+            // (Launched BEFORE the sweep: the other order was measured 10 % / 20 % slower in rounds 1 / 3, 8.37 -> 10.05 ms - behind the
+            // persistent sweep the KKT workgroups wait for sweep workgroups to leave: profiles/r03/knob_order.log.)
+            const bool ov = h->kp.kkt_overlap;
+            const KktSite site{.kind = ov ? KktSite::Overlapped : KktSite::Round, .n_kkt = n_kkt, .blind = blind,
+                               .sweep_problems = (long long)last_new_slots * h->dm.H, .tw_off = tw_off, .B = h->dm.B};
+            hipStream_t kst = ov ? sb.st_kkt : sb.st;
+            if (!ov) Sk.kkt_same_round = 1;
+            prof_begin(h, PC_KKT, kst);
+            int rk = run_kkt_stage(h, Sk, kkt_newton_args(Sk), site, Sk.kkt_list + (size_t)(par ^ 1) * h->dm.B,
+                                   ov ? last_kkt : n_kkt, ov ? nullptr : n_kkt_dev, kst);      // (overlapped: the host's count, blind rounds too)
+            prof_end(h, kst);
             if (rk != CIMPC_OK) return fail(h, rk, "kkt launch failed");
-            if (hipEventRecord(sb.ev_join, sb.st_kkt) != hipSuccess) return fail(h, CIMPC_ERR_HIP, "join record failed");
+            if (ov && hipEventRecord(sb.ev_join, sb.st_kkt) != hipSuccess) return fail(h, CIMPC_ERR_HIP, "join record failed");
         }
         // parking (iter_cap) protects a busy round from one long solve; in the sparse tail of a solve
         // it only adds rounds, so a round that serves few rollouts lets every solve run to the end
@@ -1518,18 +1438,18 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
         if (rr != CIMPC_OK) return rr;
         // the evaluation slots of this round: the compact list its requesters built (small batches run the KKT stage in the same
         // round as the evaluation of its candidates - not known to the host at launch: every (rollout, slot) pair gets a block there)
-        const int n_slots = h->kkt_overlap ? last_slots : (h->dm.B < 4 ? -2 : -1);
+        const int n_slots = h->kp.kkt_overlap ? last_slots : (h->dm.B < 4 ? -2 : -1);
         // round 4: the per-slot residual kernel goes in FRONT of the join with the overlapped KKT kernel (it reads the sweep's results
         // only; the rollouts the KKT kernel works on have no slot on this round's list), the decision kernel behind it - in the
         // rounds whose KKT recursion outlasts the sweep (about six per step of the headline batch) the 26 us of the slot kernel
         // leave the critical path
-        const bool split_join = kkt && h->kkt_overlap && n_slots >= 0;
+        const bool split_join = kkt && h->kp.kkt_overlap && n_slots >= 0;
         prof_begin(h, PC_RESID, sb.st);
         if (split_join) {
             rr = launch_resid_decide(Sk, sb.st, n_slots, 1);
             if (rr != CIMPC_OK) return fail(h, rr, "residual launch failed");
         }
-        if (kkt && h->kkt_overlap && hipStreamWaitEvent(sb.st, sb.ev_join, 0) != hipSuccess) return fail(h, CIMPC_ERR_HIP, "join failed");
+        if (kkt && h->kp.kkt_overlap && hipStreamWaitEvent(sb.st, sb.ev_join, 0) != hipSuccess) return fail(h, CIMPC_ERR_HIP, "join failed");
         rr = launch_resid_decide(Sk, sb.st, n_slots, split_join ? 2 : 0);
         prof_end(h, sb.st);
         if (rr != CIMPC_OK) return fail(h, rr, "residual launch failed");

@@ -225,6 +225,13 @@ inline int lds_opt_in(LdsOptIn& cache, const void* kernel, size_t lds) {
     cache.set[dev] = lds;
     return CIMPC_OK;
 }
+// ... and launch it
+template <class Kern, class... Args>
+int launch_lds(LdsOptIn& cache, Kern kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+    if (lds_opt_in(cache, (const void*)kernel, lds) != CIMPC_OK) return CIMPC_ERR_HIP;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
+}
 
 // dims-dispatching launchers (ip_kernel.hip / newton_kernels.hip)
 int ip_kernel_info(const cimpc_dims* dm, KernelInfo* info);

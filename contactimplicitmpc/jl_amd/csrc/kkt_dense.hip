@@ -1035,10 +1035,9 @@ bool kkt_banded_available(const NewtonDev& S) {      // window + two vectors in 
     return S.dm.mode == CIMPC_MODE_CONFIGURATION && w <= 190 && banded_lds_bytes(S) <= 160 * 1024;
 }
 
-// the twisted form: asked for (NewtonDev::kkt_tw_band, set by the host where the launch is latency-bound), reduced form, blocks of
-// eight, compile-time power-of-two window, and a band long enough for two chains
+// KktForm::BandedTwisted: reduced form, blocks of eight, compile-time power-of-two window, a band long enough for two chains
 bool kkt_banded_twisted_available(const NewtonDev& S) {
-    if (S.kkt_tw_band == 0 || S.kkt_tw_flags == nullptr || S.band_reduce == 0 || S.dm.nu <= 0) return false;
+    if (S.kkt_tw_flags == nullptr || S.band_reduce == 0 || S.dm.nu <= 0) return false;
     if (banded_rb(S) != 8 || !banded_pow2(S)) return false;
     const int w = band_halfwidth(S), slots = banded_pow2_slots(w + 8), N = S.dm.H * (S.dm.nq + S.nd);
     if (slots != 128 && slots != 64 && slots != 32) return false;
@@ -1052,49 +1051,33 @@ size_t kkt_dense_workspace_doubles(const NewtonDev& S, bool banded) {
     return (size_t)S.dm.B * ((size_t)S.N * S.N + 2 * (size_t)S.N);
 }
 
-static int launch_kkt_dense(const NewtonDev& S, const KktArgs& K, double* ws, hipStream_t s, bool banded) {
-    if (banded) {
-        const size_t lds = banded_lds_bytes(S);
-        static LdsOptIn optin[7];      // one per kernel
-        auto go = [&](auto kern, int which) {
-            if (lds_opt_in(optin[which], (const void*)kern, lds) != CIMPC_OK) return (int)CIMPC_ERR_HIP;
-            hipLaunchKernelGGL(kern, dim3(S.nb_launch), dim3(CIMPC_BANDED_THREADS), lds, s, S, K, ws);
-            return hipGetLastError() == hipSuccess ? (int)CIMPC_OK : (int)CIMPC_ERR_HIP;
-        };
-        const bool p2 = banded_pow2(S);
-        const int slots = p2 ? banded_pow2_slots(band_halfwidth(S) + banded_rb(S)) : 0;
-        if (kkt_banded_twisted_available(S)) {      // two chains per rollout from the two ends of the band (latency-bound launches)
-            static LdsOptIn optin_tw[3];
-            auto go_tw = [&](auto kern, int which) {
-                if (lds_opt_in(optin_tw[which], (const void*)kern, lds) != CIMPC_OK) return (int)CIMPC_ERR_HIP;
-                hipLaunchKernelGGL(kern, dim3(2 * S.nb_launch), dim3(CIMPC_BANDED_THREADS), lds, s, KktBandTwArgs{S, K, ws});
-                return hipGetLastError() == hipSuccess ? (int)CIMPC_OK : (int)CIMPC_ERR_HIP;
-            };
-            if (slots == 128) return go_tw(kkt_banded_twisted_kernel<8, 128>, 0);
-            if (slots == 64) return go_tw(kkt_banded_twisted_kernel<8, 64>, 1);
-            if (slots == 32) return go_tw(kkt_banded_twisted_kernel<8, 32>, 2);
-        }
-        if (banded_rb(S) == 8) {
-            if (slots == 128) return go(kkt_banded_kernel<8, 128>, 4);
-            if (slots == 64) return go(kkt_banded_kernel<8, 64>, 5);
-            if (slots == 32) return go(kkt_banded_kernel<8, 32>, 6);
-            return p2 ? go(kkt_banded_kernel<8, -1>, 0) : go(kkt_banded_kernel<8, 0>, 1);
-        }
-        return p2 ? go(kkt_banded_kernel<4, -1>, 2) : go(kkt_banded_kernel<4, 0>, 3);
+int launch_kkt_dense(const NewtonDev& S, const KktArgs& K, KktForm f, double* ws, hipStream_t s) {
+    if (f == KktForm::Dense) {
+        hipLaunchKernelGGL(kkt_dense_kernel, dim3(S.nb_launch), dim3(256), 0, s, S, K, ws);
+        return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
     }
-    hipLaunchKernelGGL(kkt_dense_kernel, dim3(S.nb_launch), dim3(256), 0, s, S, K, ws);
-    return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
-}
-int launch_kkt_dense_args(const NewtonDev& S, const KktArgs& K, double* ws, hipStream_t s, bool banded) {
-    return launch_kkt_dense(S, K, ws, s, banded);
-}
-int launch_kkt_dense_newton(const NewtonDev& S, double* ws, hipStream_t s, bool banded) {
-    KktArgs K{S.res, S.delta, S.beta, 0.0, S.stage, 1};
-    return launch_kkt_dense(S, K, ws, s, banded);
-}
-int launch_kkt_dense_raw(const NewtonDev& S, const double* r_dev, double beta, double* delta_dev, double* ws, hipStream_t s, bool banded) {
-    KktArgs K{r_dev, delta_dev, nullptr, beta, nullptr, 0};
-    return launch_kkt_dense(S, K, ws, s, banded);
+    const size_t lds = banded_lds_bytes(S);
+    const bool p2 = banded_pow2(S);
+    const int slots = p2 ? banded_pow2_slots(band_halfwidth(S) + banded_rb(S)) : 0;
+    if (f == KktForm::BandedTwisted) {      // two chains per rollout from the two ends of the band (latency-bound launches)
+        static LdsOptIn optin_tw[3];
+        auto go_tw = [&](auto kern, int which) { return launch_lds(optin_tw[which], kern, dim3(2 * S.nb_launch), dim3(CIMPC_BANDED_THREADS), lds, s, KktBandTwArgs{S, K, ws}); };
+        if (banded_rb(S) != 8) return CIMPC_ERR_INVALID;
+        if (slots == 128) return go_tw(kkt_banded_twisted_kernel<8, 128>, 0);
+        if (slots == 64) return go_tw(kkt_banded_twisted_kernel<8, 64>, 1);
+        if (slots == 32) return go_tw(kkt_banded_twisted_kernel<8, 32>, 2);
+        return CIMPC_ERR_INVALID;
+    }
+    if (f != KktForm::BandedOneEnded) return CIMPC_ERR_INVALID;
+    static LdsOptIn optin[7];      // one per kernel
+    auto go = [&](auto kern, int which) { return launch_lds(optin[which], kern, dim3(S.nb_launch), dim3(CIMPC_BANDED_THREADS), lds, s, S, K, ws); };
+    if (banded_rb(S) == 8) {
+        if (slots == 128) return go(kkt_banded_kernel<8, 128>, 4);
+        if (slots == 64) return go(kkt_banded_kernel<8, 64>, 5);
+        if (slots == 32) return go(kkt_banded_kernel<8, 32>, 6);
+        return p2 ? go(kkt_banded_kernel<8, -1>, 0) : go(kkt_banded_kernel<8, 0>, 1);
+    }
+    return p2 ? go(kkt_banded_kernel<4, -1>, 2) : go(kkt_banded_kernel<4, 0>, 3);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -314,7 +314,6 @@ __device__ __forceinline__ void start_line_search(const NewtonDev& S, int b, int
     } else {
         // the KKT kernel runs on its own stream NEXT TO the sweep of the running round: its
         // candidates join the queue of the next round
-        // (chained round, kkt_same_round = 2: the round's second sweep consumes par ^ 1 - nothing is requested of the next round)
         const int par = (S.kkt_same_round == 1) ? S.WQ.par : (S.WQ.par ^ 1);
         // overlapped KKT kernel (kkt_same_round = 0): this round's decision kernel runs AFTER this kernel and would take the
         // freshly requested candidates (stage LS*, need_sweep set, done_count 0) for an evaluation of ITS round with parked
@@ -942,16 +941,7 @@ __global__ __launch_bounds__(CIMPC_RESID_THREADS) void resid_decide_kernel(Newto
 //   L0_i L0_i^T = Y_ii - L1_i L1_i^T - L2_i L2_i^T        (compute_L!, methods.jl:466-485)
 //   forward / backward block substitution, Delta_x = P^-1 (r_p - C^T dnu)   (:506-557)
 // -------------------------------------------------------------------------------------------
-struct KktArgs {
-    const double* r;     // [B][N] right-hand side
-    double* delta;       // [B][N]
-    const double* beta;  // [B] or null (then beta_scalar)
-    double beta_scalar;
-    const int* stage;    // only rollouts with stage == STAGE_KKT (null = all)
-    int finish;          // 1: set alpha/ls_iter/cand/stage after the solve (newton loop)
-    const double* dz_override;   // [B][H][nths][nd] sensitivities to use instead of S.dz_good / S.dz (cf-mode reduction)
-    const int* only_flag;        // [B] or null: run only the rollouts whose flag is non-zero (mixed-precision refinement / fallback)
-};
+// (KktArgs: newton_state.h)
 // sensitivities a KKT solve reads: the accepted evaluation's (Newton loop), slot 0 of the last implicit_dynamics! (B1
 // seam, no stage array), or an explicit buffer
 __device__ __forceinline__ const double* kkt_dz(const NewtonDev& S, const KktArgs& K, int b, int H, int nths, int nd) {

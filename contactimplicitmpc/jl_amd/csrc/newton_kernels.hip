@@ -74,29 +74,20 @@ __global__ __launch_bounds__(256) void reset_kernel(NewtonDev S, const double* q
     else enqueue_eval(S, sb0, b, S.WQ.par, tid, nt, b - S.b0);      // round 0 evaluates slot 0 of every rollout: list entry b
 }
 
+// one workgroup per rollout: kkt_kernel (f32: fp32 MFMA block products, refined by launch_kkt_mixed) or kkt_kernel_scalar
 template <int NQ, int NU>
-static int launch_kkt_t(const NewtonDev& S, const KktArgs& K, hipStream_t s, bool f32 = false) {
-    const bool force_scalar = S.kkt_scalar != 0;      // (CIMPC_KKT_SCALAR, read at cimpc_create)
-    if (NQ <= 24 && NU <= 24 && S.dm.H <= kkt_max_h<NQ, NU>() && !force_scalar) {   // dnu / recovery staging bounds H
+static int launch_kkt_t(const NewtonDev& S, const KktArgs& K, KktForm f, bool f32, hipStream_t s) {
+    if (f == KktForm::PerRollout) {
+        if (NQ > 24 || NU > 24 || S.dm.H > kkt_max_h<NQ, NU>()) return CIMPC_ERR_INVALID;   // dnu / recovery staging bounds H
         const size_t lds = (size_t)kkt_lds_doubles<NQ, NU, 1>() * sizeof(double);
-        if (f32) {      // block products on the fp32 MFMA (launch_kkt_mixed refines the result in fp64)
-            static LdsOptIn optin32;
-            if (lds_opt_in(optin32, (const void*)kkt_kernel<NQ, NU, true>, lds) != CIMPC_OK) return CIMPC_ERR_HIP;
-            hipLaunchKernelGGL((kkt_kernel<NQ, NU, true>), dim3(S.nb_launch), dim3(64), lds, s, S, K);
-            return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
-        }
-        static LdsOptIn optin;
-        if (lds_opt_in(optin, (const void*)kkt_kernel<NQ, NU>, lds) != CIMPC_OK) return CIMPC_ERR_HIP;
-        hipLaunchKernelGGL((kkt_kernel<NQ, NU>), dim3(S.nb_launch), dim3(64), lds, s, S, K);
-    } else {
-        if (f32) return CIMPC_ERR_INVALID;
-        constexpr int LD = ((NQ > NU ? NQ : NU) + 3) & ~3;
-        const size_t lds = (size_t)(KKT_TILES * LD * LD + 10 * LD) * sizeof(double);
-        static LdsOptIn optin;
-        if (lds_opt_in(optin, (const void*)kkt_kernel_scalar<NQ, NU>, lds) != CIMPC_OK) return CIMPC_ERR_HIP;
-        hipLaunchKernelGGL((kkt_kernel_scalar<NQ, NU>), dim3(S.nb_launch), dim3(64), lds, s, S, K);
+        static LdsOptIn optin, optin32;
+        if (f32) return launch_lds(optin32, kkt_kernel<NQ, NU, true>, dim3(S.nb_launch), dim3(64), lds, s, S, K);
+        return launch_lds(optin, kkt_kernel<NQ, NU>, dim3(S.nb_launch), dim3(64), lds, s, S, K);
     }
-    return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
+    if (f != KktForm::Scalar || f32) return CIMPC_ERR_INVALID;
+    constexpr int LD = ((NQ > NU ? NQ : NU) + 3) & ~3;
+    static LdsOptIn optin;
+    return launch_lds(optin, kkt_kernel_scalar<NQ, NU>, dim3(S.nb_launch), dim3(64), (size_t)(KKT_TILES * LD * LD + 10 * LD) * sizeof(double), s, S, K);
 }
 
 // (nq, nu) pairs of the built models (the horizon-level kernels depend on these two sizes only): pushbot / particle_2D,
@@ -104,10 +95,42 @@ static int launch_kkt_t(const NewtonDev& S, const KktArgs& K, hipStream_t s, boo
 // walledcartpole, particle
 #define CIMPC_NQNU(X) X(2, 2) X(4, 2) X(11, 8) X(9, 6) X(18, 12) X(7, 3) X(4, 1) X(3, 3)
 
-static int launch_kkt_any(const NewtonDev& S, const KktArgs& K, hipStream_t s, bool f32 = false) {
+// compact-list forms: rollouts list[0 .. n) (list == null: every rollout of the launch, stage filter as kkt_kernel - Twisted / Duo)
+template <int NQ, int NU>
+static int launch_kkt_list_t(const NewtonDev& S, const KktArgs& K, KktForm f, const int* list, int n, const int* n_dev, hipStream_t s) {
+    if constexpr (NQ <= 24 && NU <= 24) {
+        if (S.dm.H > kkt_max_h<NQ, NU>()) return CIMPC_ERR_INVALID;
+        if constexpr (kkt_tld<NQ, NU>() == 16) if (f == KktForm::Duo) {      // one workgroup of two one-wave chains per rollout (16-wide tiles)
+            static LdsOptIn optin;
+            return launch_lds(optin, kkt_kernel_duo<NQ, NU>, dim3(n), dim3(128), (size_t)(kkt_duo_slice_doubles(1) + kkt_duo_slice_doubles(2)) * sizeof(double),
+                              s, KktTwArgs{S, K, list, n, n_dev});
+        }
+        if (f == KktForm::Twisted) {      // two workgroups of three wavefronts per rollout, one chain from either end
+            static LdsOptIn optin;
+            return launch_lds(optin, kkt_kernel_twisted<NQ, NU>, dim3(2 * n), dim3(192), (size_t)kkt_tw_lds_doubles<NQ, NU>() * sizeof(double), s,
+                              KktTwArgs{S, K, list, n, n_dev});
+        }
+        if (f == KktForm::Pipelined && list != nullptr) {      // three wavefronts per rollout, software-pipelined forward recursion
+            static LdsOptIn optin;
+            return launch_lds(optin, kkt_kernel_pipe<NQ, NU>, dim3(n), dim3(192), (size_t)kkt_lds_doubles<NQ, NU, 3>() * sizeof(double), s, S, K, list, n, n_dev);
+        }
+        if (f == KktForm::Packed && list != nullptr) {
+            constexpr int PACK = kkt_pack<NQ, NU>();
+            static LdsOptIn optin;
+            return launch_lds(optin, kkt_kernel_packed<NQ, NU>, dim3((n + PACK - 1) / PACK), dim3(64 * PACK), (size_t)PACK * kkt_lds_doubles<NQ, NU, 1>() * sizeof(double),
+                              s, S, K, list, n, n_dev);
+        }
+    }
+    return CIMPC_ERR_INVALID;
+}
+// condensed solve in the given form (f32: PerRollout only, the mixed sequence's passes)
+static int launch_kkt_condensed(const NewtonDev& S, const KktArgs& K, KktForm f, bool f32, const int* list, int n, const int* n_dev, hipStream_t s) {
     if (S.dm.mode != CIMPC_MODE_CONFIGURATION) return CIMPC_ERR_INVALID;
+    const bool rollout = f == KktForm::PerRollout || f == KktForm::Scalar;      // (grid: every rollout of the launch, n only gates it)
+    if (n_dev != nullptr) n = S.dm.B;      // upper bound of the grid; surplus workgroups leave at once
+    if (n <= 0) return CIMPC_OK;
     const int nq = S.dm.nq, nu = S.dm.nu;
-#define X(q, u) if (nq == q && nu == u) return launch_kkt_t<q, u>(S, K, s, f32);
+#define X(q, u) if (nq == q && nu == u) return rollout ? launch_kkt_t<q, u>(S, K, f, f32, s) : f32 ? CIMPC_ERR_INVALID : launch_kkt_list_t<q, u>(S, K, f, list, n, n_dev, s);
     CIMPC_NQNU(X)
 #undef X
     return CIMPC_ERR_INVALID;
@@ -221,14 +244,13 @@ size_t kkt_mixed_workspace_doubles(const NewtonDev& S) { return 2 * (size_t)S.dm
 bool kkt_mixed_available(const NewtonDev& S) {
     return S.dm.mode == CIMPC_MODE_CONFIGURATION && S.V == nullptr && S.dm.nq <= 24 && S.dm.nu <= 24 && S.dm.H <= 96;
 }
-int launch_kkt_mixed(const NewtonDev& S, const KktArgs& K0, double* ws, int* n_fallback, hipStream_t s) {
-    if (!kkt_mixed_available(S)) return CIMPC_ERR_INVALID;
+static int launch_kkt_mixed(const NewtonDev& S, const KktArgs& K0, double* ws, int* n_fallback, hipStream_t s) {
     const size_t BN = (size_t)S.dm.B * S.N;
     double* corr = ws; double* res = ws + BN;
     int* flag = reinterpret_cast<int*>(ws + 2 * BN);
     hipLaunchKernelGGL(kkt_mixed_init_kernel, dim3((S.nb_launch + 255) / 256), dim3(256), 0, s, S, K0, flag);
     KktArgs P = K0; P.finish = 0; P.only_flag = flag;
-    int rc = launch_kkt_any(S, P, s, true);                                   // P0
+    int rc = launch_kkt_condensed(S, P, KktForm::PerRollout, true, nullptr, S.nb_launch, nullptr, s);      // P0
     if (rc != CIMPC_OK) return rc;
     constexpr int CORRECTIONS = 4;
     for (int k = 0; k <= CORRECTIONS; ++k) {
@@ -236,11 +258,11 @@ int launch_kkt_mixed(const NewtonDev& S, const KktArgs& K0, double* ws, int* n_f
         hipLaunchKernelGGL(kkt_mixed_check_kernel, dim3(S.nb_launch), dim3(256), 0, s, S, K0, M);       // Ck
         if (k == CORRECTIONS) break;
         KktArgs Pk = P; Pk.r = res; Pk.delta = corr;
-        rc = launch_kkt_any(S, Pk, s, true);                                  // P(k+1)
+        rc = launch_kkt_condensed(S, Pk, KktForm::PerRollout, true, nullptr, S.nb_launch, nullptr, s);     // P(k+1)
         if (rc != CIMPC_OK) return rc;
     }
     KktArgs F = K0; F.only_flag = flag;                                        // fp64 fallback (keeps K0.finish)
-    rc = launch_kkt_any(S, F, s, false);
+    rc = launch_kkt_condensed(S, F, KktForm::PerRollout, false, nullptr, S.nb_launch, nullptr, s);
     if (rc != CIMPC_OK) return rc;
     return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
 }
@@ -490,13 +512,16 @@ int launch_dz_commit(const NewtonDev& S, hipStream_t s) {
     hipLaunchKernelGGL(dz_commit_kernel, dim3(S.dm.B, S.dm.H), dim3(256), 0, s, S);
     return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
 }
-bool kkt_lazy_commit_available(const NewtonDev& S) {      // every KKT stage of the Newton loop runs kkt_body on fp64 tiles (launch_kkt_packed / launch_kkt_t)
+bool kkt_mfma_available(const NewtonDev& S) {      // the bounds of launch_kkt_t's KktForm::PerRollout
     const int nq = S.dm.nq, nu = S.dm.nu;
-    if (S.dm.mode != CIMPC_MODE_CONFIGURATION || S.kkt_list == nullptr || nq > 24 || nu > 24 || S.dm.H > 96 || S.dm.H > 128 || S.kkt_scalar != 0) return false;
+    if (S.dm.mode != CIMPC_MODE_CONFIGURATION || nq > 24 || nu > 24) return false;
 #define X(q, u) if (nq == q && nu == u) return S.dm.H <= kkt_max_h<q, u>();
     CIMPC_NQNU(X)
 #undef X
     return false;
+}
+bool kkt_packed_available(const NewtonDev& S) {    // the compact-list kernels (launch_kkt_list_t)
+    return S.dm.mode == CIMPC_MODE_CONFIGURATION && S.kkt_list != nullptr && S.dm.nq <= 24 && S.dm.nu <= 24 && S.dm.H <= 96 && kkt_condensed_available(S);
 }
 int launch_solve_finish(const NewtonDev& S, double* out, hipStream_t s) {
     hipLaunchKernelGGL(solve_finish_kernel, dim3(1), dim3(256), 0, s, S, out);
@@ -517,58 +542,6 @@ int launch_resid_decide(const NewtonDev& S, hipStream_t s, int n_slots, int phas
 #undef X
     return launch_resid_t<0, 0>(S, s, n_slots, phase);        // runtime dimensions (models without a compiled set)
 }
-template <int NQ, int NU>
-static int launch_kkt_packed_t(const NewtonDev& S, const KktArgs& K, const int* list, int n, const int* n_dev, hipStream_t s, int pipe) {
-    if constexpr (NQ <= 24 && NU <= 24) {
-        constexpr int PACK = kkt_pack<NQ, NU>();
-        const size_t lds = (size_t)PACK * kkt_lds_doubles<NQ, NU, 1>() * sizeof(double);
-        static LdsOptIn optin;
-        if (lds_opt_in(optin, (const void*)kkt_kernel_packed<NQ, NU>, lds) != CIMPC_OK) return CIMPC_ERR_HIP;
-        // `pipe` (host schedule, CIMPC_KKT_PIPE): where the KKT solve is on the critical path (small batches, chained rounds).
-        // Next to a busy sweep the pipelined kernel takes twice the CUs for half the time - measured neutral - so the
-        // packed one-wave kernel stays there.
-        if (pipe == 3) {      // duo: one workgroup of two one-wave chains per rollout (16-wide tiles)
-            if constexpr (kkt_tld<NQ, NU>() == 16) {
-                const size_t ldsd = (size_t)(kkt_duo_slice_doubles(1) + kkt_duo_slice_doubles(2)) * sizeof(double);
-                static LdsOptIn optind;
-                if (lds_opt_in(optind, (const void*)kkt_kernel_duo<NQ, NU>, ldsd) != CIMPC_OK) return CIMPC_ERR_HIP;
-                hipLaunchKernelGGL((kkt_kernel_duo<NQ, NU>), dim3(n), dim3(128), ldsd, s, KktTwArgs{S, K, list, n, n_dev});
-                return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
-            } else return CIMPC_ERR_INVALID;
-        }
-        if (pipe == 2) {      // twisted: two workgroups of three wavefronts per rollout, one chain from either end
-            const size_t lds3 = (size_t)kkt_tw_lds_doubles<NQ, NU>() * sizeof(double);
-            static LdsOptIn optin3;
-            if (lds_opt_in(optin3, (const void*)kkt_kernel_twisted<NQ, NU>, lds3) != CIMPC_OK) return CIMPC_ERR_HIP;
-            hipLaunchKernelGGL((kkt_kernel_twisted<NQ, NU>), dim3(2 * n), dim3(192), lds3, s, KktTwArgs{S, K, list, n, n_dev});
-            return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
-        }
-        if (pipe) {      // three wavefronts per rollout, software-pipelined forward recursion
-            const size_t lds2 = (size_t)kkt_lds_doubles<NQ, NU, 3>() * sizeof(double);
-            static LdsOptIn optin2;
-            if (lds_opt_in(optin2, (const void*)kkt_kernel_pipe<NQ, NU>, lds2) != CIMPC_OK) return CIMPC_ERR_HIP;
-            hipLaunchKernelGGL((kkt_kernel_pipe<NQ, NU>), dim3(n), dim3(192), lds2, s, S, K, list, n, n_dev);
-            return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
-        }
-        hipLaunchKernelGGL((kkt_kernel_packed<NQ, NU>), dim3((n + PACK - 1) / PACK), dim3(64 * PACK), lds, s, S, K, list, n, n_dev);
-        return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
-    }
-    return CIMPC_ERR_INVALID;
-}
-int launch_kkt_packed(const NewtonDev& S, int n_kkt, int list_par, hipStream_t s, const int* n_dev, int pipe) {
-    const int latency = pipe >= 0 ? pipe : (S.kkt_same_round == 1 ? 1 : 0);
-    const int nq = S.dm.nq, nu = S.dm.nu;
-    if (n_dev != nullptr) n_kkt = S.dm.B;      // upper bound of the grid; surplus workgroups leave at once
-    if (n_kkt <= 0) return CIMPC_OK;
-    const bool force_scalar = S.kkt_scalar != 0;
-    if (S.kkt_list == nullptr || S.dm.mode != CIMPC_MODE_CONFIGURATION || nq > 24 || nu > 24 || S.dm.H > 96 || force_scalar) return launch_kkt(S, s);
-    const KktArgs K{S.res, S.delta, S.beta, 0.0, S.stage, 1};
-    const int* list = S.kkt_list + (size_t)list_par * S.dm.B;
-#define X(q, u) if (nq == q && nu == u) return launch_kkt_packed_t<q, u>(S, K, list, n_kkt, n_dev, s, latency);
-    CIMPC_NQNU(X)
-#undef X
-    return launch_kkt(S, s);
-}
 // ---------------------------------------------------------------------------------------------------------
 // :configurationforce mode through the :configuration solvers.  In cf mode the contact impulses (gamma_i, b_i) are extra
 // primal variables (newton_residual.jl:18-54) that appear in exactly two places: their own rows of the dynamics
@@ -581,6 +554,7 @@ int launch_kkt_packed(const NewtonDev& S, int n_kkt, int list_par, hipStream_t s
 // the right-hand side  r_x + S^T r_y  - solved by the condensed MFMA kernel or, with a velocity objective, the banded
 // LDL^T - followed by the two formulas above.  (General weights keep the dense LU of the reference.)
 // ---------------------------------------------------------------------------------------------------------
+struct CfReduce { double* dzq; double* r2; double* d2; };   // packed q rows of the sensitivities, reduced rhs, reduced solution
 __global__ __launch_bounds__(256) void cf_reduce_pre_kernel(NewtonDev S, KktArgs K, CfReduce W) {
     const int b = blockIdx.x + S.b0, tid = threadIdx.x, nt = blockDim.x;
     if (K.stage != nullptr && K.stage[b] != STAGE_KKT) return;
@@ -687,46 +661,29 @@ NewtonDev cf_shadow(const NewtonDev& S) {          // the :configuration-mode pr
 size_t cf_reduce_doubles(const NewtonDev& S) {
     return (size_t)S.dm.B * ((size_t)S.dm.H * S.nths * S.dm.nq + 2 * (size_t)S.dm.H * (S.dm.nu + 2 * S.dm.nq));
 }
-int launch_kkt_cf_reduced(const NewtonDev& S, const KktArgs& K, double* ws, double* dense_ws, hipStream_t s) {
+// f: the banded LDL^T's form (banded), else PerRollout: kkt_kernel on the reduced problem, kkt_kernel_scalar beyond its bounds
+static int launch_kkt_cf_reduced(const NewtonDev& S, const KktArgs& K, bool banded, KktForm f, const KktWorkspace& W, hipStream_t s) {
     const size_t B = S.dm.B, n_dz = (size_t)S.dm.H * S.nths * S.dm.nq, N2 = (size_t)S.dm.H * (S.dm.nu + 2 * S.dm.nq);
-    CfReduce W{ws, ws + B * n_dz, ws + B * n_dz + B * N2};
-    hipLaunchKernelGGL(cf_reduce_pre_kernel, dim3(S.nb_launch), dim3(256), 0, s, S, K, W);
+    CfReduce R{W.cf, W.cf + B * n_dz, W.cf + B * n_dz + B * N2};
+    hipLaunchKernelGGL(cf_reduce_pre_kernel, dim3(S.nb_launch), dim3(256), 0, s, S, K, R);
     const NewtonDev S2 = cf_shadow(S);
-    const KktArgs K2{W.r2, W.d2, K.beta, K.beta_scalar, K.stage, 0, W.dzq};
-    const int rc = S.V != nullptr ? launch_kkt_dense_args(S2, K2, dense_ws, s, true) : launch_kkt_any(S2, K2, s);
+    const KktArgs K2{R.r2, R.d2, K.beta, K.beta_scalar, K.stage, 0, R.dzq};
+    const KktForm f2 = kkt_mfma_available(S2) ? KktForm::PerRollout : KktForm::Scalar;
+    const int rc = banded ? launch_kkt_dense(S2, K2, f, W.dense, s) : launch_kkt_condensed(S2, K2, f2, false, nullptr, S.nb_launch, nullptr, s);
     if (rc != CIMPC_OK) return rc;
-    hipLaunchKernelGGL(cf_reduce_post_kernel, dim3(S.nb_launch), dim3(256), 0, s, S, K, W);
+    hipLaunchKernelGGL(cf_reduce_post_kernel, dim3(S.nb_launch), dim3(256), 0, s, S, K, R);
     return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
 }
-int launch_kkt_cf_reduced_newton(const NewtonDev& S, double* ws, double* dense_ws, hipStream_t s) {
-    const KktArgs K{S.res, S.delta, S.beta, 0.0, S.stage, 1};
-    return launch_kkt_cf_reduced(S, K, ws, dense_ws, s);
-}
-int launch_kkt_cf_reduced_raw(const NewtonDev& S, const double* r_dev, double beta, double* delta_dev, double* ws, double* dense_ws, hipStream_t s) {
-    const KktArgs K{r_dev, delta_dev, nullptr, beta, nullptr, 0};
-    return launch_kkt_cf_reduced(S, K, ws, dense_ws, s);
-}
 bool kkt_cf_reduce_available(const NewtonDev& S) {   // the reduced problem must have a :configuration-mode solver
-    if (S.dm.mode != CIMPC_MODE_CONFIGURATIONFORCE) return false;
-    const NewtonDev S2 = cf_shadow(S);
-    if (S.V != nullptr) return kkt_banded_available(S2);
-    const int nq = S.dm.nq, nu = S.dm.nu;
-#define X(q, u) if (nq == q && nu == u) return true;
-    CIMPC_NQNU(X)
-#undef X
-    return false;
+    return S.dm.mode == CIMPC_MODE_CONFIGURATIONFORCE && (S.V != nullptr ? kkt_banded_available(cf_shadow(S)) : kkt_condensed_available(S));
 }
 
-bool kkt_twisted_available(const NewtonDev& S) {      // MFMA tiles, a horizon long enough for two chains, the backward staging
-    if (S.dm.mode != CIMPC_MODE_CONFIGURATION || S.kkt_list == nullptr || S.kkt_scalar != 0 || S.kkt_tw_xch == nullptr) return false;
-    if (S.dm.nq > 24 || S.dm.nu > 24 || S.dm.H < KKT_TW_MIN_H || S.dm.H > 96) return false;
-    return kkt_condensed_available(S);
+bool kkt_twisted_available(const NewtonDev& S) {      // a compact-list kernel, a horizon long enough for two chains, the exchange blocks
+    return kkt_packed_available(S) && S.dm.H >= KKT_TW_MIN_H && S.kkt_tw_xch != nullptr;
 }
-
 bool kkt_duo_available(const NewtonDev& S) {      // the twisted solve's conditions on 16-wide tiles
     return S.dm.nq <= 16 && S.dm.nu <= 16 && kkt_twisted_available(S);
 }
-
 bool kkt_condensed_available(const NewtonDev& S) {      // a compiled condensed solve exists for these (nq, nu)
     const int nq = S.dm.nq, nu = S.dm.nu;
 #define X(q, u) if (nq == q && nu == u) return true;
@@ -734,46 +691,19 @@ bool kkt_condensed_available(const NewtonDev& S) {      // a compiled condensed 
 #undef X
     return false;
 }
-int launch_kkt(const NewtonDev& S, hipStream_t s) {
-    KktArgs K{S.res, S.delta, S.beta, 0.0, S.stage, 1};
-    return launch_kkt_any(S, K, s);
-}
-int launch_kkt_mixed_newton(const NewtonDev& S, double* ws, int* n_fallback, hipStream_t s) {
-    const KktArgs K{S.res, S.delta, S.beta, 0.0, S.stage, 1};
-    return launch_kkt_mixed(S, K, ws, n_fallback, s);
-}
-int launch_kkt_mixed_raw(const NewtonDev& S, const double* r_dev, double beta, double* delta_dev, double* ws, int* n_fallback, hipStream_t s) {
-    const KktArgs K{r_dev, delta_dev, nullptr, beta, nullptr, 0};
-    return launch_kkt_mixed(S, K, ws, n_fallback, s);
-}
-template <int NQ, int NU>
-static int launch_kkt_twisted_t(const NewtonDev& S, const KktArgs& K, hipStream_t s) {
-    if constexpr (NQ <= 24 && NU <= 24) {
-        const size_t lds = (size_t)kkt_tw_lds_doubles<NQ, NU>() * sizeof(double);
-        static LdsOptIn optin;
-        if (lds_opt_in(optin, (const void*)kkt_kernel_twisted<NQ, NU>, lds) != CIMPC_OK) return CIMPC_ERR_HIP;
-        hipLaunchKernelGGL((kkt_kernel_twisted<NQ, NU>), dim3(2 * S.nb_launch), dim3(192), lds, s, KktTwArgs{S, K, nullptr, S.nb_launch, nullptr});
-        return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
+
+int launch_kkt_stage(const NewtonDev& S, const KktArgs& K, KktBackend be, KktForm f, const int* list, int n, const int* n_dev,
+                     const KktWorkspace& W, hipStream_t s) {
+    const bool banded = f == KktForm::BandedOneEnded || f == KktForm::BandedTwisted;
+    switch (be) {
+    case KktBackend::Condensed: return launch_kkt_condensed(S, K, f, false, list, n, n_dev, s);
+    case KktBackend::CondensedMixed: return f == KktForm::PerRollout ? launch_kkt_mixed(S, K, W.mix, W.mix_nfb, s) : CIMPC_ERR_INVALID;
+    case KktBackend::Banded: return banded ? launch_kkt_dense(S, K, f, W.dense, s) : CIMPC_ERR_INVALID;
+    case KktBackend::DenseLu: return f == KktForm::Dense ? launch_kkt_dense(S, K, f, W.dense, s) : CIMPC_ERR_INVALID;
+    case KktBackend::CfCondensed: return f == KktForm::PerRollout ? launch_kkt_cf_reduced(S, K, false, f, W, s) : CIMPC_ERR_INVALID;
+    case KktBackend::CfBanded: return banded ? launch_kkt_cf_reduced(S, K, true, f, W, s) : CIMPC_ERR_INVALID;
     }
     return CIMPC_ERR_INVALID;
-}
-int launch_kkt_raw(const NewtonDev& S, const double* r_dev, double beta, double* delta_dev,
-                   hipStream_t s) {
-    KktArgs K{r_dev, delta_dev, nullptr, beta, nullptr, 0};
-    if (S.kkt_tw_raw == 2 && kkt_duo_available(S)) {      // (CIMPC_KKT_DUO=2: the duo kernel at the B1 seam too - the parity tests reach it in isolation here)
-        const int nq = S.dm.nq, nu = S.dm.nu;
-        const int* list = nullptr;
-#define X(q, u) if (nq == q && nu == u) return launch_kkt_packed_t<q, u>(S, K, list, S.nb_launch, nullptr, s, 3);
-        CIMPC_NQNU(X)
-#undef X
-    }
-    if (S.kkt_tw_raw != 0 && kkt_twisted_available(S)) {      // a lone solve is latency-bound: two chains from either end
-        const int nq = S.dm.nq, nu = S.dm.nu;
-#define X(q, u) if (nq == q && nu == u) return launch_kkt_twisted_t<q, u>(S, K, s);
-        CIMPC_NQNU(X)
-#undef X
-    }
-    return launch_kkt_any(S, K, s);
 }
 
 }  // namespace cimpc

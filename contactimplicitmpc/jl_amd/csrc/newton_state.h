@@ -4,6 +4,7 @@
 // leading rollout dimension B.
 #pragma once
 #include "cimpc_internal.h"
+#include "kkt_plan.h"
 
 namespace cimpc {
 constexpr int NLOG = 16;       // Newton iterations kept per rollout in the status log
@@ -24,9 +25,7 @@ struct NewtonDev {
     cimpc_dims dm;
     int b0;            // first rollout served by this launch (sub-batch offset)
     int nb_launch;     // rollouts served by this launch
-    int kkt_same_round; // 1: KKT runs before the sweep on the same stream (small batches); 2: chained round - KKT next to the first sweep,
-                        //    its candidates are evaluated by the round's second sweep (queue par ^ 1)
-    int kkt_scalar;     // 1: the non-MFMA condensed kernel everywhere (CIMPC_KKT_SCALAR, diagnostic)
+    int kkt_same_round; // 1: KKT runs before the sweep on the same stream (small batches); 0: next to the sweep (its candidates join the next round)
     int nd, nr, nth, nths, N;
     TrajDev traj, cand, ref;   // cand: [B*CS] evaluation slots; traj, ref: [B]
     double* nu;        // [B][H][nd]
@@ -106,8 +105,6 @@ struct NewtonDev {
     int kkt_tw_spins;
     int* kkt_tw_fail;  // host-mapped counter of timed-out hand-overs (null: not counted)
     int kkt_tw_nb;     // rows the bottom chain eliminates (0: kkt_tw_split's default; CIMPC_KKT_TW_NB)
-    int kkt_tw_raw;    // 1: the B1 seam (cimpc_kkt_solve: a lone solve, latency-bound) takes the twisted kernel too
-    int kkt_tw_band;   // 1: the banded LDL^T takes its twisted form (two workgroups per rollout) where it is available (kkt_dense.hip)
     // options
     double r_tol, beta_init, kappa;
     int max_iter;
@@ -132,42 +129,45 @@ struct GaitDev {
 int launch_gait_window(const NewtonDev& S, const GaitDev& G, int* window, int advance, hipStream_t s);
 int launch_reset(const NewtonDev& nd, const double* q0, const double* q1, int warm, hipStream_t s);
 int launch_dz_commit(const NewtonDev& nd, hipStream_t s);      // flush of the lazily committed sensitivities (no-op without good_src)
-bool kkt_lazy_commit_available(const NewtonDev& nd);            // every KKT stage of these dimensions runs kkt_body (fp64 tiles)
 int launch_dz_rekey(const NewtonDev& nd, double* knot, const int* window, int which, int dir, hipStream_t s);
 int launch_resid_decide(const NewtonDev& nd, hipStream_t s, int n_slots = -1, int phase = 0);   // n_slots: entries of slot_list[WQ.par] (-1: every (rollout, slot) pair gets a block)
 int launch_enqueue_all(const NewtonDev& nd, hipStream_t s);   // B3 seam: queue slot 0 of every rollout
-int launch_kkt(const NewtonDev& nd, hipStream_t s);
-bool kkt_condensed_available(const NewtonDev& nd);
-// mixed precision: block products on the fp32 MFMA, fp64 matrix-free refinement, fp64 fallback (newton_kernels.hip)
-bool kkt_mixed_available(const NewtonDev& nd);
-size_t kkt_mixed_workspace_doubles(const NewtonDev& nd);
-int launch_kkt_mixed_newton(const NewtonDev& nd, double* ws, int* n_fallback, hipStream_t s);
-int launch_kkt_mixed_raw(const NewtonDev& nd, const double* r_dev, double beta, double* delta_dev, double* ws, int* n_fallback, hipStream_t s);
-// packed variant: n_kkt rollouts from kkt_list[list_par], KKT_PACK per workgroup (dedicates whole CUs to the recursion)
-// (pipe: 0 packed one-wave kernel, 1 three-wave pipeline, 2 twisted = two three-wave chains per rollout, 3 duo = two one-wave chains in one
-//  workgroup, -1 by kkt_same_round)
-int launch_kkt_packed(const NewtonDev& nd, int n_kkt, int list_par, hipStream_t s, const int* n_dev = nullptr, int pipe = -1);
+// KKT stage (kkt_plan.h chooses the backend and the form; launch_kkt_stage launches exactly that)
+struct KktArgs {
+    const double* r;     // [B][N] right-hand side
+    double* delta;       // [B][N]
+    const double* beta;  // [B] or null (then beta_scalar)
+    double beta_scalar;
+    const int* stage;    // only rollouts with stage == STAGE_KKT (null = all)
+    int finish;          // 1: set alpha/ls_iter/cand/stage after the solve (newton loop)
+    const double* dz_override;   // [B][H][nths][nd] sensitivities to use instead of S.dz_good / S.dz (cf-mode reduction)
+    const int* only_flag;        // [B] or null: run only the rollouts whose flag is non-zero (mixed-precision refinement / fallback)
+};
+inline KktArgs kkt_newton_args(const NewtonDev& S) { return KktArgs{S.res, S.delta, S.beta, 0.0, S.stage, 1, nullptr, nullptr}; }
+inline KktArgs kkt_raw_args(const double* r, double beta, double* delta) { return KktArgs{r, delta, nullptr, beta, nullptr, 0, nullptr, nullptr}; }   // B1 seam
+// sized by kkt_dense_workspace_doubles, cf_reduce_doubles, kkt_mixed_workspace_doubles; the mixed sequence's fp64 fallback counter
+struct KktWorkspace { double* dense; double* cf; double* mix; int* mix_nfb; };
+// list / n / n_dev: the compact-list forms (n_dev: count read on the device, grid over B); Twisted / Duo with list == null: every
+// rollout.  A form the backend or the compiled (nq, nu) cannot serve returns CIMPC_ERR_INVALID (a planner bug).
+int launch_kkt_stage(const NewtonDev& S, const KktArgs& K, KktBackend be, KktForm f, const int* list, int n, const int* n_dev,
+                     const KktWorkspace& W, hipStream_t s);
+// facts of KktCaps (called where the caps are filled)
+bool kkt_condensed_available(const NewtonDev& nd);      // a compiled condensed solve exists for these (nq, nu)
+bool kkt_mfma_available(const NewtonDev& nd);           // ... with the MFMA per-rollout kernel (else kkt_kernel_scalar)
+bool kkt_packed_available(const NewtonDev& nd);         // ... and the compact-list kernels
 bool kkt_twisted_available(const NewtonDev& nd);
-bool kkt_duo_available(const NewtonDev& nd);      // ... as one workgroup of two one-wave chains (pipe = 3): next to the sweep
-int launch_queue_recycle(const IpQueues& Q, int par, hipStream_t s);
-int launch_solve_finish(const NewtonDev& nd, double* out, hipStream_t s);   // end-of-solve result block, see solve_finish_kernel
-// reference-default backend (dense jacobian! + LU with partial pivoting), any mode / objective (kkt_dense.hip)
-size_t kkt_dense_workspace_doubles(const NewtonDev& S, bool banded);
-int launch_kkt_dense_newton(const NewtonDev& S, double* ws, hipStream_t s, bool banded);
-struct KktArgs;
-int launch_kkt_dense_args(const NewtonDev& S, const KktArgs& K, double* ws, hipStream_t s, bool banded);
-// :configurationforce mode reduced to the :configuration solvers (newton_kernels.hip)
-struct CfReduce { double* dzq; double* r2; double* d2; };   // packed q rows of the sensitivities, reduced rhs, reduced solution
-NewtonDev cf_shadow(const NewtonDev& S);
-size_t cf_reduce_doubles(const NewtonDev& S);
-bool kkt_cf_reduce_available(const NewtonDev& S);
-int launch_kkt_cf_reduced_newton(const NewtonDev& S, double* ws, double* dense_ws, hipStream_t s);
-int launch_kkt_cf_reduced_raw(const NewtonDev& S, const double* r_dev, double beta, double* delta_dev, double* ws, double* dense_ws, hipStream_t s);
+bool kkt_duo_available(const NewtonDev& nd);            // ... as one workgroup of two one-wave chains
+bool kkt_mixed_available(const NewtonDev& nd);
 bool kkt_banded_available(const NewtonDev& S);
 bool kkt_banded_twisted_available(const NewtonDev& S);
-int launch_kkt_dense_raw(const NewtonDev& S, const double* r_dev, double beta, double* delta_dev, double* ws, hipStream_t s, bool banded);
-// B1 seam: solve with caller-provided residual / beta for all rollouts, no state change
-int launch_kkt_raw(const NewtonDev& nd, const double* r_dev, double beta, double* delta_dev,
-                   hipStream_t s);
+bool kkt_cf_reduce_available(const NewtonDev& S);
+size_t kkt_mixed_workspace_doubles(const NewtonDev& nd);
+size_t kkt_dense_workspace_doubles(const NewtonDev& S, bool banded);
+size_t cf_reduce_doubles(const NewtonDev& S);
+NewtonDev cf_shadow(const NewtonDev& S);      // the :configuration-mode problem the cf-mode reduction solves
+int launch_queue_recycle(const IpQueues& Q, int par, hipStream_t s);
+int launch_solve_finish(const NewtonDev& nd, double* out, hipStream_t s);   // end-of-solve result block, see solve_finish_kernel
+// banded LDL^T / dense LU of kkt_dense.hip (form: BandedOneEnded, BandedTwisted or Dense)
+int launch_kkt_dense(const NewtonDev& S, const KktArgs& K, KktForm f, double* ws, hipStream_t s);
 
 }  // namespace cimpc

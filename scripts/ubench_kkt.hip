@@ -24,9 +24,9 @@ int main() {
         hipMemcpy(d_Qi, Qi.data(), Qi.size() * 8, hipMemcpyHostToDevice); hipMemcpy(d_Ri, Ri.data(), Ri.size() * 8, hipMemcpyHostToDevice);
         S.dz = d_dz; S.Qinv = d_Qi; S.Rinv = d_Ri; S.kkt_ws = d_ws; S.stats = d_stats; S.b0 = 0; S.nb_launch = B;
         hipEvent_t a, b; hipEventCreate(&a); hipEventCreate(&b);
-        launch_kkt_raw(S, d_r, 10.0, d_delta, 0); hipDeviceSynchronize();
+        launch_kkt_stage(S, kkt_raw_args(d_r, 10.0, d_delta), KktBackend::Condensed, KktForm::PerRollout, nullptr, B, nullptr, KktWorkspace{}, 0); hipDeviceSynchronize();
         hipEventRecord(a);
-        for (int rep = 0; rep < 10; ++rep) launch_kkt_raw(S, d_r, 10.0, d_delta, 0);
+        for (int rep = 0; rep < 10; ++rep) launch_kkt_stage(S, kkt_raw_args(d_r, 10.0, d_delta), KktBackend::Condensed, KktForm::PerRollout, nullptr, B, nullptr, KktWorkspace{}, 0);
         hipEventRecord(b); hipDeviceSynchronize();
         float ms; hipEventElapsedTime(&ms, a, b);
         long long pt[32]; hipMemcpy(pt, d_stats, sizeof(pt), hipMemcpyDeviceToHost);
