@@ -15,6 +15,7 @@
 #include "cimpc_internal.h"
 #include "lin_table.h"
 #include "newton_state.h"
+#include "schedule_plan.h"
 
 using namespace cimpc;
 
@@ -40,62 +41,34 @@ struct RoundStreams {
     hipEvent_t ev_start = nullptr;  // the caller's stream at the start of a solve (uploads of q0 / q1 precede the reset kernel)
 };
 
-// Schedule settings.  The defaults are the measured optima.  A dozen of them keep an environment
-// override for the A/B scripts under scripts/ (read ONCE, in cimpc_create: a handle's configuration never changes
-// afterwards and no solve-path call touches the environment); the rest are constants of the build - their overrides were
-// removed in round 3, every one an untested configuration (the experiments they served are recorded in DESIGN.md).
+// Settings with an environment override for the A/B scripts under scripts/, read ONCE in cimpc_create (no solve-path call touches the
+// environment).  The defaults are the measured optima; the rules that use them are in schedule_plan.h and kkt_plan.h.
 struct Knobs {
-    // ---- with an override ----
-    int async_mode = 2;          // CIMPC_ASYNC: 0 lock-step rounds only, 1 always the single launch, 2 auto
-    int async_tail = -1;         // CIMPC_ASYNC_TAIL: hybrid hand-over threshold (-1: by batch size)
-    int spec_first = -1;         // CIMPC_SPEC_FIRST: step lengths of the first line-search round of a solve's first Newton iteration (-1: by batch size)
-    int iter_cap = 28;           // CIMPC_ITER_CAP (B = 512: 20 / 24 / 28 / 32 -> 8.73 / 8.65 / 8.74 / 8.56 ms, inside the spread: profiles/r03/knobs3.log)
+    SchedulePolicy sched{};      // CIMPC_ASYNC, _ASYNC_TAIL, _ASYNC_FULL_MAX, _SPEC_FIRST, _ITER_CAP, _TAIL_DIV, _DRAIN_PCT, _DRAIN_MIN, _SWEEP_WGS, _WAVES32
     bool async_debug = false;    // CIMPC_ASYNC_DEBUG
     double watchdog_s = 30.0;    // CIMPC_ASYNC_WATCHDOG_S
     bool debug_rounds = false;   // CIMPC_DEBUG_ROUNDS
-    int tail_div = 8;            // CIMPC_TAIL_DIV
-    int drain_pct = 95;          // CIMPC_DRAIN_PCT: drain parking once this percentage of the sweep's workgroups has left (0 = off; B = 512: 0 / 75 / 90 / 95 / 97 -> 10.68 / 10.97 / 10.48 / 10.45 / 10.47 ms)
-    int drain_min = 4;           // CIMPC_DRAIN_MIN: ... for solves that have had at least this many iterations in the launch
-    int async_full_max = 32;     // CIMPC_ASYNC_FULL_MAX: largest batch solved by the single persistent launch alone (larger: hybrid).
-                                 // Measured 128 -> 64 (round 3): B = 96 8.88 -> 8.11 ms, B = 128 9.72 -> 9.48 ms, B = 64 unchanged (6.9 ms); 64 -> 32 (round 6,
-                                 // after the rounds' sweep and KKT stage got faster): B = 64 5.0-5.7 -> 4.35-4.4 ms, B = 48 4.54 -> 4.07 ms with the hand-over at 32
     bool generic_static = false; // CIMPC_GENERIC_STATIC: runtime-dimension sweep with the static queue partition of rounds 2-3 instead of the dynamic pull
     KktPolicy kkt{};             // CIMPC_KKT_PIPE, _TWISTED, _DUO, _DUO_HINT, CIMPC_LAZY_DZ, CIMPC_ASYNC_KKT_TW and the KKT kernels' bounds (kkt_plan.h)
     int kkt_tw_nb = 0;           // CIMPC_KKT_TW_NB: rows eliminated from the bottom (0: the default split)
     int kkt_tw_spins = 0;        // bound of a chain's wait for its partner, in polls (0: 2^21); the tests force the time-out path through cimpc_debug_set_tw_spins
-    // ---- constants ----
-    int async_mem = 0;           // exchange buffers: ordinary device memory (uncached / fine-grained variants lost)
-    int spec_all = -1;           // speculative slots of later line-search rounds: by batch size
-    int spec_tail = 3;
-    int spec_mid = -1;           // previous search depth from which a rollout starts with three candidates: by batch size
-    int waves = 0;               // sweep workgroup size: by batch size
-    int kkt_overlap = -1;        // KKT on its own stream next to the sweep: from 64 rollouts on
-    int waves32 = 0;             // CIMPC_WAVES32: waves per sweep workgroup of the 32-lane models (0: by batch size; 4 = latency build, 8 = throughput build)
     int banded_form = 0;         // CIMPC_BANDED_FORM: banded LDL^T variants the sizes in the tree never reach - bit 0: four pivots per block, bit 1: window
                                  // of w + RB slots instead of the next power of two, bit 2: controls not eliminated (the form a singular R_t
                                  // falls back to) - tests/test_gpu_round4.py runs every form against form 0
-    int sweep_wgs = 0;           // CIMPC_SWEEP_WGS: persistent sweep workgroups (0: computed from the resident set) - sub-batch experiments
-    int async_service = 0;       // job-only workgroups of the asynchronous kernel: computed
-    int async_flags = 0;         // reserved
-    int async_sleep = 2;         // idle back-off of the asynchronous kernel (units of ~2 us), polls before looking around, wake-up fan
-    int async_spins = 48;
-    int async_fan = 1;
-    int async_tail_grid = -1;    // workgroups of the hybrid tail's persistent kernel: 3 per rollout handed over (B = 512: 512 / 320 / 256 / 192 / 96
-                                 // workgroups -> 10.85 / 10.42 / 10.35 / 10.38 / 10.6 ms)
 
     static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
     void read_environment() {
-        async_mode = env_int("CIMPC_ASYNC", async_mode);
-        async_tail = env_int("CIMPC_ASYNC_TAIL", async_tail);
-        spec_first = env_int("CIMPC_SPEC_FIRST", spec_first);
-        iter_cap = std::max(1, env_int("CIMPC_ITER_CAP", iter_cap));
+        sched.async_mode = env_int("CIMPC_ASYNC", sched.async_mode);
+        sched.async_tail = env_int("CIMPC_ASYNC_TAIL", sched.async_tail);
+        sched.spec_first = env_int("CIMPC_SPEC_FIRST", sched.spec_first);
+        sched.iter_cap = std::max(1, env_int("CIMPC_ITER_CAP", sched.iter_cap));
         async_debug = getenv("CIMPC_ASYNC_DEBUG") != nullptr;
         if (const char* v = getenv("CIMPC_ASYNC_WATCHDOG_S")) watchdog_s = atof(v);
         debug_rounds = getenv("CIMPC_DEBUG_ROUNDS") != nullptr;
-        tail_div = env_int("CIMPC_TAIL_DIV", tail_div);
-        async_full_max = env_int("CIMPC_ASYNC_FULL_MAX", async_full_max);
-        drain_pct = env_int("CIMPC_DRAIN_PCT", drain_pct);
-        drain_min = std::max(1, env_int("CIMPC_DRAIN_MIN", drain_min));
+        sched.tail_div = env_int("CIMPC_TAIL_DIV", sched.tail_div);
+        sched.async_full_max = env_int("CIMPC_ASYNC_FULL_MAX", sched.async_full_max);
+        sched.drain_pct = env_int("CIMPC_DRAIN_PCT", sched.drain_pct);
+        sched.drain_min = std::max(1, env_int("CIMPC_DRAIN_MIN", sched.drain_min));
         kkt.kkt_pipe = env_int("CIMPC_KKT_PIPE", kkt.kkt_pipe);
         kkt.kkt_twisted = env_int("CIMPC_KKT_TWISTED", kkt.kkt_twisted);
         kkt_tw_nb = env_int("CIMPC_KKT_TW_NB", kkt_tw_nb);
@@ -104,8 +77,8 @@ struct Knobs {
         kkt.kkt_duo_hint = env_int("CIMPC_KKT_DUO_HINT", kkt.kkt_duo_hint);
         kkt.async_kkt_tw = env_int("CIMPC_ASYNC_KKT_TW", kkt.async_kkt_tw);
         generic_static = env_int("CIMPC_GENERIC_STATIC", generic_static ? 1 : 0) != 0;
-        sweep_wgs = env_int("CIMPC_SWEEP_WGS", sweep_wgs);
-        waves32 = env_int("CIMPC_WAVES32", waves32);
+        sched.sweep_wgs = env_int("CIMPC_SWEEP_WGS", sched.sweep_wgs);
+        sched.waves32 = env_int("CIMPC_WAVES32", sched.waves32);
         banded_form = env_int("CIMPC_BANDED_FORM", banded_form);
     }
 };
@@ -133,7 +106,6 @@ struct cimpc_ctx {
     int dz_producer = 0;            // who wrote the per-step sensitivity memory last: 0 nobody, 1 newton_solve (dz_good), 2 implicit_dynamics (slot 0)
     int* d_good_src = nullptr;      // [B][H] NewtonDev::good_src (in use where kkt_lazy_commit holds: set_kkt_backend)
     double* d_dz_knot = nullptr;    // [B][H_ref][nths*nd] per-knot archive, allocated at the first window change that needs it
-    int wpk = 1;                 // persistent workgroups of a sweep launch
     double* d_alt = nullptr;
     double* d_zout = nullptr;
     double *d_Q = nullptr, *d_R = nullptr, *d_Qinv = nullptr, *d_Rinv = nullptr, *d_Cg = nullptr,
@@ -149,7 +121,6 @@ struct cimpc_ctx {
     double* d_rhs = nullptr;   // B1 seam staging
     double* d_pstate = nullptr;   // parked interior-point iterates
     long long ip_budget_ticks = 0;  // cimpc_ip_opts::max_time in ticks of the device's constant-rate clock (0 = unlimited)
-    int iter_cap = 28;            // (Knobs::iter_cap) measured B = 512: 16 / 20 / 24 / 32 / 48 -> 13.57 / 12.73 / 12.85 / 12.97 / 14.41 ms per batch step
     NewtonDev S{};
     int* h_counters = nullptr;   // pinned
     // bookkeeping
@@ -160,7 +131,6 @@ struct cimpc_ctx {
     KktPolicy kp{};
     KktCaps kc{};
     KktBackend kb = KktBackend::Condensed;
-    long long adapt32 = 0;         // 32-lane models: problems per sweep launch from which the throughput build is taken (0: the handle's one build)
     long long n_kkt_twisted = 0;   // KKT launches that took the twisted kernel (cimpc_get_kkt_twisted)
     int* h_twfail = nullptr;       // host-mapped: hand-overs of the twisted kernels that timed out (NewtonDev::kkt_tw_fail), never reset
     int twfail_seen = 0;           // ... its value when the host last looked
@@ -174,22 +144,19 @@ struct cimpc_ctx {
     double* d_cf_ws = nullptr;
     double* d_dense_ws = nullptr;  // [B][N*N + 2N], allocated on first use
     double *d_V = nullptr, *d_qt = nullptr, *d_vt = nullptr;
-    int waves = 4;
     int* d_ring = nullptr;       // [MAX_DEPTH][8] device counters per in-flight round (behind the queue counters: Q.count .. +ctl_ints)
     size_t ctl_ints = 0;
     int* h_ring = nullptr;       // pinned, host-mapped: {n_sweep, n_kkt, stamp}
     int* h_ring_dev = nullptr;   // device pointer of h_ring
     // asynchronous single-launch solve (newton_async_impl.h)
-    bool async_on = false, async_dirty = true;   // async_on: buffers allocated, kernel available
-    int async_mode = 2;          // 0 lock-step only, 1 always the single launch, 2 auto (by batch size / hybrid tail)
-    int async_tail = 96;         // hybrid: hand over to the asynchronous kernel when at most this many rollouts are active
+    SchedulePlan sched{};        // launch shapes and paths of the solves (schedule_plan.h)
+    bool async_dirty = true;     // the persistent kernel's queues may hold entries an aborted solve left behind
     int* a_items = nullptr;      // [K][a_cap] live interior-point queues
     int* a_jobs = nullptr;       // residual job entries, then KKT job entries
     int* a_ctrl = nullptr;       // [count K][head K][rq_head rq_tail kq_head kq_tail n_done ...]
     int* a_evals = nullptr;      // [B]
     long long* a_dbg = nullptr;  // [16] diagnostics (CIMPC_ASYNC_DEBUG)
     size_t a_cap = 0, a_rq_cap = 0, a_kq_cap = 0;
-    int a_grid = 0, a_service = 0;
     RoundStreams rs;
     bool external_stream = false;
     std::vector<double> h_tab;       // one knot staging
@@ -221,12 +188,10 @@ int fail(cimpc_ctx* h, int code, const std::string& msg) {
     } while (0)
 
 template <class T>
-int dev_alloc(cimpc_ctx* h, T** p, size_t count, int mem = 0) {
-    // mem: 0 = ordinary device memory; 1 = uncached, 2 = fine-grained device memory (experiments only)
+int dev_alloc(cimpc_ctx* h, T** p, size_t count) {
     void* v = nullptr;
     if (count == 0) count = 1;
-    hipError_t e = mem == 0 ? hipMalloc(&v, count * sizeof(T))
-                            : hipExtMallocWithFlags(&v, count * sizeof(T), mem == 1 ? hipDeviceMallocUncached : hipDeviceMallocFinegrained);
+    hipError_t e = hipMalloc(&v, count * sizeof(T));
     if (e != hipSuccess) return fail(h, CIMPC_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
     e = hipMemset(v, 0, count * sizeof(T));
     // the fill runs on the NULL stream, which the library's non-blocking streams do not wait for: a buffer
@@ -317,7 +282,7 @@ IpParams make_ip_params(cimpc_ctx* h, const TrajDev& T, int par, int* pending_co
     p.tab = h->d_tab;
     p.Q = h->Q;
     p.Q.par = par;
-    p.wpk = h->wpk;
+    p.wpk = h->sched.wpk;
     p.q = T.q;
     p.theta = T.th;
     p.gam = T.g;
@@ -332,7 +297,7 @@ IpParams make_ip_params(cimpc_ctx* h, const TrajDev& T, int par, int* pending_co
     p.pflag = h->S.pflag;
     p.pstate = h->d_pstate;
     p.pending_count = pending_counter;
-    p.iter_cap = h->iter_cap;
+    p.iter_cap = h->kn.sched.iter_cap;
     p.slots = CS;
     p.H = h->dm.H;
     p.o = h->ip;
@@ -348,32 +313,13 @@ IpParams make_ip_params(cimpc_ctx* h, const TrajDev& T, int par, int* pending_co
 int run_sweep(cimpc_ctx* h, int par, int* pending_counter, double* zout, hipStream_t st, int iter_cap = 0, int* drain_counter = nullptr,
               bool with_products = false, long long hint = -1) {
     IpParams p = make_ip_params(h, h->S.cand, par, pending_counter, zout);
-    int waves = h->waves;
-    // 32-lane models: the build of the sweep is chosen PER LAUNCH from the problems the host knows to be queued (round 5; the choice
-    // used to be made once per handle from B H): the latency build (4 waves per workgroup) below `adapt32` problems, the throughput
-    // build (8 waves, two per SIMD) from there on.  Parked iterates are the model's, not the build's: a solve may change builds.
-    // (only where the host's count is complete: with the KKT stage in the same round as the evaluation of its candidates - small
-    //  batches - the requests of that round are not known at launch; a first version sized a B = 1 sweep for ONE workgroup: 1.1 -> 20 ms)
-    if (h->ki.G == 32 && h->adapt32 > 0 && hint > 0 && h->kp.kkt_overlap && h->kn.sweep_wgs <= 0 && !(h->kn.waves32 == 4 || h->kn.waves32 == 8)) {      // (an explicit CIMPC_SWEEP_WGS keeps its grid)
-        waves = hint >= h->adapt32 ? 8 : 4;
-        const size_t groups_per_wg = 2 * (size_t)waves;
-        size_t w = ((size_t)hint + 2 * groups_per_wg - 1) / (2 * groups_per_wg);
-        w = std::max<size_t>(w, std::min<size_t>((size_t)h->dm.H_ref, (size_t)std::max<long long>(hint, 1)));
-        p.wpk = (int)std::max<size_t>(1, std::min<size_t>(w, 256));
-    }
-    // (round 4, measured and removed: one sweep workgroup per CU in rounds with few problems - <= 4 k / 8 k / 16 k - so that every
-    //  wave has its SIMD to itself: 7.97 -> 7.96 / 7.99 / 8.01 ms per step, no effect: profiles/r04/knob_small_round.log)
     if (with_products && h->S.dtn != nullptr) { p.nu = h->S.nu_cand; p.dtn = h->S.dtn; }
-    // single rollouts (B < 4: at most 7 B problems per knot): one workgroup per knot, no remaining-work scans (IpParams::direct)
-    if (h->dm.B < 4 && h->kn.sweep_wgs <= 0) { p.direct = 1; p.wpk = h->dm.H_ref; }
     if (iter_cap > 0) p.iter_cap = iter_cap;
-    if (drain_counter != nullptr && h->kn.drain_pct > 0 && p.iter_cap < h->ip.max_iter) {
-        p.drain_count = drain_counter;
-        p.drain_thresh = std::max(1, (int)((long long)p.wpk * h->kn.drain_pct / 100));
-        p.drain_min = h->kn.drain_min;
-    }
+    const SweepLaunch l = plan_sweep(h->kn.sched, h->sched, hint, p.iter_cap, h->ip.max_iter, drain_counter != nullptr);
+    p.wpk = l.wpk; p.direct = l.direct;
+    if (l.drain_thresh > 0) { p.drain_count = drain_counter; p.drain_thresh = l.drain_thresh; p.drain_min = h->kn.sched.drain_min; }
     prof_begin(h, PC_IP, st);
-    int rc = launch_ip_sweep(&h->dm, p, waves, st);
+    int rc = launch_ip_sweep(&h->dm, p, l.waves, st);
     prof_end(h, st);
     if (rc != CIMPC_OK) return fail(h, rc, "ip sweep launch failed");
     return CIMPC_OK;
@@ -538,7 +484,6 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
         h->ip_budget_ticks = std::max<long long>(1, (long long)std::llround(h->ip.max_time * 1.0e3 * (double)khz));
     }
     h->kn.read_environment();       // the only place the environment is consulted
-    h->iter_cap = h->kn.iter_cap;
     if (ip_kernel_info(&h->dm, &h->ki) != CIMPC_OK) {
         delete h;
         return fail(nullptr, CIMPC_ERR_INVALID,
@@ -563,39 +508,17 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
 
     const size_t B = d.B, H = d.H;
     int rc = CIMPC_OK;
-    {   // asynchronous single-launch solve? (queues sized for every push of one solve: they never wrap)
-        // CIMPC_ASYNC: 0 = lock-step rounds only, 1 = always the single launch, unset / 2 = auto.  Measured on
-        // MI355X (quadruped, H = 40): the single launch wins for 4 <= B <= 128 rollouts
-        // (B = 64: 8.1 vs 11.2 ms), the rounds win for large batches (B = 512: 16.5 vs 21.7 ms) - except for
-        // their sparse tail, which auto mode hands over to the asynchronous kernel.
-        h->async_mode = h->kn.async_mode;
-        h->async_tail = std::min(96, std::max(64, d.B / 6));      // measured: B = 512 -> 48 .. 96 flat; B = 1024 / 2048 -> 96 (11.1 / 18.85 ms against 11.4 / 19.5 at 170 / 256:
-                                                                   // the persistent kernel's chains do not get shorter with more rollouts handed over, the rounds do)
-        // (round 6, mid-size batches: B = 48 / 64 / 96 best at 32 - 4.07 / 4.35 / 4.41 ms -, B = 128 at 32-48 - 4.91 -, B = 192 at 48 - 4.76 ms against 5.30
-        //  with the rule above: scripts/dbg/headline_b.sh)
-        if (d.B < 256) h->async_tail = std::max(32, d.B / 4);
-        if (h->kn.async_tail >= 0) h->async_tail = h->kn.async_tail;
-        const bool want = h->async_mode != 0;
+    {   // the handle's schedule (schedule_plan.h); the persistent kernel's queues are sized for every push of one solve: they never wrap
         const size_t K = d.H_ref;
         const size_t evals = 1 + 7 * (size_t)std::max(1, h->nt.max_iter);       // per rollout and solve
         h->a_cap = B * evals * ((H + K - 1) / K + 1);
         h->a_rq_cap = B * (2 + 3 * (size_t)std::max(1, h->nt.max_iter));
         h->a_kq_cap = B * (2 + 3 * (size_t)std::max(1, h->nt.max_iter));      // (twisted KKT jobs: two entries per stage, one more after a timed-out hand-over)
         const size_t bytes = (K * h->a_cap + h->a_rq_cap + h->a_kq_cap) * sizeof(int);
-        h->async_on = want && newton_async_available(&d) && K <= 256 && bytes <= ((size_t)1 << 30);
+        h->sched = plan_schedule(h->kn.sched, ScheduleFacts{d.B, d.H, d.H_ref, h->ki.G, newton_async_available(&d) && K <= 256 && bytes <= ((size_t)1 << 30)});
     }
-    // 32-lane models (centroidal: one workgroup per CU, 512-register waves): the persistent kernel wins up to 32 rollouts only and the
-    // rounds keep their lead far into the tail - measured on BASELINE configs[4] (H = 60): B = 8 / 16 / 32 / 64 / 128 -> single launch
-    // 10.7 / 14.1 / 19.3 / 29.5 / - ms, lock-step rounds 12.1 / 17.7 / 20.5 / 22.4 / 34.9 ms, hand-over at 16 active rollouts 22.3 / 35.7 ms
-    if (h->ki.G == 32) {
-        if (getenv("CIMPC_ASYNC_FULL_MAX") == nullptr) h->kn.async_full_max = std::min(h->kn.async_full_max, 32);
-        if (h->kn.async_tail < 0) h->async_tail = 16;
-    }
-    const int xm = h->async_on ? h->kn.async_mem : 0;   // experiments: 1 uncached, 2 fine-grained
     auto A = [&](auto** p, size_t n) { if (rc == CIMPC_OK) rc = dev_alloc(h, p, n); };
-    auto AX = [&](auto** p, size_t n) { if (rc == CIMPC_OK) rc = dev_alloc(h, p, n, xm); };   // exchanged state
     A(&h->d_tab, (size_t)d.H_ref * h->ki.tab_size);
-    const int ppw = 64 / h->ki.G;
     {   // work queues: a knot can appear ceil(H / H_ref) times in one window
         const size_t K = d.H_ref;
         const size_t cap = B * CS * ((H + K - 1) / K + 1);
@@ -605,7 +528,7 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
         h->ctl_ints = 3 * K * QPAD + 2 * 8 * CPAD;
         A(&h->Q.count, h->ctl_ints);
         if (rc == CIMPC_OK) { h->Q.head = h->Q.count + 2 * K * QPAD; h->d_ring = h->Q.count + 3 * K * QPAD; }
-        AX(&h->Q.done_count, B * CS);
+        A(&h->Q.done_count, B * CS);
         A(&h->d_window, B * (H + 2));
         h->Q.window = h->d_window;
     }
@@ -634,43 +557,27 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
     S.nd = h->nd; S.nr = h->nr; S.nth = h->nth; S.nths = h->nths; S.N = h->N;
     const size_t BS = B * CS;     // evaluation slots (speculative line search)
     for (TrajDev* T : {&S.traj, &S.cand, &S.ref}) {
-        const size_t n = (T == &S.cand) ? BS : B;
-        if (T == &S.ref) {       // read-only during a solve
-            A(&T->q, n * (H + 2) * d.nq); A(&T->u, n * H * d.nu); A(&T->w, n * H * d.nw);
-            A(&T->g, n * H * d.nc); A(&T->b, n * H * d.nb); A(&T->th, n * H * h->nth);
-        } else {
-            AX(&T->q, n * (H + 2) * d.nq); AX(&T->u, n * H * d.nu); AX(&T->w, n * H * d.nw);
-            AX(&T->g, n * H * d.nc); AX(&T->b, n * H * d.nb); AX(&T->th, n * H * h->nth);
-        }
+        const size_t n = (T == &S.cand) ? BS : B;      // (S.ref: read-only during a solve)
+        A(&T->q, n * (H + 2) * d.nq); A(&T->u, n * H * d.nu); A(&T->w, n * H * d.nw);
+        A(&T->g, n * H * d.nc); A(&T->b, n * H * d.nb); A(&T->th, n * H * h->nth);
     }
-    AX(&S.nu, B * H * h->nd);
-    AX(&S.nu_cand, BS * H * h->nd);
-    AX(&S.d, BS * H * h->nd);
-    AX(&S.dz, BS * H * h->nths * h->nd);
-    AX(&S.dz_good, B * H * h->nths * h->nd);
-    AX(&h->d_good_src, B * H);
+    A(&S.nu, B * H * h->nd); A(&S.nu_cand, BS * H * h->nd); A(&S.d, BS * H * h->nd);
+    A(&S.dz, BS * H * h->nths * h->nd); A(&S.dz_good, B * H * h->nths * h->nd); A(&h->d_good_src, B * H);
     S.dtn_ld = h->ki.generic ? 0 : h->ki.dtn_ld;
-    if (S.dtn_ld > 0) AX(&S.dtn, BS * H * (size_t)S.dtn_ld);
-    AX(&S.ip_status, BS * H);
-    AX(&S.ip_iters, BS * H);
-    AX(&S.pflag, BS * H);
-    AX(&S.cur_slot, B);
+    if (S.dtn_ld > 0) A(&S.dtn, BS * H * (size_t)S.dtn_ld);
+    A(&S.ip_status, BS * H); A(&S.ip_iters, BS * H); A(&S.pflag, BS * H); A(&S.cur_slot, B);
     A(&h->d_pstate, BS * H * (2 * (size_t)h->nx + 4 * (size_t)h->ny + 4));
-    AX(&S.res, B * h->N);
-    AX(&S.res_cand, BS * h->N);
-    AX(&S.delta, B * h->N);
-    AX(&S.r_norm, B); AX(&S.r_cand, BS); AX(&S.alpha, B); AX(&S.beta, B);
-    AX(&S.ls_iter, B); AX(&S.newton_l, B); AX(&S.stage, B); AX(&S.need_sweep, BS);
+    A(&S.res, B * h->N); A(&S.res_cand, BS * h->N); A(&S.delta, B * h->N);
+    A(&S.r_norm, B); A(&S.r_cand, BS); A(&S.alpha, B); A(&S.beta, B);
+    A(&S.ls_iter, B); A(&S.newton_l, B); A(&S.stage, B); A(&S.need_sweep, BS);
     A(&S.kkt_list, 2 * B);
     A(&S.slot_list, 2 * BS);
-    AX(&S.counters, 8 * CPAD);
-    AX(&S.stats, std::max<size_t>(B * 4, 64));      // (>= 32 entries: diagnostic builds with -DCIMPC_KKT_PROF park their phase clocks at [8..23])
-    AX(&S.ro_sweeps, B); AX(&S.ro_ip_iters, B); AX(&S.ro_ip_fail, B);
-    AX(&S.nlog, B * NLOG * 4);
+    A(&S.counters, 8 * CPAD);
+    A(&S.stats, std::max<size_t>(B * 4, 64));      // (>= 32 entries: diagnostic builds with -DCIMPC_KKT_PROF park their phase clocks at [8..23])
+    A(&S.ro_sweeps, B); A(&S.ro_ip_iters, B); A(&S.ro_ip_fail, B); A(&S.nlog, B * NLOG * 4);
     A(&S.kkt_ws, B * H * (3 * (size_t)h->nd * h->nd + h->nd));
     A(&S.kkt_tw_xch, B * (3 * (size_t)h->nd * h->nd + 4 * h->nd));      // (= kkt_tw_xch_doubles(nd))
     A(&S.kkt_tw_flags, B * 32);                                          // (= KKT_TW_FLAGS per rollout, one line each)
-    (void)ppw;
     if (rc == CIMPC_OK && hipHostMalloc((void**)&h->h_counters, 8 * CPAD * sizeof(int)) != hipSuccess)
         rc = fail(h, CIMPC_ERR_HIP, "hipHostMalloc failed");
     if (rc != CIMPC_OK) {
@@ -684,15 +591,10 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
     }
     S.band_form = h->kn.banded_form;
     S.r_tol = h->nt.r_tol; S.beta_init = h->nt.beta_init; S.kappa = h->nt.kappa; S.max_iter = h->nt.max_iter;
-    // all-seven-step-lengths speculation: shortens the chain of rollouts that exhaust their line search; pays
-    // when the solve is latency-bound (small batches), costs throughput otherwise (B = 2048: -8 %)
     h->kp = h->kn.kkt;
-    h->kp.kkt_overlap = h->kn.kkt_overlap >= 0 ? h->kn.kkt_overlap != 0 : B >= 64;
+    h->kp.kkt_overlap = h->sched.kkt_overlap;
     set_kkt_backend(h);
-    S.spec_all = h->kn.spec_all >= 0 ? h->kn.spec_all : (d.B <= 128 ? 3 : 8);
-    // first line search of a solve (no history yet): 1, 1/2, 1/4 evaluated together up to mid-size batches (B = 512: 9.65 -> 9.50 ms,
-    // B = 128: 8.14 -> 8.03 ms for 0.3 more evaluated sweeps per step; B = 2048: 25.4 -> 25.6 ms, throughput-bound: one candidate there)
-    S.spec_first = h->kn.spec_first >= 0 ? h->kn.spec_first : (d.B <= 1024 ? 3 : 1);
+    S.spec_all = h->sched.spec_all; S.spec_first = h->sched.spec_first; S.spec_mid = h->sched.spec_mid;
     S.kkt_tw_nb = h->kn.kkt_tw_nb;
     S.kkt_tw_epoch = 0;
     S.kkt_tw_spins = h->kn.kkt_tw_spins > 0 ? h->kn.kkt_tw_spins : (1 << 21);
@@ -705,65 +607,18 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
         h->h_twfail[0] = 0;
         S.kkt_tw_fail = dv;
     }
-    // large batches: a rollout whose previous search needed a back-off starts the next one with 1, 1/2, 1/4 together (one
-    // round less per Newton iteration for 0.9 more evaluated sweeps per step: B = 512 11.4 -> 10.9 ms); small batches already
-    // evaluate all seven step lengths from depth 3 on
-    S.spec_mid = h->kn.spec_mid >= 0 ? h->kn.spec_mid : (d.B > 128 ? 1 : 8);
-    // 4 waves share one staged table (throughput); measured for single rollouts too (one problem per knot anyway): B = 1
-    // quadruped H = 40 cold 0.945 -> 0.926 ms, warm MPC loop 3.19 -> 3.03 ms, hopper H = 20 1.02 -> 0.97 ms against 1 wave
-    h->waves = 4;
-    // 32-lane models (round 4): from about three problems per lane group and sweep on, the throughput build of the sweep - eight waves per
-    // workgroup, two per SIMD (ip_kernel_impl.h: ip_queue_kernel<M, WIDE>; centroidal H = 60: 64 rollouts 7.9 -> 11.6 ms of sweeps per
-    // step, 128 rollouts 14.0 -> 12.2 ms, 256 rollouts 26.0 -> 22.4 ms - profiles/r04/cent_w8b.log).  CIMPC_WAVES32 = 4 / 8 forces one.
-    // (A first form that ALSO read the MGS column twice instead of keeping it in registers was LDS-bound: cent_8wave_experiment.log.)
-    if (h->ki.G == 32) {
-        if (h->kn.waves32 > 0 && h->kn.waves32 < 1000) h->waves = h->kn.waves32;
-        else if ((size_t)B * H >= 6000) h->waves = 8;
-        // Round 5: the build is chosen PER LAUNCH (run_sweep) from the problems queued for it - a step of 64 rollouts has launches of
-        // 3.8 k (one candidate per rollout) to 11.5 k problems (three): centroidal H = 60, 64 rollouts 7.87 -> 6.7 ms of sweeps per
-        // step (10.7 -> 9.6 ms per batch step), 128 rollouts 12.0 -> 11.5 ms; thresholds 5 / 7 / 9 / 11 k are equivalent at 64,
-        // 5 - 7 k best at 128 (profiles/r05/cent_adapt32.log).  CIMPC_WAVES32 >= 1000 sets the threshold, 4 / 8 force one build.
-        h->adapt32 = h->kn.waves32 >= 1000 ? h->kn.waves32 : (h->kn.waves32 == 4 || h->kn.waves32 == 8) ? 0 : 7000;
-    }
-    // the single-launch solve runs its residual jobs on the whole workgroup: 4 waves also for small batches
-    // (measured B = 8: 5.2 -> 4.4 ms, B = 64: 8.5 -> 7.5 ms)
-    if (h->async_on && (h->async_mode == 1 || (h->async_mode == 2 && B >= 4 && B <= h->kn.async_full_max))) h->waves = 4;
-    if (h->kn.waves == 1 || h->kn.waves == 2 || (h->kn.waves >= 4 && h->kn.waves <= 8)) h->waves = h->kn.waves;   // (5..8: builds with CIMPC_SWEEP_THREADS > 256)
     if (hipHostMalloc((void**)&h->h_ring, 32 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
         hipHostGetDevicePointer((void**)&h->h_ring_dev, h->h_ring, 0) != hipSuccess) {
         g_create_error = "ring allocation failed"; cimpc_destroy(h); return CIMPC_ERR_HIP;
     }
-    {
+    if (h->sched.async_on) {
         const size_t K = d.H_ref;
-        if (h->async_on) {
-            if (dev_alloc(h, &h->a_items, K * h->a_cap, xm) != CIMPC_OK || dev_alloc(h, &h->a_jobs, h->a_rq_cap + h->a_kq_cap, xm) != CIMPC_OK ||
-                dev_alloc(h, &h->a_ctrl, 2 * K * QPAD + 64 + 33 * 16, xm) != CIMPC_OK || dev_alloc(h, &h->a_evals, B, xm) != CIMPC_OK) {
-                g_create_error = h->err; cimpc_destroy(h); return CIMPC_ERR_HIP;
-            }
-            if (h->kn.async_debug && dev_alloc(h, &h->a_dbg, 16) != CIMPC_OK) { g_create_error = h->err; cimpc_destroy(h); return CIMPC_ERR_HIP; }
-            h->async_dirty = true;
+        if (dev_alloc(h, &h->a_items, K * h->a_cap) != CIMPC_OK || dev_alloc(h, &h->a_jobs, h->a_rq_cap + h->a_kq_cap) != CIMPC_OK ||
+            dev_alloc(h, &h->a_ctrl, 2 * K * QPAD + 64 + 33 * 16) != CIMPC_OK || dev_alloc(h, &h->a_evals, B) != CIMPC_OK) {
+            g_create_error = h->err; cimpc_destroy(h); return CIMPC_ERR_HIP;
         }
-    }
-    {   // persistent workgroups of a sweep launch: all resident (256 VGPRs -> 8 waves per CU), about two
-        // problems per lane group in a full round, and never fewer workgroups than busy knots (a
-        // workgroup serves one knot at a time)
-        const size_t groups_per_wg = (64 / h->ki.G) * h->waves;
-        const size_t nprob = B * H;
-        size_t w = (nprob + 2 * groups_per_wg - 1) / (2 * groups_per_wg);
-        w = std::max<size_t>(w, std::min<size_t>(d.H_ref, nprob));
-        // (32-lane models run one wave per SIMD - 512 registers - i.e. 4 waves per CU; the asynchronous launcher
-        //  clamps its grid to the occupancy the runtime reports in any case)
-        const size_t resident = (size_t)256 * std::max(1, (h->ki.G == 16 ? (h->waves > 4 ? 2 * h->waves : 8) : 4) / h->waves);
-        h->wpk = (int)std::max<size_t>(1, std::min<size_t>(w, resident));
-        if (h->kn.sweep_wgs > 0) h->wpk = h->kn.sweep_wgs;
-        // asynchronous solve: the same resident set plus dedicated residual/KKT workgroups
-        // (a line-search burst is up to 7 evaluations x H knots per rollout and every knot needs a workgroup of
-        //  its own: small batches get at least 240 - measured B = 8: 6.4 -> 5.1 ms, B = 128: 11.1 -> 10.3 ms)
-        const int a_wgs = h->kn.sweep_wgs > 0 ? h->wpk : std::max(h->wpk, 240);
-        h->a_service = std::max(1, a_wgs / 8);
-        if (h->kn.async_service > 0) h->a_service = h->kn.async_service;
-        h->a_grid = (int)std::min<size_t>(resident, (size_t)a_wgs + h->a_service);
-        if (h->a_grid <= h->a_service) h->a_grid = h->a_service + 1;
+        if (h->kn.async_debug && dev_alloc(h, &h->a_dbg, 16) != CIMPC_OK) { g_create_error = h->err; cimpc_destroy(h); return CIMPC_ERR_HIP; }
+        h->async_dirty = true;
     }
     {   // streams of the rounds (one batch: sub-batch streams were measured and only multiply the per-launch
         // latency floor - 4 sub-batches 34.8 ms/step vs 28.2 ms single batch at B = 512)
@@ -1264,7 +1119,7 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
         Sk.host_flag = h->h_ring_dev;
         // the tail is latency-bound: its stragglers (rollouts that exhaust the line search in every iteration)
         // evaluate all seven step lengths at once there, whatever the throughput-oriented setting of the rounds
-        if (!from_reset) Sk.spec_all = h->kn.spec_tail;
+        if (!from_reset) Sk.spec_all = h->sched.spec_tail;
         Sk.WQ = h->Q; Sk.WQ.par = 0;
         Sk.WQ.items = h->a_items; Sk.WQ.cap = (int)h->a_cap;
         Sk.WQ.count = h->a_ctrl; Sk.WQ.head = h->a_ctrl + K * QPAD;
@@ -1277,24 +1132,15 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
         A.epoch = c + 64;
         A.evals_left = h->a_evals;
         A.abort_flag = (volatile int*)(h->h_ring_dev + 3);
-        // (hybrid tail: few rollouts left - a smaller resident set means fewer idle workgroups polling next to the working ones)
-        int a_grid = h->a_grid, a_service = h->a_service;
-        const int tail_grid = h->kn.async_tail_grid >= 0 ? h->kn.async_tail_grid : std::max(256, 3 * h->async_tail);      // (256 = one workgroup per CU: the tail is latency bound, co-resident workgroups slow each other)
-        if (!from_reset && tail_grid > 0 && tail_grid < a_grid) {
-            a_grid = tail_grid;
-            a_service = std::max(1, a_grid / 8);
-        }
-        A.n_service = a_service;
-        A.flags = h->kn.async_flags;
-        A.idle_sleep = h->kn.async_sleep;
-        A.idle_spins = h->kn.async_spins;
-        A.wake_fan = h->kn.async_fan;
+        const int a_grid = from_reset ? h->sched.async_grid : h->sched.tail_grid;
+        A.n_service = from_reset ? h->sched.async_service : h->sched.tail_service;
+        A.idle_sleep = async_idle_sleep; A.idle_spins = async_idle_spins; A.wake_fan = async_wake_fan;
         A.dbg = h->a_dbg;
         if (h->a_dbg) HIP_TRY(h, hipMemsetAsync(h->a_dbg, 0, 16 * sizeof(long long), st));
         A.B = h->dm.B;
         // KKT stage of the persistent kernel: one job, or two cooperating jobs (the chains of the twisted solve, newton_async_impl.h)
         const KktSite site{.kind = from_reset ? KktSite::Persistent : KktSite::HybridTail, .tw_off = *(volatile int*)h->h_twfail != tw_fail0,
-                           .B = h->dm.B, .async_tail = h->async_tail, .waves = std::min(h->waves, 4)};
+                           .B = h->dm.B, .async_tail = h->sched.async_tail, .waves = std::min(h->sched.waves, 4)};
         A.kkt_tw = plan_kkt_stage(h, site) == KktForm::AsyncTwoJob ? 1 : 0;
         S.kkt_tw_epoch += h->nt.max_iter + 2;      // the launch's KKT stages take the stamps Sk.kkt_tw_epoch + 1 + (Newton iterations done)
         prof_begin(h, PC_OTHER, st);
@@ -1309,7 +1155,7 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
         long long solved_before = 0;      // interior-point problems the lock-step rounds had solved (profiling only)
         if (h->prof_on && !from_reset) { long long sv[4]; if (int rs = read_stats(h, sv); rs != CIMPC_OK) return rs; solved_before = sv[1]; }
         prof_begin(h, PC_ASYNC, st);
-        rc2 = launch_newton_async(&h->dm, p, Sk, std::min(h->waves, 4), a_grid, st);
+        rc2 = launch_newton_async(&h->dm, p, Sk, std::min(h->sched.waves, 4), a_grid, st);
         prof_end(h, st);
         if (rc2 != CIMPC_OK) return fail(h, rc2, "asynchronous newton launch failed");
         if (int rf = finish_results(st); rf != CIMPC_OK) return rf;      // (queued behind the persistent kernel)
@@ -1335,7 +1181,7 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
             long long dv[16];
             HIP_TRY(h, hipMemcpy(dv, h->a_dbg, sizeof(dv), hipMemcpyDeviceToHost));
             fprintf(stderr, "[cimpc async] WG-ms: other %.2f kkt %.2f resid %.2f ip %.2f | jobs: kkt %lld resid %lld serve %lld | grid %d service %d | group-trips %.2fM active %.1f%% | group-ms pop %.1f fence %.1f | pop: cas %lld spins %lld claim-ms %.1f wait-ms %.1f\n",
-                    dv[0] * 1e-5, dv[1] * 1e-5, dv[2] * 1e-5, dv[3] * 1e-5, dv[9], dv[10], dv[11], h->a_grid, h->a_service, dv[5] * 1e-6, dv[5] ? 100.0 * dv[4] / dv[5] : 0.0, dv[6] * 1e-5, dv[7] * 1e-5, dv[12], dv[13], dv[14] * 1e-5, dv[15] * 1e-5);
+                    dv[0] * 1e-5, dv[1] * 1e-5, dv[2] * 1e-5, dv[3] * 1e-5, dv[9], dv[10], dv[11], h->sched.async_grid, h->sched.async_service, dv[5] * 1e-6, dv[5] ? 100.0 * dv[4] / dv[5] : 0.0, dv[6] * 1e-5, dv[7] * 1e-5, dv[12], dv[13], dv[14] * 1e-5, dv[15] * 1e-5);
         }
         const long long stv[4] = {(long long)h->h_result[0], (long long)h->h_result[1], (long long)h->h_result[2], (long long)h->h_result[3]};
         h->last_stats.sweeps = stv[0];
@@ -1350,15 +1196,10 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
         return CIMPC_OK;
     };
     if ((rc = ensure_kkt_ws(h)) != CIMPC_OK) return rc;
-    const bool condensed = h->kb == KktBackend::Condensed;
-    const bool full_async = h->async_on && condensed && (h->async_mode == 1 || (h->async_mode == 2 && h->dm.B >= 4 && h->dm.B <= h->kn.async_full_max));
-    const bool hybrid = h->async_on && condensed && h->async_mode == 2 && !full_async && h->dm.B > h->kn.async_full_max;
-    if (full_async) return run_async(true, 0);
-    // safety net only: every Newton iteration needs at most 3 (speculative) rounds, each evaluation at
-    // most ceil(max_iter / iter_cap) launches of the resumable interior-point sweep
-    // (drain parking guarantees drain_min iterations of progress per launch, iter_cap parking iter_cap)
-    const int min_progress = h->kn.drain_pct > 0 ? std::min(h->iter_cap, h->kn.drain_min) : h->iter_cap;
-    const int max_rounds = (h->nt.max_iter * 8 + 2) * ((h->ip.max_iter + min_progress - 1) / min_progress + 1);
+    const SolvePath path = choose_solve_path(h->sched, h->kb);
+    if (path == SolvePath::Persistent) return run_async(true, 0);
+    const bool hybrid = path == SolvePath::Hybrid;
+    const int round_limit = max_rounds(h->kn.sched, h->nt.max_iter, h->ip.max_iter);
     // the rounds run on the library's private streams, or on the caller's stream when one was given
     RoundStreams sb = h->rs;
     if (h->external_stream) sb.st = h->stream;
@@ -1370,15 +1211,7 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
     long long launched = 0, completed = 0, rounds = 0;
     const bool dbg_rounds = h->kn.debug_rounds;
     int last_kkt = 0, last_sweep = h->dm.B, last_slots = h->dm.B, last_parked = 0, last_new_slots = h->dm.B;
-    // Single rollouts (B < 4: below the persistent kernel's range) keep ONE round queued ahead of the one the host waits for: such a
-    // round is launched BLIND - KKT kernel on the full list range with its count read on the device, everything else is
-    // device-driven anyway - and costs three empty launches if the solve turns out to be over; in exchange no round waits for the
-    // host to see the previous one's stamp and launch (about 10 us per round of a 0.7 ms solve).  Warm-started solves only - the
-    // cadence of an MPC loop, five Newton iterations over eight to ten rounds: hopper H = 20 0.652 -> 0.614 ms per MPC step; the
-    // four rounds of a cold start lose more to the empty launches than they gain (0.685 -> 0.706 ms).
-    // (not with a wall-clock budget: the round queued ahead would still run - and step the trajectory - after the host has stopped
-    //  waiting, newton.jl:187-277 ends silently at the check)
-    const bool ahead = h->dm.B < 4 && h->kb != KktBackend::CondensedMixed && warm_start != 0 && !(h->nt.max_time > 0.0 && h->nt.max_time < 1.0e6);
+    const bool ahead = round_ahead(h->sched, h->kb, warm_start != 0, h->nt.max_time > 0.0 && h->nt.max_time < 1.0e6);
     auto launch_round = [&](long long r, bool blind) -> int {
         // [KKT for rollouts that start an iteration] || sweep -> residual of every evaluated slot -> line-search decision
         const int slot = (int)(r & 1), par = (int)(r & 1);      // round r consumes Q[par] and leaves the next round's requests in Q[par ^ 1]
@@ -1416,13 +1249,7 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
             if (rk != CIMPC_OK) return fail(h, rk, "kkt launch failed");
             if (ov && hipEventRecord(sb.ev_join, sb.st_kkt) != hipSuccess) return fail(h, CIMPC_ERR_HIP, "join record failed");
         }
-        // parking (iter_cap) protects a busy round from one long solve; in the sparse tail of a solve
-        // it only adds rounds, so a round that serves few rollouts lets every solve run to the end
-        const int tail_div = h->kn.tail_div;
-        // (batches below tail_div rollouts never park: a round there is as long as its longest solve whichever way it is cut)
-        // (in a blind round `last_sweep` is one round stale: the cap is then chosen without it)
-        const bool sparse = tail_div > 0 && (h->dm.B < tail_div || (!blind && (long long)last_sweep * tail_div <= h->dm.B));
-        const int cap = sparse ? h->ip.max_iter : h->iter_cap;
+        const RoundPlan rp = plan_round(h->kn.sched, h->sched, h->ip.max_iter, kkt, blind, last_sweep, last_slots);
         // problems of this round as far as the host knows them: the evaluation slots requested + the solves the last sweep parked
         const long long hint = blind ? -1 : (long long)last_slots * h->dm.H + last_parked;
         if (dbg_rounds && !blind) {      // diagnostics only: the problems this round's sweep will find in its queues (a blocking read)
@@ -1434,23 +1261,15 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
                 fprintf(stderr, "[cimpc round %lld] sweep launch: %lld problems queued (host hint %lld)\n", r, tot, hint);
             }
         }
-        int rr = run_sweep(h, par, d_cnt + 2 * CPAD, nullptr, sb.st, cap, d_cnt + 3 * CPAD, true, hint);
+        int rr = run_sweep(h, par, d_cnt + 2 * CPAD, nullptr, sb.st, rp.cap, d_cnt + 3 * CPAD, true, hint);
         if (rr != CIMPC_OK) return rr;
-        // the evaluation slots of this round: the compact list its requesters built (small batches run the KKT stage in the same
-        // round as the evaluation of its candidates - not known to the host at launch: every (rollout, slot) pair gets a block there)
-        const int n_slots = h->kp.kkt_overlap ? last_slots : (h->dm.B < 4 ? -2 : -1);
-        // round 4: the per-slot residual kernel goes in FRONT of the join with the overlapped KKT kernel (it reads the sweep's results
-        // only; the rollouts the KKT kernel works on have no slot on this round's list), the decision kernel behind it - in the
-        // rounds whose KKT recursion outlasts the sweep (about six per step of the headline batch) the 26 us of the slot kernel
-        // leave the critical path
-        const bool split_join = kkt && h->kp.kkt_overlap && n_slots >= 0;
         prof_begin(h, PC_RESID, sb.st);
-        if (split_join) {
-            rr = launch_resid_decide(Sk, sb.st, n_slots, 1);
+        if (rp.split_join) {
+            rr = launch_resid_decide(Sk, sb.st, rp.n_slots, 1);
             if (rr != CIMPC_OK) return fail(h, rr, "residual launch failed");
         }
         if (kkt && h->kp.kkt_overlap && hipStreamWaitEvent(sb.st, sb.ev_join, 0) != hipSuccess) return fail(h, CIMPC_ERR_HIP, "join failed");
-        rr = launch_resid_decide(Sk, sb.st, n_slots, split_join ? 2 : 0);
+        rr = launch_resid_decide(Sk, sb.st, rp.n_slots, rp.split_join ? 2 : 0);
         prof_end(h, sb.st);
         if (rr != CIMPC_OK) return fail(h, rr, "residual launch failed");
         return CIMPC_OK;
@@ -1469,7 +1288,7 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
         if (rc != CIMPC_OK) return fail(h, rc, "reset launch failed");
     }
     while (true) {
-        if (completed >= max_rounds) {          // round limit reached with work left: a scheduling bug, never a silent partial solve
+        if (completed >= round_limit) {          // round limit reached with work left: a scheduling bug, never a silent partial solve
             (void)hipStreamSynchronize(sb.st); (void)hipStreamSynchronize(sb.st_kkt);
             return fail(h, CIMPC_ERR_STATE, "newton_solve: round limit reached with unfinished rollouts");
         }
@@ -1501,10 +1320,7 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
         rounds = completed;
         if ((n_sweep == 0 && last_kkt == 0) || over_budget()) break;   // newton.jl:187-277: budget ends silently
         if (hybrid) {
-            // sparse tail: few rollouts left, every round pays its fixed latency for them -> the persistent
-            // kernel finishes them along their own chains
-            const int active = h->dm.B - hr[5];
-            if (active > 0 && active <= h->async_tail) {
+            if (hand_over(h->sched, h->dm.B - hr[5])) {
                 HIP_TRY(h, hipStreamSynchronize(sb.st));
                 HIP_TRY(h, hipStreamSynchronize(sb.st_kkt));
                 return run_async(false, rounds, (int)(rounds & 1));

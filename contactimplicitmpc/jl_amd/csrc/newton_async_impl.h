@@ -21,6 +21,7 @@
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <map>
 #include "ip_kernel_impl.h"
 #ifdef CIMPC_KKT_PROF
 #undef CIMPC_KKT_PROF        // the KKT phase clocks are read from the lock-step kernels only (and this translation unit does not compile with them)
@@ -246,17 +247,18 @@ int launch_async_model(const IpParams& p, const NewtonDev& S, int waves, int gri
     static LdsOptIn optin;
     if (lds_opt_in(optin, (const void*)newton_async_kernel<M>, lds) != CIMPC_OK) return CIMPC_ERR_HIP;
     // every workgroup of this kernel must be resident (they wait for each other's jobs): clamp the grid to what the
-    // device really holds for this kernel / block size / LDS footprint
-    static int max_resident[5] = {0, 0, 0, 0, 0};
-    if (max_resident[waves] == 0) {
+    // device really holds for this kernel / block size / LDS footprint (the LDS size follows A.kkt_tw and the horizon)
+    static std::map<std::pair<int, size_t>, int> max_resident;      // (waves, LDS bytes) -> workgroups
+    int& resident = max_resident[{waves, lds}];
+    if (resident == 0) {
         int per_cu = 0, dev = 0;
         hipDeviceProp_t prop;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)newton_async_kernel<M>, 64 * waves, lds) != hipSuccess ||
             hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || per_cu < 1)
             return CIMPC_ERR_HIP;
-        max_resident[waves] = per_cu * prop.multiProcessorCount;
+        resident = per_cu * prop.multiProcessorCount;
     }
-    if (grid > max_resident[waves]) grid = max_resident[waves];
+    if (grid > resident) grid = resident;
     if (grid <= S.A.n_service) return CIMPC_ERR_INVALID;          // no workgroup left for the interior-point queues
     AsyncArgs args{p, S};
     hipLaunchKernelGGL((newton_async_kernel<M>), dim3(grid), dim3(64 * waves), lds, s, args);

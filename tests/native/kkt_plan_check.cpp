@@ -1,10 +1,11 @@
 // Host-only driver of contactimplicitmpc/jl_amd/csrc/kkt_plan.h (tests/test_kkt_plan.py): one case per input line,
 //   caps:   cfg velocity cf_tiny wide_tiles condensed mfma packed twisted duo mixed banded cf_reduce banded_twisted
 //   want:   kkt_backend (cimpc_newton_opts)
-//   policy: kkt_pipe kkt_twisted kkt_duo kkt_duo_hint kkt_duo_max kkt_tw_max kkt_pipe_max async_kkt_tw lazy_dz kkt_overlap (knob, -1: by B)
+//   policy: kkt_pipe kkt_twisted kkt_duo kkt_duo_hint kkt_duo_max kkt_tw_max kkt_pipe_max async_kkt_tw lazy_dz kkt_overlap (knob, -1: the handle's, schedule_plan.h)
 //   site:   kind (1 / 2: a lock-step round, on whichever stream kkt_overlap gives) attempt n_kkt blind sweep_problems tw_off B async_tail waves
 // and one output line per case: backend form two_ended lazy_commit.
 #include "../../contactimplicitmpc/jl_amd/csrc/kkt_plan.h"
+#include "../../contactimplicitmpc/jl_amd/csrc/schedule_plan.h"
 
 #include <cstdio>
 #include <iostream>
@@ -28,7 +29,9 @@ int main() {
             >> p.async_kkt_tw >> lazy >> overlap >> kind >> s.attempt >> s.n_kkt >> blind >> s.sweep_problems >> tw_off >> s.B >> s.async_tail >> s.waves;
         if (!std::cin) return 1;
         p.lazy_dz = lazy != 0;
-        p.kkt_overlap = overlap >= 0 ? overlap != 0 : s.B >= 64;      // as cimpc_create
+        ScheduleFacts facts;
+        facts.B = s.B;
+        p.kkt_overlap = overlap >= 0 ? overlap != 0 : plan_schedule(SchedulePolicy{}, facts).kkt_overlap;
         s.kind = (KktSite::Kind)kind;
         if (kind == KktSite::Round || kind == KktSite::Overlapped) s.kind = p.kkt_overlap ? KktSite::Overlapped : KktSite::Round;   // as the host
         s.blind = blind != 0;
