@@ -53,6 +53,8 @@ PLANT_HD Dual plog1p(Dual a) { return {log1p(a.v), a.d / (1.0 + a.v)}; }
 PLANT_HD double psqrt(double a) { return sqrt(a); }
 PLANT_HD double pexp(double a) { return exp(a); }
 PLANT_HD double plog1p(double a) { return log1p(a); }
+PLANT_HD Dual ptanh(Dual a) { const double t = tanh(a.v); return {t, a.d * (1.0 - t * t)}; }
+PLANT_HD double ptanh(double a) { return tanh(a); }
 template <class T> PLANT_HD T pconst(double a);
 template <> PLANT_HD double pconst<double>(double a) { return a; }
 template <> PLANT_HD Dual pconst<Dual>(double a) { return {a, 0.0}; }
@@ -60,6 +62,9 @@ template <> PLANT_HD Dual pconst<Dual>(double a) { return {a, 0.0}; }
 constexpr int PLANT_MAX_Q = 18, PLANT_MAX_U = 12, PLANT_MAX_BODIES = 9, PLANT_MAX_SEG = 3;
 constexpr int PLANT_NC = 4, PLANT_NB = 16, PLANT_NW = 3;     // maxima: four contacts, two (flat_2D_lc) or four (flat_3D_lc) friction directions each
 constexpr int PLANT_KIND_CHAIN = 0, PLANT_KIND_HOPPER_2D = 1, PLANT_KIND_CENTROIDAL = 2, PLANT_KIND_PARTICLE = 3, PLANT_KIND_PARTICLE_2D = 4;
+// centroidal_quadruped_box / _wall: plant_residual_centroidal_env, stepped by their own kernel instantiations (plant_kernel.hip)
+constexpr int PLANT_KIND_CENTROIDAL_BOX = 5, PLANT_KIND_CENTROIDAL_WALL = 6;
+constexpr int PLANT_WALL_NC = 8, PLANT_WALL_NB = 32;          // the wall model: four feet on the floor and the same four on the wall
 
 struct PlantChain { int n; double r[PLANT_MAX_SEG]; int k[PLANT_MAX_SEG]; };
 struct PlantModel {
@@ -135,6 +140,43 @@ PLANT_HD void plant_centroidal_derivatives(const PlantModel& M, const T* v, T* d
     d1[5] = -(wx * (I1 * wy) - wy * (I0 * wx));
     for (int i = 6; i < 18; ++i) { d2[i] = mf * v[i]; d1[i] = pconst<T>((i % 3) == 2 ? -mf * M.g : 0.0); }
 }
+// dyn += B(qm2)^T u: (sum u_i, sum R^T skew(r_i) u_i, -u_1 .. -u_4), centroidal_quadruped/model.jl:98-121 (the box and the wall
+// share it, centroidal_quadruped_box/model.jl:109-131, centroidal_quadruped_wall/model.jl:102-124).  plant_residual_centroidal
+// keeps its own inline copy of this and of plant_centroidal_dynamics: calling them changes the generated code of the existing
+// plant kernels, whose .text is held byte-identical.
+template <class T>
+PLANT_HD void plant_centroidal_actuation(const T* qm2, const double* u1, T* dyn) {
+    const T sa = psin(qm2[3]), ca = pcos(qm2[3]), sb = psin(qm2[4]), cb = pcos(qm2[4]), sc = psin(qm2[5]), cc = pcos(qm2[5]);
+    T R[3][3];
+    R[0][0] = ca * cb; R[0][1] = ca * sb * sc - sa * cc; R[0][2] = ca * sb * cc + sa * sc;
+    R[1][0] = sa * cb; R[1][1] = sa * sb * sc + ca * cc; R[1][2] = sa * sb * cc - ca * sc;
+    R[2][0] = -sb;     R[2][1] = cb * sc;                R[2][2] = cb * cc;
+    for (int f = 0; f < 4; ++f) {
+        const double ux = u1[3 * f], uy = u1[3 * f + 1], uz = u1[3 * f + 2];
+        const T rx = qm2[6 + 3 * f] - qm2[0], ry = qm2[7 + 3 * f] - qm2[1], rz = qm2[8 + 3 * f] - qm2[2];
+        // skew(r) u = r x u
+        const T cx = ry * uz - rz * uy, cy = rz * ux - rx * uz, cz = rx * uy - ry * ux;
+        dyn[0] = dyn[0] + ux; dyn[1] = dyn[1] + uy; dyn[2] = dyn[2] + uz;
+        for (int k = 0; k < 3; ++k) dyn[3 + k] = dyn[3 + k] + (R[0][k] * cx + R[1][k] * cy + R[2][k] * cz);      // R^T (r x u)
+        dyn[6 + 3 * f] = dyn[6 + 3 * f] - ux; dyn[7 + 3 * f] = dyn[7 + 3 * f] - uy; dyn[8 + 3 * f] = dyn[8 + 3 * f] - uz;
+    }
+}
+// the dynamics rows before the contact forces: integrator (dynamics/model.jl:11-36) with the joint damping, B(qm2)^T u and A^T w
+template <class T>
+PLANT_HD void plant_centroidal_dynamics(const PlantModel& M, const T* q2, const double* th, T* dyn) {
+    constexpr int nq = 18, nu = 12;
+    const double* q0 = th; const double* q1 = th + nq; const double* u1 = th + 2 * nq; const double* w1 = u1 + nu;
+    const double h = w1[4];
+    T qm2[nq], vm1[nq], vm2[nq];
+    for (int i = 0; i < nq; ++i) { vm1[i] = pconst<T>((q1[i] - q0[i]) / h); qm2[i] = (q2[i] + q1[i]) * 0.5; vm2[i] = (q2[i] - q1[i]) / h; }
+    T a1[nq], b1[nq], a2[nq], b2[nq];
+    plant_centroidal_derivatives(M, vm1, a1, b1);
+    plant_centroidal_derivatives(M, vm2, a2, b2);
+    for (int i = 0; i < nq; ++i)
+        dyn[i] = (0.5 * h) * a1[i] + b1[i] + (0.5 * h) * a2[i] - b2[i] - (h * M.joint_friction[i]) * vm2[i];
+    plant_centroidal_actuation(qm2, u1, dyn);
+    for (int i = 0; i < 3; ++i) dyn[i] = dyn[i] + w1[i];
+}
 template <class T>
 PLANT_HD void plant_residual_centroidal(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
     constexpr int nq = 18, nu = 12, nc = 4, nb = 16;
@@ -183,6 +225,60 @@ PLANT_HD void plant_residual_centroidal(const PlantModel& M, const T* z, const d
         r[nq + 2 * nc + nb + f] = gam[f] * s1[f] - kappa;
         for (int k = 0; k < 4; ++k) r[nq + 3 * nc + nb + 4 * f + k] = bf[k] * ef[k] - kappa;
         r[nq + 3 * nc + 2 * nb + f] = psi[f] * s2[f] - kappa;
+    }
+    for (int i = 0; i < nq; ++i) r[i] = dyn[i];
+}
+
+// ---- centroidal_quadruped_box (src/dynamics/centroidal_quadruped_box/model.jl) and centroidal_quadruped_wall
+// (src/dynamics/centroidal_quadruped_wall/model.jl): the centroidal model (same M, C, B, A; plant_centroidal_dynamics) with
+// other contacts.  Both files define only the damped model (box :221-230, wall :226-235); the box's feet weigh 0.5 (:219).
+//   box   nc 4: phi_i = p_z,i - e(p_x,i), e(x) = 0.2 (1 + tanh(200 (x - 0.25))) / 2 (:87-107).  The reference rotates neither J
+//         nor the force on the step edge: the normal stays vertical (its behaviour, kept).
+//   wall  nc 8: contacts 1-4 are the feet on the floor; 5-8 the same feet against the plane x = 0.25 (:87-99), phi = 0.25 - p_x,
+//         J rows = the feet's rows again (:132-145), force [-gamma; m b] on (x; y, z) (:147-160), tangential velocity
+//         m^T (v_y, v_z) (:162-173).
+// mass[1] = m_f; nc = 4 (box) or 8 (wall).  Not dispatched by plant_residual (the kinds have their own kernel instantiations).
+template <class T>
+PLANT_HD T plant_box_elevation(T x) {
+    return 0.1 * (1.0 + ptanh(200.0 * (x - 0.25)));
+}
+template <class T>
+PLANT_HD void plant_residual_centroidal_env(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
+    constexpr int nq = 18;
+    const int nc = M.nc, nb = 4 * nc;
+    const double* q1 = th + nq; const double mu = th[2 * nq + 12 + 3], h = th[2 * nq + 12 + 4];
+    const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc; const T* psi = b + nb; const T* s1 = psi + nc;
+    const T* eta = s1 + nc; const T* s2 = eta + nb;
+    T dyn[nq];
+    plant_centroidal_dynamics(M, q2, th, dyn);
+    for (int c = 0; c < nc; ++c) {
+        const int f = c & 3;                                          // the foot of contact c
+        const T* bc = b + 4 * c; const T* ec = eta + 4 * c;
+        const T t1 = bc[0] - bc[2], t2 = bc[1] - bc[3];                // m b
+        const T* p2 = q2 + 6 + 3 * f; const double* p1 = q1 + 6 + 3 * f;
+        T phi, v1, v2;
+        if (c < 4) {                                                   // floor: force (m b; gamma), velocity (v_x, v_y)
+            dyn[6 + 3 * f] = dyn[6 + 3 * f] + t1;
+            dyn[7 + 3 * f] = dyn[7 + 3 * f] + t2;
+            dyn[8 + 3 * f] = dyn[8 + 3 * f] + gam[c];
+            phi = M.kind == PLANT_KIND_CENTROIDAL_BOX ? p2[2] - plant_box_elevation(p2[0]) : p2[2];
+            v1 = (p2[0] - p1[0]) / h; v2 = (p2[1] - p1[1]) / h;
+        } else {                                                       // wall: force (-gamma; m b), velocity (v_y, v_z)
+            dyn[6 + 3 * f] = dyn[6 + 3 * f] - gam[c];
+            dyn[7 + 3 * f] = dyn[7 + 3 * f] + t1;
+            dyn[8 + 3 * f] = dyn[8 + 3 * f] + t2;
+            phi = 0.25 - p2[0];
+            v1 = (p2[1] - p1[1]) / h; v2 = (p2[2] - p1[2]) / h;
+        }
+        r[nq + c] = s1[c] - phi;
+        r[nq + nc + 4 * c + 0] = ec[0] - v1 - psi[c];
+        r[nq + nc + 4 * c + 1] = ec[1] - v2 - psi[c];
+        r[nq + nc + 4 * c + 2] = ec[2] + v1 - psi[c];
+        r[nq + nc + 4 * c + 3] = ec[3] + v2 - psi[c];
+        r[nq + nc + nb + c] = s2[c] - (mu * gam[c] - (bc[0] + bc[1] + bc[2] + bc[3]));
+        r[nq + 2 * nc + nb + c] = gam[c] * s1[c] - kappa;
+        for (int k = 0; k < 4; ++k) r[nq + 3 * nc + nb + 4 * c + k] = bc[k] * ec[k] - kappa;
+        r[nq + 3 * nc + 2 * nb + c] = psi[c] * s2[c] - kappa;
     }
     for (int i = 0; i < nq; ++i) r[i] = dyn[i];
 }
@@ -489,7 +585,8 @@ PLANT_HD void plant_residual_terrain(const PlantModel& M, const cimpc_terrain& E
 }
 
 // Which terrains a model takes (cimpc_plant_step_terrain): FLAT everywhere; planar kinds on the planar models; 3-D kinds on the
-// particle; centroidal_quadruped flat only (its reference model never calls surf or rotation).
+// particle; centroidal_quadruped, _box and _wall flat only (their reference models never call surf or rotation: the box's step
+// and the wall are inside their phi).
 inline bool terrain_valid_for(const PlantModel& M, const cimpc_terrain& E) {
     const double* f[] = {E.p, E.brk + 1, E.off, &E.coef[0][0]};
     const int n[] = {4, CIMPC_TERRAIN_MAX_PIECES - 1, CIMPC_TERRAIN_MAX_PIECES, 4 * CIMPC_TERRAIN_MAX_PIECES};
@@ -501,7 +598,7 @@ inline bool terrain_valid_for(const PlantModel& M, const cimpc_terrain& E) {
     }
     if (E.kind == CIMPC_TERRAIN_SOFTPLUS && E.p[1] == 0.0) return false;
     if (E.kind == CIMPC_TERRAIN_FLAT) return true;
-    if (M.kind == PLANT_KIND_CENTROIDAL) return false;
+    if (M.kind == PLANT_KIND_CENTROIDAL || M.kind == PLANT_KIND_CENTROIDAL_BOX || M.kind == PLANT_KIND_CENTROIDAL_WALL) return false;
     return terrain_is_3d(E.kind) == (M.kind == PLANT_KIND_PARTICLE);
 }
 
@@ -554,6 +651,17 @@ inline PlantModel plant_centroidal(bool damped) {          // centroidal_quadrup
     M.mass[0] = 13.5; M.mass[1] = 0.2;
     M.inertia[0] = 0.0178533 * 10.0; M.inertia[1] = 0.0377999 * 10.0; M.inertia[2] = 0.0456542 * 10.0;
     for (int i = 0; i < 18; ++i) M.joint_friction[i] = damped ? ((i >= 3 && i < 6) ? 30.0 : 10.0) : 0.0;      // mu_joint = 1
+    return M;
+}
+inline PlantModel plant_centroidal_box() {         // centroidal_quadruped_box/model.jl:199-230: the damped centroidal model, m_f = 0.5
+    PlantModel M = plant_centroidal(true);
+    M.kind = PLANT_KIND_CENTROIDAL_BOX;
+    M.mass[1] = 0.5;
+    return M;
+}
+inline PlantModel plant_centroidal_wall() {        // centroidal_quadruped_wall/model.jl:204-235: the damped centroidal model, nc = 8
+    PlantModel M = plant_centroidal(true);
+    M.kind = PLANT_KIND_CENTROIDAL_WALL; M.nc = PLANT_WALL_NC;
     return M;
 }
 inline PlantModel plant_particle() {           // particle/model.jl:113-121

@@ -12,6 +12,7 @@ definitions and differentiates it with torch (fp64, CPU, `torch.func` - exact de
   quadruped         src/dynamics/quadruped/model.jl:75-590  (planar kinematic tree, Lagrangian)
   flamingo          src/dynamics/flamingo/model.jl:62-503   (planar biped with toe / heel contacts)
   centroidal_quad.  src/dynamics/centroidal_quadruped/model.jl:61-229, src/dynamics/euler.jl:3-11
+  ... box / wall    src/dynamics/centroidal_quadruped_box/model.jl, src/dynamics/centroidal_quadruped_wall/model.jl
   reference traj.   src/controller/trajectory.jl:152-184    (`get_trajectory`, :split_traj_alt)
 
 It is host-side input preparation (the reference does it once per knot at policy build) - not
@@ -368,8 +369,52 @@ class CentroidalQuadrupedUndamped(CentroidalQuadruped):
         return torch.zeros(self.nq, dtype=F64)
 
 
+class CentroidalQuadrupedBox(CentroidalQuadruped):
+    """`centroidal_quadruped_box` (centroidal_quadruped_box/model.jl:87-107, 199-230): the damped centroidal model with 0.5 kg
+    feet over a 0.2 m step at x = 0.25, ϕ_i = p_z,i - e(p_x,i), e(x) = 0.2 (1 + tanh(200 (x - 0.25))) / 2.  J and the contact
+    forces are not rotated on the step edge (the reference's behaviour)."""
+    name = "centroidal_quadruped_box"
+    mass_foot = 0.5
+
+    @staticmethod
+    def elevation(x):
+        return 0.2 * (1.0 + torch.tanh(200.0 * (x - 0.25))) / 2.0
+
+    def phi(self, q):
+        p = q[6:18]
+        return p[2::3] - self.elevation(p[0::3])
+
+
+class CentroidalQuadrupedWall(CentroidalQuadruped):
+    """`centroidal_quadruped_wall` (centroidal_quadruped_wall/model.jl:87-173, 204-235): the damped centroidal model with eight
+    contacts - the four feet on the floor, then the same feet against the plane x = 0.25 (ϕ = 0.25 - p_x, J rows repeated,
+    force [-γ; m b] on (x; y, z), tangential velocity mᵀ (v_y, v_z))."""
+    name, nc = "centroidal_quadruped_wall", 8
+
+    def kinematics(self, q):                      # J_func: the feet's rows twice
+        return torch.cat([q[6:18], q[6:18]])
+
+    def phi(self, q):
+        p = q[6:18]
+        return torch.cat([p[2::3], 0.25 - p[0::3]])
+
+    def contact_forces(self, gamma, b):
+        m = self.friction_mapping()
+        parts = []
+        for i in range(self.nc):
+            mb = m @ b[4 * i:4 * i + 4]
+            parts += [mb, gamma[i:i + 1]] if i < 4 else [-gamma[i:i + 1], mb]
+        return torch.cat(parts)
+
+    def velocity_stack(self, q1, q2, h):
+        v = self.J(q2) @ (q2 - q1) / h
+        m = self.friction_mapping()
+        return torch.cat([m.T @ (v[3 * i:3 * i + 2] if i < 4 else v[3 * i + 1:3 * i + 3]) for i in range(self.nc)])
+
+
 MODELS = {"hopper_2D": Hopper2D, "particle": Particle, "quadruped": Quadruped, "flamingo": Flamingo, "centroidal_quadruped": CentroidalQuadruped,
-          "centroidal_quadruped_undamped": CentroidalQuadrupedUndamped}
+          "centroidal_quadruped_undamped": CentroidalQuadrupedUndamped, "centroidal_quadruped_box": CentroidalQuadrupedBox,
+          "centroidal_quadruped_wall": CentroidalQuadrupedWall}
 
 
 @dataclass

@@ -353,6 +353,12 @@ int cimpc_plant_step(int model, int B, const double* q0, const double* q1, const
  * The gradient of PIECEWISE is the derivative of the piece (the reference's hand-written surf_grad; zero for stairs3).
  * Every field must be finite; PIECEWISE needs 1 <= n_pieces <= CIMPC_TERRAIN_MAX_PIECES and increasing brk[1..n-1]. */
 #define CIMPC_PLANT_PARTICLE_2D 6           /* src/dynamics/particle_2D/model.jl (nq 2, nu 2, nc 1, nw 2); cimpc_plant_step_terrain only */
+/* Both entries; the terrain entry takes them on FLAT only (the box's step and the wall are inside their phi).  nq 18, nu 12, nw 3
+ * (the payload input: a force on the body position, A = eye(3, 18)), the damped models (mu_joint [10 1_3; 30 1_3; 10 1_12]). */
+#define CIMPC_PLANT_CENTROIDAL_BOX 7        /* src/dynamics/centroidal_quadruped_box/model.jl:87-107, 199-230: nc 4, nb 16; phi_i =
+                                               p_z,i - 0.2 (1 + tanh(200 (p_x,i - 0.25))) / 2, vertical normal; foot mass 0.5 */
+#define CIMPC_PLANT_CENTROIDAL_WALL 8       /* src/dynamics/centroidal_quadruped_wall/model.jl:87-173, 204-235: nc 8, nb 32; contacts
+                                               5-8 = the feet against the plane x = 0.25, force [-gamma; m b] on (x; y, z) */
 #define CIMPC_TERRAIN_FLAT 0
 #define CIMPC_TERRAIN_PIECEWISE 1
 #define CIMPC_TERRAIN_SOFTPLUS 2
@@ -370,8 +376,8 @@ typedef struct cimpc_terrain {
     double coef[CIMPC_TERRAIN_MAX_PIECES][4];
 } cimpc_terrain;
 /* cimpc_plant_step on terrain: n_terrain = 1 (every robot on `terrain[0]`) or B (robot i on terrain[i]).  Planar kinds (PIECEWISE,
- * SOFTPLUS, SINE) apply to quadruped, flamingo, hopper_2D and particle_2D; 3-D kinds to particle; centroidal_quadruped takes FLAT
- * only (its reference model ignores the environment).  A flat robot runs exactly the code of cimpc_plant_step (bit-identical
+ * SOFTPLUS, SINE) apply to quadruped, flamingo, hopper_2D and particle_2D; 3-D kinds to particle; centroidal_quadruped, _box and
+ * _wall take FLAT only (their reference models ignore the environment).  A flat robot runs exactly the code of cimpc_plant_step (bit-identical
  * results).  Any other count, an unknown kind, a kind the model does not take or a non-finite field: CIMPC_ERR_INVALID. */
 int cimpc_plant_step_terrain(int model, int B, int n_terrain, const cimpc_terrain* terrain, const double* q0, const double* q1,
                              const double* u, const double* w, double mu, double h, const cimpc_ip_opts* opts, double* q2,
