@@ -22,14 +22,13 @@ namespace cimpc {
 namespace {
 
 constexpr int NZM = PLANT_MAX_Q + 4 * PLANT_NC + 2 * PLANT_NB;      // 66 (centroidal); the planar models have 43, hopper_2D 12
-constexpr int LDA = NZM + 1;
 
 struct PlantOpts {
     double r_tol, kappa_tol, kc_floor, eps_min, ls_scale, stall_alpha;
     int max_iter, max_ls;
 };
 
-__device__ __forceinline__ void wsync() { __syncthreads(); }         // one wavefront per workgroup
+__device__ __forceinline__ void wsync() { __syncthreads(); }         // one or two wavefronts per workgroup
 
 __device__ __forceinline__ double wave_max(double v) {
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
@@ -45,172 +44,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 }  // namespace
-
-// TERRAIN = false: flat ground (cimpc_plant_step).  TERRAIN = true: robot rb stands on terrain[n_terrain == 1 ? 0 : rb]; a flat
-// robot still evaluates plant_residual, so its step is the TERRAIN = false one (a uniform branch per robot).
-template <bool TERRAIN>
-__global__ __launch_bounds__(64) void plant_step_kernel(PlantModel M, PlantOpts o, int B, const double* q0, const double* q1,
-                                                        const double* u, const double* w, double mu, double h, double* q2,
-                                                        double* gamma, double* bb, int* status, int* iters,
-                                                        const cimpc_terrain* terrain, int n_terrain) {
-    __shared__ double A[NZM * LDA];
-    __shared__ double zs[NZM], rs[NZM], ds[NZM], xs[NZM], ths[2 * PLANT_MAX_Q + PLANT_MAX_U + PLANT_NW + 2];
-    __shared__ int piv[NZM];
-    __shared__ cimpc_terrain ter;
-    const int rb = blockIdx.x, lane = threadIdx.x;
-    if (rb >= B) return;
-    bool rough = false;
-    if constexpr (TERRAIN) {
-        static_assert(sizeof(cimpc_terrain) % sizeof(double) == 0 && sizeof(cimpc_terrain) / sizeof(double) <= 64, "one word per lane");
-        const double* src = reinterpret_cast<const double*>(terrain + (n_terrain == 1 ? 0 : rb));
-        if (lane < (int)(sizeof(cimpc_terrain) / sizeof(double))) reinterpret_cast<double*>(&ter)[lane] = src[lane];
-        wsync();
-        rough = ter.kind != CIMPC_TERRAIN_FLAT || M.kind == PLANT_KIND_PARTICLE_2D;
-    }
-    auto residual = [&](const auto* zz, double kappa, auto* rr) {
-        using T = std::remove_const_t<std::remove_pointer_t<decltype(zz)>>;
-        if constexpr (TERRAIN) {
-            if (rough) { plant_residual_terrain<T>(M, ter, zz, ths, kappa, rr); return; }
-        }
-        plant_residual<T>(M, zz, ths, kappa, rr);
-    };
-    const int nq = M.nq, nu = M.nu, nz = M.nz(), ny = 2 * M.nc + M.nb(), nxy = nq + ny;
-    // θ = [q0; q1; u1; w1; μ; h], z = (q1, 1, ..., 1)
-    for (int i = lane; i < M.nth(); i += 64) {
-        double v;
-        if (i < nq) v = q0[(size_t)rb * nq + i];
-        else if (i < 2 * nq) v = q1[(size_t)rb * nq + i - nq];
-        else if (i < 2 * nq + nu) v = u[(size_t)rb * nu + i - 2 * nq];
-        else if (i < 2 * nq + nu + M.nw) v = w ? w[(size_t)rb * M.nw + i - 2 * nq - nu] : 0.0;
-        else v = (i == 2 * nq + nu + M.nw) ? mu : h;
-        ths[i] = v;
-    }
-    for (int i = lane; i < nz; i += 64) zs[i] = i < nq ? q1[(size_t)rb * nq + i] : 1.0;
-    wsync();
-
-    // residual at the current z with bilinear target kappa -> rs (every lane evaluates; lane 0 stores)
-    auto eval_r = [&](double kappa, double* out) {
-        double zl[NZM], rl[NZM];
-        for (int i = 0; i < nz; ++i) zl[i] = zs[i];
-        residual(zl, kappa, rl);
-        if (lane == 0) for (int i = 0; i < nz; ++i) out[i] = rl[i];
-        wsync();
-    };
-    auto violations = [&](const double* r, double& r_vio, double& k_vio) {
-        double a = 0.0, c = 0.0;
-        for (int i = lane; i < nz; i += 64) { const double v = fabs(r[i]); if (i < nxy) a = fmax(a, v); else c = fmax(c, v); }
-        r_vio = wave_max(a); k_vio = wave_max(c);
-    };
-    // largest a in (0, 1] with y - a dy >= (1 - tau) y on the complementarity pairs
-    auto step_length = [&](const double* D, double tau) {
-        double a = 1.0;
-        for (int i = nq + lane; i < nz; i += 64) { const double dy = D[i]; if (dy > 0.0) a = fmin(a, tau * zs[i] / dy); }
-        return wave_min(a);
-    };
-    // A = dr/dz at zs (a lane evaluates columns lane, lane + 64: nz <= 66), then LU with partial pivoting (rows lane, lane + 64)
-    auto factorize = [&]() {
-        for (int col = lane; col < nz; col += 64) {
-            Dual zl[NZM], rl[NZM];
-            for (int i = 0; i < nz; ++i) zl[i] = {zs[i], i == col ? 1.0 : 0.0};
-            residual(zl, 0.0, rl);
-            for (int i = 0; i < nz; ++i) A[i * LDA + col] = rl[i].d;
-        }
-        wsync();
-        for (int k = 0; k < nz; ++k) {
-            // pivot: largest |A[i][k]|, i >= k (ties: smallest row)
-            double best = -1.0;
-            int bi = lane;
-            for (int row = lane; row < nz; row += 64)
-                if (row >= k) { const double v = fabs(A[row * LDA + k]); if (v > best) { best = v; bi = row; } }
-            for (int off = 32; off > 0; off >>= 1) {
-                const double ob = __shfl_xor(best, off, 64);
-                const int oi = __shfl_xor(bi, off, 64);
-                if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-            }
-            const int p = bi;
-            if (lane == 0) piv[k] = p;
-            if (p != k)                                                // swap rows k and p (a lane takes columns lane, lane + 64)
-                for (int col = lane; col < nz; col += 64) {
-                    const double t0 = A[k * LDA + col];
-                    A[k * LDA + col] = A[p * LDA + col];
-                    A[p * LDA + col] = t0;
-                }
-            wsync();
-            for (int row = lane; row < nz; row += 64)
-                if (row > k) {
-                    const double l = A[row * LDA + k] / A[k * LDA + k];
-                    A[row * LDA + k] = l;
-                    for (int j = k + 1; j < nz; ++j) A[row * LDA + j] = fma(-l, A[k * LDA + j], A[row * LDA + j]);
-                }
-            wsync();
-        }
-    };
-    // x <- A^-1 x (x in LDS, nz entries)
-    auto solve = [&](double* x) {
-        if (lane == 0) for (int k = 0; k < nz; ++k) { const int p = piv[k]; if (p != k) { const double t0 = x[k]; x[k] = x[p]; x[p] = t0; } }
-        wsync();
-        for (int k = 0; k < nz; ++k) {                                 // L y = P x
-            const double xk = x[k];
-            for (int row = lane; row < nz; row += 64) if (row > k) x[row] = fma(-A[row * LDA + k], xk, x[row]);
-            wsync();
-        }
-        for (int k = nz - 1; k >= 0; --k) {                            // U x = y
-            if (lane == (k & 63)) x[k] = x[k] / A[k * LDA + k];
-            wsync();
-            const double xk = x[k];
-            for (int row = lane; row < k; row += 64) x[row] = fma(-A[row * LDA + k], xk, x[row]);
-            wsync();
-        }
-    };
-
-    eval_r(0.0, rs);
-    double r_vio, k_vio;
-    violations(rs, r_vio, k_vio);
-    int it = 0;
-    for (int n = 0; n < o.max_iter; ++n) {
-        if (r_vio < o.r_tol && k_vio < o.kappa_tol) break;
-        ++it;
-        factorize();
-        for (int i = lane; i < nz; i += 64) ds[i] = rs[i];
-        wsync();
-        solve(ds);                                                     // predictor
-        const double a_aff = step_length(ds, 1.0);
-        double s_mu = 0.0, s_aff = 0.0;
-        for (int t = lane; t < ny; t += 64) {
-            const double y1 = zs[nq + t], y2 = zs[nq + ny + t];
-            s_mu += y1 * y2;
-            s_aff += (y1 - a_aff * ds[nq + t]) * (y2 - a_aff * ds[nq + ny + t]);
-        }
-        const double mu_c = wave_sum(s_mu) / ny, mu_aff = wave_sum(s_aff) / ny;
-        double sg = fmin(fmax(mu_aff / mu_c, 0.0), 1.0);
-        sg = sg * sg * sg;
-        const double kc = fmax(sg * mu_c, o.kc_floor);
-        eval_r(kc, xs);                                                // corrector residual + the second-order term
-        for (int t = lane; t < ny; t += 64) xs[nq + ny + t] += ds[nq + t] * ds[nq + ny + t];
-        wsync();
-        solve(xs);
-        const double vm = fmax(r_vio, k_vio);
-        const double tau = fmax(1.0 - o.eps_min, 1.0 - vm * vm);
-        const double alpha = step_length(xs, tau);
-        if (alpha < o.stall_alpha) break;
-        for (int i = lane; i < nz; i += 64) zs[i] -= alpha * xs[i];
-        wsync();
-        double r_c = 0.0, k_c = 0.0, back = alpha;
-        for (int s = 1; s <= o.max_ls; ++s) {
-            eval_r(0.0, rs);
-            violations(rs, r_c, k_c);
-            if (r_c <= r_vio || k_c <= k_vio) break;
-            back *= o.ls_scale;                                        // alpha * ls_scale^s
-            for (int i = lane; i < nz; i += 64) zs[i] += back * xs[i];
-            wsync();
-        }
-        r_vio = r_c; k_vio = k_c;
-    }
-    for (int i = lane; i < nq; i += 64) q2[(size_t)rb * nq + i] = zs[i];
-    for (int i = lane; i < M.nc; i += 64) gamma[(size_t)rb * M.nc + i] = zs[nq + i];
-    for (int i = lane; i < M.nb(); i += 64) bb[(size_t)rb * M.nb() + i] = zs[nq + M.nc + i];
-    if (lane == 0) { status[rb] = (r_vio < o.r_tol && k_vio < o.kappa_tol) ? 1 : 0; iters[rb] = it; }
-}
 
 // Reductions over the NT lanes of one robot: one wavefront (NT = 64) or two (NT = 128, combined through the two LDS words red[]).
 template <int NT>
@@ -247,17 +80,48 @@ __device__ __forceinline__ double lanes_sum(double v, double* red) {
     return v;
 }
 
-// The step of plant_step_kernel for one robot on NT lanes (lane = threadIdx.x), sized by NZ: the same iteration, with reductions
-// over both wavefronts when NT = 128.  plant_step_kernel keeps its own copy: routing it through this template changed its
-// generated code, which is held byte-identical.  The LDS arrays are the caller's: A (NZ x NZ + 1),
-// zs, rs, ds, xs (NZ), ths (θ), piv (NZ + 2), red (2).  residual(z, kappa, r) evaluates the model on double or Dual.
-template <int NZ, int NT, class Residual>
-__device__ __forceinline__ void plant_ip_step(const PlantModel& M, const PlantOpts& o, int rb, const double* q0, const double* q1,
-                                              const double* u, const double* w, double mu, double h, double* q2, double* gamma,
-                                              double* bb, int* status, int* iters, double* A, double* zs, double* rs, double* ds,
-                                              double* xs, double* ths, int* piv, double* red, Residual residual) {
+// The ground a kernel instantiation stands on.  FLAT: plant_residual (cimpc_plant_step).  TERRAIN: robot rb stands on
+// terrain[n_terrain == 1 ? 0 : rb]; a flat robot still evaluates plant_residual, so its step is the FLAT one (a uniform branch per
+// robot).  ENV: plant_residual_centroidal_env on flat ground, centroidal_quadruped_box (NZ = 66, one wavefront) and
+// centroidal_quadruped_wall (NZ = 114, two wavefronts: lane j evaluates Jacobian column j, and the 114 x 115 LU stays in LDS).
+enum { GROUND_FLAT, GROUND_TERRAIN, GROUND_ENV };
+
+// One simulator step of robot blockIdx.x on NT lanes, sized by NZ (A is NZ x NZ + 1): the only statement of the iteration, with
+// reductions over both wavefronts when NT = 128.  Four instantiations: (66, 64, FLAT), (66, 64, TERRAIN), (66, 64, ENV) for the box
+// and (114, 128, ENV) for the wall.  The iteration names the LDS arrays directly: handed to a helper as pointers they cost the
+// TERRAIN instantiation 8-15 %.
+template <int NZ, int NT, int GROUND>
+__global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts o, int B, const double* q0, const double* q1,
+                                                        const double* u, const double* w, double mu, double h, double* q2,
+                                                        double* gamma, double* bb, int* status, int* iters,
+                                                        const cimpc_terrain* terrain, int n_terrain) {
+    static_assert(NT == 64 || NT == 128, "one or two wavefronts per robot");
+    __shared__ double A[NZ * (NZ + 1)];
+    __shared__ double zs[NZ], rs[NZ], ds[NZ], xs[NZ], ths[2 * PLANT_MAX_Q + PLANT_MAX_U + PLANT_NW + 2], red[2];
+    __shared__ int piv[NZ + 2];                                        // + the two wavefronts' pivot rows
+    __shared__ cimpc_terrain ter;
+    const int rb = blockIdx.x, lane = threadIdx.x;
+    if (rb >= B) return;
+    bool rough = false;
+    if constexpr (GROUND == GROUND_TERRAIN) {
+        static_assert(sizeof(cimpc_terrain) % sizeof(double) == 0 && sizeof(cimpc_terrain) / sizeof(double) <= 64, "one word per lane");
+        const double* src = reinterpret_cast<const double*>(terrain + (n_terrain == 1 ? 0 : rb));
+        if (lane < (int)(sizeof(cimpc_terrain) / sizeof(double))) reinterpret_cast<double*>(&ter)[lane] = src[lane];
+        wsync();
+        rough = ter.kind != CIMPC_TERRAIN_FLAT || M.kind == PLANT_KIND_PARTICLE_2D;
+    }
+    auto residual = [&](const auto* zz, double kappa, auto* rr) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(zz)>>;
+        if constexpr (GROUND == GROUND_ENV) {
+            plant_residual_centroidal_env<T>(M, zz, ths, kappa, rr);
+        } else {
+            if constexpr (GROUND == GROUND_TERRAIN) {
+                if (rough) { plant_residual_terrain<T>(M, ter, zz, ths, kappa, rr); return; }
+            }
+            plant_residual<T>(M, zz, ths, kappa, rr);
+        }
+    };
     constexpr int LD = NZ + 1;
-    const int lane = threadIdx.x;
     const int nq = M.nq, nu = M.nu, nz = M.nz(), ny = 2 * M.nc + M.nb(), nxy = nq + ny;
     // θ = [q0; q1; u1; w1; μ; h], z = (q1, 1, ..., 1)
     for (int i = lane; i < M.nth(); i += NT) {
@@ -403,25 +267,6 @@ __device__ __forceinline__ void plant_ip_step(const PlantModel& M, const PlantOp
     for (int i = lane; i < M.nb(); i += NT) bb[(size_t)rb * M.nb() + i] = zs[nq + M.nc + i];
     if (lane == 0) { status[rb] = (r_vio < o.r_tol && k_vio < o.kappa_tol) ? 1 : 0; iters[rb] = it; }
 }
-
-// centroidal_quadruped_box (NZ = 66, one wavefront) and centroidal_quadruped_wall (NZ = 114, two wavefronts: lane j evaluates
-// Jacobian column j, and the 114 x 115 LU stays in LDS): plant_residual_centroidal_env on flat ground.
-template <int NZ, int NT>
-__global__ __launch_bounds__(NT) void plant_step_env_kernel(PlantModel M, PlantOpts o, int B, const double* q0, const double* q1,
-                                                            const double* u, const double* w, double mu, double h, double* q2,
-                                                            double* gamma, double* bb, int* status, int* iters) {
-    static_assert(NT == 64 || NT == 128, "one or two wavefronts per robot");
-    __shared__ double A[NZ * (NZ + 1)];
-    __shared__ double zs[NZ], rs[NZ], ds[NZ], xs[NZ], ths[2 * PLANT_MAX_Q + PLANT_MAX_U + PLANT_NW + 2], red[2];
-    __shared__ int piv[NZ + 2];                                        // + the two wavefronts' pivot rows
-    const int rb = blockIdx.x;
-    if (rb >= B) return;
-    auto residual = [&](const auto* zz, double kappa, auto* rr) {
-        using T = std::remove_const_t<std::remove_pointer_t<decltype(zz)>>;
-        plant_residual_centroidal_env<T>(M, zz, ths, kappa, rr);
-    };
-    plant_ip_step<NZ, NT>(M, o, rb, q0, q1, u, w, mu, h, q2, gamma, bb, status, iters, A, zs, rs, ds, xs, ths, piv, red, residual);
-}
 constexpr int NZ_WALL = PLANT_MAX_Q + 4 * PLANT_WALL_NC + 2 * PLANT_WALL_NB;      // 114
 
 }  // namespace cimpc
@@ -455,21 +300,17 @@ bool plant_grow(T** p, size_t* cap, size_t need) {
 
 namespace {
 // Both entry points: validate, pick the model, stage inputs on the device's private stream, launch, read back.  terrain = nullptr
-// (or every terrain flat on a model cimpc_plant_step has) runs plant_step_kernel<false>, the flat step; the box and the wall (flat
-// only) run their plant_step_env_kernel instantiations.
+// (or every terrain flat on a model cimpc_plant_step has) runs the GROUND_FLAT instantiation; the box and the wall (flat only) run
+// their GROUND_ENV instantiations.
 int plant_step_impl(int model, int B, int n_terrain, const cimpc_terrain* terrain, const double* q0, const double* q1,
                     const double* u, const double* w, double mu, double h, const cimpc_ip_opts* opts, double* q2, double* gamma,
                     double* b, int* status, int* iters) {
     using namespace cimpc;
     if (B <= 0 || !q0 || !q1 || !u || !opts || !q2 || !gamma || !b || !status || !iters || h <= 0.0) return CIMPC_ERR_INVALID;
-    if (model < CIMPC_PLANT_QUADRUPED || model > CIMPC_PLANT_CENTROIDAL_WALL || (model == CIMPC_PLANT_PARTICLE_2D && !terrain))
-        return CIMPC_ERR_INVALID;
+    PlantModel M{};
+    if (!plant_model_by_id(model, &M) || (model == CIMPC_PLANT_PARTICLE_2D && !terrain)) return CIMPC_ERR_INVALID;
     if (opts->max_iter <= 0 || opts->max_ls < 0 || !(opts->r_tol > 0.0) || !(opts->kappa_tol > 0.0) || !(opts->ls_scale > 0.0 && opts->ls_scale < 1.0))
         return CIMPC_ERR_INVALID;
-    const PlantModel M = model == CIMPC_PLANT_QUADRUPED ? plant_quadruped() : model == CIMPC_PLANT_FLAMINGO ? plant_flamingo()
-                         : model == CIMPC_PLANT_HOPPER_2D ? plant_hopper_2d() : model == CIMPC_PLANT_PARTICLE ? plant_particle()
-                         : model == CIMPC_PLANT_PARTICLE_2D ? plant_particle_2d() : model == CIMPC_PLANT_CENTROIDAL_BOX ? plant_centroidal_box()
-                         : model == CIMPC_PLANT_CENTROIDAL_WALL ? plant_centroidal_wall() : plant_centroidal(model == CIMPC_PLANT_CENTROIDAL);
     bool rough = model == CIMPC_PLANT_PARTICLE_2D;
     if (terrain) {
         if (n_terrain != 1 && n_terrain != B) return CIMPC_ERR_INVALID;
@@ -509,19 +350,14 @@ int plant_step_impl(int model, int B, int n_terrain, const cimpc_terrain* terrai
     if (ok && w) ok = hipMemcpyAsync(dw, w, (size_t)B * M.nw * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
     if (ok && rough) ok = hipMemcpyAsync(W.d_ter, terrain, (size_t)n_terrain * sizeof(cimpc_terrain), hipMemcpyHostToDevice, st) == hipSuccess;
     if (ok) {
-        const bool env = M.kind == PLANT_KIND_CENTROIDAL_BOX || M.kind == PLANT_KIND_CENTROIDAL_WALL;
-        if (rough && !env)
-            hipLaunchKernelGGL(plant_step_kernel<true>, dim3(B), dim3(64), 0, st, M, o, B, dq0, dq1, du, w ? dw : nullptr, mu, h, dq2, dg, db,
-                               d_st, d_st + B, W.d_ter, n_terrain);
-        else if (!env)
-            hipLaunchKernelGGL(plant_step_kernel<false>, dim3(B), dim3(64), 0, st, M, o, B, dq0, dq1, du, w ? dw : nullptr, mu, h, dq2, dg, db,
-                               d_st, d_st + B, (const cimpc_terrain*)nullptr, 0);
-        else if (M.kind == PLANT_KIND_CENTROIDAL_BOX)
-            hipLaunchKernelGGL((plant_step_env_kernel<NZM, 64>), dim3(B), dim3(64), 0, st, M, o, B, dq0, dq1, du, w ? dw : nullptr, mu, h, dq2,
-                               dg, db, d_st, d_st + B);
-        else
-            hipLaunchKernelGGL((plant_step_env_kernel<NZ_WALL, 128>), dim3(B), dim3(128), 0, st, M, o, B, dq0, dq1, du, w ? dw : nullptr, mu,
-                               h, dq2, dg, db, d_st, d_st + B);
+        auto launch = [&](auto kernel, int nt) {
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(nt), 0, st, M, o, B, dq0, dq1, du, w ? dw : nullptr, mu, h, dq2, dg, db, d_st, d_st + B,
+                               rough ? W.d_ter : nullptr, rough ? n_terrain : 0);
+        };
+        if (M.kind == PLANT_KIND_CENTROIDAL_BOX) launch(plant_step_kernel<NZM, 64, GROUND_ENV>, 64);
+        else if (M.kind == PLANT_KIND_CENTROIDAL_WALL) launch(plant_step_kernel<NZ_WALL, 128, GROUND_ENV>, 128);
+        else if (rough) launch(plant_step_kernel<NZM, 64, GROUND_TERRAIN>, 64);
+        else launch(plant_step_kernel<NZM, 64, GROUND_FLAT>, 64);
         ok = hipGetLastError() == hipSuccess;
     }
     if (ok) ok = hipMemcpyAsync(q2, dq2, B * nq * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&

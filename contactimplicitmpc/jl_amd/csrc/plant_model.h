@@ -141,9 +141,7 @@ PLANT_HD void plant_centroidal_derivatives(const PlantModel& M, const T* v, T* d
     for (int i = 6; i < 18; ++i) { d2[i] = mf * v[i]; d1[i] = pconst<T>((i % 3) == 2 ? -mf * M.g : 0.0); }
 }
 // dyn += B(qm2)^T u: (sum u_i, sum R^T skew(r_i) u_i, -u_1 .. -u_4), centroidal_quadruped/model.jl:98-121 (the box and the wall
-// share it, centroidal_quadruped_box/model.jl:109-131, centroidal_quadruped_wall/model.jl:102-124).  plant_residual_centroidal
-// keeps its own inline copy of this and of plant_centroidal_dynamics: calling them changes the generated code of the existing
-// plant kernels, whose .text is held byte-identical.
+// share it, centroidal_quadruped_box/model.jl:109-131, centroidal_quadruped_wall/model.jl:102-124)
 template <class T>
 PLANT_HD void plant_centroidal_actuation(const T* qm2, const double* u1, T* dyn) {
     const T sa = psin(qm2[3]), ca = pcos(qm2[3]), sb = psin(qm2[4]), cb = pcos(qm2[4]), sc = psin(qm2[5]), cc = pcos(qm2[5]);
@@ -179,36 +177,12 @@ PLANT_HD void plant_centroidal_dynamics(const PlantModel& M, const T* q2, const 
 }
 template <class T>
 PLANT_HD void plant_residual_centroidal(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
-    constexpr int nq = 18, nu = 12, nc = 4, nb = 16;
-    const double* q0 = th; const double* q1 = th + nq; const double* u1 = th + 2 * nq; const double* w1 = u1 + nu;
-    const double mu = w1[3], h = w1[4];
+    constexpr int nq = 18, nc = 4, nb = 16;
+    const double* q1 = th + nq; const double mu = th[2 * nq + 12 + 3], h = th[2 * nq + 12 + 4];
     const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc; const T* psi = b + nb; const T* s1 = psi + nc;
     const T* eta = s1 + nc; const T* s2 = eta + nb;
-    T qm2[nq], vm1[nq], vm2[nq];
-    for (int i = 0; i < nq; ++i) { vm1[i] = pconst<T>((q1[i] - q0[i]) / h); qm2[i] = (q2[i] + q1[i]) * 0.5; vm2[i] = (q2[i] - q1[i]) / h; }
-    T a1[nq], b1[nq], a2[nq], b2[nq];
-    plant_centroidal_derivatives(M, vm1, a1, b1);
-    plant_centroidal_derivatives(M, vm2, a2, b2);
     T dyn[nq];
-    for (int i = 0; i < nq; ++i)
-        dyn[i] = (0.5 * h) * a1[i] + b1[i] + (0.5 * h) * a2[i] - b2[i] - (h * M.joint_friction[i]) * vm2[i];
-    {   // B(qm2)^T u
-        const T sa = psin(qm2[3]), ca = pcos(qm2[3]), sb = psin(qm2[4]), cb = pcos(qm2[4]), sc = psin(qm2[5]), cc = pcos(qm2[5]);
-        T R[3][3];
-        R[0][0] = ca * cb; R[0][1] = ca * sb * sc - sa * cc; R[0][2] = ca * sb * cc + sa * sc;
-        R[1][0] = sa * cb; R[1][1] = sa * sb * sc + ca * cc; R[1][2] = sa * sb * cc - ca * sc;
-        R[2][0] = -sb;     R[2][1] = cb * sc;                R[2][2] = cb * cc;
-        for (int f = 0; f < 4; ++f) {
-            const double ux = u1[3 * f], uy = u1[3 * f + 1], uz = u1[3 * f + 2];
-            const T rx = qm2[6 + 3 * f] - qm2[0], ry = qm2[7 + 3 * f] - qm2[1], rz = qm2[8 + 3 * f] - qm2[2];
-            // skew(r) u = r x u
-            const T cx = ry * uz - rz * uy, cy = rz * ux - rx * uz, cz = rx * uy - ry * ux;
-            dyn[0] = dyn[0] + ux; dyn[1] = dyn[1] + uy; dyn[2] = dyn[2] + uz;
-            for (int k = 0; k < 3; ++k) dyn[3 + k] = dyn[3 + k] + (R[0][k] * cx + R[1][k] * cy + R[2][k] * cz);      // R^T (r x u)
-            dyn[6 + 3 * f] = dyn[6 + 3 * f] - ux; dyn[7 + 3 * f] = dyn[7 + 3 * f] - uy; dyn[8 + 3 * f] = dyn[8 + 3 * f] - uz;
-        }
-    }
-    for (int i = 0; i < 3; ++i) dyn[i] = dyn[i] + w1[i];
+    plant_centroidal_dynamics(M, q2, th, dyn);
     for (int f = 0; f < nc; ++f) {
         const T* bf = b + 4 * f; const T* ef = eta + 4 * f;
         // J^T lambda: the foot's own coordinates, lambda = [m b; gamma]
@@ -237,7 +211,7 @@ PLANT_HD void plant_residual_centroidal(const PlantModel& M, const T* z, const d
 //   wall  nc 8: contacts 1-4 are the feet on the floor; 5-8 the same feet against the plane x = 0.25 (:87-99), phi = 0.25 - p_x,
 //         J rows = the feet's rows again (:132-145), force [-gamma; m b] on (x; y, z) (:147-160), tangential velocity
 //         m^T (v_y, v_z) (:162-173).
-// mass[1] = m_f; nc = 4 (box) or 8 (wall).  Not dispatched by plant_residual (the kinds have their own kernel instantiations).
+// mass[1] = m_f; nc = 4 (box) or 8 (wall).
 template <class T>
 PLANT_HD T plant_box_elevation(T x) {
     return 0.1 * (1.0 + ptanh(200.0 * (x - 0.25)));
@@ -704,6 +678,22 @@ inline PlantModel plant_flamingo() {           // flamingo/model.jl:458-495
     for (int i = 0; i < 6; ++i) { M.tq_a[i] = pairs[i][0]; M.tq_b[i] = pairs[i][1]; }
     for (int i = 0; i < 9; ++i) M.joint_friction[i] = 0.0;
     return M;
+}
+
+// CIMPC_PLANT_* id (include/cimpc.h) -> its model; false for any other id
+inline bool plant_model_by_id(int id, PlantModel* out) {
+    switch (id) {
+    case CIMPC_PLANT_QUADRUPED: *out = plant_quadruped(); return true;
+    case CIMPC_PLANT_FLAMINGO: *out = plant_flamingo(); return true;
+    case CIMPC_PLANT_HOPPER_2D: *out = plant_hopper_2d(); return true;
+    case CIMPC_PLANT_CENTROIDAL: *out = plant_centroidal(true); return true;
+    case CIMPC_PLANT_CENTROIDAL_UNDAMPED: *out = plant_centroidal(false); return true;
+    case CIMPC_PLANT_PARTICLE: *out = plant_particle(); return true;
+    case CIMPC_PLANT_PARTICLE_2D: *out = plant_particle_2d(); return true;
+    case CIMPC_PLANT_CENTROIDAL_BOX: *out = plant_centroidal_box(); return true;
+    case CIMPC_PLANT_CENTROIDAL_WALL: *out = plant_centroidal_wall(); return true;
+    default: return false;
+    }
 }
 
 }  // namespace cimpc

@@ -84,40 +84,40 @@ def plant_step(model: str, q0, q1, u, mu: float, h: float, w=None, opts: Interio
     return q2, g, b, st, it
 
 
-class OpenLoopDisturbance:
+class _OpenLoopSchedule:
+    """The reference's open-loop schedule: item k of a sequence held for N_sample simulator steps, each step returning
+    item / N_sample.  Called with the 1-based simulator step t; t = 1 rewinds."""
+
+    def __init__(self, items, N_sample: int):
+        self._items, self.N_sample = [np.asarray(x, dtype=np.float64) for x in items], int(N_sample)
+        self.idx, self.cnt = 0, self.N_sample
+
+    def __call__(self, t: int):
+        if t == 1:
+            self.idx, self.cnt = 0, self.N_sample
+        if self.cnt == self.N_sample:
+            self.idx += 1
+            self.cnt = 0
+        self.cnt += 1
+        return self._items[self.idx - 1] / self.N_sample
+
+
+class OpenLoopDisturbance(_OpenLoopSchedule):
     """open_loop_disturbances(w, N_sample), src/simulator/disturbances.jl:4-36: nominal disturbance w[k] (2,) or (B, 2) held for
     N_sample simulator steps, each step applying w[k] / N_sample.  Called with the 1-based simulator step t."""
 
     def __init__(self, w, N_sample: int):
-        self.w, self.N_sample = [np.asarray(x, dtype=np.float64) for x in w], int(N_sample)
-        self.idx, self.cnt = 0, self.N_sample
-
-    def __call__(self, t: int):
-        if t == 1:
-            self.idx, self.cnt = 0, self.N_sample
-        if self.cnt == self.N_sample:
-            self.idx += 1
-            self.cnt = 0
-        self.cnt += 1
-        return self.w[self.idx - 1] / self.N_sample
+        super().__init__(w, N_sample)
+        self.w = self._items
 
 
-class OpenLoopPolicy:
+class OpenLoopPolicy(_OpenLoopSchedule):
     """open_loop_policy(u; N_sample), src/simulator/policy.jl:4-34: nominal control u[k] held for N_sample simulator steps, each
     step applying u[k] / N_sample.  Usable as the `policy` of `simulate` through `lambda q: pol(t)` or called with the 1-based step."""
 
     def __init__(self, u, N_sample: int = 1):
-        self.u, self.N_sample = [np.asarray(x, dtype=np.float64) for x in u], int(N_sample)
-        self.idx, self.cnt = 0, self.N_sample
-
-    def __call__(self, t: int):
-        if t == 1:
-            self.idx, self.cnt = 0, self.N_sample
-        if self.cnt == self.N_sample:
-            self.idx += 1
-            self.cnt = 0
-        self.cnt += 1
-        return self.u[self.idx - 1] / self.N_sample
+        super().__init__(u, N_sample)
+        self.u = self._items
 
 
 class ImpulseDisturbance:

@@ -6,8 +6,8 @@
 int main() {
     int model; double kappa;
     if (scanf("%d %lf", &model, &kappa) != 2) return 1;
-    const cimpc::PlantModel M = model == 0 ? cimpc::plant_quadruped() : model == 1 ? cimpc::plant_flamingo() : model == 2 ? cimpc::plant_hopper_2d()
-                                : model == 5 ? cimpc::plant_particle() : cimpc::plant_centroidal(model == 3);
+    cimpc::PlantModel M{};
+    if (!cimpc::plant_model_by_id(model, &M)) return 1;
     const int nz = M.nz(), nth = M.nth();
     std::vector<double> z(nz), th(nth), r(nz);
     for (auto& v : z) if (scanf("%lf", &v) != 1) return 1;

@@ -32,8 +32,8 @@ int main() {
     for (double& v : E.brk) if (scanf("%lf", &v) != 1) return 1;
     for (double& v : E.off) if (scanf("%lf", &v) != 1) return 1;
     for (auto& row : E.coef) for (double& v : row) if (scanf("%lf", &v) != 1) return 1;
-    const cimpc::PlantModel M = model == 0 ? cimpc::plant_quadruped() : model == 1 ? cimpc::plant_flamingo() : model == 2 ? cimpc::plant_hopper_2d()
-                                : model == 5 ? cimpc::plant_particle() : model == 6 ? cimpc::plant_particle_2d() : cimpc::plant_centroidal(model == 3);
+    cimpc::PlantModel M{};
+    if (!cimpc::plant_model_by_id(model, &M)) return 1;
     if (!cimpc::terrain_valid_for(M, E)) { printf("invalid\n"); return 0; }
     const int nz = M.nz(), nth = M.nth();
     std::vector<double> z(nz), th(nth);

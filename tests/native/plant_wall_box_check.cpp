@@ -26,7 +26,8 @@ static void dump(int nz, const std::vector<double>& z, F eval) {
 int main() {
     int model; double kappa;
     if (scanf("%d %lf", &model, &kappa) != 2) return 1;
-    const cimpc::PlantModel M = model == CIMPC_PLANT_CENTROIDAL_BOX ? cimpc::plant_centroidal_box() : cimpc::plant_centroidal_wall();
+    cimpc::PlantModel M{};
+    if (!cimpc::plant_model_by_id(model, &M)) return 1;
     const int nz = M.nz(), nth = M.nth();
     std::vector<double> z(nz), th(nth);
     for (auto& v : z) if (scanf("%lf", &v) != 1) return 1;
