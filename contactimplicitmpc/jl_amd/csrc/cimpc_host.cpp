@@ -116,7 +116,7 @@ struct cimpc_ctx {
     double* h_stage = nullptr;   // pinned staging of cimpc_mpc_solve (window, reference, altitude in; trajectory out), allocated at its first call
     size_t h_stage_doubles = 0;
     bool advance_pending = false; // a cimpc_mpc_advance was queued on `stream` and not waited for (its staging word is in flight)
-    double* d_result = nullptr;  // end-of-solve result block (solve_finish_kernel): 8 + B (nu + 2) doubles
+    double* d_result = nullptr;  // end-of-solve result block (solve_finish_kernel): result_doubles(B, nu)
     double* h_result = nullptr;  // ... its pinned host copy, valid from the end of a solve to the next call that touches the state
     double* d_rhs = nullptr;   // B1 seam staging
     double* d_pstate = nullptr;   // parked interior-point iterates
@@ -144,16 +144,16 @@ struct cimpc_ctx {
     double* d_cf_ws = nullptr;
     double* d_dense_ws = nullptr;  // [B][N*N + 2N], allocated on first use
     double *d_V = nullptr, *d_qt = nullptr, *d_vt = nullptr;
-    int* d_ring = nullptr;       // [MAX_DEPTH][8] device counters per in-flight round (behind the queue counters: Q.count .. +ctl_ints)
+    int* d_ring = nullptr;       // the two round-counter blocks (behind the queue counters: queue_ctl, Q.count .. +ctl_ints)
     size_t ctl_ints = 0;
-    int* h_ring = nullptr;       // pinned, host-mapped: {n_sweep, n_kkt, stamp}
+    int* h_ring = nullptr;       // pinned, host-mapped ring (round_protocol.h: RingWord)
     int* h_ring_dev = nullptr;   // device pointer of h_ring
     // asynchronous single-launch solve (newton_async_impl.h)
     SchedulePlan sched{};        // launch shapes and paths of the solves (schedule_plan.h)
     bool async_dirty = true;     // the persistent kernel's queues may hold entries an aborted solve left behind
     int* a_items = nullptr;      // [K][a_cap] live interior-point queues
     int* a_jobs = nullptr;       // residual job entries, then KKT job entries
-    int* a_ctrl = nullptr;       // [count K][head K][rq_head rq_tail kq_head kq_tail n_done ...]
+    int* a_ctrl = nullptr;       // control block of the persistent solve (round_protocol.h: async_ctl)
     int* a_evals = nullptr;      // [B]
     long long* a_dbg = nullptr;  // [16] diagnostics (CIMPC_ASYNC_DEBUG)
     size_t a_cap = 0, a_rq_cap = 0, a_kq_cap = 0;
@@ -525,9 +525,10 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
         h->Q.K = (int)K; h->Q.cap = (int)cap; h->Q.par = 0;
         A(&h->Q.items, 2 * K * cap);
         // queue counters, queue heads and the round counters: ONE block, cleared by one memset at the start of a solve
-        h->ctl_ints = 3 * K * QPAD + 2 * 8 * CPAD;
+        const QueueCtl L = queue_ctl(K);
+        h->ctl_ints = L.ints;
         A(&h->Q.count, h->ctl_ints);
-        if (rc == CIMPC_OK) { h->Q.head = h->Q.count + 2 * K * QPAD; h->d_ring = h->Q.count + 3 * K * QPAD; }
+        if (rc == CIMPC_OK) { h->Q.head = h->Q.count + L.head; h->d_ring = h->Q.count + L.counters; }
         A(&h->Q.done_count, B * CS);
         A(&h->d_window, B * (H + 2));
         h->Q.window = h->d_window;
@@ -545,9 +546,9 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
     A(&h->d_vt, H * d.nq);
     A(&h->d_q0, 2 * B * d.nq);
     if (rc == CIMPC_OK) h->d_q1 = h->d_q0 + B * d.nq;
-    A(&h->d_result, 8 + B * (d.nu + 2));
+    A(&h->d_result, result_doubles(B, d.nu));
     if (rc == CIMPC_OK && (hipHostMalloc((void**)&h->h_qin, (2 * B + 1) * d.nq * sizeof(double), hipHostMallocDefault) != hipSuccess ||
-                           hipHostMalloc((void**)&h->h_result, (8 + B * (d.nu + 2)) * sizeof(double), hipHostMallocDefault) != hipSuccess))
+                           hipHostMalloc((void**)&h->h_result, result_doubles(B, d.nu) * sizeof(double), hipHostMallocDefault) != hipSuccess))
         rc = CIMPC_ERR_HIP;
     A(&h->d_rhs, B * h->N);
     NewtonDev& S = h->S;
@@ -572,13 +573,13 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
     A(&S.ls_iter, B); A(&S.newton_l, B); A(&S.stage, B); A(&S.need_sweep, BS);
     A(&S.kkt_list, 2 * B);
     A(&S.slot_list, 2 * BS);
-    A(&S.counters, 8 * CPAD);
+    A(&S.counters, ROUND_COUNTER_INTS);
     A(&S.stats, std::max<size_t>(B * 4, 64));      // (>= 32 entries: diagnostic builds with -DCIMPC_KKT_PROF park their phase clocks at [8..23])
     A(&S.ro_sweeps, B); A(&S.ro_ip_iters, B); A(&S.ro_ip_fail, B); A(&S.nlog, B * NLOG * 4);
     A(&S.kkt_ws, B * H * (3 * (size_t)h->nd * h->nd + h->nd));
-    A(&S.kkt_tw_xch, B * (3 * (size_t)h->nd * h->nd + 4 * h->nd));      // (= kkt_tw_xch_doubles(nd))
-    A(&S.kkt_tw_flags, B * 32);                                          // (= KKT_TW_FLAGS per rollout, one line each)
-    if (rc == CIMPC_OK && hipHostMalloc((void**)&h->h_counters, 8 * CPAD * sizeof(int)) != hipSuccess)
+    A(&S.kkt_tw_xch, B * kkt_tw_xch_doubles(h->nd));
+    A(&S.kkt_tw_flags, B * KKT_TW_FLAGS);
+    if (rc == CIMPC_OK && hipHostMalloc((void**)&h->h_counters, ROUND_COUNTER_INTS * sizeof(int)) != hipSuccess)
         rc = fail(h, CIMPC_ERR_HIP, "hipHostMalloc failed");
     if (rc != CIMPC_OK) {
         g_create_error = h->err;
@@ -597,7 +598,7 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
     S.spec_all = h->sched.spec_all; S.spec_first = h->sched.spec_first; S.spec_mid = h->sched.spec_mid;
     S.kkt_tw_nb = h->kn.kkt_tw_nb;
     S.kkt_tw_epoch = 0;
-    S.kkt_tw_spins = h->kn.kkt_tw_spins > 0 ? h->kn.kkt_tw_spins : (1 << 21);
+    S.kkt_tw_spins = h->kn.kkt_tw_spins > 0 ? h->kn.kkt_tw_spins : KKT_TW_SPINS;
     {
         int* dv = nullptr;
         if (hipHostMalloc((void**)&h->h_twfail, 4 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
@@ -607,14 +608,14 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
         h->h_twfail[0] = 0;
         S.kkt_tw_fail = dv;
     }
-    if (hipHostMalloc((void**)&h->h_ring, 32 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
+    if (hipHostMalloc((void**)&h->h_ring, RING_ALLOC_INTS * sizeof(int), hipHostMallocMapped) != hipSuccess ||
         hipHostGetDevicePointer((void**)&h->h_ring_dev, h->h_ring, 0) != hipSuccess) {
         g_create_error = "ring allocation failed"; cimpc_destroy(h); return CIMPC_ERR_HIP;
     }
     if (h->sched.async_on) {
         const size_t K = d.H_ref;
         if (dev_alloc(h, &h->a_items, K * h->a_cap) != CIMPC_OK || dev_alloc(h, &h->a_jobs, h->a_rq_cap + h->a_kq_cap) != CIMPC_OK ||
-            dev_alloc(h, &h->a_ctrl, 2 * K * QPAD + 64 + 33 * 16) != CIMPC_OK || dev_alloc(h, &h->a_evals, B) != CIMPC_OK) {
+            dev_alloc(h, &h->a_ctrl, async_ctl(K).ints) != CIMPC_OK || dev_alloc(h, &h->a_evals, B) != CIMPC_OK) {
             g_create_error = h->err; cimpc_destroy(h); return CIMPC_ERR_HIP;
         }
         if (h->kn.async_debug && dev_alloc(h, &h->a_dbg, 16) != CIMPC_OK) { g_create_error = h->err; cimpc_destroy(h); return CIMPC_ERR_HIP; }
@@ -965,14 +966,14 @@ int cimpc_implicit_dynamics(cimpc_handle h, const double* q, const double* theta
     }
     for (int pass = 0; pass < 64; ++pass) {
         const int par = pass & 1;
-        HIP_TRY(h, hipMemsetAsync(h->S.counters, 0, 8 * CPAD * sizeof(int), h->stream));
-        rc = run_sweep(h, par, h->S.counters + 2 * CPAD, z ? h->d_zout : nullptr, h->stream);
+        HIP_TRY(h, hipMemsetAsync(h->S.counters, 0, ROUND_COUNTER_INTS * sizeof(int), h->stream));
+        rc = run_sweep(h, par, round_counter(h->S.counters, RC_PARKED), z ? h->d_zout : nullptr, h->stream);
         if (rc != CIMPC_OK) return rc;
         HIP_TRY(h, hipMemsetAsync(h->Q.count + (size_t)par * h->Q.K * QPAD, 0, h->Q.K * QPAD * sizeof(int), h->stream));
         HIP_TRY(h, hipMemsetAsync(h->Q.head, 0, h->Q.K * QPAD * sizeof(int), h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->h_counters, h->S.counters + 2 * CPAD, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->h_counters, round_counter(h->S.counters, RC_PARKED), sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (h->h_counters[0] == 0) break;      // no solve was parked
+        if (*h->h_counters == 0) break;      // no solve was parked
     }
     auto down = [&](void* dst, const void* src, size_t row_bytes) {
         return hipMemcpy2DAsync(dst, row_bytes, src, CS * row_bytes, row_bytes, B, hipMemcpyDeviceToHost, h->stream);
@@ -1068,6 +1069,212 @@ int cimpc_kkt_solve_rho(cimpc_handle h, const double* r, double rho, double* del
     return cimpc_kkt_solve(h, r, beta, delta);
 }
 
+namespace {
+
+// What a round's last decision block published in its slot of the host ring (round_protocol.h: RingWord; new_slots is
+// deterministic: slots that only wait for a parked solve are re-listed, not re-requested)
+struct RoundCounts { int sweep, kkt, slots, new_slots, parked, finished; };
+RoundCounts read_round_counts(const int* ring, long long round) {
+    const volatile int* hr = ring_slot((const volatile int*)ring, round);
+    return {hr[RING_N_SWEEP], hr[RING_N_KKT], hr[RING_SLOTS], hr[RING_NEW_SLOTS], hr[RING_PARKED], hr[RING_FINISHED]};
+}
+
+// What one cimpc_newton_solve_dev call carries from step to step
+struct SolveRun {
+    const double *q0_dev, *q1_dev; int warm_start;
+    std::chrono::steady_clock::time_point t0;
+    int tw_fail0;          // time-outs of the twisted kernels' hand-overs before this solve
+    bool hybrid;
+    RoundStreams sb;       // the library's private streams, or the caller's stream as sb.st when one was given
+    RoundCounts last;      // counts of the last completed round (before the first: what the reset kernel requests)
+};
+
+bool has_time_budget(const cimpc_ctx* h) { return h->nt.max_time > 0.0 && h->nt.max_time < 1.0e6; }
+double elapsed_s(const SolveRun& run) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - run.t0).count(); }
+bool over_budget(const cimpc_ctx* h, const SolveRun& run) { return h->nt.max_time > 0.0 && elapsed_s(run) >= h->nt.max_time; }
+// hand-overs of the twisted kernels that timed out since the host last looked: their KKT stages are repeated one-ended.  Returns the counter.
+int note_tw_fallbacks(cimpc_ctx* h) {
+    const int cur = *(volatile int*)h->h_twfail;
+    if (cur != h->twfail_seen) { h->n_kkt_tw_fallbacks += cur - h->twfail_seen; h->twfail_seen = cur; }
+    return cur;
+}
+
+// S as the launches of a round of this parity see it: the whole batch, the parity's counter block, ring slot and lock-step queue
+NewtonDev launch_view(const cimpc_ctx* h, int parity) {
+    NewtonDev Sk = h->S;
+    Sk.b0 = 0; Sk.nb_launch = h->dm.B;
+    Sk.counters = round_counter_block(h->d_ring, parity);
+    Sk.counters_next = round_counter_block(h->d_ring, parity ^ 1);
+    Sk.host_flag = ring_slot(h->h_ring_dev, parity);
+    Sk.WQ = h->Q; Sk.WQ.par = parity;
+    return Sk;
+}
+// ... with the persistent kernel's own queues and job words, from the layout of its control block
+void wire_async_queues(const cimpc_ctx* h, NewtonDev& Sk) {
+    const AsyncCtl L = async_ctl(h->Q.K);
+    int* const c = h->a_ctrl;
+    Sk.WQ.items = h->a_items; Sk.WQ.cap = (int)h->a_cap; Sk.WQ.count = c + L.count; Sk.WQ.head = c + L.head;
+    AsyncQ& A = Sk.A;
+    A.on = 1;
+    A.rq_items = h->a_jobs; A.rq_head = c + L.rq_head; A.rq_tail = c + L.rq_tail;
+    A.kq_items = h->a_jobs + h->a_rq_cap; A.kq_head = c + L.kq_head; A.kq_tail = c + L.kq_tail;
+    A.n_done = c + L.n_done; A.epoch = c + L.epoch; A.evals_left = h->a_evals;
+    A.abort_flag = ring_abort_word((volatile int*)h->h_ring_dev);
+}
+
+// end of a solve: statistics, Newton iteration counts, r_norm and u_1 of every rollout in one block, one copy (queued on the
+// solve's stream; the caller synchronises)
+int finish_results(cimpc_ctx* h, hipStream_t st) {
+    if (launch_dz_commit(h->S, st) != CIMPC_OK) return fail(h, CIMPC_ERR_HIP, "sensitivity flush launch failed");
+    if (int rf = launch_solve_finish(h->S, h->d_result, st); rf != CIMPC_OK) return fail(h, rf, "result kernel launch failed");
+    HIP_TRY(h, hipMemcpyAsync(h->h_result, h->d_result, result_doubles(h->dm.B, h->dm.nu) * sizeof(double), hipMemcpyDeviceToHost, st));
+    return CIMPC_OK;
+}
+// ... and, once the copy has arrived, the statistics of the solve
+void publish_stats(cimpc_ctx* h, long long rounds) {
+    const double* r = h->h_result;
+    cimpc_stats& s = h->last_stats;
+    s.sweeps = (long long)r[RESULT_SWEEPS]; s.ip_solves = (long long)r[RESULT_IP_SOLVES];
+    s.ip_iters = (long long)r[RESULT_IP_ITERS]; s.ip_failures = (long long)r[RESULT_IP_FAILURES];
+    s.rounds = rounds; s.newton_iters = (long long)r[RESULT_NEWTON_SUM];
+}
+
+int print_async_debug(cimpc_ctx* h) {      // CIMPC_ASYNC_DEBUG: busy time and job counts of the persistent launch
+    long long dv[16];
+    HIP_TRY(h, hipMemcpy(dv, h->a_dbg, sizeof(dv), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[cimpc async] WG-ms: other %.2f kkt %.2f resid %.2f ip %.2f | jobs: kkt %lld resid %lld serve %lld | grid %d service %d | group-trips %.2fM active %.1f%% | group-ms pop %.1f fence %.1f | pop: cas %lld spins %lld claim-ms %.1f wait-ms %.1f\n",
+            dv[0] * 1e-5, dv[1] * 1e-5, dv[2] * 1e-5, dv[3] * 1e-5, dv[9], dv[10], dv[11], h->sched.async_grid, h->sched.async_service, dv[5] * 1e-6, dv[5] ? 100.0 * dv[4] / dv[5] : 0.0, dv[6] * 1e-5, dv[7] * 1e-5, dv[12], dv[13], dv[14] * 1e-5, dv[15] * 1e-5);
+    return CIMPC_OK;
+}
+// CIMPC_DEBUG_ROUNDS: the problems round r's sweep will find in its queues (a blocking read)
+void print_queued_problems(cimpc_ctx* h, const SolveRun& run, long long r, int par, long long hint) {
+    std::vector<int> qc((size_t)h->Q.K * QPAD);
+    (void)hipStreamSynchronize(run.sb.st); (void)hipStreamSynchronize(run.sb.st_kkt);
+    if (hipMemcpy(qc.data(), h->Q.count + (size_t)par * h->Q.K * QPAD, qc.size() * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return;
+    long long tot = 0;
+    for (int k = 0; k < h->Q.K; ++k) tot += qc[(size_t)k * QPAD];
+    fprintf(stderr, "[cimpc round %lld] sweep launch: %lld problems queued (host hint %lld)\n", r, tot, hint);
+}
+
+// ---- one persistent launch: every rollout advances on its own chain (newton_async_impl.h).  Entered
+//      from the start (from_reset) or with the rollouts the lock-step rounds left active (hybrid). ----
+int run_async(cimpc_ctx* h, SolveRun& run, bool from_reset, long long rounds_before) {
+    NewtonDev& S = h->S;
+    IpQueues LQ = h->Q; LQ.par = (int)(rounds_before & 1);      // lock-step queue of the round that would come next
+    hipStream_t st = run.sb.st;
+    if (h->async_dirty) {     // entries are reset by their consumers; only an aborted solve leaves some behind
+        HIP_TRY(h, hipMemsetAsync(h->a_items, 0xFF, (size_t)h->Q.K * h->a_cap * sizeof(int), st));
+        HIP_TRY(h, hipMemsetAsync(h->a_jobs, 0xFF, (h->a_rq_cap + h->a_kq_cap) * sizeof(int), st));
+        h->async_dirty = false;
+    }
+    HIP_TRY(h, hipMemsetAsync(h->a_ctrl, 0, async_ctl(h->Q.K).ints * sizeof(int), st));
+    volatile int* abort_word = ring_abort_word((volatile int*)h->h_ring);
+    *abort_word = 0;
+    NewtonDev Sk = launch_view(h, 0);
+    // the tail is latency-bound: its stragglers (rollouts that exhaust the line search in every iteration)
+    // evaluate all seven step lengths at once there, whatever the throughput-oriented setting of the rounds
+    if (!from_reset) Sk.spec_all = h->sched.spec_tail;
+    wire_async_queues(h, Sk);
+    AsyncQ& A = Sk.A;
+    A.n_service = from_reset ? h->sched.async_service : h->sched.tail_service;
+    A.idle_sleep = async_idle_sleep; A.idle_spins = async_idle_spins; A.wake_fan = async_wake_fan;
+    A.dbg = h->a_dbg; A.B = h->dm.B;
+    if (h->a_dbg) HIP_TRY(h, hipMemsetAsync(h->a_dbg, 0, 16 * sizeof(long long), st));
+    // KKT stage of the persistent kernel: one job, or two cooperating jobs (the chains of the twisted solve, newton_async_impl.h)
+    const KktSite site{.kind = from_reset ? KktSite::Persistent : KktSite::HybridTail, .tw_off = *(volatile int*)h->h_twfail != run.tw_fail0,
+                       .B = h->dm.B, .async_tail = h->sched.async_tail, .waves = std::min(h->sched.waves, 4)};
+    A.kkt_tw = plan_kkt_stage(h, site) == KktForm::AsyncTwoJob ? 1 : 0;
+    S.kkt_tw_epoch += h->nt.max_iter + 2;      // the launch's KKT stages take the stamps Sk.kkt_tw_epoch + 1 + (Newton iterations done)
+    prof_begin(h, PC_OTHER, st);
+    int rc2 = from_reset ? launch_reset(Sk, run.q0_dev, run.q1_dev, run.warm_start, st) : launch_async_handoff(Sk, LQ, st);
+    prof_end(h, st);
+    if (rc2 != CIMPC_OK) return fail(h, rc2, "reset / hand-off launch failed");
+    IpParams p = make_ip_params(h, S.cand, 0, round_counter(h->d_ring, RC_PARKED), nullptr);
+    if (S.dtn != nullptr) { p.nu = S.nu_cand; p.dtn = S.dtn; }
+    p.Q = Sk.WQ;
+    p.iter_cap = h->ip.max_iter + 1;      // no solve is parked (solves parked by the lock-step rounds resume and finish)
+    p.A = A;
+    long long solved_before = 0;      // interior-point problems the lock-step rounds had solved (profiling only)
+    if (h->prof_on && !from_reset) { long long sv[4]; if (int rs = read_stats(h, sv); rs != CIMPC_OK) return rs; solved_before = sv[1]; }
+    prof_begin(h, PC_ASYNC, st);
+    rc2 = launch_newton_async(&h->dm, p, Sk, std::min(h->sched.waves, 4), from_reset ? h->sched.async_grid : h->sched.tail_grid, st);
+    prof_end(h, st);
+    if (rc2 != CIMPC_OK) return fail(h, rc2, "asynchronous newton launch failed");
+    if (int rf = finish_results(h, st); rf != CIMPC_OK) return rf;      // (queued behind the persistent kernel)
+    // The host watches the persistent kernel: the reference's wall-clock budget ends the loop silently
+    // (newton.jl:187-277), and a watchdog turns a kernel that stopped making progress into an error
+    // instead of a hang (the kernel polls the host-mapped abort flag).
+    const bool budget = has_time_budget(h);
+    bool timed_out = false; long long polls = 0;
+    const auto tw = std::chrono::steady_clock::now();
+    while (hipStreamQuery(st) == hipErrorNotReady) {
+        const bool over = budget && over_budget(h, run);
+        timed_out = !over && (++polls & 0x3FF) == 0 && std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count() > h->kn.watchdog_s;
+        if (over || timed_out) { *abort_word = 1; h->async_dirty = true; break; }
+    }
+    HIP_TRY(h, hipStreamSynchronize(st));
+    note_tw_fallbacks(h);
+    if (timed_out) return fail(h, CIMPC_ERR_HIP, "asynchronous solve: watchdog expired (no completion within CIMPC_ASYNC_WATCHDOG_S)");
+    if (h->a_dbg) { if (int rd = print_async_debug(h); rd != CIMPC_OK) return rd; }
+    publish_stats(h, rounds_before + 1);
+    h->prof_ip_problems += solved_before;
+    h->prof_async_problems += h->last_stats.ip_solves - solved_before;
+    if (from_reset) h->prof_kkt_systems += h->last_stats.newton_iters;
+    return CIMPC_OK;
+}
+
+// Round r: [KKT for rollouts that start an iteration] || sweep -> residual of every evaluated slot -> line-search decision.
+// blind: launched ahead of the host's knowledge of round r - 1.
+int launch_round(cimpc_ctx* h, SolveRun& run, long long r, bool blind) {
+    const RoundStreams& sb = run.sb; const RoundCounts& last = run.last;
+    const int par = (int)(r & 1);      // round r consumes Q[par] and leaves the next round's requests in Q[par ^ 1]
+    h->S.kkt_tw_epoch += 1;      // stamp of this round's KKT stage (epoch-valued hand-over flags of the twisted kernels)
+    // a hand-over of a twisted kernel timed out earlier in this solve (its rollouts were queued again): one-ended kernels from here on
+    const bool tw_off = note_tw_fallbacks(h) != run.tw_fail0;
+    NewtonDev Sk = launch_view(h, par);
+    Sk.A.n_done = run.hybrid ? h->a_ctrl + async_ctl(h->Q.K).n_done : nullptr;
+    Sk.round_stamp = (int)(r + 1);
+    const bool kkt = (r > 0) && (blind || last.kkt > 0);
+    const int n_kkt = blind ? h->dm.B : last.kkt;
+    const int* n_kkt_dev = blind ? round_counter(Sk.counters_next, RC_KKT) : nullptr;      // the previous round's count of KKT requests
+    if (kkt) {
+        // KKT of the rollouts that start a Newton iteration (list of the previous round's decision kernel, its queue parity).  Small
+        // batches: latency matters, ahead of the sweep on its stream, the result kept in this round.  Overlapped: next to the sweep
+        // on its own stream, no fork event (every decision block of the previous round released its results before its ticket).
+        // (Launched BEFORE the sweep: the other order was measured 10 % / 20 % slower in rounds 1 / 3, 8.37 -> 10.05 ms - behind the
+        // persistent sweep the KKT workgroups wait for sweep workgroups to leave: profiles/r03/knob_order.log.)
+        const bool ov = h->kp.kkt_overlap;
+        const KktSite site{.kind = ov ? KktSite::Overlapped : KktSite::Round, .n_kkt = n_kkt, .blind = blind,
+                           .sweep_problems = (long long)last.new_slots * h->dm.H, .tw_off = tw_off, .B = h->dm.B};
+        hipStream_t kst = ov ? sb.st_kkt : sb.st;
+        if (!ov) Sk.kkt_same_round = 1;
+        prof_begin(h, PC_KKT, kst);
+        int rk = run_kkt_stage(h, Sk, kkt_newton_args(Sk), site, Sk.kkt_list + (size_t)(par ^ 1) * h->dm.B,
+                               ov ? last.kkt : n_kkt, ov ? nullptr : n_kkt_dev, kst);      // (overlapped: the host's count, blind rounds too)
+        prof_end(h, kst);
+        if (rk != CIMPC_OK) return fail(h, rk, "kkt launch failed");
+        if (ov && hipEventRecord(sb.ev_join, sb.st_kkt) != hipSuccess) return fail(h, CIMPC_ERR_HIP, "join record failed");
+    }
+    const RoundPlan rp = plan_round(h->kn.sched, h->sched, h->ip.max_iter, kkt, blind, last.sweep, last.slots);
+    // problems of this round as far as the host knows them: the evaluation slots requested + the solves the last sweep parked
+    const long long hint = blind ? -1 : (long long)last.slots * h->dm.H + last.parked;
+    if (h->kn.debug_rounds && !blind) print_queued_problems(h, run, r, par, hint);
+    int rr = run_sweep(h, par, round_counter(Sk.counters, RC_PARKED), nullptr, sb.st, rp.cap, round_counter(Sk.counters, RC_DRAINED), true, hint);
+    if (rr != CIMPC_OK) return rr;
+    prof_begin(h, PC_RESID, sb.st);
+    if (rp.split_join) {
+        rr = launch_resid_decide(Sk, sb.st, rp.n_slots, 1);
+        if (rr != CIMPC_OK) return fail(h, rr, "residual launch failed");
+    }
+    if (kkt && h->kp.kkt_overlap && hipStreamWaitEvent(sb.st, sb.ev_join, 0) != hipSuccess) return fail(h, CIMPC_ERR_HIP, "join failed");
+    rr = launch_resid_decide(Sk, sb.st, rp.n_slots, rp.split_join ? 2 : 0);
+    prof_end(h, sb.st);
+    if (rr != CIMPC_OK) return fail(h, rr, "residual launch failed");
+    return CIMPC_OK;
+}
+
+}  // namespace
+
 int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q1_dev, int warm_start) {
     int rc = check_ready(h, true);
     if (rc != CIMPC_OK) return rc;
@@ -1075,269 +1282,74 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
     HIP_TRY(h, hipSetDevice(h->device));
     if (int sy = sync_dz_stores(h, 1); sy != CIMPC_OK) return sy;
     h->dz_producer = 1;
-    NewtonDev& S = h->S;
-    const int tw_fail0 = *(volatile int*)h->h_twfail;      // time-outs of the twisted kernels' hand-overs before this solve
-    h->twfail_seen = tw_fail0;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto over_budget = [&]() {
-        if (h->nt.max_time <= 0.0) return false;
-        const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return el >= h->nt.max_time;
-    };
-    // the solve runs on the library's streams: they wait (on the device) for what the caller's stream holds - the uploads of
-    // q0 / q1 - instead of the host waiting for it
-    if (!h->external_stream) {
-        HIP_TRY(h, hipEventRecord(h->rs.ev_start, h->stream));
-        HIP_TRY(h, hipStreamWaitEvent(h->rs.st, h->rs.ev_start, 0));
+    const int B = h->dm.B;
+    SolveRun run{q0_dev, q1_dev, warm_start, {}, *(volatile int*)h->h_twfail, false, h->rs, RoundCounts{B, 0, B, B, 0, 0}};
+    h->twfail_seen = run.tw_fail0;
+    run.t0 = std::chrono::steady_clock::now();
+    // the solve runs on the caller's stream when one was given, else on the library's streams: they wait (on the device) for what
+    // the caller's stream holds - the uploads of q0 / q1 - instead of the host waiting for it
+    RoundStreams& sb = run.sb;
+    if (h->external_stream) sb.st = h->stream;
+    else {
+        HIP_TRY(h, hipEventRecord(sb.ev_start, h->stream));
+        HIP_TRY(h, hipStreamWaitEvent(sb.st, sb.ev_start, 0));
     }
-    HIP_TRY(h, hipMemsetAsync(S.stats, 0, (size_t)h->dm.B * 4 * sizeof(long long), h->external_stream ? h->stream : h->rs.st));
-    // end of a solve: statistics, Newton iteration counts, r_norm and u_1 of every rollout in one block, one copy (queued on the
-    // solve's stream; the caller synchronises)
-    auto finish_results = [&](hipStream_t st) -> int {
-        if (launch_dz_commit(S, st) != CIMPC_OK) return fail(h, CIMPC_ERR_HIP, "sensitivity flush launch failed");
-        int rf = launch_solve_finish(S, h->d_result, st);
-        if (rf != CIMPC_OK) return fail(h, rf, "result kernel launch failed");
-        HIP_TRY(h, hipMemcpyAsync(h->h_result, h->d_result, (8 + (size_t)h->dm.B * (h->dm.nu + 2)) * sizeof(double), hipMemcpyDeviceToHost, st));
-        return CIMPC_OK;
-    };
-    // ---- one persistent launch: every rollout advances on its own chain (newton_async_impl.h).  Entered
-    //      from the start (from_reset) or with the rollouts the lock-step rounds left active (hybrid). ----
-    auto run_async = [&](bool from_reset, long long rounds_before, int next_par = -1) -> int {
-        IpQueues LQ = h->Q; LQ.par = next_par >= 0 ? next_par : (int)(rounds_before & 1);      // lock-step queue of the round that would come next
-        hipStream_t st = h->external_stream ? h->stream : h->rs.st;
-        const size_t K = h->Q.K;
-        if (h->async_dirty) {     // entries are reset by their consumers; only an aborted solve leaves some behind
-            HIP_TRY(h, hipMemsetAsync(h->a_items, 0xFF, K * h->a_cap * sizeof(int), st));
-            HIP_TRY(h, hipMemsetAsync(h->a_jobs, 0xFF, (h->a_rq_cap + h->a_kq_cap) * sizeof(int), st));
-            h->async_dirty = false;
-        }
-        HIP_TRY(h, hipMemsetAsync(h->a_ctrl, 0, (2 * K * QPAD + 64 + 33 * 16) * sizeof(int), st));
-        volatile int* hm = (volatile int*)h->h_ring;
-        hm[3] = 0;
-        NewtonDev Sk = S;
-        Sk.b0 = 0; Sk.nb_launch = h->dm.B; Sk.counters = h->d_ring; Sk.counters_next = h->d_ring + 8 * CPAD;
-        Sk.host_flag = h->h_ring_dev;
-        // the tail is latency-bound: its stragglers (rollouts that exhaust the line search in every iteration)
-        // evaluate all seven step lengths at once there, whatever the throughput-oriented setting of the rounds
-        if (!from_reset) Sk.spec_all = h->sched.spec_tail;
-        Sk.WQ = h->Q; Sk.WQ.par = 0;
-        Sk.WQ.items = h->a_items; Sk.WQ.cap = (int)h->a_cap;
-        Sk.WQ.count = h->a_ctrl; Sk.WQ.head = h->a_ctrl + K * QPAD;
-        AsyncQ& A = Sk.A;
-        A.on = 1;
-        int* c = h->a_ctrl + 2 * K * QPAD;
-        A.rq_items = h->a_jobs; A.rq_head = c + 0; A.rq_tail = c + 16;
-        A.kq_items = h->a_jobs + h->a_rq_cap; A.kq_head = c + 32; A.kq_tail = c + 48;
-        A.n_done = c + 8;
-        A.epoch = c + 64;
-        A.evals_left = h->a_evals;
-        A.abort_flag = (volatile int*)(h->h_ring_dev + 3);
-        const int a_grid = from_reset ? h->sched.async_grid : h->sched.tail_grid;
-        A.n_service = from_reset ? h->sched.async_service : h->sched.tail_service;
-        A.idle_sleep = async_idle_sleep; A.idle_spins = async_idle_spins; A.wake_fan = async_wake_fan;
-        A.dbg = h->a_dbg;
-        if (h->a_dbg) HIP_TRY(h, hipMemsetAsync(h->a_dbg, 0, 16 * sizeof(long long), st));
-        A.B = h->dm.B;
-        // KKT stage of the persistent kernel: one job, or two cooperating jobs (the chains of the twisted solve, newton_async_impl.h)
-        const KktSite site{.kind = from_reset ? KktSite::Persistent : KktSite::HybridTail, .tw_off = *(volatile int*)h->h_twfail != tw_fail0,
-                           .B = h->dm.B, .async_tail = h->sched.async_tail, .waves = std::min(h->sched.waves, 4)};
-        A.kkt_tw = plan_kkt_stage(h, site) == KktForm::AsyncTwoJob ? 1 : 0;
-        S.kkt_tw_epoch += h->nt.max_iter + 2;      // the launch's KKT stages take the stamps Sk.kkt_tw_epoch + 1 + (Newton iterations done)
-        prof_begin(h, PC_OTHER, st);
-        int rc2 = from_reset ? launch_reset(Sk, q0_dev, q1_dev, warm_start, st) : launch_async_handoff(Sk, LQ, st);
-        prof_end(h, st);
-        if (rc2 != CIMPC_OK) return fail(h, rc2, "reset / hand-off launch failed");
-        IpParams p = make_ip_params(h, S.cand, 0, h->d_ring + 2 * CPAD, nullptr);
-        if (S.dtn != nullptr) { p.nu = S.nu_cand; p.dtn = S.dtn; }
-        p.Q = Sk.WQ;
-        p.iter_cap = h->ip.max_iter + 1;      // no solve is parked (solves parked by the lock-step rounds resume and finish)
-        p.A = A;
-        long long solved_before = 0;      // interior-point problems the lock-step rounds had solved (profiling only)
-        if (h->prof_on && !from_reset) { long long sv[4]; if (int rs = read_stats(h, sv); rs != CIMPC_OK) return rs; solved_before = sv[1]; }
-        prof_begin(h, PC_ASYNC, st);
-        rc2 = launch_newton_async(&h->dm, p, Sk, std::min(h->sched.waves, 4), a_grid, st);
-        prof_end(h, st);
-        if (rc2 != CIMPC_OK) return fail(h, rc2, "asynchronous newton launch failed");
-        if (int rf = finish_results(st); rf != CIMPC_OK) return rf;      // (queued behind the persistent kernel)
-        // The host watches the persistent kernel: the reference's wall-clock budget ends the loop silently
-        // (newton.jl:187-277), and a watchdog turns a kernel that stopped making progress into an error
-        // instead of a hang (the kernel polls the host-mapped abort flag).
-        const double watchdog_s = h->kn.watchdog_s;
-        const bool budget = h->nt.max_time > 0.0 && h->nt.max_time < 1.0e6;
-        bool timed_out = false;
-        const auto tw = std::chrono::steady_clock::now();
-        long long polls = 0;
-        while (hipStreamQuery(st) == hipErrorNotReady) {
-            if (budget && over_budget()) { hm[3] = 1; h->async_dirty = true; break; }
-            if ((++polls & 0x3FF) == 0 &&
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count() > watchdog_s) {
-                hm[3] = 1; h->async_dirty = true; timed_out = true; break;
-            }
-        }
-        HIP_TRY(h, hipStreamSynchronize(st));
-        if (const int twf = *(volatile int*)h->h_twfail; twf != h->twfail_seen) { h->n_kkt_tw_fallbacks += twf - h->twfail_seen; h->twfail_seen = twf; }
-        if (timed_out) return fail(h, CIMPC_ERR_HIP, "asynchronous solve: watchdog expired (no completion within CIMPC_ASYNC_WATCHDOG_S)");
-        if (h->a_dbg) {
-            long long dv[16];
-            HIP_TRY(h, hipMemcpy(dv, h->a_dbg, sizeof(dv), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[cimpc async] WG-ms: other %.2f kkt %.2f resid %.2f ip %.2f | jobs: kkt %lld resid %lld serve %lld | grid %d service %d | group-trips %.2fM active %.1f%% | group-ms pop %.1f fence %.1f | pop: cas %lld spins %lld claim-ms %.1f wait-ms %.1f\n",
-                    dv[0] * 1e-5, dv[1] * 1e-5, dv[2] * 1e-5, dv[3] * 1e-5, dv[9], dv[10], dv[11], h->sched.async_grid, h->sched.async_service, dv[5] * 1e-6, dv[5] ? 100.0 * dv[4] / dv[5] : 0.0, dv[6] * 1e-5, dv[7] * 1e-5, dv[12], dv[13], dv[14] * 1e-5, dv[15] * 1e-5);
-        }
-        const long long stv[4] = {(long long)h->h_result[0], (long long)h->h_result[1], (long long)h->h_result[2], (long long)h->h_result[3]};
-        h->last_stats.sweeps = stv[0];
-        h->last_stats.ip_solves = stv[1];
-        h->last_stats.ip_iters = stv[2];
-        h->last_stats.ip_failures = stv[3];
-        h->last_stats.rounds = rounds_before + 1;
-        h->last_stats.newton_iters = (long long)h->h_result[4];
-        h->prof_ip_problems += solved_before;
-        h->prof_async_problems += stv[1] - solved_before;
-        if (from_reset) h->prof_kkt_systems += h->last_stats.newton_iters;
-        return CIMPC_OK;
-    };
+    HIP_TRY(h, hipMemsetAsync(h->S.stats, 0, (size_t)B * 4 * sizeof(long long), sb.st));
     if ((rc = ensure_kkt_ws(h)) != CIMPC_OK) return rc;
     const SolvePath path = choose_solve_path(h->sched, h->kb);
-    if (path == SolvePath::Persistent) return run_async(true, 0);
-    const bool hybrid = path == SolvePath::Hybrid;
+    if (path == SolvePath::Persistent) return run_async(h, run, true, 0);
+    run.hybrid = path == SolvePath::Hybrid;
     const int round_limit = max_rounds(h->kn.sched, h->nt.max_iter, h->ip.max_iter);
-    // the rounds run on the library's private streams, or on the caller's stream when one was given
-    RoundStreams sb = h->rs;
-    if (h->external_stream) sb.st = h->stream;
     // Lock-step rounds.  Every kernel of a round is driven by device-side state (work queues, per-rollout stage); the host only
     // looks at the counters the last decision block publishes, one round at a time.  (Measured and removed again: rounds enqueued
     // one ahead of the host's knowledge - the KKT kernel must then be launched blind at full grid, 15.9 vs 13.7 ms at B = 512 - and
     // chained rounds {sweep || KKT} -> sweep of the new candidates -> residual: every extra sweep launch pays the slowest-solve
     // tail again, 10.7 -> 11.0-11.3 ms.)
-    long long launched = 0, completed = 0, rounds = 0;
-    const bool dbg_rounds = h->kn.debug_rounds;
-    int last_kkt = 0, last_sweep = h->dm.B, last_slots = h->dm.B, last_parked = 0, last_new_slots = h->dm.B;
-    const bool ahead = round_ahead(h->sched, h->kb, warm_start != 0, h->nt.max_time > 0.0 && h->nt.max_time < 1.0e6);
-    auto launch_round = [&](long long r, bool blind) -> int {
-        // [KKT for rollouts that start an iteration] || sweep -> residual of every evaluated slot -> line-search decision
-        const int slot = (int)(r & 1), par = (int)(r & 1);      // round r consumes Q[par] and leaves the next round's requests in Q[par ^ 1]
-        int* d_cnt = h->d_ring + 8 * CPAD * slot;
-        S.kkt_tw_epoch += 1;      // stamp of this round's KKT stage (epoch-valued hand-over flags of the twisted kernels)
-        // a hand-over of a twisted kernel timed out earlier in this solve (its rollouts were queued again): one-ended kernels from here on
-        const int tw_fails = *(volatile int*)h->h_twfail;
-        if (tw_fails != h->twfail_seen) { h->n_kkt_tw_fallbacks += tw_fails - h->twfail_seen; h->twfail_seen = tw_fails; }
-        const bool tw_off = tw_fails != tw_fail0;
-        NewtonDev Sk = S;
-        Sk.b0 = 0; Sk.nb_launch = h->dm.B; Sk.counters = d_cnt;
-        Sk.counters_next = h->d_ring + 8 * CPAD * (slot ^ 1);
-        Sk.host_flag = h->h_ring_dev + 8 * slot;
-        Sk.A.n_done = hybrid ? h->a_ctrl + 2 * (size_t)h->Q.K * QPAD + 8 : nullptr;
-        Sk.round_stamp = (int)(r + 1);
-        Sk.WQ = h->Q; Sk.WQ.par = par;       // the queue being consumed
-        const bool kkt = (r > 0) && (blind || last_kkt > 0);
-        const int n_kkt = blind ? h->dm.B : last_kkt;
-        const int* n_kkt_dev = blind ? h->d_ring + 8 * CPAD * (slot ^ 1) + 1 * CPAD : nullptr;      // the previous round's count of KKT requests
-        if (kkt) {
-            // KKT of the rollouts that start a Newton iteration (list of the previous round's decision kernel, its queue parity).  Small
-            // batches: latency matters, ahead of the sweep on its stream, the result kept in this round.  Overlapped: next to the sweep
-            // on its own stream, no fork event (every decision block of the previous round released its results before its ticket).
-            // (Launched BEFORE the sweep: the other order was measured 10 % / 20 % slower in rounds 1 / 3, 8.37 -> 10.05 ms - behind the
-            // persistent sweep the KKT workgroups wait for sweep workgroups to leave: profiles/r03/knob_order.log.)
-            const bool ov = h->kp.kkt_overlap;
-            const KktSite site{.kind = ov ? KktSite::Overlapped : KktSite::Round, .n_kkt = n_kkt, .blind = blind,
-                               .sweep_problems = (long long)last_new_slots * h->dm.H, .tw_off = tw_off, .B = h->dm.B};
-            hipStream_t kst = ov ? sb.st_kkt : sb.st;
-            if (!ov) Sk.kkt_same_round = 1;
-            prof_begin(h, PC_KKT, kst);
-            int rk = run_kkt_stage(h, Sk, kkt_newton_args(Sk), site, Sk.kkt_list + (size_t)(par ^ 1) * h->dm.B,
-                                   ov ? last_kkt : n_kkt, ov ? nullptr : n_kkt_dev, kst);      // (overlapped: the host's count, blind rounds too)
-            prof_end(h, kst);
-            if (rk != CIMPC_OK) return fail(h, rk, "kkt launch failed");
-            if (ov && hipEventRecord(sb.ev_join, sb.st_kkt) != hipSuccess) return fail(h, CIMPC_ERR_HIP, "join record failed");
-        }
-        const RoundPlan rp = plan_round(h->kn.sched, h->sched, h->ip.max_iter, kkt, blind, last_sweep, last_slots);
-        // problems of this round as far as the host knows them: the evaluation slots requested + the solves the last sweep parked
-        const long long hint = blind ? -1 : (long long)last_slots * h->dm.H + last_parked;
-        if (dbg_rounds && !blind) {      // diagnostics only: the problems this round's sweep will find in its queues (a blocking read)
-            std::vector<int> qc((size_t)h->Q.K * QPAD);
-            (void)hipStreamSynchronize(sb.st); (void)hipStreamSynchronize(sb.st_kkt);
-            if (hipMemcpy(qc.data(), h->Q.count + (size_t)par * h->Q.K * QPAD, qc.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) {
-                long long tot = 0;
-                for (int k = 0; k < h->Q.K; ++k) tot += qc[(size_t)k * QPAD];
-                fprintf(stderr, "[cimpc round %lld] sweep launch: %lld problems queued (host hint %lld)\n", r, tot, hint);
-            }
-        }
-        int rr = run_sweep(h, par, d_cnt + 2 * CPAD, nullptr, sb.st, rp.cap, d_cnt + 3 * CPAD, true, hint);
-        if (rr != CIMPC_OK) return rr;
-        prof_begin(h, PC_RESID, sb.st);
-        if (rp.split_join) {
-            rr = launch_resid_decide(Sk, sb.st, rp.n_slots, 1);
-            if (rr != CIMPC_OK) return fail(h, rr, "residual launch failed");
-        }
-        if (kkt && h->kp.kkt_overlap && hipStreamWaitEvent(sb.st, sb.ev_join, 0) != hipSuccess) return fail(h, CIMPC_ERR_HIP, "join failed");
-        rr = launch_resid_decide(Sk, sb.st, rp.n_slots, rp.split_join ? 2 : 0);
-        prof_end(h, sb.st);
-        if (rr != CIMPC_OK) return fail(h, rr, "residual launch failed");
-        return CIMPC_OK;
-    };
+    long long launched = 0, completed = 0;
+    const bool ahead = round_ahead(h->sched, h->kb, warm_start != 0, has_time_budget(h));
     HIP_TRY(h, hipMemsetAsync(h->Q.count, 0, h->ctl_ints * sizeof(int), sb.st));      // queue counters, heads, round counters
-    if (hybrid) HIP_TRY(h, hipMemsetAsync(h->a_ctrl + 2 * (size_t)h->Q.K * QPAD, 0, 64 * sizeof(int), sb.st));
-    ((volatile int*)h->h_ring)[2] = 0;
-    ((volatile int*)h->h_ring)[10] = 0;
-    {
-        NewtonDev Sk = S;
-        Sk.b0 = 0; Sk.nb_launch = h->dm.B; Sk.counters = h->d_ring;
-        Sk.WQ = h->Q; Sk.WQ.par = 0;
-        prof_begin(h, PC_OTHER, sb.st);
-        rc = launch_reset(Sk, q0_dev, q1_dev, warm_start, sb.st);
-        prof_end(h, sb.st);
-        if (rc != CIMPC_OK) return fail(h, rc, "reset launch failed");
-    }
+    if (run.hybrid) HIP_TRY(h, hipMemsetAsync(h->a_ctrl + async_ctl(h->Q.K).jobs, 0, ASYNC_JOB_INTS * sizeof(int), sb.st));
+    for (int slot = 0; slot < RING_SLOTS_COUNT; ++slot) ring_slot((volatile int*)h->h_ring, slot)[RING_STAMP] = 0;
+    prof_begin(h, PC_OTHER, sb.st);
+    rc = launch_reset(launch_view(h, 0), q0_dev, q1_dev, warm_start, sb.st);
+    prof_end(h, sb.st);
+    if (rc != CIMPC_OK) return fail(h, rc, "reset launch failed");
     while (true) {
         if (completed >= round_limit) {          // round limit reached with work left: a scheduling bug, never a silent partial solve
             (void)hipStreamSynchronize(sb.st); (void)hipStreamSynchronize(sb.st_kkt);
             return fail(h, CIMPC_ERR_STATE, "newton_solve: round limit reached with unfinished rollouts");
         }
         while (launched <= completed + (ahead ? 1 : 0)) {
-            rc = launch_round(launched, launched > completed);
+            rc = launch_round(h, run, launched, launched > completed);
             if (rc != CIMPC_OK) return rc;
             ++launched;
         }
         {   // the decision kernel's last block stamps the mapped flag when round `completed` is done
-            volatile int* hm = (volatile int*)h->h_ring + 8 * (completed & 1);
+            volatile int* hm = ring_slot((volatile int*)h->h_ring, completed);
             const int want = (int)(completed + 1);
             long long spins = 0;
-            while (hm[2] != want) {
-                if ((++spins & 0xFFFFF) == 0 && hipStreamQuery(sb.st) != hipErrorNotReady && hm[2] != want)
+            while (hm[RING_STAMP] != want) {
+                if ((++spins & 0xFFFFF) == 0 && hipStreamQuery(sb.st) != hipErrorNotReady && hm[RING_STAMP] != want)
                     return fail(h, CIMPC_ERR_HIP, "round finished without publishing its counters");
             }
         }
-        volatile int* hr = (volatile int*)h->h_ring + 8 * (completed & 1);
-        const int n_sweep = hr[0];
-        last_sweep = n_sweep;
-        last_kkt = hr[1];
-        last_slots = hr[6];
-        last_new_slots = hr[7];      // (deterministic: slots that only wait for a parked solve are re-listed, not re-requested)
-        last_parked = hr[4];
-        if (dbg_rounds) fprintf(stderr, "[cimpc round %lld] t %.3f ms: next sweep %d rollouts (%d evaluation slots), next kkt %d, parked %d, finished %d\n", completed,
-                                1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), n_sweep, last_slots, last_kkt, hr[4], hr[5]);
-        h->prof_kkt_systems += last_kkt;
+        const RoundCounts& last = run.last = read_round_counts(h->h_ring, completed);
+        if (h->kn.debug_rounds) fprintf(stderr, "[cimpc round %lld] t %.3f ms: next sweep %d rollouts (%d evaluation slots), next kkt %d, parked %d, finished %d\n", completed,
+                                        1e3 * elapsed_s(run), last.sweep, last.slots, last.kkt, last.parked, last.finished);
+        h->prof_kkt_systems += last.kkt;
         ++completed;
-        rounds = completed;
-        if ((n_sweep == 0 && last_kkt == 0) || over_budget()) break;   // newton.jl:187-277: budget ends silently
-        if (hybrid) {
-            if (hand_over(h->sched, h->dm.B - hr[5])) {
-                HIP_TRY(h, hipStreamSynchronize(sb.st));
-                HIP_TRY(h, hipStreamSynchronize(sb.st_kkt));
-                return run_async(false, rounds, (int)(rounds & 1));
-            }
+        if ((last.sweep == 0 && last.kkt == 0) || over_budget(h, run)) break;   // newton.jl:187-277: budget ends silently
+        if (run.hybrid && hand_over(h->sched, B - last.finished)) {
+            HIP_TRY(h, hipStreamSynchronize(sb.st));
+            HIP_TRY(h, hipStreamSynchronize(sb.st_kkt));
+            return run_async(h, run, false, completed);
         }
     }
     HIP_TRY(h, hipStreamSynchronize(sb.st_kkt));
-    if (int rf = finish_results(sb.st); rf != CIMPC_OK) return rf;
+    if (int rf = finish_results(h, sb.st); rf != CIMPC_OK) return rf;
     HIP_TRY(h, hipStreamSynchronize(sb.st));
-    const long long st[4] = {(long long)h->h_result[0], (long long)h->h_result[1], (long long)h->h_result[2], (long long)h->h_result[3]};
-    h->last_stats.sweeps = st[0];
-    h->last_stats.ip_solves = st[1];
-    h->last_stats.ip_iters = st[2];
-    h->last_stats.ip_failures = st[3];
-    h->last_stats.rounds = rounds;
-    h->last_stats.newton_iters = (long long)h->h_result[4];
-    h->prof_ip_problems += st[1];
+    publish_stats(h, completed);
+    h->prof_ip_problems += h->last_stats.ip_solves;
     return CIMPC_OK;
 }
 
@@ -1353,12 +1365,12 @@ int cimpc_newton_solve(cimpc_handle h, const double* q0, const double* q1, int w
     HIP_TRY(h, hipMemcpyAsync(h->d_q0, h->h_qin, 2 * ne * sizeof(double), hipMemcpyHostToDevice, h->stream));
     int rc = cimpc_newton_solve_dev(h, h->d_q0, h->d_q1, warm_start);
     if (rc != CIMPC_OK) return rc;
-    const int nu = h->dm.nu, w = nu + 2;
+    const int nu = h->dm.nu;
     for (int b = 0; b < h->dm.B; ++b) {
-        const double* o = h->h_result + 8 + (size_t)b * w;
+        const double* o = h->h_result + result_u1(b, nu);
         if (u1) std::memcpy(u1 + (size_t)b * nu, o, nu * sizeof(double));
-        if (newton_iters) newton_iters[b] = (int)o[nu];
-        if (r_norm) r_norm[b] = o[nu + 1] / (double)h->N;
+        if (newton_iters) newton_iters[b] = (int)o[record_iters(nu)];
+        if (r_norm) r_norm[b] = o[record_r_norm(nu)] / (double)h->N;
     }
     return CIMPC_OK;
 }
@@ -1604,15 +1616,14 @@ int cimpc_get_kkt_twisted(cimpc_handle h, long long* n) {
 
 int cimpc_get_kkt_twisted_fallbacks(cimpc_handle h, long long* n) {
     if (!h || !n) return CIMPC_ERR_INVALID;
-    const int cur = *(volatile int*)h->h_twfail;
-    if (cur != h->twfail_seen) { h->n_kkt_tw_fallbacks += cur - h->twfail_seen; h->twfail_seen = cur; }
+    note_tw_fallbacks(h);
     *n = h->n_kkt_tw_fallbacks;
     return CIMPC_OK;
 }
 
 int cimpc_debug_set_tw_spins(cimpc_handle h, int spins) {
     if (!h) return CIMPC_ERR_INVALID;
-    h->S.kkt_tw_spins = spins > 0 ? spins : (1 << 21);
+    h->S.kkt_tw_spins = spins > 0 ? spins : KKT_TW_SPINS;
     return CIMPC_OK;
 }
 

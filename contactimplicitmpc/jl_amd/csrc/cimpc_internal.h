@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../../include/cimpc.h"
+#include "round_protocol.h"
 
 namespace cimpc {
 
@@ -14,10 +15,6 @@ namespace cimpc {
 // balance: solves take 4..100 iterations).  Queues are double buffered by round parity: round r
 // consumes items[par], solves parked after iter_cap iterations and the evaluations requested by
 // the line search are appended to items[par ^ 1].
-constexpr int QPAD = 32;   // ints between two queue counters
-constexpr int CPAD = 32;   // ints between two ROUND counters (NewtonDev::counters[k * CPAD]): every counter on its own 128-byte line -
-                           // same-line atomics serialise in the L2 at ~50 ns each, and the decision kernel issues several per workgroup
-
 struct IpQueues {
     int* items;         // [2][K][cap]  problem id = sb*H + i
     int* count;         // [2][K] * QPAD   (every counter on its own 128-byte line: same-line atomics
@@ -42,8 +39,7 @@ struct AsyncQ {
     int* kq_tail;
     int* evals_left;    // [B] evaluation slots of the rollout's running line-search batch not yet complete
     int* n_done;        // rollouts whose Newton solve has ended
-    int* epoch;         // wake-up words, 64 B apart: [0,16) interior-point work, [16,32) jobs, 32 = any job; bucket = rollout % 16.
-                        // An idle workgroup polls only the two words of its own bucket (blockIdx % 16).
+    int* epoch;         // wake-up words (round_protocol.h: epoch_ip, epoch_job, epoch_any_job)
     volatile int* abort_flag;   // host-mapped: nonzero = time budget exhausted, leave
     long long* dbg;     // [16] diagnostics (busy ticks / job counts per kind of work) or null
     int n_service;      // workgroups [0, n_service) only take residual / KKT jobs
@@ -55,9 +51,6 @@ struct AsyncQ {
     int kkt_tw;         // 1: a rollout's KKT stage is TWO cooperating jobs - the chains of the twisted condensed solve, pushed bottom chain
                         // first (push_kkt_job) - instead of one one-ended recursion
 };
-// KKT job words: rollout index in the low 24 bits, kind above - 0 one-ended recursion, 1 top chain, 2 bottom chain of the twisted
-// solve, 3 one-ended recursion of a rollout whose twisted hand-over timed out
-constexpr int KJOB_SHIFT = 24, KJOB_MASK = (1 << KJOB_SHIFT) - 1;
 
 // Hand-offs of the asynchronous solve follow the HIP memory model literally: the producer issues an
 // agent-scope release fence (__threadfence) after writing its results and before the queue push /
@@ -111,33 +104,35 @@ __device__ __forceinline__ int aq_pop(int* items, int* head, const int* tail, lo
 
 // an evaluation spreads over up to H knots and every knot needs a workgroup of its own: wake `wake_fan` buckets
 __device__ __forceinline__ void wake_ip(const AsyncQ& A, int b) {
-    for (int k = 0; k < A.wake_fan; ++k) atomicAdd(A.epoch + ((b + k * (16 / A.wake_fan)) & 15) * 16, 1);
+    for (int k = 0; k < A.wake_fan; ++k) atomicAdd(A.epoch + epoch_ip(epoch_bucket(b + k * (EPOCH_BUCKETS / A.wake_fan))), 1);
 }
-// jobs head the rollout's chain: the (few) dedicated service workgroups all wake on word 32, the
+// jobs head the rollout's chain: the (few) dedicated service workgroups all wake on the any-job word, the
 // interior-point workgroups of the rollout's bucket on their job word
 __device__ __forceinline__ void wake_job(const AsyncQ& A, int b) {
-    atomicAdd(A.epoch + 32 * 16, 1);
-    atomicAdd(A.epoch + (16 + (b & 15)) * 16, 1);
+    atomicAdd(A.epoch + epoch_any_job(), 1);
+    atomicAdd(A.epoch + epoch_job(epoch_bucket(b)), 1);
 }
 // A rollout enters its KKT stage.  Twisted form: two consecutive entries, the BOTTOM chain first.  Claims are FIFO (aq_pop advances
 // the head by compare-and-swap), so whoever claims the top chain knows that the bottom chain already has a workgroup - every
 // workgroup of the persistent kernel is resident and a claimed job is started without waiting for anything - and the bottom chain,
 // which waits for nothing until its forward pass is done, is followed by its partner as soon as any workgroup looks at the queue
-// (jobs are taken before interior-point work).  Both waits are bounded anyway (kkt_tw_wait): a time-out re-queues kind 3.
+// (jobs are taken before interior-point work).  Both waits are bounded anyway (kkt_tw_wait): a time-out re-queues KJOB_RETRY.
 __device__ __forceinline__ void push_kkt_job(const AsyncQ& A, int b) {
     if (A.kkt_tw) {
         const int pos = atomicAdd(A.kq_tail, 2);
-        astore(A.kq_items + pos, b | (2 << KJOB_SHIFT));
-        astore(A.kq_items + pos + 1, b | (1 << KJOB_SHIFT));
-        atomicAdd(A.epoch + 32 * 16, 1);
-        atomicAdd(A.epoch + (16 + (b & 15)) * 16, 1);
-        atomicAdd(A.epoch + (16 + ((b + 1) & 15)) * 16, 1);      // (a second bucket: two workgroups are wanted)
+        astore(A.kq_items + pos, b | (KJOB_BOTTOM << KJOB_SHIFT));
+        astore(A.kq_items + pos + 1, b | (KJOB_TOP << KJOB_SHIFT));
+        atomicAdd(A.epoch + epoch_any_job(), 1);
+        atomicAdd(A.epoch + epoch_job(epoch_bucket(b)), 1);
+        atomicAdd(A.epoch + epoch_job(epoch_bucket(b + 1)), 1);      // (a second bucket: two workgroups are wanted)
     } else {
         aq_push(A.kq_items, A.kq_tail, b);
         wake_job(A, b);
     }
 }
-__device__ __forceinline__ void wake_all(const AsyncQ& A) { for (int k = 0; k <= 32; ++k) atomicAdd(A.epoch + k * 16, 1); }
+// the job word an idle workgroup watches: the dedicated service workgroups the any-job word, the others their bucket's
+__device__ __forceinline__ int job_word(bool service, int bucket) { return service ? epoch_any_job() : epoch_job(bucket); }
+__device__ __forceinline__ void wake_all(const AsyncQ& A) { for (int k = 0; k < EPOCH_WORDS; ++k) atomicAdd(A.epoch + k * EPOCH_STRIDE, 1); }
 
 __device__ __forceinline__ int* qcount(const IpQueues& Q, int par, int k) { return Q.count + ((size_t)par * Q.K + k) * QPAD; }
 __device__ __forceinline__ int* qhead(const IpQueues& Q, int k) { return Q.head + (size_t)k * QPAD; }

@@ -305,7 +305,6 @@ __host__ __device__ inline BandSplit banded_twisted_split(int N, int w, int RB) 
     sp.Nb = Nb; sp.m2 = Np - Nb - w;
     return sp;
 }
-constexpr int KKT_BAND_TW_FLAG0 = 4;      // words of NewtonDev::kkt_tw_flags[b]: 4 trace ready, 5 middle x ready, 6 chains finished
 
 // -DCIMPC_BANDED_PROF (diagnostic builds, with -DCIMPC_KKT_PROF for the accessor): shader-clock accounting of the banded kernel, rollout 0,
 // per wavefront: [0] pre-pass, window fill, first diagonal block  [1] P2  [2] barrier  [3] wavefront 0: tile (0, 0) / the others: entering rows, rhs, stores
@@ -663,7 +662,7 @@ __device__ __forceinline__ void kkt_banded_body(const NewtonDev& S, const KktArg
             // window now and none has been a pivot (the next diagonal block - pivots m2 .. - is formed later in this iteration).
             if (k == m2 - RB) {
                 BTWSTAMP(2)
-                tw_ok = kkt_tw_wait(xfl + 0, S.kkt_tw_epoch, S.kkt_tw_spins); if (!tw_ok) kkt_tw_give_up(xfl, S.kkt_tw_epoch, tid == 0);
+                tw_ok = kkt_tw_wait(xfl + TW_TRACES, S.kkt_tw_epoch, S.kkt_tw_spins); if (!tw_ok) kkt_tw_give_up(xfl, S.kkt_tw_epoch, tid == 0);
                 BTWSTAMP(3)
                 for (int e = tid; e < w * (w + 1); e += nt) {
                     const int a = e / (w + 1), a2 = e - a * (w + 1);
@@ -829,7 +828,7 @@ __device__ __forceinline__ void kkt_banded_body(const NewtonDev& S, const KktArg
         }
         __threadfence();
         __syncthreads();
-        if (tid == 0) astore(xfl + 0, S.kkt_tw_epoch);
+        if (tid == 0) astore(xfl + TW_TRACES, S.kkt_tw_epoch);
     }
     __syncthreads();              // full barrier: the rows of L and y in global memory are read back below
     // ---- back substitution  L^T x = D^-1 y.  acc_j = sum_{i > j} L[i][j] x_i is built row by row (i descending); round 4: the pending
@@ -853,7 +852,7 @@ __device__ __forceinline__ void kkt_banded_body(const NewtonDev& S, const KktArg
             return ki < nr ? ti * nr + ki : H * nr + ti * nd + (ki - nr);
         };
         BTWSTAMP(5)
-        if constexpr (TW == 2) { tw_ok = kkt_tw_wait(xfl + 1, S.kkt_tw_epoch, S.kkt_tw_spins); if (!tw_ok) kkt_tw_give_up(xfl, S.kkt_tw_epoch, tid == 0); }     // the middle rows' solution (the top chain's first w values) is in D
+        if constexpr (TW == 2) { tw_ok = kkt_tw_wait(xfl + TW_MIDDLE, S.kkt_tw_epoch, S.kkt_tw_spins); if (!tw_ok) kkt_tw_give_up(xfl, S.kkt_tw_epoch, tid == 0); }     // the middle rows' solution (the top chain's first w values) is in D
         BTWSTAMP(6)
         auto stage = [&](int ch, int t0, int nth) {              // chunk ch = rows NR-1 - ch CR downwards -> buffer ch & 1  (threads t0 .. of nth)
             const int i_hi = NR - 1 - ch * CR, i_lo = max(i_hi - CR + 1, 0), n = i_hi - i_lo + 1, tot = n * 192;
@@ -925,7 +924,7 @@ __device__ __forceinline__ void kkt_banded_body(const NewtonDev& S, const KktArg
                 const int i_lo_done = max(NR - 1 - ch * CR - CR + 1, 0);
                 if (i_lo_done <= m2 && i_lo_done + CR > m2 && tid < 64) {
                     __threadfence();
-                    if (tid == 0) astore(xfl + 1, S.kkt_tw_epoch);
+                    if (tid == 0) astore(xfl + TW_MIDDLE, S.kkt_tw_epoch);
                 }
             }
         }
@@ -938,14 +937,14 @@ __device__ __forceinline__ void kkt_banded_body(const NewtonDev& S, const KktArg
         __threadfence();
         __syncthreads();
         if (tid == 0) {
-            *tw_prev = atomicAdd(xfl + 2, 1);      // (epoch-valued flags: nothing to reset)
+            *tw_prev = atomicAdd(xfl + TW_FINISHED, 1);      // (epoch-valued flags: nothing to reset)
         }
         __syncthreads();
         if (*tw_prev == 0) return;
         __syncthreads();
         __threadfence();
-        if (tid == 0) astore(xfl + 2, 0);
-        if (aload(xfl + 3) == S.kkt_tw_epoch) {      // a hand-over of this solve timed out (poisoned numbers): queue the KKT stage again
+        if (tid == 0) astore(xfl + TW_FINISHED, 0);
+        if (aload(xfl + TW_TIMED_OUT) == S.kkt_tw_epoch) {      // a hand-over of this solve timed out (poisoned numbers): queue the KKT stage again
             if (tid == 0) kkt_tw_requeue(S, b, K.finish);
             return;
         }

@@ -86,7 +86,7 @@ __device__ __noinline__ void async_kkt_job(unsigned long long ka, int b, double*
 // (push_kkt_job: bottom chain first, FIFO claims).  The hand-over flags are epoch-valued; inside one persistent launch the stamp of a
 // rollout's KKT stage is the launch's stamp + 1 + the Newton iterations the rollout has done (the host advances its stamp by
 // max_iter + 2 per launch).  The chain that finishes last starts the line search with the whole workgroup; a hand-over that timed
-// out re-queues the stage as a one-ended job (kind 3).
+// out re-queues the stage as a one-ended job (KJOB_RETRY).
 template <int NQ, int NU, int TW>
 __device__ __noinline__ void async_kkt_tw_job(unsigned long long ka, int b, double* smem, int tid) {
     NewtonDev S = uniform_state(ka);
@@ -109,8 +109,8 @@ __device__ __noinline__ void async_kkt_tw_job(unsigned long long ka, int b, doub
     if (last == 0) return;
     __threadfence();                      // acquire the partner's share of the step in every wave
     int* xfl = S.kkt_tw_flags + (size_t)b * KKT_TW_FLAGS;
-    if (__builtin_amdgcn_readfirstlane(aload(xfl + 3)) == S.kkt_tw_epoch) {      // poisoned numbers: the stage again, one-ended
-        if (tid == 0) { aq_push(S.A.kq_items, S.A.kq_tail, b | (3 << KJOB_SHIFT)); wake_job(S.A, b); }
+    if (__builtin_amdgcn_readfirstlane(aload(xfl + TW_TIMED_OUT)) == S.kkt_tw_epoch) {      // poisoned numbers: the stage again, one-ended
+        if (tid == 0) { aq_push(S.A.kq_items, S.A.kq_tail, b | (KJOB_RETRY << KJOB_SHIFT)); wake_job(S.A, b); }
         return;
     }
     start_line_search<BlockSync>(S, b, 2, tid, (int)blockDim.x);
@@ -159,8 +159,8 @@ __global__ __launch_bounds__(256, (M::G == 16 ? 2 : 1)) void newton_async_kernel
         if (tid == 0) {
             int type = 0, job = -1;
             // wake-up words of this workgroup's bucket, read BEFORE looking for work (a push during the scan changes them)
-            s_epoch[0] = aload(A.epoch + ((int)blockIdx.x & 15) * 16);
-            s_epoch[1] = aload(A.epoch + (service ? 32 : 16 + ((int)blockIdx.x & 15)) * 16);
+            s_epoch[0] = aload(A.epoch + epoch_ip(epoch_bucket((int)blockIdx.x)));
+            s_epoch[1] = aload(A.epoch + job_word(service, epoch_bucket((int)blockIdx.x)));
             // the abort flag lives in host memory (one PCIe read): looked at now and then only
             if ((trip++ & 31u) == 31u && *A.abort_flag != 0) {
                 type = 3;
@@ -179,8 +179,8 @@ __global__ __launch_bounds__(256, (M::G == 16 ? 2 : 1)) void newton_async_kernel
             account(0);
             const int kind = job >> KJOB_SHIFT, jb = job & KJOB_MASK;
             if constexpr (kkt_tld<NQ, NU>() == 16) {
-                if ((kind == 1 || kind == 2) && (int)blockDim.x >= 256) {
-                    if (kind == 2) async_kkt_tw_job<NQ, NU, 2>(ka, jb, smem, tid);
+                if ((kind == KJOB_TOP || kind == KJOB_BOTTOM) && (int)blockDim.x >= 256) {
+                    if (kind == KJOB_BOTTOM) async_kkt_tw_job<NQ, NU, 2>(ka, jb, smem, tid);
                     else async_kkt_tw_job<NQ, NU, 1>(ka, jb, smem, tid);
                     __syncthreads();
                     account(1);
@@ -216,8 +216,8 @@ __global__ __launch_bounds__(256, (M::G == 16 ? 2 : 1)) void newton_async_kernel
         // their bucket, which producers bump after publishing, and look around anyway every ~100 us.
         if (tid == 0) {
             int leave = aload(A.n_done) >= A.B;
-            const int* wi = A.epoch + ((int)blockIdx.x & 15) * 16;
-            const int* wj = A.epoch + (service ? 32 : 16 + ((int)blockIdx.x & 15)) * 16;
+            const int* wi = A.epoch + epoch_ip(epoch_bucket((int)blockIdx.x));
+            const int* wj = A.epoch + job_word(service, epoch_bucket((int)blockIdx.x));
             unsigned spins = 0;
             while (!leave && (service || aload(wi) == s_epoch[0]) && aload(wj) == s_epoch[1]) {
                 for (int k = 0; k < A.idle_sleep; ++k) __builtin_amdgcn_s_sleep(64);

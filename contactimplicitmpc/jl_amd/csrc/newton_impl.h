@@ -61,7 +61,7 @@ __device__ __forceinline__ double ls_alpha(int iter) { return ldexp(1.0, -iter);
 // slot sb will have been evaluated when the round that consumes queue `par` reaches its residual launch
 __device__ __forceinline__ void list_slot(const NewtonDev& S, size_t sb, int par, int pos = -1) {
     if (S.slot_list == nullptr) return;
-    if (pos < 0) pos = atomicAdd(&S.counters[4 * CPAD], 1);
+    if (pos < 0) pos = atomicAdd(round_counter(S.counters, RC_SLOTS), 1);
     if (pos >= S.dm.B * CS) __builtin_trap();      // (a slot is listed at most once per round: cannot happen)
     S.slot_list[(size_t)par * S.dm.B * CS + pos] = (int)sb;
 }
@@ -99,8 +99,8 @@ __device__ __forceinline__ void enqueue_evals(const NewtonDev& S, size_t sb, int
     }
     if (tid == 0) {
         int pos = 0;
-        if (S.slot_list != nullptr) pos = atomicAdd(&S.counters[4 * CPAD], n);
-        atomicAdd(&S.counters[5 * CPAD], n);      // NEW evaluation requests of the round (a deterministic count: slots re-listed while a solve is parked are not in it)
+        if (S.slot_list != nullptr) pos = atomicAdd(round_counter(S.counters, RC_SLOTS), n);
+        atomicAdd(round_counter(S.counters, RC_NEW_SLOTS), n);      // NEW evaluation requests of the round (a deterministic count: slots re-listed while a solve is parked are not in it)
         if (pos + n > S.dm.B * CS) __builtin_trap();      // (a slot is listed at most once per round: cannot happen)
         for (int c = 0; c < n; ++c) {
             S.WQ.done_count[sb + c] = 0;
@@ -326,7 +326,7 @@ __device__ __forceinline__ void start_line_search(const NewtonDev& S, int b, int
             // (counter 0 = rollouts that need a sweep in the NEXT round: only the overlapped KKT kernel requests one there.  With the KKT
             //  stage in the same round as the evaluation of its candidates - small batches - the count made the host launch one more,
             //  empty round after the decision that ended a solve: three launches, ~40 us of a 0.55 ms single-rollout solve)
-            if (S.kkt_same_round == 0) atomicAdd(&S.counters[0 * CPAD], 1);
+            if (S.kkt_same_round == 0) atomicAdd(round_counter(S.counters, RC_SWEEP), 1);
         }
     }
 }
@@ -558,7 +558,7 @@ __device__ __forceinline__ void resid_decide_body(const NewtonDev& S, int b, dou
     if (!ASYNC && blockIdx.x == 0) {   // the queue of this round has been consumed: recycle it
         const int K = S.WQ.K, par = S.WQ.par;
         for (int k = tid; k < K; k += nt) { *qcount(S.WQ, par, k) = 0; *qhead(S.WQ, k) = 0; }
-        if (tid < 8) S.counters_next[tid * CPAD] = 0;      // counter block of the next round
+        if (tid < ROUND_COUNTERS) *round_counter(S.counters_next, tid) = 0;      // counter block of the next round
     }
     RPROF_BEGIN(1)
     // (SPLIT = 2: the per-slot scalars of the rollout are requested together with its stage, one round trip for the entry checks)
@@ -579,7 +579,7 @@ __device__ __forceinline__ void resid_decide_body(const NewtonDev& S, int b, dou
             return;
         }
         if (__syncthreads_or(mine && pre_dc < H)) {                  // an interior-point solve of this evaluation is still parked: wait for the next round
-            if (tid == 0) atomicAdd(&S.counters[0 * CPAD], 1);
+            if (tid == 0) atomicAdd(round_counter(S.counters, RC_SWEEP), 1);
             if (mine) list_slot(S, sb0 + tid, S.WQ.par ^ 1);         // its slots stay on the list
             return;
         }
@@ -597,7 +597,7 @@ __device__ __forceinline__ void resid_decide_body(const NewtonDev& S, int b, dou
             int pend = 0;
             if (tid < ncand) pend = (S.WQ.done_count[sb0 + it0 + tid] < H);
             if (__syncthreads_or(pend)) {
-                if (tid == 0) atomicAdd(&S.counters[0 * CPAD], 1);
+                if (tid == 0) atomicAdd(round_counter(S.counters, RC_SWEEP), 1);
                 return;
             }
         }
@@ -714,7 +714,7 @@ __device__ __forceinline__ void resid_decide_body(const NewtonDev& S, int b, dou
         RPROF(5)
         if (tid == 0) {
             S.stage[b] = nstage;
-            atomicAdd(&S.counters[0 * CPAD], 1);
+            atomicAdd(round_counter(S.counters, RC_SWEEP), 1);
         }
         return;
     }
@@ -806,7 +806,7 @@ __device__ __forceinline__ void resid_decide_body(const NewtonDev& S, int b, dou
         } else {
             S.stage[b] = STAGE_KKT;
             if constexpr (!ASYNC) {
-                const int pos = atomicAdd(&S.counters[1 * CPAD], 1);
+                const int pos = atomicAdd(round_counter(S.counters, RC_KKT), 1);
                 if (S.kkt_list != nullptr) S.kkt_list[(size_t)S.WQ.par * m.B + pos] = b;
             }
         }
@@ -911,18 +911,18 @@ __global__ __launch_bounds__(CIMPC_RESID_THREADS) void resid_decide_kernel(Newto
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence();
-        const int ticket = atomicAdd(&S.counters[7 * CPAD], 1);
+        const int ticket = atomicAdd(round_counter(S.counters, RC_TICKET), 1);
         if (ticket == (int)gridDim.x - 1) {
-            const int n_sweep = atomicAdd(&S.counters[0 * CPAD], 0), n_kkt = atomicAdd(&S.counters[1 * CPAD], 0);
+            const int n_sweep = atomicAdd(round_counter(S.counters, RC_SWEEP), 0), n_kkt = atomicAdd(round_counter(S.counters, RC_KKT), 0);
             volatile int* hm = S.host_flag;
-            hm[0] = n_sweep;
-            hm[1] = n_kkt;
-            hm[4] = atomicAdd(&S.counters[2 * CPAD], 0);                                   // solves parked by this round
-            hm[6] = atomicAdd(&S.counters[4 * CPAD], 0);                                   // evaluation slots of the next round
-            hm[7] = atomicAdd(&S.counters[5 * CPAD], 0);                                   // ... of which newly requested (not waiting for a parked solve)
-            hm[5] = S.A.n_done != nullptr ? atomicAdd(S.A.n_done, 0) : 0;            // rollouts finished so far
+            hm[RING_N_SWEEP] = n_sweep;
+            hm[RING_N_KKT] = n_kkt;
+            hm[RING_PARKED] = atomicAdd(round_counter(S.counters, RC_PARKED), 0);                                   // solves parked by this round
+            hm[RING_SLOTS] = atomicAdd(round_counter(S.counters, RC_SLOTS), 0);                                   // evaluation slots of the next round
+            hm[RING_NEW_SLOTS] = atomicAdd(round_counter(S.counters, RC_NEW_SLOTS), 0);                                   // ... of which newly requested (not waiting for a parked solve)
+            hm[RING_FINISHED] = S.A.n_done != nullptr ? atomicAdd(S.A.n_done, 0) : 0;            // rollouts finished so far
             __threadfence_system();
-            hm[2] = S.round_stamp;
+            hm[RING_STAMP] = S.round_stamp;
             __threadfence_system();
         }
     }
@@ -1504,11 +1504,7 @@ __host__ __device__ inline int kkt_tw_split(int H, int nb_override = 0, bool wid
 // shorter horizons keep the one-ended kernels: at H = 20 (hopper, BASELINE configs[1]) the two forms take the same time - 22 us
 // against 24 us per launch, profiles/r05/loop_trace_hopper_* - and the hand-overs are all that the second workgroup adds
 constexpr int KKT_TW_MIN_H = 24;
-// per-rollout exchange block of the two chains: [S00 | S11 | S10^T] (nd x nd each), c0, c1, dnu_{m+1}, dnu_m
-__host__ __device__ constexpr int kkt_tw_xch_doubles(int nd) { return 3 * nd * nd + 4 * nd; }
-constexpr int KKT_TW_FLAGS = 32;         // ints per rollout (one 128-byte line): [0] traces ready, [1] middle dnu ready, [2] chains finished, [3] a hand-over of
-                                         // this launch timed out; [4..7] the same four words of the banded twisted kernel (kkt_dense.hip)
-constexpr int KKT_TW_SPINS = 1 << 21;    // default bound of a wait (NewtonDev::kkt_tw_spins; cimpc_debug_set_tw_spins for the tests)
+// (the exchange block, the flag line and the default bound of a wait: round_protocol.h)
 // Wait for the partner chain's flag to show THIS launch's stamp (agent scope), then acquire.  Bounded: a partner that never becomes
 // resident must not hang the device - the caller poisons its result with NaN AND marks the rollout (kkt_tw_give_up), so that the
 // solve is repeated on the one-ended kernel instead of being used.
@@ -1521,15 +1517,15 @@ __device__ __forceinline__ bool kkt_tw_wait(const int* flag, int epoch, int spin
     __threadfence();
     return ok;
 }
-// a chain gave up waiting: word 3 of the rollout's flag line carries the launch's stamp (read by whichever chain finishes last)
+// a chain gave up waiting: TW_TIMED_OUT of the rollout's flag line carries the launch's stamp (read by whichever chain finishes last)
 __device__ __forceinline__ void kkt_tw_give_up(int* xfl, int epoch, bool one_lane) {
-    if (one_lane) astore(xfl + 3, epoch);
+    if (one_lane) astore(xfl + TW_TIMED_OUT, epoch);
 }
 // The last chain of a rollout whose hand-over timed out: the KKT stage of the rollout is queued AGAIN (it stays in STAGE_KKT; the
 // entry joins the list the decision kernel of this round builds for the next one) and the failure is counted where the host sees it.
 __device__ __forceinline__ void kkt_tw_requeue(const NewtonDev& S, int b, int finish) {
     if (finish == 1) {
-        const int pos = atomicAdd(&S.counters[1 * CPAD], 1);
+        const int pos = atomicAdd(round_counter(S.counters, RC_KKT), 1);
         if (S.kkt_list != nullptr && pos < S.dm.B) S.kkt_list[(size_t)S.WQ.par * S.dm.B + pos] = b;
     }
     if (S.kkt_tw_fail != nullptr) { __hip_atomic_fetch_add(S.kkt_tw_fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); __threadfence_system(); }
@@ -1892,7 +1888,7 @@ __device__ __forceinline__ void kkt_body(const NewtonDev& S, const KktArgs& K, i
                 }
                 if (i == nbot + 1) {      // everything the top chain waits for is written: release, raise the flag
                     __threadfence();
-                    if (lane == 0) astore(xfl + 0, S.kkt_tw_epoch);
+                    if (lane == 0) astore(xfl + TW_TRACES, S.kkt_tw_epoch);
                 }
                 return;
             }
@@ -1901,7 +1897,7 @@ __device__ __forceinline__ void kkt_body(const NewtonDev& S, const KktArgs& K, i
             [[maybe_unused]] double cm = 0.0;
             if constexpr (TW == 1) {
                 if (i >= msp) {       // middle rows: the bottom chain's share of the right-hand side (c1 for row m, c0 for row m+1)
-                    if (i == msp) { tw_ok = kkt_tw_wait(xfl + 0, S.kkt_tw_epoch, S.kkt_tw_spins); if (!tw_ok) kkt_tw_give_up(xfl, S.kkt_tw_epoch, lane == 0); }
+                    if (i == msp) { tw_ok = kkt_tw_wait(xfl + TW_TRACES, S.kkt_tw_epoch, S.kkt_tw_spins); if (!tw_ok) kkt_tw_give_up(xfl, S.kkt_tw_epoch, lane == 0); }
                     if (lane < nd) cm = tw_ok ? xc[(msp + 1 - i) * nd + lane] : __builtin_nan("");
                 }
             }
@@ -1927,7 +1923,7 @@ __device__ __forceinline__ void kkt_body(const NewtonDev& S, const KktArgs& K, i
         if constexpr (PIPE >= 2) { y0 = tile_ld<TL, F32>(t.Y0h, li, lk); y1a = tile_ld<TL, F32>(t.Y1h, li, lk); }
         if constexpr (TW == 1) {
             if (i >= msp) {       // middle rows: minus what the rows eliminated from the bottom contribute
-                if (i == msp) { TWSTAMPW(0) tw_ok = kkt_tw_wait(xfl + 0, S.kkt_tw_epoch, S.kkt_tw_spins); TWSTAMPW(1) if (!tw_ok) kkt_tw_give_up(xfl, S.kkt_tw_epoch, lane == 0); }
+                if (i == msp) { TWSTAMPW(0) tw_ok = kkt_tw_wait(xfl + TW_TRACES, S.kkt_tw_epoch, S.kkt_tw_spins); TWSTAMPW(1) if (!tw_ok) kkt_tw_give_up(xfl, S.kkt_tw_epoch, lane == 0); }
                 sub_g(y0, xS + (i == msp ? n2 : 0), tw_ok);                 // Y_mm -= S11 ,  Y_{m+1,m+1} -= S00
                 if (i == msp + 1) sub_g(y1a, xS + 2 * n2, tw_ok);           // Y_{m+1,m} -= S10^T
             }
@@ -2118,7 +2114,7 @@ __device__ __forceinline__ void kkt_body(const NewtonDev& S, const KktArgs& K, i
     // chain receives the two middle rows - its steps nbot, nbot + 1 - from the top chain)
     const int NBK = TW == 2 ? nbot : NS;
     if constexpr (TW == 2) {
-        tw_ok = kkt_tw_wait(xfl + 1, S.kkt_tw_epoch, S.kkt_tw_spins);
+        tw_ok = kkt_tw_wait(xfl + TW_MIDDLE, S.kkt_tw_epoch, S.kkt_tw_spins);
         if (!tw_ok) kkt_tw_give_up(xfl, S.kkt_tw_epoch, lane == 0);
         TWSTAMP(3)
         if (lane < 2 * nd) dn_all[(nbot + lane / nd) * VS + lane % nd] = tw_ok ? xdn[lane] : __builtin_nan("");
@@ -2149,7 +2145,7 @@ __device__ __forceinline__ void kkt_body(const NewtonDev& S, const KktArgs& K, i
         if constexpr (TW == 1) {
             if (i == msp) {
                 __threadfence();
-                if (lane == 0) astore(xfl + 1, S.kkt_tw_epoch);
+                if (lane == 0) astore(xfl + TW_MIDDLE, S.kkt_tw_epoch);
             }
         }
         lds_sync();
@@ -2229,7 +2225,7 @@ __device__ __forceinline__ void kkt_body(const NewtonDev& S, const KktArgs& K, i
         __threadfence_block();
         __syncthreads();
         if (lazy && TW == 1 && lane < 2) S.good_src[(size_t)b * H + msp + lane] = -1;      // the middle rows (both chains streamed them)
-        if (__builtin_amdgcn_readfirstlane(aload(xfl + 3)) == S.kkt_tw_epoch) {               // a hand-over timed out (forced in the tests): poisoned numbers
+        if (__builtin_amdgcn_readfirstlane(aload(xfl + TW_TIMED_OUT)) == S.kkt_tw_epoch) {               // a hand-over timed out (forced in the tests): poisoned numbers
             if (TW == 1 && lane == 0) kkt_tw_requeue(S, b, K.finish);
             return;
         }
@@ -2250,15 +2246,15 @@ __device__ __forceinline__ void kkt_body(const NewtonDev& S, const KktArgs& K, i
         if (wave == 0) {
             TWSTAMP(5)
             __threadfence();
-            if (lane == 0) vec[11 * VS] = (double)atomicAdd(xfl + 2, 1);
+            if (lane == 0) vec[11 * VS] = (double)atomicAdd(xfl + TW_FINISHED, 1);
             TWSTAMP(6)
         }
         __syncthreads();
         if ((int)vec[11 * VS] == 0) return;
         __threadfence();
-        if (wave == 0 && lane == 0) astore(xfl + 2, 0);
+        if (wave == 0 && lane == 0) astore(xfl + TW_FINISHED, 0);
         if (lazy && wave == 0 && lane < 2) S.good_src[(size_t)b * H + msp + lane] = -1;      // the middle rows (see above)
-        if (__builtin_amdgcn_readfirstlane(aload(xfl + 3)) == S.kkt_tw_epoch) {      // a hand-over of this solve timed out: the numbers are poisoned
+        if (__builtin_amdgcn_readfirstlane(aload(xfl + TW_TIMED_OUT)) == S.kkt_tw_epoch) {      // a hand-over of this solve timed out: the numbers are poisoned
             if (wave == 0 && lane == 0) kkt_tw_requeue(S, b, K.finish);
             return;
         }

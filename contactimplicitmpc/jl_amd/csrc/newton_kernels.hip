@@ -468,28 +468,27 @@ static int launch_resid_t(const NewtonDev& S, hipStream_t s, int n_slots, int ph
     return S.dm.mode == CIMPC_MODE_CONFIGURATIONFORCE ? launch_resid_m<NQ, NU, true>(S, s, n_slots, phase) : launch_resid_m<NQ, NU, false>(S, s, n_slots, phase);
 }
 // End of a solve: what the host wants back, packed into ONE block (one device-to-host copy instead of five):
-//   out[0..3] = sums over the rollouts of NewtonDev::stats, out[4] = sum of the Newton iteration counts,
-//   out[8 + b (nu + 2) + ..] = [u_1 (nu) | newton iterations | r_norm] of rollout b   (core.traj.u[1], policy.jl:142).
-// Counts travel as doubles (exact below 2^53).
+// the sums of NewtonDev::stats and of the Newton iteration counts, then [u_1 | newton iterations | r_norm] of every rollout
+// (core.traj.u[1], policy.jl:142); layout: round_protocol.h.
 __global__ __launch_bounds__(256) void solve_finish_kernel(NewtonDev S, double* out) {
-    __shared__ double red[5][256];
-    const int tid = threadIdx.x, B = S.dm.B, H = S.dm.H, nu = S.dm.nu, w = nu + 2;
-    double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    __shared__ double red[RESULT_SUMS][256];
+    const int tid = threadIdx.x, B = S.dm.B, H = S.dm.H, nu = S.dm.nu;
+    double acc[RESULT_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int b = tid; b < B; b += 256) {
-        for (int k = 0; k < 4; ++k) acc[k] += (double)S.stats[(size_t)b * 4 + k];
-        acc[4] += (double)S.newton_l[b];
-        double* o = out + 8 + (size_t)b * w;
+        for (int k = 0; k < RESULT_STATS; ++k) acc[k] += (double)S.stats[(size_t)b * 4 + k];
+        acc[RESULT_NEWTON_SUM] += (double)S.newton_l[b];
+        double* o = out + result_u1(b, nu);
         for (int k = 0; k < nu; ++k) o[k] = S.traj.u[(size_t)b * H * nu + k];
-        o[nu] = (double)S.newton_l[b];
-        o[nu + 1] = S.r_norm[b];
+        o[record_iters(nu)] = (double)S.newton_l[b];
+        o[record_r_norm(nu)] = S.r_norm[b];
     }
-    for (int k = 0; k < 5; ++k) red[k][tid] = acc[k];
+    for (int k = 0; k < RESULT_SUMS; ++k) red[k][tid] = acc[k];
     __syncthreads();
     for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) for (int k = 0; k < 5; ++k) red[k][tid] += red[k][tid + st];
+        if (tid < st) for (int k = 0; k < RESULT_SUMS; ++k) red[k][tid] += red[k][tid + st];
         __syncthreads();
     }
-    if (tid < 5) out[tid] = red[tid][0];
+    if (tid < RESULT_SUMS) out[tid] = red[tid][0];
 }
 // Flush of the lazily committed sensitivities (NewtonDev::good_src) at the end of a solve: the blocks an accept left in the
 // evaluation slots of a rollout that had no KKT stage afterwards (it converged, ran out of iterations, or the solve was cut
@@ -634,13 +633,13 @@ __global__ __launch_bounds__(256) void cf_reduce_post_kernel(NewtonDev S, KktArg
     }
     __syncthreads();
     if (K.finish) {
-        // (the reduced solve may have been the twisted banded kernel: a hand-over that timed out left its mark - words 3 / 7 of the
+        // (the reduced solve may have been the twisted banded kernel: a hand-over that timed out left its mark - the TW_TIMED_OUT words of the
         //  rollout's flag line carry the launch's stamp - and poisoned numbers; the KKT stage of the rollout is queued again instead)
         if (S.kkt_tw_flags != nullptr) {
             const int* fl = S.kkt_tw_flags + (size_t)b * KKT_TW_FLAGS;
-            if (aload(fl + 3) == S.kkt_tw_epoch || aload(fl + 7) == S.kkt_tw_epoch) {
+            if (aload(fl + TW_TIMED_OUT) == S.kkt_tw_epoch || aload(fl + KKT_BAND_TW_FLAG0 + TW_TIMED_OUT) == S.kkt_tw_epoch) {
                 if (tid == 0) {
-                    const int pos = atomicAdd(&S.counters[1 * CPAD], 1);
+                    const int pos = atomicAdd(round_counter(S.counters, RC_KKT), 1);
                     if (S.kkt_list != nullptr && pos < S.dm.B) S.kkt_list[(size_t)S.WQ.par * S.dm.B + pos] = b;
                 }
                 return;

@@ -66,13 +66,13 @@ struct NewtonDev {
     int* stage;        // [B]
     int* kkt_list;     // [2][B] rollouts that entered STAGE_KKT, per round parity (compact list for the packed KKT launch)
     int* need_sweep;   // [B*CS]
-    int* slot_list;    // [2][B*CS] evaluation slots requested for a round (by queue parity, count in counters[4]): the residual launch
+    int* slot_list;    // [2][B*CS] evaluation slots requested for a round (by queue parity, count in RC_SLOTS): the residual launch
                        // of that round gets one workgroup per ENTRY instead of one per (rollout, slot) pair - idle blocks are not free
                        // (3584 blocks, 15 % live: 50 us per launch, most of it block dispatch)
-    int* counters;     // [8 * CPAD], counter k at k * CPAD: 0 = #rollouts needing a sweep, 1 = #needing KKT, 2 = parked solves, 3 = drained workgroups, 4 = evaluation slots requested of the next round, 7 = block ticket
+    int* counters;     // the round's counter block (round_protocol.h: RoundCounter, round_counter)
     int* counters_next; // counter block of the next round (zeroed by the residual kernel)
-    int* host_flag;    // host-mapped pinned {n_sweep, n_kkt, stamp}
-    int round_stamp;   // value published to host_flag[2] when the round is complete
+    int* host_flag;    // the round's slot of the host-mapped ring (round_protocol.h: RingWord)
+    int round_stamp;   // value published as RING_STAMP when the round is complete
     int band_reduce;   // banded LDL^T backend: 1 = eliminate the controls first (every R_t inverted on the host), 0 = full interleaved form
     int band_form;     // ... test handle (CIMPC_BANDED_FORM): bit 0 = four pivots per block, bit 1 = no power-of-two padding of the window (bit 2, host only: controls kept)
     long long* stats;  // [B][4] per rollout: sweeps, ip_solves, ip_iters, ip_failures of the running solve, speculative evaluations included
@@ -99,7 +99,7 @@ struct NewtonDev {
     // The flags are EPOCH-valued (round 6): a producer stores the launch's stamp `kkt_tw_epoch` (the host bumps it for every
     // KKT stage), a consumer waits for equality and never resets - a partner that arrives after its waiter gave up cannot leave a
     // raised flag behind for the next solve of the rollout.  A wait is bounded by `kkt_tw_spins` polls; a chain that gives up marks
-    // the rollout (flag word 3 = epoch) and counts in `kkt_tw_fail` (host-mapped): the chain that finishes last then re-queues the
+    // the rollout (TW_TIMED_OUT = epoch) and counts in `kkt_tw_fail` (host-mapped): the chain that finishes last then re-queues the
     // rollout's KKT stage instead of starting the line search on poisoned numbers, and the host serves it with the one-ended kernel.
     int kkt_tw_epoch;
     int kkt_tw_spins;
