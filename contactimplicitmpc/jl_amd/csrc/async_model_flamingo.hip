@@ -1,5 +1,5 @@
 // Asynchronous single-launch Newton solve, flamingo dimensions.
 #include "newton_async_impl.h"
 namespace cimpc {
-CIMPC_DEFINE_ASYNC_MODEL(flamingo, 9, 6, 2, 4, 8)
+CIMPC_DEFINE_ASYNC_MODEL(flamingo)
 }  // namespace cimpc

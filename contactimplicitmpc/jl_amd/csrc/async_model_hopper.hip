@@ -1,5 +1,5 @@
 // Asynchronous single-launch Newton solve, hopper dimensions.
 #include "newton_async_impl.h"
 namespace cimpc {
-CIMPC_DEFINE_ASYNC_MODEL(hopper, 4, 2, 2, 1, 2)
+CIMPC_DEFINE_ASYNC_MODEL(hopper)
 }  // namespace cimpc

@@ -1,5 +1,5 @@
 // Asynchronous single-launch Newton solve, pushbot dimensions.
 #include "newton_async_impl.h"
 namespace cimpc {
-CIMPC_DEFINE_ASYNC_MODEL(pushbot, 2, 2, 2, 2, 4)
+CIMPC_DEFINE_ASYNC_MODEL(pushbot)
 }  // namespace cimpc

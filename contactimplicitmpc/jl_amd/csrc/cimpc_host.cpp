@@ -14,6 +14,7 @@
 
 #include "cimpc_internal.h"
 #include "lin_table.h"
+#include "model_table.h"
 #include "newton_state.h"
 #include "schedule_plan.h"
 
@@ -486,9 +487,9 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
     h->kn.read_environment();       // the only place the environment is consulted
     if (ip_kernel_info(&h->dm, &h->ki) != CIMPC_OK) {
         delete h;
-        return fail(nullptr, CIMPC_ERR_INVALID,
-                    "model dimensions outside the runtime-dimension kernel (nx, ny <= 64) and without a compiled set (built: pushbot, hopper_2D, hopper_3D, walledcartpole, particle, particle_2D, "
-                    "quadruped, flamingo, centroidal_quadruped are built)");
+        std::string built;
+        for (const ModelRow& r : MODEL_TABLE) (built += built.empty() ? "" : ", ") += r.name;
+        return fail(nullptr, CIMPC_ERR_INVALID, "model dimensions outside the runtime-dimension kernel (nx, ny <= 64) and without a compiled set (built: " + built + ")");
     }
     h->nx = d.nq;
     h->ny = 2 * d.nc + d.nb;

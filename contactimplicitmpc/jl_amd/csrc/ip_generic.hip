@@ -1,5 +1,5 @@
 // Runtime-dimension interior-point sweep: the fallback for model dimensions without a compiled lane-group kernel
-// (ip_dispatch.hip: CIMPC_MODELS).  The reference's operators are generic in (nx, ny, nθ)
+// (model_table.h).  The reference's operators are generic in (nx, ny, nθ)
 // (/root/reference/src/controller/linearized_solver.jl:15-65); with this kernel any model with nx, ny <= 64 loads -
 // e.g. centroidal_quadruped_wall (nq 18, nc 8, nb 32: ny = 48), which no 32-lane group holds.
 //

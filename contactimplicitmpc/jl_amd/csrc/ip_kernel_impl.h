@@ -22,6 +22,7 @@
 #include "cimpc_internal.h"
 #include "lane_group.h"
 #include "lin_table.h"
+#include "model_table.h"
 
 // wave priorities: the KKT recursion that runs next to the sweep (second stream, one wave per rollout) is the longer leg of
 // most rounds since the sweep lost a third of its instructions: it gets the issue slots first (KKT 2 / sweep 0: 11.9 -> 11.6 ms)
@@ -1422,28 +1423,34 @@ void info_model(KernelInfo* info) {
     info->adj = M::ADJ;
 }
 
-#define CIMPC_DEFINE_MODEL(name, q, u, w, c, b)                                              \
-    int ip_launch_##name(int mode, const IpParams& p, int waves, hipStream_t s) {            \
-        if (mode == 0) return launch_model<Model<q, u, w, c, b, 0>>(p, waves, s);            \
-        return launch_model<Model<q, u, w, c, b, 1>>(p, waves, s);                           \
-    }                                                                                        \
-    int ip_callback_##name(int mode, const IpCallbackArgs& a, hipStream_t s) {               \
-        if (mode == 0) return launch_callback<Model<q, u, w, c, b, 0>>(a, s);                \
-        return launch_callback<Model<q, u, w, c, b, 1>>(a, s);                               \
-    }                                                                                        \
-    void ip_info_##name(int mode, KernelInfo* info) {                                        \
-        if (mode == 0) info_model<Model<q, u, w, c, b, 0>>(info);                            \
-        else info_model<Model<q, u, w, c, b, 1>>(info);                                      \
-    }
+// The model of a row of model_table.h.  Rows of at most 32 lanes are built for both modes; a 64-lane row (ny > 32: one problem per
+// wavefront) for :configuration only - :configurationforce stays with the runtime-dimension kernel, the B2 callbacks are not offered.
+template <int ID, int MODE> using RowModel = Model<MODEL_TABLE[ID].nq, MODEL_TABLE[ID].nu, MODEL_TABLE[ID].nw, MODEL_TABLE[ID].nc, MODEL_TABLE[ID].nb, MODE>;
+template <int ID> constexpr bool ROW_TWO_MODES = model_lanes(MODEL_TABLE[ID]) <= 32;
+#define X(name, q, u, w, c, b, a) static_assert(model_lanes(MODEL_TABLE[MODEL_##name]) == RowModel<MODEL_##name, 0>::G, "model_table.h: lane-group width");
+CIMPC_MODEL_TABLE(X)
+#undef X
 
-// 64-lane models (ny > 32: one problem per wavefront): :configuration mode only - :configurationforce and the B2 callbacks stay
-// with the runtime-dimension kernel / are not offered (ip_dispatch.hip)
-#define CIMPC_DEFINE_MODEL64(name, q, u, w, c, b)                                            \
-    int ip_launch_##name(int mode, const IpParams& p, int waves, hipStream_t s) {            \
-        if (mode != 0) return CIMPC_ERR_INVALID;                                             \
-        return launch_model<Model<q, u, w, c, b, 0>>(p, waves, s);                           \
-    }                                                                                        \
-    void ip_info_##name(int mode, KernelInfo* info) { (void)mode; info_model<Model<q, u, w, c, b, 0>>(info); }
+template <int ID>
+int launch_row(int mode, const IpParams& p, int waves, hipStream_t s) {
+    if (mode == 0) return launch_model<RowModel<ID, 0>>(p, waves, s);
+    if constexpr (ROW_TWO_MODES<ID>) return launch_model<RowModel<ID, 1>>(p, waves, s);
+    return CIMPC_ERR_INVALID;
+}
+template <int ID>
+int callback_row(int mode, const IpCallbackArgs& a, hipStream_t s) {
+    if constexpr (ROW_TWO_MODES<ID>) return mode == 0 ? launch_callback<RowModel<ID, 0>>(a, s) : launch_callback<RowModel<ID, 1>>(a, s);
+    return CIMPC_ERR_INVALID;
+}
+template <int ID>
+void info_row(int mode, KernelInfo* info) {
+    if constexpr (ROW_TWO_MODES<ID>) if (mode != 0) return info_model<RowModel<ID, 1>>(info);
+    info_model<RowModel<ID, 0>>(info);
+}
+#define CIMPC_DEFINE_MODEL(name)                                                                                                        \
+    int ip_launch_##name(int mode, const IpParams& p, int waves, hipStream_t s) { return launch_row<MODEL_##name>(mode, p, waves, s); } \
+    int ip_callback_##name(int mode, const IpCallbackArgs& a, hipStream_t s) { return callback_row<MODEL_##name>(mode, a, s); }         \
+    void ip_info_##name(int mode, KernelInfo* info) { info_row<MODEL_##name>(mode, info); }
 
 }  // namespace cimpc
 

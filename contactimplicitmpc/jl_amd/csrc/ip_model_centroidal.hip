@@ -1,7 +1,7 @@
 // Interior-point sweep kernel instantiation: centroidal dimensions.
 #include "ip_kernel_impl.h"
 namespace cimpc {
-CIMPC_DEFINE_MODEL(centroidal, 18, 12, 3, 4, 16)
+CIMPC_DEFINE_MODEL(centroidal)
 }  // namespace cimpc
 
 #ifdef CIMPC_SWEEP_PROF
@@ -26,7 +26,7 @@ extern "C" int cimpc_debug_sweep_prof_centroidal(unsigned long long* out16) {
 #ifdef CIMPC_UBENCH
 // diagnostic builds only (-DCIMPC_UBENCH, scripts/dbg/ubench_ip.py): ip_kernel_impl.h: ip_ubench_kernel on the THROUGHPUT build of the 32-lane form
 extern "C" int cimpc_ubench_ip_centroidal(const double* tabs_dev, const cimpc_ip_opts* o, int waves, int reps, long long* out_host) {
-    using M = cimpc::Model<18, 12, 3, 4, 16, 0, 1>;
+    using M = cimpc::RowModel<cimpc::MODEL_centroidal, 0>::Wide;
     constexpr cimpc::LinLayout L(M::NX, M::NY, M::NTH, M::G, M::NTHS, M::ADJ);
     long long* d = nullptr;
     if (hipMalloc(&d, 8 * 8 * sizeof(long long)) != hipSuccess) return -1;

@@ -2,5 +2,5 @@
 // nc = 8 contacts, ny = 2 nc + nb = 48 > 32) - 64-lane groups, ONE problem per wavefront (round 6), :configuration mode.
 #include "ip_kernel_impl.h"
 namespace cimpc {
-CIMPC_DEFINE_MODEL64(centroidal_wall, 18, 12, 3, 8, 32)
+CIMPC_DEFINE_MODEL(centroidal_wall)
 }  // namespace cimpc

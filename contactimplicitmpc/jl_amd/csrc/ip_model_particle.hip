@@ -1,5 +1,5 @@
 // Interior-point sweep kernel instantiation: particle (src/dynamics/particle/model.jl:114-117) dimensions (lock-step rounds; no single-launch kernel).
 #include "ip_kernel_impl.h"
 namespace cimpc {
-CIMPC_DEFINE_MODEL(particle, 3, 3, 3, 1, 4)
+CIMPC_DEFINE_MODEL(particle)
 }  // namespace cimpc

@@ -1,5 +1,5 @@
 // Interior-point sweep kernel instantiation: pushbot dimensions.
 #include "ip_kernel_impl.h"
 namespace cimpc {
-CIMPC_DEFINE_MODEL(pushbot, 2, 2, 2, 2, 4)
+CIMPC_DEFINE_MODEL(pushbot)
 }  // namespace cimpc

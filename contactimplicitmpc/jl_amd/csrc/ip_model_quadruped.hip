@@ -1,7 +1,7 @@
 // Interior-point sweep kernel instantiation: quadruped dimensions.
 #include "ip_kernel_impl.h"
 namespace cimpc {
-CIMPC_DEFINE_MODEL(quadruped, 11, 8, 2, 4, 8)
+CIMPC_DEFINE_MODEL(quadruped)
 }  // namespace cimpc
 
 #ifdef CIMPC_SWEEP_PROF
@@ -16,7 +16,7 @@ extern "C" int cimpc_debug_sweep_prof(unsigned long long* out16) {
 #ifdef CIMPC_UBENCH
 // diagnostic builds only (-DCIMPC_UBENCH, scripts/dbg/ubench_ip.py): see ip_kernel_impl.h: ip_ubench_kernel
 extern "C" int cimpc_ubench_ip_quadruped(const double* tabs_dev, const cimpc_ip_opts* o, int waves, int reps, long long* out_host) {
-    using M = cimpc::Model<11, 8, 2, 4, 8, 0>;
+    using M = cimpc::RowModel<cimpc::MODEL_quadruped, 0>;
     constexpr cimpc::LinLayout L(M::NX, M::NY, M::NTH, M::G, M::NTHS, M::ADJ);
     long long* d = nullptr;
     if (hipMalloc(&d, 8 * 8 * sizeof(long long)) != hipSuccess) return -1;

@@ -1,5 +1,5 @@
 // Interior-point sweep kernel instantiation: walledcartpole (src/dynamics/walledcartpole/model.jl:143-147) dimensions (lock-step rounds; no single-launch kernel).
 #include "ip_kernel_impl.h"
 namespace cimpc {
-CIMPC_DEFINE_MODEL(walledcartpole, 4, 1, 4, 2, 4)
+CIMPC_DEFINE_MODEL(walledcartpole)
 }  // namespace cimpc

@@ -265,9 +265,10 @@ int launch_async_model(const IpParams& p, const NewtonDev& S, int waves, int gri
     return hipGetLastError() == hipSuccess ? CIMPC_OK : CIMPC_ERR_HIP;
 }
 
-#define CIMPC_DEFINE_ASYNC_MODEL(name, q, u, w, c, b)                                                   \
-    int async_launch_##name(const IpParams& p, const NewtonDev& S, int waves, int grid, hipStream_t s) { \
-        return launch_async_model<Model<q, u, w, c, b, 0>>(p, S, waves, grid, s);                       \
+#define CIMPC_DEFINE_ASYNC_MODEL(name)                                                                      \
+    static_assert(MODEL_TABLE[MODEL_##name].async, "model_table.h: the row has no single-launch solve");    \
+    int async_launch_##name(const IpParams& p, const NewtonDev& S, int waves, int grid, hipStream_t s) {    \
+        return launch_async_model<RowModel<MODEL_##name, 0>>(p, S, waves, grid, s);                         \
     }
 
 }  // namespace cimpc

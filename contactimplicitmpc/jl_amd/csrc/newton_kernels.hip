@@ -15,6 +15,7 @@
 #define CIMPC_KKT_WPROF      // per-wave clocks of the pipelined KKT kernel: this translation unit only (the asynchronous kernel's does not survive them)
 #endif
 #include "newton_impl.h"
+#include "model_table.h"
 
 namespace cimpc {
 
@@ -90,11 +91,6 @@ static int launch_kkt_t(const NewtonDev& S, const KktArgs& K, KktForm f, bool f3
     return launch_lds(optin, kkt_kernel_scalar<NQ, NU>, dim3(S.nb_launch), dim3(64), (size_t)(KKT_TILES * LD * LD + 10 * LD) * sizeof(double), s, S, K);
 }
 
-// (nq, nu) pairs of the built models (the horizon-level kernels depend on these two sizes only): pushbot / particle_2D,
-// hopper_2D, quadruped, flamingo, centroidal_quadruped (= point_foot_quadruped, centroidal_quadruped_box), hopper_3D,
-// walledcartpole, particle
-#define CIMPC_NQNU(X) X(2, 2) X(4, 2) X(11, 8) X(9, 6) X(18, 12) X(7, 3) X(4, 1) X(3, 3)
-
 // compact-list forms: rollouts list[0 .. n) (list == null: every rollout of the launch, stage filter as kkt_kernel - Twisted / Duo)
 template <int NQ, int NU>
 static int launch_kkt_list_t(const NewtonDev& S, const KktArgs& K, KktForm f, const int* list, int n, const int* n_dev, hipStream_t s) {
@@ -130,8 +126,9 @@ static int launch_kkt_condensed(const NewtonDev& S, const KktArgs& K, KktForm f,
     if (n_dev != nullptr) n = S.dm.B;      // upper bound of the grid; surplus workgroups leave at once
     if (n <= 0) return CIMPC_OK;
     const int nq = S.dm.nq, nu = S.dm.nu;
-#define X(q, u) if (nq == q && nu == u) return rollout ? launch_kkt_t<q, u>(S, K, f, f32, s) : f32 ? CIMPC_ERR_INVALID : launch_kkt_list_t<q, u>(S, K, f, list, n, n_dev, s);
-    CIMPC_NQNU(X)
+    // one instantiation per (nq, nu) of model_table.h (a pair that two rows share - pushbot / particle_2D, the two centroidal rows - repeats its branch, unreachable)
+#define X(name, q, u, w, c, b, a) if (nq == q && nu == u) return rollout ? launch_kkt_t<q, u>(S, K, f, f32, s) : f32 ? CIMPC_ERR_INVALID : launch_kkt_list_t<q, u>(S, K, f, list, n, n_dev, s);
+    CIMPC_MODEL_TABLE(X)
 #undef X
     return CIMPC_ERR_INVALID;
 }
@@ -514,8 +511,8 @@ int launch_dz_commit(const NewtonDev& S, hipStream_t s) {
 bool kkt_mfma_available(const NewtonDev& S) {      // the bounds of launch_kkt_t's KktForm::PerRollout
     const int nq = S.dm.nq, nu = S.dm.nu;
     if (S.dm.mode != CIMPC_MODE_CONFIGURATION || nq > 24 || nu > 24) return false;
-#define X(q, u) if (nq == q && nu == u) return S.dm.H <= kkt_max_h<q, u>();
-    CIMPC_NQNU(X)
+#define X(name, q, u, w, c, b, a) if (nq == q && nu == u) return S.dm.H <= kkt_max_h<q, u>();
+    CIMPC_MODEL_TABLE(X)
 #undef X
     return false;
 }
@@ -536,8 +533,8 @@ int launch_queue_recycle(const IpQueues& Q, int par, hipStream_t s) {
 }
 int launch_resid_decide(const NewtonDev& S, hipStream_t s, int n_slots, int phase) {
     const int nq = S.dm.nq, nu = S.dm.nu;
-#define X(q, u) if (nq == q && nu == u) return launch_resid_t<q, u>(S, s, n_slots, phase);
-    CIMPC_NQNU(X)
+#define X(name, q, u, w, c, b, a) if (nq == q && nu == u) return launch_resid_t<q, u>(S, s, n_slots, phase);
+    CIMPC_MODEL_TABLE(X)
 #undef X
     return launch_resid_t<0, 0>(S, s, n_slots, phase);        // runtime dimensions (models without a compiled set)
 }
@@ -684,11 +681,7 @@ bool kkt_duo_available(const NewtonDev& S) {      // the twisted solve's conditi
     return S.dm.nq <= 16 && S.dm.nu <= 16 && kkt_twisted_available(S);
 }
 bool kkt_condensed_available(const NewtonDev& S) {      // a compiled condensed solve exists for these (nq, nu)
-    const int nq = S.dm.nq, nu = S.dm.nu;
-#define X(q, u) if (nq == q && nu == u) return true;
-    CIMPC_NQNU(X)
-#undef X
-    return false;
+    return model_has_nqnu(S.dm.nq, S.dm.nu);
 }
 
 int launch_kkt_stage(const NewtonDev& S, const KktArgs& K, KktBackend be, KktForm f, const int* list, int n, const int* n_dev,

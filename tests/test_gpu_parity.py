@@ -350,6 +350,32 @@ def test_async_single_launch_matches_lockstep(gpu_required, monkeypatch, mode, B
         np.testing.assert_allclose(a[3][k], b[3][k], rtol=1e-12, atol=1e-14)
 
 
+@pytest.mark.parametrize("model", ["pushbot", "hopper", "flamingo", "centroidal"])
+def test_async_single_launch_other_models(gpu_required, monkeypatch, model):
+    """Every other row of model_table.h with a single-launch instantiation reaches ITS persistent kernel (one round), and that kernel
+    runs the arithmetic of the lock-step rounds: the case of test_newton_solve_other_models, compared as the quadruped is above."""
+    from contactimplicitmpc.jl_amd import NewtonOptions
+    B, H, H_ref = 4, 6, 8
+    d, prob, tabs, rollouts = make_case(model, 0, H_ref=H_ref, H=H, B=B, seed=23, perturb=5e-3)
+    obj = synth.make_objective(d, H, kind=model, dense_q=model == "centroidal")
+    q0 = np.stack([r[2] for r in rollouts]); q1 = np.stack([r[3] for r in rollouts])
+    monkeypatch.setenv("CIMPC_KKT_TWISTED", "0")
+    outs = []
+    for flag in ("0", "1"):
+        monkeypatch.setenv("CIMPC_ASYNC", flag)
+        s = make_solver(d, prob, rollouts, H, obj=obj, newton_opts=NewtonOptions(kappa=prob["kappa"], r_tol=1e-5, max_iter=4))
+        u1, it, rn = s.newton_solve(q0, q1)
+        outs.append((u1, it, s.trajectory(), s.rollout_counters(), s.stats()))
+    a, b = outs
+    assert b[4]["rounds"] == 1
+    np.testing.assert_array_equal(a[1], b[1])
+    for k in ("sweeps", "ip_iters", "ip_failures"):
+        np.testing.assert_array_equal(a[3][k], b[3][k])
+    np.testing.assert_allclose(a[0], b[0], rtol=1e-12, atol=1e-14)
+    for k in ("q", "u", "nu"):
+        np.testing.assert_allclose(a[2][k], b[2][k], rtol=1e-12, atol=1e-14)
+
+
 def test_full_size_schedules_agree(gpu_required, monkeypatch):
     """BASELINE.json's full-size workload (quadruped, H = 40, H_ref = 60, 512 rollouts, cold start): the hybrid
     schedule (rounds + asynchronous tail, packed KKT) and the plain lock-step rounds must produce the same
