@@ -64,6 +64,7 @@ constexpr int PLANT_NC = 4, PLANT_NB = 16, PLANT_NW = 3;     // maxima: four con
 constexpr int PLANT_KIND_CHAIN = 0, PLANT_KIND_HOPPER_2D = 1, PLANT_KIND_CENTROIDAL = 2, PLANT_KIND_PARTICLE = 3, PLANT_KIND_PARTICLE_2D = 4;
 // centroidal_quadruped_box / _wall: plant_residual_centroidal_env, stepped by their own kernel instantiations (plant_kernel.hip)
 constexpr int PLANT_KIND_CENTROIDAL_BOX = 5, PLANT_KIND_CENTROIDAL_WALL = 6;
+constexpr int PLANT_KIND_HOPPER_3D = 7;                      // hopper_3D: plant_residual_hopper_3d, stepped by kernel instantiations of its own size
 constexpr int PLANT_WALL_NC = 8, PLANT_WALL_NB = 32;          // the wall model: four feet on the floor and the same four on the wall
 
 struct PlantChain { int n; double r[PLANT_MAX_SEG]; int k[PLANT_MAX_SEG]; };
@@ -280,11 +281,15 @@ PLANT_HD void plant_residual_particle(const PlantModel& M, const T* z, const dou
     r[14] = psi[0] * s2[0] - kappa;
 }
 
+template <class T>
+PLANT_HD void plant_residual_hopper_3d(const PlantModel& M, const cimpc_terrain* E, const T* z, const double* th, double kappa, T* r);      // below the terrain
+
 // r(z, θ, κ): z = [q2; γ; b; ψ; s1; η; s2], θ = [q0; q1; u1; w1; μ; h] (θ real: only dr/dz is needed)
 template <class T>
 PLANT_HD void plant_residual(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
     if (M.kind == PLANT_KIND_CENTROIDAL) { plant_residual_centroidal<T>(M, z, th, kappa, r); return; }
     if (M.kind == PLANT_KIND_PARTICLE) { plant_residual_particle<T>(M, z, th, kappa, r); return; }
+    if (M.kind == PLANT_KIND_HOPPER_3D) { plant_residual_hopper_3d<T>(M, nullptr, z, th, kappa, r); return; }
     const int nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb();
     const double* q0 = th; const double* q1 = th + nq; const double* u1 = th + 2 * nq; const double* w1 = u1 + nu;
     const double mu = w1[M.nw], h = w1[M.nw + 1];
@@ -479,14 +484,114 @@ PLANT_HD void plant_residual_particle_terrain(const PlantModel& M, const cimpc_t
     r[14] = psi[0] * s2[0] - kappa;
 }
 
+// ---- hopper_3D (src/dynamics/hopper_3D/model.jl): q = (body position, modified Rodrigues parameters p, leg length l), all mass
+// at the body: M = diag(mb + ml x3, Jb + Jl x3, ml) (mass[0..6]), C = (0, 0, (mb + ml) g, 0...), lagrangian = 0 (:30-48); the one
+// contact is the foot k = pos - R(p) e_3 l (:33-37), four friction directions; B(qm2)^T u = (R e_3 u_3; R[:, 1:2] u_{1:2}; u_3)
+// (:54-60), A = eye(3, 7).  R is the standard rotation of the parameters, R = I + (8 S^2 + 4 (1 - |p|^2) S) / (1 + |p|^2)^2 with
+// S = skew(p): the convention the model's gait files satisfy (tests/test_hopper_3d.py).
+template <class T>
+PLANT_HD void plant_mrp_rotation(const T* p, T R[3][3]) {
+    const T n = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+    const T c = 1.0 / ((1.0 + n) * (1.0 + n)), f = 4.0 * (1.0 - n);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R[i][j] = c * (8.0 * (p[i] * p[j]));
+    for (int i = 0; i < 3; ++i) R[i][i] = R[i][i] + (1.0 - c * (8.0 * n));
+    R[0][1] = R[0][1] - c * (f * p[2]); R[0][2] = R[0][2] + c * (f * p[1]);
+    R[1][0] = R[1][0] + c * (f * p[2]); R[1][2] = R[1][2] - c * (f * p[0]);
+    R[2][0] = R[2][0] - c * (f * p[1]); R[2][1] = R[2][1] + c * (f * p[0]);
+}
+// a = R(p) e_3 and D[i][j] = da_i / dp_j.  The reference takes J = dk/dq from ForwardDiff (:70-73); a one-tangent dual cannot nest,
+// so the derivative is written out: a = e_3 + N / d, N = 8 (p_x p_z, p_y p_z, p_z^2 - |p|^2) + 4 (1 - |p|^2) (p_y, -p_x, 0),
+// d = (1 + |p|^2)^2, da_i/dp_j = (dN_i/dp_j - 4 N_i p_j / (1 + |p|^2)) / d.
+template <class T>
+PLANT_HD void plant_mrp_axis(const T* p, T a[3], T D[3][3]) {
+    const T px = p[0], py = p[1], pz = p[2];
+    const T n = px * px + py * py + pz * pz;
+    const T c = 1.0 / ((1.0 + n) * (1.0 + n)), f = 4.0 * (1.0 - n), g = 4.0 / (1.0 + n);
+    const T N[3] = {8.0 * (px * pz) + f * py, 8.0 * (py * pz) - f * px, -8.0 * (px * px + py * py)};
+    T dN[3][3];
+    dN[0][0] = 8.0 * pz - 8.0 * (px * py);  dN[0][1] = f - 8.0 * (py * py);         dN[0][2] = 8.0 * px - 8.0 * (py * pz);
+    dN[1][0] = 8.0 * (px * px) - f;         dN[1][1] = 8.0 * pz + 8.0 * (px * py);  dN[1][2] = 8.0 * py + 8.0 * (px * pz);
+    dN[2][0] = -16.0 * px;                  dN[2][1] = -16.0 * py;                  dN[2][2] = pconst<T>(0.0);
+    for (int i = 0; i < 3; ++i) {
+        a[i] = c * N[i];
+        for (int j = 0; j < 3; ++j) D[i][j] = c * (dN[i][j] - (g * N[i]) * p[j]);
+    }
+    a[2] = a[2] + 1.0;
+}
+// Both grounds: E = nullptr (or a flat E) is flat_3D_lc, surface rotation = identity; otherwise surface and rotation are taken at
+// the foot k[0:2] as plant_residual_particle_terrain takes them at the particle: force Rs^T [m b; γ], tangential velocity
+// (Rs J (q2 - q1) / h)[0:2], ϕ = k_z - surf(k_x, k_y) (:50-52, :75-87).
+template <class T>
+PLANT_HD void plant_residual_hopper_3d(const PlantModel& M, const cimpc_terrain* E, const T* z, const double* th, double kappa, T* r) {
+    constexpr int nq = 7;
+    const double* q0 = th; const double* q1 = th + 7; const double* u1 = th + 14; const double* w1 = th + 17;
+    const double mu = th[20], h = th[21];
+    const T* q2 = z; const T* gam = z + 7; const T* b = z + 8; const T* psi = z + 12; const T* s1 = z + 13; const T* eta = z + 14; const T* s2 = z + 18;
+    T qm2[nq], vm2[nq], dyn[nq];
+    for (int i = 0; i < nq; ++i) { qm2[i] = (q2[i] + q1[i]) * 0.5; vm2[i] = (q2[i] - q1[i]) / h; }
+    // 0.5 h D1L + D2L at (qm1, vm1), 0.5 h D1L - D2L at (qm2, vm2): D1L = -C, D2L = M v
+    for (int i = 0; i < nq; ++i) dyn[i] = pconst<T>(M.mass[i] * ((q1[i] - q0[i]) / h)) - M.mass[i] * vm2[i];
+    dyn[2] = dyn[2] - h * (M.mass[2] * M.g);
+    T Rm[3][3];
+    plant_mrp_rotation(qm2 + 3, Rm);
+    for (int i = 0; i < 3; ++i) {
+        dyn[i] = dyn[i] + Rm[i][2] * u1[2] + w1[i];
+        dyn[3 + i] = dyn[3 + i] + (Rm[i][0] * u1[0] + Rm[i][1] * u1[1]);
+    }
+    dyn[6] = dyn[6] + u1[2];
+    // the foot k = pos - a l at q2, J = [I, -l da/dp, -a], its velocity J (q2 - q1) / h
+    T a[3], D[3][3], k[3], v[3];
+    plant_mrp_axis(q2 + 3, a, D);
+    const T l = q2[6];
+    for (int i = 0; i < 3; ++i) {
+        k[i] = q2[i] - a[i] * l;
+        v[i] = vm2[i] - l * (D[i][0] * vm2[3] + D[i][1] * vm2[4] + D[i][2] * vm2[5]) - a[i] * vm2[6];
+    }
+    const T fl[3] = {b[0] - b[2], b[1] - b[3], gam[0]};
+    T F[3], v0, v1x, phi;
+    if (E && E->kind != CIMPC_TERRAIN_FLAT) {
+        T surf, gx, gy;
+        terrain_eval(*E, k[0], k[1], surf, gx, gy);
+        const T inv = 1.0 / psqrt(1.0 + gx * gx + gy * gy);
+        const T nx = -(gx * inv), ny = -(gy * inv), nz = inv;
+        const T vx = ny, vy = -nx, kk = 1.0 / (1.0 + nz);
+        T R[3][3];
+        R[0][0] = 1.0 - kk * (vy * vy); R[0][1] = kk * (vx * vy);       R[0][2] = vy;
+        R[1][0] = kk * (vx * vy);       R[1][1] = 1.0 - kk * (vx * vx); R[1][2] = -vx;
+        R[2][0] = -vy;                  R[2][1] = vx;                   R[2][2] = 1.0 - kk * (vx * vx + vy * vy);
+        for (int i = 0; i < 3; ++i) F[i] = R[0][i] * fl[0] + R[1][i] * fl[1] + R[2][i] * fl[2];
+        v0 = R[0][0] * v[0] + R[0][1] * v[1] + R[0][2] * v[2];
+        v1x = R[1][0] * v[0] + R[1][1] * v[1] + R[1][2] * v[2];
+        phi = k[2] - surf;
+    } else {
+        for (int i = 0; i < 3; ++i) F[i] = fl[i];
+        v0 = v[0]; v1x = v[1];
+        phi = k[2];
+    }
+    // J^T F
+    for (int i = 0; i < 3; ++i) dyn[i] = dyn[i] + F[i];
+    for (int j = 0; j < 3; ++j) dyn[3 + j] = dyn[3 + j] - l * (D[0][j] * F[0] + D[1][j] * F[1] + D[2][j] * F[2]);
+    dyn[6] = dyn[6] - (a[0] * F[0] + a[1] * F[1] + a[2] * F[2]);
+    for (int i = 0; i < nq; ++i) r[i] = dyn[i];
+    r[7] = s1[0] - phi;
+    r[8] = eta[0] - v0 - psi[0]; r[9] = eta[1] - v1x - psi[0];
+    r[10] = eta[2] + v0 - psi[0]; r[11] = eta[3] + v1x - psi[0];
+    r[12] = s2[0] - (mu * gam[0] - (b[0] + b[1] + b[2] + b[3]));
+    r[13] = gam[0] * s1[0] - kappa;
+    for (int q = 0; q < 4; ++q) r[14 + q] = b[q] * eta[q] - kappa;
+    r[18] = psi[0] * s2[0] - kappa;
+}
+
 // r(z, θ, κ) on terrain E: plant_residual with, per contact i at foot p_i, ϕ_i = p_z - surf(p_x), the world force R_i^T [m b_i; γ_i]
 // through both Jacobian rows of the foot and the tangential velocity (R_i J_i (q2 - q1) / h)[1] (simulation.jl:133-158,
 // contact_methods.jl, quadruped/model.jl:472-492, hopper_2D/model.jl:54-85).  Each contact's rotation is taken at its own foot.
-// Planar chains, hopper_2D, particle_2D and (3-D kinds) particle; centroidal_quadruped is refused by the caller.
+// Planar chains, hopper_2D, particle_2D and (3-D kinds) particle and hopper_3D; centroidal_quadruped is refused by the caller.
 template <class T>
 PLANT_HD void plant_residual_terrain(const PlantModel& M, const cimpc_terrain& E, const T* z, const double* th, double kappa, T* r) {
     if (M.kind == PLANT_KIND_PARTICLE) { plant_residual_particle_terrain<T>(M, E, z, th, kappa, r); return; }
     if (M.kind == PLANT_KIND_PARTICLE_2D) { plant_residual_particle_2d<T>(M, E, z, th, kappa, r); return; }
+    if (M.kind == PLANT_KIND_HOPPER_3D) { plant_residual_hopper_3d<T>(M, &E, z, th, kappa, r); return; }
     const int nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb();
     const double* q0 = th; const double* q1 = th + nq; const double* u1 = th + 2 * nq; const double* w1 = u1 + nu;
     const double mu = w1[M.nw], h = w1[M.nw + 1];
@@ -559,7 +664,7 @@ PLANT_HD void plant_residual_terrain(const PlantModel& M, const cimpc_terrain& E
 }
 
 // Which terrains a model takes (cimpc_plant_step_terrain): FLAT everywhere; planar kinds on the planar models; 3-D kinds on the
-// particle; centroidal_quadruped, _box and _wall flat only (their reference models never call surf or rotation: the box's step
+// particle and hopper_3D; centroidal_quadruped, _box and _wall flat only (their reference models never call surf or rotation: the box's step
 // and the wall are inside their phi).
 inline bool terrain_valid_for(const PlantModel& M, const cimpc_terrain& E) {
     const double* f[] = {E.p, E.brk + 1, E.off, &E.coef[0][0]};
@@ -573,7 +678,7 @@ inline bool terrain_valid_for(const PlantModel& M, const cimpc_terrain& E) {
     if (E.kind == CIMPC_TERRAIN_SOFTPLUS && E.p[1] == 0.0) return false;
     if (E.kind == CIMPC_TERRAIN_FLAT) return true;
     if (M.kind == PLANT_KIND_CENTROIDAL || M.kind == PLANT_KIND_CENTROIDAL_BOX || M.kind == PLANT_KIND_CENTROIDAL_WALL) return false;
-    return terrain_is_3d(E.kind) == (M.kind == PLANT_KIND_PARTICLE);
+    return terrain_is_3d(E.kind) == (M.kind == PLANT_KIND_PARTICLE || M.kind == PLANT_KIND_HOPPER_3D);
 }
 
 // ---- the two models the reference tests in closed loop ---------------------------------------------------------------
@@ -646,6 +751,16 @@ inline PlantModel plant_particle() {           // particle/model.jl:113-121
     for (int i = 0; i < 3; ++i) M.joint_friction[i] = 0.0;
     return M;
 }
+inline PlantModel plant_hopper_3d() {          // hopper_3D/model.jl:96-118
+    PlantModel M{};
+    M.kind = PLANT_KIND_HOPPER_3D; M.nc = 1; M.fd = 4; M.nw = 3;
+    M.nq = 7; M.nu = 3; M.g = 9.81; M.mu_world = 1.5; M.n_bodies = 0;
+    const double mb = 3.0, ml = 0.3, Jb = 0.75, Jl = 0.075;
+    for (int i = 0; i < 3; ++i) { M.mass[i] = mb + ml; M.mass[3 + i] = Jb + Jl; }      // diagonal of the mass matrix
+    M.mass[6] = ml;
+    for (int i = 0; i < 7; ++i) M.joint_friction[i] = 0.0;
+    return M;
+}
 inline PlantModel plant_particle_2d() {        // particle_2D/model.jl (particle_2D = Particle2D(2, 2, 2, 1, 1.0, 9.81, 1.0, 0.0, ...))
     PlantModel M{};
     M.kind = PLANT_KIND_PARTICLE_2D; M.nc = 1; M.fd = 2; M.nw = 2;
@@ -692,6 +807,7 @@ inline bool plant_model_by_id(int id, PlantModel* out) {
     case CIMPC_PLANT_PARTICLE_2D: *out = plant_particle_2d(); return true;
     case CIMPC_PLANT_CENTROIDAL_BOX: *out = plant_centroidal_box(); return true;
     case CIMPC_PLANT_CENTROIDAL_WALL: *out = plant_centroidal_wall(); return true;
+    case CIMPC_PLANT_HOPPER_3D: *out = plant_hopper_3d(); return true;      // id 9 is unassigned
     default: return false;
     }
 }

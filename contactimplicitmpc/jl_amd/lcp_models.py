@@ -9,6 +9,7 @@ definitions and differentiates it with torch (fp64, CPU, `torch.func` - exact de
   dynamics          src/dynamics/model.jl:11-36            (variational midpoint integrator)
   z / θ packing     src/simulation/index.jl:413-415, 437-451; simulation.jl:108-124
   hopper_2D         src/dynamics/hopper_2D/model.jl:31-110
+  hopper_3D         src/dynamics/hopper_3D/model.jl:30-118
   quadruped         src/dynamics/quadruped/model.jl:75-590  (planar kinematic tree, Lagrangian)
   flamingo          src/dynamics/flamingo/model.jl:62-503   (planar biped with toe / heel contacts)
   centroidal_quad.  src/dynamics/centroidal_quadruped/model.jl:61-229, src/dynamics/euler.jl:3-11
@@ -38,6 +39,7 @@ class ContactModel:
     name = ""
     nq = nu = nw = nc = 0
     space = 2                     # dim(env): 2 (x, z) or 3 (x, y, z)
+    stride_dims = 1               # leading coordinates a gait period advances (get_stride)
     mu_world = 1.0
     g = 9.81
 
@@ -178,6 +180,38 @@ class Hopper2D(ContactModel):
     def B(self, q):
         z, o = torch.zeros((), dtype=F64), torch.ones((), dtype=F64)
         return torch.stack([torch.stack([z, z, o, z]), torch.stack([-torch.sin(q[2]), torch.cos(q[2]), z, o])])
+
+
+def MRP(p):
+    """Rotation matrix of the modified Rodrigues parameters p (the one symbol hopper_3D/model.jl takes from outside the
+    reference tree): R = I + (8 S² + 4 (1 - |p|²) S) / (1 + |p|²)², S = skew(p).  The model's gait files pin the form: with Rᵀ
+    in its place gait_in_place.jld2 no longer satisfies the residual to 1e-8 (tests/test_hopper_3d.py)."""
+    n = p @ p
+    S = _skew(p)
+    return torch.eye(3, dtype=F64) + (8.0 * (S @ S) + 4.0 * (1.0 - n) * S) / (1.0 + n) ** 2
+
+
+class Hopper3D(ContactModel):
+    """src/dynamics/hopper_3D/model.jl: q = (body position, modified Rodrigues parameters, leg length), all mass at the body,
+    one contact at the foot p - R e₃ r (flat_3D_lc: four friction directions), u = (two body torques, leg force)."""
+    name, nq, nu, nw, nc, space = "hopper_3D", 7, 3, 3, 1, 3
+    stride_dims = 2
+    mu_world = 1.5
+    mb, ml, Jb, Jl = 3.0, 0.3, 0.75, 0.075
+
+    def M(self, q):
+        return torch.diag(_t([self.mb + self.ml] * 3 + [self.Jb + self.Jl] * 3 + [self.ml]))
+
+    def C(self, q, v):
+        return _t([0.0, 0.0, (self.mb + self.ml) * self.g, 0.0, 0.0, 0.0, 0.0])
+
+    def kinematics(self, q):                      # model.jl:33-37
+        return q[0:3] - MRP(q[3:6])[:, 2] * q[6]
+
+    def B(self, q):                               # model.jl:54-60
+        R = MRP(q[3:6])
+        z3, z1, o1 = torch.zeros(3, dtype=F64), torch.zeros(1, dtype=F64), torch.ones(1, dtype=F64)
+        return torch.stack([torch.cat([z3, R[:, 0], z1]), torch.cat([z3, R[:, 1], z1]), torch.cat([R[:, 2], z3, o1])])
 
 
 class Particle(ContactModel):
@@ -412,7 +446,7 @@ class CentroidalQuadrupedWall(CentroidalQuadruped):
         return torch.cat([m.T @ (v[3 * i:3 * i + 2] if i < 4 else v[3 * i + 1:3 * i + 3]) for i in range(self.nc)])
 
 
-MODELS = {"hopper_2D": Hopper2D, "particle": Particle, "quadruped": Quadruped, "flamingo": Flamingo, "centroidal_quadruped": CentroidalQuadruped,
+MODELS = {"hopper_2D": Hopper2D, "hopper_3D": Hopper3D, "particle": Particle, "quadruped": Quadruped, "flamingo": Flamingo, "centroidal_quadruped": CentroidalQuadruped,
           "centroidal_quadruped_undamped": CentroidalQuadrupedUndamped, "centroidal_quadruped_box": CentroidalQuadrupedBox,
           "centroidal_quadruped_wall": CentroidalQuadrupedWall}
 
@@ -460,9 +494,11 @@ def reference_problem_from_traj(model: ContactModel, traj, kappa: float) -> Refe
 
 
 def get_stride(model: ContactModel, q_ref: np.ndarray) -> np.ndarray:
-    """`get_stride` (mpc_utils.jl:103-107): forward progress of one gait period, first coordinate only."""
+    """`get_stride` (mpc_utils.jl:103-107): forward progress of one gait period, first coordinate only; hopper_3D moves in the
+    plane and takes x and y (hopper_3D/model.jl:89-93)."""
     stride = np.zeros(model.nq)
-    stride[0] = q_ref[-2][0] - q_ref[0][0]
+    n = model.stride_dims
+    stride[:n] = q_ref[-2][:n] - q_ref[0][:n]
     return stride
 
 

@@ -12,6 +12,8 @@ with host-side `surface` / `gradient` that evaluate exactly what the device eval
   sine1/2_3D_lc                   sin x + sin y, 0.075 sin 2πx                   SINE_SUM_3D
   sine3_3D_lc                     0.075 sin 2πx sin 2πy                          SINE_PRODUCT_3D
   quadratic_bowl_3D_lc            x² + y²                                        BOWL_3D
+
+The planar models stand on the `_2D_` terrains, particle and hopper_3D on the `_3D_` ones (`terrain_valid_for`, csrc/plant_model.h).
 """
 from __future__ import annotations
 

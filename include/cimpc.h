@@ -359,6 +359,9 @@ int cimpc_plant_step(int model, int B, const double* q0, const double* q1, const
                                                p_z,i - 0.2 (1 + tanh(200 (p_x,i - 0.25))) / 2, vertical normal; foot mass 0.5 */
 #define CIMPC_PLANT_CENTROIDAL_WALL 8       /* src/dynamics/centroidal_quadruped_wall/model.jl:87-173, 204-235: nc 8, nb 32; contacts
                                                5-8 = the feet against the plane x = 0.25, force [-gamma; m b] on (x; y, z) */
+/* Both entries; the terrain entry takes it on FLAT and on the 3-D kinds.  Id 9 is unassigned. */
+#define CIMPC_PLANT_HOPPER_3D 10            /* src/dynamics/hopper_3D/model.jl: nq 7 (position, modified Rodrigues parameters, leg
+                                               length), nu 3, nw 3, nc 1, nb 4; the contact is the foot p - R(mrp) e_3 r */
 #define CIMPC_TERRAIN_FLAT 0
 #define CIMPC_TERRAIN_PIECEWISE 1
 #define CIMPC_TERRAIN_SOFTPLUS 2
@@ -376,7 +379,7 @@ typedef struct cimpc_terrain {
     double coef[CIMPC_TERRAIN_MAX_PIECES][4];
 } cimpc_terrain;
 /* cimpc_plant_step on terrain: n_terrain = 1 (every robot on `terrain[0]`) or B (robot i on terrain[i]).  Planar kinds (PIECEWISE,
- * SOFTPLUS, SINE) apply to quadruped, flamingo, hopper_2D and particle_2D; 3-D kinds to particle; centroidal_quadruped, _box and
+ * SOFTPLUS, SINE) apply to quadruped, flamingo, hopper_2D and particle_2D; 3-D kinds to particle and hopper_3D; centroidal_quadruped, _box and
  * _wall take FLAT only (their reference models ignore the environment).  A flat robot runs exactly the code of cimpc_plant_step (bit-identical
  * results).  Any other count, an unknown kind, a kind the model does not take or a non-finite field: CIMPC_ERR_INVALID. */
 int cimpc_plant_step_terrain(int model, int B, int n_terrain, const cimpc_terrain* terrain, const double* q0, const double* q1,

@@ -446,6 +446,8 @@ const PLANT_MODELS = Dict{Symbol,NTuple{6,Int}}(
 # the centroidal quadruped against a step and a wall (plant.py: CENTROIDAL_ENV_MODELS); plant_step reads both tables
 const PLANT_ENV_MODELS = Dict{Symbol,NTuple{6,Int}}(
     :centroidal_quadruped_box => (7, 18, 12, 4, 4, 3), :centroidal_quadruped_wall => (8, 18, 12, 8, 4, 3))
+# hopper_3D (plant.py: SPATIAL_MODELS); id 9 is unassigned
+const PLANT_SPATIAL_MODELS = Dict{Symbol,NTuple{6,Int}}(:hopper_3D => (10, 7, 3, 1, 4, 3))
 """
     plant_step(model, q0, q1, u, μ, h_sim, opts; w = nothing) -> (q2, γ, b, status, iters)
 
@@ -453,9 +455,10 @@ q0, q1: nq x B; u: nu x B; w: nw x B or nothing.  Sizes are checked against the 
 """
 function plant_step(model::Symbol, q0::Matrix{Float64}, q1::Matrix{Float64}, u::Matrix{Float64}, μ, h_sim, opts;
                     w::Union{Nothing,Matrix{Float64}} = nothing)
-    haskey(PLANT_ENV_MODELS, model) || haskey(PLANT_MODELS, model) || error("cimpc_plant_step has no model $model (available: " *
-                                                                            "$(vcat(collect(keys(PLANT_MODELS)), collect(keys(PLANT_ENV_MODELS)))))")
-    id, nq, nu, nc, nf, nw = haskey(PLANT_ENV_MODELS, model) ? PLANT_ENV_MODELS[model] : PLANT_MODELS[model]
+    haskey(PLANT_SPATIAL_MODELS, model) || haskey(PLANT_ENV_MODELS, model) || haskey(PLANT_MODELS, model) || error("cimpc_plant_step has no model $model (available: " *
+        "$(vcat(collect(keys(PLANT_MODELS)), collect(keys(PLANT_ENV_MODELS)), collect(keys(PLANT_SPATIAL_MODELS)))))")
+    id, nq, nu, nc, nf, nw = haskey(PLANT_SPATIAL_MODELS, model) ? PLANT_SPATIAL_MODELS[model] :
+                             haskey(PLANT_ENV_MODELS, model) ? PLANT_ENV_MODELS[model] : PLANT_MODELS[model]
     B = size(q0, 2)
     (size(q0, 1) == nq && size(q1) == (nq, B) && size(u) == (nu, B)) || error("plant_step($model): q0, q1 must be $nq x B and u $nu x B")
     (w === nothing || size(w) == (nw, B)) || error("plant_step($model): w must be $nw x B")
