@@ -16,6 +16,7 @@
 
 #include "../../../include/cimpc.h"
 #include "plant_model.h"
+#include "plant_rollout_plan.h"
 
 namespace cimpc {
 
@@ -31,6 +32,19 @@ static_assert(NZ_HOPPER_3D >= 19, "hopper_3D: nz = 19");
 struct PlantOpts {
     double r_tol, kappa_tol, kc_floor, eps_min, ls_scale, stall_alpha;
     int max_iter, max_ls;
+};
+
+// What a launch steps: steps t0 .. t0 + n - 1 of a rollout of B robots, all in device memory.  q: (T + 2) x B x nq, rows t0 and t0 + 1
+// read, rows t0 + 2 .. t0 + n + 1 written; u: K_u x n_u x nu, w: K_w x n_w x nw or null (rollout_row picks the row of a step; n_* = 1: one
+// schedule for every robot, B: one per robot); friction mu0 (n_mu = 1) or mu[rb] (n_mu = B); per-step outputs gamma: T x B x nc,
+// b: T x B x nb, status and iters: T x B.  One simulator step is T = 1, t0 = 0, n = 1.
+struct PlantRollout {
+    double* q;
+    const double *u, *w, *mu;
+    double *gamma, *b;
+    int *status, *iters;
+    double mu0, h;
+    int t0, n, K_u, n_u, hold_u, K_w, n_w, hold_w, n_mu;
 };
 
 __device__ __forceinline__ void wsync() { __syncthreads(); }         // one or two wavefronts per workgroup
@@ -91,16 +105,15 @@ __device__ __forceinline__ double lanes_sum(double v, double* red) {
 // centroidal_quadruped_wall (NZ = 114, two wavefronts: lane j evaluates Jacobian column j, and the 114 x 115 LU stays in LDS).
 enum { GROUND_FLAT, GROUND_TERRAIN, GROUND_ENV };
 
-// One simulator step of robot blockIdx.x on NT lanes, sized by NZ (A is NZ x NZ + 1): the only statement of the iteration, with
-// reductions over both wavefronts when NT = 128.  Five instantiations: (66, 64, FLAT), (66, 64, TERRAIN), (66, 64, ENV) for the box,
-// (114, 128, ENV) for the wall and (19, 64, TERRAIN) for hopper_3D on terrain, whose per-lane z and r copies and LDS matrix shrink
-// with NZ.  The iteration names the LDS arrays directly: handed to a helper as pointers they cost the
-// TERRAIN instantiation 8-15 %.
+// Steps R.t0 .. R.t0 + R.n - 1 of robot blockIdx.x's rollout on NT lanes, sized by NZ (A is NZ x NZ + 1): the only statement of the
+// iteration, with reductions over both wavefronts when NT = 128; cimpc_plant_step is its n = 1 use.  Five instantiations: (66, 64, FLAT),
+// (66, 64, TERRAIN), (66, 64, ENV) for the box, (114, 128, ENV) for the wall and (19, 64, TERRAIN) for hopper_3D on terrain, whose
+// per-lane z and r copies and LDS matrix shrink with NZ.  The iteration names the LDS arrays directly: handed
+// to a helper as pointers they cost the TERRAIN instantiation 8-15 %.  Between steps the state stays in LDS:
+// q2 is stored to its trajectory row and shifted into theta (q1 -> q0, q2 -> q1), nothing is read back from global memory.
 template <int NZ, int NT, int GROUND>
-__global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts o, int B, const double* q0, const double* q1,
-                                                        const double* u, const double* w, double mu, double h, double* q2,
-                                                        double* gamma, double* bb, int* status, int* iters,
-                                                        const cimpc_terrain* terrain, int n_terrain) {
+__global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts o, int B, PlantRollout R, const cimpc_terrain* terrain,
+                                                        int n_terrain) {
     static_assert(NT == 64 || NT == 128, "one or two wavefronts per robot");
     __shared__ double A[NZ * (NZ + 1)];
     __shared__ double zs[NZ], rs[NZ], ds[NZ], xs[NZ], ths[2 * PLANT_MAX_Q + PLANT_MAX_U + PLANT_NW + 2], red[2];
@@ -129,19 +142,12 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
     };
     constexpr int LD = NZ + 1;
     const int nq = M.nq, nu = M.nu, nz = M.nz(), ny = 2 * M.nc + M.nb(), nxy = nq + ny;
-    // θ = [q0; q1; u1; w1; μ; h], z = (q1, 1, ..., 1)
-    for (int i = lane; i < M.nth(); i += NT) {
-        double v;
-        if (i < nq) v = q0[(size_t)rb * nq + i];
-        else if (i < 2 * nq) v = q1[(size_t)rb * nq + i - nq];
-        else if (i < 2 * nq + nu) v = u[(size_t)rb * nu + i - 2 * nq];
-        else if (i < 2 * nq + nu + M.nw) v = w ? w[(size_t)rb * M.nw + i - 2 * nq - nu] : 0.0;
-        else v = (i == 2 * nq + nu + M.nw) ? mu : h;
-        ths[i] = v;
+    // θ = [q0; q1; u1; w1; μ; h]: q0, q1 from the trajectory rows t0, t0 + 1 (entry i and nq + i by the lane that shifts them after a step)
+    for (int i = lane; i < nq; i += NT) {
+        ths[i] = R.q[((size_t)R.t0 * B + rb) * nq + i];
+        ths[nq + i] = R.q[((size_t)(R.t0 + 1) * B + rb) * nq + i];
     }
-    for (int i = lane; i < nz; i += NT) zs[i] = i < nq ? q1[(size_t)rb * nq + i] : 1.0;
-    wsync();
-
+    if (lane == 0) { ths[2 * nq + nu + M.nw] = R.n_mu == 1 ? R.mu0 : R.mu[rb]; ths[2 * nq + nu + M.nw + 1] = R.h; }
     // residual at the current z with bilinear target kappa -> rs (every lane evaluates; lane 0 stores)
     auto eval_r = [&](double kappa, double* out) {
         double zl[NZ], rl[NZ];
@@ -225,6 +231,15 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
         }
     };
 
+    for (int t = R.t0; t < R.t0 + R.n; ++t) {
+    // u1, w1 of step t, z = (q1, 1, ..., 1)
+    {
+        const double* ut = R.u + ((size_t)rollout_row(t, R.hold_u, R.K_u) * R.n_u + (R.n_u == 1 ? 0 : rb)) * nu;
+        const double* wt = R.w ? R.w + ((size_t)rollout_row(t, R.hold_w, R.K_w) * R.n_w + (R.n_w == 1 ? 0 : rb)) * M.nw : nullptr;
+        for (int i = lane; i < nu + M.nw; i += NT) ths[2 * nq + i] = i < nu ? ut[i] : wt ? wt[i - nu] : 0.0;
+    }
+    for (int i = lane; i < nz; i += NT) zs[i] = i < nq ? ths[nq + i] : 1.0;
+    wsync();
     eval_r(0.0, rs);
     double r_vio, k_vio;
     violations(rs, r_vio, k_vio);
@@ -268,10 +283,19 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
         }
         r_vio = r_c; k_vio = k_c;
     }
-    for (int i = lane; i < nq; i += NT) q2[(size_t)rb * nq + i] = zs[i];
-    for (int i = lane; i < M.nc; i += NT) gamma[(size_t)rb * M.nc + i] = zs[nq + i];
-    for (int i = lane; i < M.nb(); i += NT) bb[(size_t)rb * M.nb() + i] = zs[nq + M.nc + i];
-    if (lane == 0) { status[rb] = (r_vio < o.r_tol && k_vio < o.kappa_tol) ? 1 : 0; iters[rb] = it; }
+    // every lane is past its last read of the step's LDS (the exits above follow a barrier): q2 to row t + 2 and into θ (q1 -> q0, q2 -> q1)
+    const size_t row = (size_t)t * B + rb;
+    for (int i = lane; i < nq; i += NT) {
+        const double v = zs[i];
+        R.q[((size_t)(t + 2) * B + rb) * nq + i] = v;
+        ths[i] = ths[nq + i];
+        ths[nq + i] = v;
+    }
+    for (int i = lane; i < M.nc; i += NT) R.gamma[row * M.nc + i] = zs[nq + i];
+    for (int i = lane; i < M.nb(); i += NT) R.b[row * M.nb() + i] = zs[nq + M.nc + i];
+    if (lane == 0) { R.status[row] = (r_vio < o.r_tol && k_vio < o.kappa_tol) ? 1 : 0; R.iters[row] = it; }
+    wsync();                                                           // the next step's z overwrites what the stores above read
+    }
 }
 constexpr int NZ_WALL = PLANT_MAX_Q + 4 * PLANT_WALL_NC + 2 * PLANT_WALL_NB;      // 114
 
@@ -279,8 +303,9 @@ constexpr int NZ_WALL = PLANT_MAX_Q + 4 * PLANT_WALL_NC + 2 * PLANT_WALL_NB;    
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------
 namespace {
-// Per-device workspace of the plant entry point: buffers and a private stream live across calls (a simulator step is called
+// Per-device workspace of the plant entry points: buffers and a private stream live across calls (a simulator step is called
 // thousands of times in a closed loop; allocating and a device-wide synchronize per call stalled everything else on the GPU).
+// d_in: trajectory (T + 2) x B x nq | u schedule | w schedule | per-robot mu; d_out: gamma | b; d_st: status | iters (T x B each).
 struct PlantWs {
     int device = -1;
     hipStream_t st = nullptr;
@@ -305,14 +330,19 @@ bool plant_grow(T** p, size_t* cap, size_t need) {
 }  // namespace
 
 namespace {
-// Both entry points: validate, pick the model, stage inputs on the device's private stream, launch, read back.  terrain = nullptr
-// (or every terrain flat on a model cimpc_plant_step has) runs the GROUND_FLAT instantiation; the box and the wall (flat only) run
-// their GROUND_ENV instantiations.
-int plant_step_impl(int model, int B, int n_terrain, const cimpc_terrain* terrain, const double* q0, const double* q1,
-                    const double* u, const double* w, double mu, double h, const cimpc_ip_opts* opts, double* q2, double* gamma,
-                    double* b, int* status, int* iters) {
+// Every entry point: validate (no device needed), pick the model, stage inputs on the device's private stream, launch the rollout's
+// chunks back to back (plant_rollout_plan.h; the trajectory buffer carries the state, no host synchronize in between), read back once.
+// A simulator step is the rollout T = 1 with one u / w row per robot, and reads back trajectory row 2 alone (q_row0 = 2).  terrain =
+// nullptr (or every terrain flat on a model cimpc_plant_step has) runs the GROUND_FLAT instantiation; the box and the wall (flat only)
+// run their GROUND_ENV instantiations.
+int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain, const double* q0,
+                       const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w, int K_w, int n_w, int hold_w,
+                       const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, double* q, int q_row0, double* gamma, double* b,
+                       int* status, int* iters) {
     using namespace cimpc;
-    if (B <= 0 || !q0 || !q1 || !u || !opts || !q2 || !gamma || !b || !status || !iters || h <= 0.0) return CIMPC_ERR_INVALID;
+    if (B <= 0 || !q0 || !q1 || !u || !opts || !q || !gamma || !b || !status || !iters || h <= 0.0) return CIMPC_ERR_INVALID;
+    if (T < 1 || steps_per_launch < 0 || K_u < 1 || hold_u < 1 || (n_u != 1 && n_u != B) || !mu || (n_mu != 1 && n_mu != B)) return CIMPC_ERR_INVALID;
+    if (w && (K_w < 1 || hold_w < 1 || (n_w != 1 && n_w != B))) return CIMPC_ERR_INVALID;
     PlantModel M{};
     if (!plant_model_by_id(model, &M) || (model == CIMPC_PLANT_PARTICLE_2D && !terrain)) return CIMPC_ERR_INVALID;
     if (opts->max_iter <= 0 || opts->max_ls < 0 || !(opts->r_tol > 0.0) || !(opts->kappa_tol > 0.0) || !(opts->ls_scale > 0.0 && opts->ls_scale < 1.0))
@@ -335,30 +365,35 @@ int plant_step_impl(int model, int B, int n_terrain, const cimpc_terrain* terrai
     const size_t pnc = (size_t)M.nc, pnb = (size_t)M.nb();
     PlantOpts o{opts->r_tol, opts->kappa_tol, std::isinf(opts->undercut) ? 0.0 : opts->kappa_tol / opts->undercut, opts->eps_min,
                 opts->ls_scale, opts->stall_alpha, opts->max_iter, opts->max_ls};
-    const size_t nq = M.nq, nu = M.nu;
-    const size_t n_in = (size_t)B * (2 * nq + nu + M.nw), n_out = (size_t)B * (nq + pnc + pnb);
+    const size_t nq = M.nq, nu = M.nu, nw = M.nw, row = (size_t)B * nq, TB = (size_t)T * B;
+    const size_t n_q = (size_t)(T + 2) * row, n_us = (size_t)K_u * n_u * nu, n_ws = w ? (size_t)K_w * n_w * nw : 0, n_mus = n_mu == 1 ? 0 : (size_t)B;
     std::lock_guard<std::mutex> lock(g_plant_mu);
     PlantWs& W = g_plant_ws[dev];
     if (!W.st) {
         if (hipStreamCreateWithFlags(&W.st, hipStreamNonBlocking) != hipSuccess) return CIMPC_ERR_HIP;
         W.device = dev;
     }
-    if (!plant_grow(&W.d_in, &W.cap_in, n_in) || !plant_grow(&W.d_out, &W.cap_out, n_out) || !plant_grow(&W.d_st, &W.cap_st, 2 * (size_t)B))
+    if (!plant_grow(&W.d_in, &W.cap_in, n_q + n_us + n_ws + n_mus) || !plant_grow(&W.d_out, &W.cap_out, TB * (pnc + pnb)) ||
+        !plant_grow(&W.d_st, &W.cap_st, 2 * TB))
         return CIMPC_ERR_HIP;
     if (rough && !plant_grow(&W.d_ter, &W.cap_ter, (size_t)n_terrain)) return CIMPC_ERR_HIP;
-    double* dq0 = W.d_in; double* dq1 = dq0 + B * nq; double* du = dq1 + B * nq; double* dw = du + B * nu;
-    double* dq2 = W.d_out; double* dg = dq2 + B * nq; double* db = dg + (size_t)B * pnc;
+    double* dq = W.d_in; double* du = dq + n_q; double* dw = du + n_us; double* dmu = dw + n_ws;
+    double* dg = W.d_out; double* db = dg + TB * pnc;
     int* d_st = W.d_st;
     hipStream_t st = W.st;
-    bool ok = hipMemcpyAsync(dq0, q0, B * nq * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(dq1, q1, B * nq * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(du, u, B * nu * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok && w) ok = hipMemcpyAsync(dw, w, (size_t)B * M.nw * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    bool ok = hipMemcpyAsync(dq, q0, row * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(dq + row, q1, row * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(du, u, n_us * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok && w) ok = hipMemcpyAsync(dw, w, n_ws * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok && n_mus) ok = hipMemcpyAsync(dmu, mu, n_mus * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
     if (ok && rough) ok = hipMemcpyAsync(W.d_ter, terrain, (size_t)n_terrain * sizeof(cimpc_terrain), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok) {
+    PlantRollout R{dq, du, w ? dw : nullptr, n_mus ? dmu : nullptr, dg, db, d_st, d_st + TB, mu[0], h, 0, 0, K_u, n_u, hold_u, w ? K_w : 1,
+                   w ? n_w : 1, w ? hold_w : 1, n_mu};
+    for (int k = 0; ok && k < rollout_chunk_count(T, steps_per_launch); ++k) {
+        const RolloutChunk c = rollout_chunk(T, steps_per_launch, k);
+        R.t0 = c.t0; R.n = c.n;
         auto launch = [&](auto kernel, int nt) {
-            hipLaunchKernelGGL(kernel, dim3(B), dim3(nt), 0, st, M, o, B, dq0, dq1, du, w ? dw : nullptr, mu, h, dq2, dg, db, d_st, d_st + B,
-                               rough ? W.d_ter : nullptr, rough ? n_terrain : 0);
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(nt), 0, st, M, o, B, R, rough ? W.d_ter : nullptr, rough ? n_terrain : 0);
         };
         // hopper_3D (nz = 19): on terrain its own size measured level with the shared one (0.6 % faster, inside the spread), on flat
         // ground 1.8 % slower, so the flat hopper stays on the shared FLAT instantiation
@@ -369,11 +404,11 @@ int plant_step_impl(int model, int B, int n_terrain, const cimpc_terrain* terrai
         else launch(plant_step_kernel<NZM, 64, GROUND_FLAT>, 64);
         ok = hipGetLastError() == hipSuccess;
     }
-    if (ok) ok = hipMemcpyAsync(q2, dq2, B * nq * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                 hipMemcpyAsync(gamma, dg, (size_t)B * pnc * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                 hipMemcpyAsync(b, db, (size_t)B * pnb * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                 hipMemcpyAsync(status, d_st, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                 hipMemcpyAsync(iters, d_st + B, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
+    if (ok) ok = hipMemcpyAsync(q, dq + (size_t)q_row0 * row, (size_t)(T + 2 - q_row0) * row * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                 hipMemcpyAsync(gamma, dg, TB * pnc * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                 hipMemcpyAsync(b, db, TB * pnb * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                 hipMemcpyAsync(status, d_st, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                 hipMemcpyAsync(iters, d_st + TB, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
     return ok ? CIMPC_OK : CIMPC_ERR_HIP;
 }
@@ -382,12 +417,21 @@ int plant_step_impl(int model, int B, int n_terrain, const cimpc_terrain* terrai
 extern "C" int cimpc_plant_step(int model, int B, const double* q0, const double* q1, const double* u, const double* w,
                                 double mu, double h, const cimpc_ip_opts* opts, double* q2, double* gamma, double* b,
                                 int* status, int* iters) {
-    return plant_step_impl(model, B, 0, nullptr, q0, q1, u, w, mu, h, opts, q2, gamma, b, status, iters);
+    return plant_rollout_impl(model, B, 1, 1, 0, nullptr, q0, q1, u, 1, B, 1, w, 1, B, 1, &mu, 1, h, opts, q2, 2, gamma, b, status, iters);
 }
 
 extern "C" int cimpc_plant_step_terrain(int model, int B, int n_terrain, const cimpc_terrain* terrain, const double* q0,
                                         const double* q1, const double* u, const double* w, double mu, double h,
                                         const cimpc_ip_opts* opts, double* q2, double* gamma, double* b, int* status, int* iters) {
     if (!terrain) return CIMPC_ERR_INVALID;
-    return plant_step_impl(model, B, n_terrain, terrain, q0, q1, u, w, mu, h, opts, q2, gamma, b, status, iters);
+    return plant_rollout_impl(model, B, 1, 1, n_terrain, terrain, q0, q1, u, 1, B, 1, w, 1, B, 1, &mu, 1, h, opts, q2, 2, gamma, b, status, iters);
+}
+
+extern "C" int cimpc_plant_rollout(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                   const double* q0, const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w,
+                                   int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                                   double* q, double* gamma, double* b, int* status, int* iters) {
+    if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
+    return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
+                              h, opts, q, 0, gamma, b, status, iters);
 }

@@ -4,7 +4,8 @@ The reference steps its simulator with RoboDojo's `simulate!` (src/simulator/sim
 time-stepping complementarity problem of the model is solved to 1e-8 from `z = initialize_z!(q1)`.  `plant_step` does that
 for B independent robots of one of the models of `csrc/plant_model.h` (the planar chains quadruped and flamingo, hopper_2D, the
 3-D centroidal_quadruped and its box and wall variants, the particles, hopper_3D), on flat ground or on a terrain of terrain.py (`cimpc_plant_step_terrain`),
-`simulate` loops it with a policy and, optionally, a disturbance schedule (src/simulator/disturbances.jl).
+`simulate` loops it with a policy and, optionally, a disturbance schedule (src/simulator/disturbances.jl), `rollout` runs an
+open-loop schedule of controls and disturbances in one call with every intermediate state on the device (`cimpc_plant_rollout`).
 Parity: tests/test_gpu_plant.py against the CPU restatement of the same step.
 """
 from __future__ import annotations
@@ -184,3 +185,67 @@ def simulate(model: str, policy, q1, v1, H_sim: int, h_sim: float, mu: float, op
             policy.observe(q2, g)
         q.append(q2); us.append(u.copy()); gs.append(g); bs.append(b)
     return ok, np.array(q), np.array(us), np.array(gs), np.array(bs)
+
+
+def _schedule(a, B: int, n: int, what: str):
+    """(K, n) shared by every robot or (K, B, n) per robot -> (K, 1 or B, n)."""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim == 2:
+        a = a[:, None, :]
+    if a.ndim != 3 or a.shape[0] < 1 or a.shape[1] not in (1, B) or a.shape[2] != n:
+        raise ValueError(f"{what} must be (K, {n}) or (K, B, {n})")
+    return a
+
+
+def open_loop_controls(model: str, u, B: int, N_sample: int = 1, steps=None):
+    """What `rollout` hands to the device and what it applies: (rows (K, 1 or B, nu) = u[k] / N_sample, the expression of
+    `OpenLoopPolicy`; u_applied (steps, B, nu): row min(t // N_sample, K - 1) at the 0-based step t).  steps defaults to K N_sample."""
+    N_sample = int(N_sample)
+    if N_sample < 1:
+        raise ValueError("N_sample must be at least 1")
+    rows = np.ascontiguousarray(_schedule(u, B, model_dims(model)[2], "u") / N_sample)
+    T = rows.shape[0] * N_sample if steps is None else int(steps)
+    if T < 1:
+        raise ValueError("steps must be at least 1")
+    k = np.minimum(np.arange(T) // N_sample, rows.shape[0] - 1)
+    return rows, np.broadcast_to(rows[k], (T, B, rows.shape[2])).copy()
+
+
+def rollout(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w_hold: int = 1, opts: InteriorPointOptions = SIM_OPTS,
+            terrain=None, steps=None, steps_per_launch: int = 0):
+    """`simulate!(sim, q1, v1)` under an `open_loop_policy(u; N_sample)` for B robots in ONE call (`cimpc_plant_rollout`): the states
+    between the steps stay on the device, and every step is bit for bit the `plant_step` that `simulate` would make.  q1, v1 (B, nq) or
+    (nq,); u (K, nu) nominal controls shared by every robot or (K, B, nu), each held for N_sample steps and applied as u[k] / N_sample
+    (the expression of `OpenLoopPolicy`), the last one from there on; w None or (K_w, nw) / (K_w, B, nw) disturbances applied as they
+    stand, each held for w_hold steps; mu a friction coefficient or B of them; terrain as in `plant_step`; steps: simulator steps
+    (default K N_sample); steps_per_launch: steps per kernel launch (0: the library's default).  Returns (ok, q (steps + 2, B, nq),
+    u_applied (steps, B, nu), gamma, b, status (steps, B), iters) with q[0] = q1 - h v1, q[1] = q1."""
+    if terrain is None and model in TERRAIN_MODELS:
+        terrain = "flat_2D_lc"
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    q1 = np.atleast_2d(np.asarray(q1, dtype=np.float64)); v1 = np.atleast_2d(np.asarray(v1, dtype=np.float64))
+    B = q1.shape[0]
+    if q1.shape != (B, nq) or v1.shape != (B, nq):
+        raise ValueError(f"q1, v1 must be (B, {nq})")
+    if int(w_hold) < 1:
+        raise ValueError("w_hold must be at least 1")
+    ua, u_applied = open_loop_controls(model, u, B, N_sample, steps)
+    T = u_applied.shape[0]
+    wa = None if w is None else np.ascontiguousarray(_schedule(w, B, nw, "w"))
+    mua = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
+    if mua.size not in (1, B):
+        raise ValueError(f"mu: one friction coefficient or one per robot ({B}), got {mua.size}")
+    lib = _lib.load()
+    q0 = np.ascontiguousarray(q1 - h * v1); q1 = np.ascontiguousarray(q1)
+    q = np.zeros((T + 2, B, nq)); g = np.zeros((T, B, nc)); b = np.zeros((T, B, fd * nc))
+    st = np.zeros((T, B), dtype=np.int32); it = np.zeros((T, B), dtype=np.int32)
+    o = _lib.IpOpts(**dataclasses.asdict(opts))
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    ta, nt = (None, 0) if terrain is None else _terrain_array(terrain, B)
+    rc = lib.cimpc_plant_rollout(mid, B, T, int(steps_per_launch), nt, ta, dp(q0), dp(q1), dp(ua), ua.shape[0], ua.shape[1], int(N_sample),
+                                 dp(wa), 1 if wa is None else wa.shape[0], 1 if wa is None else wa.shape[1], int(w_hold), dp(mua), mua.size,
+                                 float(h), C.byref(o), dp(q), dp(g), dp(b), ip(st), ip(it))
+    if rc != 0:
+        raise _lib.CimpcError(f"cimpc_plant_rollout failed ({rc})")
+    return bool(st.all()), q, u_applied, g, b, st, it

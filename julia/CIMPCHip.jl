@@ -470,6 +470,66 @@ function plant_step(model::Symbol, q0::Matrix{Float64}, q1::Matrix{Float64}, u::
     return q2, γ, b, status, iters
 end
 
+# ---- open-loop rollout: T plant steps in one call (simulate!(sim, q1, v1) with an open_loop_policy, simulator.jl, policy.jl:4-34) -----
+const TERRAIN_MAX_PIECES = 8                        # CIMPC_TERRAIN_MAX_PIECES
+struct Terrain                                      # cimpc_terrain (field order = C order); coef is row-major pieces x 4
+    kind::Cint; n_pieces::Cint
+    p::NTuple{4,Cdouble}
+    brk::NTuple{TERRAIN_MAX_PIECES,Cdouble}
+    off::NTuple{TERRAIN_MAX_PIECES,Cdouble}
+    coef::NTuple{4 * TERRAIN_MAX_PIECES,Cdouble}
+end
+# (CIMPC_PLANT_* id, nq, nu, nc, friction directions per contact, nw) of a plant model, from the three tables above
+function _plant_dims(model::Symbol)
+    haskey(PLANT_SPATIAL_MODELS, model) && return PLANT_SPATIAL_MODELS[model]
+    haskey(PLANT_ENV_MODELS, model) && return PLANT_ENV_MODELS[model]
+    haskey(PLANT_MODELS, model) && return PLANT_MODELS[model]
+    error("cimpc_plant_rollout has no model $model (available: " *
+          "$(vcat(collect(keys(PLANT_MODELS)), collect(keys(PLANT_ENV_MODELS)), collect(keys(PLANT_SPATIAL_MODELS)))))")
+end
+"""
+    plant_rollout(model, q1, v1, u, μ, h_sim, opts; N_sample = 1, w = nothing, w_hold = 1, terrain = nothing, steps = K N_sample,
+                  steps_per_launch = 0) -> (ok, q, u_applied, γ, b, status, iters)
+
+`simulate!(sim, q1, v1)` under `open_loop_policy(u; N_sample)` for B robots in ONE call, every intermediate state on the device.
+q1, v1: nq x B; u: nu x K (one schedule for every robot) or nu x B x K, nominal controls applied as u[k] / N_sample (policy.jl:26);
+w: nothing, nw x K_w or nw x B x K_w, applied as it stands, each held for w_hold steps; μ: a number or B of them; terrain: nothing
+(flat ground) or a vector of 1 or B `Terrain`.  Returns q: nq x B x (steps + 2) with q[:, :, 1] = q1 - h v1, γ: nc x B x steps,
+b: nb x B x steps, status, iters: B x steps.  Sizes are checked against the model's table; unknown models are an error.
+"""
+function plant_rollout(model::Symbol, q1::Matrix{Float64}, v1::Matrix{Float64}, u::Array{Float64}, μ, h_sim, opts;
+                       N_sample::Int = 1, w::Union{Nothing,Array{Float64}} = nothing, w_hold::Int = 1,
+                       terrain::Union{Nothing,Vector{Terrain}} = nothing, steps::Int = size(u, ndims(u)) * N_sample, steps_per_launch::Int = 0)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    B = size(q1, 2)
+    (size(q1, 1) == nq && size(v1) == (nq, B)) || error("plant_rollout($model): q1, v1 must be $nq x B")
+    us = ndims(u) == 2 ? reshape(u, nu, 1, :) : u                  # nu x n_u x K, column-major = K x n_u x nu in the library's order
+    (ndims(us) == 3 && size(us, 1) == nu && size(us, 2) in (1, B) && size(us, 3) >= 1) || error("plant_rollout($model): u must be $nu x K or $nu x B x K")
+    ws = w === nothing ? nothing : ndims(w) == 2 ? reshape(w, nw, 1, :) : w
+    (ws === nothing || (ndims(ws) == 3 && size(ws, 1) == nw && size(ws, 2) in (1, B) && size(ws, 3) >= 1)) || error("plant_rollout($model): w must be $nw x K_w or $nw x B x K_w")
+    μs = Float64.(vcat(μ))
+    length(μs) in (1, B) || error("plant_rollout($model): one friction coefficient or one per robot")
+    (terrain === nothing || length(terrain) in (1, B)) || error("plant_rollout($model): one terrain or one per robot")
+    (steps >= 1 && N_sample >= 1 && w_hold >= 1) || error("plant_rollout($model): steps, N_sample, w_hold must be at least 1")
+    ua = us ./ N_sample
+    q0 = q1 .- h_sim .* v1
+    q = zeros(nq, B, steps + 2); γ = zeros(nc, B, steps); b = zeros(nf * nc, B, steps)
+    status = zeros(Cint, B, steps); iters = zeros(Cint, B, steps)
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    K_u, n_u = size(ua, 3), size(ua, 2)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu = length(μs)
+    check(@ccall LIB.cimpc_plant_rollout(id::Cint, B::Cint, steps::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                         q0::Ptr{Cdouble}, q1::Ptr{Cdouble}, ua::Ptr{Cdouble}, K_u::Cint, n_u::Cint, N_sample::Cint,
+                                         wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint, μs::Ptr{Cdouble}, n_mu::Cint,
+                                         h_sim::Cdouble, o::Ref{IpOpts}, q::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble},
+                                         status::Ptr{Cint}, iters::Ptr{Cint})::Cint)
+    rows = min.((0:steps - 1) .÷ N_sample, size(ua, 3) - 1) .+ 1
+    u_applied = repeat(ua[:, :, rows], 1, B ÷ size(ua, 2), 1)
+    return all(status .== 1), q, u_applied, γ, b, status, iters
+end
+
 end # module
 
 # executed in the INCLUDING module (ContactImplicitMPC): `eval(opts.solver)` of newton.jl:86 looks the constructor up there

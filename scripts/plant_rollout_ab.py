@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""`plant.rollout` (T plant steps in one call) against the host loop of `plant.plant_step`, and `plant_step` itself against other
+builds of the library, on one GPU in one process: alternating pairs, a host clock around calls that end in the stream synchronize.
+
+Rollout legs: the open-loop replay of quadruped gait2 (mu 0.5, T = H steps) and of hopper_3D gait_in_place (T = H steps), every robot
+from the gait's own start, B in {4, 64, 512}; per pair the loop's and the rollout's wall time per step, whose outputs are compared
+bit for bit once per leg.  Step legs: one `plant_step` call at B = 512 hopper_3D robots at gait_forward knots and at B = 256 quadrupeds
+at gait2 knots, this build against every `--step-lib NAME=PATH` (e.g. a build of the parent commit, and a copy of it for the spread
+of a build against itself), alternating per pair; `--parent-step-us LEG=US` records a figure measured elsewhere next to them.
+usage: python scripts/plant_rollout_ab.py [--pairs 5] [--calls 100] [--step-lib NAME=PATH ...] [--parent-step-us LEG=US ...]
+                                          [--out profiles/plant_rollout_ab.json]"""
+import argparse
+import ctypes as C
+import dataclasses
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from contactimplicitmpc.jl_amd import _lib, gait_io, plant  # noqa: E402
+
+GAITS = os.path.join(ROOT, "tests", "golden", "gaits")
+BATCHES = (4, 64, 512)
+
+
+def summary(us):
+    return {"median_us": round(statistics.median(us), 2), "min_us": round(min(us), 2), "max_us": round(max(us), 2), "pairs_us": [round(v, 2) for v in us]}
+
+
+def rollout_leg(name, model, q0, q1, u, h, mu, B, pairs):
+    """u (T, nu) shared by B identical robots: per pair, the loop of T `plant_step` calls and ONE `rollout`, us per step each"""
+    T = u.shape[0]
+    q1b, v1b = np.tile(q1, (B, 1)), np.tile((q1 - q0) / h, (B, 1))
+    ub = np.ascontiguousarray(np.broadcast_to(u[:, None, :], (T, B, u.shape[1])))
+
+    def loop():
+        q = [q1b - h * v1b, q1b]
+        ok = True
+        for t in range(T):
+            q2, g, b, st, it = plant.plant_step(model, q[t], q[t + 1], ub[t], mu, h)
+            ok = ok and bool(st.all())
+            q.append(q2)
+        return ok, np.array(q)
+
+    roll = lambda: plant.rollout(model, q1b, v1b, u, h, mu)
+    (ok_l, q_l), (ok_r, q_r, *_) = loop(), roll()                    # warm-up, and the outputs side by side
+    t_loop, t_roll = [], []
+    for _ in range(pairs):
+        t0 = time.perf_counter(); loop(); t1 = time.perf_counter(); roll(); t2 = time.perf_counter()
+        t_loop.append((t1 - t0) / T * 1e6); t_roll.append((t2 - t1) / T * 1e6)
+    out = {"leg": name, "model": model, "B": B, "T": T, "all_steps_converged": bool(ok_l and ok_r), "identical_q": bool(np.array_equal(q_l, q_r)),
+           "loop_per_step": summary(t_loop), "rollout_per_step": summary(t_roll)}
+    out["rollout_over_loop"] = round(out["rollout_per_step"]["median_us"] / out["loop_per_step"]["median_us"], 4)
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def step_leg(name, model, q0, q1, u, h, mu, libs, pairs, calls):
+    """one `cimpc_plant_step` call on every library in turn, `calls` calls per turn, `pairs` turns: us per call"""
+    mid, nq, nu, nc, fd, nw = plant.model_dims(model)
+    B = q0.shape[0]
+    q0, q1, u = (np.ascontiguousarray(a, dtype=np.float64) for a in (q0, q1, u))
+    q2 = np.zeros((B, nq)); g = np.zeros((B, nc)); b = np.zeros((B, fd * nc)); st = np.zeros(B, dtype=np.int32); it = np.zeros(B, dtype=np.int32)
+    o = _lib.IpOpts(**dataclasses.asdict(plant.SIM_OPTS))
+    dp = lambda a: a.ctypes.data_as(_lib._dp)
+    ip = lambda a: a.ctypes.data_as(_lib._ip)
+
+    def call(lib):
+        rc = lib.cimpc_plant_step(mid, B, dp(q0), dp(q1), dp(u), None, float(mu), float(h), C.byref(o), dp(q2), dp(g), dp(b), ip(st), ip(it))
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_step failed ({rc})")
+
+    results, outputs = {k: [] for k in libs}, {}
+    for k, lib in libs.items():                                     # warm-up, and the outputs side by side
+        for _ in range(3):
+            call(lib)
+        outputs[k] = (q2.copy(), g.copy(), b.copy(), st.copy(), it.copy())
+    for _ in range(pairs):
+        for k, lib in libs.items():
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                call(lib)
+            results[k].append((time.perf_counter() - t0) / calls * 1e6)
+    first = outputs["this"]
+    out = {"leg": name, "model": model, "B": B, "calls_per_turn": calls, "ip_iterations_per_robot": round(float(first[4].mean()), 2),
+           "all_converged": bool(first[3].all()), "per_call": {k: summary(v) for k, v in results.items()},
+           "identical_outputs": {k: all(np.array_equal(x, y) for x, y in zip(first, v)) for k, v in outputs.items() if k != "this"}}
+    print(json.dumps(out), flush=True)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=100)
+    ap.add_argument("--step-lib", action="append", default=[], metavar="NAME=PATH")
+    ap.add_argument("--parent-step-us", action="append", default=[], metavar="LEG=US")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plant_rollout_ab.json"))
+    a = ap.parse_args()
+
+    import torch                                                    # the device comes up through torch first, as in the tests
+    assert torch.cuda.is_available(), "needs a GPU"
+    libs = {"this": _lib.load()}
+    for spec in a.step_lib:
+        name, path = spec.split("=", 1)
+        lib = C.CDLL(os.path.abspath(path))
+        lib.cimpc_plant_step.restype, lib.cimpc_plant_step.argtypes = _lib.SIGNATURES["cimpc_plant_step"]
+        libs[name] = lib
+
+    quad = gait_io.load_gait(os.path.join(GAITS, "quadruped_gait2.jld2"))
+    hop = gait_io.load_joint_traj(os.path.join(GAITS, "hopper_3D_gait_in_place.jld2"))
+    fwd = gait_io.load_joint_traj(os.path.join(GAITS, "hopper_3D_gait_forward.jld2"))
+    res = {"device": torch.cuda.get_device_name(0), "pairs": a.pairs, "rollout": [], "plant_step": [],
+           "parent_step_us_from_the_command_line": dict(s.split("=", 1) for s in a.parent_step_us)}
+    k = np.arange(512) * fwd.H // 512
+    res["plant_step"].append(step_leg("hopper512", "hopper_3D", fwd.q[k], fwd.q[k + 1], fwd.u[k], 0.01, 1.5, libs, a.pairs, a.calls))
+    k = np.arange(256) * quad.H // 256
+    res["plant_step"].append(step_leg("quadruped256", "quadruped", quad.q[k], quad.q[k + 1], quad.u[k], quad.h, 0.5, libs, a.pairs, max(10, a.calls // 5)))
+    for B in BATCHES:
+        res["rollout"].append(rollout_leg("hopper_3D gait_in_place replay", "hopper_3D", hop.q[0], hop.q[1], np.asarray(hop.u), hop.h, 1.5, B, a.pairs))
+        res["rollout"].append(rollout_leg("quadruped gait2 replay", "quadruped", quad.q[0], quad.q[1], np.asarray(quad.u), quad.h, 0.5, B, a.pairs))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()
