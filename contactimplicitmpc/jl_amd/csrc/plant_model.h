@@ -1,12 +1,16 @@
-// Plant-side residual of the reference's planar-chain models (quadruped, flamingo) for the batched simulator step
-// (SURVEY.md section 8f-4).  Host- and device-compilable.
+// Plant-side residuals of the reference's models for the batched simulator step: the planar chains
+// (quadruped, flamingo) and hopper_2D, centroidal_quadruped with its box and wall variants, particle, particle_2D and hopper_3D.
+// Host- and device-compilable.
 //
 //   residual            src/simulation/simulation.jl:133-158     (LinearizedCone; plant_residual: flat ground, surface rotation =
 //                                                                 identity; plant_residual_terrain: any cimpc_terrain)
 //   dynamics            src/dynamics/model.jl:11-36              (variational midpoint integrator)
 //   quadruped           src/dynamics/quadruped/model.jl:75-590   flamingo  src/dynamics/flamingo/model.jl:62-503
 //
-// A model is a table: bodies and contact points are chains of (signed length, angle index) segments from the hip at
+// Each model's residual is one function: the ground is a template parameter (the chains, the particle) or a nullable terrain
+// (hopper_3D), and the seven rows of a contact are written by plant_contact_rows for all of them.
+//
+// A planar-chain model is a table: bodies and contact points are chains of (signed length, angle index) segments from the hip at
 // (x, z) - a segment adds r (sin θ, -cos θ).  For such a chain with absolute angles the Lagrangian derivatives the
 // integrator needs are explicit sums over the bodies,
 //   D2L = dL/dq' ,   D1L = dL/dq - (d/dq dL/dq') q'      (dynamics/model.jl:11-15 with C of quadruped/model.jl:479-484),
@@ -85,6 +89,25 @@ struct PlantModel {
     PLANT_HD int nz() const { return nq + 4 * nc + 2 * nb(); }
     PLANT_HD int nth() const { return 2 * nq + nu + nw + 2; }
 };
+
+// The rows of contact c in r(z), z = [q2; γ; b; ψ; s1; η; s2] with FD friction directions per contact (2 planar: m = [1 -1]; 4 spatial:
+// m = [1 0 -1 0; 0 1 0 -1]), given the contact's gap ϕ and tangential velocity vt (FD / 2 entries):
+//   s1 - ϕ,   η - mᵀ v_T - Eᵀψ,   s2 - (μ γ - Σ b),   γ s1 - κ,   b ∘ η - κ,   ψ s2 - κ       (simulation.jl:141-157)
+template <int FD, class T>
+PLANT_HD void plant_contact_rows(int nq, int nc, int c, const T* z, T phi, const T* vt, double mu, double kappa, T* r) {
+    const int nb = FD * nc;
+    const T* gam = z + nq; const T* b = gam + nc + FD * c; const T* psi = gam + nc + nb; const T* s1 = psi + nc;
+    const T* eta = s1 + nc + FD * c; const T* s2 = s1 + nc + nb;
+    r[nq + c] = s1[c] - phi;
+    T* re = r + nq + nc + FD * c;
+    for (int k = 0; k < FD / 2; ++k) { re[k] = eta[k] - vt[k] - psi[c]; re[FD / 2 + k] = eta[FD / 2 + k] + vt[k] - psi[c]; }
+    T sb = b[0];
+    for (int k = 1; k < FD; ++k) sb = sb + b[k];
+    r[nq + nc + nb + c] = s2[c] - (mu * gam[c] - sb);
+    r[nq + 2 * nc + nb + c] = gam[c] * s1[c] - kappa;
+    for (int k = 0; k < FD; ++k) r[nq + 3 * nc + nb + FD * c + k] = b[k] * eta[k] - kappa;
+    r[nq + 3 * nc + 2 * nb + c] = psi[c] * s2[c] - kappa;
+}
 
 // D1L, D2L at (q, v), accumulated into d1, d2 (nq entries each, zeroed here)
 template <class T>
@@ -176,30 +199,25 @@ PLANT_HD void plant_centroidal_dynamics(const PlantModel& M, const T* q2, const 
     plant_centroidal_actuation(qm2, u1, dyn);
     for (int i = 0; i < 3; ++i) dyn[i] = dyn[i] + w1[i];
 }
+
+// centroidal_quadruped: the four feet on the floor, phi_i = p_z,i.  It equals plant_residual_centroidal_env on this model bit for bit
+// (tests/test_centroidal_wall_box.py) and stays a function of its own with compile-time loops: through the env function the FLAT
+// kernel measured 2.4 % slower, and with a compile-time contact count there the TERRAIN kernel's scratch grew.
 template <class T>
 PLANT_HD void plant_residual_centroidal(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
-    constexpr int nq = 18, nc = 4, nb = 16;
+    constexpr int nq = 18, nc = 4;
     const double* q1 = th + nq; const double mu = th[2 * nq + 12 + 3], h = th[2 * nq + 12 + 4];
-    const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc; const T* psi = b + nb; const T* s1 = psi + nc;
-    const T* eta = s1 + nc; const T* s2 = eta + nb;
+    const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc;
     T dyn[nq];
     plant_centroidal_dynamics(M, q2, th, dyn);
     for (int f = 0; f < nc; ++f) {
-        const T* bf = b + 4 * f; const T* ef = eta + 4 * f;
+        const T* bf = b + 4 * f;
         // J^T lambda: the foot's own coordinates, lambda = [m b; gamma]
         dyn[6 + 3 * f] = dyn[6 + 3 * f] + (bf[0] - bf[2]);
         dyn[7 + 3 * f] = dyn[7 + 3 * f] + (bf[1] - bf[3]);
         dyn[8 + 3 * f] = dyn[8 + 3 * f] + gam[f];
-        const T vx = (q2[6 + 3 * f] - q1[6 + 3 * f]) / h, vy = (q2[7 + 3 * f] - q1[7 + 3 * f]) / h;
-        r[nq + f] = s1[f] - q2[8 + 3 * f];                           // s1 - phi(q2)
-        r[nq + nc + 4 * f + 0] = ef[0] - vx - psi[f];                // eta - m^T v_T - E^T psi
-        r[nq + nc + 4 * f + 1] = ef[1] - vy - psi[f];
-        r[nq + nc + 4 * f + 2] = ef[2] + vx - psi[f];
-        r[nq + nc + 4 * f + 3] = ef[3] + vy - psi[f];
-        r[nq + nc + nb + f] = s2[f] - (mu * gam[f] - (bf[0] + bf[1] + bf[2] + bf[3]));
-        r[nq + 2 * nc + nb + f] = gam[f] * s1[f] - kappa;
-        for (int k = 0; k < 4; ++k) r[nq + 3 * nc + nb + 4 * f + k] = bf[k] * ef[k] - kappa;
-        r[nq + 3 * nc + 2 * nb + f] = psi[f] * s2[f] - kappa;
+        const T vt[2] = {(q2[6 + 3 * f] - q1[6 + 3 * f]) / h, (q2[7 + 3 * f] - q1[7 + 3 * f]) / h};
+        plant_contact_rows<4>(nq, nc, f, z, q2[8 + 3 * f], vt, mu, kappa, r);
     }
     for (int i = 0; i < nq; ++i) r[i] = dyn[i];
 }
@@ -220,132 +238,31 @@ PLANT_HD T plant_box_elevation(T x) {
 template <class T>
 PLANT_HD void plant_residual_centroidal_env(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
     constexpr int nq = 18;
-    const int nc = M.nc, nb = 4 * nc;
+    const int nc = M.nc;
     const double* q1 = th + nq; const double mu = th[2 * nq + 12 + 3], h = th[2 * nq + 12 + 4];
-    const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc; const T* psi = b + nb; const T* s1 = psi + nc;
-    const T* eta = s1 + nc; const T* s2 = eta + nb;
+    const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc;
     T dyn[nq];
     plant_centroidal_dynamics(M, q2, th, dyn);
     for (int c = 0; c < nc; ++c) {
         const int f = c & 3;                                          // the foot of contact c
-        const T* bc = b + 4 * c; const T* ec = eta + 4 * c;
+        const T* bc = b + 4 * c;
         const T t1 = bc[0] - bc[2], t2 = bc[1] - bc[3];                // m b
         const T* p2 = q2 + 6 + 3 * f; const double* p1 = q1 + 6 + 3 * f;
-        T phi, v1, v2;
-        if (c < 4) {                                                   // floor: force (m b; gamma), velocity (v_x, v_y)
+        T phi, vt[2];
+        if (c < 4) {                                                   // floor: force (m b; gamma) on the foot's own coordinates, velocity (v_x, v_y)
             dyn[6 + 3 * f] = dyn[6 + 3 * f] + t1;
             dyn[7 + 3 * f] = dyn[7 + 3 * f] + t2;
             dyn[8 + 3 * f] = dyn[8 + 3 * f] + gam[c];
             phi = M.kind == PLANT_KIND_CENTROIDAL_BOX ? p2[2] - plant_box_elevation(p2[0]) : p2[2];
-            v1 = (p2[0] - p1[0]) / h; v2 = (p2[1] - p1[1]) / h;
+            vt[0] = (p2[0] - p1[0]) / h; vt[1] = (p2[1] - p1[1]) / h;
         } else {                                                       // wall: force (-gamma; m b), velocity (v_y, v_z)
             dyn[6 + 3 * f] = dyn[6 + 3 * f] - gam[c];
             dyn[7 + 3 * f] = dyn[7 + 3 * f] + t1;
             dyn[8 + 3 * f] = dyn[8 + 3 * f] + t2;
             phi = 0.25 - p2[0];
-            v1 = (p2[1] - p1[1]) / h; v2 = (p2[2] - p1[2]) / h;
+            vt[0] = (p2[1] - p1[1]) / h; vt[1] = (p2[2] - p1[2]) / h;
         }
-        r[nq + c] = s1[c] - phi;
-        r[nq + nc + 4 * c + 0] = ec[0] - v1 - psi[c];
-        r[nq + nc + 4 * c + 1] = ec[1] - v2 - psi[c];
-        r[nq + nc + 4 * c + 2] = ec[2] + v1 - psi[c];
-        r[nq + nc + 4 * c + 3] = ec[3] + v2 - psi[c];
-        r[nq + nc + nb + c] = s2[c] - (mu * gam[c] - (bc[0] + bc[1] + bc[2] + bc[3]));
-        r[nq + 2 * nc + nb + c] = gam[c] * s1[c] - kappa;
-        for (int k = 0; k < 4; ++k) r[nq + 3 * nc + nb + 4 * c + k] = bc[k] * ec[k] - kappa;
-        r[nq + 3 * nc + 2 * nb + c] = psi[c] * s2[c] - kappa;
-    }
-    for (int i = 0; i < nq; ++i) r[i] = dyn[i];
-}
-
-// ---- particle (src/dynamics/particle/model.jl): a point mass that is its own contact point; M = m I, C = (0, 0, m g),
-// B = A = J = I, four friction directions (flat_3D_lc).  mass[0] = m.
-template <class T>
-PLANT_HD void plant_residual_particle(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
-    const double* q0 = th; const double* q1 = th + 3; const double* u1 = th + 6; const double* w1 = th + 9;
-    const double mu = th[12], h = th[13], m = M.mass[0];
-    const T* q2 = z; const T* gam = z + 3; const T* b = z + 4; const T* psi = z + 8; const T* s1 = z + 9; const T* eta = z + 10; const T* s2 = z + 14;
-    T vm2[3];
-    for (int i = 0; i < 3; ++i) vm2[i] = (q2[i] - q1[i]) / h;
-    const T lam[3] = {b[0] - b[2], b[1] - b[3], gam[0]};
-    for (int i = 0; i < 3; ++i) {
-        const double grav = i == 2 ? -m * M.g : 0.0;
-        r[i] = pconst<T>(0.5 * h * grav + m * ((q1[i] - q0[i]) / h) + 0.5 * h * grav + u1[i] + w1[i]) - m * vm2[i] + lam[i];
-    }
-    r[3] = s1[0] - q2[2];
-    r[4] = eta[0] - vm2[0] - psi[0]; r[5] = eta[1] - vm2[1] - psi[0];
-    r[6] = eta[2] + vm2[0] - psi[0]; r[7] = eta[3] + vm2[1] - psi[0];
-    r[8] = s2[0] - (mu * gam[0] - (b[0] + b[1] + b[2] + b[3]));
-    r[9] = gam[0] * s1[0] - kappa;
-    for (int k = 0; k < 4; ++k) r[10 + k] = b[k] * eta[k] - kappa;
-    r[14] = psi[0] * s2[0] - kappa;
-}
-
-template <class T>
-PLANT_HD void plant_residual_hopper_3d(const PlantModel& M, const cimpc_terrain* E, const T* z, const double* th, double kappa, T* r);      // below the terrain
-
-// r(z, θ, κ): z = [q2; γ; b; ψ; s1; η; s2], θ = [q0; q1; u1; w1; μ; h] (θ real: only dr/dz is needed)
-template <class T>
-PLANT_HD void plant_residual(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
-    if (M.kind == PLANT_KIND_CENTROIDAL) { plant_residual_centroidal<T>(M, z, th, kappa, r); return; }
-    if (M.kind == PLANT_KIND_PARTICLE) { plant_residual_particle<T>(M, z, th, kappa, r); return; }
-    if (M.kind == PLANT_KIND_HOPPER_3D) { plant_residual_hopper_3d<T>(M, nullptr, z, th, kappa, r); return; }
-    const int nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb();
-    const double* q0 = th; const double* q1 = th + nq; const double* u1 = th + 2 * nq; const double* w1 = u1 + nu;
-    const double mu = w1[M.nw], h = w1[M.nw + 1];
-    const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc; const T* psi = b + nb; const T* s1 = psi + nc;
-    const T* eta = s1 + nc; const T* s2 = eta + nb;
-    T qm1[PLANT_MAX_Q], vm1[PLANT_MAX_Q], qm2[PLANT_MAX_Q], vm2[PLANT_MAX_Q];
-    for (int i = 0; i < nq; ++i) {
-        qm1[i] = pconst<T>(0.5 * (q0[i] + q1[i])); vm1[i] = pconst<T>((q1[i] - q0[i]) / h);
-        qm2[i] = (q2[i] + q1[i]) * 0.5; vm2[i] = (q2[i] - q1[i]) / h;
-    }
-    T a1[PLANT_MAX_Q], b1[PLANT_MAX_Q], a2[PLANT_MAX_Q], b2[PLANT_MAX_Q];
-    plant_lagrangian_derivatives(M, qm1, vm1, a1, b1);
-    plant_lagrangian_derivatives(M, qm2, vm2, a2, b2);
-    T dyn[PLANT_MAX_Q];
-    for (int i = 0; i < nq; ++i)
-        dyn[i] = (0.5 * h) * a1[i] + b1[i] + (0.5 * h) * a2[i] - b2[i] - (h * M.joint_friction[i]) * vm2[i];
-    if (M.kind == PLANT_KIND_HOPPER_2D) {
-        // B(qm2)^T u, hopper_2D/model.jl:68-71: body torque on t; leg force along the leg axis (-sin t, cos t) and on r
-        const T st = psin(qm2[2]), ct = pcos(qm2[2]);
-        dyn[2] = dyn[2] + u1[0];
-        dyn[0] = dyn[0] - u1[1] * st; dyn[1] = dyn[1] + u1[1] * ct; dyn[3] = dyn[3] + u1[1];
-    } else {
-        for (int i = 0; i < nu; ++i) { dyn[M.tq_a[i]] = dyn[M.tq_a[i]] - u1[i]; dyn[M.tq_b[i]] = dyn[M.tq_b[i]] + u1[i]; }
-    }
-    for (int i = 0; i < M.nw; ++i) dyn[i] = dyn[i] + w1[i];
-    // contacts: position, Jacobian rows (x and z) of every foot at q2
-    T s[PLANT_MAX_Q], c[PLANT_MAX_Q];
-    for (int i = 0; i < nq; ++i) { s[i] = psin(q2[i]); c[i] = pcos(q2[i]); }
-    for (int f = 0; f < nc; ++f) {
-        const PlantChain& ch = M.foot[f];
-        T pz = q2[1];
-        T lx = b[2 * f] - b[2 * f + 1], lz = gam[f];                 // contact force [m b; γ]
-        T vx = (q2[0] - q1[0]) / h;                                  // tangential foot velocity J_x (q2 - q1) / h
-        dyn[0] = dyn[0] + lx; dyn[1] = dyn[1] + lz;                  // J^T λ: base columns
-        if (M.kind == PLANT_KIND_HOPPER_2D) {
-            // foot = (x + r sin t, z - r cos t), J = [1 0 r cos t sin t; 0 1 r sin t -cos t] at q2 (hopper_2D/model.jl:35-66)
-            const T rl = q2[3];
-            pz = pz - rl * c[2];
-            dyn[2] = dyn[2] + rl * (c[2] * lx + s[2] * lz);
-            dyn[3] = dyn[3] + (s[2] * lx - c[2] * lz);
-            vx = vx + rl * (c[2] * ((q2[2] - q1[2]) / h)) + s[2] * ((q2[3] - q1[3]) / h);
-        }
-        for (int e = 0; e < (M.kind == PLANT_KIND_HOPPER_2D ? 0 : ch.n); ++e) {
-            const int k = ch.k[e]; const double rr = ch.r[e];
-            pz = pz - rr * c[k];
-            dyn[k] = dyn[k] + rr * (c[k] * lx + s[k] * lz);
-            vx = vx + rr * (c[k] * ((q2[k] - q1[k]) / h));
-        }
-        r[nq + f] = s1[f] - pz;                                      // s1 - ϕ(q2)
-        r[nq + nc + 2 * f] = eta[2 * f] - vx - psi[f];               // η - v_T stack - Eᵀψ
-        r[nq + nc + 2 * f + 1] = eta[2 * f + 1] + vx - psi[f];
-        r[nq + nc + nb + f] = s2[f] - (mu * gam[f] - (b[2 * f] + b[2 * f + 1]));
-        r[nq + 2 * nc + nb + f] = gam[f] * s1[f] - kappa;
-        r[nq + 3 * nc + nb + 2 * f] = b[2 * f] * eta[2 * f] - kappa;
-        r[nq + 3 * nc + nb + 2 * f + 1] = b[2 * f + 1] * eta[2 * f + 1] - kappa;
-        r[nq + 3 * nc + 2 * nb + f] = psi[f] * s2[f] - kappa;
+        plant_contact_rows<4>(nq, nc, c, z, phi, vt, mu, kappa, r);
     }
     for (int i = 0; i < nq; ++i) r[i] = dyn[i];
 }
@@ -423,13 +340,54 @@ PLANT_HD void terrain_frame_2d(const cimpc_terrain& E, T px, T& surf, T& c, T& s
     s = -(gx * c);
 }
 
+// 3-D contact frame: R = rot(n_s, e_z) = I + [v]x + [v]x^2 / (1 + c), v = n_s x e_z = (n_y, -n_x, 0), c = n_z (environment.jl:58-77),
+// written out, with the surface normal n_s = (-g_x, -g_y, 1) / |.| at (x, y).
+template <class T>
+PLANT_HD void terrain_frame_3d(const cimpc_terrain& E, T x, T y, T& surf, T R[3][3]) {
+    T gx, gy;
+    terrain_eval(E, x, y, surf, gx, gy);
+    const T inv = 1.0 / psqrt(1.0 + gx * gx + gy * gy);
+    const T nx = -(gx * inv), ny = -(gy * inv), nz = inv;
+    const T vx = ny, vy = -nx, k = 1.0 / (1.0 + nz);
+    R[0][0] = 1.0 - k * (vy * vy); R[0][1] = k * (vx * vy);       R[0][2] = vy;
+    R[1][0] = k * (vx * vy);       R[1][1] = 1.0 - k * (vx * vx); R[1][2] = -vx;
+    R[2][0] = -vy;                 R[2][1] = vx;                  R[2][2] = 1.0 - k * (vx * vx + vy * vy);
+}
+// ---- particle (src/dynamics/particle/model.jl): a point mass that is its own contact point; M = m I, C = (0, 0, m g),
+// B = A = J = I, four friction directions.  mass[0] = m.  ROUGH = false is flat_3D_lc (E unused); ROUGH = true is a 3-D surface
+// (particle/model.jl:58-109): force R^T [m b; γ], tangential velocity (R v)[0:2], ϕ = z - surf(x, y).  The ground is a compile-time
+// choice, as for the chains: behind a run-time branch the device compiler contracts these rows differently.
+template <bool ROUGH, class T>
+PLANT_HD void plant_residual_particle(const PlantModel& M, const cimpc_terrain* E, const T* z, const double* th, double kappa, T* r) {
+    const double* q0 = th; const double* q1 = th + 3; const double* u1 = th + 6; const double* w1 = th + 9;
+    const double mu = th[12], h = th[13], m = M.mass[0];
+    const T* q2 = z; const T* gam = z + 3; const T* b = z + 4;
+    T surf{}, R[3][3];
+    if constexpr (ROUGH) terrain_frame_3d(*E, q2[0], q2[1], surf, R);
+    const T fl[3] = {b[0] - b[2], b[1] - b[3], gam[0]};
+    T vm2[3];
+    for (int i = 0; i < 3; ++i) vm2[i] = (q2[i] - q1[i]) / h;
+    for (int i = 0; i < 3; ++i) {
+        const double grav = i == 2 ? -m * M.g : 0.0;
+        T lam = fl[i];
+        if constexpr (ROUGH) lam = R[0][i] * fl[0] + R[1][i] * fl[1] + R[2][i] * fl[2];
+        r[i] = pconst<T>(0.5 * h * grav + m * ((q1[i] - q0[i]) / h) + 0.5 * h * grav + u1[i] + w1[i]) - m * vm2[i] + lam;
+    }
+    T vt[2] = {vm2[0], vm2[1]}, phi = q2[2];
+    if constexpr (ROUGH) {
+        for (int k = 0; k < 2; ++k) vt[k] = R[k][0] * vm2[0] + R[k][1] * vm2[1] + R[k][2] * vm2[2];
+        phi = q2[2] - surf;
+    }
+    plant_contact_rows<4>(3, 1, 0, z, phi, vt, mu, kappa, r);
+}
+
 // particle_2D (src/dynamics/particle_2D/model.jl): q = (x, z), M = m I, C = (0, m g), B = A = J = I, one contact (the particle)
 // with two friction directions.  mass[0] = m.  Also its flat case: the model has no cimpc_plant_step path.
 template <class T>
 PLANT_HD void plant_residual_particle_2d(const PlantModel& M, const cimpc_terrain& E, const T* z, const double* th, double kappa, T* r) {
     const double* q0 = th; const double* q1 = th + 2; const double* u1 = th + 4; const double* w1 = th + 6;
     const double mu = th[8], h = th[9], m = M.mass[0];
-    const T* q2 = z; const T* gam = z + 2; const T* b = z + 3; const T* psi = z + 5; const T* s1 = z + 6; const T* eta = z + 7; const T* s2 = z + 9;
+    const T* q2 = z; const T* gam = z + 2; const T* b = z + 3;
     T surf, c, s;
     terrain_frame_2d(E, q2[0], surf, c, s);
     const T lt = b[0] - b[1];
@@ -441,47 +399,7 @@ PLANT_HD void plant_residual_particle_2d(const PlantModel& M, const cimpc_terrai
         r[i] = pconst<T>(0.5 * h * grav + m * ((q1[i] - q0[i]) / h) + 0.5 * h * grav + u1[i] + w1[i]) - m * vm2[i] + lam[i];
     }
     const T vt = c * vm2[0] - s * vm2[1];
-    r[2] = s1[0] - (q2[1] - surf);
-    r[3] = eta[0] - vt - psi[0]; r[4] = eta[1] + vt - psi[0];
-    r[5] = s2[0] - (mu * gam[0] - (b[0] + b[1]));
-    r[6] = gam[0] * s1[0] - kappa;
-    for (int k = 0; k < 2; ++k) r[7 + k] = b[k] * eta[k] - kappa;
-    r[9] = psi[0] * s2[0] - kappa;
-}
-
-// particle on a 3-D surface (particle/model.jl:58-109): R = rot(n_s, e_z) = I + [v]x + [v]x^2 / (1 + c), v = n_s x e_z = (n_y, -n_x, 0),
-// c = n_z (environment.jl:58-77), written out; force R^T [m b; γ], tangential velocity (R v)[1:2].
-template <class T>
-PLANT_HD void plant_residual_particle_terrain(const PlantModel& M, const cimpc_terrain& E, const T* z, const double* th, double kappa, T* r) {
-    const double* q0 = th; const double* q1 = th + 3; const double* u1 = th + 6; const double* w1 = th + 9;
-    const double mu = th[12], h = th[13], m = M.mass[0];
-    const T* q2 = z; const T* gam = z + 3; const T* b = z + 4; const T* psi = z + 8; const T* s1 = z + 9; const T* eta = z + 10; const T* s2 = z + 14;
-    T surf, gx, gy;
-    terrain_eval(E, q2[0], q2[1], surf, gx, gy);
-    const T inv = 1.0 / psqrt(1.0 + gx * gx + gy * gy);
-    const T nx = -(gx * inv), ny = -(gy * inv), nz = inv;
-    const T vx = ny, vy = -nx, k = 1.0 / (1.0 + nz);
-    T R[3][3];
-    R[0][0] = 1.0 - k * (vy * vy); R[0][1] = k * (vx * vy);       R[0][2] = vy;
-    R[1][0] = k * (vx * vy);       R[1][1] = 1.0 - k * (vx * vx); R[1][2] = -vx;
-    R[2][0] = -vy;                 R[2][1] = vx;                  R[2][2] = 1.0 - k * (vx * vx + vy * vy);
-    const T fl[3] = {b[0] - b[2], b[1] - b[3], gam[0]};
-    T vm2[3];
-    for (int i = 0; i < 3; ++i) vm2[i] = (q2[i] - q1[i]) / h;
-    for (int i = 0; i < 3; ++i) {
-        const double grav = i == 2 ? -m * M.g : 0.0;
-        const T lam = R[0][i] * fl[0] + R[1][i] * fl[1] + R[2][i] * fl[2];
-        r[i] = pconst<T>(0.5 * h * grav + m * ((q1[i] - q0[i]) / h) + 0.5 * h * grav + u1[i] + w1[i]) - m * vm2[i] + lam;
-    }
-    const T v0 = R[0][0] * vm2[0] + R[0][1] * vm2[1] + R[0][2] * vm2[2];
-    const T v1 = R[1][0] * vm2[0] + R[1][1] * vm2[1] + R[1][2] * vm2[2];
-    r[3] = s1[0] - (q2[2] - surf);
-    r[4] = eta[0] - v0 - psi[0]; r[5] = eta[1] - v1 - psi[0];
-    r[6] = eta[2] + v0 - psi[0]; r[7] = eta[3] + v1 - psi[0];
-    r[8] = s2[0] - (mu * gam[0] - (b[0] + b[1] + b[2] + b[3]));
-    r[9] = gam[0] * s1[0] - kappa;
-    for (int q = 0; q < 4; ++q) r[10 + q] = b[q] * eta[q] - kappa;
-    r[14] = psi[0] * s2[0] - kappa;
+    plant_contact_rows<2>(2, 1, 0, z, q2[1] - surf, &vt, mu, kappa, r);
 }
 
 // ---- hopper_3D (src/dynamics/hopper_3D/model.jl): q = (body position, modified Rodrigues parameters p, leg length l), all mass
@@ -520,14 +438,14 @@ PLANT_HD void plant_mrp_axis(const T* p, T a[3], T D[3][3]) {
     a[2] = a[2] + 1.0;
 }
 // Both grounds: E = nullptr (or a flat E) is flat_3D_lc, surface rotation = identity; otherwise surface and rotation are taken at
-// the foot k[0:2] as plant_residual_particle_terrain takes them at the particle: force Rs^T [m b; γ], tangential velocity
-// (Rs J (q2 - q1) / h)[0:2], ϕ = k_z - surf(k_x, k_y) (:50-52, :75-87).
+// the foot k[0:2] as the particle takes them at itself: force Rs^T [m b; γ], tangential velocity (Rs J (q2 - q1) / h)[0:2],
+// ϕ = k_z - surf(k_x, k_y) (:50-52, :75-87).
 template <class T>
 PLANT_HD void plant_residual_hopper_3d(const PlantModel& M, const cimpc_terrain* E, const T* z, const double* th, double kappa, T* r) {
     constexpr int nq = 7;
     const double* q0 = th; const double* q1 = th + 7; const double* u1 = th + 14; const double* w1 = th + 17;
     const double mu = th[20], h = th[21];
-    const T* q2 = z; const T* gam = z + 7; const T* b = z + 8; const T* psi = z + 12; const T* s1 = z + 13; const T* eta = z + 14; const T* s2 = z + 18;
+    const T* q2 = z; const T* gam = z + 7; const T* b = z + 8;
     T qm2[nq], vm2[nq], dyn[nq];
     for (int i = 0; i < nq; ++i) { qm2[i] = (q2[i] + q1[i]) * 0.5; vm2[i] = (q2[i] - q1[i]) / h; }
     // 0.5 h D1L + D2L at (qm1, vm1), 0.5 h D1L - D2L at (qm2, vm2): D1L = -C, D2L = M v
@@ -549,24 +467,16 @@ PLANT_HD void plant_residual_hopper_3d(const PlantModel& M, const cimpc_terrain*
         v[i] = vm2[i] - l * (D[i][0] * vm2[3] + D[i][1] * vm2[4] + D[i][2] * vm2[5]) - a[i] * vm2[6];
     }
     const T fl[3] = {b[0] - b[2], b[1] - b[3], gam[0]};
-    T F[3], v0, v1x, phi;
+    T F[3], vt[2], phi;
     if (E && E->kind != CIMPC_TERRAIN_FLAT) {
-        T surf, gx, gy;
-        terrain_eval(*E, k[0], k[1], surf, gx, gy);
-        const T inv = 1.0 / psqrt(1.0 + gx * gx + gy * gy);
-        const T nx = -(gx * inv), ny = -(gy * inv), nz = inv;
-        const T vx = ny, vy = -nx, kk = 1.0 / (1.0 + nz);
-        T R[3][3];
-        R[0][0] = 1.0 - kk * (vy * vy); R[0][1] = kk * (vx * vy);       R[0][2] = vy;
-        R[1][0] = kk * (vx * vy);       R[1][1] = 1.0 - kk * (vx * vx); R[1][2] = -vx;
-        R[2][0] = -vy;                  R[2][1] = vx;                   R[2][2] = 1.0 - kk * (vx * vx + vy * vy);
+        T surf, R[3][3];
+        terrain_frame_3d(*E, k[0], k[1], surf, R);
         for (int i = 0; i < 3; ++i) F[i] = R[0][i] * fl[0] + R[1][i] * fl[1] + R[2][i] * fl[2];
-        v0 = R[0][0] * v[0] + R[0][1] * v[1] + R[0][2] * v[2];
-        v1x = R[1][0] * v[0] + R[1][1] * v[1] + R[1][2] * v[2];
+        for (int i = 0; i < 2; ++i) vt[i] = R[i][0] * v[0] + R[i][1] * v[1] + R[i][2] * v[2];
         phi = k[2] - surf;
     } else {
         for (int i = 0; i < 3; ++i) F[i] = fl[i];
-        v0 = v[0]; v1x = v[1];
+        vt[0] = v[0]; vt[1] = v[1];
         phi = k[2];
     }
     // J^T F
@@ -574,29 +484,21 @@ PLANT_HD void plant_residual_hopper_3d(const PlantModel& M, const cimpc_terrain*
     for (int j = 0; j < 3; ++j) dyn[3 + j] = dyn[3 + j] - l * (D[0][j] * F[0] + D[1][j] * F[1] + D[2][j] * F[2]);
     dyn[6] = dyn[6] - (a[0] * F[0] + a[1] * F[1] + a[2] * F[2]);
     for (int i = 0; i < nq; ++i) r[i] = dyn[i];
-    r[7] = s1[0] - phi;
-    r[8] = eta[0] - v0 - psi[0]; r[9] = eta[1] - v1x - psi[0];
-    r[10] = eta[2] + v0 - psi[0]; r[11] = eta[3] + v1x - psi[0];
-    r[12] = s2[0] - (mu * gam[0] - (b[0] + b[1] + b[2] + b[3]));
-    r[13] = gam[0] * s1[0] - kappa;
-    for (int q = 0; q < 4; ++q) r[14 + q] = b[q] * eta[q] - kappa;
-    r[18] = psi[0] * s2[0] - kappa;
+    plant_contact_rows<4>(nq, 1, 0, z, phi, vt, mu, kappa, r);
 }
 
-// r(z, θ, κ) on terrain E: plant_residual with, per contact i at foot p_i, ϕ_i = p_z - surf(p_x), the world force R_i^T [m b_i; γ_i]
-// through both Jacobian rows of the foot and the tangential velocity (R_i J_i (q2 - q1) / h)[1] (simulation.jl:133-158,
-// contact_methods.jl, quadruped/model.jl:472-492, hopper_2D/model.jl:54-85).  Each contact's rotation is taken at its own foot.
-// Planar chains, hopper_2D, particle_2D and (3-D kinds) particle and hopper_3D; centroidal_quadruped is refused by the caller.
-template <class T>
-PLANT_HD void plant_residual_terrain(const PlantModel& M, const cimpc_terrain& E, const T* z, const double* th, double kappa, T* r) {
-    if (M.kind == PLANT_KIND_PARTICLE) { plant_residual_particle_terrain<T>(M, E, z, th, kappa, r); return; }
-    if (M.kind == PLANT_KIND_PARTICLE_2D) { plant_residual_particle_2d<T>(M, E, z, th, kappa, r); return; }
-    if (M.kind == PLANT_KIND_HOPPER_3D) { plant_residual_hopper_3d<T>(M, &E, z, th, kappa, r); return; }
-    const int nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb();
+// ---- planar chains and hopper_2D: r(z, θ, κ), z = [q2; γ; b; ψ; s1; η; s2], θ = [q0; q1; u1; w1; μ; h] (θ real: only dr/dz is needed).
+// ROUGH = false is flat ground (E unused): ϕ = p_z, force [m b; γ], tangential velocity v_x.  ROUGH = true, on terrain E, has per
+// contact i at foot p_i ϕ_i = p_z - surf(p_x), the world force R_i^T [m b_i; γ_i] through both Jacobian rows of the foot and the
+// tangential velocity (R_i J_i (q2 - q1) / h)[1] (simulation.jl:133-158, contact_methods.jl, quadruped/model.jl:472-492,
+// hopper_2D/model.jl:54-85).  Each contact's rotation is taken at its own foot.
+template <bool ROUGH, class T>
+PLANT_HD void plant_residual_chain(const PlantModel& M, const cimpc_terrain* E, const T* z, const double* th, double kappa, T* r) {
+    const int nq = M.nq, nu = M.nu, nc = M.nc;
+    const bool hopper = M.kind == PLANT_KIND_HOPPER_2D;
     const double* q0 = th; const double* q1 = th + nq; const double* u1 = th + 2 * nq; const double* w1 = u1 + nu;
     const double mu = w1[M.nw], h = w1[M.nw + 1];
-    const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc; const T* psi = b + nb; const T* s1 = psi + nc;
-    const T* eta = s1 + nc; const T* s2 = eta + nb;
+    const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc;
     T qm1[PLANT_MAX_Q], vm1[PLANT_MAX_Q], qm2[PLANT_MAX_Q], vm2[PLANT_MAX_Q];
     for (int i = 0; i < nq; ++i) {
         qm1[i] = pconst<T>(0.5 * (q0[i] + q1[i])); vm1[i] = pconst<T>((q1[i] - q0[i]) / h);
@@ -608,7 +510,8 @@ PLANT_HD void plant_residual_terrain(const PlantModel& M, const cimpc_terrain& E
     T dyn[PLANT_MAX_Q];
     for (int i = 0; i < nq; ++i)
         dyn[i] = (0.5 * h) * a1[i] + b1[i] + (0.5 * h) * a2[i] - b2[i] - (h * M.joint_friction[i]) * vm2[i];
-    if (M.kind == PLANT_KIND_HOPPER_2D) {
+    if (hopper) {
+        // B(qm2)^T u, hopper_2D/model.jl:68-71: body torque on t; leg force along the leg axis (-sin t, cos t) and on r
         const T st = psin(qm2[2]), ct = pcos(qm2[2]);
         dyn[2] = dyn[2] + u1[0];
         dyn[0] = dyn[0] - u1[1] * st; dyn[1] = dyn[1] + u1[1] * ct; dyn[3] = dyn[3] + u1[1];
@@ -616,51 +519,73 @@ PLANT_HD void plant_residual_terrain(const PlantModel& M, const cimpc_terrain& E
         for (int i = 0; i < nu; ++i) { dyn[M.tq_a[i]] = dyn[M.tq_a[i]] - u1[i]; dyn[M.tq_b[i]] = dyn[M.tq_b[i]] + u1[i]; }
     }
     for (int i = 0; i < M.nw; ++i) dyn[i] = dyn[i] + w1[i];
+    // contacts: position, velocity J (q2 - q1) / h and Jacobian rows (x and z) of every foot at q2; px and vz on rough ground only
     T s[PLANT_MAX_Q], c[PLANT_MAX_Q];
     for (int i = 0; i < nq; ++i) { s[i] = psin(q2[i]); c[i] = pcos(q2[i]); }
     for (int f = 0; f < nc; ++f) {
         const PlantChain& ch = M.foot[f];
-        T px = q2[0], pz = q2[1];
-        T vx = (q2[0] - q1[0]) / h, vz = (q2[1] - q1[1]) / h;        // foot velocity J (q2 - q1) / h
-        if (M.kind == PLANT_KIND_HOPPER_2D) {
+        const int ne = hopper ? 0 : ch.n;
+        T px{}, pz = q2[1], vx = (q2[0] - q1[0]) / h, vz{};
+        if constexpr (ROUGH) { px = q2[0]; vz = (q2[1] - q1[1]) / h; }
+        if (hopper) {
+            // foot = (x + r sin t, z - r cos t), J = [1 0 r cos t sin t; 0 1 r sin t -cos t] at q2 (hopper_2D/model.jl:35-66)
             const T rl = q2[3];
-            px = px + rl * s[2];
             pz = pz - rl * c[2];
             vx = vx + rl * (c[2] * ((q2[2] - q1[2]) / h)) + s[2] * ((q2[3] - q1[3]) / h);
-            vz = vz + rl * (s[2] * ((q2[2] - q1[2]) / h)) - c[2] * ((q2[3] - q1[3]) / h);
+            if constexpr (ROUGH) {
+                px = px + rl * s[2];
+                vz = vz + rl * (s[2] * ((q2[2] - q1[2]) / h)) - c[2] * ((q2[3] - q1[3]) / h);
+            }
         }
-        for (int e = 0; e < (M.kind == PLANT_KIND_HOPPER_2D ? 0 : ch.n); ++e) {
+        for (int e = 0; e < ne; ++e) {
             const int k = ch.k[e]; const double rr = ch.r[e];
-            px = px + rr * s[k];
             pz = pz - rr * c[k];
             vx = vx + rr * (c[k] * ((q2[k] - q1[k]) / h));
-            vz = vz + rr * (s[k] * ((q2[k] - q1[k]) / h));
+            if constexpr (ROUGH) {
+                px = px + rr * s[k];
+                vz = vz + rr * (s[k] * ((q2[k] - q1[k]) / h));
+            }
         }
-        T surf, cr, sr;
-        terrain_frame_2d(E, px, surf, cr, sr);
-        const T lt = b[2 * f] - b[2 * f + 1];
-        const T lx = cr * lt + sr * gam[f], lz = cr * gam[f] - sr * lt;      // R^T [lt; γ]
-        const T vt = cr * vx - sr * vz;                                       // (R v)[1]
-        dyn[0] = dyn[0] + lx; dyn[1] = dyn[1] + lz;
-        if (M.kind == PLANT_KIND_HOPPER_2D) {
+        T lx = b[2 * f] - b[2 * f + 1], lz = gam[f], vt = vx, phi = pz;      // contact force [m b; γ]
+        if constexpr (ROUGH) {
+            T surf, cr, sr;
+            terrain_frame_2d(*E, px, surf, cr, sr);
+            const T lt = lx;
+            lx = cr * lt + sr * gam[f]; lz = cr * gam[f] - sr * lt;           // R^T [lt; γ]
+            vt = cr * vx - sr * vz;                                           // (R v)[1]
+            phi = pz - surf;
+        }
+        dyn[0] = dyn[0] + lx; dyn[1] = dyn[1] + lz;                           // J^T λ: base columns
+        if (hopper) {
             const T rl = q2[3];
             dyn[2] = dyn[2] + rl * (c[2] * lx + s[2] * lz);
             dyn[3] = dyn[3] + (s[2] * lx - c[2] * lz);
         }
-        for (int e = 0; e < (M.kind == PLANT_KIND_HOPPER_2D ? 0 : ch.n); ++e) {
+        for (int e = 0; e < ne; ++e) {
             const int k = ch.k[e]; const double rr = ch.r[e];
             dyn[k] = dyn[k] + rr * (c[k] * lx + s[k] * lz);
         }
-        r[nq + f] = s1[f] - (pz - surf);
-        r[nq + nc + 2 * f] = eta[2 * f] - vt - psi[f];
-        r[nq + nc + 2 * f + 1] = eta[2 * f + 1] + vt - psi[f];
-        r[nq + nc + nb + f] = s2[f] - (mu * gam[f] - (b[2 * f] + b[2 * f + 1]));
-        r[nq + 2 * nc + nb + f] = gam[f] * s1[f] - kappa;
-        r[nq + 3 * nc + nb + 2 * f] = b[2 * f] * eta[2 * f] - kappa;
-        r[nq + 3 * nc + nb + 2 * f + 1] = b[2 * f + 1] * eta[2 * f + 1] - kappa;
-        r[nq + 3 * nc + 2 * nb + f] = psi[f] * s2[f] - kappa;
+        plant_contact_rows<2>(nq, nc, f, z, phi, &vt, mu, kappa, r);
     }
     for (int i = 0; i < nq; ++i) r[i] = dyn[i];
+}
+
+// The flat entry: every model cimpc_plant_step has (particle_2D has none; the box and the wall call plant_residual_centroidal_env).
+template <class T>
+PLANT_HD void plant_residual(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
+    if (M.kind == PLANT_KIND_CENTROIDAL) { plant_residual_centroidal<T>(M, z, th, kappa, r); return; }
+    if (M.kind == PLANT_KIND_PARTICLE) { plant_residual_particle<false, T>(M, nullptr, z, th, kappa, r); return; }
+    if (M.kind == PLANT_KIND_HOPPER_3D) { plant_residual_hopper_3d<T>(M, nullptr, z, th, kappa, r); return; }
+    plant_residual_chain<false, T>(M, nullptr, z, th, kappa, r);
+}
+// The terrain entry: planar chains, hopper_2D, particle_2D and (3-D kinds) particle and hopper_3D; the centroidal models are
+// refused by the caller.
+template <class T>
+PLANT_HD void plant_residual_terrain(const PlantModel& M, const cimpc_terrain& E, const T* z, const double* th, double kappa, T* r) {
+    if (M.kind == PLANT_KIND_PARTICLE) { plant_residual_particle<true, T>(M, &E, z, th, kappa, r); return; }
+    if (M.kind == PLANT_KIND_PARTICLE_2D) { plant_residual_particle_2d<T>(M, E, z, th, kappa, r); return; }
+    if (M.kind == PLANT_KIND_HOPPER_3D) { plant_residual_hopper_3d<T>(M, &E, z, th, kappa, r); return; }
+    plant_residual_chain<true, T>(M, &E, z, th, kappa, r);
 }
 
 // Which terrains a model takes (cimpc_plant_step_terrain): FLAT everywhere; planar kinds on the planar models; 3-D kinds on the
@@ -681,7 +606,7 @@ inline bool terrain_valid_for(const PlantModel& M, const cimpc_terrain& E) {
     return terrain_is_3d(E.kind) == (M.kind == PLANT_KIND_PARTICLE || M.kind == PLANT_KIND_HOPPER_3D);
 }
 
-// ---- the two models the reference tests in closed loop ---------------------------------------------------------------
+// ---- the models: one table per CIMPC_PLANT_* id, from the reference's model files ----------------------------------------
 inline PlantChain plant_chain(int n, double r0, int k0, double r1 = 0, int k1 = 0, double r2 = 0, int k2 = 0) {
     PlantChain c{}; c.n = n; c.r[0] = r0; c.k[0] = k0; c.r[1] = r1; c.k[1] = k1; c.r[2] = r2; c.k[2] = k2; return c;
 }

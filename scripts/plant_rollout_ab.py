@@ -4,11 +4,12 @@ builds of the library, on one GPU in one process: alternating pairs, a host cloc
 
 Rollout legs: the open-loop replay of quadruped gait2 (mu 0.5, T = H steps) and of hopper_3D gait_in_place (T = H steps), every robot
 from the gait's own start, B in {4, 64, 512}; per pair the loop's and the rollout's wall time per step, whose outputs are compared
-bit for bit once per leg.  Step legs: one `plant_step` call at B = 512 hopper_3D robots at gait_forward knots and at B = 256 quadrupeds
-at gait2 knots, this build against every `--step-lib NAME=PATH` (e.g. a build of the parent commit, and a copy of it for the spread
-of a build against itself), alternating per pair; `--parent-step-us LEG=US` records a figure measured elsewhere next to them.
+bit for bit once per leg.  Step legs (`step_legs`): one `plant_step` call per leg, a table that reaches every kernel instantiation and
+every residual of plant_model.h on flat ground and on terrain, this build against every `--step-lib NAME=PATH` (e.g. a build of the
+parent commit, and a copy of it for the spread of a build against itself), alternating per pair; the small models (B = 16) are
+compared only, not timed.  `--parent-step-us LEG=US` records a figure measured elsewhere next to them.
 usage: python scripts/plant_rollout_ab.py [--pairs 5] [--calls 100] [--step-lib NAME=PATH ...] [--parent-step-us LEG=US ...]
-                                          [--out profiles/plant_rollout_ab.json]"""
+                                          [--no-rollout] [--out profiles/plant_rollout_ab.json]"""
 import argparse
 import ctypes as C
 import dataclasses
@@ -60,8 +61,9 @@ def rollout_leg(name, model, q0, q1, u, h, mu, B, pairs):
     return out
 
 
-def step_leg(name, model, q0, q1, u, h, mu, libs, pairs, calls):
-    """one `cimpc_plant_step` call on every library in turn, `calls` calls per turn, `pairs` turns: us per call"""
+def step_leg(name, model, q0, q1, u, h, mu, libs, pairs, calls, terrain=None):
+    """one `cimpc_plant_step` call (`cimpc_plant_step_terrain` on a terrain name) on every library in turn, `calls` calls per turn,
+    `pairs` turns: us per call; pairs = 0 only compares the outputs"""
     mid, nq, nu, nc, fd, nw = plant.model_dims(model)
     B = q0.shape[0]
     q0, q1, u = (np.ascontiguousarray(a, dtype=np.float64) for a in (q0, q1, u))
@@ -69,11 +71,13 @@ def step_leg(name, model, q0, q1, u, h, mu, libs, pairs, calls):
     o = _lib.IpOpts(**dataclasses.asdict(plant.SIM_OPTS))
     dp = lambda a: a.ctypes.data_as(_lib._dp)
     ip = lambda a: a.ctypes.data_as(_lib._ip)
+    ta, nt = (None, 0) if terrain is None else plant._terrain_array(terrain, B)
 
     def call(lib):
-        rc = lib.cimpc_plant_step(mid, B, dp(q0), dp(q1), dp(u), None, float(mu), float(h), C.byref(o), dp(q2), dp(g), dp(b), ip(st), ip(it))
+        out = (dp(q0), dp(q1), dp(u), None, float(mu), float(h), C.byref(o), dp(q2), dp(g), dp(b), ip(st), ip(it))
+        rc = lib.cimpc_plant_step(mid, B, *out) if terrain is None else lib.cimpc_plant_step_terrain(mid, B, nt, ta, *out)
         if rc != 0:
-            raise _lib.CimpcError(f"cimpc_plant_step failed ({rc})")
+            raise _lib.CimpcError(f"plant step of leg {name} failed ({rc})")
 
     results, outputs = {k: [] for k in libs}, {}
     for k, lib in libs.items():                                     # warm-up, and the outputs side by side
@@ -87,10 +91,61 @@ def step_leg(name, model, q0, q1, u, h, mu, libs, pairs, calls):
                 call(lib)
             results[k].append((time.perf_counter() - t0) / calls * 1e6)
     first = outputs["this"]
-    out = {"leg": name, "model": model, "B": B, "calls_per_turn": calls, "ip_iterations_per_robot": round(float(first[4].mean()), 2),
-           "all_converged": bool(first[3].all()), "per_call": {k: summary(v) for k, v in results.items()},
+    out = {"leg": name, "model": model, "terrain": terrain, "B": B, "calls_per_turn": calls, "ip_iterations_per_robot": round(float(first[4].mean()), 2),
+           "all_converged": bool(first[3].all()), "per_call": {k: summary(v) for k, v in results.items()} if pairs else None,
            "identical_outputs": {k: all(np.array_equal(x, y) for x, y in zip(first, v)) for k, v in outputs.items() if k != "this"}}
     print(json.dumps(out), flush=True)
+    return out
+
+
+def step_legs(libs, pairs, calls):
+    """quadruped, centroidal, box and wall at B = 256 and hopper_3D at B = 512, at knots spread over their gaits; the quadruped on
+    terrain as tests/test_gpu_terrain.py places it (x over [0, 2.5], lifted by the height under the hip, h / 5), hopper_3D on the
+    sine as tests/test_gpu_hopper_3d.py does; the small models at B = 16 with the inputs of the terrain tests, outputs only"""
+    from contactimplicitmpc.jl_amd import terrain
+    gait = lambda f: gait_io.load_gait(os.path.join(GAITS, f + ".jld2"))
+    knots = lambda g, B: np.arange(B) * g.H // B
+    leg = lambda name, model, q0, q1, u, h, mu, n=calls, ter=None, timed=True: step_leg(name, model, q0, q1, u, h, mu, libs, pairs if timed else 0, n, ter)
+    out = []
+    fwd = gait_io.load_joint_traj(os.path.join(GAITS, "hopper_3D_gait_forward.jld2"))
+    k = knots(fwd, 512)
+    out.append(leg("hopper512", "hopper_3D", fwd.q[k], fwd.q[k + 1], fwd.u[k], 0.01, 1.5))
+    shift = np.zeros((512, 7)); shift[:, 0] = 0.13 * k; shift[:, 2] = 0.075
+    out.append(leg("hopper512 sine2", "hopper_3D", fwd.q[k] + shift, fwd.q[k + 1] + shift, fwd.u[k], 0.01, 1.5, ter="sine2_3D_lc"))
+    quad = gait("quadruped_gait2")
+    k = knots(quad, 256)
+    out.append(leg("quadruped256", "quadruped", quad.q[k], quad.q[k + 1], quad.u[k], quad.h, 0.5, max(10, calls // 5)))
+    for name in ("sine1_2D_lc", "piecewise1_2D_lc"):
+        q0, q1 = quad.q[k].copy(), quad.q[k + 1].copy()
+        for q in (q0, q1):
+            q[:, 0] += np.linspace(0.0, 2.5, 256)
+            q[:, 1] += terrain.get(name).surface(q[:, 0])
+        out.append(leg("quadruped256 " + name, "quadruped", q0, q1, quad.u[k], quad.h / 5, 1.0, max(10, calls // 10), ter=name))
+    for model, f in (("centroidal_quadruped", "centroidal_inplace_trot_v7"), ("centroidal_quadruped_box", "step_over_box_v0"),
+                     ("centroidal_quadruped_wall", "wall_stand_FL_4")):
+        g = gait(f)
+        k = knots(g, 256)
+        out.append(leg(model.replace("_quadruped", "") + "256", model, g.q[k], g.q[k + 1], g.u[k], g.h, g.mu, max(10, calls // 5)))
+    fl = gait("flamingo_gait_forward_36_4")
+    k = np.arange(16)
+    out.append(leg("flamingo16", "flamingo", fl.q[k], fl.q[k + 1], fl.u[k], fl.h, 0.9, timed=False))
+    rng = np.random.default_rng(7)
+    for model, name, nq in (("hopper_2D", "slope1_2D_lc", 4), ("particle", "quadratic_bowl_3D_lc", 3), ("particle_2D", "slope1_2D_lc", 2)):
+        T, q1 = terrain.get(name), np.zeros((16, nq))
+        q1[:, 0] = rng.uniform(-1.0, 1.0, 16) if model == "particle" else np.linspace(-0.2, 2.3, 16)
+        if model == "particle":
+            q1[:, 1] = rng.uniform(-1.0, 1.0, 16)
+            q1[:, 2] = T.surface(q1[:, 0], q1[:, 1]) + rng.uniform(-0.01, 0.02, 16)
+        elif model == "hopper_2D":
+            q1[:, 2] = rng.uniform(-0.2, 0.2, 16); q1[:, 3] = 0.5
+            q1[:, 1] = T.surface(q1[:, 0] + 0.5 * np.sin(q1[:, 2])) + 0.5 * np.cos(q1[:, 2]) + rng.uniform(-0.01, 0.02, 16)
+        else:
+            q1[:, 1] = T.surface(q1[:, 0]) + rng.uniform(-0.01, 0.02, 16)
+        u = rng.uniform(-1.0, 1.0, (16, plant.model_dims(model)[2]))
+        if model == "hopper_2D":
+            u[:, 1] += 3.3 * 9.81 * 0.2
+        out.append(leg(model + "16 " + name, model, q1 - 0.01 * rng.uniform(-0.5, 0.5, (16, nq)), q1, u, 0.01, 0.8 if model == "hopper_2D" else 0.5,
+                       ter=name, timed=False))
     return out
 
 
@@ -100,6 +155,7 @@ def main():
     ap.add_argument("--calls", type=int, default=100)
     ap.add_argument("--step-lib", action="append", default=[], metavar="NAME=PATH")
     ap.add_argument("--parent-step-us", action="append", default=[], metavar="LEG=US")
+    ap.add_argument("--no-rollout", action="store_true", help="the step legs only")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plant_rollout_ab.json"))
     a = ap.parse_args()
 
@@ -109,21 +165,18 @@ def main():
     for spec in a.step_lib:
         name, path = spec.split("=", 1)
         lib = C.CDLL(os.path.abspath(path))
-        lib.cimpc_plant_step.restype, lib.cimpc_plant_step.argtypes = _lib.SIGNATURES["cimpc_plant_step"]
+        for f in ("cimpc_plant_step", "cimpc_plant_step_terrain"):
+            getattr(lib, f).restype, getattr(lib, f).argtypes = _lib.SIGNATURES[f]
         libs[name] = lib
 
-    quad = gait_io.load_gait(os.path.join(GAITS, "quadruped_gait2.jld2"))
-    hop = gait_io.load_joint_traj(os.path.join(GAITS, "hopper_3D_gait_in_place.jld2"))
-    fwd = gait_io.load_joint_traj(os.path.join(GAITS, "hopper_3D_gait_forward.jld2"))
-    res = {"device": torch.cuda.get_device_name(0), "pairs": a.pairs, "rollout": [], "plant_step": [],
+    res = {"device": torch.cuda.get_device_name(0), "pairs": a.pairs, "rollout": [], "plant_step": step_legs(libs, a.pairs, a.calls),
            "parent_step_us_from_the_command_line": dict(s.split("=", 1) for s in a.parent_step_us)}
-    k = np.arange(512) * fwd.H // 512
-    res["plant_step"].append(step_leg("hopper512", "hopper_3D", fwd.q[k], fwd.q[k + 1], fwd.u[k], 0.01, 1.5, libs, a.pairs, a.calls))
-    k = np.arange(256) * quad.H // 256
-    res["plant_step"].append(step_leg("quadruped256", "quadruped", quad.q[k], quad.q[k + 1], quad.u[k], quad.h, 0.5, libs, a.pairs, max(10, a.calls // 5)))
-    for B in BATCHES:
-        res["rollout"].append(rollout_leg("hopper_3D gait_in_place replay", "hopper_3D", hop.q[0], hop.q[1], np.asarray(hop.u), hop.h, 1.5, B, a.pairs))
-        res["rollout"].append(rollout_leg("quadruped gait2 replay", "quadruped", quad.q[0], quad.q[1], np.asarray(quad.u), quad.h, 0.5, B, a.pairs))
+    if not a.no_rollout:
+        quad = gait_io.load_gait(os.path.join(GAITS, "quadruped_gait2.jld2"))
+        hop = gait_io.load_joint_traj(os.path.join(GAITS, "hopper_3D_gait_in_place.jld2"))
+        for B in BATCHES:
+            res["rollout"].append(rollout_leg("hopper_3D gait_in_place replay", "hopper_3D", hop.q[0], hop.q[1], np.asarray(hop.u), hop.h, 1.5, B, a.pairs))
+            res["rollout"].append(rollout_leg("quadruped gait2 replay", "quadruped", quad.q[0], quad.q[1], np.asarray(quad.u), quad.h, 0.5, B, a.pairs))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
