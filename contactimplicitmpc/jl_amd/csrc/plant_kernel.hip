@@ -28,6 +28,11 @@ constexpr int NZM = PLANT_MAX_Q + 4 * PLANT_NC + 2 * PLANT_NB;      // 66 (centr
 #endif
 constexpr int NZ_HOPPER_3D = CIMPC_NZ_HOPPER_3D;                    // hopper_3D on terrain steps on an instantiation of its own size
 static_assert(NZ_HOPPER_3D >= 19, "hopper_3D: nz = 19");
+#ifndef CIMPC_NZ_WALLS
+#define CIMPC_NZ_WALLS (4 + 8 + 8)          // 20; EXTRA=-DCIMPC_NZ_WALLS=66 builds the shared size for the comparison of DESIGN.md section 5.5
+#endif
+constexpr int NZ_WALLS = CIMPC_NZ_WALLS;                            // pushbot (nz = 18) and walledcartpole (nz = 20) step on an instantiation of their own size
+static_assert(NZ_WALLS >= 20, "walledcartpole: nz = 20");
 
 struct PlantOpts {
     double r_tol, kappa_tol, kc_floor, eps_min, ls_scale, stall_alpha;
@@ -103,12 +108,13 @@ __device__ __forceinline__ double lanes_sum(double v, double* red) {
 // terrain[n_terrain == 1 ? 0 : rb]; a flat robot still evaluates plant_residual, so its step is the FLAT one (a uniform branch per
 // robot).  ENV: plant_residual_centroidal_env on flat ground, centroidal_quadruped_box (NZ = 66, one wavefront) and
 // centroidal_quadruped_wall (NZ = 114, two wavefronts: lane j evaluates Jacobian column j, and the 114 x 115 LU stays in LDS).
-enum { GROUND_FLAT, GROUND_TERRAIN, GROUND_ENV };
+// WALLS: plant_residual_walls on flat ground, pushbot and walledcartpole (NZ = 20).
+enum { GROUND_FLAT, GROUND_TERRAIN, GROUND_ENV, GROUND_WALLS };
 
 // Steps R.t0 .. R.t0 + R.n - 1 of robot blockIdx.x's rollout on NT lanes, sized by NZ (A is NZ x NZ + 1): the only statement of the
-// iteration, with reductions over both wavefronts when NT = 128; cimpc_plant_step is its n = 1 use.  Five instantiations: (66, 64, FLAT),
-// (66, 64, TERRAIN), (66, 64, ENV) for the box, (114, 128, ENV) for the wall and (19, 64, TERRAIN) for hopper_3D on terrain, whose
-// per-lane z and r copies and LDS matrix shrink with NZ.  The iteration names the LDS arrays directly: handed
+// iteration, with reductions over both wavefronts when NT = 128; cimpc_plant_step is its n = 1 use.  Six instantiations: (66, 64, FLAT),
+// (66, 64, TERRAIN), (66, 64, ENV) for the box, (114, 128, ENV) for the wall, (19, 64, TERRAIN) for hopper_3D on terrain and
+// (20, 64, WALLS) for pushbot and walledcartpole, whose per-lane z and r copies and LDS matrix shrink with NZ.  The iteration names the LDS arrays directly: handed
 // to a helper as pointers they cost the TERRAIN instantiation 8-15 %.  Between steps the state stays in LDS:
 // q2 is stored to its trajectory row and shifted into theta (q1 -> q0, q2 -> q1), nothing is read back from global memory.
 template <int NZ, int NT, int GROUND>
@@ -133,6 +139,8 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
         using T = std::remove_const_t<std::remove_pointer_t<decltype(zz)>>;
         if constexpr (GROUND == GROUND_ENV) {
             plant_residual_centroidal_env<T>(M, zz, ths, kappa, rr);
+        } else if constexpr (GROUND == GROUND_WALLS) {
+            plant_residual_walls<T>(M, zz, ths, kappa, rr);
         } else {
             if constexpr (GROUND == GROUND_TERRAIN) {
                 if (rough) { plant_residual_terrain<T>(M, ter, zz, ths, kappa, rr); return; }
@@ -334,7 +342,7 @@ namespace {
 // chunks back to back (plant_rollout_plan.h; the trajectory buffer carries the state, no host synchronize in between), read back once.
 // A simulator step is the rollout T = 1 with one u / w row per robot, and reads back trajectory row 2 alone (q_row0 = 2).  terrain =
 // nullptr (or every terrain flat on a model cimpc_plant_step has) runs the GROUND_FLAT instantiation; the box and the wall (flat only)
-// run their GROUND_ENV instantiations.
+// run their GROUND_ENV instantiations, pushbot and walledcartpole (flat only) GROUND_WALLS.
 int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain, const double* q0,
                        const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w, int K_w, int n_w, int hold_w,
                        const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, double* q, int q_row0, double* gamma, double* b,
@@ -397,7 +405,8 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
         };
         // hopper_3D (nz = 19): on terrain its own size measured level with the shared one (0.6 % faster, inside the spread), on flat
         // ground 1.8 % slower, so the flat hopper stays on the shared FLAT instantiation
-        if (M.kind == PLANT_KIND_HOPPER_3D && rough) launch(plant_step_kernel<NZ_HOPPER_3D, 64, GROUND_TERRAIN>, 64);
+        if (M.kind == PLANT_KIND_PUSHBOT || M.kind == PLANT_KIND_WALLEDCARTPOLE) launch(plant_step_kernel<NZ_WALLS, 64, GROUND_WALLS>, 64);
+        else if (M.kind == PLANT_KIND_HOPPER_3D && rough) launch(plant_step_kernel<NZ_HOPPER_3D, 64, GROUND_TERRAIN>, 64);
         else if (M.kind == PLANT_KIND_CENTROIDAL_BOX) launch(plant_step_kernel<NZM, 64, GROUND_ENV>, 64);
         else if (M.kind == PLANT_KIND_CENTROIDAL_WALL) launch(plant_step_kernel<NZ_WALL, 128, GROUND_ENV>, 128);
         else if (rough) launch(plant_step_kernel<NZM, 64, GROUND_TERRAIN>, 64);

@@ -1,5 +1,6 @@
 // Plant-side residuals of the reference's models for the batched simulator step: the planar chains
-// (quadruped, flamingo) and hopper_2D, centroidal_quadruped with its box and wall variants, particle, particle_2D and hopper_3D.
+// (quadruped, flamingo) and hopper_2D, centroidal_quadruped with its box and wall variants, particle, particle_2D, hopper_3D and
+// the two models between walls, pushbot and walledcartpole.
 // Host- and device-compilable.
 //
 //   residual            src/simulation/simulation.jl:133-158     (LinearizedCone; plant_residual: flat ground, surface rotation =
@@ -65,10 +66,14 @@ template <> PLANT_HD Dual pconst<Dual>(double a) { return {a, 0.0}; }
 
 constexpr int PLANT_MAX_Q = 18, PLANT_MAX_U = 12, PLANT_MAX_BODIES = 9, PLANT_MAX_SEG = 3;
 constexpr int PLANT_NC = 4, PLANT_NB = 16, PLANT_NW = 3;     // maxima: four contacts, two (flat_2D_lc) or four (flat_3D_lc) friction directions each
+// PLANT_NW is the nw of the models with the longest θ (centroidal: 2 * 18 + 12 + 3 + 2 = 53), which is all it sizes; walledcartpole
+// has nw = 4 with nθ = 15.
 constexpr int PLANT_KIND_CHAIN = 0, PLANT_KIND_HOPPER_2D = 1, PLANT_KIND_CENTROIDAL = 2, PLANT_KIND_PARTICLE = 3, PLANT_KIND_PARTICLE_2D = 4;
 // centroidal_quadruped_box / _wall: plant_residual_centroidal_env, stepped by their own kernel instantiations (plant_kernel.hip)
 constexpr int PLANT_KIND_CENTROIDAL_BOX = 5, PLANT_KIND_CENTROIDAL_WALL = 6;
 constexpr int PLANT_KIND_HOPPER_3D = 7;                      // hopper_3D: plant_residual_hopper_3d, stepped by kernel instantiations of its own size
+// pushbot and walledcartpole: plant_residual_walls, stepped by a kernel instantiation of their own size (flat_2D_lc only)
+constexpr int PLANT_KIND_PUSHBOT = 8, PLANT_KIND_WALLEDCARTPOLE = 9;
 constexpr int PLANT_WALL_NC = 8, PLANT_WALL_NB = 32;          // the wall model: four feet on the floor and the same four on the wall
 
 struct PlantChain { int n; double r[PLANT_MAX_SEG]; int k[PLANT_MAX_SEG]; };
@@ -487,6 +492,88 @@ PLANT_HD void plant_residual_hopper_3d(const PlantModel& M, const cimpc_terrain*
     plant_contact_rows<4>(nq, 1, 0, z, phi, vt, mu, kappa, r);
 }
 
+// ---- pushbot (src/dynamics/pushbot/model.jl) and walledcartpole (src/dynamics/walledcartpole/model.jl): one point between two
+// walls, nc = 2, flat_2D_lc (surface rotation = identity), so the generic contact_forces and velocity_stack (contact_methods.jl:27-48)
+// are the force [m b; γ] and the stack (v_T, -v_T) of plant_contact_rows<2>.  A = I on all nq coordinates.
+//   pushbot         q = (θ, d): a pendulum of length l with a sliding arm; the point p = (-l sinθ + d cosθ, l cosθ + d sinθ) between walls at
+//                   x = -+0.5.  M = mb Jcᵀ Jc + ma Jdᵀ Jd and C from the Lagrangian (:66-85), Bᵀu = (l u_1 + u_2, u_1 + u_2 / l) (:106-109).
+//                   mass = (mb, ma), inertia = (l, half the distance between the walls).
+//   walledcartpole  q = (θ, x, xw1, xw2): the tip p = (x - l sinθ, l cosθ) between two walls on springs at -w + xw1 and w + xw2; M and C
+//                   from the Lagrangian (:75-99, with the pole's lc in the place of l), Bᵀu = (0, u, 0, 0) (:119-121).
+//                   mass = (mb, mt, mw), inertia = (l, w, lc, k).
+// Contact 1 is the left wall, contact 2 the right one: with G_i the 2 x nq Jacobian of p minus wall i's own coordinate, the rows are
+// r1 G_1 and r2 G_2, r1 = [0 -1; 1 0] = -r2 (pushbot :98-104, walledcartpole :111-117): tangent -+G_z, normal +-G_x.
+template <class T>
+PLANT_HD void plant_walls_derivatives(const PlantModel& M, const T* q, const T* v, T* d1, T* d2) {
+    const T s = psin(q[0]), c = pcos(q[0]);
+    if (M.kind == PLANT_KIND_PUSHBOT) {
+        const double mb = M.mass[0], ma = M.mass[1], l = M.inertia[0];
+        const T d = q[1];
+        d2[0] = (mb * l * l + ma * (l * l)) * v[0] + ma * ((d * d) * v[0]) - (ma * l) * v[1];
+        d2[1] = ma * v[1] - (ma * l) * v[0];
+        d1[0] = -((2.0 * ma) * (d * (v[1] * v[0])) - (mb * M.g * l) * s - (ma * M.g) * (l * s - d * c));
+        d1[1] = -((ma * M.g) * s - ma * (d * (v[0] * v[0])));
+        return;
+    }
+    const double mb = M.mass[0], mt = M.mass[1], mw = M.mass[2], lc = M.inertia[2], k = M.inertia[3];
+    d2[0] = (mt * lc * lc) * v[0] - (mt * lc) * (c * v[1]);
+    d2[1] = (mt + mb) * v[1] - (mt * lc) * (c * v[0]);
+    d2[2] = mw * v[2];
+    d2[3] = mw * v[3];
+    d1[0] = (mt * M.g * lc) * s;
+    d1[1] = -((mt * lc) * ((v[0] * v[0]) * s));
+    d1[2] = -((2.0 * k) * q[2]);
+    d1[3] = -((2.0 * k) * q[3]);
+}
+template <class T>
+PLANT_HD void plant_residual_walls(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
+    constexpr int MQ = 4, nc = 2;
+    const int nq = M.nq, nu = M.nu;
+    const bool push = M.kind == PLANT_KIND_PUSHBOT;
+    const double* q0 = th; const double* q1 = th + nq; const double* u1 = th + 2 * nq; const double* w1 = u1 + nu;
+    const double mu = w1[M.nw], h = w1[M.nw + 1], l = M.inertia[0], wall = M.inertia[1];
+    const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc;
+    T qm1[MQ]{}, vm1[MQ]{}, qm2[MQ]{}, vm2[MQ]{};       // pushbot fills two of the four
+    for (int i = 0; i < nq; ++i) {
+        qm1[i] = pconst<T>(0.5 * (q0[i] + q1[i])); vm1[i] = pconst<T>((q1[i] - q0[i]) / h);
+        qm2[i] = (q2[i] + q1[i]) * 0.5; vm2[i] = (q2[i] - q1[i]) / h;
+    }
+    T a1[MQ], b1[MQ], a2[MQ], b2[MQ], dyn[MQ];
+    plant_walls_derivatives(M, qm1, vm1, a1, b1);
+    plant_walls_derivatives(M, qm2, vm2, a2, b2);
+    for (int i = 0; i < nq; ++i)
+        dyn[i] = (0.5 * h) * a1[i] + b1[i] + (0.5 * h) * a2[i] - b2[i] - (h * M.joint_friction[i]) * vm2[i];
+    if (push) { dyn[0] = dyn[0] + (l * u1[0] + u1[1]); dyn[1] = dyn[1] + (u1[0] + u1[1] / l); }      // B is constant
+    else dyn[1] = dyn[1] + u1[0];
+    for (int i = 0; i < M.nw; ++i) dyn[i] = dyn[i] + w1[i];
+    // the point at q2: its x and the two rows of its Jacobian on (q_0, q_1)
+    const T s = psin(q2[0]), c = pcos(q2[0]);
+    T px, gx[2], gz[2];
+    if (push) {
+        const T d = q2[1];
+        px = d * c - l * s;
+        gx[0] = -(l * c) - d * s; gx[1] = c;
+        gz[0] = d * c - l * s;    gz[1] = s;
+    } else {
+        px = q2[1] - l * s;
+        gx[0] = -(l * c); gx[1] = pconst<T>(1.0);
+        gz[0] = -(l * s); gz[1] = pconst<T>(0.0);
+    }
+    for (int i = 0; i < nc; ++i) {
+        const double sg = i == 0 ? 1.0 : -1.0;
+        const T lt = b[2 * i] - b[2 * i + 1];
+        // Jᵀ λ with tangent row -sg G_z and normal row sg G_x; the cart-pole's wall i adds -1 on its own coordinate of G_x
+        const T fx = sg * gam[i], fz = -(sg * lt);
+        dyn[0] = dyn[0] + (gx[0] * fx + gz[0] * fz);
+        dyn[1] = dyn[1] + (gx[1] * fx + gz[1] * fz);
+        T phi = sg * px + wall;
+        if (!push) { dyn[2 + i] = dyn[2 + i] - fx; phi = phi - sg * q2[2 + i]; }
+        const T vt = -(sg * (gz[0] * vm2[0] + gz[1] * vm2[1]));
+        plant_contact_rows<2>(nq, nc, i, z, phi, &vt, mu, kappa, r);
+    }
+    for (int i = 0; i < nq; ++i) r[i] = dyn[i];
+}
+
 // ---- planar chains and hopper_2D: r(z, θ, κ), z = [q2; γ; b; ψ; s1; η; s2], θ = [q0; q1; u1; w1; μ; h] (θ real: only dr/dz is needed).
 // ROUGH = false is flat ground (E unused): ϕ = p_z, force [m b; γ], tangential velocity v_x.  ROUGH = true, on terrain E, has per
 // contact i at foot p_i ϕ_i = p_z - surf(p_x), the world force R_i^T [m b_i; γ_i] through both Jacobian rows of the foot and the
@@ -570,7 +657,8 @@ PLANT_HD void plant_residual_chain(const PlantModel& M, const cimpc_terrain* E, 
     for (int i = 0; i < nq; ++i) r[i] = dyn[i];
 }
 
-// The flat entry: every model cimpc_plant_step has (particle_2D has none; the box and the wall call plant_residual_centroidal_env).
+// The flat entry: every model cimpc_plant_step has (particle_2D has none; the box and the wall call plant_residual_centroidal_env,
+// pushbot and walledcartpole plant_residual_walls).
 template <class T>
 PLANT_HD void plant_residual(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
     if (M.kind == PLANT_KIND_CENTROIDAL) { plant_residual_centroidal<T>(M, z, th, kappa, r); return; }
@@ -590,7 +678,8 @@ PLANT_HD void plant_residual_terrain(const PlantModel& M, const cimpc_terrain& E
 
 // Which terrains a model takes (cimpc_plant_step_terrain): FLAT everywhere; planar kinds on the planar models; 3-D kinds on the
 // particle and hopper_3D; centroidal_quadruped, _box and _wall flat only (their reference models never call surf or rotation: the box's step
-// and the wall are inside their phi).
+// and the wall are inside their phi); pushbot and walledcartpole flat only as well (their walls are inside their phi, and the
+// reference runs both on flat_2D_lc alone).
 inline bool terrain_valid_for(const PlantModel& M, const cimpc_terrain& E) {
     const double* f[] = {E.p, E.brk + 1, E.off, &E.coef[0][0]};
     const int n[] = {4, CIMPC_TERRAIN_MAX_PIECES - 1, CIMPC_TERRAIN_MAX_PIECES, 4 * CIMPC_TERRAIN_MAX_PIECES};
@@ -603,6 +692,7 @@ inline bool terrain_valid_for(const PlantModel& M, const cimpc_terrain& E) {
     if (E.kind == CIMPC_TERRAIN_SOFTPLUS && E.p[1] == 0.0) return false;
     if (E.kind == CIMPC_TERRAIN_FLAT) return true;
     if (M.kind == PLANT_KIND_CENTROIDAL || M.kind == PLANT_KIND_CENTROIDAL_BOX || M.kind == PLANT_KIND_CENTROIDAL_WALL) return false;
+    if (M.kind == PLANT_KIND_PUSHBOT || M.kind == PLANT_KIND_WALLEDCARTPOLE) return false;
     return terrain_is_3d(E.kind) == (M.kind == PLANT_KIND_PARTICLE || M.kind == PLANT_KIND_HOPPER_3D);
 }
 
@@ -694,6 +784,24 @@ inline PlantModel plant_particle_2d() {        // particle_2D/model.jl (particle
     for (int i = 0; i < 2; ++i) M.joint_friction[i] = 0.0;
     return M;
 }
+inline PlantModel plant_pushbot() {            // pushbot/model.jl:116-136
+    PlantModel M{};
+    M.kind = PLANT_KIND_PUSHBOT; M.nc = 2; M.fd = 2; M.nw = 2;
+    M.nq = 2; M.nu = 2; M.g = 9.81; M.mu_world = 0.5; M.n_bodies = 0;
+    M.mass[0] = 1.0; M.mass[1] = 0.01;             // mb, ma
+    M.inertia[0] = 1.0; M.inertia[1] = 0.5;        // l, walls at x = -+0.5
+    for (int i = 0; i < 2; ++i) M.joint_friction[i] = 10.0;
+    return M;
+}
+inline PlantModel plant_walledcartpole() {     // walledcartpole/model.jl:130-154
+    PlantModel M{};
+    M.kind = PLANT_KIND_WALLEDCARTPOLE; M.nc = 2; M.fd = 2; M.nw = 4;
+    M.nq = 4; M.nu = 1; M.g = 9.81; M.mu_world = 0.1; M.n_bodies = 0;
+    M.mass[0] = 0.978; M.mass[1] = 0.411; M.mass[2] = 0.1;                              // mb, mt, mw
+    M.inertia[0] = 0.6; M.inertia[1] = 0.35; M.inertia[2] = 0.4267; M.inertia[3] = 50.0;      // l, w, lc, k
+    M.joint_friction[0] = 0.0; M.joint_friction[1] = 1.0; M.joint_friction[2] = 3.0; M.joint_friction[3] = 3.0;
+    return M;
+}
 inline PlantModel plant_flamingo() {           // flamingo/model.jl:458-495
     PlantModel M{};
     M.nq = 9; M.nu = 6; M.g = 9.81; M.mu_world = 0.9;
@@ -733,6 +841,8 @@ inline bool plant_model_by_id(int id, PlantModel* out) {
     case CIMPC_PLANT_CENTROIDAL_BOX: *out = plant_centroidal_box(); return true;
     case CIMPC_PLANT_CENTROIDAL_WALL: *out = plant_centroidal_wall(); return true;
     case CIMPC_PLANT_HOPPER_3D: *out = plant_hopper_3d(); return true;      // id 9 is unassigned
+    case CIMPC_PLANT_PUSHBOT: *out = plant_pushbot(); return true;          // id 11 is unassigned
+    case CIMPC_PLANT_WALLEDCARTPOLE: *out = plant_walledcartpole(); return true;
     default: return false;
     }
 }

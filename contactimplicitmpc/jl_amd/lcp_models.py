@@ -14,6 +14,8 @@ definitions and differentiates it with torch (fp64, CPU, `torch.func` - exact de
   flamingo          src/dynamics/flamingo/model.jl:62-503   (planar biped with toe / heel contacts)
   centroidal_quad.  src/dynamics/centroidal_quadruped/model.jl:61-229, src/dynamics/euler.jl:3-11
   ... box / wall    src/dynamics/centroidal_quadruped_box/model.jl, src/dynamics/centroidal_quadruped_wall/model.jl
+  pushbot           src/dynamics/pushbot/model.jl           (a point between two walls; Lagrangian)
+  walledcartpole    src/dynamics/walledcartpole/model.jl    (the same with walls on springs; Lagrangian)
   reference traj.   src/controller/trajectory.jl:152-184    (`get_trajectory`, :split_traj_alt)
 
 It is host-side input preparation (the reference does it once per knot at policy build) - not
@@ -233,7 +235,22 @@ class Particle(ContactModel):
         return torch.eye(3, dtype=F64)
 
 
-class PlanarChain(ContactModel):
+class LagrangianModel(ContactModel):
+    """A model stated by its `lagrangian(q, v)`: M and C come out of it by automatic differentiation, the reference's own route
+    (src/dynamics/generate_dynamics.jl:126, 143)."""
+
+    def lagrangian(self, q, v):
+        raise NotImplementedError
+
+    def lagrangian_derivatives(self, q, v):
+        # C = d/dq(dL/dq̇) q̇ - dL/dq (quadruped/model.jl:479-484); D1L = -C, D2L = dL/dq̇ = M(q) q̇
+        dLdv = grad(self.lagrangian, argnums=1)
+        d2l, cor = jvp(lambda qq: dLdv(qq, v), (q,), (v,))
+        dLdq = grad(self.lagrangian, argnums=0)(q, v)
+        return dLdq - cor, d2l
+
+
+class PlanarChain(LagrangianModel):
     """Planar articulated model with ABSOLUTE link angles: q = (x, z, angles...).  Every body / contact point is a chain
     of (signed length, angle index) segments from the hip at (x, z): a segment adds r (sin θ, -cos θ).  The Lagrangian
     is the sum over bodies of translational + rotational kinetic energy minus m g z (quadruped/model.jl:261-359,
@@ -267,13 +284,6 @@ class PlanarChain(ContactModel):
             _, pz = self._point(q, chain)
             L = L + 0.5 * m * (vx * vx + vz * vz) + 0.5 * J * v[own] ** 2 - m * self.g * pz
         return L
-
-    def lagrangian_derivatives(self, q, v):
-        # C = d/dq(dL/dq̇) q̇ - dL/dq (quadruped/model.jl:479-484); D1L = -C, D2L = dL/dq̇ = M(q) q̇
-        dLdv = grad(self.lagrangian, argnums=1)
-        d2l, cor = jvp(lambda qq: dLdv(qq, v), (q,), (v,))
-        dLdq = grad(self.lagrangian, argnums=0)(q, v)
-        return dLdq - cor, d2l
 
     def kinematics(self, q):
         pts = []
@@ -446,9 +456,81 @@ class CentroidalQuadrupedWall(CentroidalQuadruped):
         return torch.cat([m.T @ (v[3 * i:3 * i + 2] if i < 4 else v[3 * i + 1:3 * i + 3]) for i in range(self.nc)])
 
 
+_R1 = ((0.0, -1.0), (1.0, 0.0))       # r1 of both J_func; r2 = -r1
+
+
+class PushBot(LagrangianModel):
+    """src/dynamics/pushbot/model.jl: q = (θ, d), a pendulum of length l carrying a sliding arm whose tip
+    p = (-l sinθ + d cosθ, l cosθ + d sinθ) moves between walls at x = -0.5 and x = 0.5 (flat_2D_lc, two contacts at the same point)."""
+    name, nq, nu, nw, nc, space = "pushbot", 2, 2, 2, 2, 2
+    stride_dims = 0
+    mu_world = 0.5
+    mb, ma, l, mu_joint, wall = 1.0, 0.01, 1.0, 10.0, 0.5
+
+    def point(self, q):                           # _kinematics, mode = :d (:26-41)
+        s, c = torch.sin(q[0]), torch.cos(q[0])
+        return torch.stack([-self.l * s + q[1] * c, self.l * c + q[1] * s])
+
+    def lagrangian(self, q, v):                   # :66-78
+        vd = jacfwd(self.point)(q) @ v
+        s, c = torch.sin(q[0]), torch.cos(q[0])
+        vc = torch.stack([-self.l * c * v[0], -self.l * s * v[0]])
+        return (0.5 * self.mb * (vc @ vc) - self.mb * self.g * self.l * c
+                + 0.5 * self.ma * (vd @ vd) - self.ma * self.g * self.point(q)[1])
+
+    def phi(self, q):                             # :87-91
+        x = self.point(q)[0]
+        return torch.stack([x + self.wall, self.wall - x])
+
+    def J(self, q):                               # :98-104
+        r1 = _t(_R1)
+        Jd = jacfwd(self.point)(q)
+        return torch.cat([r1 @ Jd, -r1 @ Jd])
+
+    def B(self, q):                               # :106-109
+        return _t([[self.l, 1.0], [1.0, 1.0 / self.l]])
+
+    def joint_friction(self):
+        return self.mu_joint * torch.ones(2, dtype=F64)
+
+
+class WalledCartpole(LagrangianModel):
+    """src/dynamics/walledcartpole/model.jl: q = (θ, x, xw1, xw2), a cart-pole whose tip (x - l sinθ, l cosθ) moves between two walls on
+    springs at x = -w + xw1 and x = w + xw2 (flat_2D_lc, two contacts at the tip).  The Lagrangian uses the pole's lc, the kinematics l."""
+    name, nq, nu, nw, nc, space = "walledcartpole", 4, 1, 4, 2, 2
+    stride_dims = 0
+    mu_world = 0.1
+    mb, mt, mw, l, lc, w, k, mu_joint = 0.978, 0.411, 0.1, 0.6, 0.4267, 0.35, 50.0, 1.0
+
+    def tip(self, q):                             # _kinematics, mode = :tip (:42-53)
+        return torch.stack([q[1] - self.l * torch.sin(q[0]), self.l * torch.cos(q[0])])
+
+    def lagrangian(self, q, v):                   # :75-99
+        T = (0.5 * (self.mt + self.mb) * v[1] ** 2 - self.mt * v[1] * v[0] * self.lc * torch.cos(q[0]) + 0.5 * self.mt * self.lc ** 2 * v[0] ** 2
+             + 0.5 * self.mw * v[2] ** 2 + 0.5 * self.mw * v[3] ** 2)
+        V = self.mt * self.g * self.lc * torch.cos(q[0]) + self.k * q[2] ** 2 + self.k * q[3] ** 2
+        return T - V
+
+    def phi(self, q):                             # :101-109
+        x = self.tip(q)[0]
+        return torch.stack([x - q[2] + self.w, self.w + q[3] - x])
+
+    def J(self, q):                               # :111-117
+        r1 = _t(_R1)
+        Jt = jacfwd(self.tip)(q)
+        e = lambda i: _t([[1.0 if j == i else 0.0 for j in range(4)], [0.0] * 4])
+        return torch.cat([r1 @ (Jt - e(2)), -r1 @ (Jt - e(3))])
+
+    def B(self, q):                               # :119-121
+        return _t([[0.0, 1.0, 0.0, 0.0]])
+
+    def joint_friction(self):
+        return self.mu_joint * _t([0.0, 1.0, 3.0, 3.0])
+
+
 MODELS = {"hopper_2D": Hopper2D, "hopper_3D": Hopper3D, "particle": Particle, "quadruped": Quadruped, "flamingo": Flamingo, "centroidal_quadruped": CentroidalQuadruped,
           "centroidal_quadruped_undamped": CentroidalQuadrupedUndamped, "centroidal_quadruped_box": CentroidalQuadrupedBox,
-          "centroidal_quadruped_wall": CentroidalQuadrupedWall}
+          "centroidal_quadruped_wall": CentroidalQuadrupedWall, "pushbot": PushBot, "walledcartpole": WalledCartpole}
 
 
 @dataclass
@@ -486,6 +568,16 @@ def reference_problem(model: ContactModel, gait, kappa: float, update_friction: 
                             r0, rz0, rth0)
 
 
+def constant_reference(model: ContactModel, q_ref, H: int, h: float):
+    """The reference of the examples that hold one pose (examples/pushbot/push_recovery.jl:16-32, examples/cartpole/cartpole.jl:15-31):
+    q = q_ref at every knot, u, γ, b, ψ, η all zero, μ = the model's μ_world.  `reference_problem` makes its tables from it."""
+    from .gait_io import Gait
+    q = np.tile(np.asarray(q_ref, dtype=np.float64).reshape(1, model.nq), (H + 2, 1))
+    zeros = lambda n: np.zeros((H, n))
+    return Gait(q=q, u=zeros(model.nu), gamma=zeros(model.nc), b=zeros(model.nb), psi=zeros(model.nc), eta=zeros(model.nb),
+                mu=float(model.mu_world), h=float(h))
+
+
 def reference_problem_from_traj(model: ContactModel, traj, kappa: float) -> ReferenceProblem:
     """The same from a serialized ContactTraj (`load_type = :joint_traj`: z and θ come from the file as they are)."""
     r0, rz0, rth0 = model.linearize_batch(traj.z, traj.theta, kappa)
@@ -495,7 +587,7 @@ def reference_problem_from_traj(model: ContactModel, traj, kappa: float) -> Refe
 
 def get_stride(model: ContactModel, q_ref: np.ndarray) -> np.ndarray:
     """`get_stride` (mpc_utils.jl:103-107): forward progress of one gait period, first coordinate only; hopper_3D moves in the
-    plane and takes x and y (hopper_3D/model.jl:89-93)."""
+    plane and takes x and y (hopper_3D/model.jl:89-93); pushbot and walledcartpole hold a pose and have none."""
     stride = np.zeros(model.nq)
     n = model.stride_dims
     stride[:n] = q_ref[-2][:n] - q_ref[0][:n]

@@ -362,6 +362,12 @@ int cimpc_plant_step(int model, int B, const double* q0, const double* q1, const
 /* Both entries; the terrain entry takes it on FLAT and on the 3-D kinds.  Id 9 is unassigned. */
 #define CIMPC_PLANT_HOPPER_3D 10            /* src/dynamics/hopper_3D/model.jl: nq 7 (position, modified Rodrigues parameters, leg
                                                length), nu 3, nw 3, nc 1, nb 4; the contact is the foot p - R(mrp) e_3 r */
+/* Both entries; the terrain entry takes them on FLAT only (the walls are inside their phi; the reference runs both on flat_2D_lc).
+ * nc 2 (left wall, right wall), nb 4, A = I: w has nq entries.  Id 11, like 9, is unassigned. */
+#define CIMPC_PLANT_PUSHBOT 12              /* src/dynamics/pushbot/model.jl: nq 2 (pendulum angle, arm extension), nu 2, nw 2; the arm's
+                                               tip between walls at x = -0.5 and 0.5 */
+#define CIMPC_PLANT_WALLEDCARTPOLE 13       /* src/dynamics/walledcartpole/model.jl: nq 4 (pole angle, cart, two wall offsets on
+                                               springs), nu 1, nw 4; the pole's tip between walls at -0.35 + xw1 and 0.35 + xw2 */
 #define CIMPC_TERRAIN_FLAT 0
 #define CIMPC_TERRAIN_PIECEWISE 1
 #define CIMPC_TERRAIN_SOFTPLUS 2
@@ -380,7 +386,7 @@ typedef struct cimpc_terrain {
 } cimpc_terrain;
 /* cimpc_plant_step on terrain: n_terrain = 1 (every robot on `terrain[0]`) or B (robot i on terrain[i]).  Planar kinds (PIECEWISE,
  * SOFTPLUS, SINE) apply to quadruped, flamingo, hopper_2D and particle_2D; 3-D kinds to particle and hopper_3D; centroidal_quadruped, _box and
- * _wall take FLAT only (their reference models ignore the environment).  A flat robot runs exactly the code of cimpc_plant_step (bit-identical
+ * _wall, pushbot and walledcartpole take FLAT only (their reference models ignore the environment).  A flat robot runs exactly the code of cimpc_plant_step (bit-identical
  * results).  Any other count, an unknown kind, a kind the model does not take or a non-finite field: CIMPC_ERR_INVALID. */
 int cimpc_plant_step_terrain(int model, int B, int n_terrain, const cimpc_terrain* terrain, const double* q0, const double* q1,
                              const double* u, const double* w, double mu, double h, const cimpc_ip_opts* opts, double* q2,

@@ -448,6 +448,8 @@ const PLANT_ENV_MODELS = Dict{Symbol,NTuple{6,Int}}(
     :centroidal_quadruped_box => (7, 18, 12, 4, 4, 3), :centroidal_quadruped_wall => (8, 18, 12, 8, 4, 3))
 # hopper_3D (plant.py: SPATIAL_MODELS); id 9 is unassigned
 const PLANT_SPATIAL_MODELS = Dict{Symbol,NTuple{6,Int}}(:hopper_3D => (10, 7, 3, 1, 4, 3))
+# pushbot and walledcartpole, a point between two walls (plant.py: WALLED_MODELS); flat ground only; id 11 is unassigned
+const PLANT_WALLED_MODELS = Dict{Symbol,NTuple{6,Int}}(:pushbot => (12, 2, 2, 2, 2, 2), :walledcartpole => (13, 4, 1, 2, 2, 4))
 """
     plant_step(model, q0, q1, u, μ, h_sim, opts; w = nothing) -> (q2, γ, b, status, iters)
 
@@ -455,9 +457,10 @@ q0, q1: nq x B; u: nu x B; w: nw x B or nothing.  Sizes are checked against the 
 """
 function plant_step(model::Symbol, q0::Matrix{Float64}, q1::Matrix{Float64}, u::Matrix{Float64}, μ, h_sim, opts;
                     w::Union{Nothing,Matrix{Float64}} = nothing)
-    haskey(PLANT_SPATIAL_MODELS, model) || haskey(PLANT_ENV_MODELS, model) || haskey(PLANT_MODELS, model) || error("cimpc_plant_step has no model $model (available: " *
-        "$(vcat(collect(keys(PLANT_MODELS)), collect(keys(PLANT_ENV_MODELS)), collect(keys(PLANT_SPATIAL_MODELS)))))")
-    id, nq, nu, nc, nf, nw = haskey(PLANT_SPATIAL_MODELS, model) ? PLANT_SPATIAL_MODELS[model] :
+    haskey(PLANT_WALLED_MODELS, model) || haskey(PLANT_SPATIAL_MODELS, model) || haskey(PLANT_ENV_MODELS, model) || haskey(PLANT_MODELS, model) || error("cimpc_plant_step has no model $model (available: " *
+        "$(vcat(collect(keys(PLANT_MODELS)), collect(keys(PLANT_ENV_MODELS)), collect(keys(PLANT_SPATIAL_MODELS)), collect(keys(PLANT_WALLED_MODELS)))))")
+    id, nq, nu, nc, nf, nw = haskey(PLANT_WALLED_MODELS, model) ? PLANT_WALLED_MODELS[model] :
+                             haskey(PLANT_SPATIAL_MODELS, model) ? PLANT_SPATIAL_MODELS[model] :
                              haskey(PLANT_ENV_MODELS, model) ? PLANT_ENV_MODELS[model] : PLANT_MODELS[model]
     B = size(q0, 2)
     (size(q0, 1) == nq && size(q1) == (nq, B) && size(u) == (nu, B)) || error("plant_step($model): q0, q1 must be $nq x B and u $nu x B")
@@ -479,13 +482,14 @@ struct Terrain                                      # cimpc_terrain (field order
     off::NTuple{TERRAIN_MAX_PIECES,Cdouble}
     coef::NTuple{4 * TERRAIN_MAX_PIECES,Cdouble}
 end
-# (CIMPC_PLANT_* id, nq, nu, nc, friction directions per contact, nw) of a plant model, from the three tables above
+# (CIMPC_PLANT_* id, nq, nu, nc, friction directions per contact, nw) of a plant model, from the four tables above
 function _plant_dims(model::Symbol)
+    haskey(PLANT_WALLED_MODELS, model) && return PLANT_WALLED_MODELS[model]
     haskey(PLANT_SPATIAL_MODELS, model) && return PLANT_SPATIAL_MODELS[model]
     haskey(PLANT_ENV_MODELS, model) && return PLANT_ENV_MODELS[model]
     haskey(PLANT_MODELS, model) && return PLANT_MODELS[model]
     error("cimpc_plant_rollout has no model $model (available: " *
-          "$(vcat(collect(keys(PLANT_MODELS)), collect(keys(PLANT_ENV_MODELS)), collect(keys(PLANT_SPATIAL_MODELS)))))")
+          "$(vcat(collect(keys(PLANT_MODELS)), collect(keys(PLANT_ENV_MODELS)), collect(keys(PLANT_SPATIAL_MODELS)), collect(keys(PLANT_WALLED_MODELS)))))")
 end
 """
     plant_rollout(model, q1, v1, u, μ, h_sim, opts; N_sample = 1, w = nothing, w_hold = 1, terrain = nothing, steps = K N_sample,

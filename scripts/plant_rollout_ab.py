@@ -7,9 +7,10 @@ from the gait's own start, B in {4, 64, 512}; per pair the loop's and the rollou
 bit for bit once per leg.  Step legs (`step_legs`): one `plant_step` call per leg, a table that reaches every kernel instantiation and
 every residual of plant_model.h on flat ground and on terrain, this build against every `--step-lib NAME=PATH` (e.g. a build of the
 parent commit, and a copy of it for the spread of a build against itself), alternating per pair; the small models (B = 16) are
-compared only, not timed.  `--parent-step-us LEG=US` records a figure measured elsewhere next to them.
+compared only, not timed.  `--parent-step-us LEG=US` records a figure measured elsewhere next to them; `--legs TEXT ...` keeps the
+step legs whose name contains one of the texts.
 usage: python scripts/plant_rollout_ab.py [--pairs 5] [--calls 100] [--step-lib NAME=PATH ...] [--parent-step-us LEG=US ...]
-                                          [--no-rollout] [--out profiles/plant_rollout_ab.json]"""
+                                          [--legs TEXT ...] [--no-rollout] [--out profiles/plant_rollout_ab.json]"""
 import argparse
 import ctypes as C
 import dataclasses
@@ -98,15 +99,35 @@ def step_leg(name, model, q0, q1, u, h, mu, libs, pairs, calls, terrain=None):
     return out
 
 
-def step_legs(libs, pairs, calls):
+def walled_inputs(model, B, h, seed=0):
+    """pushbot / walledcartpole around their walls, as tests/walled_ref.py draws them: θ ~ U(-0.4, 0.4) with the arm's tip at
+    x ~ U(-0.52, 0.52), or θ ~ U(-0.7, 0.7), x ~ U(-0.1, 0.1), wall offsets ~ U(-0.01, 0.01); v, u ~ U(-1, 1), q0 = q1 - h v"""
+    rng = np.random.default_rng(seed)
+    if model == "pushbot":
+        th, x = rng.uniform(-0.4, 0.4, B), rng.uniform(-0.52, 0.52, B)
+        q1 = np.stack([th, (x + np.sin(th)) / np.cos(th)], -1)
+    else:
+        q1 = np.stack([rng.uniform(-0.7, 0.7, B), rng.uniform(-0.1, 0.1, B), rng.uniform(-0.01, 0.01, B), rng.uniform(-0.01, 0.01, B)], -1)
+    v = rng.uniform(-1.0, 1.0, q1.shape)
+    return q1 - h * v, q1, rng.uniform(-1.0, 1.0, (B, plant.model_dims(model)[2]))
+
+
+def step_legs(libs, pairs, calls, only=()):
     """quadruped, centroidal, box and wall at B = 256 and hopper_3D at B = 512, at knots spread over their gaits; the quadruped on
     terrain as tests/test_gpu_terrain.py places it (x over [0, 2.5], lifted by the height under the hip, h / 5), hopper_3D on the
-    sine as tests/test_gpu_hopper_3d.py does; the small models at B = 16 with the inputs of the terrain tests, outputs only"""
+    sine as tests/test_gpu_hopper_3d.py does; the small models at B = 16 with the inputs of the terrain tests, outputs only; pushbot
+    and walledcartpole at B = 512 and 8192 around their walls (`walled_inputs`)"""
     from contactimplicitmpc.jl_amd import terrain
     gait = lambda f: gait_io.load_gait(os.path.join(GAITS, f + ".jld2"))
     knots = lambda g, B: np.arange(B) * g.H // B
-    leg = lambda name, model, q0, q1, u, h, mu, n=calls, ter=None, timed=True: step_leg(name, model, q0, q1, u, h, mu, libs, pairs if timed else 0, n, ter)
+    def leg(name, model, q0, q1, u, h, mu, n=calls, ter=None, timed=True):
+        if only and not any(t in name for t in only):
+            return None
+        return step_leg(name, model, q0, q1, u, h, mu, libs, pairs if timed else 0, n, ter)
     out = []
+    for model, mu in (("pushbot", 0.5), ("walledcartpole", 0.1)):
+        for B in (512, 8192):
+            out.append(leg(f"{model}{B}", model, *walled_inputs(model, B, 0.02), 0.02, mu, calls if B == 512 else max(10, calls // 5)))
     fwd = gait_io.load_joint_traj(os.path.join(GAITS, "hopper_3D_gait_forward.jld2"))
     k = knots(fwd, 512)
     out.append(leg("hopper512", "hopper_3D", fwd.q[k], fwd.q[k + 1], fwd.u[k], 0.01, 1.5))
@@ -146,7 +167,7 @@ def step_legs(libs, pairs, calls):
             u[:, 1] += 3.3 * 9.81 * 0.2
         out.append(leg(model + "16 " + name, model, q1 - 0.01 * rng.uniform(-0.5, 0.5, (16, nq)), q1, u, 0.01, 0.8 if model == "hopper_2D" else 0.5,
                        ter=name, timed=False))
-    return out
+    return [o for o in out if o is not None]
 
 
 def main():
@@ -155,6 +176,7 @@ def main():
     ap.add_argument("--calls", type=int, default=100)
     ap.add_argument("--step-lib", action="append", default=[], metavar="NAME=PATH")
     ap.add_argument("--parent-step-us", action="append", default=[], metavar="LEG=US")
+    ap.add_argument("--legs", nargs="*", default=[], metavar="TEXT", help="only the step legs whose name contains one of these")
     ap.add_argument("--no-rollout", action="store_true", help="the step legs only")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plant_rollout_ab.json"))
     a = ap.parse_args()
@@ -169,7 +191,7 @@ def main():
             getattr(lib, f).restype, getattr(lib, f).argtypes = _lib.SIGNATURES[f]
         libs[name] = lib
 
-    res = {"device": torch.cuda.get_device_name(0), "pairs": a.pairs, "rollout": [], "plant_step": step_legs(libs, a.pairs, a.calls),
+    res = {"device": torch.cuda.get_device_name(0), "pairs": a.pairs, "rollout": [], "plant_step": step_legs(libs, a.pairs, a.calls, a.legs),
            "parent_step_us_from_the_command_line": dict(s.split("=", 1) for s in a.parent_step_us)}
     if not a.no_rollout:
         quad = gait_io.load_gait(os.path.join(GAITS, "quadruped_gait2.jld2"))
