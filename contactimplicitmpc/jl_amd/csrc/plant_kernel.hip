@@ -17,6 +17,7 @@
 #include "../../../include/cimpc.h"
 #include "plant_model.h"
 #include "plant_rollout_plan.h"
+#include "plant_workspace.h"
 
 namespace cimpc {
 
@@ -310,32 +311,11 @@ constexpr int NZ_WALL = PLANT_MAX_Q + 4 * PLANT_WALL_NC + 2 * PLANT_WALL_NB;    
 }  // namespace cimpc
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------
-namespace {
-// Per-device workspace of the plant entry points: buffers and a private stream live across calls (a simulator step is called
-// thousands of times in a closed loop; allocating and a device-wide synchronize per call stalled everything else on the GPU).
-// d_in: trajectory (T + 2) x B x nq | u schedule | w schedule | per-robot mu; d_out: gamma | b; d_st: status | iters (T x B each).
-struct PlantWs {
-    int device = -1;
-    hipStream_t st = nullptr;
-    double *d_in = nullptr, *d_out = nullptr;
-    int* d_st = nullptr;
-    cimpc_terrain* d_ter = nullptr;
-    size_t cap_in = 0, cap_out = 0, cap_st = 0, cap_ter = 0;
-};
-constexpr int PLANT_MAX_DEVICES = 16;
+namespace cimpc {
+// the workspace every plant entry point shares (plant_workspace.h)
 PlantWs g_plant_ws[PLANT_MAX_DEVICES];
 std::mutex g_plant_mu;
-
-template <class T>
-bool plant_grow(T** p, size_t* cap, size_t need) {
-    if (*cap >= need) return true;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *cap = 0;
-    if (hipMalloc((void**)p, need * sizeof(T)) != hipSuccess) return false;
-    *cap = need;
-    return true;
-}
-}  // namespace
+}  // namespace cimpc
 
 namespace {
 // Every entry point: validate (no device needed), pick the model, stage inputs on the device's private stream, launch the rollout's

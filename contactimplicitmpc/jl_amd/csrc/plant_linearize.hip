@@ -1,0 +1,163 @@
+// The plant models linearized on the device: LinearizedStep(s, z, θ, κ) = (r0, rz0, rθ0) of the reference
+// (src/controller/linearized_step.jl:10-31, implicit_dynamics.jl:37-50) from the residuals of plant_model.h, for N knots in one call.
+// One workgroup per knot; the nz + nθ Jacobian columns are strided over its lanes: lane c, c + NT, ... evaluates the residual on
+// dual numbers (z on Dual, θ on DualTh, κ = 0) with tangent 1 on z[c] or on θ[c - nz] and writes column c of rz0 or rθ0 - exact
+// derivatives, the scheme of plant_step_kernel's Jacobian with θ seeded too.  One plain double evaluation at the caller's κ gives r0.
+// Outputs are column-major, the layout cimpc_set_linearization takes.
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <type_traits>
+#include <vector>
+
+// No fused multiply-adds in this translation unit, the residuals of plant_model.h included: every operation rounds as IEEE double, so
+// an entry does not depend on which instantiation computed it (a flat knot of a terrain batch is the no-terrain call bit for bit)
+// and kappa leaves r0's bilinear rows by one subtraction each.  The kernel runs when tables are built, not per step.
+#pragma clang fp contract(off)
+
+#include "../../../include/cimpc.h"
+#include "plant_model.h"
+#include "plant_workspace.h"
+
+namespace cimpc {
+
+namespace {
+// The ground of an instantiation, as in plant_kernel.hip.  FLAT: plant_residual.  TERRAIN: knot k stands on
+// terrain[n_terrain == 1 ? 0 : k], staged in LDS; a flat knot (or no terrain at all) evaluates plant_residual.  ENV:
+// plant_residual_centroidal_env (box, wall).  WALLS: plant_residual_walls (pushbot, walledcartpole).
+enum { GROUND_FLAT, GROUND_TERRAIN, GROUND_ENV, GROUND_WALLS };
+
+constexpr int NZM = PLANT_MAX_Q + 4 * PLANT_NC + 2 * PLANT_NB;                       // 66
+constexpr int NTHM = 2 * PLANT_MAX_Q + PLANT_MAX_U + PLANT_NW + 2;                   // 53
+constexpr int NZ_WALL = PLANT_MAX_Q + 4 * PLANT_WALL_NC + 2 * PLANT_WALL_NB;         // 114
+constexpr int NZ_HOPPER_3D = 19, NTH_HOPPER_3D = 22;
+constexpr int NZ_WALLS = 20, NTH_WALLS = 15;                                         // walledcartpole; pushbot has 18 and 10
+constexpr int TERRAIN_WORDS = (int)(sizeof(cimpc_terrain) / sizeof(double));
+static_assert(sizeof(cimpc_terrain) % sizeof(double) == 0 && TERRAIN_WORDS <= 64, "a terrain is staged one word per lane");
+}  // namespace
+
+// Knot blockIdx.x on NT lanes.  The per-lane z, θ and r copies are sized by the instantiation (NZ, NTH).  z: N x nz, theta: N x nth;
+// r0: N x nz, rz0: N x (nz x nz), rth0: N x (nz x nth), the matrices column-major; a null output is skipped.
+template <int NZ, int NTH, int NT, int GROUND>
+__global__ __launch_bounds__(NT) void plant_linearize_kernel(PlantModel M, int N, const double* z, const double* theta,
+                                                             const cimpc_terrain* terrain, int n_terrain, double kappa, double* r0,
+                                                             double* rz0, double* rth0) {
+    static_assert(NT % 64 == 0, "whole wavefronts");
+    __shared__ double zs[NZ], ths[NTH];
+    __shared__ cimpc_terrain ter;
+    const int k = blockIdx.x, lane = threadIdx.x;
+    const int nz = M.nz(), nth = M.nth();
+    if (k >= N || nz > NZ || nth > NTH) return;                       // uniform over the workgroup
+    for (int i = lane; i < nz; i += NT) zs[i] = z[(size_t)k * nz + i];
+    for (int i = lane; i < nth; i += NT) ths[i] = theta[(size_t)k * nth + i];
+    if constexpr (GROUND == GROUND_TERRAIN) {
+        if (terrain) {
+            const double* src = reinterpret_cast<const double*>(terrain + (n_terrain == 1 ? 0 : k));
+            if (lane < TERRAIN_WORDS) reinterpret_cast<double*>(&ter)[lane] = src[lane];
+        }
+    }
+    __syncthreads();
+    bool rough = false;
+    if constexpr (GROUND == GROUND_TERRAIN) rough = terrain && (ter.kind != CIMPC_TERRAIN_FLAT || M.kind == PLANT_KIND_PARTICLE_2D);
+    auto residual = [&](const auto* zz, const auto* tt, double kap, auto* rr) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(zz)>>;
+        if constexpr (GROUND == GROUND_ENV) {
+            plant_residual_centroidal_env<T>(M, zz, tt, kap, rr);
+        } else if constexpr (GROUND == GROUND_WALLS) {
+            plant_residual_walls<T>(M, zz, tt, kap, rr);
+        } else {
+            if constexpr (GROUND == GROUND_TERRAIN) {
+                if (rough) { plant_residual_terrain<T>(M, ter, zz, tt, kap, rr); return; }
+            }
+            plant_residual<T>(M, zz, tt, kap, rr);
+        }
+    };
+    // columns [c_lo, c_hi) of [rz0 rθ0]: only the halves asked for
+    const int c_lo = rz0 ? 0 : nz, c_hi = rth0 ? nz + nth : nz;
+    for (int c = c_lo + lane; c < c_hi; c += NT) {
+        Dual zl[NZ], rl[NZ];
+        DualTh tl[NTH];
+        for (int i = 0; i < nz; ++i) zl[i] = {zs[i], i == c ? 1.0 : 0.0};
+        for (int i = 0; i < nth; ++i) tl[i] = {{ths[i], nz + i == c ? 1.0 : 0.0}};
+        residual(zl, tl, 0.0, rl);
+        double* out = c < nz ? rz0 + ((size_t)k * nz + c) * nz : rth0 + ((size_t)k * nth + (c - nz)) * nz;
+        for (int i = 0; i < nz; ++i) out[i] = rl[i].d;
+    }
+    if (r0 && lane < 64) {                                             // the first wavefront: every lane evaluates, lane i stores r0[i], r0[i + 64]
+        double zl[NZ], tl[NTH], rl[NZ];
+        for (int i = 0; i < nz; ++i) zl[i] = zs[i];
+        for (int i = 0; i < nth; ++i) tl[i] = ths[i];
+        residual(zl, tl, kappa, rl);
+        for (int i = lane; i < nz; i += 64) r0[(size_t)k * nz + i] = rl[i];
+    }
+}
+
+}  // namespace cimpc
+
+// ---- C ABI -------------------------------------------------------------------------------------------------------------
+// Validate (no device needed), pick the model and its instantiation, then on the plant workspace's private stream: one upload
+// (z | theta | terrains), one launch, one read-back (the outputs asked for), one synchronize.
+extern "C" int cimpc_plant_linearize(int model, int N, int n_terrain, const cimpc_terrain* terrain, const double* z, const double* theta,
+                                     double kappa, double* r0, double* rz0, double* rth0) {
+    using namespace cimpc;
+    if (N <= 0 || !z || !theta || (!r0 && !rz0 && !rth0) || !std::isfinite(kappa) || kappa < 0.0) return CIMPC_ERR_INVALID;
+    if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
+    PlantModel M{};
+    if (!plant_model_by_id(model, &M) || (model == CIMPC_PLANT_PARTICLE_2D && !terrain)) return CIMPC_ERR_INVALID;
+    const size_t nz = (size_t)M.nz(), nth = (size_t)M.nth();
+    for (int k = 0; k < N; ++k) if (!(theta[(size_t)k * nth + nth - 1] > 0.0)) return CIMPC_ERR_INVALID;      // h, the last entry of θ
+    bool rough = model == CIMPC_PLANT_PARTICLE_2D;
+    if (terrain) {
+        if (n_terrain != 1 && n_terrain != N) return CIMPC_ERR_INVALID;
+        for (int i = 0; i < n_terrain; ++i) {
+            if (!terrain_valid_for(M, terrain[i])) return CIMPC_ERR_INVALID;
+            rough = rough || terrain[i].kind != CIMPC_TERRAIN_FLAT;
+        }
+    }
+    // runs on the calling thread's CURRENT device, like the other plant entry points
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PLANT_MAX_DEVICES) return CIMPC_ERR_NO_DEVICE;
+    {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return CIMPC_ERR_NO_DEVICE;
+    }
+    const size_t n_z = (size_t)N * nz, n_th = (size_t)N * nth, n_ter = rough ? (size_t)n_terrain * TERRAIN_WORDS : 0;
+    const size_t n_r = r0 ? n_z : 0, n_rz = rz0 ? n_z * nz : 0, n_rth = rth0 ? n_z * nth : 0;
+    std::vector<double> in(n_z + n_th + n_ter), out(n_r + n_rz + n_rth);
+    std::memcpy(in.data(), z, n_z * sizeof(double));
+    std::memcpy(in.data() + n_z, theta, n_th * sizeof(double));
+    if (n_ter) std::memcpy(in.data() + n_z + n_th, terrain, n_ter * sizeof(double));
+    std::lock_guard<std::mutex> lock(g_plant_mu);
+    PlantWs& W = g_plant_ws[dev];
+    if (!W.st) {
+        if (hipStreamCreateWithFlags(&W.st, hipStreamNonBlocking) != hipSuccess) return CIMPC_ERR_HIP;
+        W.device = dev;
+    }
+    if (!plant_grow(&W.d_lin_in, &W.cap_lin_in, in.size()) || !plant_grow(&W.d_lin_out, &W.cap_lin_out, out.size())) return CIMPC_ERR_HIP;
+    hipStream_t st = W.st;
+    const double* dz = W.d_lin_in; const double* dth = dz + n_z;
+    const cimpc_terrain* dter = n_ter ? reinterpret_cast<const cimpc_terrain*>(dth + n_th) : nullptr;
+    double* dr = r0 ? W.d_lin_out : nullptr; double* drz = rz0 ? W.d_lin_out + n_r : nullptr; double* drth = rth0 ? W.d_lin_out + n_r + n_rz : nullptr;
+    bool ok = hipMemcpyAsync(W.d_lin_in, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) {
+        auto launch = [&](auto kernel, int nt) {
+            hipLaunchKernelGGL(kernel, dim3(N), dim3(nt), 0, st, M, N, dz, dth, dter, n_ter ? n_terrain : 0, kappa, dr, drz, drth);
+        };
+        // lanes: one pass over the columns where a workgroup of at most three wavefronts holds them (28, 35, 41 | 77, 119 | 167)
+        if (M.kind == PLANT_KIND_PUSHBOT || M.kind == PLANT_KIND_WALLEDCARTPOLE) launch(plant_linearize_kernel<NZ_WALLS, NTH_WALLS, 64, GROUND_WALLS>, 64);
+        else if (M.kind == PLANT_KIND_HOPPER_3D) launch(plant_linearize_kernel<NZ_HOPPER_3D, NTH_HOPPER_3D, 64, GROUND_TERRAIN>, 64);
+        else if (M.kind == PLANT_KIND_CENTROIDAL_BOX) launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_ENV>, 128);
+        else if (M.kind == PLANT_KIND_CENTROIDAL_WALL) launch(plant_linearize_kernel<NZ_WALL, NTHM, 192, GROUND_ENV>, 192);
+        else if (rough) launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_TERRAIN>, 128);
+        else launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_FLAT>, 128);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    if (ok) ok = hipMemcpyAsync(out.data(), W.d_lin_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
+    ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
+    if (!ok) return CIMPC_ERR_HIP;
+    if (r0) std::memcpy(r0, out.data(), n_r * sizeof(double));
+    if (rz0) std::memcpy(rz0, out.data() + n_r, n_rz * sizeof(double));
+    if (rth0) std::memcpy(rth0, out.data() + n_r + n_rz, n_rth * sizeof(double));
+    return CIMPC_OK;
+}

@@ -63,6 +63,16 @@ PLANT_HD double ptanh(double a) { return tanh(a); }
 template <class T> PLANT_HD T pconst(double a);
 template <> PLANT_HD double pconst<double>(double a) { return a; }
 template <> PLANT_HD Dual pconst<Dual>(double a) { return {a, 0.0}; }
+// θ on dual numbers (dr/dθ, plant_linearize.hip): an entry of θ is a DualTh, a Dual in every operation (an expression of θ is a
+// Dual) but one - as a divisor (the time step h) its quotient's tangent is (a' - (a / b) b') / b, which with b' = 0 is a' / b rounded
+// as Dual / double rounds it.  Sums and products are exact in a zero tangent, so the z-columns of a (Dual, DualTh) evaluation are the
+// (Dual, double) Jacobian bit for bit (tests/test_plant_linearize.py).
+struct DualTh : Dual {};
+PLANT_HD Dual operator/(Dual a, DualTh b) { const double q = a.v / b.v; return {q, (a.d - q * b.d) / b.v}; }
+// The lift of a θ-expression (type TH) into the residual's type T: with θ on dual numbers it is the identity, so
+// pconst<T>(expr of θ) serves (T, TH) = (double, double), (Dual, double) and (Dual, DualTh) as written.
+template <class T> PLANT_HD T pconst(Dual a);
+template <> PLANT_HD Dual pconst<Dual>(Dual a) { return a; }
 
 constexpr int PLANT_MAX_Q = 18, PLANT_MAX_U = 12, PLANT_MAX_BODIES = 9, PLANT_MAX_SEG = 3;
 constexpr int PLANT_NC = 4, PLANT_NB = 16, PLANT_NW = 3;     // maxima: four contacts, two (flat_2D_lc) or four (flat_3D_lc) friction directions each
@@ -98,8 +108,8 @@ struct PlantModel {
 // The rows of contact c in r(z), z = [q2; γ; b; ψ; s1; η; s2] with FD friction directions per contact (2 planar: m = [1 -1]; 4 spatial:
 // m = [1 0 -1 0; 0 1 0 -1]), given the contact's gap ϕ and tangential velocity vt (FD / 2 entries):
 //   s1 - ϕ,   η - mᵀ v_T - Eᵀψ,   s2 - (μ γ - Σ b),   γ s1 - κ,   b ∘ η - κ,   ψ s2 - κ       (simulation.jl:141-157)
-template <int FD, class T>
-PLANT_HD void plant_contact_rows(int nq, int nc, int c, const T* z, T phi, const T* vt, double mu, double kappa, T* r) {
+template <int FD, class T, class TH = double>
+PLANT_HD void plant_contact_rows(int nq, int nc, int c, const T* z, T phi, const T* vt, TH mu, double kappa, T* r) {
     const int nb = FD * nc;
     const T* gam = z + nq; const T* b = gam + nc + FD * c; const T* psi = gam + nc + nb; const T* s1 = psi + nc;
     const T* eta = s1 + nc + FD * c; const T* s2 = s1 + nc + nb;
@@ -171,15 +181,15 @@ PLANT_HD void plant_centroidal_derivatives(const PlantModel& M, const T* v, T* d
 }
 // dyn += B(qm2)^T u: (sum u_i, sum R^T skew(r_i) u_i, -u_1 .. -u_4), centroidal_quadruped/model.jl:98-121 (the box and the wall
 // share it, centroidal_quadruped_box/model.jl:109-131, centroidal_quadruped_wall/model.jl:102-124)
-template <class T>
-PLANT_HD void plant_centroidal_actuation(const T* qm2, const double* u1, T* dyn) {
+template <class T, class TH = double>
+PLANT_HD void plant_centroidal_actuation(const T* qm2, const TH* u1, T* dyn) {
     const T sa = psin(qm2[3]), ca = pcos(qm2[3]), sb = psin(qm2[4]), cb = pcos(qm2[4]), sc = psin(qm2[5]), cc = pcos(qm2[5]);
     T R[3][3];
     R[0][0] = ca * cb; R[0][1] = ca * sb * sc - sa * cc; R[0][2] = ca * sb * cc + sa * sc;
     R[1][0] = sa * cb; R[1][1] = sa * sb * sc + ca * cc; R[1][2] = sa * sb * cc - ca * sc;
     R[2][0] = -sb;     R[2][1] = cb * sc;                R[2][2] = cb * cc;
     for (int f = 0; f < 4; ++f) {
-        const double ux = u1[3 * f], uy = u1[3 * f + 1], uz = u1[3 * f + 2];
+        const TH ux = u1[3 * f], uy = u1[3 * f + 1], uz = u1[3 * f + 2];
         const T rx = qm2[6 + 3 * f] - qm2[0], ry = qm2[7 + 3 * f] - qm2[1], rz = qm2[8 + 3 * f] - qm2[2];
         // skew(r) u = r x u
         const T cx = ry * uz - rz * uy, cy = rz * ux - rx * uz, cz = rx * uy - ry * ux;
@@ -189,11 +199,11 @@ PLANT_HD void plant_centroidal_actuation(const T* qm2, const double* u1, T* dyn)
     }
 }
 // the dynamics rows before the contact forces: integrator (dynamics/model.jl:11-36) with the joint damping, B(qm2)^T u and A^T w
-template <class T>
-PLANT_HD void plant_centroidal_dynamics(const PlantModel& M, const T* q2, const double* th, T* dyn) {
+template <class T, class TH = double>
+PLANT_HD void plant_centroidal_dynamics(const PlantModel& M, const T* q2, const TH* th, T* dyn) {
     constexpr int nq = 18, nu = 12;
-    const double* q0 = th; const double* q1 = th + nq; const double* u1 = th + 2 * nq; const double* w1 = u1 + nu;
-    const double h = w1[4];
+    const TH* q0 = th; const TH* q1 = th + nq; const TH* u1 = th + 2 * nq; const TH* w1 = u1 + nu;
+    const TH h = w1[4];
     T qm2[nq], vm1[nq], vm2[nq];
     for (int i = 0; i < nq; ++i) { vm1[i] = pconst<T>((q1[i] - q0[i]) / h); qm2[i] = (q2[i] + q1[i]) * 0.5; vm2[i] = (q2[i] - q1[i]) / h; }
     T a1[nq], b1[nq], a2[nq], b2[nq];
@@ -208,10 +218,10 @@ PLANT_HD void plant_centroidal_dynamics(const PlantModel& M, const T* q2, const 
 // centroidal_quadruped: the four feet on the floor, phi_i = p_z,i.  It equals plant_residual_centroidal_env on this model bit for bit
 // (tests/test_centroidal_wall_box.py) and stays a function of its own with compile-time loops: through the env function the FLAT
 // kernel measured 2.4 % slower, and with a compile-time contact count there the TERRAIN kernel's scratch grew.
-template <class T>
-PLANT_HD void plant_residual_centroidal(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
+template <class T, class TH = double>
+PLANT_HD void plant_residual_centroidal(const PlantModel& M, const T* z, const TH* th, double kappa, T* r) {
     constexpr int nq = 18, nc = 4;
-    const double* q1 = th + nq; const double mu = th[2 * nq + 12 + 3], h = th[2 * nq + 12 + 4];
+    const TH* q1 = th + nq; const TH mu = th[2 * nq + 12 + 3], h = th[2 * nq + 12 + 4];
     const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc;
     T dyn[nq];
     plant_centroidal_dynamics(M, q2, th, dyn);
@@ -240,11 +250,11 @@ template <class T>
 PLANT_HD T plant_box_elevation(T x) {
     return 0.1 * (1.0 + ptanh(200.0 * (x - 0.25)));
 }
-template <class T>
-PLANT_HD void plant_residual_centroidal_env(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
+template <class T, class TH = double>
+PLANT_HD void plant_residual_centroidal_env(const PlantModel& M, const T* z, const TH* th, double kappa, T* r) {
     constexpr int nq = 18;
     const int nc = M.nc;
-    const double* q1 = th + nq; const double mu = th[2 * nq + 12 + 3], h = th[2 * nq + 12 + 4];
+    const TH* q1 = th + nq; const TH mu = th[2 * nq + 12 + 3], h = th[2 * nq + 12 + 4];
     const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc;
     T dyn[nq];
     plant_centroidal_dynamics(M, q2, th, dyn);
@@ -252,7 +262,7 @@ PLANT_HD void plant_residual_centroidal_env(const PlantModel& M, const T* z, con
         const int f = c & 3;                                          // the foot of contact c
         const T* bc = b + 4 * c;
         const T t1 = bc[0] - bc[2], t2 = bc[1] - bc[3];                // m b
-        const T* p2 = q2 + 6 + 3 * f; const double* p1 = q1 + 6 + 3 * f;
+        const T* p2 = q2 + 6 + 3 * f; const TH* p1 = q1 + 6 + 3 * f;
         T phi, vt[2];
         if (c < 4) {                                                   // floor: force (m b; gamma) on the foot's own coordinates, velocity (v_x, v_y)
             dyn[6 + 3 * f] = dyn[6 + 3 * f] + t1;
@@ -362,10 +372,11 @@ PLANT_HD void terrain_frame_3d(const cimpc_terrain& E, T x, T y, T& surf, T R[3]
 // B = A = J = I, four friction directions.  mass[0] = m.  ROUGH = false is flat_3D_lc (E unused); ROUGH = true is a 3-D surface
 // (particle/model.jl:58-109): force R^T [m b; γ], tangential velocity (R v)[0:2], ϕ = z - surf(x, y).  The ground is a compile-time
 // choice, as for the chains: behind a run-time branch the device compiler contracts these rows differently.
-template <bool ROUGH, class T>
-PLANT_HD void plant_residual_particle(const PlantModel& M, const cimpc_terrain* E, const T* z, const double* th, double kappa, T* r) {
-    const double* q0 = th; const double* q1 = th + 3; const double* u1 = th + 6; const double* w1 = th + 9;
-    const double mu = th[12], h = th[13], m = M.mass[0];
+template <bool ROUGH, class T, class TH = double>
+PLANT_HD void plant_residual_particle(const PlantModel& M, const cimpc_terrain* E, const T* z, const TH* th, double kappa, T* r) {
+    const TH* q0 = th; const TH* q1 = th + 3; const TH* u1 = th + 6; const TH* w1 = th + 9;
+    const TH mu = th[12], h = th[13];
+    const double m = M.mass[0];
     const T* q2 = z; const T* gam = z + 3; const T* b = z + 4;
     T surf{}, R[3][3];
     if constexpr (ROUGH) terrain_frame_3d(*E, q2[0], q2[1], surf, R);
@@ -388,10 +399,11 @@ PLANT_HD void plant_residual_particle(const PlantModel& M, const cimpc_terrain* 
 
 // particle_2D (src/dynamics/particle_2D/model.jl): q = (x, z), M = m I, C = (0, m g), B = A = J = I, one contact (the particle)
 // with two friction directions.  mass[0] = m.  Also its flat case: the model has no cimpc_plant_step path.
-template <class T>
-PLANT_HD void plant_residual_particle_2d(const PlantModel& M, const cimpc_terrain& E, const T* z, const double* th, double kappa, T* r) {
-    const double* q0 = th; const double* q1 = th + 2; const double* u1 = th + 4; const double* w1 = th + 6;
-    const double mu = th[8], h = th[9], m = M.mass[0];
+template <class T, class TH = double>
+PLANT_HD void plant_residual_particle_2d(const PlantModel& M, const cimpc_terrain& E, const T* z, const TH* th, double kappa, T* r) {
+    const TH* q0 = th; const TH* q1 = th + 2; const TH* u1 = th + 4; const TH* w1 = th + 6;
+    const TH mu = th[8], h = th[9];
+    const double m = M.mass[0];
     const T* q2 = z; const T* gam = z + 2; const T* b = z + 3;
     T surf, c, s;
     terrain_frame_2d(E, q2[0], surf, c, s);
@@ -445,11 +457,11 @@ PLANT_HD void plant_mrp_axis(const T* p, T a[3], T D[3][3]) {
 // Both grounds: E = nullptr (or a flat E) is flat_3D_lc, surface rotation = identity; otherwise surface and rotation are taken at
 // the foot k[0:2] as the particle takes them at itself: force Rs^T [m b; γ], tangential velocity (Rs J (q2 - q1) / h)[0:2],
 // ϕ = k_z - surf(k_x, k_y) (:50-52, :75-87).
-template <class T>
-PLANT_HD void plant_residual_hopper_3d(const PlantModel& M, const cimpc_terrain* E, const T* z, const double* th, double kappa, T* r) {
+template <class T, class TH = double>
+PLANT_HD void plant_residual_hopper_3d(const PlantModel& M, const cimpc_terrain* E, const T* z, const TH* th, double kappa, T* r) {
     constexpr int nq = 7;
-    const double* q0 = th; const double* q1 = th + 7; const double* u1 = th + 14; const double* w1 = th + 17;
-    const double mu = th[20], h = th[21];
+    const TH* q0 = th; const TH* q1 = th + 7; const TH* u1 = th + 14; const TH* w1 = th + 17;
+    const TH mu = th[20], h = th[21];
     const T* q2 = z; const T* gam = z + 7; const T* b = z + 8;
     T qm2[nq], vm2[nq], dyn[nq];
     for (int i = 0; i < nq; ++i) { qm2[i] = (q2[i] + q1[i]) * 0.5; vm2[i] = (q2[i] - q1[i]) / h; }
@@ -525,13 +537,14 @@ PLANT_HD void plant_walls_derivatives(const PlantModel& M, const T* q, const T* 
     d1[2] = -((2.0 * k) * q[2]);
     d1[3] = -((2.0 * k) * q[3]);
 }
-template <class T>
-PLANT_HD void plant_residual_walls(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
+template <class T, class TH = double>
+PLANT_HD void plant_residual_walls(const PlantModel& M, const T* z, const TH* th, double kappa, T* r) {
     constexpr int MQ = 4, nc = 2;
     const int nq = M.nq, nu = M.nu;
     const bool push = M.kind == PLANT_KIND_PUSHBOT;
-    const double* q0 = th; const double* q1 = th + nq; const double* u1 = th + 2 * nq; const double* w1 = u1 + nu;
-    const double mu = w1[M.nw], h = w1[M.nw + 1], l = M.inertia[0], wall = M.inertia[1];
+    const TH* q0 = th; const TH* q1 = th + nq; const TH* u1 = th + 2 * nq; const TH* w1 = u1 + nu;
+    const TH mu = w1[M.nw], h = w1[M.nw + 1];
+    const double l = M.inertia[0], wall = M.inertia[1];
     const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc;
     T qm1[MQ]{}, vm1[MQ]{}, qm2[MQ]{}, vm2[MQ]{};       // pushbot fills two of the four
     for (int i = 0; i < nq; ++i) {
@@ -574,17 +587,19 @@ PLANT_HD void plant_residual_walls(const PlantModel& M, const T* z, const double
     for (int i = 0; i < nq; ++i) r[i] = dyn[i];
 }
 
-// ---- planar chains and hopper_2D: r(z, θ, κ), z = [q2; γ; b; ψ; s1; η; s2], θ = [q0; q1; u1; w1; μ; h] (θ real: only dr/dz is needed).
+// ---- planar chains and hopper_2D: r(z, θ, κ), z = [q2; γ; b; ψ; s1; η; s2], θ = [q0; q1; u1; w1; μ; h].
+// θ has a type of its own, TH: double (the default) where only dr/dz is needed (the step kernel), Dual where dr/dθ is too
+// (plant_linearize.hip); every residual above takes it the same way.
 // ROUGH = false is flat ground (E unused): ϕ = p_z, force [m b; γ], tangential velocity v_x.  ROUGH = true, on terrain E, has per
 // contact i at foot p_i ϕ_i = p_z - surf(p_x), the world force R_i^T [m b_i; γ_i] through both Jacobian rows of the foot and the
 // tangential velocity (R_i J_i (q2 - q1) / h)[1] (simulation.jl:133-158, contact_methods.jl, quadruped/model.jl:472-492,
 // hopper_2D/model.jl:54-85).  Each contact's rotation is taken at its own foot.
-template <bool ROUGH, class T>
-PLANT_HD void plant_residual_chain(const PlantModel& M, const cimpc_terrain* E, const T* z, const double* th, double kappa, T* r) {
+template <bool ROUGH, class T, class TH = double>
+PLANT_HD void plant_residual_chain(const PlantModel& M, const cimpc_terrain* E, const T* z, const TH* th, double kappa, T* r) {
     const int nq = M.nq, nu = M.nu, nc = M.nc;
     const bool hopper = M.kind == PLANT_KIND_HOPPER_2D;
-    const double* q0 = th; const double* q1 = th + nq; const double* u1 = th + 2 * nq; const double* w1 = u1 + nu;
-    const double mu = w1[M.nw], h = w1[M.nw + 1];
+    const TH* q0 = th; const TH* q1 = th + nq; const TH* u1 = th + 2 * nq; const TH* w1 = u1 + nu;
+    const TH mu = w1[M.nw], h = w1[M.nw + 1];
     const T* q2 = z; const T* gam = z + nq; const T* b = gam + nc;
     T qm1[PLANT_MAX_Q], vm1[PLANT_MAX_Q], qm2[PLANT_MAX_Q], vm2[PLANT_MAX_Q];
     for (int i = 0; i < nq; ++i) {
@@ -659,8 +674,8 @@ PLANT_HD void plant_residual_chain(const PlantModel& M, const cimpc_terrain* E, 
 
 // The flat entry: every model cimpc_plant_step has (particle_2D has none; the box and the wall call plant_residual_centroidal_env,
 // pushbot and walledcartpole plant_residual_walls).
-template <class T>
-PLANT_HD void plant_residual(const PlantModel& M, const T* z, const double* th, double kappa, T* r) {
+template <class T, class TH = double>
+PLANT_HD void plant_residual(const PlantModel& M, const T* z, const TH* th, double kappa, T* r) {
     if (M.kind == PLANT_KIND_CENTROIDAL) { plant_residual_centroidal<T>(M, z, th, kappa, r); return; }
     if (M.kind == PLANT_KIND_PARTICLE) { plant_residual_particle<false, T>(M, nullptr, z, th, kappa, r); return; }
     if (M.kind == PLANT_KIND_HOPPER_3D) { plant_residual_hopper_3d<T>(M, nullptr, z, th, kappa, r); return; }
@@ -668,8 +683,8 @@ PLANT_HD void plant_residual(const PlantModel& M, const T* z, const double* th, 
 }
 // The terrain entry: planar chains, hopper_2D, particle_2D and (3-D kinds) particle and hopper_3D; the centroidal models are
 // refused by the caller.
-template <class T>
-PLANT_HD void plant_residual_terrain(const PlantModel& M, const cimpc_terrain& E, const T* z, const double* th, double kappa, T* r) {
+template <class T, class TH = double>
+PLANT_HD void plant_residual_terrain(const PlantModel& M, const cimpc_terrain& E, const T* z, const TH* th, double kappa, T* r) {
     if (M.kind == PLANT_KIND_PARTICLE) { plant_residual_particle<true, T>(M, &E, z, th, kappa, r); return; }
     if (M.kind == PLANT_KIND_PARTICLE_2D) { plant_residual_particle_2d<T>(M, E, z, th, kappa, r); return; }
     if (M.kind == PLANT_KIND_HOPPER_3D) { plant_residual_hopper_3d<T>(M, &E, z, th, kappa, r); return; }

@@ -19,7 +19,8 @@ definitions and differentiates it with torch (fp64, CPU, `torch.func` - exact de
   reference traj.   src/controller/trajectory.jl:152-184    (`get_trajectory`, :split_traj_alt)
 
 It is host-side input preparation (the reference does it once per knot at policy build) - not
-part of the timed path.  Environments: flat ground only (`flat_2D_lc`, `flat_3D_lc`: surface rotation = identity).
+part of the timed path.  Its device twin is `plant.linearize` (`cimpc_plant_linearize`: the same triple from the residuals of
+`csrc/plant_model.h` on dual numbers); `reference_problem(..., linearize=plant.linearizer(name))` builds the tables with it.  Environments: flat ground only (`flat_2D_lc`, `flat_3D_lc`: surface rotation = identity).
 """
 from __future__ import annotations
 
@@ -552,10 +553,12 @@ class ReferenceProblem:
     rth0: np.ndarray       # (H, nz, nθ)
 
 
-def reference_problem(model: ContactModel, gait, kappa: float, update_friction: bool = False) -> ReferenceProblem:
+def reference_problem(model: ContactModel, gait, kappa: float, update_friction: bool = False, linearize=None) -> ReferenceProblem:
     """`get_trajectory(...; load_type = :split_traj_alt)` (trajectory.jl:169-180) followed by the `LinearizedStep`
     of every knot at κ (`ImplicitTrajectory`, implicit_dynamics.jl:37-50).  `update_friction`:
-    `update_friction_coefficient!` (trajectory.jl:133-141) - θ carries the model's μ_world instead of the file's μ."""
+    `update_friction_coefficient!` (trajectory.jl:133-141) - θ carries the model's μ_world instead of the file's μ.
+    `linearize`: a callable `(z, th, kappa) -> (r0, rz0, rth0)` over the stacked knots; None is `model.linearize_batch` (torch, host),
+    `plant.linearizer(name)` is its device twin."""
     H = gait.H
     if update_friction:
         import dataclasses
@@ -563,7 +566,7 @@ def reference_problem(model: ContactModel, gait, kappa: float, update_friction: 
     w = np.zeros((H, model.nw))
     z = np.stack([model.pack_z(gait.q[t + 2], gait.gamma[t], gait.b[t], gait.psi[t], gait.eta[t]) for t in range(H)])
     th = np.stack([model.pack_theta(gait.q[t], gait.q[t + 1], gait.u[t], w[t], gait.mu, gait.h) for t in range(H)])
-    r0, rz0, rth0 = model.linearize_batch(z, th, kappa)
+    r0, rz0, rth0 = (linearize or model.linearize_batch)(z, th, kappa)
     return ReferenceProblem(model, H, gait.h, kappa, gait.q.copy(), gait.u.copy(), w, gait.gamma.copy(), gait.b.copy(), z, th,
                             r0, rz0, rth0)
 
@@ -578,9 +581,9 @@ def constant_reference(model: ContactModel, q_ref, H: int, h: float):
                 mu=float(model.mu_world), h=float(h))
 
 
-def reference_problem_from_traj(model: ContactModel, traj, kappa: float) -> ReferenceProblem:
+def reference_problem_from_traj(model: ContactModel, traj, kappa: float, linearize=None) -> ReferenceProblem:
     """The same from a serialized ContactTraj (`load_type = :joint_traj`: z and θ come from the file as they are)."""
-    r0, rz0, rth0 = model.linearize_batch(traj.z, traj.theta, kappa)
+    r0, rz0, rth0 = (linearize or model.linearize_batch)(traj.z, traj.theta, kappa)
     return ReferenceProblem(model, traj.H, traj.h, kappa, traj.q.copy(), traj.u.copy(), traj.w.copy(), traj.gamma.copy(),
                             traj.b.copy(), traj.z.copy(), traj.theta.copy(), r0, rz0, rth0)
 

@@ -251,3 +251,42 @@ def rollout(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w
     if rc != 0:
         raise _lib.CimpcError(f"cimpc_plant_rollout failed ({rc})")
     return bool(st.all()), q, u_applied, g, b, st, it
+
+
+def linearize(model: str, z, theta, kappa: float, terrain=None):
+    """`LinearizedStep(s, z, θ, κ)` of N knots on the device (`cimpc_plant_linearize`): the residual of `csrc/plant_model.h` and its
+    exact derivatives (dual numbers, one Jacobian column per lane).  z (N, nz), theta (N, nθ) in the model's own
+    z = [q2; γ; b; ψ; s1; η; s2], θ = [q0; q1; u1; w1; μ; h] -> r0 (N, nz), rz0 (N, nz, nz), rth0 (N, nz, nθ), row-major: the shapes and
+    index order of `ContactModel.linearize_batch`.  A single knot (1-D z) returns unbatched arrays, like `ContactModel.linearize`.
+    terrain: None (flat ground), or a terrain name / `terrain.Terrain` shared by every knot, or a sequence of N of them, with the
+    model pairing of `plant_step`."""
+    if terrain is None and model in TERRAIN_MODELS:
+        terrain = "flat_2D_lc"
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    nz, nth = nq + 4 * nc + 2 * fd * nc, 2 * nq + nu + nw + 2
+    single = np.ndim(z) == 1
+    za = np.ascontiguousarray(np.asarray(z, dtype=np.float64).reshape(-1, nz))
+    ta = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(-1, nth))
+    N = za.shape[0]
+    if N < 1 or ta.shape[0] != N:
+        raise ValueError(f"z must be (N, {nz}) and theta (N, {nth}) with the same N >= 1")
+    lib = _lib.load()
+    r0 = np.zeros((N, nz)); rz = np.zeros((N, nz, nz)); rth = np.zeros((N, nth, nz))      # the library's matrices are column-major
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    ter, nt = (None, 0) if terrain is None else _terrain_array(terrain, N)
+    rc = lib.cimpc_plant_linearize(mid, N, nt, ter, dp(za), dp(ta), float(kappa), dp(r0), dp(rz), dp(rth))
+    if rc != 0:
+        raise _lib.CimpcError(f"cimpc_plant_linearize failed ({rc})")
+    rz0, rth0 = np.ascontiguousarray(rz.transpose(0, 2, 1)), np.ascontiguousarray(rth.transpose(0, 2, 1))
+    return (r0[0], rz0[0], rth0[0]) if single else (r0, rz0, rth0)
+
+
+def linearizer(model_name: str, terrain=None):
+    """A `(z, th, kappa) -> (r0, rz0, rth0)` over the device for `lcp_models.reference_problem(..., linearize=...)`: `linearize` of
+    `model_name` (on `terrain`, shared by every knot or one per knot).  The device models are the reference's parameter tables
+    (`csrc/plant_model.h`): a `ContactModel` built with other parameters must keep the torch path (`ContactModel.linearize_batch`)."""
+    model_dims(model_name)      # an unknown model is refused here, not at the first call
+
+    def run(z, th, kappa):
+        return linearize(model_name, z, th, kappa, terrain=terrain)
+    return run

@@ -412,6 +412,22 @@ int cimpc_plant_rollout(int model, int B, int T, int steps_per_launch,
                         const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
                         double* q, double* gamma, double* b, int* status, int* iters);
 
+/* ---- the plant models linearized: LinearizedStep(s, z, theta, kappa) = (r0, rz0, rtheta0) for N knots in one call
+ * (src/controller/linearized_step.jl:10-31, implicit_dynamics.jl:37-50) -------------------------------------------------------------
+ * The residual r(z, theta, kappa) of simulation.jl:133-158 as cimpc_plant_step solves it, and its exact derivatives dr/dz, dr/dtheta
+ * (dual numbers, one column per lane) at every knot: what cimpc_set_linearization takes.  z: N x nz and theta: N x ntheta, host arrays in
+ * the model's own z = [q2; gamma; b; psi; s1; eta; s2] (nz = nq + 4 nc + 2 nb) and theta = [q0; q1; u1; w1; mu; h] (ntheta = 2 nq + nu +
+ * nw + 2).  Outputs: r0 N x nz, rz0 N x (nz x nz), rth0 N x (nz x ntheta), each knot's matrix COLUMN-major, so one knot's block can be
+ * handed to cimpc_set_linearization unchanged; any one may be NULL (skipped), not all three.  kappa enters r0 alone (the bilinear
+ * rows); the derivatives do not depend on it.  terrain: n_terrain = 0 and NULL (flat ground), or 1 or N terrains (knot k on
+ * terrain[k]) with the model pairing of cimpc_plant_step_terrain; particle_2D requires one.  Validated first, without a device
+ * (CIMPC_ERR_INVALID): unknown model, N < 1, null z or theta, no output, kappa negative or not finite, a knot's h <= 0, the terrain
+ * count and pairing.  Runs on the calling thread's current device on the plant's private stream: one upload, one launch, one
+ * read-back. */
+int cimpc_plant_linearize(int model, int N, int n_terrain, const cimpc_terrain* terrain,
+                          const double* z, const double* theta, double kappa,
+                          double* r0, double* rz0, double* rth0);
+
 #ifdef __cplusplus
 }
 #endif

@@ -534,6 +534,30 @@ function plant_rollout(model::Symbol, q1::Matrix{Float64}, v1::Matrix{Float64}, 
     return all(status .== 1), q, u_applied, γ, b, status, iters
 end
 
+# ---- the plant models linearized on the device: the `LinearizedStep` triple of N knots in one call (linearized_step.jl:10-31) --------
+"""
+    plant_linearize(model, z, θ, κ; terrain = nothing) -> (r0, rz0, rθ0)
+
+z: nz x N and θ: nθ x N (a vector is one knot), in the model's own z = [q2; γ; b; ψ; s1; η; s2] and θ = [q0; q1; u1; w1; μ; h].
+Returns r0: nz x N, rz0: nz x nz x N, rθ0: nz x nθ x N - `rz0[:, :, k]` and `rθ0[:, :, k]` are the matrices `LinearizedStep` holds
+and `set_linearization!` takes.  terrain: nothing (flat ground) or a vector of 1 or N `Terrain`.  The device models carry the
+reference's parameter tables.  Sizes are checked against the model's table; unknown models are an error.
+"""
+function plant_linearize(model::Symbol, z::VecOrMat{Float64}, θ::VecOrMat{Float64}, κ::Real;
+                         terrain::Union{Nothing,Vector{Terrain}} = nothing)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    nz = nq + 4 * nc + 2 * nf * nc; nθ = 2 * nq + nu + nw + 2
+    zs = reshape(z, size(z, 1), :); θs = reshape(θ, size(θ, 1), :)
+    N = size(zs, 2)
+    (size(zs, 1) == nz && size(θs) == (nθ, N) && N >= 1) || error("plant_linearize($model): z must be $nz x N and θ $nθ x N")
+    (terrain === nothing || length(terrain) in (1, N)) || error("plant_linearize($model): one terrain or one per knot")
+    r0 = zeros(nz, N); rz0 = zeros(nz, nz, N); rθ0 = zeros(nz, nθ, N)
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    check(@ccall LIB.cimpc_plant_linearize(id::Cint, N::Cint, n_ter::Cint, ter::Ptr{Terrain}, zs::Ptr{Cdouble}, θs::Ptr{Cdouble},
+                                           κ::Cdouble, r0::Ptr{Cdouble}, rz0::Ptr{Cdouble}, rθ0::Ptr{Cdouble})::Cint)
+    return r0, rz0, rθ0
+end
+
 end # module
 
 # executed in the INCLUDING module (ContactImplicitMPC): `eval(opts.solver)` of newton.jl:86 looks the constructor up there
