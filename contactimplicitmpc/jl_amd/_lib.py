@@ -73,6 +73,9 @@ SIGNATURES = {
     "cimpc_set_stream": (C.c_int, [_h, C.c_void_p]),
     "cimpc_synchronize": (C.c_int, [_h]),
     "cimpc_set_linearization": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "cimpc_set_linearization_batch": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "cimpc_linearize_knots": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, C.c_double]),
+    "cimpc_get_table": (C.c_int, [_h, C.c_int, _dp]),
     "cimpc_set_objective": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "cimpc_set_altitude": (C.c_int, [_h, _dp]),
     "cimpc_set_window": (C.c_int, [_h, _ip]),

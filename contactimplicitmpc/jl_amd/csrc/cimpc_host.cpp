@@ -14,8 +14,10 @@
 
 #include "cimpc_internal.h"
 #include "lin_table.h"
+#include "lin_table_build.h"
 #include "model_table.h"
 #include "newton_state.h"
+#include "plant_linearize.h"
 #include "schedule_plan.h"
 
 using namespace cimpc;
@@ -161,6 +163,10 @@ struct cimpc_ctx {
     RoundStreams rs;
     bool external_stream = false;
     std::vector<double> h_tab;       // one knot staging
+    // device table build (cimpc_set_linearization_batch, cimpc_linearize_knots), grow-only: z0 | th0 | terrains | r0 | rz0 | rth0 of
+    // the call's knots, their tables as built (committed to d_tab only when every knot's Dx could be inverted), one status word each
+    double* d_tb = nullptr;
+    size_t tb_cap = 0;
     cimpc_stats last_stats{};
     // profiling
     int prof_on = 0;             // 0 off, 1 every launch, 2 the interior-point sweep launches only (cimpc_profile_enable)
@@ -420,7 +426,7 @@ int check_ready(cimpc_ctx* h, bool need_newton) {
 
 extern "C" {
 
-int cimpc_version(void) { return 106; }      // 1.06: round 6 (+ cimpc_mpc_solve; no struct changed).  1.05: round 5 (+ cimpc_get_kkt_twisted; no struct changed).  1.04: round 4 (cimpc_ip_opts::max_time - the struct grew by one double at its end)
+int cimpc_version(void) { return 107; }      // 1.07: + cimpc_set_linearization_batch, cimpc_linearize_knots, cimpc_get_table (no struct changed).  1.06: round 6 (+ cimpc_mpc_solve; no struct changed).  1.05: round 5 (+ cimpc_get_kkt_twisted; no struct changed).  1.04: round 4 (cimpc_ip_opts::max_time - the struct grew by one double at its end)
 
 void cimpc_default_ip_opts(cimpc_ip_opts* o) {
     if (!o) return;
@@ -643,6 +649,7 @@ int cimpc_destroy(cimpc_handle h) {
     for (auto& r : h->prof_recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : h->ev_pool) (void)hipEventDestroy(e);
     for (void* p : h->allocs) (void)hipFree(p);
+    if (h->d_tb) (void)hipFree(h->d_tb);
     if (h->h_counters) (void)hipHostFree(h->h_counters);
     if (h->h_ring) (void)hipHostFree(h->h_ring);
     if (h->h_qin) (void)hipHostFree(h->h_qin);
@@ -767,6 +774,94 @@ int cimpc_set_linearization(cimpc_handle h, int t, const double* z0, const doubl
     HIP_TRY(h, hipMemcpy(h->d_tab + (size_t)(t - 1) * L.size, T.data(), (size_t)L.size * sizeof(double),
                          hipMemcpyHostToDevice));
     if (!h->knot_set[t - 1]) { h->knot_set[t - 1] = 1; h->n_knots_set++; }
+    return CIMPC_OK;
+}
+
+namespace {
+
+// The device table build behind cimpc_set_linearization_batch (model < 0: r0, rz0, rth0 come from the host) and
+// cimpc_linearize_knots (model >= 0: they are linearized on the device from z0, th0): one upload, the kernels on the handle's stream,
+// N status words back, then - only if no knot was refused - one device-to-device copy into the handle's tables.
+int build_tables_on_device(cimpc_ctx* h, int t0, int N, const double* z0, const double* th0, const double* r0, const double* rz0,
+                           const double* rth0, int model, int n_ter_up, int n_terrain, const cimpc_terrain* terrain, double kappa) {
+    if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
+    const size_t nz = h->nz, nth = h->nth;
+    const LinLayout L(h->nx, h->ny, h->nth, h->ki.G, h->ki.generic ? 0 : h->nths, h->ki.generic ? 0 : h->ki.adj);
+    if (L.size != h->ki.tab_size) return fail(h, CIMPC_ERR_STATE, "table layout of the library and of the kernel differ");
+    constexpr size_t TW = sizeof(cimpc_terrain) / sizeof(double);
+    const size_t n_z = (size_t)N * nz, n_th = (size_t)N * nth, n_ter = (size_t)n_ter_up * TW;
+    const size_t o_th = n_z, o_ter = o_th + n_th, o_r = o_ter + n_ter, o_rz = o_r + n_z, o_rth = o_rz + n_z * nz;
+    const size_t o_tab = o_rth + n_z * nth, o_st = o_tab + (size_t)N * L.size, total = o_st + ((size_t)N + 1) / 2;
+    const size_t n_up = model >= 0 ? o_r : o_tab;                  // what goes up: the inputs alone, or the triple too
+    std::vector<double> up(n_up);
+    std::memcpy(up.data(), z0, n_z * sizeof(double));
+    std::memcpy(up.data() + o_th, th0, n_th * sizeof(double));
+    if (n_ter) std::memcpy(up.data() + o_ter, terrain, n_ter * sizeof(double));
+    if (model < 0) {
+        std::memcpy(up.data() + o_r, r0, n_z * sizeof(double));
+        std::memcpy(up.data() + o_rz, rz0, n_z * nz * sizeof(double));
+        std::memcpy(up.data() + o_rth, rth0, n_z * nth * sizeof(double));
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (h->tb_cap < total) {
+        if (h->d_tb) (void)hipFree(h->d_tb);
+        h->d_tb = nullptr; h->tb_cap = 0;
+        HIP_TRY(h, hipMalloc((void**)&h->d_tb, total * sizeof(double)));
+        h->tb_cap = total;
+    }
+    double* D = h->d_tb;
+    int* d_status = reinterpret_cast<int*>(D + o_st);
+    hipStream_t st = h->stream;
+    HIP_TRY(h, hipMemcpyAsync(D, up.data(), n_up * sizeof(double), hipMemcpyHostToDevice, st));
+    bool launched = true;
+    if (model >= 0)
+        launched = plant_linearize_launch(model, N, D, D + o_th, n_ter ? reinterpret_cast<const cimpc_terrain*>(D + o_ter) : nullptr, n_terrain,
+                                          kappa, D + o_r, D + o_rz, D + o_rth, st);
+    launched = launched && lin_table_build_launch(L, N, D, D + o_th, D + o_r, D + o_rz, D + o_rth, D + o_tab, d_status, st);
+    if (!launched) {
+        (void)hipStreamSynchronize(st);
+        return fail(h, CIMPC_ERR_HIP, "the table build could not be launched");
+    }
+    std::vector<int> status(N);
+    HIP_TRY(h, hipMemcpyAsync(status.data(), d_status, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    for (int k = 0; k < N; ++k)
+        if (status[k] != 0) return fail(h, CIMPC_ERR_INVALID, "Dx = rz0[idyn, ix] is singular at knot " + std::to_string(t0 + k) + "; no knot was changed");
+    HIP_TRY(h, hipMemcpyAsync(h->d_tab + (size_t)(t0 - 1) * L.size, D + o_tab, (size_t)N * L.size * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    for (int t = t0; t < t0 + N; ++t)
+        if (!h->knot_set[t - 1]) { h->knot_set[t - 1] = 1; h->n_knots_set++; }
+    return CIMPC_OK;
+}
+
+}  // namespace
+
+int cimpc_set_linearization_batch(cimpc_handle h, int t0, int N, const double* z0, const double* th0,
+                                  const double* r0, const double* rz0, const double* rth0) {
+    if (!h || !z0 || !th0 || !r0 || !rz0 || !rth0) return fail(h, CIMPC_ERR_INVALID, "null argument");
+    if (t0 < 1 || N < 1 || N > h->dm.H_ref || t0 - 1 > h->dm.H_ref - N) return fail(h, CIMPC_ERR_INVALID, "knot range out of the table (1-based)");
+    return build_tables_on_device(h, t0, N, z0, th0, r0, rz0, rth0, -1, 0, 0, nullptr, 0.0);
+}
+
+int cimpc_linearize_knots(cimpc_handle h, int model, int t0, int N, int n_terrain, const cimpc_terrain* terrain,
+                          const double* z, const double* theta, double kappa) {
+    if (!h || !z || !theta) return fail(h, CIMPC_ERR_INVALID, "null argument");
+    if (t0 < 1 || N < 1 || N > h->dm.H_ref || t0 - 1 > h->dm.H_ref - N) return fail(h, CIMPC_ERR_INVALID, "knot range out of the table (1-based)");
+    PlantLinearizeDims pd{};
+    if (plant_linearize_check(model, N, n_terrain, terrain, z, theta, kappa, &pd) != CIMPC_OK)
+        return fail(h, CIMPC_ERR_INVALID, "cimpc_plant_linearize would refuse these arguments");
+    const cimpc_dims& d = h->dm;
+    if (pd.nq != d.nq || pd.nu != d.nu || pd.nw != d.nw || pd.nc != d.nc || pd.nb != d.nb)
+        return fail(h, CIMPC_ERR_INVALID, "the plant model's (nq, nu, nw, nc, nb) are not the handle's");
+    return build_tables_on_device(h, t0, N, z, theta, nullptr, nullptr, nullptr, model, pd.n_terrain_up, n_terrain, terrain, kappa);
+}
+
+int cimpc_get_table(cimpc_handle h, int t, double* table) {
+    if (!h || !table) return fail(h, CIMPC_ERR_INVALID, "null argument");
+    if (t < 1 || t > h->dm.H_ref) return fail(h, CIMPC_ERR_INVALID, "knot index out of range (1-based)");
+    if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, hipMemcpy(table, h->d_tab + (size_t)(t - 1) * h->ki.tab_size, (size_t)h->ki.tab_size * sizeof(double), hipMemcpyDeviceToHost));
     return CIMPC_OK;
 }
 

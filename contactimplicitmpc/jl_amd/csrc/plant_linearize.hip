@@ -17,6 +17,7 @@
 #pragma clang fp contract(off)
 
 #include "../../../include/cimpc.h"
+#include "plant_linearize.h"
 #include "plant_model.h"
 #include "plant_workspace.h"
 
@@ -95,26 +96,73 @@ __global__ __launch_bounds__(NT) void plant_linearize_kernel(PlantModel M, int N
 
 }  // namespace cimpc
 
-// ---- C ABI -------------------------------------------------------------------------------------------------------------
-// Validate (no device needed), pick the model and its instantiation, then on the plant workspace's private stream: one upload
-// (z | theta | terrains), one launch, one read-back (the outputs asked for), one synchronize.
-extern "C" int cimpc_plant_linearize(int model, int N, int n_terrain, const cimpc_terrain* terrain, const double* z, const double* theta,
-                                     double kappa, double* r0, double* rz0, double* rth0) {
-    using namespace cimpc;
-    if (N <= 0 || !z || !theta || (!r0 && !rz0 && !rth0) || !std::isfinite(kappa) || kappa < 0.0) return CIMPC_ERR_INVALID;
+// ---- launch -------------------------------------------------------------------------------------------------------------
+namespace cimpc {
+
+// The instantiation of a model's linearization, chosen in one place: N knots on `st`, all pointers device memory (a null output
+// is skipped; d_ter null: flat ground).  No synchronization.
+static bool plant_linearize_launch(const PlantModel& M, int N, const double* d_z, const double* d_th, const cimpc_terrain* d_ter,
+                                   int n_terrain, double kappa, double* d_r, double* d_rz, double* d_rth, hipStream_t st) {
+    auto launch = [&](auto kernel, int nt) {
+        hipLaunchKernelGGL(kernel, dim3(N), dim3(nt), 0, st, M, N, d_z, d_th, d_ter, d_ter ? n_terrain : 0, kappa, d_r, d_rz, d_rth);
+    };
+    // lanes: one pass over the columns where a workgroup of at most three wavefronts holds them (28, 35, 41 | 77, 119 | 167)
+    if (M.kind == PLANT_KIND_PUSHBOT || M.kind == PLANT_KIND_WALLEDCARTPOLE) launch(plant_linearize_kernel<NZ_WALLS, NTH_WALLS, 64, GROUND_WALLS>, 64);
+    else if (M.kind == PLANT_KIND_HOPPER_3D) launch(plant_linearize_kernel<NZ_HOPPER_3D, NTH_HOPPER_3D, 64, GROUND_TERRAIN>, 64);
+    else if (M.kind == PLANT_KIND_CENTROIDAL_BOX) launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_ENV>, 128);
+    else if (M.kind == PLANT_KIND_CENTROIDAL_WALL) launch(plant_linearize_kernel<NZ_WALL, NTHM, 192, GROUND_ENV>, 192);
+    else if (d_ter) launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_TERRAIN>, 128);
+    else launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_FLAT>, 128);
+    return hipGetLastError() == hipSuccess;
+}
+
+// What cimpc_plant_linearize validates without a device, but for the outputs (plant_linearize.h)
+static int plant_linearize_validate(int model, int N, int n_terrain, const cimpc_terrain* terrain, const double* z, const double* theta,
+                                    double kappa, PlantModel* M, bool* rough) {
+    if (N <= 0 || !z || !theta || !std::isfinite(kappa) || kappa < 0.0) return CIMPC_ERR_INVALID;
     if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
-    PlantModel M{};
-    if (!plant_model_by_id(model, &M) || (model == CIMPC_PLANT_PARTICLE_2D && !terrain)) return CIMPC_ERR_INVALID;
-    const size_t nz = (size_t)M.nz(), nth = (size_t)M.nth();
+    if (!plant_model_by_id(model, M) || (model == CIMPC_PLANT_PARTICLE_2D && !terrain)) return CIMPC_ERR_INVALID;
+    const size_t nth = (size_t)M->nth();
     for (int k = 0; k < N; ++k) if (!(theta[(size_t)k * nth + nth - 1] > 0.0)) return CIMPC_ERR_INVALID;      // h, the last entry of θ
-    bool rough = model == CIMPC_PLANT_PARTICLE_2D;
+    *rough = model == CIMPC_PLANT_PARTICLE_2D;
     if (terrain) {
         if (n_terrain != 1 && n_terrain != N) return CIMPC_ERR_INVALID;
         for (int i = 0; i < n_terrain; ++i) {
-            if (!terrain_valid_for(M, terrain[i])) return CIMPC_ERR_INVALID;
-            rough = rough || terrain[i].kind != CIMPC_TERRAIN_FLAT;
+            if (!terrain_valid_for(*M, terrain[i])) return CIMPC_ERR_INVALID;
+            *rough = *rough || terrain[i].kind != CIMPC_TERRAIN_FLAT;
         }
     }
+    return CIMPC_OK;
+}
+
+int plant_linearize_check(int model, int N, int n_terrain, const cimpc_terrain* terrain, const double* z, const double* theta, double kappa,
+                          PlantLinearizeDims* d) {
+    PlantModel M{};
+    bool rough = false;
+    if (int rc = plant_linearize_validate(model, N, n_terrain, terrain, z, theta, kappa, &M, &rough); rc != CIMPC_OK) return rc;
+    *d = PlantLinearizeDims{M.nq, M.nu, M.nw, M.nc, M.nb(), rough ? n_terrain : 0};
+    return CIMPC_OK;
+}
+
+bool plant_linearize_launch(int model, int N, const double* d_z, const double* d_th, const cimpc_terrain* d_ter, int n_terrain, double kappa,
+                            double* d_r, double* d_rz, double* d_rth, hipStream_t st) {
+    PlantModel M{};
+    return plant_model_by_id(model, &M) && plant_linearize_launch(M, N, d_z, d_th, d_ter, n_terrain, kappa, d_r, d_rz, d_rth, st);
+}
+
+}  // namespace cimpc
+
+// ---- C ABI -------------------------------------------------------------------------------------------------------------
+// Validate (no device needed), pick the model, then on the plant workspace's private stream: one upload (z | theta | terrains),
+// one launch, one read-back (the outputs asked for), one synchronize.
+extern "C" int cimpc_plant_linearize(int model, int N, int n_terrain, const cimpc_terrain* terrain, const double* z, const double* theta,
+                                     double kappa, double* r0, double* rz0, double* rth0) {
+    using namespace cimpc;
+    if (!r0 && !rz0 && !rth0) return CIMPC_ERR_INVALID;
+    PlantModel M{};
+    bool rough = false;
+    if (int rc = plant_linearize_validate(model, N, n_terrain, terrain, z, theta, kappa, &M, &rough); rc != CIMPC_OK) return rc;
+    const size_t nz = (size_t)M.nz(), nth = (size_t)M.nth();
     // runs on the calling thread's CURRENT device, like the other plant entry points
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PLANT_MAX_DEVICES) return CIMPC_ERR_NO_DEVICE;
@@ -140,19 +188,7 @@ extern "C" int cimpc_plant_linearize(int model, int N, int n_terrain, const cimp
     const cimpc_terrain* dter = n_ter ? reinterpret_cast<const cimpc_terrain*>(dth + n_th) : nullptr;
     double* dr = r0 ? W.d_lin_out : nullptr; double* drz = rz0 ? W.d_lin_out + n_r : nullptr; double* drth = rth0 ? W.d_lin_out + n_r + n_rz : nullptr;
     bool ok = hipMemcpyAsync(W.d_lin_in, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok) {
-        auto launch = [&](auto kernel, int nt) {
-            hipLaunchKernelGGL(kernel, dim3(N), dim3(nt), 0, st, M, N, dz, dth, dter, n_ter ? n_terrain : 0, kappa, dr, drz, drth);
-        };
-        // lanes: one pass over the columns where a workgroup of at most three wavefronts holds them (28, 35, 41 | 77, 119 | 167)
-        if (M.kind == PLANT_KIND_PUSHBOT || M.kind == PLANT_KIND_WALLEDCARTPOLE) launch(plant_linearize_kernel<NZ_WALLS, NTH_WALLS, 64, GROUND_WALLS>, 64);
-        else if (M.kind == PLANT_KIND_HOPPER_3D) launch(plant_linearize_kernel<NZ_HOPPER_3D, NTH_HOPPER_3D, 64, GROUND_TERRAIN>, 64);
-        else if (M.kind == PLANT_KIND_CENTROIDAL_BOX) launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_ENV>, 128);
-        else if (M.kind == PLANT_KIND_CENTROIDAL_WALL) launch(plant_linearize_kernel<NZ_WALL, NTHM, 192, GROUND_ENV>, 192);
-        else if (rough) launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_TERRAIN>, 128);
-        else launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_FLAT>, 128);
-        ok = hipGetLastError() == hipSuccess;
-    }
+    if (ok) ok = plant_linearize_launch(M, N, dz, dth, dter, n_terrain, kappa, dr, drz, drth, st);
     if (ok) ok = hipMemcpyAsync(out.data(), W.d_lin_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
     if (!ok) return CIMPC_ERR_HIP;

@@ -548,17 +548,18 @@ class ReferenceProblem:
     b: np.ndarray
     z: np.ndarray          # (H, nz)
     theta: np.ndarray      # (H, nθ)
-    r0: np.ndarray         # (H, nz)
+    r0: np.ndarray         # (H, nz); r0, rz0, rth0 are None where the problem was made with tables=False
     rz0: np.ndarray        # (H, nz, nz)
     rth0: np.ndarray       # (H, nz, nθ)
 
 
-def reference_problem(model: ContactModel, gait, kappa: float, update_friction: bool = False, linearize=None) -> ReferenceProblem:
+def reference_problem(model: ContactModel, gait, kappa: float, update_friction: bool = False, linearize=None, tables: bool = True) -> ReferenceProblem:
     """`get_trajectory(...; load_type = :split_traj_alt)` (trajectory.jl:169-180) followed by the `LinearizedStep`
     of every knot at κ (`ImplicitTrajectory`, implicit_dynamics.jl:37-50).  `update_friction`:
     `update_friction_coefficient!` (trajectory.jl:133-141) - θ carries the model's μ_world instead of the file's μ.
     `linearize`: a callable `(z, th, kappa) -> (r0, rz0, rth0)` over the stacked knots; None is `model.linearize_batch` (torch, host),
-    `plant.linearizer(name)` is its device twin."""
+    `plant.linearizer(name)` is its device twin.  `tables=False` skips the linearization and leaves r0 = rz0 = rth0 = None, for a
+    `CIMPCPolicy(..., device_tables=True)`, which linearizes on the device straight into the solver's tables."""
     H = gait.H
     if update_friction:
         import dataclasses
@@ -566,7 +567,7 @@ def reference_problem(model: ContactModel, gait, kappa: float, update_friction: 
     w = np.zeros((H, model.nw))
     z = np.stack([model.pack_z(gait.q[t + 2], gait.gamma[t], gait.b[t], gait.psi[t], gait.eta[t]) for t in range(H)])
     th = np.stack([model.pack_theta(gait.q[t], gait.q[t + 1], gait.u[t], w[t], gait.mu, gait.h) for t in range(H)])
-    r0, rz0, rth0 = (linearize or model.linearize_batch)(z, th, kappa)
+    r0, rz0, rth0 = (linearize or model.linearize_batch)(z, th, kappa) if tables else (None, None, None)
     return ReferenceProblem(model, H, gait.h, kappa, gait.q.copy(), gait.u.copy(), w, gait.gamma.copy(), gait.b.copy(), z, th,
                             r0, rz0, rth0)
 
@@ -581,9 +582,9 @@ def constant_reference(model: ContactModel, q_ref, H: int, h: float):
                 mu=float(model.mu_world), h=float(h))
 
 
-def reference_problem_from_traj(model: ContactModel, traj, kappa: float, linearize=None) -> ReferenceProblem:
+def reference_problem_from_traj(model: ContactModel, traj, kappa: float, linearize=None, tables: bool = True) -> ReferenceProblem:
     """The same from a serialized ContactTraj (`load_type = :joint_traj`: z and θ come from the file as they are)."""
-    r0, rz0, rth0 = (linearize or model.linearize_batch)(traj.z, traj.theta, kappa)
+    r0, rz0, rth0 = (linearize or model.linearize_batch)(traj.z, traj.theta, kappa) if tables else (None, None, None)
     return ReferenceProblem(model, traj.H, traj.h, kappa, traj.q.copy(), traj.u.copy(), traj.w.copy(), traj.gamma.copy(),
                             traj.b.copy(), traj.z.copy(), traj.theta.copy(), r0, rz0, rth0)
 

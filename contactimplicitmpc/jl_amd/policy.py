@@ -39,13 +39,16 @@ class CIMPCPolicy:
     def __init__(self, problem, obj_q, obj_u, H_mpc=None, N_sample=1, kappa_mpc=None, B=1, mode=0,
                  n_opts: NewtonOptions | None = None, ip_opts: InteriorPointOptions | None = None, device=0,
                  phase=None, obj_gamma=None, obj_b=None, obj_v=None, v_target=None, altitude_update=False,
-                 altitude_impact_threshold=1.0):
+                 altitude_impact_threshold=1.0, device_tables=False):
         """problem: a `lcp_models.ReferenceProblem` (reference trajectory + per-knot linearization at κ_mpc);
         obj_q, obj_u: (H_mpc, nq, nq), (H_mpc, nu, nu) TrackingObjective weights; obj_gamma / obj_b: contact-force
         weights of `:configurationforce` mode (mode = 1, the default of ci_mpc_policy); obj_v (+ v_target): the
         velocity weights of a TrackingVelocityObjective.  altitude_update / altitude_impact_threshold: CIMPCOptions
         (policy.jl:5-14): before every solve after the first, `update_altitude!` over the simulator steps since the last solve
-        (handed over through `observe`, which `plant.simulate` calls), then `set_altitude!` (policy.jl:110-117)."""
+        (handed over through `observe`, which `plant.simulate` calls), then `set_altitude!` (policy.jl:110-117).
+        device_tables: the knots are linearized and their tables built on the device in one call (`CIMPCSolver.linearize_knots`,
+        from problem.z, problem.theta and the device plant model of problem.model's name) instead of one `set_linearization` per
+        knot from the problem's (r0, rz0, rθ0); a problem made with `tables=False` has none and needs it."""
         m = problem.model
         self.problem = problem
         self.H = H_mpc or problem.H
@@ -54,11 +57,17 @@ class CIMPCPolicy:
         kappa = problem.kappa if kappa_mpc is None else kappa_mpc
         if abs(kappa - problem.kappa) > 0:
             raise ValueError("the linearization table was built at κ = %g, policy asks for κ_mpc = %g" % (problem.kappa, kappa))
+        if not device_tables and (problem.r0 is None or problem.rz0 is None or problem.rth0 is None):
+            raise ValueError("the problem was made with tables=False: it has no (r0, rz0, rθ0); pass device_tables=True")
+        self.kappa = kappa
         self.solver = CIMPCSolver(m.nq, m.nu, m.nw, m.nc, m.nb, problem.H, self.H, B=B, mode=mode,
                                   ip_opts=ip_opts or InteriorPointOptions(kappa_tol=kappa),       # policy.jl:54-61
                                   newton_opts=n_opts or NewtonOptions(kappa=kappa, r_tol=3e-4, max_iter=5), device=device)
-        for t in range(problem.H):
-            self.solver.set_linearization(t + 1, problem.z[t], problem.theta[t], problem.r0[t], problem.rz0[t], problem.rth0[t])
+        if device_tables:
+            self.solver.linearize_knots(m.name, problem.z, problem.theta, kappa)
+        else:
+            for t in range(problem.H):
+                self.solver.set_linearization(t + 1, problem.z[t], problem.theta[t], problem.r0[t], problem.rz0[t], problem.rth0[t])
         self.solver.set_objective(obj_q, obj_u, obj_gamma, obj_b, V=obj_v, v_target=v_target)
         from .lcp_models import get_stride
         self.stride = get_stride(m, problem.q)
@@ -105,6 +114,13 @@ class CIMPCPolicy:
             self.u = u1 / self.N_sample                      # policy.jl:142-144 (:direct)
         self.cnt += 1
         return self.u
+
+    def relinearize(self, z=None, theta=None, t0=1, terrain=None):
+        """Knots t0 .. t0+N-1 linearized again in flight, at the policy's κ, on the device: the `update!` of the reference's
+        RLin / RZLin / RθLin.  z (N, nz), theta (N, nθ); the defaults are the problem's own."""
+        z = self.problem.z if z is None else z
+        theta = self.problem.theta if theta is None else theta
+        self.solver.linearize_knots(self.problem.model.name, z, theta, self.kappa, t0=t0, terrain=terrain)
 
     def set_altitude(self, alt):
         """`set_altitude!(p.im_traj, p.altitude)` (policy.jl:116, implicit_dynamics.jl:141-154): (B, nc) or (nc,)."""

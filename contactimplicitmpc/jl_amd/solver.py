@@ -152,6 +152,54 @@ class CIMPCSolver:
         self._check(self.lib.cimpc_set_linearization(self.h, int(t), _dp(z0), _dp(th0), _dp(r0),
                                                      _dp(rz), _dp(rt)), "set_linearization")
 
+    def set_linearization_batch(self, t0, z0, th0, r0, rz0, rth0):
+        """`set_linearization` of knots t0 .. t0+N-1 (1-based) in one call, the tables built on the device
+        (`cimpc_set_linearization_batch`): z0 (N, nz), th0 (N, nθ), r0 (N, nz), rz0 (N, nz, nz), rth0 (N, nz, nθ), row-major like
+        `set_linearization`.  The tables are those of N single calls bit for bit; a knot with a singular Dx fails the whole call
+        and leaves every table as it was."""
+        z0 = np.ascontiguousarray(z0, dtype=np.float64)
+        if z0.ndim != 2 or z0.shape[0] < 1 or z0.shape[1] != self.nz:
+            raise ValueError(f"z0 must be (N, {self.nz}) with N >= 1, got {z0.shape}")
+        N = z0.shape[0]
+        th0 = _f64(th0, (N, self.nth)); r0 = _f64(r0, (N, self.nz))
+        rz0 = np.asarray(rz0, dtype=np.float64); rth0 = np.asarray(rth0, dtype=np.float64)
+        if rz0.shape != (N, self.nz, self.nz) or rth0.shape != (N, self.nz, self.nth):
+            raise ValueError("rz0 / rth0 shape mismatch")
+        self._check_knot_range(t0, N)
+        rz = np.ascontiguousarray(rz0.transpose(0, 2, 1)); rt = np.ascontiguousarray(rth0.transpose(0, 2, 1))     # column-major per knot
+        self._check(self.lib.cimpc_set_linearization_batch(self.h, int(t0), N, _dp(z0), _dp(th0), _dp(r0), _dp(rz), _dp(rt)),
+                    "set_linearization_batch")
+
+    def linearize_knots(self, model_name, z, theta, kappa, t0=1, terrain=None):
+        """Knots t0 .. t0+N-1 linearized and their tables built on the device (`cimpc_linearize_knots`): `plant.linearize(model_name,
+        z, theta, kappa, terrain=terrain)` followed by `set_linearization` of every knot, bit for bit, with nothing but z, θ and
+        the terrains crossing to the device.  z (N, nz), theta (N, nθ); names, dims and terrain as `plant.linearize` takes them."""
+        from . import plant
+        if terrain is None and model_name in plant.TERRAIN_MODELS:
+            terrain = "flat_2D_lc"
+        mid, nq, nu, nc, fd, nw = plant.model_dims(model_name)
+        if (nq, nu, nw, nc, fd * nc) != (self.nq, self.nu, self.nw, self.nc, self.nb):
+            raise ValueError(f"{model_name} has (nq, nu, nw, nc, nb) = {(nq, nu, nw, nc, fd * nc)}, the solver {(self.nq, self.nu, self.nw, self.nc, self.nb)}")
+        z = np.ascontiguousarray(z, dtype=np.float64); theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if z.ndim != 2 or z.shape[0] < 1 or z.shape[1] != self.nz or theta.shape != (z.shape[0], self.nth):
+            raise ValueError(f"z must be (N, {self.nz}) and theta (N, {self.nth}) with the same N >= 1")
+        N = z.shape[0]
+        self._check_knot_range(t0, N)
+        ter, nt = (None, 0) if terrain is None else plant._terrain_array(terrain, N)
+        self._check(self.lib.cimpc_linearize_knots(self.h, mid, int(t0), N, nt, ter, _dp(z), _dp(theta), float(kappa)), "linearize_knots")
+
+    def get_table(self, t):
+        """The packed table of knot t (1-based) as the kernels read it (`csrc/lin_table.h`) - for tests and diagnostics."""
+        if not 1 <= int(t) <= self.H_ref:
+            raise ValueError(f"knot {t} is not in 1 .. {self.H_ref}")
+        tab = np.zeros(self.query_sizes()[0])
+        self._check(self.lib.cimpc_get_table(self.h, int(t), _dp(tab)), "get_table")
+        return tab
+
+    def _check_knot_range(self, t0, N):
+        if int(t0) < 1 or int(t0) + N - 1 > self.H_ref:
+            raise ValueError(f"knots {t0} .. {int(t0) + N - 1} are not in 1 .. {self.H_ref}")
+
     def set_objective(self, Q, R, Cg=None, Cb=None, V=None, q_target=None, v_target=None):
         """TrackingObjective weights, per horizon step: Q (H,nq,nq), R (H,nu,nu) [row-major numpy
         arrays of symmetric blocks are transposed to the column-major ABI]."""

@@ -154,6 +154,20 @@ int cimpc_synchronize(cimpc_handle h);
 int cimpc_set_linearization(cimpc_handle h, int t, const double* z0, const double* th0,
                             const double* r0, const double* rz0, const double* rth0);
 
+/* ---- A1 on the device: the tables of knots t0 .. t0+N-1 (1-based) in one call -------------------------------------------------
+ * cimpc_set_linearization_batch: host arrays laid out as N consecutive inputs of cimpc_set_linearization (z0 N x nz, th0 N x nth,
+ * r0 N x nz, rz0 N x (nz x nz), rth0 N x (nz x nth), each knot's matrix column-major); one upload, the table build on the device
+ * (a workgroup per knot), no per-knot copy.  The tables are those of N calls of cimpc_set_linearization bit for bit, padding
+ * included.  Preconditions and effects are those N calls' too (pending work is drained; runs on the handle's device and stream;
+ * returns synchronized).  CIMPC_ERR_INVALID before any device work: null handle or argument, t0 < 1, N < 1, t0 + N - 1 > H_ref.
+ * A knot whose Dx = rz0[idyn, ix] is singular (a zero or non-finite pivot, what cimpc_set_linearization refuses) makes the whole
+ * call CIMPC_ERR_INVALID: cimpc_last_error names the first such knot and NO knot's table changes. */
+int cimpc_set_linearization_batch(cimpc_handle h, int t0, int N, const double* z0, const double* th0,
+                                  const double* r0, const double* rz0, const double* rth0);
+/* (cimpc_linearize_knots, declared behind cimpc_plant_linearize below, builds the same tables from (z, theta) alone) */
+/* one knot's packed table (cimpc_query_sizes: table_doubles) copied to the host - for tests and diagnostics */
+int cimpc_get_table(cimpc_handle h, int t, double* table);
+
 /* ---- objective (objective.jl:3-47), per horizon step, shared by all rollouts --------- */
 /* Q: H x (nq x nq), R: H x (nu x nu), Cg: H x (nc x nc), Cb: H x (nb x nb) (may be NULL in
  * :configuration mode).  V / q_target / v_target: TrackingVelocityObjective terms, NULL for
@@ -427,6 +441,14 @@ int cimpc_plant_rollout(int model, int B, int T, int steps_per_launch,
 int cimpc_plant_linearize(int model, int N, int n_terrain, const cimpc_terrain* terrain,
                           const double* z, const double* theta, double kappa,
                           double* r0, double* rz0, double* rth0);
+
+/* ---- cimpc_set_linearization_batch from (z, theta) alone: plant model `model` linearized at kappa (cimpc_plant_linearize's kernel and arguments;
+ * z0 = z, th0 = theta) and the tables built from its output, all on the handle's device and stream;
+ * nothing but z, theta and the terrains goes up, nothing but N status words comes back.  Equal bit for bit to
+ * cimpc_plant_linearize followed by N calls of cimpc_set_linearization.  Also CIMPC_ERR_INVALID, before any device work: everything
+ * cimpc_plant_linearize validates, and a plant model whose (nq, nu, nw, nc, nb) are not the handle's. */
+int cimpc_linearize_knots(cimpc_handle h, int model, int t0, int N, int n_terrain, const cimpc_terrain* terrain,
+                          const double* z, const double* theta, double kappa);
 
 #ifdef __cplusplus
 }

@@ -558,6 +558,59 @@ function plant_linearize(model::Symbol, z::VecOrMat{Float64}, θ::VecOrMat{Float
     return r0, rz0, rθ0
 end
 
+# ---- A1 on the device: the tables of knots t0 .. t0+N-1 in one call, built by one workgroup per knot -----------------------------------
+_lin_dims(hs::Solver) = (d = hs.dims; (Int(d.nq + 4 * d.nc + 2 * d.nb), Int(2 * d.nq + d.nu + d.nw + 2)))      # nz, nθ of the handle
+
+"""
+    set_linearization_batch!(hs, t0, z0, θ0, r0, rz0, rθ0)
+
+`set_linearization!` of knots `t0 .. t0+N-1` in one call: z0, r0: nz x N, θ0: nθ x N, rz0: nz x nz x N, rθ0: nz x nθ x N (what
+`plant_linearize` returns).  One upload, the tables built on the device, equal bit for bit to N single calls; a knot with a
+singular Dx fails the whole call and changes no table.
+"""
+function set_linearization_batch!(hs::Solver, t0::Int, z0::Matrix{Float64}, θ0::Matrix{Float64}, r0::Matrix{Float64},
+                                  rz0::Array{Float64,3}, rθ0::Array{Float64,3})
+    nz, nθ = _lin_dims(hs)
+    N = size(z0, 2)
+    (N >= 1 && size(z0, 1) == nz && size(θ0) == (nθ, N) && size(r0) == (nz, N) && size(rz0) == (nz, nz, N) && size(rθ0) == (nz, nθ, N)) ||
+        error("set_linearization_batch!: z0, r0 must be $nz x N, θ0 $nθ x N, rz0 $nz x $nz x N, rθ0 $nz x $nθ x N")
+    (1 <= t0 && t0 + N - 1 <= hs.dims.H_ref) || error("set_linearization_batch!: knots $t0 .. $(t0 + N - 1) are not in 1 .. $(hs.dims.H_ref)")
+    check(ccall((:cimpc_set_linearization_batch, LIB), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                hs.h, t0, N, z0, θ0, r0, rz0, rθ0), hs.h)
+end
+
+"""
+    linearize_knots!(hs, model, z, θ, κ; t0 = 1, terrain = nothing)
+
+Knots `t0 .. t0+N-1` linearized at κ and their tables built, all on the handle's device: `plant_linearize(model, z, θ, κ; terrain)`
+followed by `set_linearization!` of every knot, bit for bit, with only z (nz x N), θ (nθ x N) and the terrains crossing to the
+device - the in-flight `update!` of `RLin / RZLin / RθLin` for N knots.  The model's dimensions must be the handle's.
+"""
+function linearize_knots!(hs::Solver, model::Symbol, z::Matrix{Float64}, θ::Matrix{Float64}, κ::Real; t0::Int = 1,
+                          terrain::Union{Nothing,Vector{Terrain}} = nothing)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    d = hs.dims
+    (nq, nu, nw, nc, nf * nc) == (d.nq, d.nu, d.nw, d.nc, d.nb) || error("linearize_knots!: $model does not have the handle's dimensions")
+    nz, nθ = _lin_dims(hs)
+    N = size(z, 2)
+    (N >= 1 && size(z, 1) == nz && size(θ) == (nθ, N)) || error("linearize_knots!($model): z must be $nz x N and θ $nθ x N")
+    (1 <= t0 && t0 + N - 1 <= d.H_ref) || error("linearize_knots!: knots $t0 .. $(t0 + N - 1) are not in 1 .. $(d.H_ref)")
+    (terrain === nothing || length(terrain) in (1, N)) || error("linearize_knots!($model): one terrain or one per knot")
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    check(@ccall LIB.cimpc_linearize_knots(hs.h::Ptr{Cvoid}, id::Cint, t0::Cint, N::Cint, n_ter::Cint, ter::Ptr{Terrain}, z::Ptr{Cdouble},
+                                           θ::Ptr{Cdouble}, κ::Cdouble)::Cint, hs.h)
+end
+
+"One knot's packed table (csrc/lin_table.h) as the kernels read it - for tests and diagnostics."
+function get_table(hs::Solver, t::Int)
+    n = Ref{Cint}(0); nkkt = Ref{Cint}(0)
+    check(ccall((:cimpc_query_sizes, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}), hs.h, n, nkkt), hs.h)
+    table = zeros(Int(n[]))
+    check(ccall((:cimpc_get_table, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}), hs.h, t, table), hs.h)
+    return table
+end
+
 end # module
 
 # executed in the INCLUDING module (ContactImplicitMPC): `eval(opts.solver)` of newton.jl:86 looks the constructor up there
