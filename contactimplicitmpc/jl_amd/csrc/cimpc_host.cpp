@@ -1,5 +1,5 @@
 // Host runtime behind the C ABI of include/cimpc.h: handle, HBM residency, the per-knot
-// linearization packer (A1), window bucketing, and the lock-step driver of newton_solve!
+// linearization tables (A1; built by lin_table_build.h), window bucketing, and the lock-step driver of newton_solve!
 // (/root/reference/src/controller/newton.jl:169-288).  HIP runtime only - no torch, no BLAS.
 #include <hip/hip_runtime.h>
 
@@ -163,6 +163,7 @@ struct cimpc_ctx {
     RoundStreams rs;
     bool external_stream = false;
     std::vector<double> h_tab;       // one knot staging
+    std::vector<double> h_tab_work;  // the host build's workspace (lin_table_build.h)
     // device table build (cimpc_set_linearization_batch, cimpc_linearize_knots), grow-only: z0 | th0 | terrains | r0 | rz0 | rth0 of
     // the call's knots, their tables as built (committed to d_tab only when every knot's Dx could be inverted), one status word each
     double* d_tb = nullptr;
@@ -210,34 +211,11 @@ int dev_alloc(cimpc_ctx* h, T** p, size_t count) {
     return CIMPC_OK;
 }
 
-// dense inverse by Gauss-Jordan with partial pivoting (column-major n x n); false if singular
-bool invert(const double* A, double* Ai, int n) {
-    std::vector<double> M((size_t)n * 2 * n);
-    auto at = [&](int r, int c) -> double& { return M[(size_t)r * 2 * n + c]; };
-    for (int r = 0; r < n; ++r)
-        for (int c = 0; c < n; ++c) {
-            at(r, c) = A[r + (size_t)c * n];
-            at(r, n + c) = (r == c) ? 1.0 : 0.0;
-        }
-    for (int k = 0; k < n; ++k) {
-        int p = k;
-        for (int r = k + 1; r < n; ++r)
-            if (std::fabs(at(r, k)) > std::fabs(at(p, k))) p = r;
-        if (at(p, k) == 0.0 || !std::isfinite(at(p, k))) return false;
-        if (p != k)
-            for (int c = 0; c < 2 * n; ++c) std::swap(at(p, c), at(k, c));
-        const double piv = at(k, k);
-        for (int c = 0; c < 2 * n; ++c) at(k, c) /= piv;
-        for (int r = 0; r < n; ++r) {
-            if (r == k) continue;
-            const double f = at(r, k);
-            if (f == 0.0) continue;
-            for (int c = 0; c < 2 * n; ++c) at(r, c) -= f * at(k, c);
-        }
-    }
-    for (int r = 0; r < n; ++r)
-        for (int c = 0; c < n; ++c) Ai[r + (size_t)c * n] = at(r, n + c);
-    return true;
+// The handle's table layout, the one its kernels read (ki.tab_size doubles per knot)
+int table_layout(cimpc_ctx* h, LinLayout* L) {
+    *L = LinLayout(h->nx, h->ny, h->nth, h->ki.G, h->ki.generic ? 0 : h->nths, h->ki.generic ? 0 : h->ki.adj);
+    if (L->size != h->ki.tab_size) return fail(h, CIMPC_ERR_STATE, "table layout of the library and of the kernel differ");
+    return CIMPC_OK;
 }
 
 void prof_begin(cimpc_ctx* h, int cls, hipStream_t st = nullptr) {
@@ -512,6 +490,7 @@ int cimpc_create(const cimpc_dims* dims, const cimpc_ip_opts* ip, const cimpc_ne
     h->own_stream = true;
     h->knot_set.assign(d.H_ref, 0);
     h->h_tab.assign(h->ki.tab_size, 0.0);
+    h->h_tab_work.assign(lin_table_work_doubles(h->nx, h->ny), 0.0);
 
     const size_t B = d.B, H = d.H;
     int rc = CIMPC_OK;
@@ -690,88 +669,13 @@ int cimpc_set_linearization(cimpc_handle h, int t, const double* z0, const doubl
     if (!h || !z0 || !th0 || !r0 || !rz0 || !rth0) return fail(h, CIMPC_ERR_INVALID, "null argument");
     if (t < 1 || t > h->dm.H_ref) return fail(h, CIMPC_ERR_INVALID, "knot index out of range (1-based)");
     if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
-    const int nx = h->nx, ny = h->ny, nz = h->nz, nth = h->nth, G = h->ki.G;
-    const LinLayout L(nx, ny, nth, G, h->ki.generic ? 0 : h->nths, h->ki.generic ? 0 : h->ki.adj);
-    if (L.size != h->ki.tab_size) return fail(h, CIMPC_ERR_STATE, "table layout of the library and of the kernel differ");
-    std::vector<double>& T = h->h_tab;
-    std::fill(T.begin(), T.end(), 0.0);
-    auto RZ = [&](int r, int c) { return rz0[r + (size_t)c * nz]; };
-    auto RTH = [&](int r, int c) { return rth0[r + (size_t)c * nz]; };
-    // blocks (linearization_var_index / term_index are contiguous: index.jl:289-327)
-    std::vector<double> Dx((size_t)nx * nx), Ai((size_t)nx * nx), CAi((size_t)ny * nx), CAiB((size_t)ny * ny);
-    for (int c = 0; c < nx; ++c)
-        for (int r = 0; r < nx; ++r) Dx[r + (size_t)c * nx] = RZ(r, c);
-    if (!invert(Dx.data(), Ai.data(), nx))
+    LinLayout L(0, 0, 0, 0);
+    if (int rc = table_layout(h, &L); rc != CIMPC_OK) return rc;
+    // the build the device runs (lin_table_build.h), here by a team of one
+    if (!lin_table_build_knot(L, z0, th0, r0, rz0, rth0, h->h_tab_work.data(), h->h_tab.data(), SoloTeam{}))
         return fail(h, CIMPC_ERR_INVALID, "Dx = rz0[idyn, ix] is singular");
-    // CAi = Rx * Ai ; CAiB = (Rx * Ai) * Dy1   (schur.jl:40-41)
-    for (int r = 0; r < ny; ++r)
-        for (int c = 0; c < nx; ++c) {
-            double s = 0.0;
-            for (int k = 0; k < nx; ++k) s += RZ(nx + r, k) * Ai[k + (size_t)c * nx];
-            CAi[r + (size_t)c * ny] = s;
-        }
-    for (int r = 0; r < ny; ++r)
-        for (int c = 0; c < ny; ++c) {
-            double s = 0.0;
-            for (int k = 0; k < nx; ++k) s += CAi[r + (size_t)k * ny] * RZ(k, nx + c);
-            CAiB[r + (size_t)c * ny] = s;
-        }
-    for (int i = 0; i < ny; ++i)        // W[i*G + j] = Ry1[i,j] - CAiB[i,j], diagonal kept apart
-        for (int j = 0; j < ny; ++j)
-            T[L.oW + i * L.ldw + j] = (i == j) ? 0.0 : RZ(nx + i, nx + j) - CAiB[i + (size_t)j * ny];
-    for (int k = 0; k < nx; ++k) {
-        for (int i = 0; i < ny; ++i) T[L.oCAi + k * G + i] = CAi[i + (size_t)k * ny];
-        for (int i = 0; i < nx; ++i) T[L.oAi + k * G + i] = Ai[i + (size_t)k * nx];
-        for (int i = 0; i < nx; ++i) T[L.oDx + k * G + i] = RZ(i, k);
-        for (int i = 0; i < ny; ++i) T[L.oRx + k * G + i] = RZ(nx + i, k);
-    }
-    for (int k = 0; k < ny; ++k) {
-        for (int i = 0; i < nx; ++i) T[L.oDy1 + k * G + i] = RZ(i, nx + k);
-        for (int i = 0; i < ny; ++i) T[L.oRy1 + k * G + i] = RZ(nx + i, nx + k);
-    }
-    for (int k = 0; k < nth; ++k) {
-        for (int i = 0; i < nx; ++i) T[L.oRthDyn + k * G + i] = RTH(i, k);
-        for (int i = 0; i < ny; ++i) T[L.oRthRst + k * G + i] = RTH(nx + i, k);
-    }
-    // right-hand sides of the sensitivity pass as the QR sees them (lin_table.h: oGs): Gs[i, c] = (CAi rthdyn[:, c])_i - rthrst[i, c]
-    // with the kernel's chain - two partial sums over even / odd k, correctly rounded multiply-adds (IpSolver::schur_solve) -
-    // so that the columns the sweep writes do not change by a bit
-    for (int c = 0; c < L.nths; ++c)
-        for (int i = 0; i < ny; ++i) {
-            double bq[2] = {0.0, 0.0};
-            for (int k = 0; k < nx; ++k) bq[k & 1] = std::fma(RTH(k, c), CAi[i + (size_t)k * ny], bq[k & 1]);
-            T[L.gst ? L.oGs + i * L.nths + c : L.oGs + c * G + i] = (bq[0] + bq[1]) - RTH(nx + i, c);
-        }
-    // constants of the adjoint form of the sensitivity pass (lin_table.h: oK0, oAiB): A^-1 rthdyn, A^-1 B (plain sums)
-    if (L.adj) {
-        for (int c = 0; c < L.nths; ++c)
-            for (int i = 0; i < nx; ++i) {
-                double s = 0.0;
-                for (int k = 0; k < nx; ++k) s = std::fma(Ai[i + (size_t)k * nx], RTH(k, c), s);
-                T[L.oK0 + c * nx + i] = s;
-            }
-        for (int i = 0; i < nx; ++i)
-            for (int k = 0; k < ny; ++k) {
-                double s = 0.0;
-                for (int m = 0; m < nx; ++m) s = std::fma(Ai[i + (size_t)m * nx], RZ(m, nx + k), s);
-                T[L.oAiB + i * ny + k] = s;
-            }
-    }
-    for (int i = 0; i < ny; ++i) {
-        T[L.oVec + LinLayout::V_RY2 * G + i] = RZ(nx + i, nx + ny + i);
-        T[L.oVec + LinLayout::V_RY1D * G + i] = RZ(nx + i, nx + i);
-        T[L.oVec + LinLayout::V_CAIBD * G + i] = CAiB[i + (size_t)i * ny];
-        T[L.oVec + LinLayout::V_RRST0 * G + i] = r0[nx + i];
-        T[L.oVec + LinLayout::V_Y10 * G + i] = z0[nx + i];
-        T[L.oVec + LinLayout::V_Y20 * G + i] = z0[nx + ny + i];
-    }
-    for (int i = 0; i < nx; ++i) {
-        T[L.oVec + LinLayout::V_RDYN0 * G + i] = r0[i];
-        T[L.oVec + LinLayout::V_X0 * G + i] = z0[i];
-    }
-    for (int k = 0; k < nth; ++k) T[L.oTh0 + k] = th0[k];
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemcpy(h->d_tab + (size_t)(t - 1) * L.size, T.data(), (size_t)L.size * sizeof(double),
+    HIP_TRY(h, hipMemcpy(h->d_tab + (size_t)(t - 1) * L.size, h->h_tab.data(), (size_t)L.size * sizeof(double),
                          hipMemcpyHostToDevice));
     if (!h->knot_set[t - 1]) { h->knot_set[t - 1] = 1; h->n_knots_set++; }
     return CIMPC_OK;
@@ -786,8 +690,8 @@ int build_tables_on_device(cimpc_ctx* h, int t0, int N, const double* z0, const 
                            const double* rth0, int model, int n_ter_up, int n_terrain, const cimpc_terrain* terrain, double kappa) {
     if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
     const size_t nz = h->nz, nth = h->nth;
-    const LinLayout L(h->nx, h->ny, h->nth, h->ki.G, h->ki.generic ? 0 : h->nths, h->ki.generic ? 0 : h->ki.adj);
-    if (L.size != h->ki.tab_size) return fail(h, CIMPC_ERR_STATE, "table layout of the library and of the kernel differ");
+    LinLayout L(0, 0, 0, 0);
+    if (int rc = table_layout(h, &L); rc != CIMPC_OK) return rc;
     constexpr size_t TW = sizeof(cimpc_terrain) / sizeof(double);
     const size_t n_z = (size_t)N * nz, n_th = (size_t)N * nth, n_ter = (size_t)n_ter_up * TW;
     const size_t o_th = n_z, o_ter = o_th + n_th, o_r = o_ter + n_ter, o_rz = o_r + n_z, o_rth = o_rz + n_z * nz;
@@ -860,8 +764,10 @@ int cimpc_get_table(cimpc_handle h, int t, double* table) {
     if (!h || !table) return fail(h, CIMPC_ERR_INVALID, "null argument");
     if (t < 1 || t > h->dm.H_ref) return fail(h, CIMPC_ERR_INVALID, "knot index out of range (1-based)");
     if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
+    LinLayout L(0, 0, 0, 0);
+    if (int rc = table_layout(h, &L); rc != CIMPC_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipMemcpy(table, h->d_tab + (size_t)(t - 1) * h->ki.tab_size, (size_t)h->ki.tab_size * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(table, h->d_tab + (size_t)(t - 1) * L.size, (size_t)L.size * sizeof(double), hipMemcpyDeviceToHost));
     return CIMPC_OK;
 }
 
@@ -916,11 +822,17 @@ int cimpc_set_objective(cimpc_handle h, const double* Q, const double* R, const 
     }
     // the inverses first: whether every R_t could be inverted decides the form of the banded LDL^T (kkt_dense.hip:
     // kkt_banded_kernel eliminates the controls when it can), and that form decides whether the backend fits
-    std::vector<double> Qi(H * d.nq * d.nq), Ri(H * d.nu * d.nu);
+    std::vector<double> Qi(H * d.nq * d.nq), Ri(H * d.nu * d.nu), work(lin_invert_work_doubles(std::max(d.nq, d.nu)));
+    auto inverse = [&](const double* A, double* Ai, int n) {      // column-major n x n; false (Ai as it was) if singular
+        if (!lin_invert(A, n, n, work.data(), SoloTeam{})) return false;
+        for (int c = 0; c < n; ++c)
+            for (int r = 0; r < n; ++r) Ai[r + (size_t)c * n] = work[(size_t)r * 2 * n + n + c];
+        return true;
+    };
     bool q_inverted = true, r_inverted = true;
     for (size_t i = 0; i < H; ++i) {
-        if (!invert(Q + i * d.nq * d.nq, Qi.data() + i * d.nq * d.nq, d.nq)) q_inverted = false;
-        if (d.nu > 0 && !invert(R + i * d.nu * d.nu, Ri.data() + i * d.nu * d.nu, d.nu)) r_inverted = false;
+        if (!inverse(Q + i * d.nq * d.nq, Qi.data() + i * d.nq * d.nq, d.nq)) q_inverted = false;
+        if (d.nu > 0 && !inverse(R + i * d.nu * d.nu, Ri.data() + i * d.nu * d.nu, d.nu)) r_inverted = false;
     }
     h->band_reduce_ok = r_inverted && d.nu > 0 && (h->kn.banded_form & 4) == 0;
     set_kkt_backend(h);

@@ -27,7 +27,7 @@ struct LinLayout {
     // oGs (compiled lane-group models; nths = 0: absent): the right-hand sides of the sensitivity pass as the QR sees them,
     //   Gs[:, c] = CAi * rthdyn[:, c] - rthrst[:, c],  c = 0 .. nths-1  (schur_solve!, schur.jl:93-110, on column c of r_theta,
     //   linearized_solver.jl:451-479) - a constant of the knot that every converged solve used to recompute for each of its
-    //   nths columns; formed by cimpc_set_linearization with the kernel's own multiply-add chain (bit-identical columns).
+    //   nths columns; formed by lin_table_build_knot (lin_table_build.h) with the kernel's own multiply-add chain (bit-identical columns).
     //   gst = 1 (adj = 1, 16-lane groups): the block is stored by ROW, Gs[k, c] at k*nths + c - the adjoint pass of those models
     //   keeps one COLUMN c per lane (ip_kernel_impl.h: sensitivities) and reads row k with consecutive addresses
     // oK0, oAiB (adj = 1: models whose sensitivity pass runs in the adjoint form, ip_kernel_impl.h: sensitivities): the constants

@@ -1,11 +1,11 @@
 // The packed linearization tables built on the device (A1 for N knots at once): lin_table_build_knot of lin_table_build.h, the
-// arithmetic of cimpc_set_linearization, run by one workgroup per knot.  [Dx | I], CAi and CAiB live in dynamic LDS sized from
+// text cimpc_set_linearization runs on the host, here by one workgroup per knot.  [Dx | I], CAi and CAiB live in dynamic LDS sized from
 // the handle's run-time (nx, ny): 30 KB for the largest compiled model (centroidal_quadruped_wall, nx 18, ny 48), 129 KB at the
 // generic kernel's bound nx = ny = 64 - above 64 KB the kernel's limit is raised for that launch shape alone.  rz0 (104 KB for the
 // wall) is read from global memory where it is used, never staged whole.  Runs when tables are built, not per MPC step.
 #include <hip/hip_runtime.h>
 
-// every operation rounds as the host packer's does; the multiply-adds the packer fuses are spelled std::fma in the header
+// every operation rounds as it does in the host's run of the same header; the multiply-adds that are fused are spelled std::fma there
 #pragma clang fp contract(off)
 
 #include "lin_table_build.h"

@@ -332,35 +332,21 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
     if (T < 1 || steps_per_launch < 0 || K_u < 1 || hold_u < 1 || (n_u != 1 && n_u != B) || !mu || (n_mu != 1 && n_mu != B)) return CIMPC_ERR_INVALID;
     if (w && (K_w < 1 || hold_w < 1 || (n_w != 1 && n_w != B))) return CIMPC_ERR_INVALID;
     PlantModel M{};
-    if (!plant_model_by_id(model, &M) || (model == CIMPC_PLANT_PARTICLE_2D && !terrain)) return CIMPC_ERR_INVALID;
+    bool rough = false;
+    if (!plant_model_and_ground(model, B, n_terrain, terrain, &M, &rough)) return CIMPC_ERR_INVALID;
     if (opts->max_iter <= 0 || opts->max_ls < 0 || !(opts->r_tol > 0.0) || !(opts->kappa_tol > 0.0) || !(opts->ls_scale > 0.0 && opts->ls_scale < 1.0))
         return CIMPC_ERR_INVALID;
-    bool rough = model == CIMPC_PLANT_PARTICLE_2D;
-    if (terrain) {
-        if (n_terrain != 1 && n_terrain != B) return CIMPC_ERR_INVALID;
-        for (int i = 0; i < n_terrain; ++i) {
-            if (!terrain_valid_for(M, terrain[i])) return CIMPC_ERR_INVALID;
-            rough = rough || terrain[i].kind != CIMPC_TERRAIN_FLAT;
-        }
-    }
-    // runs on the calling thread's CURRENT device (the caller selects it, e.g. hipSetDevice(rank) / torch.cuda.set_device)
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PLANT_MAX_DEVICES) return CIMPC_ERR_NO_DEVICE;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return CIMPC_ERR_NO_DEVICE;
-    }
+    if (!plant_current_device(&dev)) return CIMPC_ERR_NO_DEVICE;
     const size_t pnc = (size_t)M.nc, pnb = (size_t)M.nb();
     PlantOpts o{opts->r_tol, opts->kappa_tol, std::isinf(opts->undercut) ? 0.0 : opts->kappa_tol / opts->undercut, opts->eps_min,
                 opts->ls_scale, opts->stall_alpha, opts->max_iter, opts->max_ls};
     const size_t nq = M.nq, nu = M.nu, nw = M.nw, row = (size_t)B * nq, TB = (size_t)T * B;
     const size_t n_q = (size_t)(T + 2) * row, n_us = (size_t)K_u * n_u * nu, n_ws = w ? (size_t)K_w * n_w * nw : 0, n_mus = n_mu == 1 ? 0 : (size_t)B;
     std::lock_guard<std::mutex> lock(g_plant_mu);
-    PlantWs& W = g_plant_ws[dev];
-    if (!W.st) {
-        if (hipStreamCreateWithFlags(&W.st, hipStreamNonBlocking) != hipSuccess) return CIMPC_ERR_HIP;
-        W.device = dev;
-    }
+    PlantWs* ws = plant_ws_open(dev);
+    if (!ws) return CIMPC_ERR_HIP;
+    PlantWs& W = *ws;
     if (!plant_grow(&W.d_in, &W.cap_in, n_q + n_us + n_ws + n_mus) || !plant_grow(&W.d_out, &W.cap_out, TB * (pnc + pnb)) ||
         !plant_grow(&W.d_st, &W.cap_st, 2 * TB))
         return CIMPC_ERR_HIP;

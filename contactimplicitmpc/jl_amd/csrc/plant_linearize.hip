@@ -121,17 +121,9 @@ static int plant_linearize_validate(int model, int N, int n_terrain, const cimpc
                                     double kappa, PlantModel* M, bool* rough) {
     if (N <= 0 || !z || !theta || !std::isfinite(kappa) || kappa < 0.0) return CIMPC_ERR_INVALID;
     if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
-    if (!plant_model_by_id(model, M) || (model == CIMPC_PLANT_PARTICLE_2D && !terrain)) return CIMPC_ERR_INVALID;
+    if (!plant_model_and_ground(model, N, n_terrain, terrain, M, rough)) return CIMPC_ERR_INVALID;
     const size_t nth = (size_t)M->nth();
     for (int k = 0; k < N; ++k) if (!(theta[(size_t)k * nth + nth - 1] > 0.0)) return CIMPC_ERR_INVALID;      // h, the last entry of θ
-    *rough = model == CIMPC_PLANT_PARTICLE_2D;
-    if (terrain) {
-        if (n_terrain != 1 && n_terrain != N) return CIMPC_ERR_INVALID;
-        for (int i = 0; i < n_terrain; ++i) {
-            if (!terrain_valid_for(*M, terrain[i])) return CIMPC_ERR_INVALID;
-            *rough = *rough || terrain[i].kind != CIMPC_TERRAIN_FLAT;
-        }
-    }
     return CIMPC_OK;
 }
 
@@ -163,13 +155,8 @@ extern "C" int cimpc_plant_linearize(int model, int N, int n_terrain, const cimp
     bool rough = false;
     if (int rc = plant_linearize_validate(model, N, n_terrain, terrain, z, theta, kappa, &M, &rough); rc != CIMPC_OK) return rc;
     const size_t nz = (size_t)M.nz(), nth = (size_t)M.nth();
-    // runs on the calling thread's CURRENT device, like the other plant entry points
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PLANT_MAX_DEVICES) return CIMPC_ERR_NO_DEVICE;
-    {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return CIMPC_ERR_NO_DEVICE;
-    }
+    if (!plant_current_device(&dev)) return CIMPC_ERR_NO_DEVICE;
     const size_t n_z = (size_t)N * nz, n_th = (size_t)N * nth, n_ter = rough ? (size_t)n_terrain * TERRAIN_WORDS : 0;
     const size_t n_r = r0 ? n_z : 0, n_rz = rz0 ? n_z * nz : 0, n_rth = rth0 ? n_z * nth : 0;
     std::vector<double> in(n_z + n_th + n_ter), out(n_r + n_rz + n_rth);
@@ -177,11 +164,9 @@ extern "C" int cimpc_plant_linearize(int model, int N, int n_terrain, const cimp
     std::memcpy(in.data() + n_z, theta, n_th * sizeof(double));
     if (n_ter) std::memcpy(in.data() + n_z + n_th, terrain, n_ter * sizeof(double));
     std::lock_guard<std::mutex> lock(g_plant_mu);
-    PlantWs& W = g_plant_ws[dev];
-    if (!W.st) {
-        if (hipStreamCreateWithFlags(&W.st, hipStreamNonBlocking) != hipSuccess) return CIMPC_ERR_HIP;
-        W.device = dev;
-    }
+    PlantWs* ws = plant_ws_open(dev);
+    if (!ws) return CIMPC_ERR_HIP;
+    PlantWs& W = *ws;
     if (!plant_grow(&W.d_lin_in, &W.cap_lin_in, in.size()) || !plant_grow(&W.d_lin_out, &W.cap_lin_out, out.size())) return CIMPC_ERR_HIP;
     hipStream_t st = W.st;
     const double* dz = W.d_lin_in; const double* dth = dz + n_z;

@@ -5,11 +5,15 @@
 //   step / rollout  d_in: trajectory (T + 2) x B x nq | u schedule | w schedule | per-robot mu; d_out: gamma | b; d_st: status | iters
 //                   (T x B each); d_ter: the robots' terrains
 //   linearize       d_lin_in: z | theta | terrains (N x nz, N x nth, n_terrain cimpc_terrain); d_lin_out: r0 | rz0 | rth0 (those asked for)
+// The prologue the entry points share is stated here once: which model and ground a call names (plant_model_and_ground, no device
+// needed), which device it runs on (plant_current_device), and its workspace with the stream open (plant_ws_open).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstring>
 #include <mutex>
 
 #include "../../../include/cimpc.h"
+#include "plant_model.h"
 
 namespace cimpc {
 
@@ -35,6 +39,40 @@ bool plant_grow(T** p, size_t* cap, size_t need) {
     if (hipMalloc((void**)p, need * sizeof(T)) != hipSuccess) return false;
     *cap = need;
     return true;
+}
+
+// The model behind a CIMPC_PLANT_* id and the ground of a call over n robots or knots: terrain null (flat ground), or 1 terrain for
+// all or n, one each, every one a terrain the model can stand on.  *rough: the terrain list has to reach the device (a terrain that is
+// not flat, or particle_2D, which has no flat residual and so no call without a terrain).  False: an entry point refuses the call.
+inline bool plant_model_and_ground(int model, int n, int n_terrain, const cimpc_terrain* terrain, PlantModel* M, bool* rough) {
+    if (!plant_model_by_id(model, M) || (model == CIMPC_PLANT_PARTICLE_2D && !terrain)) return false;
+    *rough = model == CIMPC_PLANT_PARTICLE_2D;
+    if (terrain) {
+        if (n_terrain != 1 && n_terrain != n) return false;
+        for (int i = 0; i < n_terrain; ++i) {
+            if (!terrain_valid_for(*M, terrain[i])) return false;
+            *rough = *rough || terrain[i].kind != CIMPC_TERRAIN_FLAT;
+        }
+    }
+    return true;
+}
+
+// The calling thread's CURRENT device (the caller selects it, e.g. hipSetDevice(rank) / torch.cuda.set_device), which every plant
+// entry point runs on.  False: none that has a workspace, or not a gfx950.
+inline bool plant_current_device(int* dev) {
+    if (hipGetDevice(dev) != hipSuccess || *dev < 0 || *dev >= PLANT_MAX_DEVICES) return false;
+    hipDeviceProp_t prop;
+    return hipGetDeviceProperties(&prop, *dev) == hipSuccess && std::strncmp(prop.gcnArchName, "gfx950", 6) == 0;
+}
+
+// The workspace of device `dev`, its stream opened on first use; the caller holds g_plant_mu.  Null: the stream could not be created.
+inline PlantWs* plant_ws_open(int dev) {
+    PlantWs& W = g_plant_ws[dev];
+    if (!W.st) {
+        if (hipStreamCreateWithFlags(&W.st, hipStreamNonBlocking) != hipSuccess) return nullptr;
+        W.device = dev;
+    }
+    return &W;
 }
 
 }  // namespace cimpc

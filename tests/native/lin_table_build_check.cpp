@@ -1,5 +1,5 @@
-// lin_table_build_knot (contactimplicitmpc/jl_amd/csrc/lin_table_build.h), the text the device kernel runs, on the host with a
-// team of one.  stdin: nx ny nth G nths adj, then z0 (nz), th0 (nth), r0 (nz), rz0 (nz x nz, column-major), rth0 (nz x nth,
+// lin_table_build_knot (contactimplicitmpc/jl_amd/csrc/lin_table_build.h), the text the device kernel and the library's host path
+// run, on the host with its team of one.  stdin: nx ny nth G nths adj, then z0 (nz), th0 (nth), r0 (nz), rz0 (nz x nz, column-major), rth0 (nz x nth,
 // column-major).  stdout: the LinLayout (one line: ldw gst oW oCAi oAi oDy1 oDx oRx oRy1 oRthDyn oRthRst oGs oK0 oAiB oVec oTh0
 // size), then "singular" or the table, one %a per entry.
 //   g++ -O2 -std=c++17 -ffp-contract=off [-fsanitize=address,undefined] lin_table_build_check.cpp
@@ -9,12 +9,6 @@
 #define __host__
 #define __device__
 #include "../../contactimplicitmpc/jl_amd/csrc/lin_table_build.h"
-
-struct One {
-    int rank() const { return 0; }
-    int size() const { return 1; }
-    void sync() const {}
-};
 
 static bool read(std::vector<double>& v) {
     for (double& x : v)
@@ -39,7 +33,7 @@ int main() {
     std::printf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d\n", L.ldw, L.gst, L.oW, L.oCAi, L.oAi, L.oDy1, L.oDx, L.oRx, L.oRy1, L.oRthDyn,
                 L.oRthRst, L.oGs, L.oK0, L.oAiB, L.oVec, L.oTh0, L.size);
     std::vector<double> work(cimpc::lin_table_work_doubles(nx, ny)), T(L.size, -1.0);      // -1: the build itself must write the padding
-    if (!cimpc::lin_table_build_knot(L, z0.data(), th0.data(), r0.data(), rz0.data(), rth0.data(), work.data(), T.data(), One{})) {
+    if (!cimpc::lin_table_build_knot(L, z0.data(), th0.data(), r0.data(), rz0.data(), rth0.data(), work.data(), T.data(), cimpc::SoloTeam{})) {
         std::puts("singular");
         return 0;
     }

@@ -1,8 +1,10 @@
 """The solver's linearization tables built on the device (`cimpc_linearize_knots`, `cimpc_set_linearization_batch`:
-lin_table_build_kernel behind plant_linearize_kernel) against the host packer `cimpc_set_linearization`, table by table and bit for
+lin_table_build_kernel behind plant_linearize_kernel) against the host path `cimpc_set_linearization`, table by table and bit for
 bit (`cimpc_get_table`): every layout family, a range inside the table, terrain, a singular knot, the sweep that consumes the
-tables, and re-linearization in flight under `CIMPCPolicy`.  Handles are small (H_ref <= 6, B = 1, N = 3 knots) except the two
-policies, which carry the quadruped gait's 60 knots."""
+tables, and re-linearization in flight under `CIMPCPolicy`.  Both paths run one text (csrc/lin_table_build.h), one on the GPU and one
+on the CPU; what that text computes is held by the recorded tables of tests/golden/lin_table_sha256.json, which the last test reads
+back from a handle.  Handles are small (H_ref <= 6, B = 1, N = 3 knots) except the two policies, which carry the quadruped gait's
+60 knots."""
 import os
 
 import numpy as np
@@ -11,6 +13,7 @@ import pytest
 from contactimplicitmpc.jl_amd import CIMPCSolver, InteriorPointOptions, NewtonOptions, _lib, gait_io, lcp_models, plant
 from contactimplicitmpc.jl_amd.policy import CIMPCPolicy
 import plant_linearize_cases as cases
+import table_build_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -260,3 +263,33 @@ def test_relinearization_in_flight_under_the_policy(monkeypatch):
     finally:
         for p in pols:
             p.close()
+
+
+# ---- 7. the recorded tables -----------------------------------------------------------------------------------------------------------
+# layout of tests/table_build_cases.py -> the handle that has it: (model, mode)
+RECORDED_HANDLES = {"quadruped": ("quadruped", 0), "hopper_3D": ("hopper_3D", 0), "centroidal": ("centroidal_quadruped", 0),
+                    "pushbot mode 1": ("pushbot", 1), "wall": ("centroidal_quadruped_wall", 0), "wall generic": ("centroidal_quadruped_wall", 1)}
+
+
+@pytest.mark.parametrize("layout", sorted(RECORDED_HANDLES))
+def test_set_linearization_puts_the_recorded_tables_into_a_handle(layout):
+    """A handle of one knot (H_ref = H = 1, B = 1) takes the layout's recorded knots one after the other: the table read back has the
+    recorded size and SHA-256; the singular knot is refused and leaves the table set before it."""
+    name, mode = RECORDED_HANDLES[layout]
+    want = table_build_cases.recorded()[layout]
+    s = _handle(lcp_models.MODELS[name](), mode, 1)
+    try:
+        assert s.query_sizes()[0] == want["size"]
+        before = None
+        for kn, knot in table_build_cases.knots(layout).items():
+            if kn == "singular":
+                assert before is not None
+                with pytest.raises(_lib.CimpcError, match="singular"):
+                    s.set_linearization(1, *knot)
+                assert table_build_cases.table_hash(s.get_table(1)) == before, "the refused knot changed the table"
+            else:
+                s.set_linearization(1, *knot)
+                before = table_build_cases.table_hash(s.get_table(1))
+                assert before == want["knots"][kn], f"{layout}, knot {kn!r}"
+    finally:
+        s.close()

@@ -1,8 +1,9 @@
 """The device table build without a device: `cimpc_set_linearization_batch`, `cimpc_linearize_knots` and `cimpc_get_table` as
 declared, exported, bound and mirrored in Julia; their argument validation (which comes before any device call); the Python shape
-checks; the `tables` keyword of `lcp_models.reference_problem`; and the kernel's own text - `lin_table_build_knot` of
+checks; the `tables` keyword of `lcp_models.reference_problem`; and the one text every table is built by - `lin_table_build_knot` of
 `contactimplicitmpc/jl_amd/csrc/lin_table_build.h`, built with g++ (tests/native/lin_table_build_check.cpp; also as a sanitized
-stand-alone program) - against a NumPy statement of what the table means, one seeded knot per layout family."""
+stand-alone program) - against a NumPy statement of what the table means, one seeded knot per layout family, and against the tables
+recorded bit for bit in tests/golden/lin_table_sha256.json (tests/table_build_cases.py)."""
 import ctypes as C
 import os
 import re
@@ -13,6 +14,8 @@ import numpy as np
 import pytest
 
 from contactimplicitmpc.jl_amd import _lib, lcp_models, policy, solver
+import table_build_cases as cases
+from table_build_cases import LAYOUTS, knot as _knot
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -144,12 +147,7 @@ def test_tables_keyword_leaves_the_tables_out_and_nothing_else():
 
 
 # ---- the kernel's text on the host ------------------------------------------------------------------------------------------------------
-# (nx, ny, nth, G, nths, adj) of the layout families: quadruped mode 0 (16 lanes, adjoint, Gs stored by row), hopper_3D mode 0 (nx > ny),
-# centroidal_quadruped mode 0 (32 lanes, ldw = G + 1), pushbot mode 1 (column form), the wall mode 0 (64 lanes), the wall as the
-# run-time-dimension kernel takes it (nths = 0, adj = 0), and the bound of that kernel, nx = ny = 64
-LAYOUTS = {"quadruped": (11, 16, 34, 16, 30, 1), "hopper_3D": (7, 6, 22, 16, 17, 1), "centroidal": (18, 24, 53, 32, 48, 1),
-           "pushbot mode 1": (2, 8, 10, 16, 6, 0), "wall": (18, 48, 53, 64, 48, 1), "wall generic": (18, 48, 53, 64, 0, 0),
-           "64 x 64": (64, 64, 140, 64, 0, 0)}
+# the layout families and their knots: tests/table_build_cases.py
 OFFSETS = ("ldw", "gst", "oW", "oCAi", "oAi", "oDy1", "oDx", "oRx", "oRy1", "oRthDyn", "oRthRst", "oGs", "oK0", "oAiB", "oVec", "oTh0", "size")
 
 
@@ -175,17 +173,6 @@ def harness(request, tmp_path_factory):
             return L, None
         return L, np.array([float.fromhex(v) for v in out[1:1 + L["size"]]])
     return run
-
-
-def _knot(name, singular=False):
-    nx, ny, nth, G, nths, adj = LAYOUTS[name]
-    rng = np.random.default_rng(sorted(LAYOUTS).index(name))
-    nz = nx + 2 * ny
-    rz0 = rng.normal(size=(nz, nz))
-    rz0[:nx, :nx] += 3.0 * np.eye(nx)
-    if singular:
-        rz0[:nx, 0] = 0.0
-    return rng.normal(size=nz), rng.uniform(0.1, 1.0, nth), rng.normal(size=nz), rz0, rng.normal(size=(nz, nth))
 
 
 def _meaning(dims, z0, th0, r0, rz0, rth0):
@@ -266,3 +253,17 @@ def test_the_built_table_means_what_lin_table_h_says(harness, name):
 def test_a_singular_dx_is_refused_as_the_packer_refuses_it(harness):
     L, T = harness(LAYOUTS["quadruped"], *_knot("quadruped", singular=True))
     assert L is not None and T is None
+
+
+@pytest.mark.parametrize("name", sorted(LAYOUTS))
+def test_the_built_table_is_the_recorded_one_bit_for_bit(harness, name):
+    """Every knot of the layout - its own, the three that make the elimination exchange rows and skip zero multipliers, the singular
+    one - against the SHA-256 recorded from the packer `cimpc_set_linearization` had of its own before it ran this text: the bits of
+    the one remaining statement of the table's arithmetic, pinned without a GPU."""
+    want = cases.recorded()[name]
+    assert sorted(want["knots"]) == sorted(cases.KNOTS)
+    for kn, k in cases.knots(name).items():
+        L, T = harness(LAYOUTS[name], *k)
+        assert L["size"] == want["size"], kn
+        assert (T is None) == (kn == "singular"), kn
+        assert cases.table_hash(T) == want["knots"][kn], f"{name}, knot {kn!r}"
