@@ -99,6 +99,14 @@ SIGNATURES = {
     "cimpc_plant_rollout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
                                       _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip]),
     "cimpc_plant_linearize": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, C.c_double, _dp, _dp, _dp]),
+    "cimpc_tvlqr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
+    "cimpc_reference_gains_lin": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double,
+                                            _dp, _dp]),
+    "cimpc_reference_gains": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double,
+                                        _dp, _dp]),
+    "cimpc_set_gains": (C.c_int, [_h, _dp]),
+    "cimpc_gain_latch": (C.c_int, [_h]),
+    "cimpc_gain_feedback": (C.c_int, [_h, _dp, _dp, C.c_double, _dp]),
     "cimpc_get_reference": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "cimpc_get_stats": (C.c_int, [_h, C.POINTER(Stats)]),
     "cimpc_get_newton_log": (C.c_int, [_h, _dp, C.c_int]),

@@ -17,6 +17,7 @@
 #include "lin_table_build.h"
 #include "model_table.h"
 #include "newton_state.h"
+#include "gains.h"
 #include "plant_linearize.h"
 #include "schedule_plan.h"
 
@@ -168,6 +169,11 @@ struct cimpc_ctx {
     // the call's knots, their tables as built (committed to d_tab only when every knot's Dx could be inverted), one status word each
     double* d_tb = nullptr;
     size_t tb_cap = 0;
+    // feedback gains (cimpc_set_gains, cimpc_gain_latch, cimpc_gain_feedback): K of every reference knot, what the last latch kept
+    // per rollout (gains.h: gain_latch_doubles) and the staging of a feedback call [q_prev | q_cur | u]; allocated at the first cimpc_set_gains
+    double *d_gK = nullptr, *d_glatch = nullptr, *d_gio = nullptr;
+    bool gains_set = false, gains_latched = false;
+    bool latch_ready = false;        // a Newton solve has run and nothing has moved the window or the reference since: cimpc_gain_latch may run
     cimpc_stats last_stats{};
     // profiling
     int prof_on = 0;             // 0 off, 1 every launch, 2 the interior-point sweep launches only (cimpc_profile_enable)
@@ -187,6 +193,12 @@ int fail(cimpc_ctx* h, int code, const std::string& msg) {
     else g_create_error = msg;
     return code;
 }
+
+}  // namespace
+
+void cimpc::set_global_error(const std::string& msg) { g_create_error = msg; }
+
+namespace {
 
 #define HIP_TRY(h, call)                                                                     \
     do {                                                                                     \
@@ -404,7 +416,7 @@ int check_ready(cimpc_ctx* h, bool need_newton) {
 
 extern "C" {
 
-int cimpc_version(void) { return 107; }      // 1.07: + cimpc_set_linearization_batch, cimpc_linearize_knots, cimpc_get_table (no struct changed).  1.06: round 6 (+ cimpc_mpc_solve; no struct changed).  1.05: round 5 (+ cimpc_get_kkt_twisted; no struct changed).  1.04: round 4 (cimpc_ip_opts::max_time - the struct grew by one double at its end)
+int cimpc_version(void) { return 108; }      // 1.08: + cimpc_tvlqr, cimpc_reference_gains(_lin), cimpc_set_gains, cimpc_gain_latch, cimpc_gain_feedback (no struct changed).  1.07: + cimpc_set_linearization_batch, cimpc_linearize_knots, cimpc_get_table (no struct changed).  1.06: round 6 (+ cimpc_mpc_solve; no struct changed).  1.05: round 5 (+ cimpc_get_kkt_twisted; no struct changed).  1.04: round 4 (cimpc_ip_opts::max_time - the struct grew by one double at its end)
 
 void cimpc_default_ip_opts(cimpc_ip_opts* o) {
     if (!o) return;
@@ -896,6 +908,7 @@ static int rekey_in(cimpc_ctx* h) {
 
 int cimpc_set_window(cimpc_handle h, const int* window) {
     if (!h || !window) return fail(h, CIMPC_ERR_INVALID, "null argument");
+    h->latch_ready = false;
     const cimpc_dims& d = h->dm;
     const int B = d.B, H = d.H, K = d.H_ref;
     std::vector<int> w0((size_t)B * (H + 2));
@@ -921,6 +934,7 @@ int cimpc_set_reference(cimpc_handle h, const double* q_ref, const double* u_ref
                         const double* w_ref, const double* gamma_ref, const double* b_ref,
                         const double* theta_ref) {
     if (!h || !q_ref || !u_ref || !theta_ref) return fail(h, CIMPC_ERR_INVALID, "q_ref, u_ref, theta_ref are required");
+    h->latch_ready = false;
     const cimpc_dims& d = h->dm;
     const size_t B = d.B, H = d.H;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -1290,6 +1304,7 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
     HIP_TRY(h, hipSetDevice(h->device));
     if (int sy = sync_dz_stores(h, 1); sy != CIMPC_OK) return sy;
     h->dz_producer = 1;
+    h->latch_ready = true;
     const int B = h->dm.B;
     SolveRun run{q0_dev, q1_dev, warm_start, {}, *(volatile int*)h->h_twfail, false, h->rs, RoundCounts{B, 0, B, B, 0, 0}};
     h->twfail_seen = run.tw_fail0;
@@ -1520,6 +1535,7 @@ static GaitDev gait_dev(cimpc_ctx* h) {
 int cimpc_set_gait(cimpc_handle h, const double* q, const double* u, const double* w, const double* gamma,
                    const double* b, const double* theta, const double* stride, const int* phase) {
     if (!h || !q || !u || !theta || !stride) return fail(h, CIMPC_ERR_INVALID, "q, u, theta, stride are required");
+    h->latch_ready = false;
     const cimpc_dims& d = h->dm;
     const size_t K = d.H_ref, B = d.B;
     if (d.H > d.H_ref) return fail(h, CIMPC_ERR_INVALID, "H_mpc must not exceed H_ref");
@@ -1559,6 +1575,7 @@ int cimpc_set_gait(cimpc_handle h, const double* q, const double* u, const doubl
 int cimpc_mpc_advance(cimpc_handle h, const double* stride) {
     if (!h || !stride) return fail(h, CIMPC_ERR_INVALID, "null argument");
     if (!h->window_set || !h->reference_set) return fail(h, CIMPC_ERR_STATE, "set_window / set_reference have not been called");
+    h->latch_ready = false;          // the window and the reference move on: a latch now would take the NEXT step's K and target
     HIP_TRY(h, hipSetDevice(h->device));
     // The advance is QUEUED on the handle's stream and not waited for: whatever comes next is ordered behind it on the device
     // (the solve's streams wait for this stream, every getter synchronises it first).  The stride goes through a pinned word;
@@ -1581,6 +1598,57 @@ int cimpc_mpc_advance(cimpc_handle h, const double* stride) {
     int rc = launch_mpc_advance(h->S, h->d_window, h->d_q0, h->dm.H_ref, h->stream);
     if (rc != CIMPC_OK) return fail(h, rc, "mpc_advance launch failed");
     if (int rk = rekey_in(h); rk != CIMPC_OK) return rk;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return CIMPC_OK;
+}
+
+// ---- feedback gains on the handle (gains.hip) -------------------------------------------------------------------------------------
+int cimpc_set_gains(cimpc_handle h, const double* K) {
+    if (!h) return CIMPC_ERR_INVALID;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
+    h->gains_latched = false;
+    if (!K) { h->gains_set = false; return CIMPC_OK; }
+    const cimpc_dims& d = h->dm;
+    const size_t nk = (size_t)d.nu * 2 * d.nq;
+    // each buffer by itself: one that could not be allocated is asked for again by the next call, and gains_set stays false until all exist
+    if (!h->d_gK && dev_alloc(h, &h->d_gK, (size_t)d.H_ref * nk) != CIMPC_OK) return CIMPC_ERR_HIP;
+    if (!h->d_glatch && dev_alloc(h, &h->d_glatch, (size_t)d.B * gain_latch_doubles(d.nq, d.nu)) != CIMPC_OK) return CIMPC_ERR_HIP;
+    if (!h->d_gio && dev_alloc(h, &h->d_gio, (size_t)d.B * (2 * d.nq + d.nu)) != CIMPC_OK) return CIMPC_ERR_HIP;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemcpy(h->d_gK, K, (size_t)d.H_ref * nk * sizeof(double), hipMemcpyHostToDevice));
+    h->gains_set = true;
+    return CIMPC_OK;
+}
+
+int cimpc_gain_latch(cimpc_handle h) {
+    if (!h) return CIMPC_ERR_INVALID;
+    if (!h->gains_set) return fail(h, CIMPC_ERR_STATE, "cimpc_set_gains has not been called");
+    if (!h->latch_ready)
+        return fail(h, CIMPC_ERR_STATE, "cimpc_gain_latch belongs between a newton solve and cimpc_mpc_advance: no solve has run, or the window or the reference moved since");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
+    const cimpc_dims& d = h->dm;
+    if (!gain_latch_launch(d.B, d.H, d.nq, d.nu, h->d_window, h->S.traj.u, h->S.ref.q, h->d_gK, h->d_glatch, h->stream))
+        return fail(h, CIMPC_ERR_HIP, "gain latch launch failed");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->gains_latched = true;
+    return CIMPC_OK;
+}
+
+int cimpc_gain_feedback(cimpc_handle h, const double* q_prev, const double* q_cur, double n_sample, double* u) {
+    if (!h || !q_prev || !q_cur || !u) return fail(h, CIMPC_ERR_INVALID, "null argument");
+    if (!std::isfinite(n_sample) || n_sample <= 0.0) return fail(h, CIMPC_ERR_INVALID, "n_sample must be finite and positive");
+    if (!h->gains_set || !h->gains_latched) return fail(h, CIMPC_ERR_STATE, "cimpc_gain_latch has not been called since cimpc_set_gains");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const cimpc_dims& d = h->dm;
+    const size_t nqB = (size_t)d.B * d.nq, nuB = (size_t)d.B * d.nu;
+    double* dq = h->d_gio;
+    HIP_TRY(h, hipMemcpyAsync(dq, q_prev, nqB * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dq + nqB, q_cur, nqB * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (!gain_feedback_launch(d.B, d.nq, d.nu, h->d_glatch, dq, dq + nqB, n_sample, dq + 2 * nqB, h->stream))
+        return fail(h, CIMPC_ERR_HIP, "gain feedback launch failed");
+    HIP_TRY(h, hipMemcpyAsync(u, dq + 2 * nqB, nuB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return CIMPC_OK;
 }

@@ -39,7 +39,8 @@ class CIMPCPolicy:
     def __init__(self, problem, obj_q, obj_u, H_mpc=None, N_sample=1, kappa_mpc=None, B=1, mode=0,
                  n_opts: NewtonOptions | None = None, ip_opts: InteriorPointOptions | None = None, device=0,
                  phase=None, obj_gamma=None, obj_b=None, obj_v=None, v_target=None, altitude_update=False,
-                 altitude_impact_threshold=1.0, device_tables=False):
+                 altitude_impact_threshold=1.0, device_tables=False, gains=False, control_gain_scaling=100.0,
+                 velocity_gain_scaling=100.0, gains_N=10):
         """problem: a `lcp_models.ReferenceProblem` (reference trajectory + per-knot linearization at κ_mpc);
         obj_q, obj_u: (H_mpc, nq, nq), (H_mpc, nu, nu) TrackingObjective weights; obj_gamma / obj_b: contact-force
         weights of `:configurationforce` mode (mode = 1, the default of ci_mpc_policy); obj_v (+ v_target): the
@@ -48,7 +49,15 @@ class CIMPCPolicy:
         (handed over through `observe`, which `plant.simulate` calls), then `set_altitude!` (policy.jl:110-117).
         device_tables: the knots are linearized and their tables built on the device in one call (`CIMPCSolver.linearize_knots`,
         from problem.z, problem.theta and the device plant model of problem.model's name) instead of one `set_linearization` per
-        knot from the problem's (r0, rz0, rθ0); a problem made with `tables=False` has none and needs it."""
+        knot from the problem's (r0, rz0, rθ0); a problem made with `tables=False` has none and needs it.
+        gains (CIMPCOptions.gains, policy.jl:11-13; needs obj_v): the time-varying LQR gains of the reference trajectory
+        (`gains.reference_gains` on problem.z, problem.theta with obj_q[0], obj_v[0], obj_u[0], gains_N repeats and the two scalings:
+        `reference_gains(s, traj, obj; N, U_scaling, V_scaling)`, gains.jl:17-51), computed once on the device; every call then returns
+        (u1 + K[window[1]] ([q_ref[1]; q_ref[2]] - [q0; q1])) / N_sample with q0 = q1 - N_sample (q1 - q_prev), q_prev the configuration of
+        the previous call: the feedback line of examples/centroidal_quadruped/continuous_policy_v3.jl:74-85 in the discrete policy -
+        a placement of this build, the reference's own policy() never applies its gains."""
+        if gains and obj_v is None:
+            raise ValueError("gains=True needs obj_v: reference_gains takes a TrackingVelocityObjective")
         m = problem.model
         self.problem = problem
         self.H = H_mpc or problem.H
@@ -75,6 +84,12 @@ class CIMPCPolicy:
         self.newton_iters = []
         self.altitude_update = bool(altitude_update)
         self.altitude_impact_threshold = float(altitude_impact_threshold)
+        self.gains = bool(gains)
+        if self.gains:
+            from .gains import reference_gains
+            self.K = reference_gains(m.name, problem.z, problem.theta, np.asarray(obj_q)[0], np.asarray(obj_v)[0], np.asarray(obj_u)[0],
+                                     N=gains_N, U_scaling=control_gain_scaling, V_scaling=velocity_gain_scaling)
+            self.solver.set_gains(self.K)
         self.reset()
 
     def reset(self):
@@ -88,6 +103,7 @@ class CIMPCPolicy:
         self.u = np.zeros((self.B, P.model.nu))
         self.altitude = np.zeros((self.B, P.model.nc))          # p.altitude .= 0.0 (policy.jl:102)
         self.gamma_hist, self.q_hist = [], []
+        self.q_prev = self.q0.copy()
 
     def observe(self, q2, gamma):
         """The outcome of one simulator step, (B, nq) and (B, nc): the part of `traj` the altitude update reads."""
@@ -107,12 +123,18 @@ class CIMPCPolicy:
                 self.set_altitude(self.altitude)
             u1, it, rn = self.solver.newton_solve(self.q0, q1, warm_start=self.solves > 0)
             self.newton_iters.append(it.copy())
+            if self.gains:
+                self.solver.gain_latch()                    # before the reference rotates: K[window[1]], p.traj.q[1], p.traj.q[2]
             self.solver.mpc_advance(self.stride)            # rot_n_stride! + update_window!
             self.q0 = q1.copy()
             self.cnt = 0
             self.solves += 1
             self.u = u1 / self.N_sample                      # policy.jl:142-144 (:direct)
         self.cnt += 1
+        if self.gains:
+            u = self.solver.gain_feedback(self.q_prev, q1, self.N_sample)
+            self.q_prev = q1.copy()
+            return u
         return self.u
 
     def relinearize(self, z=None, theta=None, t0=1, terrain=None):

@@ -356,6 +356,28 @@ class CIMPCSolver:
         st = _f64(stride, (self.nq,))
         self._check(self.lib.cimpc_mpc_advance(self.h, _dp(st)), "mpc_advance")
 
+    def set_gains(self, K):
+        """`K_traj` of the policy (reference_gains): (H_ref, nu, 2nq); None switches the feedback off (the default)."""
+        if K is None:
+            self._check(self.lib.cimpc_set_gains(self.h, None), "set_gains")
+            return
+        K = np.asarray(K, dtype=np.float64)
+        if K.shape != (self.H_ref, self.nu, 2 * self.nq):
+            raise ValueError(f"expected shape {(self.H_ref, self.nu, 2 * self.nq)}, got {K.shape}")
+        self._check(self.lib.cimpc_set_gains(self.h, _dp(np.ascontiguousarray(K.transpose(0, 2, 1)))), "set_gains")
+
+    def gain_latch(self):
+        """After a Newton solve, before `mpc_advance`: keeps u1, K[window[1]] and [q_ref[1]; q_ref[2]] of every rollout on the device."""
+        self._check(self.lib.cimpc_gain_latch(self.h), "gain_latch")
+
+    def gain_feedback(self, q_prev, q_cur, n_sample):
+        """(u1 + K ([q_ref[1]; q_ref[2]] - [q0; q_cur])) / n_sample with q0 = q_cur - n_sample (q_cur - q_prev), from the last latch:
+        q_prev, q_cur (B, nq) -> u (B, nu)."""
+        qp, qc = _f64(q_prev, (self.B, self.nq)), _f64(q_cur, (self.B, self.nq))
+        u = np.zeros((self.B, self.nu))
+        self._check(self.lib.cimpc_gain_feedback(self.h, _dp(qp), _dp(qc), float(n_sample), _dp(u)), "gain_feedback")
+        return u
+
     def set_gait(self, q, u, theta, stride, w=None, gamma=None, b=None, phase=None):
         """The controller's full reference trajectory (p.traj of the CIMPC policy): H_ref knots shared by the
         rollouts; builds every rollout's window and horizon reference on the device (phase = steps already

@@ -450,6 +450,59 @@ int cimpc_plant_linearize(int model, int N, int n_terrain, const cimpc_terrain* 
 int cimpc_linearize_knots(cimpc_handle h, int model, int t0, int N, int n_terrain, const cimpc_terrain* terrain,
                           const double* z, const double* theta, double kappa);
 
+/* ---- time-varying LQR feedback gains along the reference (src/controller/gains.jl:1-51; CIMPCOptions.gains, policy.jl:11-13) --------
+ * All matrices column-major doubles on the host.  The three stateless entries validate first, without a device (CIMPC_ERR_INVALID:
+ * null pointers - P1 excepted -, sizes < 1, N < 1, scalings not finite or <= 0, n_q / n_r / n_keep out of range, nth < 2nq + nu,
+ * nz < nq, n > 48 or m > 16), then run on the calling thread's current device on the plant's private stream.  A singular step is
+ * CIMPC_ERR_SINGULAR and cimpc_last_error(NULL) names the first singular knot or Riccati step (1-based); a non-finite entry of a
+ * knot's dz/dtheta counts as singular.  On ANY error the outputs are untouched.
+ * The planar models at their shipped gaits are singular here: the 2-D friction rows of quadruped (gait2) and flamingo
+ * (gait_forward_36_4) degenerate, rz has an exact zero pivot and the reference's `\` throws there as well.  The gains are a feature
+ * of the 3-D cone models (centroidal_quadruped and its wall / box variants, hopper_3D).
+ *
+ * cimpc_tvlqr (gains.jl:1-15): n_prob problems of equal size in one call, a workgroup each.  Starting from P[T] = Q[T], for
+ * t = T-1 .. 1:  K_t = (R_t + B_t' P B_t) \ (B_t' P A_t),  P <- Q_t + K_t' R_t K_t + (A_t - B_t K_t)' P (A_t - B_t K_t); P is not
+ * symmetrized (the reference does not).  R + B'PB is factored by LU with partial pivoting (Julia's `\`).
+ *   A: n_prob x n_ab x (n x n), B: n_prob x n_ab x (n x m), step t (0-based, T-1 steps) uses index t % n_ab;
+ *   Q: n_prob x n_q x (n x n) with n_q = 1 or T;  R: n_prob x n_r x (m x m) with n_r = 1 or T-1.
+ *   K out: n_prob x n_keep x (m x n), the first n_keep <= T-1 steps;  P1 out (may be NULL): n_prob x (n x n) = P[1]. */
+int cimpc_tvlqr(int n_prob, int n, int m, int T, int n_ab, const double* A, const double* B,
+                int n_q, const double* Q, int n_r, const double* R, int n_keep, double* K, double* P1);
+
+/* reference_gains (gains.jl:17-51) from a linearization made elsewhere: rz0 H x (nz x nz), rth0 H x (nz x nth).  Per knot
+ * dz/dtheta = -rz \ rtheta (its q rows, by LU with partial pivoting of rz' - the adjoint form), A_t = [0 I; D1 D2], B_t = [0; Du],
+ * Q = [Qq + Vs Qv, -Vs Qv; -Vs Qv, Qq + Vs Qv], R = Us Ru, the H knots repeated N times (H-periodic), K[1:H] returned.
+ * Qq, Qv: nq x nq, Ru: nu x nu = obj.q[1], obj.v[1], obj.u[1].  kappa does not enter: the derivatives do not depend on it. */
+int cimpc_reference_gains_lin(int nq, int nu, int nz, int nth, int H, int N, const double* rz0, const double* rth0,
+                              const double* Qq, const double* Qv, const double* Ru, double U_scaling, double V_scaling,
+                              double* K /* H x (nu x 2nq) */, double* P1 /* may be NULL */);
+
+/* the same from (z, theta) alone: the plant model linearized on the device (cimpc_plant_linearize's kernel, rz0 and rth0 only), then
+ * the two kernels above, on the plant workspace's stream; only z, theta, terrains and the weights go up, only K (and P1) come back.
+ * Equal bit for bit to cimpc_plant_linearize followed by cimpc_reference_gains_lin.  Refuses everything cimpc_plant_linearize
+ * refuses (z: H x nz, theta: H x ntheta, terrain: n_terrain = 0 and NULL, or 1 or H terrains). */
+int cimpc_reference_gains(int model, int H, int N, int n_terrain, const cimpc_terrain* terrain,
+                          const double* z, const double* theta,
+                          const double* Qq, const double* Qv, const double* Ru, double U_scaling, double V_scaling,
+                          double* K, double* P1);
+
+/* ---- the gains in the policy -----------------------------------------------------------------------------------------------------
+ * The feedback line of examples/centroidal_quadruped/continuous_policy_v3.jl:74-85,  u = (u1 + K[window[1]] ([q_ref[1]; q_ref[2]] -
+ * [q0; q1])) / h,  placed in the DISCRETE policy() (policy.jl:98-146), which divides by N_sample where the continuous one divides
+ * by h.  THE PLACEMENT IS THIS BUILD'S: the reference's in-tree policy() never applies its gains.
+ *   cimpc_set_gains      K: H_ref x (nu x 2nq) as cimpc_reference_gains returns it; NULL switches the feature off (the default).
+ *   cimpc_gain_latch     after a Newton solve and BEFORE cimpc_mpc_advance: per rollout keeps u1 = core.traj.u[1], K[window[1]] and
+ *                        target = [q_ref[1]; q_ref[2]] of the handle's current window and stride-rotated reference (p.traj.q[1],
+ *                        p.traj.q[2]).  CIMPC_ERR_STATE without gains set, before any solve, and once cimpc_mpc_advance,
+ *                        cimpc_set_window, cimpc_set_reference or cimpc_set_gait has moved the window or the reference since the
+ *                        last solve (a latch then would take the NEXT step's K and target).
+ *   cimpc_gain_feedback  q_prev, q_cur: B x nq, two consecutive simulator states; q0 = q_cur - n_sample (q_cur - q_prev) (the example's
+ *                        q0 = q1 - v h with v from the two states);  u (B x nu) = (u1 + K (target - [q0; q_cur])) / n_sample.
+ *                        CIMPC_ERR_STATE before a latch. */
+int cimpc_set_gains(cimpc_handle h, const double* K);
+int cimpc_gain_latch(cimpc_handle h);
+int cimpc_gain_feedback(cimpc_handle h, const double* q_prev, const double* q_cur, double n_sample, double* u);
+
 #ifdef __cplusplus
 }
 #endif

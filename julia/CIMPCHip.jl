@@ -611,6 +611,90 @@ function get_table(hs::Solver, t::Int)
     return table
 end
 
+# ---- time-varying LQR feedback gains along the reference (src/controller/gains.jl:1-51) on the device ---------------------------------
+"""
+    tvlqr(A, B, Q, R) -> (K, P1)
+
+`tvlqr` of gains.jl:1-15 with the reference's arguments: vectors of T-1 matrices A (n x n), B (n x m), R (m x m) and of T matrices Q.
+K is the reference's vector of T-1 gains (m x n).  The cost-to-go matrices stay on the device: of the reference's `P` only `P[1]`
+comes back.  A singular `R + B'PB` is an error naming the step, like the reference's `\\`.
+"""
+function tvlqr(A::AbstractVector, B::AbstractVector, Q::AbstractVector, R::AbstractVector)
+    T = length(Q)
+    (T >= 2 && length(A) == T - 1 && length(B) == T - 1 && length(R) == T - 1) || error("tvlqr: T = length(Q) >= 2 and T - 1 matrices A, B, R")
+    n, m = size(B[1])
+    dense(v, r, c) = (M = zeros(r, c, length(v)); for (i, x) in enumerate(v); M[:, :, i] .= x; end; M)
+    Ac = dense(A, n, n); Bc = dense(B, n, m); Qc = dense(Q, n, n); Rc = dense(R, m, m)
+    K = zeros(m, n, T - 1); P1 = zeros(n, n)
+    check(ccall((:cimpc_tvlqr, LIB), Cint,
+                (Cint, Cint, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Ptr{Cdouble}),
+                1, n, m, T, T - 1, Ac, Bc, T, Qc, T - 1, Rc, T - 1, K, P1))
+    return [K[:, :, t] for t = 1:T - 1], P1
+end
+
+"""
+    reference_gains(model, traj, obj; N = 10, κ = 2e-4, U_scaling = 100, V_scaling = 100) -> K[1:H]
+
+`reference_gains(s, traj, obj; ...)` of gains.jl:17-51 with the device plant model `model` (a key of the plant tables) in the place
+of the simulation: traj.z, traj.θ are linearized on the device, dz/dθ, the N-fold Riccati chain and nothing but the H gains
+(nu x 2nq each) come back.  `obj` is the TrackingVelocityObjective: obj.q[1], obj.v[1], obj.u[1] are used.  κ is accepted and does
+not enter (the derivatives do not depend on it).  The planar models at their shipped gaits are singular here, as in the reference.
+"""
+function reference_gains(model::Symbol, traj, obj; N::Int = 10, κ = 2e-4, U_scaling = 100, V_scaling = 100,
+                         terrain::Union{Nothing,Vector{Terrain}} = nothing)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    nz = nq + 4 * nc + 2 * nf * nc; nθ = 2 * nq + nu + nw + 2
+    H = traj.H
+    z = pack(traj.z, H); θ = pack(traj.θ, H)
+    (size(z) == (nz, H) && size(θ) == (nθ, H)) || error("reference_gains($model): traj.z must be $nz x H and traj.θ $nθ x H")
+    (terrain === nothing || length(terrain) in (1, H)) || error("reference_gains($model): one terrain or one per knot")
+    Qq = Matrix{Float64}(obj.q[1]); Qv = Matrix{Float64}(obj.v[1]); Ru = Matrix{Float64}(obj.u[1])
+    K = zeros(nu, 2 * nq, H)
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    Us = Float64(U_scaling); Vs = Float64(V_scaling); P1 = C_NULL
+    check(@ccall LIB.cimpc_reference_gains(id::Cint, H::Cint, N::Cint, n_ter::Cint, ter::Ptr{Terrain}, z::Ptr{Cdouble}, θ::Ptr{Cdouble},
+                                           Qq::Ptr{Cdouble}, Qv::Ptr{Cdouble}, Ru::Ptr{Cdouble}, Us::Cdouble, Vs::Cdouble,
+                                           K::Ptr{Cdouble}, P1::Ptr{Cdouble})::Cint)
+    return [K[:, :, t] for t = 1:H]
+end
+
+"The same from a linearization made elsewhere: rz0 nz x nz x H, rθ0 nz x nθ x H (what `plant_linearize` returns)."
+function reference_gains_lin(nq::Int, nu::Int, rz0::Array{Float64,3}, rθ0::Array{Float64,3}, obj; N::Int = 10, U_scaling = 100, V_scaling = 100)
+    nz, nθ, H = size(rθ0)
+    size(rz0) == (nz, nz, H) || error("reference_gains_lin: rz0 must be $nz x $nz x $H")
+    Qq = Matrix{Float64}(obj.q[1]); Qv = Matrix{Float64}(obj.v[1]); Ru = Matrix{Float64}(obj.u[1])
+    K = zeros(nu, 2 * nq, H)
+    check(ccall((:cimpc_reference_gains_lin, LIB), Cint,
+                (Cint, Cint, Cint, Cint, Cint, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Cdouble,
+                 Ptr{Cdouble}, Ptr{Cdouble}),
+                nq, nu, nz, nθ, H, N, rz0, rθ0, Qq, Qv, Ru, U_scaling, V_scaling, K, C_NULL))
+    return [K[:, :, t] for t = 1:H]
+end
+
+# The gains in the policy: the feedback line of examples/centroidal_quadruped/continuous_policy_v3.jl:74-85 placed in the discrete
+# policy() - a placement of this build, the reference's policy() never applies its gains (include/cimpc.h).
+"""
+    set_gains!(hs, K)
+
+K: the vector `reference_gains` returns - H_ref matrices nu x 2nq, one per reference knot; `nothing` switches the feedback off.
+"""
+function set_gains!(hs::Solver, K::Union{Nothing,AbstractVector{<:AbstractMatrix}})
+    K === nothing && return check(ccall((:cimpc_set_gains, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), hs.h, C_NULL), hs.h)
+    d = hs.dims
+    (length(K) == d.H_ref && all(size(k) == (d.nu, 2 * d.nq) for k in K)) ||
+        error("set_gains!: K must be $(d.H_ref) matrices $(d.nu) x $(2 * d.nq)")
+    Kc = Array{Float64,3}(cat(K...; dims = 3))          # nu x 2nq x H_ref, column-major: the library's H_ref x (nu x 2nq)
+    check(ccall((:cimpc_set_gains, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), hs.h, Kc), hs.h)
+end
+"After a Newton solve and before `mpc_advance!`: keeps u1, K[window[1]] and [q_ref[1]; q_ref[2]] of every rollout."
+gain_latch!(hs::Solver) = check(ccall((:cimpc_gain_latch, LIB), Cint, (Ptr{Cvoid},), hs.h), hs.h)
+"u (nu x B) = (u1 + K ([q_ref[1]; q_ref[2]] - [q0; q_cur])) / n_sample with q0 = q_cur - n_sample (q_cur - q_prev); q_prev, q_cur: nq x B."
+function gain_feedback!(hs::Solver, u::Matrix{Float64}, q_prev::Matrix{Float64}, q_cur::Matrix{Float64}, n_sample::Real)
+    check(ccall((:cimpc_gain_feedback, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}),
+                hs.h, q_prev, q_cur, n_sample, u), hs.h)
+    return u
+end
+
 end # module
 
 # executed in the INCLUDING module (ContactImplicitMPC): `eval(opts.solver)` of newton.jl:86 looks the constructor up there

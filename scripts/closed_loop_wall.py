@@ -2,10 +2,11 @@
 """examples/centroidal_quadruped/continuous_wall.jl with BOTH sides on the device: the MPC policy on the wall model
 (:configuration mode, H_mpc = 5, N_sample = 5, κ_mpc 2e-4, TrackingVelocityObjective of :41-51, IP r_tol 1e-4 / undercut 5,
 Newton r_tol 3e-5 / max_iter 5) and the device wall plant (CIMPC_PLANT_CENTROIDAL_WALL), for B robots that carry different
-payloads (a constant body force the controller does not know about).  The example's `gains = true` (its continuous-time policy)
-is not part of this loop: the discrete CIMPCPolicy acts alone.  Prints per robot: body height / orientation drift against the
+payloads (a constant body force the controller does not know about).  The example's `gains = true` is off by default - the discrete
+CIMPCPolicy acts alone; `--gains` adds the time-varying LQR feedback of `reference_gains` to every control (CIMPCPolicy(gains=True):
+the feedback line of the example's continuous-time policy placed in the discrete one).  Prints per robot: body height / orientation drift against the
 gait, the front-left foot's x and wall force over the stand, Newton iterations per solve.
-usage: python scripts/closed_loop_wall.py [--steps 250] [--payload 0 -5 -10 -20]"""
+usage: python scripts/closed_loop_wall.py [--steps 250] [--payload 0 -5 -10 -20] [--gains]"""
 import argparse
 import os
 import sys
@@ -19,7 +20,7 @@ from contactimplicitmpc.jl_amd import InteriorPointOptions, NewtonOptions, gait_
 from contactimplicitmpc.jl_amd.policy import CIMPCPolicy  # noqa: E402
 
 
-def run(steps=250, payload=(0.0, -5.0, -10.0, -20.0), H_mpc=5, N_sample=5, verbose=True):
+def run(steps=250, payload=(0.0, -5.0, -10.0, -20.0), H_mpc=5, N_sample=5, verbose=True, gains=False):
     kappa = 2e-4
     m = lcp_models.CentroidalQuadrupedWall()
     gait = gait_io.load_gait(os.path.join(ROOT, "tests", "golden", "gaits", "wall_stand_FL_4.jld2"))
@@ -31,7 +32,7 @@ def run(steps=250, payload=(0.0, -5.0, -10.0, -20.0), H_mpc=5, N_sample=5, verbo
     obj_v = tile(np.diag(1e-3 * np.concatenate([np.ones(3), 1e3 * np.ones(3), np.ones(12)])))
     pol = CIMPCPolicy(P, obj_q, obj_u, H_mpc=H_mpc, N_sample=N_sample, B=B, mode=0, obj_v=obj_v, v_target=np.zeros((H_mpc, 18)),
                       n_opts=NewtonOptions(kappa=kappa, r_tol=3e-5, max_iter=5),
-                      ip_opts=InteriorPointOptions(kappa_tol=kappa, r_tol=1e-4, undercut=5.0))
+                      ip_opts=InteriorPointOptions(kappa_tol=kappa, r_tol=1e-4, undercut=5.0), gains=gains)
     rnorm = []                                                                          # each solve's final Newton residual norm
     solve = pol.solver.newton_solve
     def recording(*a, **k):
@@ -54,10 +55,10 @@ def run(steps=250, payload=(0.0, -5.0, -10.0, -20.0), H_mpc=5, N_sample=5, verbo
     out = []
     for r in range(B):
         dz = q[2:, r, 2] - P.q[np.minimum(np.arange(steps) // N_sample + 2, gait.H + 1), 2]
-        out.append(dict(payload_N=float(payload[r]), height_drift_max=float(np.abs(dz).max()),
+        out.append(dict(payload_N=float(payload[r]), controls_finite=bool(np.isfinite(u[:, r]).all()), height_drift_max=float(np.abs(dz).max()),
                         orientation_max=float(np.abs(q[:, r, 3:6]).max()), fl_x_max=float(q[:, r, 6].max()),
                         fl_wall_gamma_min_on_wall=float(g[on_wall, r, 4].min()) if on_wall.any() else float("nan"),
-                        fl_wall_gamma_max=float(g[:, r, 4].max()), fl_wall_gamma_max_on_wall=float(g[on_wall, r, 4].max()), newton_iters_mean=float(iters[:, r].mean()),
+                        fl_wall_gamma_max=float(g[:, r, 4].max()), fl_wall_gamma_max_on_wall=float(g[on_wall, r, 4].max()) if on_wall.any() else float("nan"), newton_iters_mean=float(iters[:, r].mean()),
                         newton_iters_max=int(iters[:, r].max()), newton_rnorm_max=float(rnorm[:, r].max())))
         if verbose:
             o = out[-1]
@@ -74,5 +75,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=250)
     ap.add_argument("--payload", type=float, nargs="*", default=[0.0, -5.0, -10.0, -20.0])
+    ap.add_argument("--gains", action="store_true", help="add the reference_gains feedback to every control")
     a = ap.parse_args()
-    run(a.steps, tuple(a.payload))
+    run(a.steps, tuple(a.payload), gains=a.gains)
