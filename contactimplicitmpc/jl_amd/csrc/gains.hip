@@ -137,7 +137,8 @@ struct TvlqrArgs {
     int n, m, T, n_ab, n_q, n_r, n_keep;
     const double *A, *B, *Q, *R;       // problem p at A + p n_ab n^2, B + p n_ab n m, Q + p n_q n^2, R + p n_r m^2
     double *K, *P1;                    // K + p n_keep m n; P1 + p n^2 or null
-    int* status;                       // [n_prob]: 0, or the 1-based step whose R + B'PB had a zero or non-finite pivot
+    int* status;                       // [n_prob]: 0, or the first 1-based step (in walk order, T - 1 first) whose R + B'PB had a zero or
+                                       // non-finite pivot, or whose K_t or updated P holds a non-finite entry
     const int* dyn_status;             // null, or the dynamics kernel's word: anything but GAINS_NO_KNOT and the chain is not walked
 };
 
@@ -209,6 +210,7 @@ __global__ __launch_bounds__(GAINS_THREADS) void tvlqr_kernel(TvlqrArgs a) {
         for (int e = tid; e < n * n; e += GAINS_THREADS) P[e] = QT[e];
     }
     for (int t = a.T - 2; t >= 0; --t) {
+        bool finite = true;            // of the entries of K_t and of the updated P this thread computes
         const double* At = Ag + (size_t)(t % a.n_ab) * n * n;
         const double* Bt = Bg + (size_t)(t % a.n_ab) * n * m;
         const double* Rt = Rg + (a.n_r == 1 ? 0 : (size_t)t * m * m);
@@ -263,6 +265,7 @@ __global__ __launch_bounds__(GAINS_THREADS) void tvlqr_kernel(TvlqrArgs a) {
                 s /= G[k * m + k];
                 col[k] = s;
                 KT[k * n + tid] = s;
+                finite = finite && isfinite(s);
             }
         }
         __syncthreads();
@@ -280,8 +283,13 @@ __global__ __launch_bounds__(GAINS_THREADS) void tvlqr_kernel(TvlqrArgs a) {
         tile_product<2, 3>(n, n, m, [&](int r, int k) { return KT[k * n + r]; }, [&](int k, int c) { return RK[c * m + k]; },
                            [&](int r, int c, double v) { P[c * n + r] = Qt[c * n + r] + v; });
         tile_product<2, 3>(n, n, n, [&](int r, int k) { return AcT[k * n + r]; }, [&](int k, int c) { return T1[c * n + k]; },
-                           [&](int r, int c, double v) { P[c * n + r] += v; });
-        __syncthreads();
+                           [&](int r, int c, double v) { const double s = P[c * n + r] + v; P[c * n + r] = s; finite = finite && isfinite(s); });
+        // A_t enters F = B'PA and A - B K, Q_t enters P alone: neither meets a pivot test at this step, and at the last step walked
+        // (t = 0) none follows.  A non-finite K_t or P counts as singular here, on the values the threads hold.
+        if (__syncthreads_or(!finite)) {
+            if (tid == 0) a.status[prob] = t + 1;
+            return;
+        }
     }
     if (a.P1) for (int e = tid; e < n * n; e += GAINS_THREADS) a.P1[(size_t)prob * n * n + e] = P[e];
     if (tid == 0) a.status[prob] = 0;
@@ -403,7 +411,7 @@ int reference_gains_run(const GainsJob& J, const std::vector<double>& in, const 
         return gains_fail(CIMPC_ERR_SINGULAR, "rz is singular (a zero or non-finite pivot, or a non-finite dz/dtheta) at knot " + std::to_string(status[0] + 1) +
                                               " (1-based); K is untouched");
     if (status[1] != 0)
-        return gains_fail(CIMPC_ERR_SINGULAR, "R + B'PB is singular (a zero or non-finite pivot) at Riccati step " + std::to_string(status[1]) +
+        return gains_fail(CIMPC_ERR_SINGULAR, "R + B'PB is singular (a zero or non-finite pivot, or a non-finite K or P) at Riccati step " + std::to_string(status[1]) +
                                               " (1-based) of " + std::to_string(J.N * H) + "; K is untouched");
     std::memcpy(K, out.data(), n_K * sizeof(double));
     if (P1) std::memcpy(P1, out.data() + n_K, n_P * sizeof(double));
@@ -490,7 +498,7 @@ extern "C" int cimpc_tvlqr(int n_prob, int n, int m, int T, int n_ab, const doub
     const int* status = reinterpret_cast<const int*>(out.data() + n_K + n_P);
     for (int p = 0; p < n_prob; ++p)
         if (status[p] != 0)
-            return gains_fail(CIMPC_ERR_SINGULAR, "R + B'PB is singular (a zero or non-finite pivot) at Riccati step " + std::to_string(status[p]) +
+            return gains_fail(CIMPC_ERR_SINGULAR, "R + B'PB is singular (a zero or non-finite pivot, or a non-finite K or P) at Riccati step " + std::to_string(status[p]) +
                                                   " (1-based) of " + std::to_string(T - 1) + ", problem " + std::to_string(p) + "; K is untouched");
     std::memcpy(K, out.data(), n_K * sizeof(double));
     if (P1) std::memcpy(P1, out.data() + n_K, n_P * sizeof(double));

@@ -455,7 +455,9 @@ int cimpc_linearize_knots(cimpc_handle h, int model, int t0, int N, int n_terrai
  * null pointers - P1 excepted -, sizes < 1, N < 1, scalings not finite or <= 0, n_q / n_r / n_keep out of range, nth < 2nq + nu,
  * nz < nq, n > 48 or m > 16), then run on the calling thread's current device on the plant's private stream.  A singular step is
  * CIMPC_ERR_SINGULAR and cimpc_last_error(NULL) names the first singular knot or Riccati step (1-based); a non-finite entry of a
- * knot's dz/dtheta counts as singular.  On ANY error the outputs are untouched.
+ * knot's dz/dtheta counts as singular, and so does a non-finite entry of a Riccati step's K_t or updated P (a NaN or Inf in an A_t
+ * or Q_t that no pivot test meets - those of the last step walked, t = 1): the first such step in walk order, T - 1 first, is named.
+ * CIMPC_OK therefore means every entry of K and P1 is finite.  On ANY error the outputs are untouched.
  * The planar models at their shipped gaits are singular here: the 2-D friction rows of quadruped (gait2) and flamingo
  * (gait_forward_36_4) degenerate, rz has an exact zero pivot and the reference's `\` throws there as well.  The gains are a feature
  * of the 3-D cone models (centroidal_quadruped and its wall / box variants, hopper_3D).

@@ -3,7 +3,8 @@ the 3-D cone models with the objective of examples/centroidal_quadruped/continuo
 their torch linearization (`ContactModel.linearize_batch`) and the NumPy restatement's K, P1 (tests/gains_ref.py), each computed once.
 
 The cases are the smallest shapes at which the kernels can still go wrong: nz = 66 is one column past a wavefront, n = 36 no multiple of
-16, m = 12; nz = 114 the multi-wavefront, large-LDS case; nz = 19, n = 14, m = 3 the small one; and one full chain of 710 steps."""
+16, m = 12; nz = 114 the multi-wavefront, large-LDS case; nz = 19, n = 14, m = 3 the small one; one full chain of 710 steps; and the box
+quadruped (plant id 7) stepping over its box.  The shapes no model has are in tests/gains_edge_cases.py."""
 import functools
 import os
 
@@ -22,6 +23,7 @@ CASES = {
     "wall stand, knots 1-3, N = 2": ("centroidal_quadruped_wall", "wall_stand_FL_4.jld2", "gait", 3, 2),
     "hopper_3D in place, knots 1-5, N = 3": ("hopper_3D", "hopper_3D_gait_in_place.jld2", "traj", 5, 3),
     "centroidal trot, all knots, N = 10": ("centroidal_quadruped", "centroidal_inplace_trot_v7.jld2", "gait", None, 10),
+    "box step-over, knots 1-3, N = 2": ("centroidal_quadruped_box", "step_over_box_v0.jld2", "gait", 3, 2),
 }
 
 
