@@ -99,6 +99,10 @@ SIGNATURES = {
     "cimpc_plant_rollout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
                                       _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip]),
     "cimpc_plant_linearize": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, C.c_double, _dp, _dp, _dp]),
+    "cimpc_plant_sensitivity": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, C.c_double, C.c_int, _dp, _ip]),
+    "cimpc_plant_rollout_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
+                                           _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip,
+                                           C.c_double, C.c_int, _dp, _dp, _ip]),
     "cimpc_tvlqr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
     "cimpc_reference_gains_lin": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double,
                                             _dp, _dp]),

@@ -8,6 +8,7 @@
 // is defined by its converged answer (the time-stepping complementarity problem to 1e-8); the CPU restatement used by the
 // tests states the same step.  Robots are independent: B wavefronts, no communication.
 #include <hip/hip_runtime.h>
+#include <climits>
 #include <cstring>
 #include <mutex>
 #include <type_traits>
@@ -17,6 +18,8 @@
 #include "../../../include/cimpc.h"
 #include "plant_model.h"
 #include "plant_rollout_plan.h"
+#include "plant_sensitivity.h"
+#include "plant_sensitivity_plan.h"
 #include "plant_workspace.h"
 
 namespace cimpc {
@@ -43,7 +46,8 @@ struct PlantOpts {
 // What a launch steps: steps t0 .. t0 + n - 1 of a rollout of B robots, all in device memory.  q: (T + 2) x B x nq, rows t0 and t0 + 1
 // read, rows t0 + 2 .. t0 + n + 1 written; u: K_u x n_u x nu, w: K_w x n_w x nw or null (rollout_row picks the row of a step; n_* = 1: one
 // schedule for every robot, B: one per robot); friction mu0 (n_mu = 1) or mu[rb] (n_mu = B); per-step outputs gamma: T x B x nc,
-// b: T x B x nb, status and iters: T x B.  One simulator step is T = 1, t0 = 0, n = 1.
+// b: T x B x nb, status and iters: T x B; z: T x B x nz, the whole converged z of every step (what the step gradients are taken at), or
+// null (every entry point but cimpc_plant_rollout_grad).  One simulator step is T = 1, t0 = 0, n = 1.
 struct PlantRollout {
     double* q;
     const double *u, *w, *mu;
@@ -51,6 +55,7 @@ struct PlantRollout {
     int *status, *iters;
     double mu0, h;
     int t0, n, K_u, n_u, hold_u, K_w, n_w, hold_w, n_mu;
+    double* z;
 };
 
 __device__ __forceinline__ void wsync() { __syncthreads(); }         // one or two wavefronts per workgroup
@@ -302,6 +307,7 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
     }
     for (int i = lane; i < M.nc; i += NT) R.gamma[row * M.nc + i] = zs[nq + i];
     for (int i = lane; i < M.nb(); i += NT) R.b[row * M.nb() + i] = zs[nq + M.nc + i];
+    if (R.z) for (int i = lane; i < nz; i += NT) R.z[row * nz + i] = zs[i];
     if (lane == 0) { R.status[row] = (r_vio < o.r_tol && k_vio < o.kappa_tol) ? 1 : 0; R.iters[row] = it; }
     wsync();                                                           // the next step's z overwrites what the stores above read
     }
@@ -323,10 +329,19 @@ namespace {
 // A simulator step is the rollout T = 1 with one u / w row per robot, and reads back trajectory row 2 alone (q_row0 = 2).  terrain =
 // nullptr (or every terrain flat on a model cimpc_plant_step has) runs the GROUND_FLAT instantiation; the box and the wall (flat only)
 // run their GROUND_ENV instantiations, pushbot and walledcartpole (flat only) GROUND_WALLS.
+// With `grad` (cimpc_plant_rollout_grad) the steps also store their z, one launch of plant_sensitivity_kernel over all T x B entries
+// follows the chunks on the same stream - theta is put together on the device from the rollout's own buffers - and dz, its status and,
+// when asked for, z come back with the rollout's read-back.
+struct RolloutGrad {
+    double reg;
+    int n_cols;
+    double *z, *dz;      // z may be null
+    int* status;
+};
 int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain, const double* q0,
                        const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w, int K_w, int n_w, int hold_w,
                        const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, double* q, int q_row0, double* gamma, double* b,
-                       int* status, int* iters) {
+                       int* status, int* iters, const RolloutGrad* grad = nullptr) {
     using namespace cimpc;
     if (B <= 0 || !q0 || !q1 || !u || !opts || !q || !gamma || !b || !status || !iters || h <= 0.0) return CIMPC_ERR_INVALID;
     if (T < 1 || steps_per_launch < 0 || K_u < 1 || hold_u < 1 || (n_u != 1 && n_u != B) || !mu || (n_mu != 1 && n_mu != B)) return CIMPC_ERR_INVALID;
@@ -335,6 +350,9 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
     bool rough = false;
     if (!plant_model_and_ground(model, B, n_terrain, terrain, &M, &rough)) return CIMPC_ERR_INVALID;
     if (opts->max_iter <= 0 || opts->max_ls < 0 || !(opts->r_tol > 0.0) || !(opts->kappa_tol > 0.0) || !(opts->ls_scale > 0.0 && opts->ls_scale < 1.0))
+        return CIMPC_ERR_INVALID;
+    if (grad && (!grad->dz || !grad->status || !std::isfinite(grad->reg) || grad->reg < 0.0 || grad->n_cols < 1 || grad->n_cols > M.nth() ||
+                 !plant_sensitivity_fits(M.nz(), grad->n_cols) || (long long)T * B > INT_MAX))
         return CIMPC_ERR_INVALID;
     int dev = 0;
     if (!plant_current_device(&dev)) return CIMPC_ERR_NO_DEVICE;
@@ -351,6 +369,9 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
         !plant_grow(&W.d_st, &W.cap_st, 2 * TB))
         return CIMPC_ERR_HIP;
     if (rough && !plant_grow(&W.d_ter, &W.cap_ter, (size_t)n_terrain)) return CIMPC_ERR_HIP;
+    const size_t n_zs = TB * (size_t)M.nz(), n_dz = grad ? TB * (nq + pnc + pnb) * (size_t)grad->n_cols : 0;
+    if (grad && (!plant_grow(&W.d_z, &W.cap_z, n_zs) || !plant_grow(&W.d_grad, &W.cap_grad, n_dz) || !plant_grow(&W.d_grad_st, &W.cap_grad_st, TB)))
+        return CIMPC_ERR_HIP;
     double* dq = W.d_in; double* du = dq + n_q; double* dw = du + n_us; double* dmu = dw + n_ws;
     double* dg = W.d_out; double* db = dg + TB * pnc;
     int* d_st = W.d_st;
@@ -362,7 +383,7 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
     if (ok && n_mus) ok = hipMemcpyAsync(dmu, mu, n_mus * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
     if (ok && rough) ok = hipMemcpyAsync(W.d_ter, terrain, (size_t)n_terrain * sizeof(cimpc_terrain), hipMemcpyHostToDevice, st) == hipSuccess;
     PlantRollout R{dq, du, w ? dw : nullptr, n_mus ? dmu : nullptr, dg, db, d_st, d_st + TB, mu[0], h, 0, 0, K_u, n_u, hold_u, w ? K_w : 1,
-                   w ? n_w : 1, w ? hold_w : 1, n_mu};
+                   w ? n_w : 1, w ? hold_w : 1, n_mu, grad ? W.d_z : nullptr};
     for (int k = 0; ok && k < rollout_chunk_count(T, steps_per_launch); ++k) {
         const RolloutChunk c = rollout_chunk(T, steps_per_launch, k);
         R.t0 = c.t0; R.n = c.n;
@@ -378,6 +399,14 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
         else if (rough) launch(plant_step_kernel<NZM, 64, GROUND_TERRAIN>, 64);
         else launch(plant_step_kernel<NZM, 64, GROUND_FLAT>, 64);
         ok = hipGetLastError() == hipSuccess;
+    }
+    if (ok && grad) {
+        PlantSensSource src{W.d_z, nullptr, dq, du, R.w, R.mu, d_st, R.mu0, h, B, R.K_u, R.n_u, R.hold_u, R.K_w, R.n_w, R.hold_w, n_mu};
+        ok = plant_sensitivity_launch(M, (int)TB, src, rough ? W.d_ter : nullptr, rough ? n_terrain : 0, grad->reg, grad->n_cols, W.d_grad,
+                                      W.d_grad_st, st);
+        ok = ok && hipMemcpyAsync(grad->dz, W.d_grad, n_dz * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipMemcpyAsync(grad->status, W.d_grad_st, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (ok && grad->z) ok = hipMemcpyAsync(grad->z, W.d_z, n_zs * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
     }
     if (ok) ok = hipMemcpyAsync(q, dq + (size_t)q_row0 * row, (size_t)(T + 2 - q_row0) * row * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
                  hipMemcpyAsync(gamma, dg, TB * pnc * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
@@ -409,4 +438,15 @@ extern "C" int cimpc_plant_rollout(int model, int B, int T, int steps_per_launch
     if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
     return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
                               h, opts, q, 0, gamma, b, status, iters);
+}
+
+extern "C" int cimpc_plant_rollout_grad(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                        const double* q0, const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w,
+                                        int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                                        double* q, double* gamma, double* b, int* status, int* iters, double reg, int n_cols, double* z,
+                                        double* dz, int* grad_status) {
+    if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
+    const RolloutGrad grad{reg, n_cols, z, dz, grad_status};
+    return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
+                              h, opts, q, 0, gamma, b, status, iters, &grad);
 }

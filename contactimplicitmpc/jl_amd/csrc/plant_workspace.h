@@ -1,10 +1,12 @@
-// Per-device workspace of the plant entry points (plant_kernel.hip: step, terrain step, rollout; plant_linearize.hip: linearize):
+// Per-device workspace of the plant entry points (plant_kernel.hip: step, terrain step, rollout; plant_linearize.hip: linearize; plant_sensitivity.hip: step gradients):
 // buffers and a private stream live across calls (a simulator step is called thousands of times in a closed loop; allocating and a
 // device-wide synchronize per call stalled everything else on the GPU).  One mutex serializes the entry points; each keeps buffers
 // of its own, grow-only, and all share the stream.
 //   step / rollout  d_in: trajectory (T + 2) x B x nq | u schedule | w schedule | per-robot mu; d_out: gamma | b; d_st: status | iters
 //                   (T x B each); d_ter: the robots' terrains
 //   linearize       d_lin_in: z | theta | terrains (N x nz, N x nth, n_terrain cimpc_terrain); d_lin_out: r0 | rz0 | rth0 (those asked for)
+//   step gradients  d_z: the converged z of every step of a rollout (T x B x nz); d_grad: dz (N x nr x n_cols); d_grad_st: status (N);
+//                   cimpc_plant_sensitivity stages its knots in d_lin_in
 // The prologue the entry points share is stated here once: which model and ground a call names (plant_model_and_ground, no device
 // needed), which device it runs on (plant_current_device), and its workspace with the stream open (plant_ws_open).
 #pragma once
@@ -26,6 +28,9 @@ struct PlantWs {
     size_t cap_in = 0, cap_out = 0, cap_st = 0, cap_ter = 0;
     double *d_lin_in = nullptr, *d_lin_out = nullptr;
     size_t cap_lin_in = 0, cap_lin_out = 0;
+    double *d_z = nullptr, *d_grad = nullptr;
+    int* d_grad_st = nullptr;
+    size_t cap_z = 0, cap_grad = 0, cap_grad_st = 0;
 };
 constexpr int PLANT_MAX_DEVICES = 16;
 extern PlantWs g_plant_ws[PLANT_MAX_DEVICES];      // defined in plant_kernel.hip

@@ -6,7 +6,9 @@ for B independent robots of one of the models of `csrc/plant_model.h` (the plana
 3-D centroidal_quadruped and its box and wall variants, the particles, hopper_3D, pushbot and walledcartpole), on flat ground or on a terrain of terrain.py (`cimpc_plant_step_terrain`),
 `simulate` loops it with a policy and, optionally, a disturbance schedule (src/simulator/disturbances.jl), `rollout` runs an
 open-loop schedule of controls and disturbances in one call with every intermediate state on the device (`cimpc_plant_rollout`).
-Parity: tests/test_gpu_plant.py against the CPU restatement of the same step.
+`diff_sol=True` on `plant_step`, `rollout` and `simulate` adds the step gradients of `simulator(s, T; diff_sol = true)`
+(simulator.jl:23,31,60; `cimpc_plant_rollout_grad`) as a `StepGradients`; `sensitivity` is their kernel on caller-supplied knots.
+Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble solve.
 """
 from __future__ import annotations
 
@@ -55,15 +57,91 @@ def model_dims(model: str):
     raise KeyError(model)
 
 
-def plant_step(model: str, q0, q1, u, mu: float, h: float, w=None, opts: InteriorPointOptions = SIM_OPTS, terrain=None):
+@dataclasses.dataclass
+class StepGradients:
+    """The `GradientTrajectory` of `simulator(s, T; diff_sol = true)`: per simulated step the derivative of [q3; γ1; b1] (the rows
+    [q2; γ; b] of the step's z) with respect to the leading `n_cols` entries of θ = [q0; q1; u1; w1; μ; h], which the reference names
+    q1, q2, u1.  Leading axes (T, B) for a rollout, (B,) for one step.  dz (..., nr, n_cols), row-major, nr = nq + nc + nb; z (..., nz)
+    the converged z the derivative is taken at; status (...,): 1, or 0 where the step is not differentiated (it did not converge, or
+    its regularized Jacobian has a zero or non-finite pivot) and its dz is all zeros.  The nine blocks are views of dz."""
+    dz: np.ndarray
+    z: np.ndarray
+    status: np.ndarray
+    nq: int
+    nu: int
+    nc: int
+    nb: int
+
+    def _block(self, row: int, col: int):
+        r = np.cumsum([0, self.nq, self.nc, self.nb])
+        c = np.cumsum([0, self.nq, self.nq, self.nu])
+        if self.dz.shape[-1] < c[col + 1]:
+            raise ValueError(f"dz has {self.dz.shape[-1]} columns of θ; this block needs {c[col + 1]} (grad_cols)")
+        return self.dz[..., r[row]:r[row + 1], c[col]:c[col + 1]]
+
+    dq3_dq1 = property(lambda self: self._block(0, 0))
+    dq3_dq2 = property(lambda self: self._block(0, 1))
+    dq3_du1 = property(lambda self: self._block(0, 2))
+    dgamma1_dq1 = property(lambda self: self._block(1, 0))
+    dgamma1_dq2 = property(lambda self: self._block(1, 1))
+    dgamma1_du1 = property(lambda self: self._block(1, 2))
+    db1_dq1 = property(lambda self: self._block(2, 0))
+    db1_dq2 = property(lambda self: self._block(2, 1))
+    db1_du1 = property(lambda self: self._block(2, 2))
+
+
+def _grad_args(model: str, opts: InteriorPointOptions, grad_reg, grad_cols):
+    """(reg, n_cols) of a `diff_sol=True` call: the defaults κ_tol γ_reg and 2 nq + nu (the reference's nine blocks)."""
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    reg = opts.kappa_tol * opts.gamma_reg if grad_reg is None else float(grad_reg)
+    n_cols = 2 * nq + nu if grad_cols is None else int(grad_cols)
+    if not (reg >= 0.0 and np.isfinite(reg)):
+        raise ValueError("grad_reg must be finite and not negative")
+    if not 1 <= n_cols <= 2 * nq + nu + nw + 2:
+        raise ValueError(f"grad_cols must be in 1 .. {2 * nq + nu + nw + 2}")
+    return reg, n_cols
+
+
+def _rollout_call(model: str, q0, q1, ua, hold_u: int, wa, hold_w: int, mua, h: float, opts, terrain, steps_per_launch: int, T: int, grad):
+    """`cimpc_plant_rollout`, or `cimpc_plant_rollout_grad` with grad = (reg, n_cols): contiguous q0, q1 (B, nq), ua (K, 1 or B, nu),
+    wa None or (K_w, 1 or B, nw), mua (1 or B,) -> (q, gamma, b, status, iters, StepGradients or None)."""
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    B, nb, nz = q1.shape[0], fd * nc, nq + 4 * nc + 2 * fd * nc
+    lib = _lib.load()
+    q = np.zeros((T + 2, B, nq)); g = np.zeros((T, B, nc)); b = np.zeros((T, B, nb))
+    st = np.zeros((T, B), dtype=np.int32); it = np.zeros((T, B), dtype=np.int32)
+    o = _lib.IpOpts(**dataclasses.asdict(opts))
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    ta, nt = (None, 0) if terrain is None else _terrain_array(terrain, B)
+    args = (mid, B, T, int(steps_per_launch), nt, ta, dp(q0), dp(q1), dp(ua), ua.shape[0], ua.shape[1], int(hold_u),
+            dp(wa), 1 if wa is None else wa.shape[0], 1 if wa is None else wa.shape[1], int(hold_w), dp(mua), mua.size,
+            float(h), C.byref(o), dp(q), dp(g), dp(b), ip(st), ip(it))
+    if grad is None:
+        rc = lib.cimpc_plant_rollout(*args)
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_rollout failed ({rc})")
+        return q, g, b, st, it, None
+    reg, n_cols = grad
+    z = np.zeros((T, B, nz)); dz = np.zeros((T, B, n_cols, nq + nc + nb)); gst = np.zeros((T, B), dtype=np.int32)      # the library's blocks are column-major
+    rc = lib.cimpc_plant_rollout_grad(*args, reg, n_cols, dp(z), dp(dz), ip(gst))
+    if rc != 0:
+        raise _lib.CimpcError(f"cimpc_plant_rollout_grad failed ({rc})")
+    return q, g, b, st, it, StepGradients(np.ascontiguousarray(dz.transpose(0, 1, 3, 2)), z, gst, nq, nu, nc, nb)
+
+
+def plant_step(model: str, q0, q1, u, mu: float, h: float, w=None, opts: InteriorPointOptions = SIM_OPTS, terrain=None,
+               diff_sol: bool = False, grad_reg=None, grad_cols=None):
     """One simulator step for B robots: q0, q1 (B, nq), u (B, nu), w (B, nw) or None -> q2 (B, nq), gamma (B, nc),
     b (B, nb), status (B,), iters (B,).  terrain: None (flat ground, `cimpc_plant_step`) or a terrain name / `terrain.Terrain`
     shared by every robot, or a sequence of B of them (`cimpc_plant_step_terrain`; see terrain.py).  A planar model takes the planar
-    terrains, particle and hopper_3D the 3-D ones, pushbot and walledcartpole flat ground alone; any other pairing raises `CimpcError`."""
+    terrains, particle and hopper_3D the 3-D ones, pushbot and walledcartpole flat ground alone; any other pairing raises `CimpcError`.
+    diff_sol=True (simulator.jl:23,31,60) returns one more element, the step's `StepGradients` with leading axis (B,): the same step
+    through `cimpc_plant_rollout_grad` with T = 1; grad_reg (default opts.kappa_tol * opts.gamma_reg) and grad_cols (default 2 nq + nu)
+    as in `sensitivity`."""
     if terrain is None and model in TERRAIN_MODELS:
         terrain = "flat_2D_lc"
     mid, nq, nu, nc, fd, nw = model_dims(model)
-    lib = _lib.load()
     f = lambda a, n: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1, n))
     q0, q1, u = f(q0, nq), f(q1, nq), f(u, nu)
     B = q0.shape[0]
@@ -72,6 +150,12 @@ def plant_step(model: str, q0, q1, u, mu: float, h: float, w=None, opts: Interio
     wa = None if w is None else f(w, nw)
     if wa is not None and wa.shape[0] != B:
         raise ValueError("w must have the same leading dimension as q0")
+    if diff_sol:
+        q, g, b, st, it, grads = _rollout_call(model, q0, q1, u[None], 1, None if wa is None else wa[None], 1, np.array([float(mu)]), h, opts,
+                                               terrain, 0, 1, _grad_args(model, opts, grad_reg, grad_cols))
+        grads = dataclasses.replace(grads, dz=grads.dz[0], z=grads.z[0], status=grads.status[0])
+        return q[2], g[0], b[0], st[0], it[0], grads
+    lib = _lib.load()
     q2 = np.zeros((B, nq)); g = np.zeros((B, nc)); b = np.zeros((B, fd * nc))
     st = np.zeros(B, dtype=np.int32); it = np.zeros(B, dtype=np.int32)
     o = _lib.IpOpts(**dataclasses.asdict(opts))
@@ -166,26 +250,33 @@ class RandomDisturbance:
 
 
 def simulate(model: str, policy, q1, v1, H_sim: int, h_sim: float, mu: float, opts: InteriorPointOptions = SIM_OPTS,
-             disturbances=None, terrain=None):
+             disturbances=None, terrain=None, diff_sol: bool = False, grad_reg=None, grad_cols=None):
     """`simulate!(sim, q1, v1)` for B robots: q[0] = q1 - h v1, q[1] = q1; every step u = policy(q[t+1]) (B, nu),
     w = disturbances(t) (the simulator's `dist` field, simulator.jl:18,62; evaluated by RoboDojo's step as
     `disturbances(sim.dist, x, t)`, disturbances.jl:15,49; None = no disturbance), then the plant step on `terrain` (see
     plant_step).  A policy with an `observe(q2, gamma)` method is handed every step's outcome (the simulator trajectory
-    its altitude update reads, policy.jl:110-117).  Returns (ok, q (H_sim+2, B, nq), u, gamma, b)."""
+    its altitude update reads, policy.jl:110-117).  Returns (ok, q (H_sim+2, B, nq), u, gamma, b); with diff_sol=True one more
+    element, the `StepGradients` of every step with leading axes (H_sim, B) (see `plant_step`)."""
     q1 = np.atleast_2d(np.asarray(q1, dtype=np.float64)); v1 = np.atleast_2d(np.asarray(v1, dtype=np.float64))
     q = [q1 - h_sim * v1, q1.copy()]
-    us, gs, bs = [], [], []
+    us, gs, bs, grads = [], [], [], []
     ok = True
     for t in range(H_sim):
         u = np.atleast_2d(policy(q[t + 1]))
         w = None
         if disturbances is not None:
             w = np.broadcast_to(np.asarray(disturbances(t + 1), dtype=np.float64), (q1.shape[0], model_dims(model)[5]))
-        q2, g, b, st, it = plant_step(model, q[t], q[t + 1], u, mu, h_sim, w=w, opts=opts, terrain=terrain)
+        q2, g, b, st, it, *gr = plant_step(model, q[t], q[t + 1], u, mu, h_sim, w=w, opts=opts, terrain=terrain, diff_sol=diff_sol,
+                                           grad_reg=grad_reg, grad_cols=grad_cols)
+        grads += gr
         ok = ok and bool(st.all())
         if hasattr(policy, "observe"):
             policy.observe(q2, g)
         q.append(q2); us.append(u.copy()); gs.append(g); bs.append(b)
+    if diff_sol:
+        stacked = dataclasses.replace(grads[0], dz=np.array([x.dz for x in grads]), z=np.array([x.z for x in grads]),
+                                      status=np.array([x.status for x in grads]))
+        return ok, np.array(q), np.array(us), np.array(gs), np.array(bs), stacked
     return ok, np.array(q), np.array(us), np.array(gs), np.array(bs)
 
 
@@ -214,14 +305,16 @@ def open_loop_controls(model: str, u, B: int, N_sample: int = 1, steps=None):
 
 
 def rollout(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w_hold: int = 1, opts: InteriorPointOptions = SIM_OPTS,
-            terrain=None, steps=None, steps_per_launch: int = 0):
+            terrain=None, steps=None, steps_per_launch: int = 0, diff_sol: bool = False, grad_reg=None, grad_cols=None):
     """`simulate!(sim, q1, v1)` under an `open_loop_policy(u; N_sample)` for B robots in ONE call (`cimpc_plant_rollout`): the states
     between the steps stay on the device, and every step is bit for bit the `plant_step` that `simulate` would make.  q1, v1 (B, nq) or
     (nq,); u (K, nu) nominal controls shared by every robot or (K, B, nu), each held for N_sample steps and applied as u[k] / N_sample
     (the expression of `OpenLoopPolicy`), the last one from there on; w None or (K_w, nw) / (K_w, B, nw) disturbances applied as they
     stand, each held for w_hold steps; mu a friction coefficient or B of them; terrain as in `plant_step`; steps: simulator steps
     (default K N_sample); steps_per_launch: steps per kernel launch (0: the library's default).  Returns (ok, q (steps + 2, B, nq),
-    u_applied (steps, B, nu), gamma, b, status (steps, B), iters) with q[0] = q1 - h v1, q[1] = q1."""
+    u_applied (steps, B, nu), gamma, b, status (steps, B), iters) with q[0] = q1 - h v1, q[1] = q1.  diff_sol=True
+    (`cimpc_plant_rollout_grad`) returns one more element, the `StepGradients` of every step with leading axes (steps, B): one more
+    launch behind the rollout's differentiates all steps at their converged z; the other return values are bit for bit the same."""
     if terrain is None and model in TERRAIN_MODELS:
         terrain = "flat_2D_lc"
     mid, nq, nu, nc, fd, nw = model_dims(model)
@@ -237,20 +330,11 @@ def rollout(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w
     mua = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
     if mua.size not in (1, B):
         raise ValueError(f"mu: one friction coefficient or one per robot ({B}), got {mua.size}")
-    lib = _lib.load()
     q0 = np.ascontiguousarray(q1 - h * v1); q1 = np.ascontiguousarray(q1)
-    q = np.zeros((T + 2, B, nq)); g = np.zeros((T, B, nc)); b = np.zeros((T, B, fd * nc))
-    st = np.zeros((T, B), dtype=np.int32); it = np.zeros((T, B), dtype=np.int32)
-    o = _lib.IpOpts(**dataclasses.asdict(opts))
-    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
-    ta, nt = (None, 0) if terrain is None else _terrain_array(terrain, B)
-    rc = lib.cimpc_plant_rollout(mid, B, T, int(steps_per_launch), nt, ta, dp(q0), dp(q1), dp(ua), ua.shape[0], ua.shape[1], int(N_sample),
-                                 dp(wa), 1 if wa is None else wa.shape[0], 1 if wa is None else wa.shape[1], int(w_hold), dp(mua), mua.size,
-                                 float(h), C.byref(o), dp(q), dp(g), dp(b), ip(st), ip(it))
-    if rc != 0:
-        raise _lib.CimpcError(f"cimpc_plant_rollout failed ({rc})")
-    return bool(st.all()), q, u_applied, g, b, st, it
+    q, g, b, st, it, grads = _rollout_call(model, q0, q1, ua, N_sample, wa, w_hold, mua, h, opts, terrain, steps_per_launch, T,
+                                           _grad_args(model, opts, grad_reg, grad_cols) if diff_sol else None)
+    out = (bool(st.all()), q, u_applied, g, b, st, it)
+    return out + (grads,) if diff_sol else out
 
 
 def linearize(model: str, z, theta, kappa: float, terrain=None):
@@ -279,6 +363,37 @@ def linearize(model: str, z, theta, kappa: float, terrain=None):
         raise _lib.CimpcError(f"cimpc_plant_linearize failed ({rc})")
     rz0, rth0 = np.ascontiguousarray(rz.transpose(0, 2, 1)), np.ascontiguousarray(rth.transpose(0, 2, 1))
     return (r0[0], rz0[0], rth0[0]) if single else (r0, rz0, rth0)
+
+
+def sensitivity(model: str, z, theta, reg: float, n_cols=None, terrain=None):
+    """The step gradients of N knots on the device (`cimpc_plant_sensitivity`): dz = -R(z, θ; reg)⁻¹ ∂r/∂θ[:, :n_cols], rows [q2; γ; b],
+    where R is ∂r/∂z (κ = 0) with the bilinear rows' two diagonals replaced by max(y2, reg) and max(y1, reg) - this project's
+    definition (DESIGN.md sections 3, 5.5).  z (N, nz), theta (N, nθ) as in `linearize`; n_cols: leading columns of θ (default
+    2 nq + nu, up to nθ); terrain as in `linearize`.  Returns dz (N, nr, n_cols) row-major with nr = nq + nc + nb, and status (N,): 0
+    where a pivot or a result was zero or not finite - that knot's dz is all zeros.  A single knot (1-D z) returns dz (nr, n_cols)
+    and a scalar status."""
+    if terrain is None and model in TERRAIN_MODELS:
+        terrain = "flat_2D_lc"
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    nz, nth, nr = nq + 4 * nc + 2 * fd * nc, 2 * nq + nu + nw + 2, nq + nc + fd * nc
+    n_cols = 2 * nq + nu if n_cols is None else int(n_cols)
+    single = np.ndim(z) == 1
+    za = np.ascontiguousarray(np.asarray(z, dtype=np.float64).reshape(-1, nz))
+    ta = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(-1, nth))
+    N = za.shape[0]
+    if N < 1 or ta.shape[0] != N:
+        raise ValueError(f"z must be (N, {nz}) and theta (N, {nth}) with the same N >= 1")
+    if not 1 <= n_cols <= nth:
+        raise ValueError(f"n_cols must be in 1 .. {nth}")
+    lib = _lib.load()
+    dz = np.zeros((N, n_cols, nr)); st = np.zeros(N, dtype=np.int32)      # the library's blocks are column-major
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    ter, nt = (None, 0) if terrain is None else _terrain_array(terrain, N)
+    rc = lib.cimpc_plant_sensitivity(mid, N, nt, ter, dp(za), dp(ta), float(reg), n_cols, dp(dz), st.ctypes.data_as(C.POINTER(C.c_int)))
+    if rc != 0:
+        raise _lib.CimpcError(f"cimpc_plant_sensitivity failed ({rc})")
+    dz = np.ascontiguousarray(dz.transpose(0, 2, 1))
+    return (dz[0], int(st[0])) if single else (dz, st)
 
 
 def linearizer(model_name: str, terrain=None):

@@ -493,17 +493,24 @@ function _plant_dims(model::Symbol)
 end
 """
     plant_rollout(model, q1, v1, u, μ, h_sim, opts; N_sample = 1, w = nothing, w_hold = 1, terrain = nothing, steps = K N_sample,
-                  steps_per_launch = 0) -> (ok, q, u_applied, γ, b, status, iters)
+                  steps_per_launch = 0, diff_sol = false, grad_reg = nothing, grad_cols = nothing) -> (ok, q, u_applied, γ, b, status, iters)
 
 `simulate!(sim, q1, v1)` under `open_loop_policy(u; N_sample)` for B robots in ONE call, every intermediate state on the device.
 q1, v1: nq x B; u: nu x K (one schedule for every robot) or nu x B x K, nominal controls applied as u[k] / N_sample (policy.jl:26);
 w: nothing, nw x K_w or nw x B x K_w, applied as it stands, each held for w_hold steps; μ: a number or B of them; terrain: nothing
 (flat ground) or a vector of 1 or B `Terrain`.  Returns q: nq x B x (steps + 2) with q[:, :, 1] = q1 - h v1, γ: nc x B x steps,
 b: nb x B x steps, status, iters: B x steps.  Sizes are checked against the model's table; unknown models are an error.
+
+`diff_sol = true` (simulator.jl:23,31,60) appends the step gradients, a named tuple `(dz, z, status)`: dz nr x n_cols x B x steps with
+nr = nq + nc + nb the rows [q2; γ; b] and the columns the leading `grad_cols` of θ = [q0; q1; u1; w1; μ; h] (default 2nq + nu: the nine
+blocks ∂q3∂q1 ... ∂b1∂u1 of the reference's GradientTrajectory are its slices), z: nz x B x steps the converged z of every step, status
+B x steps (0: the step is not differentiated and its block is zero).  `grad_reg` (default κ_tol γ_reg) is the regularization of
+`cimpc_plant_rollout_grad`; every other return value is unchanged.
 """
 function plant_rollout(model::Symbol, q1::Matrix{Float64}, v1::Matrix{Float64}, u::Array{Float64}, μ, h_sim, opts;
                        N_sample::Int = 1, w::Union{Nothing,Array{Float64}} = nothing, w_hold::Int = 1,
-                       terrain::Union{Nothing,Vector{Terrain}} = nothing, steps::Int = size(u, ndims(u)) * N_sample, steps_per_launch::Int = 0)
+                       terrain::Union{Nothing,Vector{Terrain}} = nothing, steps::Int = size(u, ndims(u)) * N_sample, steps_per_launch::Int = 0,
+                       diff_sol::Bool = false, grad_reg = nothing, grad_cols = nothing)
     id, nq, nu, nc, nf, nw = _plant_dims(model)
     B = size(q1, 2)
     (size(q1, 1) == nq && size(v1) == (nq, B)) || error("plant_rollout($model): q1, v1 must be $nq x B")
@@ -524,6 +531,22 @@ function plant_rollout(model::Symbol, q1::Matrix{Float64}, v1::Matrix{Float64}, 
     K_u, n_u = size(ua, 3), size(ua, 2)
     wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
     n_mu = length(μs)
+    if diff_sol
+        nz = nq + 4 * nc + 2 * nf * nc; nθ = 2 * nq + nu + nw + 2; nr = nq + nc + nf * nc
+        reg = grad_reg === nothing ? o[].kappa_tol * o[].gamma_reg : Float64(grad_reg)
+        n_cols = grad_cols === nothing ? 2 * nq + nu : Int(grad_cols)
+        (1 <= n_cols <= nθ && reg >= 0) || error("plant_rollout($model): grad_cols must be in 1 .. $nθ and grad_reg >= 0")
+        z = zeros(nz, B, steps); dz = zeros(nr, n_cols, B, steps); grad_status = zeros(Cint, B, steps)
+        check(@ccall LIB.cimpc_plant_rollout_grad(id::Cint, B::Cint, steps::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                                  q0::Ptr{Cdouble}, q1::Ptr{Cdouble}, ua::Ptr{Cdouble}, K_u::Cint, n_u::Cint, N_sample::Cint,
+                                                  wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint, μs::Ptr{Cdouble}, n_mu::Cint,
+                                                  h_sim::Cdouble, o::Ref{IpOpts}, q::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble},
+                                                  status::Ptr{Cint}, iters::Ptr{Cint}, reg::Cdouble, n_cols::Cint, z::Ptr{Cdouble},
+                                                  dz::Ptr{Cdouble}, grad_status::Ptr{Cint})::Cint)
+        rows = min.((0:steps - 1) .÷ N_sample, size(ua, 3) - 1) .+ 1
+        u_applied = repeat(ua[:, :, rows], 1, B ÷ size(ua, 2), 1)
+        return all(status .== 1), q, u_applied, γ, b, status, iters, (dz = dz, z = z, status = grad_status)
+    end
     check(@ccall LIB.cimpc_plant_rollout(id::Cint, B::Cint, steps::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
                                          q0::Ptr{Cdouble}, q1::Ptr{Cdouble}, ua::Ptr{Cdouble}, K_u::Cint, n_u::Cint, N_sample::Cint,
                                          wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint, μs::Ptr{Cdouble}, n_mu::Cint,
@@ -556,6 +579,31 @@ function plant_linearize(model::Symbol, z::VecOrMat{Float64}, θ::VecOrMat{Float
     check(@ccall LIB.cimpc_plant_linearize(id::Cint, N::Cint, n_ter::Cint, ter::Ptr{Terrain}, zs::Ptr{Cdouble}, θs::Ptr{Cdouble},
                                            κ::Cdouble, r0::Ptr{Cdouble}, rz0::Ptr{Cdouble}, rθ0::Ptr{Cdouble})::Cint)
     return r0, rz0, rθ0
+end
+
+# ---- step gradients of N knots: the kernel of `plant_rollout(...; diff_sol = true)` alone ------------------------------------------------
+"""
+    plant_sensitivity(model, z, θ, reg; n_cols = 2nq + nu, terrain = nothing) -> (dz, status)
+
+dz[:, :, k] = -R(z, θ; reg)⁻¹ ∂r/∂θ[:, 1:n_cols] at knot k, rows [q2; γ; b] (nr = nq + nc + nb), where R is ∂r/∂z with the bilinear
+rows' diagonals max(y2, reg), max(y1, reg) (`cimpc_plant_sensitivity`).  z: nz x N, θ: nθ x N (a vector is one knot); status[k] = 0
+marks a knot that is not differentiable (a zero or non-finite pivot or result): its block is zero.
+"""
+function plant_sensitivity(model::Symbol, z::VecOrMat{Float64}, θ::VecOrMat{Float64}, reg::Real;
+                           n_cols::Union{Nothing,Int} = nothing, terrain::Union{Nothing,Vector{Terrain}} = nothing)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    nz = nq + 4 * nc + 2 * nf * nc; nθ = 2 * nq + nu + nw + 2; nr = nq + nc + nf * nc
+    zs = reshape(z, size(z, 1), :); θs = reshape(θ, size(θ, 1), :)
+    N = size(zs, 2)
+    cols = n_cols === nothing ? 2 * nq + nu : n_cols
+    (size(zs, 1) == nz && size(θs) == (nθ, N) && N >= 1) || error("plant_sensitivity($model): z must be $nz x N and θ $nθ x N")
+    (1 <= cols <= nθ) || error("plant_sensitivity($model): n_cols must be in 1 .. $nθ")
+    (terrain === nothing || length(terrain) in (1, N)) || error("plant_sensitivity($model): one terrain or one per knot")
+    dz = zeros(nr, cols, N); status = zeros(Cint, N)
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    check(@ccall LIB.cimpc_plant_sensitivity(id::Cint, N::Cint, n_ter::Cint, ter::Ptr{Terrain}, zs::Ptr{Cdouble}, θs::Ptr{Cdouble},
+                                             reg::Cdouble, cols::Cint, dz::Ptr{Cdouble}, status::Ptr{Cint})::Cint)
+    return dz, status
 end
 
 # ---- A1 on the device: the tables of knots t0 .. t0+N-1 in one call, built by one workgroup per knot -----------------------------------
