@@ -24,6 +24,7 @@
 
 #include "../../../include/cimpc.h"
 #include "gains.h"
+#include "lds_pivot.h"
 #include "plant_linearize.h"
 #include "plant_workspace.h"
 
@@ -34,11 +35,6 @@ namespace {
 constexpr int GAINS_THREADS = 256;
 constexpr int GAINS_NO_KNOT = 0x7f7f7f7f;          // the status word of the dynamics kernel as hipMemsetAsync(0x7f) leaves it
 constexpr size_t GAINS_MAX_LDS = 160 * 1024;       // of a gfx950 CU
-
-__device__ inline bool bad_pivot(double pv) { return !(fabs(pv) > 0.0) || !isfinite(pv); }
-
-// |a| beats |b| in a pivot search: larger, or not a number (which then stays: the pivot test refuses it)
-__device__ inline bool pivot_beats(double a, double b) { return a > b || (a != a && b == b); }
 
 // ---- dz/dtheta of one knot, q rows ---------------------------------------------------------------------------------------------
 // rz: H x (nz x nz) column-major, rth: knot t at rth + t * rth_stride, nz x (>= 2nq + nu) column-major.  The flat copy of rz is rz^T
@@ -59,18 +55,8 @@ __global__ __launch_bounds__(GAINS_THREADS) void gains_dynamics_kernel(int nq, i
     const int wcols = nz + nq;             // the augmented row [W_i | Y_i]
     const int tx = tid & 63, ty = tid >> 6;
     for (int k = 0; k < nz; ++k) {
-        if (tid < 64) {                    // pivot: the first largest |W(i, k)|, i >= k
-            double best = -1.0;
-            int bi = INT_MAX;
-            for (int i = k + tid; i < nz; i += 64) {
-                const double a = fabs(W[i * nz + k]);
-                if (pivot_beats(a, best)) { best = a; bi = i; }
-            }
-            for (int off = 32; off >= 1; off >>= 1) {
-                const double ob = __shfl_xor(best, off, 64);
-                const int oi = __shfl_xor(bi, off, 64);
-                if (pivot_beats(ob, best) || (ob == best && oi < bi)) { best = ob; bi = oi; }
-            }
+        if (tid < 64) {
+            const int bi = lds_pivot_row(W, nz, k, nz);
             if (tid == 0) ipiv[0] = bi;
         }
         __syncthreads();

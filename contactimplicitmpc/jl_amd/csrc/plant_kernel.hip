@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "../../../include/cimpc.h"
+#include "plant_ground.h"
 #include "plant_model.h"
 #include "plant_rollout_plan.h"
 #include "plant_sensitivity.h"
@@ -25,18 +26,6 @@
 namespace cimpc {
 
 namespace {
-
-constexpr int NZM = PLANT_MAX_Q + 4 * PLANT_NC + 2 * PLANT_NB;      // 66 (centroidal); the planar models have 43, hopper_2D 12
-#ifndef CIMPC_NZ_HOPPER_3D
-#define CIMPC_NZ_HOPPER_3D (7 + 4 + 8)      // 19; EXTRA=-DCIMPC_NZ_HOPPER_3D=66 builds the shared size for the comparison of DESIGN.md section 5.5
-#endif
-constexpr int NZ_HOPPER_3D = CIMPC_NZ_HOPPER_3D;                    // hopper_3D on terrain steps on an instantiation of its own size
-static_assert(NZ_HOPPER_3D >= 19, "hopper_3D: nz = 19");
-#ifndef CIMPC_NZ_WALLS
-#define CIMPC_NZ_WALLS (4 + 8 + 8)          // 20; EXTRA=-DCIMPC_NZ_WALLS=66 builds the shared size for the comparison of DESIGN.md section 5.5
-#endif
-constexpr int NZ_WALLS = CIMPC_NZ_WALLS;                            // pushbot (nz = 18) and walledcartpole (nz = 20) step on an instantiation of their own size
-static_assert(NZ_WALLS >= 20, "walledcartpole: nz = 20");
 
 struct PlantOpts {
     double r_tol, kappa_tol, kc_floor, eps_min, ls_scale, stall_alpha;
@@ -60,69 +49,36 @@ struct PlantRollout {
 
 __device__ __forceinline__ void wsync() { __syncthreads(); }         // one or two wavefronts per workgroup
 
-__device__ __forceinline__ double wave_max(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+struct LaneMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
+struct LaneMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } };
+struct LaneSum { __device__ double operator()(double a, double b) const { return a + b; } };
 
 }  // namespace
 
-// Reductions over the NT lanes of one robot: one wavefront (NT = 64) or two (NT = 128, combined through the two LDS words red[]).
-template <int NT>
-__device__ __forceinline__ double lanes_max(double v, double* red) {
-    v = wave_max(v);
+// A reduction over the NT lanes of one robot: one wavefront (NT = 64) or two (NT = 128, combined through the two LDS words red[]).
+template <int NT, class OP>
+__device__ __forceinline__ double lanes_reduce(double v, double* red, OP op) {
+    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
     if constexpr (NT == 128) {
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
         __syncthreads();
-        v = fmax(red[0], red[1]);
-        __syncthreads();
-    }
-    return v;
-}
-template <int NT>
-__device__ __forceinline__ double lanes_min(double v, double* red) {
-    v = wave_min(v);
-    if constexpr (NT == 128) {
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        v = fmin(red[0], red[1]);
-        __syncthreads();
-    }
-    return v;
-}
-template <int NT>
-__device__ __forceinline__ double lanes_sum(double v, double* red) {
-    v = wave_sum(v);
-    if constexpr (NT == 128) {
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        v = red[0] + red[1];
+        v = op(red[0], red[1]);
         __syncthreads();
     }
     return v;
 }
 
-// The ground a kernel instantiation stands on.  FLAT: plant_residual (cimpc_plant_step).  TERRAIN: robot rb stands on
-// terrain[n_terrain == 1 ? 0 : rb]; a flat robot still evaluates plant_residual, so its step is the FLAT one (a uniform branch per
-// robot).  ENV: plant_residual_centroidal_env on flat ground, centroidal_quadruped_box (NZ = 66, one wavefront) and
-// centroidal_quadruped_wall (NZ = 114, two wavefronts: lane j evaluates Jacobian column j, and the 114 x 115 LU stays in LDS).
-// WALLS: plant_residual_walls on flat ground, pushbot and walledcartpole (NZ = 20).
-enum { GROUND_FLAT, GROUND_TERRAIN, GROUND_ENV, GROUND_WALLS };
+// Lanes of a robot's workgroup: one wavefront up to the shared size, two for the wall (NZ = 114: lane j evaluates Jacobian column j, and
+// the 114 x 115 LU stays in LDS).
+constexpr int step_threads(int NZ) { return NZ <= NZM ? 64 : 128; }
 
 // Steps R.t0 .. R.t0 + R.n - 1 of robot blockIdx.x's rollout on NT lanes, sized by NZ (A is NZ x NZ + 1): the only statement of the
-// iteration, with reductions over both wavefronts when NT = 128; cimpc_plant_step is its n = 1 use.  Six instantiations: (66, 64, FLAT),
-// (66, 64, TERRAIN), (66, 64, ENV) for the box, (114, 128, ENV) for the wall, (19, 64, TERRAIN) for hopper_3D on terrain and
-// (20, 64, WALLS) for pushbot and walledcartpole, whose per-lane z and r copies and LDS matrix shrink with NZ.  The iteration names the LDS arrays directly: handed
-// to a helper as pointers they cost the TERRAIN instantiation 8-15 %.  Between steps the state stays in LDS:
-// q2 is stored to its trajectory row and shifted into theta (q1 -> q0, q2 -> q1), nothing is read back from global memory.
+// iteration, with reductions over both wavefronts when NT = 128; cimpc_plant_step is its n = 1 use.  Six instantiations, the step
+// instances of plant_ground.h: (66, 64, FLAT), (66, 64, TERRAIN), (66, 64, ENV) for the box, (114, 128, ENV) for the wall,
+// (19, 64, TERRAIN) for hopper_3D on terrain and (20, 64, WALLS) for pushbot and walledcartpole, whose per-lane z and r copies and LDS
+// matrix shrink with NZ.  The iteration names the LDS arrays directly: handed to a helper as pointers they cost
+// the TERRAIN instantiation 8-15 %.  Between steps the state stays in LDS: q2 is stored to its trajectory row
+// and shifted into theta (q1 -> q0, q2 -> q1), nothing is read back from global memory.
 template <int NZ, int NT, int GROUND>
 __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts o, int B, PlantRollout R, const cimpc_terrain* terrain,
                                                         int n_terrain) {
@@ -135,22 +91,17 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
     if (rb >= B) return;
     bool rough = false;
     if constexpr (GROUND == GROUND_TERRAIN) {
-        static_assert(sizeof(cimpc_terrain) % sizeof(double) == 0 && sizeof(cimpc_terrain) / sizeof(double) <= 64, "one word per lane");
-        const double* src = reinterpret_cast<const double*>(terrain + (n_terrain == 1 ? 0 : rb));
-        if (lane < (int)(sizeof(cimpc_terrain) / sizeof(double))) reinterpret_cast<double*>(&ter)[lane] = src[lane];
+        plant_stage_terrain(ter, terrain, n_terrain, rb, lane);
         wsync();
-        rough = ter.kind != CIMPC_TERRAIN_FLAT || M.kind == PLANT_KIND_PARTICLE_2D;
+        rough = plant_rough(M, ter);
     }
+    // plant_ground_residual of plant_ground.h, spelled out: through the helper pushbot's step came out with other bits
     auto residual = [&](const auto* zz, double kappa, auto* rr) {
         using T = std::remove_const_t<std::remove_pointer_t<decltype(zz)>>;
-        if constexpr (GROUND == GROUND_ENV) {
-            plant_residual_centroidal_env<T>(M, zz, ths, kappa, rr);
-        } else if constexpr (GROUND == GROUND_WALLS) {
-            plant_residual_walls<T>(M, zz, ths, kappa, rr);
-        } else {
-            if constexpr (GROUND == GROUND_TERRAIN) {
-                if (rough) { plant_residual_terrain<T>(M, ter, zz, ths, kappa, rr); return; }
-            }
+        if constexpr (GROUND == GROUND_ENV) plant_residual_centroidal_env<T>(M, zz, ths, kappa, rr);
+        else if constexpr (GROUND == GROUND_WALLS) plant_residual_walls<T>(M, zz, ths, kappa, rr);
+        else {
+            if constexpr (GROUND == GROUND_TERRAIN) if (rough) return plant_residual_terrain<T>(M, ter, zz, ths, kappa, rr);
             plant_residual<T>(M, zz, ths, kappa, rr);
         }
     };
@@ -173,13 +124,13 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
     auto violations = [&](const double* r, double& r_vio, double& k_vio) {
         double a = 0.0, c = 0.0;
         for (int i = lane; i < nz; i += NT) { const double v = fabs(r[i]); if (i < nxy) a = fmax(a, v); else c = fmax(c, v); }
-        r_vio = lanes_max<NT>(a, red); k_vio = lanes_max<NT>(c, red);
+        r_vio = lanes_reduce<NT>(a, red, LaneMax{}); k_vio = lanes_reduce<NT>(c, red, LaneMax{});
     };
     // largest a in (0, 1] with y - a dy >= (1 - tau) y on the complementarity pairs
     auto step_length = [&](const double* D, double tau) {
         double a = 1.0;
         for (int i = nq + lane; i < nz; i += NT) { const double dy = D[i]; if (dy > 0.0) a = fmin(a, tau * zs[i] / dy); }
-        return lanes_min<NT>(a, red);
+        return lanes_reduce<NT>(a, red, LaneMin{});
     };
     // A = dr/dz at zs (a lane evaluates columns lane, lane + NT, ...), then LU with partial pivoting (rows lane, lane + NT, ...)
     auto factorize = [&]() {
@@ -248,8 +199,8 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
     for (int t = R.t0; t < R.t0 + R.n; ++t) {
     // u1, w1 of step t, z = (q1, 1, ..., 1)
     {
-        const double* ut = R.u + ((size_t)rollout_row(t, R.hold_u, R.K_u) * R.n_u + (R.n_u == 1 ? 0 : rb)) * nu;
-        const double* wt = R.w ? R.w + ((size_t)rollout_row(t, R.hold_w, R.K_w) * R.n_w + (R.n_w == 1 ? 0 : rb)) * M.nw : nullptr;
+        const double* ut = rollout_schedule(R.u, t, R.hold_u, R.K_u, R.n_u, rb, nu);
+        const double* wt = R.w ? rollout_schedule(R.w, t, R.hold_w, R.K_w, R.n_w, rb, M.nw) : nullptr;
         for (int i = lane; i < nu + M.nw; i += NT) ths[2 * nq + i] = i < nu ? ut[i] : wt ? wt[i - nu] : 0.0;
     }
     for (int i = lane; i < nz; i += NT) zs[i] = i < nq ? ths[nq + i] : 1.0;
@@ -272,7 +223,7 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
             s_mu += y1 * y2;
             s_aff += (y1 - a_aff * ds[nq + t]) * (y2 - a_aff * ds[nq + ny + t]);
         }
-        const double mu_c = lanes_sum<NT>(s_mu, red) / ny, mu_aff = lanes_sum<NT>(s_aff, red) / ny;
+        const double mu_c = lanes_reduce<NT>(s_mu, red, LaneSum{}) / ny, mu_aff = lanes_reduce<NT>(s_aff, red, LaneSum{}) / ny;
         double sg = fmin(fmax(mu_aff / mu_c, 0.0), 1.0);
         sg = sg * sg * sg;
         const double kc = fmax(sg * mu_c, o.kc_floor);
@@ -312,7 +263,6 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
     wsync();                                                           // the next step's z overwrites what the stores above read
     }
 }
-constexpr int NZ_WALL = PLANT_MAX_Q + 4 * PLANT_WALL_NC + 2 * PLANT_WALL_NB;      // 114
 
 }  // namespace cimpc
 
@@ -387,18 +337,13 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
     for (int k = 0; ok && k < rollout_chunk_count(T, steps_per_launch); ++k) {
         const RolloutChunk c = rollout_chunk(T, steps_per_launch, k);
         R.t0 = c.t0; R.n = c.n;
-        auto launch = [&](auto kernel, int nt) {
-            hipLaunchKernelGGL(kernel, dim3(B), dim3(nt), 0, st, M, o, B, R, rough ? W.d_ter : nullptr, rough ? n_terrain : 0);
-        };
-        // hopper_3D (nz = 19): on terrain its own size measured level with the shared one (0.6 % faster, inside the spread), on flat
-        // ground 1.8 % slower, so the flat hopper stays on the shared FLAT instantiation
-        if (M.kind == PLANT_KIND_PUSHBOT || M.kind == PLANT_KIND_WALLEDCARTPOLE) launch(plant_step_kernel<NZ_WALLS, 64, GROUND_WALLS>, 64);
-        else if (M.kind == PLANT_KIND_HOPPER_3D && rough) launch(plant_step_kernel<NZ_HOPPER_3D, 64, GROUND_TERRAIN>, 64);
-        else if (M.kind == PLANT_KIND_CENTROIDAL_BOX) launch(plant_step_kernel<NZM, 64, GROUND_ENV>, 64);
-        else if (M.kind == PLANT_KIND_CENTROIDAL_WALL) launch(plant_step_kernel<NZ_WALL, 128, GROUND_ENV>, 128);
-        else if (rough) launch(plant_step_kernel<NZM, 64, GROUND_TERRAIN>, 64);
-        else launch(plant_step_kernel<NZM, 64, GROUND_FLAT>, 64);
-        ok = hipGetLastError() == hipSuccess;
+        ok = plant_visit_instance(M, rough, true, [&](auto tag) {
+            using I = decltype(tag);
+            constexpr int NT = step_threads(I::NZ);
+            auto kernel = plant_step_kernel<I::NZ, NT, I::GROUND>;
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(NT), 0, st, M, o, B, R, rough ? W.d_ter : nullptr, rough ? n_terrain : 0);
+            return hipGetLastError() == hipSuccess;
+        });
     }
     if (ok && grad) {
         PlantSensSource src{W.d_z, nullptr, dq, du, R.w, R.mu, d_st, R.mu0, h, B, R.K_u, R.n_u, R.hold_u, R.K_w, R.n_w, R.hold_w, n_mu};

@@ -3,6 +3,7 @@
 // their public id (cimpc.h: CIMPC_PLANT_*), so that plant_model.h stays out of the caller.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <vector>
 
 #include "../../../include/cimpc.h"
 
@@ -17,6 +18,19 @@ struct PlantLinearizeDims {
 // CIMPC_ERR_INVALID.
 int plant_linearize_check(int model, int N, int n_terrain, const cimpc_terrain* terrain, const double* z, const double* theta, double kappa,
                           PlantLinearizeDims* d);
+
+// The knots of a call on the device, where cimpc_plant_linearize and cimpc_plant_sensitivity stage them: z | theta | terrains packed
+// into `host`, the workspace's d_lin_in grown to take them and one upload enqueued on the workspace's stream.  The caller holds
+// g_plant_mu and keeps the PlantKnots until it has synchronized the stream.  n_terrain_up: PlantLinearizeDims' (0: d_ter is null).
+// False: the buffer could not be grown or the copy not enqueued.
+struct PlantWs;
+struct PlantKnots {
+    std::vector<double> host;
+    const double *d_z = nullptr, *d_th = nullptr;
+    const cimpc_terrain* d_ter = nullptr;
+};
+bool plant_stage_knots(PlantWs& W, int N, int nz, int nth, int n_terrain_up, const double* z, const double* theta, const cimpc_terrain* terrain,
+                       PlantKnots* k);
 
 // N knots on `st`, the kernel instantiation cimpc_plant_linearize takes.  Device pointers: z N x nz, theta N x nth, d_ter
 // n_terrain (1 or N) terrains or null; outputs r0 N x nz, rz0 N x (nz x nz), rth0 N x (nz x nth), column-major, a null one is

@@ -8,7 +8,6 @@
 #include <cmath>
 #include <cstring>
 #include <mutex>
-#include <type_traits>
 #include <vector>
 
 // No fused multiply-adds in this translation unit, the residuals of plant_model.h included: every operation rounds as IEEE double, so
@@ -17,26 +16,15 @@
 #pragma clang fp contract(off)
 
 #include "../../../include/cimpc.h"
+#include "plant_ground.h"
 #include "plant_linearize.h"
 #include "plant_model.h"
 #include "plant_workspace.h"
 
 namespace cimpc {
 
-namespace {
-// The ground of an instantiation, as in plant_kernel.hip.  FLAT: plant_residual.  TERRAIN: knot k stands on
-// terrain[n_terrain == 1 ? 0 : k], staged in LDS; a flat knot (or no terrain at all) evaluates plant_residual.  ENV:
-// plant_residual_centroidal_env (box, wall).  WALLS: plant_residual_walls (pushbot, walledcartpole).
-enum { GROUND_FLAT, GROUND_TERRAIN, GROUND_ENV, GROUND_WALLS };
-
-constexpr int NZM = PLANT_MAX_Q + 4 * PLANT_NC + 2 * PLANT_NB;                       // 66
-constexpr int NTHM = 2 * PLANT_MAX_Q + PLANT_MAX_U + PLANT_NW + 2;                   // 53
-constexpr int NZ_WALL = PLANT_MAX_Q + 4 * PLANT_WALL_NC + 2 * PLANT_WALL_NB;         // 114
-constexpr int NZ_HOPPER_3D = 19, NTH_HOPPER_3D = 22;
-constexpr int NZ_WALLS = 20, NTH_WALLS = 15;                                         // walledcartpole; pushbot has 18 and 10
-constexpr int TERRAIN_WORDS = (int)(sizeof(cimpc_terrain) / sizeof(double));
-static_assert(sizeof(cimpc_terrain) % sizeof(double) == 0 && TERRAIN_WORDS <= 64, "a terrain is staged one word per lane");
-}  // namespace
+// Lanes of a knot's workgroup: one pass over the nz + nth columns where at most three wavefronts hold them (28, 35, 41 | 77, 119 | 167)
+constexpr int linearize_threads(int NZ, int NTH) { return (NZ + NTH + 63) / 64 * 64; }
 
 // Knot blockIdx.x on NT lanes.  The per-lane z, θ and r copies are sized by the instantiation (NZ, NTH).  z: N x nz, theta: N x nth;
 // r0: N x nz, rz0: N x (nz x nz), rth0: N x (nz x nth), the matrices column-major; a null output is skipped.
@@ -53,34 +41,18 @@ __global__ __launch_bounds__(NT) void plant_linearize_kernel(PlantModel M, int N
     for (int i = lane; i < nz; i += NT) zs[i] = z[(size_t)k * nz + i];
     for (int i = lane; i < nth; i += NT) ths[i] = theta[(size_t)k * nth + i];
     if constexpr (GROUND == GROUND_TERRAIN) {
-        if (terrain) {
-            const double* src = reinterpret_cast<const double*>(terrain + (n_terrain == 1 ? 0 : k));
-            if (lane < TERRAIN_WORDS) reinterpret_cast<double*>(&ter)[lane] = src[lane];
-        }
+        if (terrain) plant_stage_terrain(ter, terrain, n_terrain, k, lane);
     }
     __syncthreads();
     bool rough = false;
-    if constexpr (GROUND == GROUND_TERRAIN) rough = terrain && (ter.kind != CIMPC_TERRAIN_FLAT || M.kind == PLANT_KIND_PARTICLE_2D);
-    auto residual = [&](const auto* zz, const auto* tt, double kap, auto* rr) {
-        using T = std::remove_const_t<std::remove_pointer_t<decltype(zz)>>;
-        if constexpr (GROUND == GROUND_ENV) {
-            plant_residual_centroidal_env<T>(M, zz, tt, kap, rr);
-        } else if constexpr (GROUND == GROUND_WALLS) {
-            plant_residual_walls<T>(M, zz, tt, kap, rr);
-        } else {
-            if constexpr (GROUND == GROUND_TERRAIN) {
-                if (rough) { plant_residual_terrain<T>(M, ter, zz, tt, kap, rr); return; }
-            }
-            plant_residual<T>(M, zz, tt, kap, rr);
-        }
-    };
+    if constexpr (GROUND == GROUND_TERRAIN) rough = terrain && plant_rough(M, ter);
+    auto residual = [&](const auto* zz, const auto* tt, double kap, auto* rr) { plant_ground_residual<GROUND>(M, ter, rough, zz, tt, kap, rr); };
     // columns [c_lo, c_hi) of [rz0 rθ0]: only the halves asked for
     const int c_lo = rz0 ? 0 : nz, c_hi = rth0 ? nz + nth : nz;
     for (int c = c_lo + lane; c < c_hi; c += NT) {
         Dual zl[NZ], rl[NZ];
         DualTh tl[NTH];
-        for (int i = 0; i < nz; ++i) zl[i] = {zs[i], i == c ? 1.0 : 0.0};
-        for (int i = 0; i < nth; ++i) tl[i] = {{ths[i], nz + i == c ? 1.0 : 0.0}};
+        plant_seed_column(nz, nth, zs, ths, c, zl, tl);
         residual(zl, tl, 0.0, rl);
         double* out = c < nz ? rz0 + ((size_t)k * nz + c) * nz : rth0 + ((size_t)k * nth + (c - nz)) * nz;
         for (int i = 0; i < nz; ++i) out[i] = rl[i].d;
@@ -99,21 +71,17 @@ __global__ __launch_bounds__(NT) void plant_linearize_kernel(PlantModel M, int N
 // ---- launch -------------------------------------------------------------------------------------------------------------
 namespace cimpc {
 
-// The instantiation of a model's linearization, chosen in one place: N knots on `st`, all pointers device memory (a null output
-// is skipped; d_ter null: flat ground).  No synchronization.
+// The model's linearization instance (plant_ground.h): N knots on `st`, all pointers device memory (a null output is skipped; d_ter
+// null: flat ground).  No synchronization.
 static bool plant_linearize_launch(const PlantModel& M, int N, const double* d_z, const double* d_th, const cimpc_terrain* d_ter,
                                    int n_terrain, double kappa, double* d_r, double* d_rz, double* d_rth, hipStream_t st) {
-    auto launch = [&](auto kernel, int nt) {
-        hipLaunchKernelGGL(kernel, dim3(N), dim3(nt), 0, st, M, N, d_z, d_th, d_ter, d_ter ? n_terrain : 0, kappa, d_r, d_rz, d_rth);
-    };
-    // lanes: one pass over the columns where a workgroup of at most three wavefronts holds them (28, 35, 41 | 77, 119 | 167)
-    if (M.kind == PLANT_KIND_PUSHBOT || M.kind == PLANT_KIND_WALLEDCARTPOLE) launch(plant_linearize_kernel<NZ_WALLS, NTH_WALLS, 64, GROUND_WALLS>, 64);
-    else if (M.kind == PLANT_KIND_HOPPER_3D) launch(plant_linearize_kernel<NZ_HOPPER_3D, NTH_HOPPER_3D, 64, GROUND_TERRAIN>, 64);
-    else if (M.kind == PLANT_KIND_CENTROIDAL_BOX) launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_ENV>, 128);
-    else if (M.kind == PLANT_KIND_CENTROIDAL_WALL) launch(plant_linearize_kernel<NZ_WALL, NTHM, 192, GROUND_ENV>, 192);
-    else if (d_ter) launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_TERRAIN>, 128);
-    else launch(plant_linearize_kernel<NZM, NTHM, 128, GROUND_FLAT>, 128);
-    return hipGetLastError() == hipSuccess;
+    return plant_visit_instance(M, d_ter != nullptr, false, [&](auto tag) {
+        using I = decltype(tag);
+        constexpr int NT = linearize_threads(I::NZ, I::NTH);
+        auto kernel = plant_linearize_kernel<I::NZ, I::NTH, NT, I::GROUND>;
+        hipLaunchKernelGGL(kernel, dim3(N), dim3(NT), 0, st, M, N, d_z, d_th, d_ter, d_ter ? n_terrain : 0, kappa, d_r, d_rz, d_rth);
+        return hipGetLastError() == hipSuccess;
+    });
 }
 
 // What cimpc_plant_linearize validates without a device, but for the outputs (plant_linearize.h)
@@ -134,6 +102,20 @@ int plant_linearize_check(int model, int N, int n_terrain, const cimpc_terrain* 
     if (int rc = plant_linearize_validate(model, N, n_terrain, terrain, z, theta, kappa, &M, &rough); rc != CIMPC_OK) return rc;
     *d = PlantLinearizeDims{M.nq, M.nu, M.nw, M.nc, M.nb(), rough ? n_terrain : 0};
     return CIMPC_OK;
+}
+
+bool plant_stage_knots(PlantWs& W, int N, int nz, int nth, int n_terrain_up, const double* z, const double* theta, const cimpc_terrain* terrain,
+                       PlantKnots* k) {
+    const size_t n_z = (size_t)N * nz, n_th = (size_t)N * nth, n_ter = (size_t)n_terrain_up * TERRAIN_WORDS;
+    k->host.resize(n_z + n_th + n_ter);
+    std::memcpy(k->host.data(), z, n_z * sizeof(double));
+    std::memcpy(k->host.data() + n_z, theta, n_th * sizeof(double));
+    if (n_ter) std::memcpy(k->host.data() + n_z + n_th, terrain, n_ter * sizeof(double));
+    if (!plant_grow(&W.d_lin_in, &W.cap_lin_in, k->host.size())) return false;
+    k->d_z = W.d_lin_in;
+    k->d_th = k->d_z + n_z;
+    k->d_ter = n_ter ? reinterpret_cast<const cimpc_terrain*>(k->d_th + n_th) : nullptr;
+    return hipMemcpyAsync(W.d_lin_in, k->host.data(), k->host.size() * sizeof(double), hipMemcpyHostToDevice, W.st) == hipSuccess;
 }
 
 bool plant_linearize_launch(int model, int N, const double* d_z, const double* d_th, const cimpc_terrain* d_ter, int n_terrain, double kappa,
@@ -157,23 +139,19 @@ extern "C" int cimpc_plant_linearize(int model, int N, int n_terrain, const cimp
     const size_t nz = (size_t)M.nz(), nth = (size_t)M.nth();
     int dev = 0;
     if (!plant_current_device(&dev)) return CIMPC_ERR_NO_DEVICE;
-    const size_t n_z = (size_t)N * nz, n_th = (size_t)N * nth, n_ter = rough ? (size_t)n_terrain * TERRAIN_WORDS : 0;
+    const size_t n_z = (size_t)N * nz;
     const size_t n_r = r0 ? n_z : 0, n_rz = rz0 ? n_z * nz : 0, n_rth = rth0 ? n_z * nth : 0;
-    std::vector<double> in(n_z + n_th + n_ter), out(n_r + n_rz + n_rth);
-    std::memcpy(in.data(), z, n_z * sizeof(double));
-    std::memcpy(in.data() + n_z, theta, n_th * sizeof(double));
-    if (n_ter) std::memcpy(in.data() + n_z + n_th, terrain, n_ter * sizeof(double));
+    std::vector<double> out(n_r + n_rz + n_rth);
+    PlantKnots in;
     std::lock_guard<std::mutex> lock(g_plant_mu);
     PlantWs* ws = plant_ws_open(dev);
     if (!ws) return CIMPC_ERR_HIP;
     PlantWs& W = *ws;
-    if (!plant_grow(&W.d_lin_in, &W.cap_lin_in, in.size()) || !plant_grow(&W.d_lin_out, &W.cap_lin_out, out.size())) return CIMPC_ERR_HIP;
+    if (!plant_grow(&W.d_lin_out, &W.cap_lin_out, out.size())) return CIMPC_ERR_HIP;
     hipStream_t st = W.st;
-    const double* dz = W.d_lin_in; const double* dth = dz + n_z;
-    const cimpc_terrain* dter = n_ter ? reinterpret_cast<const cimpc_terrain*>(dth + n_th) : nullptr;
     double* dr = r0 ? W.d_lin_out : nullptr; double* drz = rz0 ? W.d_lin_out + n_r : nullptr; double* drth = rth0 ? W.d_lin_out + n_r + n_rz : nullptr;
-    bool ok = hipMemcpyAsync(W.d_lin_in, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok) ok = plant_linearize_launch(M, N, dz, dth, dter, n_terrain, kappa, dr, drz, drth, st);
+    bool ok = plant_stage_knots(W, N, (int)nz, (int)nth, rough ? n_terrain : 0, z, theta, terrain, &in);
+    if (ok) ok = plant_linearize_launch(M, N, in.d_z, in.d_th, in.d_ter, n_terrain, kappa, dr, drz, drth, st);
     if (ok) ok = hipMemcpyAsync(out.data(), W.d_lin_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
     if (!ok) return CIMPC_ERR_HIP;

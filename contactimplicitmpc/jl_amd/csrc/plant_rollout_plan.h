@@ -2,6 +2,7 @@
 // and device: tests/native/plant_rollout_plan_check.cpp builds it with g++).  A rollout of T simulator steps runs as chained launches of
 // at most `steps_per_launch` steps on one stream; the trajectory buffer carries the state from one launch to the next.
 #pragma once
+#include <cstddef>
 
 #if defined(__HIPCC__)
 #define ROLLOUT_HD __host__ __device__
@@ -18,6 +19,12 @@ constexpr int PLANT_ROLLOUT_STEPS_PER_LAUNCH = 64;
 // Row of a K-row schedule that simulator step t (0-based) reads: every row is held for `hold` steps (the reference's N_sample:
 // open_loop_policy, src/simulator/policy.jl:4-34; open_loop_disturbances, disturbances.jl:4-36), the last one from there on.
 ROLLOUT_HD constexpr int rollout_row(int t, int hold, int K) { return t / hold < K - 1 ? t / hold : K - 1; }
+
+// What robot rb reads at step t from a schedule s of K x n x width doubles (n = 1: one schedule for every robot, else one per robot):
+// the u1 or the w1 of the step, as the step kernel and the sensitivity kernel put them into theta.
+ROLLOUT_HD constexpr const double* rollout_schedule(const double* s, int t, int hold, int K, int n, int rb, int width) {
+    return s + ((size_t)rollout_row(t, hold, K) * n + (n == 1 ? 0 : rb)) * width;
+}
 
 // Launch k of a rollout runs steps t0 .. t0 + n - 1.
 struct RolloutChunk { int t0, n; };

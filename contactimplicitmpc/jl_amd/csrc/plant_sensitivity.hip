@@ -8,7 +8,7 @@
 // converged step returns, dr/dz itself has condition numbers of 1e17-1e19 and no float64 solve of it means anything.
 //
 // One workgroup per entry.  The lanes evaluate the residual of plant_model.h on dual numbers (z on Dual, theta on DualTh), one column
-// of [dr/dz | dr/dtheta] each as in plant_linearize.hip, and write it STRAIGHT INTO LDS: the augmented matrix [R | -dr/dtheta] is
+// of [dr/dz | dr/dtheta] each (plant_seed_column, plant_ground.h), and write it STRAIGHT INTO LDS: the augmented matrix [R | -dr/dtheta] is
 // row-major there (a row operation runs over consecutive words, and a lane's column store is conflict-free across the lanes), nz
 // rows of nz + n_cols doubles (plant_sensitivity_plan.h: 62 KB at nz = 66, 150 KB for centroidal_quadruped_wall).  reg is applied,
 // the matrix is eliminated by LU with partial pivoting with all right-hand sides alongside (the FORWARD form: n_cols columns
@@ -19,15 +19,15 @@
 #include <cmath>
 #include <cstring>
 #include <mutex>
-#include <type_traits>
-#include <vector>
 
-// No fused multiply-adds in this translation unit, as in plant_linearize.hip: an entry does not depend on which instantiation computed
-// it (a flat robot of a terrain rollout is the no-terrain call bit for bit), and the elimination rounds as the float64 restatement
-// the tests hold it to.
+// No fused multiply-adds in this translation unit, the residuals of plant_model.h included: an entry does not depend on which
+// instantiation computed it (a flat robot of a terrain rollout is the no-terrain call bit for bit), and the elimination rounds as the
+// float64 restatement the tests hold it to.
 #pragma clang fp contract(off)
 
 #include "../../../include/cimpc.h"
+#include "lds_pivot.h"
+#include "plant_ground.h"
 #include "plant_linearize.h"
 #include "plant_model.h"
 #include "plant_rollout_plan.h"
@@ -37,23 +37,8 @@
 
 namespace cimpc {
 
-namespace {
-enum { GROUND_FLAT, GROUND_TERRAIN, GROUND_ENV, GROUND_WALLS };      // as in plant_linearize.hip
-
 constexpr int SENS_THREADS = 256;
-constexpr int NZM = PLANT_MAX_Q + 4 * PLANT_NC + 2 * PLANT_NB;                       // 66
-constexpr int NTHM = 2 * PLANT_MAX_Q + PLANT_MAX_U + PLANT_NW + 2;                   // 53
-constexpr int NZ_WALL = PLANT_MAX_Q + 4 * PLANT_WALL_NC + 2 * PLANT_WALL_NB;         // 114
-constexpr int NZ_HOPPER_3D = 19, NTH_HOPPER_3D = 22;
-constexpr int NZ_WALLS = 20, NTH_WALLS = 15;                                         // walledcartpole; pushbot has 18 and 10
-constexpr int TERRAIN_WORDS = (int)(sizeof(cimpc_terrain) / sizeof(double));
-static_assert(sizeof(cimpc_terrain) % sizeof(double) == 0 && TERRAIN_WORDS <= 64, "a terrain is staged one word per lane");
 static_assert((NZ_WALL + NTHM) * sizeof(double) + sizeof(cimpc_terrain) <= PLANT_SENS_STATIC_LDS, "the static LDS the plan sets aside");
-
-__device__ inline bool bad_pivot(double pv) { return !(fabs(pv) > 0.0) || !isfinite(pv); }
-// |a| beats |b| in a pivot search: larger, or not a number (which then stays: the pivot test refuses it) - as in gains.hip
-__device__ inline bool pivot_beats(double a, double b) { return a > b || (a != a && b == b); }
-}  // namespace
 
 template <int NZ, int NTH, int GROUND>
 __global__ __launch_bounds__(SENS_THREADS) void plant_sensitivity_kernel(PlantModel M, int N, PlantSensSource S, const cimpc_terrain* terrain,
@@ -77,10 +62,10 @@ __global__ __launch_bounds__(SENS_THREADS) void plant_sensitivity_kernel(PlantMo
     if (S.step_status && S.step_status[e] == 0) { refuse(); return; }      // the same word for every thread
     const int rb = S.q ? e % S.B : e;                                 // the robot or knot whose terrain this entry stands on
     for (int i = tid; i < nz; i += SENS_THREADS) zs[i] = S.z[(size_t)e * nz + i];
-    if (S.q) {                                                        // theta = [q0; q1; u1; w1; mu; h] of step t, as plant_step_kernel holds it
+    if (S.q) {                                                        // theta = [q0; q1; u1; w1; mu; h] of step t, the one plant_step_kernel stepped on
         const int t = e / S.B;
-        const double* ut = S.u + ((size_t)rollout_row(t, S.hold_u, S.K_u) * S.n_u + (S.n_u == 1 ? 0 : rb)) * nu;
-        const double* wt = S.w ? S.w + ((size_t)rollout_row(t, S.hold_w, S.K_w) * S.n_w + (S.n_w == 1 ? 0 : rb)) * M.nw : nullptr;
+        const double* ut = rollout_schedule(S.u, t, S.hold_u, S.K_u, S.n_u, rb, nu);
+        const double* wt = S.w ? rollout_schedule(S.w, t, S.hold_w, S.K_w, S.n_w, rb, M.nw) : nullptr;
         for (int i = tid; i < nq; i += SENS_THREADS) {
             ths[i] = S.q[((size_t)t * S.B + rb) * nq + i];
             ths[nq + i] = S.q[((size_t)(t + 1) * S.B + rb) * nq + i];
@@ -91,34 +76,17 @@ __global__ __launch_bounds__(SENS_THREADS) void plant_sensitivity_kernel(PlantMo
         for (int i = tid; i < nth; i += SENS_THREADS) ths[i] = S.theta[(size_t)e * nth + i];
     }
     if constexpr (GROUND == GROUND_TERRAIN) {
-        if (terrain) {
-            const double* src = reinterpret_cast<const double*>(terrain + (n_terrain == 1 ? 0 : rb));
-            if (tid < TERRAIN_WORDS) reinterpret_cast<double*>(&ter)[tid] = src[tid];
-        }
+        if (terrain) plant_stage_terrain(ter, terrain, n_terrain, rb, tid);
     }
     __syncthreads();
     bool rough = false;
-    if constexpr (GROUND == GROUND_TERRAIN) rough = terrain && (ter.kind != CIMPC_TERRAIN_FLAT || M.kind == PLANT_KIND_PARTICLE_2D);
-    auto residual = [&](const auto* zz, const auto* tt, double kap, auto* rr) {
-        using T = std::remove_const_t<std::remove_pointer_t<decltype(zz)>>;
-        if constexpr (GROUND == GROUND_ENV) {
-            plant_residual_centroidal_env<T>(M, zz, tt, kap, rr);
-        } else if constexpr (GROUND == GROUND_WALLS) {
-            plant_residual_walls<T>(M, zz, tt, kap, rr);
-        } else {
-            if constexpr (GROUND == GROUND_TERRAIN) {
-                if (rough) { plant_residual_terrain<T>(M, ter, zz, tt, kap, rr); return; }
-            }
-            plant_residual<T>(M, zz, tt, kap, rr);
-        }
-    };
+    if constexpr (GROUND == GROUND_TERRAIN) rough = terrain && plant_rough(M, ter);
     // column c of [dr/dz | -dr/dtheta[:, :n_cols]], derivatives at kappa = 0: lane c, c + 256, ... (one pass: nz + n_cols <= 167)
     for (int c = tid; c < ld; c += SENS_THREADS) {
         Dual zl[NZ], rl[NZ];
         DualTh tl[NTH];
-        for (int i = 0; i < nz; ++i) zl[i] = {zs[i], i == c ? 1.0 : 0.0};
-        for (int i = 0; i < nth; ++i) tl[i] = {{ths[i], nz + i == c ? 1.0 : 0.0}};
-        residual(zl, tl, 0.0, rl);
+        plant_seed_column(nz, nth, zs, ths, c, zl, tl);
+        plant_ground_residual<GROUND>(M, ter, rough, zl, tl, 0.0, rl);
         if (c < nz) for (int i = 0; i < nz; ++i) W[i * ld + c] = rl[i].d;
         else for (int i = 0; i < nz; ++i) W[i * ld + c] = -rl[i].d;
     }
@@ -133,18 +101,8 @@ __global__ __launch_bounds__(SENS_THREADS) void plant_sensitivity_kernel(PlantMo
     __syncthreads();
     const int tx = tid & 63, ty = tid >> 6;
     for (int k = 0; k < nz; ++k) {
-        if (tid < 64) {                    // pivot: the first largest |W(i, k)|, i >= k
-            double best = -1.0;
-            int bi = INT_MAX;
-            for (int i = k + tid; i < nz; i += 64) {
-                const double a = fabs(W[i * ld + k]);
-                if (pivot_beats(a, best)) { best = a; bi = i; }
-            }
-            for (int off = 32; off >= 1; off >>= 1) {
-                const double ob = __shfl_xor(best, off, 64);
-                const int oi = __shfl_xor(bi, off, 64);
-                if (pivot_beats(ob, best) || (ob == best && oi < bi)) { best = ob; bi = oi; }
-            }
+        if (tid < 64) {
+            const int bi = lds_pivot_row(W, ld, k, nz);
             if (tid == 0) ipiv[0] = bi;
         }
         __syncthreads();
@@ -187,21 +145,17 @@ __global__ __launch_bounds__(SENS_THREADS) void plant_sensitivity_kernel(PlantMo
     if (tid == 0) status[e] = 1;
 }
 
-// The instantiation of a model's sensitivity, chosen in one place as plant_linearize_launch chooses the linearization's.
+// The model's sensitivity instance (plant_ground.h), the one its linearization runs on.
 bool plant_sensitivity_launch(const PlantModel& M, int N, const PlantSensSource& src, const cimpc_terrain* d_ter, int n_terrain, double reg,
                               int n_cols, double* d_dz, int* d_status, hipStream_t st) {
     const size_t lds = plant_sensitivity_lds(M.nz(), n_cols);
-    auto launch = [&](auto kernel) {
+    return plant_visit_instance(M, d_ter != nullptr, false, [&](auto tag) {
+        using I = decltype(tag);
+        auto kernel = plant_sensitivity_kernel<I::NZ, I::NTH, I::GROUND>;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
         hipLaunchKernelGGL(kernel, dim3(N), dim3(SENS_THREADS), lds, st, M, N, src, d_ter, d_ter ? n_terrain : 0, reg, n_cols, d_dz, d_status);
         return hipGetLastError() == hipSuccess;
-    };
-    if (M.kind == PLANT_KIND_PUSHBOT || M.kind == PLANT_KIND_WALLEDCARTPOLE) return launch(plant_sensitivity_kernel<NZ_WALLS, NTH_WALLS, GROUND_WALLS>);
-    if (M.kind == PLANT_KIND_HOPPER_3D) return launch(plant_sensitivity_kernel<NZ_HOPPER_3D, NTH_HOPPER_3D, GROUND_TERRAIN>);
-    if (M.kind == PLANT_KIND_CENTROIDAL_BOX) return launch(plant_sensitivity_kernel<NZM, NTHM, GROUND_ENV>);
-    if (M.kind == PLANT_KIND_CENTROIDAL_WALL) return launch(plant_sensitivity_kernel<NZ_WALL, NTHM, GROUND_ENV>);
-    if (d_ter) return launch(plant_sensitivity_kernel<NZM, NTHM, GROUND_TERRAIN>);
-    return launch(plant_sensitivity_kernel<NZM, NTHM, GROUND_FLAT>);
+    });
 }
 
 }  // namespace cimpc
@@ -221,24 +175,18 @@ extern "C" int cimpc_plant_sensitivity(int model, int N, int n_terrain, const ci
     if (n_cols < 1 || (size_t)n_cols > nth || !plant_sensitivity_fits((int)nz, n_cols)) return CIMPC_ERR_INVALID;
     int dev = 0;
     if (!plant_current_device(&dev)) return CIMPC_ERR_NO_DEVICE;
-    const size_t n_z = (size_t)N * nz, n_th = (size_t)N * nth, n_ter = (size_t)pd.n_terrain_up * TERRAIN_WORDS, n_dz = (size_t)N * nr * n_cols;
-    std::vector<double> in(n_z + n_th + n_ter);
-    std::memcpy(in.data(), z, n_z * sizeof(double));
-    std::memcpy(in.data() + n_z, theta, n_th * sizeof(double));
-    if (n_ter) std::memcpy(in.data() + n_z + n_th, terrain, n_ter * sizeof(double));
+    const size_t n_dz = (size_t)N * nr * n_cols;
+    PlantKnots in;
     std::lock_guard<std::mutex> lock(g_plant_mu);
     PlantWs* ws = plant_ws_open(dev);
     if (!ws) return CIMPC_ERR_HIP;
     PlantWs& W = *ws;
-    if (!plant_grow(&W.d_lin_in, &W.cap_lin_in, in.size()) || !plant_grow(&W.d_grad, &W.cap_grad, n_dz) ||
-        !plant_grow(&W.d_grad_st, &W.cap_grad_st, (size_t)N))
-        return CIMPC_ERR_HIP;
+    if (!plant_grow(&W.d_grad, &W.cap_grad, n_dz) || !plant_grow(&W.d_grad_st, &W.cap_grad_st, (size_t)N)) return CIMPC_ERR_HIP;
     hipStream_t st = W.st;
-    const cimpc_terrain* dter = n_ter ? reinterpret_cast<const cimpc_terrain*>(W.d_lin_in + n_z + n_th) : nullptr;
+    bool ok = plant_stage_knots(W, N, (int)nz, (int)nth, pd.n_terrain_up, z, theta, terrain, &in);
     PlantSensSource src{};
-    src.z = W.d_lin_in; src.theta = W.d_lin_in + n_z;
-    bool ok = hipMemcpyAsync(W.d_lin_in, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok) ok = plant_sensitivity_launch(M, N, src, dter, n_terrain, reg, n_cols, W.d_grad, W.d_grad_st, st);
+    src.z = in.d_z; src.theta = in.d_th;
+    if (ok) ok = plant_sensitivity_launch(M, N, src, in.d_ter, n_terrain, reg, n_cols, W.d_grad, W.d_grad_st, st);
     if (ok) ok = hipMemcpyAsync(dz, W.d_grad, n_dz * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
                  hipMemcpyAsync(status, W.d_grad_st, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
