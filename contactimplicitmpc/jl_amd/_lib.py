@@ -103,6 +103,12 @@ SIGNATURES = {
     "cimpc_plant_rollout_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
                                            _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip,
                                            C.c_double, C.c_int, _dp, _dp, _ip]),
+    "cimpc_plant_rollout_tape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
+                                           _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip,
+                                           C.c_double, C.c_int, _dp, _ip, C.POINTER(_h)]),
+    "cimpc_plant_tape_vjp": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "cimpc_plant_tape_dims": (C.c_int, [_h, _ip, _ip, _ip, _ip]),
+    "cimpc_plant_tape_destroy": (C.c_int, [_h]),
     "cimpc_tvlqr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),
     "cimpc_reference_gains_lin": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double,
                                             _dp, _dp]),

@@ -21,6 +21,7 @@
 #include "plant_rollout_plan.h"
 #include "plant_sensitivity.h"
 #include "plant_sensitivity_plan.h"
+#include "plant_tape.h"
 #include "plant_workspace.h"
 
 namespace cimpc {
@@ -281,12 +282,14 @@ namespace {
 // run their GROUND_ENV instantiations, pushbot and walledcartpole (flat only) GROUND_WALLS.
 // With `grad` (cimpc_plant_rollout_grad) the steps also store their z, one launch of plant_sensitivity_kernel over all T x B entries
 // follows the chunks on the same stream - theta is put together on the device from the rollout's own buffers - and dz, its status and,
-// when asked for, z come back with the rollout's read-back.
+// when asked for, z come back with the rollout's read-back.  With `tape` (cimpc_plant_rollout_tape, plant_tape.h) that launch writes dz
+// and its status into device memory allocated here for the tape, and dz stays there: it needs no host dz, and n_cols >= 2 nq + nu.
 struct RolloutGrad {
     double reg;
     int n_cols;
     double *z, *dz;      // z may be null
     int* status;
+    cimpc::PlantTapeBuffers* tape = nullptr;
 };
 int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain, const double* q0,
                        const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w, int K_w, int n_w, int hold_w,
@@ -301,9 +304,10 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
     if (!plant_model_and_ground(model, B, n_terrain, terrain, &M, &rough)) return CIMPC_ERR_INVALID;
     if (opts->max_iter <= 0 || opts->max_ls < 0 || !(opts->r_tol > 0.0) || !(opts->kappa_tol > 0.0) || !(opts->ls_scale > 0.0 && opts->ls_scale < 1.0))
         return CIMPC_ERR_INVALID;
-    if (grad && (!grad->dz || !grad->status || !std::isfinite(grad->reg) || grad->reg < 0.0 || grad->n_cols < 1 || grad->n_cols > M.nth() ||
+    if (grad && ((!grad->dz && !grad->tape) || !grad->status || !std::isfinite(grad->reg) || grad->reg < 0.0 || grad->n_cols < 1 || grad->n_cols > M.nth() ||
                  !plant_sensitivity_fits(M.nz(), grad->n_cols) || (long long)T * B > INT_MAX))
         return CIMPC_ERR_INVALID;
+    if (grad && grad->tape && grad->n_cols < 2 * M.nq + M.nu) return CIMPC_ERR_INVALID;
     int dev = 0;
     if (!plant_current_device(&dev)) return CIMPC_ERR_NO_DEVICE;
     const size_t pnc = (size_t)M.nc, pnb = (size_t)M.nb();
@@ -320,8 +324,21 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
         return CIMPC_ERR_HIP;
     if (rough && !plant_grow(&W.d_ter, &W.cap_ter, (size_t)n_terrain)) return CIMPC_ERR_HIP;
     const size_t n_zs = TB * (size_t)M.nz(), n_dz = grad ? TB * (nq + pnc + pnb) * (size_t)grad->n_cols : 0;
-    if (grad && (!plant_grow(&W.d_z, &W.cap_z, n_zs) || !plant_grow(&W.d_grad, &W.cap_grad, n_dz) || !plant_grow(&W.d_grad_st, &W.cap_grad_st, TB)))
-        return CIMPC_ERR_HIP;
+    if (grad && !plant_grow(&W.d_z, &W.cap_z, n_zs)) return CIMPC_ERR_HIP;
+    if (grad && !grad->tape && (!plant_grow(&W.d_grad, &W.cap_grad, n_dz) || !plant_grow(&W.d_grad_st, &W.cap_grad_st, TB))) return CIMPC_ERR_HIP;
+    double* d_dz = W.d_grad;
+    int* d_gst = W.d_grad_st;
+    if (grad && grad->tape) {      // the tape's own memory, the last thing to be allocated: whatever fails from here on frees it
+        PlantTapeBuffers& tp = *grad->tape;
+        if (hipMalloc((void**)&tp.d_dz, n_dz * sizeof(double)) != hipSuccess) { tp.d_dz = nullptr; return CIMPC_ERR_HIP; }
+        if (hipMalloc((void**)&tp.d_status, TB * sizeof(int)) != hipSuccess) {
+            (void)hipFree(tp.d_dz);
+            tp.d_dz = nullptr; tp.d_status = nullptr;
+            return CIMPC_ERR_HIP;
+        }
+        tp.device = dev; tp.M = M;
+        d_dz = tp.d_dz; d_gst = tp.d_status;
+    }
     double* dq = W.d_in; double* du = dq + n_q; double* dw = du + n_us; double* dmu = dw + n_ws;
     double* dg = W.d_out; double* db = dg + TB * pnc;
     int* d_st = W.d_st;
@@ -347,10 +364,9 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
     }
     if (ok && grad) {
         PlantSensSource src{W.d_z, nullptr, dq, du, R.w, R.mu, d_st, R.mu0, h, B, R.K_u, R.n_u, R.hold_u, R.K_w, R.n_w, R.hold_w, n_mu};
-        ok = plant_sensitivity_launch(M, (int)TB, src, rough ? W.d_ter : nullptr, rough ? n_terrain : 0, grad->reg, grad->n_cols, W.d_grad,
-                                      W.d_grad_st, st);
-        ok = ok && hipMemcpyAsync(grad->dz, W.d_grad, n_dz * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-             hipMemcpyAsync(grad->status, W.d_grad_st, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
+        ok = plant_sensitivity_launch(M, (int)TB, src, rough ? W.d_ter : nullptr, rough ? n_terrain : 0, grad->reg, grad->n_cols, d_dz, d_gst, st);
+        if (ok && !grad->tape) ok = hipMemcpyAsync(grad->dz, d_dz, n_dz * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
+        ok = ok && hipMemcpyAsync(grad->status, d_gst, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
         if (ok && grad->z) ok = hipMemcpyAsync(grad->z, W.d_z, n_zs * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
     }
     if (ok) ok = hipMemcpyAsync(q, dq + (size_t)q_row0 * row, (size_t)(T + 2 - q_row0) * row * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
@@ -359,9 +375,23 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
                  hipMemcpyAsync(status, d_st, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
                  hipMemcpyAsync(iters, d_st + TB, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
+    if (!ok && grad && grad->tape) {
+        (void)hipFree(grad->tape->d_dz);
+        (void)hipFree(grad->tape->d_status);
+        grad->tape->d_dz = nullptr; grad->tape->d_status = nullptr;
+    }
     return ok ? CIMPC_OK : CIMPC_ERR_HIP;
 }
 }  // namespace
+
+int cimpc::plant_rollout_to_tape(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain, const double* q0,
+                                 const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w, int K_w, int n_w, int hold_w,
+                                 const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, double* q, double* gamma, double* b,
+                                 int* status, int* iters, double reg, int n_cols, double* z, int* grad_status, PlantTapeBuffers* tape) {
+    const RolloutGrad grad{reg, n_cols, z, nullptr, grad_status, tape};
+    return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
+                              h, opts, q, 0, gamma, b, status, iters, &grad);
+}
 
 extern "C" int cimpc_plant_step(int model, int B, const double* q0, const double* q1, const double* u, const double* w,
                                 double mu, double h, const cimpc_ip_opts* opts, double* q2, double* gamma, double* b,

@@ -1,4 +1,4 @@
-// Per-device workspace of the plant entry points (plant_kernel.hip: step, terrain step, rollout; plant_linearize.hip: linearize; plant_sensitivity.hip: step gradients):
+// Per-device workspace of the plant entry points (plant_kernel.hip: step, terrain step, rollout; plant_linearize.hip: linearize; plant_sensitivity.hip: step gradients; plant_adjoint.hip: the reverse chain):
 // buffers and a private stream live across calls (a simulator step is called thousands of times in a closed loop; allocating and a
 // device-wide synchronize per call stalled everything else on the GPU).  One mutex serializes the entry points; each keeps buffers
 // of its own, grow-only, and all share the stream.
@@ -7,6 +7,8 @@
 //   linearize       d_lin_in: z | theta | terrains (N x nz, N x nth, n_terrain cimpc_terrain); d_lin_out: r0 | rz0 | rth0 (those asked for)
 //   step gradients  d_z: the converged z of every step of a rollout (T x B x nz); d_grad: dz (N x nr x n_cols); d_grad_st: status (N);
 //                   cimpc_plant_sensitivity stages its knots in d_lin_in
+//   reverse chain   d_adj_in: gq | ggamma | gb (those given); d_adj_out: g_q0 | g_q1 | g_u_step | g_w_step | g_mu | g_h; d_adj_cut: n_cut (B).
+//                   A tape's dz and status are NOT here: they belong to the tape (plant_adjoint.hip) and live as long as it does
 // The prologue the entry points share is stated here once: which model and ground a call names (plant_model_and_ground, no device
 // needed), which device it runs on (plant_current_device), and its workspace with the stream open (plant_ws_open).
 #pragma once
@@ -31,6 +33,9 @@ struct PlantWs {
     double *d_z = nullptr, *d_grad = nullptr;
     int* d_grad_st = nullptr;
     size_t cap_z = 0, cap_grad = 0, cap_grad_st = 0;
+    double *d_adj_in = nullptr, *d_adj_out = nullptr;
+    int* d_adj_cut = nullptr;
+    size_t cap_adj_in = 0, cap_adj_out = 0, cap_adj_cut = 0;
 };
 constexpr int PLANT_MAX_DEVICES = 16;
 extern PlantWs g_plant_ws[PLANT_MAX_DEVICES];      // defined in plant_kernel.hip

@@ -8,7 +8,10 @@ for B independent robots of one of the models of `csrc/plant_model.h` (the plana
 open-loop schedule of controls and disturbances in one call with every intermediate state on the device (`cimpc_plant_rollout`).
 `diff_sol=True` on `plant_step`, `rollout` and `simulate` adds the step gradients of `simulator(s, T; diff_sol = true)`
 (simulator.jl:23,31,60; `cimpc_plant_rollout_grad`) as a `StepGradients`; `sensitivity` is their kernel on caller-supplied knots.
-Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble solve.
+`rollout_tape` keeps those gradients on the device as a `RolloutTape`, whose `vjp` backpropagates cotangents of the trajectory to the
+rollout's arguments (`cimpc_plant_rollout_tape`, `cimpc_plant_tape_vjp`); `rollout_torch` is the two as a `torch.autograd.Function`.
+Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble
+solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain.
 """
 from __future__ import annotations
 
@@ -102,9 +105,11 @@ def _grad_args(model: str, opts: InteriorPointOptions, grad_reg, grad_cols):
     return reg, n_cols
 
 
-def _rollout_call(model: str, q0, q1, ua, hold_u: int, wa, hold_w: int, mua, h: float, opts, terrain, steps_per_launch: int, T: int, grad):
+def _rollout_call(model: str, q0, q1, ua, hold_u: int, wa, hold_w: int, mua, h: float, opts, terrain, steps_per_launch: int, T: int, grad,
+                  tape=None):
     """`cimpc_plant_rollout`, or `cimpc_plant_rollout_grad` with grad = (reg, n_cols): contiguous q0, q1 (B, nq), ua (K, 1 or B, nu),
-    wa None or (K_w, 1 or B, nw), mua (1 or B,) -> (q, gamma, b, status, iters, StepGradients or None)."""
+    wa None or (K_w, 1 or B, nw), mua (1 or B,) -> (q, gamma, b, status, iters, StepGradients or None).  tape = keep_z (a bool) with grad:
+    `cimpc_plant_rollout_tape`, whose last element is (z or None, grad_status, the tape's handle)."""
     mid, nq, nu, nc, fd, nw = model_dims(model)
     B, nb, nz = q1.shape[0], fd * nc, nq + 4 * nc + 2 * fd * nc
     lib = _lib.load()
@@ -123,6 +128,14 @@ def _rollout_call(model: str, q0, q1, ua, hold_u: int, wa, hold_w: int, mua, h: 
             raise _lib.CimpcError(f"cimpc_plant_rollout failed ({rc})")
         return q, g, b, st, it, None
     reg, n_cols = grad
+    if tape is not None:      # dz stays on the device (`cimpc_plant_rollout_tape`): (z or None, grad_status, the tape's handle)
+        z = np.zeros((T, B, nz)) if tape else None
+        gst = np.zeros((T, B), dtype=np.int32)
+        handle = C.c_void_p()
+        rc = lib.cimpc_plant_rollout_tape(*args, reg, n_cols, dp(z), ip(gst), C.byref(handle))
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_rollout_tape failed ({rc})")
+        return q, g, b, st, it, (z, gst, handle)
     z = np.zeros((T, B, nz)); dz = np.zeros((T, B, n_cols, nq + nc + nb)); gst = np.zeros((T, B), dtype=np.int32)      # the library's blocks are column-major
     rc = lib.cimpc_plant_rollout_grad(*args, reg, n_cols, dp(z), dp(dz), ip(gst))
     if rc != 0:
@@ -304,17 +317,9 @@ def open_loop_controls(model: str, u, B: int, N_sample: int = 1, steps=None):
     return rows, np.broadcast_to(rows[k], (T, B, rows.shape[2])).copy()
 
 
-def rollout(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w_hold: int = 1, opts: InteriorPointOptions = SIM_OPTS,
-            terrain=None, steps=None, steps_per_launch: int = 0, diff_sol: bool = False, grad_reg=None, grad_cols=None):
-    """`simulate!(sim, q1, v1)` under an `open_loop_policy(u; N_sample)` for B robots in ONE call (`cimpc_plant_rollout`): the states
-    between the steps stay on the device, and every step is bit for bit the `plant_step` that `simulate` would make.  q1, v1 (B, nq) or
-    (nq,); u (K, nu) nominal controls shared by every robot or (K, B, nu), each held for N_sample steps and applied as u[k] / N_sample
-    (the expression of `OpenLoopPolicy`), the last one from there on; w None or (K_w, nw) / (K_w, B, nw) disturbances applied as they
-    stand, each held for w_hold steps; mu a friction coefficient or B of them; terrain as in `plant_step`; steps: simulator steps
-    (default K N_sample); steps_per_launch: steps per kernel launch (0: the library's default).  Returns (ok, q (steps + 2, B, nq),
-    u_applied (steps, B, nu), gamma, b, status (steps, B), iters) with q[0] = q1 - h v1, q[1] = q1.  diff_sol=True
-    (`cimpc_plant_rollout_grad`) returns one more element, the `StepGradients` of every step with leading axes (steps, B): one more
-    launch behind the rollout's differentiates all steps at their converged z; the other return values are bit for bit the same."""
+def _rollout_inputs(model: str, q1, v1, u, mu, N_sample, w, w_hold, terrain, steps):
+    """The arguments of `rollout` checked and laid out for `_rollout_call`: (terrain, q1 (B, nq), v1, ua (K, 1 or B, nu), u_applied
+    (T, B, nu), wa (K_w, 1 or B, nw) or None, mua (1 or B,))."""
     if terrain is None and model in TERRAIN_MODELS:
         terrain = "flat_2D_lc"
     mid, nq, nu, nc, fd, nw = model_dims(model)
@@ -330,11 +335,204 @@ def rollout(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w
     mua = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
     if mua.size not in (1, B):
         raise ValueError(f"mu: one friction coefficient or one per robot ({B}), got {mua.size}")
+    return terrain, q1, v1, ua, u_applied, wa, mua
+
+
+def rollout(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w_hold: int = 1, opts: InteriorPointOptions = SIM_OPTS,
+            terrain=None, steps=None, steps_per_launch: int = 0, diff_sol: bool = False, grad_reg=None, grad_cols=None):
+    """`simulate!(sim, q1, v1)` under an `open_loop_policy(u; N_sample)` for B robots in ONE call (`cimpc_plant_rollout`): the states
+    between the steps stay on the device, and every step is bit for bit the `plant_step` that `simulate` would make.  q1, v1 (B, nq) or
+    (nq,); u (K, nu) nominal controls shared by every robot or (K, B, nu), each held for N_sample steps and applied as u[k] / N_sample
+    (the expression of `OpenLoopPolicy`), the last one from there on; w None or (K_w, nw) / (K_w, B, nw) disturbances applied as they
+    stand, each held for w_hold steps; mu a friction coefficient or B of them; terrain as in `plant_step`; steps: simulator steps
+    (default K N_sample); steps_per_launch: steps per kernel launch (0: the library's default).  Returns (ok, q (steps + 2, B, nq),
+    u_applied (steps, B, nu), gamma, b, status (steps, B), iters) with q[0] = q1 - h v1, q[1] = q1.  diff_sol=True
+    (`cimpc_plant_rollout_grad`) returns one more element, the `StepGradients` of every step with leading axes (steps, B): one more
+    launch behind the rollout's differentiates all steps at their converged z; the other return values are bit for bit the same."""
+    terrain, q1, v1, ua, u_applied, wa, mua = _rollout_inputs(model, q1, v1, u, mu, N_sample, w, w_hold, terrain, steps)
+    T = u_applied.shape[0]
     q0 = np.ascontiguousarray(q1 - h * v1); q1 = np.ascontiguousarray(q1)
     q, g, b, st, it, grads = _rollout_call(model, q0, q1, ua, N_sample, wa, w_hold, mua, h, opts, terrain, steps_per_launch, T,
                                            _grad_args(model, opts, grad_reg, grad_cols) if diff_sol else None)
     out = (bool(st.all()), q, u_applied, g, b, st, it)
     return out + (grads,) if diff_sol else out
+
+
+def fold_schedule(g_step, K: int, hold: int, shared: bool, scale: float = 1.0):
+    """Per-step gradients g_step (T, B, n) folded back onto the schedule rows they were applied from: row min(t // hold, K - 1) takes
+    step t, and every robot when the schedule is shared, added one at a time in ascending (t, b) order, then divided by `scale`.
+    Returns (K, n) shared or (K, B, n)."""
+    T, B, n = g_step.shape
+    acc = np.zeros((K, n) if shared else (K, B, n))
+    for t in range(T):
+        k = min(t // hold, K - 1)
+        if shared:
+            for r in range(B):
+                acc[k] += g_step[t, r]
+        else:
+            acc[k] += g_step[t]
+    return acc / scale
+
+
+@dataclasses.dataclass
+class RolloutCotangents:
+    """What `RolloutTape.vjp` returns: the gradient of a loss on the trajectory with respect to the arguments of `rollout_tape`.
+    q1 (B, nq) = λ[0] + λ[1] and v1 (B, nq) = -h λ[0] (q[0] = q1 - h v1, q[1] = q1); u in the shape the caller passed, (K, nu) or
+    (K, B, nu): `fold_schedule` of u_step (T, B, nu) by N_sample, divided by N_sample (a step applies u[k] / N_sample); w likewise by
+    w_hold, undivided (None without a w, or when grad_cols stops short of its columns); mu (B,), or their sum over the robots when one
+    friction coefficient was given (None: not covered); h = Σ_b (g_h[b] - v1[b]·λ[0][b]) (None: not covered); n_cut (B,): the steps of
+    a robot whose gradient status is 0, through which nothing flows.  g_q0 = λ[0], g_q1 = λ[1] (B, nq), w_step (T, B, nw), g_mu, g_h (B,)
+    are the library's outputs as they came back (None: not covered)."""
+    q1: np.ndarray
+    v1: np.ndarray
+    u: np.ndarray
+    u_step: np.ndarray
+    w: object
+    mu: object
+    h: object
+    n_cut: np.ndarray
+    g_q0: np.ndarray
+    g_q1: np.ndarray
+    w_step: object
+    g_mu: object
+    g_h: object
+
+
+class RolloutTape:
+    """The step gradients of one rollout, kept on the device (`cimpc_plant_rollout_tape`), for any number of `vjp` calls.  model, B, T,
+    n_cols as recorded; grad_status (T, B) as `StepGradients.status`; z (T, B, nz) with keep_z, else None.  `close()` frees the device
+    memory (so does leaving a `with` block, and the finalizer); a closed tape raises on use."""
+
+    def __init__(self, handle, model: str, grad_status, z, v1, h: float, u_shape, N_sample: int, w_shape, w_hold: int, mu_shared: bool):
+        import weakref
+        self._handle, self.model, self.grad_status, self.z = handle, model, grad_status, z
+        dims = [C.c_int() for _ in range(4)]
+        rc = _lib.load().cimpc_plant_tape_dims(handle, *[C.byref(d) for d in dims])
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_tape_dims failed ({rc})")
+        mid, self.B, self.T, self.n_cols = (d.value for d in dims)
+        assert mid == model_dims(model)[0]
+        self._v1, self._h, self._u_shape, self._N_sample, self._w_shape, self._w_hold, self._mu_shared = v1, h, u_shape, N_sample, w_shape, w_hold, mu_shared
+        self._finalizer = weakref.finalize(self, _lib.load().cimpc_plant_tape_destroy, handle)
+
+    closed = property(lambda self: not self._finalizer.alive)
+
+    def close(self):
+        if self._finalizer.alive and self._finalizer() != 0:
+            raise _lib.CimpcError("cimpc_plant_tape_destroy failed")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def vjp(self, gq=None, ggamma=None, gb=None) -> RolloutCotangents:
+        """The reverse chain (`cimpc_plant_tape_vjp`) of cotangents gq (T + 2, B, nq), ggamma (T, B, nc),
+        gb (T, B, nb) - None is zeros, not all three - as a `RolloutCotangents`."""
+        if self.closed:
+            raise ValueError("the tape is closed")
+        mid, nq, nu, nc, fd, nw = model_dims(self.model)
+        B, T, nb = self.B, self.T, fd * nc
+
+        def cot(a, shape, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+            if a.shape != shape:
+                raise ValueError(f"{what} must be {shape}, got {a.shape}")
+            return a
+        gq, ggamma, gb = cot(gq, (T + 2, B, nq), "gq"), cot(ggamma, (T, B, nc), "ggamma"), cot(gb, (T, B, nb), "gb")
+        if gq is None and ggamma is None and gb is None:
+            raise ValueError("at least one of gq, ggamma, gb")
+        c_mu = 2 * nq + nu + nw
+        l0 = np.zeros((B, nq)); l1 = np.zeros((B, nq)); u_step = np.zeros((T, B, nu)); n_cut = np.zeros(B, dtype=np.int32)
+        w_step = np.zeros((T, B, nw)) if self.n_cols >= c_mu else None
+        g_mu = np.zeros(B) if self.n_cols >= c_mu + 1 else None
+        g_h = np.zeros(B) if self.n_cols >= c_mu + 2 else None
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        rc = _lib.load().cimpc_plant_tape_vjp(self._handle, dp(gq), dp(ggamma), dp(gb), dp(l0), dp(l1), dp(u_step), dp(w_step), dp(g_mu), dp(g_h),
+                                              n_cut.ctypes.data_as(C.POINTER(C.c_int)))
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_tape_vjp failed ({rc})")
+        u = fold_schedule(u_step, self._u_shape[0], self._N_sample, len(self._u_shape) == 2, self._N_sample)
+        w = None
+        if w_step is not None and self._w_shape is not None:
+            w = fold_schedule(w_step, self._w_shape[0], self._w_hold, len(self._w_shape) == 2)
+        mu = g_mu
+        if g_mu is not None and self._mu_shared:
+            mu = 0.0
+            for r in range(B):
+                mu = mu + g_mu[r]
+        h = None
+        if g_h is not None:
+            h = 0.0
+            for r in range(B):
+                h = h + (g_h[r] - float(self._v1[r] @ l0[r]))
+        return RolloutCotangents(q1=l0 + l1, v1=-self._h * l0, u=u, u_step=u_step, w=w, mu=mu, h=h, n_cut=n_cut, g_q0=l0, g_q1=l1, w_step=w_step,
+                                 g_mu=g_mu, g_h=g_h)
+
+
+def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w_hold: int = 1, opts: InteriorPointOptions = SIM_OPTS,
+                 terrain=None, steps=None, steps_per_launch: int = 0, grad_reg=None, grad_cols=None, keep_z: bool = False):
+    """`rollout` that records its step gradients on the device instead of returning them (`cimpc_plant_rollout_tape`): the arguments of
+    `rollout(..., diff_sol=True)` -> (ok, q, u_applied, gamma, b, status, iters, tape), the first seven bit for bit those of `rollout`,
+    tape a `RolloutTape` whose `vjp` turns cotangents of (q, gamma, b) into the gradient with respect to q1, v1, u, w, mu and h.
+    grad_cols (default 2 nq + nu, the least a tape takes) up to nθ adds the w, μ and h columns; keep_z also returns every step's z on
+    the tape."""
+    terrain, q1, v1, ua, u_applied, wa, mua = _rollout_inputs(model, q1, v1, u, mu, N_sample, w, w_hold, terrain, steps)
+    (T, B), (mid, nq, nu, nc, fd, nw) = u_applied.shape[:2], model_dims(model)
+    reg, n_cols = _grad_args(model, opts, grad_reg, grad_cols)
+    if n_cols < 2 * nq + nu:
+        raise ValueError(f"grad_cols must be at least {2 * nq + nu} (q0, q1 and u1) for a tape")
+    q0 = np.ascontiguousarray(q1 - h * v1); q1 = np.ascontiguousarray(q1)
+    q, g, b, st, it, (z, gst, handle) = _rollout_call(model, q0, q1, ua, N_sample, wa, w_hold, mua, h, opts, terrain, steps_per_launch, T,
+                                                      (reg, n_cols), tape=bool(keep_z))
+    tape = RolloutTape(handle, model, gst, z, v1.copy(), float(h), np.shape(u), int(N_sample), None if w is None else np.shape(w), int(w_hold),
+                       np.ndim(mu) == 0 or (mua.size == 1 and B > 1))
+    return bool(st.all()), q, u_applied, g, b, st, it, tape
+
+
+def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, **kw):
+    """`rollout_tape` inside `torch.autograd`: q1, v1, u, mu and w may be float64 tensors (on any device; they are staged through the
+    host, as every plant entry point stages its arguments), the keywords are those of `rollout_tape` -> (q, gamma, b, status) tensors on
+    the device of the first tensor given, status an int tensor without a gradient.  `backward` runs `RolloutTape.vjp` on the tape,
+    which lives on the autograd graph - any number of times with retain_graph=True - and gradients reach whichever of q1, v1, u, w, mu
+    require them; grad_cols is raised to cover w and mu when they do."""
+    import torch
+
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    tensors = [a for a in (q1, v1, u, mu, w) if isinstance(a, torch.Tensor)]
+    device = tensors[0].device if tensors else torch.device("cpu")
+    needs = lambda a: isinstance(a, torch.Tensor) and a.requires_grad
+    cols = 2 * nq + nu + (nw + 1 if needs(mu) else nw if needs(w) else 0)
+    kw = dict(kw, grad_cols=max(cols, int(kw.get("grad_cols") or 0)))
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+
+    class _Rollout(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, q1_, v1_, u_, mu_, w_):
+            ok, q, ua, g, b, st, it, tape = rollout_tape(model, host(q1_), host(v1_), host(u_), h, host(mu_), w=host(w_), **kw)
+            ctx.tape = tape
+            ctx.set_materialize_grads(False)
+            status = torch.as_tensor(st, device=device)
+            ctx.mark_non_differentiable(status)
+            return torch.as_tensor(q, device=device), torch.as_tensor(g, device=device), torch.as_tensor(b, device=device), status
+
+        @staticmethod
+        def backward(ctx, gq, ggamma, gb, gstatus):
+            if gq is None and ggamma is None and gb is None:
+                return None, None, None, None, None
+            c = ctx.tape.vjp(host(gq), host(ggamma), host(gb))
+            out = []
+            for k, (a, grad) in enumerate(zip((q1, v1, u, mu, w), (c.q1, c.v1, c.u, c.mu, c.w))):
+                if not ctx.needs_input_grad[k]:
+                    out.append(None)
+                else:
+                    out.append(torch.as_tensor(np.asarray(grad, dtype=np.float64), device=a.device).reshape(a.shape))
+            return tuple(out)
+
+    return _Rollout.apply(q1, v1, u, mu, w)
 
 
 def linearize(model: str, z, theta, kappa: float, terrain=None):

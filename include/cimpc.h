@@ -475,6 +475,49 @@ int cimpc_plant_rollout_grad(int model, int B, int T, int steps_per_launch,
                              double* q, double* gamma, double* b, int* status, int* iters,
                              double reg, int n_cols, double* z, double* dz, int* grad_status);
 
+/* ---- a loss backpropagated through a rollout: the tape of its step gradients on the device, and the reverse chain over it ------------
+ * THIS BUILD'S definition.  A rollout is q[t+2] = step(theta_t), theta_t = [q[t]; q[t+1]; u_t; w_t; mu; h],
+ * t = 0 .. T-1, with u_t, w_t the schedule rows step t applies, and D_t the step's dz block (nr x n_cols; all zeros where its gradient
+ * status is 0).  With cotangents gq (T + 2) x B x nq, ggamma T x B x nc, gb T x B x nb of a loss on the trajectory, per robot:
+ *     lambda[0 .. T+1] = gq
+ *     for t = T-1 .. 0:  a = [lambda[t+2]; ggamma[t]; gb[t]];   v = D_t' a   (v[c] = sum over r = 0 .. nr-1 of D_t[r, c] a[r], ascending r
+ *                        from 0.0, one product and one sum per term, no fused multiply-add)
+ *                        lambda[t+1] += v[nq : 2nq];  lambda[t] += v[0 : nq]   (so lambda[t] = (gq[t] + v_t[0:nq]) + v_{t-1}[nq:2nq])
+ *                        g_u_step[t] = v[2nq : 2nq+nu];  g_w_step[t] = v[the nw columns of w];  g_mu += v[mu];  g_h += v[h]  (t descending)
+ *     g_q0 = lambda[0], g_q1 = lambda[1];  n_cut = the robot's steps whose gradient status is 0: such a step cuts the flow through it
+ *     and is counted, not refused.
+ *
+ * cimpc_plant_rollout_tape: cimpc_plant_rollout_grad without its dz argument - the 25 parameters of cimpc_plant_rollout, reg, n_cols, z
+ * (T x B x nz, may be NULL), grad_status (T x B) - whose sensitivity launch writes dz and its status straight into device memory the
+ * tape owns; dz does not come back to the host.  q, gamma, b, status, iters, z and grad_status are bit for bit those of
+ * cimpc_plant_rollout_grad.  *tape: an opaque handle holding the device index, the model, B, T, n_cols and the two device buffers.
+ * Validated first, without a device: everything cimpc_plant_rollout_grad validates (its dz excepted), n_cols >= 2 nq + nu, a non-null
+ * tape.  On any failure nothing stays allocated and *tape is NULL. */
+typedef struct cimpc_plant_tape_s* cimpc_plant_tape;
+int cimpc_plant_rollout_tape(int model, int B, int T, int steps_per_launch,
+                             int n_terrain, const cimpc_terrain* terrain,
+                             const double* q0, const double* q1,
+                             const double* u, int K_u, int n_u, int hold_u,
+                             const double* w, int K_w, int n_w, int hold_w,
+                             const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                             double* q, double* gamma, double* b, int* status, int* iters,
+                             double reg, int n_cols, double* z, int* grad_status, cimpc_plant_tape* tape);
+
+/* The chain on a tape, any number of times: the cotangents go up, ONE launch walks every robot's chain (a wavefront per robot), the
+ * gradients come back.  gq (T + 2) x B x nq, ggamma T x B x nc, gb T x B x nb: any may be NULL (zeros), not all three.  Outputs:
+ * g_q0, g_q1 B x nq, g_u_step T x B x nu, n_cut B (all required); g_w_step T x B x nw, g_mu B, g_h B may each be NULL, and each is
+ * CIMPC_ERR_INVALID if given while the tape's n_cols does not reach its column (2nq + nu + nw, + 1, + 2).  Runs on the tape's device,
+ * whichever is current, on the plant's private stream.  Validated first, without a device: a null tape, no cotangent, a null required
+ * output, the columns. */
+int cimpc_plant_tape_vjp(cimpc_plant_tape tape, const double* gq, const double* ggamma, const double* gb,
+                         double* g_q0, double* g_q1, double* g_u_step, double* g_w_step, double* g_mu, double* g_h, int* n_cut);
+
+/* What a tape was recorded with; any output may be NULL.  A null tape: CIMPC_ERR_INVALID. */
+int cimpc_plant_tape_dims(cimpc_plant_tape tape, int* model, int* B, int* T, int* n_cols);
+
+/* Frees the tape's device memory and the tape.  NULL is a no-op (CIMPC_OK). */
+int cimpc_plant_tape_destroy(cimpc_plant_tape tape);
+
 /* ---- cimpc_set_linearization_batch from (z, theta) alone: plant model `model` linearized at kappa (cimpc_plant_linearize's kernel and arguments;
  * z0 = z, th0 = theta) and the tables built from its output, all on the handle's device and stream;
  * nothing but z, theta and the terrains goes up, nothing but N status words comes back.  Equal bit for bit to

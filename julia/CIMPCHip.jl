@@ -557,6 +557,108 @@ function plant_rollout(model::Symbol, q1::Matrix{Float64}, v1::Matrix{Float64}, 
     return all(status .== 1), q, u_applied, γ, b, status, iters
 end
 
+# ---- a loss backpropagated through a rollout: the tape of its step gradients on the device and the reverse chain over it ------------
+"""
+The step gradients of one rollout, kept on the device (`cimpc_plant_rollout_tape`).  `close(tape)` frees them; so does the finalizer.
+"""
+mutable struct PlantTape
+    handle::Ptr{Cvoid}
+    model::Symbol
+    B::Int; T::Int; n_cols::Int
+    grad_status::Matrix{Cint}
+    function PlantTape(handle::Ptr{Cvoid}, model::Symbol, B::Int, T::Int, n_cols::Int, grad_status::Matrix{Cint})
+        tape = new(handle, model, B, T, n_cols, grad_status)
+        finalizer(close, tape)
+        return tape
+    end
+end
+function Base.close(tape::PlantTape)
+    if tape.handle != C_NULL
+        @ccall LIB.cimpc_plant_tape_destroy(tape.handle::Ptr{Cvoid})::Cint
+        tape.handle = C_NULL
+    end
+    return nothing
+end
+"""
+    plant_rollout_tape(model, q1, v1, u, μ, h_sim, opts; N_sample = 1, w = nothing, w_hold = 1, terrain = nothing, steps = K N_sample,
+                       steps_per_launch = 0, grad_reg = nothing, grad_cols = nothing) -> (ok, q, u_applied, γ, b, status, iters, tape)
+
+`plant_rollout` that records its step gradients on the device instead of returning them: the first seven values are those of
+`plant_rollout`, `tape` a `PlantTape` for `plant_tape_vjp`.  `grad_cols` (default and least 2nq + nu) up to nθ adds the w, μ and h columns.
+"""
+function plant_rollout_tape(model::Symbol, q1::Matrix{Float64}, v1::Matrix{Float64}, u::Array{Float64}, μ, h_sim, opts;
+                            N_sample::Int = 1, w::Union{Nothing,Array{Float64}} = nothing, w_hold::Int = 1,
+                            terrain::Union{Nothing,Vector{Terrain}} = nothing, steps::Int = size(u, ndims(u)) * N_sample,
+                            steps_per_launch::Int = 0, grad_reg = nothing, grad_cols = nothing)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    B = size(q1, 2)
+    (size(q1, 1) == nq && size(v1) == (nq, B)) || error("plant_rollout_tape($model): q1, v1 must be $nq x B")
+    us = ndims(u) == 2 ? reshape(u, nu, 1, :) : u
+    (ndims(us) == 3 && size(us, 1) == nu && size(us, 2) in (1, B) && size(us, 3) >= 1) || error("plant_rollout_tape($model): u must be $nu x K or $nu x B x K")
+    ws = w === nothing ? nothing : ndims(w) == 2 ? reshape(w, nw, 1, :) : w
+    (ws === nothing || (ndims(ws) == 3 && size(ws, 1) == nw && size(ws, 2) in (1, B) && size(ws, 3) >= 1)) || error("plant_rollout_tape($model): w must be $nw x K_w or $nw x B x K_w")
+    μs = Float64.(vcat(μ))
+    length(μs) in (1, B) || error("plant_rollout_tape($model): one friction coefficient or one per robot")
+    (terrain === nothing || length(terrain) in (1, B)) || error("plant_rollout_tape($model): one terrain or one per robot")
+    (steps >= 1 && N_sample >= 1 && w_hold >= 1) || error("plant_rollout_tape($model): steps, N_sample, w_hold must be at least 1")
+    ua = us ./ N_sample
+    q0 = q1 .- h_sim .* v1
+    q = zeros(nq, B, steps + 2); γ = zeros(nc, B, steps); b = zeros(nf * nc, B, steps)
+    status = zeros(Cint, B, steps); iters = zeros(Cint, B, steps); grad_status = zeros(Cint, B, steps)
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    K_u, n_u = size(ua, 3), size(ua, 2)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu = length(μs)
+    nθ = 2 * nq + nu + nw + 2
+    reg = grad_reg === nothing ? o[].kappa_tol * o[].gamma_reg : Float64(grad_reg)
+    n_cols = grad_cols === nothing ? 2 * nq + nu : Int(grad_cols)
+    (2 * nq + nu <= n_cols <= nθ && reg >= 0) || error("plant_rollout_tape($model): grad_cols must be in $(2 * nq + nu) .. $nθ and grad_reg >= 0")
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    z = C_NULL
+    check(@ccall LIB.cimpc_plant_rollout_tape(id::Cint, B::Cint, steps::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                              q0::Ptr{Cdouble}, q1::Ptr{Cdouble}, ua::Ptr{Cdouble}, K_u::Cint, n_u::Cint, N_sample::Cint,
+                                              wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint, μs::Ptr{Cdouble}, n_mu::Cint,
+                                              h_sim::Cdouble, o::Ref{IpOpts}, q::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble},
+                                              status::Ptr{Cint}, iters::Ptr{Cint}, reg::Cdouble, n_cols::Cint, z::Ptr{Cdouble},
+                                              grad_status::Ptr{Cint}, handle::Ref{Ptr{Cvoid}})::Cint)
+    rows = min.((0:steps - 1) .÷ N_sample, size(ua, 3) - 1) .+ 1
+    u_applied = repeat(ua[:, :, rows], 1, B ÷ size(ua, 2), 1)
+    return all(status .== 1), q, u_applied, γ, b, status, iters, PlantTape(handle[], model, B, steps, n_cols, grad_status)
+end
+
+"""
+    plant_tape_vjp(tape; gq = nothing, ggamma = nothing, gb = nothing) -> (g_q0, g_q1, g_u_step, g_w_step, g_μ, g_h, n_cut)
+
+The reverse chain of `cimpc_plant_tape_vjp` over a tape: cotangents gq nq x B x (T + 2), ggamma nc x B x T, gb nb x B x T (nothing is
+zeros, not all three) -> g_q0, g_q1 nq x B (the gradients with respect to q[:, :, 1] and q[:, :, 2]: that of q1 is their sum, that of v1
+is -h g_q0), g_u_step nu x B x T per applied control, g_w_step nw x B x T, g_μ and g_h B each (`nothing` where the tape's columns stop
+short of them), n_cut B: the steps of a robot whose gradient status is 0.  May be called any number of times.
+"""
+function plant_tape_vjp(tape::PlantTape; gq::Union{Nothing,Array{Float64,3}} = nothing, ggamma::Union{Nothing,Array{Float64,3}} = nothing,
+                        gb::Union{Nothing,Array{Float64,3}} = nothing)
+    tape.handle != C_NULL || error("plant_tape_vjp: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, nb = tape.B, tape.T, nf * nc
+    (gq === nothing && ggamma === nothing && gb === nothing) && error("plant_tape_vjp: at least one of gq, ggamma, gb")
+    (gq === nothing || size(gq) == (nq, B, T + 2)) || error("plant_tape_vjp: gq must be $nq x $B x $(T + 2)")
+    (ggamma === nothing || size(ggamma) == (nc, B, T)) || error("plant_tape_vjp: ggamma must be $nc x $B x $T")
+    (gb === nothing || size(gb) == (nb, B, T)) || error("plant_tape_vjp: gb must be $nb x $B x $T")
+    c_mu = 2 * nq + nu + nw
+    g_q0 = zeros(nq, B); g_q1 = zeros(nq, B); g_u = zeros(nu, B, T); n_cut = zeros(Cint, B)
+    g_w = tape.n_cols >= c_mu ? zeros(nw, B, T) : nothing
+    g_μ = tape.n_cols >= c_mu + 1 ? zeros(B) : nothing
+    g_h = tape.n_cols >= c_mu + 2 ? zeros(B) : nothing
+    p(a) = a === nothing ? C_NULL : pointer(a)
+    GC.@preserve gq ggamma gb g_w g_μ g_h begin
+        pq, pg, pb, pw, pm, ph = p(gq), p(ggamma), p(gb), p(g_w), p(g_μ), p(g_h)
+        check(@ccall LIB.cimpc_plant_tape_vjp(tape.handle::Ptr{Cvoid}, pq::Ptr{Cdouble}, pg::Ptr{Cdouble}, pb::Ptr{Cdouble}, g_q0::Ptr{Cdouble},
+                                              g_q1::Ptr{Cdouble}, g_u::Ptr{Cdouble}, pw::Ptr{Cdouble}, pm::Ptr{Cdouble}, ph::Ptr{Cdouble},
+                                              n_cut::Ptr{Cint})::Cint)
+    end
+    return g_q0, g_q1, g_u, g_w, g_μ, g_h, n_cut
+end
+
 # ---- the plant models linearized on the device: the `LinearizedStep` triple of N knots in one call (linearized_step.jl:10-31) --------
 """
     plant_linearize(model, z, θ, κ; terrain = nothing) -> (r0, rz0, rθ0)
