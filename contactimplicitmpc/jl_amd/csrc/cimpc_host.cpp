@@ -18,6 +18,7 @@
 #include "model_table.h"
 #include "newton_state.h"
 #include "gains.h"
+#include "handle_state.h"
 #include "plant_linearize.h"
 #include "schedule_plan.h"
 
@@ -106,8 +107,6 @@ struct cimpc_ctx {
     // cimpc_set_gait: the controller's full reference trajectory + per-rollout step counters
     double *g_q = nullptr, *g_u = nullptr, *g_w = nullptr, *g_g = nullptr, *g_b = nullptr, *g_th = nullptr, *g_stride = nullptr;
     int* g_phase = nullptr;
-    bool gait_set = false;
-    int dz_producer = 0;            // who wrote the per-step sensitivity memory last: 0 nobody, 1 newton_solve (dz_good), 2 implicit_dynamics (slot 0)
     int* d_good_src = nullptr;      // [B][H] NewtonDev::good_src (in use where kkt_lazy_commit holds: set_kkt_backend)
     double* d_dz_knot = nullptr;    // [B][H_ref][nths*nd] per-knot archive, allocated at the first window change that needs it
     double* d_alt = nullptr;
@@ -116,10 +115,8 @@ struct cimpc_ctx {
            *d_Cb = nullptr;
     double *d_q0 = nullptr, *d_q1 = nullptr;      // one allocation: d_q1 = d_q0 + B nq (uploaded by one copy)
     double* h_qin = nullptr;     // pinned staging of [q0 | q1], then nq doubles for the stride of cimpc_mpc_advance
-    std::vector<int> win_mirror; // 0-based window as the HOST last uploaded it (empty: unknown - cimpc_set_gait / cimpc_mpc_advance moved it on the device)
     double* h_stage = nullptr;   // pinned staging of cimpc_mpc_solve (window, reference, altitude in; trajectory out), allocated at its first call
     size_t h_stage_doubles = 0;
-    bool advance_pending = false; // a cimpc_mpc_advance was queued on `stream` and not waited for (its staging word is in flight)
     double* d_result = nullptr;  // end-of-solve result block (solve_finish_kernel): result_doubles(B, nu)
     double* h_result = nullptr;  // ... its pinned host copy, valid from the end of a solve to the next call that touches the state
     double* d_rhs = nullptr;   // B1 seam staging
@@ -130,7 +127,7 @@ struct cimpc_ctx {
     // bookkeeping
     std::vector<char> knot_set;
     int n_knots_set = 0;
-    bool objective_set = false, window_set = false, reference_set = false, alt_set = false;
+    HandleState st;              // what is set, where the window lives, who may latch (handle_state.h): read and changed through its names only
     // KKT stage (kkt_plan.h): the knobs that take part, what the kernels can do for the problem, the solver family
     KktPolicy kp{};
     KktCaps kc{};
@@ -172,8 +169,6 @@ struct cimpc_ctx {
     // feedback gains (cimpc_set_gains, cimpc_gain_latch, cimpc_gain_feedback): K of every reference knot, what the last latch kept
     // per rollout (gains.h: gain_latch_doubles) and the staging of a feedback call [q_prev | q_cur | u]; allocated at the first cimpc_set_gains
     double *d_gK = nullptr, *d_glatch = nullptr, *d_gio = nullptr;
-    bool gains_set = false, gains_latched = false;
-    bool latch_ready = false;        // a Newton solve has run and nothing has moved the window or the reference since: cimpc_gain_latch may run
     cimpc_stats last_stats{};
     // profiling
     int prof_on = 0;             // 0 off, 1 every launch, 2 the interior-point sweep launches only (cimpc_profile_enable)
@@ -193,6 +188,7 @@ int fail(cimpc_ctx* h, int code, const std::string& msg) {
     else g_create_error = msg;
     return code;
 }
+int refuse(cimpc_ctx* h, const Refusal& r) { return r.code == CIMPC_OK ? CIMPC_OK : fail(h, r.code, r.msg); }
 
 }  // namespace
 
@@ -284,7 +280,7 @@ IpParams make_ip_params(cimpc_ctx* h, const TrajDev& T, int par, int* pending_co
     p.theta = T.th;
     p.gam = T.g;
     p.bfr = T.b;
-    p.alt = h->alt_set ? h->d_alt : nullptr;
+    p.alt = h->st.has_altitude() ? h->d_alt : nullptr;
     p.d = h->S.d;
     p.dz = h->S.dz;
     p.nu = nullptr; p.dtn = nullptr; p.dtn_ld = h->S.dtn_ld;      // (the Newton loop switches the products on, see cimpc_newton_solve_dev)
@@ -394,22 +390,15 @@ int read_stats(cimpc_ctx* h, long long out[4]) {
 // rewrites reference / gait / window / objective state with blocking NULL-stream copies must first let that work finish, or the
 // pending gait_window / rekey kernels race with the rewrite
 int drain_pending(cimpc_ctx* h) {
-    if (!h->advance_pending) return CIMPC_OK;
+    if (!h->st.drain_needed()) return CIMPC_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->advance_pending = false;
+    h->st.advance_drained();
     return CIMPC_OK;
 }
 
 int check_ready(cimpc_ctx* h, bool need_newton) {
     if (!h) return CIMPC_ERR_INVALID;
-    if (h->n_knots_set != h->dm.H_ref)
-        return fail(h, CIMPC_ERR_STATE, "set_linearization has not been called for every knot");
-    if (!h->window_set) return fail(h, CIMPC_ERR_STATE, "set_window has not been called");
-    if (need_newton) {
-        if (!h->objective_set) return fail(h, CIMPC_ERR_STATE, "set_objective has not been called");
-        if (!h->reference_set) return fail(h, CIMPC_ERR_STATE, "set_reference has not been called");
-    }
-    return CIMPC_OK;
+    return refuse(h, h->st.solve_refusal(h->n_knots_set == h->dm.H_ref, need_newton));
 }
 
 }  // namespace
@@ -662,7 +651,7 @@ int cimpc_destroy(cimpc_handle h) {
 int cimpc_set_stream(cimpc_handle h, void* hip_stream) {
     if (!h) return CIMPC_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
-    h->advance_pending = false;
+    h->st.advance_drained();
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     h->stream = static_cast<hipStream_t>(hip_stream);
     h->own_stream = false;
@@ -852,25 +841,25 @@ int cimpc_set_objective(cimpc_handle h, const double* Q, const double* R, const 
     const bool need_inv = h->kb == KktBackend::Condensed || h->kb == KktBackend::CondensedMixed || h->kb == KktBackend::CfCondensed;
     // (a refused objective leaves NO objective: the backend selection above is already committed while the device blocks still hold
     //  the previous call's - ADVICE r05 - so the handle goes back to "set_objective has not been called" instead of solving a mix)
-    if (need_inv && !q_inverted) { h->objective_set = false; return fail(h, CIMPC_ERR_INVALID, "objective block Q[i] is singular"); }
-    if (need_inv && !r_inverted) { h->objective_set = false; return fail(h, CIMPC_ERR_INVALID, "objective block R[i] is singular"); }
+    if (need_inv && !q_inverted) { h->st.objective_refused(); return fail(h, CIMPC_ERR_INVALID, "objective block Q[i] is singular"); }
+    if (need_inv && !r_inverted) { h->st.objective_refused(); return fail(h, CIMPC_ERR_INVALID, "objective block R[i] is singular"); }
     HIP_TRY(h, hipMemcpy(h->d_Q, Q, H * d.nq * d.nq * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->d_R, R, H * d.nu * d.nu * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->d_Qinv, Qi.data(), Qi.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->d_Rinv, Ri.data(), Ri.size() * sizeof(double), hipMemcpyHostToDevice));
     if (Cg) HIP_TRY(h, hipMemcpy(h->d_Cg, Cg, H * d.nc * d.nc * sizeof(double), hipMemcpyHostToDevice));
     if (Cb) HIP_TRY(h, hipMemcpy(h->d_Cb, Cb, H * d.nb * d.nb * sizeof(double), hipMemcpyHostToDevice));
-    h->objective_set = true;
+    h->st.objective_replaced();
     return CIMPC_OK;
 }
 
 int cimpc_set_altitude(cimpc_handle h, const double* alt) {
     if (!h) return CIMPC_ERR_INVALID;
-    if (!alt) { h->alt_set = false; return CIMPC_OK; }
+    if (!alt) { h->st.altitude_cleared(); return CIMPC_OK; }
     HIP_TRY(h, hipSetDevice(h->device));
     if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
     HIP_TRY(h, hipMemcpy(h->d_alt, alt, (size_t)h->dm.B * h->dm.nc * sizeof(double), hipMemcpyHostToDevice));
-    h->alt_set = true;
+    h->st.altitude_set();
     return CIMPC_OK;
 }
 
@@ -881,9 +870,9 @@ int cimpc_set_altitude(cimpc_handle h, const double* alt) {
 // slot 0 of S.dz.  When the producer changes between two calls on one handle, the blocks of the previous producer are copied
 // into the store the next call reads / falls back to, so a solve that fails there keeps what the reference would keep.
 static int sync_dz_stores(cimpc_ctx* h, int next_producer) {
-    if (h->dz_producer == 0 || h->dz_producer == next_producer) return CIMPC_OK;
+    if (!h->st.dz_sync_needed(next_producer)) return CIMPC_OK;
     const size_t row = (size_t)h->dm.H * h->nths * h->nd * sizeof(double), B = h->dm.B;
-    if (next_producer == 2)      // newton_solve ran last: dz_good -> slot 0 of every rollout
+    if (next_producer == DZ_IMPLICIT)      // newton_solve ran last: dz_good -> slot 0 of every rollout
         HIP_TRY(h, hipMemcpy2DAsync(h->S.dz, CS * row, h->S.dz_good, row, row, B, hipMemcpyDeviceToDevice, h->stream));
     else                         // implicit_dynamics ran last: slot 0 -> dz_good
         HIP_TRY(h, hipMemcpy2DAsync(h->S.dz_good, row, h->S.dz, CS * row, row, B, hipMemcpyDeviceToDevice, h->stream));
@@ -892,13 +881,13 @@ static int sync_dz_stores(cimpc_ctx* h, int next_producer) {
 }
 
 static int rekey_out(cimpc_ctx* h) {
-    if (h->dz_producer == 0 || !h->window_set) return CIMPC_OK;
+    if (!h->st.rekey_out_needed()) return CIMPC_OK;
     if (!h->d_dz_knot && dev_alloc(h, &h->d_dz_knot, (size_t)h->dm.B * h->dm.H_ref * h->nths * h->nd) != CIMPC_OK) return CIMPC_ERR_HIP;
-    int rc = launch_dz_rekey(h->S, h->d_dz_knot, h->d_window, h->dz_producer == 1 ? 0 : 1, 0, h->stream);
+    int rc = launch_dz_rekey(h->S, h->d_dz_knot, h->d_window, h->st.rekey_out_store(), 0, h->stream);
     return rc == CIMPC_OK ? CIMPC_OK : fail(h, rc, "sensitivity archive launch failed");
 }
 static int rekey_in(cimpc_ctx* h) {
-    if (h->dz_producer == 0 || !h->d_dz_knot) return CIMPC_OK;
+    if (!h->st.rekey_in_needed(h->d_dz_knot != nullptr)) return CIMPC_OK;
     for (int which = 0; which < 2; ++which) {      // both consumers see the knots' blocks
         int rc = launch_dz_rekey(h->S, h->d_dz_knot, h->d_window, which, 1, h->stream);
         if (rc != CIMPC_OK) return fail(h, rc, "sensitivity restore launch failed");
@@ -906,51 +895,45 @@ static int rekey_in(cimpc_ctx* h) {
     return CIMPC_OK;
 }
 
+// a step of a window move that the host waits for: the step's own failure first, else the stream's
+static int then_sync(cimpc_ctx* h, int rc) {
+    if (rc != CIMPC_OK) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return CIMPC_OK;
+}
+
 int cimpc_set_window(cimpc_handle h, const int* window) {
     if (!h || !window) return fail(h, CIMPC_ERR_INVALID, "null argument");
-    h->latch_ready = false;
-    const cimpc_dims& d = h->dm;
-    const int B = d.B, H = d.H, K = d.H_ref;
-    std::vector<int> w0((size_t)B * (H + 2));
-    for (size_t k = 0; k < w0.size(); ++k) {
-        const int t = window[k];
-        if (t < 1 || t > K) return fail(h, CIMPC_ERR_INVALID, "window entry out of range (1-based knot index)");
-        w0[k] = t - 1;                 // the device buckets problems by 0-based knot (newton_kernels.hip: enqueue_eval)
-    }
+    h->st.unlatch();
+    std::vector<int> w0(horizon_sizes(h->dm, h->nth, h->nd).win);      // the device buckets problems by 0-based knot (newton_kernels.hip: enqueue_eval)
+    if (int rc = refuse(h, window_to_knots(window, w0.size(), h->dm.H_ref, w0.data())); rc != CIMPC_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
-    if (int rk = rekey_out(h); rk != CIMPC_OK) return rk;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    HIP_TRY(h, hipMemcpy(h->d_window, w0.data(), w0.size() * sizeof(int), hipMemcpyHostToDevice));
-    if (int rk = rekey_in(h); rk != CIMPC_OK) return rk;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->window_set = true;
-    h->gait_set = false;               // an explicit window / reference replaces the gait-generated ones
-    h->win_mirror = w0;
-    return CIMPC_OK;
+    return window_move(h->st, WindowHome::Host, w0.data(), w0.size(),
+        [&] { return then_sync(h, rekey_out(h)); },
+        [&]() -> int { HIP_TRY(h, hipMemcpy(h->d_window, w0.data(), w0.size() * sizeof(int), hipMemcpyHostToDevice)); return CIMPC_OK; },
+        [&] { return then_sync(h, rekey_in(h)); });
 }
 
 int cimpc_set_reference(cimpc_handle h, const double* q_ref, const double* u_ref,
                         const double* w_ref, const double* gamma_ref, const double* b_ref,
                         const double* theta_ref) {
     if (!h || !q_ref || !u_ref || !theta_ref) return fail(h, CIMPC_ERR_INVALID, "q_ref, u_ref, theta_ref are required");
-    h->latch_ready = false;
-    const cimpc_dims& d = h->dm;
-    const size_t B = d.B, H = d.H;
+    h->st.unlatch();
+    const HorizonSizes n = horizon_sizes(h->dm, h->nth, h->nd);
     HIP_TRY(h, hipSetDevice(h->device));
     if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
-    HIP_TRY(h, hipMemcpy(h->S.ref.q, q_ref, B * (H + 2) * d.nq * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->S.ref.u, u_ref, B * H * d.nu * sizeof(double), hipMemcpyHostToDevice));
-    if (w_ref) HIP_TRY(h, hipMemcpy(h->S.ref.w, w_ref, B * H * d.nw * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->S.ref.q, q_ref, n.q * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->S.ref.u, u_ref, n.u * sizeof(double), hipMemcpyHostToDevice));
+    if (w_ref) HIP_TRY(h, hipMemcpy(h->S.ref.w, w_ref, n.w * sizeof(double), hipMemcpyHostToDevice));
     else {      // NULL-stream fill: make it complete before the (non-blocking) solver streams can read it
-        HIP_TRY(h, hipMemset(h->S.ref.w, 0, B * H * d.nw * sizeof(double)));
+        HIP_TRY(h, hipMemset(h->S.ref.w, 0, n.w * sizeof(double)));
         HIP_TRY(h, hipStreamSynchronize(nullptr));
     }
-    if (gamma_ref) HIP_TRY(h, hipMemcpy(h->S.ref.g, gamma_ref, B * H * d.nc * sizeof(double), hipMemcpyHostToDevice));
-    if (b_ref) HIP_TRY(h, hipMemcpy(h->S.ref.b, b_ref, B * H * d.nb * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->S.ref.th, theta_ref, B * H * h->nth * sizeof(double), hipMemcpyHostToDevice));
-    h->reference_set = true;
-    h->gait_set = false;
+    if (gamma_ref) HIP_TRY(h, hipMemcpy(h->S.ref.g, gamma_ref, n.g * sizeof(double), hipMemcpyHostToDevice));
+    if (b_ref) HIP_TRY(h, hipMemcpy(h->S.ref.b, b_ref, n.b * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->S.ref.th, theta_ref, n.th * sizeof(double), hipMemcpyHostToDevice));
+    h->st.reference_replaced();
     return CIMPC_OK;
 }
 
@@ -962,21 +945,22 @@ int cimpc_implicit_dynamics(cimpc_handle h, const double* q, const double* theta
     if (!q || !theta) return fail(h, CIMPC_ERR_INVALID, "q and theta are required");
     const cimpc_dims& d = h->dm;
     const size_t B = d.B, H = d.H;
+    const HorizonSizes row = horizon_rows(d, h->nth, h->nd);      // of one rollout
     if (d.mode == CIMPC_MODE_CONFIGURATIONFORCE && (!gamma || !b))
         return fail(h, CIMPC_ERR_INVALID, "gamma and b are required in configurationforce mode");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (int sy = sync_dz_stores(h, 2); sy != CIMPC_OK) return sy;
-    h->dz_producer = 2;
+    if (int sy = sync_dz_stores(h, DZ_IMPLICIT); sy != CIMPC_OK) return sy;
+    h->st.implicit_dynamics_started();
     TrajDev& T = h->S.cand;
     // evaluation slot 0 of every rollout (slot stride = CS rows)
     auto up = [&](double* dst, const double* src, size_t row_doubles) {
         return hipMemcpy2DAsync(dst, CS * row_doubles * sizeof(double), src, row_doubles * sizeof(double),
                                 row_doubles * sizeof(double), B, hipMemcpyHostToDevice, h->stream);
     };
-    HIP_TRY(h, up(T.q, q, (H + 2) * d.nq));
-    HIP_TRY(h, up(T.th, theta, H * h->nth));
-    if (gamma) HIP_TRY(h, up(T.g, gamma, H * d.nc));
-    if (b) HIP_TRY(h, up(T.b, b, H * d.nb));
+    HIP_TRY(h, up(T.q, q, row.q));
+    HIP_TRY(h, up(T.th, theta, row.th));
+    if (gamma) HIP_TRY(h, up(T.g, gamma, row.g));
+    if (b) HIP_TRY(h, up(T.b, b, row.b));
     // queue slot 0 of every rollout, then run rounds until no solve is parked
     HIP_TRY(h, hipMemsetAsync(h->Q.count, 0, 2 * h->Q.K * QPAD * sizeof(int), h->stream));
     HIP_TRY(h, hipMemsetAsync(h->Q.head, 0, h->Q.K * QPAD * sizeof(int), h->stream));
@@ -1000,7 +984,7 @@ int cimpc_implicit_dynamics(cimpc_handle h, const double* q, const double* theta
     auto down = [&](void* dst, const void* src, size_t row_bytes) {
         return hipMemcpy2DAsync(dst, row_bytes, src, CS * row_bytes, row_bytes, B, hipMemcpyDeviceToHost, h->stream);
     };
-    if (d_out) HIP_TRY(h, down(d_out, h->S.d, H * h->nd * sizeof(double)));
+    if (d_out) HIP_TRY(h, down(d_out, h->S.d, row.nu * sizeof(double)));
     if (dz) HIP_TRY(h, down(dz, h->S.dz, H * h->nths * h->nd * sizeof(double)));
     if (status) HIP_TRY(h, down(status, h->S.ip_status, H * sizeof(int)));
     if (iters) HIP_TRY(h, down(iters, h->S.ip_iters, H * sizeof(int)));
@@ -1302,9 +1286,8 @@ int cimpc_newton_solve_dev(cimpc_handle h, const double* q0_dev, const double* q
     if (rc != CIMPC_OK) return rc;
     if (!q0_dev || !q1_dev) return fail(h, CIMPC_ERR_INVALID, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (int sy = sync_dz_stores(h, 1); sy != CIMPC_OK) return sy;
-    h->dz_producer = 1;
-    h->latch_ready = true;
+    if (int sy = sync_dz_stores(h, DZ_NEWTON); sy != CIMPC_OK) return sy;
+    h->st.solve_started();
     const int B = h->dm.B;
     SolveRun run{q0_dev, q1_dev, warm_start, {}, *(volatile int*)h->h_twfail, false, h->rs, RoundCounts{B, 0, B, B, 0, 0}};
     h->twfail_seen = run.tw_fail0;
@@ -1409,60 +1392,50 @@ int cimpc_mpc_solve(cimpc_handle h, const int* window, const double* q_ref, cons
                     double* q, double* u, double* gamma, double* b, double* nu_dual) {
     if (!h || !q0 || !q1) return fail(h, CIMPC_ERR_INVALID, "null argument");
     if (q_ref && (!u_ref || !theta_ref)) return fail(h, CIMPC_ERR_INVALID, "q_ref, u_ref, theta_ref go together");
-    const cimpc_dims& d = h->dm;
-    const size_t B = d.B, H = d.H, K = d.H_ref;
-    const size_t nwin = B * (H + 2);
-    const size_t n_q = B * (H + 2) * d.nq, n_u = B * H * d.nu, n_w = B * H * d.nw, n_g = B * H * d.nc, n_b = B * H * d.nb,
-                 n_th = B * H * h->nth, n_nu = B * H * h->nd, n_alt = B * d.nc;
+    const HorizonSizes sz = horizon_sizes(h->dm, h->nth, h->nd);
     HIP_TRY(h, hipSetDevice(h->device));
     if (!h->h_stage) {
         // [window (as doubles' worth of ints) | q | u | w | gamma | b | theta | alt]; the way out reuses [q | u | gamma | b | nu]
-        h->h_stage_doubles = (nwin + 1) / 2 + n_q + n_u + n_w + n_g + n_b + std::max(n_th, n_nu) + n_alt + 8;
+        h->h_stage_doubles = (sz.win + 1) / 2 + sz.q + sz.u + sz.w + sz.g + sz.b + std::max(sz.th, sz.nu) + sz.alt + 8;
         if (hipHostMalloc((void**)&h->h_stage, h->h_stage_doubles * sizeof(double), hipHostMallocDefault) != hipSuccess)
             return fail(h, CIMPC_ERR_HIP, "hipHostMalloc failed");
     }
     if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
     double* stage = h->h_stage;
     int* s_win = reinterpret_cast<int*>(stage);
-    double* s_q = stage + (nwin + 1) / 2; double* s_u = s_q + n_q; double* s_w = s_u + n_u; double* s_g = s_w + n_w;
-    double* s_b = s_g + n_g; double* s_th = s_b + n_b; double* s_alt = s_th + std::max(n_th, n_nu);
+    double* s_q = stage + (sz.win + 1) / 2; double* s_u = s_q + sz.q; double* s_w = s_u + sz.u; double* s_g = s_w + sz.w;
+    double* s_b = s_g + sz.g; double* s_th = s_b + sz.b; double* s_alt = s_th + std::max(sz.th, sz.nu);
     hipStream_t st = h->stream;
     if (window) {
-        bool same = h->win_mirror.size() == nwin;
-        for (size_t k = 0; k < nwin; ++k) {
-            const int t = window[k];
-            if (t < 1 || t > (int)K) return fail(h, CIMPC_ERR_INVALID, "window entry out of range (1-based knot index)");
-            s_win[k] = t - 1;
-            same = same && h->win_mirror[k] == t - 1;
+        if (int rc = refuse(h, window_to_knots(window, sz.win, h->dm.H_ref, s_win)); rc != CIMPC_OK) return rc;
+        // the per-knot sensitivity memory moves with the window (cimpc_set_window), stream-ordered.  (A window equal to the mirror
+        // is in force already: a mirror that is not empty says so, and that no gait generates the window - handle_state.h)
+        if (!h->st.mirror_equals(s_win, sz.win)) {
+            int rc = window_move(h->st, WindowHome::Host, s_win, sz.win, [&] { return rekey_out(h); },
+                [&]() -> int { HIP_TRY(h, hipMemcpyAsync(h->d_window, s_win, sz.win * sizeof(int), hipMemcpyHostToDevice, st)); return CIMPC_OK; },
+                [&] { return rekey_in(h); });
+            if (rc != CIMPC_OK) return rc;
         }
-        if (!same) {      // the per-knot sensitivity memory moves with the window (cimpc_set_window), stream-ordered
-            if (int rk = rekey_out(h); rk != CIMPC_OK) return rk;
-            HIP_TRY(h, hipMemcpyAsync(h->d_window, s_win, nwin * sizeof(int), hipMemcpyHostToDevice, st));
-            if (int rk = rekey_in(h); rk != CIMPC_OK) return rk;
-            h->win_mirror.assign(s_win, s_win + nwin);
-        }
-        h->window_set = true;
-        h->gait_set = false;
     }
     if (q_ref) {
+        h->st.unlatch();      // (as cimpc_set_reference; the solve below sets it again)
         auto up = [&](double* dst, double* stg, const double* src, size_t n) -> hipError_t {
             if (n == 0) return hipSuccess;
             if (src) std::memcpy(stg, src, n * sizeof(double)); else std::memset(stg, 0, n * sizeof(double));
             return hipMemcpyAsync(dst, stg, n * sizeof(double), hipMemcpyHostToDevice, st);
         };
-        HIP_TRY(h, up(h->S.ref.q, s_q, q_ref, n_q));
-        HIP_TRY(h, up(h->S.ref.u, s_u, u_ref, n_u));
-        HIP_TRY(h, up(h->S.ref.w, s_w, w_ref, n_w));                       // NULL = zeros, as cimpc_set_reference
-        if (gamma_ref) HIP_TRY(h, up(h->S.ref.g, s_g, gamma_ref, n_g));   // NULL = unchanged, as cimpc_set_reference
-        if (b_ref) HIP_TRY(h, up(h->S.ref.b, s_b, b_ref, n_b));
-        HIP_TRY(h, up(h->S.ref.th, s_th, theta_ref, n_th));
-        h->reference_set = true;
-        h->gait_set = false;
+        HIP_TRY(h, up(h->S.ref.q, s_q, q_ref, sz.q));
+        HIP_TRY(h, up(h->S.ref.u, s_u, u_ref, sz.u));
+        HIP_TRY(h, up(h->S.ref.w, s_w, w_ref, sz.w));                       // NULL = zeros, as cimpc_set_reference
+        if (gamma_ref) HIP_TRY(h, up(h->S.ref.g, s_g, gamma_ref, sz.g));   // NULL = unchanged, as cimpc_set_reference
+        if (b_ref) HIP_TRY(h, up(h->S.ref.b, s_b, b_ref, sz.b));
+        HIP_TRY(h, up(h->S.ref.th, s_th, theta_ref, sz.th));
+        h->st.reference_replaced();
     }
     if (alt) {
-        std::memcpy(s_alt, alt, n_alt * sizeof(double));
-        HIP_TRY(h, hipMemcpyAsync(h->d_alt, s_alt, n_alt * sizeof(double), hipMemcpyHostToDevice, st));
-        h->alt_set = true;
+        std::memcpy(s_alt, alt, sz.alt * sizeof(double));
+        HIP_TRY(h, hipMemcpyAsync(h->d_alt, s_alt, sz.alt * sizeof(double), hipMemcpyHostToDevice, st));
+        h->st.altitude_set();
     }
     int rc = cimpc_newton_solve(h, q0, q1, warm_start, u1, newton_iters, r_norm);
     if (rc != CIMPC_OK) return rc;
@@ -1471,32 +1444,31 @@ int cimpc_mpc_solve(cimpc_handle h, const int* window, const double* q_ref, cons
         auto down = [&](double* stg, const double* src, double* dst, size_t n) -> hipError_t {
             return (dst && n) ? hipMemcpyAsync(stg, src, n * sizeof(double), hipMemcpyDeviceToHost, st) : hipSuccess;
         };
-        HIP_TRY(h, down(s_q, h->S.traj.q, q, n_q));
-        HIP_TRY(h, down(s_u, h->S.traj.u, u, n_u));
-        HIP_TRY(h, down(s_g, h->S.traj.g, gamma, n_g));
-        HIP_TRY(h, down(s_b, h->S.traj.b, b, n_b));
-        HIP_TRY(h, down(s_th, h->S.nu, nu_dual, n_nu));
+        HIP_TRY(h, down(s_q, h->S.traj.q, q, sz.q));
+        HIP_TRY(h, down(s_u, h->S.traj.u, u, sz.u));
+        HIP_TRY(h, down(s_g, h->S.traj.g, gamma, sz.g));
+        HIP_TRY(h, down(s_b, h->S.traj.b, b, sz.b));
+        HIP_TRY(h, down(s_th, h->S.nu, nu_dual, sz.nu));
         HIP_TRY(h, hipStreamSynchronize(st));
-        if (q) std::memcpy(q, s_q, n_q * sizeof(double));
-        if (u) std::memcpy(u, s_u, n_u * sizeof(double));
-        if (gamma && n_g) std::memcpy(gamma, s_g, n_g * sizeof(double));
-        if (b && n_b) std::memcpy(b, s_b, n_b * sizeof(double));
-        if (nu_dual) std::memcpy(nu_dual, s_th, n_nu * sizeof(double));
+        if (q) std::memcpy(q, s_q, sz.q * sizeof(double));
+        if (u) std::memcpy(u, s_u, sz.u * sizeof(double));
+        if (gamma && sz.g) std::memcpy(gamma, s_g, sz.g * sizeof(double));
+        if (b && sz.b) std::memcpy(b, s_b, sz.b * sizeof(double));
+        if (nu_dual) std::memcpy(nu_dual, s_th, sz.nu * sizeof(double));
     }
     return CIMPC_OK;
 }
 
 int cimpc_get_trajectory(cimpc_handle h, double* q, double* u, double* gamma, double* b, double* nu_dual) {
     if (!h) return CIMPC_ERR_INVALID;
-    const cimpc_dims& d = h->dm;
-    const size_t B = d.B, H = d.H;
+    const HorizonSizes n = horizon_sizes(h->dm, h->nth, h->nd);
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (q) HIP_TRY(h, hipMemcpy(q, h->S.traj.q, B * (H + 2) * d.nq * sizeof(double), hipMemcpyDeviceToHost));
-    if (u) HIP_TRY(h, hipMemcpy(u, h->S.traj.u, B * H * d.nu * sizeof(double), hipMemcpyDeviceToHost));
-    if (gamma) HIP_TRY(h, hipMemcpy(gamma, h->S.traj.g, B * H * d.nc * sizeof(double), hipMemcpyDeviceToHost));
-    if (b) HIP_TRY(h, hipMemcpy(b, h->S.traj.b, B * H * d.nb * sizeof(double), hipMemcpyDeviceToHost));
-    if (nu_dual) HIP_TRY(h, hipMemcpy(nu_dual, h->S.nu, B * H * h->nd * sizeof(double), hipMemcpyDeviceToHost));
+    if (q) HIP_TRY(h, hipMemcpy(q, h->S.traj.q, n.q * sizeof(double), hipMemcpyDeviceToHost));
+    if (u) HIP_TRY(h, hipMemcpy(u, h->S.traj.u, n.u * sizeof(double), hipMemcpyDeviceToHost));
+    if (gamma) HIP_TRY(h, hipMemcpy(gamma, h->S.traj.g, n.g * sizeof(double), hipMemcpyDeviceToHost));
+    if (b) HIP_TRY(h, hipMemcpy(b, h->S.traj.b, n.b * sizeof(double), hipMemcpyDeviceToHost));
+    if (nu_dual) HIP_TRY(h, hipMemcpy(nu_dual, h->S.nu, n.nu * sizeof(double), hipMemcpyDeviceToHost));
     return CIMPC_OK;
 }
 
@@ -1535,7 +1507,7 @@ static GaitDev gait_dev(cimpc_ctx* h) {
 int cimpc_set_gait(cimpc_handle h, const double* q, const double* u, const double* w, const double* gamma,
                    const double* b, const double* theta, const double* stride, const int* phase) {
     if (!h || !q || !u || !theta || !stride) return fail(h, CIMPC_ERR_INVALID, "q, u, theta, stride are required");
-    h->latch_ready = false;
+    h->st.unlatch();
     const cimpc_dims& d = h->dm;
     const size_t K = d.H_ref, B = d.B;
     if (d.H > d.H_ref) return fail(h, CIMPC_ERR_INVALID, "H_mpc must not exceed H_ref");
@@ -1562,44 +1534,38 @@ int cimpc_set_gait(cimpc_handle h, const double* q, const double* u, const doubl
     HIP_TRY(h, hipMemcpy(h->g_stride, stride, d.nq * sizeof(double), hipMemcpyHostToDevice));
     if (phase) HIP_TRY(h, hipMemcpy(h->g_phase, phase, B * sizeof(int), hipMemcpyHostToDevice));
     else { HIP_TRY(h, hipMemset(h->g_phase, 0, B * sizeof(int))); HIP_TRY(h, hipStreamSynchronize(nullptr)); }
-    if (int rk = rekey_out(h); rk != CIMPC_OK) return rk;
-    int rc = launch_gait_window(h->S, gait_dev(h), h->d_window, 0, h->stream);
-    if (rc != CIMPC_OK) return fail(h, rc, "gait window launch failed");
-    if (int rk = rekey_in(h); rk != CIMPC_OK) return rk;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->gait_set = h->window_set = h->reference_set = true;
-    h->win_mirror.clear();             // the window now lives on the device only
+    int rc = window_move(h->st, WindowHome::Device, nullptr, 0, [&] { return rekey_out(h); },      // the window now lives on the device only
+        [&] { int rg = launch_gait_window(h->S, gait_dev(h), h->d_window, 0, h->stream); return rg == CIMPC_OK ? CIMPC_OK : fail(h, rg, "gait window launch failed"); },
+        [&] { return then_sync(h, rekey_in(h)); });
+    if (rc != CIMPC_OK) return rc;
+    h->st.gait_installed();
     return CIMPC_OK;
 }
 
 int cimpc_mpc_advance(cimpc_handle h, const double* stride) {
     if (!h || !stride) return fail(h, CIMPC_ERR_INVALID, "null argument");
-    if (!h->window_set || !h->reference_set) return fail(h, CIMPC_ERR_STATE, "set_window / set_reference have not been called");
-    h->latch_ready = false;          // the window and the reference move on: a latch now would take the NEXT step's K and target
+    if (int rc = refuse(h, h->st.advance_refusal()); rc != CIMPC_OK) return rc;
+    h->st.unlatch();                 // the window and the reference move on: a latch now would take the NEXT step's K and target
     HIP_TRY(h, hipSetDevice(h->device));
     // The advance is QUEUED on the handle's stream and not waited for: whatever comes next is ordered behind it on the device
     // (the solve's streams wait for this stream, every getter synchronises it first).  The stride goes through a pinned word;
     // a second advance in a row waits for the first one's copy to have left it.
     if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
-    h->win_mirror.clear();
     double* st_pin = h->h_qin + 2 * (size_t)h->dm.B * h->dm.nq;
     std::memcpy(st_pin, stride, (size_t)h->dm.nq * sizeof(double));
-    if (h->gait_set) {          // full reference resident: regenerate the horizon from the gait (stride as given now)
-        HIP_TRY(h, hipMemcpyAsync(h->g_stride, st_pin, (size_t)h->dm.nq * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        if (int rk = rekey_out(h); rk != CIMPC_OK) return rk;
-        int rcg = launch_gait_window(h->S, gait_dev(h), h->d_window, 1, h->stream);
-        if (rcg != CIMPC_OK) return fail(h, rcg, "mpc_advance launch failed");
-        if (int rk = rekey_in(h); rk != CIMPC_OK) return rk;
-        h->advance_pending = true;
-        return CIMPC_OK;
+    auto launched = [&](int rc) { return rc == CIMPC_OK ? CIMPC_OK : fail(h, rc, "mpc_advance launch failed"); };
+    if (h->st.advances_by_gait()) {          // full reference resident: regenerate the horizon from the gait (stride as given now)
+        int rc = window_move(h->st, WindowHome::Device, nullptr, 0,
+            [&]() -> int { HIP_TRY(h, hipMemcpyAsync(h->g_stride, st_pin, (size_t)h->dm.nq * sizeof(double), hipMemcpyHostToDevice, h->stream)); return rekey_out(h); },
+            [&] { return launched(launch_gait_window(h->S, gait_dev(h), h->d_window, 1, h->stream)); },
+            [&] { return rekey_in(h); });
+        if (rc == CIMPC_OK) h->st.advance_queued();
+        return rc;
     }
-    HIP_TRY(h, hipMemcpyAsync(h->d_q0, stride, (size_t)h->dm.nq * sizeof(double), hipMemcpyHostToDevice, h->stream));   // d_q0: staging
-    if (int rk = rekey_out(h); rk != CIMPC_OK) return rk;
-    int rc = launch_mpc_advance(h->S, h->d_window, h->d_q0, h->dm.H_ref, h->stream);
-    if (rc != CIMPC_OK) return fail(h, rc, "mpc_advance launch failed");
-    if (int rk = rekey_in(h); rk != CIMPC_OK) return rk;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return CIMPC_OK;
+    return window_move(h->st, WindowHome::Device, nullptr, 0,
+        [&]() -> int { HIP_TRY(h, hipMemcpyAsync(h->d_q0, stride, (size_t)h->dm.nq * sizeof(double), hipMemcpyHostToDevice, h->stream)); return rekey_out(h); },   // d_q0: staging
+        [&] { return launched(launch_mpc_advance(h->S, h->d_window, h->d_q0, h->dm.H_ref, h->stream)); },
+        [&] { return then_sync(h, rekey_in(h)); });
 }
 
 // ---- feedback gains on the handle (gains.hip) -------------------------------------------------------------------------------------
@@ -1607,39 +1573,37 @@ int cimpc_set_gains(cimpc_handle h, const double* K) {
     if (!h) return CIMPC_ERR_INVALID;
     HIP_TRY(h, hipSetDevice(h->device));
     if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
-    h->gains_latched = false;
-    if (!K) { h->gains_set = false; return CIMPC_OK; }
+    h->st.gains_changing();
+    if (!K) { h->st.gains_cleared(); return CIMPC_OK; }
     const cimpc_dims& d = h->dm;
     const size_t nk = (size_t)d.nu * 2 * d.nq;
-    // each buffer by itself: one that could not be allocated is asked for again by the next call, and gains_set stays false until all exist
+    // each buffer by itself: one that could not be allocated is asked for again by the next call, and the gains count as set only once all exist
     if (!h->d_gK && dev_alloc(h, &h->d_gK, (size_t)d.H_ref * nk) != CIMPC_OK) return CIMPC_ERR_HIP;
     if (!h->d_glatch && dev_alloc(h, &h->d_glatch, (size_t)d.B * gain_latch_doubles(d.nq, d.nu)) != CIMPC_OK) return CIMPC_ERR_HIP;
     if (!h->d_gio && dev_alloc(h, &h->d_gio, (size_t)d.B * (2 * d.nq + d.nu)) != CIMPC_OK) return CIMPC_ERR_HIP;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     HIP_TRY(h, hipMemcpy(h->d_gK, K, (size_t)d.H_ref * nk * sizeof(double), hipMemcpyHostToDevice));
-    h->gains_set = true;
+    h->st.gains_replaced();
     return CIMPC_OK;
 }
 
 int cimpc_gain_latch(cimpc_handle h) {
     if (!h) return CIMPC_ERR_INVALID;
-    if (!h->gains_set) return fail(h, CIMPC_ERR_STATE, "cimpc_set_gains has not been called");
-    if (!h->latch_ready)
-        return fail(h, CIMPC_ERR_STATE, "cimpc_gain_latch belongs between a newton solve and cimpc_mpc_advance: no solve has run, or the window or the reference moved since");
+    if (int rc = refuse(h, h->st.latch_refusal()); rc != CIMPC_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     if (int dp = drain_pending(h); dp != CIMPC_OK) return dp;
     const cimpc_dims& d = h->dm;
     if (!gain_latch_launch(d.B, d.H, d.nq, d.nu, h->d_window, h->S.traj.u, h->S.ref.q, h->d_gK, h->d_glatch, h->stream))
         return fail(h, CIMPC_ERR_HIP, "gain latch launch failed");
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->gains_latched = true;
+    h->st.latched();
     return CIMPC_OK;
 }
 
 int cimpc_gain_feedback(cimpc_handle h, const double* q_prev, const double* q_cur, double n_sample, double* u) {
     if (!h || !q_prev || !q_cur || !u) return fail(h, CIMPC_ERR_INVALID, "null argument");
     if (!std::isfinite(n_sample) || n_sample <= 0.0) return fail(h, CIMPC_ERR_INVALID, "n_sample must be finite and positive");
-    if (!h->gains_set || !h->gains_latched) return fail(h, CIMPC_ERR_STATE, "cimpc_gain_latch has not been called since cimpc_set_gains");
+    if (int rc = refuse(h, h->st.feedback_refusal()); rc != CIMPC_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const cimpc_dims& d = h->dm;
     const size_t nqB = (size_t)d.B * d.nq, nuB = (size_t)d.B * d.nu;
@@ -1656,19 +1620,18 @@ int cimpc_gain_feedback(cimpc_handle h, const double* q_prev, const double* q_cu
 int cimpc_get_reference(cimpc_handle h, double* q_ref, double* u_ref, double* w_ref, double* gamma_ref,
                         double* b_ref, double* theta_ref, int* window) {
     if (!h) return CIMPC_ERR_INVALID;
-    const cimpc_dims& d = h->dm;
-    const size_t B = d.B, H = d.H;
+    const HorizonSizes n = horizon_sizes(h->dm, h->nth, h->nd);
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (q_ref) HIP_TRY(h, hipMemcpy(q_ref, h->S.ref.q, B * (H + 2) * d.nq * sizeof(double), hipMemcpyDeviceToHost));
-    if (u_ref) HIP_TRY(h, hipMemcpy(u_ref, h->S.ref.u, B * H * d.nu * sizeof(double), hipMemcpyDeviceToHost));
-    if (w_ref) HIP_TRY(h, hipMemcpy(w_ref, h->S.ref.w, B * H * d.nw * sizeof(double), hipMemcpyDeviceToHost));
-    if (gamma_ref) HIP_TRY(h, hipMemcpy(gamma_ref, h->S.ref.g, B * H * d.nc * sizeof(double), hipMemcpyDeviceToHost));
-    if (b_ref) HIP_TRY(h, hipMemcpy(b_ref, h->S.ref.b, B * H * d.nb * sizeof(double), hipMemcpyDeviceToHost));
-    if (theta_ref) HIP_TRY(h, hipMemcpy(theta_ref, h->S.ref.th, B * H * h->nth * sizeof(double), hipMemcpyDeviceToHost));
+    if (q_ref) HIP_TRY(h, hipMemcpy(q_ref, h->S.ref.q, n.q * sizeof(double), hipMemcpyDeviceToHost));
+    if (u_ref) HIP_TRY(h, hipMemcpy(u_ref, h->S.ref.u, n.u * sizeof(double), hipMemcpyDeviceToHost));
+    if (w_ref) HIP_TRY(h, hipMemcpy(w_ref, h->S.ref.w, n.w * sizeof(double), hipMemcpyDeviceToHost));
+    if (gamma_ref) HIP_TRY(h, hipMemcpy(gamma_ref, h->S.ref.g, n.g * sizeof(double), hipMemcpyDeviceToHost));
+    if (b_ref) HIP_TRY(h, hipMemcpy(b_ref, h->S.ref.b, n.b * sizeof(double), hipMemcpyDeviceToHost));
+    if (theta_ref) HIP_TRY(h, hipMemcpy(theta_ref, h->S.ref.th, n.th * sizeof(double), hipMemcpyDeviceToHost));
     if (window) {
-        HIP_TRY(h, hipMemcpy(window, h->d_window, B * (H + 2) * sizeof(int), hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < B * (H + 2); ++k) window[k] += 1;     // 1-based at the boundary
+        HIP_TRY(h, hipMemcpy(window, h->d_window, n.win * sizeof(int), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < n.win; ++k) window[k] += 1;     // 1-based at the boundary
     }
     return CIMPC_OK;
 }
