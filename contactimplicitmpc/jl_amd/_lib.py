@@ -61,6 +61,16 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
 _h = C.c_void_p
 
+
+class Feedback(C.Structure):
+    """cimpc_feedback: a feedback schedule of the closed-loop rollouts."""
+    _fields_ = [("K", _dp), ("x_ref", _dp), ("K_f", C.c_int), ("n_f", C.c_int), ("hold_f", C.c_int), ("n_sample", C.c_double)]
+
+
+# the 25 parameters of cimpc_plant_rollout, which the closed-loop entry points extend
+_ROLLOUT_ARGS = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
+                 _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip]
+
 # every symbol include/cimpc.h declares: (restype, argtypes)
 SIGNATURES = {
     "cimpc_default_ip_opts": (None, [C.POINTER(IpOpts)]),
@@ -107,6 +117,10 @@ SIGNATURES = {
                                            _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip,
                                            C.c_double, C.c_int, _dp, _ip, C.POINTER(_h)]),
     "cimpc_plant_tape_vjp": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "cimpc_plant_rollout_feedback": (C.c_int, _ROLLOUT_ARGS + [C.POINTER(Feedback), _dp, _dp]),
+    "cimpc_plant_rollout_grad_feedback": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _dp, _ip, C.POINTER(Feedback), _dp, _dp]),
+    "cimpc_plant_rollout_tape_feedback": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _ip, C.POINTER(_h), C.POINTER(Feedback), _dp, _dp]),
+    "cimpc_plant_tape_vjp_feedback": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp]),
     "cimpc_plant_tape_dims": (C.c_int, [_h, _ip, _ip, _ip, _ip]),
     "cimpc_plant_tape_destroy": (C.c_int, [_h]),
     "cimpc_tvlqr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),

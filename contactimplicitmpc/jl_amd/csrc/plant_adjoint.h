@@ -8,6 +8,13 @@
 //                       g_u_step[t] = v[2nq : 2nq+nu];  g_w_step[t] = v[w columns];  g_mu += v[mu column];  g_h += v[h column]
 //   g_q0 = lambda[0], g_q1 = lambda[1], n_cut = the steps whose gradient status is 0 (their D_t is all zeros)
 //
+// The chain of a CLOSED-LOOP rollout (item 3c, plant_feedback.h: u_t = ubar_t + K (x_ref - x), the blocks taken with u_t as a column
+// of theta) adds, after v = D_t' a of step t, with gu = v[2nq : 2nq+nu] and k the feedback row of step t:
+//                       gx[j] = sum_{i = 0 .. nu-1} K[k][i, j] gu[i]               ascending i from 0.0;   g_xref_step[t] = gx
+//                       lambda[t][i]   = lambda[t][i] - n_sample gx[i]             i < nq, after lambda[t] received gq[t] + v[0:nq]
+//                       lambda[t+1][i] = (lambda[t+1][i] - (1 - n_sample) gx[i]) - gx[nq + i]      after lambda[t+1] received v[nq:2nq]
+// g_u_step stays gu, which is also the gradient of ubar_t.  Without a feedback schedule (fb.K null) none of these statements runs.
+//
 // D_t is the step's dz block of plant_sensitivity.hip, nr x n_cols column-major, contiguous per (t, robot).  The chain of one robot
 // is stated here ONCE for a team of workers, the way lin_table_build.h states a table: plant_adjoint_kernel (plant_adjoint.hip) runs it
 // with a wavefront per robot, a host program (tests/native/plant_adjoint_check.cpp) with a team of one, statement for statement.
@@ -18,6 +25,8 @@
 // is followed by a sync() before dst is read.  Between the two the team works on the other block: the blocks do not depend on the chain.
 #pragma once
 #include <cstddef>
+
+#include "plant_feedback.h"
 
 // no contraction in this header's arithmetic: a * b + c rounds twice
 #ifdef __clang__
@@ -43,12 +52,16 @@ struct PlantAdjoint {
     double *g_q0, *g_q1, *g_u_step, *g_w_step, *g_mu, *g_h;
     int* n_cut;
     int B, T, nq, nu, nw, nc, nb, n_cols;
+    PlantFeedback fb{};               // fb.K null: an open-loop rollout
+    double* g_xref_step = nullptr;    // T x B x 2nq, with fb.K alone; null = not asked for
 };
 
 // doubles of the team's shared workspace: two blocks (the one in use and the one in flight), a, the three-row ring of lambda
 PADJ_HD constexpr size_t plant_adjoint_work_doubles(int nr, int n_cols, int nq) {
     return (size_t)2 * nr * n_cols + (size_t)nr + (size_t)3 * nq;
 }
+// what a closed-loop chain adds behind them: gu (nu) and gx (2nq)
+PADJ_HD constexpr size_t plant_adjoint_feedback_doubles(int nu, int nq) { return (size_t)nu + (size_t)2 * nq; }
 // what a launch of plant_adjoint_kernel needs of a CU's LDS (all of it dynamic), and whether a CU has it
 constexpr size_t PLANT_ADJ_MAX_LDS = 160 * 1024;      // of a gfx950 CU
 constexpr size_t plant_adjoint_lds(int nr, int n_cols, int nq) { return plant_adjoint_work_doubles(nr, n_cols, nq) * sizeof(double); }
@@ -67,9 +80,12 @@ struct PlantAdjointSolo {
     PADJ_HD void fetch_commit(double* dst, const double* src, int n) { for (int i = 0; i < n; ++i) dst[i] = src[i]; }
 };
 
-// The chain of robot rb.  work: shared by the team, plant_adjoint_work_doubles(nr, n_cols, nq).
-template <class Team>
-PADJ_HD inline void plant_adjoint_chain(const PlantAdjoint& P, int rb, double* work, Team& team) {
+// The chain of robot rb.  work: shared by the team, plant_adjoint_work_doubles(nr, n_cols, nq), with a feedback schedule
+// plant_adjoint_feedback_doubles(nu, nq) more.  FB: the feedback statements are compiled in (the caller has P.fb.K non-null); without
+// it the chain is, statement for statement, the open-loop one - plant_adjoint_kernel is instantiated both ways and the open-loop launch
+// carries nothing of the feedback path.
+template <bool FB, class Team>
+PADJ_HD inline void plant_adjoint_chain_as(const PlantAdjoint& P, int rb, double* work, Team& team) {
     const int me = team.rank(), np = team.size();
     const int nq = P.nq, nu = P.nu, nw = P.nw, nc = P.nc, nb = P.nb, n_cols = P.n_cols, B = P.B, T = P.T;
     const int nr = nq + nc + nb, blk = nr * n_cols;
@@ -77,6 +93,8 @@ PADJ_HD inline void plant_adjoint_chain(const PlantAdjoint& P, int rb, double* w
     double* D[2] = {work, work + blk};
     double* a = work + (size_t)2 * blk;
     double* ring = a + nr;                                            // lambda[t] lives in row t % 3
+    double* gu = ring + (size_t)3 * nq;                               // with feedback alone: the step's control cotangents and gx
+    double* gx = gu + nu;
     auto block = [&](int t) { return P.dz + ((size_t)t * B + rb) * blk; };
     auto row = [&](int t) { return ring + (t % 3) * nq; };
 
@@ -107,10 +125,24 @@ PADJ_HD inline void plant_adjoint_chain(const PlantAdjoint& P, int rb, double* w
             for (int r = 0; r < nr; ++r) v += col[r] * a[r];
             if (c < nq) l0[c] = (P.gq ? P.gq[e * nq + c] : 0.0) + v;
             else if (c < c_u) l1[c - nq] += v;
-            else if (c < c_w) P.g_u_step[e * nu + (c - c_u)] = v;
+            else if (c < c_w) { P.g_u_step[e * nu + (c - c_u)] = v; if constexpr (FB) gu[c - c_u] = v; }
             else if (c < c_mu) { if (P.g_w_step) P.g_w_step[e * nw + (c - c_w)] = v; }
             else if (c < c_h) s_mu += v;
             else s_h += v;
+        }
+        if constexpr (FB) {                                           // the feedback path of step t (plant_feedback.h)
+            const double* Kk = plant_feedback_gain(P.fb, t, rb, nu, nq);
+            team.sync();                                              // gu, lambda[t] and lambda[t+1] are whole
+            for (int j = me; j < 2 * nq; j += np) {                   // the member that owns column j
+                const double g = plant_feedback_pull(Kk, gu, nu, j);
+                gx[j] = g;
+                if (P.g_xref_step) P.g_xref_step[e * 2 * nq + j] = g;
+            }
+            team.sync();
+            for (int i = me; i < nq; i += np) {
+                l0[i] = plant_feedback_lambda0(l0[i], gx, P.fb.n_sample, i);
+                l1[i] = plant_feedback_lambda1(l1[i], gx, P.fb.n_sample, nq, i);
+            }
         }
         if (t > 0) team.fetch_commit(D[(t - 1) & 1], block(t - 1), blk);      // its last reader left it at the end of step t + 1
         team.sync();
@@ -123,6 +155,13 @@ PADJ_HD inline void plant_adjoint_chain(const PlantAdjoint& P, int rb, double* w
     if (P.g_mu && c_mu < n_cols && me == c_mu % np) P.g_mu[rb] = s_mu;
     if (P.g_h && c_h < n_cols && me == c_h % np) P.g_h[rb] = s_h;
     if (me == 0) P.n_cut[rb] = cut;
+}
+
+// The chain of robot rb, open or closed loop by what P carries.
+template <class Team>
+PADJ_HD inline void plant_adjoint_chain(const PlantAdjoint& P, int rb, double* work, Team& team) {
+    if (P.fb.K) plant_adjoint_chain_as<true>(P, rb, work, team);
+    else plant_adjoint_chain_as<false>(P, rb, work, team);
 }
 
 }  // namespace cimpc

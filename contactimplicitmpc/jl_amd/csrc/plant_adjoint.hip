@@ -4,6 +4,8 @@
 //   cimpc_plant_rollout_tape   cimpc_plant_rollout_grad whose sensitivity launch writes dz and its status into device memory the tape
 //                              owns (plant_rollout_to_tape, plant_kernel.hip); dz never crosses the bus
 //   cimpc_plant_tape_vjp       cotangents (gq, ggamma, gb) up, ONE launch of plant_adjoint_kernel, the small gradients down
+//   cimpc_plant_rollout_tape_feedback, cimpc_plant_tape_vjp_feedback   the two for a closed-loop rollout (plant_feedback.h): the tape also
+//                              owns the gain rows, the chain runs the feedback statements and returns g_xref_step when asked to
 //
 // plant_adjoint_kernel: a workgroup of one wavefront per robot walks t = T-1 .. 0 through the statements of plant_adjoint.h.  D_t
 // (nr x n_cols doubles, column-major as the sensitivity kernel wrote it) sits in LDS, loaded by the whole wavefront with consecutive
@@ -31,6 +33,7 @@ struct cimpc_plant_tape_s {
     cimpc::PlantModel M;
     double* d_dz;      // T x B x (nr x n_cols)
     int* d_status;     // T x B
+    cimpc::PlantFeedback fb;      // a closed-loop tape: fb.K the tape's device copy of the gain rows (x_ref is not needed); else fb.K null
 };
 
 namespace cimpc {
@@ -61,32 +64,56 @@ struct PlantAdjointWave {
     }
 };
 
+template <bool FB>      // FB: a closed-loop tape's chain, with the feedback statements of plant_feedback.h
 __global__ __launch_bounds__(ADJ_THREADS) void plant_adjoint_kernel(PlantAdjoint P) {
-    extern __shared__ __attribute__((aligned(16))) double adj_lds[];      // plant_adjoint_lds(nr, n_cols, nq)
+    extern __shared__ __attribute__((aligned(16))) double adj_lds[];      // plant_adjoint_lds(nr, n_cols, nq), + plant_adjoint_feedback_doubles with P.fb.K
     const int rb = blockIdx.x;
     if (rb >= P.B) return;                                                 // uniform over the workgroup
     PlantAdjointWave team;
-    plant_adjoint_chain(P, rb, adj_lds, team);
+    plant_adjoint_chain_as<FB>(P, rb, adj_lds, team);
 }
 
 }  // namespace cimpc
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------
-extern "C" int cimpc_plant_rollout_tape(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
-                                        const double* q0, const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w,
-                                        int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
-                                        double* q, double* gamma, double* b, int* status, int* iters, double reg, int n_cols, double* z,
-                                        int* grad_status, cimpc_plant_tape* tape) {
+namespace {
+int rollout_tape_impl(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain, const double* q0,
+                      const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w, int K_w, int n_w, int hold_w,
+                      const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status,
+                      int* iters, double reg, int n_cols, double* z, int* grad_status, cimpc_plant_tape* tape, bool closed_loop,
+                      const cimpc_feedback* fb, double* u_applied, double* fb_err) {
     using namespace cimpc;
     if (!tape) return CIMPC_ERR_INVALID;
     *tape = nullptr;
     if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
     PlantTapeBuffers buf;
     const int rc = plant_rollout_to_tape(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu,
-                                         n_mu, h, opts, q, gamma, b, status, iters, reg, n_cols, z, grad_status, &buf);
+                                         n_mu, h, opts, q, gamma, b, status, iters, reg, n_cols, z, grad_status, &buf, closed_loop, fb,
+                                         u_applied, fb_err);
     if (rc != CIMPC_OK) return rc;
-    *tape = new cimpc_plant_tape_s{buf.device, model, B, T, n_cols, buf.M, buf.d_dz, buf.d_status};
+    *tape = new cimpc_plant_tape_s{buf.device, model, B, T, n_cols, buf.M, buf.d_dz, buf.d_status,
+                                   PlantFeedback{buf.d_fb_K, nullptr, buf.K_f, buf.n_f, buf.hold_f, buf.n_sample}};
     return CIMPC_OK;
+}
+}  // namespace
+
+extern "C" int cimpc_plant_rollout_tape_feedback(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                                 const double* q0, const double* q1, const double* u, int K_u, int n_u, int hold_u,
+                                                 const double* w, int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h,
+                                                 const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status, int* iters,
+                                                 double reg, int n_cols, double* z, int* grad_status, cimpc_plant_tape* tape,
+                                                 const cimpc_feedback* fb, double* u_applied, double* fb_err) {
+    return rollout_tape_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu, h,
+                             opts, q, gamma, b, status, iters, reg, n_cols, z, grad_status, tape, true, fb, u_applied, fb_err);
+}
+
+extern "C" int cimpc_plant_rollout_tape(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                        const double* q0, const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w,
+                                        int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                                        double* q, double* gamma, double* b, int* status, int* iters, double reg, int n_cols, double* z,
+                                        int* grad_status, cimpc_plant_tape* tape) {
+    return rollout_tape_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu, h,
+                             opts, q, gamma, b, status, iters, reg, n_cols, z, grad_status, tape, false, nullptr, nullptr, nullptr);
 }
 
 extern "C" int cimpc_plant_tape_dims(cimpc_plant_tape tape, int* model, int* B, int* T, int* n_cols) {
@@ -109,6 +136,7 @@ extern "C" int cimpc_plant_tape_destroy(cimpc_plant_tape tape) {
         if (ok) {
             ok = hipFree(tape->d_dz) == hipSuccess;
             ok = (hipFree(tape->d_status) == hipSuccess) && ok;
+            if (tape->fb.K) ok = (hipFree(const_cast<double*>(tape->fb.K)) == hipSuccess) && ok;
             if (cur != tape->device) ok = (hipSetDevice(cur) == hipSuccess) && ok;
         }
     }
@@ -117,18 +145,23 @@ extern "C" int cimpc_plant_tape_destroy(cimpc_plant_tape tape) {
 }
 
 // Validate (no device needed), then on the tape's device and the plant workspace's private stream: one upload (gq | ggamma | gb, those
-// given), one launch, one read-back (g_q0 | g_q1 | g_u_step | g_w_step | g_mu | g_h, n_cut), one synchronize.
-extern "C" int cimpc_plant_tape_vjp(cimpc_plant_tape tape, const double* gq, const double* ggamma, const double* gb, double* g_q0,
-                                    double* g_q1, double* g_u_step, double* g_w_step, double* g_mu, double* g_h, int* n_cut) {
+// given), one launch, one read-back (g_q0 | g_q1 | g_u_step | g_w_step | g_mu | g_h, n_cut), one synchronize.  A closed-loop tape's chain always runs the
+// feedback statements; g_xref_step (T x B x 2nq, may be null) is theirs and is refused on an open-loop tape.
+extern "C" int cimpc_plant_tape_vjp_feedback(cimpc_plant_tape tape, const double* gq, const double* ggamma, const double* gb, double* g_q0,
+                                    double* g_q1, double* g_u_step, double* g_w_step, double* g_mu, double* g_h, int* n_cut,
+                                    double* g_xref_step) {
     using namespace cimpc;
     if (!tape || (!gq && !ggamma && !gb) || !g_q0 || !g_q1 || !g_u_step || !n_cut) return CIMPC_ERR_INVALID;
+    if (g_xref_step && !tape->fb.K) return CIMPC_ERR_INVALID;
     const PlantModel& M = tape->M;
     const int B = tape->B, T = tape->T, n_cols = tape->n_cols;
     const size_t nq = M.nq, nu = M.nu, nw = M.nw, nc = M.nc, nb = M.nb(), TB = (size_t)T * B;
     const size_t c_mu = 2 * nq + nu + nw;                              // the columns of theta = [q0; q1; u1; w1; mu; h]
     if ((g_w_step && (size_t)n_cols < c_mu) || (g_mu && (size_t)n_cols < c_mu + 1) || (g_h && (size_t)n_cols < c_mu + 2)) return CIMPC_ERR_INVALID;
     const int nr = (int)(nq + nc + nb);
-    if (!plant_adjoint_fits(nr, n_cols, (int)nq)) return CIMPC_ERR_INVALID;
+    const size_t lds = (plant_adjoint_work_doubles(nr, n_cols, (int)nq) + (tape->fb.K ? plant_adjoint_feedback_doubles((int)nu, (int)nq) : 0)) * sizeof(double);
+    if (!plant_adjoint_fits(nr, n_cols, (int)nq) || lds > PLANT_ADJ_MAX_LDS) return CIMPC_ERR_INVALID;
+    const size_t n_x = g_xref_step ? TB * 2 * nq : 0;
     // the staging buffers: cotangents in, gradients out, in the order of the argument list
     const size_t n_gq = gq ? (size_t)(T + 2) * B * nq : 0, n_gg = ggamma ? TB * nc : 0, n_gb = gb ? TB * nb : 0;
     const size_t n_q = (size_t)B * nq, n_u = TB * nu, n_w = g_w_step ? TB * nw : 0, n_m = g_mu ? (size_t)B : 0, n_h = g_h ? (size_t)B : 0;
@@ -139,7 +172,7 @@ extern "C" int cimpc_plant_tape_vjp(cimpc_plant_tape tape, const double* gq, con
     bool ok = false;
     PlantWs* ws = plant_ws_open(tape->device);
     if (ws && plant_grow(&ws->d_adj_in, &ws->cap_adj_in, n_gq + n_gg + n_gb) && plant_grow(&ws->d_adj_out, &ws->cap_adj_out, 2 * n_q + n_u + n_w + n_m + n_h) &&
-        plant_grow(&ws->d_adj_cut, &ws->cap_adj_cut, (size_t)B)) {
+        plant_grow(&ws->d_adj_cut, &ws->cap_adj_cut, (size_t)B) && (!n_x || plant_grow(&ws->d_adj_xref, &ws->cap_adj_xref, n_x))) {
         hipStream_t st = ws->st;
         double* d_gq = ws->d_adj_in; double* d_gg = d_gq + n_gq; double* d_gb = d_gg + n_gg;
         double* d_q0 = ws->d_adj_out; double* d_q1 = d_q0 + n_q; double* d_u = d_q1 + n_q; double* d_w = d_u + n_u; double* d_m = d_w + n_w;
@@ -149,13 +182,14 @@ extern "C" int cimpc_plant_tape_vjp(cimpc_plant_tape tape, const double* gq, con
         if (ok && ggamma) ok = hipMemcpyAsync(d_gg, ggamma, n_gg * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
         if (ok && gb) ok = hipMemcpyAsync(d_gb, gb, n_gb * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
         if (ok) {
-            const PlantAdjoint P{tape->d_dz, tape->d_status, gq ? d_gq : nullptr, ggamma ? d_gg : nullptr, gb ? d_gb : nullptr, d_q0, d_q1, d_u,
+            PlantAdjoint P{tape->d_dz, tape->d_status, gq ? d_gq : nullptr, ggamma ? d_gg : nullptr, gb ? d_gb : nullptr, d_q0, d_q1, d_u,
                                  g_w_step ? d_w : nullptr, g_mu ? d_m : nullptr, g_h ? d_h : nullptr, ws->d_adj_cut, B, T, (int)nq, (int)nu,
                                  (int)nw, (int)nc, (int)nb, n_cols};
-            const size_t lds = plant_adjoint_lds(nr, n_cols, (int)nq);
-            ok = hipFuncSetAttribute(reinterpret_cast<const void*>(plant_adjoint_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+            if (tape->fb.K) { P.fb = tape->fb; P.g_xref_step = g_xref_step ? ws->d_adj_xref : nullptr; }
+            auto kernel = tape->fb.K ? plant_adjoint_kernel<true> : plant_adjoint_kernel<false>;
+            ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
             if (ok) {
-                hipLaunchKernelGGL(plant_adjoint_kernel, dim3(B), dim3(ADJ_THREADS), lds, st, P);
+                hipLaunchKernelGGL(kernel, dim3(B), dim3(ADJ_THREADS), lds, st, P);
                 ok = hipGetLastError() == hipSuccess;
             }
         }
@@ -165,9 +199,15 @@ extern "C" int cimpc_plant_tape_vjp(cimpc_plant_tape tape, const double* gq, con
                      hipMemcpyAsync(n_cut, ws->d_adj_cut, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
         if (ok && g_w_step) ok = hipMemcpyAsync(g_w_step, d_w, n_w * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
         if (ok && g_mu) ok = hipMemcpyAsync(g_mu, d_m, n_m * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
+        if (ok && g_xref_step) ok = hipMemcpyAsync(g_xref_step, ws->d_adj_xref, n_x * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
         if (ok && g_h) ok = hipMemcpyAsync(g_h, d_h, n_h * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
         ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
     }
     if (cur != tape->device) ok = (hipSetDevice(cur) == hipSuccess) && ok;
     return ok ? CIMPC_OK : CIMPC_ERR_HIP;
+}
+
+extern "C" int cimpc_plant_tape_vjp(cimpc_plant_tape tape, const double* gq, const double* ggamma, const double* gb, double* g_q0,
+                                    double* g_q1, double* g_u_step, double* g_w_step, double* g_mu, double* g_h, int* n_cut) {
+    return cimpc_plant_tape_vjp_feedback(tape, gq, ggamma, gb, g_q0, g_q1, g_u_step, g_w_step, g_mu, g_h, n_cut, nullptr);
 }

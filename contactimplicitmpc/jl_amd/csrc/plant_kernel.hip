@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "../../../include/cimpc.h"
+#include "plant_feedback.h"
 #include "plant_ground.h"
 #include "plant_model.h"
 #include "plant_rollout_plan.h"
@@ -37,7 +38,9 @@ struct PlantOpts {
 // read, rows t0 + 2 .. t0 + n + 1 written; u: K_u x n_u x nu, w: K_w x n_w x nw or null (rollout_row picks the row of a step; n_* = 1: one
 // schedule for every robot, B: one per robot); friction mu0 (n_mu = 1) or mu[rb] (n_mu = B); per-step outputs gamma: T x B x nc,
 // b: T x B x nb, status and iters: T x B; z: T x B x nz, the whole converged z of every step (what the step gradients are taken at), or
-// null (every entry point but cimpc_plant_rollout_grad).  One simulator step is T = 1, t0 = 0, n = 1.
+// null (every entry point but cimpc_plant_rollout_grad).  One simulator step is T = 1, t0 = 0, n = 1.  fb.K non-null: a closed-loop
+// rollout (plant_feedback.h) - the step applies u_t = u row + K (x_ref - x) and stores it and the error e: u_applied T x B x nu,
+// fb_err T x B x 2nq.
 struct PlantRollout {
     double* q;
     const double *u, *w, *mu;
@@ -46,6 +49,8 @@ struct PlantRollout {
     double mu0, h;
     int t0, n, K_u, n_u, hold_u, K_w, n_w, hold_w, n_mu;
     double* z;
+    PlantFeedback fb;
+    double *u_applied, *fb_err;
 };
 
 __device__ __forceinline__ void wsync() { __syncthreads(); }         // one or two wavefronts per workgroup
@@ -80,7 +85,11 @@ constexpr int step_threads(int NZ) { return NZ <= NZM ? 64 : 128; }
 // matrix shrink with NZ.  The iteration names the LDS arrays directly: handed to a helper as pointers they cost
 // the TERRAIN instantiation 8-15 %.  Between steps the state stays in LDS: q2 is stored to its trajectory row
 // and shifted into theta (q1 -> q0, q2 -> q1), nothing is read back from global memory.
-template <int NZ, int NT, int GROUND>
+// LOOP: each of the six also with the closed-loop branch of plant_feedback.h compiled in, launched by the _feedback entry points alone.
+// The open-loop instantiations are compiled without it because the branch is not free there: in (20, 64, WALLS) it took 174 VGPRs for 167
+// and 2 waves per SIMD for 3, and pushbot's rollout at B = 8192 and 32768 came out 1.17 x and 1.31 x slower.
+// The iteration is one text, and tests/test_gpu_plant_feedback.py holds the two instantiations to the same bits on every instance.
+template <int NZ, int NT, int GROUND, bool LOOP>
 __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts o, int B, PlantRollout R, const cimpc_terrain* terrain,
                                                         int n_terrain) {
     static_assert(NT == 64 || NT == 128, "one or two wavefronts per robot");
@@ -204,6 +213,25 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
         const double* wt = R.w ? rollout_schedule(R.w, t, R.hold_w, R.K_w, R.n_w, rb, M.nw) : nullptr;
         for (int i = lane; i < nu + M.nw; i += NT) ths[2 * nq + i] = i < nu ? ut[i] : wt ? wt[i - nu] : 0.0;
     }
+    // closed loop: the law of plant_feedback.h on the two rows in ths - lane j the error e[j] (kept in xs, which the step first writes in
+    // its corrector), lane i the control u_t[i], which replaces the schedule row's in θ; both go to global memory.  Uniform over the block.
+    if constexpr (LOOP) if (R.fb.K) {
+        const size_t row = (size_t)t * B + rb;
+        const double* target = plant_feedback_target(R.fb, t, rb, nq);
+        wsync();                                                       // q0, q1 of θ are whole (other lanes wrote them)
+        for (int j = lane; j < 2 * nq; j += NT) {
+            const double e = plant_feedback_error(target, ths, ths + nq, nq, R.fb.n_sample, j);
+            xs[j] = e;
+            R.fb_err[row * (2 * nq) + j] = e;
+        }
+        wsync();
+        const double* Kk = plant_feedback_gain(R.fb, t, rb, nu, nq);
+        for (int i = lane; i < nu; i += NT) {
+            const double ui = plant_feedback_control(Kk, xs, nu, nq, i, ths[2 * nq + i]);
+            ths[2 * nq + i] = ui;
+            R.u_applied[row * nu + i] = ui;
+        }
+    }
     for (int i = lane; i < nz; i += NT) zs[i] = i < nq ? ths[nq + i] : 1.0;
     wsync();
     eval_r(0.0, rs);
@@ -284,6 +312,9 @@ namespace {
 // follows the chunks on the same stream - theta is put together on the device from the rollout's own buffers - and dz, its status and,
 // when asked for, z come back with the rollout's read-back.  With `tape` (cimpc_plant_rollout_tape, plant_tape.h) that launch writes dz
 // and its status into device memory allocated here for the tape, and dz stays there: it needs no host dz, and n_cols >= 2 nq + nu.
+// With `loop` (the _feedback entry points) the schedule goes up with the inputs, the LOOP instantiation of the kernel runs with R.fb set -
+// the law at the head of a step, then the open-loop step on the control it computed -, u_applied and fb_err come back with
+// the rollout, and the sensitivity launch reads its controls from u_applied.
 struct RolloutGrad {
     double reg;
     int n_cols;
@@ -291,10 +322,17 @@ struct RolloutGrad {
     int* status;
     cimpc::PlantTapeBuffers* tape = nullptr;
 };
+// A closed-loop call (the _feedback entry points): the host schedule and where u_applied (T x B x nu) and fb_err (T x B x 2nq) go.  The
+// schedule and the two outputs live in the workspace's d_fb: K | x_ref | u_applied | fb_err; with a tape K lives in memory the tape owns
+// (the reverse chain reads it).  The sensitivity launch then reads its controls from u_applied, a schedule with K_u = T, n_u = B, hold 1.
+struct RolloutFeedback {
+    const cimpc_feedback* fb;
+    double *u_applied, *fb_err;
+};
 int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain, const double* q0,
                        const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w, int K_w, int n_w, int hold_w,
                        const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, double* q, int q_row0, double* gamma, double* b,
-                       int* status, int* iters, const RolloutGrad* grad = nullptr) {
+                       int* status, int* iters, const RolloutGrad* grad = nullptr, const RolloutFeedback* loop = nullptr) {
     using namespace cimpc;
     if (B <= 0 || !q0 || !q1 || !u || !opts || !q || !gamma || !b || !status || !iters || h <= 0.0) return CIMPC_ERR_INVALID;
     if (T < 1 || steps_per_launch < 0 || K_u < 1 || hold_u < 1 || (n_u != 1 && n_u != B) || !mu || (n_mu != 1 && n_mu != B)) return CIMPC_ERR_INVALID;
@@ -308,6 +346,17 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
                  !plant_sensitivity_fits(M.nz(), grad->n_cols) || (long long)T * B > INT_MAX))
         return CIMPC_ERR_INVALID;
     if (grad && grad->tape && grad->n_cols < 2 * M.nq + M.nu) return CIMPC_ERR_INVALID;
+    size_t n_fk = 0, n_fx = 0;
+    if (loop) {
+        const cimpc_feedback* f = loop->fb;
+        if (!f || !f->K || !f->x_ref || !loop->u_applied || !loop->fb_err || f->K_f < 1 || f->hold_f < 1 || (f->n_f != 1 && f->n_f != B) ||
+            !std::isfinite(f->n_sample) || !(f->n_sample > 0.0) || 2 * M.nq > M.nz())
+            return CIMPC_ERR_INVALID;
+        n_fx = (size_t)f->K_f * f->n_f * 2 * M.nq;
+        n_fk = n_fx * M.nu;
+        for (size_t i = 0; i < n_fk; ++i) if (!std::isfinite(f->K[i])) return CIMPC_ERR_INVALID;
+        for (size_t i = 0; i < n_fx; ++i) if (!std::isfinite(f->x_ref[i])) return CIMPC_ERR_INVALID;
+    }
     int dev = 0;
     if (!plant_current_device(&dev)) return CIMPC_ERR_NO_DEVICE;
     const size_t pnc = (size_t)M.nc, pnb = (size_t)M.nb();
@@ -325,6 +374,8 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
     if (rough && !plant_grow(&W.d_ter, &W.cap_ter, (size_t)n_terrain)) return CIMPC_ERR_HIP;
     const size_t n_zs = TB * (size_t)M.nz(), n_dz = grad ? TB * (nq + pnc + pnb) * (size_t)grad->n_cols : 0;
     if (grad && !plant_grow(&W.d_z, &W.cap_z, n_zs)) return CIMPC_ERR_HIP;
+    const size_t n_ua = loop ? TB * nu : 0, n_fe = loop ? TB * 2 * nq : 0;
+    if (loop && !plant_grow(&W.d_fb, &W.cap_fb, n_fk + n_fx + n_ua + n_fe)) return CIMPC_ERR_HIP;
     if (grad && !grad->tape && (!plant_grow(&W.d_grad, &W.cap_grad, n_dz) || !plant_grow(&W.d_grad_st, &W.cap_grad_st, TB))) return CIMPC_ERR_HIP;
     double* d_dz = W.d_grad;
     int* d_gst = W.d_grad_st;
@@ -336,9 +387,20 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
             tp.d_dz = nullptr; tp.d_status = nullptr;
             return CIMPC_ERR_HIP;
         }
+        if (loop && hipMalloc((void**)&tp.d_fb_K, n_fk * sizeof(double)) != hipSuccess) {
+            (void)hipFree(tp.d_dz);
+            (void)hipFree(tp.d_status);
+            tp.d_dz = nullptr; tp.d_status = nullptr; tp.d_fb_K = nullptr;
+            return CIMPC_ERR_HIP;
+        }
         tp.device = dev; tp.M = M;
+        if (loop) { tp.K_f = loop->fb->K_f; tp.n_f = loop->fb->n_f; tp.hold_f = loop->fb->hold_f; tp.n_sample = loop->fb->n_sample; }
         d_dz = tp.d_dz; d_gst = tp.d_status;
     }
+    double* d_fk = loop ? (grad && grad->tape ? grad->tape->d_fb_K : W.d_fb) : nullptr;
+    double* d_fx = loop ? W.d_fb + n_fk : nullptr;
+    double* d_ua = loop ? d_fx + n_fx : nullptr;
+    double* d_fe = loop ? d_ua + n_ua : nullptr;
     double* dq = W.d_in; double* du = dq + n_q; double* dw = du + n_us; double* dmu = dw + n_ws;
     double* dg = W.d_out; double* db = dg + TB * pnc;
     int* d_st = W.d_st;
@@ -349,21 +411,25 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
     if (ok && w) ok = hipMemcpyAsync(dw, w, n_ws * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
     if (ok && n_mus) ok = hipMemcpyAsync(dmu, mu, n_mus * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
     if (ok && rough) ok = hipMemcpyAsync(W.d_ter, terrain, (size_t)n_terrain * sizeof(cimpc_terrain), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok && loop) ok = hipMemcpyAsync(d_fk, loop->fb->K, n_fk * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
+                         hipMemcpyAsync(d_fx, loop->fb->x_ref, n_fx * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
     PlantRollout R{dq, du, w ? dw : nullptr, n_mus ? dmu : nullptr, dg, db, d_st, d_st + TB, mu[0], h, 0, 0, K_u, n_u, hold_u, w ? K_w : 1,
-                   w ? n_w : 1, w ? hold_w : 1, n_mu, grad ? W.d_z : nullptr};
+                   w ? n_w : 1, w ? hold_w : 1, n_mu, grad ? W.d_z : nullptr, PlantFeedback{}, nullptr, nullptr};
+    if (loop) { R.fb = PlantFeedback{d_fk, d_fx, loop->fb->K_f, loop->fb->n_f, loop->fb->hold_f, loop->fb->n_sample}; R.u_applied = d_ua; R.fb_err = d_fe; }
     for (int k = 0; ok && k < rollout_chunk_count(T, steps_per_launch); ++k) {
         const RolloutChunk c = rollout_chunk(T, steps_per_launch, k);
         R.t0 = c.t0; R.n = c.n;
         ok = plant_visit_instance(M, rough, true, [&](auto tag) {
             using I = decltype(tag);
             constexpr int NT = step_threads(I::NZ);
-            auto kernel = plant_step_kernel<I::NZ, NT, I::GROUND>;
+            auto kernel = loop ? plant_step_kernel<I::NZ, NT, I::GROUND, true> : plant_step_kernel<I::NZ, NT, I::GROUND, false>;
             hipLaunchKernelGGL(kernel, dim3(B), dim3(NT), 0, st, M, o, B, R, rough ? W.d_ter : nullptr, rough ? n_terrain : 0);
             return hipGetLastError() == hipSuccess;
         });
     }
     if (ok && grad) {
         PlantSensSource src{W.d_z, nullptr, dq, du, R.w, R.mu, d_st, R.mu0, h, B, R.K_u, R.n_u, R.hold_u, R.K_w, R.n_w, R.hold_w, n_mu};
+        if (loop) { src.u = d_ua; src.K_u = T; src.n_u = B; src.hold_u = 1; }      // the controls the steps applied
         ok = plant_sensitivity_launch(M, (int)TB, src, rough ? W.d_ter : nullptr, rough ? n_terrain : 0, grad->reg, grad->n_cols, d_dz, d_gst, st);
         if (ok && !grad->tape) ok = hipMemcpyAsync(grad->dz, d_dz, n_dz * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
         ok = ok && hipMemcpyAsync(grad->status, d_gst, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
@@ -374,11 +440,14 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
                  hipMemcpyAsync(b, db, TB * pnb * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
                  hipMemcpyAsync(status, d_st, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
                  hipMemcpyAsync(iters, d_st + TB, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
+    if (ok && loop) ok = hipMemcpyAsync(loop->u_applied, d_ua, n_ua * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                         hipMemcpyAsync(loop->fb_err, d_fe, n_fe * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
     if (!ok && grad && grad->tape) {
         (void)hipFree(grad->tape->d_dz);
         (void)hipFree(grad->tape->d_status);
-        grad->tape->d_dz = nullptr; grad->tape->d_status = nullptr;
+        if (grad->tape->d_fb_K) (void)hipFree(grad->tape->d_fb_K);
+        grad->tape->d_dz = nullptr; grad->tape->d_status = nullptr; grad->tape->d_fb_K = nullptr;
     }
     return ok ? CIMPC_OK : CIMPC_ERR_HIP;
 }
@@ -387,10 +456,12 @@ int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terr
 int cimpc::plant_rollout_to_tape(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain, const double* q0,
                                  const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w, int K_w, int n_w, int hold_w,
                                  const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, double* q, double* gamma, double* b,
-                                 int* status, int* iters, double reg, int n_cols, double* z, int* grad_status, PlantTapeBuffers* tape) {
+                                 int* status, int* iters, double reg, int n_cols, double* z, int* grad_status, PlantTapeBuffers* tape,
+                                 bool closed_loop, const cimpc_feedback* fb, double* u_applied, double* fb_err) {
     const RolloutGrad grad{reg, n_cols, z, nullptr, grad_status, tape};
+    const RolloutFeedback loop{fb, u_applied, fb_err};
     return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
-                              h, opts, q, 0, gamma, b, status, iters, &grad);
+                              h, opts, q, 0, gamma, b, status, iters, &grad, closed_loop ? &loop : nullptr);
 }
 
 extern "C" int cimpc_plant_step(int model, int B, const double* q0, const double* q1, const double* u, const double* w,
@@ -424,4 +495,28 @@ extern "C" int cimpc_plant_rollout_grad(int model, int B, int T, int steps_per_l
     const RolloutGrad grad{reg, n_cols, z, dz, grad_status};
     return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
                               h, opts, q, 0, gamma, b, status, iters, &grad);
+}
+
+extern "C" int cimpc_plant_rollout_feedback(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                            const double* q0, const double* q1, const double* u, int K_u, int n_u, int hold_u,
+                                            const double* w, int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h,
+                                            const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status, int* iters,
+                                            const cimpc_feedback* fb, double* u_applied, double* fb_err) {
+    if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
+    const RolloutFeedback loop{fb, u_applied, fb_err};
+    return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
+                              h, opts, q, 0, gamma, b, status, iters, nullptr, &loop);
+}
+
+extern "C" int cimpc_plant_rollout_grad_feedback(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                                 const double* q0, const double* q1, const double* u, int K_u, int n_u, int hold_u,
+                                                 const double* w, int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h,
+                                                 const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status, int* iters,
+                                                 double reg, int n_cols, double* z, double* dz, int* grad_status, const cimpc_feedback* fb,
+                                                 double* u_applied, double* fb_err) {
+    if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
+    const RolloutGrad grad{reg, n_cols, z, dz, grad_status};
+    const RolloutFeedback loop{fb, u_applied, fb_err};
+    return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
+                              h, opts, q, 0, gamma, b, status, iters, &grad, &loop);
 }

@@ -7,7 +7,10 @@
 //   linearize       d_lin_in: z | theta | terrains (N x nz, N x nth, n_terrain cimpc_terrain); d_lin_out: r0 | rz0 | rth0 (those asked for)
 //   step gradients  d_z: the converged z of every step of a rollout (T x B x nz); d_grad: dz (N x nr x n_cols); d_grad_st: status (N);
 //                   cimpc_plant_sensitivity stages its knots in d_lin_in
-//   reverse chain   d_adj_in: gq | ggamma | gb (those given); d_adj_out: g_q0 | g_q1 | g_u_step | g_w_step | g_mu | g_h; d_adj_cut: n_cut (B).
+//   closed loop     d_fb: the feedback schedule and what the steps made of it, K | x_ref | u_applied (T x B x nu) | fb_err (T x B x 2nq);
+//                   with a tape, K is in the tape's memory instead
+//   reverse chain   d_adj_in: gq | ggamma | gb (those given); d_adj_out: g_q0 | g_q1 | g_u_step | g_w_step | g_mu | g_h; d_adj_cut: n_cut (B);
+//                   d_adj_xref: g_xref_step (T x B x 2nq) of a closed-loop tape.
 //                   A tape's dz and status are NOT here: they belong to the tape (plant_adjoint.hip) and live as long as it does
 // The prologue the entry points share is stated here once: which model and ground a call names (plant_model_and_ground, no device
 // needed), which device it runs on (plant_current_device), and its workspace with the stream open (plant_ws_open).
@@ -36,6 +39,8 @@ struct PlantWs {
     double *d_adj_in = nullptr, *d_adj_out = nullptr;
     int* d_adj_cut = nullptr;
     size_t cap_adj_in = 0, cap_adj_out = 0, cap_adj_cut = 0;
+    double *d_fb = nullptr, *d_adj_xref = nullptr;
+    size_t cap_fb = 0, cap_adj_xref = 0;
 };
 constexpr int PLANT_MAX_DEVICES = 16;
 extern PlantWs g_plant_ws[PLANT_MAX_DEVICES];      // defined in plant_kernel.hip

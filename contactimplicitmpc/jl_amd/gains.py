@@ -99,3 +99,17 @@ def reference_gains(model_name, z, theta, obj_q, obj_v, obj_u, N=10, U_scaling=1
                                           float(V_scaling), _dp(K), _dp(P1)), "cimpc_reference_gains")
     K = np.ascontiguousarray(K.transpose(0, 2, 1))
     return (K, np.ascontiguousarray(P1.T)) if return_P1 else K
+
+
+def gait_feedback(q_ref, K, N_sample: int = 1, n_sample=None):
+    """A gait and its `reference_gains` output as the `plant.Feedback` of a closed-loop rollout at N_sample simulator steps per knot:
+    q_ref (H + 2, nq) the gait's configurations (`gait_io.Gait.q`), K (H, nu, 2nq); x_ref[k] = [q_ref[k]; q_ref[k + 1]], the target of the
+    policy's feedback line at knot k (H-periodic: q_ref[H], q_ref[H + 1] close the cycle), every row held for N_sample steps and the last
+    from there on.  A rollout longer than H N_sample steps takes a K and x_ref tiled by the caller."""
+    from . import plant
+    q_ref, K = np.asarray(q_ref, dtype=np.float64), np.asarray(K, dtype=np.float64)
+    H = K.shape[0]
+    if K.ndim != 3 or q_ref.ndim != 2 or q_ref.shape[0] != H + 2 or K.shape[2] != 2 * q_ref.shape[1]:
+        raise ValueError("q_ref must be (H + 2, nq) beside K (H, nu, 2nq)")
+    x_ref = np.concatenate([q_ref[:H], q_ref[1:H + 1]], axis=1)
+    return plant.Feedback(K=K, x_ref=x_ref, hold=int(N_sample), n_sample=n_sample)

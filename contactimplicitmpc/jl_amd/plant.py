@@ -10,6 +10,9 @@ open-loop schedule of controls and disturbances in one call with every intermedi
 (simulator.jl:23,31,60; `cimpc_plant_rollout_grad`) as a `StepGradients`; `sensitivity` is their kernel on caller-supplied knots.
 `rollout_tape` keeps those gradients on the device as a `RolloutTape`, whose `vjp` backpropagates cotangents of the trajectory to the
 rollout's arguments (`cimpc_plant_rollout_tape`, `cimpc_plant_tape_vjp`); `rollout_torch` is the two as a `torch.autograd.Function`.
+`feedback=Feedback(K, x_ref)` on `rollout`, `rollout_tape` and `rollout_torch` closes the loop on the device, u = ū + K (x_ref − x) at
+every step (`cimpc_plant_rollout_feedback` and its kin), and `vjp` then also returns the gradient with
+respect to the gains and the reference states.
 Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble
 solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain.
 """
@@ -105,11 +108,48 @@ def _grad_args(model: str, opts: InteriorPointOptions, grad_reg, grad_cols):
     return reg, n_cols
 
 
+@dataclasses.dataclass
+class Feedback:
+    """Linear state feedback of a closed-loop rollout, u_t = ū_t + (K[k] / N_sample) (x_ref[k] − x_t) with x_t = [q0; q1], q1 = q[t + 1],
+    q0 = q1 − n_sample (q1 − q[t]) and k = min(t // hold, K_f − 1) (DESIGN.md section 3, item 3c).  K (K_f, nu, 2nq) shared by every robot
+    or (K_f, B, nu, 2nq) - `gains.reference_gains`' output is the first -, x_ref (K_f, 2nq) or (K_f, B, 2nq), shared or per robot together;
+    hold: simulator steps a row is held for, the last row from there on; n_sample: the rollout's N_sample when None.  The gains are
+    nominal, like u: a step applies K[k] / N_sample beside u[k] / N_sample."""
+    K: object
+    x_ref: object
+    hold: int = 1
+    n_sample: object = None
+
+
+def _feedback_arrays(model: str, fb: Feedback, B: int, N_sample: int):
+    """A `Feedback` checked and laid out for the library: (K rows (K_f, n_f, 2nq, nu) = K / N_sample with column-major blocks, x_ref
+    (K_f, n_f, 2nq), hold, n_sample, shared)."""
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    K, xr = np.asarray(fb.K, dtype=np.float64), np.asarray(fb.x_ref, dtype=np.float64)
+    shared = K.ndim == 3
+    if K.ndim not in (3, 4) or K.shape[0] < 1 or K.shape[-2:] != (nu, 2 * nq) or (not shared and K.shape[1] != B):
+        raise ValueError(f"Feedback.K must be (K_f, {nu}, {2 * nq}) or (K_f, B, {nu}, {2 * nq}), got {K.shape}")
+    if xr.shape != ((K.shape[0], 2 * nq) if shared else (K.shape[0], B, 2 * nq)):
+        raise ValueError(f"Feedback.x_ref must be (K_f, {2 * nq}){'' if shared else ' or (K_f, B, ' + str(2 * nq) + ')'} beside K {K.shape}, got {xr.shape}")
+    if int(fb.hold) < 1:
+        raise ValueError("Feedback.hold must be at least 1")
+    n_sample = float(N_sample if fb.n_sample is None else fb.n_sample)
+    if not (np.isfinite(n_sample) and n_sample > 0.0):
+        raise ValueError("Feedback.n_sample must be finite and positive")
+    if not (np.isfinite(K).all() and np.isfinite(xr).all()):
+        raise ValueError("Feedback.K and Feedback.x_ref must be finite")
+    if shared:
+        K, xr = K[:, None], xr[:, None]
+    return np.ascontiguousarray((K / int(N_sample)).transpose(0, 1, 3, 2)), np.ascontiguousarray(xr), int(fb.hold), n_sample, shared
+
+
 def _rollout_call(model: str, q0, q1, ua, hold_u: int, wa, hold_w: int, mua, h: float, opts, terrain, steps_per_launch: int, T: int, grad,
-                  tape=None):
+                  tape=None, feedback=None):
     """`cimpc_plant_rollout`, or `cimpc_plant_rollout_grad` with grad = (reg, n_cols): contiguous q0, q1 (B, nq), ua (K, 1 or B, nu),
     wa None or (K_w, 1 or B, nw), mua (1 or B,) -> (q, gamma, b, status, iters, StepGradients or None).  tape = keep_z (a bool) with grad:
-    `cimpc_plant_rollout_tape`, whose last element is (z or None, grad_status, the tape's handle)."""
+    `cimpc_plant_rollout_tape`, whose last element is (z or None, grad_status, the tape's handle).  feedback = the first four elements of
+    `_feedback_arrays`: the `_feedback` entry of each, and one more element, (u_applied (T, B, nu), fb_err (T, B, 2nq)) as the device
+    made them."""
     mid, nq, nu, nc, fd, nw = model_dims(model)
     B, nb, nz = q1.shape[0], fd * nc, nq + 4 * nc + 2 * fd * nc
     lib = _lib.load()
@@ -122,25 +162,31 @@ def _rollout_call(model: str, q0, q1, ua, hold_u: int, wa, hold_w: int, mua, h: 
     args = (mid, B, T, int(steps_per_launch), nt, ta, dp(q0), dp(q1), dp(ua), ua.shape[0], ua.shape[1], int(hold_u),
             dp(wa), 1 if wa is None else wa.shape[0], 1 if wa is None else wa.shape[1], int(hold_w), dp(mua), mua.size,
             float(h), C.byref(o), dp(q), dp(g), dp(b), ip(st), ip(it))
+    sfx, loop, more = "", (), ()
+    if feedback is not None:
+        Kc, xr, hold_f, n_sample = feedback
+        cfb = _lib.Feedback(dp(Kc), dp(xr), Kc.shape[0], Kc.shape[1], hold_f, n_sample)
+        u_dev, fb_err = np.zeros((T, B, nu)), np.zeros((T, B, 2 * nq))
+        sfx, loop, more = "_feedback", (C.byref(cfb), dp(u_dev), dp(fb_err)), ((u_dev, fb_err),)
     if grad is None:
-        rc = lib.cimpc_plant_rollout(*args)
+        rc = getattr(lib, "cimpc_plant_rollout" + sfx)(*args, *loop)
         if rc != 0:
-            raise _lib.CimpcError(f"cimpc_plant_rollout failed ({rc})")
-        return q, g, b, st, it, None
+            raise _lib.CimpcError(f"cimpc_plant_rollout{sfx} failed ({rc})")
+        return (q, g, b, st, it, None) + more
     reg, n_cols = grad
     if tape is not None:      # dz stays on the device (`cimpc_plant_rollout_tape`): (z or None, grad_status, the tape's handle)
         z = np.zeros((T, B, nz)) if tape else None
         gst = np.zeros((T, B), dtype=np.int32)
         handle = C.c_void_p()
-        rc = lib.cimpc_plant_rollout_tape(*args, reg, n_cols, dp(z), ip(gst), C.byref(handle))
+        rc = getattr(lib, "cimpc_plant_rollout_tape" + sfx)(*args, reg, n_cols, dp(z), ip(gst), C.byref(handle), *loop)
         if rc != 0:
-            raise _lib.CimpcError(f"cimpc_plant_rollout_tape failed ({rc})")
-        return q, g, b, st, it, (z, gst, handle)
+            raise _lib.CimpcError(f"cimpc_plant_rollout_tape{sfx} failed ({rc})")
+        return (q, g, b, st, it, (z, gst, handle)) + more
     z = np.zeros((T, B, nz)); dz = np.zeros((T, B, n_cols, nq + nc + nb)); gst = np.zeros((T, B), dtype=np.int32)      # the library's blocks are column-major
-    rc = lib.cimpc_plant_rollout_grad(*args, reg, n_cols, dp(z), dp(dz), ip(gst))
+    rc = getattr(lib, "cimpc_plant_rollout_grad" + sfx)(*args, reg, n_cols, dp(z), dp(dz), ip(gst), *loop)
     if rc != 0:
-        raise _lib.CimpcError(f"cimpc_plant_rollout_grad failed ({rc})")
-    return q, g, b, st, it, StepGradients(np.ascontiguousarray(dz.transpose(0, 1, 3, 2)), z, gst, nq, nu, nc, nb)
+        raise _lib.CimpcError(f"cimpc_plant_rollout_grad{sfx} failed ({rc})")
+    return (q, g, b, st, it, StepGradients(np.ascontiguousarray(dz.transpose(0, 1, 3, 2)), z, gst, nq, nu, nc, nb)) + more
 
 
 def plant_step(model: str, q0, q1, u, mu: float, h: float, w=None, opts: InteriorPointOptions = SIM_OPTS, terrain=None,
@@ -339,7 +385,7 @@ def _rollout_inputs(model: str, q1, v1, u, mu, N_sample, w, w_hold, terrain, ste
 
 
 def rollout(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w_hold: int = 1, opts: InteriorPointOptions = SIM_OPTS,
-            terrain=None, steps=None, steps_per_launch: int = 0, diff_sol: bool = False, grad_reg=None, grad_cols=None):
+            terrain=None, steps=None, steps_per_launch: int = 0, diff_sol: bool = False, grad_reg=None, grad_cols=None, feedback=None):
     """`simulate!(sim, q1, v1)` under an `open_loop_policy(u; N_sample)` for B robots in ONE call (`cimpc_plant_rollout`): the states
     between the steps stay on the device, and every step is bit for bit the `plant_step` that `simulate` would make.  q1, v1 (B, nq) or
     (nq,); u (K, nu) nominal controls shared by every robot or (K, B, nu), each held for N_sample steps and applied as u[k] / N_sample
@@ -348,14 +394,19 @@ def rollout(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w
     (default K N_sample); steps_per_launch: steps per kernel launch (0: the library's default).  Returns (ok, q (steps + 2, B, nq),
     u_applied (steps, B, nu), gamma, b, status (steps, B), iters) with q[0] = q1 - h v1, q[1] = q1.  diff_sol=True
     (`cimpc_plant_rollout_grad`) returns one more element, the `StepGradients` of every step with leading axes (steps, B): one more
-    launch behind the rollout's differentiates all steps at their converged z; the other return values are bit for bit the same."""
+    launch behind the rollout's differentiates all steps at their converged z; the other return values are bit for bit the same.
+    feedback: a `Feedback` closes the loop on the device (`cimpc_plant_rollout_feedback`, `cimpc_plant_rollout_grad_feedback`): u is
+    then the open-loop part ū, the returned u_applied is what the device applied, u_t = ū_t + (K / N_sample) (x_ref − x_t), every step is
+    bit for bit the open-loop step on that control, the step gradients are taken with it in θ, and one more trailing element is fb_err
+    (steps, B, 2nq), the errors x_ref − x_t."""
     terrain, q1, v1, ua, u_applied, wa, mua = _rollout_inputs(model, q1, v1, u, mu, N_sample, w, w_hold, terrain, steps)
     T = u_applied.shape[0]
     q0 = np.ascontiguousarray(q1 - h * v1); q1 = np.ascontiguousarray(q1)
-    q, g, b, st, it, grads = _rollout_call(model, q0, q1, ua, N_sample, wa, w_hold, mua, h, opts, terrain, steps_per_launch, T,
-                                           _grad_args(model, opts, grad_reg, grad_cols) if diff_sol else None)
-    out = (bool(st.all()), q, u_applied, g, b, st, it)
-    return out + (grads,) if diff_sol else out
+    loop = None if feedback is None else _feedback_arrays(model, feedback, q1.shape[0], N_sample)[:4]
+    q, g, b, st, it, grads, *fb = _rollout_call(model, q0, q1, ua, N_sample, wa, w_hold, mua, h, opts, terrain, steps_per_launch, T,
+                                                _grad_args(model, opts, grad_reg, grad_cols) if diff_sol else None, feedback=loop)
+    out = (bool(st.all()), q, fb[0][0] if fb else u_applied, g, b, st, it)
+    return (out + (grads,) if diff_sol else out) + ((fb[0][1],) if fb else ())
 
 
 def fold_schedule(g_step, K: int, hold: int, shared: bool, scale: float = 1.0):
@@ -374,6 +425,23 @@ def fold_schedule(g_step, K: int, hold: int, shared: bool, scale: float = 1.0):
     return acc / scale
 
 
+def fold_gains(u_step, fb_err, K: int, hold: int, shared: bool, scale: float = 1.0):
+    """The gradient of the gain rows of a closed-loop rollout from its per-step control gradients u_step (T, B, nu) and errors fb_err
+    (T, B, 2nq): row min(t // hold, K - 1) takes u_step[t, b] ⊗ fb_err[t, b] of every step that read it (and of every robot when the
+    schedule is shared), added one at a time in ascending (t, b) order, then divided by `scale`.  Returns (K, nu, 2nq) or (K, B, nu, 2nq)."""
+    T, B, nu = u_step.shape
+    n2 = fb_err.shape[2]
+    acc = np.zeros((K, nu, n2) if shared else (K, B, nu, n2))
+    for t in range(T):
+        k = min(t // hold, K - 1)
+        for r in range(B):
+            if shared:
+                acc[k] += u_step[t, r][:, None] * fb_err[t, r][None, :]
+            else:
+                acc[k, r] += u_step[t, r][:, None] * fb_err[t, r][None, :]
+    return acc / scale
+
+
 @dataclasses.dataclass
 class RolloutCotangents:
     """What `RolloutTape.vjp` returns: the gradient of a loss on the trajectory with respect to the arguments of `rollout_tape`.
@@ -382,7 +450,9 @@ class RolloutCotangents:
     w_hold, undivided (None without a w, or when grad_cols stops short of its columns); mu (B,), or their sum over the robots when one
     friction coefficient was given (None: not covered); h = Σ_b (g_h[b] - v1[b]·λ[0][b]) (None: not covered); n_cut (B,): the steps of
     a robot whose gradient status is 0, through which nothing flows.  g_q0 = λ[0], g_q1 = λ[1] (B, nq), w_step (T, B, nw), g_mu, g_h (B,)
-    are the library's outputs as they came back (None: not covered)."""
+    are the library's outputs as they came back (None: not covered).  On a closed-loop tape u and u_step are the gradient of the
+    open-loop part ū, and K, x_ref, in the shapes of the caller's `Feedback`, are `fold_gains` of (u_step, fb_err) divided by N_sample and
+    `fold_schedule` of xref_step (T, B, 2nq), the library's g_xref_step; all three are None on an open-loop tape."""
     q1: np.ndarray
     v1: np.ndarray
     u: np.ndarray
@@ -396,6 +466,9 @@ class RolloutCotangents:
     w_step: object
     g_mu: object
     g_h: object
+    K: object = None
+    x_ref: object = None
+    xref_step: object = None
 
 
 class RolloutTape:
@@ -403,7 +476,8 @@ class RolloutTape:
     n_cols as recorded; grad_status (T, B) as `StepGradients.status`; z (T, B, nz) with keep_z, else None.  `close()` frees the device
     memory (so does leaving a `with` block, and the finalizer); a closed tape raises on use."""
 
-    def __init__(self, handle, model: str, grad_status, z, v1, h: float, u_shape, N_sample: int, w_shape, w_hold: int, mu_shared: bool):
+    def __init__(self, handle, model: str, grad_status, z, v1, h: float, u_shape, N_sample: int, w_shape, w_hold: int, mu_shared: bool,
+                 feedback=None):
         import weakref
         self._handle, self.model, self.grad_status, self.z = handle, model, grad_status, z
         dims = [C.c_int() for _ in range(4)]
@@ -413,6 +487,7 @@ class RolloutTape:
         mid, self.B, self.T, self.n_cols = (d.value for d in dims)
         assert mid == model_dims(model)[0]
         self._v1, self._h, self._u_shape, self._N_sample, self._w_shape, self._w_hold, self._mu_shared = v1, h, u_shape, N_sample, w_shape, w_hold, mu_shared
+        self._feedback = feedback      # None, or (fb_err (T, B, 2nq), K_f, hold, shared) of a closed-loop tape
         self._finalizer = weakref.finalize(self, _lib.load().cimpc_plant_tape_destroy, handle)
 
     closed = property(lambda self: not self._finalizer.alive)
@@ -451,8 +526,13 @@ class RolloutTape:
         g_mu = np.zeros(B) if self.n_cols >= c_mu + 1 else None
         g_h = np.zeros(B) if self.n_cols >= c_mu + 2 else None
         dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-        rc = _lib.load().cimpc_plant_tape_vjp(self._handle, dp(gq), dp(ggamma), dp(gb), dp(l0), dp(l1), dp(u_step), dp(w_step), dp(g_mu), dp(g_h),
-                                              n_cut.ctypes.data_as(C.POINTER(C.c_int)))
+        xref_step = None if self._feedback is None else np.zeros((T, B, 2 * nq))
+        if xref_step is None:
+            rc = _lib.load().cimpc_plant_tape_vjp(self._handle, dp(gq), dp(ggamma), dp(gb), dp(l0), dp(l1), dp(u_step), dp(w_step), dp(g_mu), dp(g_h),
+                                                  n_cut.ctypes.data_as(C.POINTER(C.c_int)))
+        else:
+            rc = _lib.load().cimpc_plant_tape_vjp_feedback(self._handle, dp(gq), dp(ggamma), dp(gb), dp(l0), dp(l1), dp(u_step), dp(w_step), dp(g_mu),
+                                                           dp(g_h), n_cut.ctypes.data_as(C.POINTER(C.c_int)), dp(xref_step))
         if rc != 0:
             raise _lib.CimpcError(f"cimpc_plant_tape_vjp failed ({rc})")
         u = fold_schedule(u_step, self._u_shape[0], self._N_sample, len(self._u_shape) == 2, self._N_sample)
@@ -469,40 +549,52 @@ class RolloutTape:
             h = 0.0
             for r in range(B):
                 h = h + (g_h[r] - float(self._v1[r] @ l0[r]))
+        gK = gx = None
+        if xref_step is not None:
+            fb_err, K_f, hold_f, shared = self._feedback
+            gK = fold_gains(u_step, fb_err, K_f, hold_f, shared, self._N_sample)
+            gx = fold_schedule(xref_step, K_f, hold_f, shared)
         return RolloutCotangents(q1=l0 + l1, v1=-self._h * l0, u=u, u_step=u_step, w=w, mu=mu, h=h, n_cut=n_cut, g_q0=l0, g_q1=l1, w_step=w_step,
-                                 g_mu=g_mu, g_h=g_h)
+                                 g_mu=g_mu, g_h=g_h, K=gK, x_ref=gx, xref_step=xref_step)
 
 
 def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w_hold: int = 1, opts: InteriorPointOptions = SIM_OPTS,
-                 terrain=None, steps=None, steps_per_launch: int = 0, grad_reg=None, grad_cols=None, keep_z: bool = False):
+                 terrain=None, steps=None, steps_per_launch: int = 0, grad_reg=None, grad_cols=None, keep_z: bool = False, feedback=None):
     """`rollout` that records its step gradients on the device instead of returning them (`cimpc_plant_rollout_tape`): the arguments of
     `rollout(..., diff_sol=True)` -> (ok, q, u_applied, gamma, b, status, iters, tape), the first seven bit for bit those of `rollout`,
     tape a `RolloutTape` whose `vjp` turns cotangents of (q, gamma, b) into the gradient with respect to q1, v1, u, w, mu and h.
     grad_cols (default 2 nq + nu, the least a tape takes) up to nθ adds the w, μ and h columns; keep_z also returns every step's z on
-    the tape."""
+    the tape.  feedback: a `Feedback`, as in `rollout` (`cimpc_plant_rollout_tape_feedback`): u_applied is the device's, one more trailing
+    element is fb_err, and the tape's `vjp` runs the closed-loop chain, whose `RolloutCotangents` carry K, x_ref and xref_step."""
     terrain, q1, v1, ua, u_applied, wa, mua = _rollout_inputs(model, q1, v1, u, mu, N_sample, w, w_hold, terrain, steps)
     (T, B), (mid, nq, nu, nc, fd, nw) = u_applied.shape[:2], model_dims(model)
     reg, n_cols = _grad_args(model, opts, grad_reg, grad_cols)
     if n_cols < 2 * nq + nu:
         raise ValueError(f"grad_cols must be at least {2 * nq + nu} (q0, q1 and u1) for a tape")
     q0 = np.ascontiguousarray(q1 - h * v1); q1 = np.ascontiguousarray(q1)
-    q, g, b, st, it, (z, gst, handle) = _rollout_call(model, q0, q1, ua, N_sample, wa, w_hold, mua, h, opts, terrain, steps_per_launch, T,
-                                                      (reg, n_cols), tape=bool(keep_z))
+    loop = None if feedback is None else _feedback_arrays(model, feedback, B, N_sample)
+    q, g, b, st, it, (z, gst, handle), *fb = _rollout_call(model, q0, q1, ua, N_sample, wa, w_hold, mua, h, opts, terrain, steps_per_launch, T,
+                                                           (reg, n_cols), tape=bool(keep_z), feedback=None if loop is None else loop[:4])
     tape = RolloutTape(handle, model, gst, z, v1.copy(), float(h), np.shape(u), int(N_sample), None if w is None else np.shape(w), int(w_hold),
-                       np.ndim(mu) == 0 or (mua.size == 1 and B > 1))
-    return bool(st.all()), q, u_applied, g, b, st, it, tape
+                       np.ndim(mu) == 0 or (mua.size == 1 and B > 1),
+                       feedback=None if loop is None else (fb[0][1], loop[0].shape[0], loop[2], loop[4]))
+    if loop is None:
+        return bool(st.all()), q, u_applied, g, b, st, it, tape
+    return bool(st.all()), q, fb[0][0], g, b, st, it, tape, fb[0][1]
 
 
-def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, **kw):
+def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, feedback=None, **kw):
     """`rollout_tape` inside `torch.autograd`: q1, v1, u, mu and w may be float64 tensors (on any device; they are staged through the
     host, as every plant entry point stages its arguments), the keywords are those of `rollout_tape` -> (q, gamma, b, status) tensors on
     the device of the first tensor given, status an int tensor without a gradient.  `backward` runs `RolloutTape.vjp` on the tape,
     which lives on the autograd graph - any number of times with retain_graph=True - and gradients reach whichever of q1, v1, u, w, mu
-    require them; grad_cols is raised to cover w and mu when they do."""
+    require them; grad_cols is raised to cover w and mu when they do.  feedback: a `Feedback` whose K and x_ref may be tensors too; with
+    it the rollout is closed-loop, and gradients also reach K and x_ref when they require them."""
     import torch
 
     mid, nq, nu, nc, fd, nw = model_dims(model)
-    tensors = [a for a in (q1, v1, u, mu, w) if isinstance(a, torch.Tensor)]
+    fK, fx = (None, None) if feedback is None else (feedback.K, feedback.x_ref)
+    tensors = [a for a in (q1, v1, u, mu, w, fK, fx) if isinstance(a, torch.Tensor)]
     device = tensors[0].device if tensors else torch.device("cpu")
     needs = lambda a: isinstance(a, torch.Tensor) and a.requires_grad
     cols = 2 * nq + nu + (nw + 1 if needs(mu) else nw if needs(w) else 0)
@@ -511,8 +603,9 @@ def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, **kw):
 
     class _Rollout(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, q1_, v1_, u_, mu_, w_):
-            ok, q, ua, g, b, st, it, tape = rollout_tape(model, host(q1_), host(v1_), host(u_), h, host(mu_), w=host(w_), **kw)
+        def forward(ctx, q1_, v1_, u_, mu_, w_, K_, x_):
+            fb = None if feedback is None else dataclasses.replace(feedback, K=host(K_), x_ref=host(x_))
+            ok, q, ua, g, b, st, it, tape, *_ = rollout_tape(model, host(q1_), host(v1_), host(u_), h, host(mu_), w=host(w_), feedback=fb, **kw)
             ctx.tape = tape
             ctx.set_materialize_grads(False)
             status = torch.as_tensor(st, device=device)
@@ -522,17 +615,17 @@ def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, **kw):
         @staticmethod
         def backward(ctx, gq, ggamma, gb, gstatus):
             if gq is None and ggamma is None and gb is None:
-                return None, None, None, None, None
+                return None, None, None, None, None, None, None
             c = ctx.tape.vjp(host(gq), host(ggamma), host(gb))
             out = []
-            for k, (a, grad) in enumerate(zip((q1, v1, u, mu, w), (c.q1, c.v1, c.u, c.mu, c.w))):
+            for k, (a, grad) in enumerate(zip((q1, v1, u, mu, w, fK, fx), (c.q1, c.v1, c.u, c.mu, c.w, c.K, c.x_ref))):
                 if not ctx.needs_input_grad[k]:
                     out.append(None)
                 else:
                     out.append(torch.as_tensor(np.asarray(grad, dtype=np.float64), device=a.device).reshape(a.shape))
             return tuple(out)
 
-    return _Rollout.apply(q1, v1, u, mu, w)
+    return _Rollout.apply(q1, v1, u, mu, w, fK, fx)
 
 
 def linearize(model: str, z, theta, kappa: float, terrain=None):

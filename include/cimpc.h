@@ -518,6 +518,66 @@ int cimpc_plant_tape_dims(cimpc_plant_tape tape, int* model, int* B, int* T, int
 /* Frees the tape's device memory and the tape.  NULL is a no-op (CIMPC_OK). */
 int cimpc_plant_tape_destroy(cimpc_plant_tape tape);
 
+/* ---- closed-loop rollouts under linear state feedback, with gradients ------------------------------------------------------------------
+ * THIS BUILD'S definition (csrc/plant_feedback.h).  A feedback schedule has K_f rows, every row held for
+ * hold_f steps and the last from there on: K, K_f x n_f x (nu x 2nq), each block column-major - one knot of cimpc_reference_gains'
+ * output, which can be passed unchanged -, and x_ref, K_f x n_f x 2nq, with n_f = 1 (shared by every robot) or B.  Step t of a robot
+ * uses row k = min(t / hold_f, K_f - 1), q0 = q[t], q1 = q[t+1] and ubar_t, the open-loop row of u as it stands:
+ *     x[j] = j < nq ? q1[j] - n_sample (q1[j] - q0[j]) : q1[j - nq]      (cimpc_gain_feedback's expression, also for n_sample = 1)
+ *     e[j] = x_ref[k][j] - x[j];   s[i] = sum over j = 0 .. 2nq-1 of K[k][i, j] e[j]   (ascending j from 0.0, no fused multiply-add)
+ *     u_t[i] = ubar_t[i] + s[i]
+ * and is otherwise exactly the open-loop step on u_t (bit-identical to cimpc_plant_rollout on u_applied as a per-robot schedule).  The
+ * device divides nothing by N_sample: the host passes K / N_sample beside u / N_sample.  Outputs beside the rollout's: u_applied
+ * T x B x nu (u_t) and fb_err T x B x 2nq (e).  The reverse chain of such a rollout adds, after v = D_t' a of step t, gu = v[2nq : 2nq+nu]:
+ *     gx[j] = sum over i = 0 .. nu-1 of K[k][i, j] gu[i]   (ascending i from 0.0);   g_xref_step[t] = gx
+ *     lambda[t][i] -= n_sample gx[i];   lambda[t+1][i] = (lambda[t+1][i] - (1 - n_sample) gx[i]) - gx[nq + i]      (i < nq)
+ * g_u_step stays gu, the gradient of ubar_t; the gradient of K row k is the sum of gu[t, b] (x) fb_err[t, b] over the steps and robots
+ * that read it, formed by the caller.
+ *
+ * The three rollout entries take the parameters of their open-loop namesakes, then fb, u_applied, fb_err.  Validated first, without a
+ * device (CIMPC_ERR_INVALID): everything the base call validates; a null fb, K, x_ref, u_applied or fb_err; K_f < 1 or hold_f < 1; n_f
+ * outside {1, B}; n_sample not finite or not positive; any non-finite entry of K or x_ref.  A closed-loop tape also owns a device copy
+ * of the K rows and the schedule's (K_f, n_f, hold_f, n_sample). */
+typedef struct cimpc_feedback {
+    const double* K;
+    const double* x_ref;
+    int K_f, n_f, hold_f;
+    double n_sample;
+} cimpc_feedback;
+int cimpc_plant_rollout_feedback(int model, int B, int T, int steps_per_launch,
+                                 int n_terrain, const cimpc_terrain* terrain,
+                                 const double* q0, const double* q1,
+                                 const double* u, int K_u, int n_u, int hold_u,
+                                 const double* w, int K_w, int n_w, int hold_w,
+                                 const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                                 double* q, double* gamma, double* b, int* status, int* iters,
+                                 const cimpc_feedback* fb, double* u_applied, double* fb_err);
+/* dz: the blocks of cimpc_plant_sensitivity on (z[t, b], theta[t, b]) with theta's controls from u_applied, bit for bit. */
+int cimpc_plant_rollout_grad_feedback(int model, int B, int T, int steps_per_launch,
+                                      int n_terrain, const cimpc_terrain* terrain,
+                                      const double* q0, const double* q1,
+                                      const double* u, int K_u, int n_u, int hold_u,
+                                      const double* w, int K_w, int n_w, int hold_w,
+                                      const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                                      double* q, double* gamma, double* b, int* status, int* iters,
+                                      double reg, int n_cols, double* z, double* dz, int* grad_status,
+                                      const cimpc_feedback* fb, double* u_applied, double* fb_err);
+int cimpc_plant_rollout_tape_feedback(int model, int B, int T, int steps_per_launch,
+                                      int n_terrain, const cimpc_terrain* terrain,
+                                      const double* q0, const double* q1,
+                                      const double* u, int K_u, int n_u, int hold_u,
+                                      const double* w, int K_w, int n_w, int hold_w,
+                                      const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                                      double* q, double* gamma, double* b, int* status, int* iters,
+                                      double reg, int n_cols, double* z, int* grad_status, cimpc_plant_tape* tape,
+                                      const cimpc_feedback* fb, double* u_applied, double* fb_err);
+/* cimpc_plant_tape_vjp's arguments, then g_xref_step (T x B x 2nq, may be NULL).  The chain of a closed-loop tape always includes the
+ * feedback path: cimpc_plant_tape_vjp on such a tape is this call with NULL.  A non-NULL g_xref_step on an open-loop tape:
+ * CIMPC_ERR_INVALID. */
+int cimpc_plant_tape_vjp_feedback(cimpc_plant_tape tape, const double* gq, const double* ggamma, const double* gb,
+                                  double* g_q0, double* g_q1, double* g_u_step, double* g_w_step, double* g_mu, double* g_h, int* n_cut,
+                                  double* g_xref_step);
+
 /* ---- cimpc_set_linearization_batch from (z, theta) alone: plant model `model` linearized at kappa (cimpc_plant_linearize's kernel and arguments;
  * z0 = z, th0 = theta) and the tables built from its output, all on the handle's device and stream;
  * nothing but z, theta and the terrains goes up, nothing but N status words comes back.  Equal bit for bit to

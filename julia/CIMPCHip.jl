@@ -659,6 +659,153 @@ function plant_tape_vjp(tape::PlantTape; gq::Union{Nothing,Array{Float64,3}} = n
     return g_q0, g_q1, g_u, g_w, g_μ, g_h, n_cut
 end
 
+# ---- closed-loop rollouts under linear state feedback (cimpc.h: cimpc_feedback; DESIGN.md section 3, item 3c) --------------------------
+# Unexecuted, like the rest of this binding (INTEGRATION.md).
+"""
+`cimpc_feedback`: the pointers and sizes of a feedback schedule as the library reads them.  Built by the closed-loop calls from
+`K` (nu x 2nq x K_f shared, or nu x 2nq x B x K_f: a column-major block per row, `reference_gains`' layout) and `x_ref` (2nq x K_f or
+2nq x B x K_f).
+"""
+struct Feedback
+    K::Ptr{Cdouble}
+    x_ref::Ptr{Cdouble}
+    K_f::Cint; n_f::Cint; hold_f::Cint
+    n_sample::Cdouble
+end
+
+# the inputs the closed-loop rollouts share, checked and laid out: the open-loop ones and the schedule's arrays
+function _closed_loop_inputs(what, model, q1, v1, u, μ, w, terrain, steps, N_sample, w_hold, K, x_ref, hold, n_sample)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    B = size(q1, 2)
+    (size(q1, 1) == nq && size(v1) == (nq, B)) || error("$what($model): q1, v1 must be $nq x B")
+    us = ndims(u) == 2 ? reshape(u, nu, 1, :) : u
+    (ndims(us) == 3 && size(us, 1) == nu && size(us, 2) in (1, B) && size(us, 3) >= 1) || error("$what($model): u must be $nu x K or $nu x B x K")
+    ws = w === nothing ? nothing : ndims(w) == 2 ? reshape(w, nw, 1, :) : w
+    (ws === nothing || (ndims(ws) == 3 && size(ws, 1) == nw && size(ws, 2) in (1, B) && size(ws, 3) >= 1)) || error("$what($model): w must be $nw x K_w or $nw x B x K_w")
+    μs = Float64.(vcat(μ))
+    length(μs) in (1, B) || error("$what($model): one friction coefficient or one per robot")
+    (terrain === nothing || length(terrain) in (1, B)) || error("$what($model): one terrain or one per robot")
+    (steps >= 1 && N_sample >= 1 && w_hold >= 1 && hold >= 1) || error("$what($model): steps, N_sample, w_hold, hold must be at least 1")
+    Ks = ndims(K) == 3 ? reshape(K, nu, 2 * nq, 1, :) : K
+    xs = ndims(x_ref) == 2 ? reshape(x_ref, 2 * nq, 1, :) : x_ref
+    (ndims(Ks) == 4 && size(Ks)[1:2] == (nu, 2 * nq) && size(Ks, 3) in (1, B) && size(Ks, 4) >= 1 && size(xs) == (2 * nq, size(Ks, 3), size(Ks, 4))) ||
+        error("$what($model): K must be $nu x $(2 * nq) x K_f or $nu x $(2 * nq) x B x K_f beside x_ref $(2 * nq) x K_f or $(2 * nq) x B x K_f")
+    ns = n_sample === nothing ? Float64(N_sample) : Float64(n_sample)
+    (isfinite(ns) && ns > 0) || error("$what($model): n_sample must be finite and positive")
+    return us ./ N_sample, ws, μs, Array(Ks ./ N_sample), Array(Float64.(xs)), ns
+end
+
+"""
+    plant_rollout_feedback(model, q1, v1, u, μ, h_sim, opts, K, x_ref; hold = 1, n_sample = N_sample, N_sample = 1, w = nothing,
+                           w_hold = 1, terrain = nothing, steps = K N_sample, steps_per_launch = 0)
+        -> (ok, q, u_applied, γ, b, status, iters, fb_err)
+
+`plant_rollout` under u_t = ū_t + (K[k] / N_sample) (x_ref[k] - x_t), k = min(t ÷ hold, K_f - 1), in one call: u_applied nu x B x steps is
+what the device applied, fb_err 2nq x B x steps the errors x_ref - x_t.
+"""
+function plant_rollout_feedback(model::Symbol, q1::Matrix{Float64}, v1::Matrix{Float64}, u::Array{Float64}, μ, h_sim, opts,
+                                K::Array{Float64}, x_ref::Array{Float64}; hold::Int = 1, n_sample = nothing,
+                                N_sample::Int = 1, w::Union{Nothing,Array{Float64}} = nothing, w_hold::Int = 1,
+                                terrain::Union{Nothing,Vector{Terrain}} = nothing, steps::Int = size(u, ndims(u)) * N_sample,
+                                steps_per_launch::Int = 0)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    B = size(q1, 2)
+    ua, ws, μs, Ks, xs, ns = _closed_loop_inputs("plant_rollout_feedback", model, q1, v1, u, μ, w, terrain, steps, N_sample, w_hold, K, x_ref, hold, n_sample)
+    q0 = q1 .- h_sim .* v1
+    q = zeros(nq, B, steps + 2); γ = zeros(nc, B, steps); b = zeros(nf * nc, B, steps)
+    status = zeros(Cint, B, steps); iters = zeros(Cint, B, steps)
+    u_applied = zeros(nu, B, steps); fb_err = zeros(2 * nq, B, steps)
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    K_u, n_u = size(ua, 3), size(ua, 2)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu = length(μs)
+    GC.@preserve Ks xs begin
+        fb = Ref(Feedback(pointer(Ks), pointer(xs), size(Ks, 4), size(Ks, 3), hold, ns))
+        check(@ccall LIB.cimpc_plant_rollout_feedback(id::Cint, B::Cint, steps::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                                      q0::Ptr{Cdouble}, q1::Ptr{Cdouble}, ua::Ptr{Cdouble}, K_u::Cint, n_u::Cint, N_sample::Cint,
+                                                      wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint, μs::Ptr{Cdouble}, n_mu::Cint,
+                                                      h_sim::Cdouble, o::Ref{IpOpts}, q::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble},
+                                                      status::Ptr{Cint}, iters::Ptr{Cint}, fb::Ref{Feedback}, u_applied::Ptr{Cdouble},
+                                                      fb_err::Ptr{Cdouble})::Cint)
+    end
+    return all(status .== 1), q, u_applied, γ, b, status, iters, fb_err
+end
+
+"""
+    plant_rollout_tape_feedback(model, q1, v1, u, μ, h_sim, opts, K, x_ref; hold = 1, n_sample = N_sample, ..., grad_reg = nothing,
+                                grad_cols = nothing) -> (ok, q, u_applied, γ, b, status, iters, tape, fb_err)
+
+`plant_rollout_feedback` that records its step gradients on the device: `tape` a `PlantTape` whose chain (`plant_tape_vjp`,
+`plant_tape_vjp_feedback`) includes the feedback path.  The gradient of K row k is the sum of g_u_step[:, b, t] fb_err[:, b, t]' over
+the steps and robots that read it, divided by N_sample.
+"""
+function plant_rollout_tape_feedback(model::Symbol, q1::Matrix{Float64}, v1::Matrix{Float64}, u::Array{Float64}, μ, h_sim, opts,
+                                     K::Array{Float64}, x_ref::Array{Float64}; hold::Int = 1, n_sample = nothing,
+                                     N_sample::Int = 1, w::Union{Nothing,Array{Float64}} = nothing, w_hold::Int = 1,
+                                     terrain::Union{Nothing,Vector{Terrain}} = nothing, steps::Int = size(u, ndims(u)) * N_sample,
+                                     steps_per_launch::Int = 0, grad_reg = nothing, grad_cols = nothing)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    B = size(q1, 2)
+    ua, ws, μs, Ks, xs, ns = _closed_loop_inputs("plant_rollout_tape_feedback", model, q1, v1, u, μ, w, terrain, steps, N_sample, w_hold, K, x_ref, hold, n_sample)
+    q0 = q1 .- h_sim .* v1
+    q = zeros(nq, B, steps + 2); γ = zeros(nc, B, steps); b = zeros(nf * nc, B, steps)
+    status = zeros(Cint, B, steps); iters = zeros(Cint, B, steps); grad_status = zeros(Cint, B, steps)
+    u_applied = zeros(nu, B, steps); fb_err = zeros(2 * nq, B, steps)
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    K_u, n_u = size(ua, 3), size(ua, 2)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu = length(μs)
+    nθ = 2 * nq + nu + nw + 2
+    reg = grad_reg === nothing ? o[].kappa_tol * o[].gamma_reg : Float64(grad_reg)
+    n_cols = grad_cols === nothing ? 2 * nq + nu : Int(grad_cols)
+    (2 * nq + nu <= n_cols <= nθ && reg >= 0) || error("plant_rollout_tape_feedback($model): grad_cols must be in $(2 * nq + nu) .. $nθ and grad_reg >= 0")
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    z = C_NULL
+    GC.@preserve Ks xs begin
+        fb = Ref(Feedback(pointer(Ks), pointer(xs), size(Ks, 4), size(Ks, 3), hold, ns))
+        check(@ccall LIB.cimpc_plant_rollout_tape_feedback(id::Cint, B::Cint, steps::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                                           q0::Ptr{Cdouble}, q1::Ptr{Cdouble}, ua::Ptr{Cdouble}, K_u::Cint, n_u::Cint, N_sample::Cint,
+                                                           wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint, μs::Ptr{Cdouble}, n_mu::Cint,
+                                                           h_sim::Cdouble, o::Ref{IpOpts}, q::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble},
+                                                           status::Ptr{Cint}, iters::Ptr{Cint}, reg::Cdouble, n_cols::Cint, z::Ptr{Cdouble},
+                                                           grad_status::Ptr{Cint}, handle::Ref{Ptr{Cvoid}}, fb::Ref{Feedback},
+                                                           u_applied::Ptr{Cdouble}, fb_err::Ptr{Cdouble})::Cint)
+    end
+    return all(status .== 1), q, u_applied, γ, b, status, iters, PlantTape(handle[], model, B, steps, n_cols, grad_status), fb_err
+end
+
+"""
+    plant_tape_vjp_feedback(tape; gq = nothing, ggamma = nothing, gb = nothing) -> (g_q0, g_q1, g_u_step, g_w_step, g_μ, g_h, n_cut, g_xref_step)
+
+`plant_tape_vjp` on the tape of a closed-loop rollout, with g_xref_step 2nq x B x T, the gradient with respect to the reference state
+each step read (an open-loop tape is refused by the library).  g_u_step is the gradient of the open-loop part ū.
+"""
+function plant_tape_vjp_feedback(tape::PlantTape; gq::Union{Nothing,Array{Float64,3}} = nothing, ggamma::Union{Nothing,Array{Float64,3}} = nothing,
+                                 gb::Union{Nothing,Array{Float64,3}} = nothing)
+    tape.handle != C_NULL || error("plant_tape_vjp_feedback: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, nb = tape.B, tape.T, nf * nc
+    (gq === nothing && ggamma === nothing && gb === nothing) && error("plant_tape_vjp_feedback: at least one of gq, ggamma, gb")
+    (gq === nothing || size(gq) == (nq, B, T + 2)) || error("plant_tape_vjp_feedback: gq must be $nq x $B x $(T + 2)")
+    (ggamma === nothing || size(ggamma) == (nc, B, T)) || error("plant_tape_vjp_feedback: ggamma must be $nc x $B x $T")
+    (gb === nothing || size(gb) == (nb, B, T)) || error("plant_tape_vjp_feedback: gb must be $nb x $B x $T")
+    c_mu = 2 * nq + nu + nw
+    g_q0 = zeros(nq, B); g_q1 = zeros(nq, B); g_u = zeros(nu, B, T); n_cut = zeros(Cint, B); g_x = zeros(2 * nq, B, T)
+    g_w = tape.n_cols >= c_mu ? zeros(nw, B, T) : nothing
+    g_μ = tape.n_cols >= c_mu + 1 ? zeros(B) : nothing
+    g_h = tape.n_cols >= c_mu + 2 ? zeros(B) : nothing
+    p(a) = a === nothing ? C_NULL : pointer(a)
+    GC.@preserve gq ggamma gb g_w g_μ g_h begin
+        pq, pg, pb, pw, pm, ph = p(gq), p(ggamma), p(gb), p(g_w), p(g_μ), p(g_h)
+        check(@ccall LIB.cimpc_plant_tape_vjp_feedback(tape.handle::Ptr{Cvoid}, pq::Ptr{Cdouble}, pg::Ptr{Cdouble}, pb::Ptr{Cdouble},
+                                                       g_q0::Ptr{Cdouble}, g_q1::Ptr{Cdouble}, g_u::Ptr{Cdouble}, pw::Ptr{Cdouble},
+                                                       pm::Ptr{Cdouble}, ph::Ptr{Cdouble}, n_cut::Ptr{Cint}, g_x::Ptr{Cdouble})::Cint)
+    end
+    return g_q0, g_q1, g_u, g_w, g_μ, g_h, n_cut, g_x
+end
+
 # ---- the plant models linearized on the device: the `LinearizedStep` triple of N knots in one call (linearized_step.jl:10-31) --------
 """
     plant_linearize(model, z, θ, κ; terrain = nothing) -> (r0, rz0, rθ0)
