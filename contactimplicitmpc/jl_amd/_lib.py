@@ -67,7 +67,7 @@ class Feedback(C.Structure):
     _fields_ = [("K", _dp), ("x_ref", _dp), ("K_f", C.c_int), ("n_f", C.c_int), ("hold_f", C.c_int), ("n_sample", C.c_double)]
 
 
-# the 25 parameters of cimpc_plant_rollout, which the closed-loop entry points extend
+# the 25 parameters of cimpc_plant_rollout, which the gradient, tape and closed-loop entry points extend
 _ROLLOUT_ARGS = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
                  _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip]
 
@@ -106,16 +106,11 @@ SIGNATURES = {
                                    _dp, _dp, _dp, _ip, _ip]),
     "cimpc_plant_step_terrain": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, _dp, C.c_double, C.c_double,
                                            C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip]),
-    "cimpc_plant_rollout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
-                                      _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip]),
+    "cimpc_plant_rollout": (C.c_int, _ROLLOUT_ARGS),
     "cimpc_plant_linearize": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, C.c_double, _dp, _dp, _dp]),
     "cimpc_plant_sensitivity": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, C.c_double, C.c_int, _dp, _ip]),
-    "cimpc_plant_rollout_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
-                                           _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip,
-                                           C.c_double, C.c_int, _dp, _dp, _ip]),
-    "cimpc_plant_rollout_tape": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
-                                           _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip,
-                                           C.c_double, C.c_int, _dp, _ip, C.POINTER(_h)]),
+    "cimpc_plant_rollout_grad": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _dp, _ip]),
+    "cimpc_plant_rollout_tape": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _ip, C.POINTER(_h)]),
     "cimpc_plant_tape_vjp": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "cimpc_plant_rollout_feedback": (C.c_int, _ROLLOUT_ARGS + [C.POINTER(Feedback), _dp, _dp]),
     "cimpc_plant_rollout_grad_feedback": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _dp, _ip, C.POINTER(Feedback), _dp, _dp]),

@@ -29,11 +29,8 @@
 #include "plant_workspace.h"
 
 struct cimpc_plant_tape_s {
-    int device, model, B, T, n_cols;
-    cimpc::PlantModel M;
-    double* d_dz;      // T x B x (nr x n_cols)
-    int* d_status;     // T x B
-    cimpc::PlantFeedback fb;      // a closed-loop tape: fb.K the tape's device copy of the gain rows (x_ref is not needed); else fb.K null
+    cimpc::PlantTapeBuffers buf;      // the device memory, its device and model; buf.d_fb_K non-null: a closed-loop tape
+    int model, B, T, n_cols;
 };
 
 namespace cimpc {
@@ -77,22 +74,14 @@ __global__ __launch_bounds__(ADJ_THREADS) void plant_adjoint_kernel(PlantAdjoint
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------
 namespace {
-int rollout_tape_impl(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain, const double* q0,
-                      const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w, int K_w, int n_w, int hold_w,
-                      const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status,
-                      int* iters, double reg, int n_cols, double* z, int* grad_status, cimpc_plant_tape* tape, bool closed_loop,
-                      const cimpc_feedback* fb, double* u_applied, double* fb_err) {
-    using namespace cimpc;
+// A rollout whose call asks for a tape (call.grad->tape): *tape is the new tape, or null when the call is refused or fails.
+int rollout_tape_impl(const cimpc::PlantRolloutCall& call, cimpc_plant_tape* tape) {
     if (!tape) return CIMPC_ERR_INVALID;
     *tape = nullptr;
-    if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
-    PlantTapeBuffers buf;
-    const int rc = plant_rollout_to_tape(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu,
-                                         n_mu, h, opts, q, gamma, b, status, iters, reg, n_cols, z, grad_status, &buf, closed_loop, fb,
-                                         u_applied, fb_err);
+    cimpc::PlantTapeBuffers buf;
+    const int rc = cimpc::plant_rollout_to_tape(call, &buf);
     if (rc != CIMPC_OK) return rc;
-    *tape = new cimpc_plant_tape_s{buf.device, model, B, T, n_cols, buf.M, buf.d_dz, buf.d_status,
-                                   PlantFeedback{buf.d_fb_K, nullptr, buf.K_f, buf.n_f, buf.hold_f, buf.n_sample}};
+    *tape = new cimpc_plant_tape_s{buf, call.model, call.B, call.T, call.grad->n_cols};
     return CIMPC_OK;
 }
 }  // namespace
@@ -103,8 +92,8 @@ extern "C" int cimpc_plant_rollout_tape_feedback(int model, int B, int T, int st
                                                  const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status, int* iters,
                                                  double reg, int n_cols, double* z, int* grad_status, cimpc_plant_tape* tape,
                                                  const cimpc_feedback* fb, double* u_applied, double* fb_err) {
-    return rollout_tape_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu, h,
-                             opts, q, gamma, b, status, iters, reg, n_cols, z, grad_status, tape, true, fb, u_applied, fb_err);
+    return rollout_tape_impl({PLANT_ROLLOUT_CALL_BASE, .grad = cimpc::PlantRolloutGrad{reg, n_cols, z, nullptr, grad_status, true},
+                              .loop = cimpc::PlantRolloutLoop{fb, u_applied, fb_err}}, tape);
 }
 
 extern "C" int cimpc_plant_rollout_tape(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
@@ -112,8 +101,7 @@ extern "C" int cimpc_plant_rollout_tape(int model, int B, int T, int steps_per_l
                                         int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
                                         double* q, double* gamma, double* b, int* status, int* iters, double reg, int n_cols, double* z,
                                         int* grad_status, cimpc_plant_tape* tape) {
-    return rollout_tape_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu, h,
-                             opts, q, gamma, b, status, iters, reg, n_cols, z, grad_status, tape, false, nullptr, nullptr, nullptr);
+    return rollout_tape_impl({PLANT_ROLLOUT_CALL_BASE, .grad = cimpc::PlantRolloutGrad{reg, n_cols, z, nullptr, grad_status, true}}, tape);
 }
 
 extern "C" int cimpc_plant_tape_dims(cimpc_plant_tape tape, int* model, int* B, int* T, int* n_cols) {
@@ -132,12 +120,11 @@ extern "C" int cimpc_plant_tape_destroy(cimpc_plant_tape tape) {
     {
         std::lock_guard<std::mutex> lock(g_plant_mu);      // no call is walking the tape
         int cur = -1;
-        ok = hipGetDevice(&cur) == hipSuccess && (cur == tape->device || hipSetDevice(tape->device) == hipSuccess);
+        const int dev = tape->buf.device;
+        ok = hipGetDevice(&cur) == hipSuccess && (cur == dev || hipSetDevice(dev) == hipSuccess);
         if (ok) {
-            ok = hipFree(tape->d_dz) == hipSuccess;
-            ok = (hipFree(tape->d_status) == hipSuccess) && ok;
-            if (tape->fb.K) ok = (hipFree(const_cast<double*>(tape->fb.K)) == hipSuccess) && ok;
-            if (cur != tape->device) ok = (hipSetDevice(cur) == hipSuccess) && ok;
+            ok = tape->buf.release();
+            if (cur != dev) ok = (hipSetDevice(cur) == hipSuccess) && ok;
         }
     }
     delete tape;
@@ -152,14 +139,16 @@ extern "C" int cimpc_plant_tape_vjp_feedback(cimpc_plant_tape tape, const double
                                     double* g_xref_step) {
     using namespace cimpc;
     if (!tape || (!gq && !ggamma && !gb) || !g_q0 || !g_q1 || !g_u_step || !n_cut) return CIMPC_ERR_INVALID;
-    if (g_xref_step && !tape->fb.K) return CIMPC_ERR_INVALID;
-    const PlantModel& M = tape->M;
+    const PlantTapeBuffers& buf = tape->buf;
+    const PlantFeedback fb{buf.d_fb_K, nullptr, buf.K_f, buf.n_f, buf.hold_f, buf.n_sample};      // the chain does not need x_ref
+    if (g_xref_step && !fb.K) return CIMPC_ERR_INVALID;
+    const PlantModel& M = buf.M;
     const int B = tape->B, T = tape->T, n_cols = tape->n_cols;
     const size_t nq = M.nq, nu = M.nu, nw = M.nw, nc = M.nc, nb = M.nb(), TB = (size_t)T * B;
     const size_t c_mu = 2 * nq + nu + nw;                              // the columns of theta = [q0; q1; u1; w1; mu; h]
     if ((g_w_step && (size_t)n_cols < c_mu) || (g_mu && (size_t)n_cols < c_mu + 1) || (g_h && (size_t)n_cols < c_mu + 2)) return CIMPC_ERR_INVALID;
     const int nr = (int)(nq + nc + nb);
-    const size_t lds = (plant_adjoint_work_doubles(nr, n_cols, (int)nq) + (tape->fb.K ? plant_adjoint_feedback_doubles((int)nu, (int)nq) : 0)) * sizeof(double);
+    const size_t lds = (plant_adjoint_work_doubles(nr, n_cols, (int)nq) + (fb.K ? plant_adjoint_feedback_doubles((int)nu, (int)nq) : 0)) * sizeof(double);
     if (!plant_adjoint_fits(nr, n_cols, (int)nq) || lds > PLANT_ADJ_MAX_LDS) return CIMPC_ERR_INVALID;
     const size_t n_x = g_xref_step ? TB * 2 * nq : 0;
     // the staging buffers: cotangents in, gradients out, in the order of the argument list
@@ -168,9 +157,9 @@ extern "C" int cimpc_plant_tape_vjp_feedback(cimpc_plant_tape tape, const double
     std::lock_guard<std::mutex> lock(g_plant_mu);
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
-    if (cur != tape->device && hipSetDevice(tape->device) != hipSuccess) return CIMPC_ERR_HIP;
+    if (cur != buf.device && hipSetDevice(buf.device) != hipSuccess) return CIMPC_ERR_HIP;
     bool ok = false;
-    PlantWs* ws = plant_ws_open(tape->device);
+    PlantWs* ws = plant_ws_open(buf.device);
     if (ws && plant_grow(&ws->d_adj_in, &ws->cap_adj_in, n_gq + n_gg + n_gb) && plant_grow(&ws->d_adj_out, &ws->cap_adj_out, 2 * n_q + n_u + n_w + n_m + n_h) &&
         plant_grow(&ws->d_adj_cut, &ws->cap_adj_cut, (size_t)B) && (!n_x || plant_grow(&ws->d_adj_xref, &ws->cap_adj_xref, n_x))) {
         hipStream_t st = ws->st;
@@ -182,11 +171,11 @@ extern "C" int cimpc_plant_tape_vjp_feedback(cimpc_plant_tape tape, const double
         if (ok && ggamma) ok = hipMemcpyAsync(d_gg, ggamma, n_gg * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
         if (ok && gb) ok = hipMemcpyAsync(d_gb, gb, n_gb * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
         if (ok) {
-            PlantAdjoint P{tape->d_dz, tape->d_status, gq ? d_gq : nullptr, ggamma ? d_gg : nullptr, gb ? d_gb : nullptr, d_q0, d_q1, d_u,
+            PlantAdjoint P{buf.d_dz, buf.d_status, gq ? d_gq : nullptr, ggamma ? d_gg : nullptr, gb ? d_gb : nullptr, d_q0, d_q1, d_u,
                                  g_w_step ? d_w : nullptr, g_mu ? d_m : nullptr, g_h ? d_h : nullptr, ws->d_adj_cut, B, T, (int)nq, (int)nu,
                                  (int)nw, (int)nc, (int)nb, n_cols};
-            if (tape->fb.K) { P.fb = tape->fb; P.g_xref_step = g_xref_step ? ws->d_adj_xref : nullptr; }
-            auto kernel = tape->fb.K ? plant_adjoint_kernel<true> : plant_adjoint_kernel<false>;
+            if (fb.K) { P.fb = fb; P.g_xref_step = g_xref_step ? ws->d_adj_xref : nullptr; }
+            auto kernel = fb.K ? plant_adjoint_kernel<true> : plant_adjoint_kernel<false>;
             ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
             if (ok) {
                 hipLaunchKernelGGL(kernel, dim3(B), dim3(ADJ_THREADS), lds, st, P);
@@ -203,7 +192,7 @@ extern "C" int cimpc_plant_tape_vjp_feedback(cimpc_plant_tape tape, const double
         if (ok && g_h) ok = hipMemcpyAsync(g_h, d_h, n_h * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
         ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
     }
-    if (cur != tape->device) ok = (hipSetDevice(cur) == hipSuccess) && ok;
+    if (cur != buf.device) ok = (hipSetDevice(cur) == hipSuccess) && ok;
     return ok ? CIMPC_OK : CIMPC_ERR_HIP;
 }
 

@@ -303,187 +303,132 @@ std::mutex g_plant_mu;
 }  // namespace cimpc
 
 namespace {
-// Every entry point: validate (no device needed), pick the model, stage inputs on the device's private stream, launch the rollout's
-// chunks back to back (plant_rollout_plan.h; the trajectory buffer carries the state, no host synchronize in between), read back once.
+// Every entry point, on the call it filled in (plant_rollout_call.h): check it (no device needed), pick the device, lay the call out in
+// the workspace, grow, stage inputs on the device's private stream, launch the rollout's chunks back to back (plant_rollout_plan.h; the
+// trajectory buffer carries the state, no host synchronize in between), read back once.
 // A simulator step is the rollout T = 1 with one u / w row per robot, and reads back trajectory row 2 alone (q_row0 = 2).  terrain =
 // nullptr (or every terrain flat on a model cimpc_plant_step has) runs the GROUND_FLAT instantiation; the box and the wall (flat only)
 // run their GROUND_ENV instantiations, pushbot and walledcartpole (flat only) GROUND_WALLS.
-// With `grad` (cimpc_plant_rollout_grad) the steps also store their z, one launch of plant_sensitivity_kernel over all T x B entries
+// With c.grad (cimpc_plant_rollout_grad) the steps also store their z, one launch of plant_sensitivity_kernel over all T x B entries
 // follows the chunks on the same stream - theta is put together on the device from the rollout's own buffers - and dz, its status and,
 // when asked for, z come back with the rollout's read-back.  With `tape` (cimpc_plant_rollout_tape, plant_tape.h) that launch writes dz
-// and its status into device memory allocated here for the tape, and dz stays there: it needs no host dz, and n_cols >= 2 nq + nu.
-// With `loop` (the _feedback entry points) the schedule goes up with the inputs, the LOOP instantiation of the kernel runs with R.fb set -
+// and its status into device memory allocated here for the tape, and dz stays there.
+// With c.loop (the _feedback entry points) the schedule goes up with the inputs, the LOOP instantiation of the kernel runs with R.fb set -
 // the law at the head of a step, then the open-loop step on the control it computed -, u_applied and fb_err come back with
-// the rollout, and the sensitivity launch reads its controls from u_applied.
-struct RolloutGrad {
-    double reg;
-    int n_cols;
-    double *z, *dz;      // z may be null
-    int* status;
-    cimpc::PlantTapeBuffers* tape = nullptr;
-};
-// A closed-loop call (the _feedback entry points): the host schedule and where u_applied (T x B x nu) and fb_err (T x B x 2nq) go.  The
-// schedule and the two outputs live in the workspace's d_fb: K | x_ref | u_applied | fb_err; with a tape K lives in memory the tape owns
-// (the reverse chain reads it).  The sensitivity launch then reads its controls from u_applied, a schedule with K_u = T, n_u = B, hold 1.
-struct RolloutFeedback {
-    const cimpc_feedback* fb;
-    double *u_applied, *fb_err;
-};
-int plant_rollout_impl(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain, const double* q0,
-                       const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w, int K_w, int n_w, int hold_w,
-                       const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, double* q, int q_row0, double* gamma, double* b,
-                       int* status, int* iters, const RolloutGrad* grad = nullptr, const RolloutFeedback* loop = nullptr) {
+// the rollout, and the sensitivity launch reads its controls from u_applied, a schedule with K_u = T, n_u = B, hold 1.
+int plant_rollout_impl(const cimpc::PlantRolloutCall& c, cimpc::PlantTapeBuffers* tape) {
     using namespace cimpc;
-    if (B <= 0 || !q0 || !q1 || !u || !opts || !q || !gamma || !b || !status || !iters || h <= 0.0) return CIMPC_ERR_INVALID;
-    if (T < 1 || steps_per_launch < 0 || K_u < 1 || hold_u < 1 || (n_u != 1 && n_u != B) || !mu || (n_mu != 1 && n_mu != B)) return CIMPC_ERR_INVALID;
-    if (w && (K_w < 1 || hold_w < 1 || (n_w != 1 && n_w != B))) return CIMPC_ERR_INVALID;
     PlantModel M{};
     bool rough = false;
-    if (!plant_model_and_ground(model, B, n_terrain, terrain, &M, &rough)) return CIMPC_ERR_INVALID;
-    if (opts->max_iter <= 0 || opts->max_ls < 0 || !(opts->r_tol > 0.0) || !(opts->kappa_tol > 0.0) || !(opts->ls_scale > 0.0 && opts->ls_scale < 1.0))
-        return CIMPC_ERR_INVALID;
-    if (grad && ((!grad->dz && !grad->tape) || !grad->status || !std::isfinite(grad->reg) || grad->reg < 0.0 || grad->n_cols < 1 || grad->n_cols > M.nth() ||
-                 !plant_sensitivity_fits(M.nz(), grad->n_cols) || (long long)T * B > INT_MAX))
-        return CIMPC_ERR_INVALID;
-    if (grad && grad->tape && grad->n_cols < 2 * M.nq + M.nu) return CIMPC_ERR_INVALID;
-    size_t n_fk = 0, n_fx = 0;
-    if (loop) {
-        const cimpc_feedback* f = loop->fb;
-        if (!f || !f->K || !f->x_ref || !loop->u_applied || !loop->fb_err || f->K_f < 1 || f->hold_f < 1 || (f->n_f != 1 && f->n_f != B) ||
-            !std::isfinite(f->n_sample) || !(f->n_sample > 0.0) || 2 * M.nq > M.nz())
-            return CIMPC_ERR_INVALID;
-        n_fx = (size_t)f->K_f * f->n_f * 2 * M.nq;
-        n_fk = n_fx * M.nu;
-        for (size_t i = 0; i < n_fk; ++i) if (!std::isfinite(f->K[i])) return CIMPC_ERR_INVALID;
-        for (size_t i = 0; i < n_fx; ++i) if (!std::isfinite(f->x_ref[i])) return CIMPC_ERR_INVALID;
-    }
+    if (plant_rollout_check(c, &M, &rough) != CIMPC_OK || (tape != nullptr) != (c.grad && c.grad->tape)) return CIMPC_ERR_INVALID;
     int dev = 0;
     if (!plant_current_device(&dev)) return CIMPC_ERR_NO_DEVICE;
-    const size_t pnc = (size_t)M.nc, pnb = (size_t)M.nb();
+    const cimpc_ip_opts* opts = c.opts;
     PlantOpts o{opts->r_tol, opts->kappa_tol, std::isinf(opts->undercut) ? 0.0 : opts->kappa_tol / opts->undercut, opts->eps_min,
                 opts->ls_scale, opts->stall_alpha, opts->max_iter, opts->max_ls};
-    const size_t nq = M.nq, nu = M.nu, nw = M.nw, row = (size_t)B * nq, TB = (size_t)T * B;
-    const size_t n_q = (size_t)(T + 2) * row, n_us = (size_t)K_u * n_u * nu, n_ws = w ? (size_t)K_w * n_w * nw : 0, n_mus = n_mu == 1 ? 0 : (size_t)B;
+    const PlantRolloutLayout L = plant_rollout_layout(M, c);
+    const int B = c.B, T = c.T;
+    const cimpc_feedback* f = c.loop ? c.loop->fb : nullptr;
     std::lock_guard<std::mutex> lock(g_plant_mu);
     PlantWs* ws = plant_ws_open(dev);
     if (!ws) return CIMPC_ERR_HIP;
     PlantWs& W = *ws;
-    if (!plant_grow(&W.d_in, &W.cap_in, n_q + n_us + n_ws + n_mus) || !plant_grow(&W.d_out, &W.cap_out, TB * (pnc + pnb)) ||
-        !plant_grow(&W.d_st, &W.cap_st, 2 * TB))
+    if (!plant_grow(&W.d_in, &W.cap_in, L.need_in) || !plant_grow(&W.d_out, &W.cap_out, L.need_out) || !plant_grow(&W.d_st, &W.cap_st, L.need_st) ||
+        !plant_grow(&W.d_ter, &W.cap_ter, rough ? (size_t)c.n_terrain : 0) || !plant_grow(&W.d_z, &W.cap_z, L.need_z) ||
+        !plant_grow(&W.d_fb, &W.cap_fb, L.need_fb) || !plant_grow(&W.d_grad, &W.cap_grad, L.need_grad) ||
+        !plant_grow(&W.d_grad_st, &W.cap_grad_st, L.need_grad_st))
         return CIMPC_ERR_HIP;
-    if (rough && !plant_grow(&W.d_ter, &W.cap_ter, (size_t)n_terrain)) return CIMPC_ERR_HIP;
-    const size_t n_zs = TB * (size_t)M.nz(), n_dz = grad ? TB * (nq + pnc + pnb) * (size_t)grad->n_cols : 0;
-    if (grad && !plant_grow(&W.d_z, &W.cap_z, n_zs)) return CIMPC_ERR_HIP;
-    const size_t n_ua = loop ? TB * nu : 0, n_fe = loop ? TB * 2 * nq : 0;
-    if (loop && !plant_grow(&W.d_fb, &W.cap_fb, n_fk + n_fx + n_ua + n_fe)) return CIMPC_ERR_HIP;
-    if (grad && !grad->tape && (!plant_grow(&W.d_grad, &W.cap_grad, n_dz) || !plant_grow(&W.d_grad_st, &W.cap_grad_st, TB))) return CIMPC_ERR_HIP;
-    double* d_dz = W.d_grad;
-    int* d_gst = W.d_grad_st;
-    if (grad && grad->tape) {      // the tape's own memory, the last thing to be allocated: whatever fails from here on frees it
-        PlantTapeBuffers& tp = *grad->tape;
-        if (hipMalloc((void**)&tp.d_dz, n_dz * sizeof(double)) != hipSuccess) { tp.d_dz = nullptr; return CIMPC_ERR_HIP; }
-        if (hipMalloc((void**)&tp.d_status, TB * sizeof(int)) != hipSuccess) {
-            (void)hipFree(tp.d_dz);
-            tp.d_dz = nullptr; tp.d_status = nullptr;
+    double *dq = W.d_in + L.q.at, *du = W.d_in + L.u.at, *dw = W.d_in + L.w.at, *dmu = W.d_in + L.mu.at;
+    double *dg = W.d_out + L.gamma.at, *db = W.d_out + L.b.at;
+    int *d_st = W.d_st + L.status.at, *d_it = W.d_st + L.iters.at;
+    double *d_fk = W.d_fb + L.fb_K.at, *d_fx = W.d_fb + L.x_ref.at, *d_ua = W.d_fb + L.u_applied.at, *d_fe = W.d_fb + L.fb_err.at;
+    double* d_dz = W.d_grad + L.dz.at;
+    int* d_gst = W.d_grad_st + L.grad_status.at;
+    if (tape) {      // the tape's own memory, the last thing to be allocated: whatever fails from here on releases it
+        auto alloc = [](auto** p, size_t n) {
+            if (hipMalloc((void**)p, n * sizeof(**p)) == hipSuccess) return true;
+            *p = nullptr;
+            return false;
+        };
+        if (!alloc(&tape->d_dz, L.dz.n) || !alloc(&tape->d_status, L.grad_status.n) || (f && !alloc(&tape->d_fb_K, L.fb_K.n))) {
+            (void)tape->release();
             return CIMPC_ERR_HIP;
         }
-        if (loop && hipMalloc((void**)&tp.d_fb_K, n_fk * sizeof(double)) != hipSuccess) {
-            (void)hipFree(tp.d_dz);
-            (void)hipFree(tp.d_status);
-            tp.d_dz = nullptr; tp.d_status = nullptr; tp.d_fb_K = nullptr;
-            return CIMPC_ERR_HIP;
-        }
-        tp.device = dev; tp.M = M;
-        if (loop) { tp.K_f = loop->fb->K_f; tp.n_f = loop->fb->n_f; tp.hold_f = loop->fb->hold_f; tp.n_sample = loop->fb->n_sample; }
-        d_dz = tp.d_dz; d_gst = tp.d_status;
+        tape->device = dev; tape->M = M;
+        d_dz = tape->d_dz; d_gst = tape->d_status;
+        if (f) { tape->K_f = f->K_f; tape->n_f = f->n_f; tape->hold_f = f->hold_f; tape->n_sample = f->n_sample; d_fk = tape->d_fb_K; }
     }
-    double* d_fk = loop ? (grad && grad->tape ? grad->tape->d_fb_K : W.d_fb) : nullptr;
-    double* d_fx = loop ? W.d_fb + n_fk : nullptr;
-    double* d_ua = loop ? d_fx + n_fx : nullptr;
-    double* d_fe = loop ? d_ua + n_ua : nullptr;
-    double* dq = W.d_in; double* du = dq + n_q; double* dw = du + n_us; double* dmu = dw + n_ws;
-    double* dg = W.d_out; double* db = dg + TB * pnc;
-    int* d_st = W.d_st;
     hipStream_t st = W.st;
-    bool ok = hipMemcpyAsync(dq, q0, row * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(dq + row, q1, row * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(du, u, n_us * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok && w) ok = hipMemcpyAsync(dw, w, n_ws * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok && n_mus) ok = hipMemcpyAsync(dmu, mu, n_mus * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok && rough) ok = hipMemcpyAsync(W.d_ter, terrain, (size_t)n_terrain * sizeof(cimpc_terrain), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (ok && loop) ok = hipMemcpyAsync(d_fk, loop->fb->K, n_fk * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-                         hipMemcpyAsync(d_fx, loop->fb->x_ref, n_fx * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    PlantRollout R{dq, du, w ? dw : nullptr, n_mus ? dmu : nullptr, dg, db, d_st, d_st + TB, mu[0], h, 0, 0, K_u, n_u, hold_u, w ? K_w : 1,
-                   w ? n_w : 1, w ? hold_w : 1, n_mu, grad ? W.d_z : nullptr, PlantFeedback{}, nullptr, nullptr};
-    if (loop) { R.fb = PlantFeedback{d_fk, d_fx, loop->fb->K_f, loop->fb->n_f, loop->fb->hold_f, loop->fb->n_sample}; R.u_applied = d_ua; R.fb_err = d_fe; }
-    for (int k = 0; ok && k < rollout_chunk_count(T, steps_per_launch); ++k) {
-        const RolloutChunk c = rollout_chunk(T, steps_per_launch, k);
-        R.t0 = c.t0; R.n = c.n;
+    bool ok = true;      // once false nothing more is put on the stream
+    auto up = [&](auto* d, const auto* h, size_t n) { ok = ok && hipMemcpyAsync(d, h, n * sizeof(*d), hipMemcpyHostToDevice, st) == hipSuccess; };
+    auto down = [&](auto* h, const auto* d, size_t n) { ok = ok && hipMemcpyAsync(h, d, n * sizeof(*d), hipMemcpyDeviceToHost, st) == hipSuccess; };
+    up(dq, c.q0, L.row);
+    up(dq + L.row, c.q1, L.row);
+    up(du, c.u.rows, L.u.n);
+    if (c.w.rows) up(dw, c.w.rows, L.w.n);
+    if (L.mu.n) up(dmu, c.mu, L.mu.n);
+    if (rough) up(W.d_ter, c.terrain, (size_t)c.n_terrain);
+    if (f) { up(d_fk, f->K, L.fb_K.n); up(d_fx, f->x_ref, L.x_ref.n); }
+    const bool has_w = c.w.rows != nullptr;
+    PlantRollout R{dq, du, has_w ? dw : nullptr, L.mu.n ? dmu : nullptr, dg, db, d_st, d_it, c.mu[0], c.h, 0, 0, c.u.K, c.u.n, c.u.hold,
+                   has_w ? c.w.K : 1, has_w ? c.w.n : 1, has_w ? c.w.hold : 1, c.n_mu, c.grad ? W.d_z : nullptr, PlantFeedback{}, nullptr, nullptr};
+    if (f) { R.fb = PlantFeedback{d_fk, d_fx, f->K_f, f->n_f, f->hold_f, f->n_sample}; R.u_applied = d_ua; R.fb_err = d_fe; }
+    for (int k = 0; ok && k < rollout_chunk_count(T, c.steps_per_launch); ++k) {
+        const RolloutChunk ch = rollout_chunk(T, c.steps_per_launch, k);
+        R.t0 = ch.t0; R.n = ch.n;
         ok = plant_visit_instance(M, rough, true, [&](auto tag) {
             using I = decltype(tag);
             constexpr int NT = step_threads(I::NZ);
-            auto kernel = loop ? plant_step_kernel<I::NZ, NT, I::GROUND, true> : plant_step_kernel<I::NZ, NT, I::GROUND, false>;
-            hipLaunchKernelGGL(kernel, dim3(B), dim3(NT), 0, st, M, o, B, R, rough ? W.d_ter : nullptr, rough ? n_terrain : 0);
+            auto kernel = f ? plant_step_kernel<I::NZ, NT, I::GROUND, true> : plant_step_kernel<I::NZ, NT, I::GROUND, false>;
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(NT), 0, st, M, o, B, R, rough ? W.d_ter : nullptr, rough ? c.n_terrain : 0);
             return hipGetLastError() == hipSuccess;
         });
     }
-    if (ok && grad) {
-        PlantSensSource src{W.d_z, nullptr, dq, du, R.w, R.mu, d_st, R.mu0, h, B, R.K_u, R.n_u, R.hold_u, R.K_w, R.n_w, R.hold_w, n_mu};
-        if (loop) { src.u = d_ua; src.K_u = T; src.n_u = B; src.hold_u = 1; }      // the controls the steps applied
-        ok = plant_sensitivity_launch(M, (int)TB, src, rough ? W.d_ter : nullptr, rough ? n_terrain : 0, grad->reg, grad->n_cols, d_dz, d_gst, st);
-        if (ok && !grad->tape) ok = hipMemcpyAsync(grad->dz, d_dz, n_dz * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
-        ok = ok && hipMemcpyAsync(grad->status, d_gst, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
-        if (ok && grad->z) ok = hipMemcpyAsync(grad->z, W.d_z, n_zs * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
+    if (ok && c.grad) {
+        PlantSensSource src{W.d_z, nullptr, dq, du, R.w, R.mu, d_st, R.mu0, c.h, B, R.K_u, R.n_u, R.hold_u, R.K_w, R.n_w, R.hold_w, c.n_mu};
+        if (f) { src.u = d_ua; src.K_u = T; src.n_u = B; src.hold_u = 1; }      // the controls the steps applied
+        ok = plant_sensitivity_launch(M, (int)L.TB, src, rough ? W.d_ter : nullptr, rough ? c.n_terrain : 0, c.grad->reg, c.grad->n_cols, d_dz, d_gst, st);
+        if (!tape) down(c.grad->dz, d_dz, L.dz.n);
+        down(c.grad->status, d_gst, L.grad_status.n);
+        if (c.grad->z) down(c.grad->z, W.d_z, L.z.n);
     }
-    if (ok) ok = hipMemcpyAsync(q, dq + (size_t)q_row0 * row, (size_t)(T + 2 - q_row0) * row * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                 hipMemcpyAsync(gamma, dg, TB * pnc * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                 hipMemcpyAsync(b, db, TB * pnb * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                 hipMemcpyAsync(status, d_st, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                 hipMemcpyAsync(iters, d_st + TB, TB * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
-    if (ok && loop) ok = hipMemcpyAsync(loop->u_applied, d_ua, n_ua * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
-                         hipMemcpyAsync(loop->fb_err, d_fe, n_fe * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
+    down(c.q, dq + (size_t)c.q_row0 * L.row, (size_t)(T + 2 - c.q_row0) * L.row);
+    down(c.gamma, dg, L.gamma.n);
+    down(c.b, db, L.b.n);
+    down(c.status, d_st, L.status.n);
+    down(c.iters, d_it, L.iters.n);
+    if (f) { down(c.loop->u_applied, d_ua, L.u_applied.n); down(c.loop->fb_err, d_fe, L.fb_err.n); }
     ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
-    if (!ok && grad && grad->tape) {
-        (void)hipFree(grad->tape->d_dz);
-        (void)hipFree(grad->tape->d_status);
-        if (grad->tape->d_fb_K) (void)hipFree(grad->tape->d_fb_K);
-        grad->tape->d_dz = nullptr; grad->tape->d_status = nullptr; grad->tape->d_fb_K = nullptr;
-    }
+    if (!ok && tape) (void)tape->release();
     return ok ? CIMPC_OK : CIMPC_ERR_HIP;
 }
 }  // namespace
 
-int cimpc::plant_rollout_to_tape(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain, const double* q0,
-                                 const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w, int K_w, int n_w, int hold_w,
-                                 const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, double* q, double* gamma, double* b,
-                                 int* status, int* iters, double reg, int n_cols, double* z, int* grad_status, PlantTapeBuffers* tape,
-                                 bool closed_loop, const cimpc_feedback* fb, double* u_applied, double* fb_err) {
-    const RolloutGrad grad{reg, n_cols, z, nullptr, grad_status, tape};
-    const RolloutFeedback loop{fb, u_applied, fb_err};
-    return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
-                              h, opts, q, 0, gamma, b, status, iters, &grad, closed_loop ? &loop : nullptr);
+int cimpc::plant_rollout_to_tape(const PlantRolloutCall& call, PlantTapeBuffers* tape) {
+    return tape ? plant_rollout_impl(call, tape) : CIMPC_ERR_INVALID;
 }
 
 extern "C" int cimpc_plant_step(int model, int B, const double* q0, const double* q1, const double* u, const double* w,
                                 double mu, double h, const cimpc_ip_opts* opts, double* q2, double* gamma, double* b,
                                 int* status, int* iters) {
-    return plant_rollout_impl(model, B, 1, 1, 0, nullptr, q0, q1, u, 1, B, 1, w, 1, B, 1, &mu, 1, h, opts, q2, 2, gamma, b, status, iters);
+    return plant_rollout_impl({.model = model, .B = B, .T = 1, .steps_per_launch = 1, .n_terrain = 0, .terrain = nullptr, .q0 = q0, .q1 = q1,
+                               .u = {u, 1, B, 1}, .w = {w, 1, B, 1}, .mu = &mu, .n_mu = 1, .h = h, .opts = opts, .q = q2, .q_row0 = 2,
+                               .gamma = gamma, .b = b, .status = status, .iters = iters}, nullptr);
 }
 
 extern "C" int cimpc_plant_step_terrain(int model, int B, int n_terrain, const cimpc_terrain* terrain, const double* q0,
                                         const double* q1, const double* u, const double* w, double mu, double h,
                                         const cimpc_ip_opts* opts, double* q2, double* gamma, double* b, int* status, int* iters) {
-    if (!terrain) return CIMPC_ERR_INVALID;
-    return plant_rollout_impl(model, B, 1, 1, n_terrain, terrain, q0, q1, u, 1, B, 1, w, 1, B, 1, &mu, 1, h, opts, q2, 2, gamma, b, status, iters);
+    return plant_rollout_impl({.model = model, .B = B, .T = 1, .steps_per_launch = 1, .n_terrain = n_terrain, .terrain = terrain,
+                               .needs_terrain = true, .q0 = q0, .q1 = q1, .u = {u, 1, B, 1}, .w = {w, 1, B, 1}, .mu = &mu, .n_mu = 1, .h = h,
+                               .opts = opts, .q = q2, .q_row0 = 2, .gamma = gamma, .b = b, .status = status, .iters = iters}, nullptr);
 }
 
 extern "C" int cimpc_plant_rollout(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
                                    const double* q0, const double* q1, const double* u, int K_u, int n_u, int hold_u, const double* w,
                                    int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
                                    double* q, double* gamma, double* b, int* status, int* iters) {
-    if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
-    return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
-                              h, opts, q, 0, gamma, b, status, iters);
+    return plant_rollout_impl({PLANT_ROLLOUT_CALL_BASE}, nullptr);
 }
 
 extern "C" int cimpc_plant_rollout_grad(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
@@ -491,10 +436,7 @@ extern "C" int cimpc_plant_rollout_grad(int model, int B, int T, int steps_per_l
                                         int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
                                         double* q, double* gamma, double* b, int* status, int* iters, double reg, int n_cols, double* z,
                                         double* dz, int* grad_status) {
-    if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
-    const RolloutGrad grad{reg, n_cols, z, dz, grad_status};
-    return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
-                              h, opts, q, 0, gamma, b, status, iters, &grad);
+    return plant_rollout_impl({PLANT_ROLLOUT_CALL_BASE, .grad = cimpc::PlantRolloutGrad{reg, n_cols, z, dz, grad_status, false}}, nullptr);
 }
 
 extern "C" int cimpc_plant_rollout_feedback(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
@@ -502,10 +444,7 @@ extern "C" int cimpc_plant_rollout_feedback(int model, int B, int T, int steps_p
                                             const double* w, int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h,
                                             const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status, int* iters,
                                             const cimpc_feedback* fb, double* u_applied, double* fb_err) {
-    if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
-    const RolloutFeedback loop{fb, u_applied, fb_err};
-    return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
-                              h, opts, q, 0, gamma, b, status, iters, nullptr, &loop);
+    return plant_rollout_impl({PLANT_ROLLOUT_CALL_BASE, .loop = cimpc::PlantRolloutLoop{fb, u_applied, fb_err}}, nullptr);
 }
 
 extern "C" int cimpc_plant_rollout_grad_feedback(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
@@ -514,9 +453,7 @@ extern "C" int cimpc_plant_rollout_grad_feedback(int model, int B, int T, int st
                                                  const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status, int* iters,
                                                  double reg, int n_cols, double* z, double* dz, int* grad_status, const cimpc_feedback* fb,
                                                  double* u_applied, double* fb_err) {
-    if ((n_terrain != 0) != (terrain != nullptr)) return CIMPC_ERR_INVALID;
-    const RolloutGrad grad{reg, n_cols, z, dz, grad_status};
-    const RolloutFeedback loop{fb, u_applied, fb_err};
-    return plant_rollout_impl(model, B, T, steps_per_launch, n_terrain, terrain, q0, q1, u, K_u, n_u, hold_u, w, K_w, n_w, hold_w, mu, n_mu,
-                              h, opts, q, 0, gamma, b, status, iters, &grad, &loop);
+    return plant_rollout_impl({PLANT_ROLLOUT_CALL_BASE, .grad = cimpc::PlantRolloutGrad{reg, n_cols, z, dz, grad_status, false},
+                               .loop = cimpc::PlantRolloutLoop{fb, u_applied, fb_err}}, nullptr);
 }
+

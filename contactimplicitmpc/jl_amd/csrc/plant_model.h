@@ -862,4 +862,20 @@ inline bool plant_model_by_id(int id, PlantModel* out) {
     }
 }
 
+// The model behind a CIMPC_PLANT_* id and the ground of a call over n robots or knots: terrain null (flat ground), or 1 terrain for
+// all or n, one each, every one a terrain the model can stand on.  *rough: the terrain list has to reach the device (a terrain that is
+// not flat, or particle_2D, which has no flat residual and so no call without a terrain).  False: an entry point refuses the call.
+inline bool plant_model_and_ground(int model, int n, int n_terrain, const cimpc_terrain* terrain, PlantModel* M, bool* rough) {
+    if (!plant_model_by_id(model, M) || (model == CIMPC_PLANT_PARTICLE_2D && !terrain)) return false;
+    *rough = model == CIMPC_PLANT_PARTICLE_2D;
+    if (terrain) {
+        if (n_terrain != 1 && n_terrain != n) return false;
+        for (int i = 0; i < n_terrain; ++i) {
+            if (!terrain_valid_for(*M, terrain[i])) return false;
+            *rough = *rough || terrain[i].kind != CIMPC_TERRAIN_FLAT;
+        }
+    }
+    return true;
+}
+
 }  // namespace cimpc

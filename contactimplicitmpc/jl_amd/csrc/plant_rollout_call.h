@@ -1,0 +1,153 @@
+// One call of the device rollout, stated once (plain C++, host only: tests/native/plant_rollout_call_check.cpp builds it with g++):
+// what the call is given (PlantRolloutCall), every test made on it before a device is touched (plant_rollout_check), and where each
+// of its arrays lives in the plant workspace's grow-only buffers (plant_rollout_layout).  The eight entry points - cimpc_plant_step,
+// _step_terrain, _rollout, _rollout_grad, _rollout_tape and the three _feedback ones - fill a PlantRolloutCall from their C parameter
+// lists and hand it to plant_rollout_impl (plant_kernel.hip), which reads its pointers off the layout.
+#pragma once
+#include <climits>
+#include <cmath>
+#include <cstddef>
+#include <optional>
+
+#include "../../../include/cimpc.h"
+#include "plant_model.h"
+#include "plant_sensitivity_plan.h"
+
+namespace cimpc {
+
+// K x n x width doubles on the host, row k held for `hold` steps (rollout_row); n = 1: one schedule for every robot, B: one per robot
+struct PlantSchedule { const double* rows; int K, n, hold; };
+
+// The step gradients of every step (the _grad and _tape entry points): dz T x B x (nr x n_cols), its status T x B and, when asked for,
+// z T x B x nz.  tape: dz stays on the device in memory the tape owns (plant_tape.h), dz is not read, and n_cols >= 2 nq + nu.
+struct PlantRolloutGrad {
+    double reg;
+    int n_cols;
+    double *z, *dz;      // z may be null
+    int* status;
+    bool tape;
+};
+
+// A closed loop (the _feedback entry points): the host schedule and where u_applied (T x B x nu) and fb_err (T x B x 2nq) go
+struct PlantRolloutLoop {
+    const cimpc_feedback* fb;
+    double *u_applied, *fb_err;
+};
+
+// Everything a rollout call is given.  A simulator step is T = 1, steps_per_launch = 1, one u and one w row per robot, n_mu = 1 and
+// q_row0 = 2 (trajectory row 2 alone comes back).
+struct PlantRolloutCall {
+    int model, B, T, steps_per_launch;
+    int n_terrain;
+    const cimpc_terrain* terrain;
+    bool needs_terrain = false;      // cimpc_plant_step_terrain: a null terrain is refused; every other entry pairs terrain with its count
+    const double *q0, *q1;
+    PlantSchedule u, w;      // w.rows may be null: no disturbance
+    const double* mu;
+    int n_mu;
+    double h;
+    const cimpc_ip_opts* opts;
+    double* q;
+    int q_row0 = 0;          // the first trajectory row that is read back into q
+    double *gamma, *b;
+    int *status, *iters;
+    std::optional<PlantRolloutGrad> grad;
+    std::optional<PlantRolloutLoop> loop;
+};
+
+// The fields the six rollout entry points fill from the 25 parameters they share (cimpc_plant_rollout, include/cimpc.h), by the
+// parameters' names and stated once, so that no entry can transpose two of them: {PLANT_ROLLOUT_CALL_BASE, .grad = ..., .loop = ...}.
+#define PLANT_ROLLOUT_CALL_BASE                                                                                                             \
+    .model = model, .B = B, .T = T, .steps_per_launch = steps_per_launch, .n_terrain = n_terrain, .terrain = terrain, .q0 = q0, .q1 = q1, \
+    .u = {u, K_u, n_u, hold_u}, .w = {w, K_w, n_w, hold_w}, .mu = mu, .n_mu = n_mu, .h = h, .opts = opts, .q = q, .gamma = gamma, .b = b,  \
+    .status = status, .iters = iters
+
+// Elements [at, at + n) of a workspace buffer
+struct PlantSpan { size_t at = 0, n = 0; };
+
+// Where a call's arrays live, in elements of each buffer of PlantWs (plant_workspace.h), and what plant_grow is asked for (need_*; 0:
+// the call does not use the buffer).  The regions of a buffer follow each other in the order they are listed, without gaps; one that
+// the call does not have takes no room.
+struct PlantRolloutLayout {
+    size_t row = 0, TB = 0;                        // B x nq doubles of one trajectory row; T x B steps
+    PlantSpan q, u, w, mu;                         // d_in: trajectory (T + 2) x B x nq | u schedule | w schedule | per-robot mu (n_mu = B)
+    PlantSpan gamma, b;                            // d_out: T x B x nc | T x B x nb
+    PlantSpan status, iters;                       // d_st: T x B each
+    PlantSpan z;                                   // d_z: T x B x nz, with grad
+    PlantSpan dz, grad_status;                     // d_grad, d_grad_st - or, with a tape, the tape's d_dz and d_status, and need_grad* = 0
+    PlantSpan fb_K, x_ref, u_applied, fb_err;      // d_fb, with loop; with a tape K is read from the tape's d_fb_K and the K region stays unused
+    size_t need_in = 0, need_out = 0, need_st = 0, need_z = 0, need_grad = 0, need_grad_st = 0, need_fb = 0;
+};
+
+inline PlantRolloutLayout plant_rollout_layout(const PlantModel& M, const PlantRolloutCall& c) {
+    PlantRolloutLayout L;
+    const size_t nq = M.nq, nu = M.nu, nr = nq + (size_t)M.nc + (size_t)M.nb();
+    L.row = (size_t)c.B * nq;
+    L.TB = (size_t)c.T * c.B;
+    size_t at = 0;
+    auto next = [&at](size_t n) { const PlantSpan s{at, n}; at += n; return s; };
+    auto end = [&at]() { const size_t need = at; at = 0; return need; };
+    L.q = next((size_t)(c.T + 2) * L.row);
+    L.u = next((size_t)c.u.K * c.u.n * nu);
+    L.w = next(c.w.rows ? (size_t)c.w.K * c.w.n * M.nw : 0);
+    L.mu = next(c.n_mu == 1 ? 0 : (size_t)c.B);
+    L.need_in = end();
+    L.gamma = next(L.TB * M.nc);
+    L.b = next(L.TB * M.nb());
+    L.need_out = end();
+    L.status = next(L.TB);
+    L.iters = next(L.TB);
+    L.need_st = end();
+    if (c.grad) {
+        L.z = next(L.TB * M.nz());
+        L.need_z = end();
+        L.dz = next(L.TB * nr * (size_t)c.grad->n_cols);
+        L.need_grad = end();
+        L.grad_status = next(L.TB);
+        L.need_grad_st = end();
+        if (c.grad->tape) L.need_grad = L.need_grad_st = 0;
+    }
+    if (c.loop) {
+        const size_t n_x = (size_t)c.loop->fb->K_f * c.loop->fb->n_f * 2 * nq;
+        L.fb_K = next(n_x * nu);
+        L.x_ref = next(n_x);
+        L.u_applied = next(L.TB * nu);
+        L.fb_err = next(L.TB * 2 * nq);
+        L.need_fb = end();
+    }
+    return L;
+}
+
+// Every test of a call that needs no device.  CIMPC_OK: *M is the call's model and *rough says whether its terrains have to reach the
+// device; CIMPC_ERR_INVALID: the call is refused.  K and x_ref are read (they must be finite) only after every test on the schedule
+// that owns them.
+inline int plant_rollout_check(const PlantRolloutCall& c, PlantModel* M, bool* rough) {
+    const int B = c.B;
+    if (c.needs_terrain ? !c.terrain : (c.n_terrain != 0) != (c.terrain != nullptr)) return CIMPC_ERR_INVALID;
+    if (B <= 0 || !c.q0 || !c.q1 || !c.u.rows || !c.opts || !c.q || !c.gamma || !c.b || !c.status || !c.iters || c.h <= 0.0) return CIMPC_ERR_INVALID;
+    if (c.T < 1 || c.steps_per_launch < 0 || c.u.K < 1 || c.u.hold < 1 || (c.u.n != 1 && c.u.n != B) || !c.mu || (c.n_mu != 1 && c.n_mu != B))
+        return CIMPC_ERR_INVALID;
+    if (c.w.rows && (c.w.K < 1 || c.w.hold < 1 || (c.w.n != 1 && c.w.n != B))) return CIMPC_ERR_INVALID;
+    if (!plant_model_and_ground(c.model, B, c.n_terrain, c.terrain, M, rough)) return CIMPC_ERR_INVALID;
+    const cimpc_ip_opts& o = *c.opts;
+    if (o.max_iter <= 0 || o.max_ls < 0 || !(o.r_tol > 0.0) || !(o.kappa_tol > 0.0) || !(o.ls_scale > 0.0 && o.ls_scale < 1.0)) return CIMPC_ERR_INVALID;
+    if (c.grad) {
+        const PlantRolloutGrad& g = *c.grad;
+        if ((!g.dz && !g.tape) || !g.status || !std::isfinite(g.reg) || g.reg < 0.0 || g.n_cols < 1 || g.n_cols > M->nth() ||
+            !plant_sensitivity_fits(M->nz(), g.n_cols) || (long long)c.T * B > INT_MAX)
+            return CIMPC_ERR_INVALID;
+        if (g.tape && g.n_cols < 2 * M->nq + M->nu) return CIMPC_ERR_INVALID;
+    }
+    if (c.loop) {
+        const cimpc_feedback* f = c.loop->fb;
+        if (!f || !f->K || !f->x_ref || !c.loop->u_applied || !c.loop->fb_err || f->K_f < 1 || f->hold_f < 1 || (f->n_f != 1 && f->n_f != B) ||
+            !std::isfinite(f->n_sample) || !(f->n_sample > 0.0) || 2 * M->nq > M->nz())
+            return CIMPC_ERR_INVALID;
+        const PlantRolloutLayout L = plant_rollout_layout(*M, c);
+        for (size_t i = 0; i < L.fb_K.n; ++i) if (!std::isfinite(f->K[i])) return CIMPC_ERR_INVALID;
+        for (size_t i = 0; i < L.x_ref.n; ++i) if (!std::isfinite(f->x_ref[i])) return CIMPC_ERR_INVALID;
+    }
+    return CIMPC_OK;
+}
+
+}  // namespace cimpc

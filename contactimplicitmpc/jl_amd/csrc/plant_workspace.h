@@ -2,18 +2,16 @@
 // buffers and a private stream live across calls (a simulator step is called thousands of times in a closed loop; allocating and a
 // device-wide synchronize per call stalled everything else on the GPU).  One mutex serializes the entry points; each keeps buffers
 // of its own, grow-only, and all share the stream.
-//   step / rollout  d_in: trajectory (T + 2) x B x nq | u schedule | w schedule | per-robot mu; d_out: gamma | b; d_st: status | iters
-//                   (T x B each); d_ter: the robots' terrains
+//   step / rollout  d_in, d_out, d_st, d_z, d_grad, d_grad_st, d_fb: the regions of each, their order and sizes are plant_rollout_layout's
+//                   (plant_rollout_call.h); d_ter: the robots' terrains
 //   linearize       d_lin_in: z | theta | terrains (N x nz, N x nth, n_terrain cimpc_terrain); d_lin_out: r0 | rz0 | rth0 (those asked for)
-//   step gradients  d_z: the converged z of every step of a rollout (T x B x nz); d_grad: dz (N x nr x n_cols); d_grad_st: status (N);
-//                   cimpc_plant_sensitivity stages its knots in d_lin_in
-//   closed loop     d_fb: the feedback schedule and what the steps made of it, K | x_ref | u_applied (T x B x nu) | fb_err (T x B x 2nq);
-//                   with a tape, K is in the tape's memory instead
+//   step gradients  cimpc_plant_sensitivity: d_grad: dz (N x nr x n_cols); d_grad_st: status (N); it stages its knots in d_lin_in
 //   reverse chain   d_adj_in: gq | ggamma | gb (those given); d_adj_out: g_q0 | g_q1 | g_u_step | g_w_step | g_mu | g_h; d_adj_cut: n_cut (B);
 //                   d_adj_xref: g_xref_step (T x B x 2nq) of a closed-loop tape.
 //                   A tape's dz and status are NOT here: they belong to the tape (plant_adjoint.hip) and live as long as it does
-// The prologue the entry points share is stated here once: which model and ground a call names (plant_model_and_ground, no device
-// needed), which device it runs on (plant_current_device), and its workspace with the stream open (plant_ws_open).
+// The prologue the entry points share past their validation (plant_model_and_ground, plant_model.h; plant_rollout_check,
+// plant_rollout_call.h: no device needed) is stated here once: which device a call runs on (plant_current_device), and its workspace
+// with the stream open (plant_ws_open).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -53,22 +51,6 @@ bool plant_grow(T** p, size_t* cap, size_t need) {
     *p = nullptr; *cap = 0;
     if (hipMalloc((void**)p, need * sizeof(T)) != hipSuccess) return false;
     *cap = need;
-    return true;
-}
-
-// The model behind a CIMPC_PLANT_* id and the ground of a call over n robots or knots: terrain null (flat ground), or 1 terrain for
-// all or n, one each, every one a terrain the model can stand on.  *rough: the terrain list has to reach the device (a terrain that is
-// not flat, or particle_2D, which has no flat residual and so no call without a terrain).  False: an entry point refuses the call.
-inline bool plant_model_and_ground(int model, int n, int n_terrain, const cimpc_terrain* terrain, PlantModel* M, bool* rough) {
-    if (!plant_model_by_id(model, M) || (model == CIMPC_PLANT_PARTICLE_2D && !terrain)) return false;
-    *rough = model == CIMPC_PLANT_PARTICLE_2D;
-    if (terrain) {
-        if (n_terrain != 1 && n_terrain != n) return false;
-        for (int i = 0; i < n_terrain; ++i) {
-            if (!terrain_valid_for(*M, terrain[i])) return false;
-            *rough = *rough || terrain[i].kind != CIMPC_TERRAIN_FLAT;
-        }
-    }
     return true;
 }
 

@@ -121,9 +121,24 @@ class Feedback:
     n_sample: object = None
 
 
-def _feedback_arrays(model: str, fb: Feedback, B: int, N_sample: int):
-    """A `Feedback` checked and laid out for the library: (K rows (K_f, n_f, 2nq, nu) = K / N_sample with column-major blocks, x_ref
-    (K_f, n_f, 2nq), hold, n_sample, shared)."""
+@dataclasses.dataclass
+class _FeedbackArrays:
+    """A `Feedback` checked and laid out for the library: K rows (K_f, n_f, 2nq, nu) = K / N_sample with column-major blocks, x_ref
+    (K_f, n_f, 2nq), hold, n_sample, and shared: one schedule for every robot (n_f = 1).  Unpacks as those five."""
+    K: np.ndarray
+    x_ref: np.ndarray
+    hold: int
+    n_sample: float
+    shared: bool
+
+    K_f = property(lambda self: self.K.shape[0])
+
+    def __iter__(self):
+        return iter((self.K, self.x_ref, self.hold, self.n_sample, self.shared))
+
+
+def _feedback_arrays(model: str, fb: Feedback, B: int, N_sample: int) -> _FeedbackArrays:
+    """A `Feedback` checked and laid out for the library."""
     mid, nq, nu, nc, fd, nw = model_dims(model)
     K, xr = np.asarray(fb.K, dtype=np.float64), np.asarray(fb.x_ref, dtype=np.float64)
     shared = K.ndim == 3
@@ -140,16 +155,30 @@ def _feedback_arrays(model: str, fb: Feedback, B: int, N_sample: int):
         raise ValueError("Feedback.K and Feedback.x_ref must be finite")
     if shared:
         K, xr = K[:, None], xr[:, None]
-    return np.ascontiguousarray((K / int(N_sample)).transpose(0, 1, 3, 2)), np.ascontiguousarray(xr), int(fb.hold), n_sample, shared
+    return _FeedbackArrays(np.ascontiguousarray((K / int(N_sample)).transpose(0, 1, 3, 2)), np.ascontiguousarray(xr), int(fb.hold), n_sample, shared)
+
+
+@dataclasses.dataclass
+class _RolloutResult:
+    """What `_rollout_call` returns: q (T + 2, B, nq), gamma, b, status, iters as the library wrote them; grads with grad and no tape;
+    tape = (z or None, grad_status, the tape's handle) with a tape; u_applied (T, B, nu) and fb_err (T, B, 2nq) as the device made them
+    with feedback.  Whatever the call did not ask for is None."""
+    q: np.ndarray
+    gamma: np.ndarray
+    b: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    grads: object = None
+    tape: object = None
+    u_applied: object = None
+    fb_err: object = None
 
 
 def _rollout_call(model: str, q0, q1, ua, hold_u: int, wa, hold_w: int, mua, h: float, opts, terrain, steps_per_launch: int, T: int, grad,
-                  tape=None, feedback=None):
+                  tape=None, feedback=None) -> _RolloutResult:
     """`cimpc_plant_rollout`, or `cimpc_plant_rollout_grad` with grad = (reg, n_cols): contiguous q0, q1 (B, nq), ua (K, 1 or B, nu),
-    wa None or (K_w, 1 or B, nw), mua (1 or B,) -> (q, gamma, b, status, iters, StepGradients or None).  tape = keep_z (a bool) with grad:
-    `cimpc_plant_rollout_tape`, whose last element is (z or None, grad_status, the tape's handle).  feedback = the first four elements of
-    `_feedback_arrays`: the `_feedback` entry of each, and one more element, (u_applied (T, B, nu), fb_err (T, B, 2nq)) as the device
-    made them."""
+    wa None or (K_w, 1 or B, nw), mua (1 or B,).  tape = keep_z (a bool) with grad: `cimpc_plant_rollout_tape`.  feedback = a
+    `_FeedbackArrays`: the `_feedback` entry of each."""
     mid, nq, nu, nc, fd, nw = model_dims(model)
     B, nb, nz = q1.shape[0], fd * nc, nq + 4 * nc + 2 * fd * nc
     lib = _lib.load()
@@ -162,31 +191,29 @@ def _rollout_call(model: str, q0, q1, ua, hold_u: int, wa, hold_w: int, mua, h: 
     args = (mid, B, T, int(steps_per_launch), nt, ta, dp(q0), dp(q1), dp(ua), ua.shape[0], ua.shape[1], int(hold_u),
             dp(wa), 1 if wa is None else wa.shape[0], 1 if wa is None else wa.shape[1], int(hold_w), dp(mua), mua.size,
             float(h), C.byref(o), dp(q), dp(g), dp(b), ip(st), ip(it))
-    sfx, loop, more = "", (), ()
+    res = _RolloutResult(q, g, b, st, it)
+    sfx, loop = "", ()
     if feedback is not None:
-        Kc, xr, hold_f, n_sample = feedback
-        cfb = _lib.Feedback(dp(Kc), dp(xr), Kc.shape[0], Kc.shape[1], hold_f, n_sample)
-        u_dev, fb_err = np.zeros((T, B, nu)), np.zeros((T, B, 2 * nq))
-        sfx, loop, more = "_feedback", (C.byref(cfb), dp(u_dev), dp(fb_err)), ((u_dev, fb_err),)
+        cfb = _lib.Feedback(dp(feedback.K), dp(feedback.x_ref), feedback.K_f, feedback.K.shape[1], feedback.hold, feedback.n_sample)
+        res.u_applied, res.fb_err = np.zeros((T, B, nu)), np.zeros((T, B, 2 * nq))
+        sfx, loop = "_feedback", (C.byref(cfb), dp(res.u_applied), dp(res.fb_err))
+    gst = np.zeros((T, B), dtype=np.int32)
     if grad is None:
-        rc = getattr(lib, "cimpc_plant_rollout" + sfx)(*args, *loop)
-        if rc != 0:
-            raise _lib.CimpcError(f"cimpc_plant_rollout{sfx} failed ({rc})")
-        return (q, g, b, st, it, None) + more
-    reg, n_cols = grad
-    if tape is not None:      # dz stays on the device (`cimpc_plant_rollout_tape`): (z or None, grad_status, the tape's handle)
-        z = np.zeros((T, B, nz)) if tape else None
-        gst = np.zeros((T, B), dtype=np.int32)
-        handle = C.c_void_p()
-        rc = getattr(lib, "cimpc_plant_rollout_tape" + sfx)(*args, reg, n_cols, dp(z), ip(gst), C.byref(handle), *loop)
-        if rc != 0:
-            raise _lib.CimpcError(f"cimpc_plant_rollout_tape{sfx} failed ({rc})")
-        return (q, g, b, st, it, (z, gst, handle)) + more
-    z = np.zeros((T, B, nz)); dz = np.zeros((T, B, n_cols, nq + nc + nb)); gst = np.zeros((T, B), dtype=np.int32)      # the library's blocks are column-major
-    rc = getattr(lib, "cimpc_plant_rollout_grad" + sfx)(*args, reg, n_cols, dp(z), dp(dz), ip(gst), *loop)
+        name, more = "cimpc_plant_rollout", ()
+    elif tape is not None:      # dz stays on the device
+        name, z, handle = "cimpc_plant_rollout_tape", np.zeros((T, B, nz)) if tape else None, C.c_void_p()
+        more = (*grad, dp(z), ip(gst), C.byref(handle))
+    else:
+        name, z, dz = "cimpc_plant_rollout_grad", np.zeros((T, B, nz)), np.zeros((T, B, grad[1], nq + nc + nb))      # the library's blocks are column-major
+        more = (*grad, dp(z), dp(dz), ip(gst))
+    rc = getattr(lib, name + sfx)(*args, *more, *loop)
     if rc != 0:
-        raise _lib.CimpcError(f"cimpc_plant_rollout_grad{sfx} failed ({rc})")
-    return (q, g, b, st, it, StepGradients(np.ascontiguousarray(dz.transpose(0, 1, 3, 2)), z, gst, nq, nu, nc, nb)) + more
+        raise _lib.CimpcError(f"{name}{sfx} failed ({rc})")
+    if tape is not None and grad is not None:
+        res.tape = (z, gst, handle)
+    elif grad is not None:
+        res.grads = StepGradients(np.ascontiguousarray(dz.transpose(0, 1, 3, 2)), z, gst, nq, nu, nc, nb)
+    return res
 
 
 def plant_step(model: str, q0, q1, u, mu: float, h: float, w=None, opts: InteriorPointOptions = SIM_OPTS, terrain=None,
@@ -210,10 +237,10 @@ def plant_step(model: str, q0, q1, u, mu: float, h: float, w=None, opts: Interio
     if wa is not None and wa.shape[0] != B:
         raise ValueError("w must have the same leading dimension as q0")
     if diff_sol:
-        q, g, b, st, it, grads = _rollout_call(model, q0, q1, u[None], 1, None if wa is None else wa[None], 1, np.array([float(mu)]), h, opts,
-                                               terrain, 0, 1, _grad_args(model, opts, grad_reg, grad_cols))
-        grads = dataclasses.replace(grads, dz=grads.dz[0], z=grads.z[0], status=grads.status[0])
-        return q[2], g[0], b[0], st[0], it[0], grads
+        r = _rollout_call(model, q0, q1, u[None], 1, None if wa is None else wa[None], 1, np.array([float(mu)]), h, opts, terrain, 0, 1,
+                          _grad_args(model, opts, grad_reg, grad_cols))
+        grads = dataclasses.replace(r.grads, dz=r.grads.dz[0], z=r.grads.z[0], status=r.grads.status[0])
+        return r.q[2], r.gamma[0], r.b[0], r.status[0], r.iters[0], grads
     lib = _lib.load()
     q2 = np.zeros((B, nq)); g = np.zeros((B, nc)); b = np.zeros((B, fd * nc))
     st = np.zeros(B, dtype=np.int32); it = np.zeros(B, dtype=np.int32)
@@ -402,11 +429,11 @@ def rollout(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w
     terrain, q1, v1, ua, u_applied, wa, mua = _rollout_inputs(model, q1, v1, u, mu, N_sample, w, w_hold, terrain, steps)
     T = u_applied.shape[0]
     q0 = np.ascontiguousarray(q1 - h * v1); q1 = np.ascontiguousarray(q1)
-    loop = None if feedback is None else _feedback_arrays(model, feedback, q1.shape[0], N_sample)[:4]
-    q, g, b, st, it, grads, *fb = _rollout_call(model, q0, q1, ua, N_sample, wa, w_hold, mua, h, opts, terrain, steps_per_launch, T,
-                                                _grad_args(model, opts, grad_reg, grad_cols) if diff_sol else None, feedback=loop)
-    out = (bool(st.all()), q, fb[0][0] if fb else u_applied, g, b, st, it)
-    return (out + (grads,) if diff_sol else out) + ((fb[0][1],) if fb else ())
+    loop = None if feedback is None else _feedback_arrays(model, feedback, q1.shape[0], N_sample)
+    r = _rollout_call(model, q0, q1, ua, N_sample, wa, w_hold, mua, h, opts, terrain, steps_per_launch, T,
+                      _grad_args(model, opts, grad_reg, grad_cols) if diff_sol else None, feedback=loop)
+    out = (bool(r.status.all()), r.q, u_applied if loop is None else r.u_applied, r.gamma, r.b, r.status, r.iters)
+    return (out + (r.grads,) if diff_sol else out) + (() if loop is None else (r.fb_err,))
 
 
 def fold_schedule(g_step, K: int, hold: int, shared: bool, scale: float = 1.0):
@@ -477,7 +504,7 @@ class RolloutTape:
     memory (so does leaving a `with` block, and the finalizer); a closed tape raises on use."""
 
     def __init__(self, handle, model: str, grad_status, z, v1, h: float, u_shape, N_sample: int, w_shape, w_hold: int, mu_shared: bool,
-                 feedback=None):
+                 feedback=None, fb_err=None):
         import weakref
         self._handle, self.model, self.grad_status, self.z = handle, model, grad_status, z
         dims = [C.c_int() for _ in range(4)]
@@ -487,7 +514,7 @@ class RolloutTape:
         mid, self.B, self.T, self.n_cols = (d.value for d in dims)
         assert mid == model_dims(model)[0]
         self._v1, self._h, self._u_shape, self._N_sample, self._w_shape, self._w_hold, self._mu_shared = v1, h, u_shape, N_sample, w_shape, w_hold, mu_shared
-        self._feedback = feedback      # None, or (fb_err (T, B, 2nq), K_f, hold, shared) of a closed-loop tape
+        self._feedback, self._fb_err = feedback, fb_err      # a closed-loop tape: its `_FeedbackArrays` and fb_err (T, B, 2nq); else None
         self._finalizer = weakref.finalize(self, _lib.load().cimpc_plant_tape_destroy, handle)
 
     closed = property(lambda self: not self._finalizer.alive)
@@ -551,9 +578,9 @@ class RolloutTape:
                 h = h + (g_h[r] - float(self._v1[r] @ l0[r]))
         gK = gx = None
         if xref_step is not None:
-            fb_err, K_f, hold_f, shared = self._feedback
-            gK = fold_gains(u_step, fb_err, K_f, hold_f, shared, self._N_sample)
-            gx = fold_schedule(xref_step, K_f, hold_f, shared)
+            fa = self._feedback
+            gK = fold_gains(u_step, self._fb_err, fa.K_f, fa.hold, fa.shared, self._N_sample)
+            gx = fold_schedule(xref_step, fa.K_f, fa.hold, fa.shared)
         return RolloutCotangents(q1=l0 + l1, v1=-self._h * l0, u=u, u_step=u_step, w=w, mu=mu, h=h, n_cut=n_cut, g_q0=l0, g_q1=l1, w_step=w_step,
                                  g_mu=g_mu, g_h=g_h, K=gK, x_ref=gx, xref_step=xref_step)
 
@@ -573,14 +600,13 @@ def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=No
         raise ValueError(f"grad_cols must be at least {2 * nq + nu} (q0, q1 and u1) for a tape")
     q0 = np.ascontiguousarray(q1 - h * v1); q1 = np.ascontiguousarray(q1)
     loop = None if feedback is None else _feedback_arrays(model, feedback, B, N_sample)
-    q, g, b, st, it, (z, gst, handle), *fb = _rollout_call(model, q0, q1, ua, N_sample, wa, w_hold, mua, h, opts, terrain, steps_per_launch, T,
-                                                           (reg, n_cols), tape=bool(keep_z), feedback=None if loop is None else loop[:4])
+    r = _rollout_call(model, q0, q1, ua, N_sample, wa, w_hold, mua, h, opts, terrain, steps_per_launch, T, (reg, n_cols), tape=bool(keep_z),
+                      feedback=loop)
+    z, gst, handle = r.tape
     tape = RolloutTape(handle, model, gst, z, v1.copy(), float(h), np.shape(u), int(N_sample), None if w is None else np.shape(w), int(w_hold),
-                       np.ndim(mu) == 0 or (mua.size == 1 and B > 1),
-                       feedback=None if loop is None else (fb[0][1], loop[0].shape[0], loop[2], loop[4]))
-    if loop is None:
-        return bool(st.all()), q, u_applied, g, b, st, it, tape
-    return bool(st.all()), q, fb[0][0], g, b, st, it, tape, fb[0][1]
+                       np.ndim(mu) == 0 or (mua.size == 1 and B > 1), fb_err=r.fb_err, feedback=loop)
+    out = (bool(r.status.all()), r.q, u_applied if loop is None else r.u_applied, r.gamma, r.b, r.status, r.iters, tape)
+    return out if loop is None else out + (r.fb_err,)
 
 
 def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, feedback=None, **kw):
