@@ -28,11 +28,6 @@
 #include "plant_tape.h"
 #include "plant_workspace.h"
 
-struct cimpc_plant_tape_s {
-    cimpc::PlantTapeBuffers buf;      // the device memory, its device and model; buf.d_fb_K non-null: a closed-loop tape
-    int model, B, T, n_cols;
-};
-
 namespace cimpc {
 
 constexpr int ADJ_THREADS = 64;

@@ -1,4 +1,4 @@
-// Per-device workspace of the plant entry points (plant_kernel.hip: step, terrain step, rollout; plant_linearize.hip: linearize; plant_sensitivity.hip: step gradients; plant_adjoint.hip: the reverse chain):
+// Per-device workspace of the plant entry points (plant_kernel.hip: step, terrain step, rollout; plant_linearize.hip: linearize; plant_sensitivity.hip: step gradients; plant_adjoint.hip: the reverse chain; plant_tangent.hip: the forward chain):
 // buffers and a private stream live across calls (a simulator step is called thousands of times in a closed loop; allocating and a
 // device-wide synchronize per call stalled everything else on the GPU).  One mutex serializes the entry points; each keeps buffers
 // of its own, grow-only, and all share the stream.
@@ -8,6 +8,8 @@
 //   step gradients  cimpc_plant_sensitivity: d_grad: dz (N x nr x n_cols); d_grad_st: status (N); it stages its knots in d_lin_in
 //   reverse chain   d_adj_in: gq | ggamma | gb (those given); d_adj_out: g_q0 | g_q1 | g_u_step | g_w_step | g_mu | g_h; d_adj_cut: n_cut (B);
 //                   d_adj_xref: g_xref_step (T x B x 2nq) of a closed-loop tape.
+//   forward chain   d_tan_in: dq0 | dq1 | du_step | dw_step | dmu | dh | dxref_step (those given), each with a leading axis of n_dir;
+//                   d_tan_out: dq | dgamma | db | du_applied (those asked for); d_tan_cut: n_cut (B)   (plant_tangent.hip)
 //                   A tape's dz and status are NOT here: they belong to the tape (plant_adjoint.hip) and live as long as it does
 // The prologue the entry points share past their validation (plant_model_and_ground, plant_model.h; plant_rollout_check,
 // plant_rollout_call.h: no device needed) is stated here once: which device a call runs on (plant_current_device), and its workspace
@@ -39,6 +41,9 @@ struct PlantWs {
     size_t cap_adj_in = 0, cap_adj_out = 0, cap_adj_cut = 0;
     double *d_fb = nullptr, *d_adj_xref = nullptr;
     size_t cap_fb = 0, cap_adj_xref = 0;
+    double *d_tan_in = nullptr, *d_tan_out = nullptr;
+    int* d_tan_cut = nullptr;
+    size_t cap_tan_in = 0, cap_tan_out = 0, cap_tan_cut = 0;
 };
 constexpr int PLANT_MAX_DEVICES = 16;
 extern PlantWs g_plant_ws[PLANT_MAX_DEVICES];      // defined in plant_kernel.hip

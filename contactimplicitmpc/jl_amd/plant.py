@@ -12,9 +12,11 @@ open-loop schedule of controls and disturbances in one call with every intermedi
 rollout's arguments (`cimpc_plant_rollout_tape`, `cimpc_plant_tape_vjp`); `rollout_torch` is the two as a `torch.autograd.Function`.
 `feedback=Feedback(K, x_ref)` on `rollout`, `rollout_tape` and `rollout_torch` closes the loop on the device, u = ū + K (x_ref − x) at
 every step (`cimpc_plant_rollout_feedback` and its kin), and `vjp` then also returns the gradient with
-respect to the gains and the reference states.
+respect to the gains and the reference states.  `RolloutTape.jvp` is the forward chain over the same tape (`cimpc_plant_tape_jvp`; DESIGN.md
+section 3, item 3d): tangents of the rollout's arguments, any number of directions per launch, to the tangents of the whole trajectory;
+`RolloutTape.transition` is the state-transition matrix of the rollout, and `rollout_torch` answers forward-mode autograd with it.
 Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble
-solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain.
+solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain, tests/test_gpu_plant_tangent.py against restatements of the forward chain.
 """
 from __future__ import annotations
 
@@ -469,6 +471,55 @@ def fold_gains(u_step, fb_err, K: int, hold: int, shared: bool, scale: float = 1
     return acc / scale
 
 
+def spread_schedule(d, T: int, B: int, hold: int, scale: float = 1.0):
+    """The transpose of `fold_schedule`: a tangent d of schedule rows, (K, n) shared or (K, B, n), spread over the steps that apply
+    them - step t of every robot takes row min(t // hold, K - 1), divided by `scale`.  Returns (T, B, n)."""
+    d = np.asarray(d, dtype=np.float64)
+    rows = d[np.minimum(np.arange(T) // hold, d.shape[0] - 1)] / scale
+    if d.ndim == 2:
+        rows = np.broadcast_to(rows[:, None, :], (T, B, d.shape[1]))
+    return np.ascontiguousarray(rows)
+
+
+def spread_gains(dK, fb_err, hold: int, scale: float = 1.0):
+    """The transpose of `fold_gains` in its first argument: what a tangent dK of the gain rows, (K_f, nu, 2nq) shared or (K_f, B, nu, 2nq),
+    adds to the open-loop control tangent of every step, Σ_j (dK[k][i, j] / scale) fb_err[t, b, j] with k = min(t // hold, K_f - 1), the
+    terms added in the order the law sums, ascending j from 0.0.  Returns (T, B, nu)."""
+    dK = np.asarray(dK, dtype=np.float64)
+    T, B, n2 = fb_err.shape
+    rows = dK[np.minimum(np.arange(T) // hold, dK.shape[0] - 1)] / scale
+    if dK.ndim == 3:
+        rows = rows[:, None]                                                      # (T, 1 or B, nu, 2nq)
+    s = np.zeros((T, B, dK.shape[-2]))
+    for j in range(n2):
+        s = s + rows[..., j] * fb_err[:, :, j, None]
+    return s
+
+
+def tangent_group(model: str, n_cols: int, feedback: bool = False) -> int:
+    """Directions per workgroup of the forward chain, `plant_tangent_group` of csrc/plant_tangent.h restated: as many as the 160 KB of
+    a CU's LDS hold beside the two blocks - per direction x (n_cols), three rows of δq (3 nq) and with feedback δe (2nq) -, 64 at the
+    most; 0 when not even one fits.  A `jvp` of more directions runs further workgroups, and no result depends on the grouping."""
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    nr = nq + nc + fd * nc
+    per = n_cols + 3 * nq + (2 * nq if feedback else 0)
+    room = 160 * 1024 // 8 - 2 * nr * n_cols
+    return 0 if room < per else min(room // per, 64)
+
+
+@dataclasses.dataclass
+class RolloutTangents:
+    """What `RolloutTape.jvp` returns: the tangents of the trajectory, q (T + 2, B, nq), gamma (T, B, nc), b (T, B, nb), on a closed-loop
+    tape u_applied (T, B, nu), the tangent of the controls the device applied (None on an open-loop tape) - each with a leading axis of
+    n_dir when the directions were stacked -, and n_cut (B,): the steps of a robot whose gradient status is 0, through which nothing
+    flows (q[t + 2] = 0 there)."""
+    q: np.ndarray
+    gamma: np.ndarray
+    b: np.ndarray
+    u_applied: object
+    n_cut: np.ndarray
+
+
 @dataclasses.dataclass
 class RolloutCotangents:
     """What `RolloutTape.vjp` returns: the gradient of a loss on the trajectory with respect to the arguments of `rollout_tape`.
@@ -504,7 +555,7 @@ class RolloutTape:
     memory (so does leaving a `with` block, and the finalizer); a closed tape raises on use."""
 
     def __init__(self, handle, model: str, grad_status, z, v1, h: float, u_shape, N_sample: int, w_shape, w_hold: int, mu_shared: bool,
-                 feedback=None, fb_err=None):
+                 feedback=None, fb_err=None, q1_shape=None, mu_shape=()):
         import weakref
         self._handle, self.model, self.grad_status, self.z = handle, model, grad_status, z
         dims = [C.c_int() for _ in range(4)]
@@ -515,6 +566,7 @@ class RolloutTape:
         assert mid == model_dims(model)[0]
         self._v1, self._h, self._u_shape, self._N_sample, self._w_shape, self._w_hold, self._mu_shared = v1, h, u_shape, N_sample, w_shape, w_hold, mu_shared
         self._feedback, self._fb_err = feedback, fb_err      # a closed-loop tape: its `_FeedbackArrays` and fb_err (T, B, 2nq); else None
+        self._q1_shape, self._mu_shape = tuple(np.shape(v1) if q1_shape is None else q1_shape), tuple(mu_shape)      # as the caller gave them
         self._finalizer = weakref.finalize(self, _lib.load().cimpc_plant_tape_destroy, handle)
 
     closed = property(lambda self: not self._finalizer.alive)
@@ -585,6 +637,135 @@ class RolloutTape:
                                  g_mu=g_mu, g_h=g_h, K=gK, x_ref=gx, xref_step=xref_step)
 
 
+    # ---- the forward chain ----------------------------------------------------------------------------------------------------------------
+    group = property(lambda self: tangent_group(self.model, self.n_cols, self._feedback is not None),
+                     doc="directions per workgroup of a `jvp` on this tape (`tangent_group`)")
+
+    def _jvp_steps(self, n_dir: int, dq0=None, dq1=None, du_step=None, dw_step=None, dmu=None, dh=None, dxref_step=None, rows=True):
+        """`cimpc_plant_tape_jvp` / `_feedback` on per-step tangents with a leading axis of n_dir (contiguous float64; None = zeros):
+        dq0, dq1 (n_dir, B, nq), du_step (n_dir, T, B, nu), dw_step (n_dir, T, B, nw), dmu, dh (n_dir, B), dxref_step (n_dir, T, B, 2nq)
+        -> (q, gamma, b, u_applied, n_cut); rows=False leaves gamma, b and u_applied out (None)."""
+        mid, nq, nu, nc, fd, nw = model_dims(self.model)
+        B, T, nb = self.B, self.T, fd * nc
+        closed = self._feedback is not None
+        q = np.zeros((n_dir, T + 2, B, nq)); n_cut = np.zeros(B, dtype=np.int32)
+        g = np.zeros((n_dir, T, B, nc)) if rows else None
+        b = np.zeros((n_dir, T, B, nb)) if rows else None
+        ua = np.zeros((n_dir, T, B, nu)) if rows and closed else None
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        args = (self._handle, int(n_dir), dp(dq0), dp(dq1), dp(du_step), dp(dw_step), dp(dmu), dp(dh), dp(q), dp(g), dp(b),
+                n_cut.ctypes.data_as(C.POINTER(C.c_int)))
+        if closed:
+            rc = _lib.load().cimpc_plant_tape_jvp_feedback(*args, dp(dxref_step), dp(ua))
+        else:
+            rc = _lib.load().cimpc_plant_tape_jvp(*args)
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_tape_jvp failed ({rc})")
+        return q, g, b, ua, n_cut
+
+    def jvp(self, dq1=None, dv1=None, du=None, dw=None, dmu=None, dh=None, dK=None, dx_ref=None) -> RolloutTangents:
+        """The forward chain (`cimpc_plant_tape_jvp`): tangents of the arguments of `rollout_tape` - each in the
+        shape the caller gave that argument (dh a scalar; dK, dx_ref in the shapes of the `Feedback`'s K, x_ref), or every one of them with
+        one more leading axis of n_dir directions - to the tangents of the trajectory, a `RolloutTangents` (with the leading axis when the
+        arguments had it).  None is zeros, not all of them.  All directions go up in ONE launch that reads each block of the tape once
+        per `group` directions, and a direction's result does not depend by a bit on what rides with it.  What the arguments mean per step
+        (the transposes of the folds of `vjp`), element by element:
+            dq1 = δq1,  dq0 = (δq1 − h δv1) − δh v1                                   (q[0] = q1 − h v1, q[1] = q1)
+            δū_t = δu[k] / N_sample, k = min(t // N_sample, K − 1)                      (`spread_schedule`; a shared schedule goes to every robot)
+            δū_t += Σ_j (δK[k_f] / N_sample)[i, j] fb_err[t][j], ascending j from 0.0   (`spread_gains`; the device chain never sees δK)
+            δw_t = δw[min(t // w_hold, K_w − 1)];  one δμ and the one δh go to every robot;  δx_ref,t = δx_ref[k_f], k_f by the feedback's hold
+        Raises ValueError on a closed tape, a non-finite tangent, a tangent of w, mu or h whose column the tape does not cover (grad_cols),
+        a tangent of w when the rollout had none, and dK or dx_ref on an open-loop tape."""
+        if self.closed:
+            raise ValueError("the tape is closed")
+        mid, nq, nu, nc, fd, nw = model_dims(self.model)
+        B, T, fa = self.B, self.T, self._feedback
+        if fa is None and (dK is not None or dx_ref is not None):
+            raise ValueError("dK and dx_ref need the tape of a closed-loop rollout")
+        if dw is not None and self._w_shape is None:
+            raise ValueError("dw: the rollout had no w")
+        c_mu = 2 * nq + nu + nw
+        for name, a, need in (("dw", dw, c_mu), ("dmu", dmu, c_mu + 1), ("dh", dh, c_mu + 2)):
+            if a is not None and self.n_cols < need:
+                raise ValueError(f"{name}: the tape covers {self.n_cols} columns of θ, this tangent needs {need} (grad_cols)")
+        base = dict(dq1=self._q1_shape, dv1=self._q1_shape, du=tuple(self._u_shape), dw=None if self._w_shape is None else tuple(self._w_shape),
+                    dmu=self._mu_shape, dh=())
+        if fa is not None:
+            K_f = fa.K_f
+            base.update(dK=(K_f, nu, 2 * nq) if fa.shared else (K_f, B, nu, 2 * nq), dx_ref=(K_f, 2 * nq) if fa.shared else (K_f, B, 2 * nq))
+        given, n_dirs = {}, set()
+        for name, a in (("dq1", dq1), ("dv1", dv1), ("du", du), ("dw", dw), ("dmu", dmu), ("dh", dh), ("dK", dK), ("dx_ref", dx_ref)):
+            if a is None:
+                continue
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape == base[name]:
+                n_dirs.add(None); a = a[None]
+            elif a.ndim == len(base[name]) + 1 and a.shape[1:] == base[name] and a.shape[0] >= 1:
+                n_dirs.add(a.shape[0])
+            else:
+                raise ValueError(f"{name} must be {base[name]} or (n_dir,) + {base[name]}, got {a.shape}")
+            if not np.isfinite(a).all():
+                raise ValueError(f"{name} must be finite")
+            given[name] = a
+        if not given:
+            raise ValueError("at least one tangent")
+        if len(n_dirs) != 1:
+            raise ValueError("every tangent must have the same leading axis of n_dir, or none")
+        stacked = None not in n_dirs
+        n_dir = n_dirs.pop() if stacked else 1
+        get = lambda name, d: given[name][d] if name in given else None
+        dq0s = dq1s = du_s = dw_s = dmu_s = dh_s = dx_s = None
+        if any(k in given for k in ("dq1", "dv1", "dh")):
+            dq0s, dq1s = np.zeros((n_dir, B, nq)), np.zeros((n_dir, B, nq))
+            for d in range(n_dir):
+                a1 = np.broadcast_to(0.0 if get("dq1", d) is None else get("dq1", d), (B, nq))
+                av = np.broadcast_to(0.0 if get("dv1", d) is None else get("dv1", d), (B, nq))
+                ah = 0.0 if get("dh", d) is None else float(get("dh", d))
+                dq1s[d] = a1
+                dq0s[d] = (a1 - self._h * av) - ah * self._v1
+        if "du" in given or "dK" in given:
+            du_s = np.zeros((n_dir, T, B, nu))
+            for d in range(n_dir):
+                if "du" in given:
+                    du_s[d] = spread_schedule(given["du"][d], T, B, self._N_sample, self._N_sample)
+                if "dK" in given:
+                    du_s[d] = du_s[d] + spread_gains(given["dK"][d], self._fb_err, fa.hold, self._N_sample)
+        if "dw" in given:
+            dw_s = np.stack([spread_schedule(given["dw"][d], T, B, self._w_hold) for d in range(n_dir)])
+        if "dmu" in given:
+            dmu_s = np.stack([np.broadcast_to(given["dmu"][d].reshape(-1), (B,)) for d in range(n_dir)])
+        if "dh" in given:
+            dh_s = np.stack([np.full(B, float(given["dh"][d])) for d in range(n_dir)])
+        if "dx_ref" in given:
+            dx_s = np.stack([spread_schedule(given["dx_ref"][d], T, B, fa.hold) for d in range(n_dir)])
+        cont = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        q, g, b, ua, n_cut = self._jvp_steps(n_dir, cont(dq0s), cont(dq1s), cont(du_s), cont(dw_s), cont(dmu_s), cont(dh_s), cont(dx_s))
+        if not stacked:
+            q, g, b, ua = q[0], g[0], b[0], None if ua is None else ua[0]
+        return RolloutTangents(q=q, gamma=g, b=b, u_applied=ua, n_cut=n_cut)
+
+    def transition(self, t0: int = 0, t1=None):
+        """The state-transition matrix of the rollout, (B, 2nq, 2nq) = ∂[q[t1]; q[t1 + 1]] / ∂[q[t0]; q[t0 + 1]] with every other argument
+        held (on a closed-loop tape: of the closed loop); t1 defaults to T, one whole rollout - the monodromy matrix of a gait cycle.
+        ONE launch of the forward chain with the 2nq unit directions of [dq0; dq1].  The chain starts at the tape's first step, so
+        t0 must be 0: any other t0 raises ValueError (record the rollout from step t0 to start there).  A cut step inside the range
+        leaves zeros behind it, as in `jvp`."""
+        if self.closed:
+            raise ValueError("the tape is closed")
+        nq = model_dims(self.model)[1]
+        t1 = self.T if t1 is None else int(t1)
+        if int(t0) != 0:
+            raise ValueError(f"transition: t0 must be 0, the tape's first step, got {t0}; record the rollout from step {t0} to start there")
+        if not 0 <= t1 <= self.T:
+            raise ValueError(f"transition: t1 must be in 0 .. {self.T}")
+        dq0, dq1 = np.zeros((2 * nq, self.B, nq)), np.zeros((2 * nq, self.B, nq))
+        for i in range(nq):
+            dq0[i, :, i] = 1.0
+            dq1[nq + i, :, i] = 1.0
+        q = self._jvp_steps(2 * nq, dq0, dq1, rows=False)[0]
+        return np.ascontiguousarray(np.concatenate([q[:, t1], q[:, t1 + 1]], axis=2).transpose(1, 2, 0))
+
+
 def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w_hold: int = 1, opts: InteriorPointOptions = SIM_OPTS,
                  terrain=None, steps=None, steps_per_launch: int = 0, grad_reg=None, grad_cols=None, keep_z: bool = False, feedback=None):
     """`rollout` that records its step gradients on the device instead of returning them (`cimpc_plant_rollout_tape`): the arguments of
@@ -593,6 +774,7 @@ def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=No
     grad_cols (default 2 nq + nu, the least a tape takes) up to nθ adds the w, μ and h columns; keep_z also returns every step's z on
     the tape.  feedback: a `Feedback`, as in `rollout` (`cimpc_plant_rollout_tape_feedback`): u_applied is the device's, one more trailing
     element is fb_err, and the tape's `vjp` runs the closed-loop chain, whose `RolloutCotangents` carry K, x_ref and xref_step."""
+    q1_shape, mu_shape = np.shape(q1), np.shape(mu)
     terrain, q1, v1, ua, u_applied, wa, mua = _rollout_inputs(model, q1, v1, u, mu, N_sample, w, w_hold, terrain, steps)
     (T, B), (mid, nq, nu, nc, fd, nw) = u_applied.shape[:2], model_dims(model)
     reg, n_cols = _grad_args(model, opts, grad_reg, grad_cols)
@@ -604,7 +786,7 @@ def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=No
                       feedback=loop)
     z, gst, handle = r.tape
     tape = RolloutTape(handle, model, gst, z, v1.copy(), float(h), np.shape(u), int(N_sample), None if w is None else np.shape(w), int(w_hold),
-                       np.ndim(mu) == 0 or (mua.size == 1 and B > 1), fb_err=r.fb_err, feedback=loop)
+                       np.ndim(mu) == 0 or (mua.size == 1 and B > 1), fb_err=r.fb_err, feedback=loop, q1_shape=q1_shape, mu_shape=mu_shape)
     out = (bool(r.status.all()), r.q, u_applied if loop is None else r.u_applied, r.gamma, r.b, r.status, r.iters, tape)
     return out if loop is None else out + (r.fb_err,)
 
@@ -615,14 +797,16 @@ def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, feedback=None,
     the device of the first tensor given, status an int tensor without a gradient.  `backward` runs `RolloutTape.vjp` on the tape,
     which lives on the autograd graph - any number of times with retain_graph=True - and gradients reach whichever of q1, v1, u, w, mu
     require them; grad_cols is raised to cover w and mu when they do.  feedback: a `Feedback` whose K and x_ref may be tensors too; with
-    it the rollout is closed-loop, and gradients also reach K and x_ref when they require them."""
+    it the rollout is closed-loop, and gradients also reach K and x_ref when they require them.  Forward mode: under
+    `torch.autograd.forward_ad.dual_level()`, tangents on q1, v1, u, mu, w, K and x_ref reach q, gamma and b through `RolloutTape.jvp`
+    on the same tape (grad_cols is raised for a dual w or mu as for one that requires a gradient)."""
     import torch
 
     mid, nq, nu, nc, fd, nw = model_dims(model)
     fK, fx = (None, None) if feedback is None else (feedback.K, feedback.x_ref)
     tensors = [a for a in (q1, v1, u, mu, w, fK, fx) if isinstance(a, torch.Tensor)]
     device = tensors[0].device if tensors else torch.device("cpu")
-    needs = lambda a: isinstance(a, torch.Tensor) and a.requires_grad
+    needs = lambda a: isinstance(a, torch.Tensor) and (a.requires_grad or torch.autograd.forward_ad.unpack_dual(a).tangent is not None)
     cols = 2 * nq + nu + (nw + 1 if needs(mu) else nw if needs(w) else 0)
     kw = dict(kw, grad_cols=max(cols, int(kw.get("grad_cols") or 0)))
     host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
@@ -650,6 +834,11 @@ def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, feedback=None,
                 else:
                     out.append(torch.as_tensor(np.asarray(grad, dtype=np.float64), device=a.device).reshape(a.shape))
             return tuple(out)
+
+        @staticmethod
+        def jvp(ctx, tq1, tv1, tu, tmu, tw, tK, tx):
+            t = ctx.tape.jvp(dq1=host(tq1), dv1=host(tv1), du=host(tu), dmu=host(tmu), dw=host(tw), dK=host(tK), dx_ref=host(tx))
+            return torch.as_tensor(t.q, device=device), torch.as_tensor(t.gamma, device=device), torch.as_tensor(t.b, device=device), None
 
     return _Rollout.apply(q1, v1, u, mu, w, fK, fx)
 

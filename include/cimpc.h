@@ -578,6 +578,38 @@ int cimpc_plant_tape_vjp_feedback(cimpc_plant_tape tape, const double* gq, const
                                   double* g_q0, double* g_q1, double* g_u_step, double* g_w_step, double* g_mu, double* g_h, int* n_cut,
                                   double* g_xref_step);
 
+/* ---- forward tangents through a rollout's tape, many directions per launch ------------------------------------------------------------
+ * THIS BUILD'S definition (csrc/plant_tangent.h).  Per robot and per direction d, with D_t the tape's block
+ * of step t:
+ *     dq[0] = dq0, dq[1] = dq1
+ *     for t = 0 .. T-1:  closed-loop tape only, k the step's feedback row (the law of item 3c on tangents):
+ *                            de[j] = dxref_t[j] - (j < nq ? dq[t+1][j] - n_sample (dq[t+1][j] - dq[t][j]) : dq[t+1][j - nq])   (dxref_t absent = zeros)
+ *                            du_t[i] = dubar_t[i] + sum over j = 0 .. 2nq-1 of K[k][i, j] de[j]      (ascending j from 0.0)
+ *                        open-loop tape: du_t = dubar_t
+ *                        x = [dq[t]; dq[t+1]; du_t; dw_t; dmu; dh] cut to n_cols   (an input that was not passed is 0.0; nothing is skipped)
+ *                        y[r] = sum over c = 0 .. n_cols-1 of D_t[r, c] x[c]   (ascending c from 0.0, one product and one sum per term, no
+ *                        fused multiply-add);   dq[t+2] = y[0 : nq];  dgamma[t] = y[nq : nq+nc];  db[t] = y[nq+nc : nr]
+ * A step whose gradient status is 0 has a zero block: dq[t+2] = 0 there, the flow is cut and counted in n_cut, not refused.  A
+ * direction's result does not depend by a bit on how many directions ride with it or on how the library groups them.
+ *
+ * Every tangent array has a leading axis of n_dir.  In: dq0, dq1 n_dir x B x nq; du_step n_dir x T x B x nu (dubar_t, per applied
+ * control); dw_step n_dir x T x B x nw; dmu, dh n_dir x B; each may be NULL (zeros), not all of them.  Out: dq n_dir x (T + 2) x B x nq and
+ * n_cut B (required); dgamma n_dir x T x B x nc and db n_dir x T x B x nb may be NULL.  ONE launch: a workgroup per robot and group of
+ * directions reads each block once for its group.  Runs on the tape's device, whichever is current, on the plant's private stream.
+ * Validated first, without a device (CIMPC_ERR_INVALID): a null tape, n_dir < 1, no input, a null dq or n_cut, dw_step, dmu or dh given
+ * while the tape's n_cols does not reach its column (2nq + nu + nw, + 1, + 2). */
+int cimpc_plant_tape_jvp(cimpc_plant_tape tape, int n_dir, const double* dq0, const double* dq1, const double* du_step,
+                         const double* dw_step, const double* dmu, const double* dh,
+                         double* dq, double* dgamma, double* db, int* n_cut);
+/* cimpc_plant_tape_jvp's arguments, then dxref_step (n_dir x T x B x 2nq, may be NULL: zeros; it counts as an input) and du_applied
+ * (n_dir x T x B x nu, du_t; may be NULL).  Either on an open-loop tape: CIMPC_ERR_INVALID.  The chain of a closed-loop tape always
+ * includes the feedback statements: cimpc_plant_tape_jvp on such a tape is this call with two NULLs.  A tangent of the gain rows does not
+ * reach the device: the caller adds (dK[k] / N_sample) fb_err[t] to dubar_t. */
+int cimpc_plant_tape_jvp_feedback(cimpc_plant_tape tape, int n_dir, const double* dq0, const double* dq1, const double* du_step,
+                                  const double* dw_step, const double* dmu, const double* dh,
+                                  double* dq, double* dgamma, double* db, int* n_cut,
+                                  const double* dxref_step, double* du_applied);
+
 /* ---- cimpc_set_linearization_batch from (z, theta) alone: plant model `model` linearized at kappa (cimpc_plant_linearize's kernel and arguments;
  * z0 = z, th0 = theta) and the tables built from its output, all on the handle's device and stream;
  * nothing but z, theta and the terrains goes up, nothing but N status words comes back.  Equal bit for bit to

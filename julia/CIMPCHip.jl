@@ -806,6 +806,79 @@ function plant_tape_vjp_feedback(tape::PlantTape; gq::Union{Nothing,Array{Float6
     return g_q0, g_q1, g_u, g_w, g_μ, g_h, n_cut, g_x
 end
 
+# ---- forward tangents through a rollout's tape, many directions per launch ----------------------------------------------------------------
+"""
+    plant_tape_jvp(tape; dq0 = nothing, dq1 = nothing, du_step = nothing, dw_step = nothing, dμ = nothing, dh = nothing)
+        -> (dq, dγ, db, n_cut)
+
+The forward chain of `cimpc_plant_tape_jvp` over a tape, n_dir directions in one launch: tangents dq0, dq1 nq x B x n_dir of q[0], q[1],
+du_step nu x B x T x n_dir per applied control, dw_step nw x B x T x n_dir, dμ and dh B x n_dir (nothing is zeros, not all of them; dw_step,
+dμ, dh only where the tape's columns reach) to dq nq x B x (T + 2) x n_dir, dγ nc x B x T x n_dir, db nb x B x T x n_dir and n_cut (B).  For
+the arguments of `plant_rollout_tape`: dq0 = (δq1 - h δv1) - δh v1, dq1 = δq1, du_step[:, b, t] = δu[k] / N_sample.  A direction's
+result does not depend on what rides with it.
+"""
+function plant_tape_jvp(tape::PlantTape; dq0::Union{Nothing,Array{Float64,3}} = nothing, dq1::Union{Nothing,Array{Float64,3}} = nothing,
+                        du_step::Union{Nothing,Array{Float64,4}} = nothing, dw_step::Union{Nothing,Array{Float64,4}} = nothing,
+                        dμ::Union{Nothing,Matrix{Float64}} = nothing, dh::Union{Nothing,Matrix{Float64}} = nothing)
+    tape.handle != C_NULL || error("plant_tape_jvp: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, nb = tape.B, tape.T, nf * nc
+    given = [a for a in (dq0, dq1, du_step, dw_step, dμ, dh) if a !== nothing]
+    isempty(given) && error("plant_tape_jvp: at least one tangent")
+    n_dir = size(given[1], ndims(given[1]))
+    (dq0 === nothing || size(dq0) == (nq, B, n_dir)) || error("plant_tape_jvp: dq0 must be $nq x $B x n_dir")
+    (dq1 === nothing || size(dq1) == (nq, B, n_dir)) || error("plant_tape_jvp: dq1 must be $nq x $B x n_dir")
+    (du_step === nothing || size(du_step) == (nu, B, T, n_dir)) || error("plant_tape_jvp: du_step must be $nu x $B x $T x n_dir")
+    (dw_step === nothing || size(dw_step) == (nw, B, T, n_dir)) || error("plant_tape_jvp: dw_step must be $nw x $B x $T x n_dir")
+    (dμ === nothing || size(dμ) == (B, n_dir)) || error("plant_tape_jvp: dμ must be $B x n_dir")
+    (dh === nothing || size(dh) == (B, n_dir)) || error("plant_tape_jvp: dh must be $B x n_dir")
+    dq = zeros(nq, B, T + 2, n_dir); dγ = zeros(nc, B, T, n_dir); db = zeros(nb, B, T, n_dir); n_cut = zeros(Cint, B)
+    p(a) = a === nothing ? C_NULL : pointer(a)
+    GC.@preserve dq0 dq1 du_step dw_step dμ dh begin
+        p0, p1, pu, pw, pm, ph = p(dq0), p(dq1), p(du_step), p(dw_step), p(dμ), p(dh)
+        check(@ccall LIB.cimpc_plant_tape_jvp(tape.handle::Ptr{Cvoid}, n_dir::Cint, p0::Ptr{Cdouble}, p1::Ptr{Cdouble}, pu::Ptr{Cdouble},
+                                              pw::Ptr{Cdouble}, pm::Ptr{Cdouble}, ph::Ptr{Cdouble}, dq::Ptr{Cdouble}, dγ::Ptr{Cdouble},
+                                              db::Ptr{Cdouble}, n_cut::Ptr{Cint})::Cint)
+    end
+    return dq, dγ, db, n_cut
+end
+
+"""
+    plant_tape_jvp_feedback(tape; dq0, dq1, du_step, dw_step, dμ, dh, dxref_step = nothing) -> (dq, dγ, db, n_cut, du_applied)
+
+`plant_tape_jvp` on the tape of a closed-loop rollout, with dxref_step 2nq x B x T x n_dir, the tangent of the reference state each step
+read, and du_applied nu x B x T x n_dir, the tangent of the controls the device applied (an open-loop tape is refused by the library).
+du_step is the tangent of the open-loop part ū; a tangent of the gain rows is added to it by the caller, (δK[k] / N_sample) fb_err[:, b, t].
+"""
+function plant_tape_jvp_feedback(tape::PlantTape; dq0::Union{Nothing,Array{Float64,3}} = nothing, dq1::Union{Nothing,Array{Float64,3}} = nothing,
+                                 du_step::Union{Nothing,Array{Float64,4}} = nothing, dw_step::Union{Nothing,Array{Float64,4}} = nothing,
+                                 dμ::Union{Nothing,Matrix{Float64}} = nothing, dh::Union{Nothing,Matrix{Float64}} = nothing,
+                                 dxref_step::Union{Nothing,Array{Float64,4}} = nothing)
+    tape.handle != C_NULL || error("plant_tape_jvp_feedback: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, nb = tape.B, tape.T, nf * nc
+    given = [a for a in (dq0, dq1, du_step, dw_step, dμ, dh, dxref_step) if a !== nothing]
+    isempty(given) && error("plant_tape_jvp_feedback: at least one tangent")
+    n_dir = size(given[1], ndims(given[1]))
+    (dq0 === nothing || size(dq0) == (nq, B, n_dir)) || error("plant_tape_jvp_feedback: dq0 must be $nq x $B x n_dir")
+    (dq1 === nothing || size(dq1) == (nq, B, n_dir)) || error("plant_tape_jvp_feedback: dq1 must be $nq x $B x n_dir")
+    (du_step === nothing || size(du_step) == (nu, B, T, n_dir)) || error("plant_tape_jvp_feedback: du_step must be $nu x $B x $T x n_dir")
+    (dw_step === nothing || size(dw_step) == (nw, B, T, n_dir)) || error("plant_tape_jvp_feedback: dw_step must be $nw x $B x $T x n_dir")
+    (dμ === nothing || size(dμ) == (B, n_dir)) || error("plant_tape_jvp_feedback: dμ must be $B x n_dir")
+    (dh === nothing || size(dh) == (B, n_dir)) || error("plant_tape_jvp_feedback: dh must be $B x n_dir")
+    (dxref_step === nothing || size(dxref_step) == (2 * nq, B, T, n_dir)) || error("plant_tape_jvp_feedback: dxref_step must be $(2 * nq) x $B x $T x n_dir")
+    dq = zeros(nq, B, T + 2, n_dir); dγ = zeros(nc, B, T, n_dir); db = zeros(nb, B, T, n_dir); n_cut = zeros(Cint, B)
+    du_applied = zeros(nu, B, T, n_dir)
+    p(a) = a === nothing ? C_NULL : pointer(a)
+    GC.@preserve dq0 dq1 du_step dw_step dμ dh dxref_step begin
+        p0, p1, pu, pw, pm, ph, px = p(dq0), p(dq1), p(du_step), p(dw_step), p(dμ), p(dh), p(dxref_step)
+        check(@ccall LIB.cimpc_plant_tape_jvp_feedback(tape.handle::Ptr{Cvoid}, n_dir::Cint, p0::Ptr{Cdouble}, p1::Ptr{Cdouble}, pu::Ptr{Cdouble},
+                                                       pw::Ptr{Cdouble}, pm::Ptr{Cdouble}, ph::Ptr{Cdouble}, dq::Ptr{Cdouble}, dγ::Ptr{Cdouble},
+                                                       db::Ptr{Cdouble}, n_cut::Ptr{Cint}, px::Ptr{Cdouble}, du_applied::Ptr{Cdouble})::Cint)
+    end
+    return dq, dγ, db, n_cut, du_applied
+end
+
 # ---- the plant models linearized on the device: the `LinearizedStep` triple of N knots in one call (linearized_step.jl:10-31) --------
 """
     plant_linearize(model, z, θ, κ; terrain = nothing) -> (r0, rz0, rθ0)
