@@ -118,6 +118,7 @@ SIGNATURES = {
     "cimpc_plant_tape_vjp_feedback": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp]),
     "cimpc_plant_tape_jvp": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "cimpc_plant_tape_jvp_feedback": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "cimpc_plant_tape_lqr": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
     "cimpc_plant_tape_dims": (C.c_int, [_h, _ip, _ip, _ip, _ip]),
     "cimpc_plant_tape_destroy": (C.c_int, [_h]),
     "cimpc_tvlqr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),

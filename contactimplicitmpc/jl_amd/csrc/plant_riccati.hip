@@ -1,0 +1,150 @@
+// The LQ backward pass over a rollout's tape (DESIGN.md sections 3, item 3e, and 5.5): time-varying LQR gains K_t, and with linear
+// cost terms the feedforward k_t, the value's P0, p0 and the expected decrease dV, along the trajectory every robot of the tape took.
+//
+//   cimpc_plant_tape_lqr   the weights (Q, Qf, R, and q, r where given) up in ONE copy, ONE launch of plant_riccati_kernel, the gains,
+//                          the value terms, status and n_cut down in ONE copy
+//
+// plant_riccati_kernel: one workgroup of RIC_THREADS = 256 (four wavefronts, one per SIMD of the CU) per robot walks laps T steps
+// downwards through the statements of plant_riccati.h.  P, the step's matrices and both orientations of the transposed factors (Du',
+// K', Dcl') sit in LDS, so that every left factor is read along the lanes (tvlqr_kernel's note: a stride of n = 36 doubles is an 8-way
+// bank conflict); the products are the register tiles of plant_riccati_product (2 x 3, as tile_product of gains.hip), over the nonzero
+// blocks of A_t and B_t alone.  Only the nq x (2nq + nu) corner of D_t is read from the tape; the next step's corner is loaded into
+// registers before a step's arithmetic and stored to the other LDS buffer after it.  The chain is a latency chain; the robots are the
+// parallelism.  62 KB of LDS at the largest model (n = 36, m = 12), 24 KB at the quadruped.
+// gfx950, -O3: plant_riccati_kernel<false> 118 VGPRs, <true> 129 VGPRs, no scratch and no spills (see profiles/plant_riccati.json).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <vector>
+
+// No fused multiply-adds in this translation unit: the chain rounds as the float64 restatement of the definition does.
+#pragma clang fp contract(off)
+
+#include "../../../include/cimpc.h"
+#include "plant_model.h"
+#include "plant_riccati.h"
+#include "plant_tape.h"
+#include "plant_workspace.h"
+
+namespace cimpc {
+
+constexpr int RIC_THREADS = 256;
+constexpr int RIC_STAGE_DOUBLES = 4;      // per lane: a corner of up to 1024 doubles (18 x 48 = 864 at the largest model) is wholly in flight
+
+// the workgroup as the team of plant_riccati.h
+struct PlantRiccatiGroup {
+    double stage[RIC_STAGE_DOUBLES];
+    __device__ int rank() const { return threadIdx.x; }
+    __device__ int size() const { return RIC_THREADS; }
+    __device__ void sync() const { __syncthreads(); }
+    __device__ void fetch_issue(const double* src, int rows, int cols, int ld) {
+#pragma unroll
+        for (int k = 0; k < RIC_STAGE_DOUBLES; ++k) {
+            const int i = k * RIC_THREADS + (int)threadIdx.x;
+            stage[k] = i < rows * cols ? src[(size_t)(i / rows) * ld + i % rows] : 0.0;
+        }
+    }
+    __device__ void fetch_commit(double* dst, const double* src, int rows, int cols, int ld) {
+#pragma unroll
+        for (int k = 0; k < RIC_STAGE_DOUBLES; ++k) {
+            const int i = k * RIC_THREADS + (int)threadIdx.x;
+            if (i < rows * cols) dst[i] = stage[k];
+        }
+        for (int i = RIC_STAGE_DOUBLES * RIC_THREADS + (int)threadIdx.x; i < rows * cols; i += RIC_THREADS) dst[i] = src[(size_t)(i / rows) * ld + i % rows];
+    }
+};
+
+template <bool LIN>      // LIN: the chain with the linear cost terms q, r
+__global__ __launch_bounds__(RIC_THREADS) void plant_riccati_kernel(PlantRiccati L) {
+    extern __shared__ __attribute__((aligned(16))) double ric_lds[];      // plant_riccati_lds(nq, nu)
+    const int rb = blockIdx.x;
+    if (rb >= L.B) return;                                                // uniform over the workgroup
+    PlantRiccatiGroup team;
+    plant_riccati_chain_as<LIN>(L, rb, ric_lds, team);
+}
+
+namespace {
+// grow-only device buffers of the entry, one pair per device, next to the plant workspace whose stream and mutex it uses
+struct RiccatiWs { double *d_in = nullptr, *d_out = nullptr; size_t cap_in = 0, cap_out = 0; };
+RiccatiWs g_riccati_ws[PLANT_MAX_DEVICES];
+}  // namespace
+
+}  // namespace cimpc
+
+// ---- C ABI -------------------------------------------------------------------------------------------------------------
+// Validate (no device needed), then on the tape's device and the plant workspace's private stream: one upload (Q | Qf | R | q | r), one
+// launch, one read-back (K | k | P0 | p0 | dV | status | n_cut), one synchronize.
+extern "C" int cimpc_plant_tape_lqr(cimpc_plant_tape tape, int laps, int n_Q, const double* Q, const double* Qf, int n_R, const double* R,
+                                    const double* q, const double* r, double rho, int n_keep, double* K, double* k, double* P0, double* p0,
+                                    double* dV, int* status, int* n_cut) {
+    using namespace cimpc;
+    if (!tape || !Q || !Qf || !R || !K || !status || !n_cut) return CIMPC_ERR_INVALID;
+    if (!(rho >= 0.0) || !std::isfinite(rho)) return CIMPC_ERR_INVALID;
+    if (laps < 1 || n_Q < 1 || n_R < 1 || n_keep < 1) return CIMPC_ERR_INVALID;
+    if ((q != nullptr) != (r != nullptr)) return CIMPC_ERR_INVALID;
+    if (laps > 1 && q) return CIMPC_ERR_INVALID;                          // a periodic chain has no linear terms
+    if (!q && (k || p0 || dV)) return CIMPC_ERR_INVALID;
+    const PlantTapeBuffers& buf = tape->buf;
+    const int B = tape->B, T = tape->T, n_cols = tape->n_cols;
+    if (B < 1 || T < 1 || buf.device < 0 || buf.device >= PLANT_MAX_DEVICES || !buf.d_dz || !buf.d_status) return CIMPC_ERR_INVALID;
+    if ((n_Q != 1 && n_Q != T) || (n_R != 1 && n_R != T) || n_keep > T) return CIMPC_ERR_INVALID;
+    if ((long long)laps * T > (1 << 30)) return CIMPC_ERR_INVALID;
+    const PlantModel& M = buf.M;
+    const int nq = M.nq, nu = M.nu, nr = M.nq + M.nc + M.nb();
+    if (nu < 1 || n_cols < 2 * nq + nu || !plant_riccati_fits(nq, nu)) return CIMPC_ERR_INVALID;
+    const size_t n = (size_t)2 * nq, m = (size_t)nu, nn = n * n, mm = m * m, nB = (size_t)B;
+    // the staging buffers, in the order of the argument list
+    const size_t i_Q = (size_t)n_Q * nn, i_R = (size_t)n_R * mm, i_q = q ? (size_t)(T + 1) * nB * n : 0, i_r = r ? (size_t)T * nB * m : 0;
+    const size_t o_Qf = i_Q, o_R = o_Qf + nn, o_q = o_R + i_R, o_r = o_q + i_q, n_in = o_r + i_r;
+    const size_t n_K = (size_t)n_keep * nB * m * n, n_k = k ? (size_t)n_keep * nB * m : 0, n_P = P0 ? nB * nn : 0, n_p = p0 ? nB * n : 0,
+                 n_V = dV ? nB * 2 : 0;
+    const size_t o_k = n_K, o_P = o_k + n_k, o_p = o_P + n_P, o_V = o_p + n_p, o_st = o_V + n_V, n_out = o_st + nB;      // 2 B ints in B doubles
+    std::vector<double> up(n_in);
+    const std::unique_ptr<double[]> out(new double[n_out]);      // not value-initialized: K alone is 36 MB at quadruped B = 256, T = 100
+    std::memcpy(up.data(), Q, i_Q * sizeof(double));
+    std::memcpy(up.data() + o_Qf, Qf, nn * sizeof(double));
+    std::memcpy(up.data() + o_R, R, i_R * sizeof(double));
+    if (q) std::memcpy(up.data() + o_q, q, i_q * sizeof(double));
+    if (r) std::memcpy(up.data() + o_r, r, i_r * sizeof(double));
+    const size_t lds = plant_riccati_lds(nq, nu);
+    std::lock_guard<std::mutex> lock(g_plant_mu);
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
+    if (cur != buf.device && hipSetDevice(buf.device) != hipSuccess) return CIMPC_ERR_HIP;
+    bool ok = false;
+    PlantWs* ws = plant_ws_open(buf.device);
+    RiccatiWs& W = g_riccati_ws[buf.device];
+    if (ws && plant_grow(&W.d_in, &W.cap_in, n_in) && plant_grow(&W.d_out, &W.cap_out, n_out)) {
+        hipStream_t st = ws->st;
+        double* I = W.d_in;
+        double* O = W.d_out;
+        int* d_status = reinterpret_cast<int*>(O + o_st);
+        ok = hipMemcpyAsync(I, up.data(), n_in * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+        if (ok) {
+            PlantRiccati L{buf.d_dz, buf.d_status, I, I + o_Qf, I + o_R, q ? I + o_q : nullptr, r ? I + o_r : nullptr,
+                           O, k ? O + o_k : nullptr, P0 ? O + o_P : nullptr, p0 ? O + o_p : nullptr, dV ? O + o_V : nullptr,
+                           d_status, d_status + B, B, T, nq, nu, nr, n_cols, laps, n_Q, n_R, n_keep, rho};
+            auto kernel = q ? plant_riccati_kernel<true> : plant_riccati_kernel<false>;
+            ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+            if (ok) {
+                hipLaunchKernelGGL(kernel, dim3(B), dim3(RIC_THREADS), lds, st, L);
+                ok = hipGetLastError() == hipSuccess;
+            }
+        }
+        if (ok) ok = hipMemcpyAsync(out.get(), O, n_out * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
+        ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
+    }
+    if (cur != buf.device) ok = (hipSetDevice(cur) == hipSuccess) && ok;
+    if (!ok) return CIMPC_ERR_HIP;
+    std::memcpy(K, out.get(), n_K * sizeof(double));
+    if (k) std::memcpy(k, out.get() + o_k, n_k * sizeof(double));
+    if (P0) std::memcpy(P0, out.get() + o_P, n_P * sizeof(double));
+    if (p0) std::memcpy(p0, out.get() + o_p, n_p * sizeof(double));
+    if (dV) std::memcpy(dV, out.get() + o_V, n_V * sizeof(double));
+    std::memcpy(status, out.get() + o_st, nB * sizeof(int));
+    std::memcpy(n_cut, reinterpret_cast<const int*>(out.get() + o_st) + B, nB * sizeof(int));
+    return CIMPC_OK;
+}

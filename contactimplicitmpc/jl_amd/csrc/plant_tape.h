@@ -40,8 +40,8 @@ int plant_rollout_to_tape(const PlantRolloutCall& call, PlantTapeBuffers* tape);
 
 }  // namespace cimpc
 
-// What a cimpc_plant_tape points to: plant_adjoint.hip makes and frees it, the reverse chain there and the forward chain of
-// plant_tangent.hip walk it.
+// What a cimpc_plant_tape points to: plant_adjoint.hip makes and frees it, the reverse chain there, the forward chain of
+// plant_tangent.hip and the LQ backward pass of plant_riccati.hip walk it.
 struct cimpc_plant_tape_s {
     cimpc::PlantTapeBuffers buf;      // the device memory, its device and model; buf.d_fb_K non-null: a closed-loop tape
     int model, B, T, n_cols;

@@ -15,8 +15,11 @@ every step (`cimpc_plant_rollout_feedback` and its kin; DESIGN.md section 3, ite
 respect to the gains and the reference states.  `RolloutTape.jvp` is the forward chain over the same tape (`cimpc_plant_tape_jvp`; DESIGN.md
 section 3, item 3d): tangents of the rollout's arguments, any number of directions per launch, to the tangents of the whole trajectory;
 `RolloutTape.transition` is the state-transition matrix of the rollout, and `rollout_torch` answers forward-mode autograd with it.
+`RolloutTape.lqr` is the LQ backward pass over the tape (`cimpc_plant_tape_lqr`): time-varying LQR gains, and with
+linear cost terms the feedforward, for every robot along the trajectory it took; `TapeGains.feedback` hands them back to `rollout_tape` as a `Feedback`.
 Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble
-solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain, tests/test_gpu_plant_tangent.py against restatements of the forward chain.
+solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain, tests/test_gpu_plant_tangent.py against restatements of the forward chain,
+tests/test_gpu_plant_riccati.py against restatements of the backward pass.
 """
 from __future__ import annotations
 
@@ -764,6 +767,88 @@ class RolloutTape:
             dq1[nq + i, :, i] = 1.0
         q = self._jvp_steps(2 * nq, dq0, dq1, rows=False)[0]
         return np.ascontiguousarray(np.concatenate([q[:, t1], q[:, t1 + 1]], axis=2).transpose(1, 2, 0))
+
+    # ---- the LQ backward pass ---------------------------------------------------------------------------------------------------------------
+    def lqr(self, Q, R, Qf=None, q=None, r=None, rho: float = 0.0, laps: int = 1, keep=None) -> "TapeGains":
+        """Time-varying LQR gains along the trajectory this tape recorded (`cimpc_plant_tape_lqr`): ONE launch,
+        a workgroup per robot walking the tape's blocks backwards; nothing but the weights goes up and the gains come down.  State
+        x_t = [q[t]; q[t+1]] (n = 2nq), control u_t (m = nu), A_t = [0 I; D1 D2], B_t = [0; Du] from the step's block (on a closed-loop tape
+        the plant's too: the tape's own gains play no part).  Q (n, n) or (T, n, n) and R (m, m) or (T, m, m) are shared by the robots; Qf
+        (n, n) defaults to Q (its last step's); q (T + 1, B, n) and r (T, B, m), both or neither, are the cost's linear terms (q[T] the
+        terminal one): with them the feedforward k, p0 and dV are computed, δu_t = k_t − K_t δx_t.  rho ≥ 0 is added to the diagonal of
+        Quu before it is factored; laps > 1 walks the tape that many times as a periodic chain (`gains.reference_gains`' N; without q, r)
+        and returns the last lap; keep (default T) is the number of leading steps whose gains come back.  A robot whose chain met a
+        singular or non-finite step has status[b] = that walk step (1-based) and zeros; nothing is raised for it."""
+        if self.closed:
+            raise ValueError("the tape is closed")
+        mid, nq, nu, nc, fd, nw = model_dims(self.model)
+        B, T, n, m = self.B, self.T, 2 * nq, nu
+        keep = T if keep is None else int(keep)
+        if (q is None) != (r is None):
+            raise ValueError("q and r go together")
+        if not 1 <= keep <= T:
+            raise ValueError(f"keep must be in 1 .. {T}")
+        if int(laps) < 1 or (int(laps) > 1 and q is not None):
+            raise ValueError("laps must be at least 1, and 1 with linear terms")
+        if not (np.isfinite(rho) and rho >= 0.0):
+            raise ValueError("rho must be finite and not negative")
+
+        def weight(a, k, what):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape not in ((k, k), (T, k, k)):
+                raise ValueError(f"{what} must be ({k}, {k}) or ({T}, {k}, {k}), got {a.shape}")
+            return np.ascontiguousarray(np.swapaxes(a, -1, -2)), (1 if a.ndim == 2 else T)      # column-major blocks
+        Qc, n_Q = weight(Q, n, "Q")
+        Rc, n_R = weight(R, m, "R")
+        Qf = (Qc if n_Q == 1 else Qc[T - 1]) if Qf is None else np.swapaxes(np.asarray(Qf, dtype=np.float64), -1, -2)
+        Qf = np.ascontiguousarray(Qf)
+        if Qf.shape != (n, n):
+            raise ValueError(f"Qf must be ({n}, {n})")
+        lin = q is not None
+        if lin:
+            q, r = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(r, dtype=np.float64)
+            if q.shape != (T + 1, B, n) or r.shape != (T, B, m):
+                raise ValueError(f"q must be ({T + 1}, {B}, {n}) and r ({T}, {B}, {m}), got {q.shape} and {r.shape}")
+        K = np.zeros((keep, B, n, m))
+        k, p0, dV = (np.zeros((keep, B, m)), np.zeros((B, n)), np.zeros((B, 2))) if lin else (None, None, None)
+        P0, status, n_cut = np.zeros((B, n, n)), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        rc = _lib.load().cimpc_plant_tape_lqr(self._handle, int(laps), n_Q, dp(Qc), dp(Qf), n_R, dp(Rc), dp(q), dp(r), float(rho), keep, dp(K), dp(k),
+                                              dp(P0), dp(p0), dp(dV), ip(status), ip(n_cut))
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_tape_lqr failed ({rc})")
+        return TapeGains(K=np.ascontiguousarray(K.transpose(0, 1, 3, 2)), k=k, P0=np.ascontiguousarray(P0.transpose(0, 2, 1)), p0=p0, dV=dV,
+                         status=status, n_cut=n_cut, N_sample=self._N_sample)
+
+
+@dataclasses.dataclass
+class TapeGains:
+    """What `RolloutTape.lqr` returns: K (keep, B, nu, 2nq), the gains of δu_t = k_t − K_t δx_t against x_t = [q[t]; q[t+1]]; P0 (B, 2nq, 2nq),
+    the value's quadratic at the first step; with linear terms k (keep, B, nu), p0 (B, 2nq) and dV (B, 2) = (Σ k'Qu, Σ ½ k'Quu k), else
+    None; status (B,): 0, or the 1-based walk step at which that robot's chain ended (its rows are zeros then); n_cut (B,): the steps of a
+    robot whose gradient status is 0 (zero blocks, walked through)."""
+    K: np.ndarray
+    k: object
+    P0: np.ndarray
+    p0: object
+    dV: object
+    status: np.ndarray
+    n_cut: np.ndarray
+    N_sample: int = 1
+
+    def feedback(self, q_traj) -> Feedback:
+        """The `Feedback` that applies these gains around the trajectory q_traj (T + 2, B, nq) they were computed on: K · N_sample (the
+        rollout applies K[k] / N_sample), x_ref[t] = [q_traj[t]; q_traj[t+1]], hold 1, n_sample 1.0 - the law's x_t is then
+        [q[t]; q[t+1]] and a step applies u_t = ū_t + K_t (x_ref[t] − x_t).  The first half of x_ref[t] is written as the law writes its
+        state, q[t+1] − 1.0 (q[t+1] − q[t]) (q[t] to a rounding), so that on q_traj itself the error is exactly zero and the closed loop
+        retraces it bit for bit.  With keep < T the last row is held from there on."""
+        q_traj = np.asarray(q_traj, dtype=np.float64)
+        keep, B = self.K.shape[:2]
+        if q_traj.ndim != 3 or q_traj.shape[0] < keep + 1 or q_traj.shape[1] != B or 2 * q_traj.shape[2] != self.K.shape[3]:
+            raise ValueError(f"q_traj must be (at least {keep + 1}, {B}, {self.K.shape[3] // 2}), got {q_traj.shape}")
+        x_ref = np.concatenate([q_traj[1:keep + 1] - 1.0 * (q_traj[1:keep + 1] - q_traj[:keep]), q_traj[1:keep + 1]], axis=2)
+        return Feedback(K=self.K * float(self.N_sample), x_ref=np.ascontiguousarray(x_ref), hold=1, n_sample=1.0)
 
 
 def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w_hold: int = 1, opts: InteriorPointOptions = SIM_OPTS,

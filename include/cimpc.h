@@ -610,6 +610,32 @@ int cimpc_plant_tape_jvp_feedback(cimpc_plant_tape tape, int n_dir, const double
                                   double* dq, double* dgamma, double* db, int* n_cut,
                                   const double* dxref_step, double* du_applied);
 
+/* ---- the LQ backward pass over a tape (csrc/plant_riccati.h): time-varying LQR gains along the path taken --
+ * Per robot, with the state x_t = [q[t]; q[t+1]] (n = 2nq), the control u_t (m = nu) and the tape block D_t, D1 = D_t[0:nq, 0:nq],
+ * D2 = D_t[0:nq, nq:2nq], Du = D_t[0:nq, 2nq:2nq+nu]:  A_t = [0 I; D1 D2], B_t = [0; Du] (the matrices of cimpc_reference_gains; a
+ * closed-loop tape's blocks are the plant's too: its own gains play no part).  The cost is
+ *     sum over t of 1/2 x_t'Q_t x_t + q_t'x_t + 1/2 u_t'R_t u_t + r_t'u_t,  terminal 1/2 x'Q_f x + q_T'x,   the law du_t = k_t - K_t dx_t.
+ * With P = Q_f, p = q_T, for the walk steps s = 1 .. laps T, t = (laps T - s) mod T:
+ *     Qu = r_t + B'p    Quu = R_t + B'PB    Qux = B'PA    G = Quu + rho I    K_t = G \ Qux    k_t = -(G \ Qu)   (LU, partial pivoting)
+ *     dV1 += k_t'Qu     dV2 += 1/2 k_t'Quu k_t     Acl = A - B K_t
+ *     p <- q_t - K_t'r_t - K_t'(R_t k_t) + Acl'(P (B k_t) + p)        P <- Q_t + K_t'R_t K_t + Acl'P Acl     (not symmetrized)
+ * and K_t, k_t of the last lap are kept for t < n_keep.  Every product runs over the nonzero blocks of A_t, B_t alone, every element one
+ * running sum in ascending index without fused multiply-adds (csrc/plant_riccati.h states the order); a robot's result does not
+ * depend by a bit on the robots that ride along.  A step whose gradient status is 0 has a zero block (A_t = [0 I; 0 0], B_t = 0): the
+ * chain walks through it and n_cut counts it.
+ *   In (host, column-major): Q n_Q x (n x n) and R n_R x (m x m), n_Q and n_R 1 or T, shared by the robots; Q_f n x n; q (T+1) x B x n
+ *   (q[T] = q_T) and r T x B x m, both or neither (NULL: a pure-gain call; then k, p0, dV must be NULL); rho >= 0; laps >= 1 (more than
+ *   one: the periodic chain of reference_gains' N, without q, r); n_keep in 1 .. T.
+ *   Out: K n_keep x B x (m x n); k n_keep x B x m, P0 B x (n x n), p0 B x n, dV B x 2 (each may be NULL); status B; n_cut B.
+ * A zero or non-finite pivot of G, or a non-finite K_t, k_t, P or p, ends THAT robot's chain: status[b] is the 1-based walk step s and the
+ * robot's outputs are zeros; status[b] = 0 otherwise.  The other robots and the return code are unaffected.  Validated first, without a
+ * device (CIMPC_ERR_INVALID: a null tape, Q, Q_f, R, K, status or n_cut; rho negative or not finite; laps, n_Q, n_R or n_keep out of
+ * range; one of q, r alone, or either with laps > 1; k, p0 or dV without q, r; a model without controls).  ONE upload, ONE launch, ONE
+ * read-back, on the tape's device, whichever is current, on the plant's private stream. */
+int cimpc_plant_tape_lqr(cimpc_plant_tape tape, int laps, int n_Q, const double* Q, const double* Qf, int n_R, const double* R,
+                         const double* q, const double* r, double rho, int n_keep,
+                         double* K, double* k, double* P0, double* p0, double* dV, int* status, int* n_cut);
+
 /* ---- cimpc_set_linearization_batch from (z, theta) alone: plant model `model` linearized at kappa (cimpc_plant_linearize's kernel and arguments;
  * z0 = z, th0 = theta) and the tables built from its output, all on the handle's device and stream;
  * nothing but z, theta and the terrains goes up, nothing but N status words comes back.  Equal bit for bit to

@@ -879,6 +879,47 @@ function plant_tape_jvp_feedback(tape::PlantTape; dq0::Union{Nothing,Array{Float
     return dq, dγ, db, n_cut, du_applied
 end
 
+# ---- the LQ backward pass over a tape: time-varying LQR gains along the path taken ------------------------------------------------------
+"""
+    plant_tape_lqr(tape, Q, R; Qf = nothing, q = nothing, r = nothing, ρ = 0.0, laps = 1, keep = nothing)
+        -> (K, k, P0, p0, dV, status, n_cut)
+
+`cimpc_plant_tape_lqr`: with x_t = [q[t]; q[t+1]] (n = 2nq), u_t (m = nu) and A_t = [0 I; D1 D2], B_t = [0; Du] from the tape's blocks, the
+gains of δu_t = k_t - K_t δx_t for the cost Σ ½ x'Q_t x + q_t'x + ½ u'R_t u + r_t'u with the terminal ½ x'Qf x + q_T'x, in ONE launch, a
+workgroup per robot.  Q: n x n or n x n x T and R: m x m or m x m x T are shared by the robots, Qf defaults to Q (its last step's); q:
+n x B x (T + 1) and r: m x B x T, both or neither; ρ >= 0 is added to the diagonal of Quu; laps > 1 walks the tape periodically (without
+q, r); keep (default T) leading steps come back.  Returns K: m x n x B x keep, P0: n x n x B, status and n_cut (B), and with q, r
+k: m x B x keep, p0: n x B, dV: 2 x B (nothing otherwise).  status[b] != 0: that robot's chain ended at that 1-based walk step (a
+singular or non-finite step) and its outputs are zeros.
+"""
+function plant_tape_lqr(tape::PlantTape, Q::Array{Float64}, R::Array{Float64}; Qf::Union{Nothing,Matrix{Float64}} = nothing,
+                        q::Union{Nothing,Array{Float64,3}} = nothing, r::Union{Nothing,Array{Float64,3}} = nothing, ρ::Real = 0.0,
+                        laps::Integer = 1, keep::Union{Nothing,Integer} = nothing)
+    tape.handle != C_NULL || error("plant_tape_lqr: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, n, m = tape.B, tape.T, 2 * nq, nu
+    n_keep = keep === nothing ? T : Int(keep)
+    (size(Q) == (n, n) || size(Q) == (n, n, T)) || error("plant_tape_lqr: Q must be $n x $n or $n x $n x $T")
+    (size(R) == (m, m) || size(R) == (m, m, T)) || error("plant_tape_lqr: R must be $m x $m or $m x $m x $T")
+    n_Q = ndims(Q) == 2 ? 1 : T; n_R = ndims(R) == 2 ? 1 : T
+    Qend = Qf === nothing ? (ndims(Q) == 2 ? Q : Q[:, :, T]) : Qf
+    size(Qend) == (n, n) || error("plant_tape_lqr: Qf must be $n x $n")
+    (q === nothing) == (r === nothing) || error("plant_tape_lqr: q and r go together")
+    (q === nothing || (size(q) == (n, B, T + 1) && size(r) == (m, B, T))) || error("plant_tape_lqr: q must be $n x $B x $(T + 1) and r $m x $B x $T")
+    lin = q !== nothing
+    K = zeros(m, n, B, n_keep); P0 = zeros(n, n, B); status = zeros(Cint, B); n_cut = zeros(Cint, B)
+    k = lin ? zeros(m, B, n_keep) : nothing; p0 = lin ? zeros(n, B) : nothing; dV = lin ? zeros(2, B) : nothing
+    p(a) = a === nothing ? C_NULL : pointer(a)
+    GC.@preserve Qend q r k p0 dV begin
+        pQf, pq, pr, pk, pp, pV = p(Qend), p(q), p(r), p(k), p(p0), p(dV)
+        check(@ccall LIB.cimpc_plant_tape_lqr(tape.handle::Ptr{Cvoid}, laps::Cint, n_Q::Cint, Q::Ptr{Cdouble}, pQf::Ptr{Cdouble}, n_R::Cint,
+                                              R::Ptr{Cdouble}, pq::Ptr{Cdouble}, pr::Ptr{Cdouble}, ρ::Cdouble, n_keep::Cint, K::Ptr{Cdouble},
+                                              pk::Ptr{Cdouble}, P0::Ptr{Cdouble}, pp::Ptr{Cdouble}, pV::Ptr{Cdouble}, status::Ptr{Cint},
+                                              n_cut::Ptr{Cint})::Cint)
+    end
+    return K, k, P0, p0, dV, status, n_cut
+end
+
 # ---- the plant models linearized on the device: the `LinearizedStep` triple of N knots in one call (linearized_step.jl:10-31) --------
 """
     plant_linearize(model, z, θ, κ; terrain = nothing) -> (r0, rz0, rθ0)
