@@ -67,6 +67,11 @@ class Feedback(C.Structure):
     _fields_ = [("K", _dp), ("x_ref", _dp), ("K_f", C.c_int), ("n_f", C.c_int), ("hold_f", C.c_int), ("n_sample", C.c_double)]
 
 
+class TrackingCost(C.Structure):
+    """cimpc_tracking_cost: the weights and targets of a tracking cost as the library reads them."""
+    _fields_ = [("Q", _dp), ("Qf", _dp), ("R", _dp), ("x_goal", _dp), ("u_goal", _dp), ("n_Q", C.c_int), ("n_R", C.c_int), ("n_x", C.c_int)]
+
+
 # the 25 parameters of cimpc_plant_rollout, which the gradient, tape and closed-loop entry points extend
 _ROLLOUT_ARGS = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int,
                  _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), _dp, _dp, _dp, _ip, _ip]
@@ -119,6 +124,10 @@ SIGNATURES = {
     "cimpc_plant_tape_jvp": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "cimpc_plant_tape_jvp_feedback": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),
     "cimpc_plant_tape_lqr": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "cimpc_plant_tracking_cost": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TrackingCost), _dp, _dp, _dp, _dp, _dp]),
+    "cimpc_plant_tape_linesearch": (C.c_int, [_h, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double,
+                                              C.POINTER(IpOpts), _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_double, C.POINTER(TrackingCost), C.c_double,
+                                              _dp, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _ip, C.POINTER(_h)]),
     "cimpc_plant_tape_dims": (C.c_int, [_h, _ip, _ip, _ip, _ip]),
     "cimpc_plant_tape_destroy": (C.c_int, [_h]),
     "cimpc_tvlqr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),

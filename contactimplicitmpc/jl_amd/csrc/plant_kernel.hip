@@ -22,6 +22,7 @@
 #include "plant_rollout_plan.h"
 #include "plant_sensitivity.h"
 #include "plant_sensitivity_plan.h"
+#include "plant_step_launch.h"
 #include "plant_tape.h"
 #include "plant_workspace.h"
 
@@ -302,6 +303,29 @@ PlantWs g_plant_ws[PLANT_MAX_DEVICES];
 std::mutex g_plant_mu;
 }  // namespace cimpc
 
+// The chunked launches of plant_step_launch.h: the LOOP instantiation with a.fb.K, the open-loop one without.
+bool cimpc::plant_step_chunks(const PlantModel& M, bool rough, const cimpc_ip_opts& opts, int B, int T, int steps_per_launch, const PlantStepArrays& a,
+                              const cimpc_terrain* d_ter, int n_terrain, hipStream_t st) {
+    PlantOpts o{opts.r_tol, opts.kappa_tol, std::isinf(opts.undercut) ? 0.0 : opts.kappa_tol / opts.undercut, opts.eps_min,
+                opts.ls_scale, opts.stall_alpha, opts.max_iter, opts.max_ls};
+    PlantRollout R{a.q, a.u, a.w, a.mu, a.gamma, a.b, a.status, a.iters, a.mu0, a.h, 0, 0, a.K_u, a.n_u, a.hold_u, a.K_w, a.n_w, a.hold_w, a.n_mu,
+                   a.z, a.fb, a.u_applied, a.fb_err};
+    const bool loop = a.fb.K != nullptr;
+    bool ok = true;
+    for (int k = 0; ok && k < rollout_chunk_count(T, steps_per_launch); ++k) {
+        const RolloutChunk ch = rollout_chunk(T, steps_per_launch, k);
+        R.t0 = ch.t0; R.n = ch.n;
+        ok = plant_visit_instance(M, rough, true, [&](auto tag) {
+            using I = decltype(tag);
+            constexpr int NT = step_threads(I::NZ);
+            auto kernel = loop ? plant_step_kernel<I::NZ, NT, I::GROUND, true> : plant_step_kernel<I::NZ, NT, I::GROUND, false>;
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(NT), 0, st, M, o, B, R, rough ? d_ter : nullptr, rough ? n_terrain : 0);
+            return hipGetLastError() == hipSuccess;
+        });
+    }
+    return ok;
+}
+
 namespace {
 // Every entry point, on the call it filled in (plant_rollout_call.h): check it (no device needed), pick the device, lay the call out in
 // the workspace, grow, stage inputs on the device's private stream, launch the rollout's chunks back to back (plant_rollout_plan.h; the
@@ -323,9 +347,6 @@ int plant_rollout_impl(const cimpc::PlantRolloutCall& c, cimpc::PlantTapeBuffers
     if (plant_rollout_check(c, &M, &rough) != CIMPC_OK || (tape != nullptr) != (c.grad && c.grad->tape)) return CIMPC_ERR_INVALID;
     int dev = 0;
     if (!plant_current_device(&dev)) return CIMPC_ERR_NO_DEVICE;
-    const cimpc_ip_opts* opts = c.opts;
-    PlantOpts o{opts->r_tol, opts->kappa_tol, std::isinf(opts->undercut) ? 0.0 : opts->kappa_tol / opts->undercut, opts->eps_min,
-                opts->ls_scale, opts->stall_alpha, opts->max_iter, opts->max_ls};
     const PlantRolloutLayout L = plant_rollout_layout(M, c);
     const int B = c.B, T = c.T;
     const cimpc_feedback* f = c.loop ? c.loop->fb : nullptr;
@@ -370,20 +391,10 @@ int plant_rollout_impl(const cimpc::PlantRolloutCall& c, cimpc::PlantTapeBuffers
     if (rough) up(W.d_ter, c.terrain, (size_t)c.n_terrain);
     if (f) { up(d_fk, f->K, L.fb_K.n); up(d_fx, f->x_ref, L.x_ref.n); }
     const bool has_w = c.w.rows != nullptr;
-    PlantRollout R{dq, du, has_w ? dw : nullptr, L.mu.n ? dmu : nullptr, dg, db, d_st, d_it, c.mu[0], c.h, 0, 0, c.u.K, c.u.n, c.u.hold,
-                   has_w ? c.w.K : 1, has_w ? c.w.n : 1, has_w ? c.w.hold : 1, c.n_mu, c.grad ? W.d_z : nullptr, PlantFeedback{}, nullptr, nullptr};
+    PlantStepArrays R{dq, du, has_w ? dw : nullptr, L.mu.n ? dmu : nullptr, dg, db, d_st, d_it, c.mu[0], c.h, c.u.K, c.u.n, c.u.hold,
+                      has_w ? c.w.K : 1, has_w ? c.w.n : 1, has_w ? c.w.hold : 1, c.n_mu, c.grad ? W.d_z : nullptr, PlantFeedback{}, nullptr, nullptr};
     if (f) { R.fb = PlantFeedback{d_fk, d_fx, f->K_f, f->n_f, f->hold_f, f->n_sample}; R.u_applied = d_ua; R.fb_err = d_fe; }
-    for (int k = 0; ok && k < rollout_chunk_count(T, c.steps_per_launch); ++k) {
-        const RolloutChunk ch = rollout_chunk(T, c.steps_per_launch, k);
-        R.t0 = ch.t0; R.n = ch.n;
-        ok = plant_visit_instance(M, rough, true, [&](auto tag) {
-            using I = decltype(tag);
-            constexpr int NT = step_threads(I::NZ);
-            auto kernel = f ? plant_step_kernel<I::NZ, NT, I::GROUND, true> : plant_step_kernel<I::NZ, NT, I::GROUND, false>;
-            hipLaunchKernelGGL(kernel, dim3(B), dim3(NT), 0, st, M, o, B, R, rough ? W.d_ter : nullptr, rough ? c.n_terrain : 0);
-            return hipGetLastError() == hipSuccess;
-        });
-    }
+    ok = ok && plant_step_chunks(M, rough, *c.opts, B, T, c.steps_per_launch, R, rough ? W.d_ter : nullptr, rough ? c.n_terrain : 0, st);
     if (ok && c.grad) {
         PlantSensSource src{W.d_z, nullptr, dq, du, R.w, R.mu, d_st, R.mu0, c.h, B, R.K_u, R.n_u, R.hold_u, R.K_w, R.n_w, R.hold_w, c.n_mu};
         if (f) { src.u = d_ua; src.K_u = T; src.n_u = B; src.hold_u = 1; }      // the controls the steps applied

@@ -1,0 +1,333 @@
+// The forward pass of an iLQR iteration through contact (DESIGN.md sections 3, item 3f, and 5.5): n_alpha step lengths of every robot
+// in ONE closed-loop rollout of n_alpha x B robots, their costs, the per-robot choice, and the tape of the chosen trajectories.
+//
+//   cimpc_plant_tape_linesearch   the B-robot inputs up once; plant_ls_expand_kernel writes what the step kernel reads for the
+//                                 n_alpha B candidates; the closed-loop step kernel's chunks (plant_step_launch.h); plant_ls_cost_kernel
+//                                 (J and convergence per candidate); plant_ls_gather_kernel (acceptance, choice, the chosen candidates'
+//                                 rows compacted to B robots, lin_q and lin_r on them); ONE sensitivity launch over T x B entries into the
+//                                 new tape; plant_ls_restore_kernel (the parent's blocks for a robot without an acceptable candidate);
+//                                 one read-back, one synchronize
+//   cimpc_plant_tracking_cost     plant_cost.h on the host with a team of one
+//
+// The kernels here move rows and run the short ordered chains of plant_cost.h; a wavefront per workgroup.  The time of a line search is
+// the step kernel's.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+// No fused multiply-adds in this translation unit: the cost rounds as the float64 restatement of the definition does.
+#pragma clang fp contract(off)
+
+#include "../../../include/cimpc.h"
+#include "gains.h"
+#include "plant_cost.h"
+#include "plant_model.h"
+#include "plant_rollout_call.h"
+#include "plant_sensitivity.h"
+#include "plant_step_launch.h"
+#include "plant_tape.h"
+#include "plant_workspace.h"
+
+namespace cimpc {
+
+constexpr int LS_THREADS = 64;
+constexpr int LS_MAX_WORK = (int)plant_cost_work_doubles(PLANT_MAX_Q, PLANT_MAX_U);
+
+// the wavefront as the team of plant_cost.h
+struct PlantCostWave {
+    __device__ int rank() const { return threadIdx.x; }
+    __device__ int size() const { return LS_THREADS; }
+    __device__ void sync() const { __syncthreads(); }
+};
+
+// Entry e = t NB + r of the candidates' inputs, r = c B + b, from the parent's rows of robot b (all device memory): the open-loop row, the
+// gain block, the x_ref row; at t = 0 also trajectory rows 0 and 1, mu (given per robot) and the w schedule (given per robot).
+struct PlantLsExpand {
+    const double *q_nom, *u_nom, *k, *K, *w, *mu, *alpha;      // w, mu: null when shared (the step kernel then reads the parent's)
+    double *q, *u, *fb_K, *x_ref, *w_out, *mu_out;
+    int B, NB, T, nq, nu, nw, K_w;
+};
+
+__global__ __launch_bounds__(LS_THREADS) void plant_ls_expand_kernel(PlantLsExpand E) {
+    const int e = blockIdx.x, lane = threadIdx.x;
+    if (e >= E.T * E.NB) return;
+    const int t = e / E.NB, r = e % E.NB, c = r / E.B, b = r % E.B, nq = E.nq, nu = E.nu, kk = nu * 2 * nq;
+    const size_t from = (size_t)t * E.B + b;
+    for (int i = lane; i < nu; i += LS_THREADS) E.u[(size_t)e * nu + i] = plant_candidate_control(E.u_nom[from * nu + i], E.alpha[c], E.k[from * nu + i]);
+    for (int i = lane; i < kk; i += LS_THREADS) E.fb_K[(size_t)e * kk + i] = E.K[from * kk + i];
+    const double *q0 = E.q_nom + from * nq, *q1 = E.q_nom + (from + E.B) * nq;
+    for (int j = lane; j < 2 * nq; j += LS_THREADS) E.x_ref[(size_t)e * 2 * nq + j] = plant_candidate_target(q0, q1, nq, j);
+    if (t != 0) return;
+    for (int i = lane; i < nq; i += LS_THREADS) {
+        E.q[(size_t)r * nq + i] = q0[i];
+        E.q[((size_t)E.NB + r) * nq + i] = q1[i];
+    }
+    if (E.mu && lane == 0) E.mu_out[r] = E.mu[b];
+    if (E.w)
+        for (int i = lane; i < E.K_w * E.nw; i += LS_THREADS) {
+            const int row = i / E.nw, j = i % E.nw;
+            E.w_out[((size_t)row * E.NB + r) * E.nw + j] = E.w[((size_t)row * E.B + b) * E.nw + j];
+        }
+}
+
+// J of candidate robot r and whether its T steps converged, from the rollout's own buffers
+struct PlantLsCost {
+    PlantCost C;
+    const double *q, *u_applied;      // (T + 2) x NB x nq, T x NB x nu
+    const int* status;                // T x NB
+    double* J;                        // NB
+    int* conv;                        // NB
+    int B, NB;
+};
+
+__global__ __launch_bounds__(LS_THREADS) void plant_ls_cost_kernel(PlantLsCost P) {
+    __shared__ double work[LS_MAX_WORK];
+    const int r = blockIdx.x, lane = threadIdx.x;
+    if (r >= P.NB) return;
+    const int nq = P.C.nq, nu = P.C.nu;
+    PlantCostWave team;
+    const double J = plant_cost_trajectory(P.C, P.C.n_x == 1 ? 0 : r % P.B, P.q + (size_t)r * nq, (size_t)P.NB * nq, P.u_applied + (size_t)r * nu,
+                                           (size_t)P.NB * nu, work, nullptr, 0, nullptr, 0, team);
+    int all = 1;
+    for (int t = lane; t < P.C.T; t += LS_THREADS) all &= P.status[(size_t)t * P.NB + r] != 0;
+    all = __syncthreads_and(all);
+    if (lane == 0) { P.J[r] = J; P.conv[r] = all; }
+}
+
+// Row t (0 .. T+1) of robot b's chosen candidate, compacted to B robots; every workgroup of a robot finds the choice again from J and conv
+// (n_alpha <= 64 tests), the one of row 0 stores it with the acceptability flags.
+struct PlantLsGather {
+    PlantCost C;
+    const double *q, *z, *u_applied, *gamma, *b;      // the candidates': NB robots
+    const int *status, *iters, *conv;
+    const double *J, *J_nom, *dV, *alpha;
+    double armijo;
+    int n_alpha;
+    int *ok, *choice;
+    double *Cq, *Cz, *Cu, *Cg, *Cb;                   // the chosen: B robots
+    int *Cst, *Cit;
+    double *lin_q, *lin_r;
+    int B, NB, nc, nb, nz;
+};
+
+__global__ __launch_bounds__(LS_THREADS) void plant_ls_gather_kernel(PlantLsGather G) {
+    __shared__ double work[LS_MAX_WORK];
+    __shared__ int s_ok[PLANT_LS_MAX_ALPHA];
+    const int e = blockIdx.x, lane = threadIdx.x, T = G.C.T, B = G.B;
+    if (e >= (T + 2) * B) return;
+    const int t = e / B, b = e % B, nq = G.C.nq, nu = G.C.nu;
+    for (int c = lane; c < G.n_alpha; c += LS_THREADS)
+        s_ok[c] = plant_candidate_acceptable(G.conv[c * B + b] != 0, G.J[c * B + b], G.J_nom[b], G.armijo, G.alpha[c], G.dV[2 * b], G.dV[2 * b + 1]) ? 1 : 0;
+    __syncthreads();
+    const int choice = plant_linesearch_choice(G.J + b, (size_t)B, s_ok, 1, G.n_alpha);
+    if (t == 0) {
+        for (int c = lane; c < G.n_alpha; c += LS_THREADS) G.ok[c * B + b] = s_ok[c];
+        if (lane == 0) G.choice[b] = choice;
+    }
+    const int r = (choice < 0 ? 0 : choice) * B + b;
+    const size_t from = (size_t)t * G.NB + r, to = (size_t)t * B + b;
+    for (int i = lane; i < nq; i += LS_THREADS) G.Cq[to * nq + i] = G.q[from * nq + i];
+    if (t > T) return;
+    if (t < T) {
+        for (int i = lane; i < G.nz; i += LS_THREADS) G.Cz[to * G.nz + i] = G.z[from * G.nz + i];
+        for (int i = lane; i < nu; i += LS_THREADS) G.Cu[to * nu + i] = G.u_applied[from * nu + i];
+        for (int i = lane; i < G.nc; i += LS_THREADS) G.Cg[to * G.nc + i] = G.gamma[from * G.nc + i];
+        for (int i = lane; i < G.nb; i += LS_THREADS) G.Cb[to * G.nb + i] = G.b[from * G.nb + i];
+        if (lane == 0) { G.Cst[to] = G.status[from]; G.Cit[to] = G.iters[from]; }
+    }
+    PlantCostWave team;
+    (void)plant_cost_stage(G.C, t, G.C.n_x == 1 ? 0 : b, G.q + from * nq, G.q + (from + G.NB) * nq, t < T ? G.u_applied + from * nu : nullptr, work,
+                           G.lin_q + to * 2 * nq, t < T ? G.lin_r + to * nu : nullptr, team);
+}
+
+// Entry e = t B + b of the new tape gets the parent's block and status where robot b has no acceptable candidate
+__global__ __launch_bounds__(LS_THREADS) void plant_ls_restore_kernel(const int* choice, const double* parent_dz, const int* parent_status, double* dz,
+                                                                     int* status, int B, int T, int block) {
+    const int e = blockIdx.x;
+    if (e >= T * B || choice[e % B] >= 0) return;
+    for (int i = threadIdx.x; i < block; i += LS_THREADS) dz[(size_t)e * block + i] = parent_dz[(size_t)e * block + i];
+    if (threadIdx.x == 0) status[e] = parent_status[e];
+}
+
+namespace {
+// grow-only device buffers of the entry, per device, next to the plant workspace whose buffers (the candidates' rollout), stream and
+// mutex it uses: the B-robot inputs, the B-robot outputs with J, and the integer outputs
+struct LineSearchWs { double *d_in = nullptr, *d_out = nullptr; int* d_int = nullptr; size_t cap_in = 0, cap_out = 0, cap_int = 0; };
+LineSearchWs g_linesearch_ws[PLANT_MAX_DEVICES];
+
+PlantCost plant_cost_of(const cimpc_tracking_cost& c, int T, int nq, int nu) {
+    return PlantCost{c.Q, c.Qf, c.R, c.x_goal, c.u_goal, c.n_Q, c.n_R, c.n_x, T, nq, nu};
+}
+}  // namespace
+
+}  // namespace cimpc
+
+// ---- C ABI -------------------------------------------------------------------------------------------------------------
+extern "C" int cimpc_plant_tracking_cost(int nq, int nu, int B, int T, const cimpc_tracking_cost* cost, const double* q, const double* u_applied,
+                                         double* J, double* lin_q, double* lin_r) {
+    using namespace cimpc;
+    if (!cost || !q || !u_applied || !J || nq < 1 || nu < 1 || B < 1 || T < 1) return CIMPC_ERR_INVALID;
+    const PlantCost C = plant_cost_of(*cost, T, nq, nu);
+    if (!plant_cost_valid(C, B)) return CIMPC_ERR_INVALID;
+    std::vector<double> work(plant_cost_work_doubles(nq, nu));
+    PlantCostSolo team;
+    const size_t n = (size_t)2 * nq;
+    for (int b = 0; b < B; ++b)
+        J[b] = plant_cost_trajectory(C, C.n_x == 1 ? 0 : b, q + (size_t)b * nq, (size_t)B * nq, u_applied + (size_t)b * nu, (size_t)B * nu, work.data(),
+                                     lin_q ? lin_q + b * n : nullptr, B * n, lin_r ? lin_r + (size_t)b * nu : nullptr, (size_t)B * nu, team);
+    return CIMPC_OK;
+}
+
+extern "C" int cimpc_plant_tape_linesearch(cimpc_plant_tape tape, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                           const double* q_nom, const double* u_nom, const double* w, int K_w, int n_w, int hold_w,
+                                           const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, const double* K, const double* k,
+                                           const double* dV, const double* J_nom, int n_alpha, const double* alpha, double armijo,
+                                           const cimpc_tracking_cost* cost, double reg, double* J, int* ok, int* choice, double* q,
+                                           double* u_applied, double* gamma, double* b, int* status, int* iters, double* lin_q, double* lin_r,
+                                           int* grad_status, cimpc_plant_tape* new_tape) {
+    using namespace cimpc;
+    // every refusal leaves its reason where cimpc_last_error(NULL) finds it; what needs no tape is tested before the tape is looked at
+    auto refuse = [](const std::string& why) { set_global_error("cimpc_plant_tape_linesearch: " + why); return CIMPC_ERR_INVALID; };
+    if (!new_tape) return refuse("null new_tape");
+    *new_tape = nullptr;
+    const std::pair<const char*, const void*> required[] = {
+        {"tape", tape}, {"q_nom", q_nom}, {"u_nom", u_nom}, {"mu", mu}, {"opts", opts}, {"K", K}, {"k", k}, {"dV", dV}, {"J_nom", J_nom}, {"alpha", alpha},
+        {"cost", cost}, {"J", J}, {"ok", ok}, {"choice", choice}, {"q", q}, {"u_applied", u_applied}, {"gamma", gamma}, {"b", b}, {"status", status},
+        {"iters", iters}, {"lin_q", lin_q}, {"lin_r", lin_r}, {"grad_status", grad_status}};
+    for (const auto& [name, p] : required) if (!p) return refuse(std::string("null ") + name);
+    if (const char* why = plant_linesearch_refusal(n_alpha, alpha, armijo)) return refuse(why);
+    if (const char* why = plant_cost_pointers(plant_cost_of(*cost, 1, 1, 1))) return refuse(why);
+    if (!(h > 0.0)) return refuse("h not positive");
+    const PlantTapeBuffers& parent = tape->buf;
+    const int B = tape->B, T = tape->T, n_cols = tape->n_cols;
+    if (parent.device < 0 || parent.device >= PLANT_MAX_DEVICES || !parent.d_dz || !parent.d_status) return refuse("a closed tape");
+    if (!plant_linesearch_fits(n_alpha, B, T)) return refuse("n_alpha B T beyond an int");
+    // everything cimpc_plant_rollout_tape validates for the B robots of the parent, on the arrays that stand in for its arguments
+    const PlantRolloutCall parent_call{.model = tape->model, .B = B, .T = T, .steps_per_launch = steps_per_launch, .n_terrain = n_terrain, .terrain = terrain,
+                                       .q0 = q_nom, .q1 = q_nom, .u = {u_nom, T, B, 1}, .w = {w, K_w, n_w, hold_w}, .mu = mu, .n_mu = n_mu, .h = h,
+                                       .opts = opts, .q = q, .gamma = gamma, .b = b, .status = status, .iters = iters,
+                                       .grad = PlantRolloutGrad{reg, n_cols, nullptr, nullptr, grad_status, true}};
+    PlantModel M{};
+    bool rough = false;
+    if (plant_rollout_check(parent_call, &M, &rough) != CIMPC_OK) return refuse("an argument that cimpc_plant_rollout_tape refuses for the tape's B robots");
+    const int nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb(), nz = M.nz(), nw = M.nw, nr = nq + nc + nb, NB = n_alpha * B;
+    if (M.kind != parent.M.kind || nq != parent.M.nq || nu < 1 || 2 * nq > nz) return refuse("a model without controls or not the tape's");
+    PlantCost C = plant_cost_of(*cost, T, nq, nu);
+    if (const char* why = plant_cost_sizes(C, B)) return refuse(why);
+    const size_t TB = (size_t)T * B, n = (size_t)2 * nq, kk = (size_t)nu * n, block = (size_t)nr * n_cols;
+    // the inputs the candidates' law is made of are finite, as cimpc_plant_rollout_feedback asks of K and x_ref
+    auto finite = [](const double* a, size_t cnt) { for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(a[i])) return false; return true; };
+    if (!finite(K, TB * kk)) return refuse("a non-finite entry of K");
+    if (!finite(k, TB * nu)) return refuse("a non-finite entry of k");
+    if (!finite(q_nom, (size_t)(T + 2) * B * nq)) return refuse("a non-finite entry of q_nom");
+    if (!finite(u_nom, TB * nu)) return refuse("a non-finite entry of u_nom");
+    // the candidates' rollout in the plant workspace, laid out as a closed-loop tape call of NB robots lays itself out
+    const bool w_each = w && n_w != 1, mu_each = n_mu != 1;
+    const cimpc_feedback fb_shape{K, K, T, NB, 1, 1.0};
+    const PlantRolloutCall cand_call{.model = tape->model, .B = NB, .T = T, .steps_per_launch = steps_per_launch, .n_terrain = 0, .terrain = nullptr,
+                                     .q0 = q_nom, .q1 = q_nom, .u = {u_nom, T, NB, 1}, .w = {w, K_w, w_each ? NB : 1, hold_w}, .mu = mu,
+                                     .n_mu = mu_each ? NB : 1, .h = h, .opts = opts, .q = q, .gamma = gamma, .b = b, .status = status, .iters = iters,
+                                     .grad = PlantRolloutGrad{reg, n_cols, nullptr, nullptr, grad_status, true},
+                                     .loop = PlantRolloutLoop{&fb_shape, u_applied, nullptr}};
+    const PlantRolloutLayout L = plant_rollout_layout(M, cand_call);
+    // the B-robot inputs in d_in, in the order they go up
+    size_t at = 0;
+    auto next = [&at](size_t cnt) { const size_t o = at; at += cnt; return o; };
+    const size_t i_q = next((size_t)(T + 2) * B * nq), i_u = next(TB * nu), i_k = next(TB * nu), i_K = next(TB * kk),
+                 i_w = next(w_each ? (size_t)K_w * B * nw : 0), i_mu = next(mu_each ? (size_t)B : 0), i_dV = next((size_t)2 * B), i_Jn = next((size_t)B),
+                 i_al = next((size_t)n_alpha), i_Q = next((size_t)C.n_Q * n * n), i_Qf = next(n * n), i_R = next((size_t)C.n_R * nu * nu),
+                 i_xg = next((size_t)(T + 1) * C.n_x * n), i_ug = next((size_t)T * C.n_x * nu), n_in = at;
+    at = 0;      // J and the chosen candidates' rows in d_out, in the order they come back
+    const size_t o_J = next((size_t)NB), o_q = next((size_t)(T + 2) * B * nq), o_u = next(TB * nu), o_g = next(TB * nc), o_b = next(TB * nb),
+                 o_lq = next((size_t)(T + 1) * B * n), o_lr = next(TB * nu), o_z = next(TB * nz), n_out = at;
+    at = 0;      // the integers
+    const size_t j_ok = next((size_t)NB), j_ch = next((size_t)B), j_st = next(TB), j_it = next(TB), j_conv = next((size_t)NB), n_int = at;
+    std::vector<cimpc_terrain> ter;      // the candidates' terrains: robot b's for every c
+    const bool ter_each = rough && n_terrain != 1;
+    if (ter_each) for (int c = 0; c < n_alpha; ++c) ter.insert(ter.end(), terrain, terrain + B);
+    const int n_ter = !rough ? 0 : ter_each ? NB : 1;
+
+    std::lock_guard<std::mutex> lock(g_plant_mu);
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
+    const int dev = parent.device;
+    if (cur != dev && hipSetDevice(dev) != hipSuccess) return CIMPC_ERR_HIP;
+    bool ok_ = false;
+    PlantTapeBuffers buf;
+    PlantWs* ws = plant_ws_open(dev);
+    LineSearchWs& S = g_linesearch_ws[dev];
+    if (ws && plant_grow(&ws->d_in, &ws->cap_in, L.need_in) && plant_grow(&ws->d_out, &ws->cap_out, L.need_out) && plant_grow(&ws->d_st, &ws->cap_st, L.need_st) &&
+        plant_grow(&ws->d_ter, &ws->cap_ter, (size_t)n_ter) && plant_grow(&ws->d_z, &ws->cap_z, L.need_z) && plant_grow(&ws->d_fb, &ws->cap_fb, L.need_fb) &&
+        plant_grow(&S.d_in, &S.cap_in, n_in) && plant_grow(&S.d_out, &S.cap_out, n_out) && plant_grow(&S.d_int, &S.cap_int, n_int) &&
+        hipMalloc((void**)&buf.d_dz, TB * block * sizeof(double)) == hipSuccess) {      // the new tape's memory, the last to be allocated
+        if (hipMalloc((void**)&buf.d_status, TB * sizeof(int)) != hipSuccess) buf.d_status = nullptr;
+        buf.device = dev; buf.M = M;
+        PlantWs& W = *ws;
+        hipStream_t st = W.st;
+        ok_ = buf.d_status != nullptr;
+        auto up = [&](auto* d, const auto* hsrc, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(d, hsrc, cnt * sizeof(*d), hipMemcpyHostToDevice, st) == hipSuccess; };
+        auto down = [&](auto* hdst, const auto* d, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(hdst, d, cnt * sizeof(*d), hipMemcpyDeviceToHost, st) == hipSuccess; };
+        double *I = S.d_in, *O = S.d_out;
+        int* N = S.d_int;
+        up(I + i_q, q_nom, (size_t)(T + 2) * B * nq); up(I + i_u, u_nom, TB * nu); up(I + i_k, k, TB * nu); up(I + i_K, K, TB * kk);
+        if (w_each) up(I + i_w, w, (size_t)K_w * B * nw);
+        if (mu_each) up(I + i_mu, mu, (size_t)B);
+        up(I + i_dV, dV, (size_t)2 * B); up(I + i_Jn, J_nom, (size_t)B); up(I + i_al, alpha, (size_t)n_alpha);
+        up(I + i_Q, C.Q, (size_t)C.n_Q * n * n); up(I + i_Qf, C.Qf, n * n); up(I + i_R, C.R, (size_t)C.n_R * nu * nu);
+        up(I + i_xg, C.x_goal, (size_t)(T + 1) * C.n_x * n); up(I + i_ug, C.u_goal, (size_t)T * C.n_x * nu);
+        double *dq = W.d_in + L.q.at, *du = W.d_in + L.u.at, *dw = W.d_in + L.w.at, *dmu = W.d_in + L.mu.at;
+        if (w && !w_each) up(dw, w, (size_t)K_w * nw);      // a shared schedule serves the candidates as it stands
+        if (rough) up(W.d_ter, ter_each ? ter.data() : terrain, (size_t)n_ter);
+        C.Q = I + i_Q; C.Qf = I + i_Qf; C.R = I + i_R; C.x_goal = I + i_xg; C.u_goal = I + i_ug;
+        double *d_fk = W.d_fb + L.fb_K.at, *d_fx = W.d_fb + L.x_ref.at, *d_ua = W.d_fb + L.u_applied.at, *d_fe = W.d_fb + L.fb_err.at;
+        double *dg = W.d_out + L.gamma.at, *db = W.d_out + L.b.at;
+        int *d_st = W.d_st + L.status.at, *d_it = W.d_st + L.iters.at;
+        if (ok_) {
+            const PlantLsExpand E{I + i_q, I + i_u, I + i_k, I + i_K, w_each ? I + i_w : nullptr, mu_each ? I + i_mu : nullptr, I + i_al,
+                                  dq, du, d_fk, d_fx, dw, dmu, B, NB, T, nq, nu, nw, w ? K_w : 0};
+            hipLaunchKernelGGL(plant_ls_expand_kernel, dim3(T * NB), dim3(LS_THREADS), 0, st, E);
+            ok_ = hipGetLastError() == hipSuccess;
+        }
+        if (ok_) {
+            const PlantStepArrays R{dq, du, w ? dw : nullptr, mu_each ? dmu : nullptr, dg, db, d_st, d_it, mu[0], h, T, NB, 1, w ? K_w : 1,
+                                    w_each ? NB : 1, w ? hold_w : 1, mu_each ? NB : 1, W.d_z, PlantFeedback{d_fk, d_fx, T, NB, 1, 1.0}, d_ua, d_fe};
+            ok_ = plant_step_chunks(M, rough, *opts, NB, T, steps_per_launch, R, rough ? W.d_ter : nullptr, n_ter, st);
+        }
+        if (ok_) {
+            const PlantLsCost P{C, dq, d_ua, d_st, O + o_J, N + j_conv, B, NB};
+            hipLaunchKernelGGL(plant_ls_cost_kernel, dim3(NB), dim3(LS_THREADS), 0, st, P);
+            ok_ = hipGetLastError() == hipSuccess;
+        }
+        if (ok_) {
+            const PlantLsGather G{C, dq, W.d_z, d_ua, dg, db, d_st, d_it, N + j_conv, O + o_J, I + i_Jn, I + i_dV, I + i_al, armijo, n_alpha,
+                                  N + j_ok, N + j_ch, O + o_q, O + o_z, O + o_u, O + o_g, O + o_b, N + j_st, N + j_it, O + o_lq, O + o_lr,
+                                  B, NB, nc, nb, nz};
+            hipLaunchKernelGGL(plant_ls_gather_kernel, dim3((T + 2) * B), dim3(LS_THREADS), 0, st, G);
+            ok_ = hipGetLastError() == hipSuccess;
+        }
+        if (ok_) {      // the chosen trajectories' step gradients: an open-loop rollout of B robots on the controls their steps applied
+            const PlantSensSource src{O + o_z, nullptr, O + o_q, O + o_u, !w ? nullptr : w_each ? I + i_w : dw, mu_each ? I + i_mu : nullptr, N + j_st,
+                                      mu[0], h, B, T, B, 1, w ? K_w : 1, w ? n_w : 1, w ? hold_w : 1, n_mu};
+            ok_ = plant_sensitivity_launch(M, (int)TB, src, rough ? W.d_ter : nullptr, rough ? n_terrain : 0, reg, n_cols, buf.d_dz, buf.d_status, st);
+        }
+        if (ok_) {
+            hipLaunchKernelGGL(plant_ls_restore_kernel, dim3((unsigned)TB), dim3(LS_THREADS), 0, st, N + j_ch, parent.d_dz, parent.d_status, buf.d_dz,
+                               buf.d_status, B, T, (int)block);
+            ok_ = hipGetLastError() == hipSuccess;
+        }
+        down(J, O + o_J, (size_t)NB); down(q, O + o_q, (size_t)(T + 2) * B * nq); down(u_applied, O + o_u, TB * nu); down(gamma, O + o_g, TB * nc);
+        down(b, O + o_b, TB * nb); down(lin_q, O + o_lq, (size_t)(T + 1) * B * n); down(lin_r, O + o_lr, TB * nu);
+        down(ok, N + j_ok, (size_t)NB); down(choice, N + j_ch, (size_t)B); down(status, N + j_st, TB); down(iters, N + j_it, TB);
+        down(grad_status, buf.d_status, TB);
+        ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;      // this stream only
+    }
+    if (!ok_) (void)buf.release();
+    if (cur != dev) ok_ = (hipSetDevice(cur) == hipSuccess) && ok_;
+    if (!ok_) { (void)buf.release(); return CIMPC_ERR_HIP; }
+    *new_tape = new cimpc_plant_tape_s{buf, tape->model, B, T, n_cols};
+    return CIMPC_OK;
+}

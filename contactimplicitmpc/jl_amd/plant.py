@@ -17,9 +17,13 @@ section 3, item 3d): tangents of the rollout's arguments, any number of directio
 `RolloutTape.transition` is the state-transition matrix of the rollout, and `rollout_torch` answers forward-mode autograd with it.
 `RolloutTape.lqr` is the LQ backward pass over the tape (`cimpc_plant_tape_lqr`): time-varying LQR gains, and with
 linear cost terms the feedforward, for every robot along the trajectory it took; `TapeGains.feedback` hands them back to `rollout_tape` as a `Feedback`.
+`TrackingCost` is the quadratic tracking cost of a rollout, `RolloutTape.linesearch` rolls several step lengths of those gains for every robot in
+ONE closed-loop rollout, costs them, chooses per robot and returns the chosen trajectories with their tape (`cimpc_plant_tape_linesearch`; DESIGN.md
+section 3, item 3f), and `ilqr` is the loop of the two: iLQR through contact with a per-robot regularization ladder.
 Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble
 solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain, tests/test_gpu_plant_tangent.py against restatements of the forward chain,
-tests/test_gpu_plant_riccati.py against restatements of the backward pass.
+tests/test_gpu_plant_riccati.py against restatements of the backward pass, tests/test_gpu_plant_linesearch.py the line search against the
+rollouts it replaces and `ilqr` against a known answer.
 """
 from __future__ import annotations
 
@@ -819,7 +823,98 @@ class RolloutTape:
         if rc != 0:
             raise _lib.CimpcError(f"cimpc_plant_tape_lqr failed ({rc})")
         return TapeGains(K=np.ascontiguousarray(K.transpose(0, 1, 3, 2)), k=k, P0=np.ascontiguousarray(P0.transpose(0, 2, 1)), p0=p0, dV=dV,
-                         status=status, n_cut=n_cut, N_sample=self._N_sample)
+                         status=status, n_cut=n_cut, N_sample=self._N_sample, K_blocks=K)
+
+    # ---- the line search ----------------------------------------------------------------------------------------------------------------------
+    def linesearch(self, gains: "TapeGains", q, u_applied, cost: "TrackingCost", J_nom, alphas, armijo: float = 1e-4, *, parent_rows=None,
+                   mu=None, w=None, w_hold=None, terrain=None, opts=None, steps_per_launch=None, grad_reg=None) -> "LineSearch":
+        """The forward pass of an iLQR iteration about the trajectory this tape recorded (`cimpc_plant_tape_linesearch`, DESIGN.md section 3,
+        item 3f): candidate c of robot b starts from q[0], q[1], applies u_t = (u_applied[t, b] + alphas[c] k_t[b]) + K_t[b] (x_ref[t] − x_t)
+        around q (T + 2, B, nq), the tape's own trajectory, whose steps applied u_applied (T, B, nu); all len(alphas) (1 .. 64) candidates of
+        all B robots run in ONE closed-loop rollout.  gains: `lqr`'s with linear terms and keep = T; cost: the `TrackingCost` they expand;
+        J_nom (B,): the cost of (q, u_applied).  Candidate c is acceptable iff its steps converged, its J is finite and
+        J ≤ J_nom + armijo (α dV1 + α² dV2); a robot's choice is its acceptable candidate of least J (-1: none).  Returns a `LineSearch`:
+        the chosen candidates' trajectory with the cost's linear terms on it, and a new open-loop tape over it (ONE sensitivity launch over
+        T B steps); a robot without an acceptable candidate keeps (q, u_applied) and the parent tape's blocks.  parent_rows = (gamma, b,
+        status, iters) of the nominal: such a robot's rows of those four; without it they are not known here and come back as NaN and -1,
+        never as another trajectory's.  The tape must be an open-loop one (the nominal of an iLQR iteration is).
+        mu, w, w_hold, terrain, opts, steps_per_launch, grad_reg default to what the tape was recorded with (`rollout_tape` notes them)."""
+        if self.closed:
+            raise ValueError("the tape is closed")
+        if self._N_sample != 1:
+            raise ValueError("linesearch needs a tape recorded with N_sample = 1")
+        if self._feedback is not None:
+            raise ValueError("linesearch needs an open-loop tape: u_applied is the nominal's whole control")
+        mid, nq, nu, nc, fd, nw = model_dims(self.model)
+        B, T, nb, n = self.B, self.T, fd * nc, 2 * nq
+        if gains.k is None or gains.dV is None:
+            raise ValueError("linesearch needs gains with linear terms (lqr(q=, r=)): k and dV")
+        if gains.K.shape[0] < T:
+            raise ValueError(f"linesearch needs the gains of every step (keep = {T}), got keep = {gains.K.shape[0]}")
+        if gains.K.shape != (T, B, nu, n) or gains.k.shape != (T, B, nu) or gains.dV.shape != (B, 2):
+            raise ValueError("gains do not belong to this tape's shape")
+        cont = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        q, u_applied, J_nom, alphas = cont(q), cont(u_applied), cont(J_nom).reshape(-1), cont(alphas).reshape(-1)
+        if q.shape != (T + 2, B, nq) or u_applied.shape != (T, B, nu) or J_nom.shape != (B,):
+            raise ValueError(f"q must be ({T + 2}, {B}, {nq}), u_applied ({T}, {B}, {nu}) and J_nom ({B},)")
+        if not 1 <= alphas.size <= 64 or not np.isfinite(alphas).all():
+            raise ValueError("alphas: 1 to 64 finite step lengths")
+        if not armijo >= 0.0:
+            raise ValueError("armijo must not be negative")
+        ctx = dict(getattr(self, "_context", None) or {})
+        for key, val in dict(mu=mu, w=w, w_hold=w_hold, terrain=terrain, opts=opts, steps_per_launch=steps_per_launch, grad_reg=grad_reg).items():
+            if val is not None:
+                ctx[key] = val
+        if "mu" not in ctx:
+            raise ValueError("mu: this tape does not know the friction it was recorded with")
+        opts = ctx.get("opts", SIM_OPTS)
+        terrain = ctx.get("terrain")
+        if terrain is None and self.model in TERRAIN_MODELS:
+            terrain = "flat_2D_lc"
+        mua = cont(ctx["mu"]).reshape(-1)
+        if mua.size not in (1, B):
+            raise ValueError(f"mu: one friction coefficient or one per robot ({B}), got {mua.size}")
+        wa = None if ctx.get("w") is None else np.ascontiguousarray(_schedule(ctx["w"], B, nw, "w"))
+        reg = _grad_args(self.model, opts, ctx.get("grad_reg"), self.n_cols)[0]
+        Kb = gains.K_blocks      # (T, B, 2nq, nu), column-major blocks; K is what the caller sees, so K decides where the two have come apart
+        if Kb is None or Kb.shape != (T, B, n, nu) or not np.array_equal(Kb.transpose(0, 1, 3, 2), gains.K):
+            Kb = np.ascontiguousarray(gains.K.transpose(0, 1, 3, 2))
+        cc, keep = cost._struct(nq, nu, B, T)
+        na = alphas.size
+        J, ok, choice = np.zeros((na, B)), np.zeros((na, B), dtype=np.int32), np.zeros(B, dtype=np.int32)
+        cq, cu, cg, cb = np.zeros((T + 2, B, nq)), np.zeros((T, B, nu)), np.zeros((T, B, nc)), np.zeros((T, B, nb))
+        st, it, gst = (np.zeros((T, B), dtype=np.int32) for _ in range(3))
+        lq, lr = np.zeros((T + 1, B, n)), np.zeros((T, B, nu))
+        o = _lib.IpOpts(**dataclasses.asdict(opts))
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        ta, nt = (None, 0) if terrain is None else _terrain_array(terrain, B)
+        handle = C.c_void_p()
+        rc = _lib.load().cimpc_plant_tape_linesearch(
+            self._handle, int(ctx.get("steps_per_launch", 0)), nt, ta, dp(q), dp(u_applied), dp(wa), 1 if wa is None else wa.shape[0],
+            1 if wa is None else wa.shape[1], int(ctx.get("w_hold", 1)), dp(mua), mua.size, float(self._h), C.byref(o), dp(cont(Kb)), dp(cont(gains.k)),
+            dp(cont(gains.dV)), dp(J_nom), na, dp(alphas), float(armijo), C.byref(cc), reg, dp(J), ip(ok), ip(choice), dp(cq), dp(cu), dp(cg), dp(cb),
+            ip(st), ip(it), dp(lq), dp(lr), ip(gst), C.byref(handle))
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_tape_linesearch failed ({rc})")
+        tape = RolloutTape(handle, self.model, gst, None, self._v1, self._h, (T, B, nu), 1, None if wa is None else np.shape(ctx["w"]),
+                           int(ctx.get("w_hold", 1)), self._mu_shared, q1_shape=self._q1_shape, mu_shape=self._mu_shape)
+        tape._context = ctx
+        none = choice < 0
+        if none.any():      # the parent's rows for the robots that keep their trajectory
+            cq[:, none], cu[:, none] = q[:, none], u_applied[:, none]
+            _, lq0, lr0 = cost.evaluate(q, u_applied)
+            lq[:, none], lr[:, none] = lq0[:, none], lr0[:, none]
+            if parent_rows is None:
+                cg[:, none], cb[:, none], st[:, none], it[:, none] = np.nan, np.nan, -1, -1
+            else:
+                for mine, theirs in zip((cg, cb, st, it), parent_rows):
+                    theirs = np.asarray(theirs)
+                    if theirs.shape != mine.shape:
+                        raise ValueError(f"parent_rows: (gamma, b, status, iters) of the nominal, got {theirs.shape} for {mine.shape}")
+                    mine[:, none] = theirs[:, none]
+        return LineSearch(J=J, ok=ok.astype(bool), choice=choice, alphas=alphas, q=cq, u_applied=cu, gamma=cg, b=cb, status=st, iters=it, lin_q=lq,
+                          lin_r=lr, tape=tape)
 
 
 @dataclasses.dataclass
@@ -836,6 +931,7 @@ class TapeGains:
     status: np.ndarray
     n_cut: np.ndarray
     N_sample: int = 1
+    K_blocks: object = None      # K as the library wrote it, (keep, B, 2nq, nu): what `RolloutTape.linesearch` hands back without a transpose
 
     def feedback(self, q_traj) -> Feedback:
         """The `Feedback` that applies these gains around the trajectory q_traj (T + 2, B, nq) they were computed on: K · N_sample (the
@@ -849,6 +945,80 @@ class TapeGains:
             raise ValueError(f"q_traj must be (at least {keep + 1}, {B}, {self.K.shape[3] // 2}), got {q_traj.shape}")
         x_ref = np.concatenate([q_traj[1:keep + 1] - 1.0 * (q_traj[1:keep + 1] - q_traj[:keep]), q_traj[1:keep + 1]], axis=2)
         return Feedback(K=self.K * float(self.N_sample), x_ref=np.ascontiguousarray(x_ref), hold=1, n_sample=1.0)
+
+
+class TrackingCost:
+    """The quadratic tracking cost of a rollout (csrc/plant_cost.h): with x_t = [q[t]; q[t+1]] (n = 2nq) and u_t
+    (m = nu) the control step t applied,  J = Σ_{t<T} ½ (x_t − x_goal_t)'Q_t(x_t − x_goal_t) + ½ (u_t − u_goal_t)'R_t(u_t − u_goal_t)
+    + ½ (x_T − x_goal_T)'Qf(x_T − x_goal_T).  Q (n, n) or (T, n, n), R (m, m) or (T, m, m), Qf (n, n) (default Q, its last step's) are shared
+    by the robots, as in `RolloutTape.lqr`; x_goal (T + 1, n) or (T + 1, B, n) and u_goal (T, m) or (T, B, m) default to zeros."""
+
+    def __init__(self, Q, R, Qf=None, x_goal=None, u_goal=None):
+        self.Q, self.R = np.asarray(Q, dtype=np.float64), np.asarray(R, dtype=np.float64)
+        if self.Q.ndim not in (2, 3) or self.R.ndim not in (2, 3) or self.Q.shape[-1] != self.Q.shape[-2] or self.R.shape[-1] != self.R.shape[-2]:
+            raise ValueError("Q must be (n, n) or (T, n, n) and R (m, m) or (T, m, m)")
+        self.Qf = (self.Q if self.Q.ndim == 2 else self.Q[-1]) if Qf is None else np.asarray(Qf, dtype=np.float64)
+        self.x_goal = None if x_goal is None else np.asarray(x_goal, dtype=np.float64)
+        self.u_goal = None if u_goal is None else np.asarray(u_goal, dtype=np.float64)
+
+    def _struct(self, nq: int, nu: int, B: int, T: int):
+        """(`_lib.TrackingCost` for B robots and T steps, the arrays it points to)."""
+        n, m = 2 * nq, nu
+        if self.Q.shape not in ((n, n), (T, n, n)) or self.R.shape not in ((m, m), (T, m, m)) or self.Qf.shape != (n, n):
+            raise ValueError(f"TrackingCost: Q must be ({n}, {n}) or ({T}, {n}, {n}), R ({m}, {m}) or ({T}, {m}, {m}), Qf ({n}, {n})")
+
+        def goal(a, rows, k, what):
+            if a is None:
+                return np.zeros((rows, 1, k))
+            if a.ndim == 2:
+                a = a[:, None, :]
+            if a.ndim != 3 or a.shape[0] != rows or a.shape[1] not in (1, B) or a.shape[2] != k:
+                raise ValueError(f"TrackingCost: {what} must be ({rows}, {k}) or ({rows}, B, {k})")
+            return np.ascontiguousarray(a)
+        xg, ug = goal(self.x_goal, T + 1, n, "x_goal"), goal(self.u_goal, T, m, "u_goal")
+        if xg.shape[1] != ug.shape[1]:      # one of them per robot: the other is spread
+            xg, ug = (np.ascontiguousarray(np.broadcast_to(a, (a.shape[0], B, a.shape[2]))) for a in (xg, ug))
+        col = lambda a: np.ascontiguousarray(np.swapaxes(a, -1, -2))      # column-major blocks
+        Qc, Rc, Qfc = col(self.Q), col(self.R), col(self.Qf)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        return _lib.TrackingCost(dp(Qc), dp(Qfc), dp(Rc), dp(xg), dp(ug), 1 if Qc.ndim == 2 else T, 1 if Rc.ndim == 2 else T, xg.shape[1]), (Qc, Rc, Qfc, xg, ug)
+
+    def evaluate(self, q, u_applied):
+        """(J (B,), lin_q (T + 1, B, 2nq), lin_r (T, B, nu)) of trajectories q (T + 2, B, nq) with applied controls u_applied (T, B, nu), on
+        the host (`cimpc_plant_tracking_cost`) and bit for bit what the line search computes on the device; lin_q, lin_r are the q, r of
+        `RolloutTape.lqr` for the expansion about the trajectory."""
+        q, u_applied = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(u_applied, dtype=np.float64)
+        if q.ndim != 3 or u_applied.ndim != 3 or q.shape[0] != u_applied.shape[0] + 2 or q.shape[1] != u_applied.shape[1] or u_applied.shape[0] < 1:
+            raise ValueError("q must be (T + 2, B, nq) and u_applied (T, B, nu)")
+        (T, Bq, nu), nq = u_applied.shape, q.shape[2]
+        cc, keep = self._struct(nq, nu, Bq, T)
+        J, lq, lr = np.zeros(Bq), np.zeros((T + 1, Bq, 2 * nq)), np.zeros((T, Bq, nu))
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        rc = _lib.load().cimpc_plant_tracking_cost(nq, nu, Bq, T, C.byref(cc), dp(q), dp(u_applied), dp(J), dp(lq), dp(lr))
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_tracking_cost failed ({rc})")
+        return J, lq, lr
+
+
+@dataclasses.dataclass
+class LineSearch:
+    """What `RolloutTape.linesearch` returns: J (n_alpha, B) and ok (n_alpha, B) of every candidate, choice (B,) (-1: none acceptable),
+    alphas; the chosen candidates' q (T + 2, B, nq), u_applied, gamma, b, status, iters and the cost's lin_q (T + 1, B, 2nq), lin_r (T, B, nu)
+    on them - the parent's q, u_applied, lin_q, lin_r for a robot whose choice is -1, and its gamma, b, status, iters where the call was
+    given `parent_rows` (NaN and -1 otherwise); tape: the open-loop `RolloutTape` of that trajectory."""
+    J: np.ndarray
+    ok: np.ndarray
+    choice: np.ndarray
+    alphas: np.ndarray
+    q: np.ndarray
+    u_applied: np.ndarray
+    gamma: np.ndarray
+    b: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    lin_q: np.ndarray
+    lin_r: np.ndarray
+    tape: "RolloutTape"
 
 
 def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w_hold: int = 1, opts: InteriorPointOptions = SIM_OPTS,
@@ -872,8 +1042,79 @@ def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=No
     z, gst, handle = r.tape
     tape = RolloutTape(handle, model, gst, z, v1.copy(), float(h), np.shape(u), int(N_sample), None if w is None else np.shape(w), int(w_hold),
                        np.ndim(mu) == 0 or (mua.size == 1 and B > 1), fb_err=r.fb_err, feedback=loop, q1_shape=q1_shape, mu_shape=mu_shape)
+    tape._context = dict(mu=mua, w=w, w_hold=int(w_hold), terrain=terrain, opts=opts, steps_per_launch=int(steps_per_launch), grad_reg=reg)      # for `linesearch`
     out = (bool(r.status.all()), r.q, u_applied if loop is None else r.u_applied, r.gamma, r.b, r.status, r.iters, tape)
     return out if loop is None else out + (r.fb_err,)
+
+
+@dataclasses.dataclass
+class ILQRResult:
+    """What `ilqr` returns: the final nominal u (T, B, nu), q (T + 2, B, nq), gamma, b; per iteration J (n_iter, B) after it, alpha (the
+    accepted step length, NaN where rejected), rho (the regularization the gains were computed with) and accepted (bool); J0 (B,) the first
+    nominal's cost; tape and gains: the final nominal's `RolloutTape` (open; close it) and the last `TapeGains` (about the nominal before the
+    last line search)."""
+    u: np.ndarray
+    q: np.ndarray
+    gamma: np.ndarray
+    b: np.ndarray
+    J: np.ndarray
+    alpha: np.ndarray
+    rho: np.ndarray
+    accepted: np.ndarray
+    J0: np.ndarray
+    tape: RolloutTape
+    gains: object
+
+
+def ilqr(model: str, q1, v1, u, h: float, mu, cost: TrackingCost, *, alphas=(1.0, 0.5, 0.25, 0.125), max_iter: int = 10, rho0: float = 1e-6,
+         rho_factor: float = 10.0, rho_max: float = 1e6, tol: float = 1e-6, armijo: float = 1e-4, w=None, w_hold: int = 1,
+         opts: InteriorPointOptions = SIM_OPTS, terrain=None, steps_per_launch: int = 0, grad_reg=None, grad_cols=None) -> ILQRResult:
+    """iLQR through contact on the device plant: from the rollout of the controls u (T, nu) or (T, B, nu)
+    (applied as they stand), per iteration `RolloutTape.lqr` about the nominal with the cost's linear terms, then `RolloutTape.linesearch` over
+    alphas - every step length of every robot in one closed-loop rollout - and the chosen candidates become the nominal.  The regularization
+    is per robot on the ladder rho0 rho_factor^j: a rejection moves a robot one level up, an acceptance one down (not below rho0); `lqr` takes
+    a scalar, so it runs once per distinct level in use and the robots' rows are merged on the host.  A robot is no longer updated once its
+    accepted decrease is below tol |J| or its rho exceeds rho_max; it still rides along, rejected by construction.  A backward pass that
+    ends early at a robot's rho (a singular Quu) counts as a rejection: one level up.  Tapes of superseded nominals are closed, the
+    current one too if a call raises."""
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    ok, q, ua, gamma, b, status, iters, tape = rollout_tape(model, q1, v1, u, h, mu, w=w, w_hold=w_hold, opts=opts, terrain=terrain,
+                                                            steps_per_launch=steps_per_launch, grad_reg=grad_reg, grad_cols=grad_cols)
+    T, B = ua.shape[:2]
+    hist = dict(J=[], alpha=[], rho=[], accepted=[])
+    gains = None
+    try:
+        J, lq, lr = cost.evaluate(q, ua)
+        J0 = J.copy()
+        level, active = np.zeros(B, dtype=np.int64), np.ones(B, dtype=bool)
+        for _ in range(int(max_iter)):
+            rho = rho0 * float(rho_factor) ** level
+            Kb, k, dV = np.zeros((T, B, 2 * nq, nu)), np.zeros((T, B, nu)), np.zeros((B, 2))
+            lq_status, n_cut = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+            for val in np.unique(rho):
+                rows = rho == val
+                g = tape.lqr(cost.Q, cost.R, cost.Qf, q=lq, r=lr, rho=float(val))
+                Kb[:, rows], k[:, rows], dV[rows], lq_status[rows], n_cut[rows] = g.K_blocks[:, rows], g.k[:, rows], g.dV[rows], g.status[rows], g.n_cut[rows]
+            gains = TapeGains(K=Kb.transpose(0, 1, 3, 2), k=k, P0=None, p0=None, dV=dV, status=lq_status, n_cut=n_cut, K_blocks=Kb)
+            ls = tape.linesearch(gains, q, ua, cost, np.where(active & (lq_status == 0), J, -np.inf), alphas, armijo, parent_rows=(gamma, b, status, iters))
+            accepted = ls.choice >= 0
+            J_new = np.where(accepted, ls.J[np.maximum(ls.choice, 0), np.arange(B)], J)
+            hist["J"].append(J_new); hist["rho"].append(rho); hist["accepted"].append(accepted)
+            hist["alpha"].append(np.where(accepted, ls.alphas[np.maximum(ls.choice, 0)], np.nan))
+            small = accepted & (J - J_new < tol * np.abs(J))
+            level = np.where(accepted, np.maximum(level - 1, 0), np.where(active, level + 1, level))
+            active = active & ~small & (rho0 * float(rho_factor) ** level <= rho_max)
+            tape.close()
+            tape, q, ua, gamma, b, status, iters, lq, lr, J = ls.tape, ls.q, ls.u_applied, ls.gamma, ls.b, ls.status, ls.iters, ls.lin_q, ls.lin_r, J_new
+            if not active.any():
+                break
+    except BaseException:
+        tape.close()
+        raise
+    n_it = len(hist["J"])
+    stack = lambda key, dt: np.array(hist[key], dtype=dt).reshape(n_it, B)
+    return ILQRResult(u=ua, q=q, gamma=gamma, b=b, J=stack("J", np.float64), alpha=stack("alpha", np.float64), rho=stack("rho", np.float64),
+                      accepted=stack("accepted", bool), J0=J0, tape=tape, gains=gains)
 
 
 def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, feedback=None, **kw):

@@ -636,6 +636,58 @@ int cimpc_plant_tape_lqr(cimpc_plant_tape tape, int laps, int n_Q, const double*
                          const double* q, const double* r, double rho, int n_keep,
                          double* K, double* k, double* P0, double* p0, double* dV, int* status, int* n_cut);
 
+/* ---- iLQR through contact: a tracking cost and a parallel line search in one device rollout (DESIGN.md section 3, item 3f;
+ * csrc/plant_cost.h) ------------------------------------------------------------------------------------------------------------------
+ * THE COST of a robot's trajectory, with x_t = [q[t]; q[t+1]] (n = 2nq, t = 0 .. T) and u_t (m = nu) the control step t applied:
+ *     ex = x_t - x_goal_t;  qx_t = Q_t ex;   eu = u_t - u_goal_t;  ru_t = R_t eu       (every element one running sum, ascending index from 0.0,
+ *     l_t = 0.5 (ex'qx_t) + 0.5 (eu'ru_t), t < T;   l_T = 0.5 ex'(Qf ex);   J = ((l_0 + l_1) + ...) + l_T          no fused multiply-add)
+ * with lin_q[t] = qx_t (lin_q[T] = Qf ex_T) and lin_r[t] = ru_t, the q and r of cimpc_plant_tape_lqr for the expansion about the
+ * trajectory.  Q: n_Q x (n x n), R: n_R x (m x m), column-major, n_Q and n_R 1 or T, Qf n x n, shared by the robots; x_goal
+ * (T+1) x n_x x n and u_goal T x n_x x m with n_x = 1 (shared) or B.  All five pointers are required.
+ *
+ * cimpc_plant_tracking_cost: host only, no device - J (B), lin_q ((T+1) x B x n, may be NULL), lin_r (T x B x m, may be NULL) of B
+ * trajectories q ((T+2) x B x nq) with controls u_applied (T x B x nu), bit for bit what the line search's kernels compute.
+ * CIMPC_ERR_INVALID: a null cost, q, u_applied or J, a null pointer in the cost, nq, nu, B or T < 1, n_Q, n_R or n_x out of range. */
+typedef struct cimpc_tracking_cost {
+    const double* Q;
+    const double* Qf;
+    const double* R;
+    const double* x_goal;
+    const double* u_goal;
+    int n_Q, n_R, n_x;
+} cimpc_tracking_cost;
+int cimpc_plant_tracking_cost(int nq, int nu, int B, int T, const cimpc_tracking_cost* cost, const double* q, const double* u_applied,
+                              double* J, double* lin_q, double* lin_r);
+
+/* cimpc_plant_tape_linesearch: n_alpha step lengths of an iLQR forward pass in ONE rollout of n_alpha x B robots.  `tape` is the parent:
+ * the tape (model, B, T, n_cols, device) of the nominal trajectory q_nom ((T+2) x B x nq), whose steps applied u_nom (T x B x nu); K
+ * (T x B x (nu x 2nq)), k (T x B x nu) and dV (B x 2) are cimpc_plant_tape_lqr's outputs with n_keep = T, as it wrote them; J_nom (B) the
+ * nominal cost.  Candidate c of robot b is rollout robot c B + b: from q_nom[0], q_nom[1] of b, open-loop row ubar_t = u_nom[t, b] +
+ * alpha[c] k[t, b] (one rounded product, one rounded sum), under the feedback law of item 3c with K_t[b], hold 1, n_sample 1.0 and
+ * x_ref[t] = [q_nom[t+1] - 1.0 (q_nom[t+1] - q_nom[t]); q_nom[t+1]], on robot b's w, mu and terrain (w, K_w, n_w, hold_w, mu, n_mu,
+ * n_terrain, terrain, h, opts, steps_per_launch as cimpc_plant_rollout takes them for B robots).  Its trajectory is bit for bit that of
+ * cimpc_plant_rollout_feedback on those inputs.  Candidate c is acceptable iff its T steps converged, J_c is finite and
+ *     J_c <= J_nom[b] + armijo (alpha[c] dV[b][0] + alpha[c]^2 dV[b][1]);
+ * choice[b] is the acceptable candidate of least J (the lower index on a tie), -1 if none.
+ *   Out: J and ok n_alpha x B; choice B; of the CHOSEN candidate (candidate 0 where choice = -1): q (T+2) x B x nq, u_applied T x B x nu,
+ *   gamma T x B x nc, b T x B x nb, status and iters T x B, lin_q (T+1) x B x 2nq, lin_r T x B x nu; grad_status T x B; *new_tape, an
+ *   open-loop tape with the parent's n_cols over the chosen u_applied - ONE sensitivity launch over T B entries at `reg` - in which a
+ *   robot with choice = -1 has the parent tape's blocks and status (grad_status too).  Destroy it with cimpc_plant_tape_destroy.
+ * On the parent tape's device, whichever is current, on the plant's private stream: the B-robot inputs go up once, an expansion kernel
+ * writes the n_alpha B-robot inputs, the closed-loop step kernel's chunks run, a cost kernel and a gather kernel follow, then the
+ * sensitivity launch; one read-back, one synchronize.  Validated first, without a device (CIMPC_ERR_INVALID, the reason left for
+ * cimpc_last_error(NULL)), and what needs no tape before the tape is looked at: a null pointer (w and terrain excepted), n_alpha outside
+ * 1 .. 64, a non-finite alpha, armijo negative or not a number, a null pointer or a count below 1 in the cost, h not positive; then a closed
+ * tape; then n_alpha B T > INT_MAX, everything cimpc_plant_rollout_tape validates for B robots, the cost's n_Q, n_R (1 or T) and n_x (1 or
+ * B), a non-finite entry of K, k, q_nom or u_nom.  On any failure nothing stays allocated and *new_tape is NULL. */
+int cimpc_plant_tape_linesearch(cimpc_plant_tape tape, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                const double* q_nom, const double* u_nom, const double* w, int K_w, int n_w, int hold_w,
+                                const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                                const double* K, const double* k, const double* dV, const double* J_nom,
+                                int n_alpha, const double* alpha, double armijo, const cimpc_tracking_cost* cost, double reg,
+                                double* J, int* ok, int* choice, double* q, double* u_applied, double* gamma, double* b,
+                                int* status, int* iters, double* lin_q, double* lin_r, int* grad_status, cimpc_plant_tape* new_tape);
+
 /* ---- cimpc_set_linearization_batch from (z, theta) alone: plant model `model` linearized at kappa (cimpc_plant_linearize's kernel and arguments;
  * z0 = z, th0 = theta) and the tables built from its output, all on the handle's device and stream;
  * nothing but z, theta and the terrains goes up, nothing but N status words comes back.  Equal bit for bit to

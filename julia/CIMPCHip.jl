@@ -920,6 +920,119 @@ function plant_tape_lqr(tape::PlantTape, Q::Array{Float64}, R::Array{Float64}; Q
     return K, k, P0, p0, dV, status, n_cut
 end
 
+# ---- iLQR through contact: the tracking cost and the parallel line search (cimpc.h: cimpc_tracking_cost; DESIGN.md section 3, item 3f) ---
+# Unexecuted, like the rest of this binding (INTEGRATION.md).
+"""
+`cimpc_tracking_cost`: the pointers and sizes of a tracking cost as the library reads them.  Built by `plant_tracking_cost` and
+`plant_tape_linesearch` from a `TrackingCost`.
+"""
+struct TrackingCostC
+    Q::Ptr{Cdouble}
+    Qf::Ptr{Cdouble}
+    R::Ptr{Cdouble}
+    x_goal::Ptr{Cdouble}
+    u_goal::Ptr{Cdouble}
+    n_Q::Cint; n_R::Cint; n_x::Cint
+end
+
+"""
+    TrackingCost(Q, R, Qf, x_goal, u_goal)
+
+J = Σ_{t<T} ½ (x_t - x_goal_t)'Q_t (x_t - x_goal_t) + ½ (u_t - u_goal_t)'R_t (u_t - u_goal_t) + ½ (x_T - x_goal_T)'Qf (x_T - x_goal_T) with
+x_t = [q[t]; q[t+1]] (n = 2nq), u_t (m = nu) the control step t applied.  Q: n x n or n x n x T, R: m x m or m x m x T, Qf: n x n, shared
+by the robots; x_goal: n x n_x x (T + 1) and u_goal: m x n_x x T with n_x = 1 (shared) or B.
+"""
+struct TrackingCost
+    Q::Array{Float64}
+    R::Array{Float64}
+    Qf::Matrix{Float64}
+    x_goal::Array{Float64,3}
+    u_goal::Array{Float64,3}
+end
+
+function _tracking_cost_sizes(what, c::TrackingCost, nq, nu, B, T)
+    n, m = 2 * nq, nu
+    (size(c.Q) == (n, n) || size(c.Q) == (n, n, T)) || error("$what: Q must be $n x $n or $n x $n x $T")
+    (size(c.R) == (m, m) || size(c.R) == (m, m, T)) || error("$what: R must be $m x $m or $m x $m x $T")
+    size(c.Qf) == (n, n) || error("$what: Qf must be $n x $n")
+    n_x = size(c.x_goal, 2)
+    (n_x in (1, B) && size(c.x_goal) == (n, n_x, T + 1) && size(c.u_goal) == (m, n_x, T)) || error("$what: x_goal must be $n x n_x x $(T + 1) and u_goal $m x n_x x $T, n_x 1 or $B")
+    return ndims(c.Q) == 2 ? 1 : T, ndims(c.R) == 2 ? 1 : T, n_x
+end
+
+"""
+    plant_tracking_cost(cost, q, u_applied) -> (J, lin_q, lin_r)
+
+`cimpc_plant_tracking_cost` (host only): J (B), lin_q 2nq x B x (T + 1) and lin_r nu x B x T of trajectories q nq x B x (T + 2) with applied
+controls u_applied nu x B x T, bit for bit what the line search computes on the device; lin_q, lin_r are the q, r of `plant_tape_lqr`.
+"""
+function plant_tracking_cost(cost::TrackingCost, q::Array{Float64,3}, u_applied::Array{Float64,3})
+    nq, B = size(q, 1), size(q, 2)
+    nu, T = size(u_applied, 1), size(u_applied, 3)
+    (size(q, 3) == T + 2 && size(u_applied, 2) == B) || error("plant_tracking_cost: q must be nq x B x (T + 2) beside u_applied nu x B x T")
+    n_Q, n_R, n_x = _tracking_cost_sizes("plant_tracking_cost", cost, nq, nu, B, T)
+    J = zeros(B); lin_q = zeros(2 * nq, B, T + 1); lin_r = zeros(nu, B, T)
+    GC.@preserve cost begin
+        cc = Ref(TrackingCostC(pointer(cost.Q), pointer(cost.Qf), pointer(cost.R), pointer(cost.x_goal), pointer(cost.u_goal), n_Q, n_R, n_x))
+        check(@ccall LIB.cimpc_plant_tracking_cost(nq::Cint, nu::Cint, B::Cint, T::Cint, cc::Ref{TrackingCostC}, q::Ptr{Cdouble},
+                                                   u_applied::Ptr{Cdouble}, J::Ptr{Cdouble}, lin_q::Ptr{Cdouble}, lin_r::Ptr{Cdouble})::Cint)
+    end
+    return J, lin_q, lin_r
+end
+
+"""
+    plant_tape_linesearch(tape, K, k, dV, q, u_applied, cost, J_nom, alphas, μ, h_sim, opts; armijo = 1e-4, w = nothing, w_hold = 1,
+                          terrain = nothing, steps_per_launch = 0, grad_reg = nothing)
+        -> (J, ok, choice, q, u_applied, γ, b, status, iters, lin_q, lin_r, tape)
+
+`cimpc_plant_tape_linesearch`: the forward pass of an iLQR iteration about the trajectory q nq x B x (T + 2) the tape recorded, whose steps
+applied u_applied nu x B x T.  K m x n x B x T, k m x B x T, dV 2 x B are `plant_tape_lqr`'s with q, r and keep = T, J_nom (B) the cost of the
+nominal.  Candidate c of robot b applies (u_applied[:, b, t] + alphas[c] k[:, b, t]) + K_t (x_ref_t - x_t) and all length(alphas) (1 .. 64)
+candidates of all robots run in ONE closed-loop rollout; a candidate is acceptable iff its steps converged, its J is finite and
+J <= J_nom + armijo (α dV1 + α² dV2), and a robot's choice is its acceptable candidate of least J (0-based; -1: none).  Returns J and ok
+B x n_alpha, choice (B), the chosen candidates' rows (candidate 0's where choice = -1: the caller keeps the nominal's there) with the cost's
+lin_q, lin_r on them, and the open-loop `PlantTape` of that trajectory, in which a robot without a choice has the parent's blocks.
+"""
+function plant_tape_linesearch(tape::PlantTape, K::Array{Float64,4}, k::Array{Float64,3}, dV::Matrix{Float64}, q::Array{Float64,3},
+                               u_applied::Array{Float64,3}, cost::TrackingCost, J_nom::Vector{Float64}, alphas::Vector{Float64}, μ, h_sim, opts;
+                               armijo::Real = 1e-4, w::Union{Nothing,Array{Float64}} = nothing, w_hold::Int = 1,
+                               terrain::Union{Nothing,Vector{Terrain}} = nothing, steps_per_launch::Int = 0, grad_reg = nothing)
+    tape.handle != C_NULL || error("plant_tape_linesearch: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, n, m = tape.B, tape.T, 2 * nq, nu
+    (size(K) == (m, n, B, T) && size(k) == (m, B, T) && size(dV) == (2, B)) || error("plant_tape_linesearch: K must be $m x $n x $B x $T, k $m x $B x $T, dV 2 x $B")
+    (size(q) == (nq, B, T + 2) && size(u_applied) == (nu, B, T) && length(J_nom) == B) || error("plant_tape_linesearch: q, u_applied or J_nom do not fit the tape")
+    n_alpha = length(alphas)
+    (1 <= n_alpha <= 64 && all(isfinite, alphas) && armijo >= 0) || error("plant_tape_linesearch: 1 to 64 finite alphas, armijo >= 0")
+    n_Q, n_R, n_x = _tracking_cost_sizes("plant_tape_linesearch", cost, nq, nu, B, T)
+    ws = w === nothing ? nothing : ndims(w) == 2 ? reshape(w, nw, 1, :) : w
+    (ws === nothing || (ndims(ws) == 3 && size(ws, 1) == nw && size(ws, 2) in (1, B))) || error("plant_tape_linesearch: w must be $nw x K_w or $nw x B x K_w")
+    μs = Float64.(vcat(μ))
+    length(μs) in (1, B) || error("plant_tape_linesearch: one friction coefficient or one per robot")
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    reg = grad_reg === nothing ? o[].kappa_tol * o[].gamma_reg : Float64(grad_reg)
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu = length(μs)
+    J = zeros(B, n_alpha); ok = zeros(Cint, B, n_alpha); choice = zeros(Cint, B)
+    cq = zeros(nq, B, T + 2); cu = zeros(nu, B, T); γ = zeros(nc, B, T); b = zeros(nf * nc, B, T)
+    status = zeros(Cint, B, T); iters = zeros(Cint, B, T); grad_status = zeros(Cint, B, T)
+    lin_q = zeros(n, B, T + 1); lin_r = zeros(m, B, T)
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve cost begin
+        cc = Ref(TrackingCostC(pointer(cost.Q), pointer(cost.Qf), pointer(cost.R), pointer(cost.x_goal), pointer(cost.u_goal), n_Q, n_R, n_x))
+        check(@ccall LIB.cimpc_plant_tape_linesearch(tape.handle::Ptr{Cvoid}, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                                     q::Ptr{Cdouble}, u_applied::Ptr{Cdouble}, wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint,
+                                                     μs::Ptr{Cdouble}, n_mu::Cint, h_sim::Cdouble, o::Ref{IpOpts}, K::Ptr{Cdouble}, k::Ptr{Cdouble},
+                                                     dV::Ptr{Cdouble}, J_nom::Ptr{Cdouble}, n_alpha::Cint, alphas::Ptr{Cdouble}, armijo::Cdouble,
+                                                     cc::Ref{TrackingCostC}, reg::Cdouble, J::Ptr{Cdouble}, ok::Ptr{Cint}, choice::Ptr{Cint},
+                                                     cq::Ptr{Cdouble}, cu::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble}, status::Ptr{Cint},
+                                                     iters::Ptr{Cint}, lin_q::Ptr{Cdouble}, lin_r::Ptr{Cdouble}, grad_status::Ptr{Cint},
+                                                     handle::Ref{Ptr{Cvoid}})::Cint)
+    end
+    return J, ok, choice, cq, cu, γ, b, status, iters, lin_q, lin_r, PlantTape(handle[], tape.model, B, T, tape.n_cols, grad_status)
+end
+
 # ---- the plant models linearized on the device: the `LinearizedStep` triple of N knots in one call (linearized_step.jl:10-31) --------
 """
     plant_linearize(model, z, θ, κ; terrain = nothing) -> (r0, rz0, rθ0)
