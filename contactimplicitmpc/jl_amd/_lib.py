@@ -118,16 +118,22 @@ SIGNATURES = {
     "cimpc_plant_rollout_tape": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _ip, C.POINTER(_h)]),
     "cimpc_plant_tape_vjp": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "cimpc_plant_rollout_feedback": (C.c_int, _ROLLOUT_ARGS + [C.POINTER(Feedback), _dp, _dp]),
+    "cimpc_plant_rollout_feedback_limits": (C.c_int, _ROLLOUT_ARGS + [C.POINTER(Feedback), _dp, _dp, C.c_int, _dp, _dp]),
     "cimpc_plant_rollout_grad_feedback": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _dp, _ip, C.POINTER(Feedback), _dp, _dp]),
     "cimpc_plant_rollout_tape_feedback": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _ip, C.POINTER(_h), C.POINTER(Feedback), _dp, _dp]),
     "cimpc_plant_tape_vjp_feedback": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp]),
     "cimpc_plant_tape_jvp": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "cimpc_plant_tape_jvp_feedback": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),
     "cimpc_plant_tape_lqr": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "cimpc_plant_tape_lqr_box": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
+                                           C.c_int, _dp, _dp, _dp, _ip]),
     "cimpc_plant_tracking_cost": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TrackingCost), _dp, _dp, _dp, _dp, _dp]),
     "cimpc_plant_tape_linesearch": (C.c_int, [_h, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double,
                                               C.POINTER(IpOpts), _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_double, C.POINTER(TrackingCost), C.c_double,
                                               _dp, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _ip, C.POINTER(_h)]),
+    "cimpc_plant_tape_linesearch_box": (C.c_int, [_h, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double,
+                                                  C.POINTER(IpOpts), _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_double, C.POINTER(TrackingCost), C.c_double,
+                                                  _dp, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _ip, C.POINTER(_h), C.c_int, _dp, _dp]),
     "cimpc_plant_tape_dims": (C.c_int, [_h, _ip, _ip, _ip, _ip]),
     "cimpc_plant_tape_destroy": (C.c_int, [_h]),
     "cimpc_tvlqr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),

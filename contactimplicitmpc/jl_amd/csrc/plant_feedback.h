@@ -40,6 +40,15 @@ struct PlantFeedback {
     double n_sample = 1.0;
 };
 
+// The limits of the limited law: u_t[i] = plant_feedback_limit(ubar_t[i] + s[i], u_lo[i], u_hi[i]) with
+// n_lim x nu limits, n_lim = 1 (one row for every robot) or B; u_applied stores the limited value, fb_err is unchanged.  u_lo == nullptr:
+// no limits.  Kept beside PlantFeedback, not inside it: that struct lies in the arguments of the step, adjoint and tangent kernels, and
+// three more words in it changed the register allocation of the six closed-loop step instantiations.
+struct PlantFeedbackLimits {
+    const double *u_lo = nullptr, *u_hi = nullptr;      // n_lim x nu each, or both null
+    int n_lim = 1;
+};
+
 // the K block and the x_ref row step t of robot rb reads
 PFB_HD inline const double* plant_feedback_gain(const PlantFeedback& F, int t, int rb, int nu, int nq) {
     return rollout_schedule(F.K, t, F.hold_f, F.K_f, F.n_f, rb, nu * 2 * nq);
@@ -66,6 +75,13 @@ PFB_HD inline double plant_feedback_control(const double* Kk, const double* e, i
     for (int j = 0; j < 2 * nq; ++j) s = s + Kk[(size_t)j * nu + i] * e[j];
     return ubar + s;
 }
+
+// The limiter of a control with limits, stated once: lo where u < lo, hi where u > hi, u otherwise.  A
+// NaN u passes through (both comparisons are false); -inf and +inf bounds never bind; lo == hi gives that value.
+PFB_HD inline double plant_feedback_limit(double u, double lo, double hi) { return u < lo ? lo : (u > hi ? hi : u); }
+
+// robot rb's row of a limit array
+PFB_HD inline const double* plant_feedback_limits(const double* lim, int n_lim, int rb, int nu) { return lim + (size_t)(n_lim == 1 ? 0 : rb) * nu; }
 
 // gx[j] of the reverse statements: gu the step's nu control cotangents
 PFB_HD inline double plant_feedback_pull(const double* Kk, const double* gu, int nu, int j) {

@@ -11,11 +11,13 @@
 #include <climits>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <type_traits>
 
 #include <cmath>
 
 #include "../../../include/cimpc.h"
+#include "gains.h"
 #include "plant_feedback.h"
 #include "plant_ground.h"
 #include "plant_model.h"
@@ -90,9 +92,11 @@ constexpr int step_threads(int NZ) { return NZ <= NZM ? 64 : 128; }
 // The open-loop instantiations are compiled without it because the branch is not free there: in (20, 64, WALLS) it took 174 VGPRs for 167
 // and 2 waves per SIMD for 3, and pushbot's rollout at B = 8192 and 32768 came out 1.17 x and 1.31 x slower.
 // The iteration is one text, and tests/test_gpu_plant_feedback.py holds the two instantiations to the same bits on every instance.
-template <int NZ, int NT, int GROUND, bool LOOP>
+// LOOP is 0 (open loop), 1 (closed loop) or 2 (closed loop with control limits: the limiter of plant_feedback.h on the law's control,
+// DESIGN.md section 3, item 3g): six more instantiations, launched only when a call brings limits, so that the twelve keep their code.
+template <int NZ, int NT, int GROUND, int LOOP>
 __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts o, int B, PlantRollout R, const cimpc_terrain* terrain,
-                                                        int n_terrain) {
+                                                        int n_terrain, PlantFeedbackLimits lim) {
     static_assert(NT == 64 || NT == 128, "one or two wavefronts per robot");
     __shared__ double A[NZ * (NZ + 1)];
     __shared__ double zs[NZ], rs[NZ], ds[NZ], xs[NZ], ths[2 * PLANT_MAX_Q + PLANT_MAX_U + PLANT_NW + 2], red[2];
@@ -228,7 +232,9 @@ __global__ __launch_bounds__(NT) void plant_step_kernel(PlantModel M, PlantOpts 
         wsync();
         const double* Kk = plant_feedback_gain(R.fb, t, rb, nu, nq);
         for (int i = lane; i < nu; i += NT) {
-            const double ui = plant_feedback_control(Kk, xs, nu, nq, i, ths[2 * nq + i]);
+            double ui = plant_feedback_control(Kk, xs, nu, nq, i, ths[2 * nq + i]);
+            if constexpr (LOOP == 2)
+                ui = plant_feedback_limit(ui, plant_feedback_limits(lim.u_lo, lim.n_lim, rb, nu)[i], plant_feedback_limits(lim.u_hi, lim.n_lim, rb, nu)[i]);
             ths[2 * nq + i] = ui;
             R.u_applied[row * nu + i] = ui;
         }
@@ -303,7 +309,8 @@ PlantWs g_plant_ws[PLANT_MAX_DEVICES];
 std::mutex g_plant_mu;
 }  // namespace cimpc
 
-// The chunked launches of plant_step_launch.h: the LOOP instantiation with a.fb.K, the open-loop one without.
+// The chunked launches of plant_step_launch.h: the closed-loop instantiation with a.fb.K (the limited one with a.lim.u_lo too), the
+// open-loop one without.  The limits are the kernel's last parameter, behind the ones it had, so that those keep their places.
 bool cimpc::plant_step_chunks(const PlantModel& M, bool rough, const cimpc_ip_opts& opts, int B, int T, int steps_per_launch, const PlantStepArrays& a,
                               const cimpc_terrain* d_ter, int n_terrain, hipStream_t st) {
     PlantOpts o{opts.r_tol, opts.kappa_tol, std::isinf(opts.undercut) ? 0.0 : opts.kappa_tol / opts.undercut, opts.eps_min,
@@ -318,8 +325,9 @@ bool cimpc::plant_step_chunks(const PlantModel& M, bool rough, const cimpc_ip_op
         ok = plant_visit_instance(M, rough, true, [&](auto tag) {
             using I = decltype(tag);
             constexpr int NT = step_threads(I::NZ);
-            auto kernel = loop ? plant_step_kernel<I::NZ, NT, I::GROUND, true> : plant_step_kernel<I::NZ, NT, I::GROUND, false>;
-            hipLaunchKernelGGL(kernel, dim3(B), dim3(NT), 0, st, M, o, B, R, rough ? d_ter : nullptr, rough ? n_terrain : 0);
+            auto kernel = !loop ? plant_step_kernel<I::NZ, NT, I::GROUND, 0>
+                          : a.lim.u_lo ? plant_step_kernel<I::NZ, NT, I::GROUND, 2> : plant_step_kernel<I::NZ, NT, I::GROUND, 1>;
+            hipLaunchKernelGGL(kernel, dim3(B), dim3(NT), 0, st, M, o, B, R, rough ? d_ter : nullptr, rough ? n_terrain : 0, a.lim);
             return hipGetLastError() == hipSuccess;
         });
     }
@@ -390,10 +398,13 @@ int plant_rollout_impl(const cimpc::PlantRolloutCall& c, cimpc::PlantTapeBuffers
     if (L.mu.n) up(dmu, c.mu, L.mu.n);
     if (rough) up(W.d_ter, c.terrain, (size_t)c.n_terrain);
     if (f) { up(d_fk, f->K, L.fb_K.n); up(d_fx, f->x_ref, L.x_ref.n); }
+    const bool limited = f && c.loop->u_lo;
+    if (limited) { up(W.d_fb + L.u_lo.at, c.loop->u_lo, L.u_lo.n); up(W.d_fb + L.u_hi.at, c.loop->u_hi, L.u_hi.n); }
     const bool has_w = c.w.rows != nullptr;
     PlantStepArrays R{dq, du, has_w ? dw : nullptr, L.mu.n ? dmu : nullptr, dg, db, d_st, d_it, c.mu[0], c.h, c.u.K, c.u.n, c.u.hold,
                       has_w ? c.w.K : 1, has_w ? c.w.n : 1, has_w ? c.w.hold : 1, c.n_mu, c.grad ? W.d_z : nullptr, PlantFeedback{}, nullptr, nullptr};
     if (f) { R.fb = PlantFeedback{d_fk, d_fx, f->K_f, f->n_f, f->hold_f, f->n_sample}; R.u_applied = d_ua; R.fb_err = d_fe; }
+    if (limited) R.lim = PlantFeedbackLimits{W.d_fb + L.u_lo.at, W.d_fb + L.u_hi.at, c.loop->n_lim};
     ok = ok && plant_step_chunks(M, rough, *c.opts, B, T, c.steps_per_launch, R, rough ? W.d_ter : nullptr, rough ? c.n_terrain : 0, st);
     if (ok && c.grad) {
         PlantSensSource src{W.d_z, nullptr, dq, du, R.w, R.mu, d_st, R.mu0, c.h, B, R.K_u, R.n_u, R.hold_u, R.K_w, R.n_w, R.hold_w, c.n_mu};
@@ -456,6 +467,29 @@ extern "C" int cimpc_plant_rollout_feedback(int model, int B, int T, int steps_p
                                             const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status, int* iters,
                                             const cimpc_feedback* fb, double* u_applied, double* fb_err) {
     return plant_rollout_impl({PLANT_ROLLOUT_CALL_BASE, .loop = cimpc::PlantRolloutLoop{fb, u_applied, fb_err}}, nullptr);
+}
+
+// cimpc_plant_rollout_feedback under control limits: n_lim (1 or B) rows u_lo, u_hi of nu limits, -inf and
+// +inf meaning none.  The step applies and stores limit(u row + K (x_ref - x)); fb_err is the unlimited law's.  Every refusal of the
+// limits leaves its reason for cimpc_last_error(NULL), before any device is touched.
+extern "C" int cimpc_plant_rollout_feedback_limits(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                                   const double* q0, const double* q1, const double* u, int K_u, int n_u, int hold_u,
+                                                   const double* w, int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h,
+                                                   const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status, int* iters,
+                                                   const cimpc_feedback* fb, double* u_applied, double* fb_err, int n_lim, const double* u_lo,
+                                                   const double* u_hi) {
+    auto refuse = [](const char* why) { cimpc::set_global_error(std::string("cimpc_plant_rollout_feedback_limits: ") + why); return CIMPC_ERR_INVALID; };
+    if (!u_lo || !u_hi) return refuse("a null u_lo or u_hi");
+    if (n_lim != 1 && n_lim != B) return refuse("n_lim neither 1 nor B");
+    cimpc::PlantModel named{};
+    if (!cimpc::plant_model_by_id(model, &named) || named.nu < 1) return refuse("a model without controls");
+    for (size_t e = 0; e < (size_t)n_lim * named.nu; ++e) {
+        if (u_lo[e] != u_lo[e] || u_hi[e] != u_hi[e]) return refuse("a NaN limit");
+        if (u_lo[e] > u_hi[e]) return refuse("u_lo above u_hi");
+    }
+    const int rc = plant_rollout_impl({PLANT_ROLLOUT_CALL_BASE, .loop = cimpc::PlantRolloutLoop{fb, u_applied, fb_err, u_lo, u_hi, n_lim}}, nullptr);
+    if (rc == CIMPC_ERR_INVALID) cimpc::set_global_error("cimpc_plant_rollout_feedback_limits: an argument that cimpc_plant_rollout_feedback refuses");
+    return rc;
 }
 
 extern "C" int cimpc_plant_rollout_grad_feedback(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,

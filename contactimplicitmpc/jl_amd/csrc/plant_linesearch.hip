@@ -7,6 +7,9 @@
 //                                 rows compacted to B robots, lin_q and lin_r on them); ONE sensitivity launch over T x B entries into the
 //                                 new tape; plant_ls_restore_kernel (the parent's blocks for a robot without an acceptable candidate);
 //                                 one read-back, one synchronize
+//   cimpc_plant_tape_linesearch_box  the same call under control limits: the expansion kernel writes the
+//                                 limited open-loop rows limit(u_nom + alpha k) and the candidates' limit rows, and the candidates run the
+//                                 limited law (the step kernel's third state); the existing entry is this one with null limits
 //   cimpc_plant_tracking_cost     plant_cost.h on the host with a team of one
 //
 // The kernels here move rows and run the short ordered chains of plant_cost.h; a wavefront per workgroup.  The time of a line search is
@@ -50,6 +53,9 @@ struct PlantLsExpand {
     const double *q_nom, *u_nom, *k, *K, *w, *mu, *alpha;      // w, mu: null when shared (the step kernel then reads the parent's)
     double *q, *u, *fb_K, *x_ref, *w_out, *mu_out;
     int B, NB, T, nq, nu, nw, K_w;
+    const double *u_lo, *u_hi;      // n_lim x nu limits of the B robots, or both null: no limits
+    double *lo_out, *hi_out;        // the candidates' NB rows (n_lim = B), or null (n_lim = 1: the one row serves them all)
+    int n_lim;
 };
 
 __global__ __launch_bounds__(LS_THREADS) void plant_ls_expand_kernel(PlantLsExpand E) {
@@ -57,7 +63,11 @@ __global__ __launch_bounds__(LS_THREADS) void plant_ls_expand_kernel(PlantLsExpa
     if (e >= E.T * E.NB) return;
     const int t = e / E.NB, r = e % E.NB, c = r / E.B, b = r % E.B, nq = E.nq, nu = E.nu, kk = nu * 2 * nq;
     const size_t from = (size_t)t * E.B + b;
-    for (int i = lane; i < nu; i += LS_THREADS) E.u[(size_t)e * nu + i] = plant_candidate_control(E.u_nom[from * nu + i], E.alpha[c], E.k[from * nu + i]);
+    const double *lo = E.u_lo ? plant_feedback_limits(E.u_lo, E.n_lim, b, nu) : nullptr, *hi = E.u_lo ? plant_feedback_limits(E.u_hi, E.n_lim, b, nu) : nullptr;
+    for (int i = lane; i < nu; i += LS_THREADS) {
+        const double ubar = plant_candidate_control(E.u_nom[from * nu + i], E.alpha[c], E.k[from * nu + i]);
+        E.u[(size_t)e * nu + i] = lo ? plant_feedback_limit(ubar, lo[i], hi[i]) : ubar;
+    }
     for (int i = lane; i < kk; i += LS_THREADS) E.fb_K[(size_t)e * kk + i] = E.K[from * kk + i];
     const double *q0 = E.q_nom + from * nq, *q1 = E.q_nom + (from + E.B) * nq;
     for (int j = lane; j < 2 * nq; j += LS_THREADS) E.x_ref[(size_t)e * 2 * nq + j] = plant_candidate_target(q0, q1, nq, j);
@@ -67,6 +77,8 @@ __global__ __launch_bounds__(LS_THREADS) void plant_ls_expand_kernel(PlantLsExpa
         E.q[((size_t)E.NB + r) * nq + i] = q1[i];
     }
     if (E.mu && lane == 0) E.mu_out[r] = E.mu[b];
+    if (E.lo_out)
+        for (int i = lane; i < nu; i += LS_THREADS) { E.lo_out[(size_t)r * nu + i] = lo[i]; E.hi_out[(size_t)r * nu + i] = hi[i]; }
     if (E.w)
         for (int i = lane; i < E.K_w * E.nw; i += LS_THREADS) {
             const int row = i / E.nw, j = i % E.nw;
@@ -182,16 +194,17 @@ extern "C" int cimpc_plant_tracking_cost(int nq, int nu, int B, int T, const cim
     return CIMPC_OK;
 }
 
-extern "C" int cimpc_plant_tape_linesearch(cimpc_plant_tape tape, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
-                                           const double* q_nom, const double* u_nom, const double* w, int K_w, int n_w, int hold_w,
-                                           const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, const double* K, const double* k,
-                                           const double* dV, const double* J_nom, int n_alpha, const double* alpha, double armijo,
-                                           const cimpc_tracking_cost* cost, double reg, double* J, int* ok, int* choice, double* q,
-                                           double* u_applied, double* gamma, double* b, int* status, int* iters, double* lin_q, double* lin_r,
-                                           int* grad_status, cimpc_plant_tape* new_tape) {
+// Both entries: u_lo, u_hi null (cimpc_plant_tape_linesearch) or n_lim x nu limits (cimpc_plant_tape_linesearch_box).
+static int plant_tape_linesearch_call(const char* entry, cimpc_plant_tape tape, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                      const double* q_nom, const double* u_nom, const double* w, int K_w, int n_w, int hold_w,
+                                      const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, const double* K, const double* k,
+                                      const double* dV, const double* J_nom, int n_alpha, const double* alpha, double armijo,
+                                      const cimpc_tracking_cost* cost, double reg, double* J, int* ok, int* choice, double* q,
+                                      double* u_applied, double* gamma, double* b, int* status, int* iters, double* lin_q, double* lin_r,
+                                      int* grad_status, cimpc_plant_tape* new_tape, int n_lim, const double* u_lo, const double* u_hi) {
     using namespace cimpc;
     // every refusal leaves its reason where cimpc_last_error(NULL) finds it; what needs no tape is tested before the tape is looked at
-    auto refuse = [](const std::string& why) { set_global_error("cimpc_plant_tape_linesearch: " + why); return CIMPC_ERR_INVALID; };
+    auto refuse = [entry](const std::string& why) { set_global_error(std::string(entry) + ": " + why); return CIMPC_ERR_INVALID; };
     if (!new_tape) return refuse("null new_tape");
     *new_tape = nullptr;
     const std::pair<const char*, const void*> required[] = {
@@ -202,6 +215,17 @@ extern "C" int cimpc_plant_tape_linesearch(cimpc_plant_tape tape, int steps_per_
     if (const char* why = plant_linesearch_refusal(n_alpha, alpha, armijo)) return refuse(why);
     if (const char* why = plant_cost_pointers(plant_cost_of(*cost, 1, 1, 1))) return refuse(why);
     if (!(h > 0.0)) return refuse("h not positive");
+    const bool limits = u_lo || u_hi;
+    if (limits && (!u_lo || !u_hi)) return refuse("one of u_lo, u_hi without the other");
+    if (limits && n_lim != 1 && n_lim != tape->B) return refuse("n_lim neither 1 nor B");
+    if (limits) {      // the limits' entries: the model's nu by the tape's model id alone
+        PlantModel named{};
+        if (!plant_model_by_id(tape->model, &named) || named.nu < 1) return refuse("a model without controls or not the tape's");
+        for (size_t e = 0; e < (size_t)n_lim * named.nu; ++e) {
+            if (u_lo[e] != u_lo[e] || u_hi[e] != u_hi[e]) return refuse("a NaN limit");
+            if (u_lo[e] > u_hi[e]) return refuse("u_lo above u_hi");
+        }
+    }
     const PlantTapeBuffers& parent = tape->buf;
     const int B = tape->B, T = tape->T, n_cols = tape->n_cols;
     if (parent.device < 0 || parent.device >= PLANT_MAX_DEVICES || !parent.d_dz || !parent.d_status) return refuse("a closed tape");
@@ -232,7 +256,7 @@ extern "C" int cimpc_plant_tape_linesearch(cimpc_plant_tape tape, int steps_per_
                                      .q0 = q_nom, .q1 = q_nom, .u = {u_nom, T, NB, 1}, .w = {w, K_w, w_each ? NB : 1, hold_w}, .mu = mu,
                                      .n_mu = mu_each ? NB : 1, .h = h, .opts = opts, .q = q, .gamma = gamma, .b = b, .status = status, .iters = iters,
                                      .grad = PlantRolloutGrad{reg, n_cols, nullptr, nullptr, grad_status, true},
-                                     .loop = PlantRolloutLoop{&fb_shape, u_applied, nullptr}};
+                                     .loop = PlantRolloutLoop{&fb_shape, u_applied, nullptr, u_lo, u_hi, !limits || n_lim == 1 ? 1 : NB}};
     const PlantRolloutLayout L = plant_rollout_layout(M, cand_call);
     // the B-robot inputs in d_in, in the order they go up
     size_t at = 0;
@@ -240,7 +264,8 @@ extern "C" int cimpc_plant_tape_linesearch(cimpc_plant_tape tape, int steps_per_
     const size_t i_q = next((size_t)(T + 2) * B * nq), i_u = next(TB * nu), i_k = next(TB * nu), i_K = next(TB * kk),
                  i_w = next(w_each ? (size_t)K_w * B * nw : 0), i_mu = next(mu_each ? (size_t)B : 0), i_dV = next((size_t)2 * B), i_Jn = next((size_t)B),
                  i_al = next((size_t)n_alpha), i_Q = next((size_t)C.n_Q * n * n), i_Qf = next(n * n), i_R = next((size_t)C.n_R * nu * nu),
-                 i_xg = next((size_t)(T + 1) * C.n_x * n), i_ug = next((size_t)T * C.n_x * nu), n_in = at;
+                 i_xg = next((size_t)(T + 1) * C.n_x * n), i_ug = next((size_t)T * C.n_x * nu), i_lo = next(limits ? (size_t)n_lim * nu : 0),
+                 i_hi = next(limits ? (size_t)n_lim * nu : 0), n_in = at;
     at = 0;      // J and the chosen candidates' rows in d_out, in the order they come back
     const size_t o_J = next((size_t)NB), o_q = next((size_t)(T + 2) * B * nq), o_u = next(TB * nu), o_g = next(TB * nc), o_b = next(TB * nb),
                  o_lq = next((size_t)(T + 1) * B * n), o_lr = next(TB * nu), o_z = next(TB * nz), n_out = at;
@@ -279,6 +304,10 @@ extern "C" int cimpc_plant_tape_linesearch(cimpc_plant_tape tape, int steps_per_
         up(I + i_dV, dV, (size_t)2 * B); up(I + i_Jn, J_nom, (size_t)B); up(I + i_al, alpha, (size_t)n_alpha);
         up(I + i_Q, C.Q, (size_t)C.n_Q * n * n); up(I + i_Qf, C.Qf, n * n); up(I + i_R, C.R, (size_t)C.n_R * nu * nu);
         up(I + i_xg, C.x_goal, (size_t)(T + 1) * C.n_x * n); up(I + i_ug, C.u_goal, (size_t)T * C.n_x * nu);
+        if (limits) { up(I + i_lo, u_lo, (size_t)n_lim * nu); up(I + i_hi, u_hi, (size_t)n_lim * nu); }
+        // the candidates' limits: the one shared row where it stands, or NB rows the expansion kernel writes behind the loop's arrays
+        const bool lim_each = limits && n_lim != 1;
+        const double *c_lo = !limits ? nullptr : lim_each ? W.d_fb + L.u_lo.at : I + i_lo, *c_hi = !limits ? nullptr : lim_each ? W.d_fb + L.u_hi.at : I + i_hi;
         double *dq = W.d_in + L.q.at, *du = W.d_in + L.u.at, *dw = W.d_in + L.w.at, *dmu = W.d_in + L.mu.at;
         if (w && !w_each) up(dw, w, (size_t)K_w * nw);      // a shared schedule serves the candidates as it stands
         if (rough) up(W.d_ter, ter_each ? ter.data() : terrain, (size_t)n_ter);
@@ -288,13 +317,15 @@ extern "C" int cimpc_plant_tape_linesearch(cimpc_plant_tape tape, int steps_per_
         int *d_st = W.d_st + L.status.at, *d_it = W.d_st + L.iters.at;
         if (ok_) {
             const PlantLsExpand E{I + i_q, I + i_u, I + i_k, I + i_K, w_each ? I + i_w : nullptr, mu_each ? I + i_mu : nullptr, I + i_al,
-                                  dq, du, d_fk, d_fx, dw, dmu, B, NB, T, nq, nu, nw, w ? K_w : 0};
+                                  dq, du, d_fk, d_fx, dw, dmu, B, NB, T, nq, nu, nw, w ? K_w : 0, limits ? I + i_lo : nullptr, limits ? I + i_hi : nullptr,
+                                  lim_each ? W.d_fb + L.u_lo.at : nullptr, lim_each ? W.d_fb + L.u_hi.at : nullptr, n_lim};
             hipLaunchKernelGGL(plant_ls_expand_kernel, dim3(T * NB), dim3(LS_THREADS), 0, st, E);
             ok_ = hipGetLastError() == hipSuccess;
         }
         if (ok_) {
             const PlantStepArrays R{dq, du, w ? dw : nullptr, mu_each ? dmu : nullptr, dg, db, d_st, d_it, mu[0], h, T, NB, 1, w ? K_w : 1,
-                                    w_each ? NB : 1, w ? hold_w : 1, mu_each ? NB : 1, W.d_z, PlantFeedback{d_fk, d_fx, T, NB, 1, 1.0}, d_ua, d_fe};
+                                    w_each ? NB : 1, w ? hold_w : 1, mu_each ? NB : 1, W.d_z, PlantFeedback{d_fk, d_fx, T, NB, 1, 1.0}, d_ua, d_fe,
+                                    PlantFeedbackLimits{c_lo, c_hi, lim_each ? NB : 1}};
             ok_ = plant_step_chunks(M, rough, *opts, NB, T, steps_per_launch, R, rough ? W.d_ter : nullptr, n_ter, st);
         }
         if (ok_) {
@@ -330,4 +361,35 @@ extern "C" int cimpc_plant_tape_linesearch(cimpc_plant_tape tape, int steps_per_
     if (!ok_) { (void)buf.release(); return CIMPC_ERR_HIP; }
     *new_tape = new cimpc_plant_tape_s{buf, tape->model, B, T, n_cols};
     return CIMPC_OK;
+}
+
+extern "C" int cimpc_plant_tape_linesearch(cimpc_plant_tape tape, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                           const double* q_nom, const double* u_nom, const double* w, int K_w, int n_w, int hold_w,
+                                           const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, const double* K, const double* k,
+                                           const double* dV, const double* J_nom, int n_alpha, const double* alpha, double armijo,
+                                           const cimpc_tracking_cost* cost, double reg, double* J, int* ok, int* choice, double* q,
+                                           double* u_applied, double* gamma, double* b, int* status, int* iters, double* lin_q, double* lin_r,
+                                           int* grad_status, cimpc_plant_tape* new_tape) {
+    return plant_tape_linesearch_call("cimpc_plant_tape_linesearch", tape, steps_per_launch, n_terrain, terrain, q_nom, u_nom, w, K_w, n_w, hold_w, mu, n_mu,
+                                      h, opts, K, k, dV, J_nom, n_alpha, alpha, armijo, cost, reg, J, ok, choice, q, u_applied, gamma, b, status, iters,
+                                      lin_q, lin_r, grad_status, new_tape, 1, nullptr, nullptr);
+}
+
+// The line search under control limits: candidate c of robot b applies
+// u_t = limit(limit(u_nom + alpha_c k_t) + K_t (x_ref_t - x_t)) with n_lim (1 or B) rows u_lo, u_hi of nu limits.  Acceptance, choice and the
+// new tape - the open-loop tape of the chosen u_applied - are cimpc_plant_tape_linesearch's.
+extern "C" int cimpc_plant_tape_linesearch_box(cimpc_plant_tape tape, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                               const double* q_nom, const double* u_nom, const double* w, int K_w, int n_w, int hold_w,
+                                               const double* mu, int n_mu, double h, const cimpc_ip_opts* opts, const double* K, const double* k,
+                                               const double* dV, const double* J_nom, int n_alpha, const double* alpha, double armijo,
+                                               const cimpc_tracking_cost* cost, double reg, double* J, int* ok, int* choice, double* q,
+                                               double* u_applied, double* gamma, double* b, int* status, int* iters, double* lin_q, double* lin_r,
+                                               int* grad_status, cimpc_plant_tape* new_tape, int n_lim, const double* u_lo, const double* u_hi) {
+    if ((u_lo == nullptr) != (u_hi == nullptr)) {
+        cimpc::set_global_error("cimpc_plant_tape_linesearch_box: one of u_lo, u_hi without the other");
+        return CIMPC_ERR_INVALID;
+    }
+    return plant_tape_linesearch_call("cimpc_plant_tape_linesearch_box", tape, steps_per_launch, n_terrain, terrain, q_nom, u_nom, w, K_w, n_w, hold_w, mu,
+                                      n_mu, h, opts, K, k, dV, J_nom, n_alpha, alpha, armijo, cost, reg, J, ok, choice, q, u_applied, gamma, b, status,
+                                      iters, lin_q, lin_r, grad_status, new_tape, n_lim, u_lo, u_hi);
 }

@@ -42,6 +42,8 @@
 #include <cmath>
 #include <cstddef>
 
+#include "plant_boxqp.h"
+
 // no contraction in this header's arithmetic: a * b + c rounds twice
 #ifdef __clang__
 #pragma clang fp contract(off)
@@ -74,6 +76,11 @@ struct PlantRiccati {
     int *status, *n_cut;
     int B, T, nq, nu, nr, n_cols, laps, n_Q, n_R, n_keep;
     double rho;
+    // the limited pass (plant_boxqp.h), read by the BOX chain alone: u_lo, u_hi n_lim x m (n_lim 1 or B; null:
+    // no limits), u_nom T x B x m the tape's applied controls, rho_b n_rho (1 or B) regularizations (null: rho), clamped n_keep x B
+    const double *u_lo = nullptr, *u_hi = nullptr, *u_nom = nullptr, *rho_b = nullptr;
+    int* clamped = nullptr;
+    int n_lim = 1, n_rho = 1;
 };
 
 // ---- the plan: what a robot's chain needs of the team's shared memory ---------------------------------------------------------------
@@ -89,6 +96,12 @@ constexpr size_t plant_riccati_lds(int nq, int nu) { return plant_riccati_work_d
 constexpr bool plant_riccati_fits(int nq, int nu) { return nq >= 1 && nu >= 1 && plant_riccati_lds(nq, nu) <= PLANT_RIC_MAX_LDS; }
 static_assert(plant_riccati_lds(18, 12) == 63920, "centroidal_quadruped_wall (n = 36, m = 12), the largest: 62 KB, two workgroups a CU");
 static_assert(plant_riccati_lds(11, 8) == 24984, "quadruped (n = 22, m = 8): 24 KB");
+// the limited chain: plant_boxqp.h's work behind the unlimited chain's
+PRIC_HD constexpr size_t plant_riccati_box_work_doubles(int nq, int nu) { return plant_riccati_work_doubles(nq, nu) + plant_boxqp_work_doubles(nu); }
+constexpr size_t plant_riccati_box_lds(int nq, int nu) { return plant_riccati_box_work_doubles(nq, nu) * sizeof(double); }
+static_assert(plant_riccati_box_lds(18, 12) == 65760 && 2 * plant_riccati_box_lds(18, 12) <= PLANT_RIC_MAX_LDS,
+              "the largest model with limits: 64 KB, still two workgroups a CU");
+static_assert(plant_riccati_box_lds(11, 8) == 25960, "quadruped with limits: 25 KB");
 static_assert(plant_riccati_fits(18, 12) && plant_riccati_fits(11, 8) && plant_riccati_fits(1, 1) && !plant_riccati_fits(60, 12), "the plan's limits");
 
 PRIC_HD inline bool plant_riccati_bad_pivot(double pv) { return !(std::fabs(pv) > 0.0) || !std::isfinite(pv); }
@@ -147,8 +160,9 @@ PRIC_UNROLL
 }
 
 // The chain of robot rb.  work: shared by the team, plant_riccati_work_doubles(nq, nu).  LIN: the linear terms are compiled in (the
-// caller has L.q and L.r non-null and L.laps == 1).  All matrices column-major.
-template <bool LIN, class Team>
+// caller has L.q and L.r non-null and L.laps == 1).  BOX (with LIN): the limited pass of plant_boxqp.h stands where the unlimited solve
+// does, work is plant_riccati_box_work_doubles(nq, nu), rho is the robot's own and clamped is written.  All matrices column-major.
+template <bool LIN, bool BOX = false, class Team>
 PRIC_HD inline void plant_riccati_chain_as(const PlantRiccati& L, int rb, double* work, Team& team) {
     const int me = team.rank(), np = team.size();
     const int nq = L.nq, n = 2 * nq, m = L.nu, B = L.B, T = L.T, nr = L.nr, nc = n + m, fw = n + (LIN ? 1 : 0);
@@ -176,6 +190,13 @@ PRIC_HD inline void plant_riccati_chain_as(const PlantRiccati& L, int rb, double
     auto block = [&](int t) { return L.dz + ((size_t)t * B + rb) * blk; };
     const auto zero = [](int, int) { return 0.0; };
     const int steps = L.laps * T;
+    static_assert(LIN || !BOX, "the limited pass needs the linear terms");
+    double rho_box = 0.0;                    // BOX: the robot's own rho
+    PlantBoxQPWork box{};
+    if constexpr (BOX) {
+        rho_box = L.rho_b ? L.rho_b[L.n_rho == 1 ? 0 : rb] : L.rho;
+        box = plant_boxqp_carve(work + plant_riccati_work_doubles(nq, m), m);
+    }
 
     for (int e = me; e < n * n; e += np) P[e] = L.Qf[e];
     if constexpr (LIN) {
@@ -226,47 +247,55 @@ PRIC_HD inline void plant_riccati_chain_as(const PlantRiccati& L, int rb, double
                                     [&](int i, int c, double v) {
                                         if (c < m) {
                                             const double quu = Rm[c * m + i] + v;
-                                            G[c * m + i] = i == c ? quu + L.rho : quu;
+                                            G[c * m + i] = i == c ? quu + (BOX ? rho_box : L.rho) : quu;
                                             if constexpr (LIN) RK[c * m + i] = quu;      // Quu, kept for dV2 (R K is formed after it)
                                         } else F[(c - m) * m + i] = v;
                                     });
         team.sync();
-        for (int k = 0; k < m; ++k) {        // G [K | x] = [Qux | Qu], LU with partial pivoting; every member finds the pivot
-            double best = -1.0;
-            int p = k;
-            for (int i = k; i < m; ++i) {
-                const double v = std::fabs(G[k * m + i]);
-                if (plant_riccati_pivot_beats(v, best)) { best = v; p = i; }
-            }
-            team.sync();
-            if (p != k)
-                for (int j = k + me; j < m + fw; j += np) {
-                    double* col = j < m ? G + j * m : F + (j - m) * m;
-                    const double v = col[k]; col[k] = col[p]; col[p] = v;
+        if constexpr (BOX) {                 // the box QP and the final solve on its free set: plant_boxqp.h
+            const size_t lim = (size_t)(L.n_lim == 1 ? 0 : rb) * m;
+            if (!plant_boxqp_step(team, m, n, G, F, Qu, kv, KT, box, L.u_lo ? L.u_lo + lim : nullptr, L.u_lo ? L.u_hi + lim : nullptr,
+                                  L.u_lo ? L.u_nom + ((size_t)t * B + rb) * m : nullptr, s == 1, &finite)) { fail = s; break; }
+        } else {
+            for (int k = 0; k < m; ++k) {        // G [K | x] = [Qux | Qu], LU with partial pivoting; every member finds the pivot
+                double best = -1.0;
+                int p = k;
+                for (int i = k; i < m; ++i) {
+                    const double v = std::fabs(G[k * m + i]);
+                    if (plant_riccati_pivot_beats(v, best)) { best = v; p = i; }
                 }
-            team.sync();
-            const double pv = G[k * m + k];
-            if (plant_riccati_bad_pivot(pv)) { fail = s; break; }      // the same word for every member: all leave together
-            const double rp = 1.0 / pv;
-            for (int e = me; e < (m - k - 1) * (m + fw - k - 1); e += np) {      // (i, j), i fastest
-                const int i = k + 1 + e % (m - k - 1), j = k + 1 + e / (m - k - 1);
-                const double l = G[k * m + i] * rp;
-                double* col = j < m ? G + j * m : F + (j - m) * m;
-                col[i] -= l * col[k];
+                team.sync();
+                if (p != k)
+                    for (int j = k + me; j < m + fw; j += np) {
+                        double* col = j < m ? G + j * m : F + (j - m) * m;
+                        const double v = col[k]; col[k] = col[p]; col[p] = v;
+                    }
+                team.sync();
+                const double pv = G[k * m + k];
+                if (plant_riccati_bad_pivot(pv)) { fail = s; break; }      // the same word for every member: all leave together
+                const double rp = 1.0 / pv;
+                for (int e = me; e < (m - k - 1) * (m + fw - k - 1); e += np) {      // (i, j), i fastest
+                    const int i = k + 1 + e % (m - k - 1), j = k + 1 + e / (m - k - 1);
+                    const double l = G[k * m + i] * rp;
+                    double* col = j < m ? G + j * m : F + (j - m) * m;
+                    col[i] -= l * col[k];
+                }
+                team.sync();
             }
-            team.sync();
         }
         if (fail) break;
-        for (int c = me; c < fw; c += np) {  // U K = F, a column per member
-            double* col = F + c * m;
-            for (int k = m - 1; k >= 0; --k) {
-                double a = col[k];
-                for (int j = k + 1; j < m; ++j) a -= G[j * m + k] * col[j];
-                a /= G[k * m + k];
-                col[k] = a;
-                finite = finite && std::isfinite(a);
-                if (c < n) KT[k * n + c] = a;
-                else kv[k] = -a;
+        if constexpr (!BOX) {
+            for (int c = me; c < fw; c += np) {  // U K = F, a column per member
+                double* col = F + c * m;
+                for (int k = m - 1; k >= 0; --k) {
+                    double a = col[k];
+                    for (int j = k + 1; j < m; ++j) a -= G[j * m + k] * col[j];
+                    a /= G[k * m + k];
+                    col[k] = a;
+                    finite = finite && std::isfinite(a);
+                    if (c < n) KT[k * n + c] = a;
+                    else kv[k] = -a;
+                }
             }
         }
         team.sync();
@@ -303,6 +332,7 @@ PRIC_HD inline void plant_riccati_chain_as(const PlantRiccati& L, int rb, double
         if (last_lap && t < L.n_keep) {
             for (int e = me; e < m * n; e += np) L.K[((size_t)t * B + rb) * m * n + e] = F[e];
             if constexpr (LIN) if (L.k) for (int e = me; e < m; e += np) L.k[((size_t)t * B + rb) * m + e] = kv[e];
+            if constexpr (BOX) if (L.clamped && me == 0) L.clamped[(size_t)t * B + rb] = box.idx[m + 1];
         }
         team.sync();
         // T1 = P Acl = [0 P11; 0 P21] + [P12; P22] Dcl; with linear terms s = [P12; P22] (Du k) + p
@@ -345,6 +375,7 @@ PRIC_HD inline void plant_riccati_chain_as(const PlantRiccati& L, int rb, double
     if (fail) {
         for (size_t e = me; e < (size_t)L.n_keep * m * n; e += np) L.K[((e / ((size_t)m * n)) * B + rb) * m * n + e % ((size_t)m * n)] = 0.0;
         if (L.k) for (int e = me; e < L.n_keep * m; e += np) L.k[((size_t)(e / m) * B + rb) * m + e % m] = 0.0;
+        if constexpr (BOX) if (L.clamped) for (int e = me; e < L.n_keep; e += np) L.clamped[(size_t)e * B + rb] = 0;
     }
     if (L.P0) for (int e = me; e < n * n; e += np) L.P0[(size_t)rb * n * n + e] = fail ? 0.0 : P[e];
     if constexpr (LIN) {

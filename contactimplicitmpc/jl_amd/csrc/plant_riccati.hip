@@ -12,18 +12,24 @@
 // registers before a step's arithmetic and stored to the other LDS buffer after it.  The chain is a latency chain; the robots are the
 // parallelism.  62 KB of LDS at the largest model (n = 36, m = 12), 24 KB at the quadruped.
 // gfx950, -O3: plant_riccati_kernel<false> 118 VGPRs, <true> 129 VGPRs, no scratch and no spills (see profiles/plant_riccati.json).
+//
+//   cimpc_plant_tape_lqr_box   the limited pass (plant_boxqp.h): the same call with a rho per robot, control
+//                              limits and the tape's applied controls; plant_riccati_kernel<true, true>, the only instantiation that holds
+//                              the box QP, with plant_boxqp.h's work behind the chain's in LDS (64 KB at the largest model)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <vector>
 
 // No fused multiply-adds in this translation unit: the chain rounds as the float64 restatement of the definition does.
 #pragma clang fp contract(off)
 
 #include "../../../include/cimpc.h"
+#include "gains.h"
 #include "plant_model.h"
 #include "plant_riccati.h"
 #include "plant_tape.h"
@@ -57,13 +63,13 @@ struct PlantRiccatiGroup {
     }
 };
 
-template <bool LIN>      // LIN: the chain with the linear cost terms q, r
+template <bool LIN, bool BOX = false>      // LIN: the chain with the linear cost terms q, r; BOX: with control limits and a rho per robot
 __global__ __launch_bounds__(RIC_THREADS) void plant_riccati_kernel(PlantRiccati L) {
-    extern __shared__ __attribute__((aligned(16))) double ric_lds[];      // plant_riccati_lds(nq, nu)
+    extern __shared__ __attribute__((aligned(16))) double ric_lds[];      // plant_riccati_lds(nq, nu), BOX: plant_riccati_box_lds(nq, nu)
     const int rb = blockIdx.x;
     if (rb >= L.B) return;                                                // uniform over the workgroup
     PlantRiccatiGroup team;
-    plant_riccati_chain_as<LIN>(L, rb, ric_lds, team);
+    plant_riccati_chain_as<LIN, BOX>(L, rb, ric_lds, team);
 }
 
 namespace {
@@ -75,33 +81,64 @@ RiccatiWs g_riccati_ws[PLANT_MAX_DEVICES];
 }  // namespace cimpc
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------
-// Validate (no device needed), then on the tape's device and the plant workspace's private stream: one upload (Q | Qf | R | q | r), one
-// launch, one read-back (K | k | P0 | p0 | dV | status | n_cut), one synchronize.
-extern "C" int cimpc_plant_tape_lqr(cimpc_plant_tape tape, int laps, int n_Q, const double* Q, const double* Qf, int n_R, const double* R,
-                                    const double* q, const double* r, double rho, int n_keep, double* K, double* k, double* P0, double* p0,
-                                    double* dV, int* status, int* n_cut) {
+// Validate (no device needed), then on the tape's device and the plant workspace's private stream: one upload (Q | Qf | R | q | r, and
+// for the limited pass rho | u_lo | u_hi | u_nom), one launch, one read-back (K | k | P0 | p0 | dV | status | n_cut | clamped), one
+// synchronize.  box: the call came through cimpc_plant_tape_lqr_box; every refusal leaves its reason for cimpc_last_error(NULL).
+static int plant_tape_lqr_call(const char* entry, bool box, cimpc_plant_tape tape, int laps, int n_Q, const double* Q, const double* Qf, int n_R,
+                               const double* R, const double* q, const double* r, int n_rho, const double* rho_b, int n_keep, double* K, double* k,
+                               double* P0, double* p0, double* dV, int* status, int* n_cut, int n_lim, const double* u_lo, const double* u_hi,
+                               const double* u_nom, int* clamped) {
     using namespace cimpc;
-    if (!tape || !Q || !Qf || !R || !K || !status || !n_cut) return CIMPC_ERR_INVALID;
-    if (!(rho >= 0.0) || !std::isfinite(rho)) return CIMPC_ERR_INVALID;
-    if (laps < 1 || n_Q < 1 || n_R < 1 || n_keep < 1) return CIMPC_ERR_INVALID;
-    if ((q != nullptr) != (r != nullptr)) return CIMPC_ERR_INVALID;
-    if (laps > 1 && q) return CIMPC_ERR_INVALID;                          // a periodic chain has no linear terms
-    if (!q && (k || p0 || dV)) return CIMPC_ERR_INVALID;
-    const PlantTapeBuffers& buf = tape->buf;
+    auto refuse = [entry](const char* why) { set_global_error(std::string(entry) + ": " + why); return CIMPC_ERR_INVALID; };
+    if (!tape || !Q || !Qf || !R || !K || !status || !n_cut || !rho_b) return refuse("a null tape, Q, Qf, R, K, status, n_cut or rho");
+    if (laps < 1 || n_Q < 1 || n_R < 1 || n_keep < 1) return refuse("laps, n_Q, n_R or n_keep below 1");
+    const bool limits = u_lo || u_hi;
+    if (limits) {                                                         // what the limited pass needs, each by its own reason
+        if (!u_lo || !u_hi) return refuse("one of u_lo, u_hi without the other");
+        if (!u_nom) return refuse("limits without u_nom");
+        if (laps > 1) return refuse("limits with laps > 1");
+        if (!q || !r) return refuse("limits without q, r");
+    }
+    if ((q != nullptr) != (r != nullptr)) return refuse("one of q, r without the other");
+    if (laps > 1 && q) return refuse("linear terms with laps > 1");       // a periodic chain has no linear terms
+    if (!q && (k || p0 || dV)) return refuse("k, p0 or dV without q, r");
     const int B = tape->B, T = tape->T, n_cols = tape->n_cols;
-    if (B < 1 || T < 1 || buf.device < 0 || buf.device >= PLANT_MAX_DEVICES || !buf.d_dz || !buf.d_status) return CIMPC_ERR_INVALID;
-    if ((n_Q != 1 && n_Q != T) || (n_R != 1 && n_R != T) || n_keep > T) return CIMPC_ERR_INVALID;
-    if ((long long)laps * T > (1 << 30)) return CIMPC_ERR_INVALID;
+    if (n_rho != 1 && n_rho != B) return refuse("n_rho neither 1 nor B");
+    if (limits && n_lim != 1 && n_lim != B) return refuse("n_lim neither 1 nor B");
+    for (int b = 0; b < n_rho; ++b)
+        if (!(rho_b[b] >= 0.0) || !std::isfinite(rho_b[b])) return refuse("a rho that is negative or not finite");
+    if (!q && (n_rho != 1 || clamped)) return refuse("a rho per robot or clamped without q, r");
+    if (limits) {                                                         // the limits' entries: the model's nu by the tape's model id alone
+        PlantModel named{};
+        if (!plant_model_by_id(tape->model, &named) || named.nu < 1) return refuse("a model without controls");
+        for (size_t e = 0; e < (size_t)n_lim * named.nu; ++e) {
+            if (u_lo[e] != u_lo[e] || u_hi[e] != u_hi[e]) return refuse("a NaN limit");
+            if (u_lo[e] > u_hi[e]) return refuse("u_lo above u_hi");
+        }
+    }
+    const PlantTapeBuffers& buf = tape->buf;
+    if (B < 1 || T < 1 || buf.device < 0 || buf.device >= PLANT_MAX_DEVICES || !buf.d_dz || !buf.d_status) return refuse("a closed or empty tape");
+    if ((n_Q != 1 && n_Q != T) || (n_R != 1 && n_R != T) || n_keep > T) return refuse("n_Q or n_R neither 1 nor T, or n_keep above T");
+    if ((long long)laps * T > (1 << 30)) return refuse("laps T beyond 2^30");
     const PlantModel& M = buf.M;
     const int nq = M.nq, nu = M.nu, nr = M.nq + M.nc + M.nb();
-    if (nu < 1 || n_cols < 2 * nq + nu || !plant_riccati_fits(nq, nu)) return CIMPC_ERR_INVALID;
+    if (nu < 1 || n_cols < 2 * nq + nu || !plant_riccati_fits(nq, nu)) return refuse("a model without controls, or a tape without the control columns");
+    if (box && q && (nu > PLANT_BOXQP_MAX_M || plant_riccati_box_lds(nq, nu) > PLANT_RIC_MAX_LDS)) return refuse("a model too large for the limited pass");
+    if (limits)
+        for (size_t e = 0; e < (size_t)T * B * nu; ++e)
+            if (!std::isfinite(u_nom[e])) return refuse("a non-finite entry of u_nom");
+    const bool boxed = box && q;                                          // the limited chain: plant_riccati_kernel<true, true>
+    const double rho = rho_b[0];
     const size_t n = (size_t)2 * nq, m = (size_t)nu, nn = n * n, mm = m * m, nB = (size_t)B;
     // the staging buffers, in the order of the argument list
     const size_t i_Q = (size_t)n_Q * nn, i_R = (size_t)n_R * mm, i_q = q ? (size_t)(T + 1) * nB * n : 0, i_r = r ? (size_t)T * nB * m : 0;
-    const size_t o_Qf = i_Q, o_R = o_Qf + nn, o_q = o_R + i_R, o_r = o_q + i_q, n_in = o_r + i_r;
+    const size_t i_rho = boxed ? (size_t)n_rho : 0, i_lim = limits ? (size_t)n_lim * m : 0, i_un = limits ? (size_t)T * nB * m : 0;
+    const size_t o_Qf = i_Q, o_R = o_Qf + nn, o_q = o_R + i_R, o_r = o_q + i_q, o_rho = o_r + i_r, o_lo = o_rho + i_rho, o_hi = o_lo + i_lim,
+                 o_un = o_hi + i_lim, n_in = o_un + i_un;
     const size_t n_K = (size_t)n_keep * nB * m * n, n_k = k ? (size_t)n_keep * nB * m : 0, n_P = P0 ? nB * nn : 0, n_p = p0 ? nB * n : 0,
                  n_V = dV ? nB * 2 : 0;
-    const size_t o_k = n_K, o_P = o_k + n_k, o_p = o_P + n_P, o_V = o_p + n_p, o_st = o_V + n_V, n_out = o_st + nB;      // 2 B ints in B doubles
+    const size_t o_k = n_K, o_P = o_k + n_k, o_p = o_P + n_P, o_V = o_p + n_p, o_st = o_V + n_V, o_cl = o_st + nB,      // 2 B ints in B doubles
+                 n_cl = boxed && clamped ? ((size_t)n_keep * nB + 1) / 2 : 0, n_out = o_cl + n_cl;
     std::vector<double> up(n_in);
     const std::unique_ptr<double[]> out(new double[n_out]);      // not value-initialized: K alone is 36 MB at quadruped B = 256, T = 100
     std::memcpy(up.data(), Q, i_Q * sizeof(double));
@@ -109,7 +146,13 @@ extern "C" int cimpc_plant_tape_lqr(cimpc_plant_tape tape, int laps, int n_Q, co
     std::memcpy(up.data() + o_R, R, i_R * sizeof(double));
     if (q) std::memcpy(up.data() + o_q, q, i_q * sizeof(double));
     if (r) std::memcpy(up.data() + o_r, r, i_r * sizeof(double));
-    const size_t lds = plant_riccati_lds(nq, nu);
+    if (boxed) std::memcpy(up.data() + o_rho, rho_b, i_rho * sizeof(double));
+    if (limits) {
+        std::memcpy(up.data() + o_lo, u_lo, i_lim * sizeof(double));
+        std::memcpy(up.data() + o_hi, u_hi, i_lim * sizeof(double));
+        std::memcpy(up.data() + o_un, u_nom, i_un * sizeof(double));
+    }
+    const size_t lds = boxed ? plant_riccati_box_lds(nq, nu) : plant_riccati_lds(nq, nu);
     std::lock_guard<std::mutex> lock(g_plant_mu);
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
@@ -127,7 +170,12 @@ extern "C" int cimpc_plant_tape_lqr(cimpc_plant_tape tape, int laps, int n_Q, co
             PlantRiccati L{buf.d_dz, buf.d_status, I, I + o_Qf, I + o_R, q ? I + o_q : nullptr, r ? I + o_r : nullptr,
                            O, k ? O + o_k : nullptr, P0 ? O + o_P : nullptr, p0 ? O + o_p : nullptr, dV ? O + o_V : nullptr,
                            d_status, d_status + B, B, T, nq, nu, nr, n_cols, laps, n_Q, n_R, n_keep, rho};
-            auto kernel = q ? plant_riccati_kernel<true> : plant_riccati_kernel<false>;
+            if (boxed) {
+                L.rho_b = I + o_rho; L.n_rho = n_rho;
+                if (limits) { L.u_lo = I + o_lo; L.u_hi = I + o_hi; L.u_nom = I + o_un; L.n_lim = n_lim; }
+                if (clamped) L.clamped = reinterpret_cast<int*>(O + o_cl);
+            }
+            auto kernel = boxed ? plant_riccati_kernel<true, true> : q ? plant_riccati_kernel<true> : plant_riccati_kernel<false>;
             ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
             if (ok) {
                 hipLaunchKernelGGL(kernel, dim3(B), dim3(RIC_THREADS), lds, st, L);
@@ -146,5 +194,23 @@ extern "C" int cimpc_plant_tape_lqr(cimpc_plant_tape tape, int laps, int n_Q, co
     if (dV) std::memcpy(dV, out.get() + o_V, n_V * sizeof(double));
     std::memcpy(status, out.get() + o_st, nB * sizeof(int));
     std::memcpy(n_cut, reinterpret_cast<const int*>(out.get() + o_st) + B, nB * sizeof(int));
+    if (n_cl) std::memcpy(clamped, out.get() + o_cl, (size_t)n_keep * nB * sizeof(int));
     return CIMPC_OK;
+}
+
+extern "C" int cimpc_plant_tape_lqr(cimpc_plant_tape tape, int laps, int n_Q, const double* Q, const double* Qf, int n_R, const double* R,
+                                    const double* q, const double* r, double rho, int n_keep, double* K, double* k, double* P0, double* p0,
+                                    double* dV, int* status, int* n_cut) {
+    return plant_tape_lqr_call("cimpc_plant_tape_lqr", false, tape, laps, n_Q, Q, Qf, n_R, R, q, r, 1, &rho, n_keep, K, k, P0, p0, dV, status, n_cut,
+                               1, nullptr, nullptr, nullptr, nullptr);
+}
+
+// The limited pass: cimpc_plant_tape_lqr with rho as n_rho (1 or B) values, and n_lim (1 or B) rows of limits u_lo, u_hi (both null: no
+// limits) about the tape's applied controls u_nom (T x B x nu); clamped (n_keep x B, may be null): bit i set where control i was clamped.
+extern "C" int cimpc_plant_tape_lqr_box(cimpc_plant_tape tape, int laps, int n_Q, const double* Q, const double* Qf, int n_R, const double* R,
+                                        const double* q, const double* r, int n_rho, const double* rho, int n_keep, double* K, double* k,
+                                        double* P0, double* p0, double* dV, int* status, int* n_cut, int n_lim, const double* u_lo,
+                                        const double* u_hi, const double* u_nom, int* clamped) {
+    return plant_tape_lqr_call("cimpc_plant_tape_lqr_box", true, tape, laps, n_Q, Q, Qf, n_R, R, q, r, n_rho, rho, n_keep, K, k, P0, p0, dV, status,
+                               n_cut, n_lim, u_lo, u_hi, u_nom, clamped);
 }

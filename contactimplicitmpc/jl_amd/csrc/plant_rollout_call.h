@@ -29,9 +29,12 @@ struct PlantRolloutGrad {
 };
 
 // A closed loop (the _feedback entry points): the host schedule and where u_applied (T x B x nu) and fb_err (T x B x 2nq) go
+// u_lo, u_hi (both or neither): the limited law of plant_feedback.h, n_lim x nu host rows, n_lim 1 or B; not with grad.
 struct PlantRolloutLoop {
     const cimpc_feedback* fb;
     double *u_applied, *fb_err;
+    const double *u_lo = nullptr, *u_hi = nullptr;
+    int n_lim = 1;
 };
 
 // Everything a rollout call is given.  A simulator step is T = 1, steps_per_launch = 1, one u and one w row per robot, n_mu = 1 and
@@ -76,6 +79,7 @@ struct PlantRolloutLayout {
     PlantSpan z;                                   // d_z: T x B x nz, with grad
     PlantSpan dz, grad_status;                     // d_grad, d_grad_st - or, with a tape, the tape's d_dz and d_status, and need_grad* = 0
     PlantSpan fb_K, x_ref, u_applied, fb_err;      // d_fb, with loop; with a tape K is read from the tape's d_fb_K and the K region stays unused
+    PlantSpan u_lo, u_hi;                          // d_fb, behind them, with limits: n_lim x nu each
     size_t need_in = 0, need_out = 0, need_st = 0, need_z = 0, need_grad = 0, need_grad_st = 0, need_fb = 0;
 };
 
@@ -113,6 +117,10 @@ inline PlantRolloutLayout plant_rollout_layout(const PlantModel& M, const PlantR
         L.x_ref = next(n_x);
         L.u_applied = next(L.TB * nu);
         L.fb_err = next(L.TB * 2 * nq);
+        if (c.loop->u_lo) {
+            L.u_lo = next((size_t)c.loop->n_lim * nu);
+            L.u_hi = next((size_t)c.loop->n_lim * nu);
+        }
         L.need_fb = end();
     }
     return L;
@@ -146,6 +154,10 @@ inline int plant_rollout_check(const PlantRolloutCall& c, PlantModel* M, bool* r
         const PlantRolloutLayout L = plant_rollout_layout(*M, c);
         for (size_t i = 0; i < L.fb_K.n; ++i) if (!std::isfinite(f->K[i])) return CIMPC_ERR_INVALID;
         for (size_t i = 0; i < L.x_ref.n; ++i) if (!std::isfinite(f->x_ref[i])) return CIMPC_ERR_INVALID;
+        if (c.loop->u_lo || c.loop->u_hi) {      // limits: both arrays, no NaN, u_lo <= u_hi, and no gradients through the clamp
+            if (!c.loop->u_lo || !c.loop->u_hi || c.grad || (c.loop->n_lim != 1 && c.loop->n_lim != B)) return CIMPC_ERR_INVALID;
+            for (size_t i = 0; i < L.u_lo.n; ++i) if (!(c.loop->u_lo[i] <= c.loop->u_hi[i])) return CIMPC_ERR_INVALID;
+        }
     }
     return CIMPC_OK;
 }

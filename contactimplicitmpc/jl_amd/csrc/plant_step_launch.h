@@ -12,7 +12,7 @@ namespace cimpc {
 // What the steps 0 .. T-1 of a rollout of B robots read and write, all device memory; the arrays are those of PlantRollout
 // (plant_kernel.hip): q (T + 2) x B x nq with rows 0 and 1 set, the u and w schedules (w null: none), mu (n_mu = B; with n_mu = 1 mu0 is
 // used), per-step gamma, b, status, iters, z (null: not stored).  fb.K non-null: the closed loop of plant_feedback.h, with u_applied
-// T x B x nu and fb_err T x B x 2nq.
+// T x B x nu and fb_err T x B x 2nq; lim.u_lo non-null (with fb.K): the limited law, n_lim = 1 or B rows of nu limits.
 struct PlantStepArrays {
     double* q;
     const double *u, *w, *mu;
@@ -23,6 +23,7 @@ struct PlantStepArrays {
     double* z;
     PlantFeedback fb;
     double *u_applied, *fb_err;
+    PlantFeedbackLimits lim{};
 };
 
 // The rollout's chunks (plant_rollout_plan.h) back to back on `st`; the trajectory buffer carries the state, nothing is synchronized.

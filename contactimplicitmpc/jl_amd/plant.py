@@ -20,10 +20,14 @@ linear cost terms the feedforward, for every robot along the trajectory it took;
 `TrackingCost` is the quadratic tracking cost of a rollout, `RolloutTape.linesearch` rolls several step lengths of those gains for every robot in
 ONE closed-loop rollout, costs them, chooses per robot and returns the chosen trajectories with their tape (`cimpc_plant_tape_linesearch`; DESIGN.md
 section 3, item 3f), and `ilqr` is the loop of the two: iLQR through contact with a per-robot regularization ladder.
+Control limits: `Feedback(u_lo=, u_hi=)` clamps the control a closed-loop step applies, `lqr(u_lo=, u_hi=, u_nom=)`
+solves a box-constrained QP per step (and takes a rho per robot), `linesearch(u_lo=, u_hi=)` runs its candidates under the clamped law, and
+`ilqr(u_lo=, u_hi=)` is control-limited iLQR on the three (`cimpc_plant_rollout_feedback_limits`, `cimpc_plant_tape_lqr_box`,
+`cimpc_plant_tape_linesearch_box`).
 Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble
 solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain, tests/test_gpu_plant_tangent.py against restatements of the forward chain,
 tests/test_gpu_plant_riccati.py against restatements of the backward pass, tests/test_gpu_plant_linesearch.py the line search against the
-rollouts it replaces and `ilqr` against a known answer.
+rollouts it replaces and `ilqr` against a known answer, tests/test_gpu_plant_boxqp.py the limited calls against the host header and each other.
 """
 from __future__ import annotations
 
@@ -123,11 +127,17 @@ class Feedback:
     q0 = q1 − n_sample (q1 − q[t]) and k = min(t // hold, K_f − 1) (DESIGN.md section 3, item 3c).  K (K_f, nu, 2nq) shared by every robot
     or (K_f, B, nu, 2nq) - `gains.reference_gains`' output is the first -, x_ref (K_f, 2nq) or (K_f, B, 2nq), shared or per robot together;
     hold: simulator steps a row is held for, the last row from there on; n_sample: the rollout's N_sample when None.  The gains are
-    nominal, like u: a step applies K[k] / N_sample beside u[k] / N_sample."""
+    nominal, like u: a step applies K[k] / N_sample beside u[k] / N_sample.
+    u_lo, u_hi ((nu,) shared or (B, nu), both or neither; ±inf = no limit, NaN refused, u_lo ≤ u_hi): control limits (DESIGN.md section 3,
+    item 3g).  The step then applies, and `u_applied` stores, limit(u_t) = u_lo where u_t < u_lo, u_hi where u_t > u_hi, u_t otherwise -
+    the limits bound the control a simulator step applies, nothing is divided by N_sample; `fb_err` is unchanged.  The derivative of the
+    clamp is not built: `rollout_tape`, `rollout(diff_sol=True)` and `rollout_torch` refuse a `Feedback` with limits."""
     K: object
     x_ref: object
     hold: int = 1
     n_sample: object = None
+    u_lo: object = None
+    u_hi: object = None
 
 
 @dataclasses.dataclass
@@ -139,6 +149,8 @@ class _FeedbackArrays:
     hold: int
     n_sample: float
     shared: bool
+    u_lo: object = None      # (n_lim, nu) each, n_lim 1 or B, or both None
+    u_hi: object = None
 
     K_f = property(lambda self: self.K.shape[0])
 
@@ -164,7 +176,24 @@ def _feedback_arrays(model: str, fb: Feedback, B: int, N_sample: int) -> _Feedba
         raise ValueError("Feedback.K and Feedback.x_ref must be finite")
     if shared:
         K, xr = K[:, None], xr[:, None]
-    return _FeedbackArrays(np.ascontiguousarray((K / int(N_sample)).transpose(0, 1, 3, 2)), np.ascontiguousarray(xr), int(fb.hold), n_sample, shared)
+    lo, hi = _limit_arrays(fb.u_lo, fb.u_hi, B, nu, "Feedback.")
+    return _FeedbackArrays(np.ascontiguousarray((K / int(N_sample)).transpose(0, 1, 3, 2)), np.ascontiguousarray(xr), int(fb.hold), n_sample, shared, lo, hi)
+
+
+def _limit_arrays(u_lo, u_hi, B: int, nu: int, what: str = ""):
+    """Control limits checked and laid out for the library: (n_lim, nu) each with n_lim 1 or B, or (None, None)."""
+    if u_lo is None and u_hi is None:
+        return None, None
+    if u_lo is None or u_hi is None:
+        raise ValueError(f"{what}u_lo and {what}u_hi go together")
+    lo, hi = (np.ascontiguousarray(np.atleast_2d(np.asarray(a, dtype=np.float64))) for a in (u_lo, u_hi))
+    if lo.shape != hi.shape or lo.shape not in ((1, nu), (B, nu)):
+        raise ValueError(f"{what}u_lo and {what}u_hi must be ({nu},) or ({B}, {nu}), got {lo.shape} and {hi.shape}")
+    if np.isnan(lo).any() or np.isnan(hi).any():
+        raise ValueError(f"{what}u_lo and {what}u_hi must not be NaN (use -inf, +inf for no limit)")
+    if (lo > hi).any():
+        raise ValueError(f"{what}u_lo must not exceed {what}u_hi")
+    return lo, hi
 
 
 @dataclasses.dataclass
@@ -206,6 +235,11 @@ def _rollout_call(model: str, q0, q1, ua, hold_u: int, wa, hold_w: int, mua, h: 
         cfb = _lib.Feedback(dp(feedback.K), dp(feedback.x_ref), feedback.K_f, feedback.K.shape[1], feedback.hold, feedback.n_sample)
         res.u_applied, res.fb_err = np.zeros((T, B, nu)), np.zeros((T, B, 2 * nq))
         sfx, loop = "_feedback", (C.byref(cfb), dp(res.u_applied), dp(res.fb_err))
+        if feedback.u_lo is not None:
+            if grad is not None:
+                raise ValueError("a Feedback with control limits has no gradients: the derivative of the clamp is not built (rollout_tape, "
+                                 "diff_sol=True and rollout_torch refuse it; DESIGN.md section 3, item 3g)")
+            sfx, loop = "_feedback_limits", loop + (feedback.u_lo.shape[0], dp(feedback.u_lo), dp(feedback.u_hi))
     gst = np.zeros((T, B), dtype=np.int32)
     if grad is None:
         name, more = "cimpc_plant_rollout", ()
@@ -773,7 +807,7 @@ class RolloutTape:
         return np.ascontiguousarray(np.concatenate([q[:, t1], q[:, t1 + 1]], axis=2).transpose(1, 2, 0))
 
     # ---- the LQ backward pass ---------------------------------------------------------------------------------------------------------------
-    def lqr(self, Q, R, Qf=None, q=None, r=None, rho: float = 0.0, laps: int = 1, keep=None) -> "TapeGains":
+    def lqr(self, Q, R, Qf=None, q=None, r=None, rho=0.0, laps: int = 1, keep=None, *, u_lo=None, u_hi=None, u_nom=None) -> "TapeGains":
         """Time-varying LQR gains along the trajectory this tape recorded (`cimpc_plant_tape_lqr`): ONE launch,
         a workgroup per robot walking the tape's blocks backwards; nothing but the weights goes up and the gains come down.  State
         x_t = [q[t]; q[t+1]] (n = 2nq), control u_t (m = nu), A_t = [0 I; D1 D2], B_t = [0; Du] from the step's block (on a closed-loop tape
@@ -782,12 +816,22 @@ class RolloutTape:
         terminal one): with them the feedforward k, p0 and dV are computed, δu_t = k_t − K_t δx_t.  rho ≥ 0 is added to the diagonal of
         Quu before it is factored; laps > 1 walks the tape that many times as a periodic chain (`gains.reference_gains`' N; without q, r)
         and returns the last lap; keep (default T) is the number of leading steps whose gains come back.  A robot whose chain met a
-        singular or non-finite step has status[b] = that walk step (1-based) and zeros; nothing is raised for it."""
+        singular or non-finite step has status[b] = that walk step (1-based) and zeros; nothing is raised for it.
+        THE LIMITED PASS (`cimpc_plant_tape_lqr_box`): rho may be a (B,) array, one per robot, and u_lo, u_hi
+        ((nu,) shared or (B, nu); ±inf = no limit) bound the control u_nom[t] + δu_t, u_nom (T, B, nu) being the controls this tape's steps
+        applied.  Each step then solves min ½x'Gx + Qu'x over u_lo − u_nom[t] ≤ x ≤ u_hi − u_nom[t] by projected Newton: rows of K of the
+        clamped controls are zero, k lies in the box, and `TapeGains.clamped` (keep, B) has bit i set where control i was clamped.  Both need
+        q, r and laps = 1; a robot whose box QP did not converge gets status[b] like a singular step.  A scalar rho without limits is the
+        call it always was."""
         if self.closed:
             raise ValueError("the tape is closed")
         mid, nq, nu, nc, fd, nw = model_dims(self.model)
         B, T, n, m = self.B, self.T, 2 * nq, nu
         keep = T if keep is None else int(keep)
+        rho_b = np.ascontiguousarray(rho, dtype=np.float64).reshape(-1) if np.ndim(rho) else None
+        limited = u_lo is not None or u_hi is not None
+        if rho_b is not None or limited:
+            return self._lqr_box(Q, R, Qf, q, r, np.array([float(rho)]) if rho_b is None else rho_b, int(laps), keep, u_lo, u_hi, u_nom)
         if (q is None) != (r is None):
             raise ValueError("q and r go together")
         if not 1 <= keep <= T:
@@ -796,18 +840,7 @@ class RolloutTape:
             raise ValueError("laps must be at least 1, and 1 with linear terms")
         if not (np.isfinite(rho) and rho >= 0.0):
             raise ValueError("rho must be finite and not negative")
-
-        def weight(a, k, what):
-            a = np.asarray(a, dtype=np.float64)
-            if a.shape not in ((k, k), (T, k, k)):
-                raise ValueError(f"{what} must be ({k}, {k}) or ({T}, {k}, {k}), got {a.shape}")
-            return np.ascontiguousarray(np.swapaxes(a, -1, -2)), (1 if a.ndim == 2 else T)      # column-major blocks
-        Qc, n_Q = weight(Q, n, "Q")
-        Rc, n_R = weight(R, m, "R")
-        Qf = (Qc if n_Q == 1 else Qc[T - 1]) if Qf is None else np.swapaxes(np.asarray(Qf, dtype=np.float64), -1, -2)
-        Qf = np.ascontiguousarray(Qf)
-        if Qf.shape != (n, n):
-            raise ValueError(f"Qf must be ({n}, {n})")
+        Qc, n_Q, Rc, n_R, Qf = self._lqr_weights(Q, R, Qf, n, m)
         lin = q is not None
         if lin:
             q, r = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(r, dtype=np.float64)
@@ -825,9 +858,65 @@ class RolloutTape:
         return TapeGains(K=np.ascontiguousarray(K.transpose(0, 1, 3, 2)), k=k, P0=np.ascontiguousarray(P0.transpose(0, 2, 1)), p0=p0, dV=dV,
                          status=status, n_cut=n_cut, N_sample=self._N_sample, K_blocks=K)
 
+    def _lqr_weights(self, Q, R, Qf, n, m):
+        """Q, R, Qf as the library reads them: column-major blocks, and how many of each."""
+        T = self.T
+
+        def weight(a, k, what):
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape not in ((k, k), (T, k, k)):
+                raise ValueError(f"{what} must be ({k}, {k}) or ({T}, {k}, {k}), got {a.shape}")
+            return np.ascontiguousarray(np.swapaxes(a, -1, -2)), (1 if a.ndim == 2 else T)      # column-major blocks
+        Qc, n_Q = weight(Q, n, "Q")
+        Rc, n_R = weight(R, m, "R")
+        Qf = (Qc if n_Q == 1 else Qc[T - 1]) if Qf is None else np.swapaxes(np.asarray(Qf, dtype=np.float64), -1, -2)
+        Qf = np.ascontiguousarray(Qf)
+        if Qf.shape != (n, n):
+            raise ValueError(f"Qf must be ({n}, {n})")
+        return Qc, n_Q, Rc, n_R, Qf
+
+    def _lqr_box(self, Q, R, Qf, q, r, rho, laps, keep, u_lo, u_hi, u_nom) -> "TapeGains":
+        """`lqr` through `cimpc_plant_tape_lqr_box`: rho (1,) or (B,), limits or None.  The library refuses what does not fit, by reason."""
+        mid, nq, nu, nc, fd, nw = model_dims(self.model)
+        B, T, n, m = self.B, self.T, 2 * nq, nu
+        if q is None or r is None:
+            raise ValueError("a rho per robot and control limits need the linear terms q and r")
+        if not 1 <= keep <= T:
+            raise ValueError(f"keep must be in 1 .. {T}")
+        if rho.size not in (1, B):
+            raise ValueError(f"rho must be a number or one per robot ({B}), got {rho.size}")
+        Qc, n_Q, Rc, n_R, Qf = self._lqr_weights(Q, R, Qf, n, m)
+        q, r = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(r, dtype=np.float64)
+        if q.shape != (T + 1, B, n) or r.shape != (T, B, m):
+            raise ValueError(f"q must be ({T + 1}, {B}, {n}) and r ({T}, {B}, {m}), got {q.shape} and {r.shape}")
+        n_lim = 1
+        if u_lo is not None or u_hi is not None:
+            if u_lo is None or u_hi is None or u_nom is None:
+                raise ValueError("u_lo, u_hi and u_nom go together")
+            u_lo, u_hi = (np.ascontiguousarray(np.atleast_2d(np.asarray(a, dtype=np.float64))) for a in (u_lo, u_hi))
+            u_nom = np.ascontiguousarray(u_nom, dtype=np.float64)
+            if u_lo.shape != u_hi.shape or u_lo.shape not in ((1, m), (B, m)):
+                raise ValueError(f"u_lo and u_hi must be ({m},) or ({B}, {m}), got {u_lo.shape} and {u_hi.shape}")
+            if u_nom.shape != (T, B, m):
+                raise ValueError(f"u_nom must be ({T}, {B}, {m}), got {u_nom.shape}")
+            n_lim = u_lo.shape[0]
+        K, k, p0, dV = np.zeros((keep, B, n, m)), np.zeros((keep, B, m)), np.zeros((B, n)), np.zeros((B, 2))
+        P0, status, n_cut, clamped = np.zeros((B, n, n)), np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros((keep, B), dtype=np.int32)
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        lib = _lib.load()
+        rc = lib.cimpc_plant_tape_lqr_box(self._handle, laps, n_Q, dp(Qc), dp(Qf), n_R, dp(Rc), dp(q), dp(r), int(rho.size), dp(rho), keep, dp(K), dp(k),
+                                          dp(P0), dp(p0), dp(dV), ip(status), ip(n_cut), n_lim, dp(u_lo), dp(u_hi), dp(u_nom), ip(clamped))
+        if rc == -1:
+            raise ValueError(lib.cimpc_last_error(None).decode())
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_tape_lqr_box failed ({rc})")
+        return TapeGains(K=np.ascontiguousarray(K.transpose(0, 1, 3, 2)), k=k, P0=np.ascontiguousarray(P0.transpose(0, 2, 1)), p0=p0, dV=dV,
+                         status=status, n_cut=n_cut, N_sample=self._N_sample, K_blocks=K, clamped=clamped)
+
     # ---- the line search ----------------------------------------------------------------------------------------------------------------------
     def linesearch(self, gains: "TapeGains", q, u_applied, cost: "TrackingCost", J_nom, alphas, armijo: float = 1e-4, *, parent_rows=None,
-                   mu=None, w=None, w_hold=None, terrain=None, opts=None, steps_per_launch=None, grad_reg=None) -> "LineSearch":
+                   mu=None, w=None, w_hold=None, terrain=None, opts=None, steps_per_launch=None, grad_reg=None, u_lo=None, u_hi=None) -> "LineSearch":
         """The forward pass of an iLQR iteration about the trajectory this tape recorded (`cimpc_plant_tape_linesearch`, DESIGN.md section 3,
         item 3f): candidate c of robot b starts from q[0], q[1], applies u_t = (u_applied[t, b] + alphas[c] k_t[b]) + K_t[b] (x_ref[t] − x_t)
         around q (T + 2, B, nq), the tape's own trajectory, whose steps applied u_applied (T, B, nu); all len(alphas) (1 .. 64) candidates of
@@ -838,7 +927,10 @@ class RolloutTape:
         T B steps); a robot without an acceptable candidate keeps (q, u_applied) and the parent tape's blocks.  parent_rows = (gamma, b,
         status, iters) of the nominal: such a robot's rows of those four; without it they are not known here and come back as NaN and -1,
         never as another trajectory's.  The tape must be an open-loop one (the nominal of an iLQR iteration is).
-        mu, w, w_hold, terrain, opts, steps_per_launch, grad_reg default to what the tape was recorded with (`rollout_tape` notes them)."""
+        mu, w, w_hold, terrain, opts, steps_per_launch, grad_reg default to what the tape was recorded with (`rollout_tape` notes them).
+        u_lo, u_hi ((nu,) or (B, nu), both or neither; `cimpc_plant_tape_linesearch_box`): control limits.
+        A candidate's open-loop row is then limit(u_applied[t, b] + alphas[c] k_t[b]) and its steps apply the limited law of
+        `Feedback(u_lo=, u_hi=)`; acceptance, choice and the new tape (the open-loop tape of the chosen u_applied) are unchanged."""
         if self.closed:
             raise ValueError("the tape is closed")
         if self._N_sample != 1:
@@ -890,13 +982,15 @@ class RolloutTape:
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
         ta, nt = (None, 0) if terrain is None else _terrain_array(terrain, B)
         handle = C.c_void_p()
-        rc = _lib.load().cimpc_plant_tape_linesearch(
+        lo, hi = _limit_arrays(u_lo, u_hi, B, nu)
+        entry, limits = ("cimpc_plant_tape_linesearch", ()) if lo is None else ("cimpc_plant_tape_linesearch_box", (lo.shape[0], dp(lo), dp(hi)))
+        rc = getattr(_lib.load(), entry)(
             self._handle, int(ctx.get("steps_per_launch", 0)), nt, ta, dp(q), dp(u_applied), dp(wa), 1 if wa is None else wa.shape[0],
             1 if wa is None else wa.shape[1], int(ctx.get("w_hold", 1)), dp(mua), mua.size, float(self._h), C.byref(o), dp(cont(Kb)), dp(cont(gains.k)),
             dp(cont(gains.dV)), dp(J_nom), na, dp(alphas), float(armijo), C.byref(cc), reg, dp(J), ip(ok), ip(choice), dp(cq), dp(cu), dp(cg), dp(cb),
-            ip(st), ip(it), dp(lq), dp(lr), ip(gst), C.byref(handle))
+            ip(st), ip(it), dp(lq), dp(lr), ip(gst), C.byref(handle), *limits)
         if rc != 0:
-            raise _lib.CimpcError(f"cimpc_plant_tape_linesearch failed ({rc})")
+            raise _lib.CimpcError(f"{entry} failed ({rc})")
         tape = RolloutTape(handle, self.model, gst, None, self._v1, self._h, (T, B, nu), 1, None if wa is None else np.shape(ctx["w"]),
                            int(ctx.get("w_hold", 1)), self._mu_shared, q1_shape=self._q1_shape, mu_shape=self._mu_shape)
         tape._context = ctx
@@ -922,7 +1016,8 @@ class TapeGains:
     """What `RolloutTape.lqr` returns: K (keep, B, nu, 2nq), the gains of δu_t = k_t − K_t δx_t against x_t = [q[t]; q[t+1]]; P0 (B, 2nq, 2nq),
     the value's quadratic at the first step; with linear terms k (keep, B, nu), p0 (B, 2nq) and dV (B, 2) = (Σ k'Qu, Σ ½ k'Quu k), else
     None; status (B,): 0, or the 1-based walk step at which that robot's chain ended (its rows are zeros then); n_cut (B,): the steps of a
-    robot whose gradient status is 0 (zero blocks, walked through)."""
+    robot whose gradient status is 0 (zero blocks, walked through); clamped (keep, B) ints from the limited pass (`lqr(u_lo=, u_hi=)` or a
+    rho per robot), bit i set where control i was clamped at that step, else None."""
     K: np.ndarray
     k: object
     P0: np.ndarray
@@ -932,6 +1027,7 @@ class TapeGains:
     n_cut: np.ndarray
     N_sample: int = 1
     K_blocks: object = None      # K as the library wrote it, (keep, B, 2nq, nu): what `RolloutTape.linesearch` hands back without a transpose
+    clamped: object = None
 
     def feedback(self, q_traj) -> Feedback:
         """The `Feedback` that applies these gains around the trajectory q_traj (T + 2, B, nq) they were computed on: K · N_sample (the
@@ -1068,7 +1164,8 @@ class ILQRResult:
 
 def ilqr(model: str, q1, v1, u, h: float, mu, cost: TrackingCost, *, alphas=(1.0, 0.5, 0.25, 0.125), max_iter: int = 10, rho0: float = 1e-6,
          rho_factor: float = 10.0, rho_max: float = 1e6, tol: float = 1e-6, armijo: float = 1e-4, w=None, w_hold: int = 1,
-         opts: InteriorPointOptions = SIM_OPTS, terrain=None, steps_per_launch: int = 0, grad_reg=None, grad_cols=None) -> ILQRResult:
+         opts: InteriorPointOptions = SIM_OPTS, terrain=None, steps_per_launch: int = 0, grad_reg=None, grad_cols=None, u_lo=None,
+         u_hi=None) -> ILQRResult:
     """iLQR through contact on the device plant: from the rollout of the controls u (T, nu) or (T, B, nu)
     (applied as they stand), per iteration `RolloutTape.lqr` about the nominal with the cost's linear terms, then `RolloutTape.linesearch` over
     alphas - every step length of every robot in one closed-loop rollout - and the chosen candidates become the nominal.  The regularization
@@ -1076,8 +1173,20 @@ def ilqr(model: str, q1, v1, u, h: float, mu, cost: TrackingCost, *, alphas=(1.0
     a scalar, so it runs once per distinct level in use and the robots' rows are merged on the host.  A robot is no longer updated once its
     accepted decrease is below tol |J| or its rho exceeds rho_max; it still rides along, rejected by construction.  A backward pass that
     ends early at a robot's rho (a singular Quu) counts as a rejection: one level up.  Tapes of superseded nominals are closed, the
-    current one too if a call raises."""
+    current one too if a call raises.
+    CONTROL LIMITS (u_lo, u_hi: (nu,) or (B, nu), both or neither; ±inf = no limit): control-limited DDP.  The
+    initial u is first clipped into the box, u_lo where it is below, u_hi where it is above.  Each iteration is then ONE `lqr` launch with the
+    per-robot rho array and the limits about the nominal's controls (a box-constrained QP per step), and the line search's candidates
+    apply limit(limit(u + alpha k) + K (x_ref - x)): every nominal's controls lie in the box exactly.  `gains.clamped` tells which
+    controls each step clamped.  Without limits the code path is the one above, unchanged."""
     mid, nq, nu, nc, fd, nw = model_dims(model)
+    limited = u_lo is not None or u_hi is not None
+    if limited:
+        u = np.asarray(u, dtype=np.float64)
+        lo, hi = _limit_arrays(u_lo, u_hi, np.atleast_2d(np.asarray(q1)).shape[0], nu)
+        if u.ndim == 2:      # one schedule: it stays one under shared limits, and becomes one per robot under per-robot limits
+            u = u if lo.shape[0] == 1 else np.repeat(u[:, None], lo.shape[0], axis=1)
+        u = np.where(u < lo, lo, np.where(u > hi, hi, u))      # the limiter, element by element: (T, [B,] nu) against (1 or B, nu)
     ok, q, ua, gamma, b, status, iters, tape = rollout_tape(model, q1, v1, u, h, mu, w=w, w_hold=w_hold, opts=opts, terrain=terrain,
                                                             steps_per_launch=steps_per_launch, grad_reg=grad_reg, grad_cols=grad_cols)
     T, B = ua.shape[:2]
@@ -1091,12 +1200,17 @@ def ilqr(model: str, q1, v1, u, h: float, mu, cost: TrackingCost, *, alphas=(1.0
             rho = rho0 * float(rho_factor) ** level
             Kb, k, dV = np.zeros((T, B, 2 * nq, nu)), np.zeros((T, B, nu)), np.zeros((B, 2))
             lq_status, n_cut = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
-            for val in np.unique(rho):
-                rows = rho == val
-                g = tape.lqr(cost.Q, cost.R, cost.Qf, q=lq, r=lr, rho=float(val))
-                Kb[:, rows], k[:, rows], dV[rows], lq_status[rows], n_cut[rows] = g.K_blocks[:, rows], g.k[:, rows], g.dV[rows], g.status[rows], g.n_cut[rows]
-            gains = TapeGains(K=Kb.transpose(0, 1, 3, 2), k=k, P0=None, p0=None, dV=dV, status=lq_status, n_cut=n_cut, K_blocks=Kb)
-            ls = tape.linesearch(gains, q, ua, cost, np.where(active & (lq_status == 0), J, -np.inf), alphas, armijo, parent_rows=(gamma, b, status, iters))
+            if limited:      # one launch: the rho of every robot and the limits about the nominal's controls
+                gains = tape.lqr(cost.Q, cost.R, cost.Qf, q=lq, r=lr, rho=rho, u_lo=u_lo, u_hi=u_hi, u_nom=ua)
+                lq_status = gains.status
+            else:
+                for val in np.unique(rho):
+                    rows = rho == val
+                    g = tape.lqr(cost.Q, cost.R, cost.Qf, q=lq, r=lr, rho=float(val))
+                    Kb[:, rows], k[:, rows], dV[rows], lq_status[rows], n_cut[rows] = g.K_blocks[:, rows], g.k[:, rows], g.dV[rows], g.status[rows], g.n_cut[rows]
+                gains = TapeGains(K=Kb.transpose(0, 1, 3, 2), k=k, P0=None, p0=None, dV=dV, status=lq_status, n_cut=n_cut, K_blocks=Kb)
+            ls = tape.linesearch(gains, q, ua, cost, np.where(active & (lq_status == 0), J, -np.inf), alphas, armijo, parent_rows=(gamma, b, status, iters),
+                                 u_lo=u_lo, u_hi=u_hi)
             accepted = ls.choice >= 0
             J_new = np.where(accepted, ls.J[np.maximum(ls.choice, 0), np.arange(B)], J)
             hist["J"].append(J_new); hist["rho"].append(rho); hist["accepted"].append(accepted)

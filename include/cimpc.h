@@ -552,6 +552,21 @@ int cimpc_plant_rollout_feedback(int model, int B, int T, int steps_per_launch,
                                  const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
                                  double* q, double* gamma, double* b, int* status, int* iters,
                                  const cimpc_feedback* fb, double* u_applied, double* fb_err);
+/* The closed loop under control limits: cimpc_plant_rollout_feedback whose steps apply, and whose
+ * u_applied stores, limit(u_t) = u_t < u_lo ? u_lo : (u_t > u_hi ? u_hi : u_t) element by element (a NaN u_t passes through and the step
+ * does not converge); fb_err is unchanged.  u_lo, u_hi: n_lim x nu with n_lim 1 (one row for every robot) or B, -inf and +inf meaning no
+ * limit; with every limit infinite the call is cimpc_plant_rollout_feedback bit for bit.  CIMPC_ERR_INVALID before any device is touched,
+ * with its reason in cimpc_last_error(NULL): a null u_lo or u_hi, n_lim neither 1 nor B, a NaN limit, u_lo above u_hi, or whatever
+ * cimpc_plant_rollout_feedback refuses.  The tape and gradient entries take no limits: the derivative of the clamp is not built. */
+int cimpc_plant_rollout_feedback_limits(int model, int B, int T, int steps_per_launch,
+                                        int n_terrain, const cimpc_terrain* terrain,
+                                        const double* q0, const double* q1,
+                                        const double* u, int K_u, int n_u, int hold_u,
+                                        const double* w, int K_w, int n_w, int hold_w,
+                                        const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                                        double* q, double* gamma, double* b, int* status, int* iters,
+                                        const cimpc_feedback* fb, double* u_applied, double* fb_err,
+                                        int n_lim, const double* u_lo, const double* u_hi);
 /* dz: the blocks of cimpc_plant_sensitivity on (z[t, b], theta[t, b]) with theta's controls from u_applied, bit for bit. */
 int cimpc_plant_rollout_grad_feedback(int model, int B, int T, int steps_per_launch,
                                       int n_terrain, const cimpc_terrain* terrain,
@@ -636,6 +651,26 @@ int cimpc_plant_tape_lqr(cimpc_plant_tape tape, int laps, int n_Q, const double*
                          const double* q, const double* r, double rho, int n_keep,
                          double* K, double* k, double* P0, double* p0, double* dV, int* status, int* n_cut);
 
+/* ---- the limited LQ backward pass (csrc/plant_boxqp.h): control-limited DDP -----------------------------
+ * cimpc_plant_tape_lqr with two changes: rho is n_rho (1, or B: one per robot) values, each >= 0 and finite; and the controls have limits
+ * u_lo <= u <= u_hi, n_lim x m with n_lim 1 (shared) or B, -inf and +inf meaning no limit, about the tape's applied controls u_nom
+ * (T x B x m).  At every walk step the chain forms Qu, Quu, Qux and G = Quu + rho_b I as above, then, with lo = u_lo - u_nom[t, b] and
+ * hi = u_hi - u_nom[t, b], solves min 1/2 x'Gx + Qu'x, lo <= x <= hi by projected Newton (started from the limited k of the walk step
+ * before; a backtracking Armijo search on the limited step; the constants are named in csrc/plant_boxqp.h) for the clamped set c, and
+ * on the free set f:  G_ff [K_f | y] = [Qux_f | Qu_f + G_fc x_c],  K rows of c = 0,  k_f = limit(-y), k_c = x_c.  dV, P and p follow as
+ * above with these K, k.  With every limit infinite no iteration runs and every output is cimpc_plant_tape_lqr's bit for bit; a robot's
+ * outputs with rho[b] are those of the scalar call with that rho.  A direction that is no descent direction, a bad pivot, a step below
+ * the minimum or the iteration cap ends THAT robot's chain as a singular G does: status[b] = the walk step, zeros.
+ *   clamped (n_keep x B ints, may be NULL): bit i set where control i was in c at that step.
+ *   u_lo and u_hi both NULL: no limits (then n_lim, u_nom are not read).  Limits need q, r, u_nom and laps = 1; n_rho = B or clamped need
+ *   q, r.  CIMPC_ERR_INVALID before any device is touched, with its own reason in cimpc_last_error(NULL): what cimpc_plant_tape_lqr
+ *   refuses; n_rho or n_lim neither 1 nor B; a rho that is negative or not finite; one limit array without the other, limits without
+ *   u_nom, without q, r, or with laps > 1; a NaN limit; u_lo above u_hi; a non-finite entry of u_nom. */
+int cimpc_plant_tape_lqr_box(cimpc_plant_tape tape, int laps, int n_Q, const double* Q, const double* Qf, int n_R, const double* R,
+                             const double* q, const double* r, int n_rho, const double* rho, int n_keep,
+                             double* K, double* k, double* P0, double* p0, double* dV, int* status, int* n_cut,
+                             int n_lim, const double* u_lo, const double* u_hi, const double* u_nom, int* clamped);
+
 /* ---- iLQR through contact: a tracking cost and a parallel line search in one device rollout (DESIGN.md section 3, item 3f;
  * csrc/plant_cost.h) ------------------------------------------------------------------------------------------------------------------
  * THE COST of a robot's trajectory, with x_t = [q[t]; q[t+1]] (n = 2nq, t = 0 .. T) and u_t (m = nu) the control step t applied:
@@ -687,6 +722,20 @@ int cimpc_plant_tape_linesearch(cimpc_plant_tape tape, int steps_per_launch, int
                                 int n_alpha, const double* alpha, double armijo, const cimpc_tracking_cost* cost, double reg,
                                 double* J, int* ok, int* choice, double* q, double* u_applied, double* gamma, double* b,
                                 int* status, int* iters, double* lin_q, double* lin_r, int* grad_status, cimpc_plant_tape* new_tape);
+/* The line search under control limits: cimpc_plant_tape_linesearch with n_lim (1 or B) rows u_lo, u_hi of nu
+ * limits (-inf, +inf: none).  Candidate c of robot b has the open-loop row ubar_t = limit(u_nom[t, b] + alpha[c] k[t, b]) and runs under the
+ * limited law of cimpc_plant_rollout_feedback_limits: it equals that call on B robots bit for bit.  Acceptance and choice are unchanged, and
+ * the new tape is the open-loop tape of the chosen u_applied.  The expansion kernel writes the limited rows and the candidates' limit rows
+ * on the device: nothing but the B-robot arrays goes up.  u_lo and u_hi both NULL: cimpc_plant_tape_linesearch, bit for bit.  Refused
+ * with its own reason: one limit array without the other, n_lim neither 1 nor B, a NaN limit, u_lo above u_hi. */
+int cimpc_plant_tape_linesearch_box(cimpc_plant_tape tape, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                    const double* q_nom, const double* u_nom, const double* w, int K_w, int n_w, int hold_w,
+                                    const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                                    const double* K, const double* k, const double* dV, const double* J_nom,
+                                    int n_alpha, const double* alpha, double armijo, const cimpc_tracking_cost* cost, double reg,
+                                    double* J, int* ok, int* choice, double* q, double* u_applied, double* gamma, double* b,
+                                    int* status, int* iters, double* lin_q, double* lin_r, int* grad_status, cimpc_plant_tape* new_tape,
+                                    int n_lim, const double* u_lo, const double* u_hi);
 
 /* ---- cimpc_set_linearization_batch from (z, theta) alone: plant model `model` linearized at kappa (cimpc_plant_linearize's kernel and arguments;
  * z0 = z, th0 = theta) and the tables built from its output, all on the handle's device and stream;

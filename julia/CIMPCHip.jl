@@ -733,6 +733,43 @@ function plant_rollout_feedback(model::Symbol, q1::Matrix{Float64}, v1::Matrix{F
 end
 
 """
+    plant_rollout_feedback_limits(model, q1, v1, u, μ, h_sim, opts, K, x_ref, u_lo, u_hi; ...) -> (ok, q, u_applied, γ, b, status, iters, fb_err)
+
+`plant_rollout_feedback` under control limits (`cimpc_plant_rollout_feedback_limits`; DESIGN.md section 3, item 3g): u_lo, u_hi are nu x 1
+(shared) or nu x B, ±Inf meaning no limit; a step applies and u_applied stores the law's control limited to [u_lo, u_hi]; fb_err is
+unchanged.  The keywords are `plant_rollout_feedback`'s.  Unexecuted, like the rest of this binding.
+"""
+function plant_rollout_feedback_limits(model::Symbol, q1::Matrix{Float64}, v1::Matrix{Float64}, u::Array{Float64}, μ, h_sim, opts,
+                                       K::Array{Float64}, x_ref::Array{Float64}, u_lo::Matrix{Float64}, u_hi::Matrix{Float64};
+                                       hold::Int = 1, n_sample = nothing, N_sample::Int = 1, w::Union{Nothing,Array{Float64}} = nothing,
+                                       w_hold::Int = 1, terrain::Union{Nothing,Vector{Terrain}} = nothing,
+                                       steps::Int = size(u, ndims(u)) * N_sample, steps_per_launch::Int = 0)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    B = size(q1, 2)
+    (size(u_lo) == size(u_hi) && size(u_lo, 1) == nu && size(u_lo, 2) in (1, B)) || error("plant_rollout_feedback_limits: u_lo, u_hi must be $nu x 1 or $nu x $B")
+    ua, ws, μs, Ks, xs, ns = _closed_loop_inputs("plant_rollout_feedback_limits", model, q1, v1, u, μ, w, terrain, steps, N_sample, w_hold, K, x_ref, hold, n_sample)
+    q0 = q1 .- h_sim .* v1
+    q = zeros(nq, B, steps + 2); γ = zeros(nc, B, steps); b = zeros(nf * nc, B, steps)
+    status = zeros(Cint, B, steps); iters = zeros(Cint, B, steps)
+    u_applied = zeros(nu, B, steps); fb_err = zeros(2 * nq, B, steps)
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    K_u, n_u = size(ua, 3), size(ua, 2)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu = length(μs); n_lim = size(u_lo, 2)
+    GC.@preserve Ks xs begin
+        fb = Ref(Feedback(pointer(Ks), pointer(xs), size(Ks, 4), size(Ks, 3), hold, ns))
+        check(@ccall LIB.cimpc_plant_rollout_feedback_limits(id::Cint, B::Cint, steps::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                                             q0::Ptr{Cdouble}, q1::Ptr{Cdouble}, ua::Ptr{Cdouble}, K_u::Cint, n_u::Cint, N_sample::Cint,
+                                                             wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint, μs::Ptr{Cdouble}, n_mu::Cint,
+                                                             h_sim::Cdouble, o::Ref{IpOpts}, q::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble},
+                                                             status::Ptr{Cint}, iters::Ptr{Cint}, fb::Ref{Feedback}, u_applied::Ptr{Cdouble},
+                                                             fb_err::Ptr{Cdouble}, n_lim::Cint, u_lo::Ptr{Cdouble}, u_hi::Ptr{Cdouble})::Cint)
+    end
+    return all(status .== 1), q, u_applied, γ, b, status, iters, fb_err
+end
+
+"""
     plant_rollout_tape_feedback(model, q1, v1, u, μ, h_sim, opts, K, x_ref; hold = 1, n_sample = N_sample, ..., grad_reg = nothing,
                                 grad_cols = nothing) -> (ok, q, u_applied, γ, b, status, iters, tape, fb_err)
 
@@ -920,6 +957,53 @@ function plant_tape_lqr(tape::PlantTape, Q::Array{Float64}, R::Array{Float64}; Q
     return K, k, P0, p0, dV, status, n_cut
 end
 
+"""
+    plant_tape_lqr_box(tape, Q, R, q, r; Qf = nothing, ρ = 0.0, keep = nothing, u_lo = nothing, u_hi = nothing, u_nom = nothing)
+        -> (K, k, P0, p0, dV, status, n_cut, clamped)
+
+`cimpc_plant_tape_lqr_box`, the limited pass (DESIGN.md section 3, item 3g): `plant_tape_lqr` with linear terms, ρ a number or one per
+robot (length B), and control limits u_lo <= u <= u_hi, each m x 1 (shared) or m x B, ±Inf meaning no limit, about the tape's applied
+controls u_nom: m x B x T.  At every step the box-constrained QP min ½x'Gx + Qu'x, u_lo - u_nom <= x <= u_hi - u_nom is solved by projected
+Newton; K's rows of the clamped controls are zero and k lies in the box.  clamped: B x keep, bit i-1 set where control i was clamped.
+Without limits (all three nothing) the outputs are `plant_tape_lqr`'s bit for bit.  Unexecuted, like the rest of this binding.
+"""
+function plant_tape_lqr_box(tape::PlantTape, Q::Array{Float64}, R::Array{Float64}, q::Array{Float64,3}, r::Array{Float64,3};
+                            Qf::Union{Nothing,Matrix{Float64}} = nothing, ρ::Union{Real,Vector{Float64}} = 0.0,
+                            keep::Union{Nothing,Integer} = nothing, u_lo::Union{Nothing,Matrix{Float64}} = nothing,
+                            u_hi::Union{Nothing,Matrix{Float64}} = nothing, u_nom::Union{Nothing,Array{Float64,3}} = nothing)
+    tape.handle != C_NULL || error("plant_tape_lqr_box: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, n, m = tape.B, tape.T, 2 * nq, nu
+    n_keep = keep === nothing ? T : Int(keep)
+    (size(Q) == (n, n) || size(Q) == (n, n, T)) || error("plant_tape_lqr_box: Q must be $n x $n or $n x $n x $T")
+    (size(R) == (m, m) || size(R) == (m, m, T)) || error("plant_tape_lqr_box: R must be $m x $m or $m x $m x $T")
+    n_Q = ndims(Q) == 2 ? 1 : T; n_R = ndims(R) == 2 ? 1 : T
+    Qend = Qf === nothing ? (ndims(Q) == 2 ? Q : Q[:, :, T]) : Qf
+    size(Qend) == (n, n) || error("plant_tape_lqr_box: Qf must be $n x $n")
+    (size(q) == (n, B, T + 1) && size(r) == (m, B, T)) || error("plant_tape_lqr_box: q must be $n x $B x $(T + 1) and r $m x $B x $T")
+    rho = ρ isa Real ? [Float64(ρ)] : ρ
+    (length(rho) == 1 || length(rho) == B) || error("plant_tape_lqr_box: ρ must be a number or one per robot ($B)")
+    limited = u_lo !== nothing || u_hi !== nothing
+    if limited
+        (u_lo !== nothing && u_hi !== nothing && u_nom !== nothing) || error("plant_tape_lqr_box: u_lo, u_hi and u_nom go together")
+        (size(u_lo) == size(u_hi) && size(u_lo, 1) == m && size(u_lo, 2) in (1, B)) || error("plant_tape_lqr_box: u_lo, u_hi must be $m x 1 or $m x $B")
+        size(u_nom) == (m, B, T) || error("plant_tape_lqr_box: u_nom must be $m x $B x $T")
+    end
+    n_rho = length(rho); n_lim = limited ? size(u_lo, 2) : 1
+    K = zeros(m, n, B, n_keep); P0 = zeros(n, n, B); status = zeros(Cint, B); n_cut = zeros(Cint, B)
+    k = zeros(m, B, n_keep); p0 = zeros(n, B); dV = zeros(2, B); clamped = zeros(Cint, B, n_keep)
+    p(a) = a === nothing ? C_NULL : pointer(a)
+    GC.@preserve Qend u_lo u_hi u_nom begin
+        pQf, plo, phi, pun = p(Qend), p(u_lo), p(u_hi), p(u_nom)
+        check(@ccall LIB.cimpc_plant_tape_lqr_box(tape.handle::Ptr{Cvoid}, 1::Cint, n_Q::Cint, Q::Ptr{Cdouble}, pQf::Ptr{Cdouble}, n_R::Cint,
+                                                  R::Ptr{Cdouble}, q::Ptr{Cdouble}, r::Ptr{Cdouble}, n_rho::Cint, rho::Ptr{Cdouble},
+                                                  n_keep::Cint, K::Ptr{Cdouble}, k::Ptr{Cdouble}, P0::Ptr{Cdouble}, p0::Ptr{Cdouble},
+                                                  dV::Ptr{Cdouble}, status::Ptr{Cint}, n_cut::Ptr{Cint}, n_lim::Cint, plo::Ptr{Cdouble},
+                                                  phi::Ptr{Cdouble}, pun::Ptr{Cdouble}, clamped::Ptr{Cint})::Cint)
+    end
+    return K, k, P0, p0, dV, status, n_cut, clamped
+end
+
 # ---- iLQR through contact: the tracking cost and the parallel line search (cimpc.h: cimpc_tracking_cost; DESIGN.md section 3, item 3f) ---
 # Unexecuted, like the rest of this binding (INTEGRATION.md).
 """
@@ -1029,6 +1113,56 @@ function plant_tape_linesearch(tape::PlantTape, K::Array{Float64,4}, k::Array{Fl
                                                      cq::Ptr{Cdouble}, cu::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble}, status::Ptr{Cint},
                                                      iters::Ptr{Cint}, lin_q::Ptr{Cdouble}, lin_r::Ptr{Cdouble}, grad_status::Ptr{Cint},
                                                      handle::Ref{Ptr{Cvoid}})::Cint)
+    end
+    return J, ok, choice, cq, cu, γ, b, status, iters, lin_q, lin_r, PlantTape(handle[], tape.model, B, T, tape.n_cols, grad_status)
+end
+
+"""
+    plant_tape_linesearch_box(tape, K, k, dV, q, u_applied, cost, J_nom, alphas, μ, h_sim, opts, u_lo, u_hi; ...)
+
+`plant_tape_linesearch` under control limits (`cimpc_plant_tape_linesearch_box`; DESIGN.md section 3, item 3g): u_lo, u_hi nu x 1 (shared) or
+nu x B.  A candidate's open-loop row is limit(u_applied + α k) and its steps apply the limited law; everything else, the returned values
+included, is `plant_tape_linesearch`'s.  Unexecuted, like the rest of this binding.
+"""
+function plant_tape_linesearch_box(tape::PlantTape, K::Array{Float64,4}, k::Array{Float64,3}, dV::Matrix{Float64}, q::Array{Float64,3},
+                               u_applied::Array{Float64,3}, cost::TrackingCost, J_nom::Vector{Float64}, alphas::Vector{Float64}, μ, h_sim, opts,
+                               u_lo::Matrix{Float64}, u_hi::Matrix{Float64};
+                               armijo::Real = 1e-4, w::Union{Nothing,Array{Float64}} = nothing, w_hold::Int = 1,
+                               terrain::Union{Nothing,Vector{Terrain}} = nothing, steps_per_launch::Int = 0, grad_reg = nothing)
+    tape.handle != C_NULL || error("plant_tape_linesearch_box: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, n, m = tape.B, tape.T, 2 * nq, nu
+    (size(K) == (m, n, B, T) && size(k) == (m, B, T) && size(dV) == (2, B)) || error("plant_tape_linesearch_box: K must be $m x $n x $B x $T, k $m x $B x $T, dV 2 x $B")
+    (size(q) == (nq, B, T + 2) && size(u_applied) == (nu, B, T) && length(J_nom) == B) || error("plant_tape_linesearch_box: q, u_applied or J_nom do not fit the tape")
+    (size(u_lo) == size(u_hi) && size(u_lo, 1) == nu && size(u_lo, 2) in (1, B)) || error("plant_tape_linesearch_box: u_lo, u_hi must be $nu x 1 or $nu x $B")
+    n_lim = size(u_lo, 2)
+    n_alpha = length(alphas)
+    (1 <= n_alpha <= 64 && all(isfinite, alphas) && armijo >= 0) || error("plant_tape_linesearch_box: 1 to 64 finite alphas, armijo >= 0")
+    n_Q, n_R, n_x = _tracking_cost_sizes("plant_tape_linesearch_box", cost, nq, nu, B, T)
+    ws = w === nothing ? nothing : ndims(w) == 2 ? reshape(w, nw, 1, :) : w
+    (ws === nothing || (ndims(ws) == 3 && size(ws, 1) == nw && size(ws, 2) in (1, B))) || error("plant_tape_linesearch_box: w must be $nw x K_w or $nw x B x K_w")
+    μs = Float64.(vcat(μ))
+    length(μs) in (1, B) || error("plant_tape_linesearch_box: one friction coefficient or one per robot")
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    reg = grad_reg === nothing ? o[].kappa_tol * o[].gamma_reg : Float64(grad_reg)
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu = length(μs)
+    J = zeros(B, n_alpha); ok = zeros(Cint, B, n_alpha); choice = zeros(Cint, B)
+    cq = zeros(nq, B, T + 2); cu = zeros(nu, B, T); γ = zeros(nc, B, T); b = zeros(nf * nc, B, T)
+    status = zeros(Cint, B, T); iters = zeros(Cint, B, T); grad_status = zeros(Cint, B, T)
+    lin_q = zeros(n, B, T + 1); lin_r = zeros(m, B, T)
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve cost begin
+        cc = Ref(TrackingCostC(pointer(cost.Q), pointer(cost.Qf), pointer(cost.R), pointer(cost.x_goal), pointer(cost.u_goal), n_Q, n_R, n_x))
+        check(@ccall LIB.cimpc_plant_tape_linesearch_box(tape.handle::Ptr{Cvoid}, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                                     q::Ptr{Cdouble}, u_applied::Ptr{Cdouble}, wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint,
+                                                     μs::Ptr{Cdouble}, n_mu::Cint, h_sim::Cdouble, o::Ref{IpOpts}, K::Ptr{Cdouble}, k::Ptr{Cdouble},
+                                                     dV::Ptr{Cdouble}, J_nom::Ptr{Cdouble}, n_alpha::Cint, alphas::Ptr{Cdouble}, armijo::Cdouble,
+                                                     cc::Ref{TrackingCostC}, reg::Cdouble, J::Ptr{Cdouble}, ok::Ptr{Cint}, choice::Ptr{Cint},
+                                                     cq::Ptr{Cdouble}, cu::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble}, status::Ptr{Cint},
+                                                     iters::Ptr{Cint}, lin_q::Ptr{Cdouble}, lin_r::Ptr{Cdouble}, grad_status::Ptr{Cint},
+                                                     handle::Ref{Ptr{Cvoid}}, n_lim::Cint, u_lo::Ptr{Cdouble}, u_hi::Ptr{Cdouble})::Cint)
     end
     return J, ok, choice, cq, cu, γ, b, status, iters, lin_q, lin_r, PlantTape(handle[], tape.model, B, T, tape.n_cols, grad_status)
 end
