@@ -11,6 +11,8 @@
 //                                 limited open-loop rows limit(u_nom + alpha k) and the candidates' limit rows, and the candidates run the
 //                                 limited law (the step kernel's third state); the existing entry is this one with null limits
 //   cimpc_plant_tracking_cost     plant_cost.h on the host with a team of one
+//   plant_linesearch_plan / _shared / _stages   what both entries validate, upload beside the expansion kernel and launch, on device pointers
+//                                 (plant_stage_launch.h): the entries above call them, and so does the device-resident iLQR loop (plant_ilqr.hip)
 //
 // The kernels here move rows and run the short ordered chains of plant_cost.h; a wavefront per workgroup.  The time of a line search is
 // the step kernel's.
@@ -31,6 +33,7 @@
 #include "plant_model.h"
 #include "plant_rollout_call.h"
 #include "plant_sensitivity.h"
+#include "plant_stage_launch.h"
 #include "plant_step_launch.h"
 #include "plant_tape.h"
 #include "plant_workspace.h"
@@ -194,6 +197,114 @@ extern "C" int cimpc_plant_tracking_cost(int nq, int nu, int B, int T, const cim
     return CIMPC_OK;
 }
 
+// ---- the launch code (plant_stage_launch.h): what both entries and the device-resident iLQR loop share ------------------------------
+namespace cimpc {
+
+const char* plant_linesearch_plan(const PlantLsCall& c, PlantLsPlan* P) {
+    if (const char* why = plant_linesearch_refusal(c.n_alpha, c.alpha, c.armijo)) return why;
+    if (const char* why = plant_cost_pointers(plant_cost_of(*c.cost, 1, 1, 1))) return why;
+    if (!(c.h > 0.0)) return "h not positive";
+    const cimpc_plant_tape tape = c.tape;
+    const bool limits = c.u_lo || c.u_hi;
+    if (limits && (!c.u_lo || !c.u_hi)) return "one of u_lo, u_hi without the other";
+    if (limits && c.n_lim != 1 && c.n_lim != tape->B) return "n_lim neither 1 nor B";
+    if (limits) {      // the limits' entries: the model's nu by the tape's model id alone
+        PlantModel named{};
+        if (!plant_model_by_id(tape->model, &named) || named.nu < 1) return "a model without controls or not the tape's";
+        for (size_t e = 0; e < (size_t)c.n_lim * named.nu; ++e) {
+            if (c.u_lo[e] != c.u_lo[e] || c.u_hi[e] != c.u_hi[e]) return "a NaN limit";
+            if (c.u_lo[e] > c.u_hi[e]) return "u_lo above u_hi";
+        }
+    }
+    const PlantTapeBuffers& parent = tape->buf;
+    const int B = tape->B, T = tape->T, n_cols = tape->n_cols;
+    if (parent.device < 0 || parent.device >= PLANT_MAX_DEVICES || !parent.d_dz || !parent.d_status) return "a closed tape";
+    if (!plant_linesearch_fits(c.n_alpha, B, T)) return "n_alpha B T beyond an int";
+    // everything cimpc_plant_rollout_tape validates for the B robots of the parent, on the arrays that stand in for its arguments
+    const PlantRolloutCall parent_call{.model = tape->model, .B = B, .T = T, .steps_per_launch = c.steps_per_launch, .n_terrain = c.n_terrain,
+                                       .terrain = c.terrain, .q0 = c.q_nom, .q1 = c.q_nom, .u = {c.u_nom, T, B, 1}, .w = {c.w, c.K_w, c.n_w, c.hold_w},
+                                       .mu = c.mu, .n_mu = c.n_mu, .h = c.h, .opts = c.opts, .q = c.q, .gamma = c.gamma, .b = c.b, .status = c.status,
+                                       .iters = c.iters, .grad = PlantRolloutGrad{c.reg, n_cols, nullptr, nullptr, c.grad_status, true}};
+    PlantModel M{};
+    bool rough = false;
+    if (plant_rollout_check(parent_call, &M, &rough) != CIMPC_OK) return "an argument that cimpc_plant_rollout_tape refuses for the tape's B robots";
+    const int nq = M.nq, nu = M.nu, nz = M.nz(), NB = c.n_alpha * B;
+    if (M.kind != parent.M.kind || nq != parent.M.nq || nu < 1 || 2 * nq > nz) return "a model without controls or not the tape's";
+    const PlantCost C = plant_cost_of(*c.cost, T, nq, nu);
+    if (const char* why = plant_cost_sizes(C, B)) return why;
+    // the candidates' rollout in the plant workspace, laid out as a closed-loop tape call of NB robots lays itself out
+    const bool w_each = c.w && c.n_w != 1, mu_each = c.n_mu != 1;
+    const cimpc_feedback fb_shape{c.q_nom, c.q_nom, T, NB, 1, 1.0};      // only the shape is read
+    const PlantRolloutCall cand_call{.model = tape->model, .B = NB, .T = T, .steps_per_launch = c.steps_per_launch, .n_terrain = 0, .terrain = nullptr,
+                                     .q0 = c.q_nom, .q1 = c.q_nom, .u = {c.u_nom, T, NB, 1}, .w = {c.w, c.K_w, w_each ? NB : 1, c.hold_w}, .mu = c.mu,
+                                     .n_mu = mu_each ? NB : 1, .h = c.h, .opts = c.opts, .q = c.q, .gamma = c.gamma, .b = c.b, .status = c.status,
+                                     .iters = c.iters, .grad = PlantRolloutGrad{c.reg, n_cols, nullptr, nullptr, c.grad_status, true},
+                                     .loop = PlantRolloutLoop{&fb_shape, c.u_applied, nullptr, c.u_lo, c.u_hi, !limits || c.n_lim == 1 ? 1 : NB}};
+    P->M = M; P->rough = rough; P->has_w = c.w != nullptr; P->w_each = w_each; P->mu_each = mu_each; P->limits = limits;
+    P->lim_each = limits && c.n_lim != 1; P->ter_each = rough && c.n_terrain != 1;
+    P->C = C; P->L = plant_rollout_layout(M, cand_call);
+    P->model = tape->model; P->B = B; P->T = T; P->NB = NB; P->n_alpha = c.n_alpha; P->n_cols = n_cols; P->steps_per_launch = c.steps_per_launch;
+    P->K_w = c.K_w; P->n_w = c.n_w; P->hold_w = c.hold_w; P->n_mu = c.n_mu; P->n_terrain = c.n_terrain;
+    P->n_ter = !rough ? 0 : P->ter_each ? NB : 1; P->n_lim = c.n_lim;
+    P->mu0 = c.mu[0]; P->h = c.h; P->armijo = c.armijo; P->reg = c.reg; P->opts = *c.opts;
+    return nullptr;
+}
+
+std::vector<cimpc_terrain> plant_linesearch_terrains(const PlantLsPlan& P, const cimpc_terrain* terrain) {
+    std::vector<cimpc_terrain> ter;
+    if (P.ter_each) for (int c = 0; c < P.n_alpha; ++c) ter.insert(ter.end(), terrain, terrain + P.B);
+    return ter;
+}
+
+bool plant_linesearch_shared(const PlantLsPlan& P, const double* w, const cimpc_terrain* terrain, const std::vector<cimpc_terrain>& ter, PlantWs& W,
+                             hipStream_t st) {
+    bool ok_ = true;
+    if (P.has_w && !P.w_each)      // a shared schedule serves the candidates as it stands
+        ok_ = hipMemcpyAsync(W.d_in + P.L.w.at, w, (size_t)P.K_w * P.M.nw * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (P.rough)
+        ok_ = ok_ && hipMemcpyAsync(W.d_ter, P.ter_each ? ter.data() : terrain, (size_t)P.n_ter * sizeof(cimpc_terrain), hipMemcpyHostToDevice, st) == hipSuccess;
+    return ok_;
+}
+
+bool plant_linesearch_stages(const PlantLsPlan& P, const PlantLsArrays& A, PlantWs& W, hipStream_t st) {
+    const PlantModel& M = P.M;
+    const PlantRolloutLayout& L = P.L;
+    const int B = P.B, T = P.T, NB = P.NB, nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb(), nz = M.nz(), nw = M.nw, nr = nq + nc + nb, n_cols = P.n_cols;
+    const bool has_w = P.has_w, w_each = P.w_each, mu_each = P.mu_each, limits = P.limits, lim_each = P.lim_each, rough = P.rough;
+    const size_t TB = (size_t)T * B, block = (size_t)nr * n_cols;
+    // the candidates' limits: the one shared row where it stands, or NB rows the expansion kernel writes behind the loop's arrays
+    const double *c_lo = !limits ? nullptr : lim_each ? W.d_fb + L.u_lo.at : A.u_lo, *c_hi = !limits ? nullptr : lim_each ? W.d_fb + L.u_hi.at : A.u_hi;
+    double *dq = W.d_in + L.q.at, *du = W.d_in + L.u.at, *dw = W.d_in + L.w.at, *dmu = W.d_in + L.mu.at;
+    double *d_fk = W.d_fb + L.fb_K.at, *d_fx = W.d_fb + L.x_ref.at, *d_ua = W.d_fb + L.u_applied.at, *d_fe = W.d_fb + L.fb_err.at;
+    double *dg = W.d_out + L.gamma.at, *db = W.d_out + L.b.at;
+    int *d_st = W.d_st + L.status.at, *d_it = W.d_st + L.iters.at;
+    const PlantLsExpand E{A.q_nom, A.u_nom, A.k, A.K, w_each ? A.w : nullptr, mu_each ? A.mu : nullptr, A.alpha,
+                          dq, du, d_fk, d_fx, dw, dmu, B, NB, T, nq, nu, nw, has_w ? P.K_w : 0, limits ? A.u_lo : nullptr, limits ? A.u_hi : nullptr,
+                          lim_each ? W.d_fb + L.u_lo.at : nullptr, lim_each ? W.d_fb + L.u_hi.at : nullptr, P.n_lim};
+    hipLaunchKernelGGL(plant_ls_expand_kernel, dim3(T * NB), dim3(LS_THREADS), 0, st, E);
+    if (hipGetLastError() != hipSuccess) return false;
+    const PlantStepArrays R{dq, du, has_w ? dw : nullptr, mu_each ? dmu : nullptr, dg, db, d_st, d_it, P.mu0, P.h, T, NB, 1, has_w ? P.K_w : 1,
+                            w_each ? NB : 1, has_w ? P.hold_w : 1, mu_each ? NB : 1, W.d_z, PlantFeedback{d_fk, d_fx, T, NB, 1, 1.0}, d_ua, d_fe,
+                            PlantFeedbackLimits{c_lo, c_hi, lim_each ? NB : 1}};
+    if (!plant_step_chunks(M, rough, P.opts, NB, T, P.steps_per_launch, R, rough ? W.d_ter : nullptr, P.n_ter, st)) return false;
+    const PlantLsCost Pc{A.C, dq, d_ua, d_st, A.J, A.conv, B, NB};
+    hipLaunchKernelGGL(plant_ls_cost_kernel, dim3(NB), dim3(LS_THREADS), 0, st, Pc);
+    if (hipGetLastError() != hipSuccess) return false;
+    const PlantLsGather G{A.C, dq, W.d_z, d_ua, dg, db, d_st, d_it, A.conv, A.J, A.J_nom, A.dV, A.alpha, P.armijo, P.n_alpha,
+                          A.ok, A.choice, A.Cq, A.Cz, A.Cu, A.Cg, A.Cb, A.Cst, A.Cit, A.lin_q, A.lin_r, B, NB, nc, nb, nz};
+    hipLaunchKernelGGL(plant_ls_gather_kernel, dim3((T + 2) * B), dim3(LS_THREADS), 0, st, G);
+    if (hipGetLastError() != hipSuccess) return false;
+    // the chosen trajectories' step gradients: an open-loop rollout of B robots on the controls their steps applied
+    const PlantSensSource src{A.Cz, nullptr, A.Cq, A.Cu, !has_w ? nullptr : w_each ? A.w : dw, mu_each ? A.mu : nullptr, A.Cst,
+                              P.mu0, P.h, B, T, B, 1, has_w ? P.K_w : 1, has_w ? P.n_w : 1, has_w ? P.hold_w : 1, P.n_mu};
+    if (!plant_sensitivity_launch(M, (int)TB, src, rough ? W.d_ter : nullptr, rough ? P.n_terrain : 0, P.reg, n_cols, A.dz, A.status, st)) return false;
+    hipLaunchKernelGGL(plant_ls_restore_kernel, dim3((unsigned)TB), dim3(LS_THREADS), 0, st, A.choice, A.parent_dz, A.parent_status, A.dz, A.status, B, T,
+                       (int)block);
+    return hipGetLastError() == hipSuccess;
+}
+
+}  // namespace cimpc
+
 // Both entries: u_lo, u_hi null (cimpc_plant_tape_linesearch) or n_lim x nu limits (cimpc_plant_tape_linesearch_box).
 static int plant_tape_linesearch_call(const char* entry, cimpc_plant_tape tape, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
                                       const double* q_nom, const double* u_nom, const double* w, int K_w, int n_w, int hold_w,
@@ -212,36 +323,17 @@ static int plant_tape_linesearch_call(const char* entry, cimpc_plant_tape tape, 
         {"cost", cost}, {"J", J}, {"ok", ok}, {"choice", choice}, {"q", q}, {"u_applied", u_applied}, {"gamma", gamma}, {"b", b}, {"status", status},
         {"iters", iters}, {"lin_q", lin_q}, {"lin_r", lin_r}, {"grad_status", grad_status}};
     for (const auto& [name, p] : required) if (!p) return refuse(std::string("null ") + name);
-    if (const char* why = plant_linesearch_refusal(n_alpha, alpha, armijo)) return refuse(why);
-    if (const char* why = plant_cost_pointers(plant_cost_of(*cost, 1, 1, 1))) return refuse(why);
-    if (!(h > 0.0)) return refuse("h not positive");
-    const bool limits = u_lo || u_hi;
-    if (limits && (!u_lo || !u_hi)) return refuse("one of u_lo, u_hi without the other");
-    if (limits && n_lim != 1 && n_lim != tape->B) return refuse("n_lim neither 1 nor B");
-    if (limits) {      // the limits' entries: the model's nu by the tape's model id alone
-        PlantModel named{};
-        if (!plant_model_by_id(tape->model, &named) || named.nu < 1) return refuse("a model without controls or not the tape's");
-        for (size_t e = 0; e < (size_t)n_lim * named.nu; ++e) {
-            if (u_lo[e] != u_lo[e] || u_hi[e] != u_hi[e]) return refuse("a NaN limit");
-            if (u_lo[e] > u_hi[e]) return refuse("u_lo above u_hi");
-        }
-    }
+    PlantLsPlan P;
+    if (const char* why = plant_linesearch_plan(PlantLsCall{tape, steps_per_launch, n_terrain, terrain, q_nom, u_nom, w, K_w, n_w, hold_w, mu, n_mu, h, opts,
+                                                            n_alpha, alpha, armijo, cost, reg, q, u_applied, gamma, b, status, iters, grad_status, n_lim,
+                                                            u_lo, u_hi}, &P))
+        return refuse(why);
     const PlantTapeBuffers& parent = tape->buf;
-    const int B = tape->B, T = tape->T, n_cols = tape->n_cols;
-    if (parent.device < 0 || parent.device >= PLANT_MAX_DEVICES || !parent.d_dz || !parent.d_status) return refuse("a closed tape");
-    if (!plant_linesearch_fits(n_alpha, B, T)) return refuse("n_alpha B T beyond an int");
-    // everything cimpc_plant_rollout_tape validates for the B robots of the parent, on the arrays that stand in for its arguments
-    const PlantRolloutCall parent_call{.model = tape->model, .B = B, .T = T, .steps_per_launch = steps_per_launch, .n_terrain = n_terrain, .terrain = terrain,
-                                       .q0 = q_nom, .q1 = q_nom, .u = {u_nom, T, B, 1}, .w = {w, K_w, n_w, hold_w}, .mu = mu, .n_mu = n_mu, .h = h,
-                                       .opts = opts, .q = q, .gamma = gamma, .b = b, .status = status, .iters = iters,
-                                       .grad = PlantRolloutGrad{reg, n_cols, nullptr, nullptr, grad_status, true}};
-    PlantModel M{};
-    bool rough = false;
-    if (plant_rollout_check(parent_call, &M, &rough) != CIMPC_OK) return refuse("an argument that cimpc_plant_rollout_tape refuses for the tape's B robots");
-    const int nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb(), nz = M.nz(), nw = M.nw, nr = nq + nc + nb, NB = n_alpha * B;
-    if (M.kind != parent.M.kind || nq != parent.M.nq || nu < 1 || 2 * nq > nz) return refuse("a model without controls or not the tape's");
-    PlantCost C = plant_cost_of(*cost, T, nq, nu);
-    if (const char* why = plant_cost_sizes(C, B)) return refuse(why);
+    const PlantModel& M = P.M;
+    const PlantRolloutLayout& L = P.L;
+    PlantCost C = P.C;
+    const int B = P.B, T = P.T, n_cols = P.n_cols, nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb(), nz = M.nz(), nw = M.nw, nr = nq + nc + nb, NB = P.NB;
+    const bool limits = P.limits, w_each = P.w_each, mu_each = P.mu_each;
     const size_t TB = (size_t)T * B, n = (size_t)2 * nq, kk = (size_t)nu * n, block = (size_t)nr * n_cols;
     // the inputs the candidates' law is made of are finite, as cimpc_plant_rollout_feedback asks of K and x_ref
     auto finite = [](const double* a, size_t cnt) { for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(a[i])) return false; return true; };
@@ -249,15 +341,6 @@ static int plant_tape_linesearch_call(const char* entry, cimpc_plant_tape tape, 
     if (!finite(k, TB * nu)) return refuse("a non-finite entry of k");
     if (!finite(q_nom, (size_t)(T + 2) * B * nq)) return refuse("a non-finite entry of q_nom");
     if (!finite(u_nom, TB * nu)) return refuse("a non-finite entry of u_nom");
-    // the candidates' rollout in the plant workspace, laid out as a closed-loop tape call of NB robots lays itself out
-    const bool w_each = w && n_w != 1, mu_each = n_mu != 1;
-    const cimpc_feedback fb_shape{K, K, T, NB, 1, 1.0};
-    const PlantRolloutCall cand_call{.model = tape->model, .B = NB, .T = T, .steps_per_launch = steps_per_launch, .n_terrain = 0, .terrain = nullptr,
-                                     .q0 = q_nom, .q1 = q_nom, .u = {u_nom, T, NB, 1}, .w = {w, K_w, w_each ? NB : 1, hold_w}, .mu = mu,
-                                     .n_mu = mu_each ? NB : 1, .h = h, .opts = opts, .q = q, .gamma = gamma, .b = b, .status = status, .iters = iters,
-                                     .grad = PlantRolloutGrad{reg, n_cols, nullptr, nullptr, grad_status, true},
-                                     .loop = PlantRolloutLoop{&fb_shape, u_applied, nullptr, u_lo, u_hi, !limits || n_lim == 1 ? 1 : NB}};
-    const PlantRolloutLayout L = plant_rollout_layout(M, cand_call);
     // the B-robot inputs in d_in, in the order they go up
     size_t at = 0;
     auto next = [&at](size_t cnt) { const size_t o = at; at += cnt; return o; };
@@ -271,10 +354,7 @@ static int plant_tape_linesearch_call(const char* entry, cimpc_plant_tape tape, 
                  o_lq = next((size_t)(T + 1) * B * n), o_lr = next(TB * nu), o_z = next(TB * nz), n_out = at;
     at = 0;      // the integers
     const size_t j_ok = next((size_t)NB), j_ch = next((size_t)B), j_st = next(TB), j_it = next(TB), j_conv = next((size_t)NB), n_int = at;
-    std::vector<cimpc_terrain> ter;      // the candidates' terrains: robot b's for every c
-    const bool ter_each = rough && n_terrain != 1;
-    if (ter_each) for (int c = 0; c < n_alpha; ++c) ter.insert(ter.end(), terrain, terrain + B);
-    const int n_ter = !rough ? 0 : ter_each ? NB : 1;
+    const std::vector<cimpc_terrain> ter = plant_linesearch_terrains(P, terrain);      // the candidates' terrains: robot b's for every c
 
     std::lock_guard<std::mutex> lock(g_plant_mu);
     int cur = -1;
@@ -286,7 +366,7 @@ static int plant_tape_linesearch_call(const char* entry, cimpc_plant_tape tape, 
     PlantWs* ws = plant_ws_open(dev);
     LineSearchWs& S = g_linesearch_ws[dev];
     if (ws && plant_grow(&ws->d_in, &ws->cap_in, L.need_in) && plant_grow(&ws->d_out, &ws->cap_out, L.need_out) && plant_grow(&ws->d_st, &ws->cap_st, L.need_st) &&
-        plant_grow(&ws->d_ter, &ws->cap_ter, (size_t)n_ter) && plant_grow(&ws->d_z, &ws->cap_z, L.need_z) && plant_grow(&ws->d_fb, &ws->cap_fb, L.need_fb) &&
+        plant_grow(&ws->d_ter, &ws->cap_ter, (size_t)P.n_ter) && plant_grow(&ws->d_z, &ws->cap_z, L.need_z) && plant_grow(&ws->d_fb, &ws->cap_fb, L.need_fb) &&
         plant_grow(&S.d_in, &S.cap_in, n_in) && plant_grow(&S.d_out, &S.cap_out, n_out) && plant_grow(&S.d_int, &S.cap_int, n_int) &&
         hipMalloc((void**)&buf.d_dz, TB * block * sizeof(double)) == hipSuccess) {      // the new tape's memory, the last to be allocated
         if (hipMalloc((void**)&buf.d_status, TB * sizeof(int)) != hipSuccess) buf.d_status = nullptr;
@@ -305,50 +385,13 @@ static int plant_tape_linesearch_call(const char* entry, cimpc_plant_tape tape, 
         up(I + i_Q, C.Q, (size_t)C.n_Q * n * n); up(I + i_Qf, C.Qf, n * n); up(I + i_R, C.R, (size_t)C.n_R * nu * nu);
         up(I + i_xg, C.x_goal, (size_t)(T + 1) * C.n_x * n); up(I + i_ug, C.u_goal, (size_t)T * C.n_x * nu);
         if (limits) { up(I + i_lo, u_lo, (size_t)n_lim * nu); up(I + i_hi, u_hi, (size_t)n_lim * nu); }
-        // the candidates' limits: the one shared row where it stands, or NB rows the expansion kernel writes behind the loop's arrays
-        const bool lim_each = limits && n_lim != 1;
-        const double *c_lo = !limits ? nullptr : lim_each ? W.d_fb + L.u_lo.at : I + i_lo, *c_hi = !limits ? nullptr : lim_each ? W.d_fb + L.u_hi.at : I + i_hi;
-        double *dq = W.d_in + L.q.at, *du = W.d_in + L.u.at, *dw = W.d_in + L.w.at, *dmu = W.d_in + L.mu.at;
-        if (w && !w_each) up(dw, w, (size_t)K_w * nw);      // a shared schedule serves the candidates as it stands
-        if (rough) up(W.d_ter, ter_each ? ter.data() : terrain, (size_t)n_ter);
+        ok_ = ok_ && plant_linesearch_shared(P, w, terrain, ter, W, st);
         C.Q = I + i_Q; C.Qf = I + i_Qf; C.R = I + i_R; C.x_goal = I + i_xg; C.u_goal = I + i_ug;
-        double *d_fk = W.d_fb + L.fb_K.at, *d_fx = W.d_fb + L.x_ref.at, *d_ua = W.d_fb + L.u_applied.at, *d_fe = W.d_fb + L.fb_err.at;
-        double *dg = W.d_out + L.gamma.at, *db = W.d_out + L.b.at;
-        int *d_st = W.d_st + L.status.at, *d_it = W.d_st + L.iters.at;
         if (ok_) {
-            const PlantLsExpand E{I + i_q, I + i_u, I + i_k, I + i_K, w_each ? I + i_w : nullptr, mu_each ? I + i_mu : nullptr, I + i_al,
-                                  dq, du, d_fk, d_fx, dw, dmu, B, NB, T, nq, nu, nw, w ? K_w : 0, limits ? I + i_lo : nullptr, limits ? I + i_hi : nullptr,
-                                  lim_each ? W.d_fb + L.u_lo.at : nullptr, lim_each ? W.d_fb + L.u_hi.at : nullptr, n_lim};
-            hipLaunchKernelGGL(plant_ls_expand_kernel, dim3(T * NB), dim3(LS_THREADS), 0, st, E);
-            ok_ = hipGetLastError() == hipSuccess;
-        }
-        if (ok_) {
-            const PlantStepArrays R{dq, du, w ? dw : nullptr, mu_each ? dmu : nullptr, dg, db, d_st, d_it, mu[0], h, T, NB, 1, w ? K_w : 1,
-                                    w_each ? NB : 1, w ? hold_w : 1, mu_each ? NB : 1, W.d_z, PlantFeedback{d_fk, d_fx, T, NB, 1, 1.0}, d_ua, d_fe,
-                                    PlantFeedbackLimits{c_lo, c_hi, lim_each ? NB : 1}};
-            ok_ = plant_step_chunks(M, rough, *opts, NB, T, steps_per_launch, R, rough ? W.d_ter : nullptr, n_ter, st);
-        }
-        if (ok_) {
-            const PlantLsCost P{C, dq, d_ua, d_st, O + o_J, N + j_conv, B, NB};
-            hipLaunchKernelGGL(plant_ls_cost_kernel, dim3(NB), dim3(LS_THREADS), 0, st, P);
-            ok_ = hipGetLastError() == hipSuccess;
-        }
-        if (ok_) {
-            const PlantLsGather G{C, dq, W.d_z, d_ua, dg, db, d_st, d_it, N + j_conv, O + o_J, I + i_Jn, I + i_dV, I + i_al, armijo, n_alpha,
-                                  N + j_ok, N + j_ch, O + o_q, O + o_z, O + o_u, O + o_g, O + o_b, N + j_st, N + j_it, O + o_lq, O + o_lr,
-                                  B, NB, nc, nb, nz};
-            hipLaunchKernelGGL(plant_ls_gather_kernel, dim3((T + 2) * B), dim3(LS_THREADS), 0, st, G);
-            ok_ = hipGetLastError() == hipSuccess;
-        }
-        if (ok_) {      // the chosen trajectories' step gradients: an open-loop rollout of B robots on the controls their steps applied
-            const PlantSensSource src{O + o_z, nullptr, O + o_q, O + o_u, !w ? nullptr : w_each ? I + i_w : dw, mu_each ? I + i_mu : nullptr, N + j_st,
-                                      mu[0], h, B, T, B, 1, w ? K_w : 1, w ? n_w : 1, w ? hold_w : 1, n_mu};
-            ok_ = plant_sensitivity_launch(M, (int)TB, src, rough ? W.d_ter : nullptr, rough ? n_terrain : 0, reg, n_cols, buf.d_dz, buf.d_status, st);
-        }
-        if (ok_) {
-            hipLaunchKernelGGL(plant_ls_restore_kernel, dim3((unsigned)TB), dim3(LS_THREADS), 0, st, N + j_ch, parent.d_dz, parent.d_status, buf.d_dz,
-                               buf.d_status, B, T, (int)block);
-            ok_ = hipGetLastError() == hipSuccess;
+            const PlantLsArrays A{I + i_q, I + i_u, I + i_k, I + i_K, w_each ? I + i_w : nullptr, mu_each ? I + i_mu : nullptr, I + i_dV, I + i_Jn, I + i_al,
+                                  limits ? I + i_lo : nullptr, limits ? I + i_hi : nullptr, C, O + o_J, N + j_ok, N + j_ch, N + j_conv, O + o_q, O + o_z,
+                                  O + o_u, O + o_g, O + o_b, N + j_st, N + j_it, O + o_lq, O + o_lr, parent.d_dz, parent.d_status, buf.d_dz, buf.d_status};
+            ok_ = plant_linesearch_stages(P, A, W, st);
         }
         down(J, O + o_J, (size_t)NB); down(q, O + o_q, (size_t)(T + 2) * B * nq); down(u_applied, O + o_u, TB * nu); down(gamma, O + o_g, TB * nc);
         down(b, O + o_b, TB * nb); down(lin_q, O + o_lq, (size_t)(T + 1) * B * n); down(lin_r, O + o_lr, TB * nu);

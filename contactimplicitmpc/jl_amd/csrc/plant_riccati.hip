@@ -32,6 +32,7 @@
 #include "gains.h"
 #include "plant_model.h"
 #include "plant_riccati.h"
+#include "plant_stage_launch.h"
 #include "plant_tape.h"
 #include "plant_workspace.h"
 
@@ -77,6 +78,16 @@ namespace {
 struct RiccatiWs { double *d_in = nullptr, *d_out = nullptr; size_t cap_in = 0, cap_out = 0; };
 RiccatiWs g_riccati_ws[PLANT_MAX_DEVICES];
 }  // namespace
+
+// The limited chain for a caller whose arrays are on the device already (plant_stage_launch.h): cimpc_plant_tape_lqr_box below, and the
+// device-resident iLQR loop of plant_ilqr.hip.
+bool plant_riccati_box_launch(const PlantRiccati& L, hipStream_t st) {
+    const size_t lds = plant_riccati_box_lds(L.nq, L.nu);
+    auto kernel = plant_riccati_kernel<true, true>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+    hipLaunchKernelGGL(kernel, dim3(L.B), dim3(RIC_THREADS), lds, st, L);
+    return hipGetLastError() == hipSuccess;
+}
 
 }  // namespace cimpc
 
@@ -175,11 +186,15 @@ static int plant_tape_lqr_call(const char* entry, bool box, cimpc_plant_tape tap
                 if (limits) { L.u_lo = I + o_lo; L.u_hi = I + o_hi; L.u_nom = I + o_un; L.n_lim = n_lim; }
                 if (clamped) L.clamped = reinterpret_cast<int*>(O + o_cl);
             }
-            auto kernel = boxed ? plant_riccati_kernel<true, true> : q ? plant_riccati_kernel<true> : plant_riccati_kernel<false>;
-            ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
-            if (ok) {
-                hipLaunchKernelGGL(kernel, dim3(B), dim3(RIC_THREADS), lds, st, L);
-                ok = hipGetLastError() == hipSuccess;
+            if (boxed) {
+                ok = plant_riccati_box_launch(L, st);
+            } else {
+                auto kernel = q ? plant_riccati_kernel<true> : plant_riccati_kernel<false>;
+                ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+                if (ok) {
+                    hipLaunchKernelGGL(kernel, dim3(B), dim3(RIC_THREADS), lds, st, L);
+                    ok = hipGetLastError() == hipSuccess;
+                }
             }
         }
         if (ok) ok = hipMemcpyAsync(out.get(), O, n_out * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;

@@ -12,6 +12,8 @@
 //                   d_tan_out: dq | dgamma | db | du_applied (those asked for); d_tan_cut: n_cut (B)   (plant_tangent.hip)
 //   line search     the rollout of its n_alpha x B candidates in d_in, d_out, d_st, d_z, d_fb, d_ter, laid out as a closed-loop tape call of that
 //                   many robots (K in d_fb); its B-robot inputs and outputs in buffers of its own   (plant_linesearch.hip)
+//   iLQR loop       the same candidates' rollout, iteration after iteration; the nominal, the gains, the rules' rows, the line search's outputs
+//                   and the history in two buffers of its own   (plant_ilqr.hip)
 //                   A tape's dz and status are NOT here: they belong to the tape (plant_adjoint.hip) and live as long as it does
 // The prologue the entry points share past their validation (plant_model_and_ground, plant_model.h; plant_rollout_check,
 // plant_rollout_call.h: no device needed) is stated here once: which device a call runs on (plant_current_device), and its workspace

@@ -24,6 +24,8 @@ Control limits: `Feedback(u_lo=, u_hi=)` clamps t
 solves a box-constrained QP per step (and takes a rho per robot), `linesearch(u_lo=, u_hi=)` runs its candidates under the clamped law, and
 `ilqr(u_lo=, u_hi=)` is control-limited iLQR on the three (`cimpc_plant_rollout_feedback_limits`, `cimpc_plant_tape_lqr_box`,
 `cimpc_plant_tape_linesearch_box`).
+`ilqr(device_loop=True)` and `ilqr_from_tape` run every iteration of that loop in one library call, on arrays that stay on the device
+(`cimpc_plant_ilqr`); tests/test_gpu_plant_ilqr.py holds them to the host loop bit for bit.
 Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble
 solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain, tests/test_gpu_plant_tangent.py against restatements of the forward chain,
 tests/test_gpu_plant_riccati.py against restatements of the backward pass, tests/test_gpu_plant_linesearch.py the line search against the
@@ -1165,7 +1167,7 @@ class ILQRResult:
 def ilqr(model: str, q1, v1, u, h: float, mu, cost: TrackingCost, *, alphas=(1.0, 0.5, 0.25, 0.125), max_iter: int = 10, rho0: float = 1e-6,
          rho_factor: float = 10.0, rho_max: float = 1e6, tol: float = 1e-6, armijo: float = 1e-4, w=None, w_hold: int = 1,
          opts: InteriorPointOptions = SIM_OPTS, terrain=None, steps_per_launch: int = 0, grad_reg=None, grad_cols=None, u_lo=None,
-         u_hi=None) -> ILQRResult:
+         u_hi=None, device_loop: bool = False) -> ILQRResult:
     """iLQR through contact on the device plant: from the rollout of the controls u (T, nu) or (T, B, nu)
     (applied as they stand), per iteration `RolloutTape.lqr` about the nominal with the cost's linear terms, then `RolloutTape.linesearch` over
     alphas - every step length of every robot in one closed-loop rollout - and the chosen candidates become the nominal.  The regularization
@@ -1178,7 +1180,15 @@ def ilqr(model: str, q1, v1, u, h: float, mu, cost: TrackingCost, *, alphas=(1.0
     initial u is first clipped into the box, u_lo where it is below, u_hi where it is above.  Each iteration is then ONE `lqr` launch with the
     per-robot rho array and the limits about the nominal's controls (a box-constrained QP per step), and the line search's candidates
     apply limit(limit(u + alpha k) + K (x_ref - x)): every nominal's controls lie in the box exactly.  `gains.clamped` tells which
-    controls each step clamped.  Without limits the code path is the one above, unchanged."""
+    controls each step clamped.  Without limits the code path is the one above, unchanged.
+    DEVICE-RESIDENT LOOP (device_loop=True; `cimpc_plant_ilqr`): the same iterations in ONE library call, on
+    arrays that stay on the device - one limited `lqr` launch per iteration with the per-robot rho (without limits too: null limits give
+    `lqr`'s bits), the line search's kernels, and the bookkeeping above as kernels (csrc/plant_ilqr.h).  The host reads one int per
+    iteration (how many robots are still active); the result is bit for bit the host loop's.  `gains` is the last iteration's `TapeGains`
+    (P0 and p0 None; clamped with limits only).  The default, False, is the host loop, untouched."""
+    if device_loop:
+        return _ilqr_device(model, q1, v1, u, h, mu, cost, alphas, max_iter, rho0, rho_factor, rho_max, tol, armijo, w, w_hold, opts, terrain,
+                            steps_per_launch, grad_reg, grad_cols, u_lo, u_hi)
     mid, nq, nu, nc, fd, nw = model_dims(model)
     limited = u_lo is not None or u_hi is not None
     if limited:
@@ -1229,6 +1239,120 @@ def ilqr(model: str, q1, v1, u, h: float, mu, cost: TrackingCost, *, alphas=(1.0
     stack = lambda key, dt: np.array(hist[key], dtype=dt).reshape(n_it, B)
     return ILQRResult(u=ua, q=q, gamma=gamma, b=b, J=stack("J", np.float64), alpha=stack("alpha", np.float64), rho=stack("rho", np.float64),
                       accepted=stack("accepted", bool), J0=J0, tape=tape, gains=gains)
+
+
+def _ilqr_loop_args(alphas, max_iter, rho0, rho_factor, rho_max, tol, armijo):
+    """The loop's own arguments checked for `cimpc_plant_ilqr`: (alphas (n_alpha,), max_iter, the ladder (max_iter + 1,))."""
+    max_iter = int(max_iter)
+    if max_iter < 1:
+        raise ValueError("max_iter must be at least 1")
+    alphas = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+    if not 1 <= alphas.size <= 64 or not np.isfinite(alphas).all():
+        raise ValueError("alphas: 1 to 64 finite step lengths")
+    if not armijo >= 0.0:
+        raise ValueError("armijo must not be negative")
+    # the ladder by the host loop's own expression, on the levels a loop of max_iter iterations can reach
+    with np.errstate(over="ignore", invalid="ignore"):
+        ladder = np.ascontiguousarray(rho0 * float(rho_factor) ** np.arange(max_iter + 1, dtype=np.int64), dtype=np.float64)
+    if not (np.isfinite(ladder).all() and (ladder >= 0.0).all()):
+        raise ValueError("rho0 rho_factor^j must be finite and not negative for j = 0 .. max_iter")
+    if np.isnan(rho_max) or np.isnan(tol):
+        raise ValueError("rho_max and tol must be numbers")
+    return alphas, max_iter, ladder
+
+
+def _ilqr_device(model, q1, v1, u, h, mu, cost, alphas, max_iter, rho0, rho_factor, rho_max, tol, armijo, w, w_hold, opts, terrain,
+                 steps_per_launch, grad_reg, grad_cols, u_lo, u_hi) -> ILQRResult:
+    """`ilqr(device_loop=True)`: the first rollout and its cost as the host loop makes them, then `cimpc_plant_ilqr`.  What can be refused
+    from shapes alone is refused before the library is called."""
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    nb, n = fd * nc, 2 * nq
+    if not isinstance(cost, TrackingCost):
+        raise ValueError("cost must be a TrackingCost")
+    alphas, max_iter, ladder = _ilqr_loop_args(alphas, max_iter, rho0, rho_factor, rho_max, tol, armijo)
+    u = np.asarray(u, dtype=np.float64)
+    if u.ndim not in (2, 3) or u.shape[-1] != nu or u.shape[0] < 1:
+        raise ValueError(f"u must be (T, {nu}) or (T, B, {nu}), got {u.shape}")
+    q1a, v1a = np.atleast_2d(np.asarray(q1, dtype=np.float64)), np.atleast_2d(np.asarray(v1, dtype=np.float64))
+    B = q1a.shape[0]
+    if q1a.shape != (B, nq) or v1a.shape != (B, nq):
+        raise ValueError(f"q1 and v1 must be ({nq},) or (B, {nq}), got {np.shape(q1)} and {np.shape(v1)}")
+    if u.ndim == 3 and u.shape[1] not in (1, B):
+        raise ValueError(f"u has {u.shape[1]} robots, q1 {B}")
+    T = u.shape[0]
+    lo, hi = _limit_arrays(u_lo, u_hi, B, nu)
+    cost._struct(nq, nu, B, T)
+    if lo is not None:      # the host loop's first lines: the initial controls clipped into the box
+        if u.ndim == 2:
+            u = u if lo.shape[0] == 1 else np.repeat(u[:, None], lo.shape[0], axis=1)
+        u = np.where(u < lo, lo, np.where(u > hi, hi, u))
+    ok, q, ua, gamma, b, status, iters, tape = rollout_tape(model, q1, v1, u, h, mu, w=w, w_hold=w_hold, opts=opts, terrain=terrain,
+                                                            steps_per_launch=steps_per_launch, grad_reg=grad_reg, grad_cols=grad_cols)
+    try:
+        return ilqr_from_tape(tape, q, ua, gamma, b, status, iters, cost, alphas=alphas, max_iter=max_iter, rho0=rho0, rho_factor=rho_factor,
+                              rho_max=rho_max, tol=tol, armijo=armijo, u_lo=u_lo, u_hi=u_hi)
+    finally:
+        tape.close()      # the first nominal's tape is superseded, as in the host loop
+
+
+def ilqr_from_tape(tape: RolloutTape, q, u_applied, gamma, b, status, iters, cost: TrackingCost, *, alphas=(1.0, 0.5, 0.25, 0.125),
+                   max_iter: int = 10, rho0: float = 1e-6, rho_factor: float = 10.0, rho_max: float = 1e6, tol: float = 1e-6, armijo: float = 1e-4,
+                   u_lo=None, u_hi=None) -> ILQRResult:
+    """The device-resident iLQR loop (`cimpc_plant_ilqr`) from a nominal that is already rolled out: tape and
+    (q, u_applied, gamma, b, status, iters) as `rollout_tape` returned them (open loop, N_sample = 1; with limits, u_applied inside the box).
+    The tape is read, not consumed: it answers `lqr` and `vjp` afterwards as before.  mu, w, terrain, opts and the rest are what the tape
+    was recorded with.  `ilqr(device_loop=True)` is `rollout_tape`, then this, then closing that tape."""
+    if tape.closed:
+        raise ValueError("the tape is closed")
+    if tape._N_sample != 1 or tape._feedback is not None:
+        raise ValueError("ilqr needs an open-loop tape recorded with N_sample = 1")
+    model = tape.model
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    B, T, nb, n = tape.B, tape.T, fd * nc, 2 * nq
+    alphas, max_iter, ladder = _ilqr_loop_args(alphas, max_iter, rho0, rho_factor, rho_max, tol, armijo)
+    cont = lambda a, dt=np.float64: np.ascontiguousarray(a, dtype=dt)
+    q, ua, gamma, b, status, iters = cont(q), cont(u_applied), cont(gamma), cont(b), cont(status, np.int32), cont(iters, np.int32)
+    want = dict(q=(T + 2, B, nq), u_applied=(T, B, nu), gamma=(T, B, nc), b=(T, B, nb), status=(T, B), iters=(T, B))
+    for (name, shape), a in zip(want.items(), (q, ua, gamma, b, status, iters)):
+        if a.shape != shape:
+            raise ValueError(f"{name} must be {shape}, got {a.shape}")
+    lo, hi = _limit_arrays(u_lo, u_hi, B, nu)
+    cc, keep = cost._struct(nq, nu, B, T)
+    J0, lq0, lr0 = cost.evaluate(q, ua)
+    ctx = tape._context
+    terrain = ctx.get("terrain")
+    wa = None if ctx.get("w") is None else np.ascontiguousarray(_schedule(ctx["w"], B, nw, "w"))
+    mua = np.ascontiguousarray(ctx["mu"], dtype=np.float64).reshape(-1)
+    oq, ou, og, ob = np.zeros((T + 2, B, nq)), np.zeros((T, B, nu)), np.zeros((T, B, nc)), np.zeros((T, B, nb))
+    ost, oit, gst = (np.zeros((T, B), dtype=np.int32) for _ in range(3))
+    olq, olr = np.zeros((T + 1, B, n)), np.zeros((T, B, nu))
+    hJ, hal, hrho, hacc = np.zeros((max_iter, B)), np.zeros((max_iter, B)), np.zeros((max_iter, B)), np.zeros((max_iter, B), dtype=np.int32)
+    Kb, k, dV = np.zeros((T, B, n, nu)), np.zeros((T, B, nu)), np.zeros((B, 2))
+    lqs, n_cut = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    clamped = None if lo is None else np.zeros((T, B), dtype=np.int32)
+    n_iter, handle = C.c_int(0), C.c_void_p()
+    o = _lib.IpOpts(**dataclasses.asdict(ctx.get("opts", SIM_OPTS)))
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int))
+    ta, nt = (None, 0) if terrain is None else _terrain_array(terrain, B)
+    lib = _lib.load()
+    rc = lib.cimpc_plant_ilqr(
+        tape._handle, int(ctx.get("steps_per_launch", 0)), nt, ta, dp(q), dp(ua), dp(gamma), dp(b), ip(status), ip(iters), dp(J0), dp(lq0), dp(lr0),
+        dp(wa), 1 if wa is None else wa.shape[0], 1 if wa is None else wa.shape[1], int(ctx.get("w_hold", 1)), dp(mua), mua.size, float(tape._h), C.byref(o),
+        C.byref(cc), alphas.size, dp(alphas), float(armijo), float(ctx["grad_reg"]), ladder.size, dp(ladder), float(rho_max), float(tol), max_iter,
+        1 if lo is None else lo.shape[0], dp(lo), dp(hi), dp(oq), dp(ou), dp(og), dp(ob), ip(ost), ip(oit), dp(olq), dp(olr), ip(gst),
+        dp(hJ), dp(hal), dp(hrho), ip(hacc), C.byref(n_iter), dp(Kb), dp(k), dp(dV), ip(lqs), ip(n_cut), ip(clamped), C.byref(handle))
+    if rc == -1:
+        raise ValueError(lib.cimpc_last_error(None).decode())
+    if rc != 0:
+        raise _lib.CimpcError(f"cimpc_plant_ilqr failed ({rc})")
+    final = RolloutTape(handle, model, gst, None, tape._v1, tape._h, (T, B, nu), 1, None if wa is None else np.shape(ctx["w"]),
+                        int(ctx.get("w_hold", 1)), tape._mu_shared, q1_shape=tape._q1_shape, mu_shape=tape._mu_shape)
+    final._context = dict(ctx)
+    n_it = n_iter.value
+    gains = TapeGains(K=np.ascontiguousarray(Kb.transpose(0, 1, 3, 2)), k=k, P0=None, p0=None, dV=dV, status=lqs, n_cut=n_cut, K_blocks=Kb, clamped=clamped)
+    return ILQRResult(u=ou, q=oq, gamma=og, b=ob, J=hJ[:n_it].copy(), alpha=hal[:n_it].copy(), rho=hrho[:n_it].copy(), accepted=hacc[:n_it].astype(bool),
+                      J0=J0, tape=final, gains=gains)
 
 
 def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, feedback=None, **kw):

@@ -737,6 +737,40 @@ int cimpc_plant_tape_linesearch_box(cimpc_plant_tape tape, int steps_per_launch,
                                     int* status, int* iters, double* lin_q, double* lin_r, int* grad_status, cimpc_plant_tape* new_tape,
                                     int n_lim, const double* u_lo, const double* u_hi);
 
+/* cimpc_plant_ilqr: the device-resident iLQR loop - up to max_iter iterations of backward pass, line search
+ * and per-robot bookkeeping in ONE call, on arrays that stay on the device.  `tape` is the first nominal's open-loop tape (read, never
+ * consumed); q_nom, u_nom, gamma_nom, b_nom, status_nom, iters_nom are that rollout's rows (shapes as cimpc_plant_tape_linesearch's outputs),
+ * J_nom (B), lin_q_nom, lin_r_nom its cost (cimpc_plant_tracking_cost).  The rollout arguments, cost, alpha, armijo, reg and the optional
+ * limits (n_lim, u_lo, u_hi; both NULL: none) are cimpc_plant_tape_linesearch_box's.  ladder: n_ladder >= max_iter + 1 regularizations, a
+ * robot's rho being ladder[level]; the caller computes it (rho0 rho_factor^j), nothing on the device evaluates a power.
+ * Per iteration, on the plant's private stream: rho per robot from the ladder; plant_riccati_kernel<true, true> (cimpc_plant_tape_lqr_box's
+ * kernel with n_rho = B, n_keep = T, the cost's weights and the nominal's lin_q, lin_r, u) about the nominal's tape;
+ * J_nom = active and status == 0 ? J : -inf; the kernels of cimpc_plant_tape_linesearch_box; then a commit kernel: a robot with an acceptable
+ * candidate takes the chosen rows as its nominal and moves one level down (not below 0), any other active robot moves one level up; a
+ * robot stops being active once its accepted decrease is below tol |J| or ladder[level] > rho_max, and rides along rejected from then on
+ * (csrc/plant_ilqr.h states the rules).  The host reads ONE int per iteration, the number of robots still active, and stops at 0.  The
+ * weights, goals, limits, w, mu, terrains and alphas go up once; everything comes down once, at the end.  Two tape buffers alternate.
+ *   Out: the final nominal's q, u_applied, gamma, b, status, iters, lin_q, lin_r, grad_status; *n_iter iterations run (1 .. max_iter);
+ *   hist_J, hist_alpha (NaN where rejected), hist_rho, hist_accepted: max_iter x B, the first *n_iter rows written; of the LAST iteration's
+ *   backward pass K (T x B x (nu x 2nq)), k, dV (B x 2), lq_status, n_cut (B), clamped (T x B) - each may be NULL: not copied; *new_tape the
+ *   final nominal's open-loop tape (destroy it with cimpc_plant_tape_destroy).  Every array is bit for bit what the host loop over the two
+ *   entries above arrives at.
+ * Validated first, without a device (CIMPC_ERR_INVALID, the reason left for cimpc_last_error(NULL)): a null pointer (w, terrain, the limits
+ * and the six optional outputs excepted), max_iter < 1, a ladder shorter than max_iter + 1, a ladder entry that is negative or not finite,
+ * rho_max or tol not a number, everything cimpc_plant_tape_linesearch_box refuses of the arguments they share, a tape without the
+ * control columns, a model too large for the limited pass, a non-finite entry of q_nom or u_nom.  On any failure both tape buffers are
+ * freed and *new_tape is NULL. */
+int cimpc_plant_ilqr(cimpc_plant_tape tape, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                     const double* q_nom, const double* u_nom, const double* gamma_nom, const double* b_nom, const int* status_nom,
+                     const int* iters_nom, const double* J_nom, const double* lin_q_nom, const double* lin_r_nom,
+                     const double* w, int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                     const cimpc_tracking_cost* cost, int n_alpha, const double* alpha, double armijo, double reg,
+                     int n_ladder, const double* ladder, double rho_max, double tol, int max_iter,
+                     int n_lim, const double* u_lo, const double* u_hi,
+                     double* q, double* u_applied, double* gamma, double* b, int* status, int* iters, double* lin_q, double* lin_r,
+                     int* grad_status, double* hist_J, double* hist_alpha, double* hist_rho, int* hist_accepted, int* n_iter,
+                     double* K, double* k, double* dV, int* lq_status, int* n_cut, int* clamped, cimpc_plant_tape* new_tape);
+
 /* ---- cimpc_set_linearization_batch from (z, theta) alone: plant model `model` linearized at kappa (cimpc_plant_linearize's kernel and arguments;
  * z0 = z, th0 = theta) and the tables built from its output, all on the handle's device and stream;
  * nothing but z, theta and the terrains goes up, nothing but N status words comes back.  Equal bit for bit to

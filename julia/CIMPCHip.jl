@@ -1167,6 +1167,82 @@ function plant_tape_linesearch_box(tape::PlantTape, K::Array{Float64,4}, k::Arra
     return J, ok, choice, cq, cu, γ, b, status, iters, lin_q, lin_r, PlantTape(handle[], tape.model, B, T, tape.n_cols, grad_status)
 end
 
+"""
+    plant_ilqr(tape, q, u_applied, γ, b, status, iters, cost, μ, h_sim, opts; alphas = [1.0, 0.5, 0.25, 0.125], max_iter = 10, rho0 = 1e-6,
+               rho_factor = 10.0, rho_max = 1e6, tol = 1e-6, armijo = 1e-4, u_lo = nothing, u_hi = nothing, w = nothing, w_hold = 1,
+               terrain = nothing, steps_per_launch = 0, grad_reg = nothing)
+        -> (q, u_applied, γ, b, status, iters, lin_q, lin_r, J, alpha, rho, accepted, J0, K, k, dV, lq_status, n_cut, clamped, tape)
+
+`cimpc_plant_ilqr`, the device-resident iLQR loop (DESIGN.md section 3, item 3h): from the nominal the open-loop `tape` recorded (q
+nq x B x (T + 2), u_applied nu x B x T, γ, b, status, iters as `plant_rollout_tape` returned them), up to max_iter iterations of the limited
+backward pass with a rho per robot, the line search over alphas and the loop's bookkeeping (csrc/plant_ilqr.h), all on the device; the host
+reads one Cint per iteration.  The ladder rho0 rho_factor^j, j = 0 .. max_iter, is computed here.  u_lo, u_hi: nu x 1 or nu x B limits, or
+nothing.  The tape is read, not consumed.  Returns the final nominal's rows with the cost's lin_q, lin_r, the history J, alpha (NaN where
+rejected), rho, accepted (B x n_iter each), the first nominal's cost J0, the last iteration's gains K m x n x B x T, k, dV, lq_status, n_cut,
+clamped (B x T), and the final nominal's `PlantTape`.  Unexecuted, like the rest of this binding: written against include/cimpc.h and
+checked against its prototype by text only.
+"""
+function plant_ilqr(tape::PlantTape, q::Array{Float64,3}, u_applied::Array{Float64,3}, γ::Array{Float64,3}, b::Array{Float64,3},
+                    status::Matrix{Cint}, iters::Matrix{Cint}, cost::TrackingCost, μ, h_sim, opts;
+                    alphas::Vector{Float64} = [1.0, 0.5, 0.25, 0.125], max_iter::Int = 10, rho0::Real = 1e-6, rho_factor::Real = 10.0,
+                    rho_max::Real = 1e6, tol::Real = 1e-6, armijo::Real = 1e-4, u_lo::Union{Nothing,Matrix{Float64}} = nothing,
+                    u_hi::Union{Nothing,Matrix{Float64}} = nothing, w::Union{Nothing,Array{Float64}} = nothing, w_hold::Int = 1,
+                    terrain::Union{Nothing,Vector{Terrain}} = nothing, steps_per_launch::Int = 0, grad_reg = nothing)
+    tape.handle != C_NULL || error("plant_ilqr: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, n, m = tape.B, tape.T, 2 * nq, nu
+    (size(q) == (nq, B, T + 2) && size(u_applied) == (nu, B, T) && size(γ) == (nc, B, T) && size(b) == (nf * nc, B, T) && size(status) == (B, T) &&
+     size(iters) == (B, T)) || error("plant_ilqr: the nominal's rows do not fit the tape")
+    max_iter >= 1 || error("plant_ilqr: max_iter must be at least 1")
+    n_alpha = length(alphas)
+    (1 <= n_alpha <= 64 && all(isfinite, alphas) && armijo >= 0) || error("plant_ilqr: 1 to 64 finite alphas, armijo >= 0")
+    ladder = [Float64(rho0) * Float64(rho_factor)^j for j in 0:max_iter]
+    (all(isfinite, ladder) && all(>=(0), ladder)) || error("plant_ilqr: rho0 rho_factor^j must be finite and not negative")
+    n_ladder = length(ladder)
+    (u_lo === nothing) == (u_hi === nothing) || error("plant_ilqr: u_lo and u_hi go together")
+    limited = u_lo !== nothing
+    (!limited || (size(u_lo) == size(u_hi) && size(u_lo, 1) == nu && size(u_lo, 2) in (1, B))) || error("plant_ilqr: u_lo, u_hi must be $nu x 1 or $nu x $B")
+    n_lim = limited ? size(u_lo, 2) : 1
+    lo, hi = limited ? (u_lo, u_hi) : (C_NULL, C_NULL)
+    n_Q, n_R, n_x = _tracking_cost_sizes("plant_ilqr", cost, nq, nu, B, T)
+    J0, lin_q0, lin_r0 = plant_tracking_cost(cost, q, u_applied)
+    ws = w === nothing ? nothing : ndims(w) == 2 ? reshape(w, nw, 1, :) : w
+    (ws === nothing || (ndims(ws) == 3 && size(ws, 1) == nw && size(ws, 2) in (1, B))) || error("plant_ilqr: w must be $nw x K_w or $nw x B x K_w")
+    μs = Float64.(vcat(μ))
+    length(μs) in (1, B) || error("plant_ilqr: one friction coefficient or one per robot")
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    reg = grad_reg === nothing ? o[].kappa_tol * o[].gamma_reg : Float64(grad_reg)
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu = length(μs)
+    oq = zeros(nq, B, T + 2); ou = zeros(nu, B, T); og = zeros(nc, B, T); ob = zeros(nf * nc, B, T)
+    ost = zeros(Cint, B, T); oit = zeros(Cint, B, T); grad_status = zeros(Cint, B, T)
+    lin_q = zeros(n, B, T + 1); lin_r = zeros(m, B, T)
+    hJ = zeros(B, max_iter); hal = zeros(B, max_iter); hrho = zeros(B, max_iter); hacc = zeros(Cint, B, max_iter)
+    n_iter = Ref{Cint}(0)
+    K = zeros(m, n, B, T); k = zeros(m, B, T); dV = zeros(2, B)
+    lq_status = zeros(Cint, B); n_cut = zeros(Cint, B); clamped = zeros(Cint, B, T)
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve cost begin
+        cc = Ref(TrackingCostC(pointer(cost.Q), pointer(cost.Qf), pointer(cost.R), pointer(cost.x_goal), pointer(cost.u_goal), n_Q, n_R, n_x))
+        check(@ccall LIB.cimpc_plant_ilqr(tape.handle::Ptr{Cvoid}, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                          q::Ptr{Cdouble}, u_applied::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble}, status::Ptr{Cint},
+                                          iters::Ptr{Cint}, J0::Ptr{Cdouble}, lin_q0::Ptr{Cdouble}, lin_r0::Ptr{Cdouble},
+                                          wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint, μs::Ptr{Cdouble}, n_mu::Cint, h_sim::Cdouble,
+                                          o::Ref{IpOpts}, cc::Ref{TrackingCostC}, n_alpha::Cint, alphas::Ptr{Cdouble}, armijo::Cdouble,
+                                          reg::Cdouble, n_ladder::Cint, ladder::Ptr{Cdouble}, rho_max::Cdouble, tol::Cdouble, max_iter::Cint,
+                                          n_lim::Cint, lo::Ptr{Cdouble}, hi::Ptr{Cdouble},
+                                          oq::Ptr{Cdouble}, ou::Ptr{Cdouble}, og::Ptr{Cdouble}, ob::Ptr{Cdouble}, ost::Ptr{Cint}, oit::Ptr{Cint},
+                                          lin_q::Ptr{Cdouble}, lin_r::Ptr{Cdouble}, grad_status::Ptr{Cint}, hJ::Ptr{Cdouble}, hal::Ptr{Cdouble},
+                                          hrho::Ptr{Cdouble}, hacc::Ptr{Cint}, n_iter::Ref{Cint}, K::Ptr{Cdouble}, k::Ptr{Cdouble},
+                                          dV::Ptr{Cdouble}, lq_status::Ptr{Cint}, n_cut::Ptr{Cint}, clamped::Ptr{Cint},
+                                          handle::Ref{Ptr{Cvoid}})::Cint)
+    end
+    it = 1:Int(n_iter[])
+    return oq, ou, og, ob, ost, oit, lin_q, lin_r, hJ[:, it], hal[:, it], hrho[:, it], hacc[:, it] .!= 0, J0, K, k, dV, lq_status, n_cut, clamped,
+           PlantTape(handle[], tape.model, B, T, tape.n_cols, grad_status)
+end
+
 # ---- the plant models linearized on the device: the `LinearizedStep` triple of N knots in one call (linearized_step.jl:10-31) --------
 """
     plant_linearize(model, z, θ, κ; terrain = nothing) -> (r0, rz0, rθ0)
