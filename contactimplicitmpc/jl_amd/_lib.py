@@ -121,6 +121,9 @@ SIGNATURES = {
     "cimpc_plant_rollout_feedback_limits": (C.c_int, _ROLLOUT_ARGS + [C.POINTER(Feedback), _dp, _dp, C.c_int, _dp, _dp]),
     "cimpc_plant_rollout_grad_feedback": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _dp, _ip, C.POINTER(Feedback), _dp, _dp]),
     "cimpc_plant_rollout_tape_feedback": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _ip, C.POINTER(_h), C.POINTER(Feedback), _dp, _dp]),
+    "cimpc_plant_rollout_grad_feedback_limits": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _dp, _ip, C.POINTER(Feedback), _dp, _dp, C.c_int, _dp, _dp]),
+    "cimpc_plant_rollout_tape_feedback_limits": (C.c_int, _ROLLOUT_ARGS + [C.c_double, C.c_int, _dp, _ip, C.POINTER(_h), C.POINTER(Feedback), _dp, _dp,
+                                                                           C.c_int, _dp, _dp, _ip]),
     "cimpc_plant_tape_vjp_feedback": (C.c_int, [_h, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp]),
     "cimpc_plant_tape_jvp": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "cimpc_plant_tape_jvp_feedback": (C.c_int, [_h, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),

@@ -15,6 +15,12 @@
 //                       lambda[t+1][i] = (lambda[t+1][i] - (1 - n_sample) gx[i]) - gx[nq + i]      after lambda[t+1] received v[nq:2nq]
 // g_u_step stays gu, which is also the gradient of ubar_t.  Without a feedback schedule (fb.K null) none of these statements runs.
 //
+// The chain of a LIMITED closed-loop rollout (item 3i; `clamped` non-null, T x B mask words, bit i set where control i of the step is
+// clamped - plant_feedback_free of plant_feedback.h on the applied control) changes one statement: for column c_u + i, after v is formed,
+//                       gm = free ? v : 0.0;   g_u_step[t][i] = gm;   gu[i] = gm
+// and everything behind it is unchanged: a clamped control passes nothing to ubar, K or x.  The mask word of step t - 1 is read when block
+// t - 1 is sent for, a step ahead of its use.
+//
 // D_t is the step's dz block of plant_sensitivity.hip, nr x n_cols column-major, contiguous per (t, robot).  The chain of one robot
 // is stated here ONCE for a team of workers, the way lin_table_build.h states a table: plant_adjoint_kernel (plant_adjoint.hip) runs it
 // with a wavefront per robot, a host program (tests/native/plant_adjoint_check.cpp) with a team of one, statement for statement.
@@ -54,7 +60,11 @@ struct PlantAdjoint {
     int B, T, nq, nu, nw, nc, nb, n_cols;
     PlantFeedback fb{};               // fb.K null: an open-loop rollout
     double* g_xref_step = nullptr;    // T x B x 2nq, with fb.K alone; null = not asked for
+    const int* clamped = nullptr;     // T x B mask words, with fb.K alone; null = a closed loop without limits (item 3i)
 };
+
+// the three compile-time states of the chain, as LOOP is of the step kernel: open loop, closed loop, closed loop with the clamp's mask
+constexpr int PLANT_CHAIN_OPEN = 0, PLANT_CHAIN_LOOP = 1, PLANT_CHAIN_CLAMP = 2;
 
 // doubles of the team's shared workspace: two blocks (the one in use and the one in flight), a, the three-row ring of lambda
 PADJ_HD constexpr size_t plant_adjoint_work_doubles(int nr, int n_cols, int nq) {
@@ -81,11 +91,13 @@ struct PlantAdjointSolo {
 };
 
 // The chain of robot rb.  work: shared by the team, plant_adjoint_work_doubles(nr, n_cols, nq), with a feedback schedule
-// plant_adjoint_feedback_doubles(nu, nq) more.  FB: the feedback statements are compiled in (the caller has P.fb.K non-null); without
-// it the chain is, statement for statement, the open-loop one - plant_adjoint_kernel is instantiated both ways and the open-loop launch
-// carries nothing of the feedback path.
-template <bool FB, class Team>
+// plant_adjoint_feedback_doubles(nu, nq) more.  FB != 0: the feedback statements are compiled in (the caller has P.fb.K non-null); without
+// it the chain is, statement for statement, the open-loop one - plant_adjoint_kernel is instantiated each way and the open-loop launch
+// carries nothing of the feedback path.  FB == PLANT_CHAIN_CLAMP: the mask is read too (the caller has P.clamped non-null); the other two
+// carry nothing of it.  (`true` still names the closed loop: it converts to 1.)
+template <int FB, class Team>
 PADJ_HD inline void plant_adjoint_chain_as(const PlantAdjoint& P, int rb, double* work, Team& team) {
+    static_assert(FB == PLANT_CHAIN_OPEN || FB == PLANT_CHAIN_LOOP || FB == PLANT_CHAIN_CLAMP, "open loop, closed loop, or closed loop with the mask");
     const int me = team.rank(), np = team.size();
     const int nq = P.nq, nu = P.nu, nw = P.nw, nc = P.nc, nb = P.nb, n_cols = P.n_cols, B = P.B, T = P.T;
     const int nr = nq + nc + nb, blk = nr * n_cols;
@@ -103,6 +115,8 @@ PADJ_HD inline void plant_adjoint_chain_as(const PlantAdjoint& P, int rb, double
         row(T)[i] = P.gq ? P.gq[((size_t)T * B + rb) * nq + i] : 0.0;
     }
     team.fetch_issue(block(T - 1), blk);
+    int word_next = 0;                                                // the mask word of the block in flight
+    if constexpr (FB == PLANT_CHAIN_CLAMP) word_next = P.clamped[(size_t)(T - 1) * B + rb];
     team.fetch_commit(D[(T - 1) & 1], block(T - 1), blk);
     team.sync();
 
@@ -110,7 +124,11 @@ PADJ_HD inline void plant_adjoint_chain_as(const PlantAdjoint& P, int rb, double
     int cut = 0;
     for (int t = T - 1; t >= 0; --t) {
         const size_t e = (size_t)t * B + rb;
-        if (t > 0) team.fetch_issue(block(t - 1), blk);               // in flight while block t is used
+        const int word = word_next;
+        if (t > 0) {
+            team.fetch_issue(block(t - 1), blk);                      // in flight while block t is used
+            if constexpr (FB == PLANT_CHAIN_CLAMP) word_next = P.clamped[e - B];
+        }
         if (me == 0 && P.status[e] == 0) ++cut;
         const double* l2 = row(t + 2);
         for (int i = me; i < nr; i += np)
@@ -125,12 +143,16 @@ PADJ_HD inline void plant_adjoint_chain_as(const PlantAdjoint& P, int rb, double
             for (int r = 0; r < nr; ++r) v += col[r] * a[r];
             if (c < nq) l0[c] = (P.gq ? P.gq[e * nq + c] : 0.0) + v;
             else if (c < c_u) l1[c - nq] += v;
-            else if (c < c_w) { P.g_u_step[e * nu + (c - c_u)] = v; if constexpr (FB) gu[c - c_u] = v; }
+            else if (c < c_w) {
+                if constexpr (FB == PLANT_CHAIN_CLAMP) v = plant_feedback_word_free(word, c - c_u) ? v : 0.0;      // gm of item 3i
+                P.g_u_step[e * nu + (c - c_u)] = v;
+                if constexpr (FB != PLANT_CHAIN_OPEN) gu[c - c_u] = v;
+            }
             else if (c < c_mu) { if (P.g_w_step) P.g_w_step[e * nw + (c - c_w)] = v; }
             else if (c < c_h) s_mu += v;
             else s_h += v;
         }
-        if constexpr (FB) {                                           // the feedback path of step t (plant_feedback.h)
+        if constexpr (FB != PLANT_CHAIN_OPEN) {                       // the feedback path of step t (plant_feedback.h)
             const double* Kk = plant_feedback_gain(P.fb, t, rb, nu, nq);
             team.sync();                                              // gu, lambda[t] and lambda[t+1] are whole
             for (int j = me; j < 2 * nq; j += np) {                   // the member that owns column j
@@ -160,8 +182,9 @@ PADJ_HD inline void plant_adjoint_chain_as(const PlantAdjoint& P, int rb, double
 // The chain of robot rb, open or closed loop by what P carries.
 template <class Team>
 PADJ_HD inline void plant_adjoint_chain(const PlantAdjoint& P, int rb, double* work, Team& team) {
-    if (P.fb.K) plant_adjoint_chain_as<true>(P, rb, work, team);
-    else plant_adjoint_chain_as<false>(P, rb, work, team);
+    if (P.fb.K && P.clamped) plant_adjoint_chain_as<PLANT_CHAIN_CLAMP>(P, rb, work, team);
+    else if (P.fb.K) plant_adjoint_chain_as<PLANT_CHAIN_LOOP>(P, rb, work, team);
+    else plant_adjoint_chain_as<PLANT_CHAIN_OPEN>(P, rb, work, team);
 }
 
 }  // namespace cimpc

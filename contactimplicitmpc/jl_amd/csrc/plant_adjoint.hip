@@ -6,6 +6,8 @@
 //   cimpc_plant_tape_vjp       cotangents (gq, ggamma, gb) up, ONE launch of plant_adjoint_kernel, the small gradients down
 //   cimpc_plant_rollout_tape_feedback, cimpc_plant_tape_vjp_feedback   the two for a closed-loop rollout (plant_feedback.h): the tape also
 //                              owns the gain rows, the chain runs the feedback statements and returns g_xref_step when asked to
+//   cimpc_plant_rollout_tape_feedback_limits   the closed loop under control limits (item 3i): the tape also owns the mask of clamped
+//                              controls, and cimpc_plant_tape_vjp_feedback on it launches the third instantiation of the chain
 //
 // plant_adjoint_kernel: a workgroup of one wavefront per robot walks t = T-1 .. 0 through the statements of plant_adjoint.h.  D_t
 // (nr x n_cols doubles, column-major as the sensitivity kernel wrote it) sits in LDS, loaded by the whole wavefront with consecutive
@@ -17,12 +19,14 @@
 #include <climits>
 #include <mutex>
 #include <new>
+#include <string>
 
 // No fused multiply-adds in this translation unit: the chain rounds as the float64 restatement of the definition does, whatever the
 // compiler would make of `v += d * a`.
 #pragma clang fp contract(off)
 
 #include "../../../include/cimpc.h"
+#include "gains.h"
 #include "plant_adjoint.h"
 #include "plant_model.h"
 #include "plant_tape.h"
@@ -56,7 +60,9 @@ struct PlantAdjointWave {
     }
 };
 
-template <bool FB>      // FB: a closed-loop tape's chain, with the feedback statements of plant_feedback.h
+// FB: PLANT_CHAIN_OPEN, PLANT_CHAIN_LOOP (a closed-loop tape's chain, with the feedback statements of plant_feedback.h) or
+// PLANT_CHAIN_CLAMP (a limited closed-loop tape's, which also reads the tape's mask of clamped controls)
+template <int FB>
 __global__ __launch_bounds__(ADJ_THREADS) void plant_adjoint_kernel(PlantAdjoint P) {
     extern __shared__ __attribute__((aligned(16))) double adj_lds[];      // plant_adjoint_lds(nr, n_cols, nq), + plant_adjoint_feedback_doubles with P.fb.K
     const int rb = blockIdx.x;
@@ -89,6 +95,27 @@ extern "C" int cimpc_plant_rollout_tape_feedback(int model, int B, int T, int st
                                                  const cimpc_feedback* fb, double* u_applied, double* fb_err) {
     return rollout_tape_impl({PLANT_ROLLOUT_CALL_BASE, .grad = cimpc::PlantRolloutGrad{reg, n_cols, z, nullptr, grad_status, true},
                               .loop = cimpc::PlantRolloutLoop{fb, u_applied, fb_err}}, tape);
+}
+
+// cimpc_plant_rollout_tape_feedback under control limits: the rollout runs under the limited law, the tape
+// also owns the mask of clamped controls, and the words come back in clamped (T x B).  Every refusal of the limits leaves its reason for
+// cimpc_last_error(NULL), before any device is touched.
+extern "C" int cimpc_plant_rollout_tape_feedback_limits(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                                        const double* q0, const double* q1, const double* u, int K_u, int n_u, int hold_u,
+                                                        const double* w, int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h,
+                                                        const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status, int* iters,
+                                                        double reg, int n_cols, double* z, int* grad_status, cimpc_plant_tape* tape,
+                                                        const cimpc_feedback* fb, double* u_applied, double* fb_err, int n_lim, const double* u_lo,
+                                                        const double* u_hi, int* clamped) {
+    const cimpc::PlantRolloutLoop loop{fb, u_applied, fb_err, u_lo, u_hi, n_lim, clamped};
+    if (const char* why = cimpc::plant_limits_refusal(model, B, loop, true)) {
+        if (tape) *tape = nullptr;
+        cimpc::set_global_error(std::string("cimpc_plant_rollout_tape_feedback_limits: ") + why);
+        return CIMPC_ERR_INVALID;
+    }
+    const int rc = rollout_tape_impl({PLANT_ROLLOUT_CALL_BASE, .grad = cimpc::PlantRolloutGrad{reg, n_cols, z, nullptr, grad_status, true}, .loop = loop}, tape);
+    if (rc == CIMPC_ERR_INVALID) cimpc::set_global_error("cimpc_plant_rollout_tape_feedback_limits: an argument that cimpc_plant_rollout_tape_feedback refuses");
+    return rc;
 }
 
 extern "C" int cimpc_plant_rollout_tape(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
@@ -128,7 +155,8 @@ extern "C" int cimpc_plant_tape_destroy(cimpc_plant_tape tape) {
 
 // Validate (no device needed), then on the tape's device and the plant workspace's private stream: one upload (gq | ggamma | gb, those
 // given), one launch, one read-back (g_q0 | g_q1 | g_u_step | g_w_step | g_mu | g_h, n_cut), one synchronize.  A closed-loop tape's chain always runs the
-// feedback statements; g_xref_step (T x B x 2nq, may be null) is theirs and is refused on an open-loop tape.
+// feedback statements; g_xref_step (T x B x 2nq, may be null) is theirs and is refused on an open-loop tape.  A tape that owns a mask of
+// clamped controls (cimpc_plant_rollout_tape_feedback_limits) launches the PLANT_CHAIN_CLAMP instantiation, which needs no more LDS.
 extern "C" int cimpc_plant_tape_vjp_feedback(cimpc_plant_tape tape, const double* gq, const double* ggamma, const double* gb, double* g_q0,
                                     double* g_q1, double* g_u_step, double* g_w_step, double* g_mu, double* g_h, int* n_cut,
                                     double* g_xref_step) {
@@ -169,8 +197,8 @@ extern "C" int cimpc_plant_tape_vjp_feedback(cimpc_plant_tape tape, const double
             PlantAdjoint P{buf.d_dz, buf.d_status, gq ? d_gq : nullptr, ggamma ? d_gg : nullptr, gb ? d_gb : nullptr, d_q0, d_q1, d_u,
                                  g_w_step ? d_w : nullptr, g_mu ? d_m : nullptr, g_h ? d_h : nullptr, ws->d_adj_cut, B, T, (int)nq, (int)nu,
                                  (int)nw, (int)nc, (int)nb, n_cols};
-            if (fb.K) { P.fb = fb; P.g_xref_step = g_xref_step ? ws->d_adj_xref : nullptr; }
-            auto kernel = fb.K ? plant_adjoint_kernel<true> : plant_adjoint_kernel<false>;
+            if (fb.K) { P.fb = fb; P.g_xref_step = g_xref_step ? ws->d_adj_xref : nullptr; P.clamped = buf.d_clamped; }
+            auto kernel = !fb.K ? plant_adjoint_kernel<PLANT_CHAIN_OPEN> : buf.d_clamped ? plant_adjoint_kernel<PLANT_CHAIN_CLAMP> : plant_adjoint_kernel<PLANT_CHAIN_LOOP>;
             ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
             if (ok) {
                 hipLaunchKernelGGL(kernel, dim3(B), dim3(ADJ_THREADS), lds, st, P);

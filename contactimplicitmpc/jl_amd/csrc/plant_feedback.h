@@ -33,6 +33,9 @@
 namespace cimpc {
 
 // A feedback schedule in the memory its reader reads (device memory for the kernels).  K == nullptr: open loop.
+// The struct does not grow with the clamp's derivative: the mask of clamped controls that the two chains
+// read is appended to PlantAdjoint and PlantTangent instead.  This struct also lies in the arguments of the step kernel, whose
+// instantiations a word more in it would compile differently (see PlantFeedbackLimits below), and the step kernel has no use for the mask.
 struct PlantFeedback {
     const double* K = nullptr;      // K_f x n_f x (nu x 2nq), blocks column-major
     const double* x_ref = nullptr;  // K_f x n_f x 2nq
@@ -82,6 +85,23 @@ PFB_HD inline double plant_feedback_limit(double u, double lo, double hi) { retu
 
 // robot rb's row of a limit array
 PFB_HD inline const double* plant_feedback_limits(const double* lim, int n_lim, int rb, int nu) { return lim + (size_t)(n_lim == 1 ? 0 : rb) * nu; }
+
+// The derivative of the limited law, stated once.  Control i of step t is FREE when its APPLIED value
+// u = u_applied[t, b, i] lies strictly inside its limits, and CLAMPED otherwise: on a bound, whether the limiter moved it there or the law
+// landed there; with lo == hi; and when u is NaN (every comparison is false; such a step fails and is cut anyway).  Infinite bounds never
+// clamp.  The limited law's derivative is the unlimited law's where the control is free and exactly 0.0 where it is clamped: an element of
+// the generalized derivative everywhere, the classical derivative off the bounds.
+PFB_HD inline bool plant_feedback_free(double u, double lo, double hi) { return (lo < u) && (u < hi); }
+
+// The mask word of one (step, robot): bit i set where control i is clamped; u the nu applied controls, lo and hi the robot's limit rows.
+// nu <= 12 (PLANT_MAX_U), so an int holds it.
+PFB_HD inline int plant_feedback_clamped(const double* u, const double* lo, const double* hi, int nu) {
+    int word = 0;
+    for (int i = 0; i < nu; ++i) if (!plant_feedback_free(u[i], lo[i], hi[i])) word |= 1 << i;
+    return word;
+}
+// whether control i is free by a mask word
+PFB_HD inline bool plant_feedback_word_free(int word, int i) { return ((word >> i) & 1) == 0; }
 
 // gx[j] of the reverse statements: gu the step's nu control cotangents
 PFB_HD inline double plant_feedback_pull(const double* Kk, const double* gu, int nu, int j) {

@@ -334,6 +334,21 @@ bool cimpc::plant_step_chunks(const PlantModel& M, bool rough, const cimpc_ip_op
     return ok;
 }
 
+namespace cimpc {
+// The mask of clamped controls of a limited closed-loop rollout: one work item per (step, robot) writes
+// plant_feedback_clamped of its nu applied controls against the robot's limit rows - comparisons only, so the host's
+// plant.clamped_controls gives the same words.  u_applied: T x B x nu, clamped: T x B, n = T x B.
+constexpr int CLAMP_MASK_THREADS = 256;
+__global__ __launch_bounds__(CLAMP_MASK_THREADS) void plant_clamp_mask_kernel(const double* u_applied, PlantFeedbackLimits lim, int n, int B, int nu,
+                                                                              int* clamped) {
+    const int e = (int)blockIdx.x * CLAMP_MASK_THREADS + (int)threadIdx.x;      // n <= INT_MAX (plant_rollout_check)
+    if (e >= n) return;
+    const int rb = e % B;
+    clamped[e] = plant_feedback_clamped(u_applied + (size_t)e * nu, plant_feedback_limits(lim.u_lo, lim.n_lim, rb, nu),
+                                        plant_feedback_limits(lim.u_hi, lim.n_lim, rb, nu), nu);
+}
+}  // namespace cimpc
+
 namespace {
 // Every entry point, on the call it filled in (plant_rollout_call.h): check it (no device needed), pick the device, lay the call out in
 // the workspace, grow, stage inputs on the device's private stream, launch the rollout's chunks back to back (plant_rollout_plan.h; the
@@ -348,6 +363,9 @@ namespace {
 // With c.loop (the _feedback entry points) the schedule goes up with the inputs, the LOOP instantiation of the kernel runs with R.fb set -
 // the law at the head of a step, then the open-loop step on the control it computed -, u_applied and fb_err come back with
 // the rollout, and the sensitivity launch reads its controls from u_applied, a schedule with K_u = T, n_u = B, hold 1.
+// With limits on the loop the LOOP = 2 instantiation runs; the sensitivity launch is unchanged - its blocks are taken with the applied
+// control as theta's column and do not see the clamp -, and with a tape plant_clamp_mask_kernel follows the chunks and writes the mask
+// words into memory the tape owns, which also come back in c.loop->clamped.
 int plant_rollout_impl(const cimpc::PlantRolloutCall& c, cimpc::PlantTapeBuffers* tape) {
     using namespace cimpc;
     PlantModel M{};
@@ -358,6 +376,7 @@ int plant_rollout_impl(const cimpc::PlantRolloutCall& c, cimpc::PlantTapeBuffers
     const PlantRolloutLayout L = plant_rollout_layout(M, c);
     const int B = c.B, T = c.T;
     const cimpc_feedback* f = c.loop ? c.loop->fb : nullptr;
+    const bool limited = f && c.loop->u_lo;
     std::lock_guard<std::mutex> lock(g_plant_mu);
     PlantWs* ws = plant_ws_open(dev);
     if (!ws) return CIMPC_ERR_HIP;
@@ -379,7 +398,8 @@ int plant_rollout_impl(const cimpc::PlantRolloutCall& c, cimpc::PlantTapeBuffers
             *p = nullptr;
             return false;
         };
-        if (!alloc(&tape->d_dz, L.dz.n) || !alloc(&tape->d_status, L.grad_status.n) || (f && !alloc(&tape->d_fb_K, L.fb_K.n))) {
+        if (!alloc(&tape->d_dz, L.dz.n) || !alloc(&tape->d_status, L.grad_status.n) || (f && !alloc(&tape->d_fb_K, L.fb_K.n)) ||
+            (limited && !alloc(&tape->d_clamped, L.TB))) {
             (void)tape->release();
             return CIMPC_ERR_HIP;
         }
@@ -398,7 +418,6 @@ int plant_rollout_impl(const cimpc::PlantRolloutCall& c, cimpc::PlantTapeBuffers
     if (L.mu.n) up(dmu, c.mu, L.mu.n);
     if (rough) up(W.d_ter, c.terrain, (size_t)c.n_terrain);
     if (f) { up(d_fk, f->K, L.fb_K.n); up(d_fx, f->x_ref, L.x_ref.n); }
-    const bool limited = f && c.loop->u_lo;
     if (limited) { up(W.d_fb + L.u_lo.at, c.loop->u_lo, L.u_lo.n); up(W.d_fb + L.u_hi.at, c.loop->u_hi, L.u_hi.n); }
     const bool has_w = c.w.rows != nullptr;
     PlantStepArrays R{dq, du, has_w ? dw : nullptr, L.mu.n ? dmu : nullptr, dg, db, d_st, d_it, c.mu[0], c.h, c.u.K, c.u.n, c.u.hold,
@@ -406,6 +425,13 @@ int plant_rollout_impl(const cimpc::PlantRolloutCall& c, cimpc::PlantTapeBuffers
     if (f) { R.fb = PlantFeedback{d_fk, d_fx, f->K_f, f->n_f, f->hold_f, f->n_sample}; R.u_applied = d_ua; R.fb_err = d_fe; }
     if (limited) R.lim = PlantFeedbackLimits{W.d_fb + L.u_lo.at, W.d_fb + L.u_hi.at, c.loop->n_lim};
     ok = ok && plant_step_chunks(M, rough, *c.opts, B, T, c.steps_per_launch, R, rough ? W.d_ter : nullptr, rough ? c.n_terrain : 0, st);
+    if (ok && limited && tape) {      // the mask of the controls the steps applied
+        const int n = (int)L.TB;
+        hipLaunchKernelGGL(plant_clamp_mask_kernel, dim3((unsigned)((n + CLAMP_MASK_THREADS - 1) / CLAMP_MASK_THREADS)), dim3(CLAMP_MASK_THREADS), 0, st,
+                           (const double*)d_ua, R.lim, n, B, M.nu, tape->d_clamped);
+        ok = hipGetLastError() == hipSuccess;
+        down(c.loop->clamped, tape->d_clamped, L.TB);
+    }
     if (ok && c.grad) {
         PlantSensSource src{W.d_z, nullptr, dq, du, R.w, R.mu, d_st, R.mu0, c.h, B, R.K_u, R.n_u, R.hold_u, R.K_w, R.n_w, R.hold_w, c.n_mu};
         if (f) { src.u = d_ua; src.K_u = T; src.n_u = B; src.hold_u = 1; }      // the controls the steps applied
@@ -478,16 +504,12 @@ extern "C" int cimpc_plant_rollout_feedback_limits(int model, int B, int T, int 
                                                    const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status, int* iters,
                                                    const cimpc_feedback* fb, double* u_applied, double* fb_err, int n_lim, const double* u_lo,
                                                    const double* u_hi) {
-    auto refuse = [](const char* why) { cimpc::set_global_error(std::string("cimpc_plant_rollout_feedback_limits: ") + why); return CIMPC_ERR_INVALID; };
-    if (!u_lo || !u_hi) return refuse("a null u_lo or u_hi");
-    if (n_lim != 1 && n_lim != B) return refuse("n_lim neither 1 nor B");
-    cimpc::PlantModel named{};
-    if (!cimpc::plant_model_by_id(model, &named) || named.nu < 1) return refuse("a model without controls");
-    for (size_t e = 0; e < (size_t)n_lim * named.nu; ++e) {
-        if (u_lo[e] != u_lo[e] || u_hi[e] != u_hi[e]) return refuse("a NaN limit");
-        if (u_lo[e] > u_hi[e]) return refuse("u_lo above u_hi");
+    const cimpc::PlantRolloutLoop loop{fb, u_applied, fb_err, u_lo, u_hi, n_lim};
+    if (const char* why = cimpc::plant_limits_refusal(model, B, loop, false)) {
+        cimpc::set_global_error(std::string("cimpc_plant_rollout_feedback_limits: ") + why);
+        return CIMPC_ERR_INVALID;
     }
-    const int rc = plant_rollout_impl({PLANT_ROLLOUT_CALL_BASE, .loop = cimpc::PlantRolloutLoop{fb, u_applied, fb_err, u_lo, u_hi, n_lim}}, nullptr);
+    const int rc = plant_rollout_impl({PLANT_ROLLOUT_CALL_BASE, .loop = loop}, nullptr);
     if (rc == CIMPC_ERR_INVALID) cimpc::set_global_error("cimpc_plant_rollout_feedback_limits: an argument that cimpc_plant_rollout_feedback refuses");
     return rc;
 }
@@ -502,3 +524,21 @@ extern "C" int cimpc_plant_rollout_grad_feedback(int model, int B, int T, int st
                                .loop = cimpc::PlantRolloutLoop{fb, u_applied, fb_err}}, nullptr);
 }
 
+// cimpc_plant_rollout_grad_feedback under control limits: the rollout of cimpc_plant_rollout_feedback_limits
+// with the step gradients of every step.  The blocks are taken with the applied - limited - control as theta's column, so they are those
+// of an open-loop rollout on u_applied and do not see the clamp; there is no mask output (plant.clamped_controls restates it on u_applied).
+extern "C" int cimpc_plant_rollout_grad_feedback_limits(int model, int B, int T, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                                        const double* q0, const double* q1, const double* u, int K_u, int n_u, int hold_u,
+                                                        const double* w, int K_w, int n_w, int hold_w, const double* mu, int n_mu, double h,
+                                                        const cimpc_ip_opts* opts, double* q, double* gamma, double* b, int* status, int* iters,
+                                                        double reg, int n_cols, double* z, double* dz, int* grad_status, const cimpc_feedback* fb,
+                                                        double* u_applied, double* fb_err, int n_lim, const double* u_lo, const double* u_hi) {
+    const cimpc::PlantRolloutLoop loop{fb, u_applied, fb_err, u_lo, u_hi, n_lim};
+    if (const char* why = cimpc::plant_limits_refusal(model, B, loop, false)) {
+        cimpc::set_global_error(std::string("cimpc_plant_rollout_grad_feedback_limits: ") + why);
+        return CIMPC_ERR_INVALID;
+    }
+    const int rc = plant_rollout_impl({PLANT_ROLLOUT_CALL_BASE, .grad = cimpc::PlantRolloutGrad{reg, n_cols, z, dz, grad_status, false}, .loop = loop}, nullptr);
+    if (rc == CIMPC_ERR_INVALID) cimpc::set_global_error("cimpc_plant_rollout_grad_feedback_limits: an argument that cimpc_plant_rollout_grad_feedback refuses");
+    return rc;
+}

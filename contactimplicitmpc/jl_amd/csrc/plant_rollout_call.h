@@ -2,7 +2,8 @@
 // what the call is given (PlantRolloutCall), every test made on it before a device is touched (plant_rollout_check), and where each
 // of its arrays lives in the plant workspace's grow-only buffers (plant_rollout_layout).  The eight entry points - cimpc_plant_step,
 // _step_terrain, _rollout, _rollout_grad, _rollout_tape and the three _feedback ones - fill a PlantRolloutCall from their C parameter
-// lists and hand it to plant_rollout_impl (plant_kernel.hip), which reads its pointers off the layout.
+// lists and hand it to plant_rollout_impl (plant_kernel.hip), which reads its pointers off the layout; so do the three _feedback_limits
+// entries, whose limits plant_limits_refusal tests by reason.
 #pragma once
 #include <climits>
 #include <cmath>
@@ -29,12 +30,15 @@ struct PlantRolloutGrad {
 };
 
 // A closed loop (the _feedback entry points): the host schedule and where u_applied (T x B x nu) and fb_err (T x B x 2nq) go
-// u_lo, u_hi (both or neither): the limited law of plant_feedback.h, n_lim x nu host rows, n_lim 1 or B; not with grad.
+// u_lo, u_hi (both or neither): the limited law of plant_feedback.h, n_lim x nu host rows, n_lim 1 or B.  With grad the blocks are taken
+// with the applied control as theta's column, so they do not see the clamp; with a tape the tape also owns the mask of clamped controls
+// (DESIGN.md section 3, item 3i), and clamped (T x B words) is where it comes back: limits on a tape without it are refused.
 struct PlantRolloutLoop {
     const cimpc_feedback* fb;
     double *u_applied, *fb_err;
     const double *u_lo = nullptr, *u_hi = nullptr;
     int n_lim = 1;
+    int* clamped = nullptr;
 };
 
 // Everything a rollout call is given.  A simulator step is T = 1, steps_per_launch = 1, one u and one w row per robot, n_mu = 1 and
@@ -126,6 +130,22 @@ inline PlantRolloutLayout plant_rollout_layout(const PlantModel& M, const PlantR
     return L;
 }
 
+// Why the limits of a closed loop are refused, or null when they stand: what the three _feedback_limits entries leave for
+// cimpc_last_error(NULL), in the order cimpc_plant_rollout_feedback_limits has tested them since it exists.  tape: the call records a tape.
+inline const char* plant_limits_refusal(int model, int B, const PlantRolloutLoop& l, bool tape) {
+    if (!l.u_lo || !l.u_hi) return "a null u_lo or u_hi";
+    if (l.n_lim != 1 && l.n_lim != B) return "n_lim neither 1 nor B";
+    PlantModel named{};
+    if (!plant_model_by_id(model, &named) || named.nu < 1) return "a model without controls";
+    const size_t n = l.n_lim > 0 ? (size_t)l.n_lim * named.nu : 0;
+    for (size_t e = 0; e < n; ++e) {
+        if (l.u_lo[e] != l.u_lo[e] || l.u_hi[e] != l.u_hi[e]) return "a NaN limit";
+        if (l.u_lo[e] > l.u_hi[e]) return "u_lo above u_hi";
+    }
+    if (tape && !l.clamped) return "limits on a tape without clamped";
+    return nullptr;
+}
+
 // Every test of a call that needs no device.  CIMPC_OK: *M is the call's model and *rough says whether its terrains have to reach the
 // device; CIMPC_ERR_INVALID: the call is refused.  K and x_ref are read (they must be finite) only after every test on the schedule
 // that owns them.
@@ -154,10 +174,8 @@ inline int plant_rollout_check(const PlantRolloutCall& c, PlantModel* M, bool* r
         const PlantRolloutLayout L = plant_rollout_layout(*M, c);
         for (size_t i = 0; i < L.fb_K.n; ++i) if (!std::isfinite(f->K[i])) return CIMPC_ERR_INVALID;
         for (size_t i = 0; i < L.x_ref.n; ++i) if (!std::isfinite(f->x_ref[i])) return CIMPC_ERR_INVALID;
-        if (c.loop->u_lo || c.loop->u_hi) {      // limits: both arrays, no NaN, u_lo <= u_hi, and no gradients through the clamp
-            if (!c.loop->u_lo || !c.loop->u_hi || c.grad || (c.loop->n_lim != 1 && c.loop->n_lim != B)) return CIMPC_ERR_INVALID;
-            for (size_t i = 0; i < L.u_lo.n; ++i) if (!(c.loop->u_lo[i] <= c.loop->u_hi[i])) return CIMPC_ERR_INVALID;
-        }
+        // limits: both arrays, n_lim 1 or B, no NaN, u_lo <= u_hi, and on a tape somewhere for the mask to go
+        if ((c.loop->u_lo || c.loop->u_hi) && plant_limits_refusal(c.model, B, *c.loop, c.grad && c.grad->tape)) return CIMPC_ERR_INVALID;
     }
     return CIMPC_OK;
 }

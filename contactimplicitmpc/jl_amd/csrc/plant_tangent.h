@@ -6,6 +6,8 @@
 //   for t = 0 .. T-1:   closed-loop tape only (k the step's feedback row; the functions of plant_feedback.h on tangents - the law is linear):
 //                           de[j]   = plant_feedback_error(dxref_t, dq[t], dq[t+1], nq, n_sample, j)      j = 0 .. 2nq-1   (dxref_t absent = zeros)
 //                           du_t[i] = plant_feedback_control(K[k], de, nu, nq, i, dubar_t[i])              i = 0 .. nu-1
+//                       limited closed-loop tape (item 3i; `clamped` non-null, the mask words of plant_feedback.h):
+//                           du_t[i] = free ? plant_feedback_control(K[k], de, nu, nq, i, dubar_t[i]) : 0.0                 and du_applied stores it
 //                       open-loop tape: du_t = dubar_t
 //                       x = [dq[t]; dq[t+1]; du_t; dw_t; dmu; dh] cut to n_cols      (an input that was not passed is 0.0; nothing is skipped)
 //                       y[r] = sum_{c = 0 .. n_cols-1} D_t[r, c] x[c]                ascending c from 0.0, one product and one sum per term
@@ -55,7 +57,11 @@ struct PlantTangent {
     PlantFeedback fb{};                   // fb.K null: an open-loop tape
     const double* dxref_step = nullptr;
     double* du_applied = nullptr;
+    const int* clamped = nullptr;         // T x B mask words, with fb.K alone; null = a closed loop without limits (item 3i)
 };
+
+// the three compile-time states of the chain, as in plant_adjoint.h: open loop, closed loop, closed loop with the clamp's mask
+constexpr int PLANT_TANGENT_OPEN = 0, PLANT_TANGENT_LOOP = 1, PLANT_TANGENT_CLAMP = 2;
 
 // ---- the plan: what a group of nd directions needs of the team's shared memory, and how many directions a workgroup takes --------------
 // per direction: x (n_cols), the three-row ring of dq (3 nq), and with feedback de (2nq); du_t has no buffer of its own: it is x[2nq : 2nq+nu]
@@ -97,10 +103,13 @@ struct PlantTangentSolo {
 };
 
 // The chain of robot rb for the directions [d0, d0 + nd), d0 + nd <= P.n_dir.  work: shared by the team,
-// plant_tangent_work_doubles(nr, n_cols, nq, nu, FB, nd).  FB: the feedback statements are compiled in (the caller has P.fb.K non-null);
-// without it the chain carries nothing of the feedback path.  The group with d0 = 0 reports n_cut.
-template <bool FB, class Team>
+// plant_tangent_work_doubles(nr, n_cols, nq, nu, FB != 0, nd).  FB != 0: the feedback statements are compiled in (the caller has P.fb.K
+// non-null); without it the chain carries nothing of the feedback path.  FB == PLANT_TANGENT_CLAMP: the mask is read too (the caller has
+// P.clamped non-null), its word of step t + 1 when block t + 1 is sent for; the other two carry nothing of it, and it needs no shared
+// memory.  (`true` still names the closed loop: it converts to 1.)  The group with d0 = 0 reports n_cut.
+template <int FB, class Team>
 PTAN_HD inline void plant_tangent_chain_as(const PlantTangent& P, int rb, int d0, int nd, double* work, Team& team) {
+    static_assert(FB == PLANT_TANGENT_OPEN || FB == PLANT_TANGENT_LOOP || FB == PLANT_TANGENT_CLAMP, "open loop, closed loop, or closed loop with the mask");
     const int me = team.rank(), np = team.size();
     const int nq = P.nq, nu = P.nu, nw = P.nw, nc = P.nc, nb = P.nb, n_cols = P.n_cols, B = P.B, T = P.T;
     const int nr = nq + nc + nb, blk = nr * n_cols;
@@ -123,13 +132,19 @@ PTAN_HD inline void plant_tangent_chain_as(const PlantTangent& P, int rb, int d0
         P.dq[(((size_t)(d0 + d) * (T + 2) + 1) * B + rb) * nq + i] = a1;
     }
     team.fetch_issue(block(0), blk);
+    int word_next = 0;                                                // the mask word of the block in flight
+    if constexpr (FB == PLANT_TANGENT_CLAMP) word_next = P.clamped[rb];
     team.fetch_commit(D[0], block(0), blk);
     team.sync();
 
     int cut = 0;
     for (int t = 0; t < T; ++t) {
         const size_t e = (size_t)t * B + rb;
-        if (t + 1 < T) team.fetch_issue(block(t + 1), blk);           // in flight while block t is used
+        const int word = word_next;
+        if (t + 1 < T) {
+            team.fetch_issue(block(t + 1), blk);                      // in flight while block t is used
+            if constexpr (FB == PLANT_TANGENT_CLAMP) word_next = P.clamped[e + B];
+        }
         if (me == 0 && P.status[e] == 0) ++cut;
         // x but for its controls on a closed-loop tape, and de
         for (int k = me; k < nd * n_cols; k += np) {                  // (c, d), c fastest
@@ -138,13 +153,13 @@ PTAN_HD inline void plant_tangent_chain_as(const PlantTangent& P, int rb, int d0
             double v;
             if (c < nq) v = row(d, t)[c];
             else if (c < c_u) v = row(d, t + 1)[c - nq];
-            else if (c < c_w) { if constexpr (FB) continue; else v = P.du_step ? P.du_step[s * nu + (c - c_u)] : 0.0; }
+            else if (c < c_w) { if constexpr (FB != PLANT_TANGENT_OPEN) continue; else v = P.du_step ? P.du_step[s * nu + (c - c_u)] : 0.0; }
             else if (c < c_mu) v = P.dw_step ? P.dw_step[s * nw + (c - c_w)] : 0.0;
             else if (c < c_h) v = P.dmu ? P.dmu[(size_t)(d0 + d) * B + rb] : 0.0;
             else v = P.dh ? P.dh[(size_t)(d0 + d) * B + rb] : 0.0;
             xs[(size_t)d * n_cols + c] = v;
         }
-        if constexpr (FB) {                                           // the feedback path of step t (plant_feedback.h), on tangents
+        if constexpr (FB != PLANT_TANGENT_OPEN) {                     // the feedback path of step t (plant_feedback.h), on tangents
             for (int k = me; k < nd * 2 * nq; k += np) {              // (j, d), j fastest
                 const int j = k % (2 * nq), d = k / (2 * nq);
                 double* de = es + (size_t)d * 2 * nq;
@@ -156,7 +171,10 @@ PTAN_HD inline void plant_tangent_chain_as(const PlantTangent& P, int rb, int d0
             for (int k = me; k < nd * nu; k += np) {                  // (i, d), i fastest
                 const int i = k % nu, d = k / nu;
                 const size_t s = ((size_t)(d0 + d) * TB + e) * nu + i;
-                const double u = plant_feedback_control(Kk, es + (size_t)d * 2 * nq, nu, nq, i, P.du_step ? P.du_step[s] : 0.0);
+                double u;
+                if constexpr (FB == PLANT_TANGENT_CLAMP) {            // item 3i: nothing passes a clamped control
+                    u = plant_feedback_word_free(word, i) ? plant_feedback_control(Kk, es + (size_t)d * 2 * nq, nu, nq, i, P.du_step ? P.du_step[s] : 0.0) : 0.0;
+                } else u = plant_feedback_control(Kk, es + (size_t)d * 2 * nq, nu, nq, i, P.du_step ? P.du_step[s] : 0.0);
                 xs[(size_t)d * n_cols + c_u + i] = u;
                 if (P.du_applied) P.du_applied[s] = u;
             }
@@ -184,8 +202,9 @@ PTAN_HD inline void plant_tangent_chain_as(const PlantTangent& P, int rb, int d0
 // The chain of (robot rb, group [d0, d0 + nd)), open or closed loop by what P carries.
 template <class Team>
 PTAN_HD inline void plant_tangent_chain(const PlantTangent& P, int rb, int d0, int nd, double* work, Team& team) {
-    if (P.fb.K) plant_tangent_chain_as<true>(P, rb, d0, nd, work, team);
-    else plant_tangent_chain_as<false>(P, rb, d0, nd, work, team);
+    if (P.fb.K && P.clamped) plant_tangent_chain_as<PLANT_TANGENT_CLAMP>(P, rb, d0, nd, work, team);
+    else if (P.fb.K) plant_tangent_chain_as<PLANT_TANGENT_LOOP>(P, rb, d0, nd, work, team);
+    else plant_tangent_chain_as<PLANT_TANGENT_OPEN>(P, rb, d0, nd, work, team);
 }
 
 }  // namespace cimpc

@@ -4,7 +4,8 @@
 //   cimpc_plant_tape_jvp            tangents (dq0, dq1, du_step, dw_step, dmu, dh; those given) up, ONE launch of plant_tangent_kernel,
 //                                   the trajectory tangents (dq, dgamma, db) and n_cut down
 //   cimpc_plant_tape_jvp_feedback   the same with dxref_step in and du_applied out, on a closed-loop tape; a closed-loop tape's chain
-//                                   runs the feedback statements through either entry
+//                                   runs the feedback statements through either entry, and the tape of a limited closed loop
+//                                   (item 3i) launches the third instantiation, which reads the tape's mask of clamped controls
 //
 // plant_tangent_kernel: grid (B, direction groups), a workgroup of TAN_THREADS = 256 (four wavefronts, one per SIMD of the CU) walks
 // t = 0 .. T-1 through the statements of plant_tangent.h for one robot and plant_tangent_group(...) directions.  D_t (nr x n_cols
@@ -52,7 +53,9 @@ struct PlantTangentGroup {
     }
 };
 
-template <bool FB>      // FB: a closed-loop tape's chain, with the feedback statements of plant_feedback.h
+// FB: PLANT_TANGENT_OPEN, PLANT_TANGENT_LOOP (a closed-loop tape's chain, with the feedback statements of plant_feedback.h) or
+// PLANT_TANGENT_CLAMP (a limited closed-loop tape's, which also reads the tape's mask of clamped controls)
+template <int FB>
 __global__ __launch_bounds__(TAN_THREADS) void plant_tangent_kernel(PlantTangent P, int group) {
     extern __shared__ __attribute__((aligned(16))) double tan_lds[];      // plant_tangent_lds(nr, n_cols, nq, nu, FB, group)
     const int rb = blockIdx.x, d0 = (int)blockIdx.y * group;
@@ -116,8 +119,8 @@ extern "C" int cimpc_plant_tape_jvp_feedback(cimpc_plant_tape tape, int n_dir, c
             PlantTangent P{buf.d_dz, buf.d_status, dq0 ? d_q0 : nullptr, dq1 ? d_q1 : nullptr, du_step ? d_u : nullptr, dw_step ? d_w : nullptr,
                            dmu ? d_m : nullptr, dh ? d_h : nullptr, d_dq, dgamma ? d_dg : nullptr, db ? d_db : nullptr, ws->d_tan_cut, B, T,
                            (int)nq, (int)nu, (int)nw, (int)nc, (int)nb, n_cols, n_dir};
-            if (fb.K) { P.fb = fb; P.dxref_step = dxref_step ? d_x : nullptr; P.du_applied = du_applied ? d_ua : nullptr; }
-            auto kernel = fb.K ? plant_tangent_kernel<true> : plant_tangent_kernel<false>;
+            if (fb.K) { P.fb = fb; P.dxref_step = dxref_step ? d_x : nullptr; P.du_applied = du_applied ? d_ua : nullptr; P.clamped = buf.d_clamped; }
+            auto kernel = !fb.K ? plant_tangent_kernel<PLANT_TANGENT_OPEN> : buf.d_clamped ? plant_tangent_kernel<PLANT_TANGENT_CLAMP> : plant_tangent_kernel<PLANT_TANGENT_LOOP>;
             ok = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
             if (ok) {
                 hipLaunchKernelGGL(kernel, dim3(B, (unsigned)n_groups), dim3(TAN_THREADS), lds, st, P, per);

@@ -19,14 +19,16 @@ struct PlantTapeBuffers {
     double* d_fb_K = nullptr;    // a closed-loop tape's copy of the gain rows, K_f x n_f x (nu x 2nq); null: an open-loop tape
     int K_f = 1, n_f = 1, hold_f = 1;
     double n_sample = 1.0;
+    int* d_clamped = nullptr;    // a limited closed-loop tape's mask words, T x B (plant_feedback_clamped); null: no limits
 
-    // Frees whichever of the three allocations are set, on the current device, and nulls them.  False: a free failed.
+    // Frees whichever of the four allocations are set, on the current device, and nulls them.  False: a free failed.
     bool release() {
         bool ok = true;
         if (d_dz) ok = hipFree(d_dz) == hipSuccess;
         if (d_status) ok = (hipFree(d_status) == hipSuccess) && ok;
         if (d_fb_K) ok = (hipFree(d_fb_K) == hipSuccess) && ok;
-        d_dz = nullptr; d_status = nullptr; d_fb_K = nullptr;
+        if (d_clamped) ok = (hipFree(d_clamped) == hipSuccess) && ok;
+        d_dz = nullptr; d_status = nullptr; d_fb_K = nullptr; d_clamped = nullptr;
         return ok;
     }
 };
@@ -35,7 +37,8 @@ struct PlantTapeBuffers {
 // the plant mutex it allocates d_dz and d_status on the current device, has the sensitivity launch target them DIRECTLY (no copy
 // through the workspace's d_grad), reads the status back and leaves dz on the device.  On any failure the pointers are null and
 // nothing stays allocated.  With call.loop (cimpc_plant_rollout_tape_feedback) the tape also gets d_fb_K and the schedule's
-// (K_f, n_f, hold_f, n_sample).
+// (K_f, n_f, hold_f, n_sample).  With limits on that loop (cimpc_plant_rollout_tape_feedback_limits) it also gets d_clamped, which
+// plant_clamp_mask_kernel fills behind the rollout's chunks from u_applied and the limits where they lie on the device.
 int plant_rollout_to_tape(const PlantRolloutCall& call, PlantTapeBuffers* tape);
 
 }  // namespace cimpc

@@ -24,6 +24,10 @@ Control limits: `Feedback(u_lo=, u_hi=)` clamps t
 solves a box-constrained QP per step (and takes a rho per robot), `linesearch(u_lo=, u_hi=)` runs its candidates under the clamped law, and
 `ilqr(u_lo=, u_hi=)` is control-limited iLQR on the three (`cimpc_plant_rollout_feedback_limits`, `cimpc_plant_tape_lqr_box`,
 `cimpc_plant_tape_linesearch_box`).
+`Feedback(..., u_lo=, u_hi=, clamp_grad=True)` differentiates that clamped closed loop: a control is free where
+its applied value lies strictly inside its limits and clamped otherwise, the limited law's derivative is the unlimited law's where free and
+exactly 0.0 where clamped, and `rollout(diff_sol=True)`, `rollout_tape`, `vjp`, `jvp`, `transition` and `rollout_torch` then work under limits
+(`cimpc_plant_rollout_grad_feedback_limits`, `cimpc_plant_rollout_tape_feedback_limits`); `clamped_controls` restates the mask on the host.
 `ilqr(device_loop=True)` and `ilqr_from_tape` run every iteration of that loop in one library call, on arrays that stay on the device
 (`cimpc_plant_ilqr`); tests/test_gpu_plant_ilqr.py holds them to the host loop bit for bit.
 Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble
@@ -132,14 +136,20 @@ class Feedback:
     nominal, like u: a step applies K[k] / N_sample beside u[k] / N_sample.
     u_lo, u_hi ((nu,) shared or (B, nu), both or neither; ±inf = no limit, NaN refused, u_lo ≤ u_hi): control limits (DESIGN.md section 3,
     item 3g).  The step then applies, and `u_applied` stores, limit(u_t) = u_lo where u_t < u_lo, u_hi where u_t > u_hi, u_t otherwise -
-    the limits bound the control a simulator step applies, nothing is divided by N_sample; `fb_err` is unchanged.  The derivative of the
-    clamp is not built: `rollout_tape`, `rollout(diff_sol=True)` and `rollout_torch` refuse a `Feedback` with limits."""
+    the limits bound the control a simulator step applies, nothing is divided by N_sample; `fb_err` is unchanged.
+    clamp_grad (a bool; True needs limits): the derivative of the clamp is a convention the caller asks for.
+    With limits and clamp_grad=False every gradient call - `rollout_tape`, `rollout(diff_sol=True)`, `rollout_torch` - refuses the `Feedback`.
+    With clamp_grad=True control i of step t is free where u_lo[i] < u_applied[t, b, i] < u_hi[i] and clamped otherwise (on a bound, however
+    it got there; with u_lo[i] == u_hi[i]; NaN), and the limited law's derivative is the unlimited law's where the control is free and exactly
+    0.0 where it is clamped - an element of the generalized derivative everywhere, the classical derivative off the bounds.  The limits are
+    constants: there is no gradient with respect to u_lo or u_hi."""
     K: object
     x_ref: object
     hold: int = 1
     n_sample: object = None
     u_lo: object = None
     u_hi: object = None
+    clamp_grad: bool = False
 
 
 @dataclasses.dataclass
@@ -153,6 +163,7 @@ class _FeedbackArrays:
     shared: bool
     u_lo: object = None      # (n_lim, nu) each, n_lim 1 or B, or both None
     u_hi: object = None
+    clamp_grad: bool = False      # with limits alone: gradient calls take the derivative of DESIGN.md section 3, item 3i
 
     K_f = property(lambda self: self.K.shape[0])
 
@@ -179,7 +190,32 @@ def _feedback_arrays(model: str, fb: Feedback, B: int, N_sample: int) -> _Feedba
     if shared:
         K, xr = K[:, None], xr[:, None]
     lo, hi = _limit_arrays(fb.u_lo, fb.u_hi, B, nu, "Feedback.")
-    return _FeedbackArrays(np.ascontiguousarray((K / int(N_sample)).transpose(0, 1, 3, 2)), np.ascontiguousarray(xr), int(fb.hold), n_sample, shared, lo, hi)
+    if not isinstance(fb.clamp_grad, (bool, np.bool_)):
+        raise ValueError(f"Feedback.clamp_grad must be a bool, got {fb.clamp_grad!r}")
+    if fb.clamp_grad and lo is None:
+        raise ValueError("Feedback.clamp_grad=True needs control limits (u_lo, u_hi): without them there is no clamp to differentiate")
+    return _FeedbackArrays(np.ascontiguousarray((K / int(N_sample)).transpose(0, 1, 3, 2)), np.ascontiguousarray(xr), int(fb.hold), n_sample, shared, lo, hi,
+                           bool(fb.clamp_grad))
+
+
+def clamped_controls(u_applied, u_lo, u_hi):
+    """The mask of clamped controls of a limited closed loop (`plant_feedback_free` of csrc/plant_feedback.h on
+    the host): u_applied (T, B, nu) as a limited rollout returned it, u_lo, u_hi (nu,) or (B, nu) -> (T, B) int32 words, bit i set where
+    control i is clamped, that is where NOT (u_lo[i] < u_applied[t, b, i] < u_hi[i]): on a bound, with u_lo[i] == u_hi[i], or NaN; infinite
+    limits never clamp.  Comparisons only, so the words are those of `RolloutTape.clamped` bit for bit."""
+    ua = np.asarray(u_applied, dtype=np.float64)
+    if ua.ndim != 3 or not 1 <= ua.shape[2] <= 31:
+        raise ValueError(f"u_applied must be (T, B, nu), got {ua.shape}")
+    T, B, nu = ua.shape
+    lo, hi = _limit_arrays(u_lo, u_hi, B, nu)
+    if lo is None:
+        raise ValueError("clamped_controls needs u_lo and u_hi")
+    with np.errstate(invalid="ignore"):
+        free = (lo[None] < ua) & (ua < hi[None])
+    words = np.zeros((T, B), dtype=np.int32)
+    for i in range(nu):
+        words |= np.where(free[:, :, i], 0, 1 << i).astype(np.int32)
+    return words
 
 
 def _limit_arrays(u_lo, u_hi, B: int, nu: int, what: str = ""):
@@ -202,7 +238,7 @@ def _limit_arrays(u_lo, u_hi, B: int, nu: int, what: str = ""):
 class _RolloutResult:
     """What `_rollout_call` returns: q (T + 2, B, nq), gamma, b, status, iters as the library wrote them; grads with grad and no tape;
     tape = (z or None, grad_status, the tape's handle) with a tape; u_applied (T, B, nu) and fb_err (T, B, 2nq) as the device made them
-    with feedback.  Whatever the call did not ask for is None."""
+    with feedback; clamped (T, B) int32, the mask words of a limited tape.  Whatever the call did not ask for is None."""
     q: np.ndarray
     gamma: np.ndarray
     b: np.ndarray
@@ -212,13 +248,14 @@ class _RolloutResult:
     tape: object = None
     u_applied: object = None
     fb_err: object = None
+    clamped: object = None
 
 
 def _rollout_call(model: str, q0, q1, ua, hold_u: int, wa, hold_w: int, mua, h: float, opts, terrain, steps_per_launch: int, T: int, grad,
                   tape=None, feedback=None) -> _RolloutResult:
     """`cimpc_plant_rollout`, or `cimpc_plant_rollout_grad` with grad = (reg, n_cols): contiguous q0, q1 (B, nq), ua (K, 1 or B, nu),
     wa None or (K_w, 1 or B, nw), mua (1 or B,).  tape = keep_z (a bool) with grad: `cimpc_plant_rollout_tape`.  feedback = a
-    `_FeedbackArrays`: the `_feedback` entry of each."""
+    `_FeedbackArrays`: the `_feedback` entry of each, with limits the `_feedback_limits` one (with grad only under clamp_grad)."""
     mid, nq, nu, nc, fd, nw = model_dims(model)
     B, nb, nz = q1.shape[0], fd * nc, nq + 4 * nc + 2 * fd * nc
     lib = _lib.load()
@@ -238,10 +275,14 @@ def _rollout_call(model: str, q0, q1, ua, hold_u: int, wa, hold_w: int, mua, h: 
         res.u_applied, res.fb_err = np.zeros((T, B, nu)), np.zeros((T, B, 2 * nq))
         sfx, loop = "_feedback", (C.byref(cfb), dp(res.u_applied), dp(res.fb_err))
         if feedback.u_lo is not None:
-            if grad is not None:
-                raise ValueError("a Feedback with control limits has no gradients: the derivative of the clamp is not built (rollout_tape, "
-                                 "diff_sol=True and rollout_torch refuse it; DESIGN.md section 3, item 3g)")
+            if grad is not None and not feedback.clamp_grad:
+                raise ValueError("a Feedback with control limits has no gradients by default: the derivative of the clamp is a convention to be "
+                                 "asked for with Feedback(..., clamp_grad=True) (rollout_tape, diff_sol=True and rollout_torch refuse it "
+                                 "otherwise; DESIGN.md section 3, item 3i)")
             sfx, loop = "_feedback_limits", loop + (feedback.u_lo.shape[0], dp(feedback.u_lo), dp(feedback.u_hi))
+            if grad is not None and tape is not None:
+                res.clamped = np.zeros((T, B), dtype=np.int32)
+                loop = loop + (ip(res.clamped),)
     gst = np.zeros((T, B), dtype=np.int32)
     if grad is None:
         name, more = "cimpc_plant_rollout", ()
@@ -470,7 +511,9 @@ def rollout(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=None, w
     feedback: a `Feedback` closes the loop on the device (`cimpc_plant_rollout_feedback`, `cimpc_plant_rollout_grad_feedback`): u is
     then the open-loop part ū, the returned u_applied is what the device applied, u_t = ū_t + (K / N_sample) (x_ref − x_t), every step is
     bit for bit the open-loop step on that control, the step gradients are taken with it in θ, and one more trailing element is fb_err
-    (steps, B, 2nq), the errors x_ref − x_t."""
+    (steps, B, 2nq), the errors x_ref − x_t.  A `Feedback` with limits and diff_sol=True needs clamp_grad=True
+    (`cimpc_plant_rollout_grad_feedback_limits`): the blocks are taken with the applied, limited control in θ, so they are those of the
+    open-loop rollout on u_applied."""
     terrain, q1, v1, ua, u_applied, wa, mua = _rollout_inputs(model, q1, v1, u, mu, N_sample, w, w_hold, terrain, steps)
     T = u_applied.shape[0]
     q0 = np.ascontiguousarray(q1 - h * v1); q1 = np.ascontiguousarray(q1)
@@ -595,10 +638,12 @@ class RolloutCotangents:
 class RolloutTape:
     """The step gradients of one rollout, kept on the device (`cimpc_plant_rollout_tape`), for any number of `vjp` calls.  model, B, T,
     n_cols as recorded; grad_status (T, B) as `StepGradients.status`; z (T, B, nz) with keep_z, else None.  `close()` frees the device
-    memory (so does leaving a `with` block, and the finalizer); a closed tape raises on use."""
+    memory (so does leaving a `with` block, and the finalizer); a closed tape raises on use.  clamped: (T, B) int32 on the tape of a limited
+    closed loop (`Feedback(..., clamp_grad=True)`), bit i set where control i of that step is clamped (`clamped_controls`; DESIGN.md section 3,
+    item 3i), else None; `vjp`, `jvp` and `transition` on such a tape pass nothing through a clamped control."""
 
     def __init__(self, handle, model: str, grad_status, z, v1, h: float, u_shape, N_sample: int, w_shape, w_hold: int, mu_shared: bool,
-                 feedback=None, fb_err=None, q1_shape=None, mu_shape=()):
+                 feedback=None, fb_err=None, q1_shape=None, mu_shape=(), clamped=None):
         import weakref
         self._handle, self.model, self.grad_status, self.z = handle, model, grad_status, z
         dims = [C.c_int() for _ in range(4)]
@@ -609,6 +654,7 @@ class RolloutTape:
         assert mid == model_dims(model)[0]
         self._v1, self._h, self._u_shape, self._N_sample, self._w_shape, self._w_hold, self._mu_shared = v1, h, u_shape, N_sample, w_shape, w_hold, mu_shared
         self._feedback, self._fb_err = feedback, fb_err      # a closed-loop tape: its `_FeedbackArrays` and fb_err (T, B, 2nq); else None
+        self.clamped = clamped
         self._q1_shape, self._mu_shape = tuple(np.shape(v1) if q1_shape is None else q1_shape), tuple(mu_shape)      # as the caller gave them
         self._finalizer = weakref.finalize(self, _lib.load().cimpc_plant_tape_destroy, handle)
 
@@ -1031,18 +1077,20 @@ class TapeGains:
     K_blocks: object = None      # K as the library wrote it, (keep, B, 2nq, nu): what `RolloutTape.linesearch` hands back without a transpose
     clamped: object = None
 
-    def feedback(self, q_traj) -> Feedback:
+    def feedback(self, q_traj, u_lo=None, u_hi=None, clamp_grad: bool = False) -> Feedback:
         """The `Feedback` that applies these gains around the trajectory q_traj (T + 2, B, nq) they were computed on: K · N_sample (the
         rollout applies K[k] / N_sample), x_ref[t] = [q_traj[t]; q_traj[t+1]], hold 1, n_sample 1.0 - the law's x_t is then
         [q[t]; q[t+1]] and a step applies u_t = ū_t + K_t (x_ref[t] − x_t).  The first half of x_ref[t] is written as the law writes its
         state, q[t+1] − 1.0 (q[t+1] − q[t]) (q[t] to a rounding), so that on q_traj itself the error is exactly zero and the closed loop
-        retraces it bit for bit.  With keep < T the last row is held from there on."""
+        retraces it bit for bit.  With keep < T the last row is held from there on.  u_lo, u_hi and clamp_grad are passed through to the
+        `Feedback`: with the limits of the `ilqr(u_lo=, u_hi=)` that made these gains and clamp_grad=True, `rollout_tape` tapes the clamped
+        closed loop that result describes."""
         q_traj = np.asarray(q_traj, dtype=np.float64)
         keep, B = self.K.shape[:2]
         if q_traj.ndim != 3 or q_traj.shape[0] < keep + 1 or q_traj.shape[1] != B or 2 * q_traj.shape[2] != self.K.shape[3]:
             raise ValueError(f"q_traj must be (at least {keep + 1}, {B}, {self.K.shape[3] // 2}), got {q_traj.shape}")
         x_ref = np.concatenate([q_traj[1:keep + 1] - 1.0 * (q_traj[1:keep + 1] - q_traj[:keep]), q_traj[1:keep + 1]], axis=2)
-        return Feedback(K=self.K * float(self.N_sample), x_ref=np.ascontiguousarray(x_ref), hold=1, n_sample=1.0)
+        return Feedback(K=self.K * float(self.N_sample), x_ref=np.ascontiguousarray(x_ref), hold=1, n_sample=1.0, u_lo=u_lo, u_hi=u_hi, clamp_grad=clamp_grad)
 
 
 class TrackingCost:
@@ -1126,7 +1174,9 @@ def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=No
     tape a `RolloutTape` whose `vjp` turns cotangents of (q, gamma, b) into the gradient with respect to q1, v1, u, w, mu and h.
     grad_cols (default 2 nq + nu, the least a tape takes) up to nθ adds the w, μ and h columns; keep_z also returns every step's z on
     the tape.  feedback: a `Feedback`, as in `rollout` (`cimpc_plant_rollout_tape_feedback`): u_applied is the device's, one more trailing
-    element is fb_err, and the tape's `vjp` runs the closed-loop chain, whose `RolloutCotangents` carry K, x_ref and xref_step."""
+    element is fb_err, and the tape's `vjp` runs the closed-loop chain, whose `RolloutCotangents` carry K, x_ref and xref_step.  A `Feedback`
+    with limits is taken only with clamp_grad=True (`cimpc_plant_rollout_tape_feedback_limits`): the rollout runs
+    under the limited law, `tape.clamped` holds the mask of clamped controls, and both chains pass nothing through a clamped control."""
     q1_shape, mu_shape = np.shape(q1), np.shape(mu)
     terrain, q1, v1, ua, u_applied, wa, mua = _rollout_inputs(model, q1, v1, u, mu, N_sample, w, w_hold, terrain, steps)
     (T, B), (mid, nq, nu, nc, fd, nw) = u_applied.shape[:2], model_dims(model)
@@ -1139,7 +1189,8 @@ def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=No
                       feedback=loop)
     z, gst, handle = r.tape
     tape = RolloutTape(handle, model, gst, z, v1.copy(), float(h), np.shape(u), int(N_sample), None if w is None else np.shape(w), int(w_hold),
-                       np.ndim(mu) == 0 or (mua.size == 1 and B > 1), fb_err=r.fb_err, feedback=loop, q1_shape=q1_shape, mu_shape=mu_shape)
+                       np.ndim(mu) == 0 or (mua.size == 1 and B > 1), fb_err=r.fb_err, feedback=loop, q1_shape=q1_shape, mu_shape=mu_shape,
+                       clamped=r.clamped)
     tape._context = dict(mu=mua, w=w, w_hold=int(w_hold), terrain=terrain, opts=opts, steps_per_launch=int(steps_per_launch), grad_reg=reg)      # for `linesearch`
     out = (bool(r.status.all()), r.q, u_applied if loop is None else r.u_applied, r.gamma, r.b, r.status, r.iters, tape)
     return out if loop is None else out + (r.fb_err,)
@@ -1361,7 +1412,8 @@ def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, feedback=None,
     the device of the first tensor given, status an int tensor without a gradient.  `backward` runs `RolloutTape.vjp` on the tape,
     which lives on the autograd graph - any number of times with retain_graph=True - and gradients reach whichever of q1, v1, u, w, mu
     require them; grad_cols is raised to cover w and mu when they do.  feedback: a `Feedback` whose K and x_ref may be tensors too; with
-    it the rollout is closed-loop, and gradients also reach K and x_ref when they require them.  Forward mode: under
+    it the rollout is closed-loop, and gradients also reach K and x_ref when they require them; with limits and clamp_grad=True it is the
+    clamped closed loop, differentiated by DESIGN.md section 3, item 3i.  Forward mode: under
     `torch.autograd.forward_ad.dual_level()`, tangents on q1, v1, u, mu, w, K and x_ref reach q, gamma and b through `RolloutTape.jvp`
     on the same tape (grad_cols is raised for a dual w or mu as for one that requires a gradient)."""
     import torch

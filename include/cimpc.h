@@ -557,7 +557,8 @@ int cimpc_plant_rollout_feedback(int model, int B, int T, int steps_per_launch,
  * does not converge); fb_err is unchanged.  u_lo, u_hi: n_lim x nu with n_lim 1 (one row for every robot) or B, -inf and +inf meaning no
  * limit; with every limit infinite the call is cimpc_plant_rollout_feedback bit for bit.  CIMPC_ERR_INVALID before any device is touched,
  * with its reason in cimpc_last_error(NULL): a null u_lo or u_hi, n_lim neither 1 nor B, a NaN limit, u_lo above u_hi, or whatever
- * cimpc_plant_rollout_feedback refuses.  The tape and gradient entries take no limits: the derivative of the clamp is not built. */
+ * cimpc_plant_rollout_feedback refuses.  cimpc_plant_rollout_grad_feedback and cimpc_plant_rollout_tape_feedback take no limits; their
+ * _limits namesakes below do, with the derivative of the clamp that DESIGN.md section 3, item 3i defines. */
 int cimpc_plant_rollout_feedback_limits(int model, int B, int T, int steps_per_launch,
                                         int n_terrain, const cimpc_terrain* terrain,
                                         const double* q0, const double* q1,
@@ -586,6 +587,43 @@ int cimpc_plant_rollout_tape_feedback(int model, int B, int T, int steps_per_lau
                                       double* q, double* gamma, double* b, int* status, int* iters,
                                       double reg, int n_cols, double* z, int* grad_status, cimpc_plant_tape* tape,
                                       const cimpc_feedback* fb, double* u_applied, double* fb_err);
+/* ---- the limited closed loop, differentiated (csrc/plant_feedback.h) ---------------------------------------
+ * Control i of step t of a robot is FREE when its APPLIED value lies strictly inside its limits, u_lo[i] < u_applied[t, b, i] < u_hi[i],
+ * and CLAMPED otherwise: on a bound (whether the limiter moved it there or the law landed there), with u_lo[i] == u_hi[i], and when it is
+ * NaN; infinite limits never clamp.  The derivative of the limited law is the unlimited law's where the control is free and exactly 0.0
+ * where it is clamped - an element of the generalized derivative everywhere, the classical derivative off the bounds.  In the chains:
+ *     forward:  du_t[i] = free ? dubar_t[i] + sum_j K[k][i, j] de[j] : 0.0                (du_applied stores it)
+ *     reverse:  gm = free ? v[2nq + i] : 0.0;   g_u_step[t][i] = gm;   gu[i] = gm          (gx = K' gu and the lambda updates unchanged)
+ * g_u_step stays the gradient of ubar_t, and the caller's sums over it give the gradients of K and x_ref as before.  The limits are
+ * constants: no gradient with respect to u_lo or u_hi.
+ *
+ * cimpc_plant_rollout_grad_feedback_limits: cimpc_plant_rollout_grad_feedback under the limits of cimpc_plant_rollout_feedback_limits.  The
+ * blocks are taken with the applied control as theta's column - they are those of cimpc_plant_rollout_grad on u_applied and do not see the
+ * clamp.  cimpc_plant_rollout_tape_feedback_limits: cimpc_plant_rollout_tape_feedback under those limits; the tape also owns the mask of
+ * clamped controls, which comes back in clamped, T x B words, bit i set where control i is clamped (nu <= 12), and cimpc_plant_tape_vjp,
+ * _vjp_feedback, _jvp and _jvp_feedback on such a tape run the statements above.  Both refuse (CIMPC_ERR_INVALID before any device is touched,
+ * the reason in cimpc_last_error(NULL)) what cimpc_plant_rollout_feedback_limits refuses of the limits, the tape entry also a NULL clamped,
+ * and then whatever their namesakes without limits refuse. */
+int cimpc_plant_rollout_grad_feedback_limits(int model, int B, int T, int steps_per_launch,
+                                             int n_terrain, const cimpc_terrain* terrain,
+                                             const double* q0, const double* q1,
+                                             const double* u, int K_u, int n_u, int hold_u,
+                                             const double* w, int K_w, int n_w, int hold_w,
+                                             const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                                             double* q, double* gamma, double* b, int* status, int* iters,
+                                             double reg, int n_cols, double* z, double* dz, int* grad_status,
+                                             const cimpc_feedback* fb, double* u_applied, double* fb_err,
+                                             int n_lim, const double* u_lo, const double* u_hi);
+int cimpc_plant_rollout_tape_feedback_limits(int model, int B, int T, int steps_per_launch,
+                                             int n_terrain, const cimpc_terrain* terrain,
+                                             const double* q0, const double* q1,
+                                             const double* u, int K_u, int n_u, int hold_u,
+                                             const double* w, int K_w, int n_w, int hold_w,
+                                             const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                                             double* q, double* gamma, double* b, int* status, int* iters,
+                                             double reg, int n_cols, double* z, int* grad_status, cimpc_plant_tape* tape,
+                                             const cimpc_feedback* fb, double* u_applied, double* fb_err,
+                                             int n_lim, const double* u_lo, const double* u_hi, int* clamped);
 /* cimpc_plant_tape_vjp's arguments, then g_xref_step (T x B x 2nq, may be NULL).  The chain of a closed-loop tape always includes the
  * feedback path: cimpc_plant_tape_vjp on such a tape is this call with NULL.  A non-NULL g_xref_step on an open-loop tape:
  * CIMPC_ERR_INVALID. */

@@ -814,6 +814,102 @@ function plant_rollout_tape_feedback(model::Symbol, q1::Matrix{Float64}, v1::Mat
 end
 
 """
+    plant_rollout_tape_feedback_limits(model, q1, v1, u, μ, h_sim, opts, K, x_ref, u_lo, u_hi; ...)
+        -> (ok, q, u_applied, γ, b, status, iters, tape, fb_err, clamped)
+
+`plant_rollout_tape_feedback` under control limits, differentiated by DESIGN.md section 3, item 3i (`cimpc_plant_rollout_tape_feedback_limits`):
+u_lo, u_hi are nu x 1 (shared) or nu x B, ±Inf meaning no limit.  Control i of a step is free where u_lo[i] < u_applied[i, b, t] < u_hi[i] and
+clamped otherwise; clamped (B x steps) holds a word per step whose bit i - 1 is set where control i is clamped, the tape owns the same mask, and
+`plant_tape_vjp`, `plant_tape_vjp_feedback` and `plant_tape_jvp` on it pass nothing through a clamped control: the limited law's derivative is the
+unlimited law's where free and exactly 0.0 where clamped.  The keywords are `plant_rollout_tape_feedback`'s.  Unexecuted, like the rest of this binding.
+"""
+function plant_rollout_tape_feedback_limits(model::Symbol, q1::Matrix{Float64}, v1::Matrix{Float64}, u::Array{Float64}, μ, h_sim, opts,
+                                            K::Array{Float64}, x_ref::Array{Float64}, u_lo::Matrix{Float64}, u_hi::Matrix{Float64};
+                                            hold::Int = 1, n_sample = nothing, N_sample::Int = 1, w::Union{Nothing,Array{Float64}} = nothing,
+                                            w_hold::Int = 1, terrain::Union{Nothing,Vector{Terrain}} = nothing,
+                                            steps::Int = size(u, ndims(u)) * N_sample, steps_per_launch::Int = 0, grad_reg = nothing,
+                                            grad_cols = nothing)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    B = size(q1, 2)
+    (size(u_lo) == size(u_hi) && size(u_lo, 1) == nu && size(u_lo, 2) in (1, B)) || error("plant_rollout_tape_feedback_limits: u_lo, u_hi must be $nu x 1 or $nu x $B")
+    ua, ws, μs, Ks, xs, ns = _closed_loop_inputs("plant_rollout_tape_feedback_limits", model, q1, v1, u, μ, w, terrain, steps, N_sample, w_hold, K, x_ref, hold, n_sample)
+    q0 = q1 .- h_sim .* v1
+    q = zeros(nq, B, steps + 2); γ = zeros(nc, B, steps); b = zeros(nf * nc, B, steps)
+    status = zeros(Cint, B, steps); iters = zeros(Cint, B, steps); grad_status = zeros(Cint, B, steps); clamped = zeros(Cint, B, steps)
+    u_applied = zeros(nu, B, steps); fb_err = zeros(2 * nq, B, steps)
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    K_u, n_u = size(ua, 3), size(ua, 2)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu = length(μs); n_lim = size(u_lo, 2)
+    nθ = 2 * nq + nu + nw + 2
+    reg = grad_reg === nothing ? o[].kappa_tol * o[].gamma_reg : Float64(grad_reg)
+    n_cols = grad_cols === nothing ? 2 * nq + nu : Int(grad_cols)
+    (2 * nq + nu <= n_cols <= nθ && reg >= 0) || error("plant_rollout_tape_feedback_limits($model): grad_cols must be in $(2 * nq + nu) .. $nθ and grad_reg >= 0")
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    z = C_NULL
+    GC.@preserve Ks xs begin
+        fb = Ref(Feedback(pointer(Ks), pointer(xs), size(Ks, 4), size(Ks, 3), hold, ns))
+        check(@ccall LIB.cimpc_plant_rollout_tape_feedback_limits(id::Cint, B::Cint, steps::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                                                  q0::Ptr{Cdouble}, q1::Ptr{Cdouble}, ua::Ptr{Cdouble}, K_u::Cint, n_u::Cint, N_sample::Cint,
+                                                                  wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint, μs::Ptr{Cdouble}, n_mu::Cint,
+                                                                  h_sim::Cdouble, o::Ref{IpOpts}, q::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble},
+                                                                  status::Ptr{Cint}, iters::Ptr{Cint}, reg::Cdouble, n_cols::Cint, z::Ptr{Cdouble},
+                                                                  grad_status::Ptr{Cint}, handle::Ref{Ptr{Cvoid}}, fb::Ref{Feedback},
+                                                                  u_applied::Ptr{Cdouble}, fb_err::Ptr{Cdouble}, n_lim::Cint, u_lo::Ptr{Cdouble},
+                                                                  u_hi::Ptr{Cdouble}, clamped::Ptr{Cint})::Cint)
+    end
+    return all(status .== 1), q, u_applied, γ, b, status, iters, PlantTape(handle[], model, B, steps, n_cols, grad_status), fb_err, clamped
+end
+
+"""
+    plant_rollout_grad_feedback_limits(model, q1, v1, u, μ, h_sim, opts, K, x_ref, u_lo, u_hi; ...)
+        -> (ok, q, u_applied, γ, b, status, iters, (dz, z, status), fb_err)
+
+`plant_rollout_feedback_limits` with the step gradients of every step (`cimpc_plant_rollout_grad_feedback_limits`; DESIGN.md section 3, item 3i):
+dz nr x grad_cols x B x steps, z nz x B x steps and the gradient status B x steps, as `plant_rollout(...; diff_sol = true)` returns them.  The blocks
+are taken with the applied, limited control in θ: they are those of the open-loop rollout on u_applied and do not see the clamp.  The keywords are
+`plant_rollout_tape_feedback`'s.  Unexecuted, like the rest of this binding.
+"""
+function plant_rollout_grad_feedback_limits(model::Symbol, q1::Matrix{Float64}, v1::Matrix{Float64}, u::Array{Float64}, μ, h_sim, opts,
+                                            K::Array{Float64}, x_ref::Array{Float64}, u_lo::Matrix{Float64}, u_hi::Matrix{Float64};
+                                            hold::Int = 1, n_sample = nothing, N_sample::Int = 1, w::Union{Nothing,Array{Float64}} = nothing,
+                                            w_hold::Int = 1, terrain::Union{Nothing,Vector{Terrain}} = nothing,
+                                            steps::Int = size(u, ndims(u)) * N_sample, steps_per_launch::Int = 0, grad_reg = nothing,
+                                            grad_cols = nothing)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    B = size(q1, 2)
+    (size(u_lo) == size(u_hi) && size(u_lo, 1) == nu && size(u_lo, 2) in (1, B)) || error("plant_rollout_grad_feedback_limits: u_lo, u_hi must be $nu x 1 or $nu x $B")
+    ua, ws, μs, Ks, xs, ns = _closed_loop_inputs("plant_rollout_grad_feedback_limits", model, q1, v1, u, μ, w, terrain, steps, N_sample, w_hold, K, x_ref, hold, n_sample)
+    q0 = q1 .- h_sim .* v1
+    q = zeros(nq, B, steps + 2); γ = zeros(nc, B, steps); b = zeros(nf * nc, B, steps)
+    status = zeros(Cint, B, steps); iters = zeros(Cint, B, steps); grad_status = zeros(Cint, B, steps)
+    u_applied = zeros(nu, B, steps); fb_err = zeros(2 * nq, B, steps)
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    K_u, n_u = size(ua, 3), size(ua, 2)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu = length(μs); n_lim = size(u_lo, 2)
+    nb = nf * nc; nr = nq + nc + nb; nz = nq + 4 * nc + 2 * nb; nθ = 2 * nq + nu + nw + 2
+    reg = grad_reg === nothing ? o[].kappa_tol * o[].gamma_reg : Float64(grad_reg)
+    n_cols = grad_cols === nothing ? 2 * nq + nu : Int(grad_cols)
+    (1 <= n_cols <= nθ && reg >= 0) || error("plant_rollout_grad_feedback_limits($model): grad_cols must be in 1 .. $nθ and grad_reg >= 0")
+    z = zeros(nz, B, steps); dz = zeros(nr, n_cols, B, steps)
+    GC.@preserve Ks xs begin
+        fb = Ref(Feedback(pointer(Ks), pointer(xs), size(Ks, 4), size(Ks, 3), hold, ns))
+        check(@ccall LIB.cimpc_plant_rollout_grad_feedback_limits(id::Cint, B::Cint, steps::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                                                  q0::Ptr{Cdouble}, q1::Ptr{Cdouble}, ua::Ptr{Cdouble}, K_u::Cint, n_u::Cint, N_sample::Cint,
+                                                                  wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint, μs::Ptr{Cdouble}, n_mu::Cint,
+                                                                  h_sim::Cdouble, o::Ref{IpOpts}, q::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble},
+                                                                  status::Ptr{Cint}, iters::Ptr{Cint}, reg::Cdouble, n_cols::Cint, z::Ptr{Cdouble},
+                                                                  dz::Ptr{Cdouble}, grad_status::Ptr{Cint}, fb::Ref{Feedback},
+                                                                  u_applied::Ptr{Cdouble}, fb_err::Ptr{Cdouble}, n_lim::Cint, u_lo::Ptr{Cdouble},
+                                                                  u_hi::Ptr{Cdouble})::Cint)
+    end
+    return all(status .== 1), q, u_applied, γ, b, status, iters, (dz = dz, z = z, status = grad_status), fb_err
+end
+
+"""
     plant_tape_vjp_feedback(tape; gq = nothing, ggamma = nothing, gb = nothing) -> (g_q0, g_q1, g_u_step, g_w_step, g_μ, g_h, n_cut, g_xref_step)
 
 `plant_tape_vjp` on the tape of a closed-loop rollout, with g_xref_step 2nq x B x T, the gradient with respect to the reference state
