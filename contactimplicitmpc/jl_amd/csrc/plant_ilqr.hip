@@ -10,6 +10,9 @@
 //                               gamma, b, status, iters, lin_q, lin_r), elsewhere they stay; row 0's workgroup updates level, active, J,
 //                               writes the history row and counts the robot into n_active[iteration] if it is still active
 //
+// plant_ilqr_iteration (plant_stage_launch.h) is that body on device pointers; the entry here calls it once per iteration, and so does the
+// receding-horizon policy (plant_mpc.hip), whose handle keeps the arrays between control steps.
+//
 // The weights, goals, limits, w, mu, the terrains (with the per-candidate copy) and the alphas go up once.  Per iteration the host reads
 // ONE int, n_active, and stops at 0 as the Python loop does; everything else comes down once, at the end.  Two tape buffers are
 // allocated once and alternate (iteration 1's parent is the caller's tape, which is only read); the final one is returned, the other freed.
@@ -87,6 +90,32 @@ __global__ __launch_bounds__(ILQR_THREADS) void plant_ilqr_commit_kernel(PlantIl
     for (int i = lane; i < P.nc; i += ILQR_THREADS) P.Ng[at * P.nc + i] = P.Cg[at * P.nc + i];
     for (int i = lane; i < P.nb; i += ILQR_THREADS) P.Nb[at * P.nb + i] = P.Cb[at * P.nb + i];
     if (lane == 0) { P.Nst[at] = P.Cst[at]; P.Nit[at] = P.Cit[at]; }
+}
+
+bool plant_ilqr_iteration(const PlantLsPlan& P, const PlantIlqrArrays& A, int it, const double* parent_dz, const int* parent_status, double* dz,
+                          int* status, PlantWs& W, hipStream_t st) {
+    const PlantModel& M = P.M;
+    const PlantCost& C = A.C;
+    const int B = P.B, T = P.T, nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb(), nr = nq + nc + nb;
+    const unsigned rows = (unsigned)((B + ILQR_THREADS - 1) / ILQR_THREADS);
+    hipLaunchKernelGGL(plant_ilqr_rho_kernel, dim3(rows), dim3(ILQR_THREADS), 0, st, A.ladder, A.level, A.rho_b, B);
+    if (hipGetLastError() != hipSuccess) return false;
+    PlantRiccati R{parent_dz, parent_status, C.Q, C.Qf, C.R, A.Nlq, A.Nlr, A.K, A.k, nullptr, nullptr, A.dV,
+                   A.lq_status, A.n_cut, B, T, nq, nu, nr, P.n_cols, 1, C.n_Q, C.n_R, T, 0.0};
+    R.rho_b = A.rho_b; R.n_rho = B; R.clamped = A.clamped;
+    if (P.limits) { R.u_lo = A.u_lo; R.u_hi = A.u_hi; R.u_nom = A.Nu; R.n_lim = P.n_lim; }
+    if (!plant_riccati_box_launch(R, st)) return false;
+    hipLaunchKernelGGL(plant_ilqr_nominal_kernel, dim3(rows), dim3(ILQR_THREADS), 0, st, A.active, A.J, A.lq_status, A.J_nom, B);
+    if (hipGetLastError() != hipSuccess) return false;
+    const PlantLsArrays S{A.Nq, A.Nu, A.k, A.K, A.w, A.mu, A.dV, A.J_nom, A.alpha, A.u_lo, A.u_hi, C, A.J_cand, A.ok, A.choice, A.conv, A.Cq, A.Cz,
+                          A.Cu, A.Cg, A.Cb, A.Cst, A.Cit, A.Clq, A.Clr, parent_dz, parent_status, dz, status};
+    if (!plant_linesearch_stages(P, S, W, st)) return false;
+    const size_t row = (size_t)it * B;
+    const PlantIlqrCommit Cm{A.choice, A.Cq, A.Cu, A.Cg, A.Cb, A.Clq, A.Clr, A.Cst, A.Cit, A.Nq, A.Nu, A.Ng, A.Nb, A.Nlq, A.Nlr, A.Nst, A.Nit,
+                             A.J_cand, A.alpha, A.ladder, A.level, A.active, A.J, A.hist_J + row, A.hist_alpha + row, A.hist_rho + row,
+                             A.hist_accepted + row, A.n_active + it, A.rho_max, A.tol, B, T, nq, nu, nc, nb};
+    hipLaunchKernelGGL(plant_ilqr_commit_kernel, dim3((unsigned)((T + 2) * B)), dim3(ILQR_THREADS), 0, st, Cm);
+    return hipGetLastError() == hipSuccess;
 }
 
 namespace {
@@ -199,39 +228,15 @@ extern "C" int cimpc_plant_ilqr(cimpc_plant_tape tape, int steps_per_launch, int
         ok_ = ok_ && hipMemsetAsync(N + j_lev, 0, nB * sizeof(int), st) == hipSuccess && hipMemsetAsync(N + j_nact, 0, (size_t)max_iter * sizeof(int), st) == hipSuccess;
         ok_ = ok_ && plant_linesearch_shared(P, w, terrain, ter, W, st);
         C.Q = F + i_Q; C.Qf = F + i_Qf; C.R = F + i_R; C.x_goal = F + i_xg; C.u_goal = F + i_ug;
-        const unsigned rows = (unsigned)((B + ILQR_THREADS - 1) / ILQR_THREADS);
+        const PlantIlqrArrays A{F + i_lad, N + j_lev, N + j_act, F + m_J, F + r_rho, F + r_Jn, F + m_q, F + m_u, F + m_g, F + m_b, F + m_lq, F + m_lr,
+                                N + j_st, N + j_it, F + g_K, F + g_k, F + g_dV, N + j_lqs, N + j_cut, N + j_cl, limits ? F + i_lo : nullptr,
+                                limits ? F + i_hi : nullptr, F + i_al, w_each ? F + i_w : nullptr, mu_each ? F + i_mu : nullptr, C, F + o_J, N + j_ok,
+                                N + j_ch, N + j_conv, F + o_q, F + o_z, F + o_u, F + o_g, F + o_b, N + j_cst, N + j_cit, F + o_lq, F + o_lr,
+                                F + h_J, F + h_al, F + h_rho, N + j_hacc, N + j_nact, rho_max, tol};
         for (int it = 0; it < max_iter && ok_; ++it) {
             const PlantTapeBuffers& parent = it == 0 ? caller : bufs[(it - 1) & 1];
             PlantTapeBuffers& fresh = bufs[it & 1];
-            hipLaunchKernelGGL(plant_ilqr_rho_kernel, dim3(rows), dim3(ILQR_THREADS), 0, st, F + i_lad, N + j_lev, F + r_rho, B);
-            ok_ = hipGetLastError() == hipSuccess;
-            if (ok_) {
-                PlantRiccati R{parent.d_dz, parent.d_status, F + i_Q, F + i_Qf, F + i_R, F + m_lq, F + m_lr, F + g_K, F + g_k, nullptr, nullptr, F + g_dV,
-                               N + j_lqs, N + j_cut, B, T, nq, nu, nr, n_cols, 1, C.n_Q, C.n_R, T, 0.0};
-                R.rho_b = F + r_rho; R.n_rho = B; R.clamped = N + j_cl;
-                if (limits) { R.u_lo = F + i_lo; R.u_hi = F + i_hi; R.u_nom = F + m_u; R.n_lim = n_lim; }
-                ok_ = plant_riccati_box_launch(R, st);
-            }
-            if (ok_) {
-                hipLaunchKernelGGL(plant_ilqr_nominal_kernel, dim3(rows), dim3(ILQR_THREADS), 0, st, N + j_act, F + m_J, N + j_lqs, F + r_Jn, B);
-                ok_ = hipGetLastError() == hipSuccess;
-            }
-            if (ok_) {
-                const PlantLsArrays A{F + m_q, F + m_u, F + g_k, F + g_K, w_each ? F + i_w : nullptr, mu_each ? F + i_mu : nullptr, F + g_dV, F + r_Jn, F + i_al,
-                                      limits ? F + i_lo : nullptr, limits ? F + i_hi : nullptr, C, F + o_J, N + j_ok, N + j_ch, N + j_conv, F + o_q, F + o_z,
-                                      F + o_u, F + o_g, F + o_b, N + j_cst, N + j_cit, F + o_lq, F + o_lr, parent.d_dz, parent.d_status, fresh.d_dz,
-                                      fresh.d_status};
-                ok_ = plant_linesearch_stages(P, A, W, st);
-            }
-            if (ok_) {
-                const size_t row = (size_t)it * B;
-                const PlantIlqrCommit Cm{N + j_ch, F + o_q, F + o_u, F + o_g, F + o_b, F + o_lq, F + o_lr, N + j_cst, N + j_cit,
-                                         F + m_q, F + m_u, F + m_g, F + m_b, F + m_lq, F + m_lr, N + j_st, N + j_it, F + o_J, F + i_al, F + i_lad,
-                                         N + j_lev, N + j_act, F + m_J, F + h_J + row, F + h_al + row, F + h_rho + row, N + j_hacc + row, N + j_nact + it,
-                                         rho_max, tol, B, T, nq, nu, nc, nb};
-                hipLaunchKernelGGL(plant_ilqr_commit_kernel, dim3((unsigned)((T + 2) * B)), dim3(ILQR_THREADS), 0, st, Cm);
-                ok_ = hipGetLastError() == hipSuccess;
-            }
+            ok_ = plant_ilqr_iteration(P, A, it, parent.d_dz, parent.d_status, fresh.d_dz, fresh.d_status, W, st);
             int n_active = 0;      // the iteration's one read
             down(&n_active, N + j_nact + it, (size_t)1);
             ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;

@@ -40,16 +40,6 @@
 
 namespace cimpc {
 
-constexpr int LS_THREADS = 64;
-constexpr int LS_MAX_WORK = (int)plant_cost_work_doubles(PLANT_MAX_Q, PLANT_MAX_U);
-
-// the wavefront as the team of plant_cost.h
-struct PlantCostWave {
-    __device__ int rank() const { return threadIdx.x; }
-    __device__ int size() const { return LS_THREADS; }
-    __device__ void sync() const { __syncthreads(); }
-};
-
 // Entry e = t NB + r of the candidates' inputs, r = c B + b, from the parent's rows of robot b (all device memory): the open-loop row, the
 // gain block, the x_ref row; at t = 0 also trajectory rows 0 and 1, mu (given per robot) and the w schedule (given per robot).
 struct PlantLsExpand {

@@ -24,6 +24,16 @@
 
 namespace cimpc {
 
+constexpr int LS_THREADS = 64;
+constexpr int LS_MAX_WORK = (int)plant_cost_work_doubles(PLANT_MAX_Q, PLANT_MAX_U);
+
+// the wavefront as the team of plant_cost.h: the line search's kernels (plant_linesearch.hip) and the policy's nominal kernel (plant_mpc.hip)
+struct PlantCostWave {
+    __device__ int rank() const { return threadIdx.x; }
+    __device__ int size() const { return LS_THREADS; }
+    __device__ void sync() const { __syncthreads(); }
+};
+
 // The host arguments a line search is planned from (the names of cimpc_plant_tape_linesearch_box).  q .. grad_status are the caller's
 // output arrays: only that they are given is looked at.
 struct PlantLsCall {
@@ -82,6 +92,36 @@ std::vector<cimpc_terrain> plant_linesearch_terrains(const PlantLsPlan& P, const
 bool plant_linesearch_shared(const PlantLsPlan& P, const double* w, const cimpc_terrain* terrain, const std::vector<cimpc_terrain>& ter, PlantWs& W,
                              hipStream_t st);
 bool plant_linesearch_stages(const PlantLsPlan& P, const PlantLsArrays& A, PlantWs& W, hipStream_t st);
+
+// One iteration of the device-resident iLQR loop (plant_ilqr.hip), all device memory: the rules' state
+// (ladder, level, active, J; plant_ilqr.h) and rows (rho_b, J_nom), the nominal (N*), the backward pass's outputs, the limits (null: none),
+// alpha, w and mu where they are per robot (else null), C with device pointers, the line search's outputs (PlantLsArrays' names), and the
+// history: max_iter rows of B and max_iter words of n_active, of which iteration `it` writes its own.
+struct PlantIlqrArrays {
+    const double* ladder;
+    int *level, *active;
+    double *J, *rho_b, *J_nom;
+    double *Nq, *Nu, *Ng, *Nb, *Nlq, *Nlr;
+    int *Nst, *Nit;
+    double *K, *k, *dV;
+    int *lq_status, *n_cut, *clamped;
+    const double *u_lo, *u_hi;
+    const double *alpha, *w, *mu;
+    PlantCost C;
+    double* J_cand;
+    int *ok, *choice, *conv;
+    double *Cq, *Cz, *Cu, *Cg, *Cb;
+    int *Cst, *Cit;
+    double *Clq, *Clr;
+    double *hist_J, *hist_alpha, *hist_rho;
+    int *hist_accepted, *n_active;
+    double rho_max, tol;
+};
+
+// The body of the loop on `st`, nothing copied or synchronized: the rho kernel, plant_riccati_box_launch about the parent tape's blocks, the
+// nominal-cost kernel, plant_linesearch_stages into the fresh blocks, the commit kernel.  cimpc_plant_ilqr and cimpc_plant_mpc_control call it.
+bool plant_ilqr_iteration(const PlantLsPlan& P, const PlantIlqrArrays& A, int it, const double* parent_dz, const int* parent_status, double* dz,
+                          int* status, PlantWs& W, hipStream_t st);
 
 // L with every pointer on the device, q and r given; sets the kernel's dynamic LDS (plant_riccati_box_lds) and launches B workgroups.
 bool plant_riccati_box_launch(const PlantRiccati& L, hipStream_t st);

@@ -14,6 +14,8 @@
 //                   many robots (K in d_fb); its B-robot inputs and outputs in buffers of its own   (plant_linesearch.hip)
 //   iLQR loop       the same candidates' rollout, iteration after iteration; the nominal, the gains, the rules' rows, the line search's outputs
 //                   and the history in two buffers of its own   (plant_ilqr.hip)
+//   MPC policy      the same candidates' rollout at every control step; everything else - the problem, the plan, its nominal, three tape
+//                   buffers - belongs to the cimpc_plant_mpc handle, which copies its terrains into d_ter at every step   (plant_mpc.hip)
 //                   A tape's dz and status are NOT here: they belong to the tape (plant_adjoint.hip) and live as long as it does
 // The prologue the entry points share past their validation (plant_model_and_ground, plant_model.h; plant_rollout_check,
 // plant_rollout_call.h: no device needed) is stated here once: which device a call runs on (plant_current_device), and its workspace

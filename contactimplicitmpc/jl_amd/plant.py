@@ -30,6 +30,9 @@ exactly 0.0 where clamped, and `rollout(diff_sol=True)`, `rollout_tape`, `vjp`, 
 (`cimpc_plant_rollout_grad_feedback_limits`, `cimpc_plant_rollout_tape_feedback_limits`); `clamped_controls` restates the mask on the host.
 `ilqr(device_loop=True)` and `ilqr_from_tape` run every iteration of that loop in one library call, on arrays that stay on the device
 (`cimpc_plant_ilqr`); tests/test_gpu_plant_ilqr.py holds them to the host loop bit for bit.
+`ILQRPolicy` is that loop as a receding-horizon controller (`cimpc_plant_mpc`): the problem, a `TrackingReference`,
+and the plan stay on the device between control steps, `control(q1, v1)` re-plans from the measured state and returns the control to apply;
+tests/test_gpu_plant_mpc.py holds every control step to `ilqr(device_loop=True)` on the step's goal window bit for bit.
 Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble
 solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain, tests/test_gpu_plant_tangent.py against restatements of the forward chain,
 tests/test_gpu_plant_riccati.py against restatements of the backward pass, tests/test_gpu_plant_linesearch.py the line search against the
@@ -1404,6 +1407,234 @@ def ilqr_from_tape(tape: RolloutTape, q, u_applied, gamma, b, status, iters, cos
     gains = TapeGains(K=np.ascontiguousarray(Kb.transpose(0, 1, 3, 2)), k=k, P0=None, p0=None, dV=dV, status=lqs, n_cut=n_cut, K_blocks=Kb, clamped=clamped)
     return ILQRResult(u=ou, q=oq, gamma=og, b=ob, J=hJ[:n_it].copy(), alpha=hal[:n_it].copy(), rho=hrho[:n_it].copy(), accepted=hacc[:n_it].astype(bool),
                       J0=J0, tape=final, gains=gains)
+
+
+class TrackingReference:
+    """The reference a receding-horizon policy tracks (csrc/plant_mpc.h): weights as `TrackingCost` takes them
+    for a horizon of H stages - Q (n, n) or (H, n, n), R (m, m) or (H, m, m), Qf -, indexed by stage and never shifted, and L stages of goals,
+    x_ref (L + 1, n) or (L + 1, B, n) and u_ref (L, m) or (L, B, m) (defaults: zeros, with L = 1 when neither is given).  `window(s, H)` is the
+    `TrackingCost` of control step s: x goal row min(s + t, L) at stage t = 0 .. H and u goal row min(s + t, L - 1) at t < H - the last goal
+    is held."""
+
+    def __init__(self, Q, R, Qf=None, x_ref=None, u_ref=None):
+        self.Q, self.R = np.asarray(Q, dtype=np.float64), np.asarray(R, dtype=np.float64)
+        if self.Q.ndim not in (2, 3) or self.R.ndim not in (2, 3) or self.Q.shape[-1] != self.Q.shape[-2] or self.R.shape[-1] != self.R.shape[-2]:
+            raise ValueError("Q must be (n, n) or (H, n, n) and R (m, m) or (H, m, m)")
+        self.Qf = None if Qf is None else np.asarray(Qf, dtype=np.float64)
+        n, m = self.Q.shape[-1], self.R.shape[-1]
+        xr = None if x_ref is None else np.asarray(x_ref, dtype=np.float64)
+        ur = None if u_ref is None else np.asarray(u_ref, dtype=np.float64)
+        if xr is not None and (xr.ndim not in (2, 3) or xr.shape[0] < 2 or xr.shape[-1] != n):
+            raise ValueError(f"x_ref must be (L + 1, {n}) or (L + 1, B, {n}) with L at least 1, got {xr.shape}")
+        if ur is not None and (ur.ndim not in (2, 3) or ur.shape[0] < 1 or ur.shape[-1] != m):
+            raise ValueError(f"u_ref must be (L, {m}) or (L, B, {m}) with L at least 1, got {ur.shape}")
+        L = xr.shape[0] - 1 if xr is not None else ur.shape[0] if ur is not None else 1
+        if ur is not None and ur.shape[0] != L:
+            raise ValueError(f"x_ref has {L + 1} rows, so u_ref must have {L}, got {ur.shape[0]}")
+        self.L = int(L)
+        self.x_ref = np.zeros((L + 1, n)) if xr is None else xr
+        self.u_ref = np.zeros((L, m)) if ur is None else ur
+
+    def rows(self, s: int, H: int):
+        """(x rows (H + 1,), u rows (H,)) of the goal window of control step s: the index rule of csrc/plant_mpc.h on the host."""
+        s, H = int(s), int(H)
+        if s < 0 or H < 1:
+            raise ValueError("s must not be negative and H at least 1")
+        return np.minimum(s + np.arange(H + 1), self.L), np.minimum(s + np.arange(H), self.L - 1)
+
+    def window(self, s: int, H: int) -> "TrackingCost":
+        xi, ui = self.rows(s, H)
+        return TrackingCost(self.Q, self.R, self.Qf, x_goal=self.x_ref[xi], u_goal=self.u_ref[ui])
+
+    def _arrays(self, B: int):
+        """(x_ref (L + 1, n_x, n), u_ref (L, n_x, m)) for B robots, n_x 1 or B: one of them per robot spreads the other, as `TrackingCost` does."""
+        out = []
+        for a, what in ((self.x_ref, "x_ref"), (self.u_ref, "u_ref")):
+            a = a[:, None, :] if a.ndim == 2 else a
+            if a.shape[1] not in (1, B):
+                raise ValueError(f"TrackingReference: {what} has {a.shape[1]} robots, the policy {B}")
+            out.append(a)
+        if out[0].shape[1] != out[1].shape[1]:
+            out = [np.broadcast_to(a, (a.shape[0], B, a.shape[2])) for a in out]
+        return tuple(np.ascontiguousarray(a) for a in out)
+
+
+@dataclasses.dataclass
+class ILQRPolicyStep:
+    """The diagnostics of one control step of an `ILQRPolicy`: the step s and the shift it was made with; J0 (B,) the warm start's cost; per
+    iteration run J, alpha (NaN where rejected), rho, accepted (n_done, B), as `ILQRResult` has them; converged (B,): every step of the final
+    nominal converged."""
+    s: int
+    shift: int
+    J0: np.ndarray
+    J: np.ndarray
+    alpha: np.ndarray
+    rho: np.ndarray
+    accepted: np.ndarray
+    n_done: int
+    converged: np.ndarray
+
+
+class ILQRPolicy:
+    """Receding-horizon iLQR through contact for B robots, with the plan and the problem resident on the device (`cimpc_plant_mpc`; DESIGN.md
+    section 3, item 3j).  ref: a `TrackingReference`; u0 (H, nu) or (H, B, nu): the first plan, clipped into the limits where there are any;
+    mu, terrain, opts, grad_reg, grad_cols, u_lo, u_hi, alphas, rho0 .. armijo as `ilqr` takes them, n_iter its max_iter.  The planning model
+    takes no disturbance.  `control(q1, v1, shift=None) -> u (B, nu)` is one control step: bit for bit
+    `ilqr(model, q1, v1, u_warm, h, mu, ref.window(s, H), max_iter=n_iter, ..., device_loop=True).u[0]` with
+    u_warm[t] = plan[min(t + shift, H - 1)], after which the result's u is the plan and s has advanced by shift; shift defaults to 0 on the
+    first call after construction or `reset` and to 1 afterwards.  `last` holds the step's `ILQRPolicyStep`, `plan()` returns the current
+    (u, q, gamma, b, status, iters).  As a policy of `simulate`: `start(q0)` stores the configuration before the first one, `policy(q)` is
+    `control(q, (q - previous) / h)`.  A context manager; `close()` frees the device memory."""
+
+    def __init__(self, model: str, B: int, H: int, h: float, mu, ref: TrackingReference, u0, *, n_iter: int = 1, alphas=(1.0, 0.5, 0.25, 0.125),
+                 rho0: float = 1e-6, rho_factor: float = 10.0, rho_max: float = 1e6, tol: float = 1e-6, armijo: float = 1e-4,
+                 opts: InteriorPointOptions = SIM_OPTS, terrain=None, steps_per_launch: int = 0, grad_reg=None, grad_cols=None, u_lo=None, u_hi=None):
+        self._handle = None
+        mid, nq, nu, nc, fd, nw = model_dims(model)
+        B, H = int(B), int(H)
+        if B < 1 or H < 1:
+            raise ValueError("B and H must be at least 1")
+        if not isinstance(ref, TrackingReference):
+            raise ValueError("ref must be a TrackingReference")
+        if not float(h) > 0.0:
+            raise ValueError("h must be positive")
+        alphas, n_iter, ladder = _ilqr_loop_args(alphas, n_iter, rho0, rho_factor, rho_max, tol, armijo)
+        reg, n_cols = _grad_args(model, opts, grad_reg, grad_cols)
+        if n_cols < 2 * nq + nu:
+            raise ValueError(f"grad_cols must be at least {2 * nq + nu} (q0, q1 and u1)")
+        lo, hi = _limit_arrays(u_lo, u_hi, B, nu)
+        xr, ur = ref._arrays(B)
+        cc, keep = ref.window(0, H)._struct(nq, nu, B, H)
+        mua = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
+        if mua.size not in (1, B):
+            raise ValueError(f"mu: one friction coefficient or one per robot ({B}), got {mua.size}")
+        if terrain is None and model in TERRAIN_MODELS:
+            terrain = "flat_2D_lc"
+        self.model, self.B, self.H, self.h, self.ref = model, B, H, float(h), ref
+        self._dims, self._lo, self._hi, self.n_iter = (nq, nu, nc, fd * nc), lo, hi, n_iter
+        u0 = self._plan_rows(u0)
+        ta, nt = (None, 0) if terrain is None else _terrain_array(terrain, B)
+        o = _lib.IpOpts(**dataclasses.asdict(opts))
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        Qc, Rc, Qfc = keep[:3]
+        handle = C.c_void_p()
+        lib = _lib.load()
+        rc = lib.cimpc_plant_mpc_create(mid, B, H, int(steps_per_launch), nt, ta, dp(mua), mua.size, float(h), C.byref(o), dp(Qc), dp(Qfc), dp(Rc), cc.n_Q,
+                                        cc.n_R, ref.L, xr.shape[1], dp(xr), dp(ur), alphas.size, dp(alphas), float(armijo), reg, n_cols, ladder.size,
+                                        dp(ladder), float(rho_max), float(tol), n_iter, 1 if lo is None else lo.shape[0], dp(lo), dp(hi), dp(u0),
+                                        C.byref(handle))
+        if rc == -1:
+            raise ValueError(lib.cimpc_last_error(None).decode())
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_mpc_create failed ({rc})")
+        self._handle, self._lib = handle, lib
+        self.s, self._fresh, self._prev, self.last = 0, True, None, None
+
+    def _plan_rows(self, u0):
+        """u0 (H, nu) or (H, B, nu) -> (H, B, nu), contiguous, clipped into the limits as `ilqr` clips its initial controls."""
+        nu = self._dims[1]
+        u = np.asarray(u0, dtype=np.float64)
+        if u.ndim == 2:
+            u = u[:, None, :]
+        if u.ndim != 3 or u.shape[0] != self.H or u.shape[1] not in (1, self.B) or u.shape[2] != nu:
+            raise ValueError(f"u0 must be ({self.H}, {nu}) or ({self.H}, {self.B}, {nu}), got {np.shape(u0)}")
+        if not np.isfinite(u).all():
+            raise ValueError("u0 must be finite")
+        u = np.broadcast_to(u, (self.H, self.B, nu))
+        if self._lo is not None:
+            u = np.where(u < self._lo, self._lo, np.where(u > self._hi, self._hi, u))
+        return np.ascontiguousarray(u, dtype=np.float64)
+
+    def _open(self):
+        if self._handle is None:
+            raise ValueError("the policy is closed")
+        return self._handle
+
+    def control(self, q1, v1, shift=None):
+        handle = self._open()
+        nq, nu = self._dims[:2]
+        q1, v1 = np.atleast_2d(np.asarray(q1, dtype=np.float64)), np.atleast_2d(np.asarray(v1, dtype=np.float64))
+        if q1.shape != (self.B, nq) or v1.shape != (self.B, nq):
+            raise ValueError(f"q1 and v1 must be ({self.B}, {nq}), got {q1.shape} and {v1.shape}")
+        shift = (0 if self._fresh else 1) if shift is None else int(shift)
+        if shift < 0:
+            raise ValueError("shift must not be negative")
+        if not (np.isfinite(q1).all() and np.isfinite(v1).all()):
+            raise ValueError("q1 and v1 must be finite")
+        s = self.s + shift
+        q0 = np.ascontiguousarray(q1 - self.h * v1); q1 = np.ascontiguousarray(q1)
+        B, n_iter = self.B, self.n_iter
+        u, J0, conv = np.zeros((B, nu)), np.zeros(B), np.zeros(B, dtype=np.int32)
+        hJ, hal, hrho, hacc = np.zeros((n_iter, B)), np.zeros((n_iter, B)), np.zeros((n_iter, B)), np.zeros((n_iter, B), dtype=np.int32)
+        n_done = C.c_int(0)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        rc = self._lib.cimpc_plant_mpc_control(handle, s, shift, dp(q0), dp(q1), dp(u), dp(J0), dp(hJ), dp(hal), dp(hrho), ip(hacc), C.byref(n_done), ip(conv))
+        if rc == -1:
+            raise ValueError(self._lib.cimpc_last_error(None).decode())
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_mpc_control failed ({rc})")
+        k = n_done.value
+        self.s, self._fresh = s, False
+        self.last = ILQRPolicyStep(s=s, shift=shift, J0=J0, J=hJ[:k].copy(), alpha=hal[:k].copy(), rho=hrho[:k].copy(), accepted=hacc[:k].astype(bool),
+                                   n_done=k, converged=conv.astype(bool))
+        return u
+
+    def plan(self):
+        handle = self._open()
+        nq, nu, nc, nb = self._dims
+        H, B = self.H, self.B
+        u, q, g, b = np.zeros((H, B, nu)), np.zeros((H + 2, B, nq)), np.zeros((H, B, nc)), np.zeros((H, B, nb))
+        st, it = np.zeros((H, B), dtype=np.int32), np.zeros((H, B), dtype=np.int32)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        rc = self._lib.cimpc_plant_mpc_plan(handle, dp(u), dp(q), dp(g), dp(b), ip(st), ip(it))
+        if rc == -1:
+            raise ValueError(self._lib.cimpc_last_error(None).decode())
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_mpc_plan failed ({rc})")
+        return u, q, g, b, st, it
+
+    def reset(self, u0=None, s: int = 0):
+        handle = self._open()
+        if int(s) < 0:
+            raise ValueError("s must not be negative")
+        if u0 is not None:
+            u = self._plan_rows(u0)
+            rc = self._lib.cimpc_plant_mpc_reset(handle, u.ctypes.data_as(C.POINTER(C.c_double)))
+            if rc == -1:
+                raise ValueError(self._lib.cimpc_last_error(None).decode())
+            if rc != 0:
+                raise _lib.CimpcError(f"cimpc_plant_mpc_reset failed ({rc})")
+        self.s, self._fresh, self._prev = int(s), True, None
+
+    def start(self, q0):
+        self._prev = np.atleast_2d(np.asarray(q0, dtype=np.float64)).copy()
+
+    def __call__(self, q):
+        q = np.atleast_2d(np.asarray(q, dtype=np.float64))
+        if self._prev is None:
+            raise ValueError("start(q0) must be called with the configuration before the first one")
+        u = self.control(q, (q - self._prev) / self.h)
+        self._prev = q.copy()
+        return u
+
+    def close(self):
+        if self._handle is not None:
+            handle, self._handle = self._handle, None
+            self._lib.cimpc_plant_mpc_destroy(handle)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, feedback=None, **kw):

@@ -809,6 +809,45 @@ int cimpc_plant_ilqr(cimpc_plant_tape tape, int steps_per_launch, int n_terrain,
                      int* grad_status, double* hist_J, double* hist_alpha, double* hist_rho, int* hist_accepted, int* n_iter,
                      double* K, double* k, double* dV, int* lq_status, int* n_cut, int* clamped, cimpc_plant_tape* new_tape);
 
+/* ---- the receding-horizon iLQR policy (csrc/plant_mpc.h) --------------------------------------------------
+ * A cimpc_plant_mpc keeps the problem and the plan of B robots on ONE device between control steps: the weights Q (n_Q x (n x n)), Qf,
+ * R (n_R x (m x m)) as cimpc_tracking_cost takes them for T = H; the reference x_ref (L + 1) x n_x x n and u_ref L x n_x x m, n_x 1 or B;
+ * the limits (n_lim, u_lo, u_hi; both NULL: none), mu (n_mu 1 or B), the terrains, h, opts, alpha, armijo, reg, n_cols, the ladder,
+ * rho_max, tol and n_iter as cimpc_plant_ilqr takes them (n_iter is its max_iter); the plan u (H x B x m) with the nominal it was rolled
+ * out to; the gains and the rules' arrays of the loop; and three tape buffers, allocated once.  The planning model takes no disturbance.
+ *
+ * Control step s over the horizon H reads x goal row min(s + t, L) at stage t = 0 .. H and u goal row min(s + t, L - 1) at t < H (the last
+ * goal is held; the weights are indexed by stage and not shifted), starts from u_warm[t] = u_plan[min(t + shift, H - 1)], q[0] = q0,
+ * q[1] = q1, every robot at level 0 and active, and is then BIT FOR BIT cimpc_plant_rollout_tape on u_warm, cimpc_plant_tracking_cost on
+ * it and cimpc_plant_ilqr with max_iter = n_iter on that goal window: the final nominal's controls are the new plan and its row 0 is u.
+ *
+ * cimpc_plant_mpc_create: everything goes up once; u0 (H x B x m, finite, inside the limits where there are any) is loaded as the plan.
+ * cimpc_plant_mpc_control: up 2 B nq doubles; down u (B x m), J0 (B, the warm start's cost), the first *n_done rows of hist_J, hist_alpha
+ *   (NaN where rejected), hist_rho, hist_accepted (n_iter x B each), converged (B: every step of the final nominal converged), and one int
+ *   per iteration; no allocation once the shared workspace has its size.
+ * cimpc_plant_mpc_plan: the current plan u (H x B x m) and its nominal q ((H + 2) x B x nq), gamma, b, status, iters (as cimpc_plant_rollout
+ *   lays them out) - each may be NULL; before the first control step only u is meaningful.
+ * cimpc_plant_mpc_reset: loads a new plan u0.  cimpc_plant_mpc_dims: each pointer may be NULL.  cimpc_plant_mpc_destroy: NULL is fine.
+ * Refused with CIMPC_ERR_INVALID before any device is touched, the reason left for cimpc_last_error(NULL) and the handle as it was (after
+ * a refused create *handle is NULL): a null pointer (terrain and the limits excepted); H or L below 1; n_iter below 1; shift or s
+ * negative; a shift with no plan loaded; a non-finite entry of q0, q1 or u0; an entry of u0 outside the limits; what cimpc_plant_ilqr
+ * refuses of the arguments they share.  After a HIP error a handle refuses further use, naming that. */
+typedef struct cimpc_plant_mpc_s* cimpc_plant_mpc;
+int cimpc_plant_mpc_create(int model, int B, int H, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                           const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                           const double* Q, const double* Qf, const double* R, int n_Q, int n_R,
+                           int L, int n_x, const double* x_ref, const double* u_ref,
+                           int n_alpha, const double* alpha, double armijo, double reg, int n_cols,
+                           int n_ladder, const double* ladder, double rho_max, double tol, int n_iter,
+                           int n_lim, const double* u_lo, const double* u_hi, const double* u0, cimpc_plant_mpc* handle);
+int cimpc_plant_mpc_control(cimpc_plant_mpc handle, int s, int shift, const double* q0, const double* q1,
+                            double* u, double* J0, double* hist_J, double* hist_alpha, double* hist_rho, int* hist_accepted,
+                            int* n_done, int* converged);
+int cimpc_plant_mpc_plan(cimpc_plant_mpc handle, double* u, double* q, double* gamma, double* b, int* status, int* iters);
+int cimpc_plant_mpc_reset(cimpc_plant_mpc handle, const double* u0);
+int cimpc_plant_mpc_dims(cimpc_plant_mpc handle, int* model, int* B, int* H, int* L, int* n_iter);
+int cimpc_plant_mpc_destroy(cimpc_plant_mpc handle);
+
 /* ---- cimpc_set_linearization_batch from (z, theta) alone: plant model `model` linearized at kappa (cimpc_plant_linearize's kernel and arguments;
  * z0 = z, th0 = theta) and the tables built from its output, all on the handle's device and stream;
  * nothing but z, theta and the terrains goes up, nothing but N status words comes back.  Equal bit for bit to

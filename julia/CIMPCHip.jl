@@ -1339,6 +1339,151 @@ function plant_ilqr(tape::PlantTape, q::Array{Float64,3}, u_applied::Array{Float
            PlantTape(handle[], tape.model, B, T, tape.n_cols, grad_status)
 end
 
+# ---- the receding-horizon iLQR policy (DESIGN.md section 3, item 3j): a handle with the problem and the plan on the device -------------
+"""
+    PlantMpc
+
+The handle of `cimpc_plant_mpc` with the sizes it was created with.  Unexecuted, like the rest of this binding.
+"""
+mutable struct PlantMpc
+    handle::Ptr{Cvoid}
+    model::Symbol
+    B::Int
+    H::Int
+    L::Int
+    n_iter::Int
+end
+
+"""
+    plant_mpc_create(model, B, H, μ, h_sim, opts, Q, Qf, R, x_ref, u_ref, u0; n_iter = 1, alphas = [1.0, 0.5, 0.25, 0.125], rho0 = 1e-6,
+                     rho_factor = 10.0, rho_max = 1e6, tol = 1e-6, armijo = 1e-4, u_lo = nothing, u_hi = nothing, terrain = nothing,
+                     steps_per_launch = 0, grad_reg = nothing, grad_cols = nothing) -> PlantMpc
+
+`cimpc_plant_mpc_create`: the problem of a receding-horizon iLQR policy goes up once.  Q n x n x n_Q, Qf n x n, R m x m x n_R (column-major
+blocks, n = 2nq, m = nu, n_Q and n_R 1 or H); x_ref n x n_x x (L + 1) and u_ref m x n_x x L with n_x 1 or B; u0 m x B x H, the first plan,
+inside the limits u_lo, u_hi (nu x 1 or nu x B) where there are any.  The ladder rho0 rho_factor^j, j = 0 .. n_iter, is computed here.
+Unexecuted, like the rest of this binding: written against include/cimpc.h and checked against its prototype by text only.
+"""
+function plant_mpc_create(model::Symbol, B::Int, H::Int, μ, h_sim, opts, Q::Array{Float64,3}, Qf::Matrix{Float64}, R::Array{Float64,3},
+                          x_ref::Array{Float64,3}, u_ref::Array{Float64,3}, u0::Array{Float64,3}; n_iter::Int = 1,
+                          alphas::Vector{Float64} = [1.0, 0.5, 0.25, 0.125], rho0::Real = 1e-6, rho_factor::Real = 10.0, rho_max::Real = 1e6,
+                          tol::Real = 1e-6, armijo::Real = 1e-4, u_lo::Union{Nothing,Matrix{Float64}} = nothing,
+                          u_hi::Union{Nothing,Matrix{Float64}} = nothing, terrain::Union{Nothing,Vector{Terrain}} = nothing,
+                          steps_per_launch::Int = 0, grad_reg = nothing, grad_cols = nothing)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    n, m = 2 * nq, nu
+    (B >= 1 && H >= 1 && n_iter >= 1) || error("plant_mpc_create: B, H and n_iter must be at least 1")
+    n_Q, n_R, n_x, L = size(Q, 3), size(R, 3), size(x_ref, 2), size(u_ref, 3)
+    (size(Q) == (n, n, n_Q) && n_Q in (1, H) && size(R) == (m, m, n_R) && n_R in (1, H) && size(Qf) == (n, n)) || error("plant_mpc_create: the weights do not fit the model")
+    (L >= 1 && n_x in (1, B) && size(x_ref) == (n, n_x, L + 1) && size(u_ref) == (m, n_x, L)) || error("plant_mpc_create: x_ref must be $n x n_x x (L + 1) and u_ref $m x n_x x L")
+    size(u0) == (m, B, H) || error("plant_mpc_create: u0 must be $m x $B x $H")
+    n_alpha = length(alphas)
+    (1 <= n_alpha <= 64 && all(isfinite, alphas) && armijo >= 0) || error("plant_mpc_create: 1 to 64 finite alphas, armijo >= 0")
+    ladder = [Float64(rho0) * Float64(rho_factor)^j for j in 0:n_iter]
+    (all(isfinite, ladder) && all(>=(0), ladder)) || error("plant_mpc_create: rho0 rho_factor^j must be finite and not negative")
+    n_ladder = length(ladder)
+    (u_lo === nothing) == (u_hi === nothing) || error("plant_mpc_create: u_lo and u_hi go together")
+    limited = u_lo !== nothing
+    (!limited || (size(u_lo) == size(u_hi) && size(u_lo, 1) == nu && size(u_lo, 2) in (1, B))) || error("plant_mpc_create: u_lo, u_hi must be $nu x 1 or $nu x $B")
+    n_lim = limited ? size(u_lo, 2) : 1
+    lo, hi = limited ? (u_lo, u_hi) : (C_NULL, C_NULL)
+    μs = Float64.(vcat(μ))
+    length(μs) in (1, B) || error("plant_mpc_create: one friction coefficient or one per robot")
+    n_mu = length(μs)
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    reg = grad_reg === nothing ? o[].kappa_tol * o[].gamma_reg : Float64(grad_reg)
+    n_cols = grad_cols === nothing ? 2 * nq + nu : Int(grad_cols)
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    check(@ccall LIB.cimpc_plant_mpc_create(id::Cint, B::Cint, H::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                            μs::Ptr{Cdouble}, n_mu::Cint, h_sim::Cdouble, o::Ref{IpOpts}, Q::Ptr{Cdouble}, Qf::Ptr{Cdouble},
+                                            R::Ptr{Cdouble}, n_Q::Cint, n_R::Cint, L::Cint, n_x::Cint, x_ref::Ptr{Cdouble}, u_ref::Ptr{Cdouble},
+                                            n_alpha::Cint, alphas::Ptr{Cdouble}, armijo::Cdouble, reg::Cdouble, n_cols::Cint, n_ladder::Cint,
+                                            ladder::Ptr{Cdouble}, rho_max::Cdouble, tol::Cdouble, n_iter::Cint, n_lim::Cint, lo::Ptr{Cdouble},
+                                            hi::Ptr{Cdouble}, u0::Ptr{Cdouble}, handle::Ref{Ptr{Cvoid}})::Cint)
+    return PlantMpc(handle[], model, B, H, L, n_iter)
+end
+
+"""
+    plant_mpc_control(p, s, shift, q0, q1) -> (u, J0, J, alpha, rho, accepted, converged)
+
+`cimpc_plant_mpc_control`: one control step of the policy from the measured q0, q1 (nq x B): the plan advanced by `shift`, the goal window
+of step `s`, up to n_iter iterations on the device.  u nu x B is the control to apply; J, alpha, rho, accepted are B x n_done.  Unexecuted,
+like the rest of this binding: written against include/cimpc.h and checked against its prototype by text only.
+"""
+function plant_mpc_control(p::PlantMpc, s::Int, shift::Int, q0::Matrix{Float64}, q1::Matrix{Float64})
+    p.handle != C_NULL || error("plant_mpc_control: the policy is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(p.model)
+    (size(q0) == (nq, p.B) && size(q1) == (nq, p.B)) || error("plant_mpc_control: q0 and q1 must be $nq x $(p.B)")
+    (s >= 0 && shift >= 0) || error("plant_mpc_control: s and shift must not be negative")
+    B, n_iter = p.B, p.n_iter
+    u = zeros(nu, B); J0 = zeros(B); converged = zeros(Cint, B)
+    hJ = zeros(B, n_iter); hal = zeros(B, n_iter); hrho = zeros(B, n_iter); hacc = zeros(Cint, B, n_iter)
+    n_done = Ref{Cint}(0)
+    check(@ccall LIB.cimpc_plant_mpc_control(p.handle::Ptr{Cvoid}, s::Cint, shift::Cint, q0::Ptr{Cdouble}, q1::Ptr{Cdouble}, u::Ptr{Cdouble},
+                                             J0::Ptr{Cdouble}, hJ::Ptr{Cdouble}, hal::Ptr{Cdouble}, hrho::Ptr{Cdouble}, hacc::Ptr{Cint},
+                                             n_done::Ref{Cint}, converged::Ptr{Cint})::Cint)
+    it = 1:Int(n_done[])
+    return u, J0, hJ[:, it], hal[:, it], hrho[:, it], hacc[:, it] .!= 0, converged .!= 0
+end
+
+"""
+    plant_mpc_plan(p) -> (u, q, γ, b, status, iters)
+
+`cimpc_plant_mpc_plan`: the current plan u nu x B x H and its nominal q nq x B x (H + 2), γ, b, status, iters.  Unexecuted, like the rest of
+this binding: written against include/cimpc.h and checked against its prototype by text only.
+"""
+function plant_mpc_plan(p::PlantMpc)
+    p.handle != C_NULL || error("plant_mpc_plan: the policy is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(p.model)
+    B, H = p.B, p.H
+    u = zeros(nu, B, H); q = zeros(nq, B, H + 2); γ = zeros(nc, B, H); b = zeros(nf * nc, B, H)
+    status = zeros(Cint, B, H); iters = zeros(Cint, B, H)
+    check(@ccall LIB.cimpc_plant_mpc_plan(p.handle::Ptr{Cvoid}, u::Ptr{Cdouble}, q::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble},
+                                          status::Ptr{Cint}, iters::Ptr{Cint})::Cint)
+    return u, q, γ, b, status, iters
+end
+
+"""
+    plant_mpc_reset(p, u0)
+
+`cimpc_plant_mpc_reset`: loads a new plan u0 (nu x B x H).  Unexecuted, like the rest of this binding: written against include/cimpc.h and
+checked against its prototype by text only.
+"""
+function plant_mpc_reset(p::PlantMpc, u0::Array{Float64,3})
+    p.handle != C_NULL || error("plant_mpc_reset: the policy is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(p.model)
+    size(u0) == (nu, p.B, p.H) || error("plant_mpc_reset: u0 must be $nu x $(p.B) x $(p.H)")
+    check(@ccall LIB.cimpc_plant_mpc_reset(p.handle::Ptr{Cvoid}, u0::Ptr{Cdouble})::Cint)
+    return p
+end
+
+"""
+    plant_mpc_dims(p) -> (model id, B, H, L, n_iter)
+
+`cimpc_plant_mpc_dims`, as the library holds them.  Unexecuted, like the rest of this binding: written against include/cimpc.h and checked
+against its prototype by text only.
+"""
+function plant_mpc_dims(p::PlantMpc)
+    p.handle != C_NULL || error("plant_mpc_dims: the policy is closed")
+    model = Ref{Cint}(0); B = Ref{Cint}(0); H = Ref{Cint}(0); L = Ref{Cint}(0); n_iter = Ref{Cint}(0)
+    check(@ccall LIB.cimpc_plant_mpc_dims(p.handle::Ptr{Cvoid}, model::Ref{Cint}, B::Ref{Cint}, H::Ref{Cint}, L::Ref{Cint}, n_iter::Ref{Cint})::Cint)
+    return Int(model[]), Int(B[]), Int(H[]), Int(L[]), Int(n_iter[])
+end
+
+"""
+    plant_mpc_destroy(p)
+
+`cimpc_plant_mpc_destroy`: frees the policy's device memory; a second call does nothing.  Unexecuted, like the rest of this binding: written
+against include/cimpc.h and checked against its prototype by text only.
+"""
+function plant_mpc_destroy(p::PlantMpc)
+    p.handle == C_NULL && return nothing
+    h, p.handle = p.handle, C_NULL
+    check(@ccall LIB.cimpc_plant_mpc_destroy(h::Ptr{Cvoid})::Cint)
+    return nothing
+end
+
 # ---- the plant models linearized on the device: the `LinearizedStep` triple of N knots in one call (linearized_step.jl:10-31) --------
 """
     plant_linearize(model, z, θ, κ; terrain = nothing) -> (r0, rz0, rθ0)
