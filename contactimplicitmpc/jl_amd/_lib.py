@@ -149,6 +149,16 @@ SIGNATURES = {
     "cimpc_plant_mpc_reset": (C.c_int, [_h, _dp]),
     "cimpc_plant_mpc_dims": (C.c_int, [_h, _ip, _ip, _ip, _ip, _ip]),
     "cimpc_plant_mpc_destroy": (C.c_int, [_h]),
+    "cimpc_plant_sampler_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, C.c_int, C.c_double, C.POINTER(IpOpts),
+                                             _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_int,
+                                             C.c_ulonglong, C.c_int, _dp, _dp, _dp, C.POINTER(_h)]),
+    "cimpc_plant_sampler_control": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _ip]),
+    "cimpc_plant_sampler_plan": (C.c_int, [_h, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "cimpc_plant_sampler_raw_weights": (C.c_int, [_h, _dp]),
+    "cimpc_plant_sampler_reset": (C.c_int, [_h, _dp]),
+    "cimpc_plant_sampler_dims": (C.c_int, [_h, _ip, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "cimpc_plant_sampler_destroy": (C.c_int, [_h]),
+    "cimpc_plant_sample_noise": (C.c_int, [C.c_ulonglong, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "cimpc_plant_tape_dims": (C.c_int, [_h, _ip, _ip, _ip, _ip]),
     "cimpc_plant_tape_destroy": (C.c_int, [_h]),
     "cimpc_tvlqr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),

@@ -256,6 +256,13 @@ bool plant_linesearch_shared(const PlantLsPlan& P, const double* w, const cimpc_
     return ok_;
 }
 
+bool plant_candidates_cost_launch(const PlantCost& C, const double* q, const double* u_applied, const int* status, double* J, int* conv, int B, int NB,
+                                  hipStream_t st) {
+    const PlantLsCost Pc{C, q, u_applied, status, J, conv, B, NB};
+    hipLaunchKernelGGL(plant_ls_cost_kernel, dim3(NB), dim3(LS_THREADS), 0, st, Pc);
+    return hipGetLastError() == hipSuccess;
+}
+
 bool plant_linesearch_stages(const PlantLsPlan& P, const PlantLsArrays& A, PlantWs& W, hipStream_t st) {
     const PlantModel& M = P.M;
     const PlantRolloutLayout& L = P.L;
@@ -277,9 +284,7 @@ bool plant_linesearch_stages(const PlantLsPlan& P, const PlantLsArrays& A, Plant
                             w_each ? NB : 1, has_w ? P.hold_w : 1, mu_each ? NB : 1, W.d_z, PlantFeedback{d_fk, d_fx, T, NB, 1, 1.0}, d_ua, d_fe,
                             PlantFeedbackLimits{c_lo, c_hi, lim_each ? NB : 1}};
     if (!plant_step_chunks(M, rough, P.opts, NB, T, P.steps_per_launch, R, rough ? W.d_ter : nullptr, P.n_ter, st)) return false;
-    const PlantLsCost Pc{A.C, dq, d_ua, d_st, A.J, A.conv, B, NB};
-    hipLaunchKernelGGL(plant_ls_cost_kernel, dim3(NB), dim3(LS_THREADS), 0, st, Pc);
-    if (hipGetLastError() != hipSuccess) return false;
+    if (!plant_candidates_cost_launch(A.C, dq, d_ua, d_st, A.J, A.conv, B, NB, st)) return false;
     const PlantLsGather G{A.C, dq, W.d_z, d_ua, dg, db, d_st, d_it, A.conv, A.J, A.J_nom, A.dV, A.alpha, P.armijo, P.n_alpha,
                           A.ok, A.choice, A.Cq, A.Cz, A.Cu, A.Cg, A.Cb, A.Cst, A.Cit, A.lin_q, A.lin_r, B, NB, nc, nb, nz};
     hipLaunchKernelGGL(plant_ls_gather_kernel, dim3((T + 2) * B), dim3(LS_THREADS), 0, st, G);

@@ -92,6 +92,11 @@ std::vector<cimpc_terrain> plant_linesearch_terrains(const PlantLsPlan& P, const
 bool plant_linesearch_shared(const PlantLsPlan& P, const double* w, const cimpc_terrain* terrain, const std::vector<cimpc_terrain>& ter, PlantWs& W,
                              hipStream_t st);
 bool plant_linesearch_stages(const PlantLsPlan& P, const PlantLsArrays& A, PlantWs& W, hipStream_t st);
+// plant_ls_cost_kernel on `st`, all device memory: J and conv (every step converged) of the NB = n B candidates (c B + b) of a rollout with
+// trajectory q (T + 2) x NB x nq, applied controls u_applied T x NB x nu and status T x NB; C with device pointers and the rollout's T, nq, nu.
+// The line search calls it, and so does the sampling policy (plant_sample.hip).
+bool plant_candidates_cost_launch(const PlantCost& C, const double* q, const double* u_applied, const int* status, double* J, int* conv, int B, int NB,
+                                  hipStream_t st);
 
 // One iteration of the device-resident iLQR loop (plant_ilqr.hip), all device memory: the rules' state
 // (ladder, level, active, J; plant_ilqr.h) and rows (rho_b, J_nom), the nominal (N*), the backward pass's outputs, the limits (null: none),

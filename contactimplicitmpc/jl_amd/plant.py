@@ -33,6 +33,10 @@ exactly 0.0 where clamped, and `rollout(diff_sol=True)`, `rollout_tape`, `vjp`, 
 `ILQRPolicy` is that loop as a receding-horizon controller (`cimpc_plant_mpc`): the problem, a `TrackingReference`,
 and the plan stay on the device between control steps, `control(q1, v1)` re-plans from the measured state and returns the control to apply;
 tests/test_gpu_plant_mpc.py holds every control step to `ilqr(device_loop=True)` on the step's goal window bit for bit.
+`SamplingPolicy` is the sampling controller beside it (`cimpc_plant_sampler`), with the same surface: per control
+step N perturbed copies of the plan per robot in ONE open-loop rollout of N B robots, `TrackingCost` on each, and the best one (predictive
+sampling) or their softmax mean (MPPI) as the new plan - no tape and no gradient; `sampling_noise` gives the noise's bits on the host;
+tests/test_gpu_plant_sample.py holds every control step to the composition of those pieces bit for bit.
 Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble
 solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain, tests/test_gpu_plant_tangent.py against restatements of the forward chain,
 tests/test_gpu_plant_riccati.py against restatements of the backward pass, tests/test_gpu_plant_linesearch.py the line search against the
@@ -1459,6 +1463,60 @@ class TrackingReference:
         return tuple(np.ascontiguousarray(a) for a in out)
 
 
+class _DevicePolicy:
+    """What the device-resident policies share: the plan's rows as they go up, the open handle, the surface of a policy of `simulate`, and
+    the context manager.  A subclass names its destroy entry in `_DESTROY` and has `control(q1, v1)`."""
+    _DESTROY = None
+
+    def _plan_rows(self, u0):
+        """u0 (H, nu) or (H, B, nu) -> (H, B, nu), contiguous, clipped into the limits as `ilqr` clips its initial controls."""
+        nu = self._dims[1]
+        u = np.asarray(u0, dtype=np.float64)
+        if u.ndim == 2:
+            u = u[:, None, :]
+        if u.ndim != 3 or u.shape[0] != self.H or u.shape[1] not in (1, self.B) or u.shape[2] != nu:
+            raise ValueError(f"u0 must be ({self.H}, {nu}) or ({self.H}, {self.B}, {nu}), got {np.shape(u0)}")
+        if not np.isfinite(u).all():
+            raise ValueError("u0 must be finite")
+        u = np.broadcast_to(u, (self.H, self.B, nu))
+        if self._lo is not None:
+            u = np.where(u < self._lo, self._lo, np.where(u > self._hi, self._hi, u))
+        return np.ascontiguousarray(u, dtype=np.float64)
+
+    def _open(self):
+        if self._handle is None:
+            raise ValueError("the policy is closed")
+        return self._handle
+
+    def start(self, q0):
+        self._prev = np.atleast_2d(np.asarray(q0, dtype=np.float64)).copy()
+
+    def __call__(self, q):
+        q = np.atleast_2d(np.asarray(q, dtype=np.float64))
+        if self._prev is None:
+            raise ValueError("start(q0) must be called with the configuration before the first one")
+        u = self.control(q, (q - self._prev) / self.h)
+        self._prev = q.copy()
+        return u
+
+    def close(self):
+        if self._handle is not None:
+            handle, self._handle = self._handle, None
+            getattr(self._lib, self._DESTROY)(handle)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 @dataclasses.dataclass
 class ILQRPolicyStep:
     """The diagnostics of one control step of an `ILQRPolicy`: the step s and the shift it was made with; J0 (B,) the warm start's cost; per
@@ -1475,7 +1533,7 @@ class ILQRPolicyStep:
     converged: np.ndarray
 
 
-class ILQRPolicy:
+class ILQRPolicy(_DevicePolicy):
     """Receding-horizon iLQR through contact for B robots, with the plan and the problem resident on the device (`cimpc_plant_mpc`; DESIGN.md
     section 3, item 3j).  ref: a `TrackingReference`; u0 (H, nu) or (H, B, nu): the first plan, clipped into the limits where there are any;
     mu, terrain, opts, grad_reg, grad_cols, u_lo, u_hi, alphas, rho0 .. armijo as `ilqr` takes them, n_iter its max_iter.  The planning model
@@ -1485,6 +1543,7 @@ class ILQRPolicy:
     first call after construction or `reset` and to 1 afterwards.  `last` holds the step's `ILQRPolicyStep`, `plan()` returns the current
     (u, q, gamma, b, status, iters).  As a policy of `simulate`: `start(q0)` stores the configuration before the first one, `policy(q)` is
     `control(q, (q - previous) / h)`.  A context manager; `close()` frees the device memory."""
+    _DESTROY = "cimpc_plant_mpc_destroy"
 
     def __init__(self, model: str, B: int, H: int, h: float, mu, ref: TrackingReference, u0, *, n_iter: int = 1, alphas=(1.0, 0.5, 0.25, 0.125),
                  rho0: float = 1e-6, rho_factor: float = 10.0, rho_max: float = 1e6, tol: float = 1e-6, armijo: float = 1e-4,
@@ -1529,26 +1588,6 @@ class ILQRPolicy:
             raise _lib.CimpcError(f"cimpc_plant_mpc_create failed ({rc})")
         self._handle, self._lib = handle, lib
         self.s, self._fresh, self._prev, self.last = 0, True, None, None
-
-    def _plan_rows(self, u0):
-        """u0 (H, nu) or (H, B, nu) -> (H, B, nu), contiguous, clipped into the limits as `ilqr` clips its initial controls."""
-        nu = self._dims[1]
-        u = np.asarray(u0, dtype=np.float64)
-        if u.ndim == 2:
-            u = u[:, None, :]
-        if u.ndim != 3 or u.shape[0] != self.H or u.shape[1] not in (1, self.B) or u.shape[2] != nu:
-            raise ValueError(f"u0 must be ({self.H}, {nu}) or ({self.H}, {self.B}, {nu}), got {np.shape(u0)}")
-        if not np.isfinite(u).all():
-            raise ValueError("u0 must be finite")
-        u = np.broadcast_to(u, (self.H, self.B, nu))
-        if self._lo is not None:
-            u = np.where(u < self._lo, self._lo, np.where(u > self._hi, self._hi, u))
-        return np.ascontiguousarray(u, dtype=np.float64)
-
-    def _open(self):
-        if self._handle is None:
-            raise ValueError("the policy is closed")
-        return self._handle
 
     def control(self, q1, v1, shift=None):
         handle = self._open()
@@ -1608,33 +1647,184 @@ class ILQRPolicy:
                 raise _lib.CimpcError(f"cimpc_plant_mpc_reset failed ({rc})")
         self.s, self._fresh, self._prev = int(s), True, None
 
-    def start(self, q0):
-        self._prev = np.atleast_2d(np.asarray(q0, dtype=np.float64)).copy()
 
-    def __call__(self, q):
-        q = np.atleast_2d(np.asarray(q, dtype=np.float64))
-        if self._prev is None:
-            raise ValueError("start(q0) must be called with the configuration before the first one")
-        u = self.control(q, (q - self._prev) / self.h)
-        self._prev = q.copy()
+def sampling_noise(seed: int, draw: int, B: int, N: int, n_rows: int, nu: int):
+    """The deviates of the sampling policy on the host (`cimpc_plant_sample_noise`; csrc/plant_sample.h), the device's bits and no device
+    needed: eps (n_rows, N, B, nu), entry (j, c, b, i) from the Philox4x32-10 counter (draw, b, c, j nu + i) under the 64-bit seed.  A centred
+    Irwin-Hall deviate of order 8 with unit variance - not a Gaussian."""
+    seed, draw, B, N, n_rows, nu = int(seed), int(draw), int(B), int(N), int(n_rows), int(nu)
+    if min(B, N, n_rows, nu) < 1:
+        raise ValueError("B, N, n_rows and nu must be at least 1")
+    if not (0 <= seed < 2 ** 64 and 0 <= draw < 2 ** 32):
+        raise ValueError("seed must lie in 0 .. 2^64 - 1 and draw in 0 .. 2^32 - 1")
+    eps = np.zeros((n_rows, N, B, nu))
+    rc = _lib.load().cimpc_plant_sample_noise(seed, draw, B, N, n_rows, nu, eps.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != 0:
+        raise _lib.CimpcError(f"cimpc_plant_sample_noise failed ({rc})")
+    return eps
+
+
+@dataclasses.dataclass
+class SamplingPolicyStep:
+    """The diagnostics of one control step of a `SamplingPolicy`: the step s and the shift it was made with; J0 (B,) the warm start's cost;
+    per iteration J_nom (candidate 0's cost), J_best (the choice's), choice (-1: no eligible candidate, the plan was kept), n_eligible
+    (n_iter, B); J and weights (n_iter, N, B), the weights normalised; converged (B,): the last iteration has a choice, every step of which
+    converged."""
+    s: int
+    shift: int
+    J0: np.ndarray
+    J_nom: np.ndarray
+    J_best: np.ndarray
+    choice: np.ndarray
+    n_eligible: np.ndarray
+    J: np.ndarray
+    weights: np.ndarray
+    converged: np.ndarray
+
+
+class SamplingPolicy(_DevicePolicy):
+    """Sampling MPC through contact for B robots, with the plan and the problem resident on the device (`cimpc_plant_sampler`; DESIGN.md
+    section 3, item 3k): predictive sampling (lam = 0) and the MPPI mean (lam > 0).  ref, u0, mu, terrain, opts, u_lo, u_hi as `ILQRPolicy`
+    takes them; sigma (nu,) or a number: the standard deviation of the noise per control; n_samples: the candidates N per robot, of which
+    candidate 0 is the plan itself; noise_hold: steps a noise row is held for; n_iter: iterations per control step; seed: 64 bits.
+    `control(q1, v1, shift=None) -> u (B, nu)` is one control step: n_iter times, N perturbed copies of the plan per robot in ONE open-loop
+    rollout of N B robots, `TrackingCost` on each, and the plan replaced by the eligible candidate of least cost (lam = 0) or moved to the
+    softmax mean of the eligible ones at temperature lam.  The noise is the deviate of `sampling_noise` - not a Gaussian - at draw
+    s n_iter + it, so a control step at the same s sees the same noise.  `last` holds the step's `SamplingPolicyStep`, `plan()` returns the
+    current (u, q, gamma, b, status, iters); `plan()[0]` can be handed to `ILQRPolicy.reset`.  The surface is `ILQRPolicy`'s, so it is a
+    policy of `simulate`."""
+    _DESTROY = "cimpc_plant_sampler_destroy"
+
+    def __init__(self, model: str, B: int, H: int, h: float, mu, ref: TrackingReference, u0, *, n_samples: int = 16, sigma, noise_hold: int = 1,
+                 lam: float = 0.0, n_iter: int = 1, seed: int = 0, u_lo=None, u_hi=None, terrain=None, opts: InteriorPointOptions = SIM_OPTS,
+                 steps_per_launch: int = 0):
+        self._handle = None
+        mid, nq, nu, nc, fd, nw = model_dims(model)
+        B, H, N, n_iter, noise_hold, seed = int(B), int(H), int(n_samples), int(n_iter), int(noise_hold), int(seed)
+        if B < 1 or H < 1:
+            raise ValueError("B and H must be at least 1")
+        if not isinstance(ref, TrackingReference):
+            raise ValueError("ref must be a TrackingReference")
+        if not float(h) > 0.0:
+            raise ValueError("h must be positive")
+        if N < 1 or N * B * H > 2 ** 31 - 1:
+            raise ValueError("n_samples must be at least 1 and n_samples B H must fit an int")
+        if n_iter < 1 or noise_hold < 1:
+            raise ValueError("n_iter and noise_hold must be at least 1")
+        lam = float(lam)
+        if not lam >= 0.0:
+            raise ValueError("lam must not be negative")
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must lie in 0 .. 2^64 - 1")
+        sig = np.asarray(sigma, dtype=np.float64)
+        sig = np.full(nu, float(sig)) if sig.ndim == 0 else np.ascontiguousarray(sig)
+        if sig.shape != (nu,):
+            raise ValueError(f"sigma must be a number or ({nu},), got {np.shape(sigma)}")
+        if not (np.isfinite(sig).all() and (sig >= 0.0).all()):
+            raise ValueError("sigma must be finite and not negative")
+        lo, hi = _limit_arrays(u_lo, u_hi, B, nu)
+        xr, ur = ref._arrays(B)
+        cc, keep = ref.window(0, H)._struct(nq, nu, B, H)
+        mua = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
+        if mua.size not in (1, B):
+            raise ValueError(f"mu: one friction coefficient or one per robot ({B}), got {mua.size}")
+        if terrain is None and model in TERRAIN_MODELS:
+            terrain = "flat_2D_lc"
+        self.model, self.B, self.H, self.h, self.ref = model, B, H, float(h), ref
+        self.n_samples, self.sigma, self.noise_hold, self.lam, self.seed, self.mu = N, sig, noise_hold, lam, seed, mua
+        self._dims, self._lo, self._hi, self.n_iter = (nq, nu, nc, fd * nc), lo, hi, n_iter
+        u0 = self._plan_rows(u0)
+        ta, nt = (None, 0) if terrain is None else _terrain_array(terrain, B)
+        o = _lib.IpOpts(**dataclasses.asdict(opts))
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        Qc, Rc, Qfc = keep[:3]
+        handle = C.c_void_p()
+        lib = _lib.load()
+        rc = lib.cimpc_plant_sampler_create(mid, B, H, int(steps_per_launch), nt, ta, dp(mua), mua.size, float(h), C.byref(o), dp(Qc), dp(Qfc), dp(Rc),
+                                            cc.n_Q, cc.n_R, ref.L, xr.shape[1], dp(xr), dp(ur), N, dp(sig), noise_hold, lam, n_iter, seed,
+                                            1 if lo is None else lo.shape[0], dp(lo), dp(hi), dp(u0), C.byref(handle))
+        if rc == -1:
+            raise ValueError(lib.cimpc_last_error(None).decode())
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_sampler_create failed ({rc})")
+        self._handle, self._lib = handle, lib
+        self.s, self._fresh, self._prev, self.last = 0, True, None, None
+
+    def control(self, q1, v1, shift=None):
+        handle = self._open()
+        nq, nu = self._dims[:2]
+        q1, v1 = np.atleast_2d(np.asarray(q1, dtype=np.float64)), np.atleast_2d(np.asarray(v1, dtype=np.float64))
+        if q1.shape != (self.B, nq) or v1.shape != (self.B, nq):
+            raise ValueError(f"q1 and v1 must be ({self.B}, {nq}), got {q1.shape} and {v1.shape}")
+        shift = (0 if self._fresh else 1) if shift is None else int(shift)
+        if shift < 0:
+            raise ValueError("shift must not be negative")
+        if not (np.isfinite(q1).all() and np.isfinite(v1).all()):
+            raise ValueError("q1 and v1 must be finite")
+        s = self.s + shift
+        q0 = np.ascontiguousarray(q1 - self.h * v1); q1 = np.ascontiguousarray(q1)
+        B, N, n_iter = self.B, self.n_samples, self.n_iter
+        u, J0, conv = np.zeros((B, nu)), np.zeros(B), np.zeros(B, dtype=np.int32)
+        hJn, hJb = np.zeros((n_iter, B)), np.zeros((n_iter, B))
+        hch, hne = np.zeros((n_iter, B), dtype=np.int32), np.zeros((n_iter, B), dtype=np.int32)
+        J, wts = np.zeros((n_iter, N, B)), np.zeros((n_iter, N, B))
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        rc = self._lib.cimpc_plant_sampler_control(handle, s, shift, dp(q0), dp(q1), dp(u), dp(J0), dp(hJn), dp(hJb), ip(hch), ip(hne), dp(J), dp(wts), ip(conv))
+        if rc == -1:
+            raise ValueError(self._lib.cimpc_last_error(None).decode())
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_sampler_control failed ({rc})")
+        self.s, self._fresh = s, False
+        self.last = SamplingPolicyStep(s=s, shift=shift, J0=J0, J_nom=hJn, J_best=hJb, choice=hch, n_eligible=hne, J=J, weights=wts, converged=conv.astype(bool))
         return u
 
-    def close(self):
-        if self._handle is not None:
-            handle, self._handle = self._handle, None
-            self._lib.cimpc_plant_mpc_destroy(handle)
+    def plan(self):
+        handle = self._open()
+        nq, nu, nc, nb = self._dims
+        H, B = self.H, self.B
+        u, q, g, b = np.zeros((H, B, nu)), np.zeros((H + 2, B, nq)), np.zeros((H, B, nc)), np.zeros((H, B, nb))
+        st, it = np.zeros((H, B), dtype=np.int32), np.zeros((H, B), dtype=np.int32)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        rc = self._lib.cimpc_plant_sampler_plan(handle, dp(u), dp(q), dp(g), dp(b), ip(st), ip(it))
+        if rc == -1:
+            raise ValueError(self._lib.cimpc_last_error(None).decode())
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_sampler_plan failed ({rc})")
+        return u, q, g, b, st, it
 
-    def __enter__(self):
-        return self
+    def raw_weights(self):
+        """The unnormalised weights w_c (n_iter, N, B) of the last control step (`cimpc_plant_sampler_raw_weights`): `last.weights` is w_c / S."""
+        handle = self._open()
+        w = np.zeros((self.n_iter, self.n_samples, self.B))
+        rc = self._lib.cimpc_plant_sampler_raw_weights(handle, w.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc == -1:
+            raise ValueError(self._lib.cimpc_last_error(None).decode())
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_sampler_raw_weights failed ({rc})")
+        return w
 
-    def __exit__(self, *exc):
-        self.close()
+    @property
+    def plan_rollouts(self) -> int:
+        """The B-robot rollouts `plan()` has run so far (`cimpc_plant_sampler_dims`): with lam > 0 one per control step whose plan was asked for."""
+        handle, n = self._open(), C.c_int(0)
+        if self._lib.cimpc_plant_sampler_dims(handle, None, None, None, None, None, None, C.byref(n)) != 0:
+            raise _lib.CimpcError("cimpc_plant_sampler_dims failed")
+        return n.value
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def reset(self, u0=None, s: int = 0):
+        handle = self._open()
+        if int(s) < 0:
+            raise ValueError("s must not be negative")
+        if u0 is not None:
+            u = self._plan_rows(u0)
+            rc = self._lib.cimpc_plant_sampler_reset(handle, u.ctypes.data_as(C.POINTER(C.c_double)))
+            if rc == -1:
+                raise ValueError(self._lib.cimpc_last_error(None).decode())
+            if rc != 0:
+                raise _lib.CimpcError(f"cimpc_plant_sampler_reset failed ({rc})")
+        self.s, self._fresh, self._prev = int(s), True, None
 
 
 def rollout_torch(model: str, q1, v1, u, h: float, mu, *, w=None, feedback=None, **kw):

@@ -848,6 +848,62 @@ int cimpc_plant_mpc_reset(cimpc_plant_mpc handle, const double* u0);
 int cimpc_plant_mpc_dims(cimpc_plant_mpc handle, int* model, int* B, int* H, int* L, int* n_iter);
 int cimpc_plant_mpc_destroy(cimpc_plant_mpc handle);
 
+/* ---- the sampling policy: predictive sampling and the MPPI mean (csrc/plant_sample.h) --------------------
+ * A cimpc_plant_sampler keeps the problem and the plan of B robots on ONE device between control steps: the weights, the reference of L
+ * stages, the limits, mu, the terrains, h and opts as cimpc_plant_mpc_create takes them; sigma (m entries, finite, >= 0), the number of
+ * candidates N, noise_hold (>= 1), the temperature lam (>= 0), n_iter and the 64-bit seed; the plan u (H x B x m); and the trajectory that
+ * goes with it.  The planning model takes no disturbance and nothing is differentiated.
+ *
+ * Control step s reads the goal window of cimpc_plant_mpc (x row min(s + t, L), u row min(s + t, L - 1)), starts from
+ * u_warm[t] = u_plan[min(t + shift, H - 1)], q[0] = q0, q[1] = q1, and runs n_iter iterations.  Iteration `it` rolls out N candidates per
+ * robot in ONE open-loop rollout of N B robots (candidate c of robot b is rollout robot c B + b, on robot b's mu and terrain): candidate 0
+ * is the plan to the bit, candidate c >= 1 is u_c[t, b, i] = limit(u_nom[t, b, i] + sigma[i] eps) with eps the deviate of
+ * cimpc_plant_sample_noise at draw = (uint32)(s n_iter + it), row t / noise_hold - a centred Irwin-Hall deviate of order 8 with unit
+ * variance, NOT a Gaussian.  A candidate is eligible when its H steps all converged and its cost J (cimpc_plant_tracking_cost) is finite;
+ * the choice is the eligible candidate of least J, the lower index on a tie, -1 if there is none, and then the plan is kept.  lam = 0
+ * (predictive sampling): the new plan is the choice's controls.  lam > 0 (MPPI): w_c = exp(-((J_c - J_choice) / lam)) for the eligible,
+ * 0.0 otherwise, and u_new = limit(u_nom + (sum_c w_c (u_c - u_nom)) / (sum_c w_c)), both sums over ascending c from 0.0.
+ *
+ * cimpc_plant_sampler_create: everything goes up once; u0 (H x B x m, finite, inside the limits where there are any) is loaded as the plan.
+ * cimpc_plant_sampler_control: up 2 B nq doubles; down u (B x m: row 0 of the new plan), J0 (B: candidate 0's cost in iteration 0, the warm
+ *   start's own), hist_J_nom (candidate 0's cost), hist_J_best (the choice's; J_nom's with choice -1), hist_choice, hist_n_eligible
+ *   (n_iter x B each), J and weights (n_iter x N x B each; either may be NULL and is then not copied; the weights are normalised, with
+ *   lam = 0 they are 1.0 at the choice and 0.0 elsewhere, with choice -1 all 0.0) and converged (B: the last iteration has a choice, every
+ *   step of which converged - with lam > 0 too it refers to the choice, not to the mean).  One read-back, one synchronize, and no
+ *   allocation once the shared workspace has its size.
+ * cimpc_plant_sampler_plan: the current plan u (H x B x m) and its trajectory q ((H + 2) x B x nq), gamma, b, status, iters (as
+ *   cimpc_plant_rollout lays them out) - each may be NULL; before the first control step only u is meaningful.  With lam = 0 the trajectory
+ *   is the chosen candidate's, already on the device.  With lam > 0, or after a reset, the plan has not been rolled out: the first call that
+ *   asks for a row then runs ONE open-loop rollout of the B robots from the last (q0, q1), bit for bit cimpc_plant_rollout on the plan, and
+ *   keeps it until the next control step or reset.
+ * cimpc_plant_sampler_raw_weights: w (n_iter x N x B), the unnormalised weights w_c of the last control step, of which `weights` is w_c / S -
+ *   what a check of the mean needs to restate it to the bit; refused before the first control step.
+ * cimpc_plant_sampler_reset: loads a new plan u0.  cimpc_plant_sampler_dims: each pointer may be NULL; n_rollouts counts the rollouts
+ *   cimpc_plant_sampler_plan has run.  cimpc_plant_sampler_destroy: NULL is fine.
+ * cimpc_plant_sample_noise: host only, no device: eps n_rows x N x B x nu, entry (j, c, b, i) the deviate of counter (draw, b, c, j nu + i)
+ *   under the key (seed & 0xffffffff, seed >> 32) - Philox4x32-10 and the rule of csrc/plant_sample.h with a team of one, the device's bits.
+ * Refused with CIMPC_ERR_INVALID before any device is touched, the reason left for cimpc_last_error(NULL) and the handle as it was (after
+ * a refused create *handle is NULL): a null pointer (terrain, the limits, J and weights excepted); N below 1; N B H beyond an int; a sigma
+ * entry that is negative or not finite; noise_hold below 1; lam negative or not a number; H or L below 1; n_iter below 1; shift or s
+ * negative; a shift with no plan loaded; a non-finite entry of q0, q1 or u0; an entry of u0 outside the limits; what cimpc_plant_rollout
+ * and cimpc_plant_tracking_cost refuse of the arguments they share.  After a HIP error a handle refuses further use, naming that. */
+typedef struct cimpc_plant_sampler_s* cimpc_plant_sampler;
+int cimpc_plant_sampler_create(int model, int B, int H, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                               const double* mu, int n_mu, double h, const cimpc_ip_opts* opts,
+                               const double* Q, const double* Qf, const double* R, int n_Q, int n_R,
+                               int L, int n_x, const double* x_ref, const double* u_ref,
+                               int N, const double* sigma, int noise_hold, double lam, int n_iter, unsigned long long seed,
+                               int n_lim, const double* u_lo, const double* u_hi, const double* u0, cimpc_plant_sampler* handle);
+int cimpc_plant_sampler_control(cimpc_plant_sampler handle, int s, int shift, const double* q0, const double* q1,
+                                double* u, double* J0, double* hist_J_nom, double* hist_J_best, int* hist_choice, int* hist_n_eligible,
+                                double* J, double* weights, int* converged);
+int cimpc_plant_sampler_plan(cimpc_plant_sampler handle, double* u, double* q, double* gamma, double* b, int* status, int* iters);
+int cimpc_plant_sampler_raw_weights(cimpc_plant_sampler handle, double* w);
+int cimpc_plant_sampler_reset(cimpc_plant_sampler handle, const double* u0);
+int cimpc_plant_sampler_dims(cimpc_plant_sampler handle, int* model, int* B, int* H, int* L, int* N, int* n_iter, int* n_rollouts);
+int cimpc_plant_sampler_destroy(cimpc_plant_sampler handle);
+int cimpc_plant_sample_noise(unsigned long long seed, unsigned int draw, int B, int N, int n_rows, int nu, double* eps);
+
 /* ---- cimpc_set_linearization_batch from (z, theta) alone: plant model `model` linearized at kappa (cimpc_plant_linearize's kernel and arguments;
  * z0 = z, th0 = theta) and the tables built from its output, all on the handle's device and stream;
  * nothing but z, theta and the terrains goes up, nothing but N status words comes back.  Equal bit for bit to

@@ -1484,6 +1484,173 @@ function plant_mpc_destroy(p::PlantMpc)
     return nothing
 end
 
+# ---- the sampling policy (DESIGN.md section 3, item 3k): predictive sampling and the MPPI mean on a handle ---------------------------------
+"""
+    PlantSampler
+
+The handle of `cimpc_plant_sampler` with the sizes it was created with.  Unexecuted, like the rest of this binding.
+"""
+mutable struct PlantSampler
+    handle::Ptr{Cvoid}
+    model::Symbol
+    B::Int
+    H::Int
+    L::Int
+    N::Int
+    n_iter::Int
+end
+
+"""
+    plant_sampler_create(model, B, H, μ, h_sim, opts, Q, Qf, R, x_ref, u_ref, u0, sigma; n_samples = 16, noise_hold = 1, lam = 0.0,
+                         n_iter = 1, seed = 0, u_lo = nothing, u_hi = nothing, terrain = nothing, steps_per_launch = 0) -> PlantSampler
+
+`cimpc_plant_sampler_create`: the problem of a sampling policy goes up once.  The weights, the reference, u0 and the limits as
+`plant_mpc_create` takes them; sigma: nu standard deviations, finite and not negative; lam = 0 is predictive sampling, lam > 0 the MPPI
+mean.  The noise is a centred Irwin-Hall deviate of order 8, not a Gaussian.  Unexecuted, like the rest of this binding: written against
+include/cimpc.h and checked against its prototype by text only.
+"""
+function plant_sampler_create(model::Symbol, B::Int, H::Int, μ, h_sim, opts, Q::Array{Float64,3}, Qf::Matrix{Float64}, R::Array{Float64,3},
+                              x_ref::Array{Float64,3}, u_ref::Array{Float64,3}, u0::Array{Float64,3}, sigma::Vector{Float64};
+                              n_samples::Int = 16, noise_hold::Int = 1, lam::Real = 0.0, n_iter::Int = 1, seed::Integer = 0,
+                              u_lo::Union{Nothing,Matrix{Float64}} = nothing, u_hi::Union{Nothing,Matrix{Float64}} = nothing,
+                              terrain::Union{Nothing,Vector{Terrain}} = nothing, steps_per_launch::Int = 0)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    n, m = 2 * nq, nu
+    (B >= 1 && H >= 1 && n_iter >= 1 && n_samples >= 1 && noise_hold >= 1) || error("plant_sampler_create: B, H, n_iter, n_samples and noise_hold must be at least 1")
+    n_Q, n_R, n_x, L = size(Q, 3), size(R, 3), size(x_ref, 2), size(u_ref, 3)
+    (size(Q) == (n, n, n_Q) && n_Q in (1, H) && size(R) == (m, m, n_R) && n_R in (1, H) && size(Qf) == (n, n)) || error("plant_sampler_create: the weights do not fit the model")
+    (L >= 1 && n_x in (1, B) && size(x_ref) == (n, n_x, L + 1) && size(u_ref) == (m, n_x, L)) || error("plant_sampler_create: x_ref must be $n x n_x x (L + 1) and u_ref $m x n_x x L")
+    size(u0) == (m, B, H) || error("plant_sampler_create: u0 must be $m x $B x $H")
+    (length(sigma) == nu && all(isfinite, sigma) && all(>=(0), sigma)) || error("plant_sampler_create: sigma must be $nu finite entries that are not negative")
+    lam >= 0 || error("plant_sampler_create: lam must not be negative")
+    (u_lo === nothing) == (u_hi === nothing) || error("plant_sampler_create: u_lo and u_hi go together")
+    limited = u_lo !== nothing
+    (!limited || (size(u_lo) == size(u_hi) && size(u_lo, 1) == nu && size(u_lo, 2) in (1, B))) || error("plant_sampler_create: u_lo, u_hi must be $nu x 1 or $nu x $B")
+    n_lim = limited ? size(u_lo, 2) : 1
+    lo, hi = limited ? (u_lo, u_hi) : (C_NULL, C_NULL)
+    μs = Float64.(vcat(μ))
+    length(μs) in (1, B) || error("plant_sampler_create: one friction coefficient or one per robot")
+    n_mu = length(μs)
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    sd = UInt64(seed)
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    check(@ccall LIB.cimpc_plant_sampler_create(id::Cint, B::Cint, H::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                                μs::Ptr{Cdouble}, n_mu::Cint, h_sim::Cdouble, o::Ref{IpOpts}, Q::Ptr{Cdouble}, Qf::Ptr{Cdouble},
+                                                R::Ptr{Cdouble}, n_Q::Cint, n_R::Cint, L::Cint, n_x::Cint, x_ref::Ptr{Cdouble}, u_ref::Ptr{Cdouble},
+                                                n_samples::Cint, sigma::Ptr{Cdouble}, noise_hold::Cint, lam::Cdouble, n_iter::Cint, sd::Culonglong,
+                                                n_lim::Cint, lo::Ptr{Cdouble}, hi::Ptr{Cdouble}, u0::Ptr{Cdouble}, handle::Ref{Ptr{Cvoid}})::Cint)
+    return PlantSampler(handle[], model, B, H, L, n_samples, n_iter)
+end
+
+"""
+    plant_sampler_control(p, s, shift, q0, q1) -> (u, J0, J_nom, J_best, choice, n_eligible, J, weights, converged)
+
+`cimpc_plant_sampler_control`: one control step of the policy from the measured q0, q1 (nq x B).  u nu x B is the control to apply; J_nom,
+J_best, choice (-1: the plan was kept), n_eligible are B x n_iter; J and the normalised weights B x N x n_iter.  Unexecuted, like the rest
+of this binding: written against include/cimpc.h and checked against its prototype by text only.
+"""
+function plant_sampler_control(p::PlantSampler, s::Int, shift::Int, q0::Matrix{Float64}, q1::Matrix{Float64})
+    p.handle != C_NULL || error("plant_sampler_control: the policy is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(p.model)
+    (size(q0) == (nq, p.B) && size(q1) == (nq, p.B)) || error("plant_sampler_control: q0 and q1 must be $nq x $(p.B)")
+    (s >= 0 && shift >= 0) || error("plant_sampler_control: s and shift must not be negative")
+    B, N, n_iter = p.B, p.N, p.n_iter
+    u = zeros(nu, B); J0 = zeros(B); converged = zeros(Cint, B)
+    hJn = zeros(B, n_iter); hJb = zeros(B, n_iter); hch = zeros(Cint, B, n_iter); hne = zeros(Cint, B, n_iter)
+    J = zeros(B, N, n_iter); weights = zeros(B, N, n_iter)
+    check(@ccall LIB.cimpc_plant_sampler_control(p.handle::Ptr{Cvoid}, s::Cint, shift::Cint, q0::Ptr{Cdouble}, q1::Ptr{Cdouble}, u::Ptr{Cdouble},
+                                                 J0::Ptr{Cdouble}, hJn::Ptr{Cdouble}, hJb::Ptr{Cdouble}, hch::Ptr{Cint}, hne::Ptr{Cint},
+                                                 J::Ptr{Cdouble}, weights::Ptr{Cdouble}, converged::Ptr{Cint})::Cint)
+    return u, J0, hJn, hJb, Int.(hch), Int.(hne), J, weights, converged .!= 0
+end
+
+"""
+    plant_sampler_plan(p) -> (u, q, γ, b, status, iters)
+
+`cimpc_plant_sampler_plan`: the current plan u nu x B x H and its trajectory q nq x B x (H + 2), γ, b, status, iters; with lam > 0 the first
+call after a control step rolls the mean out.  Unexecuted, like the rest of this binding: written against include/cimpc.h and checked
+against its prototype by text only.
+"""
+function plant_sampler_plan(p::PlantSampler)
+    p.handle != C_NULL || error("plant_sampler_plan: the policy is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(p.model)
+    B, H = p.B, p.H
+    u = zeros(nu, B, H); q = zeros(nq, B, H + 2); γ = zeros(nc, B, H); b = zeros(nf * nc, B, H)
+    status = zeros(Cint, B, H); iters = zeros(Cint, B, H)
+    check(@ccall LIB.cimpc_plant_sampler_plan(p.handle::Ptr{Cvoid}, u::Ptr{Cdouble}, q::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble},
+                                              status::Ptr{Cint}, iters::Ptr{Cint})::Cint)
+    return u, q, γ, b, status, iters
+end
+
+"""
+    plant_sampler_raw_weights(p) -> w
+
+`cimpc_plant_sampler_raw_weights`: the unnormalised weights B x N x n_iter of the last control step.  Unexecuted, like the rest of this
+binding: written against include/cimpc.h and checked against its prototype by text only.
+"""
+function plant_sampler_raw_weights(p::PlantSampler)
+    p.handle != C_NULL || error("plant_sampler_raw_weights: the policy is closed")
+    w = zeros(p.B, p.N, p.n_iter)
+    check(@ccall LIB.cimpc_plant_sampler_raw_weights(p.handle::Ptr{Cvoid}, w::Ptr{Cdouble})::Cint)
+    return w
+end
+
+"""
+    plant_sampler_reset(p, u0)
+
+`cimpc_plant_sampler_reset`: loads a new plan u0 (nu x B x H).  Unexecuted, like the rest of this binding: written against include/cimpc.h
+and checked against its prototype by text only.
+"""
+function plant_sampler_reset(p::PlantSampler, u0::Array{Float64,3})
+    p.handle != C_NULL || error("plant_sampler_reset: the policy is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(p.model)
+    size(u0) == (nu, p.B, p.H) || error("plant_sampler_reset: u0 must be $nu x $(p.B) x $(p.H)")
+    check(@ccall LIB.cimpc_plant_sampler_reset(p.handle::Ptr{Cvoid}, u0::Ptr{Cdouble})::Cint)
+    return p
+end
+
+"""
+    plant_sampler_dims(p) -> (model id, B, H, L, N, n_iter, n_rollouts)
+
+`cimpc_plant_sampler_dims`, as the library holds them; n_rollouts counts the rollouts `plant_sampler_plan` has run.  Unexecuted, like the
+rest of this binding: written against include/cimpc.h and checked against its prototype by text only.
+"""
+function plant_sampler_dims(p::PlantSampler)
+    p.handle != C_NULL || error("plant_sampler_dims: the policy is closed")
+    model = Ref{Cint}(0); B = Ref{Cint}(0); H = Ref{Cint}(0); L = Ref{Cint}(0); N = Ref{Cint}(0); n_iter = Ref{Cint}(0); n_rollouts = Ref{Cint}(0)
+    check(@ccall LIB.cimpc_plant_sampler_dims(p.handle::Ptr{Cvoid}, model::Ref{Cint}, B::Ref{Cint}, H::Ref{Cint}, L::Ref{Cint}, N::Ref{Cint},
+                                              n_iter::Ref{Cint}, n_rollouts::Ref{Cint})::Cint)
+    return Int(model[]), Int(B[]), Int(H[]), Int(L[]), Int(N[]), Int(n_iter[]), Int(n_rollouts[])
+end
+
+"""
+    plant_sampler_destroy(p)
+
+`cimpc_plant_sampler_destroy`: frees the policy's device memory; a second call does nothing.  Unexecuted, like the rest of this binding:
+written against include/cimpc.h and checked against its prototype by text only.
+"""
+function plant_sampler_destroy(p::PlantSampler)
+    p.handle == C_NULL && return nothing
+    h, p.handle = p.handle, C_NULL
+    check(@ccall LIB.cimpc_plant_sampler_destroy(h::Ptr{Cvoid})::Cint)
+    return nothing
+end
+
+"""
+    plant_sample_noise(seed, draw, B, N, n_rows, nu) -> eps
+
+`cimpc_plant_sample_noise`: the deviates of the sampling policy on the host, nu x B x N x n_rows, the device's bits; no device is needed.
+Unexecuted, like the rest of this binding: written against include/cimpc.h and checked against its prototype by text only.
+"""
+function plant_sample_noise(seed::Integer, draw::Integer, B::Int, N::Int, n_rows::Int, nu::Int)
+    (B >= 1 && N >= 1 && n_rows >= 1 && nu >= 1) || error("plant_sample_noise: B, N, n_rows and nu must be at least 1")
+    eps = zeros(nu, B, N, n_rows)
+    sd, dr = UInt64(seed), UInt32(draw)
+    check(@ccall LIB.cimpc_plant_sample_noise(sd::Culonglong, dr::Cuint, B::Cint, N::Cint, n_rows::Cint, nu::Cint, eps::Ptr{Cdouble})::Cint)
+    return eps
+end
+
 # ---- the plant models linearized on the device: the `LinearizedStep` triple of N knots in one call (linearized_step.jl:10-31) --------
 """
     plant_linearize(model, z, θ, κ; terrain = nothing) -> (r0, rz0, rθ0)
