@@ -130,6 +130,8 @@ SIGNATURES = {
     "cimpc_plant_tape_lqr": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
     "cimpc_plant_tape_lqr_box": (C.c_int, [_h, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
                                            C.c_int, _dp, _dp, _dp, _ip]),
+    "cimpc_plant_tape_lqr_shooting": (C.c_int, [_h, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
+                                                C.c_int, _dp, _dp, _dp, _ip, C.c_int, _dp]),
     "cimpc_plant_tracking_cost": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TrackingCost), _dp, _dp, _dp, _dp, _dp]),
     "cimpc_plant_tape_linesearch": (C.c_int, [_h, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double,
                                               C.POINTER(IpOpts), _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_double, C.POINTER(TrackingCost), C.c_double,
@@ -159,6 +161,15 @@ SIGNATURES = {
     "cimpc_plant_sampler_dims": (C.c_int, [_h, _ip, _ip, _ip, _ip, _ip, _ip, _ip]),
     "cimpc_plant_sampler_destroy": (C.c_int, [_h]),
     "cimpc_plant_sample_noise": (C.c_int, [C.c_ulonglong, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
+    "cimpc_plant_rollout_segments": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int,
+                                               C.c_int, _dp, C.c_int, C.c_double, C.POINTER(IpOpts), C.POINTER(TrackingCost), C.c_double, C.c_int,
+                                               _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _ip, C.POINTER(_h)]),
+    "cimpc_plant_shooting_forward": (C.c_int, [_h, C.c_int, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "cimpc_plant_shooting_linesearch": (C.c_int, [_h, C.c_int, C.c_int, C.c_int, C.POINTER(Terrain), _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double,
+                                                  C.POINTER(IpOpts), _dp, _dp, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_double, C.POINTER(TrackingCost),
+                                                  C.c_double, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _ip, C.POINTER(_h),
+                                                  C.c_int, _dp, _dp]),
+    "cimpc_plant_shooting_cost": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TrackingCost), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "cimpc_plant_tape_dims": (C.c_int, [_h, _ip, _ip, _ip, _ip]),
     "cimpc_plant_tape_destroy": (C.c_int, [_h]),
     "cimpc_tvlqr": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp]),

@@ -29,6 +29,13 @@
 // a_ij -= l a_kj; back-substitution s -= u_kj x_j ascending j, then s / u_kk).  The chain does not depend on the team, the batch, or
 // which robots ride along.
 //
+// THE DEFECT HOOK (multiple shooting; plant_shooting.h): with defects d_j (j = 1 .. M-1, 2nq numbers each) at
+// the nodes t = j seg_len, the dynamics about the segments' trajectories are dx_{t+1} = A dx_t + B du_t + d_{t+1} at a node, and the affine
+// term moves the value's linear term: at the top of the walk step of t, if t + 1 is a node,  p <- p + P d.  P d has no zero structure:
+// (P d)[c] = sum_k P[c, k] d[k] is ONE running sum over k = 0 .. n-1 ascending from 0.0, one rounded product and one rounded sum per term,
+// and p[c] + (P d)[c] one more rounded sum.  The hook is compiled into the SHOOT chain alone; every other instantiation keeps its
+// statements, and with them its instructions.
+//
 // A zero or non-finite pivot, or a non-finite K, k, P or p, ends the robot's chain: status[b] = the 1-based walk step s, and the
 // robot's outputs are zeros.  Other robots are unaffected.
 //
@@ -81,6 +88,9 @@ struct PlantRiccati {
     const double *u_lo = nullptr, *u_hi = nullptr, *u_nom = nullptr, *rho_b = nullptr;
     int* clamped = nullptr;
     int n_lim = 1, n_rho = 1;
+    // the defect hook, read by the SHOOT chain alone: defects (T / seg_len - 1) x B x n, the defect of node j = 1 .. at step j seg_len
+    const double* defects = nullptr;
+    int seg_len = 0;
 };
 
 // ---- the plan: what a robot's chain needs of the team's shared memory ---------------------------------------------------------------
@@ -102,6 +112,11 @@ constexpr size_t plant_riccati_box_lds(int nq, int nu) { return plant_riccati_bo
 static_assert(plant_riccati_box_lds(18, 12) == 65760 && 2 * plant_riccati_box_lds(18, 12) <= PLANT_RIC_MAX_LDS,
               "the largest model with limits: 64 KB, still two workgroups a CU");
 static_assert(plant_riccati_box_lds(11, 8) == 25960, "quadruped with limits: 25 KB");
+// the chain with the defect hook: the limited chain's work and the node's defect (n) behind it
+PRIC_HD constexpr size_t plant_riccati_shoot_work_doubles(int nq, int nu) { return plant_riccati_box_work_doubles(nq, nu) + (size_t)2 * nq; }
+constexpr size_t plant_riccati_shoot_lds(int nq, int nu) { return plant_riccati_shoot_work_doubles(nq, nu) * sizeof(double); }
+static_assert(plant_riccati_shoot_lds(18, 12) == 66048 && 2 * plant_riccati_shoot_lds(18, 12) <= PLANT_RIC_MAX_LDS,
+              "the largest model with limits and defects: 64.5 KB, still two workgroups a CU");
 static_assert(plant_riccati_fits(18, 12) && plant_riccati_fits(11, 8) && plant_riccati_fits(1, 1) && !plant_riccati_fits(60, 12), "the plan's limits");
 
 PRIC_HD inline bool plant_riccati_bad_pivot(double pv) { return !(std::fabs(pv) > 0.0) || !std::isfinite(pv); }
@@ -162,7 +177,8 @@ PRIC_UNROLL
 // The chain of robot rb.  work: shared by the team, plant_riccati_work_doubles(nq, nu).  LIN: the linear terms are compiled in (the
 // caller has L.q and L.r non-null and L.laps == 1).  BOX (with LIN): the limited pass of plant_boxqp.h stands where the unlimited solve
 // does, work is plant_riccati_box_work_doubles(nq, nu), rho is the robot's own and clamped is written.  All matrices column-major.
-template <bool LIN, bool BOX = false, class Team>
+// SHOOT (with BOX): the defect hook is compiled in, L.defects and L.seg_len are read, work is plant_riccati_shoot_work_doubles(nq, nu).
+template <bool LIN, bool BOX = false, bool SHOOT = false, class Team>
 PRIC_HD inline void plant_riccati_chain_as(const PlantRiccati& L, int rb, double* work, Team& team) {
     const int me = team.rank(), np = team.size();
     const int nq = L.nq, n = 2 * nq, m = L.nu, B = L.B, T = L.T, nr = L.nr, nc = n + m, fw = n + (LIN ? 1 : 0);
@@ -191,6 +207,7 @@ PRIC_HD inline void plant_riccati_chain_as(const PlantRiccati& L, int rb, double
     const auto zero = [](int, int) { return 0.0; };
     const int steps = L.laps * T;
     static_assert(LIN || !BOX, "the limited pass needs the linear terms");
+    static_assert(BOX || !SHOOT, "the defect hook stands in the limited chain");
     double rho_box = 0.0;                    // BOX: the robot's own rho
     PlantBoxQPWork box{};
     if constexpr (BOX) {
@@ -225,6 +242,20 @@ PRIC_HD inline void plant_riccati_chain_as(const PlantRiccati& L, int rb, double
         const double* rt = LIN ? L.r + ((size_t)t * B + rb) * m : nullptr;
         bool finite = true;                  // of the entries of K, k, P and p this member computes
         if (s < steps) team.fetch_issue(block(tn), nq, nc, nr);      // in flight while step t is worked
+        if constexpr (SHOOT) {               // t + 1 a node: p <- p + P d, the defect staged behind the box QP's work
+            if (t + 1 < T && (t + 1) % L.seg_len == 0) {
+                double* dn = work + plant_riccati_box_work_doubles(nq, m);
+                const double* d = L.defects + ((size_t)((t + 1) / L.seg_len - 1) * B + rb) * n;
+                for (int e = me; e < n; e += np) dn[e] = d[e];
+                team.sync();
+                for (int c = np - 1 - me; c < n; c += np) {
+                    double a = 0.0;
+                    for (int k = 0; k < n; ++k) a += P[k * n + c] * dn[k];
+                    pv_[c] = pv_[c] + a;
+                }
+                team.sync();
+            }
+        }
         for (int e = me; e < nq * m; e += np) DuT[(e % nq) * m + e / nq] = Du[e];
         for (int e = me; e < m * m; e += np) Rm[e] = Rt[e];
         team.sync();

@@ -16,6 +16,9 @@
 //   cimpc_plant_tape_lqr_box   the limited pass (plant_boxqp.h): the same call with a rho per robot, control
 //                              limits and the tape's applied controls; plant_riccati_kernel<true, true>, the only instantiation that holds
 //                              the box QP, with plant_boxqp.h's work behind the chain's in LDS (64 KB at the largest model)
+//   cimpc_plant_tape_lqr_shooting   the limited pass with the defect hook of plant_riccati.h (multiple shooting):
+//                              plant_riccati_shoot_kernel, a kernel of its own so that the instantiations above keep their names and
+//                              their instructions; the node's defect is staged behind the box QP's work (64.5 KB at the largest model)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -73,6 +76,15 @@ __global__ __launch_bounds__(RIC_THREADS) void plant_riccati_kernel(PlantRiccati
     plant_riccati_chain_as<LIN, BOX>(L, rb, ric_lds, team);
 }
 
+// the limited chain with the defect hook: L.defects and L.seg_len set, plant_riccati_shoot_lds(nq, nu) of LDS
+__global__ __launch_bounds__(RIC_THREADS) void plant_riccati_shoot_kernel(PlantRiccati L) {
+    extern __shared__ __attribute__((aligned(16))) double ric_lds[];
+    const int rb = blockIdx.x;
+    if (rb >= L.B) return;                                                // uniform over the workgroup
+    PlantRiccatiGroup team;
+    plant_riccati_chain_as<true, true, true>(L, rb, ric_lds, team);
+}
+
 namespace {
 // grow-only device buffers of the entry, one pair per device, next to the plant workspace whose stream and mutex it uses
 struct RiccatiWs { double *d_in = nullptr, *d_out = nullptr; size_t cap_in = 0, cap_out = 0; };
@@ -89,16 +101,25 @@ bool plant_riccati_box_launch(const PlantRiccati& L, hipStream_t st) {
     return hipGetLastError() == hipSuccess;
 }
 
+// The limited chain with the defect hook, beside it: L.defects and L.seg_len set, every pointer on the device.
+static bool plant_riccati_shoot_launch(const PlantRiccati& L, hipStream_t st) {
+    const size_t lds = plant_riccati_shoot_lds(L.nq, L.nu);
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(plant_riccati_shoot_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+    hipLaunchKernelGGL(plant_riccati_shoot_kernel, dim3(L.B), dim3(RIC_THREADS), lds, st, L);
+    return hipGetLastError() == hipSuccess;
+}
+
 }  // namespace cimpc
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------
 // Validate (no device needed), then on the tape's device and the plant workspace's private stream: one upload (Q | Qf | R | q | r, and
 // for the limited pass rho | u_lo | u_hi | u_nom), one launch, one read-back (K | k | P0 | p0 | dV | status | n_cut | clamped), one
 // synchronize.  box: the call came through cimpc_plant_tape_lqr_box; every refusal leaves its reason for cimpc_last_error(NULL).
+// shoot: it came through cimpc_plant_tape_lqr_shooting, with defects ((T / seg_len - 1) x B x 2nq) behind u_nom in the upload.
 static int plant_tape_lqr_call(const char* entry, bool box, cimpc_plant_tape tape, int laps, int n_Q, const double* Q, const double* Qf, int n_R,
                                const double* R, const double* q, const double* r, int n_rho, const double* rho_b, int n_keep, double* K, double* k,
                                double* P0, double* p0, double* dV, int* status, int* n_cut, int n_lim, const double* u_lo, const double* u_hi,
-                               const double* u_nom, int* clamped) {
+                               const double* u_nom, int* clamped, bool shoot = false, int seg_len = 0, const double* defects = nullptr) {
     using namespace cimpc;
     auto refuse = [entry](const char* why) { set_global_error(std::string(entry) + ": " + why); return CIMPC_ERR_INVALID; };
     if (!tape || !Q || !Qf || !R || !K || !status || !n_cut || !rho_b) return refuse("a null tape, Q, Qf, R, K, status, n_cut or rho");
@@ -114,6 +135,12 @@ static int plant_tape_lqr_call(const char* entry, bool box, cimpc_plant_tape tap
     if (laps > 1 && q) return refuse("linear terms with laps > 1");       // a periodic chain has no linear terms
     if (!q && (k || p0 || dV)) return refuse("k, p0 or dV without q, r");
     const int B = tape->B, T = tape->T, n_cols = tape->n_cols;
+    if (shoot) {                                                          // what the defect hook needs, each by its own reason
+        if (!defects) return refuse("null defects");
+        if (!q || !r) return refuse("defects without q, r");
+        if (laps > 1) return refuse("defects with laps > 1");
+        if (seg_len < 1 || T % seg_len != 0) return refuse("T not divisible by segment_len");
+    }
     if (n_rho != 1 && n_rho != B) return refuse("n_rho neither 1 nor B");
     if (limits && n_lim != 1 && n_lim != B) return refuse("n_lim neither 1 nor B");
     for (int b = 0; b < n_rho; ++b)
@@ -138,6 +165,9 @@ static int plant_tape_lqr_call(const char* entry, bool box, cimpc_plant_tape tap
     if (limits)
         for (size_t e = 0; e < (size_t)T * B * nu; ++e)
             if (!std::isfinite(u_nom[e])) return refuse("a non-finite entry of u_nom");
+    const size_t i_def = shoot ? (size_t)(T / seg_len - 1) * B * 2 * nq : 0;
+    for (size_t e = 0; e < i_def; ++e)
+        if (!std::isfinite(defects[e])) return refuse("a non-finite entry of defects");
     const bool boxed = box && q;                                          // the limited chain: plant_riccati_kernel<true, true>
     const double rho = rho_b[0];
     const size_t n = (size_t)2 * nq, m = (size_t)nu, nn = n * n, mm = m * m, nB = (size_t)B;
@@ -145,7 +175,7 @@ static int plant_tape_lqr_call(const char* entry, bool box, cimpc_plant_tape tap
     const size_t i_Q = (size_t)n_Q * nn, i_R = (size_t)n_R * mm, i_q = q ? (size_t)(T + 1) * nB * n : 0, i_r = r ? (size_t)T * nB * m : 0;
     const size_t i_rho = boxed ? (size_t)n_rho : 0, i_lim = limits ? (size_t)n_lim * m : 0, i_un = limits ? (size_t)T * nB * m : 0;
     const size_t o_Qf = i_Q, o_R = o_Qf + nn, o_q = o_R + i_R, o_r = o_q + i_q, o_rho = o_r + i_r, o_lo = o_rho + i_rho, o_hi = o_lo + i_lim,
-                 o_un = o_hi + i_lim, n_in = o_un + i_un;
+                 o_un = o_hi + i_lim, o_def = o_un + i_un, n_in = o_def + i_def;
     const size_t n_K = (size_t)n_keep * nB * m * n, n_k = k ? (size_t)n_keep * nB * m : 0, n_P = P0 ? nB * nn : 0, n_p = p0 ? nB * n : 0,
                  n_V = dV ? nB * 2 : 0;
     const size_t o_k = n_K, o_P = o_k + n_k, o_p = o_P + n_P, o_V = o_p + n_p, o_st = o_V + n_V, o_cl = o_st + nB,      // 2 B ints in B doubles
@@ -163,7 +193,8 @@ static int plant_tape_lqr_call(const char* entry, bool box, cimpc_plant_tape tap
         std::memcpy(up.data() + o_hi, u_hi, i_lim * sizeof(double));
         std::memcpy(up.data() + o_un, u_nom, i_un * sizeof(double));
     }
-    const size_t lds = boxed ? plant_riccati_box_lds(nq, nu) : plant_riccati_lds(nq, nu);
+    if (i_def) std::memcpy(up.data() + o_def, defects, i_def * sizeof(double));
+    const size_t lds = shoot ? plant_riccati_shoot_lds(nq, nu) : boxed ? plant_riccati_box_lds(nq, nu) : plant_riccati_lds(nq, nu);
     std::lock_guard<std::mutex> lock(g_plant_mu);
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
@@ -186,7 +217,10 @@ static int plant_tape_lqr_call(const char* entry, bool box, cimpc_plant_tape tap
                 if (limits) { L.u_lo = I + o_lo; L.u_hi = I + o_hi; L.u_nom = I + o_un; L.n_lim = n_lim; }
                 if (clamped) L.clamped = reinterpret_cast<int*>(O + o_cl);
             }
-            if (boxed) {
+            if (shoot) {
+                L.defects = I + o_def; L.seg_len = seg_len;
+                ok = plant_riccati_shoot_launch(L, st);
+            } else if (boxed) {
                 ok = plant_riccati_box_launch(L, st);
             } else {
                 auto kernel = q ? plant_riccati_kernel<true> : plant_riccati_kernel<false>;
@@ -228,4 +262,15 @@ extern "C" int cimpc_plant_tape_lqr_box(cimpc_plant_tape tape, int laps, int n_Q
                                         const double* u_hi, const double* u_nom, int* clamped) {
     return plant_tape_lqr_call("cimpc_plant_tape_lqr_box", true, tape, laps, n_Q, Q, Qf, n_R, R, q, r, n_rho, rho, n_keep, K, k, P0, p0, dV, status,
                                n_cut, n_lim, u_lo, u_hi, u_nom, clamped);
+}
+
+// The limited pass with defects (multiple shooting): cimpc_plant_tape_lqr_box on a tape whose horizon is cut
+// into T / segment_len segments, with the defect of node j = 1 .. (defects, (T / segment_len - 1) x B x 2nq) entering the value's linear term
+// at the walk step of t = j segment_len - 1:  p <- p + P d.  Needs q, r and laps = 1.
+extern "C" int cimpc_plant_tape_lqr_shooting(cimpc_plant_tape tape, int n_Q, const double* Q, const double* Qf, int n_R, const double* R,
+                                             const double* q, const double* r, int n_rho, const double* rho, int n_keep, double* K, double* k,
+                                             double* P0, double* p0, double* dV, int* status, int* n_cut, int n_lim, const double* u_lo,
+                                             const double* u_hi, const double* u_nom, int* clamped, int segment_len, const double* defects) {
+    return plant_tape_lqr_call("cimpc_plant_tape_lqr_shooting", true, tape, 1, n_Q, Q, Qf, n_R, R, q, r, n_rho, rho, n_keep, K, k, P0, p0, dV, status,
+                               n_cut, n_lim, u_lo, u_hi, u_nom, clamped, true, segment_len, defects);
 }

@@ -37,6 +37,15 @@ tests/test_gpu_plant_mpc.py holds every control step to `ilqr(device_loop=True)`
 step N perturbed copies of the plan per robot in ONE open-loop rollout of N B robots, `TrackingCost` on each, and the best one (predictive
 sampling) or their softmax mean (MPPI) as the new plan - no tape and no gradient; `sampling_noise` gives the noise's bits on the host;
 tests/test_gpu_plant_sample.py holds every control step to the composition of those pieces bit for bit.
+`rollout_segments` is the first stage of multiple shooting (`cimpc_plant_rollout_segments`): the horizon cut into
+M segments that roll out abreast as M B robots for T / M steps, from nodes the caller gives (`segment_nodes` takes them from a trajectory); the
+`ShootingNominal` it returns carries the segments' rows, the defects at the nodes, optionally the cost on the segments' own rows
+(`TrackingCost.evaluate_segments` on the host) and an ordinary `RolloutTape`, whose `lqr(defects=, segment_len=)` is the backward pass with
+defects (`cimpc_plant_tape_lqr_shooting`) and whose gains `ShootingNominal.forward` runs through the affine dynamics (`cimpc_plant_shooting_forward`: the
+nodes' displacements and the quadratic model's two terms); `ShootingNominal.linesearch` rolls every step length of every segment out in ONE closed-loop
+rollout and accepts on the merit J + weight D (`cimpc_plant_shooting_linesearch`), and `ilqr_shooting` is the host loop over the four, which takes a
+STATE initial guess `q_guess`; tests/test_gpu_plant_shooting.py holds the calls to the calls and chains they are made of bit for bit and
+`ilqr_shooting(segments=1)` to `ilqr`.
 Parity: tests/test_gpu_plant.py against the CPU restatement of the same step, tests/test_gpu_plant_gradients.py against a longdouble
 solve, tests/test_gpu_plant_adjoint.py against restatements of the reverse chain, tests/test_gpu_plant_tangent.py against restatements of the forward chain,
 tests/test_gpu_plant_riccati.py against restatements of the backward pass, tests/test_gpu_plant_linesearch.py the line search against the
@@ -862,7 +871,8 @@ class RolloutTape:
         return np.ascontiguousarray(np.concatenate([q[:, t1], q[:, t1 + 1]], axis=2).transpose(1, 2, 0))
 
     # ---- the LQ backward pass ---------------------------------------------------------------------------------------------------------------
-    def lqr(self, Q, R, Qf=None, q=None, r=None, rho=0.0, laps: int = 1, keep=None, *, u_lo=None, u_hi=None, u_nom=None) -> "TapeGains":
+    def lqr(self, Q, R, Qf=None, q=None, r=None, rho=0.0, laps: int = 1, keep=None, *, u_lo=None, u_hi=None, u_nom=None, defects=None,
+            segment_len=None) -> "TapeGains":
         """Time-varying LQR gains along the trajectory this tape recorded (`cimpc_plant_tape_lqr`): ONE launch,
         a workgroup per robot walking the tape's blocks backwards; nothing but the weights goes up and the gains come down.  State
         x_t = [q[t]; q[t+1]] (n = 2nq), control u_t (m = nu), A_t = [0 I; D1 D2], B_t = [0; Du] from the step's block (on a closed-loop tape
@@ -877,16 +887,23 @@ class RolloutTape:
         applied.  Each step then solves min ½x'Gx + Qu'x over u_lo − u_nom[t] ≤ x ≤ u_hi − u_nom[t] by projected Newton: rows of K of the
         clamped controls are zero, k lies in the box, and `TapeGains.clamped` (keep, B) has bit i set where control i was clamped.  Both need
         q, r and laps = 1; a robot whose box QP did not converge gets status[b] like a singular step.  A scalar rho without limits is the
-        call it always was."""
+        call it always was.
+        THE PASS WITH DEFECTS (`cimpc_plant_tape_lqr_shooting`): on the tape of `rollout_segments`, defects
+        (M - 1, B, 2nq) and segment_len = L, both or neither, state the mismatch at the nodes t = j L, about which the dynamics are affine,
+        δx_{t+1} = A δx_t + B δu_t + d; the walk step of t = j L - 1 then starts from p + P d.  It is the limited pass otherwise (rho per robot
+        and limits work as there), needs q, r and laps = 1, and with all-zero defects gives that pass's K and k.  With None it is exactly the
+        call above."""
         if self.closed:
             raise ValueError("the tape is closed")
+        if (defects is None) != (segment_len is None):
+            raise ValueError("defects and segment_len go together")
         mid, nq, nu, nc, fd, nw = model_dims(self.model)
         B, T, n, m = self.B, self.T, 2 * nq, nu
         keep = T if keep is None else int(keep)
         rho_b = np.ascontiguousarray(rho, dtype=np.float64).reshape(-1) if np.ndim(rho) else None
         limited = u_lo is not None or u_hi is not None
-        if rho_b is not None or limited:
-            return self._lqr_box(Q, R, Qf, q, r, np.array([float(rho)]) if rho_b is None else rho_b, int(laps), keep, u_lo, u_hi, u_nom)
+        if rho_b is not None or limited or defects is not None:
+            return self._lqr_box(Q, R, Qf, q, r, np.array([float(rho)]) if rho_b is None else rho_b, int(laps), keep, u_lo, u_hi, u_nom, defects, segment_len)
         if (q is None) != (r is None):
             raise ValueError("q and r go together")
         if not 1 <= keep <= T:
@@ -930,12 +947,22 @@ class RolloutTape:
             raise ValueError(f"Qf must be ({n}, {n})")
         return Qc, n_Q, Rc, n_R, Qf
 
-    def _lqr_box(self, Q, R, Qf, q, r, rho, laps, keep, u_lo, u_hi, u_nom) -> "TapeGains":
-        """`lqr` through `cimpc_plant_tape_lqr_box`: rho (1,) or (B,), limits or None.  The library refuses what does not fit, by reason."""
+    def _lqr_box(self, Q, R, Qf, q, r, rho, laps, keep, u_lo, u_hi, u_nom, defects=None, segment_len=None) -> "TapeGains":
+        """`lqr` through `cimpc_plant_tape_lqr_box`: rho (1,) or (B,), limits or None; with defects through `cimpc_plant_tape_lqr_shooting`.  The
+        library refuses what does not fit, by reason."""
         mid, nq, nu, nc, fd, nw = model_dims(self.model)
         B, T, n, m = self.B, self.T, 2 * nq, nu
         if q is None or r is None:
-            raise ValueError("a rho per robot and control limits need the linear terms q and r")
+            raise ValueError("a rho per robot, control limits and defects need the linear terms q and r")
+        if defects is not None:
+            segment_len = int(segment_len)
+            if laps != 1:
+                raise ValueError("defects need laps = 1")
+            if segment_len < 1 or T % segment_len != 0:
+                raise ValueError(f"segment_len: T = {T} is not divisible by segment_len = {segment_len}")
+            defects = np.ascontiguousarray(defects, dtype=np.float64)
+            if defects.shape != (T // segment_len - 1, B, n):
+                raise ValueError(f"defects must be ({T // segment_len - 1}, {B}, {n}) for segment_len = {segment_len}, got {defects.shape}")
         if not 1 <= keep <= T:
             raise ValueError(f"keep must be in 1 .. {T}")
         if rho.size not in (1, B):
@@ -960,12 +987,20 @@ class RolloutTape:
         dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
         lib = _lib.load()
-        rc = lib.cimpc_plant_tape_lqr_box(self._handle, laps, n_Q, dp(Qc), dp(Qf), n_R, dp(Rc), dp(q), dp(r), int(rho.size), dp(rho), keep, dp(K), dp(k),
-                                          dp(P0), dp(p0), dp(dV), ip(status), ip(n_cut), n_lim, dp(u_lo), dp(u_hi), dp(u_nom), ip(clamped))
+        if defects is None:
+            entry = "cimpc_plant_tape_lqr_box"
+            rc = lib.cimpc_plant_tape_lqr_box(self._handle, laps, n_Q, dp(Qc), dp(Qf), n_R, dp(Rc), dp(q), dp(r), int(rho.size), dp(rho), keep, dp(K), dp(k),
+                                              dp(P0), dp(p0), dp(dV), ip(status), ip(n_cut), n_lim, dp(u_lo), dp(u_hi), dp(u_nom), ip(clamped))
+        else:
+            entry = "cimpc_plant_tape_lqr_shooting"
+            keep_alive = defects if defects.size else np.zeros(1)      # M = 1: no node, but the library asks for a pointer
+            rc = lib.cimpc_plant_tape_lqr_shooting(self._handle, n_Q, dp(Qc), dp(Qf), n_R, dp(Rc), dp(q), dp(r), int(rho.size), dp(rho), keep, dp(K), dp(k),
+                                                   dp(P0), dp(p0), dp(dV), ip(status), ip(n_cut), n_lim, dp(u_lo), dp(u_hi), dp(u_nom), ip(clamped),
+                                                   segment_len, dp(keep_alive))
         if rc == -1:
             raise ValueError(lib.cimpc_last_error(None).decode())
         if rc != 0:
-            raise _lib.CimpcError(f"cimpc_plant_tape_lqr_box failed ({rc})")
+            raise _lib.CimpcError(f"{entry} failed ({rc})")
         return TapeGains(K=np.ascontiguousarray(K.transpose(0, 1, 3, 2)), k=k, P0=np.ascontiguousarray(P0.transpose(0, 2, 1)), p0=p0, dV=dV,
                          status=status, n_cut=n_cut, N_sample=self._N_sample, K_blocks=K, clamped=clamped)
 
@@ -1152,6 +1187,34 @@ class TrackingCost:
             raise _lib.CimpcError(f"cimpc_plant_tracking_cost failed ({rc})")
         return J, lq, lr
 
+    def evaluate_segments(self, qs, u, segments: int):
+        """(J (B,), D (B,), defects (M - 1, B, 2nq), lin_q (T + 1, B, 2nq), lin_r (T, B, nu)) of the segment trajectories qs (L + 2, M B, nq) of a
+        multiple-shooting rollout (`rollout_segments`; csrc/plant_shooting.h) under the controls u (T, B, nu), T = M L: every stage on the rows of
+        the segment that owns its step, the defects where one segment ends less where the next starts, on the host
+        (`cimpc_plant_shooting_cost`) and bit for bit what `rollout_segments(cost=)` computes on the device.  With segments = 1 J, lin_q and
+        lin_r are `evaluate`'s."""
+        qs, u, M = np.ascontiguousarray(qs, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64), int(segments)
+        if qs.ndim != 3 or u.ndim != 3:
+            raise ValueError("qs must be (L + 2, M B, nq) and u (T, B, nu)")
+        (T, B, nu), nq = u.shape, qs.shape[2]
+        if M < 1 or T < 1 or T % M != 0:
+            raise ValueError(f"segments: T = {T} is not divisible by segments = {M}")
+        if qs.shape[:2] != (T // M + 2, M * B):
+            raise ValueError(f"qs must be ({T // M + 2}, {M * B}, nq) for u {u.shape} in {M} segments")
+        cc, keep = self._struct(nq, nu, B, T)
+        J, D, d, lq, lr = np.zeros(B), np.zeros(B), np.zeros((M - 1, B, 2 * nq)), np.zeros((T + 1, B, 2 * nq)), np.zeros((T, B, nu))
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        rc = _lib.load().cimpc_plant_shooting_cost(nq, nu, B, T, M, C.byref(cc), dp(qs), dp(u), dp(J), dp(D), dp(d), dp(lq), dp(lr))
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_shooting_cost failed ({rc}): {_last_error()}")
+        return J, D, d, lq, lr
+
+
+def _last_error() -> str:
+    """What the last refused call of this thread left for `cimpc_last_error(NULL)`."""
+    msg = _lib.load().cimpc_last_error(None)
+    return "" if msg is None else msg.decode(errors="replace")
+
 
 @dataclasses.dataclass
 class LineSearch:
@@ -1201,6 +1264,355 @@ def rollout_tape(model: str, q1, v1, u, h: float, mu, *, N_sample: int = 1, w=No
     tape._context = dict(mu=mua, w=w, w_hold=int(w_hold), terrain=terrain, opts=opts, steps_per_launch=int(steps_per_launch), grad_reg=reg)      # for `linesearch`
     out = (bool(r.status.all()), r.q, u_applied if loop is None else r.u_applied, r.gamma, r.b, r.status, r.iters, tape)
     return out if loop is None else out + (r.fb_err,)
+
+
+@dataclasses.dataclass
+class ShootingNominal:
+    """What `rollout_segments` returns (csrc/plant_shooting.h): the M segments of every robot's horizon, rolled out
+    abreast.  segments = M, L = T / M; qs (L + 2, M B, nq) the segments' trajectories, segment j of robot b being virtual robot j B + b and its
+    rows 0, 1 node j; nodes (M, B, 2nq) and u (T, B, nu) as given; gamma, b, status, iters in (T, B) layout, each step from the segment that owns
+    it; defects (M - 1, B, 2nq): where segment j - 1 ends less node j; D (B,) their absolute sum; tape: an ordinary `RolloutTape` of B robots and
+    T steps (`lqr`, `vjp` and `jvp` accept it).  With `cost=`: J (B,), lin_q (T + 1, B, 2nq), lin_r (T, B, nu) of the cost on the segments' own
+    rows, else None."""
+    segments: int
+    qs: np.ndarray
+    nodes: np.ndarray
+    u: np.ndarray
+    gamma: np.ndarray
+    b: np.ndarray
+    status: np.ndarray
+    iters: np.ndarray
+    defects: np.ndarray
+    D: np.ndarray
+    tape: "RolloutTape"
+    J: object = None
+    lin_q: object = None
+    lin_r: object = None
+
+    def forward(self, gains: "TapeGains", Q, R, Qf=None):
+        """The linear forward pass at alpha = 1 (`cimpc_plant_shooting_forward`; csrc/plant_shooting.h) with the gains of
+        `tape.lqr(Q, R, Qf, q=lin_q, r=lin_r, defects=self.defects, segment_len=L)`: dx_0 = 0, du_t = k_t - K_t dx_t,
+        dx_{t+1} = A_t dx_t + B_t du_t + d_{t+1}.  Needs `rollout_segments(cost=)`.  Returns (dx_nodes (M - 1, B, 2nq): what each node moves by per
+        unit step length; du (T, B, nu); dJ (B, 2): the quadratic model's two terms, the decrease it predicts for a full step being dJ1 + dJ2).
+        With one segment there is no node and nothing is launched: dJ is the backward pass's dV, as in `plant.ilqr`, and du its k."""
+        tape = self.tape
+        if tape.closed:
+            raise ValueError("the tape is closed")
+        if self.lin_q is None:
+            raise ValueError("forward needs the cost's linear terms: rollout_segments(cost=)")
+        mid, nq, nu, nc, fd, nw = model_dims(tape.model)
+        B, T, n, M = tape.B, tape.T, 2 * nq, self.segments
+        if gains.k is None or gains.K.shape != (T, B, nu, n) or gains.k.shape != (T, B, nu):
+            raise ValueError(f"forward needs the gains of every step with linear terms (lqr(q=, r=), keep = {T})")
+        if M == 1:
+            return np.zeros((0, B, n)), gains.k.copy(), gains.dV.copy()
+        Qc, n_Q, Rc, n_R, Qfc = tape._lqr_weights(Q, R, Qf, n, nu)
+        Kb = gains.K_blocks
+        if Kb is None or Kb.shape != (T, B, n, nu) or not np.array_equal(Kb.transpose(0, 1, 3, 2), gains.K):
+            Kb = np.ascontiguousarray(gains.K.transpose(0, 1, 3, 2))
+        cont = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        dxn, du, dJ = np.zeros((M - 1, B, n)), np.zeros((T, B, nu)), np.zeros((B, 2))
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        lib = _lib.load()
+        rc = lib.cimpc_plant_shooting_forward(tape._handle, n_Q, dp(Qc), dp(Qfc), n_R, dp(Rc), dp(cont(self.lin_q)), dp(cont(self.lin_r)), dp(cont(Kb)),
+                                              dp(cont(gains.k)), T // M, dp(cont(self.defects)), dp(dxn), dp(du), dp(dJ))
+        if rc == -1:
+            raise ValueError(lib.cimpc_last_error(None).decode())
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_shooting_forward failed ({rc})")
+        return dxn, du, dJ
+
+    def linesearch(self, gains: "TapeGains", cost: "TrackingCost", alphas, defect_weight, armijo: float = 1e-4, *, dx_nodes=None, dJ=None, phi_nom=None,
+                   u_lo=None, u_hi=None) -> "ShootingLineSearch":
+        """The line search of a multiple-shooting iteration (`cimpc_plant_shooting_linesearch`; csrc/plant_shooting.h): every step length of every
+        segment of every robot in ONE closed-loop rollout of n_alpha M B robots for L steps.  gains: `tape.lqr(..., defects=self.defects,
+        segment_len=L)` with every step's rows; dx_nodes, dJ: `self.forward(gains, ...)`'s (computed here with the cost's weights when not
+        given); defect_weight: a number or (B,), the nu of the merit phi = J + nu D; phi_nom (B,): the nominal's merit (default
+        self.J + nu self.D; -inf forces a rejection).  Candidate c of segment j starts from node j + alphas[c] dx_nodes[j - 1] and runs the
+        candidate law of `RolloutTape.linesearch` on its segment's rows; it is acceptable iff all its steps converged, phi_c is finite and
+        phi_c <= phi_nom + armijo (alpha (dJ1 - nu D_nom) + alpha^2 dJ2); the choice is the acceptable candidate of least phi.  Returns a
+        `ShootingLineSearch` whose `nominal` is the chosen candidates' `ShootingNominal` - the parent's rows and blocks for a robot without one.
+        With one segment it is `RolloutTape.linesearch` to the bit."""
+        tape = self.tape
+        if tape.closed:
+            raise ValueError("the tape is closed")
+        if self.lin_q is None:
+            raise ValueError("linesearch needs the nominal's cost: rollout_segments(cost=)")
+        mid, nq, nu, nc, fd, nw = model_dims(tape.model)
+        B, T, n, M, nb = tape.B, tape.T, 2 * nq, self.segments, fd * nc
+        L = T // M
+        if gains.k is None or gains.K.shape != (T, B, nu, n) or gains.k.shape != (T, B, nu):
+            raise ValueError(f"linesearch needs the gains of every step with linear terms (lqr(q=, r=), keep = {T})")
+        cont = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        alphas = cont(alphas).reshape(-1)
+        if not 1 <= alphas.size <= 64 or not np.isfinite(alphas).all():
+            raise ValueError("alphas: 1 to 64 finite step lengths")
+        if not armijo >= 0.0:
+            raise ValueError("armijo must not be negative")
+        weight = cont(defect_weight).reshape(-1)
+        if weight.size not in (1, B) or not (np.isfinite(weight).all() and (weight >= 0.0).all()):
+            raise ValueError(f"defect_weight: a finite number that is not negative, or one per robot ({B})")
+        if dx_nodes is None or dJ is None:
+            dx_nodes, _, dJ = self.forward(gains, cost.Q, cost.R, cost.Qf)
+        dx_nodes, dJ = cont(dx_nodes), cont(dJ)
+        if dx_nodes.shape != (M - 1, B, n) or dJ.shape != (B, 2):
+            raise ValueError(f"dx_nodes must be ({M - 1}, {B}, {n}) and dJ ({B}, 2)")
+        phi0 = self.J + np.broadcast_to(weight, (B,)) * self.D
+        phi_nom = cont(phi0 if phi_nom is None else phi_nom).reshape(-1)
+        if phi_nom.shape != (B,):
+            raise ValueError(f"phi_nom must be ({B},)")
+        ctx = dict(getattr(tape, "_context", None) or {})
+        opts, terrain = ctx.get("opts", SIM_OPTS), ctx.get("terrain")
+        mua = cont(ctx["mu"]).reshape(-1)
+        wa = None if ctx.get("w") is None else np.ascontiguousarray(_schedule(ctx["w"], B, nw, "w"))
+        reg = _grad_args(tape.model, opts, ctx.get("grad_reg"), tape.n_cols)[0]
+        Kb = gains.K_blocks
+        if Kb is None or Kb.shape != (T, B, n, nu) or not np.array_equal(Kb.transpose(0, 1, 3, 2), gains.K):
+            Kb = np.ascontiguousarray(gains.K.transpose(0, 1, 3, 2))
+        cc, keep = cost._struct(nq, nu, B, T)
+        na = alphas.size
+        J, Dc, phi = np.zeros((na, B)), np.zeros((na, B)), np.zeros((na, B))
+        ok, choice = np.zeros((na, B), dtype=np.int32), np.zeros(B, dtype=np.int32)
+        qs, cu, cg, cb = np.zeros((L + 2, M * B, nq)), np.zeros((T, B, nu)), np.zeros((T, B, nc)), np.zeros((T, B, nb))
+        st, it, gst = (np.zeros((T, B), dtype=np.int32) for _ in range(3))
+        d, D, Jn, lq, lr = np.zeros((M - 1, B, n)), np.zeros(B), np.zeros(B), np.zeros((T + 1, B, n)), np.zeros((T, B, nu))
+        o = _lib.IpOpts(**dataclasses.asdict(opts))
+        dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+        pad = lambda a: a if a.size else np.zeros(1)      # one segment: no node, but the library asks for a pointer
+        ta, nt = (None, 0) if terrain is None else _terrain_array(terrain, B)
+        lo, hi = _limit_arrays(u_lo, u_hi, B, nu)
+        handle = C.c_void_p()
+        lib = _lib.load()
+        dxp, dfp = pad(dx_nodes), pad(d)
+        rc = lib.cimpc_plant_shooting_linesearch(
+            tape._handle, M, int(ctx.get("steps_per_launch", 0)), nt, ta, dp(cont(self.qs)), dp(cont(self.u)), dp(wa), 1 if wa is None else wa.shape[0],
+            1 if wa is None else wa.shape[1], int(ctx.get("w_hold", 1)), dp(mua), mua.size, float(tape._h), C.byref(o), dp(cont(Kb)), dp(cont(gains.k)), dp(dxp),
+            dp(dJ), dp(phi_nom), dp(cont(self.D)), weight.size, dp(weight), na, dp(alphas), float(armijo), C.byref(cc), reg, dp(J), dp(Dc), dp(phi), ip(ok),
+            ip(choice), dp(qs), dp(cu), dp(cg), dp(cb), ip(st), ip(it), dp(dfp), dp(D), dp(Jn), dp(lq), dp(lr), ip(gst), C.byref(handle),
+            1 if lo is None else lo.shape[0], dp(lo), dp(hi))
+        if rc == -1:
+            raise ValueError(lib.cimpc_last_error(None).decode())
+        if rc != 0:
+            raise _lib.CimpcError(f"cimpc_plant_shooting_linesearch failed ({rc})")
+        if M > 1:
+            d = dfp
+        new_tape = RolloutTape(handle, tape.model, gst, None, tape._v1, tape._h, (T, B, nu), 1, tape._w_shape, tape._w_hold, tape._mu_shared,
+                               q1_shape=tape._q1_shape, mu_shape=tape._mu_shape)
+        new_tape._context = ctx
+        none = choice < 0
+        if none.any():      # the parent's rows for the robots that keep their trajectory
+            cols = (np.arange(M)[:, None] * B + np.nonzero(none)[0][None, :]).reshape(-1)
+            qs[:, cols] = self.qs[:, cols]
+            for mine, theirs in ((cu, self.u), (cg, self.gamma), (cb, self.b), (st, self.status), (it, self.iters), (lq, self.lin_q), (lr, self.lin_r), (d, self.defects)):
+                mine[:, none] = theirs[:, none]
+            D[none], Jn[none] = self.D[none], self.J[none]
+        nodes = np.ascontiguousarray(np.concatenate([qs[0], qs[1]], axis=1).reshape(M, B, n))
+        nominal = ShootingNominal(segments=M, qs=qs, nodes=nodes, u=cu, gamma=cg, b=cb, status=st, iters=it, defects=d, D=D, tape=new_tape, J=Jn, lin_q=lq, lin_r=lr)
+        return ShootingLineSearch(J=J, D=Dc, phi=phi, ok=ok.astype(bool), choice=choice, alphas=alphas, nominal=nominal)
+
+    def q_stitched(self):
+        """(T + 2, B, nq): row t < T from the segment that owns step t, rows T and T + 1 the last segment's end.  Continuous where the defects are zero."""
+        M, B = self.segments, self.nodes.shape[1]
+        L = self.qs.shape[0] - 2
+        per = self.qs.reshape(L + 2, M, B, -1)
+        return np.concatenate([per[:L].transpose(1, 0, 2, 3).reshape(M * L, B, -1), per[L:, M - 1]], axis=0)
+
+
+@dataclasses.dataclass
+class ShootingLineSearch:
+    """What `ShootingNominal.linesearch` returns: J, D and phi (n_alpha, B) of every candidate - its cost, its own defects' sum, its merit -,
+    ok (n_alpha, B), choice (B,) (-1: none acceptable), alphas, and nominal: the chosen candidates as a `ShootingNominal` with their tape (the
+    parent's rows and blocks for a robot whose choice is -1)."""
+    J: np.ndarray
+    D: np.ndarray
+    phi: np.ndarray
+    ok: np.ndarray
+    choice: np.ndarray
+    alphas: np.ndarray
+    nominal: ShootingNominal
+
+
+@dataclasses.dataclass
+class ShootingResult:
+    """What `ilqr_shooting` returns: `ILQRResult`'s fields - the final u (T, B, nu), q (T + 2, B, nq) stitched from the segments, gamma, b; per
+    iteration J, alpha, rho, accepted; J0; tape and gains - plus phi and D (n_iter, B), the merit and the defects' sum after each iteration,
+    phi0 and D0 (B,) the first nominal's, nodes (M, B, 2nq) the final ones, and nominal, the final `ShootingNominal`."""
+    u: np.ndarray
+    q: np.ndarray
+    gamma: np.ndarray
+    b: np.ndarray
+    J: np.ndarray
+    alpha: np.ndarray
+    rho: np.ndarray
+    accepted: np.ndarray
+    J0: np.ndarray
+    tape: "RolloutTape"
+    gains: object
+    phi: np.ndarray
+    D: np.ndarray
+    phi0: np.ndarray
+    D0: np.ndarray
+    nodes: np.ndarray
+    nominal: ShootingNominal
+
+
+def ilqr_shooting(model: str, q1, v1, u, h: float, mu, cost: "TrackingCost", *, segments: int, defect_weight=None, defect_tol=None, q_guess=None,
+                  alphas=(1.0, 0.5, 0.25, 0.125), max_iter: int = 10, rho0: float = 1e-6, rho_factor: float = 10.0, rho_max: float = 1e6, tol: float = 1e-6,
+                  armijo: float = 1e-4, w=None, w_hold: int = 1, opts: InteriorPointOptions = SIM_OPTS, terrain=None, steps_per_launch: int = 0, grad_reg=None,
+                  grad_cols=None, u_lo=None, u_hi=None) -> ShootingResult:
+    """Multiple-shooting iLQR through contact on the device plant (Giftthaler et al. 2018): the horizon cut into
+    `segments` = M pieces whose start states, the nodes, are decision variables beside the controls.  A host loop over the device calls: per
+    iteration `rollout_segments`' tape gives `lqr(defects=)` (one limited launch with the per-robot rho), `ShootingNominal.forward` the nodes'
+    displacements and the model's two terms, `ShootingNominal.linesearch` every step length of every segment in one rollout, and the chosen
+    candidates become the nominal.  The bookkeeping is `ilqr`'s with the merit phi = J + defect_weight D in the place of J, and a robot stops
+    only once its gaps are closed: small = accepted and (phi - phi_new < tol |phi|) and (D_new <= defect_tol).
+    q_guess (T + 2, B, nq): a STATE initial guess - a reference gait, the previous plan's states -, whose rows j L, j L + 1 become the nodes
+    j >= 1 (node 0 is the measured state q1 - h v1, q1); with None the nodes are those of a sequential `rollout_tape` under u: no defect, the
+    start of `ilqr`.  defect_weight (a number or (B,)) and defect_tol have NO default when segments > 1 - nothing here measures a good one -
+    and are refused by name when missing; with segments = 1 both are ignored, and the result is `ilqr`'s host loop to the bit."""
+    M = int(segments)
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    if M < 1:
+        raise ValueError("segments must be at least 1")
+    if M > 1 and defect_weight is None:
+        raise ValueError("defect_weight: required with segments > 1 (the weight of the defects in the merit J + defect_weight D has no default)")
+    if M > 1 and defect_tol is None:
+        raise ValueError("defect_tol: required with segments > 1 (the largest D a finished robot may keep has no default)")
+    weight = np.zeros(1) if M == 1 else np.ascontiguousarray(defect_weight, dtype=np.float64).reshape(-1)
+    d_tol = np.inf if M == 1 else float(defect_tol)
+    q1a, v1a = np.atleast_2d(np.asarray(q1, dtype=np.float64)), np.atleast_2d(np.asarray(v1, dtype=np.float64))
+    B = q1a.shape[0]
+    limited = u_lo is not None or u_hi is not None
+    if limited:
+        u = np.asarray(u, dtype=np.float64)
+        lo, hi = _limit_arrays(u_lo, u_hi, B, nu)
+        if u.ndim == 2:
+            u = u if lo.shape[0] == 1 else np.repeat(u[:, None], lo.shape[0], axis=1)
+        u = np.where(u < lo, lo, np.where(u > hi, hi, u))
+    ua = np.ascontiguousarray(np.broadcast_to(_schedule(u, B, nu, "u"), (np.shape(u)[0], B, nu)))
+    T = ua.shape[0]
+    if T % M != 0:
+        raise ValueError(f"segments: T = {T} is not divisible by segments = {M}")
+    L = T // M
+    kw = dict(w=w, w_hold=w_hold, opts=opts, terrain=terrain, steps_per_launch=steps_per_launch, grad_reg=grad_reg, grad_cols=grad_cols)
+    if q_guess is None:
+        ok, q_seq, *_, t0 = rollout_tape(model, q1a, v1a, ua, h, mu, **kw)
+        t0.close()
+        nodes = segment_nodes(q_seq, M)
+    else:
+        q_guess = np.asarray(q_guess, dtype=np.float64)
+        if q_guess.shape != (T + 2, B, nq):
+            raise ValueError(f"q_guess must be ({T + 2}, {B}, {nq}), got {q_guess.shape}")
+        nodes = segment_nodes(q_guess, M)
+        nodes[0] = np.concatenate([q1a - h * v1a, q1a], axis=1)      # node 0 is the measured state and never moves
+    nom = rollout_segments(model, nodes, ua, h, mu, segments=M, cost=cost, **kw)
+    hist = dict(J=[], alpha=[], rho=[], accepted=[], phi=[], D=[])
+    gains = None
+    wB = np.broadcast_to(weight, (B,))
+    try:
+        phi = nom.J + wB * nom.D
+        J0, phi0, D0 = nom.J.copy(), phi.copy(), nom.D.copy()
+        level, active = np.zeros(B, dtype=np.int64), np.ones(B, dtype=bool)
+        for _ in range(int(max_iter)):
+            rho = rho0 * float(rho_factor) ** level
+            gains = nom.tape.lqr(cost.Q, cost.R, cost.Qf, q=nom.lin_q, r=nom.lin_r, rho=rho, u_lo=u_lo, u_hi=u_hi, u_nom=nom.u if limited else None,
+                                 defects=nom.defects, segment_len=L)
+            good = gains.status == 0
+            if not good.all():      # a chain that ended early left zeros: nothing to run forward for that robot, which is rejected below
+                gains = dataclasses.replace(gains, K=np.where(good[None, :, None, None], gains.K, 0.0), k=np.where(good[None, :, None], gains.k, 0.0), K_blocks=None)
+            dxn, _, dJ = nom.forward(gains, cost.Q, cost.R, cost.Qf)
+            ls = nom.linesearch(gains, cost, alphas, weight, armijo, dx_nodes=dxn, dJ=dJ, phi_nom=np.where(active & good, phi, -np.inf), u_lo=u_lo, u_hi=u_hi)
+            accepted = ls.choice >= 0
+            pick = (np.maximum(ls.choice, 0), np.arange(B))
+            phi_new, new = np.where(accepted, ls.phi[pick], phi), ls.nominal
+            hist["J"].append(new.J.copy()); hist["rho"].append(rho); hist["accepted"].append(accepted); hist["phi"].append(phi_new); hist["D"].append(new.D.copy())
+            hist["alpha"].append(np.where(accepted, ls.alphas[np.maximum(ls.choice, 0)], np.nan))
+            small = accepted & (phi - phi_new < tol * np.abs(phi)) & (new.D <= d_tol)
+            level = np.where(accepted, np.maximum(level - 1, 0), np.where(active, level + 1, level))
+            active = active & ~small & (rho0 * float(rho_factor) ** level <= rho_max)
+            nom.tape.close()
+            nom, phi = new, phi_new
+            if not active.any():
+                break
+    except BaseException:
+        nom.tape.close()
+        raise
+    n_it = len(hist["J"])
+    stack = lambda key, dt: np.array(hist[key], dtype=dt).reshape(n_it, B)
+    return ShootingResult(u=nom.u, q=nom.q_stitched(), gamma=nom.gamma, b=nom.b, J=stack("J", np.float64), alpha=stack("alpha", np.float64),
+                          rho=stack("rho", np.float64), accepted=stack("accepted", bool), J0=J0, tape=nom.tape, gains=gains, phi=stack("phi", np.float64),
+                          D=stack("D", np.float64), phi0=phi0, D0=D0, nodes=nom.nodes, nominal=nom)
+
+
+def segment_nodes(q, segments: int):
+    """The nodes (M, B, 2nq) a trajectory q (T + 2, B, nq) passes through: node j = [q[j L]; q[j L + 1]].  On a sequential rollout's q they give
+    `rollout_segments` zero defects."""
+    q, M = np.asarray(q, dtype=np.float64), int(segments)
+    T = q.shape[0] - 2
+    if q.ndim != 3 or M < 1 or T < 1 or T % M != 0:
+        raise ValueError(f"segments: q must be (T + 2, B, nq) with T divisible by segments = {M}")
+    L = T // M
+    return np.ascontiguousarray(np.concatenate([q[0:T:L], q[1:T + 1:L]], axis=2))
+
+
+def rollout_segments(model: str, nodes, u, h: float, mu, *, segments: int, w=None, w_hold: int = 1, terrain=None, opts: InteriorPointOptions = SIM_OPTS,
+                     grad_reg=None, grad_cols=None, steps_per_launch: int = 0, cost: "TrackingCost" = None) -> ShootingNominal:
+    """A multiple-shooting rollout (`cimpc_plant_rollout_segments`): the horizon of T steps cut into `segments` = M
+    pieces of L = T / M steps, all rolled out at once as M B robots for L steps - the card is filled along time, and the call takes the time of
+    L steps where `rollout_tape` takes that of T.  nodes (M, B, 2nq): [q[0]; q[1]] each segment starts from, node 0 the measured state
+    (`segment_nodes` takes them from a trajectory); u (T, nu) or (T, B, nu), applied as it stands; w, w_hold, mu, terrain, opts, grad_reg,
+    grad_cols as `rollout_tape` takes them, step l of segment j reading the rows of global step j L + l.  Every step is bit for bit `rollout`'s
+    for that virtual robot and every block `sensitivity`'s; the result is a `ShootingNominal`.  cost: a `TrackingCost`, whose J, lin_q and lin_r on
+    the segments' rows are then computed on the device too."""
+    if terrain is None and model in TERRAIN_MODELS:
+        terrain = "flat_2D_lc"
+    mid, nq, nu, nc, fd, nw = model_dims(model)
+    M = int(segments)
+    nodes = np.ascontiguousarray(nodes, dtype=np.float64)
+    if M < 1:
+        raise ValueError("segments must be at least 1")
+    if nodes.ndim != 3 or nodes.shape[0] != M or nodes.shape[2] != 2 * nq:
+        raise ValueError(f"nodes must be (segments, B, {2 * nq}) = ({M}, B, {2 * nq}), got {nodes.shape}")
+    if not np.isfinite(nodes).all():
+        raise ValueError("nodes: a non-finite entry")
+    B = nodes.shape[1]
+    ua = _schedule(u, B, nu, "u")
+    T = ua.shape[0]
+    if T % M != 0:
+        raise ValueError(f"segments: T = {T} is not divisible by segments = {M}")
+    L, nb = T // M, fd * nc
+    ua = np.ascontiguousarray(np.broadcast_to(ua, (T, B, nu)))
+    if int(w_hold) < 1:
+        raise ValueError("w_hold must be at least 1")
+    wa = None if w is None else np.ascontiguousarray(_schedule(w, B, nw, "w"))
+    mua = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
+    if mua.size not in (1, B):
+        raise ValueError(f"mu: one friction coefficient or one per robot ({B}), got {mua.size}")
+    reg, n_cols = _grad_args(model, opts, grad_reg, grad_cols)
+    if n_cols < 2 * nq + nu:
+        raise ValueError(f"grad_cols must be at least {2 * nq + nu} (q0, q1 and u1) for a tape")
+    qs, g, b = np.zeros((L + 2, M * B, nq)), np.zeros((T, B, nc)), np.zeros((T, B, nb))
+    st, it, gst = (np.zeros((T, B), dtype=np.int32) for _ in range(3))
+    d, D = np.zeros((M - 1, B, 2 * nq)), np.zeros(B)
+    J, lq, lr = (np.zeros(B), np.zeros((T + 1, B, 2 * nq)), np.zeros((T, B, nu))) if cost is not None else (None, None, None)
+    cc, keep = (None, None) if cost is None else cost._struct(nq, nu, B, T)
+    o = _lib.IpOpts(**dataclasses.asdict(opts))
+    dp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    ta, nt = (None, 0) if terrain is None else _terrain_array(terrain, B)
+    handle = C.c_void_p()
+    rc = _lib.load().cimpc_plant_rollout_segments(
+        mid, B, T, M, int(steps_per_launch), nt, ta, dp(nodes), dp(ua), dp(wa), 1 if wa is None else wa.shape[0], 1 if wa is None else wa.shape[1],
+        int(w_hold), dp(mua), mua.size, float(h), C.byref(o), None if cc is None else C.byref(cc), reg, n_cols, dp(qs), dp(g), dp(b), ip(st), ip(it),
+        dp(d), dp(D), dp(J), dp(lq), dp(lr), ip(gst), C.byref(handle))
+    if rc != 0:
+        raise _lib.CimpcError(f"cimpc_plant_rollout_segments failed ({rc}): {_last_error()}")
+    v1 = (nodes[0, :, nq:] - nodes[0, :, :nq]) / h
+    tape = RolloutTape(handle, model, gst, None, v1, float(h), (T, B, nu), 1, None if w is None else np.shape(w), int(w_hold),
+                       np.ndim(mu) == 0 or (mua.size == 1 and B > 1), q1_shape=(B, nq), mu_shape=np.shape(mu))
+    tape._context = dict(mu=mua, w=w, w_hold=int(w_hold), terrain=terrain, opts=opts, steps_per_launch=int(steps_per_launch), grad_reg=reg)
+    return ShootingNominal(segments=M, qs=qs, nodes=nodes, u=ua, gamma=g, b=b, status=st, iters=it, defects=d, D=D, tape=tape, J=J, lin_q=lq, lin_r=lr)
 
 
 @dataclasses.dataclass

@@ -904,6 +904,86 @@ int cimpc_plant_sampler_dims(cimpc_plant_sampler handle, int* model, int* B, int
 int cimpc_plant_sampler_destroy(cimpc_plant_sampler handle);
 int cimpc_plant_sample_noise(unsigned long long seed, unsigned int draw, int B, int N, int n_rows, int nu, double* eps);
 
+/* ---- multiple shooting: the segments of a horizon rolled out abreast (csrc/plant_shooting.h) ---------------
+ * The horizon of T steps is cut into `segments` = M pieces of L = T / M steps.  Segment j of robot b is virtual robot r = j B + b of ONE
+ * open-loop rollout of M B robots for L steps: it starts from node j, nodes[j, b] = [q[0]; q[1]] of that segment (2nq numbers), and its step
+ * l reads the inputs of global step t = j L + l - u[t, b], the w row t / hold_w (the last one held), and mu and terrain of robot b.  Every
+ * step is bit for bit the step cimpc_plant_rollout makes for that virtual robot, and its block the one cimpc_plant_rollout_grad gives.
+ *   qs       (L + 2) x (M B) x nq: the segments' trajectories, rows 0 and 1 of virtual robot r being node j
+ *   gamma, b, status, iters, grad_status   in (T, B) layout: global step t of robot b, each taken from the segment that owns the step
+ *   defects  (M - 1) x B x 2nq (not written with M = 1): d_j = [qs[L, (j-1) B + b]; qs[L+1, (j-1) B + b]] - nodes[j, b], where segment j-1
+ *            ends less where segment j starts;  D (B) = sum_j sum_i |d_j[i]|, ascending j then i, one running sum
+ *   cost     may be NULL; else J (B), lin_q ((T+1) x B x 2nq) and lin_r (T x B x nu) are written: stage t of the tracking cost on rows l, l+1
+ *            of the segment that owns step t with the goals and weights of global step t, the terminal stage on rows L, L+1 of the last
+ *            segment, J = ((l_0 + l_1) + ...) + l_T in ascending global t.  With M = 1 these are cimpc_plant_tracking_cost's bits.
+ *   tape     an ordinary cimpc_plant_tape of B robots and T steps whose block t is the block of the segment step that owns t:
+ *            cimpc_plant_tape_lqr, _vjp and _jvp accept it.  With nodes taken from a sequential rollout every defect is 0.0 and the tape
+ *            is cimpc_plant_rollout_tape's bit for bit.
+ * CIMPC_ERR_INVALID before any device is touched, the reason left for cimpc_last_error(NULL) and *tape NULL: a null pointer (terrain, w,
+ * cost and its three outputs excepted); segments below 1; T not divisible by segments; a non-finite entry of nodes; a model without
+ * controls; what cimpc_plant_rollout_tape refuses for B robots over T steps with u as a T x B x nu schedule; what
+ * cimpc_plant_tracking_cost refuses of the cost.
+ *
+ * cimpc_plant_shooting_cost: host only, no device - J, D (B each), defects, lin_q, lin_r (each may be NULL) of segment trajectories qs with
+ * the controls u (T x B x nu), bit for bit what cimpc_plant_rollout_segments computes on the device. */
+int cimpc_plant_rollout_segments(int model, int B, int T, int segments, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                 const double* nodes, const double* u, const double* w, int K_w, int n_w, int hold_w, const double* mu,
+                                 int n_mu, double h, const cimpc_ip_opts* opts, const cimpc_tracking_cost* cost, double reg, int n_cols,
+                                 double* qs, double* gamma, double* b, int* status, int* iters, double* defects, double* D, double* J,
+                                 double* lin_q, double* lin_r, int* grad_status, cimpc_plant_tape* tape);
+/* cimpc_plant_tape_lqr_shooting: the backward pass with defects, on the tape of cimpc_plant_rollout_segments.  It is cimpc_plant_tape_lqr_box with
+ * laps = 1 (rho per robot, limits, u_nom and clamped as there; q and r are required) and one hook: with segment_len = L and defects
+ * ((T / L - 1) x B x 2nq, d_j at node t = j L) the dynamics about the segments' trajectories are affine at a node,
+ * dx_{t+1} = A dx_t + B du_t + d_{t+1}, and at the top of the walk step of t, if t + 1 is a node, the value's linear term becomes
+ * p + P d:  (P d)[c] = sum_k P[c, k] d[k], one running sum over ascending k from 0.0, then one rounded sum with p[c]
+ * (csrc/plant_riccati.h).  With every defect 0.0, K and k are cimpc_plant_tape_lqr_box's.  A kernel of its own runs it; the
+ * kernels of cimpc_plant_tape_lqr and cimpc_plant_tape_lqr_box are untouched.  Also CIMPC_ERR_INVALID, each with its reason: null defects;
+ * defects without q, r; T not divisible by segment_len (or segment_len below 1); a non-finite entry of defects. */
+int cimpc_plant_tape_lqr_shooting(cimpc_plant_tape tape, int n_Q, const double* Q, const double* Qf, int n_R, const double* R,
+                                  const double* q, const double* r, int n_rho, const double* rho, int n_keep, double* K, double* k,
+                                  double* P0, double* p0, double* dV, int* status, int* n_cut, int n_lim, const double* u_lo,
+                                  const double* u_hi, const double* u_nom, int* clamped, int segment_len, const double* defects);
+/* cimpc_plant_shooting_forward: the linear forward pass of one multiple-shooting iteration at alpha = 1, over the tape's blocks (A_t = [0 I; D1 D2],
+ * B_t = [0; Du]; a cut step's block is zero) with the gains K (T x B x (m x n), column-major as cimpc_plant_tape_lqr writes them with n_keep = T)
+ * and k (T x B x m) of cimpc_plant_tape_lqr_shooting and the defects of its call:  dx_0 = 0,  du_t = k_t - K_t dx_t,
+ * dx_{t+1} = A_t dx_t + B_t du_t + d_{t+1} (d at the nodes t + 1 = j segment_len alone).  Out: dx_nodes ((T / segment_len - 1) x B x n), dx at the
+ * nodes - what a candidate's node moves by per unit step length; du (T x B x m, may be NULL); dJ (B x 2), the two terms of the quadratic model,
+ * dJ1 = sum_t (lin_q[t].dx_t + lin_r[t].du_t) + lin_q[T].dx_T and dJ2 = 1/2 sum_t (dx_t'Q_t dx_t + du_t'R_t du_t) + 1/2 dx_T'Qf dx_T.  Every sum
+ * is one ordered chain (csrc/plant_shooting.h), so the result does not depend on the batch.  ONE launch, a workgroup per robot.
+ * CIMPC_ERR_INVALID with its reason before any device is touched: a null pointer (du excepted); a closed tape; T not divisible by
+ * segment_len; n_Q or n_R neither 1 nor T; a non-finite entry of K, k or defects. */
+int cimpc_plant_shooting_forward(cimpc_plant_tape tape, int n_Q, const double* Q, const double* Qf, int n_R, const double* R, const double* lin_q,
+                                 const double* lin_r, const double* K, const double* k, int segment_len, const double* defects,
+                                 double* dx_nodes, double* du, double* dJ);
+/* cimpc_plant_shooting_linesearch: the line search of a multiple-shooting iteration - n_alpha step lengths of every segment of every robot in ONE
+ * closed-loop rollout of n_alpha M B robots for L = T / M steps.  `tape` is the parent, the stitched tape of the nominal qs_nom ((L+2) x (M B) x nq)
+ * whose steps applied u_nom (T x B x nu); K, k are cimpc_plant_tape_lqr_shooting's (n_keep = T), dx_nodes and dJ cimpc_plant_shooting_forward's
+ * (with one segment: no node, dJ = the backward pass's dV); phi_nom (B) the nominal's merit J + weight D, D_nom (B) its D; weight: n_weight (1 or B)
+ * defect weights, each >= 0 and finite.  Candidate c of segment j of robot b is rollout robot (c M + j) B + b: it starts from node j moved by
+ * alpha[c] dx_nodes[j-1, b] (one rounded product and one rounded sum per entry; node 0 as it stands) and runs cimpc_plant_tape_linesearch_box's
+ * candidate law on its segment's own rows - limit(u_nom + alpha k), gains K, x_ref from the segment's parent rows - with the inputs of global step
+ * j L + l.  J (n_alpha x B): the cost on the candidate's own segments in global order with the controls its steps applied; D_cand: its own
+ * defects' absolute sum; phi = J + weight D_cand.  A candidate is acceptable iff all its M L steps converged, phi is finite and
+ * phi <= phi_nom + armijo (alpha (dJ1 - weight D_nom) + alpha^2 dJ2); choice (B): the acceptable candidate of least phi, the lower index on a
+ * tie, -1 if none.  With one segment these are cimpc_plant_tape_linesearch_box's bits.  The chosen candidate's M segments come back compacted as
+ * cimpc_plant_rollout_segments returns a rollout - qs, and u_applied, gamma, b, status, iters in (T, B) layout, defects, D, J_chosen, lin_q, lin_r -
+ * (candidate 0's where choice = -1: the caller keeps the nominal's there) with new_tape, made by ONE sensitivity launch over the chosen L x M B
+ * entries and stitched; a robot without an acceptable candidate has the parent's blocks in it.
+ * CIMPC_ERR_INVALID with its reason before any device is touched: a null pointer (terrain, w and the limits excepted); what
+ * cimpc_plant_tape_linesearch_box refuses of alpha, armijo and the limits; a closed tape; T not divisible by segments; n_weight neither 1 nor B,
+ * a weight that is negative or not finite; what cimpc_plant_rollout_segments refuses of the rollout's arguments; a non-finite entry of K, k,
+ * qs_nom, u_nom or dx_nodes. */
+int cimpc_plant_shooting_linesearch(cimpc_plant_tape tape, int segments, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
+                                    const double* qs_nom, const double* u_nom, const double* w, int K_w, int n_w, int hold_w, const double* mu,
+                                    int n_mu, double h, const cimpc_ip_opts* opts, const double* K, const double* k, const double* dx_nodes,
+                                    const double* dJ, const double* phi_nom, const double* D_nom, int n_weight, const double* weight,
+                                    int n_alpha, const double* alpha, double armijo, const cimpc_tracking_cost* cost, double reg, double* J,
+                                    double* D_cand, double* phi, int* ok, int* choice, double* qs, double* u_applied, double* gamma, double* b,
+                                    int* status, int* iters, double* defects, double* D, double* J_chosen, double* lin_q, double* lin_r,
+                                    int* grad_status, cimpc_plant_tape* new_tape, int n_lim, const double* u_lo, const double* u_hi);
+int cimpc_plant_shooting_cost(int nq, int nu, int B, int T, int segments, const cimpc_tracking_cost* cost, const double* qs, const double* u,
+                              double* J, double* D, double* defects, double* lin_q, double* lin_r);
+
 /* ---- cimpc_set_linearization_batch from (z, theta) alone: plant model `model` linearized at kappa (cimpc_plant_linearize's kernel and arguments;
  * z0 = z, th0 = theta) and the tables built from its output, all on the handle's device and stream;
  * nothing but z, theta and the terrains goes up, nothing but N status words comes back.  Equal bit for bit to

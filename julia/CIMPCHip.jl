@@ -1651,6 +1651,219 @@ function plant_sample_noise(seed::Integer, draw::Integer, B::Int, N::Int, n_rows
     return eps
 end
 
+# ---- multiple shooting: the segments of a horizon rolled out abreast (DESIGN.md section 3, item 3l; csrc/plant_shooting.h) --------------
+# Unexecuted, like the rest of this binding: written against include/cimpc.h and checked against its prototypes by text only.
+"""
+    plant_rollout_segments(model, nodes, u, μ, h_sim, opts; cost = nothing, w = nothing, w_hold = 1, terrain = nothing,
+                           steps_per_launch = 0, grad_reg = nothing, grad_cols = nothing)
+        -> (qs, γ, b, status, iters, defects, D, J, lin_q, lin_r, tape)
+
+`cimpc_plant_rollout_segments`: nodes 2nq x B x M and u nu x B x T with T = M L.  Segment j of robot b is virtual robot j B + b of ONE
+rollout of M B robots for L steps; qs is nq x (M B) x (L + 2), γ, b, status, iters are in (T, B) layout, defects 2nq x B x (M - 1), D (B).
+With a `TrackingCost` J (B), lin_q 2nq x B x (T + 1) and lin_r nu x B x T are the cost on the segments' own rows, else `nothing`.  The
+tape is an ordinary `PlantTape` of B robots and T steps.
+"""
+function plant_rollout_segments(model::Symbol, nodes::Array{Float64,3}, u::Array{Float64,3}, μ, h_sim, opts;
+                                cost::Union{Nothing,TrackingCost} = nothing, w::Union{Nothing,Array{Float64}} = nothing, w_hold::Int = 1,
+                                terrain::Union{Nothing,Vector{Terrain}} = nothing, steps_per_launch::Int = 0, grad_reg = nothing, grad_cols = nothing)
+    id, nq, nu, nc, nf, nw = _plant_dims(model)
+    n, B, M, T = 2 * nq, size(nodes, 2), size(nodes, 3), size(u, 3)
+    (size(nodes, 1) == n && size(u, 1) == nu && size(u, 2) == B) || error("plant_rollout_segments: nodes must be $n x B x M and u $nu x B x T")
+    (M >= 1 && T >= 1 && T % M == 0) || error("plant_rollout_segments: T must be a multiple of the number of segments")
+    L = T ÷ M
+    ws = w === nothing ? nothing : ndims(w) == 2 ? reshape(w, nw, 1, :) : w
+    (ws === nothing || (ndims(ws) == 3 && size(ws, 1) == nw && size(ws, 2) in (1, B))) || error("plant_rollout_segments: w must be $nw x K_w or $nw x B x K_w")
+    μs = Float64.(vcat(μ))
+    length(μs) in (1, B) || error("plant_rollout_segments: one friction coefficient or one per robot")
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    reg = grad_reg === nothing ? o[].kappa_tol * o[].gamma_reg : Float64(grad_reg)
+    n_cols = grad_cols === nothing ? n + nu : Int(grad_cols)
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu = length(μs)
+    qs = zeros(nq, M * B, L + 2); γ = zeros(nc, B, T); b = zeros(nf * nc, B, T)
+    status = zeros(Cint, B, T); iters = zeros(Cint, B, T); grad_status = zeros(Cint, B, T)
+    defects = zeros(n, B, M - 1); D = zeros(B)
+    J = zeros(B); lin_q = zeros(n, B, T + 1); lin_r = zeros(nu, B, T)
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve cost begin
+        cc = cost === nothing ? C_NULL : begin
+            n_Q, n_R, n_x = _tracking_cost_sizes("plant_rollout_segments", cost, nq, nu, B, T)
+            Ref(TrackingCostC(pointer(cost.Q), pointer(cost.Qf), pointer(cost.R), pointer(cost.x_goal), pointer(cost.u_goal), n_Q, n_R, n_x))
+        end
+        check(@ccall LIB.cimpc_plant_rollout_segments(id::Cint, B::Cint, T::Cint, M::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                                      nodes::Ptr{Cdouble}, u::Ptr{Cdouble}, wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint,
+                                                      μs::Ptr{Cdouble}, n_mu::Cint, h_sim::Cdouble, o::Ref{IpOpts}, cc::Ptr{TrackingCostC},
+                                                      reg::Cdouble, n_cols::Cint, qs::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble},
+                                                      status::Ptr{Cint}, iters::Ptr{Cint}, defects::Ptr{Cdouble}, D::Ptr{Cdouble}, J::Ptr{Cdouble},
+                                                      lin_q::Ptr{Cdouble}, lin_r::Ptr{Cdouble}, grad_status::Ptr{Cint}, handle::Ref{Ptr{Cvoid}})::Cint)
+    end
+    cost === nothing && return qs, γ, b, status, iters, defects, D, nothing, nothing, nothing, PlantTape(handle[], model, B, T, n_cols, grad_status)
+    return qs, γ, b, status, iters, defects, D, J, lin_q, lin_r, PlantTape(handle[], model, B, T, n_cols, grad_status)
+end
+
+"""
+    plant_tape_lqr_shooting(tape, Q, R, q, r, defects, segment_len; Qf = nothing, ρ = 0.0, keep = nothing, u_lo = nothing, u_hi = nothing,
+                            u_nom = nothing) -> (K, k, P0, p0, dV, status, n_cut, clamped)
+
+`cimpc_plant_tape_lqr_shooting`: `plant_tape_lqr_box` on the tape of `plant_rollout_segments` with the defects 2nq x B x (T / segment_len - 1)
+at the nodes t = j segment_len: the walk step of t = j segment_len - 1 starts from p + P d.  With all-zero defects K and k are
+`plant_tape_lqr_box`'s.  Unexecuted, like the rest of this binding.
+"""
+function plant_tape_lqr_shooting(tape::PlantTape, Q::Array{Float64}, R::Array{Float64}, q::Array{Float64,3}, r::Array{Float64,3},
+                                 defects::Array{Float64,3}, segment_len::Int; Qf::Union{Nothing,Matrix{Float64}} = nothing,
+                                 ρ::Union{Real,Vector{Float64}} = 0.0, keep::Union{Nothing,Integer} = nothing,
+                                 u_lo::Union{Nothing,Matrix{Float64}} = nothing, u_hi::Union{Nothing,Matrix{Float64}} = nothing,
+                                 u_nom::Union{Nothing,Array{Float64,3}} = nothing)
+    tape.handle != C_NULL || error("plant_tape_lqr_shooting: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, n, m = tape.B, tape.T, 2 * nq, nu
+    n_keep = keep === nothing ? T : Int(keep)
+    (segment_len >= 1 && T % segment_len == 0) || error("plant_tape_lqr_shooting: T must be a multiple of segment_len")
+    size(defects) == (n, B, T ÷ segment_len - 1) || error("plant_tape_lqr_shooting: defects must be $n x $B x $(T ÷ segment_len - 1)")
+    (size(Q) == (n, n) || size(Q) == (n, n, T)) || error("plant_tape_lqr_shooting: Q must be $n x $n or $n x $n x $T")
+    (size(R) == (m, m) || size(R) == (m, m, T)) || error("plant_tape_lqr_shooting: R must be $m x $m or $m x $m x $T")
+    n_Q = ndims(Q) == 2 ? 1 : T; n_R = ndims(R) == 2 ? 1 : T
+    Qend = Qf === nothing ? (ndims(Q) == 2 ? Q : Q[:, :, T]) : Qf
+    size(Qend) == (n, n) || error("plant_tape_lqr_shooting: Qf must be $n x $n")
+    (size(q) == (n, B, T + 1) && size(r) == (m, B, T)) || error("plant_tape_lqr_shooting: q must be $n x $B x $(T + 1) and r $m x $B x $T")
+    rho = ρ isa Real ? [Float64(ρ)] : ρ
+    (length(rho) == 1 || length(rho) == B) || error("plant_tape_lqr_shooting: ρ must be a number or one per robot ($B)")
+    limited = u_lo !== nothing || u_hi !== nothing
+    if limited
+        (u_lo !== nothing && u_hi !== nothing && u_nom !== nothing) || error("plant_tape_lqr_shooting: u_lo, u_hi and u_nom go together")
+        (size(u_lo) == size(u_hi) && size(u_lo, 1) == m && size(u_lo, 2) in (1, B)) || error("plant_tape_lqr_shooting: u_lo, u_hi must be $m x 1 or $m x $B")
+        size(u_nom) == (m, B, T) || error("plant_tape_lqr_shooting: u_nom must be $m x $B x $T")
+    end
+    n_rho = length(rho); n_lim = limited ? size(u_lo, 2) : 1
+    K = zeros(m, n, B, n_keep); P0 = zeros(n, n, B); status = zeros(Cint, B); n_cut = zeros(Cint, B)
+    k = zeros(m, B, n_keep); p0 = zeros(n, B); dV = zeros(2, B); clamped = zeros(Cint, B, n_keep)
+    d = isempty(defects) ? zeros(1) : defects      # one segment: no node, but the library asks for a pointer
+    p(a) = a === nothing ? C_NULL : pointer(a)
+    GC.@preserve Qend u_lo u_hi u_nom begin
+        pQf, plo, phi, pun = p(Qend), p(u_lo), p(u_hi), p(u_nom)
+        check(@ccall LIB.cimpc_plant_tape_lqr_shooting(tape.handle::Ptr{Cvoid}, n_Q::Cint, Q::Ptr{Cdouble}, pQf::Ptr{Cdouble}, n_R::Cint,
+                                                       R::Ptr{Cdouble}, q::Ptr{Cdouble}, r::Ptr{Cdouble}, n_rho::Cint, rho::Ptr{Cdouble},
+                                                       n_keep::Cint, K::Ptr{Cdouble}, k::Ptr{Cdouble}, P0::Ptr{Cdouble}, p0::Ptr{Cdouble},
+                                                       dV::Ptr{Cdouble}, status::Ptr{Cint}, n_cut::Ptr{Cint}, n_lim::Cint, plo::Ptr{Cdouble},
+                                                       phi::Ptr{Cdouble}, pun::Ptr{Cdouble}, clamped::Ptr{Cint}, segment_len::Cint,
+                                                       d::Ptr{Cdouble})::Cint)
+    end
+    return K, k, P0, p0, dV, status, n_cut, clamped
+end
+
+"""
+    plant_shooting_forward(tape, Q, R, lin_q, lin_r, K, k, defects, segment_len; Qf = nothing) -> (dx_nodes, du, dJ)
+
+`cimpc_plant_shooting_forward`: the linear forward pass at α = 1 over the tape's blocks with the gains K m x n x B x T, k m x B x T of
+`plant_tape_lqr_shooting` and its defects: dx at the nodes 2nq x B x (T / segment_len - 1), du m x B x T and dJ 2 x B, the quadratic model's
+two terms.  Unexecuted, like the rest of this binding.
+"""
+function plant_shooting_forward(tape::PlantTape, Q::Array{Float64}, R::Array{Float64}, lin_q::Array{Float64,3}, lin_r::Array{Float64,3},
+                                K::Array{Float64,4}, k::Array{Float64,3}, defects::Array{Float64,3}, segment_len::Int;
+                                Qf::Union{Nothing,Matrix{Float64}} = nothing)
+    tape.handle != C_NULL || error("plant_shooting_forward: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, n, m = tape.B, tape.T, 2 * nq, nu
+    (segment_len >= 1 && T % segment_len == 0) || error("plant_shooting_forward: T must be a multiple of segment_len")
+    M = T ÷ segment_len
+    (size(defects) == (n, B, M - 1) && M > 1) || error("plant_shooting_forward: defects must be $n x $B x $(M - 1), at least one node")
+    (size(K) == (m, n, B, T) && size(k) == (m, B, T)) || error("plant_shooting_forward: K must be $m x $n x $B x $T and k $m x $B x $T")
+    (size(lin_q) == (n, B, T + 1) && size(lin_r) == (m, B, T)) || error("plant_shooting_forward: lin_q must be $n x $B x $(T + 1) and lin_r $m x $B x $T")
+    (size(Q) == (n, n) || size(Q) == (n, n, T)) || error("plant_shooting_forward: Q must be $n x $n or $n x $n x $T")
+    (size(R) == (m, m) || size(R) == (m, m, T)) || error("plant_shooting_forward: R must be $m x $m or $m x $m x $T")
+    n_Q = ndims(Q) == 2 ? 1 : T; n_R = ndims(R) == 2 ? 1 : T
+    Qend = Qf === nothing ? (ndims(Q) == 2 ? Q : Q[:, :, T]) : Qf
+    size(Qend) == (n, n) || error("plant_shooting_forward: Qf must be $n x $n")
+    dx_nodes = zeros(n, B, M - 1); du = zeros(m, B, T); dJ = zeros(2, B)
+    check(@ccall LIB.cimpc_plant_shooting_forward(tape.handle::Ptr{Cvoid}, n_Q::Cint, Q::Ptr{Cdouble}, Qend::Ptr{Cdouble}, n_R::Cint, R::Ptr{Cdouble},
+                                                  lin_q::Ptr{Cdouble}, lin_r::Ptr{Cdouble}, K::Ptr{Cdouble}, k::Ptr{Cdouble}, segment_len::Cint,
+                                                  defects::Ptr{Cdouble}, dx_nodes::Ptr{Cdouble}, du::Ptr{Cdouble}, dJ::Ptr{Cdouble})::Cint)
+    return dx_nodes, du, dJ
+end
+
+"""
+    plant_shooting_linesearch(tape, segments, qs_nom, u_nom, K, k, dx_nodes, dJ, phi_nom, D_nom, weight, alphas, cost, μ, h_sim, opts; armijo = 1e-4,
+                              w = nothing, w_hold = 1, terrain = nothing, steps_per_launch = 0, grad_reg = nothing, u_lo = nothing, u_hi = nothing)
+        -> (J, D_cand, phi, ok, choice, qs, u_applied, γ, b, status, iters, defects, D, J_chosen, lin_q, lin_r, tape)
+
+`cimpc_plant_shooting_linesearch`: the line search of a multiple-shooting iteration, every step length of every segment of every robot in ONE
+closed-loop rollout of length(alphas) M B robots for T / M steps; phi = J + weight D, acceptance on phi, the chosen candidate's segments compacted
+as `plant_rollout_segments` returns a rollout, with their stitched `PlantTape`.  weight: a vector of 1 or B defect weights.  Unexecuted, like the
+rest of this binding.
+"""
+function plant_shooting_linesearch(tape::PlantTape, segments::Int, qs_nom::Array{Float64,3}, u_nom::Array{Float64,3}, K::Array{Float64,4}, k::Array{Float64,3},
+                                   dx_nodes::Array{Float64,3}, dJ::Matrix{Float64}, phi_nom::Vector{Float64}, D_nom::Vector{Float64}, weight::Vector{Float64},
+                                   alphas::Vector{Float64}, cost::TrackingCost, μ, h_sim, opts; armijo::Real = 1e-4,
+                                   w::Union{Nothing,Array{Float64}} = nothing, w_hold::Int = 1, terrain::Union{Nothing,Vector{Terrain}} = nothing,
+                                   steps_per_launch::Int = 0, grad_reg = nothing, u_lo::Union{Nothing,Matrix{Float64}} = nothing,
+                                   u_hi::Union{Nothing,Matrix{Float64}} = nothing)
+    tape.handle != C_NULL || error("plant_shooting_linesearch: the tape is closed")
+    id, nq, nu, nc, nf, nw = _plant_dims(tape.model)
+    B, T, n, m, M = tape.B, tape.T, 2 * nq, nu, segments
+    (M >= 1 && T % M == 0) || error("plant_shooting_linesearch: T must be a multiple of the number of segments")
+    L = T ÷ M
+    (size(qs_nom) == (nq, M * B, L + 2) && size(u_nom) == (nu, B, T)) || error("plant_shooting_linesearch: qs_nom must be $nq x $(M * B) x $(L + 2) and u_nom $nu x $B x $T")
+    (size(K) == (m, n, B, T) && size(k) == (m, B, T) && size(dJ) == (2, B)) || error("plant_shooting_linesearch: K must be $m x $n x $B x $T, k $m x $B x $T, dJ 2 x $B")
+    size(dx_nodes) == (n, B, M - 1) || error("plant_shooting_linesearch: dx_nodes must be $n x $B x $(M - 1)")
+    (length(phi_nom) == B && length(D_nom) == B && length(weight) in (1, B)) || error("plant_shooting_linesearch: phi_nom and D_nom have B entries, weight 1 or B")
+    n_alpha = length(alphas)
+    (1 <= n_alpha <= 64 && all(isfinite, alphas) && armijo >= 0) || error("plant_shooting_linesearch: 1 to 64 finite alphas, armijo >= 0")
+    n_Q, n_R, n_x = _tracking_cost_sizes("plant_shooting_linesearch", cost, nq, nu, B, T)
+    ws = w === nothing ? nothing : ndims(w) == 2 ? reshape(w, nw, 1, :) : w
+    μs = Float64.(vcat(μ))
+    length(μs) in (1, B) || error("plant_shooting_linesearch: one friction coefficient or one per robot")
+    (u_lo === nothing) == (u_hi === nothing) || error("plant_shooting_linesearch: u_lo and u_hi go together")
+    o = Ref(opts isa IpOpts ? opts : IpOpts(opts))
+    reg = grad_reg === nothing ? o[].kappa_tol * o[].gamma_reg : Float64(grad_reg)
+    n_ter, ter = terrain === nothing ? (0, C_NULL) : (length(terrain), terrain)
+    wp, K_w, n_w = ws === nothing ? (C_NULL, 1, 1) : (ws, size(ws, 3), size(ws, 2))
+    n_mu, n_weight = length(μs), length(weight)
+    n_lim = u_lo === nothing ? 1 : size(u_lo, 2)
+    J = zeros(B, n_alpha); Dc = zeros(B, n_alpha); phi = zeros(B, n_alpha); ok = zeros(Cint, B, n_alpha); choice = zeros(Cint, B)
+    qs = zeros(nq, M * B, L + 2); cu = zeros(nu, B, T); γ = zeros(nc, B, T); b = zeros(nf * nc, B, T)
+    status = zeros(Cint, B, T); iters = zeros(Cint, B, T); grad_status = zeros(Cint, B, T)
+    defects = zeros(n, B, max(M - 1, 1)); D = zeros(B); Jn = zeros(B); lin_q = zeros(n, B, T + 1); lin_r = zeros(m, B, T)
+    dxp = isempty(dx_nodes) ? zeros(1) : dx_nodes      # one segment: no node, but the library asks for a pointer
+    handle = Ref{Ptr{Cvoid}}(C_NULL)
+    p(a) = a === nothing ? C_NULL : pointer(a)
+    GC.@preserve cost u_lo u_hi begin
+        plo, phi_ = p(u_lo), p(u_hi)
+        cc = Ref(TrackingCostC(pointer(cost.Q), pointer(cost.Qf), pointer(cost.R), pointer(cost.x_goal), pointer(cost.u_goal), n_Q, n_R, n_x))
+        check(@ccall LIB.cimpc_plant_shooting_linesearch(tape.handle::Ptr{Cvoid}, M::Cint, steps_per_launch::Cint, n_ter::Cint, ter::Ptr{Terrain},
+                                                         qs_nom::Ptr{Cdouble}, u_nom::Ptr{Cdouble}, wp::Ptr{Cdouble}, K_w::Cint, n_w::Cint, w_hold::Cint,
+                                                         μs::Ptr{Cdouble}, n_mu::Cint, h_sim::Cdouble, o::Ref{IpOpts}, K::Ptr{Cdouble}, k::Ptr{Cdouble},
+                                                         dxp::Ptr{Cdouble}, dJ::Ptr{Cdouble}, phi_nom::Ptr{Cdouble}, D_nom::Ptr{Cdouble}, n_weight::Cint,
+                                                         weight::Ptr{Cdouble}, n_alpha::Cint, alphas::Ptr{Cdouble}, armijo::Cdouble, cc::Ref{TrackingCostC},
+                                                         reg::Cdouble, J::Ptr{Cdouble}, Dc::Ptr{Cdouble}, phi::Ptr{Cdouble}, ok::Ptr{Cint}, choice::Ptr{Cint},
+                                                         qs::Ptr{Cdouble}, cu::Ptr{Cdouble}, γ::Ptr{Cdouble}, b::Ptr{Cdouble}, status::Ptr{Cint},
+                                                         iters::Ptr{Cint}, defects::Ptr{Cdouble}, D::Ptr{Cdouble}, Jn::Ptr{Cdouble}, lin_q::Ptr{Cdouble},
+                                                         lin_r::Ptr{Cdouble}, grad_status::Ptr{Cint}, handle::Ref{Ptr{Cvoid}}, n_lim::Cint, plo::Ptr{Cdouble},
+                                                         phi_::Ptr{Cdouble})::Cint)
+    end
+    return J, Dc, phi, ok, choice, qs, cu, γ, b, status, iters, defects[:, :, 1:M-1], D, Jn, lin_q, lin_r, PlantTape(handle[], tape.model, B, T, tape.n_cols, grad_status)
+end
+
+"""
+    plant_shooting_cost(cost, qs, u, segments) -> (J, D, defects, lin_q, lin_r)
+
+`cimpc_plant_shooting_cost` (host only): the cost and the defects of segment trajectories qs nq x (M B) x (L + 2) under the controls u
+nu x B x T, bit for bit what `plant_rollout_segments` computes on the device.
+"""
+function plant_shooting_cost(cost::TrackingCost, qs::Array{Float64,3}, u::Array{Float64,3}, segments::Int)
+    nq, nu, B, T, M = size(qs, 1), size(u, 1), size(u, 2), size(u, 3), segments
+    (M >= 1 && T % M == 0 && size(qs, 2) == M * B && size(qs, 3) == T ÷ M + 2) || error("plant_shooting_cost: qs must be nq x (M B) x (T / M + 2) beside u nu x B x T")
+    n_Q, n_R, n_x = _tracking_cost_sizes("plant_shooting_cost", cost, nq, nu, B, T)
+    J = zeros(B); D = zeros(B); defects = zeros(2 * nq, B, M - 1); lin_q = zeros(2 * nq, B, T + 1); lin_r = zeros(nu, B, T)
+    GC.@preserve cost begin
+        cc = Ref(TrackingCostC(pointer(cost.Q), pointer(cost.Qf), pointer(cost.R), pointer(cost.x_goal), pointer(cost.u_goal), n_Q, n_R, n_x))
+        check(@ccall LIB.cimpc_plant_shooting_cost(nq::Cint, nu::Cint, B::Cint, T::Cint, M::Cint, cc::Ref{TrackingCostC}, qs::Ptr{Cdouble},
+                                                   u::Ptr{Cdouble}, J::Ptr{Cdouble}, D::Ptr{Cdouble}, defects::Ptr{Cdouble}, lin_q::Ptr{Cdouble},
+                                                   lin_r::Ptr{Cdouble})::Cint)
+    end
+    return J, D, defects, lin_q, lin_r
+end
+
 # ---- the plant models linearized on the device: the `LinearizedStep` triple of N knots in one call (linearized_step.jl:10-31) --------
 """
     plant_linearize(model, z, θ, κ; terrain = nothing) -> (r0, rz0, rθ0)
