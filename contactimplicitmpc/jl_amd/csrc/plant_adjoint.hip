@@ -138,16 +138,10 @@ extern "C" int cimpc_plant_tape_dims(cimpc_plant_tape tape, int* model, int* B, 
 extern "C" int cimpc_plant_tape_destroy(cimpc_plant_tape tape) {
     using namespace cimpc;
     if (!tape) return CIMPC_OK;
-    bool ok = true;
+    bool ok = false;
     {
-        std::lock_guard<std::mutex> lock(g_plant_mu);      // no call is walking the tape
-        int cur = -1;
-        const int dev = tape->buf.device;
-        ok = hipGetDevice(&cur) == hipSuccess && (cur == dev || hipSetDevice(dev) == hipSuccess);
-        if (ok) {
-            ok = tape->buf.release();
-            if (cur != dev) ok = (hipSetDevice(cur) == hipSuccess) && ok;
-        }
+        PlantDeviceScope scope(tape->buf.device);      // no call is walking the tape
+        if (scope.rc() == CIMPC_OK) ok = scope.leave(tape->buf.release());
     }
     delete tape;
     return ok ? CIMPC_OK : CIMPC_ERR_HIP;
@@ -177,10 +171,8 @@ extern "C" int cimpc_plant_tape_vjp_feedback(cimpc_plant_tape tape, const double
     // the staging buffers: cotangents in, gradients out, in the order of the argument list
     const size_t n_gq = gq ? (size_t)(T + 2) * B * nq : 0, n_gg = ggamma ? TB * nc : 0, n_gb = gb ? TB * nb : 0;
     const size_t n_q = (size_t)B * nq, n_u = TB * nu, n_w = g_w_step ? TB * nw : 0, n_m = g_mu ? (size_t)B : 0, n_h = g_h ? (size_t)B : 0;
-    std::lock_guard<std::mutex> lock(g_plant_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
-    if (cur != buf.device && hipSetDevice(buf.device) != hipSuccess) return CIMPC_ERR_HIP;
+    PlantDeviceScope scope(buf.device);
+    if (scope.rc() != CIMPC_OK) return scope.rc();
     bool ok = false;
     PlantWs* ws = plant_ws_open(buf.device);
     if (ws && plant_grow(&ws->d_adj_in, &ws->cap_adj_in, n_gq + n_gg + n_gb) && plant_grow(&ws->d_adj_out, &ws->cap_adj_out, 2 * n_q + n_u + n_w + n_m + n_h) &&
@@ -215,8 +207,7 @@ extern "C" int cimpc_plant_tape_vjp_feedback(cimpc_plant_tape tape, const double
         if (ok && g_h) ok = hipMemcpyAsync(g_h, d_h, n_h * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
         ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
     }
-    if (cur != buf.device) ok = (hipSetDevice(cur) == hipSuccess) && ok;
-    return ok ? CIMPC_OK : CIMPC_ERR_HIP;
+    return scope.leave(ok) ? CIMPC_OK : CIMPC_ERR_HIP;
 }
 
 extern "C" int cimpc_plant_tape_vjp(cimpc_plant_tape tape, const double* gq, const double* ggamma, const double* gb, double* g_q0,

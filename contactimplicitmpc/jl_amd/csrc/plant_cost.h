@@ -26,6 +26,8 @@
 #include <cmath>
 #include <cstddef>
 
+#include "../../../include/cimpc.h"
+
 #ifdef __HIPCC__
 #define PCOST_HD __host__ __device__
 #else
@@ -41,6 +43,11 @@ struct PlantCost {
     int n_Q, n_R, n_x;
     int T, nq, nu;
 };
+
+// The C ABI's cost on the caller's pointers, for a rollout of T steps of a model with nq, nu
+inline PlantCost plant_cost_of(const cimpc_tracking_cost& c, int T, int nq, int nu) {
+    return PlantCost{c.Q, c.Qf, c.R, c.x_goal, c.u_goal, c.n_Q, c.n_R, c.n_x, T, nq, nu};
+}
 
 // ex (n) | eu (m) | qx (n) | ru (m) | l_t and one of padding
 PCOST_HD constexpr size_t plant_cost_work_doubles(int nq, int nu) { return (size_t)4 * nq + 2 * (size_t)nu + 2; }

@@ -22,7 +22,6 @@
 #include <cmath>
 #include <mutex>
 #include <string>
-#include <utility>
 #include <vector>
 
 // No fused multiply-adds in this translation unit: the rules round as the NumPy lines of plant.ilqr do.
@@ -119,10 +118,8 @@ bool plant_ilqr_iteration(const PlantLsPlan& P, const PlantIlqrArrays& A, int it
 }
 
 namespace {
-// grow-only device buffers of the entry, per device, next to the plant workspace whose buffers (the candidates' rollout), stream and
-// mutex it uses: every double and every int of the loop
-struct IlqrWs { double* d_f = nullptr; int* d_i = nullptr; size_t cap_f = 0, cap_i = 0; };
-IlqrWs g_ilqr_ws[PLANT_MAX_DEVICES];
+// the entry's own buffers, beside the candidates' rollout in the plant workspace: every double of the loop in d_in, every int in d_int
+PlantStageWs g_ilqr_ws[PLANT_MAX_DEVICES];
 }  // namespace
 
 }  // namespace cimpc
@@ -139,16 +136,16 @@ extern "C" int cimpc_plant_ilqr(cimpc_plant_tape tape, int steps_per_launch, int
                                 int* lq_status, int* n_cut, int* clamped, cimpc_plant_tape* new_tape) {
     using namespace cimpc;
     // every refusal leaves its reason where cimpc_last_error(NULL) finds it; what needs no tape is tested before the tape is looked at
-    auto refuse = [](const std::string& why) { set_global_error("cimpc_plant_ilqr: " + why); return CIMPC_ERR_INVALID; };
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_ilqr", why); };
     if (!new_tape) return refuse("null new_tape");
     *new_tape = nullptr;
-    const std::pair<const char*, const void*> required[] = {
+    const PlantRequired required[] = {
         {"tape", tape}, {"q_nom", q_nom}, {"u_nom", u_nom}, {"gamma_nom", gamma_nom}, {"b_nom", b_nom}, {"status_nom", status_nom}, {"iters_nom", iters_nom},
         {"J_nom", J_nom}, {"lin_q_nom", lin_q_nom}, {"lin_r_nom", lin_r_nom}, {"mu", mu}, {"opts", opts}, {"cost", cost}, {"alpha", alpha},
         {"ladder", ladder}, {"q", q}, {"u_applied", u_applied}, {"gamma", gamma}, {"b", b}, {"status", status}, {"iters", iters}, {"lin_q", lin_q},
         {"lin_r", lin_r}, {"grad_status", grad_status}, {"hist_J", hist_J}, {"hist_alpha", hist_alpha}, {"hist_rho", hist_rho},
         {"hist_accepted", hist_accepted}, {"n_iter", n_iter}};
-    for (const auto& [name, p] : required) if (!p) return refuse(std::string("null ") + name);
+    if (const char* name = plant_first_null(required)) return refuse(std::string("null ") + name);
     if (const char* why = plant_ilqr_refusal(max_iter, n_ladder, ladder, rho_max, tol)) return refuse(why);
     // what cimpc_plant_tape_linesearch_box refuses
     PlantLsPlan P;
@@ -159,50 +156,48 @@ extern "C" int cimpc_plant_ilqr(cimpc_plant_tape tape, int steps_per_launch, int
     const PlantTapeBuffers& caller = tape->buf;
     const PlantModel& M = P.M;
     const PlantRolloutLayout& L = P.L;
-    PlantCost C = P.C;
     const int B = P.B, T = P.T, n_cols = P.n_cols, nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb(), nz = M.nz(), nw = M.nw, nr = nq + nc + nb, NB = P.NB;
     const bool limits = P.limits, w_each = P.w_each, mu_each = P.mu_each;
-    const size_t TB = (size_t)T * B, n = (size_t)2 * nq, kk = (size_t)nu * n, block = (size_t)nr * n_cols, nB = (size_t)B;
+    const size_t TB = (size_t)T * B, n = (size_t)2 * nq, kk = (size_t)nu * n, block = (size_t)nr * n_cols, nB = (size_t)B, traj = (size_t)(T + 2) * B * nq;
     // what cimpc_plant_tape_lqr_box refuses of a limited pass with linear terms, one lap and every step's gains kept
     if (n_cols < 2 * nq + nu || !plant_riccati_fits(nq, nu)) return refuse("a model without controls, or a tape without the control columns");
     if (nu > PLANT_BOXQP_MAX_M || plant_riccati_box_lds(nq, nu) > PLANT_RIC_MAX_LDS) return refuse("a model too large for the limited pass");
     if (T > (1 << 30)) return refuse("laps T beyond 2^30");
-    auto finite = [](const double* a, size_t cnt) { for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(a[i])) return false; return true; };
-    if (!finite(q_nom, (size_t)(T + 2) * B * nq)) return refuse("a non-finite entry of q_nom");
-    if (!finite(u_nom, TB * nu)) return refuse("a non-finite entry of u_nom");
+    if (!plant_all_finite(q_nom, traj)) return refuse("a non-finite entry of q_nom");
+    if (!plant_all_finite(u_nom, TB * nu)) return refuse("a non-finite entry of u_nom");
 
     // the doubles: what goes up once | the nominal | the gains | the rules' rows | the line search's outputs | the history
-    size_t at = 0;
-    auto next = [&at](size_t cnt) { const size_t o = at; at += cnt; return o; };
-    const size_t i_w = next(w_each ? (size_t)K_w * B * nw : 0), i_mu = next(mu_each ? nB : 0), i_al = next((size_t)n_alpha), i_lad = next((size_t)n_ladder),
-                 i_Q = next((size_t)C.n_Q * n * n), i_Qf = next(n * n), i_R = next((size_t)C.n_R * nu * nu), i_xg = next((size_t)(T + 1) * C.n_x * n),
-                 i_ug = next((size_t)T * C.n_x * nu), i_lo = next(limits ? (size_t)n_lim * nu : 0), i_hi = next(limits ? (size_t)n_lim * nu : 0);
-    const size_t m_q = next((size_t)(T + 2) * B * nq), m_u = next(TB * nu), m_g = next(TB * nc), m_b = next(TB * nb), m_lq = next((size_t)(T + 1) * B * n),
-                 m_lr = next(TB * nu), m_J = next(nB);
-    const size_t g_K = next(TB * kk), g_k = next(TB * nu), g_dV = next(2 * nB), r_rho = next(nB), r_Jn = next(nB);
-    const size_t o_J = next((size_t)NB), o_q = next((size_t)(T + 2) * B * nq), o_u = next(TB * nu), o_g = next(TB * nc), o_b = next(TB * nb),
-                 o_lq = next((size_t)(T + 1) * B * n), o_lr = next(TB * nu), o_z = next(TB * nz);
-    const size_t h_J = next((size_t)max_iter * B), h_al = next((size_t)max_iter * B), h_rho = next((size_t)max_iter * B), n_f = at;
-    at = 0;      // the integers
-    const size_t j_st = next(TB), j_it = next(TB), j_lev = next(nB), j_act = next(nB), j_lqs = next(nB), j_cut = next(nB), j_cl = next(TB),
-                 j_ok = next((size_t)NB), j_ch = next(nB), j_cst = next(TB), j_cit = next(TB), j_conv = next((size_t)NB), j_hacc = next((size_t)max_iter * B),
-                 j_nact = next((size_t)max_iter), n_i = at;
+    PlantCursor at;
+    const PlantSpan i_w = at.take(w_each ? (size_t)K_w * B * nw : 0), i_mu = at.take(mu_each ? nB : 0), i_al = at.take((size_t)n_alpha),
+                    i_lad = at.take((size_t)n_ladder);
+    const PlantCostSpans i_cost = plant_cost_spans(at, P.C);
+    const PlantSpan i_lo = at.take(limits ? (size_t)n_lim * nu : 0), i_hi = at.take(limits ? (size_t)n_lim * nu : 0);
+    const PlantSpan m_q = at.take(traj), m_u = at.take(TB * nu), m_g = at.take(TB * nc), m_b = at.take(TB * nb), m_lq = at.take((size_t)(T + 1) * B * n),
+                    m_lr = at.take(TB * nu), m_J = at.take(nB);
+    const PlantSpan g_K = at.take(TB * kk), g_k = at.take(TB * nu), g_dV = at.take(2 * nB), r_rho = at.take(nB), r_Jn = at.take(nB);
+    const PlantSpan o_J = at.take((size_t)NB), o_q = at.take(traj), o_u = at.take(TB * nu), o_g = at.take(TB * nc), o_b = at.take(TB * nb),
+                    o_lq = at.take((size_t)(T + 1) * B * n), o_lr = at.take(TB * nu), o_z = at.take(TB * nz);
+    const PlantSpan h_J = at.take((size_t)max_iter * B), h_al = at.take((size_t)max_iter * B), h_rho = at.take((size_t)max_iter * B);
+    const size_t n_f = at.end();
+    // the integers
+    const PlantSpan j_st = at.take(TB), j_it = at.take(TB), j_lev = at.take(nB), j_act = at.take(nB), j_lqs = at.take(nB), j_cut = at.take(nB), j_cl = at.take(TB),
+                    j_ok = at.take((size_t)NB), j_ch = at.take(nB), j_cst = at.take(TB), j_cit = at.take(TB), j_conv = at.take((size_t)NB),
+                    j_hacc = at.take((size_t)max_iter * B), j_nact = at.take((size_t)max_iter);
+    const size_t n_i = at.end();
     const std::vector<cimpc_terrain> ter = plant_linesearch_terrains(P, terrain);      // the candidates' terrains: robot b's for every c
     const std::vector<int> ones(nB, 1);
 
-    std::lock_guard<std::mutex> lock(g_plant_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
     const int dev = caller.device;
-    if (cur != dev && hipSetDevice(dev) != hipSuccess) return CIMPC_ERR_HIP;
+    PlantDeviceScope scope(dev);
+    if (scope.rc() != CIMPC_OK) return scope.rc();
     bool ok_ = false;
     int done = 0;
     PlantTapeBuffers bufs[2];      // iteration i writes bufs[i & 1] and reads bufs[(i - 1) & 1] (iteration 0: the caller's tape)
     PlantWs* ws = plant_ws_open(dev);
-    IlqrWs& S = g_ilqr_ws[dev];
+    PlantStageWs& S = g_ilqr_ws[dev];
     if (ws && plant_grow(&ws->d_in, &ws->cap_in, L.need_in) && plant_grow(&ws->d_out, &ws->cap_out, L.need_out) && plant_grow(&ws->d_st, &ws->cap_st, L.need_st) &&
         plant_grow(&ws->d_ter, &ws->cap_ter, (size_t)P.n_ter) && plant_grow(&ws->d_z, &ws->cap_z, L.need_z) && plant_grow(&ws->d_fb, &ws->cap_fb, L.need_fb) &&
-        plant_grow(&S.d_f, &S.cap_f, n_f) && plant_grow(&S.d_i, &S.cap_i, n_i)) {
+        S.grow(n_f, 0, n_i)) {
         ok_ = true;
         for (int s = 0; s < (max_iter > 1 ? 2 : 1) && ok_; ++s) {      // the tapes' memory, the last to be allocated
             bufs[s].device = dev; bufs[s].M = M;
@@ -211,51 +206,44 @@ extern "C" int cimpc_plant_ilqr(cimpc_plant_tape tape, int steps_per_launch, int
         }
         PlantWs& W = *ws;
         hipStream_t st = W.st;
-        auto up = [&](auto* d, const auto* hsrc, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(d, hsrc, cnt * sizeof(*d), hipMemcpyHostToDevice, st) == hipSuccess; };
-        auto down = [&](auto* hdst, const auto* d, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(hdst, d, cnt * sizeof(*d), hipMemcpyDeviceToHost, st) == hipSuccess; };
-        double* F = S.d_f;
-        int* N = S.d_i;
-        // up, once
-        if (w_each) up(F + i_w, w, (size_t)K_w * B * nw);
-        if (mu_each) up(F + i_mu, mu, nB);
-        up(F + i_al, alpha, (size_t)n_alpha); up(F + i_lad, ladder, (size_t)n_ladder);
-        up(F + i_Q, C.Q, (size_t)C.n_Q * n * n); up(F + i_Qf, C.Qf, n * n); up(F + i_R, C.R, (size_t)C.n_R * nu * nu);
-        up(F + i_xg, C.x_goal, (size_t)(T + 1) * C.n_x * n); up(F + i_ug, C.u_goal, (size_t)T * C.n_x * nu);
-        if (limits) { up(F + i_lo, u_lo, (size_t)n_lim * nu); up(F + i_hi, u_hi, (size_t)n_lim * nu); }
-        up(F + m_q, q_nom, (size_t)(T + 2) * B * nq); up(F + m_u, u_nom, TB * nu); up(F + m_g, gamma_nom, TB * nc); up(F + m_b, b_nom, TB * nb);
-        up(F + m_lq, lin_q_nom, (size_t)(T + 1) * B * n); up(F + m_lr, lin_r_nom, TB * nu); up(F + m_J, J_nom, nB);
-        up(N + j_st, status_nom, TB); up(N + j_it, iters_nom, TB); up(N + j_act, ones.data(), nB);
-        ok_ = ok_ && hipMemsetAsync(N + j_lev, 0, nB * sizeof(int), st) == hipSuccess && hipMemsetAsync(N + j_nact, 0, (size_t)max_iter * sizeof(int), st) == hipSuccess;
+        PlantStreamCopier copy{{st}, ok_};
+        double* F = S.d_in;
+        int* N = S.d_int;
+        // the problem and the nominal go to the device, once
+        copy.up(F, i_w, w); copy.up(F, i_mu, mu);      // where they are per robot
+        copy.up(F, i_al, alpha); copy.up(F, i_lad, ladder);
+        const PlantCost C = plant_cost_up(copy, F, i_cost, P.C);
+        copy.up(F, i_lo, u_lo); copy.up(F, i_hi, u_hi);
+        copy.up(F, m_q, q_nom); copy.up(F, m_u, u_nom); copy.up(F, m_g, gamma_nom); copy.up(F, m_b, b_nom);
+        copy.up(F, m_lq, lin_q_nom); copy.up(F, m_lr, lin_r_nom); copy.up(F, m_J, J_nom);
+        copy.up(N, j_st, status_nom); copy.up(N, j_it, iters_nom); copy.up(N, j_act, ones.data());
+        ok_ = ok_ && hipMemsetAsync(j_lev.on(N), 0, j_lev.n * sizeof(int), st) == hipSuccess && hipMemsetAsync(j_nact.on(N), 0, j_nact.n * sizeof(int), st) == hipSuccess;
         ok_ = ok_ && plant_linesearch_shared(P, w, terrain, ter, W, st);
-        C.Q = F + i_Q; C.Qf = F + i_Qf; C.R = F + i_R; C.x_goal = F + i_xg; C.u_goal = F + i_ug;
-        const PlantIlqrArrays A{F + i_lad, N + j_lev, N + j_act, F + m_J, F + r_rho, F + r_Jn, F + m_q, F + m_u, F + m_g, F + m_b, F + m_lq, F + m_lr,
-                                N + j_st, N + j_it, F + g_K, F + g_k, F + g_dV, N + j_lqs, N + j_cut, N + j_cl, limits ? F + i_lo : nullptr,
-                                limits ? F + i_hi : nullptr, F + i_al, w_each ? F + i_w : nullptr, mu_each ? F + i_mu : nullptr, C, F + o_J, N + j_ok,
-                                N + j_ch, N + j_conv, F + o_q, F + o_z, F + o_u, F + o_g, F + o_b, N + j_cst, N + j_cit, F + o_lq, F + o_lr,
-                                F + h_J, F + h_al, F + h_rho, N + j_hacc, N + j_nact, rho_max, tol};
+        const PlantIlqrArrays A{i_lad.on(F), j_lev.on(N), j_act.on(N), m_J.on(F), r_rho.on(F), r_Jn.on(F), m_q.on(F), m_u.on(F), m_g.on(F), m_b.on(F), m_lq.on(F),
+                                m_lr.on(F), j_st.on(N), j_it.on(N), g_K.on(F), g_k.on(F), g_dV.on(F), j_lqs.on(N), j_cut.on(N), j_cl.on(N), i_lo.or_null(F),
+                                i_hi.or_null(F), i_al.on(F), i_w.or_null(F), i_mu.or_null(F), C, o_J.on(F), j_ok.on(N), j_ch.on(N), j_conv.on(N), o_q.on(F),
+                                o_z.on(F), o_u.on(F), o_g.on(F), o_b.on(F), j_cst.on(N), j_cit.on(N), o_lq.on(F), o_lr.on(F), h_J.on(F), h_al.on(F),
+                                h_rho.on(F), j_hacc.on(N), j_nact.on(N), rho_max, tol};
         for (int it = 0; it < max_iter && ok_; ++it) {
             const PlantTapeBuffers& parent = it == 0 ? caller : bufs[(it - 1) & 1];
             PlantTapeBuffers& fresh = bufs[it & 1];
             ok_ = plant_ilqr_iteration(P, A, it, parent.d_dz, parent.d_status, fresh.d_dz, fresh.d_status, W, st);
             int n_active = 0;      // the iteration's one read
-            down(&n_active, N + j_nact + it, (size_t)1);
+            copy.down(&n_active, N, j_nact.part((size_t)it, 1));
             ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;
             if (ok_) done = it + 1;
             if (n_active == 0) break;
         }
         if (ok_) {      // down, once
             const PlantTapeBuffers& last = bufs[(done - 1) & 1];
-            const size_t hn = (size_t)done * B;
-            down(q, F + m_q, (size_t)(T + 2) * B * nq); down(u_applied, F + m_u, TB * nu); down(gamma, F + m_g, TB * nc); down(b, F + m_b, TB * nb);
-            down(lin_q, F + m_lq, (size_t)(T + 1) * B * n); down(lin_r, F + m_lr, TB * nu); down(status, N + j_st, TB); down(iters, N + j_it, TB);
-            down(grad_status, last.d_status, TB);
-            down(hist_J, F + h_J, hn); down(hist_alpha, F + h_al, hn); down(hist_rho, F + h_rho, hn); down(hist_accepted, N + j_hacc, hn);
-            if (K) down(K, F + g_K, TB * kk);
-            if (k) down(k, F + g_k, TB * nu);
-            if (dV) down(dV, F + g_dV, 2 * nB);
-            if (lq_status) down(lq_status, N + j_lqs, nB);
-            if (n_cut) down(n_cut, N + j_cut, nB);
-            if (clamped) down(clamped, N + j_cl, TB);
+            const size_t hn = (size_t)done * B;      // the history rows that were written
+            copy.down(q, F, m_q); copy.down(u_applied, F, m_u); copy.down(gamma, F, m_g); copy.down(b, F, m_b);
+            copy.down(lin_q, F, m_lq); copy.down(lin_r, F, m_lr); copy.down(status, N, j_st); copy.down(iters, N, j_it);
+            copy.down(grad_status, last.d_status, PlantSpan{0, TB});
+            copy.down(hist_J, F, h_J.part(0, hn)); copy.down(hist_alpha, F, h_al.part(0, hn)); copy.down(hist_rho, F, h_rho.part(0, hn));
+            copy.down(hist_accepted, N, j_hacc.part(0, hn));
+            copy.down(K, F, g_K); copy.down(k, F, g_k); copy.down(dV, F, g_dV);      // the optional outputs: where they are given
+            copy.down(lq_status, N, j_lqs); copy.down(n_cut, N, j_cut); copy.down(clamped, N, j_cl);
         }
         ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;      // this stream only
     }
@@ -263,12 +251,10 @@ extern "C" int cimpc_plant_ilqr(cimpc_plant_tape tape, int steps_per_launch, int
     for (int s = 0; s < 2; ++s)
         if (s != keep) ok_ = bufs[s].release() && ok_;
     if (!ok_ && keep >= 0) (void)bufs[keep].release();
-    if (cur != dev) {
-        const bool back = hipSetDevice(cur) == hipSuccess;
-        if (!back && ok_) (void)bufs[keep].release();
-        ok_ = back && ok_;
+    if (!scope.leave(ok_)) {
+        if (ok_) (void)bufs[keep].release();      // the device could not be restored: the new tape does not outlive the call
+        return CIMPC_ERR_HIP;
     }
-    if (!ok_) return CIMPC_ERR_HIP;
     *n_iter = done;
     *new_tape = new cimpc_plant_tape_s{bufs[keep], tape->model, B, T, n_cols};
     return CIMPC_OK;

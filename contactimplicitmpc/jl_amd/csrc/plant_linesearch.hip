@@ -21,7 +21,6 @@
 #include <cmath>
 #include <mutex>
 #include <string>
-#include <utility>
 #include <vector>
 
 // No fused multiply-adds in this translation unit: the cost rounds as the float64 restatement of the definition does.
@@ -159,14 +158,9 @@ __global__ __launch_bounds__(LS_THREADS) void plant_ls_restore_kernel(const int*
 }
 
 namespace {
-// grow-only device buffers of the entry, per device, next to the plant workspace whose buffers (the candidates' rollout), stream and
-// mutex it uses: the B-robot inputs, the B-robot outputs with J, and the integer outputs
-struct LineSearchWs { double *d_in = nullptr, *d_out = nullptr; int* d_int = nullptr; size_t cap_in = 0, cap_out = 0, cap_int = 0; };
-LineSearchWs g_linesearch_ws[PLANT_MAX_DEVICES];
-
-PlantCost plant_cost_of(const cimpc_tracking_cost& c, int T, int nq, int nu) {
-    return PlantCost{c.Q, c.Qf, c.R, c.x_goal, c.u_goal, c.n_Q, c.n_R, c.n_x, T, nq, nu};
-}
+// the entry's own buffers, beside the candidates' rollout in the plant workspace: the B-robot inputs, the B-robot outputs with J, the
+// integer outputs (plant_linesearch_layout, plant_staging.h)
+PlantStageWs g_linesearch_ws[PLANT_MAX_DEVICES];
 }  // namespace
 
 }  // namespace cimpc
@@ -263,6 +257,12 @@ bool plant_candidates_cost_launch(const PlantCost& C, const double* q, const dou
     return hipGetLastError() == hipSuccess;
 }
 
+bool plant_restore_launch(const int* choice, const double* parent_dz, const int* parent_status, double* dz, int* status, int B, int T, int block,
+                          hipStream_t st) {
+    hipLaunchKernelGGL(plant_ls_restore_kernel, dim3((unsigned)((size_t)T * B)), dim3(LS_THREADS), 0, st, choice, parent_dz, parent_status, dz, status, B, T, block);
+    return hipGetLastError() == hipSuccess;
+}
+
 bool plant_linesearch_stages(const PlantLsPlan& P, const PlantLsArrays& A, PlantWs& W, hipStream_t st) {
     const PlantModel& M = P.M;
     const PlantRolloutLayout& L = P.L;
@@ -293,9 +293,7 @@ bool plant_linesearch_stages(const PlantLsPlan& P, const PlantLsArrays& A, Plant
     const PlantSensSource src{A.Cz, nullptr, A.Cq, A.Cu, !has_w ? nullptr : w_each ? A.w : dw, mu_each ? A.mu : nullptr, A.Cst,
                               P.mu0, P.h, B, T, B, 1, has_w ? P.K_w : 1, has_w ? P.n_w : 1, has_w ? P.hold_w : 1, P.n_mu};
     if (!plant_sensitivity_launch(M, (int)TB, src, rough ? W.d_ter : nullptr, rough ? P.n_terrain : 0, P.reg, n_cols, A.dz, A.status, st)) return false;
-    hipLaunchKernelGGL(plant_ls_restore_kernel, dim3((unsigned)TB), dim3(LS_THREADS), 0, st, A.choice, A.parent_dz, A.parent_status, A.dz, A.status, B, T,
-                       (int)block);
-    return hipGetLastError() == hipSuccess;
+    return plant_restore_launch(A.choice, A.parent_dz, A.parent_status, A.dz, A.status, B, T, (int)block, st);
 }
 
 }  // namespace cimpc
@@ -310,14 +308,14 @@ static int plant_tape_linesearch_call(const char* entry, cimpc_plant_tape tape, 
                                       int* grad_status, cimpc_plant_tape* new_tape, int n_lim, const double* u_lo, const double* u_hi) {
     using namespace cimpc;
     // every refusal leaves its reason where cimpc_last_error(NULL) finds it; what needs no tape is tested before the tape is looked at
-    auto refuse = [entry](const std::string& why) { set_global_error(std::string(entry) + ": " + why); return CIMPC_ERR_INVALID; };
+    auto refuse = [entry](const std::string& why) { return plant_refuse(entry, why); };
     if (!new_tape) return refuse("null new_tape");
     *new_tape = nullptr;
-    const std::pair<const char*, const void*> required[] = {
+    const PlantRequired required[] = {
         {"tape", tape}, {"q_nom", q_nom}, {"u_nom", u_nom}, {"mu", mu}, {"opts", opts}, {"K", K}, {"k", k}, {"dV", dV}, {"J_nom", J_nom}, {"alpha", alpha},
         {"cost", cost}, {"J", J}, {"ok", ok}, {"choice", choice}, {"q", q}, {"u_applied", u_applied}, {"gamma", gamma}, {"b", b}, {"status", status},
         {"iters", iters}, {"lin_q", lin_q}, {"lin_r", lin_r}, {"grad_status", grad_status}};
-    for (const auto& [name, p] : required) if (!p) return refuse(std::string("null ") + name);
+    if (const char* name = plant_first_null(required)) return refuse(std::string("null ") + name);
     PlantLsPlan P;
     if (const char* why = plant_linesearch_plan(PlantLsCall{tape, steps_per_launch, n_terrain, terrain, q_nom, u_nom, w, K_w, n_w, hold_w, mu, n_mu, h, opts,
                                                             n_alpha, alpha, armijo, cost, reg, q, u_applied, gamma, b, status, iters, grad_status, n_lim,
@@ -326,76 +324,57 @@ static int plant_tape_linesearch_call(const char* entry, cimpc_plant_tape tape, 
     const PlantTapeBuffers& parent = tape->buf;
     const PlantModel& M = P.M;
     const PlantRolloutLayout& L = P.L;
-    PlantCost C = P.C;
-    const int B = P.B, T = P.T, n_cols = P.n_cols, nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb(), nz = M.nz(), nw = M.nw, nr = nq + nc + nb, NB = P.NB;
-    const bool limits = P.limits, w_each = P.w_each, mu_each = P.mu_each;
-    const size_t TB = (size_t)T * B, n = (size_t)2 * nq, kk = (size_t)nu * n, block = (size_t)nr * n_cols;
+    const int B = P.B, T = P.T, n_cols = P.n_cols;
+    const size_t TB = (size_t)T * B, block = (size_t)(M.nq + M.nc + M.nb()) * n_cols;
+    // the B-robot inputs in d_in, J and the chosen candidates' rows in d_out, the integers in d_int
+    const PlantLsLayout S = plant_linesearch_layout(M, P.C, PlantLsShape{B, T, P.n_alpha, P.K_w, P.n_lim, P.w_each, P.mu_each, P.limits});
     // the inputs the candidates' law is made of are finite, as cimpc_plant_rollout_feedback asks of K and x_ref
-    auto finite = [](const double* a, size_t cnt) { for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(a[i])) return false; return true; };
-    if (!finite(K, TB * kk)) return refuse("a non-finite entry of K");
-    if (!finite(k, TB * nu)) return refuse("a non-finite entry of k");
-    if (!finite(q_nom, (size_t)(T + 2) * B * nq)) return refuse("a non-finite entry of q_nom");
-    if (!finite(u_nom, TB * nu)) return refuse("a non-finite entry of u_nom");
-    // the B-robot inputs in d_in, in the order they go up
-    size_t at = 0;
-    auto next = [&at](size_t cnt) { const size_t o = at; at += cnt; return o; };
-    const size_t i_q = next((size_t)(T + 2) * B * nq), i_u = next(TB * nu), i_k = next(TB * nu), i_K = next(TB * kk),
-                 i_w = next(w_each ? (size_t)K_w * B * nw : 0), i_mu = next(mu_each ? (size_t)B : 0), i_dV = next((size_t)2 * B), i_Jn = next((size_t)B),
-                 i_al = next((size_t)n_alpha), i_Q = next((size_t)C.n_Q * n * n), i_Qf = next(n * n), i_R = next((size_t)C.n_R * nu * nu),
-                 i_xg = next((size_t)(T + 1) * C.n_x * n), i_ug = next((size_t)T * C.n_x * nu), i_lo = next(limits ? (size_t)n_lim * nu : 0),
-                 i_hi = next(limits ? (size_t)n_lim * nu : 0), n_in = at;
-    at = 0;      // J and the chosen candidates' rows in d_out, in the order they come back
-    const size_t o_J = next((size_t)NB), o_q = next((size_t)(T + 2) * B * nq), o_u = next(TB * nu), o_g = next(TB * nc), o_b = next(TB * nb),
-                 o_lq = next((size_t)(T + 1) * B * n), o_lr = next(TB * nu), o_z = next(TB * nz), n_out = at;
-    at = 0;      // the integers
-    const size_t j_ok = next((size_t)NB), j_ch = next((size_t)B), j_st = next(TB), j_it = next(TB), j_conv = next((size_t)NB), n_int = at;
+    if (!plant_all_finite(K, S.K.n)) return refuse("a non-finite entry of K");
+    if (!plant_all_finite(k, S.k.n)) return refuse("a non-finite entry of k");
+    if (!plant_all_finite(q_nom, S.q_nom.n)) return refuse("a non-finite entry of q_nom");
+    if (!plant_all_finite(u_nom, S.u_nom.n)) return refuse("a non-finite entry of u_nom");
     const std::vector<cimpc_terrain> ter = plant_linesearch_terrains(P, terrain);      // the candidates' terrains: robot b's for every c
 
-    std::lock_guard<std::mutex> lock(g_plant_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
     const int dev = parent.device;
-    if (cur != dev && hipSetDevice(dev) != hipSuccess) return CIMPC_ERR_HIP;
+    PlantDeviceScope scope(dev);
+    if (scope.rc() != CIMPC_OK) return scope.rc();
     bool ok_ = false;
     PlantTapeBuffers buf;
     PlantWs* ws = plant_ws_open(dev);
-    LineSearchWs& S = g_linesearch_ws[dev];
+    PlantStageWs& G = g_linesearch_ws[dev];
     if (ws && plant_grow(&ws->d_in, &ws->cap_in, L.need_in) && plant_grow(&ws->d_out, &ws->cap_out, L.need_out) && plant_grow(&ws->d_st, &ws->cap_st, L.need_st) &&
         plant_grow(&ws->d_ter, &ws->cap_ter, (size_t)P.n_ter) && plant_grow(&ws->d_z, &ws->cap_z, L.need_z) && plant_grow(&ws->d_fb, &ws->cap_fb, L.need_fb) &&
-        plant_grow(&S.d_in, &S.cap_in, n_in) && plant_grow(&S.d_out, &S.cap_out, n_out) && plant_grow(&S.d_int, &S.cap_int, n_int) &&
+        G.grow(S.need_in, S.need_out, S.need_int) &&
         hipMalloc((void**)&buf.d_dz, TB * block * sizeof(double)) == hipSuccess) {      // the new tape's memory, the last to be allocated
         if (hipMalloc((void**)&buf.d_status, TB * sizeof(int)) != hipSuccess) buf.d_status = nullptr;
         buf.device = dev; buf.M = M;
         PlantWs& W = *ws;
         hipStream_t st = W.st;
         ok_ = buf.d_status != nullptr;
-        auto up = [&](auto* d, const auto* hsrc, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(d, hsrc, cnt * sizeof(*d), hipMemcpyHostToDevice, st) == hipSuccess; };
-        auto down = [&](auto* hdst, const auto* d, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(hdst, d, cnt * sizeof(*d), hipMemcpyDeviceToHost, st) == hipSuccess; };
-        double *I = S.d_in, *O = S.d_out;
-        int* N = S.d_int;
-        up(I + i_q, q_nom, (size_t)(T + 2) * B * nq); up(I + i_u, u_nom, TB * nu); up(I + i_k, k, TB * nu); up(I + i_K, K, TB * kk);
-        if (w_each) up(I + i_w, w, (size_t)K_w * B * nw);
-        if (mu_each) up(I + i_mu, mu, (size_t)B);
-        up(I + i_dV, dV, (size_t)2 * B); up(I + i_Jn, J_nom, (size_t)B); up(I + i_al, alpha, (size_t)n_alpha);
-        up(I + i_Q, C.Q, (size_t)C.n_Q * n * n); up(I + i_Qf, C.Qf, n * n); up(I + i_R, C.R, (size_t)C.n_R * nu * nu);
-        up(I + i_xg, C.x_goal, (size_t)(T + 1) * C.n_x * n); up(I + i_ug, C.u_goal, (size_t)T * C.n_x * nu);
-        if (limits) { up(I + i_lo, u_lo, (size_t)n_lim * nu); up(I + i_hi, u_hi, (size_t)n_lim * nu); }
+        PlantStreamCopier copy{{st}, ok_};
+        double *I = G.d_in, *O = G.d_out;
+        int* N = G.d_int;
+        copy.up(I, S.q_nom, q_nom); copy.up(I, S.u_nom, u_nom); copy.up(I, S.k, k); copy.up(I, S.K, K);
+        copy.up(I, S.w, w); copy.up(I, S.mu, mu);      // where they are per robot
+        copy.up(I, S.dV, dV); copy.up(I, S.J_nom, J_nom); copy.up(I, S.alpha, alpha);
+        const PlantCost C = plant_cost_up(copy, I, S.cost, P.C);
+        copy.up(I, S.u_lo, u_lo); copy.up(I, S.u_hi, u_hi);
         ok_ = ok_ && plant_linesearch_shared(P, w, terrain, ter, W, st);
-        C.Q = I + i_Q; C.Qf = I + i_Qf; C.R = I + i_R; C.x_goal = I + i_xg; C.u_goal = I + i_ug;
         if (ok_) {
-            const PlantLsArrays A{I + i_q, I + i_u, I + i_k, I + i_K, w_each ? I + i_w : nullptr, mu_each ? I + i_mu : nullptr, I + i_dV, I + i_Jn, I + i_al,
-                                  limits ? I + i_lo : nullptr, limits ? I + i_hi : nullptr, C, O + o_J, N + j_ok, N + j_ch, N + j_conv, O + o_q, O + o_z,
-                                  O + o_u, O + o_g, O + o_b, N + j_st, N + j_it, O + o_lq, O + o_lr, parent.d_dz, parent.d_status, buf.d_dz, buf.d_status};
+            const PlantLsArrays A{S.q_nom.on(I), S.u_nom.on(I), S.k.on(I), S.K.on(I), S.w.or_null(I), S.mu.or_null(I), S.dV.on(I), S.J_nom.on(I), S.alpha.on(I),
+                                  S.u_lo.or_null(I), S.u_hi.or_null(I), C, S.J.on(O), S.ok.on(N), S.choice.on(N), S.conv.on(N), S.q.on(O), S.z.on(O),
+                                  S.u_applied.on(O), S.gamma.on(O), S.b.on(O), S.status.on(N), S.iters.on(N), S.lin_q.on(O), S.lin_r.on(O), parent.d_dz,
+                                  parent.d_status, buf.d_dz, buf.d_status};
             ok_ = plant_linesearch_stages(P, A, W, st);
         }
-        down(J, O + o_J, (size_t)NB); down(q, O + o_q, (size_t)(T + 2) * B * nq); down(u_applied, O + o_u, TB * nu); down(gamma, O + o_g, TB * nc);
-        down(b, O + o_b, TB * nb); down(lin_q, O + o_lq, (size_t)(T + 1) * B * n); down(lin_r, O + o_lr, TB * nu);
-        down(ok, N + j_ok, (size_t)NB); down(choice, N + j_ch, (size_t)B); down(status, N + j_st, TB); down(iters, N + j_it, TB);
-        down(grad_status, buf.d_status, TB);
+        copy.down(J, O, S.J); copy.down(q, O, S.q); copy.down(u_applied, O, S.u_applied); copy.down(gamma, O, S.gamma);
+        copy.down(b, O, S.b); copy.down(lin_q, O, S.lin_q); copy.down(lin_r, O, S.lin_r);
+        copy.down(ok, N, S.ok); copy.down(choice, N, S.choice); copy.down(status, N, S.status); copy.down(iters, N, S.iters);
+        copy.down(grad_status, buf.d_status, PlantSpan{0, TB});
         ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;      // this stream only
     }
     if (!ok_) (void)buf.release();
-    if (cur != dev) ok_ = (hipSetDevice(cur) == hipSuccess) && ok_;
+    ok_ = scope.leave(ok_);
     if (!ok_) { (void)buf.release(); return CIMPC_ERR_HIP; }
     *new_tape = new cimpc_plant_tape_s{buf, tape->model, B, T, n_cols};
     return CIMPC_OK;
@@ -423,10 +402,7 @@ extern "C" int cimpc_plant_tape_linesearch_box(cimpc_plant_tape tape, int steps_
                                                const cimpc_tracking_cost* cost, double reg, double* J, int* ok, int* choice, double* q,
                                                double* u_applied, double* gamma, double* b, int* status, int* iters, double* lin_q, double* lin_r,
                                                int* grad_status, cimpc_plant_tape* new_tape, int n_lim, const double* u_lo, const double* u_hi) {
-    if ((u_lo == nullptr) != (u_hi == nullptr)) {
-        cimpc::set_global_error("cimpc_plant_tape_linesearch_box: one of u_lo, u_hi without the other");
-        return CIMPC_ERR_INVALID;
-    }
+    if ((u_lo == nullptr) != (u_hi == nullptr)) return cimpc::plant_refuse("cimpc_plant_tape_linesearch_box", "one of u_lo, u_hi without the other");
     return plant_tape_linesearch_call("cimpc_plant_tape_linesearch_box", tape, steps_per_launch, n_terrain, terrain, q_nom, u_nom, w, K_w, n_w, hold_w, mu,
                                       n_mu, h, opts, K, k, dV, J_nom, n_alpha, alpha, armijo, cost, reg, J, ok, choice, q, u_applied, gamma, b, status,
                                       iters, lin_q, lin_r, grad_status, new_tape, n_lim, u_lo, u_hi);

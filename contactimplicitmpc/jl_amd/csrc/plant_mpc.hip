@@ -19,7 +19,6 @@
 #include <cmath>
 #include <mutex>
 #include <string>
-#include <utility>
 #include <vector>
 
 // No fused multiply-adds in this translation unit: the cost rounds as cimpc_plant_tracking_cost does.
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(MPC_THREADS) void plant_mpc_converged_kernel(const 
 
 }  // namespace cimpc
 
-// What a cimpc_plant_mpc points to.  F and N are the handle's doubles and ints; the members named i_*, m_*, ... are offsets into them.
+// What a cimpc_plant_mpc points to.  F and N are the handle's doubles and ints; the members named i_*, m_*, ... are their regions (plant_staging.h).
 struct cimpc_plant_mpc_s {
     cimpc::PlantLsPlan P;
     int device = -1, model = 0, B = 0, H = 0, L = 0, n_x = 1, n_iter = 0;
@@ -106,41 +105,24 @@ struct cimpc_plant_mpc_s {
     cimpc::PlantTapeBuffers tapes[3];    // the warm-start nominal's, and the two that alternate
     std::vector<double> lo, hi;          // the limits on the host (n_lim x nu; empty: none), for the plans cimpc_plant_mpc_reset is given
     // doubles: the problem | the plan's two control buffers | the nominal | the gains | the rules' rows | the line search's outputs | the history
-    size_t i_mu, i_al, i_lad, i_Q, i_Qf, i_R, i_xr, i_ur, i_xg, i_ug, i_lo, i_hi, p_u[2], m_q, m_g, m_b, m_lq, m_lr, m_J, m_J0, m_z, g_K, g_k, g_dV, r_rho,
-        r_Jn, o_J, o_q, o_u, o_g, o_b, o_lq, o_lr, o_z, h_J, h_al, h_rho, n_f;
-    size_t j_st, j_it, j_lev, j_act, j_lqs, j_cut, j_cl, j_ok, j_ch, j_cst, j_cit, j_conv, j_hacc, j_nact, j_done, n_i;
+    // i_ref: Q | Qf | R | x_ref | u_ref, the cost over the reference's L steps; i_xg, i_ug: the goal window of a control step
+    cimpc::PlantCostSpans i_ref;
+    cimpc::PlantSpan i_mu, i_al, i_lad, i_xg, i_ug, i_lo, i_hi, p_u[2], m_q, m_g, m_b, m_lq, m_lr, m_J, m_J0, m_z, g_K, g_k, g_dV, r_rho, r_Jn, o_J, o_q, o_u, o_g,
+        o_b, o_lq, o_lr, o_z, h_J, h_al, h_rho;
+    cimpc::PlantSpan j_st, j_it, j_lev, j_act, j_lqs, j_cut, j_cl, j_ok, j_ch, j_cst, j_cit, j_conv, j_hacc, j_nact, j_done;
+    size_t n_f = 0, n_i = 0;
 };
 
 namespace {
 using namespace cimpc;
 
-int mpc_refuse(const char* entry, const std::string& why) {
-    set_global_error(std::string(entry) + ": " + why);
-    return CIMPC_ERR_INVALID;
-}
-
 // Frees what the handle owns on its device (the caller holds g_plant_mu and has selected the device).
 bool mpc_release(cimpc_plant_mpc_s* h) {
     bool ok = true;
     for (auto& t : h->tapes) ok = t.release() && ok;
-    if (h->F) ok = (hipFree(h->F) == hipSuccess) && ok;
-    if (h->N) ok = (hipFree(h->N) == hipSuccess) && ok;
-    if (h->d_ter) ok = (hipFree(h->d_ter) == hipSuccess) && ok;
-    h->F = nullptr; h->N = nullptr; h->d_ter = nullptr;
-    return ok;
-}
-
-// Runs `body` under the plant mutex on the handle's device; the current device is restored.
-template <class Body>
-int mpc_on_device(cimpc_plant_mpc_s* h, Body&& body) {
-    std::lock_guard<std::mutex> lock(g_plant_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
-    if (cur != h->device && hipSetDevice(h->device) != hipSuccess) return CIMPC_ERR_HIP;
-    bool ok = body();
-    if (cur != h->device) ok = (hipSetDevice(cur) == hipSuccess) && ok;
-    if (!ok) h->failed = true;
-    return ok ? CIMPC_OK : CIMPC_ERR_HIP;
+    ok = plant_free(&h->F) && ok;
+    ok = plant_free(&h->N) && ok;
+    return plant_free(&h->d_ter) && ok;
 }
 
 const char* const MPC_FAILED = "a handle that met a HIP error refuses further use";
@@ -153,12 +135,12 @@ extern "C" int cimpc_plant_mpc_create(int model, int B, int H, int steps_per_lau
                                       int n_cols, int n_ladder, const double* ladder, double rho_max, double tol, int n_iter, int n_lim,
                                       const double* u_lo, const double* u_hi, const double* u0, cimpc_plant_mpc* handle) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { return mpc_refuse("cimpc_plant_mpc_create", why); };
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_mpc_create", why); };
     if (!handle) return refuse("null handle");
     *handle = nullptr;
-    const std::pair<const char*, const void*> required[] = {{"mu", mu}, {"opts", opts}, {"Q", Q}, {"Qf", Qf}, {"R", R}, {"x_ref", x_ref}, {"u_ref", u_ref},
-                                                            {"alpha", alpha}, {"ladder", ladder}, {"u0", u0}};
-    for (const auto& [name, p] : required) if (!p) return refuse(std::string("null ") + name);
+    const PlantRequired required[] = {{"mu", mu}, {"opts", opts}, {"Q", Q}, {"Qf", Qf}, {"R", R}, {"x_ref", x_ref}, {"u_ref", u_ref},
+                                      {"alpha", alpha}, {"ladder", ladder}, {"u0", u0}};
+    if (const char* name = plant_first_null(required)) return refuse(std::string("null ") + name);
     if (const char* why = plant_mpc_problem_refusal(H, L, n_iter)) return refuse(why);
     if (const char* why = plant_ilqr_refusal(n_iter, n_ladder, ladder, rho_max, tol)) return refuse(why);
     // the stand-in for the parent tape of cimpc_plant_ilqr: its sizes and model; its memory is the handle's, allocated below
@@ -190,30 +172,31 @@ extern "C" int cimpc_plant_mpc_create(int model, int B, int H, int steps_per_lau
     S.rho_max = rho_max; S.tol = tol;
     const bool limits = P.limits, mu_each = P.mu_each;
     if (limits) { S.lo.assign(u_lo, u_lo + (size_t)n_lim * nu); S.hi.assign(u_hi, u_hi + (size_t)n_lim * nu); }
-    const size_t TB = (size_t)T * B, n = (size_t)2 * nq, kk = (size_t)nu * n, block = (size_t)nr * n_cols, nB = (size_t)B;
-    size_t at = 0;
-    auto next = [&at](size_t cnt) { const size_t o = at; at += cnt; return o; };
-    S.i_mu = next(mu_each ? nB : 0); S.i_al = next((size_t)n_alpha); S.i_lad = next((size_t)n_ladder); S.i_Q = next((size_t)n_Q * n * n); S.i_Qf = next(n * n);
-    S.i_R = next((size_t)n_R * nu * nu); S.i_xr = next((size_t)(L + 1) * n_x * n); S.i_ur = next((size_t)L * n_x * nu);
-    S.i_xg = next((size_t)(T + 1) * n_x * n); S.i_ug = next((size_t)T * n_x * nu); S.i_lo = next(limits ? (size_t)n_lim * nu : 0);
-    S.i_hi = next(limits ? (size_t)n_lim * nu : 0);
-    S.p_u[0] = next(TB * nu); S.p_u[1] = next(TB * nu);
-    S.m_q = next((size_t)(T + 2) * B * nq); S.m_g = next(TB * nc); S.m_b = next(TB * nb); S.m_lq = next((size_t)(T + 1) * B * n); S.m_lr = next(TB * nu);
-    S.m_J = next(nB); S.m_J0 = next(nB); S.m_z = next(TB * nz);
-    S.g_K = next(TB * kk); S.g_k = next(TB * nu); S.g_dV = next(2 * nB); S.r_rho = next(nB); S.r_Jn = next(nB);
-    S.o_J = next((size_t)NB); S.o_q = next((size_t)(T + 2) * B * nq); S.o_u = next(TB * nu); S.o_g = next(TB * nc); S.o_b = next(TB * nb);
-    S.o_lq = next((size_t)(T + 1) * B * n); S.o_lr = next(TB * nu); S.o_z = next(TB * nz);
-    S.h_J = next((size_t)n_iter * B); S.h_al = next((size_t)n_iter * B); S.h_rho = next((size_t)n_iter * B); S.n_f = at;
-    at = 0;
-    S.j_st = next(TB); S.j_it = next(TB); S.j_lev = next(nB); S.j_act = next(nB); S.j_lqs = next(nB); S.j_cut = next(nB); S.j_cl = next(TB);
-    S.j_ok = next((size_t)NB); S.j_ch = next(nB); S.j_cst = next(TB); S.j_cit = next(TB); S.j_conv = next((size_t)NB); S.j_hacc = next((size_t)n_iter * B);
-    S.j_nact = next((size_t)n_iter); S.j_done = next(nB); S.n_i = at;
+    const size_t TB = (size_t)T * B, n = (size_t)2 * nq, kk = (size_t)nu * n, block = (size_t)nr * n_cols, nB = (size_t)B, traj = (size_t)(T + 2) * B * nq;
+    const PlantCost reference = plant_cost_of(cost, L, nq, nu);      // the weights, and x_ref, u_ref as the goals of L steps
+    PlantCursor at;
+    S.i_mu = at.take(mu_each ? nB : 0); S.i_al = at.take((size_t)n_alpha); S.i_lad = at.take((size_t)n_ladder);
+    S.i_ref = plant_cost_spans(at, reference);
+    S.i_xg = at.take((size_t)(T + 1) * n_x * n); S.i_ug = at.take((size_t)T * n_x * nu);
+    S.i_lo = at.take(limits ? (size_t)n_lim * nu : 0); S.i_hi = at.take(limits ? (size_t)n_lim * nu : 0);
+    S.p_u[0] = at.take(TB * nu); S.p_u[1] = at.take(TB * nu);
+    S.m_q = at.take(traj); S.m_g = at.take(TB * nc); S.m_b = at.take(TB * nb); S.m_lq = at.take((size_t)(T + 1) * B * n); S.m_lr = at.take(TB * nu);
+    S.m_J = at.take(nB); S.m_J0 = at.take(nB); S.m_z = at.take(TB * nz);
+    S.g_K = at.take(TB * kk); S.g_k = at.take(TB * nu); S.g_dV = at.take(2 * nB); S.r_rho = at.take(nB); S.r_Jn = at.take(nB);
+    S.o_J = at.take((size_t)NB); S.o_q = at.take(traj); S.o_u = at.take(TB * nu); S.o_g = at.take(TB * nc); S.o_b = at.take(TB * nb);
+    S.o_lq = at.take((size_t)(T + 1) * B * n); S.o_lr = at.take(TB * nu); S.o_z = at.take(TB * nz);
+    S.h_J = at.take((size_t)n_iter * B); S.h_al = at.take((size_t)n_iter * B); S.h_rho = at.take((size_t)n_iter * B);
+    S.n_f = at.end();
+    S.j_st = at.take(TB); S.j_it = at.take(TB); S.j_lev = at.take(nB); S.j_act = at.take(nB); S.j_lqs = at.take(nB); S.j_cut = at.take(nB); S.j_cl = at.take(TB);
+    S.j_ok = at.take((size_t)NB); S.j_ch = at.take(nB); S.j_cst = at.take(TB); S.j_cit = at.take(TB); S.j_conv = at.take((size_t)NB);
+    S.j_hacc = at.take((size_t)n_iter * B); S.j_nact = at.take((size_t)n_iter); S.j_done = at.take(nB);
+    S.n_i = at.end();
     const std::vector<cimpc_terrain> ter = plant_linesearch_terrains(P, terrain);      // the candidates' terrains: robot b's for every c
 
     int dev = 0;
     if (!plant_current_device(&dev)) { delete hd; return CIMPC_ERR_NO_DEVICE; }
     S.device = dev;
-    const int rc = mpc_on_device(hd, [&]() {
+    const int rc = plant_handle_on_device(hd, [&]() {
         PlantWs* ws = plant_ws_open(dev);
         if (!ws) return false;
         bool ok_ = hipMalloc((void**)&S.F, S.n_f * sizeof(double)) == hipSuccess;
@@ -227,24 +210,23 @@ extern "C" int cimpc_plant_mpc_create(int model, int B, int H, int steps_per_lau
             if (ok_ && hipMalloc((void**)&t.d_status, TB * sizeof(int)) != hipSuccess) { t.d_status = nullptr; ok_ = false; }
         }
         hipStream_t st = ws->st;
-        auto up = [&](auto* d, const auto* hsrc, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(d, hsrc, cnt * sizeof(*d), hipMemcpyHostToDevice, st) == hipSuccess; };
+        PlantStreamCopier copy{{st}, ok_};
         double* F = S.F;
         if (ok_) {
             ok_ = hipMemsetAsync(F, 0, S.n_f * sizeof(double), st) == hipSuccess && hipMemsetAsync(S.N, 0, S.n_i * sizeof(int), st) == hipSuccess;
-            if (mu_each) up(F + S.i_mu, mu, nB);
-            up(F + S.i_al, alpha, (size_t)n_alpha); up(F + S.i_lad, ladder, (size_t)n_ladder);
-            up(F + S.i_Q, Q, (size_t)n_Q * n * n); up(F + S.i_Qf, Qf, n * n); up(F + S.i_R, R, (size_t)n_R * nu * nu);
-            up(F + S.i_xr, x_ref, (size_t)(L + 1) * n_x * n); up(F + S.i_ur, u_ref, (size_t)L * n_x * nu);
-            if (limits) { up(F + S.i_lo, u_lo, (size_t)n_lim * nu); up(F + S.i_hi, u_hi, (size_t)n_lim * nu); }
-            up(F + S.p_u[0], u0, TB * nu);
-            if (P.rough) up(S.d_ter, P.ter_each ? ter.data() : terrain, (size_t)P.n_ter);
+            copy.up(F, S.i_mu, mu);      // where it is per robot
+            copy.up(F, S.i_al, alpha); copy.up(F, S.i_lad, ladder);
+            (void)plant_cost_up(copy, F, S.i_ref, reference);
+            copy.up(F, S.i_lo, u_lo); copy.up(F, S.i_hi, u_hi);
+            copy.up(F, S.p_u[0], u0);
+            if (P.rough) copy.up(S.d_ter, PlantSpan{0, (size_t)P.n_ter}, P.ter_each ? ter.data() : terrain);
         }
         ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;      // the host arrays are the caller's: nothing of them is read after the return
         if (!ok_) (void)mpc_release(hd);
         return ok_;
     });
     if (rc != CIMPC_OK) { delete hd; return rc; }
-    S.P.C.Q = S.F + S.i_Q; S.P.C.Qf = S.F + S.i_Qf; S.P.C.R = S.F + S.i_R; S.P.C.x_goal = S.F + S.i_xg; S.P.C.u_goal = S.F + S.i_ug;
+    S.P.C = plant_cost_on(S.P.C, S.F, PlantCostSpans{S.i_ref.Q, S.i_ref.Qf, S.i_ref.R, S.i_xg, S.i_ug});      // the weights, and the goal window
     S.cur = 0; S.has_plan = true;
     *handle = hd;
     return CIMPC_OK;
@@ -253,11 +235,11 @@ extern "C" int cimpc_plant_mpc_create(int model, int B, int H, int steps_per_lau
 extern "C" int cimpc_plant_mpc_control(cimpc_plant_mpc handle, int s, int shift, const double* q0, const double* q1, double* u, double* J0, double* hist_J,
                                        double* hist_alpha, double* hist_rho, int* hist_accepted, int* n_done, int* converged) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { return mpc_refuse("cimpc_plant_mpc_control", why); };
-    const std::pair<const char*, const void*> required[] = {{"handle", handle}, {"q0", q0}, {"q1", q1}, {"u", u}, {"J0", J0}, {"hist_J", hist_J},
-                                                            {"hist_alpha", hist_alpha}, {"hist_rho", hist_rho}, {"hist_accepted", hist_accepted},
-                                                            {"n_done", n_done}, {"converged", converged}};
-    for (const auto& [name, p] : required) if (!p) return refuse(std::string("null ") + name);
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_mpc_control", why); };
+    const PlantRequired required[] = {{"handle", handle}, {"q0", q0}, {"q1", q1}, {"u", u}, {"J0", J0}, {"hist_J", hist_J},
+                                      {"hist_alpha", hist_alpha}, {"hist_rho", hist_rho}, {"hist_accepted", hist_accepted},
+                                      {"n_done", n_done}, {"converged", converged}};
+    if (const char* name = plant_first_null(required)) return refuse(std::string("null ") + name);
     cimpc_plant_mpc_s& S = *handle;
     if (S.failed) return refuse(MPC_FAILED);
     if (const char* why = plant_mpc_step_refusal(s, shift, S.has_plan)) return refuse(why);
@@ -268,7 +250,7 @@ extern "C" int cimpc_plant_mpc_control(cimpc_plant_mpc handle, int s, int shift,
     const size_t TB = (size_t)T * B, nB = (size_t)B, row = nB * nq;
     if (const char* why = plant_mpc_state_refusal(q0, q1, row)) return refuse(why);
     int done = 0;
-    const int rc = mpc_on_device(handle, [&]() {
+    const int rc = plant_handle_on_device(handle, [&]() {
         PlantWs* ws = plant_ws_open(S.device);
         // the workspace grows only when another call has not yet made it as large: no allocation from the second control step on
         if (!ws || !plant_grow(&ws->d_in, &ws->cap_in, Lw.need_in) || !plant_grow(&ws->d_out, &ws->cap_out, Lw.need_out) ||
@@ -278,62 +260,61 @@ extern "C" int cimpc_plant_mpc_control(cimpc_plant_mpc handle, int s, int shift,
         PlantWs& W = *ws;
         hipStream_t st = W.st;
         bool ok_ = true;
-        auto up = [&](auto* d, const auto* hsrc, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(d, hsrc, cnt * sizeof(*d), hipMemcpyHostToDevice, st) == hipSuccess; };
-        auto down = [&](auto* hdst, const auto* d, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(hdst, d, cnt * sizeof(*d), hipMemcpyDeviceToHost, st) == hipSuccess; };
+        PlantStreamCopier copy{{st}, ok_};
         double* F = S.F;
         int* N = S.N;
-        double *u_plan = F + S.p_u[S.cur], *u_nom = F + S.p_u[1 - S.cur];
-        const double* d_mu = P.mu_each ? F + S.i_mu : nullptr;
-        up(F + S.m_q, q0, row); up(F + S.m_q + row, q1, row);      // up: 2 B nq doubles
+        double *u_plan = S.p_u[S.cur].on(F), *u_nom = S.p_u[1 - S.cur].on(F);
+        const double* d_mu = S.i_mu.or_null(F);
+        copy.up(F, S.m_q.part(0, row), q0); copy.up(F, S.m_q.part(row, row), q1);      // 2 B nq doubles
         if (P.rough)      // the workspace's terrains, which another plant call may have overwritten
             ok_ = ok_ && hipMemcpyAsync(W.d_ter, S.d_ter, (size_t)P.n_ter * sizeof(cimpc_terrain), hipMemcpyDeviceToDevice, st) == hipSuccess;
         if (ok_) {
-            const PlantMpcBegin Bg{u_plan, u_nom, F + S.i_xr, F + S.i_ur, F + S.i_xg, F + S.i_ug, N + S.j_lev, N + S.j_act, N + S.j_nact, F + S.h_J, F + S.h_al,
-                                   F + S.h_rho, N + S.j_hacc, B, H, S.L, S.n_x, nq, nu, n_iter, s, shift};
+            const PlantMpcBegin Bg{u_plan, u_nom, S.i_ref.x_goal.on(F), S.i_ref.u_goal.on(F), S.i_xg.on(F), S.i_ug.on(F), S.j_lev.on(N), S.j_act.on(N), S.j_nact.on(N), S.h_J.on(F), S.h_al.on(F),
+                                   S.h_rho.on(F), S.j_hacc.on(N), B, H, S.L, S.n_x, nq, nu, n_iter, s, shift};
             hipLaunchKernelGGL(plant_mpc_begin_kernel, dim3((unsigned)((H + 1) * B)), dim3(MPC_THREADS), 0, st, Bg);
             ok_ = hipGetLastError() == hipSuccess;
         }
         if (ok_) {      // the first rollout of the control step, as cimpc_plant_rollout_tape runs it: rows are kept whether or not a step converged
-            const PlantStepArrays R{F + S.m_q, u_nom, nullptr, d_mu, F + S.m_g, F + S.m_b, N + S.j_st, N + S.j_it, P.mu0, P.h, H, B, 1, 1, 1, 1, P.n_mu,
-                                    F + S.m_z, PlantFeedback{}, nullptr, nullptr};
+            const PlantStepArrays R{S.m_q.on(F), u_nom, nullptr, d_mu, S.m_g.on(F), S.m_b.on(F), S.j_st.on(N), S.j_it.on(N), P.mu0, P.h, H, B, 1, 1, 1, 1, P.n_mu,
+                                    S.m_z.on(F), PlantFeedback{}, nullptr, nullptr};
             ok_ = plant_step_chunks(M, P.rough, P.opts, B, T, P.steps_per_launch, R, P.rough ? W.d_ter : nullptr, P.rough ? P.n_terrain : 0, st);
         }
         if (ok_) {
-            const PlantSensSource src{F + S.m_z, nullptr, F + S.m_q, u_nom, nullptr, d_mu, N + S.j_st, P.mu0, P.h, B, H, B, 1, 1, 1, 1, P.n_mu};
+            const PlantSensSource src{S.m_z.on(F), nullptr, S.m_q.on(F), u_nom, nullptr, d_mu, S.j_st.on(N), P.mu0, P.h, B, H, B, 1, 1, 1, 1, P.n_mu};
             ok_ = plant_sensitivity_launch(M, (int)TB, src, P.rough ? W.d_ter : nullptr, P.rough ? P.n_terrain : 0, P.reg, P.n_cols, S.tapes[0].d_dz,
                                            S.tapes[0].d_status, st);
         }
         if (ok_) {
-            hipLaunchKernelGGL(plant_mpc_nominal_kernel, dim3((unsigned)B), dim3(MPC_THREADS), 0, st, P.C, (const double*)(F + S.m_q), (const double*)u_nom,
-                               F + S.m_lq, F + S.m_lr, F + S.m_J, F + S.m_J0, B);
+            hipLaunchKernelGGL(plant_mpc_nominal_kernel, dim3((unsigned)B), dim3(MPC_THREADS), 0, st, P.C, (const double*)S.m_q.on(F), (const double*)u_nom,
+                               S.m_lq.on(F), S.m_lr.on(F), S.m_J.on(F), S.m_J0.on(F), B);
             ok_ = hipGetLastError() == hipSuccess;
         }
-        const bool limits = P.limits;
-        const PlantIlqrArrays A{F + S.i_lad, N + S.j_lev, N + S.j_act, F + S.m_J, F + S.r_rho, F + S.r_Jn, F + S.m_q, u_nom, F + S.m_g, F + S.m_b, F + S.m_lq,
-                                F + S.m_lr, N + S.j_st, N + S.j_it, F + S.g_K, F + S.g_k, F + S.g_dV, N + S.j_lqs, N + S.j_cut, N + S.j_cl,
-                                limits ? F + S.i_lo : nullptr, limits ? F + S.i_hi : nullptr, F + S.i_al, nullptr, d_mu, P.C, F + S.o_J, N + S.j_ok, N + S.j_ch,
-                                N + S.j_conv, F + S.o_q, F + S.o_z, F + S.o_u, F + S.o_g, F + S.o_b, N + S.j_cst, N + S.j_cit, F + S.o_lq, F + S.o_lr,
-                                F + S.h_J, F + S.h_al, F + S.h_rho, N + S.j_hacc, N + S.j_nact, S.rho_max, S.tol};
+        const PlantIlqrArrays A{S.i_lad.on(F), S.j_lev.on(N), S.j_act.on(N), S.m_J.on(F), S.r_rho.on(F), S.r_Jn.on(F), S.m_q.on(F), u_nom, S.m_g.on(F), S.m_b.on(F), S.m_lq.on(F),
+                                S.m_lr.on(F), S.j_st.on(N), S.j_it.on(N), S.g_K.on(F), S.g_k.on(F), S.g_dV.on(F), S.j_lqs.on(N), S.j_cut.on(N), S.j_cl.on(N),
+                                S.i_lo.or_null(F), S.i_hi.or_null(F), S.i_al.on(F), nullptr, d_mu, P.C, S.o_J.on(F), S.j_ok.on(N), S.j_ch.on(N),
+                                S.j_conv.on(N), S.o_q.on(F), S.o_z.on(F), S.o_u.on(F), S.o_g.on(F), S.o_b.on(F), S.j_cst.on(N), S.j_cit.on(N), S.o_lq.on(F), S.o_lr.on(F),
+                                S.h_J.on(F), S.h_al.on(F), S.h_rho.on(F), S.j_hacc.on(N), S.j_nact.on(N), S.rho_max, S.tol};
         for (int it = 0; it < n_iter && ok_; ++it) {      // iteration 0's parent is the warm-start nominal's buffer; then the two alternate
             const PlantTapeBuffers& parent = S.tapes[it == 0 ? 0 : 1 + ((it - 1) & 1)];
             PlantTapeBuffers& fresh = S.tapes[1 + (it & 1)];
             ok_ = plant_ilqr_iteration(P, A, it, parent.d_dz, parent.d_status, fresh.d_dz, fresh.d_status, W, st);
             int n_active = 0;      // the iteration's one read
-            down(&n_active, N + S.j_nact + it, (size_t)1);
+            copy.down(&n_active, N, S.j_nact.part((size_t)it, 1));
             ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;
             if (ok_) done = it + 1;
             if (n_active == 0) break;
         }
         if (ok_) {
             hipLaunchKernelGGL(plant_mpc_converged_kernel, dim3((unsigned)((B + MPC_THREADS - 1) / MPC_THREADS)), dim3(MPC_THREADS), 0, st,
-                               (const int*)(N + S.j_st), N + S.j_done, B, H);
+                               (const int*)S.j_st.on(N), S.j_done.on(N), B, H);
             ok_ = hipGetLastError() == hipSuccess;
         }
         if (ok_) {      // down: what the signature names
-            const size_t hn = (size_t)done * B;
-            down(u, u_nom, nB * nu); down(J0, F + S.m_J0, nB);
-            down(hist_J, F + S.h_J, hn); down(hist_alpha, F + S.h_al, hn); down(hist_rho, F + S.h_rho, hn); down(hist_accepted, N + S.j_hacc, hn);
-            down(converged, N + S.j_done, nB);
+            const size_t hn = (size_t)done * B;      // the history rows that were written
+            copy.down(u, F, S.p_u[1 - S.cur].part(0, nB * nu)); copy.down(J0, F, S.m_J0);
+            copy.down(hist_J, F, S.h_J.part(0, hn)); copy.down(hist_alpha, F, S.h_al.part(0, hn)); copy.down(hist_rho, F, S.h_rho.part(0, hn));
+            copy.down(hist_accepted, N, S.j_hacc.part(0, hn));
+            copy.down(converged, N, S.j_done);
         }
         ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;      // this stream only
         return ok_;
@@ -346,30 +327,26 @@ extern "C" int cimpc_plant_mpc_control(cimpc_plant_mpc handle, int s, int shift,
 
 extern "C" int cimpc_plant_mpc_plan(cimpc_plant_mpc handle, double* u, double* q, double* gamma, double* b, int* status, int* iters) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { return mpc_refuse("cimpc_plant_mpc_plan", why); };
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_mpc_plan", why); };
     if (!handle) return refuse("null handle");
     cimpc_plant_mpc_s& S = *handle;
     if (S.failed) return refuse(MPC_FAILED);
     if (!S.has_plan) return refuse("no plan loaded");
-    const PlantModel& M = S.P.M;
-    const size_t TB = (size_t)S.H * S.B;
-    return mpc_on_device(handle, [&]() {
+    return plant_handle_on_device(handle, [&]() {
         PlantWs* ws = plant_ws_open(S.device);
         if (!ws) return false;
         hipStream_t st = ws->st;
         bool ok_ = true;
-        auto down = [&](auto* hdst, const auto* d, size_t cnt) {
-            if (hdst) ok_ = ok_ && hipMemcpyAsync(hdst, d, cnt * sizeof(*d), hipMemcpyDeviceToHost, st) == hipSuccess;
-        };
-        down(u, S.F + S.p_u[S.cur], TB * M.nu); down(q, S.F + S.m_q, (size_t)(S.H + 2) * S.B * M.nq); down(gamma, S.F + S.m_g, TB * M.nc);
-        down(b, S.F + S.m_b, TB * M.nb()); down(status, S.N + S.j_st, TB); down(iters, S.N + S.j_it, TB);
+        PlantStreamCopier copy{{st}, ok_};      // every output is optional
+        copy.down(u, S.F, S.p_u[S.cur]); copy.down(q, S.F, S.m_q); copy.down(gamma, S.F, S.m_g);
+        copy.down(b, S.F, S.m_b); copy.down(status, S.N, S.j_st); copy.down(iters, S.N, S.j_it);
         return (hipStreamSynchronize(st) == hipSuccess) && ok_;
     });
 }
 
 extern "C" int cimpc_plant_mpc_reset(cimpc_plant_mpc handle, const double* u0) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { return mpc_refuse("cimpc_plant_mpc_reset", why); };
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_mpc_reset", why); };
     if (!handle) return refuse("null handle");
     if (!u0) return refuse("null u0");
     cimpc_plant_mpc_s& S = *handle;
@@ -377,11 +354,12 @@ extern "C" int cimpc_plant_mpc_reset(cimpc_plant_mpc handle, const double* u0) {
     const PlantLsPlan& P = S.P;
     const int nu = P.M.nu;
     if (const char* why = plant_mpc_plan_refusal(u0, S.H, S.B, nu, P.limits ? S.lo.data() : nullptr, P.limits ? S.hi.data() : nullptr, P.n_lim)) return refuse(why);
-    const size_t cnt = (size_t)S.H * S.B * nu;
-    const int rc = mpc_on_device(handle, [&]() {
+    const int rc = plant_handle_on_device(handle, [&]() {
         PlantWs* ws = plant_ws_open(S.device);
         if (!ws) return false;
-        const bool ok_ = hipMemcpyAsync(S.F + S.p_u[S.cur], u0, cnt * sizeof(double), hipMemcpyHostToDevice, ws->st) == hipSuccess;
+        bool ok_ = true;
+        PlantStreamCopier copy{{ws->st}, ok_};
+        copy.up(S.F, S.p_u[S.cur], u0);
         return (hipStreamSynchronize(ws->st) == hipSuccess) && ok_;
     });
     if (rc == CIMPC_OK) S.has_plan = true;
@@ -401,16 +379,10 @@ extern "C" int cimpc_plant_mpc_dims(cimpc_plant_mpc handle, int* model, int* B, 
 extern "C" int cimpc_plant_mpc_destroy(cimpc_plant_mpc handle) {
     using namespace cimpc;
     if (!handle) return CIMPC_OK;
-    bool ok = true;
+    bool ok = false;
     {
-        std::lock_guard<std::mutex> lock(g_plant_mu);      // no call is using the handle
-        int cur = -1;
-        const int dev = handle->device;
-        ok = hipGetDevice(&cur) == hipSuccess && (cur == dev || hipSetDevice(dev) == hipSuccess);
-        if (ok) {
-            ok = mpc_release(handle);
-            if (cur != dev) ok = (hipSetDevice(cur) == hipSuccess) && ok;
-        }
+        PlantDeviceScope scope(handle->device);      // no call is using the handle
+        if (scope.rc() == CIMPC_OK) ok = scope.leave(mpc_release(handle));
     }
     delete handle;
     return ok ? CIMPC_OK : CIMPC_ERR_HIP;

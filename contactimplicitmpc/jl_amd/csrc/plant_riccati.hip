@@ -45,27 +45,7 @@ constexpr int RIC_THREADS = 256;
 constexpr int RIC_STAGE_DOUBLES = 4;      // per lane: a corner of up to 1024 doubles (18 x 48 = 864 at the largest model) is wholly in flight
 
 // the workgroup as the team of plant_riccati.h
-struct PlantRiccatiGroup {
-    double stage[RIC_STAGE_DOUBLES];
-    __device__ int rank() const { return threadIdx.x; }
-    __device__ int size() const { return RIC_THREADS; }
-    __device__ void sync() const { __syncthreads(); }
-    __device__ void fetch_issue(const double* src, int rows, int cols, int ld) {
-#pragma unroll
-        for (int k = 0; k < RIC_STAGE_DOUBLES; ++k) {
-            const int i = k * RIC_THREADS + (int)threadIdx.x;
-            stage[k] = i < rows * cols ? src[(size_t)(i / rows) * ld + i % rows] : 0.0;
-        }
-    }
-    __device__ void fetch_commit(double* dst, const double* src, int rows, int cols, int ld) {
-#pragma unroll
-        for (int k = 0; k < RIC_STAGE_DOUBLES; ++k) {
-            const int i = k * RIC_THREADS + (int)threadIdx.x;
-            if (i < rows * cols) dst[i] = stage[k];
-        }
-        for (int i = RIC_STAGE_DOUBLES * RIC_THREADS + (int)threadIdx.x; i < rows * cols; i += RIC_THREADS) dst[i] = src[(size_t)(i / rows) * ld + i % rows];
-    }
-};
+using PlantRiccatiGroup = PlantCornerTeam<RIC_THREADS, RIC_STAGE_DOUBLES>;
 
 template <bool LIN, bool BOX = false>      // LIN: the chain with the linear cost terms q, r; BOX: with control limits and a rho per robot
 __global__ __launch_bounds__(RIC_THREADS) void plant_riccati_kernel(PlantRiccati L) {
@@ -86,9 +66,7 @@ __global__ __launch_bounds__(RIC_THREADS) void plant_riccati_shoot_kernel(PlantR
 }
 
 namespace {
-// grow-only device buffers of the entry, one pair per device, next to the plant workspace whose stream and mutex it uses
-struct RiccatiWs { double *d_in = nullptr, *d_out = nullptr; size_t cap_in = 0, cap_out = 0; };
-RiccatiWs g_riccati_ws[PLANT_MAX_DEVICES];
+PlantStageWs g_riccati_ws[PLANT_MAX_DEVICES];      // d_in: the packed upload; d_out: the packed read-back, its ints included
 }  // namespace
 
 // The limited chain for a caller whose arrays are on the device already (plant_stage_launch.h): cimpc_plant_tape_lqr_box below, and the
@@ -112,7 +90,8 @@ static bool plant_riccati_shoot_launch(const PlantRiccati& L, hipStream_t st) {
 }  // namespace cimpc
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------
-// Validate (no device needed), then on the tape's device and the plant workspace's private stream: one upload (Q | Qf | R | q | r, and
+// Validate (no device needed), lay the two packs out (plant_staging.h: an array's extent is stated once, where its region is taken), then
+// on the tape's device and the plant workspace's private stream: one upload (Q | Qf | R | q | r, and
 // for the limited pass rho | u_lo | u_hi | u_nom), one launch, one read-back (K | k | P0 | p0 | dV | status | n_cut | clamped), one
 // synchronize.  box: the call came through cimpc_plant_tape_lqr_box; every refusal leaves its reason for cimpc_last_error(NULL).
 // shoot: it came through cimpc_plant_tape_lqr_shooting, with defects ((T / seg_len - 1) x B x 2nq) behind u_nom in the upload.
@@ -121,7 +100,7 @@ static int plant_tape_lqr_call(const char* entry, bool box, cimpc_plant_tape tap
                                double* P0, double* p0, double* dV, int* status, int* n_cut, int n_lim, const double* u_lo, const double* u_hi,
                                const double* u_nom, int* clamped, bool shoot = false, int seg_len = 0, const double* defects = nullptr) {
     using namespace cimpc;
-    auto refuse = [entry](const char* why) { set_global_error(std::string(entry) + ": " + why); return CIMPC_ERR_INVALID; };
+    auto refuse = [entry](const char* why) { return plant_refuse(entry, why); };
     if (!tape || !Q || !Qf || !R || !K || !status || !n_cut || !rho_b) return refuse("a null tape, Q, Qf, R, K, status, n_cut or rho");
     if (laps < 1 || n_Q < 1 || n_R < 1 || n_keep < 1) return refuse("laps, n_Q, n_R or n_keep below 1");
     const bool limits = u_lo || u_hi;
@@ -162,63 +141,53 @@ static int plant_tape_lqr_call(const char* entry, bool box, cimpc_plant_tape tap
     const int nq = M.nq, nu = M.nu, nr = M.nq + M.nc + M.nb();
     if (nu < 1 || n_cols < 2 * nq + nu || !plant_riccati_fits(nq, nu)) return refuse("a model without controls, or a tape without the control columns");
     if (box && q && (nu > PLANT_BOXQP_MAX_M || plant_riccati_box_lds(nq, nu) > PLANT_RIC_MAX_LDS)) return refuse("a model too large for the limited pass");
-    if (limits)
-        for (size_t e = 0; e < (size_t)T * B * nu; ++e)
-            if (!std::isfinite(u_nom[e])) return refuse("a non-finite entry of u_nom");
-    const size_t i_def = shoot ? (size_t)(T / seg_len - 1) * B * 2 * nq : 0;
-    for (size_t e = 0; e < i_def; ++e)
-        if (!std::isfinite(defects[e])) return refuse("a non-finite entry of defects");
+    if (limits && !plant_all_finite(u_nom, (size_t)T * B * nu)) return refuse("a non-finite entry of u_nom");
+    const size_t n = (size_t)2 * nq, m = (size_t)nu, nn = n * n, mm = m * m, nB = (size_t)B;
+    const size_t n_def = shoot ? (size_t)(T / seg_len - 1) * B * n : 0;
+    if (!plant_all_finite(defects, n_def)) return refuse("a non-finite entry of defects");
     const bool boxed = box && q;                                          // the limited chain: plant_riccati_kernel<true, true>
     const double rho = rho_b[0];
-    const size_t n = (size_t)2 * nq, m = (size_t)nu, nn = n * n, mm = m * m, nB = (size_t)B;
-    // the staging buffers, in the order of the argument list
-    const size_t i_Q = (size_t)n_Q * nn, i_R = (size_t)n_R * mm, i_q = q ? (size_t)(T + 1) * nB * n : 0, i_r = r ? (size_t)T * nB * m : 0;
-    const size_t i_rho = boxed ? (size_t)n_rho : 0, i_lim = limits ? (size_t)n_lim * m : 0, i_un = limits ? (size_t)T * nB * m : 0;
-    const size_t o_Qf = i_Q, o_R = o_Qf + nn, o_q = o_R + i_R, o_r = o_q + i_q, o_rho = o_r + i_r, o_lo = o_rho + i_rho, o_hi = o_lo + i_lim,
-                 o_un = o_hi + i_lim, o_def = o_un + i_un, n_in = o_def + i_def;
-    const size_t n_K = (size_t)n_keep * nB * m * n, n_k = k ? (size_t)n_keep * nB * m : 0, n_P = P0 ? nB * nn : 0, n_p = p0 ? nB * n : 0,
-                 n_V = dV ? nB * 2 : 0;
-    const size_t o_k = n_K, o_P = o_k + n_k, o_p = o_P + n_P, o_V = o_p + n_p, o_st = o_V + n_V, o_cl = o_st + nB,      // 2 B ints in B doubles
-                 n_cl = boxed && clamped ? ((size_t)n_keep * nB + 1) / 2 : 0, n_out = o_cl + n_cl;
+    // the packed upload, in the order of the argument list; an array the call does not have takes no room
+    PlantCursor at;
+    const PlantSpan i_Q = at.take((size_t)n_Q * nn), i_Qf = at.take(nn), i_R = at.take((size_t)n_R * mm), i_q = at.take(q ? (size_t)(T + 1) * nB * n : 0),
+                    i_r = at.take(r ? (size_t)T * nB * m : 0), i_rho = at.take(boxed ? (size_t)n_rho : 0), i_lo = at.take(limits ? (size_t)n_lim * m : 0),
+                    i_hi = at.take(limits ? (size_t)n_lim * m : 0), i_un = at.take(limits ? (size_t)T * nB * m : 0), i_def = at.take(n_def);
+    const size_t n_in = at.end();
+    // the packed read-back; status | n_cut are 2 B ints in B doubles, clamped n_keep x B ints in doubles behind them
+    const PlantSpan o_K = at.take((size_t)n_keep * nB * m * n), o_k = at.take(k ? (size_t)n_keep * nB * m : 0), o_P = at.take(P0 ? nB * nn : 0),
+                    o_p = at.take(p0 ? nB * n : 0), o_V = at.take(dV ? nB * 2 : 0), o_st = at.take(nB),
+                    o_cl = at.take(boxed && clamped ? ((size_t)n_keep * nB + 1) / 2 : 0);
+    const size_t n_out = at.end();
     std::vector<double> up(n_in);
     const std::unique_ptr<double[]> out(new double[n_out]);      // not value-initialized: K alone is 36 MB at quadruped B = 256, T = 100
-    std::memcpy(up.data(), Q, i_Q * sizeof(double));
-    std::memcpy(up.data() + o_Qf, Qf, nn * sizeof(double));
-    std::memcpy(up.data() + o_R, R, i_R * sizeof(double));
-    if (q) std::memcpy(up.data() + o_q, q, i_q * sizeof(double));
-    if (r) std::memcpy(up.data() + o_r, r, i_r * sizeof(double));
-    if (boxed) std::memcpy(up.data() + o_rho, rho_b, i_rho * sizeof(double));
-    if (limits) {
-        std::memcpy(up.data() + o_lo, u_lo, i_lim * sizeof(double));
-        std::memcpy(up.data() + o_hi, u_hi, i_lim * sizeof(double));
-        std::memcpy(up.data() + o_un, u_nom, i_un * sizeof(double));
-    }
-    if (i_def) std::memcpy(up.data() + o_def, defects, i_def * sizeof(double));
+    bool packed = true;
+    PlantCopier<PlantHostCopy> pack{{}, packed};
+    pack.up(up.data(), i_Q, Q); pack.up(up.data(), i_Qf, Qf); pack.up(up.data(), i_R, R); pack.up(up.data(), i_q, q); pack.up(up.data(), i_r, r);
+    pack.up(up.data(), i_rho, rho_b); pack.up(up.data(), i_lo, u_lo); pack.up(up.data(), i_hi, u_hi); pack.up(up.data(), i_un, u_nom);
+    pack.up(up.data(), i_def, defects);
     const size_t lds = shoot ? plant_riccati_shoot_lds(nq, nu) : boxed ? plant_riccati_box_lds(nq, nu) : plant_riccati_lds(nq, nu);
-    std::lock_guard<std::mutex> lock(g_plant_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
-    if (cur != buf.device && hipSetDevice(buf.device) != hipSuccess) return CIMPC_ERR_HIP;
+    PlantDeviceScope scope(buf.device);
+    if (scope.rc() != CIMPC_OK) return scope.rc();
     bool ok = false;
     PlantWs* ws = plant_ws_open(buf.device);
-    RiccatiWs& W = g_riccati_ws[buf.device];
-    if (ws && plant_grow(&W.d_in, &W.cap_in, n_in) && plant_grow(&W.d_out, &W.cap_out, n_out)) {
+    PlantStageWs& W = g_riccati_ws[buf.device];
+    if (ws && W.grow(n_in, n_out, 0)) {
         hipStream_t st = ws->st;
         double* I = W.d_in;
         double* O = W.d_out;
-        int* d_status = reinterpret_cast<int*>(O + o_st);
+        int* d_status = reinterpret_cast<int*>(o_st.on(O));
         ok = hipMemcpyAsync(I, up.data(), n_in * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
         if (ok) {
-            PlantRiccati L{buf.d_dz, buf.d_status, I, I + o_Qf, I + o_R, q ? I + o_q : nullptr, r ? I + o_r : nullptr,
-                           O, k ? O + o_k : nullptr, P0 ? O + o_P : nullptr, p0 ? O + o_p : nullptr, dV ? O + o_V : nullptr,
+            PlantRiccati L{buf.d_dz, buf.d_status, i_Q.on(I), i_Qf.on(I), i_R.on(I), i_q.or_null(I), i_r.or_null(I),
+                           o_K.on(O), o_k.or_null(O), o_P.or_null(O), o_p.or_null(O), o_V.or_null(O),
                            d_status, d_status + B, B, T, nq, nu, nr, n_cols, laps, n_Q, n_R, n_keep, rho};
             if (boxed) {
-                L.rho_b = I + o_rho; L.n_rho = n_rho;
-                if (limits) { L.u_lo = I + o_lo; L.u_hi = I + o_hi; L.u_nom = I + o_un; L.n_lim = n_lim; }
-                if (clamped) L.clamped = reinterpret_cast<int*>(O + o_cl);
+                L.rho_b = i_rho.on(I); L.n_rho = n_rho;
+                if (limits) { L.u_lo = i_lo.on(I); L.u_hi = i_hi.on(I); L.u_nom = i_un.on(I); L.n_lim = n_lim; }
+                if (clamped) L.clamped = reinterpret_cast<int*>(o_cl.on(O));
             }
             if (shoot) {
-                L.defects = I + o_def; L.seg_len = seg_len;
+                L.defects = i_def.on(I); L.seg_len = seg_len;
                 ok = plant_riccati_shoot_launch(L, st);
             } else if (boxed) {
                 ok = plant_riccati_box_launch(L, st);
@@ -234,16 +203,11 @@ static int plant_tape_lqr_call(const char* entry, bool box, cimpc_plant_tape tap
         if (ok) ok = hipMemcpyAsync(out.get(), O, n_out * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess;
         ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
     }
-    if (cur != buf.device) ok = (hipSetDevice(cur) == hipSuccess) && ok;
-    if (!ok) return CIMPC_ERR_HIP;
-    std::memcpy(K, out.get(), n_K * sizeof(double));
-    if (k) std::memcpy(k, out.get() + o_k, n_k * sizeof(double));
-    if (P0) std::memcpy(P0, out.get() + o_P, n_P * sizeof(double));
-    if (p0) std::memcpy(p0, out.get() + o_p, n_p * sizeof(double));
-    if (dV) std::memcpy(dV, out.get() + o_V, n_V * sizeof(double));
-    std::memcpy(status, out.get() + o_st, nB * sizeof(int));
-    std::memcpy(n_cut, reinterpret_cast<const int*>(out.get() + o_st) + B, nB * sizeof(int));
-    if (n_cl) std::memcpy(clamped, out.get() + o_cl, (size_t)n_keep * nB * sizeof(int));
+    if (!scope.leave(ok)) return CIMPC_ERR_HIP;
+    pack.down(K, out.get(), o_K); pack.down(k, out.get(), o_k); pack.down(P0, out.get(), o_P); pack.down(p0, out.get(), o_p); pack.down(dV, out.get(), o_V);
+    const int* words = reinterpret_cast<const int*>(o_st.on(out.get()));      // status | n_cut
+    pack.down(status, words, PlantSpan{0, nB}); pack.down(n_cut, words, PlantSpan{nB, nB});
+    if (o_cl.n) pack.down(clamped, reinterpret_cast<const int*>(o_cl.on(out.get())), PlantSpan{0, (size_t)n_keep * nB});
     return CIMPC_OK;
 }
 

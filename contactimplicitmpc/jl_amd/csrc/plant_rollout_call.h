@@ -13,6 +13,7 @@
 #include "../../../include/cimpc.h"
 #include "plant_model.h"
 #include "plant_sensitivity_plan.h"
+#include "plant_staging.h"
 
 namespace cimpc {
 
@@ -69,9 +70,6 @@ struct PlantRolloutCall {
     .u = {u, K_u, n_u, hold_u}, .w = {w, K_w, n_w, hold_w}, .mu = mu, .n_mu = n_mu, .h = h, .opts = opts, .q = q, .gamma = gamma, .b = b,  \
     .status = status, .iters = iters
 
-// Elements [at, at + n) of a workspace buffer
-struct PlantSpan { size_t at = 0, n = 0; };
-
 // Where a call's arrays live, in elements of each buffer of PlantWs (plant_workspace.h), and what plant_grow is asked for (need_*; 0:
 // the call does not use the buffer).  The regions of a buffer follow each other in the order they are listed, without gaps; one that
 // the call does not have takes no room.
@@ -92,40 +90,38 @@ inline PlantRolloutLayout plant_rollout_layout(const PlantModel& M, const PlantR
     const size_t nq = M.nq, nu = M.nu, nr = nq + (size_t)M.nc + (size_t)M.nb();
     L.row = (size_t)c.B * nq;
     L.TB = (size_t)c.T * c.B;
-    size_t at = 0;
-    auto next = [&at](size_t n) { const PlantSpan s{at, n}; at += n; return s; };
-    auto end = [&at]() { const size_t need = at; at = 0; return need; };
-    L.q = next((size_t)(c.T + 2) * L.row);
-    L.u = next((size_t)c.u.K * c.u.n * nu);
-    L.w = next(c.w.rows ? (size_t)c.w.K * c.w.n * M.nw : 0);
-    L.mu = next(c.n_mu == 1 ? 0 : (size_t)c.B);
-    L.need_in = end();
-    L.gamma = next(L.TB * M.nc);
-    L.b = next(L.TB * M.nb());
-    L.need_out = end();
-    L.status = next(L.TB);
-    L.iters = next(L.TB);
-    L.need_st = end();
+    PlantCursor at;
+    L.q = at.take((size_t)(c.T + 2) * L.row);
+    L.u = at.take((size_t)c.u.K * c.u.n * nu);
+    L.w = at.take(c.w.rows ? (size_t)c.w.K * c.w.n * M.nw : 0);
+    L.mu = at.take(c.n_mu == 1 ? 0 : (size_t)c.B);
+    L.need_in = at.end();
+    L.gamma = at.take(L.TB * M.nc);
+    L.b = at.take(L.TB * M.nb());
+    L.need_out = at.end();
+    L.status = at.take(L.TB);
+    L.iters = at.take(L.TB);
+    L.need_st = at.end();
     if (c.grad) {
-        L.z = next(L.TB * M.nz());
-        L.need_z = end();
-        L.dz = next(L.TB * nr * (size_t)c.grad->n_cols);
-        L.need_grad = end();
-        L.grad_status = next(L.TB);
-        L.need_grad_st = end();
+        L.z = at.take(L.TB * M.nz());
+        L.need_z = at.end();
+        L.dz = at.take(L.TB * nr * (size_t)c.grad->n_cols);
+        L.need_grad = at.end();
+        L.grad_status = at.take(L.TB);
+        L.need_grad_st = at.end();
         if (c.grad->tape) L.need_grad = L.need_grad_st = 0;
     }
     if (c.loop) {
         const size_t n_x = (size_t)c.loop->fb->K_f * c.loop->fb->n_f * 2 * nq;
-        L.fb_K = next(n_x * nu);
-        L.x_ref = next(n_x);
-        L.u_applied = next(L.TB * nu);
-        L.fb_err = next(L.TB * 2 * nq);
+        L.fb_K = at.take(n_x * nu);
+        L.x_ref = at.take(n_x);
+        L.u_applied = at.take(L.TB * nu);
+        L.fb_err = at.take(L.TB * 2 * nq);
         if (c.loop->u_lo) {
-            L.u_lo = next((size_t)c.loop->n_lim * nu);
-            L.u_hi = next((size_t)c.loop->n_lim * nu);
+            L.u_lo = at.take((size_t)c.loop->n_lim * nu);
+            L.u_hi = at.take((size_t)c.loop->n_lim * nu);
         }
-        L.need_fb = end();
+        L.need_fb = at.end();
     }
     return L;
 }

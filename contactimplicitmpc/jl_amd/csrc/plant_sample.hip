@@ -22,7 +22,6 @@
 #include <cstdint>
 #include <mutex>
 #include <string>
-#include <utility>
 #include <vector>
 
 // No fused multiply-adds in this translation unit: the candidates and the mean round as the float64 restatement does.
@@ -142,7 +141,7 @@ __global__ __launch_bounds__(SMP_THREADS) void plant_sample_update_kernel(PlantS
 
 }  // namespace cimpc
 
-// What a cimpc_plant_sampler points to.  F and I are the handle's doubles and ints; the members named i_*, m_*, ... are offsets into them.
+// What a cimpc_plant_sampler points to.  F and I are the handle's doubles and ints; the members named i_*, m_*, ... are their regions (plant_staging.h).
 struct cimpc_plant_sampler_s {
     cimpc::PlantModel M{};
     cimpc::PlantCost C{};               // device pointers; T = H
@@ -161,39 +160,21 @@ struct cimpc_plant_sampler_s {
     cimpc_terrain* d_ter = nullptr;      // the candidates' terrains (n_ter), whose first n_terrain are the robots'
     std::vector<double> lo, hi;          // the limits on the host (n_lim x nu; empty: none), for the plans cimpc_plant_sampler_reset is given
     // doubles: the problem | the plan's two control buffers | the plan's trajectory | J, weights and unnormalised weights per iteration | the history
-    size_t i_mu, i_sig, i_Q, i_Qf, i_R, i_xr, i_ur, i_xg, i_ug, i_lo, i_hi, p_u[2], m_q, m_g, m_b, o_J, o_w, o_wr, h_Jn, h_Jb, n_f;
-    size_t j_st, j_it, j_conv, j_ok, j_ch, j_ne, j_done, n_i;
+    // i_ref: Q | Qf | R | x_ref | u_ref, the cost over the reference's L steps; i_xg, i_ug: the goal window of a control step
+    cimpc::PlantCostSpans i_ref;
+    cimpc::PlantSpan i_mu, i_sig, i_xg, i_ug, i_lo, i_hi, p_u[2], m_q, m_g, m_b, o_J, o_w, o_wr, h_Jn, h_Jb;
+    cimpc::PlantSpan j_st, j_it, j_conv, j_ok, j_ch, j_ne, j_done;
+    size_t n_f = 0, n_i = 0;
 };
 
 namespace {
 using namespace cimpc;
 
-int smp_refuse(const char* entry, const std::string& why) {
-    set_global_error(std::string(entry) + ": " + why);
-    return CIMPC_ERR_INVALID;
-}
-
 // Frees what the handle owns on its device (the caller holds g_plant_mu and has selected the device).
 bool smp_release(cimpc_plant_sampler_s* h) {
-    bool ok = true;
-    if (h->F) ok = (hipFree(h->F) == hipSuccess) && ok;
-    if (h->I) ok = (hipFree(h->I) == hipSuccess) && ok;
-    if (h->d_ter) ok = (hipFree(h->d_ter) == hipSuccess) && ok;
-    h->F = nullptr; h->I = nullptr; h->d_ter = nullptr;
-    return ok;
-}
-
-// Runs `body` under the plant mutex on the handle's device; the current device is restored.
-template <class Body>
-int smp_on_device(cimpc_plant_sampler_s* h, Body&& body) {
-    std::lock_guard<std::mutex> lock(g_plant_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
-    if (cur != h->device && hipSetDevice(h->device) != hipSuccess) return CIMPC_ERR_HIP;
-    bool ok = body();
-    if (cur != h->device) ok = (hipSetDevice(cur) == hipSuccess) && ok;
-    if (!ok) h->failed = true;
-    return ok ? CIMPC_OK : CIMPC_ERR_HIP;
+    bool ok = plant_free(&h->F);
+    ok = plant_free(&h->I) && ok;
+    return plant_free(&h->d_ter) && ok;
 }
 
 const char* const SMP_FAILED = "a handle that met a HIP error refuses further use";
@@ -202,7 +183,7 @@ const char* const SMP_FAILED = "a handle that met a HIP error refuses further us
 bool smp_roll_plan(cimpc_plant_sampler_s& S, PlantWs& W, hipStream_t st) {
     double* F = S.F;
     if (S.rough && hipMemcpyAsync(W.d_ter, S.d_ter, (size_t)S.n_terrain * sizeof(cimpc_terrain), hipMemcpyDeviceToDevice, st) != hipSuccess) return false;
-    const PlantStepArrays R{F + S.m_q, F + S.p_u[S.cur], nullptr, S.mu_each ? F + S.i_mu : nullptr, F + S.m_g, F + S.m_b, S.I + S.j_st, S.I + S.j_it, S.mu0, S.h,
+    const PlantStepArrays R{S.m_q.on(F), S.p_u[S.cur].on(F), nullptr, S.i_mu.or_null(F), S.m_g.on(F), S.m_b.on(F), S.j_st.on(S.I), S.j_it.on(S.I), S.mu0, S.h,
                             S.H, S.B, 1, 1, 1, 1, S.n_mu, nullptr, PlantFeedback{}, nullptr, nullptr};
     return plant_step_chunks(S.M, S.rough, S.opts, S.B, S.H, S.steps_per_launch, R, S.rough ? W.d_ter : nullptr, S.rough ? S.n_terrain : 0, st);
 }
@@ -211,8 +192,8 @@ bool smp_roll_plan(cimpc_plant_sampler_s& S, PlantWs& W, hipStream_t st) {
 // ---- C ABI -------------------------------------------------------------------------------------------------------------
 extern "C" int cimpc_plant_sample_noise(unsigned long long seed, unsigned int draw, int B, int N, int n_rows, int nu, double* eps) {
     using namespace cimpc;
-    if (!eps) return smp_refuse("cimpc_plant_sample_noise", "null eps");
-    if (B < 1 || N < 1 || n_rows < 1 || nu < 1) return smp_refuse("cimpc_plant_sample_noise", "B, N, n_rows or nu below 1");
+    if (!eps) return plant_refuse("cimpc_plant_sample_noise", "null eps");
+    if (B < 1 || N < 1 || n_rows < 1 || nu < 1) return plant_refuse("cimpc_plant_sample_noise", "B, N, n_rows or nu below 1");
     size_t at = 0;
     for (int j = 0; j < n_rows; ++j)
         for (int c = 0; c < N; ++c)
@@ -228,12 +209,11 @@ extern "C" int cimpc_plant_sampler_create(int model, int B, int H, int steps_per
                                           int n_iter, unsigned long long seed, int n_lim, const double* u_lo, const double* u_hi, const double* u0,
                                           cimpc_plant_sampler* handle) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { return smp_refuse("cimpc_plant_sampler_create", why); };
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_sampler_create", why); };
     if (!handle) return refuse("null handle");
     *handle = nullptr;
-    const std::pair<const char*, const void*> required[] = {{"mu", mu}, {"opts", opts}, {"Q", Q}, {"Qf", Qf}, {"R", R}, {"x_ref", x_ref}, {"u_ref", u_ref},
-                                                            {"u0", u0}};
-    for (const auto& [name, p] : required) if (!p) return refuse(std::string("null ") + name);
+    const PlantRequired required[] = {{"mu", mu}, {"opts", opts}, {"Q", Q}, {"Qf", Qf}, {"R", R}, {"x_ref", x_ref}, {"u_ref", u_ref}, {"u0", u0}};
+    if (const char* name = plant_first_null(required)) return refuse(std::string("null ") + name);
     if (const char* why = plant_mpc_problem_refusal(H, L, n_iter)) return refuse(why);
     PlantModel named{};
     if (!plant_model_by_id(model, &named)) return refuse("an unknown model");
@@ -276,25 +256,27 @@ extern "C" int cimpc_plant_sampler_create(int model, int B, int H, int steps_per
     S.mu0 = mu[0]; S.h = h; S.lam = lam; S.seed = (uint64_t)seed;
     if (limits) { S.lo.assign(u_lo, u_lo + (size_t)n_lim * nu); S.hi.assign(u_hi, u_hi + (size_t)n_lim * nu); }
     const size_t TB = (size_t)T * B, n = (size_t)2 * nq, nB = (size_t)B, nNB = (size_t)NB;
-    size_t at = 0;
-    auto next = [&at](size_t cnt) { const size_t o = at; at += cnt; return o; };
-    S.i_mu = next(mu_each ? nB : 0); S.i_sig = next((size_t)nu); S.i_Q = next((size_t)n_Q * n * n); S.i_Qf = next(n * n); S.i_R = next((size_t)n_R * nu * nu);
-    S.i_xr = next((size_t)(L + 1) * n_x * n); S.i_ur = next((size_t)L * n_x * nu); S.i_xg = next((size_t)(T + 1) * n_x * n); S.i_ug = next((size_t)T * n_x * nu);
-    S.i_lo = next(limits ? (size_t)n_lim * nu : 0); S.i_hi = next(limits ? (size_t)n_lim * nu : 0);
-    S.p_u[0] = next(TB * nu); S.p_u[1] = next(TB * nu);
-    S.m_q = next((size_t)(T + 2) * B * nq); S.m_g = next(TB * nc); S.m_b = next(TB * nb);
-    S.o_J = next((size_t)n_iter * nNB); S.o_w = next((size_t)n_iter * nNB); S.o_wr = next((size_t)n_iter * nNB);
-    S.h_Jn = next((size_t)n_iter * B); S.h_Jb = next((size_t)n_iter * B); S.n_f = at;
-    at = 0;
-    S.j_st = next(TB); S.j_it = next(TB); S.j_conv = next(nNB); S.j_ok = next(nNB); S.j_ch = next((size_t)n_iter * B); S.j_ne = next((size_t)n_iter * B);
-    S.j_done = next(nB); S.n_i = at;
+    const PlantCost reference{Q, Qf, R, x_ref, u_ref, n_Q, n_R, n_x, L, nq, nu};      // the weights, and x_ref, u_ref as the goals of L steps
+    PlantCursor at;
+    S.i_mu = at.take(mu_each ? nB : 0); S.i_sig = at.take((size_t)nu);
+    S.i_ref = plant_cost_spans(at, reference);
+    S.i_xg = at.take((size_t)(T + 1) * n_x * n); S.i_ug = at.take((size_t)T * n_x * nu);
+    S.i_lo = at.take(limits ? (size_t)n_lim * nu : 0); S.i_hi = at.take(limits ? (size_t)n_lim * nu : 0);
+    S.p_u[0] = at.take(TB * nu); S.p_u[1] = at.take(TB * nu);
+    S.m_q = at.take((size_t)(T + 2) * B * nq); S.m_g = at.take(TB * nc); S.m_b = at.take(TB * nb);
+    S.o_J = at.take((size_t)n_iter * nNB); S.o_w = at.take((size_t)n_iter * nNB); S.o_wr = at.take((size_t)n_iter * nNB);
+    S.h_Jn = at.take((size_t)n_iter * B); S.h_Jb = at.take((size_t)n_iter * B);
+    S.n_f = at.end();
+    S.j_st = at.take(TB); S.j_it = at.take(TB); S.j_conv = at.take(nNB); S.j_ok = at.take(nNB); S.j_ch = at.take((size_t)n_iter * B);
+    S.j_ne = at.take((size_t)n_iter * B); S.j_done = at.take(nB);
+    S.n_i = at.end();
     std::vector<cimpc_terrain> ter;      // the candidates' terrains: robot b's for every c
     if (ter_each) for (int c = 0; c < N; ++c) ter.insert(ter.end(), terrain, terrain + B);
 
     int dev = 0;
     if (!plant_current_device(&dev)) { delete hd; return CIMPC_ERR_NO_DEVICE; }
     S.device = dev;
-    const int rc = smp_on_device(hd, [&]() {
+    const int rc = plant_handle_on_device(hd, [&]() {
         PlantWs* ws = plant_ws_open(dev);
         if (!ws) return false;
         bool ok_ = hipMalloc((void**)&S.F, S.n_f * sizeof(double)) == hipSuccess;
@@ -302,24 +284,23 @@ extern "C" int cimpc_plant_sampler_create(int model, int B, int H, int steps_per
         if (ok_ && hipMalloc((void**)&S.I, S.n_i * sizeof(int)) != hipSuccess) { S.I = nullptr; ok_ = false; }
         if (ok_ && S.n_ter > 0 && hipMalloc((void**)&S.d_ter, (size_t)S.n_ter * sizeof(cimpc_terrain)) != hipSuccess) { S.d_ter = nullptr; ok_ = false; }
         hipStream_t st = ws->st;
-        auto up = [&](auto* d, const auto* hsrc, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(d, hsrc, cnt * sizeof(*d), hipMemcpyHostToDevice, st) == hipSuccess; };
+        PlantStreamCopier copy{{st}, ok_};
         double* F = S.F;
         if (ok_) {
             ok_ = hipMemsetAsync(F, 0, S.n_f * sizeof(double), st) == hipSuccess && hipMemsetAsync(S.I, 0, S.n_i * sizeof(int), st) == hipSuccess;
-            if (mu_each) up(F + S.i_mu, mu, nB);
-            up(F + S.i_sig, sigma, (size_t)nu);
-            up(F + S.i_Q, Q, (size_t)n_Q * n * n); up(F + S.i_Qf, Qf, n * n); up(F + S.i_R, R, (size_t)n_R * nu * nu);
-            up(F + S.i_xr, x_ref, (size_t)(L + 1) * n_x * n); up(F + S.i_ur, u_ref, (size_t)L * n_x * nu);
-            if (limits) { up(F + S.i_lo, u_lo, (size_t)n_lim * nu); up(F + S.i_hi, u_hi, (size_t)n_lim * nu); }
-            up(F + S.p_u[0], u0, TB * nu);
-            if (rough) up(S.d_ter, ter_each ? ter.data() : terrain, (size_t)S.n_ter);
+            copy.up(F, S.i_mu, mu);      // where it is per robot
+            copy.up(F, S.i_sig, sigma);
+            (void)plant_cost_up(copy, F, S.i_ref, reference);
+            copy.up(F, S.i_lo, u_lo); copy.up(F, S.i_hi, u_hi);
+            copy.up(F, S.p_u[0], u0);
+            if (rough) copy.up(S.d_ter, PlantSpan{0, (size_t)S.n_ter}, ter_each ? ter.data() : terrain);
         }
         ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;      // the host arrays are the caller's: nothing of them is read after the return
         if (!ok_) (void)smp_release(hd);
         return ok_;
     });
     if (rc != CIMPC_OK) { delete hd; return rc; }
-    S.C.Q = S.F + S.i_Q; S.C.Qf = S.F + S.i_Qf; S.C.R = S.F + S.i_R; S.C.x_goal = S.F + S.i_xg; S.C.u_goal = S.F + S.i_ug;
+    S.C = plant_cost_on(S.C, S.F, PlantCostSpans{S.i_ref.Q, S.i_ref.Qf, S.i_ref.R, S.i_xg, S.i_ug});      // the weights, and the goal window
     S.cur = 0; S.has_plan = true;
     *handle = hd;
     return CIMPC_OK;
@@ -329,11 +310,11 @@ extern "C" int cimpc_plant_sampler_control(cimpc_plant_sampler handle, int s, in
                                            double* hist_J_nom, double* hist_J_best, int* hist_choice, int* hist_n_eligible, double* J, double* weights,
                                            int* converged) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { return smp_refuse("cimpc_plant_sampler_control", why); };
-    const std::pair<const char*, const void*> required[] = {{"handle", handle}, {"q0", q0}, {"q1", q1}, {"u", u}, {"J0", J0}, {"hist_J_nom", hist_J_nom},
-                                                            {"hist_J_best", hist_J_best}, {"hist_choice", hist_choice},
-                                                            {"hist_n_eligible", hist_n_eligible}, {"converged", converged}};
-    for (const auto& [name, p] : required) if (!p) return refuse(std::string("null ") + name);
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_sampler_control", why); };
+    const PlantRequired required[] = {{"handle", handle}, {"q0", q0}, {"q1", q1}, {"u", u}, {"J0", J0}, {"hist_J_nom", hist_J_nom},
+                                      {"hist_J_best", hist_J_best}, {"hist_choice", hist_choice},
+                                      {"hist_n_eligible", hist_n_eligible}, {"converged", converged}};
+    if (const char* name = plant_first_null(required)) return refuse(std::string("null ") + name);
     cimpc_plant_sampler_s& S = *handle;
     if (S.failed) return refuse(SMP_FAILED);
     if (const char* why = plant_mpc_step_refusal(s, shift, S.has_plan)) return refuse(why);
@@ -342,7 +323,7 @@ extern "C" int cimpc_plant_sampler_control(cimpc_plant_sampler handle, int s, in
     const int B = S.B, H = S.H, N = S.N, NB = S.NB, nq = M.nq, nu = M.nu, nc = M.nc, nb = M.nb(), n_iter = S.n_iter;
     const size_t nB = (size_t)B, nNB = (size_t)NB, row = nB * nq;
     if (const char* why = plant_mpc_state_refusal(q0, q1, row)) return refuse(why);
-    const int rc = smp_on_device(handle, [&]() {
+    const int rc = plant_handle_on_device(handle, [&]() {
         PlantWs* ws = plant_ws_open(S.device);
         // the workspace grows only when another call has not yet made it as large: no allocation from the second control step on
         if (!ws || !plant_grow(&ws->d_in, &ws->cap_in, Lw.need_in) || !plant_grow(&ws->d_out, &ws->cap_out, Lw.need_out) ||
@@ -351,18 +332,16 @@ extern "C" int cimpc_plant_sampler_control(cimpc_plant_sampler handle, int s, in
         PlantWs& W = *ws;
         hipStream_t st = W.st;
         bool ok_ = true;
-        auto up = [&](auto* d, const auto* hsrc, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(d, hsrc, cnt * sizeof(*d), hipMemcpyHostToDevice, st) == hipSuccess; };
-        auto down = [&](auto* hdst, const auto* d, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(hdst, d, cnt * sizeof(*d), hipMemcpyDeviceToHost, st) == hipSuccess; };
+        PlantStreamCopier copy{{st}, ok_};
         double* F = S.F;
         int* I = S.I;
-        double *u_plan = F + S.p_u[S.cur], *u_nom = F + S.p_u[1 - S.cur];
-        const double* d_mu = S.mu_each ? F + S.i_mu : nullptr;
-        const bool limits = S.limits;
-        up(F + S.m_q, q0, row); up(F + S.m_q + row, q1, row);      // up: 2 B nq doubles
+        double *u_plan = S.p_u[S.cur].on(F), *u_nom = S.p_u[1 - S.cur].on(F);
+        const double* d_mu = S.i_mu.or_null(F);
+        copy.up(F, S.m_q.part(0, row), q0); copy.up(F, S.m_q.part(row, row), q1);      // 2 B nq doubles
         if (S.rough)      // the workspace's terrains, which another plant call may have overwritten
             ok_ = ok_ && hipMemcpyAsync(W.d_ter, S.d_ter, (size_t)S.n_ter * sizeof(cimpc_terrain), hipMemcpyDeviceToDevice, st) == hipSuccess;
         if (ok_) {
-            const PlantSampleBegin Bg{u_plan, u_nom, F + S.i_xr, F + S.i_ur, F + S.i_xg, F + S.i_ug, B, H, S.L, S.n_x, nq, nu, s, shift};
+            const PlantSampleBegin Bg{u_plan, u_nom, S.i_ref.x_goal.on(F), S.i_ref.u_goal.on(F), S.i_xg.on(F), S.i_ug.on(F), B, H, S.L, S.n_x, nq, nu, s, shift};
             hipLaunchKernelGGL(plant_sample_begin_kernel, dim3((unsigned)((H + 1) * B)), dim3(LS_THREADS), 0, st, Bg);
             ok_ = hipGetLastError() == hipSuccess;
         }
@@ -370,32 +349,31 @@ extern "C" int cimpc_plant_sampler_control(cimpc_plant_sampler handle, int s, in
         int *d_st = W.d_st + Lw.status.at, *d_it = W.d_st + Lw.iters.at;
         const size_t items = (size_t)S.n_rows * nNB * nu + nNB * nq + nNB;
         for (int it = 0; it < n_iter && ok_; ++it) {
-            const PlantSampleExpand E{u_nom, F + S.m_q, d_mu, F + S.i_sig, limits ? F + S.i_lo : nullptr, limits ? F + S.i_hi : nullptr, dq, du, dmu,
+            const PlantSampleExpand E{u_nom, S.m_q.on(F), d_mu, S.i_sig.on(F), S.i_lo.or_null(F), S.i_hi.or_null(F), dq, du, dmu,
                                       S.n_lim, B, N, H, nq, nu, S.noise_hold, S.n_rows, S.seed, plant_sample_draw(s, n_iter, it)};
             hipLaunchKernelGGL(plant_sample_expand_kernel, dim3((unsigned)((items + SMP_THREADS - 1) / SMP_THREADS)), dim3(SMP_THREADS), 0, st, E);
             if (hipGetLastError() != hipSuccess) { ok_ = false; break; }
             const PlantStepArrays R{dq, du, nullptr, S.mu_each ? dmu : nullptr, dg, db, d_st, d_it, S.mu0, S.h, H, NB, 1, 1, 1, 1, S.mu_each ? NB : 1,
                                     nullptr, PlantFeedback{}, nullptr, nullptr};
             if (!plant_step_chunks(M, S.rough, S.opts, NB, H, S.steps_per_launch, R, S.rough ? W.d_ter : nullptr, S.n_ter, st)) { ok_ = false; break; }
-            double* Jit = F + S.o_J + (size_t)it * nNB;
-            if (!plant_candidates_cost_launch(S.C, dq, du, d_st, Jit, I + S.j_conv, B, NB, st)) { ok_ = false; break; }
-            const size_t hrow = (size_t)it * B;
-            const PlantSampleUpdate U{Jit, I + S.j_conv, du, u_nom, limits ? F + S.i_lo : nullptr, limits ? F + S.i_hi : nullptr, S.n_lim, I + S.j_ok,
-                                      F + S.o_wr + (size_t)it * nNB, F + S.o_w + (size_t)it * nNB, F + S.h_Jn + hrow, F + S.h_Jb + hrow, I + S.j_ch + hrow, I + S.j_ne + hrow,
+            const size_t cand0 = (size_t)it * nNB, robot0 = (size_t)it * B;      // this iteration's rows of the per-iteration arrays
+            double* Jit = S.o_J.part(cand0, nNB).on(F);
+            if (!plant_candidates_cost_launch(S.C, dq, du, d_st, Jit, S.j_conv.on(I), B, NB, st)) { ok_ = false; break; }
+            const PlantSampleUpdate U{Jit, S.j_conv.on(I), du, u_nom, S.i_lo.or_null(F), S.i_hi.or_null(F), S.n_lim, S.j_ok.on(I),
+                                      S.o_wr.part(cand0, nNB).on(F), S.o_w.part(cand0, nNB).on(F), S.h_Jn.part(robot0, nB).on(F), S.h_Jb.part(robot0, nB).on(F),
+                                      S.j_ch.part(robot0, nB).on(I), S.j_ne.part(robot0, nB).on(I),
                                       B, N, H, nu, S.lam};
             const int last = it + 1 == n_iter;
-            const PlantSampleKeep K{dq, dg, db, d_st, d_it, F + S.m_q, F + S.m_g, F + S.m_b, I + S.j_st, I + S.j_it, I + S.j_done, nq, nc, nb,
+            const PlantSampleKeep K{dq, dg, db, d_st, d_it, S.m_q.on(F), S.m_g.on(F), S.m_b.on(F), S.j_st.on(I), S.j_it.on(I), S.j_done.on(I), nq, nc, nb,
                                     last && S.lam == 0.0 ? 1 : 0, last};
             hipLaunchKernelGGL(plant_sample_update_kernel, dim3((unsigned)B), dim3(SMP_THREADS), 0, st, U, K);
             ok_ = hipGetLastError() == hipSuccess;
         }
         if (ok_) {      // down: what the signature names
-            const size_t hn = (size_t)n_iter * B;
-            down(u, u_nom, nB * nu); down(J0, F + S.o_J, nB);
-            down(hist_J_nom, F + S.h_Jn, hn); down(hist_J_best, F + S.h_Jb, hn); down(hist_choice, I + S.j_ch, hn); down(hist_n_eligible, I + S.j_ne, hn);
-            if (J) down(J, F + S.o_J, (size_t)n_iter * nNB);
-            if (weights) down(weights, F + S.o_w, (size_t)n_iter * nNB);
-            down(converged, I + S.j_done, nB);
+            copy.down(u, F, S.p_u[1 - S.cur].part(0, nB * nu)); copy.down(J0, F, S.o_J.part(0, nB));
+            copy.down(hist_J_nom, F, S.h_Jn); copy.down(hist_J_best, F, S.h_Jb); copy.down(hist_choice, I, S.j_ch); copy.down(hist_n_eligible, I, S.j_ne);
+            copy.down(J, F, S.o_J); copy.down(weights, F, S.o_w);      // where they are asked for
+            copy.down(converged, I, S.j_done);
         }
         ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;      // this stream only
         return ok_;
@@ -409,15 +387,13 @@ extern "C" int cimpc_plant_sampler_control(cimpc_plant_sampler handle, int s, in
 
 extern "C" int cimpc_plant_sampler_plan(cimpc_plant_sampler handle, double* u, double* q, double* gamma, double* b, int* status, int* iters) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { return smp_refuse("cimpc_plant_sampler_plan", why); };
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_sampler_plan", why); };
     if (!handle) return refuse("null handle");
     cimpc_plant_sampler_s& S = *handle;
     if (S.failed) return refuse(SMP_FAILED);
     if (!S.has_plan) return refuse("no plan loaded");
-    const PlantModel& M = S.M;
-    const size_t TB = (size_t)S.H * S.B;
     const bool wants_rows = q || gamma || b || status || iters;
-    return smp_on_device(handle, [&]() {
+    return plant_handle_on_device(handle, [&]() {
         PlantWs* ws = plant_ws_open(S.device);
         if (!ws) return false;
         hipStream_t st = ws->st;
@@ -426,45 +402,46 @@ extern "C" int cimpc_plant_sampler_plan(cimpc_plant_sampler handle, double* u, d
             ok_ = plant_grow(&ws->d_ter, &ws->cap_ter, (size_t)S.n_terrain) && smp_roll_plan(S, *ws, st);
             if (ok_) { S.traj_valid = true; ++S.n_rollouts; }
         }
-        auto down = [&](auto* hdst, const auto* d, size_t cnt) {
-            if (hdst) ok_ = ok_ && hipMemcpyAsync(hdst, d, cnt * sizeof(*d), hipMemcpyDeviceToHost, st) == hipSuccess;
-        };
-        down(u, S.F + S.p_u[S.cur], TB * M.nu); down(q, S.F + S.m_q, (size_t)(S.H + 2) * S.B * M.nq); down(gamma, S.F + S.m_g, TB * M.nc);
-        down(b, S.F + S.m_b, TB * M.nb()); down(status, S.I + S.j_st, TB); down(iters, S.I + S.j_it, TB);
+        PlantStreamCopier copy{{st}, ok_};      // every output is optional
+        copy.down(u, S.F, S.p_u[S.cur]); copy.down(q, S.F, S.m_q); copy.down(gamma, S.F, S.m_g);
+        copy.down(b, S.F, S.m_b); copy.down(status, S.I, S.j_st); copy.down(iters, S.I, S.j_it);
         return (hipStreamSynchronize(st) == hipSuccess) && ok_;
     });
 }
 
 extern "C" int cimpc_plant_sampler_raw_weights(cimpc_plant_sampler handle, double* w) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { return smp_refuse("cimpc_plant_sampler_raw_weights", why); };
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_sampler_raw_weights", why); };
     if (!handle) return refuse("null handle");
     if (!w) return refuse("null w");
     cimpc_plant_sampler_s& S = *handle;
     if (S.failed) return refuse(SMP_FAILED);
     if (!S.has_state) return refuse("no control step yet");
-    return smp_on_device(handle, [&]() {
+    return plant_handle_on_device(handle, [&]() {
         PlantWs* ws = plant_ws_open(S.device);
         if (!ws) return false;
-        const bool ok_ = hipMemcpyAsync(w, S.F + S.o_wr, (size_t)S.n_iter * S.NB * sizeof(double), hipMemcpyDeviceToHost, ws->st) == hipSuccess;
+        bool ok_ = true;
+        PlantStreamCopier copy{{ws->st}, ok_};
+        copy.down(w, S.F, S.o_wr);
         return (hipStreamSynchronize(ws->st) == hipSuccess) && ok_;
     });
 }
 
 extern "C" int cimpc_plant_sampler_reset(cimpc_plant_sampler handle, const double* u0) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { return smp_refuse("cimpc_plant_sampler_reset", why); };
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_sampler_reset", why); };
     if (!handle) return refuse("null handle");
     if (!u0) return refuse("null u0");
     cimpc_plant_sampler_s& S = *handle;
     if (S.failed) return refuse(SMP_FAILED);
     const int nu = S.M.nu;
     if (const char* why = plant_mpc_plan_refusal(u0, S.H, S.B, nu, S.limits ? S.lo.data() : nullptr, S.limits ? S.hi.data() : nullptr, S.n_lim)) return refuse(why);
-    const size_t cnt = (size_t)S.H * S.B * nu;
-    const int rc = smp_on_device(handle, [&]() {
+    const int rc = plant_handle_on_device(handle, [&]() {
         PlantWs* ws = plant_ws_open(S.device);
         if (!ws) return false;
-        const bool ok_ = hipMemcpyAsync(S.F + S.p_u[S.cur], u0, cnt * sizeof(double), hipMemcpyHostToDevice, ws->st) == hipSuccess;
+        bool ok_ = true;
+        PlantStreamCopier copy{{ws->st}, ok_};
+        copy.up(S.F, S.p_u[S.cur], u0);
         return (hipStreamSynchronize(ws->st) == hipSuccess) && ok_;
     });
     if (rc == CIMPC_OK) { S.has_plan = true; S.traj_valid = false; }
@@ -486,16 +463,10 @@ extern "C" int cimpc_plant_sampler_dims(cimpc_plant_sampler handle, int* model, 
 extern "C" int cimpc_plant_sampler_destroy(cimpc_plant_sampler handle) {
     using namespace cimpc;
     if (!handle) return CIMPC_OK;
-    bool ok = true;
+    bool ok = false;
     {
-        std::lock_guard<std::mutex> lock(g_plant_mu);      // no call is using the handle
-        int cur = -1;
-        const int dev = handle->device;
-        ok = hipGetDevice(&cur) == hipSuccess && (cur == dev || hipSetDevice(dev) == hipSuccess);
-        if (ok) {
-            ok = smp_release(handle);
-            if (cur != dev) ok = (hipSetDevice(cur) == hipSuccess) && ok;
-        }
+        PlantDeviceScope scope(handle->device);      // no call is using the handle
+        if (scope.rc() == CIMPC_OK) ok = scope.leave(smp_release(handle));
     }
     delete handle;
     return ok ? CIMPC_OK : CIMPC_ERR_HIP;

@@ -19,7 +19,8 @@
 //                                  candidate's own segments in global order, its D, convergence), plant_shoot_gather_kernel (phi, acceptance and
 //                                  choice per REAL robot, the chosen candidate's M segments compacted to M B virtual robots), ONE sensitivity
 //                                  launch over the chosen L x M B entries, plant_shoot_stitch_kernel and plant_shoot_total_kernel as in the
-//                                  rollout, plant_shoot_restore_kernel (the parent's blocks for a robot without an acceptable candidate)
+//                                  rollout, the line search's restore kernel (plant_restore_launch: the parent's blocks for a robot without an
+//                                  acceptable candidate)
 //
 // The kernels here move rows and run the short ordered chains of plant_shooting.h and plant_cost.h; a wavefront per workgroup.  The time of
 // the call is the step kernel's, for L steps.
@@ -28,7 +29,6 @@
 #include <cmath>
 #include <mutex>
 #include <string>
-#include <utility>
 #include <vector>
 
 // No fused multiply-adds in this translation unit: the cost and the defects round as the float64 restatement of the definition does.
@@ -230,38 +230,9 @@ __global__ __launch_bounds__(LS_THREADS) void plant_shoot_gather_kernel(PlantSho
     if (lane == 0) { G.Cst[to] = G.status[from]; G.Cit[to] = G.iters[from]; }
 }
 
-// Entry e = t B + b of the new tape gets the parent's block and status where robot b has no acceptable candidate
-__global__ __launch_bounds__(LS_THREADS) void plant_shoot_restore_kernel(const int* choice, const double* parent_dz, const int* parent_status, double* dz,
-                                                                        int* status, int B, int T, int block) {
-    const int e = blockIdx.x;
-    if (e >= T * B || choice[e % B] >= 0) return;
-    for (int i = threadIdx.x; i < block; i += LS_THREADS) dz[(size_t)e * block + i] = parent_dz[(size_t)e * block + i];
-    if (threadIdx.x == 0) status[e] = parent_status[e];
-}
-
 // the wavefront as the team of plant_shoot_forward_chain: the corner of the step ahead rides in registers while a step is worked
 constexpr int SHOOT_FWD_STAGE = 16;      // per lane: a corner of up to 1024 doubles (18 x 48 = 864 at the largest model) is wholly in flight
-struct PlantShootWave {
-    double stage[SHOOT_FWD_STAGE];
-    __device__ int rank() const { return threadIdx.x; }
-    __device__ int size() const { return LS_THREADS; }
-    __device__ void sync() const { __syncthreads(); }
-    __device__ void fetch_issue(const double* src, int rows, int cols, int ld) {
-#pragma unroll
-        for (int k = 0; k < SHOOT_FWD_STAGE; ++k) {
-            const int i = k * LS_THREADS + (int)threadIdx.x;
-            stage[k] = i < rows * cols ? src[(size_t)(i / rows) * ld + i % rows] : 0.0;
-        }
-    }
-    __device__ void fetch_commit(double* dst, const double* src, int rows, int cols, int ld) {
-#pragma unroll
-        for (int k = 0; k < SHOOT_FWD_STAGE; ++k) {
-            const int i = k * LS_THREADS + (int)threadIdx.x;
-            if (i < rows * cols) dst[i] = stage[k];
-        }
-        for (int i = SHOOT_FWD_STAGE * LS_THREADS + (int)threadIdx.x; i < rows * cols; i += LS_THREADS) dst[i] = src[(size_t)(i / rows) * ld + i % rows];
-    }
-};
+using PlantShootWave = PlantCornerTeam<LS_THREADS, SHOOT_FWD_STAGE>;
 
 constexpr int SHOOT_FWD_MAX_WORK = (int)plant_shoot_forward_work_doubles(PLANT_MAX_Q, PLANT_MAX_U);
 __global__ __launch_bounds__(LS_THREADS) void plant_shoot_forward_kernel(PlantShootForward F) {
@@ -273,10 +244,8 @@ __global__ __launch_bounds__(LS_THREADS) void plant_shoot_forward_kernel(PlantSh
 }
 
 namespace {
-// grow-only device buffers of the entry, per device, next to the plant workspace whose buffers (the segments' rollout), stream and mutex it
-// uses: the B-robot inputs, the stitched outputs, the integer outputs
-struct ShootingWs { double *d_in = nullptr, *d_out = nullptr; int* d_int = nullptr; size_t cap_in = 0, cap_out = 0, cap_int = 0; };
-ShootingWs g_shooting_ws[PLANT_MAX_DEVICES];
+// the entries' own buffers, beside the segments' rollout in the plant workspace: the B-robot inputs, the stitched outputs, the integer outputs
+PlantStageWs g_shooting_ws[PLANT_MAX_DEVICES];
 
 // Why the rollout arguments of cimpc_plant_rollout_segments are refused, or null: the tests of plant_rollout_check (plant_rollout_call.h) on
 // the arguments the entry shares with cimpc_plant_rollout_tape, each with its reason, in that function's order.
@@ -296,10 +265,6 @@ const char* shoot_call_refusal(int model, int B, int n_terrain, const cimpc_terr
     if (!plant_sensitivity_fits(M.nz(), n_cols)) return "a block too large for the sensitivity kernel";
     return nullptr;
 }
-
-PlantCost shoot_cost_of(const cimpc_tracking_cost& c, int T, int nq, int nu) {
-    return PlantCost{c.Q, c.Qf, c.R, c.x_goal, c.u_goal, c.n_Q, c.n_R, c.n_x, T, nq, nu};
-}
 }  // namespace
 
 }  // namespace cimpc
@@ -308,11 +273,11 @@ PlantCost shoot_cost_of(const cimpc_tracking_cost& c, int T, int nq, int nu) {
 extern "C" int cimpc_plant_shooting_cost(int nq, int nu, int B, int T, int segments, const cimpc_tracking_cost* cost, const double* qs, const double* u,
                                          double* J, double* D, double* defects, double* lin_q, double* lin_r) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { set_global_error("cimpc_plant_shooting_cost: " + why); return CIMPC_ERR_INVALID; };
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_shooting_cost", why); };
     if (!cost || !qs || !u || !J || !D) return refuse("a null cost, qs, u, J or D");
     if (nq < 1 || nu < 1) return refuse("nq or nu below 1");
     if (const char* why = plant_shooting_refusal(T, segments, B)) return refuse(why);
-    const PlantCost C = shoot_cost_of(*cost, T, nq, nu);
+    const PlantCost C = plant_cost_of(*cost, T, nq, nu);
     if (const char* why = plant_cost_pointers(C)) return refuse(why);
     if (const char* why = plant_cost_sizes(C, B)) return refuse(why);
     const int M = segments, L = T / M;
@@ -333,10 +298,10 @@ extern "C" int cimpc_plant_shooting_forward(cimpc_plant_tape tape, int n_Q, cons
                                             const double* lin_r, const double* K, const double* k, int segment_len, const double* defects,
                                             double* dx_nodes, double* du, double* dJ) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { set_global_error("cimpc_plant_shooting_forward: " + why); return CIMPC_ERR_INVALID; };
-    const std::pair<const char*, const void*> required[] = {{"tape", tape}, {"Q", Q}, {"Qf", Qf}, {"R", R}, {"lin_q", lin_q}, {"lin_r", lin_r}, {"K", K}, {"k", k},
-                                                            {"defects", defects}, {"dx_nodes", dx_nodes}, {"dJ", dJ}};
-    for (const auto& [name, p] : required) if (!p) return refuse(std::string("null ") + name);
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_shooting_forward", why); };
+    const PlantRequired required[] = {{"tape", tape}, {"Q", Q}, {"Qf", Qf}, {"R", R}, {"lin_q", lin_q}, {"lin_r", lin_r}, {"K", K}, {"k", k},
+                                      {"defects", defects}, {"dx_nodes", dx_nodes}, {"dJ", dJ}};
+    if (const char* name = plant_first_null(required)) return refuse(std::string("null ") + name);
     const PlantTapeBuffers& buf = tape->buf;
     const int B = tape->B, T = tape->T, n_cols = tape->n_cols;
     if (B < 1 || T < 1 || buf.device < 0 || buf.device >= PLANT_MAX_DEVICES || !buf.d_dz || !buf.d_status) return refuse("a closed tape");
@@ -344,43 +309,38 @@ extern "C" int cimpc_plant_shooting_forward(cimpc_plant_tape tape, int n_Q, cons
     const PlantModel& Mo = buf.M;
     const int nq = Mo.nq, nu = Mo.nu, nr = nq + Mo.nc + Mo.nb(), M = T / segment_len;
     if (nu < 1 || n_cols < 2 * nq + nu || nq > PLANT_MAX_Q || nu > PLANT_MAX_U) return refuse("a model without controls, or a tape without the control columns");
-    const size_t n = (size_t)2 * nq, m = (size_t)nu, TB = (size_t)T * B, n_def = (size_t)(M - 1) * B * n;
-    auto finite = [](const double* a, size_t cnt) { for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(a[i])) return false; return true; };
-    if (!finite(K, TB * m * n) || !finite(k, TB * m)) return refuse("a non-finite entry of K or k");
-    if (!finite(defects, n_def)) return refuse("a non-finite entry of defects");
-    size_t at = 0;
-    auto next = [&at](size_t cnt) { const size_t o = at; at += cnt; return o; };
-    const size_t i_Q = next((size_t)n_Q * n * n), i_Qf = next(n * n), i_R = next((size_t)n_R * m * m), i_lq = next((size_t)(T + 1) * B * n), i_lr = next(TB * m),
-                 i_K = next(TB * m * n), i_k = next(TB * m), i_d = next(n_def), n_in = at;
-    at = 0;
-    const size_t o_x = next(n_def), o_u = next(TB * m), o_J = next((size_t)2 * B), n_out = at;
-    std::lock_guard<std::mutex> lock(g_plant_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
-    if (cur != buf.device && hipSetDevice(buf.device) != hipSuccess) return CIMPC_ERR_HIP;
+    const size_t n = (size_t)2 * nq, m = (size_t)nu, TB = (size_t)T * B;
+    PlantCursor at;
+    const PlantSpan i_Q = at.take((size_t)n_Q * n * n), i_Qf = at.take(n * n), i_R = at.take((size_t)n_R * m * m), i_lq = at.take((size_t)(T + 1) * B * n),
+                    i_lr = at.take(TB * m), i_K = at.take(TB * m * n), i_k = at.take(TB * m), i_d = at.take((size_t)(M - 1) * B * n);
+    const size_t n_in = at.end();
+    const PlantSpan o_x = at.take(i_d.n), o_u = at.take(TB * m), o_J = at.take((size_t)2 * B);
+    const size_t n_out = at.end();
+    if (!plant_all_finite(K, i_K.n) || !plant_all_finite(k, i_k.n)) return refuse("a non-finite entry of K or k");
+    if (!plant_all_finite(defects, i_d.n)) return refuse("a non-finite entry of defects");
+    PlantDeviceScope scope(buf.device);
+    if (scope.rc() != CIMPC_OK) return scope.rc();
     bool ok_ = false;
     PlantWs* ws = plant_ws_open(buf.device);
-    ShootingWs& S = g_shooting_ws[buf.device];
-    if (ws && plant_grow(&S.d_in, &S.cap_in, n_in) && plant_grow(&S.d_out, &S.cap_out, n_out)) {
+    PlantStageWs& S = g_shooting_ws[buf.device];
+    if (ws && S.grow(n_in, n_out, 0)) {
         hipStream_t st = ws->st;
         ok_ = true;
-        auto up = [&](double* d, const double* hsrc, size_t cnt) { ok_ = ok_ && (!cnt || hipMemcpyAsync(d, hsrc, cnt * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess); };
-        auto down = [&](double* hdst, const double* d, size_t cnt) { ok_ = ok_ && (!cnt || hipMemcpyAsync(hdst, d, cnt * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess); };
+        PlantStreamCopier copy{{st}, ok_};
         double *I = S.d_in, *O = S.d_out;
-        up(I + i_Q, Q, (size_t)n_Q * n * n); up(I + i_Qf, Qf, n * n); up(I + i_R, R, (size_t)n_R * m * m); up(I + i_lq, lin_q, (size_t)(T + 1) * B * n);
-        up(I + i_lr, lin_r, TB * m); up(I + i_K, K, TB * m * n); up(I + i_k, k, TB * m); up(I + i_d, defects, n_def);
+        copy.up(I, i_Q, Q); copy.up(I, i_Qf, Qf); copy.up(I, i_R, R); copy.up(I, i_lq, lin_q);
+        copy.up(I, i_lr, lin_r); copy.up(I, i_K, K); copy.up(I, i_k, k); copy.up(I, i_d, defects);
         if (ok_) {
-            const PlantShootForward F{buf.d_dz, I + i_K, I + i_k, I + i_Q, I + i_Qf, I + i_R, I + i_lq, I + i_lr, I + i_d, O + o_x, O + o_u, O + o_J,
-                                      B, T, nq, nu, nr, n_cols, n_Q, n_R, segment_len};
+            const PlantShootForward F{buf.d_dz, i_K.on(I), i_k.on(I), i_Q.on(I), i_Qf.on(I), i_R.on(I), i_lq.on(I), i_lr.on(I), i_d.on(I), o_x.on(O), o_u.on(O),
+                                      o_J.on(O), B, T, nq, nu, nr, n_cols, n_Q, n_R, segment_len};
             hipLaunchKernelGGL(plant_shoot_forward_kernel, dim3(B), dim3(LS_THREADS), 0, st, F);
             ok_ = hipGetLastError() == hipSuccess;
         }
-        down(dx_nodes, O + o_x, n_def); down(dJ, O + o_J, (size_t)2 * B);
-        if (du) down(du, O + o_u, TB * m);
+        copy.down(dx_nodes, O, o_x); copy.down(dJ, O, o_J);
+        copy.down(du, O, o_u);      // where it is asked for
         ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;      // this stream only
     }
-    if (cur != buf.device) ok_ = (hipSetDevice(cur) == hipSuccess) && ok_;
-    return ok_ ? CIMPC_OK : CIMPC_ERR_HIP;
+    return scope.leave(ok_) ? CIMPC_OK : CIMPC_ERR_HIP;
 }
 
 extern "C" int cimpc_plant_rollout_segments(int model, int B, int T, int segments, int steps_per_launch, int n_terrain, const cimpc_terrain* terrain,
@@ -390,12 +350,12 @@ extern "C" int cimpc_plant_rollout_segments(int model, int B, int T, int segment
                                             double* lin_q, double* lin_r, int* grad_status, cimpc_plant_tape* tape) {
     using namespace cimpc;
     // every refusal leaves its reason where cimpc_last_error(NULL) finds it, before any device is touched
-    auto refuse = [](const std::string& why) { set_global_error("cimpc_plant_rollout_segments: " + why); return CIMPC_ERR_INVALID; };
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_rollout_segments", why); };
     if (!tape) return refuse("null tape");
     *tape = nullptr;
-    const std::pair<const char*, const void*> required[] = {{"nodes", nodes}, {"u", u}, {"mu", mu}, {"opts", opts}, {"qs", qs}, {"gamma", gamma}, {"b", b},
-                                                            {"status", status}, {"iters", iters}, {"defects", defects}, {"D", D}, {"grad_status", grad_status}};
-    for (const auto& [name, p] : required) if (!p) return refuse(std::string("null ") + name);
+    const PlantRequired required[] = {{"nodes", nodes}, {"u", u}, {"mu", mu}, {"opts", opts}, {"qs", qs}, {"gamma", gamma}, {"b", b},
+                                      {"status", status}, {"iters", iters}, {"defects", defects}, {"D", D}, {"grad_status", grad_status}};
+    if (const char* name = plant_first_null(required)) return refuse(std::string("null ") + name);
     if (cost && (!J || !lin_q || !lin_r)) return refuse("a cost without J, lin_q or lin_r");
     if (const char* why = plant_shooting_refusal(T, segments, B)) return refuse(why);
     {      // the nodes, by the model's nq from its id alone, before anything else reads the call
@@ -417,7 +377,7 @@ extern "C" int cimpc_plant_rollout_segments(int model, int B, int T, int segment
     const int M = segments, L = T / M, MB = M * B, nq = Mo.nq, nu = Mo.nu, nc = Mo.nc, nb = Mo.nb(), nw = Mo.nw, nr = nq + nc + nb;
     PlantCost C{};
     if (cost) {
-        C = shoot_cost_of(*cost, T, nq, nu);
+        C = plant_cost_of(*cost, T, nq, nu);
         if (const char* why = plant_cost_pointers(C)) return refuse(why);
         if (const char* why = plant_cost_sizes(C, B)) return refuse(why);
     }
@@ -429,21 +389,12 @@ extern "C" int cimpc_plant_rollout_segments(int model, int B, int T, int segment
                                 .gamma = gamma, .b = b, .status = status, .iters = iters,
                                 .grad = PlantRolloutGrad{reg, n_cols, nullptr, qs, grad_status, false}};
     const PlantRolloutLayout Lo = plant_rollout_layout(Mo, virt);
-    const size_t TB = (size_t)T * B, n = (size_t)2 * nq, block = (size_t)nr * n_cols, n_def = (size_t)(M - 1) * B * n;
+    const size_t TB = (size_t)T * B, block = (size_t)nr * n_cols;
     const int n_ter = !rough ? 0 : ter_each ? MB : 1;
     std::vector<cimpc_terrain> ter;      // the virtual robots' terrains: robot b's for every segment
     if (ter_each) for (int j = 0; j < M; ++j) ter.insert(ter.end(), terrain, terrain + B);
-    // the B-robot inputs in d_in, in the order they go up
-    size_t at = 0;
-    auto next = [&at](size_t cnt) { const size_t o = at; at += cnt; return o; };
-    const size_t i_nd = next((size_t)MB * n), i_u = next(TB * nu), i_w = next(has_w ? (size_t)K_w * n_w * nw : 0), i_mu = next(mu_each ? (size_t)B : 0),
-                 i_Q = next(cost ? (size_t)C.n_Q * n * n : 0), i_Qf = next(cost ? n * n : 0), i_R = next(cost ? (size_t)C.n_R * nu * nu : 0),
-                 i_xg = next(cost ? (size_t)(T + 1) * C.n_x * n : 0), i_ug = next(cost ? (size_t)T * C.n_x * nu : 0), n_in = at;
-    at = 0;      // the stitched outputs in d_out, in the order they come back
-    const size_t o_g = next(TB * nc), o_b = next(TB * nb), o_def = next(n_def), o_D = next((size_t)B), o_J = next((size_t)B), o_lt = next((size_t)(T + 1) * B),
-                 o_lq = next((size_t)(T + 1) * B * n), o_lr = next(TB * nu), n_out = at;
-    at = 0;
-    const size_t j_st = next(TB), j_it = next(TB), n_int = at;
+    // the B-robot inputs in d_in, the stitched outputs in d_out, the integers in d_int
+    const PlantSegmentsLayout Y = plant_segments_layout(Mo, C, PlantSegmentsShape{B, T, M, K_w, n_w, has_w, mu_each, cost != nullptr});
 
     int dev = 0;
     if (!plant_current_device(&dev)) return CIMPC_ERR_NO_DEVICE;
@@ -451,34 +402,27 @@ extern "C" int cimpc_plant_rollout_segments(int model, int B, int T, int segment
     bool ok_ = false;
     PlantTapeBuffers buf;
     PlantWs* ws = plant_ws_open(dev);
-    ShootingWs& S = g_shooting_ws[dev];
+    PlantStageWs& S = g_shooting_ws[dev];
     if (ws && plant_grow(&ws->d_in, &ws->cap_in, Lo.need_in) && plant_grow(&ws->d_out, &ws->cap_out, Lo.need_out) && plant_grow(&ws->d_st, &ws->cap_st, Lo.need_st) &&
         plant_grow(&ws->d_ter, &ws->cap_ter, (size_t)n_ter) && plant_grow(&ws->d_z, &ws->cap_z, Lo.need_z) && plant_grow(&ws->d_grad, &ws->cap_grad, Lo.need_grad) &&
-        plant_grow(&ws->d_grad_st, &ws->cap_grad_st, Lo.need_grad_st) && plant_grow(&S.d_in, &S.cap_in, n_in) && plant_grow(&S.d_out, &S.cap_out, n_out) &&
-        plant_grow(&S.d_int, &S.cap_int, n_int) && hipMalloc((void**)&buf.d_dz, TB * block * sizeof(double)) == hipSuccess) {      // the tape's memory, the last
+        plant_grow(&ws->d_grad_st, &ws->cap_grad_st, Lo.need_grad_st) && S.grow(Y.need_in, Y.need_out, Y.need_int) && hipMalloc((void**)&buf.d_dz, TB * block * sizeof(double)) == hipSuccess) {      // the tape's memory, the last
         if (hipMalloc((void**)&buf.d_status, TB * sizeof(int)) != hipSuccess) buf.d_status = nullptr;
         buf.device = dev; buf.M = Mo;
         PlantWs& W = *ws;
         hipStream_t st = W.st;
         ok_ = buf.d_status != nullptr;
-        auto up = [&](auto* d, const auto* hsrc, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(d, hsrc, cnt * sizeof(*d), hipMemcpyHostToDevice, st) == hipSuccess; };
-        auto down = [&](auto* hdst, const auto* d, size_t cnt) { ok_ = ok_ && hipMemcpyAsync(hdst, d, cnt * sizeof(*d), hipMemcpyDeviceToHost, st) == hipSuccess; };
+        PlantStreamCopier copy{{st}, ok_};
         double *I = S.d_in, *O = S.d_out;
         int* N = S.d_int;
-        up(I + i_nd, nodes, (size_t)MB * n); up(I + i_u, u, TB * nu);
-        if (has_w) up(I + i_w, w, (size_t)K_w * n_w * nw);
-        if (mu_each) up(I + i_mu, mu, (size_t)B);
-        if (rough) up(W.d_ter, ter_each ? ter.data() : terrain, (size_t)n_ter);
-        if (cost) {
-            up(I + i_Q, C.Q, (size_t)C.n_Q * n * n); up(I + i_Qf, C.Qf, n * n); up(I + i_R, C.R, (size_t)C.n_R * nu * nu);
-            up(I + i_xg, C.x_goal, (size_t)(T + 1) * C.n_x * n); up(I + i_ug, C.u_goal, (size_t)T * C.n_x * nu);
-            C.Q = I + i_Q; C.Qf = I + i_Qf; C.R = I + i_R; C.x_goal = I + i_xg; C.u_goal = I + i_ug;
-        }
+        copy.up(I, Y.nodes, nodes); copy.up(I, Y.u, u);
+        copy.up(I, Y.w, w); copy.up(I, Y.mu, mu);      // w where it is given, mu where it is per robot
+        if (rough) copy.up(W.d_ter, PlantSpan{0, (size_t)n_ter}, ter_each ? ter.data() : terrain);
+        if (cost) C = plant_cost_up(copy, I, Y.cost, C);
         double *dq = W.d_in + Lo.q.at, *du = W.d_in + Lo.u.at, *dw = W.d_in + Lo.w.at, *dmu = W.d_in + Lo.mu.at;
         double *dg = W.d_out + Lo.gamma.at, *db = W.d_out + Lo.b.at, *d_dz = W.d_grad + Lo.dz.at;
         int *d_st = W.d_st + Lo.status.at, *d_it = W.d_st + Lo.iters.at, *d_gst = W.d_grad_st + Lo.grad_status.at;
         if (ok_) {
-            const PlantShootSpread Sp{I + i_nd, I + i_u, has_w ? I + i_w : nullptr, mu_each ? I + i_mu : nullptr, dq, du, dw, dmu, B, M, L, nq, nu, nw,
+            const PlantShootSpread Sp{Y.nodes.on(I), Y.u.on(I), Y.w.or_null(I), Y.mu.or_null(I), dq, du, dw, dmu, B, M, L, nq, nu, nw,
                                       has_w ? K_w : 1, has_w ? n_w : 1, has_w ? hold_w : 1};
             hipLaunchKernelGGL(plant_shoot_spread_kernel, dim3((unsigned)TB), dim3(LS_THREADS), 0, st, Sp);
             ok_ = hipGetLastError() == hipSuccess;
@@ -491,20 +435,20 @@ extern "C" int cimpc_plant_rollout_segments(int model, int B, int T, int segment
             ok_ = plant_sensitivity_launch(Mo, (int)TB, src, rough ? W.d_ter : nullptr, n_ter, reg, n_cols, d_dz, d_gst, st);
         }
         if (ok_) {
-            const PlantShootStitch Ss{C, dq, I + i_u, dg, db, d_dz, d_st, d_it, d_gst, O + o_g, O + o_b, buf.d_dz, N + j_st, N + j_it, buf.d_status,
-                                      O + o_def, O + o_lt, O + o_lq, O + o_lr, B, M, T, nq, nu, nc, nb, (int)block};
+            const PlantShootStitch Ss{C, dq, Y.u.on(I), dg, db, d_dz, d_st, d_it, d_gst, Y.gamma.on(O), Y.b.on(O), buf.d_dz, Y.status.on(N), Y.iters.on(N),
+                                      buf.d_status, Y.defects.on(O), Y.lt.on(O), Y.lin_q.on(O), Y.lin_r.on(O), B, M, T, nq, nu, nc, nb, (int)block};
             hipLaunchKernelGGL(plant_shoot_stitch_kernel, dim3((unsigned)((T + 1) * B)), dim3(LS_THREADS), 0, st, Ss);
             ok_ = hipGetLastError() == hipSuccess;
         }
         if (ok_) {
             hipLaunchKernelGGL(plant_shoot_total_kernel, dim3((unsigned)((B + SHOOT_TOTAL_THREADS - 1) / SHOOT_TOTAL_THREADS)), dim3(SHOOT_TOTAL_THREADS), 0, st,
-                               (const double*)(O + o_def), cost ? (const double*)(O + o_lt) : nullptr, O + o_D, O + o_J, B, M, T, nq);
+                               (const double*)Y.defects.on(O), cost ? (const double*)Y.lt.on(O) : nullptr, Y.D.on(O), Y.J.on(O), B, M, T, nq);
             ok_ = hipGetLastError() == hipSuccess;
         }
-        down(qs, dq, (size_t)(L + 2) * MB * nq); down(gamma, O + o_g, TB * nc); down(b, O + o_b, TB * nb); down(status, N + j_st, TB);
-        down(iters, N + j_it, TB); down(D, O + o_D, (size_t)B); down(grad_status, buf.d_status, TB);
-        if (n_def) down(defects, O + o_def, n_def);
-        if (cost) { down(J, O + o_J, (size_t)B); down(lin_q, O + o_lq, (size_t)(T + 1) * B * n); down(lin_r, O + o_lr, TB * nu); }
+        copy.down(qs, W.d_in, Lo.q); copy.down(gamma, O, Y.gamma); copy.down(b, O, Y.b); copy.down(status, N, Y.status);
+        copy.down(iters, N, Y.iters); copy.down(D, O, Y.D); copy.down(grad_status, buf.d_status, PlantSpan{0, TB});
+        copy.down(defects, O, Y.defects);      // none with one segment
+        if (cost) { copy.down(J, O, Y.J); copy.down(lin_q, O, Y.lin_q); copy.down(lin_r, O, Y.lin_r); }
         ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;      // this stream only
     }
     if (!ok_) { (void)buf.release(); return CIMPC_ERR_HIP; }
@@ -524,15 +468,15 @@ extern "C" int cimpc_plant_shooting_linesearch(cimpc_plant_tape tape, int segmen
                                                int* status, int* iters, double* defects, double* D, double* J_chosen, double* lin_q, double* lin_r,
                                                int* grad_status, cimpc_plant_tape* new_tape, int n_lim, const double* u_lo, const double* u_hi) {
     using namespace cimpc;
-    auto refuse = [](const std::string& why) { set_global_error("cimpc_plant_shooting_linesearch: " + why); return CIMPC_ERR_INVALID; };
+    auto refuse = [](const std::string& why) { return plant_refuse("cimpc_plant_shooting_linesearch", why); };
     if (!new_tape) return refuse("null new_tape");
     *new_tape = nullptr;
-    const std::pair<const char*, const void*> required[] = {
+    const PlantRequired required[] = {
         {"tape", tape}, {"qs_nom", qs_nom}, {"u_nom", u_nom}, {"mu", mu}, {"opts", opts}, {"K", K}, {"k", k}, {"dx_nodes", dx_nodes}, {"dJ", dJ}, {"phi_nom", phi_nom},
         {"D_nom", D_nom}, {"alpha", alpha}, {"cost", cost}, {"J", J}, {"D_cand", D_cand}, {"phi", phi}, {"ok", ok}, {"choice", choice}, {"qs", qs},
         {"u_applied", u_applied}, {"gamma", gamma}, {"b", b}, {"status", status}, {"iters", iters}, {"defects", defects}, {"D", D}, {"J_chosen", J_chosen},
         {"lin_q", lin_q}, {"lin_r", lin_r}, {"grad_status", grad_status}};
-    for (const auto& [name, p] : required) if (!p) return refuse(std::string("null ") + name);
+    if (const char* name = plant_first_null(required)) return refuse(std::string("null ") + name);
     if (const char* why = plant_linesearch_refusal(n_alpha, alpha, armijo)) return refuse(why);
     const PlantTapeBuffers& parent = tape->buf;
     const int B = tape->B, T = tape->T, n_cols = tape->n_cols, model = tape->model;
@@ -553,14 +497,13 @@ extern "C" int cimpc_plant_shooting_linesearch(cimpc_plant_tape tape, int segmen
     PlantModel Mc{};
     bool rough = false;
     if (!plant_model_and_ground(model, B, n_terrain, terrain, &Mc, &rough)) return refuse("a terrain the model does not take");
-    PlantCost C = shoot_cost_of(*cost, T, nq, nu);
+    PlantCost C = plant_cost_of(*cost, T, nq, nu);
     if (const char* why = plant_cost_pointers(C)) return refuse(why);
     if (const char* why = plant_cost_sizes(C, B)) return refuse(why);
     const size_t TB = (size_t)T * B, n = (size_t)2 * nq, kk = (size_t)nu * n, block = (size_t)nr * n_cols, n_def = (size_t)(M - 1) * B * n, n_qs = (size_t)(L + 2) * MB * nq;
-    auto finite = [](const double* a, size_t cnt) { for (size_t i = 0; i < cnt; ++i) if (!std::isfinite(a[i])) return false; return true; };
-    if (!finite(K, TB * kk) || !finite(k, TB * nu)) return refuse("a non-finite entry of K or k");
-    if (!finite(qs_nom, n_qs) || !finite(u_nom, TB * nu)) return refuse("a non-finite entry of qs_nom or u_nom");
-    if (!finite(dx_nodes, n_def)) return refuse("a non-finite entry of dx_nodes");
+    if (!plant_all_finite(K, TB * kk) || !plant_all_finite(k, TB * nu)) return refuse("a non-finite entry of K or k");
+    if (!plant_all_finite(qs_nom, n_qs) || !plant_all_finite(u_nom, TB * nu)) return refuse("a non-finite entry of qs_nom or u_nom");
+    if (!plant_all_finite(dx_nodes, n_def)) return refuse("a non-finite entry of dx_nodes");
     const bool has_w = w != nullptr, mu_each = n_mu != 1, lim_each = limits && n_lim != 1, ter_each = rough && n_terrain != 1;
     // the candidates' rollout in the plant workspace, laid out as a closed-loop tape call of NB robots over L steps lays itself out
     const cimpc_feedback fb_shape{qs_nom, qs_nom, L, NB, 1, 1.0};      // only the shape is read
@@ -573,63 +516,58 @@ extern "C" int cimpc_plant_shooting_linesearch(cimpc_plant_tape tape, int segmen
     std::vector<cimpc_terrain> ter;      // the candidates' terrains: robot b's for every (c, j)
     if (ter_each) for (int cj = 0; cj < n_alpha * M; ++cj) ter.insert(ter.end(), terrain, terrain + B);
     const size_t nA = (size_t)n_alpha * B;
-    size_t at = 0;
-    auto next = [&at](size_t cnt) { const size_t o = at; at += cnt; return o; };
-    const size_t i_q = next(n_qs), i_u = next(TB * nu), i_k = next(TB * nu), i_K = next(TB * kk), i_dx = next(n_def), i_w = next(has_w ? (size_t)K_w * n_w * nw : 0),
-                 i_mu = next(mu_each ? (size_t)B : 0), i_dJ = next((size_t)2 * B), i_pn = next((size_t)B), i_Dn = next((size_t)B), i_al = next((size_t)n_alpha),
-                 i_wt = next((size_t)n_weight), i_Q = next((size_t)C.n_Q * n * n), i_Qf = next(n * n), i_R = next((size_t)C.n_R * nu * nu),
-                 i_xg = next((size_t)(T + 1) * C.n_x * n), i_ug = next((size_t)T * C.n_x * nu), i_lo = next(limits ? (size_t)n_lim * nu : 0),
-                 i_hi = next(limits ? (size_t)n_lim * nu : 0), n_in = at;
-    at = 0;
-    const size_t o_J = next(nA), o_Dc = next(nA), o_phi = next(nA), o_q = next(n_qs), o_z = next(TB * nz), o_u = next(TB * nu), o_us = next(TB * nu), o_gv = next(TB * nc),
-                 o_bv = next(TB * nb), o_w = next(has_w ? TB * nw : 0), o_mu = next(mu_each ? (size_t)MB : 0), o_g = next(TB * nc), o_b = next(TB * nb),
-                 o_def = next(n_def), o_D = next((size_t)B), o_Jn = next((size_t)B), o_lt = next((size_t)(T + 1) * B), o_lq = next((size_t)(T + 1) * B * n),
-                 o_lr = next(TB * nu), n_out = at;
-    at = 0;
-    const size_t j_ok = next(nA), j_ch = next((size_t)B), j_conv = next(nA), j_stv = next(TB), j_itv = next(TB), j_st = next(TB), j_it = next(TB), n_int = at;
+    // the B-robot inputs in d_in, in the order they go up
+    PlantCursor at;
+    const PlantSpan i_q = at.take(n_qs), i_u = at.take(TB * nu), i_k = at.take(TB * nu), i_K = at.take(TB * kk), i_dx = at.take(n_def),
+                    i_w = at.take(has_w ? (size_t)K_w * n_w * nw : 0), i_mu = at.take(mu_each ? (size_t)B : 0), i_dJ = at.take((size_t)2 * B), i_pn = at.take((size_t)B),
+                    i_Dn = at.take((size_t)B), i_al = at.take((size_t)n_alpha), i_wt = at.take((size_t)n_weight);
+    const PlantCostSpans i_cost = plant_cost_spans(at, C);
+    const PlantSpan i_lo = at.take(limits ? (size_t)n_lim * nu : 0), i_hi = at.take(limits ? (size_t)n_lim * nu : 0);
+    const size_t n_in = at.end();
+    // d_out: the candidates' J, D, phi | the chosen segments as M B virtual robots | the stitched outputs
+    const PlantSpan o_J = at.take(nA), o_Dc = at.take(nA), o_phi = at.take(nA), o_q = at.take(n_qs), o_z = at.take(TB * nz), o_u = at.take(TB * nu), o_us = at.take(TB * nu),
+                    o_gv = at.take(TB * nc), o_bv = at.take(TB * nb), o_w = at.take(has_w ? TB * nw : 0), o_mu = at.take(mu_each ? (size_t)MB : 0), o_g = at.take(TB * nc),
+                    o_b = at.take(TB * nb), o_def = at.take(n_def), o_D = at.take((size_t)B), o_Jn = at.take((size_t)B), o_lt = at.take((size_t)(T + 1) * B),
+                    o_lq = at.take((size_t)(T + 1) * B * n), o_lr = at.take(TB * nu);
+    const size_t n_out = at.end();
+    const PlantSpan j_ok = at.take(nA), j_ch = at.take((size_t)B), j_conv = at.take(nA), j_stv = at.take(TB), j_itv = at.take(TB), j_st = at.take(TB), j_it = at.take(TB);
+    const size_t n_int = at.end();
 
-    std::lock_guard<std::mutex> lock(g_plant_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
     const int dev = parent.device;
-    if (cur != dev && hipSetDevice(dev) != hipSuccess) return CIMPC_ERR_HIP;
+    PlantDeviceScope scope(dev);
+    if (scope.rc() != CIMPC_OK) return scope.rc();
     bool ok_ = false;
     PlantTapeBuffers buf;
     PlantWs* ws = plant_ws_open(dev);
-    ShootingWs& S = g_shooting_ws[dev];
+    PlantStageWs& S = g_shooting_ws[dev];
     if (ws && plant_grow(&ws->d_in, &ws->cap_in, Lo.need_in) && plant_grow(&ws->d_out, &ws->cap_out, Lo.need_out) && plant_grow(&ws->d_st, &ws->cap_st, Lo.need_st) &&
         plant_grow(&ws->d_ter, &ws->cap_ter, (size_t)n_ter) && plant_grow(&ws->d_z, &ws->cap_z, Lo.need_z) && plant_grow(&ws->d_fb, &ws->cap_fb, Lo.need_fb) &&
-        plant_grow(&ws->d_grad, &ws->cap_grad, TB * block) && plant_grow(&ws->d_grad_st, &ws->cap_grad_st, TB) && plant_grow(&S.d_in, &S.cap_in, n_in) &&
-        plant_grow(&S.d_out, &S.cap_out, n_out) && plant_grow(&S.d_int, &S.cap_int, n_int) &&
+        plant_grow(&ws->d_grad, &ws->cap_grad, TB * block) && plant_grow(&ws->d_grad_st, &ws->cap_grad_st, TB) && S.grow(n_in, n_out, n_int) &&
         hipMalloc((void**)&buf.d_dz, TB * block * sizeof(double)) == hipSuccess) {      // the new tape's memory, the last to be allocated
         if (hipMalloc((void**)&buf.d_status, TB * sizeof(int)) != hipSuccess) buf.d_status = nullptr;
         buf.device = dev; buf.M = Mo;
         PlantWs& W = *ws;
         hipStream_t st = W.st;
         ok_ = buf.d_status != nullptr;
-        auto up = [&](auto* d, const auto* hsrc, size_t cnt) { ok_ = ok_ && (!cnt || hipMemcpyAsync(d, hsrc, cnt * sizeof(*d), hipMemcpyHostToDevice, st) == hipSuccess); };
-        auto down = [&](auto* hdst, const auto* d, size_t cnt) { ok_ = ok_ && (!cnt || hipMemcpyAsync(hdst, d, cnt * sizeof(*d), hipMemcpyDeviceToHost, st) == hipSuccess); };
+        PlantStreamCopier copy{{st}, ok_};
         double *I = S.d_in, *O = S.d_out;
         int* N = S.d_int;
-        up(I + i_q, qs_nom, n_qs); up(I + i_u, u_nom, TB * nu); up(I + i_k, k, TB * nu); up(I + i_K, K, TB * kk); up(I + i_dx, dx_nodes, n_def);
-        if (has_w) up(I + i_w, w, (size_t)K_w * n_w * nw);
-        if (mu_each) up(I + i_mu, mu, (size_t)B);
-        up(I + i_dJ, dJ, (size_t)2 * B); up(I + i_pn, phi_nom, (size_t)B); up(I + i_Dn, D_nom, (size_t)B); up(I + i_al, alpha, (size_t)n_alpha);
-        up(I + i_wt, weight, (size_t)n_weight);
-        up(I + i_Q, C.Q, (size_t)C.n_Q * n * n); up(I + i_Qf, C.Qf, n * n); up(I + i_R, C.R, (size_t)C.n_R * nu * nu);
-        up(I + i_xg, C.x_goal, (size_t)(T + 1) * C.n_x * n); up(I + i_ug, C.u_goal, (size_t)T * C.n_x * nu);
-        if (limits) { up(I + i_lo, u_lo, (size_t)n_lim * nu); up(I + i_hi, u_hi, (size_t)n_lim * nu); }
-        if (rough) up(W.d_ter, ter_each ? ter.data() : terrain, (size_t)n_ter);
-        C.Q = I + i_Q; C.Qf = I + i_Qf; C.R = I + i_R; C.x_goal = I + i_xg; C.u_goal = I + i_ug;
+        copy.up(I, i_q, qs_nom); copy.up(I, i_u, u_nom); copy.up(I, i_k, k); copy.up(I, i_K, K); copy.up(I, i_dx, dx_nodes);
+        copy.up(I, i_w, w); copy.up(I, i_mu, mu);      // w where it is given, mu where it is per robot
+        copy.up(I, i_dJ, dJ); copy.up(I, i_pn, phi_nom); copy.up(I, i_Dn, D_nom); copy.up(I, i_al, alpha);
+        copy.up(I, i_wt, weight);
+        C = plant_cost_up(copy, I, i_cost, C);
+        copy.up(I, i_lo, u_lo); copy.up(I, i_hi, u_hi);
+        if (rough) copy.up(W.d_ter, PlantSpan{0, (size_t)n_ter}, ter_each ? ter.data() : terrain);
         double *dq = W.d_in + Lo.q.at, *du = W.d_in + Lo.u.at, *dw = W.d_in + Lo.w.at, *dmu = W.d_in + Lo.mu.at;
         double *d_fk = W.d_fb + Lo.fb_K.at, *d_fx = W.d_fb + Lo.x_ref.at, *d_ua = W.d_fb + Lo.u_applied.at, *d_fe = W.d_fb + Lo.fb_err.at;
         double *dg = W.d_out + Lo.gamma.at, *db = W.d_out + Lo.b.at;
         int *d_st = W.d_st + Lo.status.at, *d_it = W.d_st + Lo.iters.at;
-        const double *c_lo = !limits ? nullptr : lim_each ? W.d_fb + Lo.u_lo.at : I + i_lo, *c_hi = !limits ? nullptr : lim_each ? W.d_fb + Lo.u_hi.at : I + i_hi;
+        const double *c_lo = !limits ? nullptr : lim_each ? W.d_fb + Lo.u_lo.at : i_lo.on(I), *c_hi = !limits ? nullptr : lim_each ? W.d_fb + Lo.u_hi.at : i_hi.on(I);
         if (ok_) {
-            const PlantShootExpand E{I + i_q, I + i_u, I + i_k, I + i_K, I + i_dx, has_w ? I + i_w : nullptr, mu_each ? I + i_mu : nullptr, I + i_al,
+            const PlantShootExpand E{i_q.on(I), i_u.on(I), i_k.on(I), i_K.on(I), i_dx.on(I), i_w.or_null(I), i_mu.or_null(I), i_al.on(I),
                                      dq, du, d_fk, d_fx, dw, dmu, B, M, L, NB, nq, nu, nw, has_w ? K_w : 1, has_w ? n_w : 1, has_w ? hold_w : 1,
-                                     limits ? I + i_lo : nullptr, limits ? I + i_hi : nullptr, lim_each ? W.d_fb + Lo.u_lo.at : nullptr,
+                                     i_lo.or_null(I), i_hi.or_null(I), lim_each ? W.d_fb + Lo.u_lo.at : nullptr,
                                      lim_each ? W.d_fb + Lo.u_hi.at : nullptr, n_lim};
             hipLaunchKernelGGL(plant_shoot_expand_kernel, dim3((unsigned)(L * NB)), dim3(LS_THREADS), 0, st, E);
             ok_ = hipGetLastError() == hipSuccess;
@@ -638,47 +576,43 @@ extern "C" int cimpc_plant_shooting_linesearch(cimpc_plant_tape tape, int segmen
                                 mu_each ? NB : 1, W.d_z, PlantFeedback{d_fk, d_fx, L, NB, 1, 1.0}, d_ua, d_fe, PlantFeedbackLimits{c_lo, c_hi, lim_each ? NB : 1}};
         ok_ = ok_ && plant_step_chunks(Mo, rough, *opts, NB, L, steps_per_launch, R, rough ? W.d_ter : nullptr, n_ter, st);
         if (ok_) {
-            const PlantShootCandCost Pc{C, dq, d_ua, d_st, O + o_J, O + o_Dc, N + j_conv, B, M, NB, n_alpha};
+            const PlantShootCandCost Pc{C, dq, d_ua, d_st, o_J.on(O), o_Dc.on(O), j_conv.on(N), B, M, NB, n_alpha};
             hipLaunchKernelGGL(plant_shoot_cand_cost_kernel, dim3((unsigned)nA), dim3(LS_THREADS), 0, st, Pc);
             ok_ = hipGetLastError() == hipSuccess;
         }
         if (ok_) {
-            const PlantShootGather G{dq, W.d_z, d_ua, dg, db, has_w ? dw : nullptr, d_st, d_it, N + j_conv, O + o_J, O + o_Dc, I + i_pn, I + i_Dn, I + i_dJ, I + i_al,
-                                     I + i_wt, armijo, n_alpha, n_weight, O + o_phi, N + j_ok, N + j_ch, O + o_q, O + o_z, O + o_u, O + o_us, O + o_gv, O + o_bv,
-                                     has_w ? O + o_w : nullptr, mu_each ? O + o_mu : nullptr, mu_each ? I + i_mu : nullptr, N + j_stv, N + j_itv, B, M, L, NB, nq, nu, nc,
+            const PlantShootGather G{dq, W.d_z, d_ua, dg, db, has_w ? dw : nullptr, d_st, d_it, j_conv.on(N), o_J.on(O), o_Dc.on(O), i_pn.on(I), i_Dn.on(I), i_dJ.on(I), i_al.on(I),
+                                     i_wt.on(I), armijo, n_alpha, n_weight, o_phi.on(O), j_ok.on(N), j_ch.on(N), o_q.on(O), o_z.on(O), o_u.on(O), o_us.on(O), o_gv.on(O), o_bv.on(O),
+                                     o_w.or_null(O), o_mu.or_null(O), i_mu.or_null(I), j_stv.on(N), j_itv.on(N), B, M, L, NB, nq, nu, nc,
                                      nb, nz, nw};
             hipLaunchKernelGGL(plant_shoot_gather_kernel, dim3((unsigned)((L + 2) * MB)), dim3(LS_THREADS), 0, st, G);
             ok_ = hipGetLastError() == hipSuccess;
         }
         if (ok_) {      // the chosen segments' step gradients, each on its own virtual robot's rows l, l+1 and the control its step applied
-            const PlantSensSource src{O + o_z, nullptr, O + o_q, O + o_u, has_w ? O + o_w : nullptr, mu_each ? O + o_mu : nullptr, N + j_stv, mu[0], h, MB, L, MB, 1,
+            const PlantSensSource src{o_z.on(O), nullptr, o_q.on(O), o_u.on(O), o_w.or_null(O), o_mu.or_null(O), j_stv.on(N), mu[0], h, MB, L, MB, 1,
                                       has_w ? L : 1, has_w ? MB : 1, 1, mu_each ? MB : 1};
             ok_ = plant_sensitivity_launch(Mo, (int)TB, src, rough ? W.d_ter : nullptr, !rough ? 0 : ter_each ? MB : 1, reg, n_cols, W.d_grad, W.d_grad_st, st);
         }
         if (ok_) {
-            const PlantShootStitch Ss{C, O + o_q, O + o_us, O + o_gv, O + o_bv, W.d_grad, N + j_stv, N + j_itv, W.d_grad_st, O + o_g, O + o_b, buf.d_dz, N + j_st, N + j_it,
-                                      buf.d_status, O + o_def, O + o_lt, O + o_lq, O + o_lr, B, M, T, nq, nu, nc, nb, (int)block};
+            const PlantShootStitch Ss{C, o_q.on(O), o_us.on(O), o_gv.on(O), o_bv.on(O), W.d_grad, j_stv.on(N), j_itv.on(N), W.d_grad_st, o_g.on(O), o_b.on(O), buf.d_dz, j_st.on(N), j_it.on(N),
+                                      buf.d_status, o_def.on(O), o_lt.on(O), o_lq.on(O), o_lr.on(O), B, M, T, nq, nu, nc, nb, (int)block};
             hipLaunchKernelGGL(plant_shoot_stitch_kernel, dim3((unsigned)((T + 1) * B)), dim3(LS_THREADS), 0, st, Ss);
             ok_ = hipGetLastError() == hipSuccess;
         }
         if (ok_) {
             hipLaunchKernelGGL(plant_shoot_total_kernel, dim3((unsigned)((B + SHOOT_TOTAL_THREADS - 1) / SHOOT_TOTAL_THREADS)), dim3(SHOOT_TOTAL_THREADS), 0, st,
-                               (const double*)(O + o_def), (const double*)(O + o_lt), O + o_D, O + o_Jn, B, M, T, nq);
+                               (const double*)o_def.on(O), (const double*)o_lt.on(O), o_D.on(O), o_Jn.on(O), B, M, T, nq);
             ok_ = hipGetLastError() == hipSuccess;
         }
-        if (ok_) {
-            hipLaunchKernelGGL(plant_shoot_restore_kernel, dim3((unsigned)TB), dim3(LS_THREADS), 0, st, (const int*)(N + j_ch), (const double*)parent.d_dz,
-                               (const int*)parent.d_status, buf.d_dz, buf.d_status, B, T, (int)block);
-            ok_ = hipGetLastError() == hipSuccess;
-        }
-        down(J, O + o_J, nA); down(D_cand, O + o_Dc, nA); down(phi, O + o_phi, nA); down(ok, N + j_ok, nA); down(choice, N + j_ch, (size_t)B);
-        down(qs, O + o_q, n_qs); down(u_applied, O + o_us, TB * nu); down(gamma, O + o_g, TB * nc); down(b, O + o_b, TB * nb); down(status, N + j_st, TB);
-        down(iters, N + j_it, TB); down(defects, O + o_def, n_def); down(D, O + o_D, (size_t)B); down(J_chosen, O + o_Jn, (size_t)B);
-        down(lin_q, O + o_lq, (size_t)(T + 1) * B * n); down(lin_r, O + o_lr, TB * nu); down(grad_status, buf.d_status, TB);
+        ok_ = ok_ && plant_restore_launch(j_ch.on(N), parent.d_dz, parent.d_status, buf.d_dz, buf.d_status, B, T, (int)block, st);
+        copy.down(J, O, o_J); copy.down(D_cand, O, o_Dc); copy.down(phi, O, o_phi); copy.down(ok, N, j_ok); copy.down(choice, N, j_ch);
+        copy.down(qs, O, o_q); copy.down(u_applied, O, o_us); copy.down(gamma, O, o_g); copy.down(b, O, o_b); copy.down(status, N, j_st);
+        copy.down(iters, N, j_it); copy.down(defects, O, o_def); copy.down(D, O, o_D); copy.down(J_chosen, O, o_Jn);
+        copy.down(lin_q, O, o_lq); copy.down(lin_r, O, o_lr); copy.down(grad_status, buf.d_status, PlantSpan{0, TB});
         ok_ = (hipStreamSynchronize(st) == hipSuccess) && ok_;      // this stream only
     }
     if (!ok_) (void)buf.release();
-    if (cur != dev) ok_ = (hipSetDevice(cur) == hipSuccess) && ok_;
+    ok_ = scope.leave(ok_);
     if (!ok_) { (void)buf.release(); return CIMPC_ERR_HIP; }
     *new_tape = new cimpc_plant_tape_s{buf, model, B, T, n_cols};
     return CIMPC_OK;

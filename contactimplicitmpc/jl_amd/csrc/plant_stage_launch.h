@@ -8,6 +8,7 @@
 //   plant_linesearch_shared    the uploads that do not pass through the expansion kernel: a shared w schedule, the terrains
 //   plant_linesearch_stages    the kernels of one line search back to back on `st`: expand, the step kernel's chunks, cost, gather, ONE
 //                              sensitivity launch, restore.  Nothing is copied or synchronized.
+//   plant_restore_launch       the last of those stages on its own
 //   plant_riccati_box_launch   plant_riccati_kernel<true, true> on `st`
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +33,32 @@ struct PlantCostWave {
     __device__ int rank() const { return threadIdx.x; }
     __device__ int size() const { return LS_THREADS; }
     __device__ void sync() const { __syncthreads(); }
+};
+
+// A workgroup of THREADS as the team of a chain that fetches the next step's corner while it works a step (plant_riccati.h's Team;
+// plant_shoot_forward_chain's): fetch_issue loads up to STAGE x THREADS doubles of the rows x cols corner of a column-major block with
+// leading dimension ld into registers, fetch_commit leaves them packed in dst and reads what did not fit straight from src.
+template <int THREADS, int STAGE>
+struct PlantCornerTeam {
+    double stage[STAGE];
+    __device__ int rank() const { return threadIdx.x; }
+    __device__ int size() const { return THREADS; }
+    __device__ void sync() const { __syncthreads(); }
+    __device__ void fetch_issue(const double* src, int rows, int cols, int ld) {
+#pragma unroll
+        for (int k = 0; k < STAGE; ++k) {
+            const int i = k * THREADS + (int)threadIdx.x;
+            stage[k] = i < rows * cols ? src[(size_t)(i / rows) * ld + i % rows] : 0.0;
+        }
+    }
+    __device__ void fetch_commit(double* dst, const double* src, int rows, int cols, int ld) {
+#pragma unroll
+        for (int k = 0; k < STAGE; ++k) {
+            const int i = k * THREADS + (int)threadIdx.x;
+            if (i < rows * cols) dst[i] = stage[k];
+        }
+        for (int i = STAGE * THREADS + (int)threadIdx.x; i < rows * cols; i += THREADS) dst[i] = src[(size_t)(i / rows) * ld + i % rows];
+    }
 };
 
 // The host arguments a line search is planned from (the names of cimpc_plant_tape_linesearch_box).  q .. grad_status are the caller's
@@ -97,6 +124,11 @@ bool plant_linesearch_stages(const PlantLsPlan& P, const PlantLsArrays& A, Plant
 // The line search calls it, and so does the sampling policy (plant_sample.hip).
 bool plant_candidates_cost_launch(const PlantCost& C, const double* q, const double* u_applied, const int* status, double* J, int* conv, int B, int NB,
                                   hipStream_t st);
+
+// plant_ls_restore_kernel on `st`, all device memory: entry t B + b of the new tape (dz: blocks of `block` doubles; status) gets the parent's
+// where choice[b] < 0.  The line search calls it, and so does the line search of multiple shooting (plant_shooting.hip; section 3, item 3l).
+bool plant_restore_launch(const int* choice, const double* parent_dz, const int* parent_status, double* dz, int* status, int B, int T, int block,
+                          hipStream_t st);
 
 // One iteration of the device-resident iLQR loop (plant_ilqr.hip), all device memory: the rules' state
 // (ladder, level, active, J; plant_ilqr.h) and rows (rho_b, J_nom), the nominal (N*), the backward pass's outputs, the limits (null: none),

@@ -95,10 +95,8 @@ extern "C" int cimpc_plant_tape_jvp_feedback(cimpc_plant_tape tape, int n_dir, c
     const size_t i_q0 = dq0 ? nD * B * nq : 0, i_q1 = dq1 ? nD * B * nq : 0, i_u = du_step ? nD * TB * nu : 0, i_w = dw_step ? nD * TB * nw : 0,
                  i_m = dmu ? nD * B : 0, i_h = dh ? nD * B : 0, i_x = dxref_step ? nD * TB * 2 * nq : 0;
     const size_t o_q = nD * (size_t)(T + 2) * B * nq, o_g = dgamma ? nD * TB * nc : 0, o_b = db ? nD * TB * nb : 0, o_u = du_applied ? nD * TB * nu : 0;
-    std::lock_guard<std::mutex> lock(g_plant_mu);
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) return CIMPC_ERR_NO_DEVICE;
-    if (cur != buf.device && hipSetDevice(buf.device) != hipSuccess) return CIMPC_ERR_HIP;
+    PlantDeviceScope scope(buf.device);
+    if (scope.rc() != CIMPC_OK) return scope.rc();
     bool ok = false;
     PlantWs* ws = plant_ws_open(buf.device);
     if (ws && plant_grow(&ws->d_tan_in, &ws->cap_tan_in, i_q0 + i_q1 + i_u + i_w + i_m + i_h + i_x) &&
@@ -131,8 +129,7 @@ extern "C" int cimpc_plant_tape_jvp_feedback(cimpc_plant_tape tape, int n_dir, c
                      hipMemcpyAsync(n_cut, ws->d_tan_cut, (size_t)B * sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
         ok = (hipStreamSynchronize(st) == hipSuccess) && ok;      // this stream only
     }
-    if (cur != buf.device) ok = (hipSetDevice(cur) == hipSuccess) && ok;
-    return ok ? CIMPC_OK : CIMPC_ERR_HIP;
+    return scope.leave(ok) ? CIMPC_OK : CIMPC_ERR_HIP;
 }
 
 extern "C" int cimpc_plant_tape_jvp(cimpc_plant_tape tape, int n_dir, const double* dq0, const double* dq1, const double* du_step,

@@ -16,10 +16,19 @@
 //                   and the history in two buffers of its own   (plant_ilqr.hip)
 //   MPC policy      the same candidates' rollout at every control step; everything else - the problem, the plan, its nominal, three tape
 //                   buffers - belongs to the cimpc_plant_mpc handle, which copies its terrains into d_ter at every step   (plant_mpc.hip)
+//   sampling policy the candidates' open-loop rollout in d_in, d_out, d_st, d_ter; the problem and the plan belong to the
+//                   cimpc_plant_sampler handle   (plant_sample.hip)
+//   shooting        cimpc_plant_rollout_segments: the M B virtual robots' rollout in d_in, d_out, d_st, d_z, d_ter and their blocks in d_grad,
+//                   d_grad_st, laid out as a gradient call of that many robots over T / M steps; _shooting_linesearch: its n_alpha M B
+//                   candidates as a closed-loop tape call (K in d_fb), the chosen segments' blocks in d_grad, d_grad_st before they are
+//                   stitched into the new tape; the B-robot inputs and stitched outputs in buffers of its own   (plant_shooting.hip)
+//   The stage entries' own buffers (LQ pass, line search, iLQR loop, shooting) are a PlantStageWs each, below; their regions are laid
+//   out and copied by plant_staging.h
 //                   A tape's dz and status are NOT here: they belong to the tape (plant_adjoint.hip) and live as long as it does
 // The prologue the entry points share past their validation (plant_model_and_ground, plant_model.h; plant_rollout_check,
 // plant_rollout_call.h: no device needed) is stated here once: which device a call runs on (plant_current_device), and its workspace
-// with the stream open (plant_ws_open).
+// with the stream open (plant_ws_open), the device a tape or a handle lives on selected for the call (PlantDeviceScope), and the
+// staging copies on the workspace's stream (PlantStreamCopier).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -27,6 +36,7 @@
 
 #include "../../../include/cimpc.h"
 #include "plant_model.h"
+#include "plant_staging.h"
 
 namespace cimpc {
 
@@ -65,6 +75,14 @@ bool plant_grow(T** p, size_t* cap, size_t need) {
     return true;
 }
 
+// Frees *p where it is set, and clears it
+template <class T>
+bool plant_free(T** p) {
+    const bool ok = !*p || hipFree(*p) == hipSuccess;
+    *p = nullptr;
+    return ok;
+}
+
 // The calling thread's CURRENT device (the caller selects it, e.g. hipSetDevice(rank) / torch.cuda.set_device), which every plant
 // entry point runs on.  False: none that has a workspace, or not a gfx950.
 inline bool plant_current_device(int* dev) {
@@ -82,5 +100,57 @@ inline PlantWs* plant_ws_open(int dev) {
     }
     return &W;
 }
+
+// Grow-only device buffers of one stage entry, per device, next to the plant workspace whose stream and mutex the entry uses: doubles in,
+// doubles out, ints.  Each entry keeps an array of its own (g_*_ws in its file); an entry that stages everything in one buffer of doubles
+// leaves d_out alone.
+struct PlantStageWs {
+    double *d_in = nullptr, *d_out = nullptr;
+    int* d_int = nullptr;
+    size_t cap_in = 0, cap_out = 0, cap_int = 0;
+    bool grow(size_t in, size_t out, size_t ints) { return plant_grow(&d_in, &cap_in, in) && plant_grow(&d_out, &cap_out, out) && plant_grow(&d_int, &cap_int, ints); }
+};
+
+// g_plant_mu held and device `dev` selected, from the constructor until the object goes; rc(): CIMPC_OK, or why `dev` could not be
+// selected (nothing to undo then).  leave(ok) selects the caller's device again and folds a failure to do so into ok; the mutex stays
+// held, so an entry whose new tape must not outlive a failed restore can still release it.
+class PlantDeviceScope {
+public:
+    explicit PlantDeviceScope(int dev) : dev_(dev) {
+        if (hipGetDevice(&cur_) != hipSuccess) rc_ = CIMPC_ERR_NO_DEVICE;
+        else if (cur_ != dev_ && hipSetDevice(dev_) != hipSuccess) rc_ = CIMPC_ERR_HIP;
+        entered_ = rc_ == CIMPC_OK;
+    }
+    ~PlantDeviceScope() { (void)leave(true); }
+    int rc() const { return rc_; }
+    bool leave(bool ok) {
+        if (entered_ && cur_ != dev_) ok = (hipSetDevice(cur_) == hipSuccess) && ok;
+        entered_ = false;
+        return ok;
+    }
+
+private:
+    std::lock_guard<std::mutex> lock_{g_plant_mu};
+    int dev_, cur_ = -1, rc_ = CIMPC_OK;
+    bool entered_ = false;
+};
+
+// `body` on the device of a handle (cimpc_plant_mpc, cimpc_plant_sampler: `device`, `failed`) under the plant mutex; a HIP error latches
+// the handle.
+template <class Handle, class Body>
+int plant_handle_on_device(Handle* h, Body&& body) {
+    PlantDeviceScope scope(h->device);
+    if (scope.rc() != CIMPC_OK) return scope.rc();
+    const bool ok = scope.leave(body());
+    if (!ok) h->failed = true;
+    return ok ? CIMPC_OK : CIMPC_ERR_HIP;
+}
+
+// plant_staging.h's copier on a stream: PlantStreamCopier copy{{st}, ok};
+struct PlantStreamCopy {
+    hipStream_t st;
+    bool operator()(void* d, const void* s, size_t bytes, bool up) const { return hipMemcpyAsync(d, s, bytes, up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, st) == hipSuccess; }
+};
+using PlantStreamCopier = PlantCopier<PlantStreamCopy>;
 
 }  // namespace cimpc

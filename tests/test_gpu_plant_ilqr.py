@@ -20,6 +20,7 @@ import plant_boxqp_cases as pbc
 import plant_gradient_cases as pgc
 import plant_ilqr_cases as pic
 import plant_linesearch_cases as plc
+import plant_staging_cases as pst
 
 pytestmark = pytest.mark.gpu
 
@@ -180,3 +181,20 @@ def test_the_callers_tape_is_untouched_and_a_second_loop_gives_the_first_ones_bi
     whole.tape.close()
     for name in ("u", "q", "J", "alpha", "rho", "accepted"):
         _same(getattr(whole, name), getattr(first, name), f"ilqr(device_loop=True) against ilqr_from_tape: {name}")
+
+
+# ---- the optional staged arrays ----------------------------------------------------------------------------------------------------------------
+def test_shared_absent_and_per_robot_arrays_give_the_same_bits():
+    """The entry's optional staged arrays (csrc/plant_staging.h) at B = 2, T = 4, two step lengths, two iterations: mu, w and the limits shared
+    against the same values per robot, and no limits against infinite ones, every returned array bit for bit (tests/plant_staging_cases.py)."""
+    from contactimplicitmpc.jl_amd import plant
+    args, _, (Q, R, Qf, x_goal, u_goal) = pst.hopper()
+    cost = plant.TrackingCost(Q, R, Qf, x_goal=x_goal, u_goal=u_goal)
+
+    def run(mu, **kw):
+        res = plant.ilqr(*args, mu, cost, device_loop=True, **pst.LOOP, **kw)
+        out = pst.arrays(res)
+        res.tape.close()
+        return out
+
+    print("cimpc_plant_ilqr:", pst.loop_pairs(run), "arrays compared")

@@ -22,6 +22,7 @@ import pytest
 import plant_gradient_cases as pgc
 import plant_linesearch_cases as plc
 import plant_riccati_cases as prc
+import plant_staging_cases as pst
 
 pytestmark = pytest.mark.gpu
 ALPHAS = (1.0, 0.3, 0.0)
@@ -297,3 +298,21 @@ def test_ilqr_through_contact_on_the_hoppers():
     ok, q, ua, *_ = plant.rollout(c["model"], c["q1"], c["v1"], res.u, c["h"], c["mu"])
     _same(q, res.q, "the open-loop rollout of the returned controls")
     _same(cost.evaluate(res.q, res.u)[0], res.J[-1], "the returned cost")
+
+
+# ---- the optional staged arrays ----------------------------------------------------------------------------------------------------------------
+def test_shared_absent_and_per_robot_arrays_give_the_same_bits():
+    """`plant.ilqr`'s host loop: cimpc_plant_tape_linesearch_box and cimpc_plant_tape_lqr_box, iteration after iteration."""
+    # the entry's optional staged arrays (csrc/plant_staging.h) at B = 2, T = 4, two step lengths, two iterations: mu, w and the limits shared
+    # against the same values per robot, and no limits against infinite ones, every returned array bit for bit (tests/plant_staging_cases.py).
+    from contactimplicitmpc.jl_amd import plant
+    args, _, (Q, R, Qf, x_goal, u_goal) = pst.hopper()
+    cost = plant.TrackingCost(Q, R, Qf, x_goal=x_goal, u_goal=u_goal)
+
+    def run(mu, **kw):
+        res = plant.ilqr(*args, mu, cost, device_loop=False, **pst.LOOP, **kw)
+        out = pst.arrays(res)
+        res.tape.close()
+        return out
+
+    print("cimpc_plant_tape_linesearch_box, cimpc_plant_tape_lqr_box:", pst.loop_pairs(run), "arrays compared")

@@ -20,6 +20,7 @@ import plant_boxqp_cases as pbc
 import plant_gradient_cases as pgc
 import plant_ilqr_cases as pic
 import plant_mpc_cases as pmc
+import plant_staging_cases as pst
 
 pytestmark = pytest.mark.gpu
 
@@ -267,3 +268,25 @@ def test_the_policy_controls_better_than_replaying_its_first_plan():
     J_mpc, J_open = pmc.executed_cost(ref, q_mpc, u_mpc), pmc.executed_cost(ref, q_open, u_open)
     print(f"executed cost under MPC {J_mpc.tolist()}, under open-loop replay of the step-0 plan {J_open.tolist()}")
     assert (J_mpc < J_open).all(), f"MPC {J_mpc.tolist()} against open loop {J_open.tolist()}"
+
+
+# ---- the optional staged arrays ----------------------------------------------------------------------------------------------------------------
+def test_shared_absent_and_per_robot_arrays_give_the_same_bits():
+    """Two control steps of a policy whose mu and limits are shared against the same values per robot, and without limits against infinite
+    ones (csrc/plant_staging.h; tests/plant_staging_cases.py): the controls, the diagnostics and the plan bit for bit, at B = 2, H = 4."""
+    from contactimplicitmpc.jl_amd import plant
+    (model, q1, v1, u, h), _, _ = pst.hopper()
+    ref = pmc.hopper_reference(plant, L=6)
+
+    def run(mu, u_lo=None, u_hi=None):
+        lim = {} if u_lo is None else dict(u_lo=u_lo, u_hi=u_hi)
+        u0 = u if u_lo is None else np.clip(u, u_lo, u_hi)      # a plan inside its limits
+        out = {}
+        with plant.ILQRPolicy(model, pst.B, pst.T, h, mu, ref, u0, n_iter=pst.ITERS, alphas=pst.ALPHAS, rho0=1e-6, tol=0.0, **lim) as pol:
+            for s in range(2):
+                out[f"step {s}: u"] = pol.control(q1, v1)
+                out.update(pst.arrays(pol.last, f"step {s}: "))
+            out.update(zip(("plan u", "plan q", "plan gamma", "plan b", "plan status", "plan iters"), pol.plan()))
+        return out
+
+    print("cimpc_plant_mpc_create, _control, _plan:", pst.loop_pairs(run, with_w=False), "arrays compared")

@@ -31,6 +31,7 @@ import plant_gradient_cases as pgc
 import plant_riccati_cases as prc
 import plant_shooting_cases as psc
 import plant_shooting_ref as psr
+import plant_staging_cases as pst
 
 pytestmark = pytest.mark.gpu
 
@@ -503,3 +504,22 @@ def test_contact_from_the_goal_trajectory_closes_the_gaps(M):
         prev = res.phi[i]
     assert (res.D[-1] <= CONTACT_SHOOTING["defect_tol"]).all(), f"gaps left open: D {res.D[-1]}"
     assert ok and (gap <= REPLAY_BOUND).all(), gap
+
+
+# ---- the optional staged arrays ----------------------------------------------------------------------------------------------------------------
+def test_shared_absent_and_per_robot_arrays_give_the_same_bits():
+    """`plant.ilqr_shooting` with two segments: cimpc_plant_rollout_segments, cimpc_plant_tape_lqr_shooting, cimpc_plant_shooting_forward and
+    cimpc_plant_shooting_linesearch, iteration after iteration."""
+    # the entry's optional staged arrays (csrc/plant_staging.h) at B = 2, T = 4, two step lengths, two iterations: mu, w and the limits shared
+    # against the same values per robot, and no limits against infinite ones, every returned array bit for bit (tests/plant_staging_cases.py).
+    from contactimplicitmpc.jl_amd import plant
+    args, _, (Q, R, Qf, x_goal, u_goal) = pst.hopper()
+    cost = plant.TrackingCost(Q, R, Qf, x_goal=x_goal, u_goal=u_goal)
+
+    def run(mu, **kw):
+        res = plant.ilqr_shooting(*args, mu, cost, segments=pst.SEGMENTS, defect_weight=10.0, defect_tol=1e-6, **pst.LOOP, **kw)
+        out = pst.arrays(res)
+        res.tape.close()
+        return out
+
+    print("the shooting entries:", pst.loop_pairs(run), "arrays compared")
